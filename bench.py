@@ -31,6 +31,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -217,6 +218,61 @@ def remove_shared_pages():
             pass
 
 
+def tree_writable(dirs) -> bool:
+    """True when this user may create or write every directory in dirs (a missing one is created in its nearest existing parent)."""
+    for d in dirs:
+        while not os.path.isdir(d):
+            d = os.path.dirname(d)
+        if not os.access(d, os.W_OK):
+            return False
+    return True
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_TEXT_WIDTH = 26              # a decoded string is at most one character per AR position
+
+
+def dump_outputs(dirpath: str, results, page_seeds) -> None:
+    """--dump-outputs: what the caller of the timed path received for the pages of the last step, as float32 .npy files in dirpath.
+
+      page_seed        [pages]          the synthetic page each row below belongs to (tuatara_amd/synth.py seed)
+      words_per_page   [pages]          result items per page; the arrays below hold the pages' items back to back
+      bbox             [words, 4]       each item's box (the engine's f32 bbox)
+      ids              [words, 26]      each item's token ids
+      text             [words, 26]      each item's decoded string as latin-1 byte codes, 0-padded
+
+    Over DUMP_MAX_BYTES in all, a fixed sample of the pages (seeded shuffle, kept in page order) is written instead."""
+    import numpy as np
+
+    bytes_per_word = (4 + 26 + DUMP_TEXT_WIDTH) * 4
+    order = np.random.default_rng(0).permutation(len(results))
+    keep, total = [], 5 * 128            # (the five .npy headers)
+    for i in order:
+        total += 2 * 4 + len(results[i]) * bytes_per_word
+        if total > DUMP_MAX_BYTES:
+            break
+        keep.append(int(i))
+    keep.sort()
+    sel = [results[i] for i in keep]
+    n = sum(len(r) for r in sel)
+    text = np.zeros((n, DUMP_TEXT_WIDTH), np.float32)
+    k = 0
+    for r in sel:
+        for t in r.texts:
+            b = t.encode("latin1")
+            assert len(b) <= DUMP_TEXT_WIDTH, t
+            text[k, :len(b)] = np.frombuffer(b, np.uint8)
+            k += 1
+    arrays = {"page_seed": np.array([page_seeds[i] for i in keep], np.float32),
+              "words_per_page": np.array([len(r) for r in sel], np.float32),
+              "bbox": np.concatenate([np.asarray(r.bbox, np.float32).reshape(-1, 4) for r in sel]) if sel else np.zeros((0, 4), np.float32),
+              "ids": np.concatenate([np.asarray(r.ids, np.float32).reshape(-1, 26) for r in sel]) if sel else np.zeros((0, 26), np.float32),
+              "text": text}
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def stub_rank(kind: str, rank: int, world: int, wd, args) -> None:
     """A rank body without a GPU (TUATARA_BENCH_STUB, tests/test_launch_cpu.py): ok = every rank reports, rank 0 prints the line;
     fail = rank 1 leaves with status 7; hang = rank 1 never returns (the launcher's deadline ends it); stage = rank 1 sits in a watched
@@ -262,8 +318,12 @@ def main():
     ap.add_argument("--deadline", type=float, default=1500.0, help="N > 1 started from this one command: seconds the ranks get before the launcher ends them (exit status 124)")
     ap.add_argument("--stage-deadline", type=float, default=300.0, help="seconds a rank may spend in one of its watched stages (engine / communicator set-up, first gather) before it "
                     "leaves with status 3 naming the stage")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step returned to its caller (rank 0's pages: "
+                    "boxes, token ids, strings) as DIR/<name>.npy in float32, at most 64 MB (bench.py: dump_outputs)")
     ap.add_argument("--cpu-baseline-child", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_child is not None:
         return cpu_baseline_child(args.cpu_baseline_child)
 
@@ -304,11 +364,14 @@ def main():
     from tuatara_amd import weights as W
     from tuatara_amd.engine import Comm, DeviceBuffer, Engine
 
-    os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
-    with open(os.path.join(ROOT, "build", ".bench_lock"), "w") as lk:      # one rank builds (a no-op when the library is current)
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        B.build_lib()
-        fcntl.flock(lk, fcntl.LOCK_UN)
+    # one rank builds (a no-op when the library is current).  A tree this user cannot write (built by another user) runs the library build()
+    # left in it, so the lock lives in the temp directory, not in the tree
+    if tree_writable([B.OBJDIR, B.LIBDIR]):
+        lock = os.path.join(tempfile.gettempdir(), f"tuatara_bench_build_{os.getuid()}_{zlib.crc32(ROOT.encode()):08x}.lock")
+        with open(lock, "w") as lk:
+            fcntl.flock(lk, fcntl.LOCK_EX)
+            B.build_lib()
+            fcntl.flock(lk, fcntl.LOCK_UN)
     wdir = os.path.join(tempfile.gettempdir(), f"tuatara_bench_weights_{os.getuid()}_{local_rank}")
     W.make_synthetic_weights(wdir, seed=0, structured=True)
 
@@ -351,12 +414,14 @@ def main():
         lat = []
         fence()
         t0 = time.perf_counter()
-        for _ in range(max(args.steps, 10)):
+        for _ in range(args.steps):
             t1 = time.perf_counter()
             res = call()
             lat.append((time.perf_counter() - t1) * 1e3)
         fence()
         dt = time.perf_counter() - t0
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, res, [0])
         if rank == 0:
             print(json.dumps({"metric": "p50 page latency (1024x768 page, crop batch sharded over the GPUs)", "value": float(np.median(lat)), "unit": "ms",
                               "n_gpus": world, "steps": len(lat), "warmup": max(2, args.warmup), "ms_per_step": dt / len(lat) * 1e3, "higher_is_better": False,
@@ -409,11 +474,16 @@ def main():
             run_passes(eng, args.warmup * R)
     eng.set_profiling(1)           # timed region: HIP events around the dominant kernels only (the CRAFT convolutions)
     fence()
+    first_timed = pass_no[0]
     t0 = time.perf_counter()
     kept = []
     run_passes(eng, args.steps * R, kept)
     fence()
     dt = time.perf_counter() - t0
+    assert len(kept) == args.steps * R, (len(kept), args.steps, R)
+    if rank == 0 and args.dump_outputs:        # the last step: its R passes, pass j on buffer j % NB
+        dump_outputs(args.dump_outputs, [pg for r in kept[-R:] for pg in r],
+                     [sd for j in range(first_timed + len(kept) - R, first_timed + len(kept)) for sd in seeds[j % NB]])
     prof = eng.get_profile()
     kinds = eng.get_profile_kinds()
     eng.set_profiling(0)

@@ -60,16 +60,11 @@ def test_an_external_launcher_is_left_alone():
     assert json.loads(p.stdout.strip().splitlines()[-1])["n_gpus"] == 2
 
 
-def test_run_ranks_needs_a_json_line():
+def test_run_ranks_needs_a_json_line(tmp_path):
     from tuatara_amd import launch
     import io
-    script = os.path.join(ROOT, "tests", "data", "_silent_rank.py")
-    os.makedirs(os.path.dirname(script), exist_ok=True)
-    with open(script, "w") as f:
-        f.write("print('no result here')\n")
-    try:
-        out, err = io.StringIO(), io.StringIO()
-        rc, js = launch.run_ranks(script, [], 2, deadline_s=20, out=out, err=err)
-        assert rc == 1 and js is None and out.getvalue() == ""
-    finally:
-        os.remove(script)
+    script = tmp_path / "_silent_rank.py"
+    script.write_text("print('no result here')\n")
+    out, err = io.StringIO(), io.StringIO()
+    rc, js = launch.run_ranks(str(script), [], 2, deadline_s=20, out=out, err=err)
+    assert rc == 1 and js is None and out.getvalue() == ""

@@ -49,13 +49,12 @@ def test_oracle_one_batch_equals_reference_fanout(oracle_models):
 
 
 def test_reference_binary_reproduces_the_fixture_when_the_reference_is_here(tmp_path):
-    """In the build container (/root/reference present) the recipe runs again: same strings, logits within thread-schedule / CPU-kernel noise of the
-    committed ones.  Skipped on machines without the reference (the GPU box)."""
+    """Where build() compiled the reference's fan-out (oracle/_ref/ref_infer), it runs again: same strings, logits within thread-schedule / CPU-kernel
+    noise of the committed ones.  Skipped where build() had no reference sources to compile."""
     import pytest
     from oracle import build_ref_infer as B
-    if not os.path.exists(B.REF):
-        pytest.skip("no /root/reference here")
-    assert B.build()
+    if not os.path.exists(B.BIN):
+        pytest.skip("oracle/_ref/ref_infer not built (build() makes it where the reference sources are)")
     arch = str(tmp_path / "parseq_torchscript.bin")
     B.export_parseq_archive(arch)
     crops, ref, texts = _golden()

@@ -35,11 +35,10 @@ def test_engine_host_decoder_matches_the_reference_tokenizer():
 
 
 def test_committed_vectors_are_what_the_reference_produces_here():
-    """Where the reference is on this machine (the build container), rebuild its tokenizer and regenerate the cases."""
+    """The reference's tokenizer as build() compiled it (oracle/_ref/ref_tokenizer) regenerates the table and decodes a new case like the oracle."""
     from oracle import build_ref_tokenizer as B
-    if not os.path.exists(B.REF):
-        pytest.skip("no /root/reference on this machine")
-    assert B.build()
+    if not os.path.exists(B.BIN):
+        pytest.skip("oracle/_ref/ref_tokenizer not built (build() makes it where the reference sources are)")
     rng = np.random.default_rng(1)
     eye = np.full((98, 1, 98), -20.0, np.float32)
     for i in range(98):
