@@ -4,7 +4,7 @@
 result, and save an annotated copy (the reference's three panels: boxes on the page, text at the boxes, running text).  Drawing uses PIL only
 (the reference draws with cv2 and opens a window; neither is needed for the results).
 
-  python bindings/run_ocr.py [image] [weights_dir] [outputs_dir]
+  python bindings/run_ocr.py [--rectify] [image] [weights_dir] [outputs_dir]   (--rectify: deskewed crops, words drawn as their quads)
 """
 from __future__ import annotations
 
@@ -32,7 +32,10 @@ def annotate(image: np.ndarray, result) -> Image.Image:
     for item in sorted(result, key=lambda it: (it["bbox"][1], it["bbox"][0])):
         x1, y1, x2, y2 = (int(v) for v in item["bbox"])
         text = item["text"]
-        db.rectangle([x1, y1, x2, y2], outline=(0, 255, 0), width=2)
+        if "quad" in item:       # rectified crops (pytuatara.image_to_data(..., rectify=True)): the word's own quadrilateral
+            db.polygon([tuple(p) for p in item["quad"]], outline=(0, 255, 0), width=2)
+        else:
+            db.rectangle([x1, y1, x2, y2], outline=(0, 255, 0), width=2)
         dp.text((x1, y1), text, fill=(255, 0, 0))
         l, t, r, btm = dr.textbbox((0, 0), text or " ")
         tw, th = r - l, btm - t
@@ -49,13 +52,15 @@ def annotate(image: np.ndarray, result) -> Image.Image:
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
+    rectify = "--rectify" in argv
+    argv = [a for a in argv if a != "--rectify"]
     image_path = argv[0] if len(argv) > 0 else os.path.join(HERE, "..", "tests", "data", "funsd_0001129658.png")
     weights_dir = argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "weights")
     outputs_dir = argv[2] if len(argv) > 2 else os.path.join(HERE, "..", "outputs")
     import pytuatara
 
     numpy_image = np.array(Image.open(image_path).convert("RGB"))
-    result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir)
+    result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir, rectify=True) if rectify else pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir)
     print(result)
     os.makedirs(outputs_dir, exist_ok=True)
     stem = os.path.splitext(os.path.basename(image_path))[0]

@@ -2,6 +2,8 @@
 //   ocr_cli <image.png> <weights_dir> <outputs_dir>
 // reads the image as BGR (what cv::imread(path, cv::IMREAD_COLOR) hands the reference), calls image_to_data and,
 // unlike the reference (which discards the result), prints one "x1 y1 x2 y2<TAB>text" line per item.
+//   ocr_cli --rectify <image.png> <weights_dir> <outputs_dir>   reads tilted words on deskewed crops (DESIGN.md "Rectified crops") and
+// prints "x1 y1 x2 y2<TAB>tl.x tl.y tr.x tr.y br.x br.y bl.x bl.y<TAB>text" per item.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <cstdio>
 #include <iostream>
@@ -20,8 +22,18 @@ int main(int argc, const char** argv) {
       printf("%d %d\n", img.rows, img.cols);
       return 0;
     }
+    if (argc == 5 && std::string(argv[1]) == "--rectify") {
+      pngdec::Image img = pngdec::read(argv[2]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[3], argv[4], true);
+      for (const OutputItemEx& it : items) {
+        const std::vector<float>& q = it.quad;
+        printf("%g %g %g %g\t%g %g %g %g %g %g %g %g\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7],
+               it.text.c_str());
+      }
+      return 0;
+    }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--rectify] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

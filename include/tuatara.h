@@ -30,6 +30,20 @@ std::vector<OutputItem> image_to_data(const uint8_t* image, int rows, int cols, 
 struct ImageView { const uint8_t* data; int rows, cols; std::ptrdiff_t row_stride; };   // row_stride 0 = tightly packed
 std::vector<std::vector<OutputItem>> images_to_data(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir);
 
+// Rectified crops (opt-in; DESIGN.md "Rectified crops"): the same items as image_to_data - order, text boxes, failures - each with the
+// word's quadrilateral; with rectify = true a tilted word is deskewed (up to 45 degrees) before the recogniser reads it, so `text` may
+// differ from image_to_data's; with rectify = false the crops are image_to_data's.  OutputItem keeps the reference's layout.
+// TUATARA_CROP_MODE=1 in the environment (beside TUATARA_STRICT_CROPS) makes image_to_data / images_to_data use rectified crops too.
+struct OutputItemEx {
+  std::string text;
+  std::vector<float> bbox;  // x1, y1, x2, y2
+  std::vector<float> quad;  // tl.x, tl.y, tr.x, tr.y, br.x, br.y, bl.x, bl.y in image pixels; tl -> tr is the baseline
+};
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify);
+
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)
 #include <opencv2/core.hpp>

@@ -27,6 +27,12 @@ typedef struct ttr_result ttr_result;
    (tuatara.cpp:363-376, :443-446, :307); this mode meets its outputs at the level of fp32 rounding noise and is the default.
    TTR_PREC_BF16: operands rounded to bf16 (fastest; logits differ by up to ~1e-1).  TTR_PREC_F32: fp32 MFMA throughout. */
 enum { TTR_PREC_BF16 = 0, TTR_PREC_F32 = 1, TTR_PREC_F16X4 = 2 };
+/* ttr_config.crop_mode.  TTR_CROP_BOUNDING: the recogniser sees the axis-aligned boundingRect of each word's rotated rectangle, resized to
+   32 x 128 - the reference's crop (tuatara.cpp:408-418, :440), bit for bit; the default.  TTR_CROP_RECTIFIED: a word whose rectangle is
+   tilted is sampled on its own quadrilateral, deskewed by up to 45 degrees (DESIGN.md "Rectified crops"); axis-aligned words keep the
+   reference's crop.  The items, their order and their bboxes are the same in both modes; only text / ids may change.  Text rotated by more
+   than 45 degrees, or upside down, is not recovered (geometry alone cannot tell 90 from 270 degrees, or 0 from 180). */
+enum { TTR_CROP_BOUNDING = 0, TTR_CROP_RECTIFIED = 1 };
 enum { TTR_ORDER_AS_IS = 0 };  /* channel order: the engine reproduces "swap, detect; swap back, recognise"
                                   (tuatara.cpp:349, :441) relative to whatever the caller passes */
 
@@ -43,6 +49,7 @@ typedef struct ttr_config {
   int strict_crops;      /* 0: clamp crops to the image; 1: fail like the reference's cv::Exception at :416 */
   int max_components;    /* capacity for CCL candidates per page (default 4096) */
   int verbose;           /* 1: the reference's progress lines on stdout (tuatara.cpp:328-329, :342, :386, :421, :434, :488, :509); TUATARA_VERBOSE=1 does the same */
+  int crop_mode;         /* TTR_CROP_BOUNDING (default) or TTR_CROP_RECTIFIED (appended last: the fields above keep their offsets) */
 } ttr_config;
 
 void ttr_config_default(ttr_config* cfg);
@@ -85,6 +92,11 @@ int ttr_result_count(const ttr_result* r);
 const char* ttr_result_text(const ttr_result* r, int i);
 const float* ttr_result_bbox(const ttr_result* r, int i);   /* {x1,y1,x2,y2}, tuatara.cpp:272 */
 const int32_t* ttr_result_ids(const ttr_result* r, int i);  /* 26 argmax token ids of crop i */
+/* the word's quadrilateral {tl.x, tl.y, tr.x, tr.y, br.x, br.y, bl.x, bl.y} in image pixels, unrounded: tl -> tr is the baseline (the side
+ * of the rotated rectangle nearest horizontal, skew in [-45, 45] degrees, pointing right), tl -> bl points down.  Filled in every crop
+ * mode; ttr_result_quads is the bulk view [count][8] (NULL when the result is empty). */
+const float* ttr_result_quad(const ttr_result* r, int i);
+const float* ttr_result_quads(const ttr_result* r);
 void ttr_result_free(ttr_result* r);
 /* bulk views for bindings (valid until ttr_result_free): all boxes [count][4], all ids [count][26]; the texts of all
  * items, each followed by '\n' (no token maps to '\n'), copied into buf when cap suffices; returns the bytes needed. */
@@ -155,6 +167,11 @@ int ttr_resize_canvas(ttr_engine* e, const uint8_t* hwc_u8, int h, int w, int ro
  * receives the adjusted rects {cx,cy,w,h,angle} in image pixels. */
 int ttr_pack_crops(ttr_engine* e, const uint8_t* hwc_u8, int h, int w, int row_stride, const float* rects5, int n,
                    float ratio, uint8_t* crops, float* boxes_out);
+/* The TTR_CROP_RECTIFIED twin of ttr_pack_crops, whatever the engine's crop_mode: the same rects and clamp, each crop made by the
+ * rectified rule (kind 0 = ttr_pack_crops's crop for an axis-aligned rect, kind 1 = the deskewed quadrilateral); quads_out (optional)
+ * receives the quads [n][8] as ttr_result_quad gives them.  A rect whose clamped boundingRect is empty yields a zero crop. */
+int ttr_pack_crops_rectified(ttr_engine* e, const uint8_t* hwc_u8, int h, int w, int row_stride, const float* rects5, int n,
+                             float ratio, uint8_t* crops, float* quads_out);
 /* PARSeq forward (tuatara.cpp:443-446 + :307): crops u8 [n][32][128][3] -> logits f32 [n][26][95];
  * ar_logits (optional) receives the autoregressive pass's logits - per crop defined up to and including its EOS step (upstream leaves
  * its loop when every crop has emitted EOS; behind a crop's own EOS the bf16 engine skips it, and zero-fills the steps behind the batch's

@@ -88,6 +88,9 @@ int ttr_dbg_component_rect(int area, int x0, int y0, int x1, int y1, const int32
 /* adjust_result_coordinates + boundingRect + format (tuatara.cpp:236-274, :416): rect5 in heat-map
  * pixels -> adjusted rect5, crop xywh (unclamped) and the tesseract bbox. */
 int ttr_dbg_box_geometry(const float* rect5, float ratio, float* adjusted5, int32_t* xywh, float* bbox4);
+/* the rectified-crop rule on one rect {cx,cy,w,h,angle} in image pixels (geometry.h: deskew_quad): quad8 {tl, tr, br, bl}, coef6
+ * {X0, Ax, Bx, Y0, Ay, By} in double, fixed6 the same in int64 units of 2^-16 px.  Returns the crop kind (0 or 1). */
+int ttr_dbg_deskew(const float* rect5, float* quad8, double* coef6, int64_t* fixed6);
 
 
 #ifdef __cplusplus

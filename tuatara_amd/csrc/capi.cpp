@@ -15,12 +15,23 @@ static void run_locked(ttr_engine* e, const uint8_t* d_pages, int n, int h, int 
   for (int i = 0; i < n; ++i) { out[i] = new ttr_result(); out[i]->r = std::move(res[i]); }
 }
 
+// the stage entry points' crop rectangle of one heat-map rect: adjust_result_coordinates + boundingRect, clamped to the image (tuatara.cpp:406-418)
+static RRect stage_crop_rect(const float* r5, float ratio, int h, int w, int* rect5) {
+  const RRect r{r5[0], r5[1], r5[2], r5[3], r5[4]};
+  const RRect b = adjust_coordinates(r, 1.f / ratio, 1.f / ratio);
+  int xywh[4];
+  bounding_rect(b, xywh);
+  rect5[0] = std::max(xywh[0], 0); rect5[1] = std::max(xywh[1], 0);
+  rect5[2] = std::min(xywh[0] + xywh[2], w); rect5[3] = std::min(xywh[1] + xywh[3], h);
+  return b;
+}
+
 extern "C" {
 
 void ttr_config_default(ttr_config* c) {
   c->precision = TTR_PREC_F16X4; c->device = 0; c->canvas_size = 1024; c->mag_ratio = 1.0f;
   c->text_threshold = 0.7f; c->link_threshold = 0.4f; c->low_text = 0.4f; c->min_area = 10;
-  c->strict_crops = 0; c->max_components = 4096; c->verbose = 0;
+  c->strict_crops = 0; c->max_components = 4096; c->verbose = 0; c->crop_mode = TTR_CROP_BOUNDING;
 }
 
 const char* ttr_last_error(void) { return g_last_error.c_str(); }
@@ -119,6 +130,10 @@ const char* ttr_result_text(const ttr_result* r, int i) { return r->r.text[i].c_
 const float* ttr_result_bbox(const ttr_result* r, int i) { return &r->r.bbox[4 * (size_t)i]; }
 
 const int32_t* ttr_result_ids(const ttr_result* r, int i) { return &r->r.ids[26 * (size_t)i]; }
+
+const float* ttr_result_quad(const ttr_result* r, int i) { return &r->r.quad[8 * (size_t)i]; }
+
+const float* ttr_result_quads(const ttr_result* r) { return r && !r->r.quad.empty() ? r->r.quad.data() : nullptr; }
 
 void ttr_result_free(ttr_result* r) { delete r; }
 
@@ -222,13 +237,8 @@ int ttr_pack_crops(ttr_engine* e, const uint8_t* img, int h, int w, int row_stri
   if (n <= 0) return 0;
   std::vector<int> rects((size_t)n * 5, 0);
   for (int i = 0; i < n; ++i) {
-    RRect r{rects5[5 * i], rects5[5 * i + 1], rects5[5 * i + 2], rects5[5 * i + 3], rects5[5 * i + 4]};
-    RRect b = adjust_coordinates(r, 1.f / ratio, 1.f / ratio);
+    RRect b = stage_crop_rect(rects5 + 5 * i, ratio, h, w, &rects[5 * i]);
     if (boxes_out) { boxes_out[5 * i] = b.cx; boxes_out[5 * i + 1] = b.cy; boxes_out[5 * i + 2] = b.w; boxes_out[5 * i + 3] = b.h; boxes_out[5 * i + 4] = b.angle; }
-    int xywh[4];
-    bounding_rect(b, xywh);
-    rects[5 * i] = std::max(xywh[0], 0); rects[5 * i + 1] = std::max(xywh[1], 0);
-    rects[5 * i + 2] = std::min(xywh[0] + xywh[2], w); rects[5 * i + 3] = std::min(xywh[1] + xywh[3], h);
   }
   E.staging_img.ensure((size_t)h * w * 3);
   E.rects_dev.ensure(rects.size() * 4);
@@ -236,6 +246,37 @@ int ttr_pack_crops(ttr_engine* e, const uint8_t* img, int h, int w, int row_stri
   TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
   TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
   launch_pack_crops(E.staging_img.as<uint8_t>(), 0, w * 3, E.rects_dev.as<int>(), E.crops.as<uint8_t>(), n, E.stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_pack_crops_rectified(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const float* rects5, int n, float ratio, uint8_t* crops_out,
+                             float* quads_out) {
+  TTR_GUARD_BEGIN
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_pack_crops_rectified");
+  if (n <= 0) return 0;
+  std::vector<int> rects((size_t)n * 5, 0);
+  std::vector<int64_t> coef((size_t)n * 8, 0);
+  for (int i = 0; i < n; ++i) {
+    const RRect b = stage_crop_rect(rects5 + 5 * i, ratio, h, w, &rects[5 * i]);
+    Pt2f q[4]; double cf[6]; int64_t fx[6];
+    coef[8 * i] = deskew_quad(b, q, cf);
+    deskew_fixed(cf, fx);
+    for (int k = 0; k < 6; ++k) coef[8 * i + 1 + k] = fx[k];
+    if (quads_out) for (int k = 0; k < 4; ++k) { quads_out[8 * i + 2 * k] = q[k].x; quads_out[8 * i + 2 * k + 1] = q[k].y; }
+  }
+  E.staging_img.ensure((size_t)h * w * 3);
+  E.rects_dev.ensure(rects.size() * 4);
+  E.coef_dev.ensure(coef.size() * 8);
+  E.crops.ensure((size_t)n * 32 * 128 * 3);
+  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(E.coef_dev.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice, E.stream));
+  launch_pack_crops_rect(E.staging_img.as<uint8_t>(), 0, w * 3, h, w, E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
   TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
   TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
   return 0;

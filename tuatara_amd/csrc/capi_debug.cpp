@@ -430,4 +430,15 @@ int ttr_dbg_box_geometry(const float* r5, float ratio, float* adj5, int32_t* xyw
   TTR_GUARD_END(-1)
 }
 
+int ttr_dbg_deskew(const float* r5, float* quad8, double* coef6, int64_t* fixed6) {
+  TTR_GUARD_BEGIN
+  const RRect r{r5[0], r5[1], r5[2], r5[3], r5[4]};
+  Pt2f q[4];
+  const int kind = deskew_quad(r, q, coef6);
+  deskew_fixed(coef6, fixed6);
+  for (int k = 0; k < 4; ++k) { quad8[2 * k] = q[k].x; quad8[2 * k + 1] = q[k].y; }
+  return kind;
+  TTR_GUARD_END(-1)
+}
+
 }  // extern "C"

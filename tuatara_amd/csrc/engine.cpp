@@ -396,6 +396,7 @@ void Engine::load_parseq(const std::string& dir) {
 
 Engine::Engine(const std::string& dir, const ttr_config& c) : cfg(c) {
   { const char* v = getenv("TUATARA_VERBOSE"); verbose = cfg.verbose != 0 || (v && *v && std::string(v) != "0"); }
+  if (cfg.crop_mode != TTR_CROP_BOUNDING && cfg.crop_mode != TTR_CROP_RECTIFIED) throw std::runtime_error("crop_mode must be TTR_CROP_BOUNDING (0) or TTR_CROP_RECTIFIED (1)");
   prec = cfg.precision == TTR_PREC_F32 ? kF32 : cfg.precision == TTR_PREC_F16X4 ? kSplit : kBF16;
   es = prec == kBF16 ? 2 : 4;
   int ndev = 0;

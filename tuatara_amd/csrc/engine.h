@@ -259,6 +259,7 @@ struct Result {
   std::vector<std::string> text;
   std::vector<float> bbox;   // 4 per item
   std::vector<int32_t> ids;  // 26 per item
+  std::vector<float> quad;   // 8 per item: the word's corners tl, tr, br, bl in image pixels (geometry.h: deskew_quad), every crop mode
 };
 
 struct CclBatch {   // device workspaces of the CCL stage for a batch of equally sized pages
@@ -394,9 +395,9 @@ struct Engine {
   bool lane_go_pending = false;                   // craft_forward_split records lane_go behind slice3.20 when set
   int craft_ws_npl = 0;                           // planes per value the split CRAFT workspaces were laid out for
   DevBuf pq_ws[24];
-  DevBuf canvas, heat, staging_img, crops, rects_dev, logits, ar_logits, ids_dev, tokens;
+  DevBuf canvas, heat, staging_img, crops, rects_dev, coef_dev, logits, ar_logits, ids_dev, tokens;
   CclBatch ccl;
-  PinnedBuf h_counters, h_cand, h_rows, h_rects_f, h_rects[2], h_ids[2];   // pinned staging of the small host <-> device transfers
+  PinnedBuf h_counters, h_cand, h_rows, h_rects_f, h_rects[2], h_coef[2], h_ids[2];   // (h_coef: crop_mode = TTR_CROP_RECTIFIED only)   // pinned staging of the small host <-> device transfers
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   float stage_ms[4] = {0, 0, 0, 0};
   float host_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // host wall-clock splits of the last run_pages (ttr_last_host_us)
@@ -601,6 +602,7 @@ struct Engine {
     CanvasGeom g{}; int H = 0, W = 0, H2 = 0, W2 = 0; size_t page_bytes = 0;
     std::vector<std::vector<RRect>> boxes;
     std::vector<int> rects, page_of;
+    std::vector<int64_t> coef;         // crop_mode = TTR_CROP_RECTIFIED: {kind, X0, Ax, Bx, Y0, Ay, By, 0} per crop, beside rects
     int N = 0, slot = 0, group = 16;
     int det_groups = -1;               // CRAFT groups enqueued for it (group_ev[det_groups]: behind the copy of its detector range word)
     bool live = false, enqueued = false;
@@ -618,6 +620,9 @@ struct Engine {
   void detect_collect_local(PageBatch& B);
 
   void recog_enqueue(PageBatch& B);
+  // the crop packer of a batch whose rects / coef are known: copies them through the pinned staging of slot sl and enqueues
+  // pack_crops_kernel (crop_mode 0) or pack_crops_rect_kernel (crop_mode 1) into `crops`
+  void pack_batch_crops(const PageBatch& B, int sl);
 
   void finish(PageBatch& B, std::vector<Result>& results);
 

@@ -6,6 +6,12 @@
 
 namespace ttr {
 
+static void push_quad(const RRect& b, std::vector<float>& quad) {   // Result::quad: the word's corners tl, tr, br, bl
+  Pt2f q[4]; double cf[6];
+  deskew_quad(b, q, cf);
+  for (int i = 0; i < 4; ++i) { quad.push_back(q[i].x); quad.push_back(q[i].y); }
+}
+
 void Engine::allgather_host(const void* mine, size_t bytes, void* all) {
   Comm& c = *comm;
   const size_t b = std::max<size_t>(bytes, 1);
@@ -191,7 +197,7 @@ void Engine::detect_collect_local(PageBatch& B) {
   const float ratio_w = 1.f / B.g.ratio, ratio_h = 1.f / B.g.ratio;   // tuatara.cpp:360-361
   std::vector<std::vector<RRect>> dets(n);
   B.boxes.assign(n, std::vector<RRect>());
-  B.rects.clear(); B.page_of.clear();        // x0,y0,x1,y1,page per crop; page index per crop
+  B.rects.clear(); B.page_of.clear(); B.coef.clear();   // x0,y0,x1,y1,page per crop; page index per crop; rectified crops' coefficients
   host_us[1] = host_us[2] = host_us[3] = 0.f;
   for (int gi = 0; gi < groups; ++gi) ccl_collect(gi * GP, std::min(GP, n - gi * GP), gi, B.H2, B.W2, dets);
   // the detector's range word of THIS batch, before any of its boxes is used: a saturated heat map fails this batch and no other
@@ -223,9 +229,32 @@ void Engine::detect_collect_local(PageBatch& B) {
       B.boxes[i].push_back(b);
       B.rects.insert(B.rects.end(), {x0, y0, x1, y1, i});
       B.page_of.push_back(i);
+      if (cfg.crop_mode == TTR_CROP_RECTIFIED) {                    // DESIGN.md "Rectified crops": same items, other pixels
+        Pt2f q[4]; double cf[6]; int64_t fx[6];
+        const int kind = deskew_quad(b, q, cf);
+        deskew_fixed(cf, fx);
+        B.coef.insert(B.coef.end(), {(int64_t)kind, fx[0], fx[1], fx[2], fx[3], fx[4], fx[5], 0});
+      }
     }
   }
   B.N = (int)B.page_of.size();
+}
+
+void Engine::pack_batch_crops(const PageBatch& B, int sl) {
+  rects_dev.ensure(B.rects.size() * 4);
+  h_rects[sl].ensure(B.rects.size() * 4);
+  memcpy(h_rects[sl].p, B.rects.data(), B.rects.size() * 4);
+  TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[sl].p, B.rects.size() * 4, hipMemcpyHostToDevice, stream));
+  if (cfg.crop_mode != TTR_CROP_RECTIFIED) {
+    launch_pack_crops(B.d_pages, B.page_bytes, B.w * 3, rects_dev.as<int>(), crops.as<uint8_t>(), B.N, stream);
+    return;
+  }
+  if (B.coef.size() != (size_t)B.N * 8) throw std::runtime_error("rectified crops: coefficient count does not match the crop count");
+  coef_dev.ensure(B.coef.size() * 8);
+  h_coef[sl].ensure(B.coef.size() * 8);
+  memcpy(h_coef[sl].p, B.coef.data(), B.coef.size() * 8);
+  TTR_HIP_CHECK(hipMemcpyAsync(coef_dev.p, h_coef[sl].p, B.coef.size() * 8, hipMemcpyHostToDevice, stream));
+  launch_pack_crops_rect(B.d_pages, B.page_bytes, B.w * 3, B.h, B.w, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), B.N, stream);
 }
 
 void Engine::recog_enqueue(PageBatch& B) {
@@ -234,14 +263,10 @@ void Engine::recog_enqueue(PageBatch& B) {
   h_ids[sl].ensure((size_t)N * 26 * 4 + 4);
   TTR_HIP_CHECK(hipEventRecord(evr[sl][0], stream));
   if (N > 0) {
-    rects_dev.ensure(B.rects.size() * 4);
-    h_rects[sl].ensure(B.rects.size() * 4);
-    memcpy(h_rects[sl].p, B.rects.data(), B.rects.size() * 4);
     crops.ensure((size_t)N * 32 * 128 * 3);
     logits.ensure((size_t)N * 26 * 95 * 4);
     ids_dev.ensure((size_t)std::max(N, B.cap) * 26 * 4);
-    TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[sl].p, B.rects.size() * 4, hipMemcpyHostToDevice, stream));
-    launch_pack_crops(B.d_pages, B.page_bytes, B.w * 3, rects_dev.as<int>(), crops.as<uint8_t>(), N, stream);
+    pack_batch_crops(B, sl);
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, ids_dev.as<int>());
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
@@ -291,13 +316,14 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   auto decode_page = [&](int pg) {
     Result& r = results[pg];
     const int c0 = first[pg], cnt = first[pg + 1] - c0;
-    r.text.reserve(cnt); r.bbox.reserve((size_t)cnt * 4);
+    r.text.reserve(cnt); r.bbox.reserve((size_t)cnt * 4); r.quad.reserve((size_t)cnt * 8);
     r.ids.assign(&ids[(size_t)c0 * 26], &ids[(size_t)(c0 + cnt) * 26]);
     for (int k = 0; k < cnt; ++k) {
       r.text.push_back(tok.decode(&ids[(size_t)(c0 + k) * 26], 26));   // :486-505
       float bb[4];
       tesseract_bbox(B.boxes[pg][k], bb);                               // :511
       r.bbox.insert(r.bbox.end(), bb, bb + 4);
+      push_quad(B.boxes[pg][k], r.quad);
     }
   };
   if (N >= 256) parallel_pages(n, decode_page);
@@ -358,11 +384,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   const int lo = std::min(N, rank * per), hi = std::min(N, lo + per);
   crops.ensure((size_t)world * per * 32 * 128 * 3);           // (the last shard may be ragged: the buffer holds world * per crops)
   if (rank == 0) {
-    rects_dev.ensure(B.rects.size() * 4);
-    h_rects[0].ensure(B.rects.size() * 4);
-    memcpy(h_rects[0].p, B.rects.data(), B.rects.size() * 4);
-    TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[0].p, B.rects.size() * 4, hipMemcpyHostToDevice, stream));
-    launch_pack_crops(B.d_pages, B.page_bytes, B.w * 3, rects_dev.as<int>(), crops.as<uint8_t>(), N, stream);
+    pack_batch_crops(B, 0);
   }
   c->tr->broadcast(crops.p, (size_t)N * 32 * 128 * 3, 0, stream);
   logits.ensure((size_t)per * 26 * 95 * 4);
@@ -391,6 +413,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
       float bb[4];
       tesseract_bbox(B.boxes[pg][k], bb);
       r.bbox.insert(r.bbox.end(), bb, bb + 4);
+      push_quad(B.boxes[pg][k], r.quad);
     }
   }
 }

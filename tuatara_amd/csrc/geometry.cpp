@@ -53,6 +53,37 @@ void tesseract_bbox(const RRect& r, float bbox[4]) {
   bbox[0] = std::round(min_x); bbox[1] = std::round(min_y); bbox[2] = std::round(max_x); bbox[3] = std::round(max_y);
 }
 
+// ---------------------------------------------------------------- rectified crops (DESIGN.md "Rectified crops")
+// The side P[s] -> P[s+1] of rect_points runs at r.angle + (s - 1) * 90 degrees (P0 -> P1 is the h side, P1 -> P2 the w side; the
+// order P0..P3 is clockwise on screen).  The baseline is the side whose direction, folded, lies in (-45, 45]; a tie at 45 goes to
+// the longer side, then to the side at +45.  Every step is exact in double on the float angle, so tests/rectify_ref.py repeats it.
+int deskew_quad(const RRect& r, Pt2f quad[4], double coef[6]) {
+  Pt2f p[4];
+  rect_points(r, p);
+  const double a = r.angle;
+  const double j = std::isfinite(a) ? std::ceil((a - 45.) / 90.) : 0.;
+  const double theta = a - 90. * j;                       // the baseline's direction, in (-45, 45]
+  int s = (int)(((1 - (long long)j) % 4 + 4) % 4);
+  if (theta == 45.) {                                     // the side at -45 is P[s-1] -> P[s]; even s is an h side, odd s a w side
+    const float len_s = (s & 1) ? r.w : r.h, len_m = (s & 1) ? r.h : r.w;
+    if (len_m > len_s) s = (s + 3) & 3;
+  }
+  for (int i = 0; i < 4; ++i) quad[i] = p[(s + i) & 3];
+  // A = tr - tl, B = bl - tl; X0 = tl.x + 0.5 A.x / 128 + 0.5 B.x / 32, left to right, one statement per rounding (no contraction)
+  const double Ax = ((double)quad[1].x - (double)quad[0].x) / 128., Bx = ((double)quad[3].x - (double)quad[0].x) / 32.;
+  const double Ay = ((double)quad[1].y - (double)quad[0].y) / 128., By = ((double)quad[3].y - (double)quad[0].y) / 32.;
+  double x0 = (double)quad[0].x + 0.5 * Ax;
+  x0 = x0 + 0.5 * Bx;
+  double y0 = (double)quad[0].y + 0.5 * Ay;
+  y0 = y0 + 0.5 * By;
+  coef[0] = x0; coef[1] = Ax; coef[2] = Bx; coef[3] = y0; coef[4] = Ay; coef[5] = By;
+  return std::isfinite(a) && std::fmod(a, 90.) == 0. ? 0 : 1;
+}
+
+void deskew_fixed(const double coef[6], int64_t fixed[6]) {
+  for (int i = 0; i < 6; ++i) fixed[i] = (int64_t)std::llrint(coef[i] * 65536.);
+}
+
 // ---------------------------------------------------------------- convex hull (monotone chain, exact on integer-valued input)
 static double cross(const Pt2f& o, const Pt2f& a, const Pt2f& b) {
   return ((double)a.x - o.x) * ((double)b.y - o.y) - ((double)a.y - o.y) * ((double)b.x - o.x);

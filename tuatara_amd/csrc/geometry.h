@@ -20,6 +20,15 @@ RRect min_area_rect(const Pt2f* pts, int n);                  // cv::minAreaRect
 RRect finish_min_area_rect(int kind, const float v[6]);
 RRect adjust_coordinates(const RRect& r, float ratio_w, float ratio_h, float ratio_net = 2.f);  // tuatara.cpp:236-253
 
+// Rectified crops (ttr_config.crop_mode = TTR_CROP_RECTIFIED; DESIGN.md "Rectified crops").  quad = the word's corners tl, tr, br, bl
+// (clockwise on screen, fp32 from rect_points): the baseline tl -> tr is the side nearest horizontal, skew in [-45, 45] degrees, x
+// component positive; tl -> bl points down.  coef = {X0, Ax, Bx, Y0, Ay, By} in image pixels: output pixel (u, v) of the 32 x 128 crop
+// samples (X0 + u Ax + v Bx, Y0 + u Ay + v By).  Returns the crop kind: 0 when r.angle is a multiple of 90 (the boundingRect crop,
+// bit for bit the reference's), else 1 (the affine sampler, post_ops.hip: pack_crops_rect_kernel).
+int deskew_quad(const RRect& r, Pt2f quad[4], double coef[6]);
+// the coefficients as the kernel takes them: llrint to int64 in units of 2^-16 px
+void deskew_fixed(const double coef[6], int64_t fixed[6]);
+
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.
 struct Component {

@@ -264,6 +264,10 @@ void launch_ccl(const float* heat /*[pages][H][W][2]*/, int pages, int H, int W,
 // crops: rects5[n] = {x0,y0,x1,y1,page} (clamped, x1/y1 exclusive) of images u8 [pages][h,w,3] (page stride page_bytes)
 // -> out u8 [N][32][128][3]; one launch for the crops of every page of a batch
 void launch_pack_crops(const uint8_t* images, size_t page_bytes, int stride, const int* rects5, uint8_t* out, int N, hipStream_t s);
+// crop_mode = TTR_CROP_RECTIFIED: coef8 = {kind, X0, Ax, Bx, Y0, Ay, By, 0} per crop (geometry.h: deskew_quad / deskew_fixed);
+// kind 0 crops are pack_crops_kernel's, kind 1 crops the affine sampler on pages of h x w
+void launch_pack_crops_rect(const uint8_t* images, size_t page_bytes, int stride, int h, int w, const int* rects5, const int64_t* coef8, uint8_t* out,
+                            int N, hipStream_t s);
 // get_detected_boxes' per-component tail on the GPU (tuatara.cpp:162-179: niter, ROI, dilation, findNonZero + minAreaRect): one lane per candidate, geometry.cpp's
 // arithmetic step for step (float32 calipers, double where OpenCV is double) -> CclBuffers::rects.  After launch_ccl on the same stream.
 void launch_ccl_rects(const CclBuffers& b, int pages, int H, int W, hipStream_t s);

@@ -510,4 +510,63 @@ void launch_pack_crops(const uint8_t* images, size_t page_bytes, int stride, con
   hipLaunchKernelGGL(pack_crops_kernel, dim3(N), dim3(256), 0, s, images, page_bytes, stride, rects5, out);
 }
 
+// ------------------------------------------------------------------ rectified crop-batch packer (crop_mode = TTR_CROP_RECTIFIED)
+// One workgroup per crop, one launch per batch.  Kind 0: pack_crops_kernel's resample of the boundingRect, bit for bit.  Kind 1:
+// output pixel (u, v) samples the page at (X0 + u Ax + v Bx, Y0 + u Ay + v By), int64 in units of 2^-16 px (DESIGN.md "Rectified
+// crops"): 11-bit bilinear weights, border replicated, no floating point.  A thread makes 4 adjacent pixels of a row and stores them
+// as three dwords, so a wave writes 768 contiguous bytes (two output rows); the coefficients are workgroup-uniform (scalar loads).
+__device__ __forceinline__ void affine_pixel_u8c3(const uint8_t* __restrict__ image, int stride, int h, int w, long long sx, long long sy, uint8_t* out3) {
+  const long long ix = sx >> 16, iy = sy >> 16;
+  const int fx = (int)((sx >> 5) & 2047), fy = (int)((sy >> 5) & 2047);
+  const int x0 = (int)(ix < 0 ? 0 : (ix > w - 1 ? w - 1 : ix)), x1 = (int)(ix + 1 < 0 ? 0 : (ix + 1 > w - 1 ? w - 1 : ix + 1));
+  const int y0 = (int)(iy < 0 ? 0 : (iy > h - 1 ? h - 1 : iy)), y1 = (int)(iy + 1 < 0 ? 0 : (iy + 1 > h - 1 ? h - 1 : iy + 1));
+  const uint8_t* r0 = image + (size_t)y0 * stride;
+  const uint8_t* r1 = image + (size_t)y1 * stride;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int t = (2048 - fx) * r0[x0 * 3 + c] + fx * r0[x1 * 3 + c];
+    const int b = (2048 - fx) * r1[x0 * 3 + c] + fx * r1[x1 * 3 + c];
+    const int v = ((2048 - fy) * t + fy * b + (1 << 21)) >> 22;
+    out3[c] = (uint8_t)(v > 255 ? 255 : v);
+  }
+}
+
+__global__ __launch_bounds__(256) void pack_crops_rect_kernel(const uint8_t* __restrict__ images, size_t page_bytes, int stride, int h, int w,
+                                                              const int* __restrict__ rects, const int64_t* __restrict__ coef, uint8_t* __restrict__ out) {
+  const int n = blockIdx.x;
+  const int x0 = rects[5 * n], y0 = rects[5 * n + 1], x1 = rects[5 * n + 2], y1 = rects[5 * n + 3];
+  const uint8_t* image = images + (size_t)rects[5 * n + 4] * page_bytes;
+  uint32_t* o = reinterpret_cast<uint32_t*>(out + (size_t)n * 32 * 128 * 3);   // 12288 bytes per crop: dword aligned
+  if (x1 <= x0 || y1 <= y0) {
+    for (int p = threadIdx.x; p < 32 * 128 * 3 / 4; p += blockDim.x) o[p] = 0;
+    return;
+  }
+  const int64_t* cf = coef + 8 * n;
+  const int kind = (int)cf[0];
+  const long long X0 = cf[1], Ax = cf[2], Bx = cf[3], Y0 = cf[4], Ay = cf[5], By = cf[6];
+  const ResizeGeom g = make_resize_geom(y1 - y0, x1 - x0, 32, 128);
+  const uint8_t* src = image + (size_t)y0 * stride + (size_t)x0 * 3;
+  for (int q = threadIdx.x; q < 32 * 32; q += blockDim.x) {
+    const int v = q >> 5, u0 = (q & 31) * 4;
+    uint8_t px[12];
+    if (kind == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) resize_pixel_u8c3(src, stride, g, v, u0 + k, px + 3 * k);
+    } else {
+      long long sx = X0 + (long long)u0 * Ax + (long long)v * Bx, sy = Y0 + (long long)u0 * Ay + (long long)v * By;
+#pragma unroll
+      for (int k = 0; k < 4; ++k, sx += Ax, sy += Ay) affine_pixel_u8c3(image, stride, h, w, sx, sy, px + 3 * k);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      o[3 * q + k] = (uint32_t)px[4 * k] | ((uint32_t)px[4 * k + 1] << 8) | ((uint32_t)px[4 * k + 2] << 16) | ((uint32_t)px[4 * k + 3] << 24);
+  }
+}
+
+void launch_pack_crops_rect(const uint8_t* images, size_t page_bytes, int stride, int h, int w, const int* rects5, const int64_t* coef8, uint8_t* out,
+                            int N, hipStream_t s) {
+  if (N <= 0) return;
+  hipLaunchKernelGGL(pack_crops_rect_kernel, dim3(N), dim3(256), 0, s, images, page_bytes, stride, h, w, rects5, coef8, out);
+}
+
 }  // namespace ttr

@@ -12,27 +12,43 @@ namespace {
 std::mutex g_mu;
 std::map<std::string, ttr_engine*> g_engines;  // one engine per (weights_dir, precision); lives for the process
 
-ttr_engine* engine_for(const std::string& weights_dir) {
+// crop_mode < 0: the process default (TUATARA_CROP_MODE, else TTR_CROP_BOUNDING)
+ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1) {
   std::lock_guard<std::mutex> lk(g_mu);
   ttr_config cfg;
   ttr_config_default(&cfg);
+  if (const char* p = std::getenv("TUATARA_CROP_MODE")) cfg.crop_mode = std::atoi(p);
+  if (crop_mode >= 0) cfg.crop_mode = crop_mode;
   if (const char* p = std::getenv("TUATARA_PRECISION")) {   // default: TTR_PREC_F16X4 (fp32-equivalent, the reference computes in fp32)
     const std::string v(p);
     cfg.precision = v == "f32" ? TTR_PREC_F32 : v == "bf16" ? TTR_PREC_BF16 : TTR_PREC_F16X4;
   }
   if (const char* p = std::getenv("TUATARA_STRICT_CROPS")) cfg.strict_crops = std::atoi(p);
   if (const char* p = std::getenv("TUATARA_DEVICE")) cfg.device = std::atoi(p);
-  std::string key = weights_dir + "#" + std::to_string(cfg.precision) + "#" + std::to_string(cfg.device);
+  std::string key = weights_dir + "#" + std::to_string(cfg.precision) + "#" + std::to_string(cfg.device) + "#" + std::to_string(cfg.crop_mode);
   auto it = g_engines.find(key);
   if (it != g_engines.end()) return it->second;
   ttr_engine* e = ttr_create(weights_dir.c_str(), &cfg);
   if (e) g_engines[key] = e;
   return e;
 }
-}  // namespace
 
-std::vector<OutputItem> image_to_data(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
-                                      std::string outputs_dir) {
+void fill(OutputItem& o, const ttr_result* r, int i) {
+  o.text = ttr_result_text(r, i);
+  const float* b = ttr_result_bbox(r, i);
+  o.bbox.assign(b, b + 4);
+}
+void fill(OutputItemEx& o, const ttr_result* r, int i) {
+  o.text = ttr_result_text(r, i);
+  const float* b = ttr_result_bbox(r, i);
+  o.bbox.assign(b, b + 4);
+  const float* q = ttr_result_quad(r, i);
+  o.quad.assign(q, q + 8);
+}
+
+template <class Item>
+std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
+                          const std::string& outputs_dir, int crop_mode) {
   if (weights_dir.empty()) {  // tuatara.cpp:315-318
     std::cerr << "Please provide a value for weights_dir" << std::endl;
     return {};
@@ -41,7 +57,7 @@ std::vector<OutputItem> image_to_data(const uint8_t* image, int rows, int cols, 
     std::cerr << "Please provide a value for outputs_dir" << std::endl;
     return {};
   }
-  ttr_engine* e = engine_for(weights_dir);
+  ttr_engine* e = engine_for(weights_dir, crop_mode);
   if (!e) {  // tuatara.cpp:337-340, :429-432
     std::cerr << "error loading craft/parseq model: " << ttr_last_error() << std::endl;
     return {};
@@ -55,20 +71,17 @@ std::vector<OutputItem> image_to_data(const uint8_t* image, int rows, int cols, 
     std::cerr << "tuatara: " << ttr_last_error() << std::endl;
     return {};
   }
-  std::vector<OutputItem> out(ttr_result_count(r));
-  for (size_t i = 0; i < out.size(); ++i) {
-    out[i].text = ttr_result_text(r, (int)i);
-    const float* b = ttr_result_bbox(r, (int)i);
-    out[i].bbox.assign(b, b + 4);
-  }
+  std::vector<Item> out(ttr_result_count(r));
+  for (size_t i = 0; i < out.size(); ++i) fill(out[i], r, (int)i);
   ttr_result_free(r);
   return out;
 }
 
-std::vector<std::vector<OutputItem>> images_to_data(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir) {
+template <class Item>
+std::vector<std::vector<Item>> run_many(const std::vector<ImageView>& images, const std::string& weights_dir, const std::string& outputs_dir, int crop_mode) {
   if (weights_dir.empty()) { std::cerr << "Please provide a value for weights_dir" << std::endl; return {}; }   // tuatara.cpp:315-318
   if (outputs_dir.empty()) { std::cerr << "Please provide a value for outputs_dir" << std::endl; return {}; }   // tuatara.cpp:320-323
-  ttr_engine* e = engine_for(weights_dir);
+  ttr_engine* e = engine_for(weights_dir, crop_mode);
   if (!e) { std::cerr << "error loading craft/parseq model: " << ttr_last_error() << std::endl; return {}; }     // tuatara.cpp:337-340, :429-432
   const int n = (int)images.size();
   std::vector<const uint8_t*> ptr(n);
@@ -85,15 +98,31 @@ std::vector<std::vector<OutputItem>> images_to_data(const std::vector<ImageView>
     return {};
   }
   if (rc > 0) std::cerr << "tuatara: " << ttr_last_error() << std::endl;   // some images failed: theirs stay empty, the rest are returned (a loop over image_to_data)
-  std::vector<std::vector<OutputItem>> out(n);
+  std::vector<std::vector<Item>> out(n);
   for (int i = 0; i < n; ++i) {
     out[i].resize(ttr_result_count(rs[i]));
-    for (size_t k = 0; k < out[i].size(); ++k) {
-      out[i][k].text = ttr_result_text(rs[i], (int)k);
-      const float* b = ttr_result_bbox(rs[i], (int)k);
-      out[i][k].bbox.assign(b, b + 4);
-    }
+    for (size_t k = 0; k < out[i].size(); ++k) fill(out[i][k], rs[i], (int)k);
     ttr_result_free(rs[i]);
   }
   return out;
+}
+}  // namespace
+
+std::vector<OutputItem> image_to_data(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                      std::string outputs_dir) {
+  return run_one<OutputItem>(image, rows, cols, row_stride, weights_dir, outputs_dir, -1);
+}
+
+std::vector<std::vector<OutputItem>> images_to_data(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir) {
+  return run_many<OutputItem>(images, weights_dir, outputs_dir, -1);
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify) {
+  return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1);
+}
+
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify) {
+  return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1);
 }

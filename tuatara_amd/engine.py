@@ -18,12 +18,13 @@ _LIBPATH = os.environ.get("TUATARA_LIB") or os.path.join(os.path.dirname(os.path
 _lib = None
 
 PREC_BF16, PREC_F32, PREC_F16X4 = 0, 1, 2
+CROP_BOUNDING, CROP_RECTIFIED = 0, 1
 
 
 class Config(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("canvas_size", C.c_int), ("mag_ratio", C.c_float),
                 ("text_threshold", C.c_float), ("link_threshold", C.c_float), ("low_text", C.c_float), ("min_area", C.c_int),
-                ("strict_crops", C.c_int), ("max_components", C.c_int), ("verbose", C.c_int)]
+                ("strict_crops", C.c_int), ("max_components", C.c_int), ("verbose", C.c_int), ("crop_mode", C.c_int)]
 
 
 # every symbol include/tuatara_hip.h declares: (name, restype, argtypes)
@@ -44,6 +45,8 @@ SYMBOLS = [
     ("ttr_result_text", C.c_char_p, [_VP, _I]),
     ("ttr_result_bbox", _PF, [_VP, _I]),
     ("ttr_result_ids", _PI, [_VP, _I]),
+    ("ttr_result_quad", _PF, [_VP, _I]),
+    ("ttr_result_quads", _PF, [_VP]),
     ("ttr_result_free", None, [_VP]),
     ("ttr_result_bboxes", _PF, [_VP]),
     ("ttr_result_ids_all", _PI, [_VP]),
@@ -53,6 +56,7 @@ SYMBOLS = [
     ("ttr_ccl_boxes", _I, [_VP, _PF, _I, _I, _PF, _I, _PI]),
     ("ttr_resize_canvas", _I, [_VP, _PU8, _I, _I, _I, _PU8, C.c_size_t, _PI, _PI, _PF]),
     ("ttr_pack_crops", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _F, _PU8, _PF]),
+    ("ttr_pack_crops_rectified", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _F, _PU8, _PF]),
     ("ttr_parseq_logits", _I, [_VP, _PU8, _I, _PF, _PF, _PI]),
     ("ttr_decode_ids", _I, [_PI, _I, C.c_char_p]),
     ("ttr_engine_set_tuning", _I, [_VP, C.c_char_p, _I]),
@@ -61,6 +65,7 @@ SYMBOLS = [
     ("ttr_dbg_tcp_share", _I, [_I, _I, C.c_char_p, _I, _VP, C.c_size_t]),
     ("ttr_dbg_component_rect", _I, [_I, _I, _I, _I, _I, _PI, _I, _I, _PF]),
     ("ttr_dbg_box_geometry", _I, [_PF, _F, _PF, _PI, _PF]),
+    ("ttr_dbg_deskew", _I, [_PF, _PF, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     ("ttr_dev_alloc", _VP, [C.c_size_t]),
     ("ttr_dev_free", None, [_VP]),
     ("ttr_dev_upload", _I, [_VP, _VP, C.c_size_t]),
@@ -174,14 +179,31 @@ def box_geometry(rect5, ratio: float):
     return adj, tuple(int(v) for v in xywh), [float(v) for v in bbox]
 
 
+def deskew(rect5):
+    """Engine host geometry (no GPU): the rectified-crop rule on one rect {cx,cy,w,h,angle} in image pixels (ttr_dbg_deskew) ->
+    (kind, quad f32 [4,2] tl/tr/br/bl, coef f64 [6] {X0,Ax,Bx,Y0,Ay,By}, fixed int64 [6] in units of 2^-16 px)."""
+    r = np.ascontiguousarray(rect5, dtype=np.float32)
+    quad, coef, fixed = np.zeros(8, np.float32), np.zeros(6, np.float64), np.zeros(6, np.int64)
+    kind = load().ttr_dbg_deskew(_f(r), _f(quad), coef.ctypes.data_as(C.POINTER(C.c_double)), fixed.ctypes.data_as(C.POINTER(C.c_int64)))
+    if kind < 0:
+        raise EngineError(load().ttr_last_error().decode())
+    return kind, quad.reshape(4, 2), coef, fixed
+
+
+def _quad_pairs(q8) -> list:
+    """8 floats tl, tr, br, bl -> [[x, y], ...] (4 pairs)"""
+    q = [float(v) for v in q8]
+    return [q[0:2], q[2:4], q[4:6], q[6:8]]
+
+
 class PageResult(collections.abc.Sequence):
     """One page's words as the list of {"text", "bbox", "ids"} dicts pytuatara.image_to_data returns, materialised on access:
-    the batch hand-over keeps the arrays the C ABI filled (`texts`, `bbox` f32 [n,4], `ids` i32 [n,26]) and builds dicts only
-    for the items a caller touches."""
-    __slots__ = ("texts", "bbox", "ids")
+    the batch hand-over keeps the arrays the C ABI filled (`texts`, `bbox` f32 [n,4], `ids` i32 [n,26]; `quad` f32 [n,8] in the
+    rectified crop mode, else None) and builds dicts only for the items a caller touches."""
+    __slots__ = ("texts", "bbox", "ids", "quad")
 
-    def __init__(self, texts, bbox, ids):
-        self.texts, self.bbox, self.ids = texts, bbox, ids
+    def __init__(self, texts, bbox, ids, quad=None):
+        self.texts, self.bbox, self.ids, self.quad = texts, bbox, ids, quad
 
     def __len__(self):
         return len(self.texts)
@@ -193,7 +215,10 @@ class PageResult(collections.abc.Sequence):
             j += len(self)
         if not 0 <= j < len(self):
             raise IndexError(j)
-        return {"text": self.texts[j], "bbox": self.bbox[j].tolist(), "ids": self.ids[j].tolist()}
+        d = {"text": self.texts[j], "bbox": self.bbox[j].tolist(), "ids": self.ids[j].tolist()}
+        if self.quad is not None:
+            d["quad"] = _quad_pairs(self.quad[j])
+        return d
 
     def __eq__(self, other):
         return list(self) == list(other)
@@ -277,8 +302,16 @@ class Engine:
         if rc != 0:
             raise EngineError(self.lib.ttr_last_error().decode())
 
+    @property
+    def rectified(self) -> bool:
+        """crop_mode = CROP_RECTIFIED: result dicts carry "quad" (4 [x, y] corners tl, tr, br, bl)"""
+        return self.cfg.crop_mode == CROP_RECTIFIED
+
+    def _quads(self, r, n: int) -> np.ndarray:
+        return np.ctypeslib.as_array(self.lib.ttr_result_quads(r), (n, 8)).copy() if n else np.zeros((0, 8), np.float32)
+
     def _take(self, r) -> List[dict]:
-        """ttr_result -> the reference's list of {"text", "bbox"} dicts (+ "ids"), through the bulk getters."""
+        """ttr_result -> the reference's list of {"text", "bbox"} dicts (+ "ids"; + "quad" when rectified), through the bulk getters."""
         n = self.lib.ttr_result_count(r)
         out = []
         if n:
@@ -289,6 +322,9 @@ class Engine:
             self.lib.ttr_result_texts(r, buf, need)
             texts = buf.raw[:need].decode("latin1").split("\n")
             out = [{"text": texts[i], "bbox": bb[i], "ids": ids[i]} for i in range(n)]
+            if self.rectified:
+                for d, q in zip(out, self._quads(r, n)):
+                    d["quad"] = _quad_pairs(q)
         self.lib.ttr_result_free(r)
         return out
 
@@ -305,7 +341,7 @@ class Engine:
         out, k = [], 0
         for i in range(n):
             c = int(counts[i])
-            out.append(PageResult(texts[k:k + c], bb[k:k + c], ids[k:k + c]))
+            out.append(PageResult(texts[k:k + c], bb[k:k + c], ids[k:k + c], self._quads(arr[i], c) if self.rectified else None))
             k += c
             self.lib.ttr_result_free(arr[i])
         return out
@@ -491,6 +527,17 @@ class Engine:
         self._check(self.lib.ttr_pack_crops(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _f(rects), n,
                                             C.c_float(ratio), _u8(crops), _f(boxes)))
         return crops, boxes
+
+    def pack_crops_rectified(self, image: np.ndarray, rects: np.ndarray, ratio: float):
+        """ttr_pack_crops_rectified: the crop_mode = CROP_RECTIFIED crops of heat-map rects -> (crops u8 [n,32,128,3], quads f32 [n,4,2])."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        rects = np.ascontiguousarray(rects, dtype=np.float32).reshape(-1, 5)
+        n = len(rects)
+        crops = np.zeros((n, 32, 128, 3), np.uint8)
+        quads = np.zeros((n, 4, 2), np.float32)
+        self._check(self.lib.ttr_pack_crops_rectified(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _f(rects), n,
+                                                      C.c_float(ratio), _u8(crops), _f(quads)))
+        return crops, quads
 
     def parseq_logits(self, crops: np.ndarray, want_ar: bool = False):
         crops = np.ascontiguousarray(crops, dtype=np.uint8)

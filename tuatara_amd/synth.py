@@ -56,3 +56,43 @@ def synthetic_page(seed: int, h: int = 1024, w: int = 768, n_words: int = 40, sc
             k += 1
     a = np.asarray(page, dtype=np.uint8)
     return np.ascontiguousarray(np.repeat(a[:, :, None], 3, 2))
+
+
+def synthetic_rotated_page(seed: int, h: int = 1024, w: int = 768, n_words: int = 16, max_deg: float = 30.0):
+    """Words drawn as synthetic_page draws them (PIL's default font magnified 2x), each rotated by a seeded skew in [-max_deg, max_deg]
+    degrees (image coordinates, y down: positive turns the baseline clockwise on screen) and pasted where it overlaps no other word.
+    Returns (page u8 [h, w, 3], words): per placed word a dict {"word", "centre": (cx, cy) in image pixels (pixel centres at integers),
+    "angle": skew in degrees, "tile": the upright word u8 [th, tw] as it was rotated}.  Fewer than n_words are placed when the page is full."""
+    from PIL import Image, ImageDraw, ImageFont
+
+    rng = np.random.default_rng(seed)
+    font = ImageFont.load_default()
+    page = Image.new("L", (w, h), 255)
+    taken = []                                     # axis-aligned bounds (x0, y0, x1, y1) of the rotated words placed so far, with a margin
+    words = []
+    for _ in range(n_words):
+        word = "".join(rng.choice(list(ALNUM), size=int(rng.integers(4, 11))))
+        tile = Image.new("L", (80, 16), 255)
+        ImageDraw.Draw(tile).text((3, 2), word, fill=0, font=font)
+        bb = Image.eval(tile, lambda v: 255 - v).getbbox()
+        tile = tile.crop((bb[0] - 2, bb[1] - 2, bb[2] + 2, bb[3] + 2))
+        tile = tile.resize((tile.size[0] * 2, tile.size[1] * 2), Image.NEAREST)
+        ang = float(rng.uniform(-max_deg, max_deg))
+        rot = tile.rotate(-ang, resample=Image.BILINEAR, expand=True, fillcolor=255)
+        mask = tile.point(lambda v: 255).rotate(-ang, resample=Image.BILINEAR, expand=True, fillcolor=0)
+        rw, rh = rot.size
+        for _try in range(200):
+            x = int(rng.integers(4, max(5, w - rw - 4)))
+            y = int(rng.integers(4, max(5, h - rh - 4)))
+            box = (x - 6, y - 6, x + rw + 6, y + rh + 6)
+            if x + rw <= w - 4 and y + rh <= h - 4 and all(box[2] <= t[0] or t[2] <= box[0] or box[3] <= t[1] or t[3] <= box[1] for t in taken):
+                break
+        else:
+            continue
+        page.paste(rot, (x, y), mask)
+        taken.append(box)
+        # PIL's expand keeps the tile's centre at the centre of the rotated canvas; pixel centres sit at integer coordinates
+        words.append({"word": word, "centre": (x + rw / 2.0 - 0.5, y + rh / 2.0 - 0.5), "angle": ang,
+                      "tile": np.asarray(tile, dtype=np.uint8).copy()})
+    a = np.asarray(page, dtype=np.uint8)
+    return np.ascontiguousarray(np.repeat(a[:, :, None], 3, 2)), words
