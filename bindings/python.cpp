@@ -1,7 +1,9 @@
 // pybind11 module `pytuatara` — same surface as /root/reference/bindings/python.cpp:43-58:
 //   pytuatara.image_to_data(image, weights_dir, outputs_dir) -> list[{"text": str, "bbox": [x1,y1,x2,y2]}]
 // plus a keyword-only rectify=False on both calls: rectify=True reads tilted words on deskewed crops (DESIGN.md "Rectified crops") and
-// every dict gains "quad": [[x, y] x 4] (tl, tr, br, bl); engines are cached per (weights_dir, rectify).
+// every dict gains "quad": [[x, y] x 4] (tl, tr, br, bl); engines are cached per (weights_dir, rectify).  And a keyword-only conf=False:
+// conf=True adds "conf" (the word's confidence, a probability in (0, 1]) and "char_conf" (one probability per character of "text";
+// DESIGN.md "Recognition confidence"); it combines with rectify.  With both False every dict is the reference's {text, bbox}.
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -21,36 +23,40 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-template <class Item>
-static py::dict item_dict(const Item& item) {
+struct Keys { bool quad = false, conf = false; };   // the optional keys of an OutputItemEx's dict
+
+static py::dict item_dict(const OutputItem& item, Keys = Keys()) {
   py::dict d;
   d["text"] = item.text;
   d["bbox"] = item.bbox;
   return d;
 }
-template <>
-py::dict item_dict<OutputItemEx>(const OutputItemEx& item) {
+static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
   d["text"] = item.text;
   d["bbox"] = item.bbox;
-  d["quad"] = quad_pairs(item.quad);
+  if (k.quad) d["quad"] = quad_pairs(item.quad);
+  if (k.conf) {
+    d["conf"] = item.conf;
+    d["char_conf"] = item.char_conf;
+  }
   return d;
 }
 
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
-                                      std::string output_dir, bool rectify) {
+                                      std::string output_dir, bool rectify, bool conf) {
   py::buffer_info buf = image.request();
   if (buf.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
   if (buf.shape[2] != 3) throw std::runtime_error("Input array should have 3 channels");
   const int rows = (int)buf.shape[0], cols = (int)buf.shape[1];
   py::list result;
-  if (rectify) {
+  if (rectify || conf) {
     std::vector<OutputItemEx> items;
     {
       py::gil_scoped_release nogil;
-      items = image_to_data_ex(static_cast<const uint8_t*>(buf.ptr), rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, true);
+      items = image_to_data_ex(static_cast<const uint8_t*>(buf.ptr), rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
     }
-    for (const auto& item : items) result.append(item_dict(item));
+    for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf}));
     return result;
   }
   std::vector<OutputItem> items;
@@ -66,17 +72,17 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
 // images: a sequence of uint8 arrays [H, W, 3] of any sizes.  What a caller of the reference writes as a loop over image_to_data (bindings/run_ocr.py:92),
 // on one cached engine: same-sized images travel as batches, the host-to-device copies run beside the GPU's work, the GIL is released meanwhile.
 template <class Item>
-static py::list pages_list(const std::vector<std::vector<Item>>& pages) {
+static py::list pages_list(const std::vector<std::vector<Item>>& pages, Keys k = Keys()) {
   py::list result;
   for (const auto& items : pages) {
     py::list page;
-    for (const auto& item : items) page.append(item_dict(item));
+    for (const auto& item : items) page.append(item_dict(item, k));
     result.append(page);
   }
   return result;
 }
 
-static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify) {
+static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf) {
   std::vector<py::array_t<unsigned char, py::array::c_style | py::array::forcecast>> keep;   // contiguous uint8 views / copies, alive for the call
   std::vector<ImageView> views;
   for (py::handle h : images) {
@@ -88,13 +94,13 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
     views.push_back(ImageView{static_cast<const uint8_t*>(buf.ptr), (int)buf.shape[0], (int)buf.shape[1], (std::ptrdiff_t)buf.shape[1] * 3});
     keep.push_back(std::move(a));
   }
-  if (rectify) {
+  if (rectify || conf) {
     std::vector<std::vector<OutputItemEx>> pages;
     {
       py::gil_scoped_release nogil;
-      pages = images_to_data_ex(views, weights_dir, output_dir, true);
+      pages = images_to_data_ex(views, weights_dir, output_dir, rectify);
     }
-    return pages_list(pages);
+    return pages_list(pages, Keys{rectify, conf});
   }
   std::vector<std::vector<OutputItem>> pages;
   {
@@ -107,7 +113,8 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
 PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
-        py::arg("rectify") = false, "Extract text and bounding boxes from an image");
+        py::arg("rectify") = false, py::arg("conf") = false, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
-        py::arg("rectify") = false, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
+        py::arg("rectify") = false, py::arg("conf") = false,
+        "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
 }

@@ -34,10 +34,13 @@ std::vector<std::vector<OutputItem>> images_to_data(const std::vector<ImageView>
 // word's quadrilateral; with rectify = true a tilted word is deskewed (up to 45 degrees) before the recogniser reads it, so `text` may
 // differ from image_to_data's; with rectify = false the crops are image_to_data's.  OutputItem keeps the reference's layout.
 // TUATARA_CROP_MODE=1 in the environment (beside TUATARA_STRICT_CROPS) makes image_to_data / images_to_data use rectified crops too.
+// Every OutputItemEx also carries the recogniser's confidence: `conf` for the word and `char_conf` per character (ttr_result_conf / ttr_result_prob).
 struct OutputItemEx {
   std::string text;
   std::vector<float> bbox;  // x1, y1, x2, y2
   std::vector<float> quad;  // tl.x, tl.y, tr.x, tr.y, br.x, br.y, bl.x, bl.y in image pixels; tl -> tr is the baseline
+  float conf = 0.f;                // the recogniser's confidence in `text`, a probability in (0, 1] (DESIGN.md "Recognition confidence")
+  std::vector<float> char_conf;    // one probability per character of `text`, in order (char_conf.size() == text.size())
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, bool rectify);

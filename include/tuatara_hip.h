@@ -97,6 +97,16 @@ const int32_t* ttr_result_ids(const ttr_result* r, int i);  /* 26 argmax token i
  * mode; ttr_result_quads is the bulk view [count][8] (NULL when the result is empty). */
 const float* ttr_result_quad(const ttr_result* r, int i);
 const float* ttr_result_quads(const ttr_result* r);
+/* Recognition confidence (DESIGN.md "Recognition confidence"), every crop mode and entry point; a probability in (0, 1], never 0-100.
+ * ttr_result_prob: 26 floats parallel to ttr_result_ids - prob[p] = 1 / sum_c exp(x[c] - x[id[p]]), the softmax value of the argmax id
+ * over the refined logits x of position p (the reference's Tokenizer::max_dist, tuatara.cpp:101-106, which it computes and discards).
+ * ttr_result_conf: the word's confidence - the fp32 product, in position order from 1.0f, of prob over the positions that make up the
+ * text (before the first EOS, id 0, and not id 88), times prob[EOS] when the row has an EOS (upstream PARSeq's convention).  Bulk views:
+ * ttr_result_confs [count], ttr_result_probs_all [count][26] (NULL when the result is empty). */
+float ttr_result_conf(const ttr_result* r, int i);
+const float* ttr_result_prob(const ttr_result* r, int i);
+const float* ttr_result_confs(const ttr_result* r);
+const float* ttr_result_probs_all(const ttr_result* r);
 void ttr_result_free(ttr_result* r);
 /* bulk views for bindings (valid until ttr_result_free): all boxes [count][4], all ids [count][26]; the texts of all
  * items, each followed by '\n' (no token maps to '\n'), copied into buf when cap suffices; returns the bytes needed. */
@@ -107,6 +117,12 @@ int ttr_result_texts(const ttr_result* r, char* buf, size_t cap);
  * above ('\n' after each item, copied when texts_cap >= *texts_need).  Returns the total item count. */
 int ttr_results_gather(ttr_result* const* rs, int n, int32_t* counts, float* bboxes, int32_t* ids, char* texts, size_t texts_cap,
                        size_t* texts_need);
+/* ... and their confidences (either output may be NULL): conf[total], probs[total][26], in ttr_results_gather's item order.  Returns the total. */
+int ttr_results_gather_conf(ttr_result* const* rs, int n, float* conf, float* probs);
+/* The confidence rule on the host, no GPU: ids / probs of n_pos positions -> char_conf[*n_chars] (prob of each character of
+ * ttr_decode_ids(ids), in order; n_pos entries always suffice) and *conf (the product above; bit-equal to ttr_result_conf given the same
+ * probs).  Takes any ids: ids outside [0, 98) are dropped as ttr_decode_ids drops them.  Outputs may be NULL.  Returns *n_chars, -1 on bad arguments. */
+int ttr_confidence_from_probs(const int32_t* ids, const float* probs, int n_pos, float* char_conf, int* n_chars, float* conf);
 
 /* ---- multi-GPU: RCCL in the C++ host -----------------------------------------------------------------
  * One process per GPU, one engine per process.  The OCR path has no data-path collective: pages are independent.  The one exchange is
@@ -142,6 +158,9 @@ int ttr_engine_attach_comm(ttr_engine* e, ttr_comm* c);
  * (rank, page, crop) order.  Returns the number of id rows (and the sizes through world / pages / ids_need); buffers that are too
  * small or NULL are not written. */
 int ttr_last_gathered(ttr_engine* e, int* world, int* pages, int32_t* counts, size_t counts_cap, int32_t* ids, size_t ids_cap, size_t* ids_need);
+/* ... and the same rows' confidences, gathered in the same collective as the ids: conf[rows], probs[rows][26] (same order as ids).  Returns
+ * the number of rows; buffers that are too small or NULL are not written. */
+int ttr_last_gathered_conf(ttr_engine* e, float* conf, size_t conf_cap, float* probs, size_t probs_cap);
 /* bytes of every rank concatenated by rank into all[world * bytes] (small host buffers; also the barrier of the benchmark) */
 int ttr_comm_allgather_host(ttr_comm* c, const void* mine, size_t bytes, void* all);
 /* the framing of a gathered batch, host logic only (no GPU): counts[world][pages] -> cap (payload rows per rank), total[world],
@@ -177,6 +196,9 @@ int ttr_pack_crops_rectified(ttr_engine* e, const uint8_t* hwc_u8, int h, int w,
  * its loop when every crop has emitted EOS; behind a crop's own EOS the bf16 engine skips it, and zero-fills the steps behind the batch's
  * exit) -, ids (optional) the argmax ids [n][26]. */
 int ttr_parseq_logits(ttr_engine* e, const uint8_t* crops, int n, float* logits, float* ar_logits, int32_t* ids);
+/* The recogniser's final decode on host logits f32 [n][26][95] (uploaded, decode_conf_kernel, downloaded): ids [n][26] as the engine forms
+ * them, probs [n][26] and conf [n] as ttr_result_prob / ttr_result_conf give them.  Any output may be NULL. */
+int ttr_logits_confidence(ttr_engine* e, const float* logits, int n, int32_t* ids, float* probs, float* conf);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

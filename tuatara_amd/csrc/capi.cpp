@@ -135,6 +135,27 @@ const float* ttr_result_quad(const ttr_result* r, int i) { return &r->r.quad[8 *
 
 const float* ttr_result_quads(const ttr_result* r) { return r && !r->r.quad.empty() ? r->r.quad.data() : nullptr; }
 
+float ttr_result_conf(const ttr_result* r, int i) { return r->r.conf[(size_t)i]; }
+
+const float* ttr_result_prob(const ttr_result* r, int i) { return &r->r.prob[26 * (size_t)i]; }
+
+const float* ttr_result_confs(const ttr_result* r) { return r && !r->r.conf.empty() ? r->r.conf.data() : nullptr; }
+
+const float* ttr_result_probs_all(const ttr_result* r) { return r && !r->r.prob.empty() ? r->r.prob.data() : nullptr; }
+
+int ttr_results_gather_conf(ttr_result* const* rs, int n, float* conf, float* probs) {
+  if (!rs || n < 0) return -1;
+  size_t oc = 0, op = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!rs[i]) continue;
+    const Result& r = rs[i]->r;
+    if (conf && !r.conf.empty()) memcpy(conf + oc, r.conf.data(), r.conf.size() * 4);
+    if (probs && !r.prob.empty()) memcpy(probs + op, r.prob.data(), r.prob.size() * 4);
+    oc += r.conf.size(); op += r.prob.size();
+  }
+  return (int)oc;
+}
+
 void ttr_result_free(ttr_result* r) { delete r; }
 
 const float* ttr_result_bboxes(const ttr_result* r) { return r && !r->r.bbox.empty() ? r->r.bbox.data() : nullptr; }
@@ -291,10 +312,10 @@ int ttr_parseq_logits(ttr_engine* e, const uint8_t* crops, int n, float* logits,
   if (n <= 0) return 0;
   E.crops.ensure((size_t)n * 32 * 128 * 3);
   E.logits.ensure((size_t)n * 26 * 95 * 4);
-  E.ids_dev.ensure((size_t)n * 26 * 4);
+  const Engine::RecOut o = E.rec_out(n);
   if (ar_logits) E.ar_logits.ensure((size_t)n * 26 * 95 * 4);
   TTR_HIP_CHECK(hipMemcpyAsync(E.crops.p, crops, (size_t)n * 32 * 128 * 3, hipMemcpyHostToDevice, E.stream));
-  E.parseq_forward(E.crops.as<uint8_t>(), n, E.logits.as<float>(), ar_logits ? E.ar_logits.as<float>() : nullptr, E.ids_dev.as<int>());
+  E.parseq_forward(E.crops.as<uint8_t>(), n, E.logits.as<float>(), ar_logits ? E.ar_logits.as<float>() : nullptr, o.ids, o.prob, o.conf);
   TTR_HIP_CHECK(hipMemcpyAsync(logits, E.logits.p, (size_t)n * 26 * 95 * 4, hipMemcpyDeviceToHost, E.stream));
   if (ar_logits) TTR_HIP_CHECK(hipMemcpyAsync(ar_logits, E.ar_logits.p, (size_t)n * 26 * 95 * 4, hipMemcpyDeviceToHost, E.stream));
   if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, E.ids_dev.p, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
@@ -303,6 +324,32 @@ int ttr_parseq_logits(ttr_engine* e, const uint8_t* crops, int n, float* logits,
   E.range_verify(Engine::kRangeStage, "ttr_parseq_logits");
   return 0;
   TTR_GUARD_END(-1)
+}
+
+int ttr_logits_confidence(ttr_engine* e, const float* logits, int n, int32_t* ids, float* probs, float* conf) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && !logits)) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_logits_confidence");
+  if (n == 0) return 0;
+  E.logits.ensure((size_t)n * 26 * 95 * 4);
+  const Engine::RecOut o = E.rec_out(n);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream);
+  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, o.ids, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (probs) TTR_HIP_CHECK(hipMemcpyAsync(probs, o.prob, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (conf) TTR_HIP_CHECK(hipMemcpyAsync(conf, o.conf, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_confidence_from_probs(const int32_t* ids, const float* probs, int n_pos, float* char_conf, int* n_chars, float* conf) {
+  if (!ids || !probs || n_pos < 0) return -1;
+  const int k = confidence_from_probs(ids, probs, n_pos, char_conf, conf);
+  if (n_chars) *n_chars = k;
+  return k;
 }
 
 int ttr_decode_ids(const int32_t* ids, int n, char* buf) {

@@ -355,6 +355,17 @@ int ttr_last_gathered(ttr_engine* e, int* world, int* pages, int32_t* counts, si
   TTR_GUARD_END(-1)
 }
 
+int ttr_last_gathered_conf(ttr_engine* e, float* conf, size_t conf_cap, float* probs, size_t probs_cap) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  EngineScope lk(*e->e);
+  const auto& g = e->e->last_gathered;
+  if (conf && conf_cap >= g.conf.size() && !g.conf.empty()) memcpy(conf, g.conf.data(), g.conf.size() * 4);
+  if (probs && probs_cap >= g.prob.size() && !g.prob.empty()) memcpy(probs, g.prob.data(), g.prob.size() * 4);
+  return (int)g.conf.size();
+  TTR_GUARD_END(-1)
+}
+
 int ttr_gather_layout(const int32_t* counts, int world, int pages, int* cap, int32_t* total, int64_t* first) {
   TTR_GUARD_BEGIN
   if (!counts || world < 1 || pages < 0) throw std::runtime_error("bad arguments");

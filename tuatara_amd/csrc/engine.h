@@ -260,6 +260,8 @@ struct Result {
   std::vector<float> bbox;   // 4 per item
   std::vector<int32_t> ids;  // 26 per item
   std::vector<float> quad;   // 8 per item: the word's corners tl, tr, br, bl in image pixels (geometry.h: deskew_quad), every crop mode
+  std::vector<float> prob;   // 26 per item: softmax probability of each argmax id (decode_conf.hip)
+  std::vector<float> conf;   // 1 per item: the word's confidence (DESIGN.md "Recognition confidence")
 };
 
 struct CclBatch {   // device workspaces of the CCL stage for a batch of equally sized pages
@@ -517,7 +519,7 @@ struct Engine {
   Comm* comm = nullptr;
   DevBuf gath_dev[2];
   PinnedBuf h_gath[2];
-  struct Gathered { int world = 0, pages = 0; std::vector<int32_t> counts, ids; } last_gathered;
+  struct Gathered { int world = 0, pages = 0; std::vector<int32_t> counts, ids; std::vector<float> prob, conf; } last_gathered;
   // small host buffers of every rank, concatenated by rank (also the barrier): staged through device memory on the copy stream
   void allgather_host(const void* mine, size_t bytes, void* all);
   Engine(const std::string& dir, const ttr_config& c);
@@ -572,8 +574,17 @@ struct Engine {
   void decoder_tail(const void* sa, int N, int R, const float* resid_pos, int resid_mod, float* tgt, void* t384, void* t384b, void* t1536,
                     const void* kvmem, float* logits_out, int logits_ld, const int* done_tok = nullptr, int done_col = 0);
 
-  // crops u8 [N][32][128][3] (device) -> logits f32 [N][26][95], ids i32 [N][26] (device); d_ar optional
-  void parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids);
+  // crops u8 [N][32][128][3] (device) -> logits f32 [N][26][95], ids i32 [N][26], prob f32 [N][26], conf f32 [N] (device); d_ar optional
+  void parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf);
+  // The recogniser's outputs of `rows` crops share one device buffer (ids_dev), laid out [rows][26] ids | [rows][26] prob | [rows] conf, so that
+  // one device-to-host copy and one collective carry all three.  Ensures the buffer (never inside a launch function).
+  struct RecOut { int* ids; float* prob; float* conf; };
+  static constexpr int kRecWords = 26 + 26 + 1;   // 4-byte words per crop
+  RecOut rec_out(int rows) {
+    ids_dev.ensure((size_t)std::max(rows, 1) * kRecWords * 4);
+    int* b = ids_dev.as<int>();
+    return RecOut{b, reinterpret_cast<float*>(b + (size_t)rows * 26), reinterpret_cast<float*>(b + (size_t)rows * 52)};
+  }
 
   // ---- post-processing of one page's heat map: GPU CCL + host calipers
   struct PageBoxes { std::vector<RRect> det; };
@@ -608,6 +619,7 @@ struct Engine {
     bool live = false, enqueued = false;
     std::vector<int32_t> all_counts;   // with a communicator: crops per page of every rank [world][n]
     int cap = 0;                       // ... and the largest rank total (rows of the gathered payload per rank)
+    int rows = 0;                      // rows of the recogniser's output block (RecOut) staged in h_ids[slot]: max(N, cap)
   };
   PageBatch q1, q2;        // streamed batches: q1 = boxes known (recogniser enqueued or not), q2 = older, recogniser enqueued, results not yet returned
 

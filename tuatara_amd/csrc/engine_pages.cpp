@@ -260,28 +260,28 @@ void Engine::pack_batch_crops(const PageBatch& B, int sl) {
 void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
   range_use(kRangeRec0 + (sl & 1));          // the recogniser's kernels of this batch watch the slot's own word
-  h_ids[sl].ensure((size_t)N * 26 * 4 + 4);
+  B.rows = std::max(N, comm ? B.cap : 0);   // the output block's rows (RecOut): with a communicator, the gathered payload's rows per rank
+  const size_t block = (size_t)B.rows * kRecWords * 4;
+  h_ids[sl].ensure(block + 4);
+  const RecOut out = rec_out(B.rows);
   TTR_HIP_CHECK(hipEventRecord(evr[sl][0], stream));
   if (N > 0) {
     crops.ensure((size_t)N * 32 * 128 * 3);
     logits.ensure((size_t)N * 26 * 95 * 4);
-    ids_dev.ensure((size_t)std::max(N, B.cap) * 26 * 4);
     pack_batch_crops(B, sl);
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
-    parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, ids_dev.as<int>());
+    parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf);
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
-    TTR_HIP_CHECK(hipMemcpyAsync(h_ids[sl].as<int32_t>(), ids_dev.p, (size_t)N * 26 * 4, hipMemcpyDeviceToHost, stream));
+    TTR_HIP_CHECK(hipMemcpyAsync(h_ids[sl].p, ids_dev.p, block, hipMemcpyDeviceToHost, stream));   // ids, prob and conf in one copy
   } else {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
   }
-  if (comm && B.cap > 0) {   // the payload: cap rows of 26 ids per rank, straight from the recogniser's device buffer
-    const size_t per = (size_t)B.cap * 26;
-    ids_dev.ensure(per * 4);
-    gath_dev[sl].ensure(per * 4 * comm->world);
-    h_gath[sl].ensure(per * 4 * comm->world);
-    comm->tr->all_gather(ids_dev.p, gath_dev[sl].p, per * 4, false, stream);
-    TTR_HIP_CHECK(hipMemcpyAsync(h_gath[sl].p, gath_dev[sl].p, per * 4 * comm->world, hipMemcpyDeviceToHost, stream));
+  if (comm && B.cap > 0) {   // the payload: the output block of cap rows per rank - [cap][26] ids | [cap][26] prob | [cap] conf -, straight from the recogniser's device buffer
+    gath_dev[sl].ensure(block * comm->world);
+    h_gath[sl].ensure(block * comm->world);
+    comm->tr->all_gather(ids_dev.p, gath_dev[sl].p, block, false, stream);
+    TTR_HIP_CHECK(hipMemcpyAsync(h_gath[sl].p, gath_dev[sl].p, block * comm->world, hipMemcpyDeviceToHost, stream));
   }
   range_fetch(kRangeRec0 + (sl & 1));
   TTR_HIP_CHECK(hipEventRecord(done_ev[sl], stream));
@@ -304,11 +304,21 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
     const GatherLayout L = GatherLayout::from_counts(B.all_counts.data(), comm->world, n);
     last_gathered.world = L.world; last_gathered.pages = n; last_gathered.counts = B.all_counts;
     last_gathered.ids.resize((size_t)L.first.back() * 26);
+    last_gathered.prob.resize((size_t)L.first.back() * 26);
+    last_gathered.conf.resize((size_t)L.first.back());
     const int32_t* g = h_gath[B.slot].as<int32_t>();
-    for (int r = 0; r < L.world; ++r)
-      if (L.total[r]) memcpy(&last_gathered.ids[(size_t)L.first[(size_t)r * n] * 26], g + (size_t)r * B.cap * 26, (size_t)L.total[r] * 26 * 4);
+    for (int r = 0; r < L.world; ++r) {   // rank r's block: cap rows of each of the three arrays
+      if (!L.total[r]) continue;
+      const int32_t* gr = g + (size_t)r * B.cap * kRecWords;
+      const size_t f = (size_t)L.first[(size_t)r * n];
+      memcpy(&last_gathered.ids[f * 26], gr, (size_t)L.total[r] * 26 * 4);
+      memcpy(&last_gathered.prob[f * 26], gr + (size_t)B.cap * 26, (size_t)L.total[r] * 26 * 4);
+      memcpy(&last_gathered.conf[f], gr + (size_t)B.cap * 52, (size_t)L.total[r] * 4);
+    }
   }
   const int32_t* ids = h_ids[B.slot].as<int32_t>();
+  const float* prob = reinterpret_cast<const float*>(ids + (size_t)B.rows * 26);
+  const float* conf = reinterpret_cast<const float*>(ids + (size_t)B.rows * 52);
   // crops are ordered by page: page pg owns crops [first[pg], first[pg + 1]); pages decode independently
   std::vector<int> first(n + 1, 0);
   for (int c = 0; c < N; ++c) first[B.page_of[c] + 1]++;
@@ -318,6 +328,8 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
     const int c0 = first[pg], cnt = first[pg + 1] - c0;
     r.text.reserve(cnt); r.bbox.reserve((size_t)cnt * 4); r.quad.reserve((size_t)cnt * 8);
     r.ids.assign(&ids[(size_t)c0 * 26], &ids[(size_t)(c0 + cnt) * 26]);
+    r.prob.assign(&prob[(size_t)c0 * 26], &prob[(size_t)(c0 + cnt) * 26]);
+    r.conf.assign(&conf[c0], &conf[c0 + cnt]);
     for (int k = 0; k < cnt; ++k) {
       r.text.push_back(tok.decode(&ids[(size_t)(c0 + k) * 26], 26));   // :486-505
       float bb[4];
@@ -388,19 +400,30 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   }
   c->tr->broadcast(crops.p, (size_t)N * 32 * 128 * 3, 0, stream);
   logits.ensure((size_t)per * 26 * 95 * 4);
-  ids_dev.ensure((size_t)per * 26 * 4);
+  const RecOut out = rec_out(per);                              // per rank: [per][26] ids | [per][26] prob | [per] conf, one collective
+  const size_t block = (size_t)per * kRecWords * 4;
   range_use(kRangeRec0);
-  if (hi > lo) parseq_forward(crops.as<uint8_t>() + (size_t)lo * 32 * 128 * 3, hi - lo, logits.as<float>(), nullptr, ids_dev.as<int>());
-  gath_dev[0].ensure((size_t)world * per * 26 * 4);
-  h_gath[0].ensure((size_t)world * per * 26 * 4);
-  c->tr->all_gather(ids_dev.p, gath_dev[0].p, (size_t)per * 26 * 4, false, stream);
-  TTR_HIP_CHECK(hipMemcpyAsync(h_gath[0].p, gath_dev[0].p, (size_t)world * per * 26 * 4, hipMemcpyDeviceToHost, stream));
+  if (hi > lo) parseq_forward(crops.as<uint8_t>() + (size_t)lo * 32 * 128 * 3, hi - lo, logits.as<float>(), nullptr, out.ids, out.prob, out.conf);
+  gath_dev[0].ensure((size_t)world * block);
+  h_gath[0].ensure((size_t)world * block);
+  c->tr->all_gather(ids_dev.p, gath_dev[0].p, block, false, stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(h_gath[0].p, gath_dev[0].p, (size_t)world * block, hipMemcpyDeviceToHost, stream));
   range_fetch(kRangeRec0);
   TTR_HIP_CHECK(hipEventRecord(done_ev[0], stream));
   spin_event(done_ev[0]);
   range_verify(kRangeRec0, "the recogniser of a sharded page");
   if (rank != 0) return;
-  const int32_t* ids = h_gath[0].as<int32_t>();                // shard r occupies rows [r * per, r * per + its size): crop k = row k
+  // shard r's block starts at word r * per * kRecWords: crop k is row k % per of shard k / per
+  std::vector<int32_t> ids((size_t)N * 26);
+  std::vector<float> prob((size_t)N * 26), conf(N);
+  const int32_t* g = h_gath[0].as<int32_t>();
+  for (int r = 0; r * per < N; ++r) {
+    const int32_t* gr = g + (size_t)r * per * kRecWords;
+    const int cnt = std::min(per, N - r * per);
+    memcpy(&ids[(size_t)r * per * 26], gr, (size_t)cnt * 26 * 4);
+    memcpy(&prob[(size_t)r * per * 26], gr + (size_t)per * 26, (size_t)cnt * 26 * 4);
+    memcpy(&conf[(size_t)r * per], gr + (size_t)per * 52, (size_t)cnt * 4);
+  }
   std::vector<int> first(pages + 1, 0);
   for (int k = 0; k < N; ++k) first[B.page_of[k] + 1]++;
   for (int pg = 0; pg < pages; ++pg) first[pg + 1] += first[pg];
@@ -408,6 +431,8 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
     Result& r = results[pg];
     const int c0 = first[pg], cnt = first[pg + 1] - c0;
     r.ids.assign(&ids[(size_t)c0 * 26], &ids[(size_t)(c0 + cnt) * 26]);
+    r.prob.assign(&prob[(size_t)c0 * 26], &prob[(size_t)(c0 + cnt) * 26]);
+    r.conf.assign(&conf[c0], &conf[c0 + cnt]);
     for (int k = 0; k < cnt; ++k) {
       r.text.push_back(tok.decode(&ids[(size_t)(c0 + k) * 26], 26));
       float bb[4];

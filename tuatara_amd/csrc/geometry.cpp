@@ -288,4 +288,18 @@ std::string Tokenizer::decode(const int* ids, int n) const {
   return s;
 }
 
+int confidence_from_probs(const int* ids, const float* probs, int n, float* char_conf, float* conf) {
+  float c = 1.f;
+  int k = 0;
+  for (int p = 0; p < n; ++p) {
+    if (ids[p] == 0) { c *= probs[p]; break; }                 // the EOS ends the text; its probability counts (upstream PARSeq's probs[:eos + 1])
+    if (ids[p] == 88 || ids[p] < 0 || ids[p] >= 98) continue;   // dropped by Tokenizer::decode
+    c *= probs[p];
+    if (char_conf) char_conf[k] = probs[p];
+    ++k;
+  }
+  if (conf) *conf = c;
+  return k;
+}
+
 }  // namespace ttr

@@ -52,4 +52,10 @@ struct Tokenizer {
   std::string decode(const int* ids, int n) const;
 };
 
+// The confidence rule (DESIGN.md "Recognition confidence") on the host, for any ids: the characters of decode(ids) are the positions before the
+// first id 0 (the EOS) whose id is not 88 and lies in [0, 98); char_conf (n entries suffice) receives their probs in position order, *conf the fp32
+// product from 1.0f of those probs, in order, times probs[EOS] when there is an EOS.  decode_conf_kernel forms the same product.  Returns the
+// number of characters (= decode(ids, n).size()).
+int confidence_from_probs(const int* ids, const float* probs, int n, float* char_conf, float* conf);
+
 }  // namespace ttr

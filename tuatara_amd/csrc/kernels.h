@@ -194,6 +194,9 @@ void launch_dec_cross_attn(Precision prec, const void* q, const void* kvmem, voi
 void launch_argmax(const float* logits, int ld, int C, int* tokens, int tok_ld, int col, int N, hipStream_t s, const int* skip = nullptr, int skip_n = 0,
                    int* done_count = nullptr, int eos = 0);
 void launch_fill_i32(int* p, int value, int n, int stride, hipStream_t s);
+// decode_conf.hip: the refinement pass's final decode - logits f32 [N][26][95] -> ids [N][26] (bit-identical to launch_argmax's), prob f32 [N][26]
+// (softmax value of each id), conf f32 [N] (product over the text's characters and the EOS; DESIGN.md "Recognition confidence")
+void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s);
 
 // ---- mlp_fused.hip: x_out = x + fc2(GELU(fc1(LayerNorm(x)))) [+ y = LayerNorm_next(x_out)] for the ViT encoder blocks (bf16, E = 384)
 struct MlpParams {

@@ -44,6 +44,11 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
   o.bbox.assign(b, b + 4);
   const float* q = ttr_result_quad(r, i);
   o.quad.assign(q, q + 8);
+  o.conf = ttr_result_conf(r, i);
+  float cc[26];
+  int nc = 0;
+  ttr_confidence_from_probs(ttr_result_ids(r, i), ttr_result_prob(r, i), 26, cc, &nc, nullptr);
+  o.char_conf.assign(cc, cc + nc);
 }
 
 template <class Item>

@@ -47,11 +47,18 @@ SYMBOLS = [
     ("ttr_result_ids", _PI, [_VP, _I]),
     ("ttr_result_quad", _PF, [_VP, _I]),
     ("ttr_result_quads", _PF, [_VP]),
+    ("ttr_result_conf", _F, [_VP, _I]),
+    ("ttr_result_prob", _PF, [_VP, _I]),
+    ("ttr_result_confs", _PF, [_VP]),
+    ("ttr_result_probs_all", _PF, [_VP]),
     ("ttr_result_free", None, [_VP]),
     ("ttr_result_bboxes", _PF, [_VP]),
     ("ttr_result_ids_all", _PI, [_VP]),
     ("ttr_result_texts", _I, [_VP, C.c_char_p, C.c_size_t]),
     ("ttr_results_gather", _I, [C.POINTER(_VP), _I, _PI, _PF, _PI, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ttr_results_gather_conf", _I, [C.POINTER(_VP), _I, _PF, _PF]),
+    ("ttr_confidence_from_probs", _I, [_PI, _PF, _I, _PF, C.POINTER(C.c_int), _PF]),
+    ("ttr_logits_confidence", _I, [_VP, _PF, _I, _PI, _PF, _PF]),
     ("ttr_craft_heatmap", _I, [_VP, _PU8, _I, _I, _PF]),
     ("ttr_ccl_boxes", _I, [_VP, _PF, _I, _I, _PF, _I, _PI]),
     ("ttr_resize_canvas", _I, [_VP, _PU8, _I, _I, _I, _PU8, C.c_size_t, _PI, _PI, _PF]),
@@ -99,6 +106,7 @@ SYMBOLS = [
     ("ttr_comm_world", _I, [_VP]),
     ("ttr_engine_attach_comm", _I, [_VP, _VP]),
     ("ttr_last_gathered", _I, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int), _PI, C.c_size_t, _PI, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ttr_last_gathered_conf", _I, [_VP, _PF, C.c_size_t, _PF, C.c_size_t]),
     ("ttr_comm_allgather_host", _I, [_VP, _VP, C.c_size_t, _VP]),
     ("ttr_gather_layout", _I, [_PI, _I, _I, C.POINTER(C.c_int), _PI, C.POINTER(C.c_int64)]),
     ("ttr_pages_to_data_dev_sharded", _I, [_VP, _VP, _I, _I, _I, C.POINTER(_VP)]),
@@ -190,6 +198,26 @@ def deskew(rect5):
     return kind, quad.reshape(4, 2), coef, fixed
 
 
+def confidence_from_probs(ids, probs):
+    """The confidence rule on the host (ttr_confidence_from_probs, no GPU): ids / probs of one row -> (char_conf f32 [len(text)], conf f32)."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+    probs = np.ascontiguousarray(probs, dtype=np.float32).ravel()
+    if len(ids) != len(probs):
+        raise ValueError("ids and probs differ in length")
+    cc = np.zeros(max(len(ids), 1), np.float32)
+    nc, conf = C.c_int(), C.c_float()
+    if load().ttr_confidence_from_probs(_i(ids), _f(probs), len(ids), _f(cc), C.byref(nc), C.byref(conf)) < 0:
+        raise EngineError("ttr_confidence_from_probs: bad arguments")
+    return cc[:nc.value].copy(), np.float32(conf.value)
+
+
+def _add_conf(d: dict, conf, prob) -> dict:
+    """the conf=True keys of a result dict: "conf" (the kernel's word confidence) and "char_conf" (one probability per character of "text")"""
+    d["conf"] = float(conf)
+    d["char_conf"] = confidence_from_probs(d["ids"], prob)[0].tolist()
+    return d
+
+
 def _quad_pairs(q8) -> list:
     """8 floats tl, tr, br, bl -> [[x, y], ...] (4 pairs)"""
     q = [float(v) for v in q8]
@@ -199,11 +227,16 @@ def _quad_pairs(q8) -> list:
 class PageResult(collections.abc.Sequence):
     """One page's words as the list of {"text", "bbox", "ids"} dicts pytuatara.image_to_data returns, materialised on access:
     the batch hand-over keeps the arrays the C ABI filled (`texts`, `bbox` f32 [n,4], `ids` i32 [n,26]; `quad` f32 [n,8] in the
-    rectified crop mode, else None) and builds dicts only for the items a caller touches."""
-    __slots__ = ("texts", "bbox", "ids", "quad")
+    rectified crop mode, else None; `conf` f32 [n] and `prob` f32 [n,26] always) and builds dicts only for the items a caller touches.
+    with_conf: the dicts carry "conf" and "char_conf" too (DESIGN.md "Recognition confidence")."""
+    __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf")
 
-    def __init__(self, texts, bbox, ids, quad=None):
+    def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False):
         self.texts, self.bbox, self.ids, self.quad = texts, bbox, ids, quad
+        n = len(texts)
+        self.conf = conf if conf is not None else np.zeros(n, np.float32)
+        self.prob = prob if prob is not None else np.zeros((n, 26), np.float32)
+        self.with_conf = with_conf
 
     def __len__(self):
         return len(self.texts)
@@ -218,6 +251,8 @@ class PageResult(collections.abc.Sequence):
         d = {"text": self.texts[j], "bbox": self.bbox[j].tolist(), "ids": self.ids[j].tolist()}
         if self.quad is not None:
             d["quad"] = _quad_pairs(self.quad[j])
+        if self.with_conf:
+            _add_conf(d, self.conf[j], self.prob[j])
         return d
 
     def __eq__(self, other):
@@ -310,8 +345,9 @@ class Engine:
     def _quads(self, r, n: int) -> np.ndarray:
         return np.ctypeslib.as_array(self.lib.ttr_result_quads(r), (n, 8)).copy() if n else np.zeros((0, 8), np.float32)
 
-    def _take(self, r) -> List[dict]:
-        """ttr_result -> the reference's list of {"text", "bbox"} dicts (+ "ids"; + "quad" when rectified), through the bulk getters."""
+    def _take(self, r, conf: bool = False) -> List[dict]:
+        """ttr_result -> the reference's list of {"text", "bbox"} dicts (+ "ids"; + "quad" when rectified; + "conf", "char_conf" with conf),
+        through the bulk getters."""
         n = self.lib.ttr_result_count(r)
         out = []
         if n:
@@ -325,11 +361,17 @@ class Engine:
             if self.rectified:
                 for d, q in zip(out, self._quads(r, n)):
                     d["quad"] = _quad_pairs(q)
+            if conf:
+                cf = np.ctypeslib.as_array(self.lib.ttr_result_confs(r), (n,)).copy()
+                pr = np.ctypeslib.as_array(self.lib.ttr_result_probs_all(r), (n, 26)).copy()
+                for d, c, p in zip(out, cf, pr):
+                    _add_conf(d, c, p)
         self.lib.ttr_result_free(r)
         return out
 
-    def _take_many(self, arr, n: int) -> List[List[dict]]:
-        """A batch of ttr_results -> list (per page) of lists of {"text", "bbox", "ids"}: one gather call for the whole batch."""
+    def _take_many(self, arr, n: int, conf: bool = False) -> List[List[dict]]:
+        """A batch of ttr_results -> list (per page) of lists of {"text", "bbox", "ids"} (+ "conf", "char_conf" with conf): one gather call
+        for the whole batch."""
         counts = np.zeros(n, np.int32)
         need = C.c_size_t()
         total = self.lib.ttr_results_gather(arr, n, _i(counts), None, None, None, 0, C.byref(need))
@@ -338,16 +380,21 @@ class Engine:
         buf = C.create_string_buffer(max(need.value, 1))
         self.lib.ttr_results_gather(arr, n, None, _f(bb), _i(ids), buf, need.value, None)
         texts = buf.raw[:need.value].decode("latin1").split("\n")
+        cf = np.zeros(max(total, 1), np.float32)
+        pr = np.zeros((max(total, 1), 26), np.float32)
+        self.lib.ttr_results_gather_conf(arr, n, _f(cf), _f(pr))
         out, k = [], 0
         for i in range(n):
             c = int(counts[i])
-            out.append(PageResult(texts[k:k + c], bb[k:k + c], ids[k:k + c], self._quads(arr[i], c) if self.rectified else None))
+            out.append(PageResult(texts[k:k + c], bb[k:k + c], ids[k:k + c], self._quads(arr[i], c) if self.rectified else None,
+                                  cf[k:k + c], pr[k:k + c], conf))
             k += c
             self.lib.ttr_result_free(arr[i])
         return out
 
     # ---- hot path
-    def image_to_data(self, image: np.ndarray) -> List[dict]:
+    def image_to_data(self, image: np.ndarray, conf: bool = False) -> List[dict]:
+        """conf=True: every dict gains "conf" (the word's confidence, a probability) and "char_conf" (one probability per character of "text")."""
         if image.ndim != 3:
             raise RuntimeError("Input array should have 3 dimensions")          # bindings/python.cpp:15-17 of the reference
         if image.shape[2] != 3:
@@ -355,9 +402,9 @@ class Engine:
         image = np.ascontiguousarray(image, dtype=np.uint8)
         r = C.c_void_p()
         self._check(self.lib.ttr_image_to_data(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, C.byref(r)))
-        return self._take(r)
+        return self._take(r, conf)
 
-    def images_to_data(self, images, keep: bool = True):
+    def images_to_data(self, images, keep: bool = True, conf: bool = False):
         """image_to_data over a list of host images [H, W, 3] u8 of any sizes (ttr_images_to_data): one result list per image, input order."""
         arrs = []
         for im in images:
@@ -379,36 +426,36 @@ class Engine:
         if rc > 0:                              # rc images failed: their results are empty, the others delivered (include/tuatara_hip.h)
             self.last_images_error = self.lib.ttr_last_error().decode()
         if keep:
-            return self._take_many(out, n)
+            return self._take_many(out, n, conf)
         counts = []
         for i in range(n):
             counts.append(self.lib.ttr_result_count(out[i]))
             self.lib.ttr_result_free(out[i])
         return counts
 
-    def pages_to_data_dev(self, d_pages, n: int, h: int, w: int, keep: bool = True):
+    def pages_to_data_dev(self, d_pages, n: int, h: int, w: int, keep: bool = True, conf: bool = False):
         """d_pages: DeviceBuffer or raw device pointer holding [n][h][w][3] u8."""
         ptr = d_pages.ptr if isinstance(d_pages, DeviceBuffer) else d_pages
         arr = (C.c_void_p * n)()
         self._check(self.lib.ttr_pages_to_data_dev(self.h, ptr, n, h, w, arr))
         if keep:
-            return self._take_many(arr, n)
+            return self._take_many(arr, n, conf)
         counts = []
         for i in range(n):
             counts.append(self.lib.ttr_result_count(arr[i]))
             self.lib.ttr_result_free(arr[i])
         return counts
 
-    def _stream_take(self, arr, n_prev: int, keep: bool):
+    def _stream_take(self, arr, n_prev: int, keep: bool, conf: bool = False):
         if keep:
-            return self._take_many(arr, n_prev)
+            return self._take_many(arr, n_prev, conf)
         counts = []
         for i in range(n_prev):
             counts.append(self.lib.ttr_result_count(arr[i]))
             self.lib.ttr_result_free(arr[i])
         return counts
 
-    def stream_push(self, d_pages, n: int, h: int, w: int, keep: bool = True, max_batch: int = 0):
+    def stream_push(self, d_pages, n: int, h: int, w: int, keep: bool = True, max_batch: int = 0, conf: bool = False):
         """Streamed batches (ttr_stream_push): enqueue batch k+1, get batch k's results (an empty list on the first push).  The
         pages of a batch must stay alive until its results have come back."""
         ptr = d_pages.ptr if isinstance(d_pages, DeviceBuffer) else d_pages
@@ -416,13 +463,13 @@ class Engine:
         arr = (C.c_void_p * self._max_pushed)()
         n_prev = C.c_int(0)
         self._check(self.lib.ttr_stream_push(self.h, ptr, n, h, w, arr, C.byref(n_prev)))
-        return self._stream_take(arr, n_prev.value, keep)
+        return self._stream_take(arr, n_prev.value, keep, conf)
 
-    def stream_flush(self, keep: bool = True):
+    def stream_flush(self, keep: bool = True, conf: bool = False):
         arr = (C.c_void_p * getattr(self, "_max_pushed", 1))()
         n_prev = C.c_int(0)
         self._check(self.lib.ttr_stream_flush(self.h, arr, C.byref(n_prev)))
-        return self._stream_take(arr, n_prev.value, keep)
+        return self._stream_take(arr, n_prev.value, keep, conf)
 
     def last_stage_ms(self):
         ms = (C.c_float * 4)()
@@ -548,6 +595,15 @@ class Engine:
         self._check(self.lib.ttr_parseq_logits(self.h, _u8(crops), n, _f(logits), _f(ar) if want_ar else None, _i(ids)))
         return (logits, ar, ids) if want_ar else (logits, ids)
 
+    def logits_confidence(self, logits: np.ndarray):
+        """The recogniser's final decode on host logits f32 [n, 26, 95] (ttr_logits_confidence: decode_conf_kernel) -> (ids i32 [n, 26],
+        prob f32 [n, 26], conf f32 [n])."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, 26, 95)
+        n = len(logits)
+        ids, prob, conf = np.zeros((n, 26), np.int32), np.zeros((n, 26), np.float32), np.zeros(n, np.float32)
+        self._check(self.lib.ttr_logits_confidence(self.h, _f(logits), n, _i(ids), _f(prob), _f(conf)))
+        return ids, prob, conf
+
     def dbg_conv_pool(self, x0: np.ndarray, w: np.ndarray, bias: Optional[np.ndarray], ks: int, act: int = 0, pool_relu: bool = False,
                       want_full: bool = True):
         """bf16 engines: conv + fused 2x2 max-pool -> (full f32 [B,H,W,Cout] or None, pooled f32 [B,H/2,W/2,Cout])."""
@@ -672,14 +728,23 @@ class Comm:
         self.lib.ttr_last_gathered(self.eng.h, None, None, _i(counts), counts.size, _i(ids), ids.size, None)
         return counts, ids
 
-    def pages_to_data_sharded(self, d_pages, n: int, h: int, w: int):
+    def last_gathered_conf(self):
+        """(conf f32 [rows], prob f32 [rows, 26]) of the same rows as last_gathered(), carried by the same collective."""
+        rows = self.lib.ttr_last_gathered_conf(self.eng.h, None, 0, None, 0)
+        if rows < 0:
+            raise EngineError(self.lib.ttr_last_error().decode())
+        conf, prob = np.zeros(rows, np.float32), np.zeros((rows, 26), np.float32)
+        self.lib.ttr_last_gathered_conf(self.eng.h, _f(conf), conf.size, _f(prob), prob.size)
+        return conf, prob
+
+    def pages_to_data_sharded(self, d_pages, n: int, h: int, w: int, conf: bool = False):
         """Latency mode (ttr_pages_to_data_dev_sharded): rank 0 passes the device pages, the others None."""
         ptr = d_pages.ptr if isinstance(d_pages, DeviceBuffer) else d_pages
         arr = (C.c_void_p * max(n, 1))()
         k = self.lib.ttr_pages_to_data_dev_sharded(self.h, ptr, n, h, w, arr)
         if k < 0:
             raise EngineError(self.lib.ttr_last_error().decode())
-        return self.eng._take_many(arr, k) if k else []
+        return self.eng._take_many(arr, k, conf) if k else []
 
     def close(self):
         if getattr(self, "h", None):
