@@ -3,7 +3,10 @@
 // plus a keyword-only rectify=False on both calls: rectify=True reads tilted words on deskewed crops (DESIGN.md "Rectified crops") and
 // every dict gains "quad": [[x, y] x 4] (tl, tr, br, bl); engines are cached per (weights_dir, rectify).  And a keyword-only conf=False:
 // conf=True adds "conf" (the word's confidence, a probability in (0, 1]) and "char_conf" (one probability per character of "text";
-// DESIGN.md "Recognition confidence"); it combines with rectify.  With both False every dict is the reference's {text, bbox}.
+// DESIGN.md "Recognition confidence"); it combines with rectify.  And keyword-only orient=None|"flip"|"quarter" and orient_page=False: every
+// word is also read turned (by 180 degrees, or by 90, 180 and 270), keeps the reading the recogniser is most sure of, and its dict gains
+// "orient" (degrees clockwise; DESIGN.md "Word orientation"); orient_page=True decides once per page.  They combine with rectify and conf;
+// engines are cached per (weights_dir, rectify, orient, orient_page).  With all of them off every dict is the reference's {text, bbox}.
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -23,7 +26,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItem& item, Keys = Keys()) {
   py::dict d;
@@ -40,23 +43,35 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
     d["conf"] = item.conf;
     d["char_conf"] = item.char_conf;
   }
+  if (k.orient) d["orient"] = item.orient;
   return d;
 }
 
+// orient=None|"flip"|"quarter" -> TTR_ORIENT_*
+static int orient_mode(const py::object& orient) {
+  if (orient.is_none()) return 0;
+  const std::string v = py::str(orient);
+  if (v == "flip") return 1;
+  if (v == "quarter") return 2;
+  throw std::invalid_argument("orient must be None, \"flip\" or \"quarter\"");
+}
+
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
-                                      std::string output_dir, bool rectify, bool conf) {
+                                      std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page) {
+  const int orient = orient_mode(orient_kw);
   py::buffer_info buf = image.request();
   if (buf.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
   if (buf.shape[2] != 3) throw std::runtime_error("Input array should have 3 channels");
   const int rows = (int)buf.shape[0], cols = (int)buf.shape[1];
   py::list result;
-  if (rectify || conf) {
+  if (rectify || conf || orient) {
     std::vector<OutputItemEx> items;
     {
       py::gil_scoped_release nogil;
-      items = image_to_data_ex(static_cast<const uint8_t*>(buf.ptr), rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
+      items = orient ? image_to_data_ex(static_cast<const uint8_t*>(buf.ptr), rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
+                     : image_to_data_ex(static_cast<const uint8_t*>(buf.ptr), rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
     }
-    for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf}));
+    for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0}));
     return result;
   }
   std::vector<OutputItem> items;
@@ -82,7 +97,9 @@ static py::list pages_list(const std::vector<std::vector<Item>>& pages, Keys k =
   return result;
 }
 
-static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf) {
+static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf, py::object orient_kw,
+                                       bool orient_page) {
+  const int orient = orient_mode(orient_kw);
   std::vector<py::array_t<unsigned char, py::array::c_style | py::array::forcecast>> keep;   // contiguous uint8 views / copies, alive for the call
   std::vector<ImageView> views;
   for (py::handle h : images) {
@@ -94,13 +111,13 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
     views.push_back(ImageView{static_cast<const uint8_t*>(buf.ptr), (int)buf.shape[0], (int)buf.shape[1], (std::ptrdiff_t)buf.shape[1] * 3});
     keep.push_back(std::move(a));
   }
-  if (rectify || conf) {
+  if (rectify || conf || orient) {
     std::vector<std::vector<OutputItemEx>> pages;
     {
       py::gil_scoped_release nogil;
-      pages = images_to_data_ex(views, weights_dir, output_dir, rectify);
+      pages = orient ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient, orient_page) : images_to_data_ex(views, weights_dir, output_dir, rectify);
     }
-    return pages_list(pages, Keys{rectify, conf});
+    return pages_list(pages, Keys{rectify, conf, orient != 0});
   }
   std::vector<std::vector<OutputItem>> pages;
   {
@@ -113,8 +130,9 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
 PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
-        py::arg("rectify") = false, py::arg("conf") = false, "Extract text and bounding boxes from an image");
+        py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
+        "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
-        py::arg("rectify") = false, py::arg("conf") = false,
+        py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
         "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
 }

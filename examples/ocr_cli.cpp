@@ -6,6 +6,8 @@
 // prints "x1 y1 x2 y2<TAB>tl.x tl.y tr.x tr.y br.x br.y bl.x bl.y<TAB>text" per item.
 //   ocr_cli --conf <image.png> <weights_dir> <outputs_dir>      prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item, conf being the recogniser's
 // confidence in the word, a probability to 6 decimals (DESIGN.md "Recognition confidence").
+//   ocr_cli --orient <image.png> <weights_dir> <outputs_dir>    reads every word at the quarter turn the recogniser is most sure of (DESIGN.md
+// "Word orientation", TTR_ORIENT_QUARTER, per word) and prints "x1 y1 x2 y2<TAB>degrees<TAB>conf<TAB>text" per item.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <cstdio>
 #include <iostream>
@@ -40,8 +42,15 @@ int main(int argc, const char** argv) {
       for (const OutputItemEx& it : items) printf("%g %g %g %g\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.conf, it.text.c_str());
       return 0;
     }
+    if (argc == 5 && std::string(argv[1]) == "--orient") {
+      pngdec::Image img = pngdec::read(argv[2]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[3], argv[4], false, 2, false);
+      for (const OutputItemEx& it : items)
+        printf("%g %g %g %g\t%d\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.orient, it.conf, it.text.c_str());
+      return 0;
+    }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--rectify | --conf] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--rectify | --conf | --orient] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

@@ -41,11 +41,20 @@ struct OutputItemEx {
   std::vector<float> quad;  // tl.x, tl.y, tr.x, tr.y, br.x, br.y, bl.x, bl.y in image pixels; tl -> tr is the baseline
   float conf = 0.f;                // the recogniser's confidence in `text`, a probability in (0, 1] (DESIGN.md "Recognition confidence")
   std::vector<float> char_conf;    // one probability per character of `text`, in order (char_conf.size() == text.size())
+  int orient = 0;                  // word orientation: the turn the word was read at, in degrees clockwise (0, 90, 180, 270; DESIGN.md "Word orientation")
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, bool rectify);
 std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
                                                          bool rectify);
+// Word orientation (opt-in; DESIGN.md "Word orientation"): orient = TTR_ORIENT_FLIP (1) also reads every word turned by 180 degrees,
+// TTR_ORIENT_QUARTER (2) by 90, 180 and 270; each item keeps the reading the recogniser is most sure of and says which in `orient`.
+// orient_page = true: one turn per page, by a vote of its words.  orient = 0 is the calls above.  TUATARA_ORIENT=flip|quarter in the
+// environment makes image_to_data / images_to_data / the calls above read orientations too (per word).  Items, order and boxes do not change.
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

@@ -31,8 +31,15 @@ enum { TTR_PREC_BF16 = 0, TTR_PREC_F32 = 1, TTR_PREC_F16X4 = 2 };
    32 x 128 - the reference's crop (tuatara.cpp:408-418, :440), bit for bit; the default.  TTR_CROP_RECTIFIED: a word whose rectangle is
    tilted is sampled on its own quadrilateral, deskewed by up to 45 degrees (DESIGN.md "Rectified crops"); axis-aligned words keep the
    reference's crop.  The items, their order and their bboxes are the same in both modes; only text / ids may change.  Text rotated by more
-   than 45 degrees, or upside down, is not recovered (geometry alone cannot tell 90 from 270 degrees, or 0 from 180). */
+   than 45 degrees, or upside down, is recovered only by word orientation (ttr_config.orient below; geometry alone cannot tell 90 from
+   270 degrees, or 0 from 180). */
 enum { TTR_CROP_BOUNDING = 0, TTR_CROP_RECTIFIED = 1 };
+/* ttr_config.orient (DESIGN.md "Word orientation").  TTR_ORIENT_OFF: the default; the same kernels and bits as without the field.
+   TTR_ORIENT_FLIP: every word is also read turned by 180 degrees; TTR_ORIENT_QUARTER: by 90, 180 and 270 degrees.  A turn t is the number
+   of quarter turns clockwise by which the word lies on the page relative to upright.  Each word keeps the reading the recogniser is most sure
+   of (the largest conf; ties to the lower turn).  The items, their order, bbox and quad are those of orient = 0; only text, ids, prob and conf
+   may change.  ttr_config.orient_page = 1 decides once per page (a vote of the words) and reports every word at the page's turn. */
+enum { TTR_ORIENT_OFF = 0, TTR_ORIENT_FLIP = 1, TTR_ORIENT_QUARTER = 2 };
 enum { TTR_ORDER_AS_IS = 0 };  /* channel order: the engine reproduces "swap, detect; swap back, recognise"
                                   (tuatara.cpp:349, :441) relative to whatever the caller passes */
 
@@ -50,6 +57,8 @@ typedef struct ttr_config {
   int max_components;    /* capacity for CCL candidates per page (default 4096) */
   int verbose;           /* 1: the reference's progress lines on stdout (tuatara.cpp:328-329, :342, :386, :421, :434, :488, :509); TUATARA_VERBOSE=1 does the same */
   int crop_mode;         /* TTR_CROP_BOUNDING (default) or TTR_CROP_RECTIFIED (appended last: the fields above keep their offsets) */
+  int orient;            /* TTR_ORIENT_OFF (default), TTR_ORIENT_FLIP or TTR_ORIENT_QUARTER; other values make ttr_create fail */
+  int orient_page;       /* 0 (default): the turn is chosen per word; 1: once per page */
 } ttr_config;
 
 void ttr_config_default(ttr_config* cfg);
@@ -124,6 +133,26 @@ int ttr_results_gather_conf(ttr_result* const* rs, int n, float* conf, float* pr
  * probs).  Takes any ids: ids outside [0, 98) are dropped as ttr_decode_ids drops them.  Outputs may be NULL.  Returns *n_chars, -1 on bad arguments. */
 int ttr_confidence_from_probs(const int32_t* ids, const float* probs, int n_pos, float* char_conf, int* n_chars, float* conf);
 
+/* Word orientation (DESIGN.md "Word orientation"), every entry point but ttr_pages_to_data_dev_sharded (which refuses orient != 0).
+ * ttr_result_orient: the chosen turn of item i, 0..3 (quarter turns clockwise; 0 when orient is off); ttr_result_orients: [count] (NULL
+ * when orient is off or the result is empty).  ttr_result_orient_candidates: K, the candidate turns per word (1 when off, 2 with
+ * TTR_ORIENT_FLIP - turns {0, 2} -, 4 with TTR_ORIENT_QUARTER).  ttr_result_orient_confs: [count][K] the conf of every candidate reading, in
+ * ascending turn order (column 0 is the orient = 0 conf; when off, the same as ttr_result_confs).  ttr_result_page_orient: the page's turn
+ * (the vote; 0 when off), reported in both orient_page modes. */
+int ttr_result_orient(const ttr_result* r, int i);
+const int32_t* ttr_result_orients(const ttr_result* r);
+int ttr_result_orient_candidates(const ttr_result* r);
+const float* ttr_result_orient_confs(const ttr_result* r);
+int ttr_result_page_orient(const ttr_result* r);
+/* ... for a batch of results in one call (any output may be NULL): turns[total], cand_conf[total][K] (K of the results' engine),
+ * page_turns[n], in ttr_results_gather's item order.  Returns the total item count, -1 when the results differ in K. */
+int ttr_results_gather_orient(ttr_result* const* rs, int n, int32_t* turns, float* cand_conf, int32_t* page_turns);
+/* The choice on the host, no GPU: the n words of ONE page, conf[n][k] and ids[n][k][26] of their k candidate readings in ascending turn
+ * order (k = 1: turn {0}; 2: turns {0, 2}; 4: turns {0, 1, 2, 3}) -> turns[n] and *page_turn, as turns 0..3.  Per word: the largest conf,
+ * strict > in ascending turn order.  Page: the argmax of the votes of the words whose winning text has at least 2 characters, ties to the
+ * lower turn, 0 without votes; per_page = 1: every turns[i] = *page_turn.  Returns 0, -1 on bad arguments. */
+int ttr_orient_select(const float* conf, const int32_t* ids, int n, int k, int per_page, int32_t* turns, int32_t* page_turn);
+
 /* ---- multi-GPU: RCCL in the C++ host -----------------------------------------------------------------
  * One process per GPU, one engine per process.  The OCR path has no data-path collective: pages are independent.  The one exchange is
  * the gather of the decoded token ids, and it runs device buffer to device buffer with ncclAllGather (/opt/rocm/include/rccl/rccl.h:678)
@@ -191,6 +220,13 @@ int ttr_pack_crops(ttr_engine* e, const uint8_t* hwc_u8, int h, int w, int row_s
  * receives the quads [n][8] as ttr_result_quad gives them.  A rect whose clamped boundingRect is empty yields a zero crop. */
 int ttr_pack_crops_rectified(ttr_engine* e, const uint8_t* hwc_u8, int h, int w, int row_stride, const float* rects5, int n,
                              float ratio, uint8_t* crops, float* quads_out);
+/* The crop of a word read at `turn` (0..3 quarter turns clockwise), whatever the engine's crop_mode and orient: the same rects and clamp
+ * as ttr_pack_crops.  Turn 0 is ttr_pack_crops's crop (crop_mode 0) or ttr_pack_crops_rectified's (crop_mode 1) bit for bit.  Turn t >= 1
+ * samples the turned quad Q_t[k] = Q[(k + t) mod 4] by the rectified sampler, Q being the deskewed quad (crop_mode 1) or the clamped
+ * boundingRect's pixel edges (crop_mode 0).  quads_out (optional) receives Q_t [n][8].  A rect whose clamped boundingRect is empty yields
+ * a zero crop. */
+int ttr_pack_crops_oriented(ttr_engine* e, const uint8_t* hwc_u8, int h, int w, int row_stride, const float* rects5, int n,
+                            float ratio, int crop_mode, int turn, uint8_t* crops, float* quads_out);
 /* PARSeq forward (tuatara.cpp:443-446 + :307): crops u8 [n][32][128][3] -> logits f32 [n][26][95];
  * ar_logits (optional) receives the autoregressive pass's logits - per crop defined up to and including its EOS step (upstream leaves
  * its loop when every crop has emitted EOS; behind a crop's own EOS the bf16 engine skips it, and zero-fills the steps behind the batch's

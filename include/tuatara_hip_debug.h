@@ -91,6 +91,10 @@ int ttr_dbg_box_geometry(const float* rect5, float ratio, float* adjusted5, int3
 /* the rectified-crop rule on one rect {cx,cy,w,h,angle} in image pixels (geometry.h: deskew_quad): quad8 {tl, tr, br, bl}, coef6
  * {X0, Ax, Bx, Y0, Ay, By} in double, fixed6 the same in int64 units of 2^-16 px.  Returns the crop kind (0 or 1). */
 int ttr_dbg_deskew(const float* rect5, float* quad8, double* coef6, int64_t* fixed6);
+/* word orientation (geometry.h: box_edge_quad / turn_coef) on one rect {cx,cy,w,h,angle} in image pixels of an h x w page: the word's quad Q
+ * (crop_mode 1: the deskewed quad; 0: the clamped boundingRect's pixel edges) turned by `turn` quarter turns, quad8 = Q_t, fixed6 its
+ * coefficients as the engine hands them to pack_crops_rect_kernel.  Returns 0, -1 on bad arguments. */
+int ttr_dbg_orient_quad(const float* rect5, int h, int w, int crop_mode, int turn, float* quad8, int64_t* fixed6);
 
 
 #ifdef __cplusplus

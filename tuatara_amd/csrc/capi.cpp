@@ -32,6 +32,7 @@ void ttr_config_default(ttr_config* c) {
   c->precision = TTR_PREC_F16X4; c->device = 0; c->canvas_size = 1024; c->mag_ratio = 1.0f;
   c->text_threshold = 0.7f; c->link_threshold = 0.4f; c->low_text = 0.4f; c->min_area = 10;
   c->strict_crops = 0; c->max_components = 4096; c->verbose = 0; c->crop_mode = TTR_CROP_BOUNDING;
+  c->orient = TTR_ORIENT_OFF; c->orient_page = 0;
 }
 
 const char* ttr_last_error(void) { return g_last_error.c_str(); }
@@ -154,6 +155,54 @@ int ttr_results_gather_conf(ttr_result* const* rs, int n, float* conf, float* pr
     oc += r.conf.size(); op += r.prob.size();
   }
   return (int)oc;
+}
+
+int ttr_result_orient(const ttr_result* r, int i) { return r && !r->r.orient.empty() ? r->r.orient[(size_t)i] : 0; }
+
+const int32_t* ttr_result_orients(const ttr_result* r) { return r && !r->r.orient.empty() ? r->r.orient.data() : nullptr; }
+
+int ttr_result_orient_candidates(const ttr_result* r) { return r ? r->r.orient_k : 1; }
+
+const float* ttr_result_orient_confs(const ttr_result* r) {   // (off: K = 1, the candidate confs are the confs)
+  if (!r) return nullptr;
+  const std::vector<float>& v = r->r.orient_k > 1 ? r->r.orient_conf : r->r.conf;
+  return v.empty() ? nullptr : v.data();
+}
+
+int ttr_result_page_orient(const ttr_result* r) { return r ? r->r.page_orient : 0; }
+
+int ttr_results_gather_orient(ttr_result* const* rs, int n, int32_t* turns, float* cand_conf, int32_t* page_turns) {
+  if (!rs || n < 0) return -1;
+  int k = 0;
+  for (int i = 0; i < n; ++i) {   // (an empty result - an image that failed - has no candidates to disagree with)
+    if (!rs[i] || rs[i]->r.text.empty()) continue;
+    if (k && rs[i]->r.orient_k != k) return -1;
+    k = rs[i]->r.orient_k;
+  }
+  size_t ot = 0, oc = 0;
+  for (int i = 0; i < n; ++i) {
+    if (page_turns) page_turns[i] = rs[i] ? rs[i]->r.page_orient : 0;
+    if (!rs[i]) continue;
+    const Result& r = rs[i]->r;
+    const size_t cnt = r.text.size();
+    if (turns) {
+      if (r.orient.size() == cnt) { if (cnt) memcpy(turns + ot, r.orient.data(), cnt * 4); }
+      else std::fill(turns + ot, turns + ot + cnt, 0);
+    }
+    const std::vector<float>& cc = r.orient_k > 1 ? r.orient_conf : r.conf;
+    if (cand_conf) {
+      if (cc.size() == cnt * r.orient_k) { if (cnt) memcpy(cand_conf + oc, cc.data(), cc.size() * 4); }
+      else std::fill(cand_conf + oc, cand_conf + oc + cnt * r.orient_k, 0.f);
+    }
+    ot += cnt; oc += cnt * r.orient_k;
+  }
+  return (int)ot;
+}
+
+int ttr_orient_select(const float* conf, const int32_t* ids, int n, int k, int per_page, int32_t* turns, int32_t* page_turn) {
+  if (n < 0 || (k != 1 && k != 2 && k != 4) || !page_turn || (n > 0 && (!conf || !ids || !turns))) return -1;
+  orient_select(conf, ids, n, k, per_page != 0, turns, page_turn);
+  return 0;
 }
 
 void ttr_result_free(ttr_result* r) { delete r; }
@@ -298,6 +347,52 @@ int ttr_pack_crops_rectified(ttr_engine* e, const uint8_t* img, int h, int w, in
   TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
   TTR_HIP_CHECK(hipMemcpyAsync(E.coef_dev.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice, E.stream));
   launch_pack_crops_rect(E.staging_img.as<uint8_t>(), 0, w * 3, h, w, E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_pack_crops_oriented(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const float* rects5, int n, float ratio, int crop_mode, int turn,
+                            uint8_t* crops_out, float* quads_out) {
+  TTR_GUARD_BEGIN
+  if (crop_mode != TTR_CROP_BOUNDING && crop_mode != TTR_CROP_RECTIFIED) throw std::runtime_error("crop_mode must be 0 or 1");
+  if (turn < 0 || turn > 3) throw std::runtime_error("turn must be 0..3");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_pack_crops_oriented");
+  if (n <= 0) return 0;
+  std::vector<int> rects((size_t)n * 5, 0);
+  std::vector<int64_t> coef((size_t)n * 8, 0);
+  for (int i = 0; i < n; ++i) {
+    int* rc = &rects[5 * (size_t)i];
+    const RRect b = stage_crop_rect(rects5 + 5 * i, ratio, h, w, rc);
+    Pt2f q[4], qt[4]; double cf[6]; int64_t fx[6];
+    const int kind = deskew_quad(b, q, cf);                       // Q: the deskewed quad (crop_mode 1) ...
+    if (crop_mode == TTR_CROP_BOUNDING) box_edge_quad(rc[0], rc[1], rc[2], rc[3], q);   // ... or the clamped boundingRect's pixel edges
+    if (turn == 0 && crop_mode == TTR_CROP_RECTIFIED) {           // ttr_pack_crops_rectified's crop
+      coef[8 * i] = kind;
+      deskew_fixed(cf, fx);
+    } else {
+      coef[8 * i] = 1;
+      turn_coef(q, turn, fx);
+    }
+    for (int k = 0; k < 6; ++k) coef[8 * i + 1 + k] = fx[k];
+    for (int k = 0; k < 4; ++k) qt[k] = q[(k + turn) & 3];
+    if (quads_out) for (int k = 0; k < 4; ++k) { quads_out[8 * i + 2 * k] = qt[k].x; quads_out[8 * i + 2 * k + 1] = qt[k].y; }
+  }
+  E.staging_img.ensure((size_t)h * w * 3);
+  E.rects_dev.ensure(rects.size() * 4);
+  E.coef_dev.ensure(coef.size() * 8);
+  E.crops.ensure((size_t)n * 32 * 128 * 3);
+  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
+  if (turn == 0 && crop_mode == TTR_CROP_BOUNDING) {              // ttr_pack_crops's crop
+    launch_pack_crops(E.staging_img.as<uint8_t>(), 0, w * 3, E.rects_dev.as<int>(), E.crops.as<uint8_t>(), n, E.stream);
+  } else {
+    TTR_HIP_CHECK(hipMemcpyAsync(E.coef_dev.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice, E.stream));
+    launch_pack_crops_rect(E.staging_img.as<uint8_t>(), 0, w * 3, h, w, E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
+  }
   TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
   TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
   return 0;

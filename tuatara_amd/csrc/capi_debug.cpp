@@ -441,4 +441,21 @@ int ttr_dbg_deskew(const float* r5, float* quad8, double* coef6, int64_t* fixed6
   TTR_GUARD_END(-1)
 }
 
+int ttr_dbg_orient_quad(const float* r5, int h, int w, int crop_mode, int turn, float* quad8, int64_t* fixed6) {
+  TTR_GUARD_BEGIN
+  if (turn < 0 || turn > 3 || (crop_mode != TTR_CROP_BOUNDING && crop_mode != TTR_CROP_RECTIFIED)) throw std::runtime_error("bad turn or crop_mode");
+  const RRect r{r5[0], r5[1], r5[2], r5[3], r5[4]};
+  Pt2f q[4]; double cf[6];
+  deskew_quad(r, q, cf);
+  if (crop_mode == TTR_CROP_BOUNDING) {
+    int xywh[4];
+    bounding_rect(r, xywh);
+    box_edge_quad(std::max(xywh[0], 0), std::max(xywh[1], 0), std::min(xywh[0] + xywh[2], w), std::min(xywh[1] + xywh[3], h), q);
+  }
+  turn_coef(q, turn, fixed6);
+  for (int k = 0; k < 4; ++k) { quad8[2 * k] = q[(k + turn) & 3].x; quad8[2 * k + 1] = q[(k + turn) & 3].y; }
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 }  // extern "C"

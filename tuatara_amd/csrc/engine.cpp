@@ -397,6 +397,9 @@ void Engine::load_parseq(const std::string& dir) {
 Engine::Engine(const std::string& dir, const ttr_config& c) : cfg(c) {
   { const char* v = getenv("TUATARA_VERBOSE"); verbose = cfg.verbose != 0 || (v && *v && std::string(v) != "0"); }
   if (cfg.crop_mode != TTR_CROP_BOUNDING && cfg.crop_mode != TTR_CROP_RECTIFIED) throw std::runtime_error("crop_mode must be TTR_CROP_BOUNDING (0) or TTR_CROP_RECTIFIED (1)");
+  if (cfg.orient != TTR_ORIENT_OFF && cfg.orient != TTR_ORIENT_FLIP && cfg.orient != TTR_ORIENT_QUARTER)
+    throw std::runtime_error("orient must be TTR_ORIENT_OFF (0), TTR_ORIENT_FLIP (1) or TTR_ORIENT_QUARTER (2)");
+  if (cfg.orient_page != 0 && cfg.orient_page != 1) throw std::runtime_error("orient_page must be 0 (per word) or 1 (per page)");
   prec = cfg.precision == TTR_PREC_F32 ? kF32 : cfg.precision == TTR_PREC_F16X4 ? kSplit : kBF16;
   es = prec == kBF16 ? 2 : 4;
   int ndev = 0;

@@ -262,6 +262,10 @@ struct Result {
   std::vector<float> quad;   // 8 per item: the word's corners tl, tr, br, bl in image pixels (geometry.h: deskew_quad), every crop mode
   std::vector<float> prob;   // 26 per item: softmax probability of each argmax id (decode_conf.hip)
   std::vector<float> conf;   // 1 per item: the word's confidence (DESIGN.md "Recognition confidence")
+  // word orientation (cfg.orient != TTR_ORIENT_OFF; DESIGN.md "Word orientation"): empty when off
+  std::vector<int32_t> orient;      // 1 per item: the chosen turn 0..3
+  std::vector<float> orient_conf;   // orient_k per item: every candidate's conf, ascending turn
+  int orient_k = 1, page_orient = 0;
 };
 
 struct CclBatch {   // device workspaces of the CCL stage for a batch of equally sized pages
@@ -398,6 +402,8 @@ struct Engine {
   int craft_ws_npl = 0;                           // planes per value the split CRAFT workspaces were laid out for
   DevBuf pq_ws[24];
   DevBuf canvas, heat, staging_img, crops, rects_dev, coef_dev, logits, ar_logits, ids_dev, tokens;
+  DevBuf orient_in, orient_cand, orient_side;     // word orientation: the twins' coef | rects | page firsts; their recogniser block; the side block (orient.hip)
+  PinnedBuf h_orient_in[2], h_orient[2];          // ... per slot: staging of orient_in, host copy of the side block
   CclBatch ccl;
   PinnedBuf h_counters, h_cand, h_rows, h_rects_f, h_rects[2], h_coef[2], h_ids[2];   // (h_coef: crop_mode = TTR_CROP_RECTIFIED only)   // pinned staging of the small host <-> device transfers
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -580,11 +586,14 @@ struct Engine {
   // one device-to-host copy and one collective carry all three.  Ensures the buffer (never inside a launch function).
   struct RecOut { int* ids; float* prob; float* conf; };
   static constexpr int kRecWords = 26 + 26 + 1;   // 4-byte words per crop
-  RecOut rec_out(int rows) {
-    ids_dev.ensure((size_t)std::max(rows, 1) * kRecWords * 4);
-    int* b = ids_dev.as<int>();
+  RecOut rec_out(int rows) { return rec_block(ids_dev, rows); }
+  static RecOut rec_block(DevBuf& d, int rows) {
+    d.ensure((size_t)std::max(rows, 1) * kRecWords * 4);
+    int* b = d.as<int>();
     return RecOut{b, reinterpret_cast<float*>(b + (size_t)rows * 26), reinterpret_cast<float*>(b + (size_t)rows * 52)};
   }
+  // word orientation: candidate turns per word (1 = off, 2 = {0, 2}, 4 = {0, 1, 2, 3})
+  int orient_k() const { return cfg.orient == TTR_ORIENT_QUARTER ? 4 : cfg.orient == TTR_ORIENT_FLIP ? 2 : 1; }
 
   // ---- post-processing of one page's heat map: GPU CCL + host calipers
   struct PageBoxes { std::vector<RRect> det; };
@@ -614,6 +623,7 @@ struct Engine {
     std::vector<std::vector<RRect>> boxes;
     std::vector<int> rects, page_of;
     std::vector<int64_t> coef;         // crop_mode = TTR_CROP_RECTIFIED: {kind, X0, Ax, Bx, Y0, Ay, By, 0} per crop, beside rects
+    std::vector<int64_t> twin;         // orient != 0: {1, X0, Ax, Bx, Y0, Ay, By, 0} of the (K - 1) N twin crops, candidate-major (row (j - 1) N + c)
     int N = 0, slot = 0, group = 16;
     int det_groups = -1;               // CRAFT groups enqueued for it (group_ev[det_groups]: behind the copy of its detector range word)
     bool live = false, enqueued = false;
@@ -635,6 +645,9 @@ struct Engine {
   // the crop packer of a batch whose rects / coef are known: copies them through the pinned staging of slot sl and enqueues
   // pack_crops_kernel (crop_mode 0) or pack_crops_rect_kernel (crop_mode 1) into `crops`
   void pack_batch_crops(const PageBatch& B, int sl);
+  // word orientation: the twins' coefficients, rects and the pages' first words through the pinned staging of slot sl (one copy), then
+  // pack_crops_rect_kernel on the (K - 1) N twin rows into `crops` behind the batch's N crops
+  void pack_twin_crops(const PageBatch& B, int sl);
 
   void finish(PageBatch& B, std::vector<Result>& results);
 

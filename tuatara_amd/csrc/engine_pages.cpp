@@ -197,7 +197,9 @@ void Engine::detect_collect_local(PageBatch& B) {
   const float ratio_w = 1.f / B.g.ratio, ratio_h = 1.f / B.g.ratio;   // tuatara.cpp:360-361
   std::vector<std::vector<RRect>> dets(n);
   B.boxes.assign(n, std::vector<RRect>());
-  B.rects.clear(); B.page_of.clear(); B.coef.clear();   // x0,y0,x1,y1,page per crop; page index per crop; rectified crops' coefficients
+  B.rects.clear(); B.page_of.clear(); B.coef.clear(); B.twin.clear();   // x0,y0,x1,y1,page per crop; page index per crop; rectified crops' coefficients; twins'
+  const int K = orient_k();
+  std::vector<Pt2f> oq;                                        // orient != 0: each word's quad Q (DESIGN.md "Word orientation")
   host_us[1] = host_us[2] = host_us[3] = 0.f;
   for (int gi = 0; gi < groups; ++gi) ccl_collect(gi * GP, std::min(GP, n - gi * GP), gi, B.H2, B.W2, dets);
   // the detector's range word of THIS batch, before any of its boxes is used: a saturated heat map fails this batch and no other
@@ -229,15 +231,27 @@ void Engine::detect_collect_local(PageBatch& B) {
       B.boxes[i].push_back(b);
       B.rects.insert(B.rects.end(), {x0, y0, x1, y1, i});
       B.page_of.push_back(i);
+      Pt2f q[4];
       if (cfg.crop_mode == TTR_CROP_RECTIFIED) {                    // DESIGN.md "Rectified crops": same items, other pixels
-        Pt2f q[4]; double cf[6]; int64_t fx[6];
+        double cf[6]; int64_t fx[6];
         const int kind = deskew_quad(b, q, cf);
         deskew_fixed(cf, fx);
         B.coef.insert(B.coef.end(), {(int64_t)kind, fx[0], fx[1], fx[2], fx[3], fx[4], fx[5], 0});
+      } else if (K > 1) {
+        box_edge_quad(x0, y0, x1, y1, q);
       }
+      if (K > 1) oq.insert(oq.end(), q, q + 4);
     }
   }
   B.N = (int)B.page_of.size();
+  for (int j = 1; j < K; ++j) {                                 // the twins, candidate-major in ascending turn
+    const int t = K == 2 ? 2 * j : j;
+    for (int c = 0; c < B.N; ++c) {
+      int64_t fx[6];
+      turn_coef(&oq[4 * (size_t)c], t, fx);
+      B.twin.insert(B.twin.end(), {(int64_t)1, fx[0], fx[1], fx[2], fx[3], fx[4], fx[5], 0});
+    }
+  }
 }
 
 void Engine::pack_batch_crops(const PageBatch& B, int sl) {
@@ -257,6 +271,25 @@ void Engine::pack_batch_crops(const PageBatch& B, int sl) {
   launch_pack_crops_rect(B.d_pages, B.page_bytes, B.w * 3, B.h, B.w, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), B.N, stream);
 }
 
+void Engine::pack_twin_crops(const PageBatch& B, int sl) {
+  const int N = B.N, T = (int)(B.twin.size() / 8);
+  if (T != (orient_k() - 1) * N) throw std::runtime_error("word orientation: twin count does not match the crop count");
+  // orient_in: coef int64 [T][8] | rects int32 [T][5] (row (j - 1) N + c = the word's rects row) | first int32 [pages + 1]
+  const size_t coef_b = (size_t)T * 64, rect_b = (size_t)T * 20, first_b = (size_t)(B.n + 1) * 4;
+  h_orient_in[sl].ensure(coef_b + rect_b + first_b);
+  orient_in.ensure(coef_b + rect_b + first_b);
+  uint8_t* h = h_orient_in[sl].as<uint8_t>();
+  memcpy(h, B.twin.data(), coef_b);
+  for (int r = 0; r < T; ++r) memcpy(h + coef_b + (size_t)r * 20, &B.rects[(size_t)(r % N) * 5], 20);
+  int32_t* first = reinterpret_cast<int32_t*>(h + coef_b + rect_b);
+  std::fill(first, first + B.n + 1, 0);
+  for (int c = 0; c < N; ++c) first[B.page_of[c] + 1]++;
+  for (int pg = 0; pg < B.n; ++pg) first[pg + 1] += first[pg];
+  TTR_HIP_CHECK(hipMemcpyAsync(orient_in.p, h, coef_b + rect_b + first_b, hipMemcpyHostToDevice, stream));
+  launch_pack_crops_rect(B.d_pages, B.page_bytes, B.w * 3, B.h, B.w, reinterpret_cast<const int*>(orient_in.as<uint8_t>() + coef_b), orient_in.as<int64_t>(),
+                         crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, stream);
+}
+
 void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
   range_use(kRangeRec0 + (sl & 1));          // the recogniser's kernels of this batch watch the slot's own word
@@ -266,13 +299,25 @@ void Engine::recog_enqueue(PageBatch& B) {
   const RecOut out = rec_out(B.rows);
   TTR_HIP_CHECK(hipEventRecord(evr[sl][0], stream));
   if (N > 0) {
-    crops.ensure((size_t)N * 32 * 128 * 3);
-    logits.ensure((size_t)N * 26 * 95 * 4);
+    const int K = orient_k(), T = (K - 1) * N;                 // word orientation: T twin crops behind the batch's N (DESIGN.md "Word orientation")
+    crops.ensure((size_t)(N + T) * 32 * 128 * 3);
+    logits.ensure((size_t)std::max(N, T) * 26 * 95 * 4);
+    const RecOut cand = T ? rec_block(orient_cand, T) : RecOut{};
+    const size_t side_b = ((size_t)N * (K + 1) + B.n) * 4;   // [N] turn | [N][K] candidate conf | [pages] page turn
+    if (T) { orient_side.ensure(side_b); h_orient[sl].ensure(side_b); }
     pack_batch_crops(B, sl);
+    if (T) pack_twin_crops(B, sl);
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf);
+    if (T) {   // the twins as a pass of their own (turn 0 keeps its batch, and with it its bits), then the choice, in place in the standard block
+      parseq_forward(crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, logits.as<float>(), nullptr, cand.ids, cand.prob, cand.conf);
+      const size_t first_off = (size_t)T * 84;
+      launch_orient_select(out.ids, out.prob, out.conf, cand.ids, cand.prob, cand.conf, reinterpret_cast<const int*>(orient_in.as<uint8_t>() + first_off), B.n, N, K,
+                           cfg.orient_page, orient_side.as<int>(), stream);
+    }
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
     TTR_HIP_CHECK(hipMemcpyAsync(h_ids[sl].p, ids_dev.p, block, hipMemcpyDeviceToHost, stream));   // ids, prob and conf in one copy
+    if (T) TTR_HIP_CHECK(hipMemcpyAsync(h_orient[sl].p, orient_side.p, side_b, hipMemcpyDeviceToHost, stream));
   } else {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
@@ -319,6 +364,10 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   const int32_t* ids = h_ids[B.slot].as<int32_t>();
   const float* prob = reinterpret_cast<const float*>(ids + (size_t)B.rows * 26);
   const float* conf = reinterpret_cast<const float*>(ids + (size_t)B.rows * 52);
+  const int K = orient_k();
+  const int32_t* o_turn = K > 1 && N > 0 ? h_orient[B.slot].as<int32_t>() : nullptr;   // the side block (orient.hip)
+  const float* o_conf = o_turn ? reinterpret_cast<const float*>(o_turn + N) : nullptr;
+  const int32_t* o_page = o_turn ? o_turn + (size_t)N * (K + 1) : nullptr;
   // crops are ordered by page: page pg owns crops [first[pg], first[pg + 1]); pages decode independently
   std::vector<int> first(n + 1, 0);
   for (int c = 0; c < N; ++c) first[B.page_of[c] + 1]++;
@@ -330,6 +379,14 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
     r.ids.assign(&ids[(size_t)c0 * 26], &ids[(size_t)(c0 + cnt) * 26]);
     r.prob.assign(&prob[(size_t)c0 * 26], &prob[(size_t)(c0 + cnt) * 26]);
     r.conf.assign(&conf[c0], &conf[c0 + cnt]);
+    if (K > 1) {
+      r.orient_k = K;
+      if (o_turn) {
+        r.orient.assign(&o_turn[c0], &o_turn[c0 + cnt]);
+        r.orient_conf.assign(&o_conf[(size_t)c0 * K], &o_conf[(size_t)(c0 + cnt) * K]);
+        r.page_orient = o_page[pg];
+      }
+    }
     for (int k = 0; k < cnt; ++k) {
       r.text.push_back(tok.decode(&ids[(size_t)(c0 + k) * 26], 26));   // :486-505
       float bb[4];
@@ -370,6 +427,7 @@ void Engine::run_pages(const uint8_t* d_pages, int n, int h, int w, std::vector<
 
 void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results) {
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");
+  if (cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("latency mode does not support word orientation: create the engine with orient = TTR_ORIENT_OFF");
   if (q1.live || q2.live) throw std::runtime_error("streamed batches are in flight: call ttr_stream_flush until it returns none");
   Comm* const c = comm;
   const int world = c->world, rank = c->rank;

@@ -69,6 +69,11 @@ int deskew_quad(const RRect& r, Pt2f quad[4], double coef[6]) {
     if (len_m > len_s) s = (s + 3) & 3;
   }
   for (int i = 0; i < 4; ++i) quad[i] = p[(s + i) & 3];
+  quad_coef(quad, coef);
+  return std::isfinite(a) && std::fmod(a, 90.) == 0. ? 0 : 1;
+}
+
+void quad_coef(const Pt2f quad[4], double coef[6]) {
   // A = tr - tl, B = bl - tl; X0 = tl.x + 0.5 A.x / 128 + 0.5 B.x / 32, left to right, one statement per rounding (no contraction)
   const double Ax = ((double)quad[1].x - (double)quad[0].x) / 128., Bx = ((double)quad[3].x - (double)quad[0].x) / 32.;
   const double Ay = ((double)quad[1].y - (double)quad[0].y) / 128., By = ((double)quad[3].y - (double)quad[0].y) / 32.;
@@ -77,11 +82,48 @@ int deskew_quad(const RRect& r, Pt2f quad[4], double coef[6]) {
   double y0 = (double)quad[0].y + 0.5 * Ay;
   y0 = y0 + 0.5 * By;
   coef[0] = x0; coef[1] = Ax; coef[2] = Bx; coef[3] = y0; coef[4] = Ay; coef[5] = By;
-  return std::isfinite(a) && std::fmod(a, 90.) == 0. ? 0 : 1;
 }
 
 void deskew_fixed(const double coef[6], int64_t fixed[6]) {
   for (int i = 0; i < 6; ++i) fixed[i] = (int64_t)std::llrint(coef[i] * 65536.);
+}
+
+// ---------------------------------------------------------------- word orientation (DESIGN.md "Word orientation")
+void box_edge_quad(int x0, int y0, int x1, int y1, Pt2f quad[4]) {
+  const float l = (float)x0 - 0.5f, t = (float)y0 - 0.5f, r = (float)x1 - 0.5f, b = (float)y1 - 0.5f;
+  quad[0] = Pt2f{l, t}; quad[1] = Pt2f{r, t}; quad[2] = Pt2f{r, b}; quad[3] = Pt2f{l, b};
+}
+
+void turn_coef(const Pt2f quad[4], int turn, int64_t fixed[6]) {
+  Pt2f q[4];
+  for (int k = 0; k < 4; ++k) q[k] = quad[(k + turn) & 3];
+  double cf[6];
+  quad_coef(q, cf);
+  deskew_fixed(cf, fixed);
+}
+
+static int text_chars(const int32_t* ids) {   // |S| of the confidence rule: characters before the first EOS (id 0), id 88 and ids outside [0, 98) dropped
+  int k = 0;
+  for (int p = 0; p < 26; ++p) {
+    if (ids[p] == 0) break;
+    if (ids[p] != 88 && ids[p] >= 0 && ids[p] < 98) ++k;
+  }
+  return k;
+}
+
+void orient_select(const float* conf, const int32_t* ids, int n, int k, int per_page, int32_t* turns, int32_t* page_turn) {
+  int votes[4] = {0, 0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    int best = 0;
+    for (int j = 1; j < k; ++j) if (conf[(size_t)i * k + j] > conf[(size_t)i * k + best]) best = j;
+    turns[i] = best;
+    if (text_chars(ids + ((size_t)i * k + best) * 26) >= 2) ++votes[best];
+  }
+  int pt = 0;
+  for (int j = 1; j < k; ++j) if (votes[j] > votes[pt]) pt = j;
+  const int step = k == 2 ? 2 : 1;   // candidate column -> turn
+  for (int i = 0; i < n; ++i) turns[i] = step * (per_page ? pt : turns[i]);
+  *page_turn = step * pt;
 }
 
 // ---------------------------------------------------------------- convex hull (monotone chain, exact on integer-valued input)

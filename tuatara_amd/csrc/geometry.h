@@ -28,6 +28,20 @@ RRect adjust_coordinates(const RRect& r, float ratio_w, float ratio_h, float rat
 int deskew_quad(const RRect& r, Pt2f quad[4], double coef[6]);
 // the coefficients as the kernel takes them: llrint to int64 in units of 2^-16 px
 void deskew_fixed(const double coef[6], int64_t fixed[6]);
+// the quad -> coefficients step of deskew_quad on its own (any quad tl, tr, br, bl): the sampler's rule in double, in deskew_quad's order
+void quad_coef(const Pt2f quad[4], double coef[6]);
+
+// Word orientation (ttr_config.orient; DESIGN.md "Word orientation").  A turn t = the quarter turns clockwise by which the word lies on the
+// page.  box_edge_quad: the crop_mode = 0 quad of a clamped boundingRect [x0, x1) x [y0, y1) as pixel edges (rect_points' coordinates:
+// pixel centres at integers).  turn_coef: the fixed-point coefficients of the turned quad Q_t[k] = Q[(k + t) mod 4] (quad_coef +
+// deskew_fixed), sampled by the kind-1 rule.
+void box_edge_quad(int x0, int y0, int x1, int y1, Pt2f quad[4]);
+void turn_coef(const Pt2f quad[4], int turn, int64_t fixed[6]);
+// The choice between the k candidate readings of n words of one page (orient_select_kernel, orient.hip, makes the same choice): conf [n][k],
+// ids [n][k][26], candidates in ascending turn order ({0}, {0, 2} or {0, 1, 2, 3}) -> turns[n], *page_turn as turns 0..3.  Per word: the
+// largest conf, strict > in ascending order.  Page: argmax of the votes of the words whose winning text has >= 2 characters (|S| of the
+// confidence rule), ties to the lower turn, 0 without votes; per_page: every turn = it.
+void orient_select(const float* conf, const int32_t* ids, int n, int k, int per_page, int32_t* turns, int32_t* page_turn);
 
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.

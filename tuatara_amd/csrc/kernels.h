@@ -197,6 +197,11 @@ void launch_fill_i32(int* p, int value, int n, int stride, hipStream_t s);
 // decode_conf.hip: the refinement pass's final decode - logits f32 [N][26][95] -> ids [N][26] (bit-identical to launch_argmax's), prob f32 [N][26]
 // (softmax value of each id), conf f32 [N] (product over the text's characters and the EOS; DESIGN.md "Recognition confidence")
 void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s);
+// orient.hip: word orientation (DESIGN.md "Word orientation") - per page, the chosen candidate of every word and the page vote.  ids / prob / conf: the
+// standard block of the batch (turn 0), overwritten in place with the chosen readings; cids / cprob / cconf: the (K - 1) N twin rows, candidate-major;
+// first [pages + 1]: each page's first word; side: [N] int32 turn | [N][K] f32 candidate conf | [pages] int32 page turn.  K = 2 or 4.
+void launch_orient_select(int* ids, float* prob, float* conf, const int* cids, const float* cprob, const float* cconf, const int* first, int pages, int N,
+                          int K, int per_page, int* side, hipStream_t s);
 
 // ---- mlp_fused.hip: x_out = x + fc2(GELU(fc1(LayerNorm(x)))) [+ y = LayerNorm_next(x_out)] for the ViT encoder blocks (bf16, E = 384)
 struct MlpParams {

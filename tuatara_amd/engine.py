@@ -19,12 +19,14 @@ _lib = None
 
 PREC_BF16, PREC_F32, PREC_F16X4 = 0, 1, 2
 CROP_BOUNDING, CROP_RECTIFIED = 0, 1
+ORIENT_OFF, ORIENT_FLIP, ORIENT_QUARTER = 0, 1, 2
 
 
 class Config(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("canvas_size", C.c_int), ("mag_ratio", C.c_float),
                 ("text_threshold", C.c_float), ("link_threshold", C.c_float), ("low_text", C.c_float), ("min_area", C.c_int),
-                ("strict_crops", C.c_int), ("max_components", C.c_int), ("verbose", C.c_int), ("crop_mode", C.c_int)]
+                ("strict_crops", C.c_int), ("max_components", C.c_int), ("verbose", C.c_int), ("crop_mode", C.c_int),
+                ("orient", C.c_int), ("orient_page", C.c_int)]
 
 
 # every symbol include/tuatara_hip.h declares: (name, restype, argtypes)
@@ -51,6 +53,13 @@ SYMBOLS = [
     ("ttr_result_prob", _PF, [_VP, _I]),
     ("ttr_result_confs", _PF, [_VP]),
     ("ttr_result_probs_all", _PF, [_VP]),
+    ("ttr_result_orient", _I, [_VP, _I]),
+    ("ttr_result_orients", _PI, [_VP]),
+    ("ttr_result_orient_candidates", _I, [_VP]),
+    ("ttr_result_orient_confs", _PF, [_VP]),
+    ("ttr_result_page_orient", _I, [_VP]),
+    ("ttr_results_gather_orient", _I, [C.POINTER(_VP), _I, _PI, _PF, _PI]),
+    ("ttr_orient_select", _I, [_PF, _PI, _I, _I, _I, _PI, _PI]),
     ("ttr_result_free", None, [_VP]),
     ("ttr_result_bboxes", _PF, [_VP]),
     ("ttr_result_ids_all", _PI, [_VP]),
@@ -64,6 +73,7 @@ SYMBOLS = [
     ("ttr_resize_canvas", _I, [_VP, _PU8, _I, _I, _I, _PU8, C.c_size_t, _PI, _PI, _PF]),
     ("ttr_pack_crops", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _F, _PU8, _PF]),
     ("ttr_pack_crops_rectified", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _F, _PU8, _PF]),
+    ("ttr_pack_crops_oriented", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _F, _I, _I, _PU8, _PF]),
     ("ttr_parseq_logits", _I, [_VP, _PU8, _I, _PF, _PF, _PI]),
     ("ttr_decode_ids", _I, [_PI, _I, C.c_char_p]),
     ("ttr_engine_set_tuning", _I, [_VP, C.c_char_p, _I]),
@@ -73,6 +83,7 @@ SYMBOLS = [
     ("ttr_dbg_component_rect", _I, [_I, _I, _I, _I, _I, _PI, _I, _I, _PF]),
     ("ttr_dbg_box_geometry", _I, [_PF, _F, _PF, _PI, _PF]),
     ("ttr_dbg_deskew", _I, [_PF, _PF, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    ("ttr_dbg_orient_quad", _I, [_PF, _I, _I, _I, _I, _PF, C.POINTER(C.c_int64)]),
     ("ttr_dev_alloc", _VP, [C.c_size_t]),
     ("ttr_dev_free", None, [_VP]),
     ("ttr_dev_upload", _I, [_VP, _VP, C.c_size_t]),
@@ -198,6 +209,16 @@ def deskew(rect5):
     return kind, quad.reshape(4, 2), coef, fixed
 
 
+def orient_quad(rect5, h: int, w: int, crop_mode: int, turn: int):
+    """Engine host geometry (no GPU): a word's quad turned by `turn` quarter turns and its fixed-point coefficients, as the engine forms its
+    twin crops (ttr_dbg_orient_quad) -> (quad f32 [4,2] = Q_t, fixed int64 [6])."""
+    r = np.ascontiguousarray(rect5, dtype=np.float32)
+    quad, fixed = np.zeros(8, np.float32), np.zeros(6, np.int64)
+    if load().ttr_dbg_orient_quad(_f(r), int(h), int(w), int(crop_mode), int(turn), _f(quad), fixed.ctypes.data_as(C.POINTER(C.c_int64))) != 0:
+        raise EngineError(load().ttr_last_error().decode())
+    return quad.reshape(4, 2), fixed
+
+
 def confidence_from_probs(ids, probs):
     """The confidence rule on the host (ttr_confidence_from_probs, no GPU): ids / probs of one row -> (char_conf f32 [len(text)], conf f32)."""
     ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
@@ -209,6 +230,18 @@ def confidence_from_probs(ids, probs):
     if load().ttr_confidence_from_probs(_i(ids), _f(probs), len(ids), _f(cc), C.byref(nc), C.byref(conf)) < 0:
         raise EngineError("ttr_confidence_from_probs: bad arguments")
     return cc[:nc.value].copy(), np.float32(conf.value)
+
+
+def orient_select(conf, ids, per_page: bool = False):
+    """The orientation choice on the host (ttr_orient_select, no GPU): one page's conf f32 [n, k] and ids i32 [n, k, 26] of k candidate
+    readings in ascending turn order (k = 2: turns 0, 2; k = 4: turns 0..3) -> (turns i32 [n] as 0..3, page turn)."""
+    conf = np.ascontiguousarray(conf, dtype=np.float32)
+    n, k = conf.shape
+    ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(n, k, 26)
+    turns, pt = np.zeros(max(n, 1), np.int32), C.c_int32()
+    if load().ttr_orient_select(_f(conf), _i(ids), n, k, int(per_page), _i(turns), C.byref(pt)) != 0:
+        raise EngineError("ttr_orient_select: bad arguments")
+    return turns[:n].copy(), int(pt.value)
 
 
 def _add_conf(d: dict, conf, prob) -> dict:
@@ -228,15 +261,18 @@ class PageResult(collections.abc.Sequence):
     """One page's words as the list of {"text", "bbox", "ids"} dicts pytuatara.image_to_data returns, materialised on access:
     the batch hand-over keeps the arrays the C ABI filled (`texts`, `bbox` f32 [n,4], `ids` i32 [n,26]; `quad` f32 [n,8] in the
     rectified crop mode, else None; `conf` f32 [n] and `prob` f32 [n,26] always) and builds dicts only for the items a caller touches.
-    with_conf: the dicts carry "conf" and "char_conf" too (DESIGN.md "Recognition confidence")."""
-    __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf")
+    with_conf: the dicts carry "conf" and "char_conf" too (DESIGN.md "Recognition confidence").  Word orientation (orient != 0; DESIGN.md
+    "Word orientation"): `orient` i32 [n] the chosen turns 0..3 (dicts gain "orient" in degrees), `orient_conf` f32 [n, K] every candidate's
+    conf in ascending turn order, `page_orient` the page's turn; None / None / 0 when orientation is off."""
+    __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient")
 
-    def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False):
+    def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0):
         self.texts, self.bbox, self.ids, self.quad = texts, bbox, ids, quad
         n = len(texts)
         self.conf = conf if conf is not None else np.zeros(n, np.float32)
         self.prob = prob if prob is not None else np.zeros((n, 26), np.float32)
         self.with_conf = with_conf
+        self.orient, self.orient_conf, self.page_orient = orient, orient_conf, page_orient
 
     def __len__(self):
         return len(self.texts)
@@ -253,6 +289,8 @@ class PageResult(collections.abc.Sequence):
             d["quad"] = _quad_pairs(self.quad[j])
         if self.with_conf:
             _add_conf(d, self.conf[j], self.prob[j])
+        if self.orient is not None:
+            d["orient"] = 90 * int(self.orient[j])
         return d
 
     def __eq__(self, other):
@@ -342,6 +380,16 @@ class Engine:
         """crop_mode = CROP_RECTIFIED: result dicts carry "quad" (4 [x, y] corners tl, tr, br, bl)"""
         return self.cfg.crop_mode == CROP_RECTIFIED
 
+    @property
+    def orienting(self) -> bool:
+        """orient != ORIENT_OFF: result dicts carry "orient" (the chosen turn in degrees clockwise: 0, 90, 180 or 270)"""
+        return self.cfg.orient != ORIENT_OFF
+
+    @property
+    def orient_candidates(self) -> int:
+        """K, the candidate turns per word: 1 (off), 2 (ORIENT_FLIP: 0, 180) or 4 (ORIENT_QUARTER)"""
+        return {ORIENT_FLIP: 2, ORIENT_QUARTER: 4}.get(self.cfg.orient, 1)
+
     def _quads(self, r, n: int) -> np.ndarray:
         return np.ctypeslib.as_array(self.lib.ttr_result_quads(r), (n, 8)).copy() if n else np.zeros((0, 8), np.float32)
 
@@ -366,6 +414,9 @@ class Engine:
                 pr = np.ctypeslib.as_array(self.lib.ttr_result_probs_all(r), (n, 26)).copy()
                 for d, c, p in zip(out, cf, pr):
                     _add_conf(d, c, p)
+            if self.orienting:
+                for d, t in zip(out, np.ctypeslib.as_array(self.lib.ttr_result_orients(r), (n,)).tolist()):
+                    d["orient"] = 90 * t
         self.lib.ttr_result_free(r)
         return out
 
@@ -383,11 +434,17 @@ class Engine:
         cf = np.zeros(max(total, 1), np.float32)
         pr = np.zeros((max(total, 1), 26), np.float32)
         self.lib.ttr_results_gather_conf(arr, n, _f(cf), _f(pr))
+        if self.orienting:                      # the chosen turns, every candidate's conf and the page turns, one call
+            K = self.orient_candidates
+            ot, oc, op = np.zeros(max(total, 1), np.int32), np.zeros((max(total, 1), K), np.float32), np.zeros(max(n, 1), np.int32)
+            if self.lib.ttr_results_gather_orient(arr, n, _i(ot), _f(oc), _i(op)) < 0:
+                raise EngineError("ttr_results_gather_orient: the results differ in their candidate count")
         out, k = [], 0
         for i in range(n):
             c = int(counts[i])
+            orient = (ot[k:k + c], oc[k:k + c], int(op[i])) if self.orienting else (None, None, 0)
             out.append(PageResult(texts[k:k + c], bb[k:k + c], ids[k:k + c], self._quads(arr[i], c) if self.rectified else None,
-                                  cf[k:k + c], pr[k:k + c], conf))
+                                  cf[k:k + c], pr[k:k + c], conf, *orient))
             k += c
             self.lib.ttr_result_free(arr[i])
         return out
@@ -584,6 +641,18 @@ class Engine:
         quads = np.zeros((n, 4, 2), np.float32)
         self._check(self.lib.ttr_pack_crops_rectified(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _f(rects), n,
                                                       C.c_float(ratio), _u8(crops), _f(quads)))
+        return crops, quads
+
+    def pack_crops_oriented(self, image: np.ndarray, rects: np.ndarray, ratio: float, crop_mode: int, turn: int):
+        """ttr_pack_crops_oriented: the crops of heat-map rects read at `turn` quarter turns clockwise -> (crops u8 [n,32,128,3], turned quads
+        f32 [n,4,2]).  Turn 0 is pack_crops (crop_mode 0) / pack_crops_rectified (crop_mode 1)."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        rects = np.ascontiguousarray(rects, dtype=np.float32).reshape(-1, 5)
+        n = len(rects)
+        crops = np.zeros((n, 32, 128, 3), np.uint8)
+        quads = np.zeros((n, 4, 2), np.float32)
+        self._check(self.lib.ttr_pack_crops_oriented(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _f(rects), n,
+                                                     C.c_float(ratio), int(crop_mode), int(turn), _u8(crops), _f(quads)))
         return crops, quads
 
     def parseq_logits(self, crops: np.ndarray, want_ar: bool = False):
