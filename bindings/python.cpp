@@ -28,12 +28,6 @@ static py::list quad_pairs(const std::vector<float>& q) {
 
 struct Keys { bool quad = false, conf = false, orient = false; };   // the optional keys of an OutputItemEx's dict
 
-static py::dict item_dict(const OutputItem& item, Keys = Keys()) {
-  py::dict d;
-  d["text"] = item.text;
-  d["bbox"] = item.bbox;
-  return d;
-}
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
   d["text"] = item.text;
@@ -62,41 +56,22 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   py::buffer_info buf = image.request();
   if (buf.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
   if (buf.shape[2] != 3) throw std::runtime_error("Input array should have 3 channels");
+  const uint8_t* data = static_cast<const uint8_t*>(buf.ptr);
   const int rows = (int)buf.shape[0], cols = (int)buf.shape[1];
-  py::list result;
-  if (rectify || conf || orient) {
-    std::vector<OutputItemEx> items;
-    {
-      py::gil_scoped_release nogil;
-      items = orient ? image_to_data_ex(static_cast<const uint8_t*>(buf.ptr), rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
-                     : image_to_data_ex(static_cast<const uint8_t*>(buf.ptr), rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
-    }
-    for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0}));
-    return result;
-  }
-  std::vector<OutputItem> items;
+  std::vector<OutputItemEx> items;
   {
-    py::gil_scoped_release nogil;
-    items = image_to_data(static_cast<const uint8_t*>(buf.ptr), rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir);
+    py::gil_scoped_release nogil;   // (orient = None: the 7-argument call, which leaves the orientation to TUATARA_ORIENT)
+    items = orient ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
+                   : image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
   }
-  for (const auto& item : items) result.append(item_dict(item));
+  py::list result;
+  for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0}));
   return result;
 }
 
 // pytuatara.images_to_data(images, weights_dir, outputs_dir) -> list (one entry per image, input order) of the lists image_to_data returns.
 // images: a sequence of uint8 arrays [H, W, 3] of any sizes.  What a caller of the reference writes as a loop over image_to_data (bindings/run_ocr.py:92),
 // on one cached engine: same-sized images travel as batches, the host-to-device copies run beside the GPU's work, the GIL is released meanwhile.
-template <class Item>
-static py::list pages_list(const std::vector<std::vector<Item>>& pages, Keys k = Keys()) {
-  py::list result;
-  for (const auto& items : pages) {
-    py::list page;
-    for (const auto& item : items) page.append(item_dict(item, k));
-    result.append(page);
-  }
-  return result;
-}
-
 static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf, py::object orient_kw,
                                        bool orient_page) {
   const int orient = orient_mode(orient_kw);
@@ -111,20 +86,18 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
     views.push_back(ImageView{static_cast<const uint8_t*>(buf.ptr), (int)buf.shape[0], (int)buf.shape[1], (std::ptrdiff_t)buf.shape[1] * 3});
     keep.push_back(std::move(a));
   }
-  if (rectify || conf || orient) {
-    std::vector<std::vector<OutputItemEx>> pages;
-    {
-      py::gil_scoped_release nogil;
-      pages = orient ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient, orient_page) : images_to_data_ex(views, weights_dir, output_dir, rectify);
-    }
-    return pages_list(pages, Keys{rectify, conf, orient != 0});
-  }
-  std::vector<std::vector<OutputItem>> pages;
+  std::vector<std::vector<OutputItemEx>> pages;
   {
     py::gil_scoped_release nogil;
-    pages = images_to_data(views, weights_dir, output_dir);
+    pages = orient ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient, orient_page) : images_to_data_ex(views, weights_dir, output_dir, rectify);
   }
-  return pages_list(pages);
+  py::list result;
+  for (const auto& items : pages) {
+    py::list page;
+    for (const auto& item : items) page.append(item_dict(item, Keys{rectify, conf, orient != 0}));
+    result.append(page);
+  }
+  return result;
 }
 
 PYBIND11_MODULE(pytuatara, m) {

@@ -9,10 +9,14 @@ thread_local std::string g_last_error;
 
 using namespace ttr;
 
+void hand_out(std::vector<Result>& results, int n, ttr_result** out) {
+  for (int i = 0; i < n; ++i) { out[i] = new ttr_result(); out[i]->r = std::move(results[i]); }
+}
+
 static void run_locked(ttr_engine* e, const uint8_t* d_pages, int n, int h, int w, ttr_result** out) {
   std::vector<Result> res;
   e->e->run_pages(d_pages, n, h, w, res);
-  for (int i = 0; i < n; ++i) { out[i] = new ttr_result(); out[i]->r = std::move(res[i]); }
+  hand_out(res, n, out);
 }
 
 // the stage entry points' crop rectangle of one heat-map rect: adjust_result_coordinates + boundingRect, clamped to the image (tuatara.cpp:406-418)
@@ -69,7 +73,7 @@ int ttr_stream_push(ttr_engine* e, const uint8_t* d_pages, int n, int h, int w, 
   std::vector<Result> res;
   int np = 0;
   e->e->stream_push(d_pages, n, h, w, res, np);
-  for (int i = 0; i < np; ++i) { out_prev[i] = new ttr_result(); out_prev[i]->r = std::move(res[i]); }
+  hand_out(res, np, out_prev);
   *n_prev = np;
   return 0;
   TTR_GUARD_END(-1)
@@ -82,7 +86,7 @@ int ttr_stream_flush(ttr_engine* e, ttr_result** out_prev, int* n_prev) {
   std::vector<Result> res;
   int np = 0;
   e->e->stream_flush(res, np);
-  for (int i = 0; i < np; ++i) { out_prev[i] = new ttr_result(); out_prev[i]->r = std::move(res[i]); }
+  hand_out(res, np, out_prev);
   *n_prev = np;
   return 0;
   TTR_GUARD_END(-1)
@@ -112,7 +116,7 @@ int ttr_images_to_data(ttr_engine* e, const uint8_t* const* images, const int* h
   std::vector<int> failed;
   std::string first;
   E.run_images(imgs, res, failed, first);
-  for (int i = 0; i < n; ++i) { out[i] = new ttr_result(); out[i]->r = std::move(res[i]); }
+  hand_out(res, n, out);
   if (!failed.empty()) {   // partial failure: every other image's result stands; the failed ones are empty (header)
     std::string msg = std::to_string(failed.size()) + " of " + std::to_string(n) + " images failed (indices";
     for (size_t k = 0; k < failed.size() && k < 16; ++k) msg += " " + std::to_string(failed[k]);

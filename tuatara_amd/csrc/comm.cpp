@@ -387,7 +387,7 @@ int ttr_pages_to_data_dev_sharded(ttr_comm* c, const uint8_t* d_pages, int n, in
   std::vector<Result> res;
   try { E.run_pages_sharded(d_pages, n, h, w, res); } catch (...) { E.comm = keep; throw; }
   E.comm = keep;
-  for (size_t i = 0; i < res.size(); ++i) { out[i] = new ttr_result(); out[i]->r = std::move(res[i]); }
+  hand_out(res, (int)res.size(), out);
   return (int)res.size();
   TTR_GUARD_END(-1)
 }

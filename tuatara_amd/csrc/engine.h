@@ -586,11 +586,18 @@ struct Engine {
   // one device-to-host copy and one collective carry all three.  Ensures the buffer (never inside a launch function).
   struct RecOut { int* ids; float* prob; float* conf; };
   static constexpr int kRecWords = 26 + 26 + 1;   // 4-byte words per crop
+  static constexpr int kLogitWords = 26 * 95;     // 4-byte words of a crop's logits
   RecOut rec_out(int rows) { return rec_block(ids_dev, rows); }
   static RecOut rec_block(DevBuf& d, int rows) {
     d.ensure((size_t)std::max(rows, 1) * kRecWords * 4);
     int* b = d.as<int>();
     return RecOut{b, reinterpret_cast<float*>(b + (size_t)rows * 26), reinterpret_cast<float*>(b + (size_t)rows * 52)};
+  }
+  // the host's view of such a block of `rows` rows, as it lands in h_ids[slot] or as rank r's share of h_gath[slot]
+  struct RecRows { const int32_t* ids; const float* prob; const float* conf; };
+  static RecRows rec_rows(const void* block, int rows) {
+    const int32_t* b = static_cast<const int32_t*>(block);
+    return RecRows{b, reinterpret_cast<const float*>(b + (size_t)rows * 26), reinterpret_cast<const float*>(b + (size_t)rows * 52)};
   }
   // word orientation: candidate turns per word (1 = off, 2 = {0, 2}, 4 = {0, 1, 2, 3})
   int orient_k() const { return cfg.orient == TTR_ORIENT_QUARTER ? 4 : cfg.orient == TTR_ORIENT_FLIP ? 2 : 1; }
@@ -650,6 +657,9 @@ struct Engine {
   void pack_twin_crops(const PageBatch& B, int sl);
 
   void finish(PageBatch& B, std::vector<Result>& results);
+  // results[pg] for every page of B from its boxes and the decoded rows of its crops (crop c is row c); side: the orientation side block
+  // of the batch (orient.hip) or null
+  void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, std::vector<Result>& results);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it
@@ -690,6 +700,8 @@ struct Engine {
 // ---- shared by the C ABI translation units
 struct ttr_engine { std::unique_ptr<ttr::Engine> e; };
 struct ttr_result { ttr::Result r; };
+// the C ABI's hand-over of results[0, n) to the caller: out[i] owns results[i] (ttr_result_free)
+void hand_out(std::vector<ttr::Result>& results, int n, ttr_result** out);
 
 // Every entry point: the engine's lock, and the engine's device made current for the calling thread (HIP's current device is per
 // thread: allocations, hipFuncSetAttribute and device queries inside the call must hit the device the stream belongs to).

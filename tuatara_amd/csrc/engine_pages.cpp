@@ -12,6 +12,32 @@ static void push_quad(const RRect& b, std::vector<float>& quad) {   // Result::q
   for (int i = 0; i < 4; ++i) { quad.push_back(q[i].x); quad.push_back(q[i].y); }
 }
 
+// crops are ordered by page: page pg owns crops [first[pg], first[pg + 1])
+static std::vector<int> page_first(const std::vector<int>& page_of, int pages) {
+  std::vector<int> first(pages + 1, 0);
+  for (int pg : page_of) first[pg + 1]++;
+  for (int pg = 0; pg < pages; ++pg) first[pg + 1] += first[pg];
+  return first;
+}
+
+// a gathered payload without its padding: rank r's output block of `cap` rows (at r * cap * kRecWords) holds total[r] rows, which land
+// rank after rank in g's ids / prob / conf
+static void compact_gathered(const int32_t* payload, int cap, const std::vector<int>& total, Engine::Gathered& g) {
+  size_t rows = 0;
+  for (int t : total) rows += t;
+  g.ids.resize(rows * 26); g.prob.resize(rows * 26); g.conf.resize(rows);
+  size_t f = 0;
+  for (size_t r = 0; r < total.size(); ++r) {
+    if (!total[r]) continue;
+    const Engine::RecRows v = Engine::rec_rows(payload + r * cap * Engine::kRecWords, cap);
+    const size_t t = total[r];
+    std::copy(v.ids, v.ids + t * 26, g.ids.data() + f * 26);
+    std::copy(v.prob, v.prob + t * 26, g.prob.data() + f * 26);
+    std::copy(v.conf, v.conf + t, g.conf.data() + f);
+    f += t;
+  }
+}
+
 void Engine::allgather_host(const void* mine, size_t bytes, void* all) {
   Comm& c = *comm;
   const size_t b = std::max<size_t>(bytes, 1);
@@ -281,10 +307,8 @@ void Engine::pack_twin_crops(const PageBatch& B, int sl) {
   uint8_t* h = h_orient_in[sl].as<uint8_t>();
   memcpy(h, B.twin.data(), coef_b);
   for (int r = 0; r < T; ++r) memcpy(h + coef_b + (size_t)r * 20, &B.rects[(size_t)(r % N) * 5], 20);
-  int32_t* first = reinterpret_cast<int32_t*>(h + coef_b + rect_b);
-  std::fill(first, first + B.n + 1, 0);
-  for (int c = 0; c < N; ++c) first[B.page_of[c] + 1]++;
-  for (int pg = 0; pg < B.n; ++pg) first[pg + 1] += first[pg];
+  const std::vector<int> first = page_first(B.page_of, B.n);
+  std::copy(first.begin(), first.end(), reinterpret_cast<int32_t*>(h + coef_b + rect_b));
   TTR_HIP_CHECK(hipMemcpyAsync(orient_in.p, h, coef_b + rect_b + first_b, hipMemcpyHostToDevice, stream));
   launch_pack_crops_rect(B.d_pages, B.page_bytes, B.w * 3, B.h, B.w, reinterpret_cast<const int*>(orient_in.as<uint8_t>() + coef_b), orient_in.as<int64_t>(),
                          crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, stream);
@@ -301,7 +325,7 @@ void Engine::recog_enqueue(PageBatch& B) {
   if (N > 0) {
     const int K = orient_k(), T = (K - 1) * N;                 // word orientation: T twin crops behind the batch's N (DESIGN.md "Word orientation")
     crops.ensure((size_t)(N + T) * 32 * 128 * 3);
-    logits.ensure((size_t)std::max(N, T) * 26 * 95 * 4);
+    logits.ensure((size_t)std::max(N, T) * kLogitWords * 4);
     const RecOut cand = T ? rec_block(orient_cand, T) : RecOut{};
     const size_t side_b = ((size_t)N * (K + 1) + B.n) * 4;   // [N] turn | [N][K] candidate conf | [pages] page turn
     if (T) { orient_side.ensure(side_b); h_orient[sl].ensure(side_b); }
@@ -348,57 +372,46 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   if (comm) {   // compact the gathered payload: (rank, page, crop) order, no padding
     const GatherLayout L = GatherLayout::from_counts(B.all_counts.data(), comm->world, n);
     last_gathered.world = L.world; last_gathered.pages = n; last_gathered.counts = B.all_counts;
-    last_gathered.ids.resize((size_t)L.first.back() * 26);
-    last_gathered.prob.resize((size_t)L.first.back() * 26);
-    last_gathered.conf.resize((size_t)L.first.back());
-    const int32_t* g = h_gath[B.slot].as<int32_t>();
-    for (int r = 0; r < L.world; ++r) {   // rank r's block: cap rows of each of the three arrays
-      if (!L.total[r]) continue;
-      const int32_t* gr = g + (size_t)r * B.cap * kRecWords;
-      const size_t f = (size_t)L.first[(size_t)r * n];
-      memcpy(&last_gathered.ids[f * 26], gr, (size_t)L.total[r] * 26 * 4);
-      memcpy(&last_gathered.prob[f * 26], gr + (size_t)B.cap * 26, (size_t)L.total[r] * 26 * 4);
-      memcpy(&last_gathered.conf[f], gr + (size_t)B.cap * 52, (size_t)L.total[r] * 4);
-    }
+    compact_gathered(h_gath[B.slot].as<int32_t>(), B.cap, L.total, last_gathered);
   }
-  const int32_t* ids = h_ids[B.slot].as<int32_t>();
-  const float* prob = reinterpret_cast<const float*>(ids + (size_t)B.rows * 26);
-  const float* conf = reinterpret_cast<const float*>(ids + (size_t)B.rows * 52);
-  const int K = orient_k();
-  const int32_t* o_turn = K > 1 && N > 0 ? h_orient[B.slot].as<int32_t>() : nullptr;   // the side block (orient.hip)
-  const float* o_conf = o_turn ? reinterpret_cast<const float*>(o_turn + N) : nullptr;
-  const int32_t* o_page = o_turn ? o_turn + (size_t)N * (K + 1) : nullptr;
-  // crops are ordered by page: page pg owns crops [first[pg], first[pg + 1]); pages decode independently
-  std::vector<int> first(n + 1, 0);
-  for (int c = 0; c < N; ++c) first[B.page_of[c] + 1]++;
-  for (int pg = 0; pg < n; ++pg) first[pg + 1] += first[pg];
+  const int32_t* side = orient_k() > 1 && N > 0 ? h_orient[B.slot].as<int32_t>() : nullptr;
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, results);
+  host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
+  B.live = false; B.enqueued = false;
+}
+
+void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, std::vector<Result>& results) {
+  const int n = B.n, N = B.N, K = orient_k();
+  const std::vector<int> first = page_first(B.page_of, n);
+  // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
+  const float* o_conf = side ? reinterpret_cast<const float*>(side + N) : nullptr;
+  const int32_t* o_page = side ? side + (size_t)N * (K + 1) : nullptr;
   auto decode_page = [&](int pg) {
     Result& r = results[pg];
     const int c0 = first[pg], cnt = first[pg + 1] - c0;
     r.text.reserve(cnt); r.bbox.reserve((size_t)cnt * 4); r.quad.reserve((size_t)cnt * 8);
-    r.ids.assign(&ids[(size_t)c0 * 26], &ids[(size_t)(c0 + cnt) * 26]);
-    r.prob.assign(&prob[(size_t)c0 * 26], &prob[(size_t)(c0 + cnt) * 26]);
-    r.conf.assign(&conf[c0], &conf[c0 + cnt]);
+    r.ids.assign(&rows.ids[(size_t)c0 * 26], &rows.ids[(size_t)(c0 + cnt) * 26]);
+    r.prob.assign(&rows.prob[(size_t)c0 * 26], &rows.prob[(size_t)(c0 + cnt) * 26]);
+    r.conf.assign(&rows.conf[c0], &rows.conf[c0 + cnt]);
     if (K > 1) {
       r.orient_k = K;
-      if (o_turn) {
-        r.orient.assign(&o_turn[c0], &o_turn[c0 + cnt]);
+      if (side) {
+        r.orient.assign(&side[c0], &side[c0 + cnt]);
         r.orient_conf.assign(&o_conf[(size_t)c0 * K], &o_conf[(size_t)(c0 + cnt) * K]);
         r.page_orient = o_page[pg];
       }
     }
     for (int k = 0; k < cnt; ++k) {
-      r.text.push_back(tok.decode(&ids[(size_t)(c0 + k) * 26], 26));   // :486-505
+      r.text.push_back(tok.decode(&rows.ids[(size_t)(c0 + k) * 26], 26));   // :486-505
       float bb[4];
-      tesseract_bbox(B.boxes[pg][k], bb);                               // :511
+      tesseract_bbox(B.boxes[pg][k], bb);                                    // :511
       r.bbox.insert(r.bbox.end(), bb, bb + 4);
       push_quad(B.boxes[pg][k], r.quad);
     }
   };
+  // pages decode independently
   if (N >= 256) parallel_pages(n, decode_page);
   else for (int pg = 0; pg < n; ++pg) decode_page(pg);
-  host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
-  B.live = false; B.enqueued = false;
 }
 
 void Engine::run_pages(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results) {
@@ -457,7 +470,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
     pack_batch_crops(B, 0);
   }
   c->tr->broadcast(crops.p, (size_t)N * 32 * 128 * 3, 0, stream);
-  logits.ensure((size_t)per * 26 * 95 * 4);
+  logits.ensure((size_t)per * kLogitWords * 4);
   const RecOut out = rec_out(per);                              // per rank: [per][26] ids | [per][26] prob | [per] conf, one collective
   const size_t block = (size_t)per * kRecWords * 4;
   range_use(kRangeRec0);
@@ -471,34 +484,12 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   spin_event(done_ev[0]);
   range_verify(kRangeRec0, "the recogniser of a sharded page");
   if (rank != 0) return;
-  // shard r's block starts at word r * per * kRecWords: crop k is row k % per of shard k / per
-  std::vector<int32_t> ids((size_t)N * 26);
-  std::vector<float> prob((size_t)N * 26), conf(N);
-  const int32_t* g = h_gath[0].as<int32_t>();
-  for (int r = 0; r * per < N; ++r) {
-    const int32_t* gr = g + (size_t)r * per * kRecWords;
-    const int cnt = std::min(per, N - r * per);
-    memcpy(&ids[(size_t)r * per * 26], gr, (size_t)cnt * 26 * 4);
-    memcpy(&prob[(size_t)r * per * 26], gr + (size_t)per * 26, (size_t)cnt * 26 * 4);
-    memcpy(&conf[(size_t)r * per], gr + (size_t)per * 52, (size_t)cnt * 4);
-  }
-  std::vector<int> first(pages + 1, 0);
-  for (int k = 0; k < N; ++k) first[B.page_of[k] + 1]++;
-  for (int pg = 0; pg < pages; ++pg) first[pg + 1] += first[pg];
-  for (int pg = 0; pg < pages; ++pg) {
-    Result& r = results[pg];
-    const int c0 = first[pg], cnt = first[pg + 1] - c0;
-    r.ids.assign(&ids[(size_t)c0 * 26], &ids[(size_t)(c0 + cnt) * 26]);
-    r.prob.assign(&prob[(size_t)c0 * 26], &prob[(size_t)(c0 + cnt) * 26]);
-    r.conf.assign(&conf[c0], &conf[c0 + cnt]);
-    for (int k = 0; k < cnt; ++k) {
-      r.text.push_back(tok.decode(&ids[(size_t)(c0 + k) * 26], 26));
-      float bb[4];
-      tesseract_bbox(B.boxes[pg][k], bb);
-      r.bbox.insert(r.bbox.end(), bb, bb + 4);
-      push_quad(B.boxes[pg][k], r.quad);
-    }
-  }
+  // shard r (per rows, the last one ragged) holds crops [r * per, r * per + total[r])
+  std::vector<int> total(world);
+  for (int r = 0; r < world; ++r) total[r] = std::max(0, std::min(per, N - r * per));
+  Gathered g;
+  compact_gathered(h_gath[0].as<int32_t>(), per, total, g);
+  decode_pages(B, RecRows{g.ids.data(), g.prob.data(), g.conf.data()}, nullptr, results);
 }
 
 void Engine::stream_push(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& prev_results, int& prev_n) {

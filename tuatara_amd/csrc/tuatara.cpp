@@ -40,15 +40,14 @@ ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int o
   return e;
 }
 
-void fill(OutputItem& o, const ttr_result* r, int i) {
+template <class Item>
+void fill(Item& o, const ttr_result* r, int i) {   // text and bbox: OutputItem, and the start of OutputItemEx
   o.text = ttr_result_text(r, i);
   const float* b = ttr_result_bbox(r, i);
   o.bbox.assign(b, b + 4);
 }
 void fill(OutputItemEx& o, const ttr_result* r, int i) {
-  o.text = ttr_result_text(r, i);
-  const float* b = ttr_result_bbox(r, i);
-  o.bbox.assign(b, b + 4);
+  fill<OutputItemEx>(o, r, i);
   const float* q = ttr_result_quad(r, i);
   o.quad.assign(q, q + 8);
   o.conf = ttr_result_conf(r, i);
@@ -59,22 +58,20 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
   o.orient = 90 * ttr_result_orient(r, i);
 }
 
+// the checks in front of both calls, then the cached engine; null once the reference's message is printed
+ttr_engine* open_engine(const std::string& weights_dir, const std::string& outputs_dir, int crop_mode, int orient, int orient_page) {
+  if (weights_dir.empty()) { std::cerr << "Please provide a value for weights_dir" << std::endl; return nullptr; }   // tuatara.cpp:315-318
+  if (outputs_dir.empty()) { std::cerr << "Please provide a value for outputs_dir" << std::endl; return nullptr; }   // tuatara.cpp:320-323 (never used afterwards, there or here)
+  ttr_engine* e = engine_for(weights_dir, crop_mode, orient, orient_page);
+  if (!e) std::cerr << "error loading craft/parseq model: " << ttr_last_error() << std::endl;                       // tuatara.cpp:337-340, :429-432
+  return e;
+}
+
 template <class Item>
 std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
                           const std::string& outputs_dir, int crop_mode, int orient = -1, int orient_page = 0) {
-  if (weights_dir.empty()) {  // tuatara.cpp:315-318
-    std::cerr << "Please provide a value for weights_dir" << std::endl;
-    return {};
-  }
-  if (outputs_dir.empty()) {  // tuatara.cpp:320-323 (never used afterwards, there or here)
-    std::cerr << "Please provide a value for outputs_dir" << std::endl;
-    return {};
-  }
-  ttr_engine* e = engine_for(weights_dir, crop_mode, orient, orient_page);
-  if (!e) {  // tuatara.cpp:337-340, :429-432
-    std::cerr << "error loading craft/parseq model: " << ttr_last_error() << std::endl;
-    return {};
-  }
+  ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page);
+  if (!e) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
     return {};
@@ -93,10 +90,8 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
 template <class Item>
 std::vector<std::vector<Item>> run_many(const std::vector<ImageView>& images, const std::string& weights_dir, const std::string& outputs_dir, int crop_mode,
                                         int orient = -1, int orient_page = 0) {
-  if (weights_dir.empty()) { std::cerr << "Please provide a value for weights_dir" << std::endl; return {}; }   // tuatara.cpp:315-318
-  if (outputs_dir.empty()) { std::cerr << "Please provide a value for outputs_dir" << std::endl; return {}; }   // tuatara.cpp:320-323
-  ttr_engine* e = engine_for(weights_dir, crop_mode, orient, orient_page);
-  if (!e) { std::cerr << "error loading craft/parseq model: " << ttr_last_error() << std::endl; return {}; }     // tuatara.cpp:337-340, :429-432
+  ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page);
+  if (!e) return {};
   const int n = (int)images.size();
   std::vector<const uint8_t*> ptr(n);
   std::vector<int> hs(n), ws(n), st(n);

@@ -393,33 +393,6 @@ class Engine:
     def _quads(self, r, n: int) -> np.ndarray:
         return np.ctypeslib.as_array(self.lib.ttr_result_quads(r), (n, 8)).copy() if n else np.zeros((0, 8), np.float32)
 
-    def _take(self, r, conf: bool = False) -> List[dict]:
-        """ttr_result -> the reference's list of {"text", "bbox"} dicts (+ "ids"; + "quad" when rectified; + "conf", "char_conf" with conf),
-        through the bulk getters."""
-        n = self.lib.ttr_result_count(r)
-        out = []
-        if n:
-            bb = np.ctypeslib.as_array(self.lib.ttr_result_bboxes(r), (n, 4)).tolist()
-            ids = np.ctypeslib.as_array(self.lib.ttr_result_ids_all(r), (n, 26)).tolist()
-            need = self.lib.ttr_result_texts(r, None, 0)
-            buf = C.create_string_buffer(need)
-            self.lib.ttr_result_texts(r, buf, need)
-            texts = buf.raw[:need].decode("latin1").split("\n")
-            out = [{"text": texts[i], "bbox": bb[i], "ids": ids[i]} for i in range(n)]
-            if self.rectified:
-                for d, q in zip(out, self._quads(r, n)):
-                    d["quad"] = _quad_pairs(q)
-            if conf:
-                cf = np.ctypeslib.as_array(self.lib.ttr_result_confs(r), (n,)).copy()
-                pr = np.ctypeslib.as_array(self.lib.ttr_result_probs_all(r), (n, 26)).copy()
-                for d, c, p in zip(out, cf, pr):
-                    _add_conf(d, c, p)
-            if self.orienting:
-                for d, t in zip(out, np.ctypeslib.as_array(self.lib.ttr_result_orients(r), (n,)).tolist()):
-                    d["orient"] = 90 * t
-        self.lib.ttr_result_free(r)
-        return out
-
     def _take_many(self, arr, n: int, conf: bool = False) -> List[List[dict]]:
         """A batch of ttr_results -> list (per page) of lists of {"text", "bbox", "ids"} (+ "conf", "char_conf" with conf): one gather call
         for the whole batch."""
@@ -449,6 +422,16 @@ class Engine:
             self.lib.ttr_result_free(arr[i])
         return out
 
+    def _results(self, arr, n: int, keep: bool, conf: bool = False):
+        """n ttr_results -> _take_many's pages (keep), else each page's word count; frees them either way."""
+        if keep:
+            return self._take_many(arr, n, conf)
+        counts = []
+        for i in range(n):
+            counts.append(self.lib.ttr_result_count(arr[i]))
+            self.lib.ttr_result_free(arr[i])
+        return counts
+
     # ---- hot path
     def image_to_data(self, image: np.ndarray, conf: bool = False) -> List[dict]:
         """conf=True: every dict gains "conf" (the word's confidence, a probability) and "char_conf" (one probability per character of "text")."""
@@ -457,9 +440,9 @@ class Engine:
         if image.shape[2] != 3:
             raise RuntimeError("Input array should have 3 channels")            # the C ABI reads rows of 3 * w bytes
         image = np.ascontiguousarray(image, dtype=np.uint8)
-        r = C.c_void_p()
-        self._check(self.lib.ttr_image_to_data(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, C.byref(r)))
-        return self._take(r, conf)
+        arr = (C.c_void_p * 1)()
+        self._check(self.lib.ttr_image_to_data(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, arr))
+        return list(self._take_many(arr, 1, conf)[0])
 
     def images_to_data(self, images, keep: bool = True, conf: bool = False):
         """image_to_data over a list of host images [H, W, 3] u8 of any sizes (ttr_images_to_data): one result list per image, input order."""
@@ -482,35 +465,14 @@ class Engine:
             self._check(rc)
         if rc > 0:                              # rc images failed: their results are empty, the others delivered (include/tuatara_hip.h)
             self.last_images_error = self.lib.ttr_last_error().decode()
-        if keep:
-            return self._take_many(out, n, conf)
-        counts = []
-        for i in range(n):
-            counts.append(self.lib.ttr_result_count(out[i]))
-            self.lib.ttr_result_free(out[i])
-        return counts
+        return self._results(out, n, keep, conf)
 
     def pages_to_data_dev(self, d_pages, n: int, h: int, w: int, keep: bool = True, conf: bool = False):
         """d_pages: DeviceBuffer or raw device pointer holding [n][h][w][3] u8."""
         ptr = d_pages.ptr if isinstance(d_pages, DeviceBuffer) else d_pages
         arr = (C.c_void_p * n)()
         self._check(self.lib.ttr_pages_to_data_dev(self.h, ptr, n, h, w, arr))
-        if keep:
-            return self._take_many(arr, n, conf)
-        counts = []
-        for i in range(n):
-            counts.append(self.lib.ttr_result_count(arr[i]))
-            self.lib.ttr_result_free(arr[i])
-        return counts
-
-    def _stream_take(self, arr, n_prev: int, keep: bool, conf: bool = False):
-        if keep:
-            return self._take_many(arr, n_prev, conf)
-        counts = []
-        for i in range(n_prev):
-            counts.append(self.lib.ttr_result_count(arr[i]))
-            self.lib.ttr_result_free(arr[i])
-        return counts
+        return self._results(arr, n, keep, conf)
 
     def stream_push(self, d_pages, n: int, h: int, w: int, keep: bool = True, max_batch: int = 0, conf: bool = False):
         """Streamed batches (ttr_stream_push): enqueue batch k+1, get batch k's results (an empty list on the first push).  The
@@ -520,13 +482,13 @@ class Engine:
         arr = (C.c_void_p * self._max_pushed)()
         n_prev = C.c_int(0)
         self._check(self.lib.ttr_stream_push(self.h, ptr, n, h, w, arr, C.byref(n_prev)))
-        return self._stream_take(arr, n_prev.value, keep, conf)
+        return self._results(arr, n_prev.value, keep, conf)
 
     def stream_flush(self, keep: bool = True, conf: bool = False):
         arr = (C.c_void_p * getattr(self, "_max_pushed", 1))()
         n_prev = C.c_int(0)
         self._check(self.lib.ttr_stream_flush(self.h, arr, C.byref(n_prev)))
-        return self._stream_take(arr, n_prev.value, keep, conf)
+        return self._results(arr, n_prev.value, keep, conf)
 
     def last_stage_ms(self):
         ms = (C.c_float * 4)()
