@@ -2,7 +2,12 @@
 """Benchmark of the OCR hot path (BASELINE.json metric: pages/sec whole-node, 1024x768 pages,
 ~40 crops/page, + p50 page latency).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what `value` needs and nothing else: set-up, warm-up, the K timed steps, --dump-outputs, the line (with the figures the
+timed region itself yields: `roofline`, `roofline_craft_family`, the last pass's stage times).  `--full` adds what takes runs of its own:
+the CPU baseline, the dominant kernel alone on the chip (`roofline.*_exclusive`), the per-layer and PARSeq rooflines, and the comparison
+legs behind the timed region (all 26 AR steps, detected boxes, single-page latency, host pages, the bf16 and fp32-MFMA engines).
 
 A *step* is `--reps` (1) passes of the hot path (resize/pad -> CRAFT -> union-find CCL -> calipers ->
 crop-batch packer -> PARSeq -> token ids), each over one batch of `--pages` synthetic pages per GPU,
@@ -19,7 +24,7 @@ average duration, `achieved` = its ALGORITHMIC flops / its time, `frac` = achiev
 what the matrix pipe executes for it (x 3 or x 4 in the split-operand precision) is `mfma_pipe_frac`.
 
 `value` is measured in the engine's DEFAULT precision, f16x4 (fp32-equivalent split-operand f16 MFMA: logits
-within 1e-3 of the CPU fp32 reference, identical boxes and strings - tests/test_gpu_x4_parity.py); the bf16 and
+within 1e-3 of the CPU fp32 reference, identical boxes and strings - tests/test_gpu_x4_parity.py); with --full the bf16 and
 fp32-MFMA engines are timed beside it on the same workload.
 """
 from __future__ import annotations
@@ -307,8 +312,10 @@ def main():
                     "boxes are replaced by a fixed 5 x 8 grid of 150 x 40 px boxes so that PARSeq sees exactly 40 crops per page; detected: the synthetic detector's own boxes")
     ap.add_argument("--buffers", type=int, default=16, help="distinct device page buffers rotated over the passes (each holds --pages distinct pages of the 512-seed stream; 16 x 32 = all 512 seeds)")
     ap.add_argument("--precision", default="f16x4", choices=["f16x4", "bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the comparison legs after the timed region (bf16 / fp32 engines, detected boxes, latency, host buffers)")
+    ap.add_argument("--full", action="store_true", help="also measure what value does not need: the CPU baseline, the exclusive / per-layer / PARSeq rooflines and the "
+                    "comparison legs after the timed region (off: set-up, warm-up, the timed steps, --dump-outputs and the line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the runs after the timed region (bf16 / fp32 engines, detected boxes, latency, host buffers, rooflines)")
     ap.add_argument("--latency-iters", type=int, default=20)
     ap.add_argument("--stream", type=int, default=1, help="1: feed the passes through ttr_stream_push (batch j's detector and batch j-1's recogniser are enqueued before batch j-2's results are awaited, "
                     "host box extraction overlaps GPU work; two streams by default: batch j-1's recogniser runs beside batch j's detector, tuning key recog_overlap); 0: one synchronous ttr_pages_to_data_dev call per pass")
@@ -347,11 +354,12 @@ def main():
     if stub:                              # tests/test_launch_cpu.py: the launcher and the watchdog with a rank body that needs no GPU
         return stub_rank(stub, rank, world, wd, args)
 
-    # the CPU leg first, in a child process, while this process has not touched the GPU (and runs nothing else)
+    # --full: the CPU leg first, in a child process, while this process has not touched the GPU (and runs nothing else)
     # (N > 1: rank 0 runs it at the END instead, when every rank's GPU work is done and the other ranks have left - the host is then as quiet as here, and no
     # rank waits at a rendezvous for a CPU measurement)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.mode == "throughput":
+    cpu_leg = args.full and not args.no_cpu_baseline
+    if rank == 0 and world == 1 and cpu_leg and args.mode == "throughput":
         cpu = run_cpu_baseline(args.words, grid, layout)
 
     os.environ.setdefault("TUATARA_PRELOAD_TORCH", "0")   # the GPU processes of the benchmark stay torch-free (tuatara_amd/engine.py: load)
@@ -490,10 +498,11 @@ def main():
     stage = eng.last_stage_ms()
     # In the timed region a batch's recogniser runs on its own stream beside the next batch's detector (tuning key "recog_overlap", the engine's default: +3 % pages/s):
     # the dominant kernel's launches then share the chip with the recogniser's, and their durations say so.  The same kernel ALONE on the chip: a few passes
-    # with the overlap off, outside the timed region -> roofline.*_exclusive
+    # with the overlap off, outside the timed region (--full) -> roofline.*_exclusive
     kinds_excl = None
     overlap_on = not any(kv.startswith("recog_overlap=0") for kv in args.tune) and stream
-    if overlap_on and not args.no_extras and world == 1:
+    extras = args.full and not args.no_extras and world == 1
+    if overlap_on and extras:
         eng.set_tuning(b"recog_overlap", 0)
         run_passes(eng, 1)
         eng.lib.ttr_dev_sync(eng.h)
@@ -587,7 +596,7 @@ def main():
             if overlap_on:
                 roof["shares_the_chip"] = ("in the timed region this kernel's launches run while the previous batch's recogniser is on the chip too (engine default \"recog_overlap\": "
                                            "the recogniser on its own stream, +3 % pages/s): avg_launch_us / achieved / frac are what the kernel gets of a shared machine; "
-                                           "the *_exclusive keys = the same launches alone on the chip (overlap off, passes behind the timed region)")
+                                           "the *_exclusive keys (--full) = the same launches alone on the chip (overlap off, passes behind the timed region)")
             if kinds_excl:
                 ke = [k for k in kinds_excl if k["kind"] == dom["kind"] and k["stage"] == 0 and k["ms"] > 0 and k["launches"] > 0]
                 if ke:
@@ -638,8 +647,8 @@ def main():
                                       "by_kernel": sorted((line(k) for k in craft_kinds), key=lambda d: -d["avg_launch_us"] * d["launches_per_pass"])},
         }
 
-    # ------------------------------------------------------------------ comparison legs (outside the timed region; 1 GPU only)
-    if world == 1 and not args.no_extras:
+    # ------------------------------------------------------------------ comparison legs (--full; outside the timed region; 1 GPU only)
+    if extras:
         def rate(e, passes):
             run_passes(e, 1)
             e.lib.ttr_dev_sync(e.h)
@@ -748,7 +757,7 @@ def main():
         comm.close()
         comm = None
     if rank == 0:
-        if world > 1 and not args.no_cpu_baseline:
+        if world > 1 and cpu_leg:
             eng.close()                   # the GPU is released; the other ranks are leaving or gone
             time.sleep(2.0)
             cpu = run_cpu_baseline(args.words, grid, layout)

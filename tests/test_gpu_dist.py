@@ -194,7 +194,7 @@ def test_bench_starts_its_own_ranks_two_ranks_on_one_gpu(weights):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env.update(TUATARA_BENCH_SHARE_GPU="1", TUATARA_PRELOAD_TORCH="0", TUATARA_COMM_TIMEOUT="240")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pages", "8", "--buffers", "3", "--deadline", "800"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pages", "8", "--buffers", "3", "--deadline", "800", "--full"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, (out.stdout[-500:], out.stderr[-3000:])
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -203,7 +203,7 @@ def test_bench_starts_its_own_ranks_two_ranks_on_one_gpu(weights):
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["gathered_id_rows_last_pass"] == 2 * 8 * 40                      # every page of both ranks: 40 rows of 26 ids
     assert d["config"]["pages_per_gpu_per_pass"] == 8 and "SHARE one GPU" in d["config"]["parallelism"]
-    assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["cores"] >= 1      # an N > 1 line carries the CPU leg too (rank 0, behind the timed region)
+    assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["cores"] >= 1      # an N > 1 --full line carries the CPU leg too (rank 0, behind the timed region)
     assert len(d["ranks"]) == 2
     assert len(d["per_rank_pages_per_s"]["by_rank"]) == 2 and d["per_rank_pages_per_s"]["min"] <= d["per_rank_pages_per_s"]["max"]
 
