@@ -24,6 +24,17 @@ int ttr_dbg_split_gemm(ttr_engine* e, const float* x, int M, int K, const float*
                        const float* resid, int cfg, float* out);
 int ttr_dbg_conv_pool(ttr_engine* e, const float* in0, int C0, int B, int H, int W, int ks, const float* wgt, const float* bias,
                       int Cout, int act, int pool_relu, float* out_full, float* out_pool);
+/* The tap on the split detector (f16x4 engines): one forward pass over B canvases u8 [B][H][W][3] with every launch noting where its tensors live (inputs,
+ * out, out_relu, out_pool, the low-resolution z of a commuted up-convolution, the heat map; tensors a fusion never writes have no record).  Returns the number
+ * of records (-1 on error); heat_out (may be NULL) f32 [B][H/2][W/2][2].  Nothing is copied during the pass and no kernel is added; a pass without the tap is
+ * unchanged.  The records hold until the engine's next detector pass. */
+int ttr_dbg_craft_taps(ttr_engine* e, const uint8_t* canvas, int B, int H, int W, float* heat_out);
+int ttr_dbg_craft_tap_count(ttr_engine* e);
+/* record i: text = "layer\nrole\nkernel kind" (role: canvas, in0, in1, out, out_relu, out_pool, z, heat), dims = {B, H, W, real channels, row length in channels,
+ * form (0 fp32, 1 packed pairs [x0 | x1], 2 pairs, 3 triples, 4 u8), f16 planes per value} */
+int ttr_dbg_craft_tap_info(ttr_engine* e, int i, char* text, size_t cap, int dims[7]);
+/* tensor i joined to fp32 on the host (split.h: join2 / join3, every step exact), f32 [B][H][W][row length]: padding channels included */
+int ttr_dbg_craft_tap_read(ttr_engine* e, int i, float* out);
 /* Which kernel serves bf16 layers: -1 = first-generation igemm only, 0 = automatic (default),
  * 1..6 = force that gemm2 tile configuration where it applies.  Process-wide; for tuning and tests. */
 void ttr_set_gemm_config(int cfg);

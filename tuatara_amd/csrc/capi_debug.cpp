@@ -268,6 +268,74 @@ int ttr_dbg_conv_pool(ttr_engine* e, const float* in0, int C0, int B, int H, int
   TTR_GUARD_END(-1)
 }
 
+// The tap on the split detector (engine.h: Engine::CraftTap): one forward pass of B canvases with the switch on, then the records and their tensors.
+int ttr_dbg_craft_taps(ttr_engine* e, const uint8_t* canvas, int B, int H, int W, float* heat_out) {
+  TTR_GUARD_BEGIN
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_dbg_craft_taps");
+  if (E.prec != kSplit) throw std::runtime_error("ttr_dbg_craft_taps: f16x4 engines only");
+  if (B < 1 || H < 32 || W < 32) throw std::runtime_error("ttr_dbg_craft_taps: B >= 1, H, W >= 32");
+  const size_t nc = (size_t)B * H * W * 3, nh = (size_t)B * H * W / 4 * 2;
+  E.canvas.ensure(nc);
+  E.heat.ensure(nh * 4);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.canvas.p, canvas, nc, hipMemcpyHostToDevice, E.stream));
+  struct Off { Engine& E; ~Off() { E.craft_tap_on = false; } } off{E};
+  E.craft_tap_on = true;
+  E.craft_forward(E.canvas.as<uint8_t>(), B, H, W, E.heat.as<float>());
+  if (heat_out) TTR_HIP_CHECK(hipMemcpyAsync(heat_out, E.heat.p, nh * 4, hipMemcpyDeviceToHost, E.stream));
+  E.range_fetch(Engine::kRangeStage);
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  E.range_verify(Engine::kRangeStage, "ttr_dbg_craft_taps");
+  return (int)E.craft_taps.size();
+  TTR_GUARD_END(-1)
+}
+
+int ttr_dbg_craft_tap_count(ttr_engine* e) { return e ? (int)e->e->craft_taps.size() : -1; }
+
+int ttr_dbg_craft_tap_info(ttr_engine* e, int i, char* text, size_t cap, int dims[7]) {
+  TTR_GUARD_BEGIN
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (i < 0 || i >= (int)E.craft_taps.size()) throw std::runtime_error("ttr_dbg_craft_tap_info: no such record");
+  const Engine::CraftTap& t = E.craft_taps[i];
+  const std::string s = t.layer + "\n" + t.role + "\n" + t.kind;
+  if (!text || cap < s.size() + 1) throw std::runtime_error("ttr_dbg_craft_tap_info: text buffer too small");
+  memcpy(text, s.c_str(), s.size() + 1);
+  dims[0] = t.B; dims[1] = t.H; dims[2] = t.W; dims[3] = t.C; dims[4] = t.ld; dims[5] = t.form;
+  dims[6] = t.form == Engine::kTapTriples ? 3 : t.form == Engine::kTapPairs || t.form == Engine::kTapPacked ? 2 : 0;   // f16 planes per value
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_dbg_craft_tap_read(ttr_engine* e, int i, float* out) {
+  TTR_GUARD_BEGIN
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (i < 0 || i >= (int)E.craft_taps.size()) throw std::runtime_error("ttr_dbg_craft_tap_read: no such record");
+  const Engine::CraftTap& t = E.craft_taps[i];
+  const size_t M = (size_t)t.B * t.H * t.W, ld = (size_t)t.ld;
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  if (t.form == Engine::kTapF32) { TTR_HIP_CHECK(hipMemcpy(out, t.p, M * ld * 4, hipMemcpyDeviceToHost)); return 0; }
+  if (t.form == Engine::kTapU8) {
+    std::vector<uint8_t> h(M * ld);
+    TTR_HIP_CHECK(hipMemcpy(h.data(), t.p, h.size(), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < h.size(); ++j) out[j] = (float)h[j];
+    return 0;
+  }
+  const size_t npl = t.form == Engine::kTapTriples ? 3 : 2;   // pixel row [x0 (ld) | x1 (ld) (| x2 (ld))]; packed pairs are that row with ld = 32
+  std::vector<_Float16> h(M * npl * ld);
+  TTR_HIP_CHECK(hipMemcpy(h.data(), t.p, h.size() * 2, hipMemcpyDeviceToHost));
+  for (size_t m = 0; m < M; ++m) {
+    const _Float16* row = h.data() + m * npl * ld;
+    float* o = out + m * ld;
+    if (npl == 3) for (size_t c = 0; c < ld; ++c) o[c] = (float)row[c] + ((float)row[ld + c] + (float)row[2 * ld + c]) * (1.f / 2048.f);   // split.h: join3, every step exact
+    else for (size_t c = 0; c < ld; ++c) o[c] = (float)row[c] + (float)row[ld + c] * (1.f / 2048.f);                                       // join2
+  }
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 void ttr_set_gemm_config(int cfg) { set_gemm_config(cfg); }
 
 void ttr_set_decoder_mode(int mode) { g_tuning_default.decoder_mode = mode; }

@@ -549,6 +549,19 @@ struct Engine {
   void sconv(const char* name, const void* in0, int C0, const void* in1, int C1, int B, int H, int W, void* out, int act,
              void* out_relu = nullptr, void* out_pool = nullptr, int pool_relu = 0, int out_planes = -1, int out_ld = 0, bool packed = false, float* tail_heat = nullptr);
   void craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, float* d_heat);
+  // Developer tap on the split detector (ttr_dbg_craft_taps): with craft_tap_on, every launch of craft_forward_split notes where its tensors live - each one
+  // already has a workspace slot of its own, so nothing is copied and no kernel is added; the records are read after a stream synchronise and hold until the
+  // engine's next forward pass.  Off (the default), tap() returns at once: same launches, same bits.
+  enum { kTapF32 = 0, kTapPacked = 1, kTapPairs = 2, kTapTriples = 3, kTapU8 = 4 };   // CraftTap::form (packed pairs: pixel rows [x0 (32) | x1 (32)])
+  struct CraftTap {
+    std::string layer, role, kind;   // role: "in0", "in1", "out", "out_relu", "out_pool", "z", "heat"; kind: the kernel that ran (outputs only)
+    const void* p; int B, H, W, C, ld, form;   // C real channels of a pixel row of ld channels
+  };
+  bool craft_tap_on = false;
+  std::vector<CraftTap> craft_taps;
+  void tap(const char* layer, const char* role, const void* p, int B, int H, int W, int C, int ld, int form, const char* kind = "") {
+    if (craft_tap_on && p) craft_taps.push_back(CraftTap{layer, role, kind, p, B, H, W, C, ld, form});
+  }
 
   // ---- PARSeq
   // split-operand linear on planes: in [M][3 K] -> out (planes [M][3 out_ld] or fp32 [M][out_ld]) and / or out_f32 (+ fp32 residual)

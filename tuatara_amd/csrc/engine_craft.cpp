@@ -136,6 +136,13 @@ void Engine::sconv(const char* name, const void* in0, int C0, const void* in1, i
     if (const char* e = conv3p_check(p)) throw std::runtime_error(std::string(name) + ": " + e);
     const char* pk = tail_heat ? "conv3p_kernel<32,NP=2> + conv_cls.6 + conv_cls.8 (head tail)" : "conv3p_kernel<32,NP=2> (packed pairs, 32 input channels)";
     const std::string per_layer = std::string(name) + " | " + pk;
+    if (craft_tap_on) {
+      int creal = L.cout;
+      for (const auto& c : craft_convs()) if (std::string(c.name) == name) creal = c.cout;
+      tap(name, "in0", in0, B, H, W, 32, 32, kTapPacked);
+      if (tail_heat) tap(name, "heat", tail_heat, B, H, W, 2, 2, kTapF32, pk);   // (the group conv_cls.4 -> .6 -> .8: the members have no tensors)
+      else tap(name, "out", out, B, H, W, creal, p.out_ld, out_planes ? kTapPacked : kTapF32, pk);
+    }
     timed(profiling == 2 ? per_layer.c_str() : pk, flops + tail_flops,
           2.0 * p.M * L.cout * 9 * 64 * 2 + (tail_heat ? 2.0 * p.M * 16 * 32 * 6 : 0.0), [&] { launch_conv3p(p, stream); },
           (double)p.M * 128.0 + (tail_heat ? (double)p.M * 8.0 : (double)p.M * (out_planes ? 128.0 : 32.0 * 4)) + (double)L.cout * 9 * 64 * 2 * 2);   // pixel rows [x0 | x1] of 128 B in and out (or the heat map)
@@ -162,6 +169,9 @@ void Engine::sconv(const char* name, const void* in0, int C0, const void* in1, i
     flops += 2.0 * p.M * 64 * 27;
     const char* fk = "conv3p_kernel<64,NP=3> + conv1_1 (fused first layer)";
     const std::string fl = std::string("slice1.0 + ") + name + " | " + fk;
+    tap(name, "canvas", sconv_canvas, B, H, W, 3, 3, kTapU8);
+    tap(name, "out", out, B, H, W, p.Cout, p.out_ld, out_planes, fk);
+    tap(name, "out_pool", out_pool, B, H / 2, W / 2, p.Cout, p.out_ld, out_planes, fk);
     timed(profiling == 2 ? fl.c_str() : fk, flops, flops * np, [&] { launch_conv3p(p, stream); },
           (double)p.M * 3.0 + (out ? (double)p.M * p.Cout * 2.0 * out_planes : 0.0) + (out_pool ? (double)p.M / 4 * p.Cout * 2.0 * out_planes : 0.0) + (double)p.Cout * L.k * 6.0);
     return;
@@ -178,6 +188,16 @@ void Engine::sconv(const char* name, const void* in0, int C0, const void* in1, i
                        (out_pool ? (double)p.M / 4 * p.Cout * ob : 0.0) + (double)p.Cout * L.k * 2.0 * 3;
   // profiling == 2 (every launch bracketed: bench.py's per-layer pass behind the timed region): the kind is "layer | kernel", so that every layer states its own roof
   const std::string per_layer = std::string(name) + " | " + kind;
+  if (craft_tap_on) {
+    int cin = Ct, creal = L.cout;   // real channels: the head's tensors carry zero padding channels behind them
+    for (const auto& c : craft_convs()) if (std::string(c.name) == name) { cin = c.cin; creal = c.cout; }
+    tap(name, "in0", in0, B, H, W, C1 ? C0 : cin, C0, np - 1);
+    tap(name, "in1", in1, B, H, W, C1, C1, np - 1);
+    const int form = out_planes ? out_planes : kTapF32;
+    tap(name, "out", out, B, H, W, creal, p.out_ld, form, kind);
+    tap(name, "out_relu", out_relu, B, H, W, creal, p.out_ld, form, kind);
+    tap(name, "out_pool", out_pool, B, H / 2, W / 2, creal, p.out_ld, form, kind);
+  }
   timed(profiling == 2 ? per_layer.c_str() : kind, flops, flops * np, [&] { if (c3) launch_conv3p(p, stream); else launch_gemm2(p, 0, stream); }, bytes);
 }
 
@@ -205,6 +225,10 @@ void Engine::upconv_commuted(const char* name, const void* y_lo, int C0, const v
   if (const char* e = gemm2_check(b)) throw std::runtime_error(std::string(name) + " (skip half): " + e);
   const char* kind = np == 3 ? "gemm2_kernel<SP,NP=3> (CRAFT 1x1 / dilated)" : "gemm2_kernel<SP,NP=4> (CRAFT 1x1 / dilated)";
   // algorithmic flops: the layer's own (SURVEY.md section 8(d) counts the convolution as the reference runs it); executed: what the two launches multiply
+  tap(name, "in0", y_lo, B, H / 2, W / 2, C0, C0, np - 1);
+  tap(name, "in1", skip, B, H, W, C1, C1, np - 1);
+  tap(name, "z", z, B, H / 2, W / 2, Cout, Cout, kTapF32, kind);
+  tap(name, "out", out, B, H, W, Cout, Cout, np - 1, kind);
   const std::string la = std::string(name) + " (W_up . y at the low resolution) | " + kind, lb = std::string(name) + " (skip half + upsample(z) in the epilogue) | " + kind;
   timed(profiling == 2 ? la.c_str() : kind, 2.0 * Mhi * Cout * C0, 2.0 * Mlo * Cout * C0 * np, [&] { launch_gemm2(a, 0, stream); }, (double)Mlo * C0 * 2.0 * (np - 1) + (double)Mlo * Cout * 4.0 + (double)Cout * C0 * 6.0);
   timed(profiling == 2 ? lb.c_str() : kind, 2.0 * Mhi * Cout * C1, 2.0 * Mhi * Cout * C1 * np, [&] { launch_gemm2(b, 0, stream); },
@@ -213,11 +237,14 @@ void Engine::upconv_commuted(const char* name, const void* y_lo, int C0, const v
 
 void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, float* d_heat) {
   prof_stage = 0;
+  craft_taps.clear();   // (records of an earlier pass point into workspaces this one rewrites)
   const size_t M0 = (size_t)B * H * W, M1 = M0 / 4, M2 = M1 / 4, M3 = M2 / 4, M4 = M3 / 4;
   const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8, H4 = H / 16, W4 = W / 16;
   size_t k = 0;
   const int npl = tn.craft_products == 4 ? 3 : 2;                                       // planes per value
-  const int layout = npl * 2 + (tn.head_packed && npl == 2 ? 1 : 0);   // (plane count and the head tensors' row form: both move the zero padding channels)
+  // the 32-channel head tensors as packed pairs, or (triples; maps that do not tile into 8 x 32 patches) as rows with 32 zero channels behind the real ones
+  const bool head_packed = tn.head_packed && npl == 2 && H1 % 8 == 0 && W1 % 32 == 0;
+  const int layout = npl * 2 + (head_packed ? 1 : 0);   // (plane count and the head tensors' row form AS THIS PAGE TAKES IT: both move the zero padding channels)
   if (layout != craft_ws_npl) {   // another plane count: the zero padding channels of the head tensors sit elsewhere - start from fresh buffers
     TTR_HIP_CHECK(hipStreamSynchronize(stream)); TTR_HIP_CHECK(hipStreamSynchronize(lane_stream));
     craft_ws_set[0].clear(); craft_ws_set[1].clear();
@@ -234,6 +261,8 @@ void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, f
     range_tag("craft.slice1.0");
     timed(profiling == 2 ? "slice1.0 | conv1_split_kernel" : "conv1_split_kernel", 2.0 * M0 * 64 * 27, 2.0 * M0 * 64 * 27 * (npl + 1), [&] { launch_conv1_split(d_canvas, L0.ws.p, L0.b.as<float>(), L0.inv_scale, c11, B, H, W, stream, npl); },
           (double)M0 * 3.0 + (double)M0 * 64 * 2.0 * npl);
+    tap("slice1.0", "canvas", d_canvas, B, H, W, 3, 3, kTapU8);
+    tap("slice1.0", "out", c11, B, H, W, 64, 64, npl, "conv1_split_kernel");
   } else k++;   // (the workspace slot stays reserved: the slots behind it keep their sizes whichever way this page goes)
   void* p1 = pbuf(M1, 64);
   {
@@ -256,6 +285,8 @@ void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, f
   void* c51 = pbuf(M4, 512); sconv("slice4.34", p4, 512, nullptr, 0, B, H4, W4, c51, kActRelu);
   void* c52 = pbuf(M4, 512); sconv("slice4.37", c51, 512, nullptr, 0, B, H4, W4, c52, kActNone);          // relu5_3 skip
   void* mp = pbuf(M4, 512);  prof_break(), launch_maxpool3x3s1_planes(c52, mp, B, H4, W4, 512, stream, npl);
+  tap("maxpool3x3", "in0", c52, B, H4, W4, 512, 512, npl);
+  tap("maxpool3x3", "out", mp, B, H4, W4, 512, 512, npl, "maxpool3x3s1_planes");
   void* c6 = pbuf(M4, 1024); sconv("slice5.1", mp, 512, nullptr, 0, B, H4, W4, c6, kActNone);
   void* fc7 = pbuf(M4, 1024); sconv("slice5.2", c6, 1024, nullptr, 0, B, H4, W4, fc7, kActNone);
   void* u1a = pbuf(M4, 512); sconv("upconv1.0", fc7, 1024, c52, 512, B, H4, W4, u1a, kActRelu);
@@ -269,6 +300,8 @@ void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, f
       return o;
     }
     void* up = pbuf(Mhi, C0); prof_break(), launch_upsample2x_planes(y_lo, up, B, Hh / 2, Wh / 2, C0, stream, npl);
+    tap((std::string(name) + ".upsample").c_str(), "in0", y_lo, B, Hh / 2, Wh / 2, C0, C0, npl);
+    tap((std::string(name) + ".upsample").c_str(), "out", up, B, Hh, Wh, C0, C0, npl, "upsample2x_planes");
     void* o = pbuf(Mhi, Cout); sconv(name, up, C0, skip, C1, B, Hh, Wh, o, kActRelu);
     return o;
   };
@@ -281,7 +314,7 @@ void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, f
   // the two 1x1 layers (16 -> 16 -> 2) on the fp32 MFMA kernel
   // (head_packed, pairs only: the 32-channel tensors as 128-byte pixel rows [x0 | x1], their consumers on packed pairs - conv3p.hip, NP = 2)
   void *u4b, *h0, *h2, *h4 = nullptr;
-  if (tn.head_packed && npl == 2 && H1 % 8 == 0 && W1 % 32 == 0) {
+  if (head_packed) {
     u4b = pbuf(M1, 32); sconv("upconv4.3", u4a, 64, nullptr, 0, B, H1, W1, u4b, kActRelu);
     h0 = pbuf(M1, 32);  sconv("conv_cls.0", u4b, 64, nullptr, 0, B, H1, W1, h0, kActRelu, nullptr, nullptr, 0, -1, 0, true);
     h2 = pbuf(M1, 32);  sconv("conv_cls.2", h0, 64, nullptr, 0, B, H1, W1, h2, kActRelu, nullptr, nullptr, 0, -1, 0, true);
@@ -304,6 +337,10 @@ void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, f
     void* h6 = fbuf(M1, 32);
     conv("conv_cls.6", h4, 32, nullptr, 0, 0, B, H1, W1, h6, kActRelu);
     conv("conv_cls.8", h6, 32, nullptr, 0, 0, B, H1, W1, nullptr, kActNone, d_heat);
+    tap("conv_cls.6", "in0", h4, B, H1, W1, 16, 32, kTapF32);
+    tap("conv_cls.6", "out", h6, B, H1, W1, 16, 32, kTapF32, "igemm_kernel<f32> (CRAFT head 1x1)");
+    tap("conv_cls.8", "in0", h6, B, H1, W1, 16, 32, kTapF32);
+    tap("conv_cls.8", "heat", d_heat, B, H1, W1, 2, 2, kTapF32, "igemm_kernel<f32> (CRAFT head 1x1)");
   }
   prof_break();
 }

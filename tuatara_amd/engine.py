@@ -93,6 +93,10 @@ SYMBOLS = [
     ("ttr_set_profiling", _I, [_VP, _I]),
     ("ttr_dbg_conv_pool", _I, [_VP, _PF, _I, _I, _I, _I, _I, _PF, _PF, _I, _I, _I, _PF, _PF]),
     ("ttr_dbg_split_gemm", _I, [_VP, _PF, _I, _I, _PF, _PF, _I, _I, _I, _I, _PF, _I, _PF]),
+    ("ttr_dbg_craft_taps", _I, [_VP, _PU8, _I, _I, _I, _PF]),
+    ("ttr_dbg_craft_tap_count", _I, [_VP]),
+    ("ttr_dbg_craft_tap_info", _I, [_VP, _I, C.c_char_p, C.c_size_t, _PI]),
+    ("ttr_dbg_craft_tap_read", _I, [_VP, _I, _PF]),
     ("ttr_set_gemm_config", None, [_I]),
     ("ttr_set_decoder_mode", None, [_I]),
     ("ttr_set_tuning", _I, [C.c_char_p, _I]),
@@ -566,6 +570,34 @@ class Engine:
         heat = np.zeros((H // 2, W // 2, 2), np.float32)
         self._check(self.lib.ttr_craft_heatmap(self.h, _u8(canvas), H, W, _f(heat)))
         return heat
+
+    def craft_taps(self, canvases: np.ndarray):
+        """f16x4 engines, developer hook (ttr_dbg_craft_taps): one detector pass over canvases u8 [B, H, W, 3] (or [H, W, 3]) with the tap on ->
+        (heat f32 [B, H/2, W/2, 2], records).  A record is a dict: layer, role (canvas / in0 / in1 / out / out_relu / out_pool / z / heat), kind (the
+        kernel, on outputs), B, H, W, C (real channels), ld (row length in channels), form (0 fp32, 1 packed pairs, 2 pairs, 3 triples, 4 u8), index.
+        craft_tap_read(index) fetches a tensor; the records hold until this engine's next detector pass."""
+        canvases = np.ascontiguousarray(canvases, dtype=np.uint8)
+        if canvases.ndim == 3:
+            canvases = canvases[None]
+        B, H, W = canvases.shape[:3]
+        heat = np.zeros((B, H // 2, W // 2, 2), np.float32)
+        n = self.lib.ttr_dbg_craft_taps(self.h, _u8(canvases), B, H, W, _f(heat))
+        if n < 0:
+            raise EngineError(self.lib.ttr_last_error().decode())
+        recs = []
+        text, dims = C.create_string_buffer(512), np.zeros(7, np.int32)
+        for i in range(n):
+            self._check(self.lib.ttr_dbg_craft_tap_info(self.h, i, text, 512, _i(dims)))
+            layer, role, kind = text.value.decode().split("\n")
+            recs.append(dict(index=i, layer=layer, role=role, kind=kind, B=int(dims[0]), H=int(dims[1]), W=int(dims[2]), C=int(dims[3]), ld=int(dims[4]),
+                             form=int(dims[5])))
+        return heat, recs
+
+    def craft_tap_read(self, rec) -> np.ndarray:
+        """Tensor of a craft_taps record joined to fp32 on the host, every step exact: f32 [B, H, W, ld], padding channels included."""
+        out = np.zeros((rec["B"], rec["H"], rec["W"], rec["ld"]), np.float32)
+        self._check(self.lib.ttr_dbg_craft_tap_read(self.h, rec["index"], _f(out)))
+        return out
 
     def ccl_boxes(self, heat: np.ndarray, max_rects: int = 8192) -> np.ndarray:
         heat = np.ascontiguousarray(heat, dtype=np.float32)
