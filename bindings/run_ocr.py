@@ -18,10 +18,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.append(os.path.join(HERE, "..", "build", "bindings"))   # where the build puts pytuatara (reference: run_ocr.py:6)
 
 
-def annotate(image: np.ndarray, result) -> Image.Image:
+def annotate(image: np.ndarray, result, by_lines: bool = False) -> Image.Image:
     """The reference's three panels side by side (run_ocr.py:10-82), drawn with PIL: the page with its boxes | each text at its
     box position | the texts as running text in reading order - sorted by (y1, x1) (:12), starting at (10, 30), wrapped at the
-    page width, 10 px between words and lines (:20-25, :62-75)."""
+    page width, 10 px between words and lines (:20-25, :62-75).  by_lines=True (items read with lines=True, carrying "line" and
+    "word"): the third panel follows the page's text lines instead - items in (line, word) order, a new row for every line."""
     page = Image.fromarray(image).convert("RGB")
     w, h = page.size
     boxes = page.copy()
@@ -29,7 +30,9 @@ def annotate(image: np.ndarray, result) -> Image.Image:
     running = Image.new("RGB", page.size, "black")
     db, dp, dr = ImageDraw.Draw(boxes), ImageDraw.Draw(panel), ImageDraw.Draw(running)
     tx, ty, gap = 10, 30, 10
-    for item in sorted(result, key=lambda it: (it["bbox"][1], it["bbox"][0])):
+    by_lines = by_lines and all("line" in it for it in result)
+    last_line = None
+    for item in sorted(result, key=(lambda it: (it["line"], it["word"])) if by_lines else (lambda it: (it["bbox"][1], it["bbox"][0]))):
         x1, y1, x2, y2 = (int(v) for v in item["bbox"])
         text = item["text"]
         if "quad" in item:       # rectified crops (pytuatara.image_to_data(..., rectify=True)): the word's own quadrilateral
@@ -39,6 +42,10 @@ def annotate(image: np.ndarray, result) -> Image.Image:
         dp.text((x1, y1), text, fill=(255, 0, 0))
         l, t, r, btm = dr.textbbox((0, 0), text or " ")
         tw, th = r - l, btm - t
+        if by_lines and last_line is not None and item["line"] != last_line and tx > 10:   # a new text line starts a new row
+            tx = 10
+            ty += th + gap
+        last_line = item.get("line")
         if tx + tw > w:
             tx = 10
             ty += th + gap
@@ -52,19 +59,22 @@ def annotate(image: np.ndarray, result) -> Image.Image:
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    rectify = "--rectify" in argv
-    argv = [a for a in argv if a != "--rectify"]
+    rectify, lines = "--rectify" in argv, "--lines" in argv
+    argv = [a for a in argv if a not in ("--rectify", "--lines")]
     image_path = argv[0] if len(argv) > 0 else os.path.join(HERE, "..", "tests", "data", "funsd_0001129658.png")
     weights_dir = argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "weights")
     outputs_dir = argv[2] if len(argv) > 2 else os.path.join(HERE, "..", "outputs")
     import pytuatara
 
     numpy_image = np.array(Image.open(image_path).convert("RGB"))
-    result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir, rectify=True) if rectify else pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir)
+    kw = dict(rectify=True) if rectify else {}
+    if lines:
+        kw["lines"] = True
+    result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir, **kw)
     print(result)
     os.makedirs(outputs_dir, exist_ok=True)
     stem = os.path.splitext(os.path.basename(image_path))[0]
-    annotate(numpy_image, result).save(os.path.join(outputs_dir, stem + "_annotated_with_ocr_results.png"))
+    annotate(numpy_image, result, by_lines=lines).save(os.path.join(outputs_dir, stem + "_annotated_with_ocr_results.png"))
     return result
 
 

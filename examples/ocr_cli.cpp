@@ -8,7 +8,10 @@
 // confidence in the word, a probability to 6 decimals (DESIGN.md "Recognition confidence").
 //   ocr_cli --orient <image.png> <weights_dir> <outputs_dir>    reads every word at the quarter turn the recogniser is most sure of (DESIGN.md
 // "Word orientation", TTR_ORIENT_QUARTER, per word) and prints "x1 y1 x2 y2<TAB>degrees<TAB>conf<TAB>text" per item.
+//   ocr_cli --lines <image.png> <weights_dir> <outputs_dir>     groups the words into text lines (DESIGN.md "Text lines") and prints the page's text, one line
+// of the page per output line, in reading order, the words joined by one space.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
+#include <algorithm>
 #include <cstdio>
 #include <iostream>
 
@@ -49,8 +52,21 @@ int main(int argc, const char** argv) {
         printf("%g %g %g %g\t%d\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.orient, it.conf, it.text.c_str());
       return 0;
     }
+    if (argc == 5 && std::string(argv[1]) == "--lines") {
+      pngdec::Image img = pngdec::read(argv[2]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[3], argv[4], false, -1, false, true);
+      std::vector<size_t> at(items.size());
+      for (size_t i = 0; i < at.size(); ++i) at[i] = i;
+      std::sort(at.begin(), at.end(), [&](size_t a, size_t b) { return items[a].line != items[b].line ? items[a].line < items[b].line : items[a].word < items[b].word; });
+      for (size_t k = 0; k < at.size(); ++k) {
+        if (k) fputc(items[at[k]].line != items[at[k - 1]].line ? '\n' : ' ', stdout);
+        fputs(items[at[k]].text.c_str(), stdout);
+      }
+      if (!at.empty()) fputc('\n', stdout);
+      return 0;
+    }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--rectify | --conf | --orient] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--rectify | --conf | --orient | --lines] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

@@ -42,6 +42,7 @@ struct OutputItemEx {
   float conf = 0.f;                // the recogniser's confidence in `text`, a probability in (0, 1] (DESIGN.md "Recognition confidence")
   std::vector<float> char_conf;    // one probability per character of `text`, in order (char_conf.size() == text.size())
   int orient = 0;                  // word orientation: the turn the word was read at, in degrees clockwise (0, 90, 180, 270; DESIGN.md "Word orientation")
+  int line = -1, word = -1;        // text lines: the item's line of its page, in reading order, and its position inside that line; -1 when lines are off (DESIGN.md "Text lines")
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, bool rectify);
@@ -55,6 +56,14 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
                                            std::string outputs_dir, bool rectify, int orient, bool orient_page);
 std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
                                                          bool rectify, int orient, bool orient_page);
+// Text lines (opt-in; DESIGN.md "Text lines"): lines = true also groups every page's words into lines in reading order; each item says its
+// `line` and its `word` position in it (sort the items by (line, word) to read the page; join a line's words by ' ').  lines = false is the
+// calls above, unless TUATARA_LINES=1 is set in the environment, which turns lines on for image_to_data / images_to_data / every call above.
+// Items, order, boxes and text do not change.  In these two overloads orient = -1 leaves the orientation to TUATARA_ORIENT.
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

@@ -59,6 +59,8 @@ typedef struct ttr_config {
   int crop_mode;         /* TTR_CROP_BOUNDING (default) or TTR_CROP_RECTIFIED (appended last: the fields above keep their offsets) */
   int orient;            /* TTR_ORIENT_OFF (default), TTR_ORIENT_FLIP or TTR_ORIENT_QUARTER; other values make ttr_create fail */
   int orient_page;       /* 0 (default): the turn is chosen per word; 1: once per page */
+  int lines;             /* 0 (default): off, the same kernels and bits as without the field; 1: the words are also grouped into text lines in
+                            reading order (DESIGN.md "Text lines"); other values make ttr_create fail.  Needs max_components <= 4096 */
 } ttr_config;
 
 void ttr_config_default(ttr_config* cfg);
@@ -152,6 +154,38 @@ int ttr_results_gather_orient(ttr_result* const* rs, int n, int32_t* turns, floa
  * strict > in ascending turn order.  Page: the argmax of the votes of the words whose winning text has at least 2 characters, ties to the
  * lower turn, 0 without votes; per_page = 1: every turns[i] = *page_turn.  Returns 0, -1 on bad arguments. */
 int ttr_orient_select(const float* conf, const int32_t* ids, int n, int k, int per_page, int32_t* turns, int32_t* page_turn);
+
+/* Text lines (ttr_config.lines = 1; DESIGN.md "Text lines"), every entry point but ttr_pages_to_data_dev_sharded (which refuses lines != 0).
+ * The items, their order and every other output are those of lines = 0; the result also says which line of its page each item belongs to and
+ * which word of that line it is, and gives the page's lines in reading order.  Lines depend only on the page's own quads (ttr_result_quads).
+ * ttr_result_line_count: the page's lines.  ttr_result_lines / ttr_result_words: [count] each item's line (in line order) and its position
+ * inside that line.  ttr_result_reading_order: [count] the item indices in reading order, each line's members consecutive.
+ * ttr_result_line_first: [lines + 1] the lines' offsets into the reading order.  ttr_result_line_bboxes: [lines][4] min / max of the members'
+ * bbox.  With lines = 0, or for an empty result, the pointers are NULL and the count is 0. */
+int ttr_result_line_count(const ttr_result* r);
+const int32_t* ttr_result_lines(const ttr_result* r);
+const int32_t* ttr_result_words(const ttr_result* r);
+const int32_t* ttr_result_reading_order(const ttr_result* r);
+const int32_t* ttr_result_line_first(const ttr_result* r);
+const float* ttr_result_line_bboxes(const ttr_result* r);
+/* The text of line l (its members' text in word order, joined by one space) and of the page (its lines joined by '\n'), without a
+ * terminator.  Both return the bytes needed, like ttr_result_texts: buf is written only when cap suffices.  0 with lines = 0. */
+int ttr_result_line_text(const ttr_result* r, int l, char* buf, size_t cap);
+int ttr_result_page_text(const ttr_result* r, char* buf, size_t cap);
+/* ... for a batch of results in one call (any output may be NULL): n_lines[n]; line, word and order [total] in ttr_results_gather's item
+ * order (order holds indices local to its result); line_first: per result its n_lines + 1 offsets (local), result after result - total
+ * lines + n entries, at most total + n; line_bboxes [total lines][4].  A result without lines (lines = 0, or empty) contributes 0 lines, its
+ * single line_first entry 0, and -1 for line / word / order of any items it has.  Returns the total line count, -1 on bad arguments. */
+int ttr_results_gather_lines(ttr_result* const* rs, int n, int32_t* n_lines, int32_t* line, int32_t* word, int32_t* order, int32_t* line_first,
+                             float* line_bboxes);
+/* The rule on the host, no GPU: the n words of ONE page as quads [n][8] (tl, tr, br, bl in image pixels, as ttr_result_quad gives them) ->
+ * line[n], word[n], *n_lines.  Integer arithmetic on llrint(16 x): exact, the same as line_group_kernel's.  Returns 0; -1 on bad arguments, a
+ * coordinate that is not finite or one with |x| >= 32768. */
+int ttr_lines_from_quads(const float* quads, int n, int32_t* line, int32_t* word, int32_t* n_lines);
+/* The rule on the GPU as a stage entry point, whatever the engine's `lines`: host quads of several pages - page p owns quads
+ * [first[p], first[p + 1]), first[0] = 0, at most 4096 per page - are uploaded, line_group_kernel runs once, and line[first[pages]],
+ * word[first[pages]] and n_lines[pages] come back.  Returns 0, -1 on error (ttr_last_error). */
+int ttr_group_lines(ttr_engine* e, const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines);
 
 /* ---- multi-GPU: RCCL in the C++ host -----------------------------------------------------------------
  * One process per GPU, one engine per process.  The OCR path has no data-path collective: pages are independent.  The one exchange is

@@ -36,7 +36,7 @@ void ttr_config_default(ttr_config* c) {
   c->precision = TTR_PREC_F16X4; c->device = 0; c->canvas_size = 1024; c->mag_ratio = 1.0f;
   c->text_threshold = 0.7f; c->link_threshold = 0.4f; c->low_text = 0.4f; c->min_area = 10;
   c->strict_crops = 0; c->max_components = 4096; c->verbose = 0; c->crop_mode = TTR_CROP_BOUNDING;
-  c->orient = TTR_ORIENT_OFF; c->orient_page = 0;
+  c->orient = TTR_ORIENT_OFF; c->orient_page = 0; c->lines = 0;
 }
 
 const char* ttr_last_error(void) { return g_last_error.c_str(); }
@@ -207,6 +207,74 @@ int ttr_orient_select(const float* conf, const int32_t* ids, int n, int k, int p
   if (n < 0 || (k != 1 && k != 2 && k != 4) || !page_turn || (n > 0 && (!conf || !ids || !turns))) return -1;
   orient_select(conf, ids, n, k, per_page != 0, turns, page_turn);
   return 0;
+}
+
+int ttr_result_line_count(const ttr_result* r) { return r ? r->r.n_lines : 0; }
+
+const int32_t* ttr_result_lines(const ttr_result* r) { return r && !r->r.line.empty() ? r->r.line.data() : nullptr; }
+
+const int32_t* ttr_result_words(const ttr_result* r) { return r && !r->r.word.empty() ? r->r.word.data() : nullptr; }
+
+const int32_t* ttr_result_reading_order(const ttr_result* r) { return r && !r->r.order.empty() ? r->r.order.data() : nullptr; }
+
+const int32_t* ttr_result_line_first(const ttr_result* r) { return r && r->r.n_lines > 0 ? r->r.line_first.data() : nullptr; }
+
+const float* ttr_result_line_bboxes(const ttr_result* r) { return r && !r->r.line_bbox.empty() ? r->r.line_bbox.data() : nullptr; }
+
+static int copy_out(const std::string& t, char* buf, size_t cap) {
+  if (buf && cap >= t.size() && !t.empty()) memcpy(buf, t.data(), t.size());
+  return (int)t.size();
+}
+
+int ttr_result_line_text(const ttr_result* r, int l, char* buf, size_t cap) {
+  if (!r || l < 0 || l >= r->r.n_lines) return 0;
+  return copy_out(r->r.line_text(l), buf, cap);
+}
+
+int ttr_result_page_text(const ttr_result* r, char* buf, size_t cap) {
+  if (!r || r->r.n_lines <= 0) return 0;
+  return copy_out(r->r.page_text(), buf, cap);
+}
+
+int ttr_results_gather_lines(ttr_result* const* rs, int n, int32_t* n_lines, int32_t* line, int32_t* word, int32_t* order, int32_t* line_first,
+                             float* line_bboxes) {
+  if (!rs || n < 0) return -1;
+  size_t oi = 0, ol = 0, of = 0;
+  for (int i = 0; i < n; ++i) {
+    static const Result none;
+    const Result& r = rs[i] ? rs[i]->r : none;
+    const size_t cnt = r.text.size(), nl = (size_t)r.n_lines;
+    if (n_lines) n_lines[i] = r.n_lines;
+    const bool has = nl > 0 && r.line.size() == cnt;
+    auto put = [&](int32_t* dst, const std::vector<int32_t>& v) {
+      if (!dst) return;
+      if (has) std::copy(v.begin(), v.end(), dst + oi); else std::fill(dst + oi, dst + oi + cnt, -1);
+    };
+    put(line, r.line); put(word, r.word); put(order, r.order);
+    if (line_first) { if (has) std::copy(r.line_first.begin(), r.line_first.end(), line_first + of); else line_first[of] = 0; }
+    if (line_bboxes && has) std::copy(r.line_bbox.begin(), r.line_bbox.end(), line_bboxes + 4 * ol);
+    oi += cnt; ol += has ? nl : 0; of += (has ? nl : 0) + 1;
+  }
+  return (int)ol;
+}
+
+int ttr_lines_from_quads(const float* quads, int n, int32_t* line, int32_t* word, int32_t* n_lines) {
+  if (n < 0 || !n_lines || (n > 0 && (!quads || !line || !word))) return -1;
+  std::vector<int32_t> cuv((size_t)n * 6);
+  for (int i = 0; i < n; ++i) if (!lines_cuv(quads + 8 * (size_t)i, cuv.data() + 6 * (size_t)i)) return -1;
+  lines_from_cuv(cuv.data(), n, line, word, n_lines);
+  return 0;
+}
+
+int ttr_group_lines(ttr_engine* e, const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines) {
+  TTR_GUARD_BEGIN
+  if (!e || pages < 0 || (pages > 0 && !first) || (pages > 0 && first[pages] > 0 && !quads)) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_group_lines");
+  E.group_lines(quads, first, pages, line, word, n_lines);
+  return 0;
+  TTR_GUARD_END(-1)
 }
 
 void ttr_result_free(ttr_result* r) { delete r; }

@@ -400,6 +400,8 @@ Engine::Engine(const std::string& dir, const ttr_config& c) : cfg(c) {
   if (cfg.orient != TTR_ORIENT_OFF && cfg.orient != TTR_ORIENT_FLIP && cfg.orient != TTR_ORIENT_QUARTER)
     throw std::runtime_error("orient must be TTR_ORIENT_OFF (0), TTR_ORIENT_FLIP (1) or TTR_ORIENT_QUARTER (2)");
   if (cfg.orient_page != 0 && cfg.orient_page != 1) throw std::runtime_error("orient_page must be 0 (per word) or 1 (per page)");
+  if (cfg.lines != 0 && cfg.lines != 1) throw std::runtime_error("lines must be 0 (off) or 1 (group the words into text lines)");
+  if (cfg.lines && cfg.max_components > kLinesMaxWords) throw std::runtime_error("lines = 1 needs max_components <= " + std::to_string(kLinesMaxWords));
   prec = cfg.precision == TTR_PREC_F32 ? kF32 : cfg.precision == TTR_PREC_F16X4 ? kSplit : kBF16;
   es = prec == kBF16 ? 2 : 4;
   int ndev = 0;

@@ -266,6 +266,13 @@ struct Result {
   std::vector<int32_t> orient;      // 1 per item: the chosen turn 0..3
   std::vector<float> orient_conf;   // orient_k per item: every candidate's conf, ascending turn
   int orient_k = 1, page_orient = 0;
+  // text lines (cfg.lines = 1; DESIGN.md "Text lines"): empty / 0 when off
+  std::vector<int32_t> line, word;          // 1 per item: its line in line order, its position inside that line
+  std::vector<int32_t> order, line_first;   // the items in reading order; [n_lines + 1] the lines' offsets into `order`
+  std::vector<float> line_bbox;             // 4 per line: min / max of the members' bbox
+  int n_lines = 0;
+  std::string line_text(int l) const;       // the members' text in word order, joined by ' '
+  std::string page_text() const;            // the lines joined by '\n'
 };
 
 struct CclBatch {   // device workspaces of the CCL stage for a batch of equally sized pages
@@ -404,6 +411,8 @@ struct Engine {
   DevBuf canvas, heat, staging_img, crops, rects_dev, coef_dev, logits, ar_logits, ids_dev, tokens;
   DevBuf orient_in, orient_cand, orient_side;     // word orientation: the twins' coef | rects | page firsts; their recogniser block; the side block (orient.hip)
   PinnedBuf h_orient_in[2], h_orient[2];          // ... per slot: staging of orient_in, host copy of the side block
+  DevBuf lines_in, lines_side;                    // text lines: the words' cuv | page firsts; the side block (lines.hip)
+  PinnedBuf h_lines_in[2], h_lines[2];            // ... per slot: staging of lines_in, host copy of the side block
   CclBatch ccl;
   PinnedBuf h_counters, h_cand, h_rows, h_rects_f, h_rects[2], h_coef[2], h_ids[2];   // (h_coef: crop_mode = TTR_CROP_RECTIFIED only)   // pinned staging of the small host <-> device transfers
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -669,10 +678,17 @@ struct Engine {
   // pack_crops_rect_kernel on the (K - 1) N twin rows into `crops` behind the batch's N crops
   void pack_twin_crops(const PageBatch& B, int sl);
 
+  // text lines: the words' fixed-point c, u, v and the pages' first words into the pinned staging of slot sl (host only; returns the largest
+  // word count of a page), then one copy of them, line_group_kernel into the side block and its copy to h_lines[sl]
+  int stage_batch_lines(const PageBatch& B, int sl);
+  void group_batch_lines(const PageBatch& B, int sl, int max_words);
+  // the stage form (ttr_group_lines): host quads [first[pages]][8] of several pages -> line, word [first[pages]], n_lines [pages]
+  void group_lines(const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines);
+
   void finish(PageBatch& B, std::vector<Result>& results);
   // results[pg] for every page of B from its boxes and the decoded rows of its crops (crop c is row c); side: the orientation side block
-  // of the batch (orient.hip) or null
-  void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, std::vector<Result>& results);
+  // of the batch (orient.hip) or null; lines_side: the text lines' side block (lines.hip) or null
+  void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, std::vector<Result>& results);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it

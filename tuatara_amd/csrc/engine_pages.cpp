@@ -1,6 +1,7 @@
 // image_to_data (tuatara.cpp:314-512) over batches of device-resident pages: detector + CCL -> boxes -> crop batch -> recogniser -> strings,
 // in four phases so that several batches can be in flight; the multi-GPU exchange points; the sharded latency mode.
 #include <deque>
+#include <limits>
 
 #include "engine.h"
 
@@ -10,6 +11,24 @@ static void push_quad(const RRect& b, std::vector<float>& quad) {   // Result::q
   Pt2f q[4]; double cf[6];
   deskew_quad(b, q, cf);
   for (int i = 0; i < 4; ++i) { quad.push_back(q[i].x); quad.push_back(q[i].y); }
+}
+
+std::string Result::line_text(int l) const {
+  std::string t;
+  for (int k = line_first[(size_t)l]; k < line_first[(size_t)l + 1]; ++k) {
+    if (k > line_first[(size_t)l]) t += ' ';
+    t += text[(size_t)order[(size_t)k]];
+  }
+  return t;
+}
+
+std::string Result::page_text() const {
+  std::string t;
+  for (int l = 0; l < n_lines; ++l) {
+    if (l) t += '\n';
+    t += line_text(l);
+  }
+  return t;
 }
 
 // crops are ordered by page: page pg owns crops [first[pg], first[pg + 1])
@@ -314,8 +333,69 @@ void Engine::pack_twin_crops(const PageBatch& B, int sl) {
                          crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, stream);
 }
 
+int Engine::stage_batch_lines(const PageBatch& B, int sl) {
+  const int N = B.N;
+  h_lines_in[sl].ensure((size_t)N * 24 + (size_t)(B.n + 1) * 4);   // cuv int32 [N][6] | first int32 [pages + 1]
+  int32_t* cuv = h_lines_in[sl].as<int32_t>();
+  std::vector<float> q;
+  q.reserve(8);
+  int c = 0;
+  for (int pg = 0; pg < B.n; ++pg)
+    for (const RRect& b : B.boxes[pg]) {                       // (crop order: page after page)
+      q.clear();
+      push_quad(b, q);
+      if (c >= N || !lines_cuv(q.data(), cuv + 6 * (size_t)c)) throw std::runtime_error("text lines: a word's corner is not finite or lies beyond 32768 px");
+      ++c;
+    }
+  if (c != N) throw std::runtime_error("text lines: box count does not match the crop count");
+  const std::vector<int> first = page_first(B.page_of, B.n);
+  std::copy(first.begin(), first.end(), cuv + 6 * (size_t)N);
+  int max_words = 0;
+  for (int pg = 0; pg < B.n; ++pg) max_words = std::max(max_words, first[pg + 1] - first[pg]);
+  if (max_words > kLinesMaxWords) throw std::runtime_error("text lines: a page has more than " + std::to_string(kLinesMaxWords) + " words");
+  return max_words;
+}
+
+void Engine::group_batch_lines(const PageBatch& B, int sl, int max_words) {
+  const int N = B.N;
+  const size_t in_b = (size_t)N * 24 + (size_t)(B.n + 1) * 4, side_b = ((size_t)2 * N + B.n) * 4;   // the side block: [N] line | [N] word | [pages] n_lines
+  lines_in.ensure(in_b);
+  h_lines[sl].ensure(side_b); lines_side.ensure(side_b);
+  TTR_HIP_CHECK(hipMemcpyAsync(lines_in.p, h_lines_in[sl].p, in_b, hipMemcpyHostToDevice, stream));
+  launch_line_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, B.n, N, max_words, lines_side.as<int>(), stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(h_lines[sl].p, lines_side.p, side_b, hipMemcpyDeviceToHost, stream));
+}
+
+void Engine::group_lines(const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines) {
+  if (pages <= 0) return;
+  if (first[0] != 0) throw std::runtime_error("ttr_group_lines: first[0] must be 0");
+  int max_words = 0;
+  for (int pg = 0; pg < pages; ++pg) {
+    if (first[pg + 1] < first[pg]) throw std::runtime_error("ttr_group_lines: first must not decrease");
+    max_words = std::max(max_words, first[pg + 1] - first[pg]);
+  }
+  if (max_words > kLinesMaxWords) throw std::runtime_error("ttr_group_lines: more than " + std::to_string(kLinesMaxWords) + " words on a page");
+  const int N = first[pages];
+  const size_t cuv_b = (size_t)N * 24, in_b = cuv_b + (size_t)(pages + 1) * 4, side_b = ((size_t)2 * N + pages) * 4;
+  h_lines_in[0].ensure(in_b); lines_in.ensure(in_b);
+  h_lines[0].ensure(side_b); lines_side.ensure(side_b);
+  int32_t* cuv = h_lines_in[0].as<int32_t>();
+  for (int c = 0; c < N; ++c)
+    if (!lines_cuv(quads + 8 * (size_t)c, cuv + 6 * (size_t)c)) throw std::runtime_error("ttr_group_lines: a coordinate is not finite or has |x| >= 32768");
+  std::copy(first, first + pages + 1, cuv + 6 * (size_t)N);
+  TTR_HIP_CHECK(hipMemcpyAsync(lines_in.p, cuv, in_b, hipMemcpyHostToDevice, stream));
+  launch_line_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, pages, N, max_words, lines_side.as<int>(), stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(h_lines[0].p, lines_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  const int32_t* side = h_lines[0].as<int32_t>();
+  if (line && N) std::copy(side, side + N, line);
+  if (word && N) std::copy(side + N, side + 2 * (size_t)N, word);
+  if (n_lines) std::copy(side + 2 * (size_t)N, side + 2 * (size_t)N + pages, n_lines);
+}
+
 void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
+  const int line_words = cfg.lines && N > 0 ? stage_batch_lines(B, sl) : 0;   // text lines: the host part, before anything of this batch is enqueued
   range_use(kRangeRec0 + (sl & 1));          // the recogniser's kernels of this batch watch the slot's own word
   B.rows = std::max(N, comm ? B.cap : 0);   // the output block's rows (RecOut): with a communicator, the gathered payload's rows per rank
   const size_t block = (size_t)B.rows * kRecWords * 4;
@@ -331,6 +411,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (T) { orient_side.ensure(side_b); h_orient[sl].ensure(side_b); }
     pack_batch_crops(B, sl);
     if (T) pack_twin_crops(B, sl);
+    if (cfg.lines) group_batch_lines(B, sl, line_words);               // text lines: from the boxes alone, so inside the packing stage (DESIGN.md "Text lines")
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf);
     if (T) {   // the twins as a pass of their own (turn 0 keeps its batch, and with it its bits), then the choice, in place in the standard block
@@ -375,12 +456,13 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
     compact_gathered(h_gath[B.slot].as<int32_t>(), B.cap, L.total, last_gathered);
   }
   const int32_t* side = orient_k() > 1 && N > 0 ? h_orient[B.slot].as<int32_t>() : nullptr;
-  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, results);
+  const int32_t* lines_block = cfg.lines && N > 0 ? h_lines[B.slot].as<int32_t>() : nullptr;   // the side block (lines.hip)
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, results);
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
 
-void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, std::vector<Result>& results) {
+void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, std::vector<Result>& results) {
   const int n = B.n, N = B.N, K = orient_k();
   const std::vector<int> first = page_first(B.page_of, n);
   // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
@@ -407,6 +489,25 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
       tesseract_bbox(B.boxes[pg][k], bb);                                    // :511
       r.bbox.insert(r.bbox.end(), bb, bb + 4);
       push_quad(B.boxes[pg][k], r.quad);
+    }
+    if (lines_side && cnt > 0) {   // [N] line | [N] word | [pages] n_lines -> the page's lines in reading order
+      r.line.assign(&lines_side[c0], &lines_side[c0 + cnt]);
+      r.word.assign(&lines_side[(size_t)N + c0], &lines_side[(size_t)N + c0 + cnt]);
+      r.n_lines = lines_side[2 * (size_t)N + pg];
+      r.order.assign(cnt, 0);
+      r.line_first.assign((size_t)std::max(r.n_lines, 0) + 1, 0);
+      if (!lines_reading_order(r.line.data(), r.word.data(), cnt, r.n_lines, r.order.data(), r.line_first.data()))
+        throw std::runtime_error("text lines: the side block of page " + std::to_string(pg) + " is not a numbering of its lines");
+      const float inf = std::numeric_limits<float>::infinity();
+      r.line_bbox.assign((size_t)r.n_lines * 4, 0.f);
+      for (int l = 0; l < r.n_lines; ++l) {
+        float* lb = &r.line_bbox[4 * (size_t)l];
+        lb[0] = lb[1] = inf; lb[2] = lb[3] = -inf;
+        for (int k = r.line_first[l]; k < r.line_first[l + 1]; ++k) {
+          const float* bb = &r.bbox[4 * (size_t)r.order[k]];
+          lb[0] = std::min(lb[0], bb[0]); lb[1] = std::min(lb[1], bb[1]); lb[2] = std::max(lb[2], bb[2]); lb[3] = std::max(lb[3], bb[3]);
+        }
+      }
     }
   };
   // pages decode independently
@@ -441,6 +542,7 @@ void Engine::run_pages(const uint8_t* d_pages, int n, int h, int w, std::vector<
 void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results) {
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");
   if (cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("latency mode does not support word orientation: create the engine with orient = TTR_ORIENT_OFF");
+  if (cfg.lines) throw std::runtime_error("latency mode does not support text lines: create the engine with lines = 0");
   if (q1.live || q2.live) throw std::runtime_error("streamed batches are in flight: call ttr_stream_flush until it returns none");
   Comm* const c = comm;
   const int world = c->world, rank = c->rank;
@@ -489,7 +591,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   for (int r = 0; r < world; ++r) total[r] = std::max(0, std::min(per, N - r * per));
   Gathered g;
   compact_gathered(h_gath[0].as<int32_t>(), per, total, g);
-  decode_pages(B, RecRows{g.ids.data(), g.prob.data(), g.conf.data()}, nullptr, results);
+  decode_pages(B, RecRows{g.ids.data(), g.prob.data(), g.conf.data()}, nullptr, nullptr, results);
 }
 
 void Engine::stream_push(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& prev_results, int& prev_n) {

@@ -126,6 +126,113 @@ void orient_select(const float* conf, const int32_t* ids, int n, int k, int per_
   *page_turn = step * pt;
 }
 
+// ---------------------------------------------------------------- text lines (DESIGN.md "Text lines")
+bool lines_cuv(const float* q, int32_t cuv[6]) {
+  int64_t p[8];
+  for (int k = 0; k < 8; ++k) {
+    if (!std::isfinite(q[k]) || std::fabs(q[k]) >= 32768.f) return false;
+    p[k] = (int64_t)std::llrint(16. * (double)q[k]);
+  }
+  for (int a = 0; a < 2; ++a) {   // tl = p[0..1], tr = p[2..3], br = p[4..5], bl = p[6..7]
+    cuv[a] = (int32_t)(p[a] + p[2 + a] + p[4 + a] + p[6 + a]);
+    cuv[2 + a] = (int32_t)((p[2 + a] - p[a]) + (p[4 + a] - p[6 + a]));
+    cuv[4 + a] = (int32_t)((p[6 + a] - p[a]) + (p[4 + a] - p[2 + a]));
+  }
+  return true;
+}
+
+namespace {
+struct LineWord {
+  int64_t cx, cy, ux, uy, vx, vy, uu, vv, A;
+  bool ok;
+};
+inline int64_t iabs64(int64_t x) { return x < 0 ? -x : x; }
+// j seen from i's frame: same band and near
+inline bool lines_frame(const LineWord& i, const LineWord& j) {
+  const int64_t dx = j.cx - i.cx, dy = j.cy - i.cy;
+  if (iabs64(dx * i.vx + dy * i.vy) > i.vv) return false;
+  const int64_t s = dx * i.ux + dy * i.uy;
+  const int64_t e = iabs64(j.ux * i.ux + j.uy * i.uy) + iabs64(j.vx * i.ux + j.vy * i.uy);
+  return std::max(s - e - i.uu, -s - e - i.uu) <= 2 * i.A;
+}
+inline bool lines_link(const LineWord& i, const LineWord& j) {
+  if (!i.ok || !j.ok) return false;
+  const int64_t dot = i.ux * j.ux + i.uy * j.uy;
+  if (dot <= 0 || 64 * iabs64(i.ux * j.uy - i.uy * j.ux) > 17 * dot) return false;
+  if (i.vv > 4 * j.vv || j.vv > 4 * i.vv) return false;
+  return lines_frame(i, j) && lines_frame(j, i);
+}
+}  // namespace
+
+void lines_from_cuv(const int32_t* cuv, int n, int32_t* line, int32_t* word, int32_t* n_lines) {
+  *n_lines = 0;
+  if (n <= 0) return;
+  std::vector<LineWord> w((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const int32_t* t = cuv + 6 * (size_t)i;
+    LineWord& a = w[i];
+    a.cx = t[0]; a.cy = t[1]; a.ux = t[2]; a.uy = t[3]; a.vx = t[4]; a.vy = t[5];
+    a.uu = a.ux * a.ux + a.uy * a.uy; a.vv = a.vx * a.vx + a.vy * a.vy; a.A = iabs64(a.ux * a.vy - a.uy * a.vx);
+    a.ok = a.uu != 0 && a.vv != 0 && a.A != 0;
+  }
+  std::vector<int> root((size_t)n);   // the smallest member index of each word's line
+  for (int i = 0; i < n; ++i) root[i] = i;
+  auto find = [&](int i) { while (root[i] != i) { root[i] = root[root[i]]; i = root[i]; } return i; };
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j)
+      if (lines_link(w[i], w[j])) {
+        const int a = find(i), b = find(j);
+        if (a != b) root[std::max(a, b)] = std::min(a, b);
+      }
+  for (int i = 0; i < n; ++i) root[i] = find(i);
+  std::vector<int64_t> Ux((size_t)n, 0), Uy((size_t)n, 0), key((size_t)n);
+  for (int i = 0; i < n; ++i) { Ux[root[i]] += w[i].ux; Uy[root[i]] += w[i].uy; }
+  for (int i = 0; i < n; ++i) key[i] = w[i].cx * Ux[root[i]] + w[i].cy * Uy[root[i]];
+  std::vector<int> idx((size_t)n);
+  for (int i = 0; i < n; ++i) idx[i] = i;
+  std::sort(idx.begin(), idx.end(), [&](int a, int b) {   // lines together, each in word order
+    if (root[a] != root[b]) return root[a] < root[b];
+    if (key[a] != key[b]) return key[a] < key[b];
+    return a < b;
+  });
+  std::vector<int> firsts;           // each line's first word
+  for (int k = 0, pos = 0; k < n; ++k) {
+    pos = k > 0 && root[idx[k]] == root[idx[k - 1]] ? pos + 1 : 0;
+    word[idx[k]] = pos;
+    if (pos == 0) firsts.push_back(idx[k]);
+  }
+  std::sort(firsts.begin(), firsts.end(), [&](int a, int b) {
+    if (w[a].cy != w[b].cy) return w[a].cy < w[b].cy;
+    if (w[a].cx != w[b].cx) return w[a].cx < w[b].cx;
+    return a < b;
+  });
+  std::vector<int> line_of_root((size_t)n, 0);
+  for (size_t l = 0; l < firsts.size(); ++l) line_of_root[root[firsts[l]]] = (int)l;
+  for (int i = 0; i < n; ++i) line[i] = line_of_root[root[i]];
+  *n_lines = (int32_t)firsts.size();
+}
+
+bool lines_reading_order(const int32_t* line, const int32_t* word, int n, int n_lines, int32_t* order, int32_t* line_first) {
+  if (n_lines < 0 || n_lines > n) return false;
+  std::fill(line_first, line_first + n_lines + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    if (line[i] < 0 || line[i] >= n_lines) return false;
+    line_first[line[i] + 1]++;
+  }
+  for (int l = 0; l < n_lines; ++l) {
+    if (line_first[l + 1] == 0) return false;
+    line_first[l + 1] += line_first[l];
+  }
+  std::fill(order, order + n, -1);
+  for (int i = 0; i < n; ++i) {
+    if (word[i] < 0 || word[i] >= line_first[line[i] + 1] - line_first[line[i]]) return false;
+    int32_t& o = order[line_first[line[i]] + word[i]];
+    if (o >= 0) return false;
+    o = i;
+  }
+  return true;
+}
+
 // ---------------------------------------------------------------- convex hull (monotone chain, exact on integer-valued input)
 static double cross(const Pt2f& o, const Pt2f& a, const Pt2f& b) {
   return ((double)a.x - o.x) * ((double)b.y - o.y) - ((double)a.y - o.y) * ((double)b.x - o.x);

@@ -43,6 +43,17 @@ void turn_coef(const Pt2f quad[4], int turn, int64_t fixed[6]);
 // confidence rule), ties to the lower turn, 0 without votes; per_page: every turn = it.
 void orient_select(const float* conf, const int32_t* ids, int n, int k, int per_page, int32_t* turns, int32_t* page_turn);
 
+// Text lines (ttr_config.lines; DESIGN.md "Text lines").  lines_cuv: one quad tl, tr, br, bl (8 floats, image pixels) in the rule's fixed point
+// (llrint(16 x) per coordinate) -> cuv = {c.x, c.y, u.x, u.y, v.x, v.y}: c = tl + tr + br + bl (4 x the centre), u = (tr - tl) + (br - bl) (2 x the
+// width vector), v = (bl - tl) + (br - tr) (2 x the height vector).  Returns false for a coordinate that is not finite or has |x| >= 32768 (every
+// product of the rule then stays far inside int64).  lines_from_cuv: the rule on n words of ONE page (line_group_kernel, lines.hip, computes the
+// same): line[n] = each word's line in line order, word[n] = its position inside its line, *n_lines.  Integer arithmetic only.
+bool lines_cuv(const float* quad8, int32_t cuv[6]);
+void lines_from_cuv(const int32_t* cuv, int n, int32_t* line, int32_t* word, int32_t* n_lines);
+// ... derived from line / word: order[n] = the item indices in reading order (each line's members consecutive, in word order) and
+// line_first[n_lines + 1] = the lines' offsets into it.  Returns false when line / word are not a numbering of n_lines non-empty lines.
+bool lines_reading_order(const int32_t* line, const int32_t* word, int n, int n_lines, int32_t* order, int32_t* line_first);
+
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.
 struct Component {

@@ -203,6 +203,12 @@ void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float
 void launch_orient_select(int* ids, float* prob, float* conf, const int* cids, const float* cprob, const float* cconf, const int* first, int pages, int N,
                           int K, int per_page, int* side, hipStream_t s);
 
+// lines.hip: text lines (DESIGN.md "Text lines") - per page, every word's line and its position in it.  cuv [N][6]: the words' fixed-point c, u, v
+// (geometry.h: lines_cuv), ordered by page; first [pages + 1]: each page's first word; max_words: the largest word count of a page of this launch
+// (<= kLinesMaxWords: the page's words live in LDS); side: [N] int32 line | [N] int32 word | [pages] int32 n_lines.
+constexpr int kLinesMaxWords = 4096;
+void launch_line_group(const int* cuv, const int* first, int pages, int N, int max_words, int* side, hipStream_t s);
+
 // ---- mlp_fused.hip: x_out = x + fc2(GELU(fc1(LayerNorm(x)))) [+ y = LayerNorm_next(x_out)] for the ViT encoder blocks (bf16, E = 384)
 struct MlpParams {
   const float* x;          // [M][384] f32 residual stream

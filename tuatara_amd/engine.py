@@ -26,7 +26,7 @@ class Config(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("canvas_size", C.c_int), ("mag_ratio", C.c_float),
                 ("text_threshold", C.c_float), ("link_threshold", C.c_float), ("low_text", C.c_float), ("min_area", C.c_int),
                 ("strict_crops", C.c_int), ("max_components", C.c_int), ("verbose", C.c_int), ("crop_mode", C.c_int),
-                ("orient", C.c_int), ("orient_page", C.c_int)]
+                ("orient", C.c_int), ("orient_page", C.c_int), ("lines", C.c_int)]
 
 
 # every symbol include/tuatara_hip.h declares: (name, restype, argtypes)
@@ -60,6 +60,17 @@ SYMBOLS = [
     ("ttr_result_page_orient", _I, [_VP]),
     ("ttr_results_gather_orient", _I, [C.POINTER(_VP), _I, _PI, _PF, _PI]),
     ("ttr_orient_select", _I, [_PF, _PI, _I, _I, _I, _PI, _PI]),
+    ("ttr_result_line_count", _I, [_VP]),
+    ("ttr_result_lines", _PI, [_VP]),
+    ("ttr_result_words", _PI, [_VP]),
+    ("ttr_result_reading_order", _PI, [_VP]),
+    ("ttr_result_line_first", _PI, [_VP]),
+    ("ttr_result_line_bboxes", _PF, [_VP]),
+    ("ttr_result_line_text", _I, [_VP, _I, C.c_char_p, C.c_size_t]),
+    ("ttr_result_page_text", _I, [_VP, C.c_char_p, C.c_size_t]),
+    ("ttr_results_gather_lines", _I, [C.POINTER(_VP), _I, _PI, _PI, _PI, _PI, _PI, _PF]),
+    ("ttr_lines_from_quads", _I, [_PF, _I, _PI, _PI, _PI]),
+    ("ttr_group_lines", _I, [_VP, _PF, _PI, _I, _PI, _PI, _PI]),
     ("ttr_result_free", None, [_VP]),
     ("ttr_result_bboxes", _PF, [_VP]),
     ("ttr_result_ids_all", _PI, [_VP]),
@@ -248,6 +259,17 @@ def orient_select(conf, ids, per_page: bool = False):
     return turns[:n].copy(), int(pt.value)
 
 
+def lines_from_quads(quads):
+    """The text-line rule on the host (ttr_lines_from_quads, no GPU; DESIGN.md "Text lines"): one page's quads f32 [n, 8] (tl, tr, br, bl) ->
+    (line i32 [n] in line order, word i32 [n] the position inside the line, n_lines)."""
+    q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+    n = len(q)
+    line, word, nl = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), C.c_int32()
+    if load().ttr_lines_from_quads(_f(q), n, _i(line), _i(word), C.byref(nl)) != 0:
+        raise EngineError("ttr_lines_from_quads: a coordinate is not finite or has |x| >= 32768")
+    return line[:n].copy(), word[:n].copy(), int(nl.value)
+
+
 def _add_conf(d: dict, conf, prob) -> dict:
     """the conf=True keys of a result dict: "conf" (the kernel's word confidence) and "char_conf" (one probability per character of "text")"""
     d["conf"] = float(conf)
@@ -267,10 +289,16 @@ class PageResult(collections.abc.Sequence):
     rectified crop mode, else None; `conf` f32 [n] and `prob` f32 [n,26] always) and builds dicts only for the items a caller touches.
     with_conf: the dicts carry "conf" and "char_conf" too (DESIGN.md "Recognition confidence").  Word orientation (orient != 0; DESIGN.md
     "Word orientation"): `orient` i32 [n] the chosen turns 0..3 (dicts gain "orient" in degrees), `orient_conf` f32 [n, K] every candidate's
-    conf in ascending turn order, `page_orient` the page's turn; None / None / 0 when orientation is off."""
-    __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient")
+    conf in ascending turn order, `page_orient` the page's turn; None / None / 0 when orientation is off.  Text lines (lines=True; DESIGN.md
+    "Text lines"): `line` / `word` i32 [n] (dicts gain "line" and "word"), `order` i32 [n] the items in reading order, `line_first` i32
+    [n_lines + 1] the lines' offsets into it, `line_bbox` f32 [n_lines, 4]; `lines` the list of {"text", "bbox", "items"} in reading order and
+    `text` the page's text (words joined by ' ', lines by '\\n'); line is None, lines [] and text "" when lines are off."""
+    __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
+                 "line", "word", "order", "line_first", "line_bbox")
 
-    def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0):
+    def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0,
+                 line=None, word=None, order=None, line_first=None, line_bbox=None):
+        self.line, self.word, self.order, self.line_first, self.line_bbox = line, word, order, line_first, line_bbox
         self.texts, self.bbox, self.ids, self.quad = texts, bbox, ids, quad
         n = len(texts)
         self.conf = conf if conf is not None else np.zeros(n, np.float32)
@@ -295,7 +323,25 @@ class PageResult(collections.abc.Sequence):
             _add_conf(d, self.conf[j], self.prob[j])
         if self.orient is not None:
             d["orient"] = 90 * int(self.orient[j])
+        if self.line is not None:
+            d["line"], d["word"] = int(self.line[j]), int(self.word[j])
         return d
+
+    @property
+    def lines(self) -> list:
+        """the page's text lines in reading order: {"text": the words joined by ' ', "bbox": [x1, y1, x2, y2], "items": item indices in word order}"""
+        if self.line is None:
+            return []
+        out = []
+        for l in range(len(self.line_first) - 1):
+            items = self.order[self.line_first[l]:self.line_first[l + 1]].tolist()
+            out.append({"text": " ".join(self.texts[i] for i in items), "bbox": self.line_bbox[l].tolist(), "items": items})
+        return out
+
+    @property
+    def text(self) -> str:
+        """the page's text: its lines in reading order, joined by '\\n' ("" when lines are off)"""
+        return "\n".join(ln["text"] for ln in self.lines)
 
     def __eq__(self, other):
         return list(self) == list(other)
@@ -394,6 +440,23 @@ class Engine:
         """K, the candidate turns per word: 1 (off), 2 (ORIENT_FLIP: 0, 180) or 4 (ORIENT_QUARTER)"""
         return {ORIENT_FLIP: 2, ORIENT_QUARTER: 4}.get(self.cfg.orient, 1)
 
+    @property
+    def grouping_lines(self) -> bool:
+        """lines=True: result dicts carry "line" and "word", PageResult.lines / .text are filled (DESIGN.md "Text lines")"""
+        return self.cfg.lines != 0
+
+    def group_lines(self, quads, first):
+        """ttr_group_lines: line_group_kernel on host quads f32 [N, 8] of several pages (page p owns rows [first[p], first[p + 1])), whatever
+        the engine's `lines` -> (line i32 [N], word i32 [N], n_lines i32 [pages])."""
+        q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        pages, N = len(first) - 1, len(q)
+        if pages < 0 or (pages > 0 and int(first[-1]) != N) or (pages == 0 and N):
+            raise ValueError("first must hold pages + 1 offsets ending at len(quads)")
+        line, word, nl = np.zeros(max(N, 1), np.int32), np.zeros(max(N, 1), np.int32), np.zeros(max(pages, 1), np.int32)
+        self._check(self.lib.ttr_group_lines(self.h, _f(q), _i(first), pages, _i(line), _i(word), _i(nl)))
+        return line[:N].copy(), word[:N].copy(), nl[:pages].copy()
+
     def _quads(self, r, n: int) -> np.ndarray:
         return np.ctypeslib.as_array(self.lib.ttr_result_quads(r), (n, 8)).copy() if n else np.zeros((0, 8), np.float32)
 
@@ -416,12 +479,22 @@ class Engine:
             ot, oc, op = np.zeros(max(total, 1), np.int32), np.zeros((max(total, 1), K), np.float32), np.zeros(max(n, 1), np.int32)
             if self.lib.ttr_results_gather_orient(arr, n, _i(ot), _f(oc), _i(op)) < 0:
                 raise EngineError("ttr_results_gather_orient: the results differ in their candidate count")
-        out, k = [], 0
+        if self.grouping_lines:                 # every page's lines, one call
+            nl, ll, lw, lo = np.zeros(max(n, 1), np.int32), np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.int32)
+            lf, lb = np.zeros(total + n + 1, np.int32), np.zeros((max(total, 1), 4), np.float32)
+            if self.lib.ttr_results_gather_lines(arr, n, _i(nl), _i(ll), _i(lw), _i(lo), _i(lf), _f(lb)) < 0:
+                raise EngineError("ttr_results_gather_lines: bad arguments")
+        out, k, kl = [], 0, 0
         for i in range(n):
             c = int(counts[i])
             orient = (ot[k:k + c], oc[k:k + c], int(op[i])) if self.orienting else (None, None, 0)
+            lines = (None,) * 5
+            if self.grouping_lines:
+                m = int(nl[i])
+                lines = (ll[k:k + c], lw[k:k + c], lo[k:k + c], lf[kl + i:kl + i + m + 1], lb[kl:kl + m])
+                kl += m
             out.append(PageResult(texts[k:k + c], bb[k:k + c], ids[k:k + c], self._quads(arr[i], c) if self.rectified else None,
-                                  cf[k:k + c], pr[k:k + c], conf, *orient))
+                                  cf[k:k + c], pr[k:k + c], conf, *orient, *lines))
             k += c
             self.lib.ttr_result_free(arr[i])
         return out
