@@ -39,6 +39,8 @@ def annotate(image: np.ndarray, result, by_lines: bool = False) -> Image.Image:
             db.polygon([tuple(p) for p in item["quad"]], outline=(0, 255, 0), width=2)
         else:
             db.rectangle([x1, y1, x2, y2], outline=(0, 255, 0), width=2)
+        for ch in item.get("chars", ()):   # character boxes (chars=True): every cell of the word
+            db.polygon([tuple(p) for p in ch["quad"]], outline=(0, 160, 255))
         dp.text((x1, y1), text, fill=(255, 0, 0))
         l, t, r, btm = dr.textbbox((0, 0), text or " ")
         tw, th = r - l, btm - t
@@ -59,8 +61,8 @@ def annotate(image: np.ndarray, result, by_lines: bool = False) -> Image.Image:
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    rectify, lines = "--rectify" in argv, "--lines" in argv
-    argv = [a for a in argv if a not in ("--rectify", "--lines")]
+    rectify, lines, chars = "--rectify" in argv, "--lines" in argv, "--chars" in argv
+    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars")]
     image_path = argv[0] if len(argv) > 0 else os.path.join(HERE, "..", "tests", "data", "funsd_0001129658.png")
     weights_dir = argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "weights")
     outputs_dir = argv[2] if len(argv) > 2 else os.path.join(HERE, "..", "outputs")
@@ -70,6 +72,8 @@ def main(argv=None):
     kw = dict(rectify=True) if rectify else {}
     if lines:
         kw["lines"] = True
+    if chars:
+        kw["chars"] = True
     result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir, **kw)
     print(result)
     os.makedirs(outputs_dir, exist_ok=True)

@@ -10,8 +10,11 @@
 // "Word orientation", TTR_ORIENT_QUARTER, per word) and prints "x1 y1 x2 y2<TAB>degrees<TAB>conf<TAB>text" per item.
 //   ocr_cli --lines <image.png> <weights_dir> <outputs_dir>     groups the words into text lines (DESIGN.md "Text lines") and prints the page's text, one line
 // of the page per output line, in reading order, the words joined by one space.
+//   ocr_cli --chars <image.png> <weights_dir> <outputs_dir>     cuts every word into its characters (DESIGN.md "Character boxes") and prints one line per
+// character, "c x1 y1 x2 y2" with the character's bbox as integers, the words in item order.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <iostream>
 
@@ -65,8 +68,16 @@ int main(int argc, const char** argv) {
       if (!at.empty()) fputc('\n', stdout);
       return 0;
     }
+    if (argc == 5 && std::string(argv[1]) == "--chars") {
+      pngdec::Image img = pngdec::read(argv[2]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[3], argv[4], false, -1, false, false, true);
+      for (const auto& it : items)
+        for (const CharBox& c : it.chars)
+          printf("%s %d %d %d %d\n", c.ch.c_str(), (int)std::lround(c.bbox[0]), (int)std::lround(c.bbox[1]), (int)std::lround(c.bbox[2]), (int)std::lround(c.bbox[3]));
+      return 0;
+    }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--rectify | --conf | --orient | --lines] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--rectify | --conf | --orient | --lines | --chars] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

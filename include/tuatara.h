@@ -35,6 +35,11 @@ std::vector<std::vector<OutputItem>> images_to_data(const std::vector<ImageView>
 // differ from image_to_data's; with rectify = false the crops are image_to_data's.  OutputItem keeps the reference's layout.
 // TUATARA_CROP_MODE=1 in the environment (beside TUATARA_STRICT_CROPS) makes image_to_data / images_to_data use rectified crops too.
 // Every OutputItemEx also carries the recogniser's confidence: `conf` for the word and `char_conf` per character (ttr_result_conf / ttr_result_prob).
+struct CharBox {                   // one character of an item's text (character boxes; DESIGN.md "Character boxes")
+  std::string ch;                  // the character
+  std::vector<float> quad;         // 8: tl, tr, br, bl in image pixels, along the word's baseline
+  std::vector<float> bbox;         // 4: min x, min y, max x, max y of those corners
+};
 struct OutputItemEx {
   std::string text;
   std::vector<float> bbox;  // x1, y1, x2, y2
@@ -42,6 +47,7 @@ struct OutputItemEx {
   float conf = 0.f;                // the recogniser's confidence in `text`, a probability in (0, 1] (DESIGN.md "Recognition confidence")
   std::vector<float> char_conf;    // one probability per character of `text`, in order (char_conf.size() == text.size())
   int orient = 0;                  // word orientation: the turn the word was read at, in degrees clockwise (0, 90, 180, 270; DESIGN.md "Word orientation")
+  std::vector<CharBox> chars;      // character boxes: one per character of `text`, in text order; empty when chars are off (DESIGN.md "Character boxes")
   int line = -1, word = -1;        // text lines: the item's line of its page, in reading order, and its position inside that line; -1 when lines are off (DESIGN.md "Text lines")
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
@@ -64,6 +70,14 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
                                            std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines);
 std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
                                                          bool rectify, int orient, bool orient_page, bool lines);
+// Character boxes (opt-in; DESIGN.md "Character boxes"): chars = true also gives every item one CharBox per character of its text, cut from the
+// detector's region map along the word's baseline.  chars = false is the calls above, unless TUATARA_CHARS=1 is set in the environment, which
+// turns them on for image_to_data / images_to_data / every call above.  Items, order, boxes and text do not change.  orient = -1 leaves the
+// orientation to TUATARA_ORIENT, lines = false leaves the lines to TUATARA_LINES.
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

@@ -61,6 +61,8 @@ typedef struct ttr_config {
   int orient_page;       /* 0 (default): the turn is chosen per word; 1: once per page */
   int lines;             /* 0 (default): off, the same kernels and bits as without the field; 1: the words are also grouped into text lines in
                             reading order (DESIGN.md "Text lines"); other values make ttr_create fail.  Needs max_components <= 4096 */
+  int chars;             /* 0 (default): off, the same kernels and bits as without the field; 1: every item also carries one quadrilateral and one bbox per
+                            character of its text (DESIGN.md "Character boxes"); other values make ttr_create fail */
 } ttr_config;
 
 void ttr_config_default(ttr_config* cfg);
@@ -186,6 +188,41 @@ int ttr_lines_from_quads(const float* quads, int n, int32_t* line, int32_t* word
  * [first[p], first[p + 1]), first[0] = 0, at most 4096 per page - are uploaded, line_group_kernel runs once, and line[first[pages]],
  * word[first[pages]] and n_lines[pages] come back.  Returns 0, -1 on error (ttr_last_error). */
 int ttr_group_lines(ttr_engine* e, const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines);
+
+/* Character boxes (ttr_config.chars = 1; DESIGN.md "Character boxes"), every entry point but ttr_pages_to_data_dev_sharded (which refuses chars != 0).
+ * The items, their order and every other output are those of chars = 0; every item also carries one quadrilateral and one bbox per character of its
+ * text, in text order, cut from the detector's region map along the word's baseline (of the turned quad when orientation is on).
+ * ttr_result_char_count: the characters of item i (= strlen of its text).  ttr_result_char_first: [count + 1] offsets of the items' characters.
+ * ttr_result_char_quads: [total][8] tl, tr, br, bl in image pixels.  ttr_result_char_bboxes: [total][4] min x, min y, max x, max y of those corners.
+ * ttr_result_char_cuts: [count][27] the cuts b[0..K] along the baseline in 1/256 of the 128 profile columns (0..32768), -1 beyond K.
+ * ttr_result_char_modes: [count] 0 = even split of the inked extent (no ink, or fewer than two columns per character), 1 = valley cuts.
+ * ttr_result_char_profiles: [count][128] the word's profile.  With chars = 0, or for an empty result, the pointers are NULL and the count is 0. */
+int ttr_result_char_count(const ttr_result* r, int i);
+const int32_t* ttr_result_char_first(const ttr_result* r);
+const float* ttr_result_char_quads(const ttr_result* r);
+const float* ttr_result_char_bboxes(const ttr_result* r);
+const int32_t* ttr_result_char_cuts(const ttr_result* r);
+const int32_t* ttr_result_char_modes(const ttr_result* r);
+const uint8_t* ttr_result_char_profiles(const ttr_result* r);
+/* ... for a batch of results in one call (any output may be NULL): char_first: per result its count + 1 offsets (local to the result), result
+ * after result - total items + n entries; char_quads [total characters][8], char_bboxes [..][4]; cuts [total items][27], modes [total items],
+ * profiles [total items][128] in ttr_results_gather's item order.  A result without characters (chars = 0, or empty) contributes zeros to
+ * char_first, -1 cuts, 0 modes and profiles.  Returns the total character count, -1 on bad arguments. */
+int ttr_results_gather_chars(ttr_result* const* rs, int n, int32_t* char_first, float* char_quads, float* char_bboxes, int32_t* cuts, int32_t* modes,
+                             uint8_t* profiles);
+/* The rule on the host, no GPU.  ttr_char_cuts_from_profile: one profile q128, K in 0..26 and qlow = (int)(low_text * 255.f) -> cuts27, *mode.
+ * ttr_chars_from_map: n words on ONE region plane tnorm [H2][W2] (f32, normalised) of a page whose canvas ratio is `ratio`; quads [n][8] as
+ * ttr_result_quad gives them, turns [n] in 0..3, nchars [n] in 0..26 -> cuts [n][27], modes [n], profiles [n][128].
+ * ttr_char_quads_from_cuts: one word's quad, turn and cuts -> quads_out [K][8], bboxes_out [K][4].  Each returns 0; -1 on bad arguments, a
+ * coordinate that is not finite or has |x| >= 32768, or a ratio outside (0, 2048]. */
+int ttr_char_cuts_from_profile(const uint8_t* q128, int K, int qlow, int32_t* cuts27, int32_t* mode);
+int ttr_chars_from_map(const float* tnorm, int H2, int W2, float ratio, float low_text, const float* quads, const int32_t* turns, const int32_t* nchars, int n,
+                       int32_t* cuts, int32_t* modes, uint8_t* profiles);
+int ttr_char_quads_from_cuts(const float* quad, int turn, const int32_t* cuts27, int K, float* quads_out, float* bboxes_out);
+/* The rule on the GPU as a stage entry point, whatever the engine's `chars`: the same arguments as ttr_chars_from_map, the map and the words are
+ * uploaded and char_cut_kernel runs once.  Refuses while batches stream.  Returns 0, -1 on error (ttr_last_error). */
+int ttr_char_cuts(ttr_engine* e, const float* tnorm, int H2, int W2, float ratio, float low_text, const float* quads, const int32_t* turns, const int32_t* nchars,
+                  int n, int32_t* cuts, int32_t* modes, uint8_t* profiles);
 
 /* ---- multi-GPU: RCCL in the C++ host -----------------------------------------------------------------
  * One process per GPU, one engine per process.  The OCR path has no data-path collective: pages are independent.  The one exchange is

@@ -36,7 +36,7 @@ void ttr_config_default(ttr_config* c) {
   c->precision = TTR_PREC_F16X4; c->device = 0; c->canvas_size = 1024; c->mag_ratio = 1.0f;
   c->text_threshold = 0.7f; c->link_threshold = 0.4f; c->low_text = 0.4f; c->min_area = 10;
   c->strict_crops = 0; c->max_components = 4096; c->verbose = 0; c->crop_mode = TTR_CROP_BOUNDING;
-  c->orient = TTR_ORIENT_OFF; c->orient_page = 0; c->lines = 0;
+  c->orient = TTR_ORIENT_OFF; c->orient_page = 0; c->lines = 0; c->chars = 0;
 }
 
 const char* ttr_last_error(void) { return g_last_error.c_str(); }
@@ -273,6 +273,82 @@ int ttr_group_lines(ttr_engine* e, const float* quads, const int32_t* first, int
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_group_lines");
   E.group_lines(quads, first, pages, line, word, n_lines);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_result_char_count(const ttr_result* r, int i) {
+  if (!r || r->r.char_first.empty() || i < 0 || (size_t)i + 1 >= r->r.char_first.size()) return 0;
+  return r->r.char_first[(size_t)i + 1] - r->r.char_first[(size_t)i];
+}
+
+const int32_t* ttr_result_char_first(const ttr_result* r) { return r && !r->r.char_first.empty() ? r->r.char_first.data() : nullptr; }
+
+const float* ttr_result_char_quads(const ttr_result* r) { return r && !r->r.char_quad.empty() ? r->r.char_quad.data() : nullptr; }
+
+const float* ttr_result_char_bboxes(const ttr_result* r) { return r && !r->r.char_bbox.empty() ? r->r.char_bbox.data() : nullptr; }
+
+const int32_t* ttr_result_char_cuts(const ttr_result* r) { return r && !r->r.char_cuts.empty() ? r->r.char_cuts.data() : nullptr; }
+
+const int32_t* ttr_result_char_modes(const ttr_result* r) { return r && !r->r.char_mode.empty() ? r->r.char_mode.data() : nullptr; }
+
+const uint8_t* ttr_result_char_profiles(const ttr_result* r) { return r && !r->r.char_profile.empty() ? r->r.char_profile.data() : nullptr; }
+
+int ttr_results_gather_chars(ttr_result* const* rs, int n, int32_t* char_first, float* char_quads, float* char_bboxes, int32_t* cuts, int32_t* modes,
+                             uint8_t* profiles) {
+  if (!rs || n < 0) return -1;
+  size_t oi = 0, oc = 0, of = 0;
+  for (int i = 0; i < n; ++i) {
+    static const Result none;
+    const Result& r = rs[i] ? rs[i]->r : none;
+    const size_t cnt = r.text.size();
+    const bool has = cnt > 0 && r.char_first.size() == cnt + 1;
+    const size_t nc = has ? (size_t)r.char_first[cnt] : 0;
+    if (char_first) { if (has) std::copy(r.char_first.begin(), r.char_first.end(), char_first + of); else std::fill(char_first + of, char_first + of + cnt + 1, 0); }
+    if (char_quads && nc) std::copy(r.char_quad.begin(), r.char_quad.end(), char_quads + 8 * oc);
+    if (char_bboxes && nc) std::copy(r.char_bbox.begin(), r.char_bbox.end(), char_bboxes + 4 * oc);
+    if (cuts) { if (has) std::copy(r.char_cuts.begin(), r.char_cuts.end(), cuts + 27 * oi); else std::fill(cuts + 27 * oi, cuts + 27 * (oi + cnt), -1); }
+    if (modes) { if (has) std::copy(r.char_mode.begin(), r.char_mode.end(), modes + oi); else std::fill(modes + oi, modes + oi + cnt, 0); }
+    if (profiles) { if (has) std::copy(r.char_profile.begin(), r.char_profile.end(), profiles + 128 * oi); else std::fill(profiles + 128 * oi, profiles + 128 * (oi + cnt), (uint8_t)0); }
+    oi += cnt; oc += nc; of += cnt + 1;
+  }
+  return (int)oc;
+}
+
+int ttr_char_cuts_from_profile(const uint8_t* q128, int K, int qlow, int32_t* cuts27, int32_t* mode) {
+  if (!q128 || !cuts27 || !mode || K < 0 || K > kCharsMax) return -1;
+  chars_cuts_from_profile(q128, K, qlow, cuts27, mode);
+  return 0;
+}
+
+int ttr_chars_from_map(const float* tnorm, int H2, int W2, float ratio, float low_text, const float* quads, const int32_t* turns, const int32_t* nchars, int n,
+                       int32_t* cuts, int32_t* modes, uint8_t* profiles) {
+  if (n < 0 || (n > 0 && (!tnorm || H2 <= 0 || W2 <= 0 || !quads || !turns || !nchars || !cuts || !modes || !profiles))) return -1;
+  const double k = chars_scale(ratio);
+  const int qlow = (int)(low_text * 255.f);
+  for (int c = 0; c < n; ++c) {
+    int64_t fx[6];
+    if (turns[c] < 0 || turns[c] > 3 || nchars[c] < 0 || nchars[c] > kCharsMax || !chars_coef(quads + 8 * (size_t)c, turns[c], k, fx)) return -1;
+    chars_profile(tnorm, H2, W2, fx, profiles + 128 * (size_t)c);
+    chars_cuts_from_profile(profiles + 128 * (size_t)c, nchars[c], qlow, cuts + 27 * (size_t)c, modes + c);
+  }
+  return 0;
+}
+
+int ttr_char_quads_from_cuts(const float* quad, int turn, const int32_t* cuts27, int K, float* quads_out, float* bboxes_out) {
+  if (!quad || turn < 0 || turn > 3 || K < 0 || K > kCharsMax || (K > 0 && (!cuts27 || !quads_out || !bboxes_out))) return -1;
+  chars_quads_from_cuts(quad, turn, cuts27, K, quads_out, bboxes_out);
+  return 0;
+}
+
+int ttr_char_cuts(ttr_engine* e, const float* tnorm, int H2, int W2, float ratio, float low_text, const float* quads, const int32_t* turns, const int32_t* nchars,
+                  int n, int32_t* cuts, int32_t* modes, uint8_t* profiles) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && (!tnorm || !quads || !turns || !nchars))) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_char_cuts");
+  E.char_cuts(tnorm, H2, W2, ratio, low_text, quads, turns, nchars, n, cuts, modes, profiles);
   return 0;
   TTR_GUARD_END(-1)
 }

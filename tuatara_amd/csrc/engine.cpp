@@ -402,6 +402,7 @@ Engine::Engine(const std::string& dir, const ttr_config& c) : cfg(c) {
   if (cfg.orient_page != 0 && cfg.orient_page != 1) throw std::runtime_error("orient_page must be 0 (per word) or 1 (per page)");
   if (cfg.lines != 0 && cfg.lines != 1) throw std::runtime_error("lines must be 0 (off) or 1 (group the words into text lines)");
   if (cfg.lines && cfg.max_components > kLinesMaxWords) throw std::runtime_error("lines = 1 needs max_components <= " + std::to_string(kLinesMaxWords));
+  if (cfg.chars != 0 && cfg.chars != 1) throw std::runtime_error("chars must be 0 or 1");
   prec = cfg.precision == TTR_PREC_F32 ? kF32 : cfg.precision == TTR_PREC_F16X4 ? kSplit : kBF16;
   es = prec == kBF16 ? 2 : 4;
   int ndev = 0;
@@ -439,6 +440,7 @@ Engine::~Engine() {
   for (auto& x : group_ev) (void)hipEventDestroy(x);
   if (copy_ev) (void)hipEventDestroy(copy_ev);
   for (auto& x : done_ev) if (x) (void)hipEventDestroy(x);
+  for (auto& sl : chars_ev) for (auto& x : sl) if (x) (void)hipEventDestroy(x);
   for (auto& sl : evr) for (auto& x : sl) if (x) (void)hipEventDestroy(x);
   for (auto& x : up_ev) if (x) (void)hipEventDestroy(x);
   if (up_stream) (void)hipStreamDestroy(up_stream);

@@ -273,6 +273,11 @@ struct Result {
   int n_lines = 0;
   std::string line_text(int l) const;       // the members' text in word order, joined by ' '
   std::string page_text() const;            // the lines joined by '\n'
+  // character boxes (cfg.chars = 1; DESIGN.md "Character boxes"): empty when off
+  std::vector<int32_t> char_first;          // [items + 1]: item i owns characters [char_first[i], char_first[i + 1])
+  std::vector<float> char_quad, char_bbox;  // 8 / 4 per character: tl, tr, br, bl; min x, min y, max x, max y
+  std::vector<int32_t> char_cuts, char_mode;   // 27 / 1 per item: the cuts b[0..K] in 1/256 column (-1 beyond K); 0 uniform, 1 valley cuts
+  std::vector<uint8_t> char_profile;        // 128 per item: the word's profile q
 };
 
 struct CclBatch {   // device workspaces of the CCL stage for a batch of equally sized pages
@@ -413,6 +418,9 @@ struct Engine {
   PinnedBuf h_orient_in[2], h_orient[2];          // ... per slot: staging of orient_in, host copy of the side block
   DevBuf lines_in, lines_side;                    // text lines: the words' cuv | page firsts; the side block (lines.hip)
   PinnedBuf h_lines_in[2], h_lines[2];            // ... per slot: staging of lines_in, host copy of the side block
+  DevBuf chars_map[2], chars_in, chars_side;      // character boxes: per slot the batch's region planes (a copy of ccl.tnorm); coef | page_of | turns | nchars; the side block (chars.hip)
+  PinnedBuf h_chars_in[2], h_chars[2];            // ... per slot: staging of chars_in, host copy of the side block
+  hipEvent_t chars_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // ... per slot: the planes are copied; char_cut_kernel has read them (created with the first chars batch)
   CclBatch ccl;
   PinnedBuf h_counters, h_cand, h_rows, h_rects_f, h_rects[2], h_coef[2], h_ids[2];   // (h_coef: crop_mode = TTR_CROP_RECTIFIED only)   // pinned staging of the small host <-> device transfers
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -685,10 +693,20 @@ struct Engine {
   // the stage form (ttr_group_lines): host quads [first[pages]][8] of several pages -> line, word [first[pages]], n_lines [pages]
   void group_lines(const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines);
 
+  // character boxes: detect_enqueue keeps the batch's region planes (keep_batch_map, behind its CCL); stage_batch_chars writes every word's coefficients
+  // (all four turns when orientation is on) and page into the pinned staging of slot sl (host only); cut_batch_chars copies them, runs char_cut_kernel
+  // behind the recogniser (K and the turn are read on the device) and copies the side block to h_chars[sl]
+  void keep_batch_map(const PageBatch& B);
+  void stage_batch_chars(const PageBatch& B, int sl);
+  void cut_batch_chars(const PageBatch& B, int sl, const int* ids, const int* turns);
+  // the stage form (ttr_char_cuts): a host map and host quads / turns / nchars through char_cut_kernel
+  void char_cuts(const float* tnorm, int H2, int W2, float ratio, float low_text, const float* quads, const int32_t* turns, const int32_t* nchars, int n,
+                 int32_t* cuts, int32_t* modes, uint8_t* profiles);
+
   void finish(PageBatch& B, std::vector<Result>& results);
   // results[pg] for every page of B from its boxes and the decoded rows of its crops (crop c is row c); side: the orientation side block
-  // of the batch (orient.hip) or null; lines_side: the text lines' side block (lines.hip) or null
-  void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, std::vector<Result>& results);
+  // of the batch (orient.hip) or null; lines_side: the text lines' side block (lines.hip) or null; chars_side: the characters' (chars.hip) or null
+  void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, std::vector<Result>& results);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it

@@ -208,6 +208,7 @@ void Engine::detect_enqueue(PageBatch& B) {
     }
   }
   if (two) TTR_HIP_CHECK(hipStreamWaitEvent(stream, lane_done, 0));       // the batch's detector is complete when the main stream gets here
+  if (cfg.chars) keep_batch_map(B);                                       // character boxes: the next batch's detector overwrites tnorm before this batch's recogniser runs
   range_fetch(kRangeDet0 + (B.slot & 1));
   while ((int)group_ev.size() <= groups) { hipEvent_t e; TTR_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); group_ev.push_back(e); }
   TTR_HIP_CHECK(hipEventRecord(group_ev[groups], stream));                // (behind the word's copy: detect_collect_local waits for it)
@@ -393,9 +394,86 @@ void Engine::group_lines(const float* quads, const int32_t* first, int pages, in
   if (n_lines) std::copy(side + 2 * (size_t)N, side + 2 * (size_t)N + pages, n_lines);
 }
 
+void Engine::keep_batch_map(const PageBatch& B) {
+  const int sl = B.slot & 1;
+  for (auto& x : chars_ev[sl]) if (!x) TTR_HIP_CHECK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+  const size_t bytes = (size_t)B.n * B.H2 * B.W2 * 4;
+  chars_map[sl].ensure(bytes);
+  TTR_HIP_CHECK(hipStreamWaitEvent(stream, chars_ev[sl][1], 0));   // the slot's previous batch may still be cut on the recogniser's stream (no-op before the first)
+  TTR_HIP_CHECK(hipMemcpyAsync(chars_map[sl].p, ccl.tnorm.p, bytes, hipMemcpyDeviceToDevice, stream));
+  TTR_HIP_CHECK(hipEventRecord(chars_ev[sl][0], stream));
+}
+
+static size_t chars_in_bytes(int N, int KT) { return (size_t)N * KT * 48 + (size_t)N * 4; }   // coef int64 [N][KT][6] | page_of int32 [N]
+
+void Engine::stage_batch_chars(const PageBatch& B, int sl) {
+  const int N = B.N, KT = orient_k() > 1 ? 4 : 1;
+  h_chars_in[sl].ensure(chars_in_bytes(N, KT));
+  int64_t* coef = h_chars_in[sl].as<int64_t>();
+  int32_t* page_of = reinterpret_cast<int32_t*>(coef + (size_t)N * KT * 6);
+  const double k = chars_scale(B.g.ratio);
+  std::vector<float> q;
+  q.reserve(8);
+  int c = 0;
+  for (int pg = 0; pg < B.n; ++pg)
+    for (const RRect& b : B.boxes[pg]) {                       // (crop order: page after page)
+      q.clear();
+      push_quad(b, q);
+      if (c >= N) throw std::runtime_error("character boxes: box count does not match the crop count");
+      for (int t = 0; t < KT; ++t)
+        if (!chars_coef(q.data(), t, k, coef + ((size_t)c * KT + t) * 6)) throw std::runtime_error("character boxes: a word's corner is not finite or lies beyond 32768 px");
+      page_of[c] = pg;
+      ++c;
+    }
+  if (c != N) throw std::runtime_error("character boxes: box count does not match the crop count");
+}
+
+void Engine::cut_batch_chars(const PageBatch& B, int sl, const int* ids, const int* turns) {
+  const int N = B.N, KT = orient_k() > 1 ? 4 : 1;
+  if (!chars_ev[sl & 1][0] || chars_map[sl & 1].cap < (size_t)B.n * B.H2 * B.W2 * 4) throw std::runtime_error("character boxes: the batch's region planes were not kept");
+  const size_t in_b = chars_in_bytes(N, KT), side_b = char_side_bytes(N);
+  chars_in.ensure(in_b); chars_side.ensure(side_b); h_chars[sl].ensure(side_b);
+  TTR_HIP_CHECK(hipMemcpyAsync(chars_in.p, h_chars_in[sl].p, in_b, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipStreamWaitEvent(stream, chars_ev[sl & 1][0], 0));
+  launch_char_cut(chars_map[sl & 1].as<float>(), B.H2, B.W2, chars_in.as<int64_t>(), KT, reinterpret_cast<const int*>(chars_in.as<int64_t>() + (size_t)N * KT * 6), turns, ids,
+                  nullptr, (int)(cfg.low_text * 255.f), N, chars_side.as<int>(), stream);
+  TTR_HIP_CHECK(hipEventRecord(chars_ev[sl & 1][1], stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(h_chars[sl].p, chars_side.p, side_b, hipMemcpyDeviceToHost, stream));
+}
+
+void Engine::char_cuts(const float* tnorm, int H2, int W2, float ratio, float low_text, const float* quads, const int32_t* turns, const int32_t* nchars, int n,
+                       int32_t* cuts, int32_t* modes, uint8_t* profiles) {
+  if (n <= 0) return;
+  if (H2 <= 0 || W2 <= 0 || (size_t)H2 * W2 > ((size_t)1 << 28)) throw std::runtime_error("ttr_char_cuts: bad map size");
+  const double k = chars_scale(ratio);
+  // chars_in: coef int64 [n][4][6] | page_of int32 [n] (all 0) | turns int32 [n] | nchars int32 [n]
+  const size_t coef_b = (size_t)n * 192, in_b = coef_b + (size_t)n * 12, side_b = char_side_bytes(n), map_b = (size_t)H2 * W2 * 4;
+  h_chars_in[0].ensure(in_b); chars_in.ensure(in_b); chars_side.ensure(side_b); h_chars[0].ensure(side_b); chars_map[0].ensure(map_b);
+  int64_t* coef = h_chars_in[0].as<int64_t>();
+  int32_t* tail = reinterpret_cast<int32_t*>(coef + (size_t)n * 24);
+  for (int c = 0; c < n; ++c) {
+    for (int t = 0; t < 4; ++t)
+      if (!chars_coef(quads + 8 * (size_t)c, t, k, coef + ((size_t)c * 4 + t) * 6)) throw std::runtime_error("ttr_char_cuts: a coordinate is not finite or has |x| >= 32768, or the ratio is out of range");
+    if (turns[c] < 0 || turns[c] > 3) throw std::runtime_error("ttr_char_cuts: a turn outside 0..3");
+    if (nchars[c] < 0 || nchars[c] > kCharsMax) throw std::runtime_error("ttr_char_cuts: a character count outside 0..26");
+    tail[c] = 0; tail[(size_t)n + c] = turns[c]; tail[2 * (size_t)n + c] = nchars[c];
+  }
+  TTR_HIP_CHECK(hipMemcpyAsync(chars_map[0].p, tnorm, map_b, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(chars_in.p, coef, in_b, hipMemcpyHostToDevice, stream));
+  const int* d_tail = reinterpret_cast<const int*>(chars_in.as<int64_t>() + (size_t)n * 24);
+  launch_char_cut(chars_map[0].as<float>(), H2, W2, chars_in.as<int64_t>(), 4, d_tail, d_tail + n, nullptr, d_tail + 2 * (size_t)n, (int)(low_text * 255.f), n, chars_side.as<int>(), stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(h_chars[0].p, chars_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  const int32_t* side = h_chars[0].as<int32_t>();
+  if (cuts) std::copy(side, side + (size_t)n * 27, cuts);
+  if (modes) std::copy(side + (size_t)n * 27, side + (size_t)n * 28, modes);
+  if (profiles) memcpy(profiles, side + (size_t)n * 28, (size_t)n * 128);
+}
+
 void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
   const int line_words = cfg.lines && N > 0 ? stage_batch_lines(B, sl) : 0;   // text lines: the host part, before anything of this batch is enqueued
+  if (cfg.chars && N > 0) stage_batch_chars(B, sl);                          // character boxes: likewise
   range_use(kRangeRec0 + (sl & 1));          // the recogniser's kernels of this batch watch the slot's own word
   B.rows = std::max(N, comm ? B.cap : 0);   // the output block's rows (RecOut): with a communicator, the gathered payload's rows per rank
   const size_t block = (size_t)B.rows * kRecWords * 4;
@@ -420,6 +498,7 @@ void Engine::recog_enqueue(PageBatch& B) {
       launch_orient_select(out.ids, out.prob, out.conf, cand.ids, cand.prob, cand.conf, reinterpret_cast<const int*>(orient_in.as<uint8_t>() + first_off), B.n, N, K,
                            cfg.orient_page, orient_side.as<int>(), stream);
     }
+    if (cfg.chars) cut_batch_chars(B, sl, out.ids, T ? orient_side.as<int>() : nullptr);   // character boxes: K and the turn are the chosen reading's, read on the device
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
     TTR_HIP_CHECK(hipMemcpyAsync(h_ids[sl].p, ids_dev.p, block, hipMemcpyDeviceToHost, stream));   // ids, prob and conf in one copy
     if (T) TTR_HIP_CHECK(hipMemcpyAsync(h_orient[sl].p, orient_side.p, side_b, hipMemcpyDeviceToHost, stream));
@@ -457,12 +536,13 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   }
   const int32_t* side = orient_k() > 1 && N > 0 ? h_orient[B.slot].as<int32_t>() : nullptr;
   const int32_t* lines_block = cfg.lines && N > 0 ? h_lines[B.slot].as<int32_t>() : nullptr;   // the side block (lines.hip)
-  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, results);
+  const void* chars_block = cfg.chars && N > 0 ? h_chars[B.slot].p : nullptr;                   // the side block (chars.hip)
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, results);
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
 
-void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, std::vector<Result>& results) {
+void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, std::vector<Result>& results) {
   const int n = B.n, N = B.N, K = orient_k();
   const std::vector<int> first = page_first(B.page_of, n);
   // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
@@ -509,6 +589,28 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
         }
       }
     }
+    if (chars_side && cnt > 0) {   // [N][27] cuts | [N] mode | [N][128] u8 profile -> the page's characters
+      const int32_t* cuts = static_cast<const int32_t*>(chars_side);
+      const int32_t* modes = cuts + (size_t)N * 27;
+      const uint8_t* prof = reinterpret_cast<const uint8_t*>(cuts + (size_t)N * 28);
+      r.char_cuts.assign(&cuts[(size_t)c0 * 27], &cuts[(size_t)(c0 + cnt) * 27]);
+      r.char_mode.assign(&modes[c0], &modes[c0 + cnt]);
+      r.char_profile.assign(&prof[(size_t)c0 * 128], &prof[(size_t)(c0 + cnt) * 128]);
+      r.char_first.assign((size_t)cnt + 1, 0);
+      for (int k = 0; k < cnt; ++k) {
+        const int K = text_chars(&r.ids[(size_t)k * 26]);
+        if (!chars_cuts_valid(&r.char_cuts[(size_t)k * 27], K) || (r.char_mode[k] != 0 && r.char_mode[k] != 1))
+          throw std::runtime_error("character boxes: the side block of word " + std::to_string(k) + " of page " + std::to_string(pg) + " does not hold " + std::to_string(K) + " ascending cells");
+        r.char_first[(size_t)k + 1] = r.char_first[k] + K;
+      }
+      const size_t total = (size_t)r.char_first[cnt];
+      r.char_quad.assign(total * 8, 0.f); r.char_bbox.assign(total * 4, 0.f);
+      for (int k = 0; k < cnt; ++k) {
+        const int K = r.char_first[(size_t)k + 1] - r.char_first[k];
+        chars_quads_from_cuts(&r.quad[(size_t)k * 8], r.orient.empty() ? 0 : r.orient[k], &r.char_cuts[(size_t)k * 27], K, r.char_quad.data() + 8 * (size_t)r.char_first[k],
+                              r.char_bbox.data() + 4 * (size_t)r.char_first[k]);
+      }
+    }
   };
   // pages decode independently
   if (N >= 256) parallel_pages(n, decode_page);
@@ -543,6 +645,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");
   if (cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("latency mode does not support word orientation: create the engine with orient = TTR_ORIENT_OFF");
   if (cfg.lines) throw std::runtime_error("latency mode does not support text lines: create the engine with lines = 0");
+  if (cfg.chars) throw std::runtime_error("latency mode does not support character boxes: create the engine with chars = 0");
   if (q1.live || q2.live) throw std::runtime_error("streamed batches are in flight: call ttr_stream_flush until it returns none");
   Comm* const c = comm;
   const int world = c->world, rank = c->rank;
@@ -591,7 +694,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   for (int r = 0; r < world; ++r) total[r] = std::max(0, std::min(per, N - r * per));
   Gathered g;
   compact_gathered(h_gath[0].as<int32_t>(), per, total, g);
-  decode_pages(B, RecRows{g.ids.data(), g.prob.data(), g.conf.data()}, nullptr, nullptr, results);
+  decode_pages(B, RecRows{g.ids.data(), g.prob.data(), g.conf.data()}, nullptr, nullptr, nullptr, results);
 }
 
 void Engine::stream_push(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& prev_results, int& prev_n) {

@@ -102,7 +102,7 @@ void turn_coef(const Pt2f quad[4], int turn, int64_t fixed[6]) {
   deskew_fixed(cf, fixed);
 }
 
-static int text_chars(const int32_t* ids) {   // |S| of the confidence rule: characters before the first EOS (id 0), id 88 and ids outside [0, 98) dropped
+int text_chars(const int32_t* ids) {   // |S| of the confidence rule: characters before the first EOS (id 0), id 88 and ids outside [0, 98) dropped
   int k = 0;
   for (int p = 0; p < 26; ++p) {
     if (ids[p] == 0) break;
@@ -230,6 +230,116 @@ bool lines_reading_order(const int32_t* line, const int32_t* word, int n, int n_
     if (o >= 0) return false;
     o = i;
   }
+  return true;
+}
+
+// ---------------------------------------------------------------- character boxes (DESIGN.md "Character boxes")
+double chars_scale(float ratio) {
+  const float ratio_w = 1.f / ratio;
+  const float twice = ratio_w * 2.f;
+  return 1.0 / (double)twice;
+}
+
+bool chars_coef(const float* q, int turn, double k, int64_t fixed[6]) {
+  if (!(k > 0.) || !(k <= 1024.)) return false;
+  for (int i = 0; i < 8; ++i)
+    if (!std::isfinite(q[i]) || std::fabs(q[i]) >= 32768.f) return false;
+  const float* tl = q + 2 * (turn & 3);
+  const float* tr = q + 2 * ((turn + 1) & 3);
+  const float* bl = q + 2 * ((turn + 3) & 3);
+  for (int a = 0; a < 2; ++a) {   // x, then y: one statement per rounding (no contraction)
+    const double A = (double)tr[a] - (double)tl[a], B = (double)bl[a] - (double)tl[a];
+    const double Ak = A * k, Bk = B * k;
+    const double Au = Ak / (double)kCharsU, Bv = Bk / (double)kCharsV;
+    const double hA = 0.5 * Au, hB = 0.5 * Bv;
+    double x0 = (double)tl[a] * k;
+    x0 = x0 + hA;
+    x0 = x0 + hB;
+    const double s0 = 65536. * x0, s1 = 65536. * Au, s2 = 65536. * Bv;
+    fixed[3 * a] = (int64_t)std::llrint(s0); fixed[3 * a + 1] = (int64_t)std::llrint(s1); fixed[3 * a + 2] = (int64_t)std::llrint(s2);
+  }
+  return true;
+}
+
+void chars_profile(const float* T, int H2, int W2, const int64_t fx[6], uint8_t q[128]) {
+  for (int u = 0; u < kCharsU; ++u) {
+    float P = 0.f;
+    for (int v = 0; v < kCharsV; ++v) {
+      const int64_t sx = (fx[0] + u * fx[1] + v * fx[2] + 32768) >> 16, sy = (fx[3] + u * fx[4] + v * fx[5] + 32768) >> 16;
+      const int ix = (int)std::min<int64_t>(std::max<int64_t>(sx, 0), W2 - 1), iy = (int)std::min<int64_t>(std::max<int64_t>(sy, 0), H2 - 1);
+      const float t = T[(size_t)iy * W2 + ix];
+      P = v == 0 ? t : std::fmax(P, t);     // (fmaxf: a NaN loses against a number)
+    }
+    const float s = std::fmax(P, 0.f) * 255.f;
+    q[u] = (uint8_t)(int)std::fmin(s, 255.f);
+  }
+}
+
+void chars_cuts_from_profile(const uint8_t* q, int K, int qlow, int32_t cuts[27], int32_t* mode) {
+  std::fill(cuts, cuts + kCharsMax + 1, -1);
+  *mode = 0;
+  if (K <= 0) return;
+  K = std::min(K, kCharsMax);
+  int u0 = -1, u1 = 0;
+  for (int u = 0; u < kCharsU; ++u)
+    if ((int)q[u] > qlow) { if (u0 < 0) u0 = u; u1 = u + 1; }
+  const bool ink = u0 >= 0;
+  if (!ink) { u0 = 0; u1 = kCharsU; }
+  const int L = u1 - u0;
+  if (!ink || L < 2 * K) {                         // the uniform fallback
+    for (int j = 0; j <= K; ++j) cuts[j] = 256 * u0 + (256 * L * j) / K;
+    return;
+  }
+  *mode = 1;
+  constexpr int32_t kInf = 0x3fffffff;
+  const int wlo = std::max(1, L / (2 * K)), whi = std::min(L, (2 * L + K - 1) / K);
+  int32_t D[2][kCharsU + 1];
+  uint8_t arg[kCharsMax + 1][kCharsU + 1];
+  std::fill(D[0], D[0] + kCharsU + 1, kInf);
+  D[0][u0] = 0;
+  for (int j = 1; j <= K; ++j) {
+    const int32_t* prev = D[(j - 1) & 1];
+    int32_t* cur = D[j & 1];
+    std::fill(cur, cur + kCharsU + 1, kInf);
+    for (int c = j == K ? u1 : u0 + 1; c <= u1; ++c) {
+      int32_t best = kInf; int bc = 0;
+      for (int cp = std::max(u0, c - whi); cp <= c - wlo; ++cp) {
+        if (prev[cp] >= kInf) continue;
+        const int w = c - cp, dev = w * K - L;
+        const int32_t cost = prev[cp] + (j > 1 ? (int)q[cp - 1] + (int)q[cp] : 0) + (kCharsLam * (dev < 0 ? -dev : dev)) / L;
+        if (cost < best) { best = cost; bc = cp; }   // (strict: ties go to the smallest c')
+      }
+      cur[c] = best; arg[j][c] = (uint8_t)bc;
+    }
+  }
+  int c = u1;
+  for (int j = K; j >= 1; --j) { cuts[j] = 256 * c; c = arg[j][c]; }
+  cuts[0] = 256 * c;
+}
+
+void chars_quads_from_cuts(const float* q, int turn, const int32_t* cuts, int K, float* quads, float* bboxes) {
+  double p[4][2];
+  for (int j = 0; j < 4; ++j) { p[j][0] = q[2 * ((j + turn) & 3)]; p[j][1] = q[2 * ((j + turn) & 3) + 1]; }   // tl', tr', br', bl'
+  for (int j = 0; j < K; ++j) {
+    const double t0 = (double)cuts[j] / 32768., t1 = (double)cuts[j + 1] / 32768.;
+    float* o = quads + 8 * (size_t)j;
+    for (int a = 0; a < 2; ++a) {
+      const double top = p[1][a] - p[0][a], bot = p[2][a] - p[3][a];
+      o[a] = (float)(p[0][a] + t0 * top); o[2 + a] = (float)(p[0][a] + t1 * top);
+      o[4 + a] = (float)(p[3][a] + t1 * bot); o[6 + a] = (float)(p[3][a] + t0 * bot);
+    }
+    float* b = bboxes + 4 * (size_t)j;
+    b[0] = std::min(std::min(o[0], o[2]), std::min(o[4], o[6])); b[1] = std::min(std::min(o[1], o[3]), std::min(o[5], o[7]));
+    b[2] = std::max(std::max(o[0], o[2]), std::max(o[4], o[6])); b[3] = std::max(std::max(o[1], o[3]), std::max(o[5], o[7]));
+  }
+}
+
+bool chars_cuts_valid(const int32_t cuts[27], int K) {
+  if (K < 0 || K > kCharsMax) return false;
+  if (K == 0) { for (int j = 0; j <= kCharsMax; ++j) if (cuts[j] != -1) return false; return true; }
+  if (cuts[0] < 0 || cuts[K] > 32768) return false;
+  for (int j = 0; j < K; ++j) if (cuts[j + 1] < cuts[j]) return false;
+  for (int j = K + 1; j <= kCharsMax; ++j) if (cuts[j] != -1) return false;
   return true;
 }
 

@@ -54,6 +54,26 @@ void lines_from_cuv(const int32_t* cuv, int n, int32_t* line, int32_t* word, int
 // line_first[n_lines + 1] = the lines' offsets into it.  Returns false when line / word are not a numbering of n_lines non-empty lines.
 bool lines_reading_order(const int32_t* line, const int32_t* word, int n, int n_lines, int32_t* order, int32_t* line_first);
 
+// Character boxes (ttr_config.chars; DESIGN.md "Character boxes").  The word's profile is the normalised region map sampled on a 128 x 16 grid
+// over the turned quad Q'[j] = Q[(j + t) mod 4] (column maximum, as a byte); the K cells are cut from it.  Constants of the rule:
+constexpr int kCharsU = 128, kCharsV = 16, kCharsLam = 64, kCharsMax = 26;
+// |S| of the confidence rule: the characters of a row of 26 ids (positions before the first id 0, id 88 and ids outside [0, 98) dropped)
+int text_chars(const int32_t* ids);
+// the image-pixel -> heat-pixel scale of a canvas ratio: k = 1 / (double)(ratio_w * 2.f), ratio_w = 1.f / ratio (adjust_coordinates' inverse)
+double chars_scale(float ratio);
+// one quad (8 floats, tl tr br bl, image pixels) at turn t -> fixed = {X0, Ax, Bx, Y0, Ay, By} in 2^-16 heat pixels: column u, row v samples
+// (X0 + u Ax + v Bx, Y0 + u Ay + v By).  Double, one rounding per statement, then llrint(65536 x).  Returns false for a coordinate that is not
+// finite or has |x| >= 32768, and for a scale outside (0, 1024] (every sum of the sampler then stays far inside int64).
+bool chars_coef(const float* quad8, int turn, double k, int64_t fixed[6]);
+// the profile q[128] of one word on T [H2][W2] (char_cut_kernel, chars.hip, computes the same bytes)
+void chars_profile(const float* T, int H2, int W2, const int64_t fixed[6], uint8_t q[128]);
+// q[128], K (0..26), qlow -> cuts[27] in 1/256 column (b[0..K], -1 beyond K) and *mode (0 uniform, 1 valley cuts).  Integer arithmetic only.
+void chars_cuts_from_profile(const uint8_t* q, int K, int qlow, int32_t cuts[27], int32_t* mode);
+// the K cells of one word as quads [K][8] (tl, tr, br, bl) and bboxes [K][4] (min x, min y, max x, max y), in double, cast to float
+void chars_quads_from_cuts(const float* quad8, int turn, const int32_t* cuts, int K, float* quads, float* bboxes);
+// what decode_pages accepts from the device: K + 1 ascending entries in [0, 32768], then -1
+bool chars_cuts_valid(const int32_t cuts[27], int K);
+
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.
 struct Component {

@@ -209,6 +209,13 @@ void launch_orient_select(int* ids, float* prob, float* conf, const int* cids, c
 constexpr int kLinesMaxWords = 4096;
 void launch_line_group(const int* cuv, const int* first, int pages, int N, int max_words, int* side, hipStream_t s);
 
+// chars.hip: character boxes (DESIGN.md "Character boxes") - per word, the K cells cut from the region map.  map [pages][H2][W2] f32; coef [N][KT][6]
+// int64 (geometry.h: chars_coef; KT = 1: turn 0, KT = 4: every turn, the kernel picks turns[c]); page_of [N]; turns [N] or null (= 0); K from ids
+// [N][26] or, when given, from nchars [N]; qlow = (int)(low_text * 255.f); side: [N][27] int32 cuts | [N] int32 mode | [N][128] u8 profile.
+inline size_t char_side_bytes(int N) { return (size_t)N * (27 * 4 + 4 + 128); }
+void launch_char_cut(const float* map, int H2, int W2, const int64_t* coef, int KT, const int* page_of, const int* turns, const int* ids, const int* nchars,
+                     int qlow, int N, int* side, hipStream_t s);
+
 // ---- mlp_fused.hip: x_out = x + fc2(GELU(fc1(LayerNorm(x)))) [+ y = LayerNorm_next(x_out)] for the ViT encoder blocks (bf16, E = 384)
 struct MlpParams {
   const float* x;          // [M][384] f32 residual stream

@@ -26,7 +26,7 @@ class Config(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("canvas_size", C.c_int), ("mag_ratio", C.c_float),
                 ("text_threshold", C.c_float), ("link_threshold", C.c_float), ("low_text", C.c_float), ("min_area", C.c_int),
                 ("strict_crops", C.c_int), ("max_components", C.c_int), ("verbose", C.c_int), ("crop_mode", C.c_int),
-                ("orient", C.c_int), ("orient_page", C.c_int), ("lines", C.c_int)]
+                ("orient", C.c_int), ("orient_page", C.c_int), ("lines", C.c_int), ("chars", C.c_int)]
 
 
 # every symbol include/tuatara_hip.h declares: (name, restype, argtypes)
@@ -71,6 +71,18 @@ SYMBOLS = [
     ("ttr_results_gather_lines", _I, [C.POINTER(_VP), _I, _PI, _PI, _PI, _PI, _PI, _PF]),
     ("ttr_lines_from_quads", _I, [_PF, _I, _PI, _PI, _PI]),
     ("ttr_group_lines", _I, [_VP, _PF, _PI, _I, _PI, _PI, _PI]),
+    ("ttr_result_char_count", _I, [_VP, _I]),
+    ("ttr_result_char_first", _PI, [_VP]),
+    ("ttr_result_char_quads", _PF, [_VP]),
+    ("ttr_result_char_bboxes", _PF, [_VP]),
+    ("ttr_result_char_cuts", _PI, [_VP]),
+    ("ttr_result_char_modes", _PI, [_VP]),
+    ("ttr_result_char_profiles", _PU8, [_VP]),
+    ("ttr_results_gather_chars", _I, [C.POINTER(_VP), _I, _PI, _PF, _PF, _PI, _PI, _PU8]),
+    ("ttr_char_cuts_from_profile", _I, [_PU8, _I, _I, _PI, _PI]),
+    ("ttr_chars_from_map", _I, [_PF, _I, _I, _F, _F, _PF, _PI, _PI, _I, _PI, _PI, _PU8]),
+    ("ttr_char_quads_from_cuts", _I, [_PF, _I, _PI, _I, _PF, _PF]),
+    ("ttr_char_cuts", _I, [_VP, _PF, _I, _I, _F, _F, _PF, _PI, _PI, _I, _PI, _PI, _PU8]),
     ("ttr_result_free", None, [_VP]),
     ("ttr_result_bboxes", _PF, [_VP]),
     ("ttr_result_ids_all", _PI, [_VP]),
@@ -270,6 +282,50 @@ def lines_from_quads(quads):
     return line[:n].copy(), word[:n].copy(), int(nl.value)
 
 
+def char_cuts_from_profile(q, K: int, qlow: int):
+    """The cut rule on one profile (ttr_char_cuts_from_profile, no GPU; DESIGN.md "Character boxes"): q u8 [128], K characters (0..26),
+    qlow = int(low_text * 255) -> (cuts i32 [27]: b[0..K] in 1/256 column, -1 beyond K; mode 0 uniform / 1 valley cuts)."""
+    q = np.ascontiguousarray(q, dtype=np.uint8).reshape(128)
+    cuts, mode = np.zeros(27, np.int32), C.c_int32()
+    if load().ttr_char_cuts_from_profile(_u8(q), int(K), int(qlow), _i(cuts), C.byref(mode)) != 0:
+        raise EngineError("ttr_char_cuts_from_profile: K must lie in 0..26")
+    return cuts, int(mode.value)
+
+
+def _chars_args(tnorm, quads, turns, nchars):
+    t = np.ascontiguousarray(tnorm, dtype=np.float32)
+    if t.ndim != 2:
+        raise ValueError("tnorm must be a [H2, W2] plane")
+    q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+    n = len(q)
+    tu = np.ascontiguousarray(turns, dtype=np.int32).reshape(-1)
+    nc = np.ascontiguousarray(nchars, dtype=np.int32).reshape(-1)
+    if len(tu) != n or len(nc) != n:
+        raise ValueError("turns and nchars must hold one entry per quad")
+    out = np.zeros((max(n, 1), 27), np.int32), np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 128), np.uint8)
+    return t, q, tu, nc, n, out
+
+
+def chars_from_map(tnorm, ratio: float, low_text: float, quads, turns, nchars):
+    """The character rule on the host (ttr_chars_from_map, no GPU; DESIGN.md "Character boxes"): one page's normalised region plane f32
+    [H2, W2], its canvas ratio, n words as quads f32 [n, 8], turns i32 [n] and character counts i32 [n] ->
+    (cuts i32 [n, 27], mode i32 [n], profile u8 [n, 128])."""
+    t, q, tu, nc, n, (cuts, modes, prof) = _chars_args(tnorm, quads, turns, nchars)
+    if load().ttr_chars_from_map(_f(t), t.shape[0], t.shape[1], float(ratio), float(low_text), _f(q), _i(tu), _i(nc), n, _i(cuts), _i(modes), _u8(prof)) != 0:
+        raise EngineError("ttr_chars_from_map: a coordinate is not finite or has |x| >= 32768, or a turn, count or ratio is out of range")
+    return cuts[:n].copy(), modes[:n].copy(), prof[:n].copy()
+
+
+def char_quads_from_cuts(quad, turn: int, cuts, K: int):
+    """One word's cells (ttr_char_quads_from_cuts): quad f32 [8], turn, cuts i32 [27], K -> (quads f32 [K, 8], bboxes f32 [K, 4])."""
+    q = np.ascontiguousarray(quad, dtype=np.float32).reshape(8)
+    c = np.ascontiguousarray(cuts, dtype=np.int32).reshape(27)
+    oq, ob = np.zeros((max(K, 1), 8), np.float32), np.zeros((max(K, 1), 4), np.float32)
+    if load().ttr_char_quads_from_cuts(_f(q), int(turn), _i(c), int(K), _f(oq), _f(ob)) != 0:
+        raise EngineError("ttr_char_quads_from_cuts: bad arguments")
+    return oq[:K].copy(), ob[:K].copy()
+
+
 def _add_conf(d: dict, conf, prob) -> dict:
     """the conf=True keys of a result dict: "conf" (the kernel's word confidence) and "char_conf" (one probability per character of "text")"""
     d["conf"] = float(conf)
@@ -292,12 +348,19 @@ class PageResult(collections.abc.Sequence):
     conf in ascending turn order, `page_orient` the page's turn; None / None / 0 when orientation is off.  Text lines (lines=True; DESIGN.md
     "Text lines"): `line` / `word` i32 [n] (dicts gain "line" and "word"), `order` i32 [n] the items in reading order, `line_first` i32
     [n_lines + 1] the lines' offsets into it, `line_bbox` f32 [n_lines, 4]; `lines` the list of {"text", "bbox", "items"} in reading order and
-    `text` the page's text (words joined by ' ', lines by '\\n'); line is None, lines [] and text "" when lines are off."""
+    `text` the page's text (words joined by ' ', lines by '\\n'); line is None, lines [] and text "" when lines are off.  Character boxes
+    (chars=True; DESIGN.md "Character boxes"): `char_first` i32 [n + 1] the items' offsets into `char_quad` f32 [total, 8] and `char_bbox`
+    f32 [total, 4], `char_cuts` i32 [n, 27], `char_mode` i32 [n], `char_profile` u8 [n, 128], `word_quad` f32 [n, 8] the words' own quads
+    in every crop mode; dicts gain "chars", a list of {"char", "quad", "bbox"}; all None when chars are off."""
     __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
-                 "line", "word", "order", "line_first", "line_bbox")
+                 "line", "word", "order", "line_first", "line_bbox",
+                 "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad")
 
     def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0,
-                 line=None, word=None, order=None, line_first=None, line_bbox=None):
+                 line=None, word=None, order=None, line_first=None, line_bbox=None,
+                 char_first=None, char_quad=None, char_bbox=None, char_cuts=None, char_mode=None, char_profile=None, word_quad=None):
+        self.char_first, self.char_quad, self.char_bbox = char_first, char_quad, char_bbox
+        self.char_cuts, self.char_mode, self.char_profile, self.word_quad = char_cuts, char_mode, char_profile, word_quad
         self.line, self.word, self.order, self.line_first, self.line_bbox = line, word, order, line_first, line_bbox
         self.texts, self.bbox, self.ids, self.quad = texts, bbox, ids, quad
         n = len(texts)
@@ -325,6 +388,11 @@ class PageResult(collections.abc.Sequence):
             d["orient"] = 90 * int(self.orient[j])
         if self.line is not None:
             d["line"], d["word"] = int(self.line[j]), int(self.word[j])
+        if self.char_first is not None:
+            a, b = int(self.char_first[j]), int(self.char_first[j + 1])
+            text = self.texts[j]
+            d["chars"] = [{"char": text[k - a] if k - a < len(text) else "", "quad": _quad_pairs(self.char_quad[k]), "bbox": self.char_bbox[k].tolist()}
+                          for k in range(a, b)]
         return d
 
     @property
@@ -445,6 +513,18 @@ class Engine:
         """lines=True: result dicts carry "line" and "word", PageResult.lines / .text are filled (DESIGN.md "Text lines")"""
         return self.cfg.lines != 0
 
+    @property
+    def cutting_chars(self) -> bool:
+        """chars=True: result dicts carry "chars", PageResult.char_* are filled (DESIGN.md "Character boxes")"""
+        return self.cfg.chars != 0
+
+    def char_cuts(self, tnorm, ratio: float, low_text: float, quads, turns, nchars):
+        """ttr_char_cuts: char_cut_kernel on a host region plane and host words, whatever the engine's `chars`; arguments and results as
+        chars_from_map."""
+        t, q, tu, nc, n, (cuts, modes, prof) = _chars_args(tnorm, quads, turns, nchars)
+        self._check(self.lib.ttr_char_cuts(self.h, _f(t), t.shape[0], t.shape[1], float(ratio), float(low_text), _f(q), _i(tu), _i(nc), n, _i(cuts), _i(modes), _u8(prof)))
+        return cuts[:n].copy(), modes[:n].copy(), prof[:n].copy()
+
     def group_lines(self, quads, first):
         """ttr_group_lines: line_group_kernel on host quads f32 [N, 8] of several pages (page p owns rows [first[p], first[p + 1])), whatever
         the engine's `lines` -> (line i32 [N], word i32 [N], n_lines i32 [pages])."""
@@ -484,7 +564,14 @@ class Engine:
             lf, lb = np.zeros(total + n + 1, np.int32), np.zeros((max(total, 1), 4), np.float32)
             if self.lib.ttr_results_gather_lines(arr, n, _i(nl), _i(ll), _i(lw), _i(lo), _i(lf), _f(lb)) < 0:
                 raise EngineError("ttr_results_gather_lines: bad arguments")
-        out, k, kl = [], 0, 0
+        if self.cutting_chars:                  # every page's characters, one call
+            ctot = self.lib.ttr_results_gather_chars(arr, n, None, None, None, None, None, None)
+            if ctot < 0:
+                raise EngineError("ttr_results_gather_chars: bad arguments")
+            chf, chq, chb = np.zeros(total + n + 1, np.int32), np.zeros((max(ctot, 1), 8), np.float32), np.zeros((max(ctot, 1), 4), np.float32)
+            chc, chm, chp = np.zeros((max(total, 1), 27), np.int32), np.zeros(max(total, 1), np.int32), np.zeros((max(total, 1), 128), np.uint8)
+            self.lib.ttr_results_gather_chars(arr, n, _i(chf), _f(chq), _f(chb), _i(chc), _i(chm), _u8(chp))
+        out, k, kl, kc = [], 0, 0, 0
         for i in range(n):
             c = int(counts[i])
             orient = (ot[k:k + c], oc[k:k + c], int(op[i])) if self.orienting else (None, None, 0)
@@ -493,8 +580,14 @@ class Engine:
                 m = int(nl[i])
                 lines = (ll[k:k + c], lw[k:k + c], lo[k:k + c], lf[kl + i:kl + i + m + 1], lb[kl:kl + m])
                 kl += m
+            chars = (None,) * 7
+            if self.cutting_chars:
+                first = chf[k + i:k + i + c + 1]
+                m = int(first[-1])
+                chars = (first, chq[kc:kc + m], chb[kc:kc + m], chc[k:k + c], chm[k:k + c], chp[k:k + c], self._quads(arr[i], c))
+                kc += m
             out.append(PageResult(texts[k:k + c], bb[k:k + c], ids[k:k + c], self._quads(arr[i], c) if self.rectified else None,
-                                  cf[k:k + c], pr[k:k + c], conf, *orient, *lines))
+                                  cf[k:k + c], pr[k:k + c], conf, *orient, *lines, *chars))
             k += c
             self.lib.ttr_result_free(arr[i])
         return out
