@@ -9,8 +9,9 @@
 // engines are cached per (weights_dir, rectify, orient, orient_page, lines).  And a keyword-only lines=False: lines=True groups each page's
 // words into text lines in reading order and every dict gains "line" (its line of the page) and "word" (its position in that line; DESIGN.md
 // "Text lines"); sort by (line, word) to read the page.  And a keyword-only chars=False: chars=True gives every dict "chars", a list of
-// {"char", "quad", "bbox"} with one entry per character of "text" (DESIGN.md "Character boxes").  With all of them off every dict is the
-// reference's {text, bbox}.
+// {"char", "quad", "bbox"} with one entry per character of "text" (DESIGN.md "Character boxes").  And a keyword-only blocks=False: blocks=True
+// groups each page's text lines into blocks in reading order, a column read to its end before the next (DESIGN.md "Text blocks"); it turns lines
+// on, and every dict gains "block" beside "line" and "word".  With all of them off every dict is the reference's {text, bbox}.
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -30,7 +31,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
@@ -46,6 +47,7 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
     d["line"] = item.line;
     d["word"] = item.word;
   }
+  if (k.blocks) d["block"] = item.block;
   if (k.chars) {
     py::list cs;
     for (const CharBox& c : item.chars) {
@@ -70,8 +72,10 @@ static int orient_mode(const py::object& orient) {
 }
 
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
-                                      std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars) {
+                                      std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
+                                      bool blocks) {
   const int orient = orient_mode(orient_kw);
+  lines = lines || blocks;   // blocks are made of lines
   py::buffer_info buf = image.request();
   if (buf.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
   if (buf.shape[2] != 3) throw std::runtime_error("Input array should have 3 channels");
@@ -80,13 +84,14 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   std::vector<OutputItemEx> items;
   {
     py::gil_scoped_release nogil;   // (orient = None: the 7-argument call, which leaves the orientation to TUATARA_ORIENT)
-    items = chars    ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, true)
+    items = blocks   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
+            : chars  ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, true)
             : lines  ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true)
             : orient ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
                      : image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
   }
   py::list result;
-  for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars}));
+  for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks}));
   return result;
 }
 
@@ -94,8 +99,9 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
 // images: a sequence of uint8 arrays [H, W, 3] of any sizes.  What a caller of the reference writes as a loop over image_to_data (bindings/run_ocr.py:92),
 // on one cached engine: same-sized images travel as batches, the host-to-device copies run beside the GPU's work, the GIL is released meanwhile.
 static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf, py::object orient_kw,
-                                       bool orient_page, bool lines, bool chars) {
+                                       bool orient_page, bool lines, bool chars, bool blocks) {
   const int orient = orient_mode(orient_kw);
+  lines = lines || blocks;   // blocks are made of lines
   std::vector<py::array_t<unsigned char, py::array::c_style | py::array::forcecast>> keep;   // contiguous uint8 views / copies, alive for the call
   std::vector<ImageView> views;
   for (py::handle h : images) {
@@ -110,7 +116,8 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   std::vector<std::vector<OutputItemEx>> pages;
   {
     py::gil_scoped_release nogil;
-    pages = chars    ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, true)
+    pages = blocks   ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
+            : chars  ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, true)
             : lines  ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true)
             : orient ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient, orient_page)
                      : images_to_data_ex(views, weights_dir, output_dir, rectify);
@@ -118,7 +125,7 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   py::list result;
   for (const auto& items : pages) {
     py::list page;
-    for (const auto& item : items) page.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars}));
+    for (const auto& item : items) page.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks}));
     result.append(page);
   }
   return result;
@@ -128,8 +135,8 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
 }

@@ -18,11 +18,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.append(os.path.join(HERE, "..", "build", "bindings"))   # where the build puts pytuatara (reference: run_ocr.py:6)
 
 
-def annotate(image: np.ndarray, result, by_lines: bool = False) -> Image.Image:
+def annotate(image: np.ndarray, result, by_lines: bool = False, by_blocks: bool = False) -> Image.Image:
     """The reference's three panels side by side (run_ocr.py:10-82), drawn with PIL: the page with its boxes | each text at its
     box position | the texts as running text in reading order - sorted by (y1, x1) (:12), starting at (10, 30), wrapped at the
     page width, 10 px between words and lines (:20-25, :62-75).  by_lines=True (items read with lines=True, carrying "line" and
-    "word"): the third panel follows the page's text lines instead - items in (line, word) order, a new row for every line."""
+    "word"): the third panel follows the page's text lines instead - items in (line, word) order, a new row for every line.
+    by_blocks=True (items read with blocks=True, carrying "block" too): the third panel follows the page's text blocks - items in (block, line,
+    word) order, a new row for every line and an empty row between blocks, so a column is read to its end before the next begins."""
     page = Image.fromarray(image).convert("RGB")
     w, h = page.size
     boxes = page.copy()
@@ -30,9 +32,11 @@ def annotate(image: np.ndarray, result, by_lines: bool = False) -> Image.Image:
     running = Image.new("RGB", page.size, "black")
     db, dp, dr = ImageDraw.Draw(boxes), ImageDraw.Draw(panel), ImageDraw.Draw(running)
     tx, ty, gap = 10, 30, 10
-    by_lines = by_lines and all("line" in it for it in result)
-    last_line = None
-    for item in sorted(result, key=(lambda it: (it["line"], it["word"])) if by_lines else (lambda it: (it["bbox"][1], it["bbox"][0]))):
+    by_blocks = by_blocks and all("block" in it and "line" in it for it in result)
+    by_lines = by_blocks or (by_lines and all("line" in it for it in result))
+    last_line = last_block = None
+    key = (lambda it: (it["block"], it["line"], it["word"])) if by_blocks else (lambda it: (it["line"], it["word"])) if by_lines else (lambda it: (it["bbox"][1], it["bbox"][0]))
+    for item in sorted(result, key=key):
         x1, y1, x2, y2 = (int(v) for v in item["bbox"])
         text = item["text"]
         if "quad" in item:       # rectified crops (pytuatara.image_to_data(..., rectify=True)): the word's own quadrilateral
@@ -47,7 +51,9 @@ def annotate(image: np.ndarray, result, by_lines: bool = False) -> Image.Image:
         if by_lines and last_line is not None and item["line"] != last_line and tx > 10:   # a new text line starts a new row
             tx = 10
             ty += th + gap
-        last_line = item.get("line")
+        if by_blocks and last_block is not None and item["block"] != last_block:               # a new block: one empty row
+            ty += th + gap
+        last_line, last_block = item.get("line"), item.get("block")
         if tx + tw > w:
             tx = 10
             ty += th + gap
@@ -61,8 +67,8 @@ def annotate(image: np.ndarray, result, by_lines: bool = False) -> Image.Image:
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    rectify, lines, chars = "--rectify" in argv, "--lines" in argv, "--chars" in argv
-    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars")]
+    rectify, lines, chars, blocks = "--rectify" in argv, "--lines" in argv, "--chars" in argv, "--blocks" in argv
+    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks")]
     image_path = argv[0] if len(argv) > 0 else os.path.join(HERE, "..", "tests", "data", "funsd_0001129658.png")
     weights_dir = argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "weights")
     outputs_dir = argv[2] if len(argv) > 2 else os.path.join(HERE, "..", "outputs")
@@ -74,11 +80,13 @@ def main(argv=None):
         kw["lines"] = True
     if chars:
         kw["chars"] = True
+    if blocks:                      # (blocks are made of lines: blocks=True turns lines on)
+        kw["blocks"] = True
     result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir, **kw)
     print(result)
     os.makedirs(outputs_dir, exist_ok=True)
     stem = os.path.splitext(os.path.basename(image_path))[0]
-    annotate(numpy_image, result, by_lines=lines).save(os.path.join(outputs_dir, stem + "_annotated_with_ocr_results.png"))
+    annotate(numpy_image, result, by_lines=lines, by_blocks=blocks).save(os.path.join(outputs_dir, stem + "_annotated_with_ocr_results.png"))
     return result
 
 

@@ -12,6 +12,8 @@
 // of the page per output line, in reading order, the words joined by one space.
 //   ocr_cli --chars <image.png> <weights_dir> <outputs_dir>     cuts every word into its characters (DESIGN.md "Character boxes") and prints one line per
 // character, "c x1 y1 x2 y2" with the character's bbox as integers, the words in item order.
+//   ocr_cli --blocks <image.png> <weights_dir> <outputs_dir>    groups the text lines into blocks (DESIGN.md "Text blocks") and prints the page's text block
+// after block in reading order - a column to its end before the next -, one line of the page per output line and an empty line between blocks.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <algorithm>
 #include <cmath>
@@ -68,6 +70,23 @@ int main(int argc, const char** argv) {
       if (!at.empty()) fputc('\n', stdout);
       return 0;
     }
+    if (argc == 5 && std::string(argv[1]) == "--blocks") {
+      pngdec::Image img = pngdec::read(argv[2]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[3], argv[4], false, -1, false, true, false, true);
+      std::vector<size_t> at(items.size());
+      for (size_t i = 0; i < at.size(); ++i) at[i] = i;
+      std::sort(at.begin(), at.end(), [&](size_t a, size_t b) {
+        const OutputItemEx &x = items[a], &y = items[b];
+        return x.block != y.block ? x.block < y.block : x.block_line != y.block_line ? x.block_line < y.block_line : x.word < y.word;
+      });
+      for (size_t k = 0; k < at.size(); ++k) {
+        const OutputItemEx &it = items[at[k]];
+        if (k) fputs(it.block != items[at[k - 1]].block ? "\n\n" : it.block_line != items[at[k - 1]].block_line ? "\n" : " ", stdout);
+        fputs(it.text.c_str(), stdout);
+      }
+      if (!at.empty()) fputc('\n', stdout);
+      return 0;
+    }
     if (argc == 5 && std::string(argv[1]) == "--chars") {
       pngdec::Image img = pngdec::read(argv[2]);
       std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[3], argv[4], false, -1, false, false, true);
@@ -77,7 +96,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--rectify | --conf | --orient | --lines | --chars] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--rectify | --conf | --orient | --lines | --chars | --blocks] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

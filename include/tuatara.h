@@ -49,6 +49,7 @@ struct OutputItemEx {
   int orient = 0;                  // word orientation: the turn the word was read at, in degrees clockwise (0, 90, 180, 270; DESIGN.md "Word orientation")
   std::vector<CharBox> chars;      // character boxes: one per character of `text`, in text order; empty when chars are off (DESIGN.md "Character boxes")
   int line = -1, word = -1;        // text lines: the item's line of its page, in reading order, and its position inside that line; -1 when lines are off (DESIGN.md "Text lines")
+  int block = -1, block_line = -1;  // text blocks: the item's block of its page, in reading order, and its line's position inside that block (what a caller sorts by: block, block_line, word); -1 when blocks are off (DESIGN.md "Text blocks")
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, bool rectify);
@@ -78,6 +79,16 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
                                            std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars);
 std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
                                                          bool rectify, int orient, bool orient_page, bool lines, bool chars);
+// Text blocks (opt-in; DESIGN.md "Text blocks"): blocks = true also groups every page's text lines into blocks (paragraphs, column pieces) in
+// reading order - a column is read to its end before the next begins; each item says its `block` and its line's position `block_line` in it (sort
+// the items by (block, block_line, word) to read the page; put a blank line between blocks).  Blocks are made of lines: blocks = true turns lines on.
+// blocks = false is the calls above, unless TUATARA_BLOCKS=1 is set in the environment, which turns blocks (and lines) on for image_to_data /
+// images_to_data / every call above.  Items, order, boxes and text do not change.  orient = -1, lines = false and chars = false leave those to
+// the environment.
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

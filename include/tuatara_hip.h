@@ -63,6 +63,8 @@ typedef struct ttr_config {
                             reading order (DESIGN.md "Text lines"); other values make ttr_create fail.  Needs max_components <= 4096 */
   int chars;             /* 0 (default): off, the same kernels and bits as without the field; 1: every item also carries one quadrilateral and one bbox per
                             character of its text (DESIGN.md "Character boxes"); other values make ttr_create fail */
+  int blocks;            /* 0 (default): off, the same kernels and bits as without the field; 1: the text lines are also grouped into blocks (paragraphs,
+                            column pieces) in reading order (DESIGN.md "Text blocks"); other values make ttr_create fail.  Needs lines = 1 */
 } ttr_config;
 
 void ttr_config_default(ttr_config* cfg);
@@ -223,6 +225,47 @@ int ttr_char_quads_from_cuts(const float* quad, int turn, const int32_t* cuts27,
  * uploaded and char_cut_kernel runs once.  Refuses while batches stream.  Returns 0, -1 on error (ttr_last_error). */
 int ttr_char_cuts(ttr_engine* e, const float* tnorm, int H2, int W2, float ratio, float low_text, const float* quads, const int32_t* turns, const int32_t* nchars,
                   int n, int32_t* cuts, int32_t* modes, uint8_t* profiles);
+
+/* Text blocks (ttr_config.blocks = 1 with lines = 1; DESIGN.md "Text blocks"), every entry point but ttr_pages_to_data_dev_sharded (which refuses
+ * blocks != 0).  Every other output is that of blocks = 0; the result also groups the page's text lines into blocks and gives the blocks in reading
+ * order: a column is read to its end before the next begins.  Blocks depend only on the page's own quads (ttr_result_quads).
+ * ttr_result_block_count: the page's blocks.  ttr_result_block_mode: 1 when the blocks were ordered by the precedence relation, 0 when the page has
+ * more than 512 blocks and they are ordered by their top-left corners alone.  ttr_result_line_blocks / ttr_result_line_pos: [lines] each line's
+ * block (in block order) and its position inside that block.  ttr_result_blocks: [count] each item's block.  ttr_result_block_order: [lines] the
+ * line indices in block reading order, each block's lines consecutive.  ttr_result_block_first: [blocks + 1] the blocks' offsets into it.
+ * ttr_result_block_bboxes: [blocks][4] min / max of the member lines' bboxes.  With blocks = 0, or for an empty result, the pointers are NULL, the
+ * counts are 0 and ttr_result_block_mode is 0 (the stage calls ttr_blocks_from_quads / ttr_group_blocks report mode 1 for an empty page, as the
+ * rule states it). */
+int ttr_result_block_count(const ttr_result* r);
+int ttr_result_block_mode(const ttr_result* r);
+const int32_t* ttr_result_line_blocks(const ttr_result* r);
+const int32_t* ttr_result_line_pos(const ttr_result* r);
+const int32_t* ttr_result_blocks(const ttr_result* r);
+const int32_t* ttr_result_block_order(const ttr_result* r);
+const int32_t* ttr_result_block_first(const ttr_result* r);
+const float* ttr_result_block_bboxes(const ttr_result* r);
+/* The text of block b (its lines in order, joined by '\n') and of the page read by blocks (the blocks joined by "\n\n"), without a terminator.
+ * Both return the bytes needed, like ttr_result_texts: buf is written only when cap suffices.  0 with blocks = 0.  ttr_result_page_text is unchanged. */
+int ttr_result_block_text(const ttr_result* r, int b, char* buf, size_t cap);
+int ttr_result_page_text_blocks(const ttr_result* r, char* buf, size_t cap);
+/* ... for a batch of results in one call (any output may be NULL): n_blocks[n], modes[n]; blocks [total items] in ttr_results_gather's item order;
+ * line_blocks, line_pos and block_order [total lines] in ttr_results_gather_lines' line order (block_order holds line indices local to its result);
+ * block_first: per result its n_blocks + 1 offsets (local), result after result; block_bboxes [total blocks][4].  A result without blocks
+ * (blocks = 0, or empty) contributes 0 blocks, no lines, its single block_first entry 0, and -1 for the blocks of any items it has.  Returns the
+ * total block count, -1 on bad arguments. */
+int ttr_results_gather_blocks(ttr_result* const* rs, int n, int32_t* n_blocks, int32_t* modes, int32_t* blocks, int32_t* line_blocks, int32_t* line_pos,
+                              int32_t* block_order, int32_t* block_first, float* block_bboxes);
+/* The rule on the host, no GPU: the n words of ONE page as quads [n][8] -> the line rule's line[n], word[n], *n_lines, then block[n], pos[n] (per
+ * line: entries [0, *n_lines), the rest -1), *n_blocks, *mode.  Any output may be NULL.  Integer arithmetic, exact, the same as
+ * block_group_kernel's.  Returns 0; -1 for the inputs ttr_lines_from_quads refuses. */
+int ttr_blocks_from_quads(const float* quads, int n, int32_t* line, int32_t* word, int32_t* n_lines, int32_t* block, int32_t* pos, int32_t* n_blocks,
+                          int32_t* mode);
+/* The rule on the GPU as a stage entry point, whatever the engine's config: host quads of several pages (as ttr_group_lines) are uploaded,
+ * line_group_kernel and block_group_kernel run once each, and line, word, block, pos [first[pages]] (block and pos per line within each page's
+ * range, -1 beyond its lines), n_lines, n_blocks and mode [pages] come back.  Any output may be NULL.  Refuses while batches stream.  Returns 0,
+ * -1 on error (ttr_last_error). */
+int ttr_group_blocks(ttr_engine* e, const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines, int32_t* block,
+                     int32_t* pos, int32_t* n_blocks, int32_t* mode);
 
 /* ---- multi-GPU: RCCL in the C++ host -----------------------------------------------------------------
  * One process per GPU, one engine per process.  The OCR path has no data-path collective: pages are independent.  The one exchange is

@@ -36,7 +36,7 @@ void ttr_config_default(ttr_config* c) {
   c->precision = TTR_PREC_F16X4; c->device = 0; c->canvas_size = 1024; c->mag_ratio = 1.0f;
   c->text_threshold = 0.7f; c->link_threshold = 0.4f; c->low_text = 0.4f; c->min_area = 10;
   c->strict_crops = 0; c->max_components = 4096; c->verbose = 0; c->crop_mode = TTR_CROP_BOUNDING;
-  c->orient = TTR_ORIENT_OFF; c->orient_page = 0; c->lines = 0; c->chars = 0;
+  c->orient = TTR_ORIENT_OFF; c->orient_page = 0; c->lines = 0; c->chars = 0; c->blocks = 0;
 }
 
 const char* ttr_last_error(void) { return g_last_error.c_str(); }
@@ -349,6 +349,87 @@ int ttr_char_cuts(ttr_engine* e, const float* tnorm, int H2, int W2, float ratio
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_char_cuts");
   E.char_cuts(tnorm, H2, W2, ratio, low_text, quads, turns, nchars, n, cuts, modes, profiles);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_result_block_count(const ttr_result* r) { return r ? r->r.n_blocks : 0; }
+
+int ttr_result_block_mode(const ttr_result* r) { return r && r->r.n_blocks > 0 ? r->r.block_mode : 0; }
+
+const int32_t* ttr_result_line_blocks(const ttr_result* r) { return r && !r->r.line_block.empty() ? r->r.line_block.data() : nullptr; }
+
+const int32_t* ttr_result_line_pos(const ttr_result* r) { return r && !r->r.line_pos.empty() ? r->r.line_pos.data() : nullptr; }
+
+const int32_t* ttr_result_blocks(const ttr_result* r) { return r && !r->r.block.empty() ? r->r.block.data() : nullptr; }
+
+const int32_t* ttr_result_block_order(const ttr_result* r) { return r && !r->r.block_order.empty() ? r->r.block_order.data() : nullptr; }
+
+const int32_t* ttr_result_block_first(const ttr_result* r) { return r && r->r.n_blocks > 0 ? r->r.block_first.data() : nullptr; }
+
+const float* ttr_result_block_bboxes(const ttr_result* r) { return r && !r->r.block_bbox.empty() ? r->r.block_bbox.data() : nullptr; }
+
+int ttr_result_block_text(const ttr_result* r, int b, char* buf, size_t cap) {
+  if (!r || b < 0 || b >= r->r.n_blocks) return 0;
+  return copy_out(r->r.block_text(b), buf, cap);
+}
+
+int ttr_result_page_text_blocks(const ttr_result* r, char* buf, size_t cap) {
+  if (!r || r->r.n_blocks <= 0) return 0;
+  return copy_out(r->r.page_text_blocks(), buf, cap);
+}
+
+int ttr_results_gather_blocks(ttr_result* const* rs, int n, int32_t* n_blocks, int32_t* modes, int32_t* blocks, int32_t* line_blocks, int32_t* line_pos,
+                              int32_t* block_order, int32_t* block_first, float* block_bboxes) {
+  if (!rs || n < 0) return -1;
+  size_t oi = 0, ol = 0, ob = 0, of = 0;
+  for (int i = 0; i < n; ++i) {
+    static const Result none;
+    const Result& r = rs[i] ? rs[i]->r : none;
+    const size_t cnt = r.text.size(), nb = (size_t)r.n_blocks;
+    const bool has = nb > 0 && r.block.size() == cnt;
+    const size_t nl = has ? r.line_block.size() : 0;
+    if (n_blocks) n_blocks[i] = has ? r.n_blocks : 0;
+    if (modes) modes[i] = has ? r.block_mode : 0;
+    if (blocks) { if (has) std::copy(r.block.begin(), r.block.end(), blocks + oi); else std::fill(blocks + oi, blocks + oi + cnt, -1); }
+    if (has) {
+      if (line_blocks) std::copy(r.line_block.begin(), r.line_block.end(), line_blocks + ol);
+      if (line_pos) std::copy(r.line_pos.begin(), r.line_pos.end(), line_pos + ol);
+      if (block_order) std::copy(r.block_order.begin(), r.block_order.end(), block_order + ol);
+      if (block_bboxes) std::copy(r.block_bbox.begin(), r.block_bbox.end(), block_bboxes + 4 * ob);
+    }
+    if (block_first) { if (has) std::copy(r.block_first.begin(), r.block_first.end(), block_first + of); else block_first[of] = 0; }
+    oi += cnt; ol += nl; ob += has ? nb : 0; of += (has ? nb : 0) + 1;
+  }
+  return (int)ob;
+}
+
+int ttr_blocks_from_quads(const float* quads, int n, int32_t* line, int32_t* word, int32_t* n_lines, int32_t* block, int32_t* pos, int32_t* n_blocks,
+                          int32_t* mode) {
+  if (n < 0 || (n > 0 && !quads)) return -1;
+  std::vector<int32_t> cuv((size_t)n * 6), ln((size_t)n), wd((size_t)n), bl((size_t)n), ps((size_t)n);
+  for (int i = 0; i < n; ++i) if (!lines_cuv(quads + 8 * (size_t)i, cuv.data() + 6 * (size_t)i)) return -1;
+  int32_t nl = 0, nb = 0, md = 1;
+  lines_from_cuv(cuv.data(), n, ln.data(), wd.data(), &nl);
+  blocks_from_lines(cuv.data(), n, ln.data(), wd.data(), nl, bl.data(), ps.data(), &nb, &md);
+  if (line) std::copy(ln.begin(), ln.end(), line);
+  if (word) std::copy(wd.begin(), wd.end(), word);
+  if (block) std::copy(bl.begin(), bl.end(), block);
+  if (pos) std::copy(ps.begin(), ps.end(), pos);
+  if (n_lines) *n_lines = nl;
+  if (n_blocks) *n_blocks = nb;
+  if (mode) *mode = md;
+  return 0;
+}
+
+int ttr_group_blocks(ttr_engine* e, const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines, int32_t* block,
+                     int32_t* pos, int32_t* n_blocks, int32_t* mode) {
+  TTR_GUARD_BEGIN
+  if (!e || pages < 0 || (pages > 0 && !first) || (pages > 0 && first[pages] > 0 && !quads)) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_group_blocks");
+  E.group_blocks(quads, first, pages, line, word, n_lines, block, pos, n_blocks, mode);
   return 0;
   TTR_GUARD_END(-1)
 }

@@ -403,6 +403,8 @@ Engine::Engine(const std::string& dir, const ttr_config& c) : cfg(c) {
   if (cfg.lines != 0 && cfg.lines != 1) throw std::runtime_error("lines must be 0 (off) or 1 (group the words into text lines)");
   if (cfg.lines && cfg.max_components > kLinesMaxWords) throw std::runtime_error("lines = 1 needs max_components <= " + std::to_string(kLinesMaxWords));
   if (cfg.chars != 0 && cfg.chars != 1) throw std::runtime_error("chars must be 0 or 1");
+  if (cfg.blocks != 0 && cfg.blocks != 1) throw std::runtime_error("blocks must be 0 or 1");
+  if (cfg.blocks && !cfg.lines) throw std::runtime_error("blocks needs lines = 1");
   prec = cfg.precision == TTR_PREC_F32 ? kF32 : cfg.precision == TTR_PREC_F16X4 ? kSplit : kBF16;
   es = prec == kBF16 ? 2 : 4;
   int ndev = 0;

@@ -278,6 +278,14 @@ struct Result {
   std::vector<float> char_quad, char_bbox;  // 8 / 4 per character: tl, tr, br, bl; min x, min y, max x, max y
   std::vector<int32_t> char_cuts, char_mode;   // 27 / 1 per item: the cuts b[0..K] in 1/256 column (-1 beyond K); 0 uniform, 1 valley cuts
   std::vector<uint8_t> char_profile;        // 128 per item: the word's profile q
+  // text blocks (cfg.blocks = 1; DESIGN.md "Text blocks"): empty / 0 when off
+  std::vector<int32_t> line_block, line_pos;     // 1 per line: its block in reading order, its position inside that block
+  std::vector<int32_t> block;                    // 1 per item: its line's block
+  std::vector<int32_t> block_order, block_first; // the lines in block reading order; [n_blocks + 1] the blocks' offsets into `block_order`
+  std::vector<float> block_bbox;                 // 4 per block: min / max of the member lines' bbox
+  int n_blocks = 0, block_mode = 0;              // block_mode 1: ordered by the precedence relation; 0: more than 512 blocks, by key alone
+  std::string block_text(int b) const;           // the block's lines joined by '\n'
+  std::string page_text_blocks() const;          // the blocks in reading order, joined by "\n\n"
 };
 
 struct CclBatch {   // device workspaces of the CCL stage for a batch of equally sized pages
@@ -418,6 +426,8 @@ struct Engine {
   PinnedBuf h_orient_in[2], h_orient[2];          // ... per slot: staging of orient_in, host copy of the side block
   DevBuf lines_in, lines_side;                    // text lines: the words' cuv | page firsts; the side block (lines.hip)
   PinnedBuf h_lines_in[2], h_lines[2];            // ... per slot: staging of lines_in, host copy of the side block
+  DevBuf blocks_side;                             // text blocks: the side block (blocks.hip)
+  PinnedBuf h_blocks[2];                          // ... per slot: its host copy
   DevBuf chars_map[2], chars_in, chars_side;      // character boxes: per slot the batch's region planes (a copy of ccl.tnorm); coef | page_of | turns | nchars; the side block (chars.hip)
   PinnedBuf h_chars_in[2], h_chars[2];            // ... per slot: staging of chars_in, host copy of the side block
   hipEvent_t chars_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // ... per slot: the planes are copied; char_cut_kernel has read them (created with the first chars batch)
@@ -692,6 +702,12 @@ struct Engine {
   void group_batch_lines(const PageBatch& B, int sl, int max_words);
   // the stage form (ttr_group_lines): host quads [first[pages]][8] of several pages -> line, word [first[pages]], n_lines [pages]
   void group_lines(const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines);
+  // text blocks: block_group_kernel behind line_group_kernel of the same batch (it reads lines_in and lines_side on the device) and the copy of its
+  // side block to h_blocks[sl]; the stage form (ttr_group_blocks): both kernels on host quads, block / pos [first[pages]] indexed by line within
+  // each page's range, n_blocks / mode [pages]; any output may be null
+  void group_batch_blocks(const PageBatch& B, int sl, int max_words);
+  void group_blocks(const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines, int32_t* block, int32_t* pos,
+                    int32_t* n_blocks, int32_t* mode);
 
   // character boxes: detect_enqueue keeps the batch's region planes (keep_batch_map, behind its CCL); stage_batch_chars writes every word's coefficients
   // (all four turns when orientation is on) and page into the pinned staging of slot sl (host only); cut_batch_chars copies them, runs char_cut_kernel
@@ -705,8 +721,10 @@ struct Engine {
 
   void finish(PageBatch& B, std::vector<Result>& results);
   // results[pg] for every page of B from its boxes and the decoded rows of its crops (crop c is row c); side: the orientation side block
-  // of the batch (orient.hip) or null; lines_side: the text lines' side block (lines.hip) or null; chars_side: the characters' (chars.hip) or null
-  void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, std::vector<Result>& results);
+  // of the batch (orient.hip) or null; lines_side: the text lines' side block (lines.hip) or null; chars_side: the characters' (chars.hip) or null;
+  // blocks_side: the text blocks' (blocks.hip) or null
+  void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
+                    std::vector<Result>& results);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it

@@ -31,6 +31,24 @@ std::string Result::page_text() const {
   return t;
 }
 
+std::string Result::block_text(int b) const {
+  std::string t;
+  for (int k = block_first[(size_t)b]; k < block_first[(size_t)b + 1]; ++k) {
+    if (k > block_first[(size_t)b]) t += '\n';
+    t += line_text(block_order[(size_t)k]);
+  }
+  return t;
+}
+
+std::string Result::page_text_blocks() const {
+  std::string t;
+  for (int b = 0; b < n_blocks; ++b) {
+    if (b) t += "\n\n";
+    t += block_text(b);
+  }
+  return t;
+}
+
 // crops are ordered by page: page pg owns crops [first[pg], first[pg + 1])
 static std::vector<int> page_first(const std::vector<int>& page_of, int pages) {
   std::vector<int> first(pages + 1, 0);
@@ -394,6 +412,51 @@ void Engine::group_lines(const float* quads, const int32_t* first, int pages, in
   if (n_lines) std::copy(side + 2 * (size_t)N, side + 2 * (size_t)N + pages, n_lines);
 }
 
+static size_t blocks_side_bytes(int N, int pages) { return ((size_t)2 * N + (size_t)2 * pages) * 4; }   // [N] block | [N] pos | [pages] n_blocks | [pages] mode
+
+void Engine::group_batch_blocks(const PageBatch& B, int sl, int max_words) {
+  const int N = B.N;
+  const size_t side_b = blocks_side_bytes(N, B.n);
+  blocks_side.ensure(side_b); h_blocks[sl].ensure(side_b);
+  launch_block_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, lines_side.as<int>(), B.n, N, max_words, blocks_side.as<int>(), stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(h_blocks[sl].p, blocks_side.p, side_b, hipMemcpyDeviceToHost, stream));
+}
+
+void Engine::group_blocks(const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines, int32_t* block, int32_t* pos,
+                          int32_t* n_blocks, int32_t* mode) {
+  if (pages <= 0) return;
+  if (first[0] != 0) throw std::runtime_error("ttr_group_blocks: first[0] must be 0");
+  int max_words = 0;
+  for (int pg = 0; pg < pages; ++pg) {
+    if (first[pg + 1] < first[pg]) throw std::runtime_error("ttr_group_blocks: first must not decrease");
+    max_words = std::max(max_words, first[pg + 1] - first[pg]);
+  }
+  if (max_words > kLinesMaxWords) throw std::runtime_error("ttr_group_blocks: more than " + std::to_string(kLinesMaxWords) + " words on a page");
+  const int N = first[pages];
+  const size_t in_b = (size_t)N * 24 + (size_t)(pages + 1) * 4, lside_b = ((size_t)2 * N + pages) * 4, side_b = blocks_side_bytes(N, pages);
+  h_lines_in[0].ensure(in_b); lines_in.ensure(in_b);
+  h_lines[0].ensure(lside_b); lines_side.ensure(lside_b);
+  h_blocks[0].ensure(side_b); blocks_side.ensure(side_b);
+  int32_t* cuv = h_lines_in[0].as<int32_t>();
+  for (int c = 0; c < N; ++c)
+    if (!lines_cuv(quads + 8 * (size_t)c, cuv + 6 * (size_t)c)) throw std::runtime_error("ttr_group_blocks: a coordinate is not finite or has |x| >= 32768");
+  std::copy(first, first + pages + 1, cuv + 6 * (size_t)N);
+  TTR_HIP_CHECK(hipMemcpyAsync(lines_in.p, cuv, in_b, hipMemcpyHostToDevice, stream));
+  launch_line_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, pages, N, max_words, lines_side.as<int>(), stream);
+  launch_block_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, lines_side.as<int>(), pages, N, max_words, blocks_side.as<int>(), stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(h_lines[0].p, lines_side.p, lside_b, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(h_blocks[0].p, blocks_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  const int32_t *ls = h_lines[0].as<int32_t>(), *bs = h_blocks[0].as<int32_t>();
+  if (line && N) std::copy(ls, ls + N, line);
+  if (word && N) std::copy(ls + N, ls + 2 * (size_t)N, word);
+  if (n_lines) std::copy(ls + 2 * (size_t)N, ls + 2 * (size_t)N + pages, n_lines);
+  if (block && N) std::copy(bs, bs + N, block);
+  if (pos && N) std::copy(bs + N, bs + 2 * (size_t)N, pos);
+  if (n_blocks) std::copy(bs + 2 * (size_t)N, bs + 2 * (size_t)N + pages, n_blocks);
+  if (mode) std::copy(bs + 2 * (size_t)N + pages, bs + 2 * (size_t)N + 2 * (size_t)pages, mode);
+}
+
 void Engine::keep_batch_map(const PageBatch& B) {
   const int sl = B.slot & 1;
   for (auto& x : chars_ev[sl]) if (!x) TTR_HIP_CHECK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
@@ -490,6 +553,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     pack_batch_crops(B, sl);
     if (T) pack_twin_crops(B, sl);
     if (cfg.lines) group_batch_lines(B, sl, line_words);               // text lines: from the boxes alone, so inside the packing stage (DESIGN.md "Text lines")
+    if (cfg.blocks) group_batch_blocks(B, sl, line_words);             // text blocks: directly behind, from the lines' side block on the device (DESIGN.md "Text blocks")
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf);
     if (T) {   // the twins as a pass of their own (turn 0 keeps its batch, and with it its bits), then the choice, in place in the standard block
@@ -537,12 +601,14 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   const int32_t* side = orient_k() > 1 && N > 0 ? h_orient[B.slot].as<int32_t>() : nullptr;
   const int32_t* lines_block = cfg.lines && N > 0 ? h_lines[B.slot].as<int32_t>() : nullptr;   // the side block (lines.hip)
   const void* chars_block = cfg.chars && N > 0 ? h_chars[B.slot].p : nullptr;                   // the side block (chars.hip)
-  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, results);
+  const int32_t* blocks_block = cfg.blocks && N > 0 ? h_blocks[B.slot].as<int32_t>() : nullptr;   // the side block (blocks.hip)
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results);
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
 
-void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, std::vector<Result>& results) {
+void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
+                          std::vector<Result>& results) {
   const int n = B.n, N = B.N, K = orient_k();
   const std::vector<int> first = page_first(B.page_of, n);
   // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
@@ -586,6 +652,32 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
         for (int k = r.line_first[l]; k < r.line_first[l + 1]; ++k) {
           const float* bb = &r.bbox[4 * (size_t)r.order[k]];
           lb[0] = std::min(lb[0], bb[0]); lb[1] = std::min(lb[1], bb[1]); lb[2] = std::max(lb[2], bb[2]); lb[3] = std::max(lb[3], bb[3]);
+        }
+      }
+    }
+    if (blocks_side && lines_side && cnt > 0) {   // [N] block | [N] pos | [pages] n_blocks | [pages] mode, per line -> the page's blocks in reading order
+      const int nl = r.n_lines;
+      r.line_block.assign(&blocks_side[c0], &blocks_side[c0 + nl]);
+      r.line_pos.assign(&blocks_side[(size_t)N + c0], &blocks_side[(size_t)N + c0 + nl]);
+      r.n_blocks = blocks_side[2 * (size_t)N + pg];
+      r.block_mode = blocks_side[2 * (size_t)N + n + pg];
+      if (r.n_blocks < 1 || r.n_blocks > nl)   // (checked before anything is sized by it)
+        throw std::runtime_error("text blocks: the side block of page " + std::to_string(pg) + " is not a numbering of its blocks");
+      r.block_order.assign((size_t)nl, 0);
+      r.block_first.assign((size_t)r.n_blocks + 1, 0);
+      if ((r.block_mode != 0 && r.block_mode != 1) ||
+          !blocks_reading_order(r.line_block.data(), r.line_pos.data(), nl, r.n_blocks, r.block_order.data(), r.block_first.data()))
+        throw std::runtime_error("text blocks: the side block of page " + std::to_string(pg) + " is not a numbering of its blocks");
+      r.block.resize((size_t)cnt);
+      for (int k = 0; k < cnt; ++k) r.block[k] = r.line_block[r.line[k]];
+      const float inf = std::numeric_limits<float>::infinity();
+      r.block_bbox.assign((size_t)r.n_blocks * 4, 0.f);
+      for (int b = 0; b < r.n_blocks; ++b) {
+        float* o = &r.block_bbox[4 * (size_t)b];
+        o[0] = o[1] = inf; o[2] = o[3] = -inf;
+        for (int k = r.block_first[b]; k < r.block_first[b + 1]; ++k) {
+          const float* lb = &r.line_bbox[4 * (size_t)r.block_order[k]];
+          o[0] = std::min(o[0], lb[0]); o[1] = std::min(o[1], lb[1]); o[2] = std::max(o[2], lb[2]); o[3] = std::max(o[3], lb[3]);
         }
       }
     }
@@ -644,6 +736,7 @@ void Engine::run_pages(const uint8_t* d_pages, int n, int h, int w, std::vector<
 void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results) {
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");
   if (cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("latency mode does not support word orientation: create the engine with orient = TTR_ORIENT_OFF");
+  if (cfg.blocks) throw std::runtime_error("latency mode does not support text blocks: create the engine with blocks = 0");
   if (cfg.lines) throw std::runtime_error("latency mode does not support text lines: create the engine with lines = 0");
   if (cfg.chars) throw std::runtime_error("latency mode does not support character boxes: create the engine with chars = 0");
   if (q1.live || q2.live) throw std::runtime_error("streamed batches are in flight: call ttr_stream_flush until it returns none");
@@ -694,7 +787,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   for (int r = 0; r < world; ++r) total[r] = std::max(0, std::min(per, N - r * per));
   Gathered g;
   compact_gathered(h_gath[0].as<int32_t>(), per, total, g);
-  decode_pages(B, RecRows{g.ids.data(), g.prob.data(), g.conf.data()}, nullptr, nullptr, nullptr, results);
+  decode_pages(B, RecRows{g.ids.data(), g.prob.data(), g.conf.data()}, nullptr, nullptr, nullptr, nullptr, results);
 }
 
 void Engine::stream_push(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& prev_results, int& prev_n) {

@@ -233,6 +233,160 @@ bool lines_reading_order(const int32_t* line, const int32_t* word, int n, int n_
   return true;
 }
 
+// ---------------------------------------------------------------- text blocks (DESIGN.md "Text blocks")
+namespace {
+struct BlockLine {
+  int64_t Cx, Cy, Dx, Dy, Hx, Hy, DD, HH;
+  bool ok;
+};
+// b seen from a's frame: stacked and overlapping along a's axis
+inline bool blocks_frame(const BlockLine& a, const BlockLine& b) {
+  const int64_t dx = b.Cx - a.Cx, dy = b.Cy - a.Cy;
+  if (iabs64(dx * a.Hx + dy * a.Hy) > 9 * a.HH) return false;
+  const int64_t s = dx * a.Dx + dy * a.Dy, e = iabs64(b.Dx * a.Dx + b.Dy * a.Dy);
+  return std::min(a.DD, s + e) - std::max(-a.DD, s - e) >= std::min(a.DD, e);
+}
+inline bool blocks_link(const BlockLine& a, const BlockLine& b) {
+  if (!a.ok || !b.ok) return false;
+  const int64_t dot = a.Dx * b.Dx + a.Dy * b.Dy;
+  if (dot <= 0 || 64 * iabs64(a.Dx * b.Dy - a.Dy * b.Dx) > 17 * dot) return false;
+  if (4 * a.HH > 9 * b.HH || 4 * b.HH > 9 * a.HH) return false;
+  return blocks_frame(a, b) && blocks_frame(b, a);
+}
+struct BlockBox {
+  int32_t x0, y0, x1, y1, root;
+  int64_t cy() const { return (int64_t)y0 + y1; }
+};
+}  // namespace
+
+void blocks_from_lines(const int32_t* cuv, int n, const int32_t* line, const int32_t* word, int n_lines, int32_t* block, int32_t* pos, int32_t* n_blocks,
+                       int32_t* mode) {
+  *n_blocks = 0;
+  *mode = 1;
+  std::fill(block, block + std::max(n, 0), -1);
+  std::fill(pos, pos + std::max(n, 0), -1);
+  if (n <= 0 || n_lines <= 0) return;
+  const int nl = n_lines;
+  // 1: the lines' descriptors
+  std::vector<int> cnt((size_t)nl, 0), fst((size_t)nl, 0), lst((size_t)nl, 0);
+  std::vector<int64_t> Vx((size_t)nl, 0), Vy((size_t)nl, 0);
+  for (int i = 0; i < n; ++i) { ++cnt[line[i]]; Vx[line[i]] += cuv[6 * (size_t)i + 4]; Vy[line[i]] += cuv[6 * (size_t)i + 5]; }
+  for (int i = 0; i < n; ++i) {
+    if (word[i] == 0) fst[line[i]] = i;
+    if (word[i] == cnt[line[i]] - 1) lst[line[i]] = i;
+  }
+  std::vector<BlockLine> L((size_t)nl);
+  for (int l = 0; l < nl; ++l) {
+    const int32_t *f = cuv + 6 * (size_t)fst[l], *e = cuv + 6 * (size_t)lst[l];
+    const int64_t ax = (int64_t)f[0] - f[2], ay = (int64_t)f[1] - f[3], bx = (int64_t)e[0] + e[2], by = (int64_t)e[1] + e[3];
+    BlockLine& a = L[l];
+    a.Cx = ax + bx; a.Cy = ay + by; a.Dx = bx - ax; a.Dy = by - ay;
+    a.Hx = Vx[l] / cnt[l]; a.Hy = Vy[l] / cnt[l];      // (truncating)
+    a.DD = a.Dx * a.Dx + a.Dy * a.Dy; a.HH = a.Hx * a.Hx + a.Hy * a.Hy;
+    a.ok = a.DD != 0 && a.HH != 0 && a.Dx * a.Hy - a.Dy * a.Hx != 0;
+  }
+  // 2, 3: links -> components, the root the smallest line
+  std::vector<int> root((size_t)nl);
+  for (int l = 0; l < nl; ++l) root[l] = l;
+  auto find = [&](int i) { while (root[i] != i) { root[i] = root[root[i]]; i = root[i]; } return i; };
+  for (int i = 0; i < nl; ++i)
+    for (int j = i + 1; j < nl; ++j)
+      if (blocks_link(L[i], L[j])) {
+        const int a = find(i), b = find(j);
+        if (a != b) root[std::max(a, b)] = std::min(a, b);
+      }
+  for (int l = 0; l < nl; ++l) root[l] = find(l);
+  // 4: the lines' order inside their block
+  std::vector<int64_t> Sx((size_t)nl, 0), Sy((size_t)nl, 0), key((size_t)nl);
+  for (int l = 0; l < nl; ++l) { Sx[root[l]] += L[l].Hx; Sy[root[l]] += L[l].Hy; }
+  for (int l = 0; l < nl; ++l) key[l] = L[l].Cx * Sx[root[l]] + L[l].Cy * Sy[root[l]];
+  std::vector<int> idx((size_t)nl);
+  for (int l = 0; l < nl; ++l) idx[l] = l;
+  std::sort(idx.begin(), idx.end(), [&](int a, int b) {
+    if (root[a] != root[b]) return root[a] < root[b];
+    if (key[a] != key[b]) return key[a] < key[b];
+    return a < b;
+  });
+  for (int k = 0, p = 0; k < nl; ++k) {
+    p = k > 0 && root[idx[k]] == root[idx[k - 1]] ? p + 1 : 0;
+    pos[idx[k]] = p;
+  }
+  // 5: the blocks' boxes, in root order
+  std::vector<int> bix((size_t)nl, -1);
+  std::vector<BlockBox> B;
+  for (int l = 0; l < nl; ++l)
+    if (root[l] == l) { bix[l] = (int)B.size(); B.push_back(BlockBox{INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, l}); }
+  for (int i = 0; i < n; ++i) {
+    const int32_t* t = cuv + 6 * (size_t)i;
+    BlockBox& b = B[bix[root[line[i]]]];
+    const int32_t ex = std::abs(t[2]) + std::abs(t[4]), ey = std::abs(t[3]) + std::abs(t[5]);
+    b.x0 = std::min(b.x0, t[0] - ex); b.x1 = std::max(b.x1, t[0] + ex);
+    b.y0 = std::min(b.y0, t[1] - ey); b.y1 = std::max(b.y1, t[1] + ey);
+  }
+  const int nb = (int)B.size();
+  auto key_less = [&](int a, int b) {
+    if (B[a].y0 != B[b].y0) return B[a].y0 < B[b].y0;
+    if (B[a].x0 != B[b].x0) return B[a].x0 < B[b].x0;
+    return a < b;                                      // (the blocks are in root order)
+  };
+  std::vector<int> by_key((size_t)nb), rank((size_t)nb);
+  for (int b = 0; b < nb; ++b) by_key[b] = b;
+  std::sort(by_key.begin(), by_key.end(), key_less);
+  *n_blocks = nb;
+  if (nb > kBlocksMaxOrdered) {                        // 8: by key alone
+    *mode = 0;
+    for (int k = 0; k < nb; ++k) rank[by_key[k]] = k;
+  } else {
+    // 6: precedence.  The blocks ranked by cy: "S lies between A and B" is a range of ranks, so the clause is an AND of two rows of the
+    // x-overlap matrix (columns in cy rank) under a range mask
+    const int W = (nb + 63) / 64;
+    std::vector<int> by_cy((size_t)nb), cyr((size_t)nb);
+    for (int b = 0; b < nb; ++b) by_cy[b] = b;
+    std::sort(by_cy.begin(), by_cy.end(), [&](int a, int b) { return B[a].cy() != B[b].cy() ? B[a].cy() < B[b].cy() : a < b; });
+    for (int k = 0; k < nb; ++k) cyr[by_cy[k]] = k;
+    auto xov = [&](int a, int b) { return B[a].x0 < B[b].x1 && B[b].x0 < B[a].x1; };
+    std::vector<uint64_t> X((size_t)nb * W, 0), P((size_t)nb * W, 0);   // X[a]: bit cyr[s] = xov(s, a); P[b]: bit a = a precedes b
+    for (int a = 0; a < nb; ++a)
+      for (int s = 0; s < nb; ++s)
+        if (xov(s, a)) X[(size_t)a * W + (cyr[s] >> 6)] |= 1ull << (cyr[s] & 63);
+    for (int b = 0; b < nb; ++b)
+      for (int a = 0; a < nb; ++a) {
+        if (a == b) continue;
+        bool p = xov(a, b) && cyr[a] < cyr[b];
+        if (!p && B[a].x1 <= B[b].x0) {
+          const int lo = std::min(cyr[a], cyr[b]) + 1, hi = std::max(cyr[a], cyr[b]);   // the ranks strictly between: [lo, hi)
+          bool spanned = false;
+          for (int w = lo >> 6; w <= (hi - 1) >> 6 && lo < hi && !spanned; ++w) {
+            uint64_t m = X[(size_t)a * W + w] & X[(size_t)b * W + w];
+            if (w == lo >> 6) m &= ~0ull << (lo & 63);
+            if (w == hi >> 6) m &= (1ull << (hi & 63)) - 1;
+            spanned = m != 0;
+          }
+          p = !spanned;
+        }
+        if (p) P[(size_t)b * W + (a >> 6)] |= 1ull << (a & 63);
+      }
+    // 7: the order
+    std::vector<uint64_t> U((size_t)W, 0);             // the unplaced blocks
+    for (int b = 0; b < nb; ++b) U[b >> 6] |= 1ull << (b & 63);
+    for (int round = 0; round < nb; ++round) {
+      int pick = -1, any = -1;
+      for (int k = 0; k < nb && pick < 0; ++k) {       // (ascending key)
+        const int b = by_key[k];
+        if (!(U[b >> 6] >> (b & 63) & 1)) continue;
+        if (any < 0) any = b;
+        bool held = false;
+        for (int w = 0; w < W && !held; ++w) held = (P[(size_t)b * W + w] & U[w]) != 0;
+        if (!held) pick = b;
+      }
+      if (pick < 0) pick = any;                        // a cycle
+      rank[pick] = round;
+      U[pick >> 6] &= ~(1ull << (pick & 63));
+    }
+  }
+  for (int l = 0; l < nl; ++l) block[l] = rank[bix[root[l]]];
+}
+
 // ---------------------------------------------------------------- character boxes (DESIGN.md "Character boxes")
 double chars_scale(float ratio) {
   const float ratio_w = 1.f / ratio;

@@ -54,6 +54,19 @@ void lines_from_cuv(const int32_t* cuv, int n, int32_t* line, int32_t* word, int
 // line_first[n_lines + 1] = the lines' offsets into it.  Returns false when line / word are not a numbering of n_lines non-empty lines.
 bool lines_reading_order(const int32_t* line, const int32_t* word, int n, int n_lines, int32_t* order, int32_t* line_first);
 
+// Text blocks (ttr_config.blocks; DESIGN.md "Text blocks").  blocks_from_lines: the rule on ONE page from the words' cuv and the line rule's
+// outputs (block_group_kernel, blocks.hip, computes the same): block[l] = the rank of line l's block in reading order, pos[l] = the line's rank
+// inside its block, for l < n_lines (both arrays hold n entries, the rest is -1: lines never outnumber words), *n_blocks, *mode = 1 when the
+// blocks are ordered by the precedence relation, 0 when there are more than kBlocksMaxOrdered and they are ordered by their keys alone.
+constexpr int kBlocksMaxOrdered = 512;
+void blocks_from_lines(const int32_t* cuv, int n, const int32_t* line, const int32_t* word, int n_lines, int32_t* block, int32_t* pos, int32_t* n_blocks,
+                       int32_t* mode);
+// ... derived from block / pos: order[n_lines] = the line indices in block reading order (each block's lines consecutive, by pos) and
+// block_first[n_blocks + 1].  Returns false when block / pos are not a numbering of n_blocks non-empty blocks.
+inline bool blocks_reading_order(const int32_t* block, const int32_t* pos, int n_lines, int n_blocks, int32_t* order, int32_t* block_first) {
+  return lines_reading_order(block, pos, n_lines, n_blocks, order, block_first);
+}
+
 // Character boxes (ttr_config.chars; DESIGN.md "Character boxes").  The word's profile is the normalised region map sampled on a 128 x 16 grid
 // over the turned quad Q'[j] = Q[(j + t) mod 4] (column maximum, as a byte); the K cells are cut from it.  Constants of the rule:
 constexpr int kCharsU = 128, kCharsV = 16, kCharsLam = 64, kCharsMax = 26;

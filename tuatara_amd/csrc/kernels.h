@@ -209,6 +209,12 @@ void launch_orient_select(int* ids, float* prob, float* conf, const int* cids, c
 constexpr int kLinesMaxWords = 4096;
 void launch_line_group(const int* cuv, const int* first, int pages, int N, int max_words, int* side, hipStream_t s);
 
+// blocks.hip: text blocks (DESIGN.md "Text blocks") - per page, every line's block in reading order and its position in it.  cuv, first, N, max_words:
+// as launch_line_group; lside: line_group_kernel's side block of the same launch (read on the device); side: [N] int32 block | [N] int32 pos |
+// [pages] int32 n_blocks | [pages] int32 mode, block and pos indexed by line within the page's range (-1 beyond its lines).
+constexpr int kBlocksCap = 512;   // (= geometry.h: kBlocksMaxOrdered) more blocks on a page are ordered by key alone
+void launch_block_group(const int* cuv, const int* first, const int* lside, int pages, int N, int max_words, int* side, hipStream_t s);
+
 // chars.hip: character boxes (DESIGN.md "Character boxes") - per word, the K cells cut from the region map.  map [pages][H2][W2] f32; coef [N][KT][6]
 // int64 (geometry.h: chars_coef; KT = 1: turn 0, KT = 4: every turn, the kernel picks turns[c]); page_of [N]; turns [N] or null (= 0); K from ids
 // [N][26] or, when given, from nchars [N]; qlow = (int)(low_text * 255.f); side: [N][27] int32 cuts | [N] int32 mode | [N][128] u8 profile.

@@ -26,7 +26,7 @@ class Config(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("canvas_size", C.c_int), ("mag_ratio", C.c_float),
                 ("text_threshold", C.c_float), ("link_threshold", C.c_float), ("low_text", C.c_float), ("min_area", C.c_int),
                 ("strict_crops", C.c_int), ("max_components", C.c_int), ("verbose", C.c_int), ("crop_mode", C.c_int),
-                ("orient", C.c_int), ("orient_page", C.c_int), ("lines", C.c_int), ("chars", C.c_int)]
+                ("orient", C.c_int), ("orient_page", C.c_int), ("lines", C.c_int), ("chars", C.c_int), ("blocks", C.c_int)]
 
 
 # every symbol include/tuatara_hip.h declares: (name, restype, argtypes)
@@ -83,6 +83,19 @@ SYMBOLS = [
     ("ttr_chars_from_map", _I, [_PF, _I, _I, _F, _F, _PF, _PI, _PI, _I, _PI, _PI, _PU8]),
     ("ttr_char_quads_from_cuts", _I, [_PF, _I, _PI, _I, _PF, _PF]),
     ("ttr_char_cuts", _I, [_VP, _PF, _I, _I, _F, _F, _PF, _PI, _PI, _I, _PI, _PI, _PU8]),
+    ("ttr_result_block_count", _I, [_VP]),
+    ("ttr_result_block_mode", _I, [_VP]),
+    ("ttr_result_line_blocks", _PI, [_VP]),
+    ("ttr_result_line_pos", _PI, [_VP]),
+    ("ttr_result_blocks", _PI, [_VP]),
+    ("ttr_result_block_order", _PI, [_VP]),
+    ("ttr_result_block_first", _PI, [_VP]),
+    ("ttr_result_block_bboxes", _PF, [_VP]),
+    ("ttr_result_block_text", _I, [_VP, _I, C.c_char_p, C.c_size_t]),
+    ("ttr_result_page_text_blocks", _I, [_VP, C.c_char_p, C.c_size_t]),
+    ("ttr_results_gather_blocks", _I, [C.POINTER(_VP), _I, _PI, _PI, _PI, _PI, _PI, _PI, _PI, _PF]),
+    ("ttr_blocks_from_quads", _I, [_PF, _I, _PI, _PI, _PI, _PI, _PI, _PI, _PI]),
+    ("ttr_group_blocks", _I, [_VP, _PF, _PI, _I, _PI, _PI, _PI, _PI, _PI, _PI, _PI]),
     ("ttr_result_free", None, [_VP]),
     ("ttr_result_bboxes", _PF, [_VP]),
     ("ttr_result_ids_all", _PI, [_VP]),
@@ -292,6 +305,20 @@ def char_cuts_from_profile(q, K: int, qlow: int):
     return cuts, int(mode.value)
 
 
+def blocks_from_quads(quads):
+    """The text-block rule on the host (ttr_blocks_from_quads, no GPU; DESIGN.md "Text blocks"): one page's quads f32 [n, 8] -> (line i32 [n],
+    word i32 [n], n_lines, block i32 [n_lines] each line's block in reading order, pos i32 [n_lines] its position inside that block, n_blocks,
+    mode: 1 ordered by the precedence relation, 0 more than 512 blocks, by key alone)."""
+    q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+    n = len(q)
+    line, word, block, pos = (np.zeros(max(n, 1), np.int32) for _ in range(4))
+    nl, nb, mode = C.c_int32(), C.c_int32(), C.c_int32()
+    if load().ttr_blocks_from_quads(_f(q), n, _i(line), _i(word), C.byref(nl), _i(block), _i(pos), C.byref(nb), C.byref(mode)) != 0:
+        raise EngineError("ttr_blocks_from_quads: a coordinate is not finite or has |x| >= 32768")
+    m = int(nl.value)
+    return line[:n].copy(), word[:n].copy(), m, block[:m].copy(), pos[:m].copy(), int(nb.value), int(mode.value)
+
+
 def _chars_args(tnorm, quads, turns, nchars):
     t = np.ascontiguousarray(tnorm, dtype=np.float32)
     if t.ndim != 2:
@@ -351,14 +378,23 @@ class PageResult(collections.abc.Sequence):
     `text` the page's text (words joined by ' ', lines by '\\n'); line is None, lines [] and text "" when lines are off.  Character boxes
     (chars=True; DESIGN.md "Character boxes"): `char_first` i32 [n + 1] the items' offsets into `char_quad` f32 [total, 8] and `char_bbox`
     f32 [total, 4], `char_cuts` i32 [n, 27], `char_mode` i32 [n], `char_profile` u8 [n, 128], `word_quad` f32 [n, 8] the words' own quads
-    in every crop mode; dicts gain "chars", a list of {"char", "quad", "bbox"}; all None when chars are off."""
+    in every crop mode; dicts gain "chars", a list of {"char", "quad", "bbox"}; all None when chars are off.  Text blocks (blocks=True;
+    DESIGN.md "Text blocks"): `block` i32 [n] each item's block (dicts gain "block"), `line_block` / `line_pos` i32 [n_lines] each line's block
+    in reading order and its position in it, `block_order` i32 [n_lines] the lines in block reading order, `block_first` i32 [n_blocks + 1],
+    `block_bbox` f32 [n_blocks, 4], `block_mode` (1: ordered by the precedence relation, 0: more than 512 blocks, by key alone); `blocks` the
+    list of {"text", "bbox", "lines"} in reading order and `text_blocks` the page read block after block (lines joined by '\\n', blocks by a
+    blank line); block is None, blocks [] and text_blocks "" when blocks are off."""
     __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
-                 "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad")
+                 "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad",
+                 "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode")
 
     def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0,
                  line=None, word=None, order=None, line_first=None, line_bbox=None,
-                 char_first=None, char_quad=None, char_bbox=None, char_cuts=None, char_mode=None, char_profile=None, word_quad=None):
+                 char_first=None, char_quad=None, char_bbox=None, char_cuts=None, char_mode=None, char_profile=None, word_quad=None,
+                 block=None, line_block=None, line_pos=None, block_order=None, block_first=None, block_bbox=None, block_mode=0):
+        self.block, self.line_block, self.line_pos, self.block_order = block, line_block, line_pos, block_order
+        self.block_first, self.block_bbox, self.block_mode = block_first, block_bbox, block_mode
         self.char_first, self.char_quad, self.char_bbox = char_first, char_quad, char_bbox
         self.char_cuts, self.char_mode, self.char_profile, self.word_quad = char_cuts, char_mode, char_profile, word_quad
         self.line, self.word, self.order, self.line_first, self.line_bbox = line, word, order, line_first, line_bbox
@@ -388,6 +424,8 @@ class PageResult(collections.abc.Sequence):
             d["orient"] = 90 * int(self.orient[j])
         if self.line is not None:
             d["line"], d["word"] = int(self.line[j]), int(self.word[j])
+        if self.block is not None:
+            d["block"] = int(self.block[j])
         if self.char_first is not None:
             a, b = int(self.char_first[j]), int(self.char_first[j + 1])
             text = self.texts[j]
@@ -410,6 +448,23 @@ class PageResult(collections.abc.Sequence):
     def text(self) -> str:
         """the page's text: its lines in reading order, joined by '\\n' ("" when lines are off)"""
         return "\n".join(ln["text"] for ln in self.lines)
+
+    @property
+    def blocks(self) -> list:
+        """the page's text blocks in reading order: {"text": the block's lines joined by '\\n', "bbox": [x1, y1, x2, y2], "lines": line indices
+        (into `lines`) in order}"""
+        if self.block is None:
+            return []
+        lines, out = self.lines, []
+        for b in range(len(self.block_first) - 1):
+            members = self.block_order[self.block_first[b]:self.block_first[b + 1]].tolist()
+            out.append({"text": "\n".join(lines[l]["text"] for l in members), "bbox": self.block_bbox[b].tolist(), "lines": members})
+        return out
+
+    @property
+    def text_blocks(self) -> str:
+        """the page's text read block after block, the blocks joined by a blank line ("" when blocks are off)"""
+        return "\n\n".join(b["text"] for b in self.blocks)
 
     def __eq__(self, other):
         return list(self) == list(other)
@@ -518,6 +573,26 @@ class Engine:
         """chars=True: result dicts carry "chars", PageResult.char_* are filled (DESIGN.md "Character boxes")"""
         return self.cfg.chars != 0
 
+    @property
+    def grouping_blocks(self) -> bool:
+        """blocks=True: result dicts carry "block", PageResult.blocks / .text_blocks are filled (DESIGN.md "Text blocks")"""
+        return self.cfg.blocks != 0
+
+    def group_blocks(self, quads, first):
+        """ttr_group_blocks: line_group_kernel and block_group_kernel on host quads f32 [N, 8] of several pages (page p owns rows [first[p],
+        first[p + 1])), whatever the engine's config -> (line i32 [N], word i32 [N], n_lines i32 [pages], block i32 [N], pos i32 [N], n_blocks
+        i32 [pages], mode i32 [pages]); block and pos are per line, within each page's range: entries [first[p], first[p] + n_lines[p]), -1
+        behind them."""
+        q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+        first = np.ascontiguousarray(first, dtype=np.int32)
+        pages, N = len(first) - 1, len(q)
+        if pages < 0 or (pages > 0 and int(first[-1]) != N) or (pages == 0 and N):
+            raise ValueError("first must hold pages + 1 offsets ending at len(quads)")
+        line, word, block, pos = (np.zeros(max(N, 1), np.int32) for _ in range(4))
+        nl, nb, mode = (np.zeros(max(pages, 1), np.int32) for _ in range(3))
+        self._check(self.lib.ttr_group_blocks(self.h, _f(q), _i(first), pages, _i(line), _i(word), _i(nl), _i(block), _i(pos), _i(nb), _i(mode)))
+        return line[:N].copy(), word[:N].copy(), nl[:pages].copy(), block[:N].copy(), pos[:N].copy(), nb[:pages].copy(), mode[:pages].copy()
+
     def char_cuts(self, tnorm, ratio: float, low_text: float, quads, turns, nchars):
         """ttr_char_cuts: char_cut_kernel on a host region plane and host words, whatever the engine's `chars`; arguments and results as
         chars_from_map."""
@@ -571,7 +646,13 @@ class Engine:
             chf, chq, chb = np.zeros(total + n + 1, np.int32), np.zeros((max(ctot, 1), 8), np.float32), np.zeros((max(ctot, 1), 4), np.float32)
             chc, chm, chp = np.zeros((max(total, 1), 27), np.int32), np.zeros(max(total, 1), np.int32), np.zeros((max(total, 1), 128), np.uint8)
             self.lib.ttr_results_gather_chars(arr, n, _i(chf), _f(chq), _f(chb), _i(chc), _i(chm), _u8(chp))
-        out, k, kl, kc = [], 0, 0, 0
+        if self.grouping_blocks:                # every page's blocks, one call
+            bn, bm, bi = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(total, 1), np.int32)
+            bl, bp, bo = np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.int32), np.zeros(max(total, 1), np.int32)
+            bf, bbx = np.zeros(total + n + 1, np.int32), np.zeros((max(total, 1), 4), np.float32)
+            if self.lib.ttr_results_gather_blocks(arr, n, _i(bn), _i(bm), _i(bi), _i(bl), _i(bp), _i(bo), _i(bf), _f(bbx)) < 0:
+                raise EngineError("ttr_results_gather_blocks: bad arguments")
+        out, k, kl, kc, kbl, kb = [], 0, 0, 0, 0, 0
         for i in range(n):
             c = int(counts[i])
             orient = (ot[k:k + c], oc[k:k + c], int(op[i])) if self.orienting else (None, None, 0)
@@ -586,8 +667,16 @@ class Engine:
                 m = int(first[-1])
                 chars = (first, chq[kc:kc + m], chb[kc:kc + m], chc[k:k + c], chm[k:k + c], chp[k:k + c], self._quads(arr[i], c))
                 kc += m
+            blocks = (None,) * 6 + (0,)
+            if self.grouping_blocks and int(bn[i]) > 0:
+                m, ml = int(bn[i]), int(nl[i])
+                blocks = (bi[k:k + c], bl[kbl:kbl + ml], bp[kbl:kbl + ml], bo[kbl:kbl + ml], bf[kb + i:kb + i + m + 1], bbx[kb:kb + m], int(bm[i]))
+                kbl += ml
+                kb += m
+            elif self.grouping_blocks:              # an empty page: no blocks
+                blocks = (bi[k:k], bl[:0], bp[:0], bo[:0], np.zeros(1, np.int32), bbx[:0], 0)
             out.append(PageResult(texts[k:k + c], bb[k:k + c], ids[k:k + c], self._quads(arr[i], c) if self.rectified else None,
-                                  cf[k:k + c], pr[k:k + c], conf, *orient, *lines, *chars))
+                                  cf[k:k + c], pr[k:k + c], conf, *orient, *lines, *chars, *blocks))
             k += c
             self.lib.ttr_result_free(arr[i])
         return out

@@ -58,6 +58,48 @@ def synthetic_page(seed: int, h: int = 1024, w: int = 768, n_words: int = 40, sc
     return np.ascontiguousarray(np.repeat(a[:, :, None], 3, 2))
 
 
+def synthetic_columns_page(seed: int, h: int = 512, w: int = 768, rows: int = 6, scale: int = 2, gutter: int = 96, ink: str = "glyphs"):
+    """A two-column page: `rows` rows of words per column, drawn as synthetic_page draws them (PIL's default font magnified `scale` x), the rows
+    of both columns on the same baselines 18 `scale` px apart, the columns `gutter` px apart (several text heights, so no text line crosses it).
+    Every row is filled to its column's width, the last to at least half of it.  ink "glyphs": the words as drawn; "bars": every word a bar of seeded black-and-white noise of
+    the word's size, the dark "words" of the smoke test - the synthetic detector follows ink density, so it shatters thin glyph strokes into
+    fragments but gives exactly one box per bar.  Returns (page u8 [h, w, 3], words): per word a dict {"word",
+    "column": 0 left / 1 right, "row", "box": (x0, y0, x1, y1) of its tile}, column after column, row after row."""
+    from PIL import Image, ImageDraw, ImageFont
+
+    if ink not in ("glyphs", "bars"):
+        raise ValueError("ink must be 'glyphs' or 'bars'")
+    rng = np.random.default_rng(seed)
+    font = ImageFont.load_default()
+    page = Image.new("L", (w, h), 255)
+    margin, pitch, space = 24, 18 * scale, 10 * scale
+    colw = (w - 2 * margin - gutter) // 2
+    words = []
+    for col in range(2):
+        x_col = margin + col * (colw + gutter)
+        for r in range(rows):
+            room = colw if r < rows - 1 else int(colw * float(rng.uniform(0.55, 0.8)))
+            x = x_col
+            while True:
+                word = "".join(rng.choice(list(ALNUM), size=int(rng.integers(3, 8))))
+                tile = Image.new("L", (70, 14), 255)
+                ImageDraw.Draw(tile).text((1, 1), word, fill=0, font=font)
+                bbox = Image.eval(tile, lambda v: 255 - v).getbbox()
+                tile = tile.crop((0, 0, bbox[2] + 1, 14)).resize(((bbox[2] + 1) * scale, 14 * scale), Image.NEAREST)
+                if x + tile.size[0] > x_col + room:
+                    break
+                if ink == "bars":
+                    bar = np.full((tile.size[1], tile.size[0]), 255, np.uint8)
+                    bar[3 * scale:11 * scale, scale:-scale] = rng.integers(0, 2, (8 * scale, tile.size[0] - 2 * scale), dtype=np.uint8) * 255
+                    tile = Image.fromarray(bar)
+                y = margin + r * pitch
+                page.paste(tile, (x, y))
+                words.append({"word": word, "column": col, "row": r, "box": (x, y, x + tile.size[0], y + tile.size[1])})
+                x += tile.size[0] + space
+    a = np.asarray(page, dtype=np.uint8)
+    return np.ascontiguousarray(np.repeat(a[:, :, None], 3, 2)), words
+
+
 def synthetic_rotated_page(seed: int, h: int = 1024, w: int = 768, n_words: int = 16, max_deg: float = 30.0):
     """Words drawn as synthetic_page draws them (PIL's default font magnified 2x), each rotated by a seeded skew in [-max_deg, max_deg]
     degrees (image coordinates, y down: positive turns the baseline clockwise on screen) and pasted where it overlaps no other word.
