@@ -98,8 +98,9 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
 // pytuatara.images_to_data(images, weights_dir, outputs_dir) -> list (one entry per image, input order) of the lists image_to_data returns.
 // images: a sequence of uint8 arrays [H, W, 3] of any sizes.  What a caller of the reference writes as a loop over image_to_data (bindings/run_ocr.py:92),
 // on one cached engine: same-sized images travel as batches, the host-to-device copies run beside the GPU's work, the GIL is released meanwhile.
+// Keyword-only mixed_batches=False: True batches images that share one detector canvas, whatever their sizes (DESIGN.md "Mixed-size batches"); same results.
 static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf, py::object orient_kw,
-                                       bool orient_page, bool lines, bool chars, bool blocks) {
+                                       bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches) {
   const int orient = orient_mode(orient_kw);
   lines = lines || blocks;   // blocks are made of lines
   std::vector<py::array_t<unsigned char, py::array::c_style | py::array::forcecast>> keep;   // contiguous uint8 views / copies, alive for the call
@@ -116,7 +117,8 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   std::vector<std::vector<OutputItemEx>> pages;
   {
     py::gil_scoped_release nogil;
-    pages = blocks   ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
+    pages = mixed_batches ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, true)
+            : blocks ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
             : chars  ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, true)
             : lines  ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true)
             : orient ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient, orient_page)
@@ -138,5 +140,5 @@ PYBIND11_MODULE(pytuatara, m) {
         py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
 }

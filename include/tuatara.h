@@ -89,6 +89,12 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
                                            std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks);
 std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
                                                          bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks);
+// Mixed-size batches (opt-in; DESIGN.md "Mixed-size batches"): the list form batches images of equal size; mixed_batches = true batches images that
+// share one detector canvas instead, whatever their sizes - scans of one paper size that differ by a few pixels travel together.  Every result is
+// the same either way.  mixed_batches = false is the call above, unless TUATARA_MIXED_BATCHES=1 is set in the environment, which turns it on for
+// images_to_data and every images_to_data_ex.  The other arguments as above.
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

@@ -65,6 +65,9 @@ typedef struct ttr_config {
                             character of its text (DESIGN.md "Character boxes"); other values make ttr_create fail */
   int blocks;            /* 0 (default): off, the same kernels and bits as without the field; 1: the text lines are also grouped into blocks (paragraphs,
                             column pieces) in reading order (DESIGN.md "Text blocks"); other values make ttr_create fail.  Needs lines = 1 */
+  int mixed_batches;     /* 0 (default): ttr_images_to_data batches images of equal size, as without the field; 1: it batches images that share one
+                            detector canvas, whatever their sizes (DESIGN.md "Mixed-size batches"); other values make ttr_create fail.  Every result is
+                            the same either way; only the batching changes */
 } ttr_config;
 
 void ttr_config_default(ttr_config* cfg);
@@ -102,6 +105,26 @@ int ttr_stream_flush(ttr_engine* e, ttr_result** out_prev, int* n_prev);
  * a row: the reference's "Error reading image from file", tuatara.cpp:344-347) or the images of a batch that failed on the GPU: those keep EMPTY results, every
  * other out[i] is delivered, and ttr_last_error() lists the failed indices with the first failure's message - what a loop over image_to_data gives. */
 int ttr_images_to_data(ttr_engine* e, const uint8_t* const* images, const int* hs, const int* ws, const int* row_strides, int n, ttr_result** out);
+
+/* Mixed-size batches (DESIGN.md "Mixed-size batches").  The detector never sees a page's size, only its canvas: H x W = the page scaled by `ratio`
+ * (so that its longer side is at most canvas_size), each side rounded up to a multiple of 32.  Pages of different sizes and row strides that share
+ * one canvas can therefore travel as one batch.  A ttr_page is one such page in device memory; with a row stride it can be a window of a larger
+ * device image.
+ * ttr_canvas_geometry: host only, no GPU work - the canvas and ratio the engine gives an h x w page (e = NULL: an engine of the default config).
+ * Returns 0; -1 for h <= 0, w <= 0 or a page too thin to resize (ttr_last_error).
+ * ttr_pages_to_data_dev_v / ttr_stream_push_v: ttr_pages_to_data_dev / ttr_stream_push for n such pages; every result equals the page's own
+ * single call.  A batch whose pages do not share one canvas is refused before anything is enqueued (the message names the first offending page and
+ * both canvases); a page with h <= 0, w <= 0, a row stride shorter than 3 w or too thin to resize fails the call.  Streamed batches of both kinds
+ * mix freely and are returned by the same ttr_stream_flush; the pages must stay valid until their batch's results have been returned.  With a
+ * communicator attached they are collectives like their twins.
+ * ttr_images_to_data with ttr_config.mixed_batches = 1 batches by canvas instead of by size: same results, fewer and larger batches for lists
+ * of many sizes.  ttr_last_images_batches: the pages per batch of the last ttr_images_to_data call, in run order (at most cap entries are
+ * written); returns their number. */
+typedef struct ttr_page { const uint8_t* data; int h, w; int row_stride; } ttr_page;   /* device memory, u8 HWC 3 channels; row_stride in bytes, 0 = 3 * w */
+int ttr_canvas_geometry(const ttr_engine* e, int h, int w, int* H, int* W, float* ratio);
+int ttr_pages_to_data_dev_v(ttr_engine* e, const ttr_page* pages, int n, ttr_result** out);
+int ttr_stream_push_v(ttr_engine* e, const ttr_page* pages, int n, ttr_result** out_prev, int* n_prev);
+int ttr_last_images_batches(ttr_engine* e, int32_t* pages_per_batch, int cap);
 
 int ttr_result_count(const ttr_result* r);
 const char* ttr_result_text(const ttr_result* r, int i);
@@ -341,6 +364,17 @@ int ttr_pack_crops_rectified(ttr_engine* e, const uint8_t* hwc_u8, int h, int w,
  * a zero crop. */
 int ttr_pack_crops_oriented(ttr_engine* e, const uint8_t* hwc_u8, int h, int w, int row_stride, const float* rects5, int n,
                             float ratio, int crop_mode, int turn, uint8_t* crops, float* quads_out);
+/* The table kernels of a mixed-size batch as stage entry points (DESIGN.md "Mixed-size batches"); both refuse while batches stream.
+ * ttr_resize_canvas_batch: n host images of different sizes that share one canvas (row_strides in bytes, NULL = tightly packed; the pages keep
+ * their strides on the device) -> canvases u8 [n][*H][*W][3] and ratios [n], by ONE launch of resize_pad_pages_kernel; canvas i is byte for byte
+ * ttr_resize_canvas's of image i.
+ * ttr_pack_crops_batch: n rects in heat-map pixels, rect i on page page_of[i] of n_pages such images, each page at its own ratio
+ * (ttr_canvas_geometry) -> crops [n][32][128][3] and quads_out (optional) [n][8], by ONE launch of the table packer; crop i is byte for byte
+ * ttr_pack_crops_oriented's for the same crop_mode and turn on its page alone. */
+int ttr_resize_canvas_batch(ttr_engine* e, const uint8_t* const* images, const int* hs, const int* ws, const int* row_strides, int n, uint8_t* canvases,
+                            size_t cap, int* H, int* W, float* ratios);
+int ttr_pack_crops_batch(ttr_engine* e, const uint8_t* const* images, const int* hs, const int* ws, const int* row_strides, int n_pages,
+                         const float* rects5, const int32_t* page_of, int n, int crop_mode, int turn, uint8_t* crops, float* quads_out);
 /* PARSeq forward (tuatara.cpp:443-446 + :307): crops u8 [n][32][128][3] -> logits f32 [n][26][95];
  * ar_logits (optional) receives the autoregressive pass's logits - per crop defined up to and including its EOS step (upstream leaves
  * its loop when every crop has emitted EOS; behind a crop's own EOS the bf16 engine skips it, and zero-fills the steps behind the batch's

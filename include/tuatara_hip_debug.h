@@ -106,6 +106,9 @@ int ttr_dbg_deskew(const float* rect5, float* quad8, double* coef6, int64_t* fix
  * (crop_mode 1: the deskewed quad; 0: the clamped boundingRect's pixel edges) turned by `turn` quarter turns, quad8 = Q_t, fixed6 its
  * coefficients as the engine hands them to pack_crops_rect_kernel.  Returns 0, -1 on bad arguments. */
 int ttr_dbg_orient_quad(const float* rect5, int h, int w, int crop_mode, int turn, float* quad8, int64_t* fixed6);
+/* canvas_geometry on the host for any canvas_size / mag_ratio (what ttr_canvas_geometry answers for an engine of that config): h32 x w32, the ratio and
+ * the resized page's target_h x target_w inside the canvas.  Any output may be NULL.  Returns 0, -1 for h <= 0 or w <= 0. */
+int ttr_dbg_canvas_geometry(int h, int w, int canvas_size, float mag_ratio, int* H, int* W, float* ratio, int* target_h, int* target_w);
 
 
 #ifdef __cplusplus

@@ -1,5 +1,6 @@
 // The C ABI of include/tuatara_hip.h: extern "C", plain pointers and sizes, no exceptions across it.
 #include "engine.h"
+#include "page_table.h"
 
 namespace ttr {
 
@@ -30,13 +31,54 @@ static RRect stage_crop_rect(const float* r5, float ratio, int h, int w, int* re
   return b;
 }
 
+// ttr_pack_crops_oriented's rule for one rect on an h x w page: the clamped crop rectangle rc[0..4), the packer's coefficients coef8 and the turned quad
+static void oriented_crop(const float* r5, float ratio, int h, int w, int crop_mode, int turn, int* rc, int64_t* coef8, float* quad8) {
+  const RRect b = stage_crop_rect(r5, ratio, h, w, rc);
+  Pt2f q[4], qt[4]; double cf[6]; int64_t fx[6];
+  const int kind = deskew_quad(b, q, cf);                       // Q: the deskewed quad (crop_mode 1) ...
+  if (crop_mode == TTR_CROP_BOUNDING) box_edge_quad(rc[0], rc[1], rc[2], rc[3], q);   // ... or the clamped boundingRect's pixel edges
+  if (turn == 0 && crop_mode == TTR_CROP_RECTIFIED) {           // ttr_pack_crops_rectified's crop
+    coef8[0] = kind;
+    deskew_fixed(cf, fx);
+  } else {
+    coef8[0] = 1;
+    turn_coef(q, turn, fx);
+  }
+  for (int k = 0; k < 6; ++k) coef8[1 + k] = fx[k];
+  for (int k = 0; k < 4; ++k) qt[k] = q[(k + turn) & 3];
+  if (quad8) for (int k = 0; k < 4; ++k) { quad8[2 * k] = qt[k].x; quad8[2 * k + 1] = qt[k].y; }
+}
+
+// the stage calls of the table kernels: n host images, each with its own row stride kept, one after another in staging_img at offsets rounded up to 256
+// bytes -> their pages (checked: sizes, strides, one canvas) and the device page table of slot 0, both enqueued on the engine's stream
+static std::vector<Engine::Page> stage_host_pages(Engine& E, const uint8_t* const* images, const int* hs, const int* ws, const int* row_strides, int n) {
+  if (n <= 0 || !images || !hs || !ws) throw std::runtime_error("null argument");
+  std::vector<Engine::Page> pages((size_t)n);
+  std::vector<size_t> off((size_t)n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    const long long stride = row_strides ? (long long)row_strides[i] : (long long)ws[i] * 3;
+    if (!images[i] || hs[i] <= 0 || ws[i] <= 0 || stride < (long long)ws[i] * 3 || stride > 0x7fffffffLL) throw std::runtime_error("Error reading image from file");
+    off[i + 1] = (off[i] + (size_t)hs[i] * (size_t)stride + 255) & ~(size_t)255;
+  }
+  E.staging_img.ensure(off[n]);
+  for (int i = 0; i < n; ++i) {
+    const int stride = row_strides ? row_strides[i] : ws[i] * 3;
+    pages[i] = Engine::Page{E.staging_img.as<uint8_t>() + off[i], hs[i], ws[i], stride, CanvasGeom{}};
+  }
+  E.check_pages(pages);
+  for (int i = 0; i < n; ++i)
+    TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.as<uint8_t>() + off[i], (size_t)pages[i].stride, images[i], (size_t)pages[i].stride, (size_t)ws[i] * 3, hs[i], hipMemcpyHostToDevice, E.stream));
+  E.upload_page_table(pages, 0);
+  return pages;
+}
+
 extern "C" {
 
 void ttr_config_default(ttr_config* c) {
   c->precision = TTR_PREC_F16X4; c->device = 0; c->canvas_size = 1024; c->mag_ratio = 1.0f;
   c->text_threshold = 0.7f; c->link_threshold = 0.4f; c->low_text = 0.4f; c->min_area = 10;
   c->strict_crops = 0; c->max_components = 4096; c->verbose = 0; c->crop_mode = TTR_CROP_BOUNDING;
-  c->orient = TTR_ORIENT_OFF; c->orient_page = 0; c->lines = 0; c->chars = 0; c->blocks = 0;
+  c->orient = TTR_ORIENT_OFF; c->orient_page = 0; c->lines = 0; c->chars = 0; c->blocks = 0; c->mixed_batches = 0;
 }
 
 const char* ttr_last_error(void) { return g_last_error.c_str(); }
@@ -76,6 +118,54 @@ int ttr_stream_push(ttr_engine* e, const uint8_t* d_pages, int n, int h, int w, 
   hand_out(res, np, out_prev);
   *n_prev = np;
   return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_canvas_geometry(const ttr_engine* e, int h, int w, int* H, int* W, float* ratio) {
+  TTR_GUARD_BEGIN
+  ttr_config c;
+  if (e) c = e->e->cfg; else ttr_config_default(&c);
+  if (h <= 0 || w <= 0) throw std::runtime_error("Error reading image from file");
+  const CanvasGeom g = canvas_geometry(h, w, c.canvas_size, c.mag_ratio);
+  if (g.target_h <= 0 || g.target_w <= 0) throw std::runtime_error("image too thin to resize");
+  if (H) *H = g.h32;
+  if (W) *W = g.w32;
+  if (ratio) *ratio = g.ratio;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_pages_to_data_dev_v(ttr_engine* e, const ttr_page* pages, int n, ttr_result** out) {
+  TTR_GUARD_BEGIN
+  if (!e || !out || (n > 0 && !pages)) throw std::runtime_error("null argument");
+  EngineScope lk(*e->e);
+  std::vector<Result> res;
+  e->e->run_pages_v(pages, n, res);
+  hand_out(res, n, out);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_stream_push_v(ttr_engine* e, const ttr_page* pages, int n, ttr_result** out_prev, int* n_prev) {
+  TTR_GUARD_BEGIN
+  if (!e || !out_prev || !n_prev || (n > 0 && !pages)) throw std::runtime_error("null argument");
+  EngineScope lk(*e->e);
+  std::vector<Result> res;
+  int np = 0;
+  e->e->stream_push_v(pages, n, res, np);
+  hand_out(res, np, out_prev);
+  *n_prev = np;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_last_images_batches(ttr_engine* e, int32_t* pages_per_batch, int cap) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  EngineScope lk(*e->e);
+  const std::vector<int32_t>& b = e->e->last_batches;
+  if (pages_per_batch) for (int i = 0; i < (int)b.size() && i < cap; ++i) pages_per_batch[i] = b[i];
+  return (int)b.size();
   TTR_GUARD_END(-1)
 }
 
@@ -593,23 +683,8 @@ int ttr_pack_crops_oriented(ttr_engine* e, const uint8_t* img, int h, int w, int
   if (n <= 0) return 0;
   std::vector<int> rects((size_t)n * 5, 0);
   std::vector<int64_t> coef((size_t)n * 8, 0);
-  for (int i = 0; i < n; ++i) {
-    int* rc = &rects[5 * (size_t)i];
-    const RRect b = stage_crop_rect(rects5 + 5 * i, ratio, h, w, rc);
-    Pt2f q[4], qt[4]; double cf[6]; int64_t fx[6];
-    const int kind = deskew_quad(b, q, cf);                       // Q: the deskewed quad (crop_mode 1) ...
-    if (crop_mode == TTR_CROP_BOUNDING) box_edge_quad(rc[0], rc[1], rc[2], rc[3], q);   // ... or the clamped boundingRect's pixel edges
-    if (turn == 0 && crop_mode == TTR_CROP_RECTIFIED) {           // ttr_pack_crops_rectified's crop
-      coef[8 * i] = kind;
-      deskew_fixed(cf, fx);
-    } else {
-      coef[8 * i] = 1;
-      turn_coef(q, turn, fx);
-    }
-    for (int k = 0; k < 6; ++k) coef[8 * i + 1 + k] = fx[k];
-    for (int k = 0; k < 4; ++k) qt[k] = q[(k + turn) & 3];
-    if (quads_out) for (int k = 0; k < 4; ++k) { quads_out[8 * i + 2 * k] = qt[k].x; quads_out[8 * i + 2 * k + 1] = qt[k].y; }
-  }
+  for (int i = 0; i < n; ++i)
+    oriented_crop(rects5 + 5 * (size_t)i, ratio, h, w, crop_mode, turn, &rects[5 * (size_t)i], &coef[8 * (size_t)i], quads_out ? quads_out + 8 * (size_t)i : nullptr);
   E.staging_img.ensure((size_t)h * w * 3);
   E.rects_dev.ensure(rects.size() * 4);
   E.coef_dev.ensure(coef.size() * 8);
@@ -624,6 +699,63 @@ int ttr_pack_crops_oriented(ttr_engine* e, const uint8_t* img, int h, int w, int
   }
   TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
   TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_resize_canvas_batch(ttr_engine* e, const uint8_t* const* images, const int* hs, const int* ws, const int* row_strides, int n, uint8_t* canvases,
+                            size_t cap, int* H, int* W, float* ratios) {
+  TTR_GUARD_BEGIN
+  if (!e || !canvases || !H || !W) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_resize_canvas_batch");
+  const std::vector<Engine::Page> pages = stage_host_pages(E, images, hs, ws, row_strides, n);
+  const CanvasGeom& g = pages[0].g;
+  *H = g.h32; *W = g.w32;
+  if (ratios) for (int i = 0; i < n; ++i) ratios[i] = pages[i].g.ratio;
+  const size_t need = (size_t)n * g.h32 * g.w32 * 3;
+  if (cap < need) throw std::runtime_error("canvas buffer too small");
+  E.canvas.ensure(need);
+  launch_resize_pad_pages(E.page_table[0].as<PageRow>(), E.canvas.as<uint8_t>(), g.h32, g.w32, 1, n, E.stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(canvases, E.canvas.p, need, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_pack_crops_batch(ttr_engine* e, const uint8_t* const* images, const int* hs, const int* ws, const int* row_strides, int n_pages,
+                         const float* rects5, const int32_t* page_of, int n, int crop_mode, int turn, uint8_t* crops_out, float* quads_out) {
+  TTR_GUARD_BEGIN
+  if (crop_mode != TTR_CROP_BOUNDING && crop_mode != TTR_CROP_RECTIFIED) throw std::runtime_error("crop_mode must be 0 or 1");
+  if (turn < 0 || turn > 3) throw std::runtime_error("turn must be 0..3");
+  if (!e || (n > 0 && (!rects5 || !page_of || !crops_out))) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_pack_crops_batch");
+  if (n <= 0) return 0;
+  for (int i = 0; i < n; ++i)
+    if (page_of[i] < 0 || page_of[i] >= n_pages) throw std::runtime_error("ttr_pack_crops_batch: page_of[" + std::to_string(i) + "] is not a page of the batch");
+  const std::vector<Engine::Page> pages = stage_host_pages(E, images, hs, ws, row_strides, n_pages);
+  std::vector<int> rects((size_t)n * 5, 0);
+  std::vector<int64_t> coef((size_t)n * 8, 0);
+  for (int i = 0; i < n; ++i) {
+    const Engine::Page& P = pages[(size_t)page_of[i]];
+    oriented_crop(rects5 + 5 * (size_t)i, P.g.ratio, P.h, P.w, crop_mode, turn, &rects[5 * (size_t)i], &coef[8 * (size_t)i], quads_out ? quads_out + 8 * (size_t)i : nullptr);
+    rects[5 * (size_t)i + 4] = page_of[i];
+  }
+  E.rects_dev.ensure(rects.size() * 4);
+  E.coef_dev.ensure(coef.size() * 8);
+  E.crops.ensure((size_t)n * 32 * 128 * 3);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
+  if (turn == 0 && crop_mode == TTR_CROP_BOUNDING) {
+    launch_pack_crops_pages(E.page_table[0].as<PageRow>(), E.rects_dev.as<int>(), E.crops.as<uint8_t>(), n, E.stream);
+  } else {
+    TTR_HIP_CHECK(hipMemcpyAsync(E.coef_dev.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice, E.stream));
+    launch_pack_crops_rect_pages(E.page_table[0].as<PageRow>(), E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
+  }
+  TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));   // (rects and coef are pageable host vectors: they live until here)
   return 0;
   TTR_GUARD_END(-1)
 }

@@ -509,6 +509,17 @@ int ttr_dbg_deskew(const float* r5, float* quad8, double* coef6, int64_t* fixed6
   TTR_GUARD_END(-1)
 }
 
+int ttr_dbg_canvas_geometry(int h, int w, int canvas_size, float mag_ratio, int* H, int* W, float* ratio, int* target_h, int* target_w) {
+  if (h <= 0 || w <= 0) return -1;
+  const CanvasGeom g = canvas_geometry(h, w, canvas_size, mag_ratio);
+  if (H) *H = g.h32;
+  if (W) *W = g.w32;
+  if (ratio) *ratio = g.ratio;
+  if (target_h) *target_h = g.target_h;
+  if (target_w) *target_w = g.target_w;
+  return 0;
+}
+
 int ttr_dbg_orient_quad(const float* r5, int h, int w, int crop_mode, int turn, float* quad8, int64_t* fixed6) {
   TTR_GUARD_BEGIN
   if (turn < 0 || turn > 3 || (crop_mode != TTR_CROP_BOUNDING && crop_mode != TTR_CROP_RECTIFIED)) throw std::runtime_error("bad turn or crop_mode");

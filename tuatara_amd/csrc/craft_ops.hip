@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "page_table.h"
 #include "resize_dev.h"
 
 namespace ttr {
@@ -27,6 +28,24 @@ void launch_resize_pad_u8(const uint8_t* src, int sh, int sw, int sstride, uint8
                           int pages, size_t src_page) {
   ResizeGeom g = make_resize_geom(sh, sw, th, tw);
   hipLaunchKernelGGL(resize_pad_u8_kernel, dim3((W + 255) / 256, H, pages), dim3(256), 0, s, src, src_page, sstride, g, dst, H, W, swap_rb);
+}
+
+// blockIdx.z = page of a batch of pages of different sizes that share the canvas: source, stride and geometry from the page's table row (block-uniform)
+__global__ void resize_pad_pages_kernel(const PageRow* __restrict__ table, uint8_t* dst, int H, int W, int swap_rb) {
+  int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= W) return;
+  const PageRow& r = table[blockIdx.z];
+  const ResizeGeom g = r.g;
+  dst += (size_t)blockIdx.z * H * W * 3;
+  uint8_t px[3] = {0, 0, 0};
+  if (y < g.dh && x < g.dw) resize_pixel_u8c3(r.data, r.stride, g, y, x, px);
+  uint8_t* d = dst + ((size_t)y * W + x) * 3;
+  d[0] = swap_rb ? px[2] : px[0]; d[1] = px[1]; d[2] = swap_rb ? px[0] : px[2];
+}
+
+void launch_resize_pad_pages(const PageRow* table, uint8_t* dst, int H, int W, int swap_rb, int pages, hipStream_t s) {
+  if (pages <= 0) return;
+  hipLaunchKernelGGL(resize_pad_pages_kernel, dim3((W + 255) / 256, H, pages), dim3(256), 0, s, table, dst, H, W, swap_rb);
 }
 
 // ------------------------------------------------------------------ first layer im2col

@@ -405,6 +405,7 @@ Engine::Engine(const std::string& dir, const ttr_config& c) : cfg(c) {
   if (cfg.chars != 0 && cfg.chars != 1) throw std::runtime_error("chars must be 0 or 1");
   if (cfg.blocks != 0 && cfg.blocks != 1) throw std::runtime_error("blocks must be 0 or 1");
   if (cfg.blocks && !cfg.lines) throw std::runtime_error("blocks needs lines = 1");
+  if (cfg.mixed_batches != 0 && cfg.mixed_batches != 1) throw std::runtime_error("mixed_batches must be 0 or 1");
   prec = cfg.precision == TTR_PREC_F32 ? kF32 : cfg.precision == TTR_PREC_F16X4 ? kSplit : kBF16;
   es = prec == kBF16 ? 2 : 4;
   int ndev = 0;
@@ -445,6 +446,7 @@ Engine::~Engine() {
   for (auto& sl : chars_ev) for (auto& x : sl) if (x) (void)hipEventDestroy(x);
   for (auto& sl : evr) for (auto& x : sl) if (x) (void)hipEventDestroy(x);
   for (auto& x : up_ev) if (x) (void)hipEventDestroy(x);
+  for (auto& x : table_ev) if (x) (void)hipEventDestroy(x);
   if (up_stream) (void)hipStreamDestroy(up_stream);
   if (copy_stream) (void)hipStreamDestroy(copy_stream);
   if (recog_stream) (void)hipStreamDestroy(recog_stream);

@@ -664,9 +664,13 @@ struct Engine {
   // while the host turns batch j's components into boxes, and still has a whole recogniser queued while the host decodes batch j-2,
   // returns to the caller and comes back with batch j+1 — no GPU idle at any hand-over; one stream, every kernel still runs alone.
   // Host staging (crop rectangles, token ids) and the completion events exist twice (slot = batch parity).
+  // A page of a batch by itself: where it lives on the device, its size and row stride, and its geometry on the batch's canvas.
+  struct Page { const uint8_t* data = nullptr; int h = 0, w = 0, stride = 0; CanvasGeom g{}; };
   struct PageBatch {
-    const uint8_t* d_pages = nullptr; int n = 0, h = 0, w = 0;
-    CanvasGeom g{}; int H = 0, W = 0, H2 = 0, W2 = 0; size_t page_bytes = 0;
+    const uint8_t* d_pages = nullptr; int n = 0, h = 0, w = 0;   // a uniform batch as its entry point passed it: n pages of h x w, contiguous
+    bool mixed = false;                // the pages came one by one (ttr_page) and may differ in size and stride: the table kernels run (DESIGN.md "Mixed-size batches")
+    std::vector<Page> pages;           // [n] every page by itself; filled by detect_enqueue from the scalars above for a uniform batch
+    int H = 0, W = 0, H2 = 0, W2 = 0;  // the canvas all pages share
     std::vector<std::vector<RRect>> boxes;
     std::vector<int> rects, page_of;
     std::vector<int64_t> coef;         // crop_mode = TTR_CROP_RECTIFIED: {kind, X0, Ax, Bx, Y0, Ay, By, 0} per crop, beside rects
@@ -681,6 +685,16 @@ struct Engine {
   PageBatch q1, q2;        // streamed batches: q1 = boxes known (recogniser enqueued or not), q2 = older, recogniser enqueued, results not yet returned
 
   void detect_enqueue(PageBatch& B);
+  // Mixed-size batches: the device page table of a batch (page_table.h), one per pipeline slot - the resize of batch j reads its table on the main stream while
+  // the packers of batch j - 1 read theirs on the recogniser's.  upload_page_table writes the rows into the slot's pinned buffer and copies them once, on
+  // `stream`, behind table_ev[sl] (recorded behind the last packer that read the slot's previous table; a no-op before the first).
+  DevBuf page_table[2];
+  PinnedBuf h_page_table[2];
+  hipEvent_t table_ev[2] = {nullptr, nullptr};
+  void upload_page_table(const std::vector<Page>& pages, int sl);
+  // every page's size, stride and canvas geometry checked and filled in; throws today's messages, and refuses pages that do not share one canvas
+  void check_pages(std::vector<Page>& pages) const;
+  static PageBatch mixed_batch(const ttr_page* pages, int n);
 
   // With a communicator attached a batch is a collective: a {status, pages} header travels before anything whose size depends on the
   // ranks' inputs, so that a rank that failed in its detector (`pre`: what detect_enqueue threw; or the box extraction below) or passed
@@ -730,6 +744,8 @@ struct Engine {
   // its own they would race with it
   void refuse_while_streaming(const char* what) const { if (q1.live || q2.live) throw std::runtime_error(std::string(what) + ": streamed batches are in flight: call ttr_stream_flush until it returns none"); }
   void run_pages(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results);
+  void run_pages_v(const ttr_page* pages, int n, std::vector<Result>& results);   // pages of different sizes and strides that share one canvas
+  void run_batch(PageBatch& B, std::vector<Result>& results);
 
   // Latency mode (the reference's 6-thread fan-out over chunks of the crop batch, tuatara.cpp:450-485, across
   // GPUs): rank 0 detects and packs the crop batch, the batch is broadcast, rank r recognises the contiguous shard r of
@@ -740,6 +756,8 @@ struct Engine {
   // Streamed form: returns the results of the batch pushed TWO calls earlier (prev_n = its page count, 0 for the first two pushes).
   // The pages of a batch must stay valid until its results have been returned (the crop packer reads them one push later).
   void stream_push(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& prev_results, int& prev_n);
+  void stream_push_v(const ttr_page* pages, int n, std::vector<Result>& prev_results, int& prev_n);   // mixes freely with stream_push
+  void push_batch(PageBatch&& B, std::vector<Result>& prev_results, int& prev_n);
   // results of the oldest batch in flight (prev_n = 0: none left)
   void stream_flush(std::vector<Result>& prev_results, int& prev_n);
 
@@ -756,7 +774,10 @@ struct Engine {
   // results[i] = what run_pages returns for image i alone.  An unreadable entry (null / empty / short stride: the reference's "Error reading image from file",
   // tuatara.cpp:344-347) and every image of a batch that failed on the GPU (e.g. the range guard) keep an empty result and are listed in `failed` (input
   // indices; first_error: the first failure's message); everything else is delivered - what a loop over image_to_data does with one bad image.
+  // cfg.mixed_batches = 1: the buckets are canvases (h32, w32) instead of sizes, every batch's images are staged one after another at offsets rounded up to
+  // 256 bytes and run through the table path; an image whose geometry is invalid fails alone, before bucketing.
   void run_images(const std::vector<HostImage>& imgs, std::vector<Result>& results, std::vector<int>& failed, std::string& first_error);
+  std::vector<int32_t> last_batches;   // pages per batch of the last run_images call, in run order (ttr_last_images_batches)
   int stream_fail_age = 0;   // set by stream_push / stream_flush before they throw: 0 = the batch being pushed never entered the pipeline, 2 = the batch whose results were due failed and has left it
 };
 

@@ -4,6 +4,7 @@
 #include <limits>
 
 #include "engine.h"
+#include "page_table.h"
 
 namespace ttr {
 
@@ -172,18 +173,52 @@ void Engine::ccl_collect(int p0, int pages, int g, int H2, int W2, std::vector<s
   host_us[1] += (float)(tc1 - tc0); host_us[2] += (float)(tc2 - tc1); host_us[3] += (float)(now_us() - tc2);
 }
 
+void Engine::check_pages(std::vector<Page>& pages) const {
+  for (size_t i = 0; i < pages.size(); ++i) {
+    Page& P = pages[i];
+    if (!P.data || P.h <= 0 || P.w <= 0 || P.stride < P.w * 3) throw std::runtime_error("Error reading image from file");  // image.empty(), tuatara.cpp:344
+    P.g = canvas_geometry(P.h, P.w, cfg.canvas_size, cfg.mag_ratio);
+    if (P.g.target_h <= 0 || P.g.target_w <= 0) throw std::runtime_error("image too thin to resize");
+    if (P.g.h32 != pages[0].g.h32 || P.g.w32 != pages[0].g.w32)
+      throw std::runtime_error("mixed-size batch: page " + std::to_string(i) + " (" + std::to_string(P.h) + " x " + std::to_string(P.w) + ") has canvas " + std::to_string(P.g.h32) + " x " +
+                               std::to_string(P.g.w32) + ", page 0 (" + std::to_string(pages[0].h) + " x " + std::to_string(pages[0].w) + ") has canvas " + std::to_string(pages[0].g.h32) +
+                               " x " + std::to_string(pages[0].g.w32) + ": the pages of a batch must share one detector canvas (ttr_canvas_geometry)");
+  }
+}
+
+void Engine::upload_page_table(const std::vector<Page>& pages, int sl) {
+  const size_t bytes = pages.size() * sizeof(PageRow);
+  h_page_table[sl].ensure(bytes); page_table[sl].ensure(bytes);
+  PageRow* rows = h_page_table[sl].as<PageRow>();
+  for (size_t i = 0; i < pages.size(); ++i) {
+    const Page& P = pages[i];
+    rows[i] = PageRow{P.data, P.h, P.w, P.stride, 0, make_resize_geom(P.h, P.w, P.g.target_h, P.g.target_w)};
+  }
+  if (!table_ev[sl]) TTR_HIP_CHECK(hipEventCreateWithFlags(&table_ev[sl], hipEventDisableTiming));
+  TTR_HIP_CHECK(hipStreamWaitEvent(stream, table_ev[sl], 0));   // the packers of the slot's previous batch may still read its table on the recogniser's stream (no-op before the first)
+  TTR_HIP_CHECK(hipMemcpyAsync(page_table[sl].p, rows, bytes, hipMemcpyHostToDevice, stream));
+}
+
 void Engine::detect_enqueue(PageBatch& B) {
   range_use(kRangeDet0 + (B.slot & 1));   // the detector's kernels of this batch watch its own word (engine.h)
-  if (B.h <= 0 || B.w <= 0) throw std::runtime_error("Error reading image from file");  // image.empty(), tuatara.cpp:344
-  B.g = canvas_geometry(B.h, B.w, cfg.canvas_size, cfg.mag_ratio);
-  if (B.g.target_h <= 0 || B.g.target_w <= 0) throw std::runtime_error("image too thin to resize");
-  B.H = B.g.h32; B.W = B.g.w32; B.H2 = B.H / 2; B.W2 = B.W / 2;
-  B.page_bytes = (size_t)B.h * B.w * 3;
+  if (!B.mixed) {                         // a uniform batch: every page is its entry point's scalars
+    if (B.h <= 0 || B.w <= 0) throw std::runtime_error("Error reading image from file");  // image.empty(), tuatara.cpp:344
+    const CanvasGeom g = canvas_geometry(B.h, B.w, cfg.canvas_size, cfg.mag_ratio);
+    if (g.target_h <= 0 || g.target_w <= 0) throw std::runtime_error("image too thin to resize");
+    B.pages.resize((size_t)B.n);
+    for (int i = 0; i < B.n; ++i) B.pages[i] = Page{B.d_pages + (size_t)i * B.h * B.w * 3, B.h, B.w, B.w * 3, g};
+  } else {
+    check_pages(B.pages);                 // (before anything is enqueued)
+  }
+  const Page& P0 = B.pages[0];
+  B.H = P0.g.h32; B.W = P0.g.w32; B.H2 = B.H / 2; B.W2 = B.W / 2;
   const int n = B.n, H = B.H, W = B.W, H2 = B.H2, W2 = B.W2;
   canvas.ensure((size_t)n * H * W * 3);
   heat.ensure((size_t)n * H2 * W2 * 2 * 4);
+  if (B.mixed) upload_page_table(B.pages, B.slot & 1);   // ahead of the resize; the batch's packers read it later (engine.h)
   TTR_HIP_CHECK(hipEventRecord(ev[0], stream));
-  launch_resize_pad_u8(B.d_pages, B.h, B.w, B.w * 3, canvas.as<uint8_t>(), B.g.target_h, B.g.target_w, H, W, 1, stream, n, B.page_bytes);
+  if (B.mixed) launch_resize_pad_pages(page_table[B.slot & 1].as<PageRow>(), canvas.as<uint8_t>(), H, W, 1, n, stream);
+  else launch_resize_pad_u8(P0.data, P0.h, P0.w, P0.stride, canvas.as<uint8_t>(), P0.g.target_h, P0.g.target_w, H, W, 1, stream, n, (size_t)P0.h * P0.w * 3);
   // CRAFT in groups of <= 16 pages: bounds the activation workspace (~0.5 GB/page) and keeps every tensor
   // inside the 2 GiB window gemm2's 32-bit buffer offsets address.  Each group's CCL follows its CRAFT, so the host reads
   // group g's components back (and runs its calipers) while the GPU is busy with group g + 1.
@@ -258,7 +293,6 @@ void Engine::detect_collect(PageBatch& B, std::exception_ptr pre) {
 
 void Engine::detect_collect_local(PageBatch& B) {
   const int n = B.n, GP = B.group, groups = (n + GP - 1) / GP;
-  const float ratio_w = 1.f / B.g.ratio, ratio_h = 1.f / B.g.ratio;   // tuatara.cpp:360-361
   std::vector<std::vector<RRect>> dets(n);
   B.boxes.assign(n, std::vector<RRect>());
   B.rects.clear(); B.page_of.clear(); B.coef.clear(); B.twin.clear();   // x0,y0,x1,y1,page per crop; page index per crop; rectified crops' coefficients; twins'
@@ -275,21 +309,23 @@ void Engine::detect_collect_local(PageBatch& B) {
       for (int r = 0; r < 8; ++r)
         for (int c = 0; c < 5; ++c) {
           RRect g;
-          g.cx = (c + 0.5f) * (float)B.W2 / 5.f; g.cy = (r + 0.5f) * (float)B.H2 / 8.f; g.w = 75.f * B.g.ratio; g.h = 20.f * B.g.ratio; g.angle = 0.f;
+          g.cx = (c + 0.5f) * (float)B.W2 / 5.f; g.cy = (r + 0.5f) * (float)B.H2 / 8.f; g.w = 75.f * B.pages[i].g.ratio; g.h = 20.f * B.pages[i].g.ratio; g.angle = 0.f;
           dets[i].push_back(g);
         }
     }
   }
   for (int i = 0; i < n; ++i) {
+    const Page& P = B.pages[i];
+    const float ratio_w = 1.f / P.g.ratio, ratio_h = 1.f / P.g.ratio;   // tuatara.cpp:360-361
     for (const RRect& r : dets[i]) {
       RRect b = adjust_coordinates(r, ratio_w, ratio_h);            // :406
       int xywh[4];
       bounding_rect(b, xywh);                                       // :416
       int x0 = xywh[0], y0 = xywh[1], x1 = xywh[0] + xywh[2], y1 = xywh[1] + xywh[3];
       if (cfg.strict_crops) {
-        if (x0 < 0 || y0 < 0 || x1 > B.w || y1 > B.h) throw std::runtime_error("text box leaves the image (cv::Exception in the reference, tuatara.cpp:416)");
+        if (x0 < 0 || y0 < 0 || x1 > P.w || y1 > P.h) throw std::runtime_error("text box leaves the image (cv::Exception in the reference, tuatara.cpp:416)");
       } else {
-        x0 = std::max(x0, 0); y0 = std::max(y0, 0); x1 = std::min(x1, B.w); y1 = std::min(y1, B.h);
+        x0 = std::max(x0, 0); y0 = std::max(y0, 0); x1 = std::min(x1, P.w); y1 = std::min(y1, P.h);
       }
       if (x1 <= x0 || y1 <= y0) continue;
       B.boxes[i].push_back(b);
@@ -323,8 +359,13 @@ void Engine::pack_batch_crops(const PageBatch& B, int sl) {
   h_rects[sl].ensure(B.rects.size() * 4);
   memcpy(h_rects[sl].p, B.rects.data(), B.rects.size() * 4);
   TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[sl].p, B.rects.size() * 4, hipMemcpyHostToDevice, stream));
+  // (a uniform batch: its pages are page_bytes apart behind the first; a mixed one: each crop's page from the slot's table)
+  const Page& P0 = B.pages[0];
+  const size_t page_bytes = (size_t)P0.h * P0.w * 3;
+  const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
   if (cfg.crop_mode != TTR_CROP_RECTIFIED) {
-    launch_pack_crops(B.d_pages, B.page_bytes, B.w * 3, rects_dev.as<int>(), crops.as<uint8_t>(), B.N, stream);
+    if (B.mixed) { launch_pack_crops_pages(table, rects_dev.as<int>(), crops.as<uint8_t>(), B.N, stream); TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream)); }
+    else launch_pack_crops(P0.data, page_bytes, P0.stride, rects_dev.as<int>(), crops.as<uint8_t>(), B.N, stream);
     return;
   }
   if (B.coef.size() != (size_t)B.N * 8) throw std::runtime_error("rectified crops: coefficient count does not match the crop count");
@@ -332,7 +373,8 @@ void Engine::pack_batch_crops(const PageBatch& B, int sl) {
   h_coef[sl].ensure(B.coef.size() * 8);
   memcpy(h_coef[sl].p, B.coef.data(), B.coef.size() * 8);
   TTR_HIP_CHECK(hipMemcpyAsync(coef_dev.p, h_coef[sl].p, B.coef.size() * 8, hipMemcpyHostToDevice, stream));
-  launch_pack_crops_rect(B.d_pages, B.page_bytes, B.w * 3, B.h, B.w, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), B.N, stream);
+  if (B.mixed) { launch_pack_crops_rect_pages(table, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), B.N, stream); TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream)); }
+  else launch_pack_crops_rect(P0.data, page_bytes, P0.stride, P0.h, P0.w, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), B.N, stream);
 }
 
 void Engine::pack_twin_crops(const PageBatch& B, int sl) {
@@ -348,8 +390,15 @@ void Engine::pack_twin_crops(const PageBatch& B, int sl) {
   const std::vector<int> first = page_first(B.page_of, B.n);
   std::copy(first.begin(), first.end(), reinterpret_cast<int32_t*>(h + coef_b + rect_b));
   TTR_HIP_CHECK(hipMemcpyAsync(orient_in.p, h, coef_b + rect_b + first_b, hipMemcpyHostToDevice, stream));
-  launch_pack_crops_rect(B.d_pages, B.page_bytes, B.w * 3, B.h, B.w, reinterpret_cast<const int*>(orient_in.as<uint8_t>() + coef_b), orient_in.as<int64_t>(),
-                         crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, stream);
+  const Page& P0 = B.pages[0];
+  if (B.mixed) {
+    launch_pack_crops_rect_pages(page_table[sl & 1].as<PageRow>(), reinterpret_cast<const int*>(orient_in.as<uint8_t>() + coef_b), orient_in.as<int64_t>(),
+                                 crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, stream);
+    TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the batch's last reader of the slot's table)
+  } else {
+    launch_pack_crops_rect(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, reinterpret_cast<const int*>(orient_in.as<uint8_t>() + coef_b), orient_in.as<int64_t>(),
+                           crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, stream);
+  }
 }
 
 int Engine::stage_batch_lines(const PageBatch& B, int sl) {
@@ -474,11 +523,11 @@ void Engine::stage_batch_chars(const PageBatch& B, int sl) {
   h_chars_in[sl].ensure(chars_in_bytes(N, KT));
   int64_t* coef = h_chars_in[sl].as<int64_t>();
   int32_t* page_of = reinterpret_cast<int32_t*>(coef + (size_t)N * KT * 6);
-  const double k = chars_scale(B.g.ratio);
   std::vector<float> q;
   q.reserve(8);
   int c = 0;
-  for (int pg = 0; pg < B.n; ++pg)
+  for (int pg = 0; pg < B.n; ++pg) {
+    const double k = chars_scale(B.pages[pg].g.ratio);         // (the ratio of the word's page)
     for (const RRect& b : B.boxes[pg]) {                       // (crop order: page after page)
       q.clear();
       push_quad(b, q);
@@ -488,6 +537,7 @@ void Engine::stage_batch_chars(const PageBatch& B, int sl) {
       page_of[c] = pg;
       ++c;
     }
+  }
   if (c != N) throw std::runtime_error("character boxes: box count does not match the crop count");
 }
 
@@ -709,16 +759,40 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
   else for (int pg = 0; pg < n; ++pg) decode_page(pg);
 }
 
+Engine::PageBatch Engine::mixed_batch(const ttr_page* pages, int n) {
+  if (n > 0 && !pages) throw std::runtime_error("null argument");
+  PageBatch B;
+  B.n = n; B.mixed = true;
+  B.pages.resize((size_t)std::max(n, 0));
+  for (int i = 0; i < n; ++i) {
+    // (a stride that does not fit the kernels' int stays invalid: check_pages refuses it as shorter than a row)
+    const long long stride = pages[i].row_stride ? (long long)pages[i].row_stride : (long long)pages[i].w * 3;
+    B.pages[i] = Page{pages[i].data, pages[i].h, pages[i].w, stride > 0x7fffffffLL ? -1 : (int)stride, CanvasGeom{}};
+  }
+  return B;
+}
+
 void Engine::run_pages(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results) {
-  results.assign(n, Result());
+  PageBatch B;
+  B.d_pages = d_pages; B.n = n; B.h = h; B.w = w;
+  run_batch(B, results);
+}
+
+void Engine::run_pages_v(const ttr_page* pages, int n, std::vector<Result>& results) {
+  PageBatch B = mixed_batch(pages, n);
+  run_batch(B, results);
+}
+
+void Engine::run_batch(PageBatch& B, std::vector<Result>& results) {
+  const int n = B.n;
+  results.assign(std::max(n, 0), Result());
   if (n <= 0) return;
   if (q1.live || q2.live) throw std::runtime_error("streamed batches are in flight: call ttr_stream_flush until it returns none");
   const double th0 = now_us();
   // the reference's progress lines (tuatara.cpp:328-329, :342, :421, :434: the models are loaded once per engine here, so those
   // lines report a fact; :386, :488, :509), on request only: callers do not parse stdout
   if (verbose) std::cout << ttr_version() << " (HIP " << HIP_VERSION_MAJOR << "." << HIP_VERSION_MINOR << ")\ncraft model loaded" << std::endl;
-  PageBatch B;
-  B.d_pages = d_pages; B.n = n; B.h = h; B.w = w; B.slot = 0;
+  B.slot = 0;
   std::exception_ptr pre;
   { RangeScope r("ttr:detect_enqueue"); try { detect_enqueue(B); } catch (...) { if (!comm) throw; pre = std::current_exception(); } }
   host_us[0] = (float)(now_us() - th0);
@@ -791,11 +865,20 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
 }
 
 void Engine::stream_push(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& prev_results, int& prev_n) {
-  prev_results.clear(); prev_n = 0;
-  if (n <= 0) throw std::runtime_error("stream_push: empty batch");
-  const double th0 = now_us();
   PageBatch B;
   B.d_pages = d_pages; B.n = n; B.h = h; B.w = w;
+  push_batch(std::move(B), prev_results, prev_n);
+}
+
+void Engine::stream_push_v(const ttr_page* pages, int n, std::vector<Result>& prev_results, int& prev_n) {
+  prev_results.clear(); prev_n = 0;
+  push_batch(mixed_batch(pages, n), prev_results, prev_n);
+}
+
+void Engine::push_batch(PageBatch&& B, std::vector<Result>& prev_results, int& prev_n) {
+  prev_results.clear(); prev_n = 0;
+  if (B.n <= 0) throw std::runtime_error("stream_push: empty batch");
+  const double th0 = now_us();
   B.slot = q1.live ? (q1.slot ^ 1) : 0;     // from the pipeline's state, not a counter: a push that throws leaves q1 / q2 and the slot parity as they were
   std::exception_ptr pre;      // (with a communicator: a failing rank still takes part in this batch's header exchange, detect_collect)
   stream_fail_age = 0;
@@ -842,9 +925,11 @@ void Engine::run_images(const std::vector<HostImage>& imgs, std::vector<Result>&
   const int n = (int)imgs.size();
   results.assign(n, Result());
   failed.clear(); first_error.clear();
+  last_batches.clear();
   if (n == 0) return;
   if (q1.live || q2.live) throw std::runtime_error("streamed batches are in flight: call ttr_stream_flush until it returns none");
   if (comm) throw std::runtime_error("ttr_images_to_data runs on one engine: detach the communicator (every rank takes its own list)");
+  const bool mixed = cfg.mixed_batches != 0;   // buckets are canvases, batches run through the table path (DESIGN.md "Mixed-size batches")
   std::vector<char> bad(n, 0);
   for (int i = 0; i < n; ++i) {
     const HostImage& im = imgs[i];
@@ -852,26 +937,46 @@ void Engine::run_images(const std::vector<HostImage>& imgs, std::vector<Result>&
       std::cerr << "Error reading image from file";
       bad[i] = 1; failed.push_back(i);
       if (first_error.empty()) first_error = "Error reading image from file (image " + std::to_string(i) + ")";
+    } else if (mixed) {   // a page the resize cannot take would fail its whole batch: it fails alone, here, and its canvas-mates go on
+      const CanvasGeom g = canvas_geometry(im.h, im.w, cfg.canvas_size, cfg.mag_ratio);
+      if (g.target_h <= 0 || g.target_w <= 0) {
+        std::cerr << "tuatara: image too thin to resize" << std::endl;
+        bad[i] = 1; failed.push_back(i);
+        if (first_error.empty()) first_error = "image too thin to resize (image " + std::to_string(i) + ")";
+      }
     }
   }
   // buckets of equal (h, w), the largest canvases first (the engine's grow-only workspaces then grow once), cut into batches
+  // (mixed: buckets of equal canvas (h32, w32) instead, input order inside a bucket; the map's order breaks ties of the sort below by ascending key)
   std::map<std::pair<int, int>, std::vector<int>> by_size;
-  for (int i = 0; i < n; ++i) if (!bad[i]) by_size[{imgs[i].h, imgs[i].w}].push_back(i);
+  for (int i = 0; i < n; ++i) {
+    if (bad[i]) continue;
+    if (mixed) { const CanvasGeom g = canvas_geometry(imgs[i].h, imgs[i].w, cfg.canvas_size, cfg.mag_ratio); by_size[{g.h32, g.w32}].push_back(i); }
+    else by_size[{imgs[i].h, imgs[i].w}].push_back(i);
+  }
   std::vector<std::pair<std::pair<int, int>, std::vector<int>>> buckets(by_size.begin(), by_size.end());
   std::stable_sort(buckets.begin(), buckets.end(), [&](const auto& a, const auto& b) {
+    if (mixed) return (size_t)a.first.first * a.first.second > (size_t)b.first.first * b.first.second;
     const CanvasGeom ga = canvas_geometry(a.first.first, a.first.second, cfg.canvas_size, cfg.mag_ratio), gb = canvas_geometry(b.first.first, b.first.second, cfg.canvas_size, cfg.mag_ratio);
     return (size_t)ga.h32 * ga.w32 > (size_t)gb.h32 * gb.w32;
   });
-  struct Batch { int h, w; std::vector<int> idx; };
+  struct Batch { int h, w; std::vector<int> idx; std::vector<size_t> off; };   // off (mixed): [idx.size() + 1] every image's offset in the staging slot, rounded up to 256 bytes
   std::vector<Batch> batches;
   size_t max_bytes = 0;
   const int cap = std::max(1, tn.images_batch);
   for (auto& b : buckets)
     for (size_t o = 0; o < b.second.size(); o += cap) {
-      Batch t{b.first.first, b.first.second, std::vector<int>(b.second.begin() + o, b.second.begin() + std::min(b.second.size(), o + cap))};
-      max_bytes = std::max(max_bytes, t.idx.size() * (size_t)t.h * t.w * 3);
+      Batch t{b.first.first, b.first.second, std::vector<int>(b.second.begin() + o, b.second.begin() + std::min(b.second.size(), o + cap)), {}};
+      if (mixed) {
+        t.off.assign(1, 0);
+        for (int i : t.idx) t.off.push_back((t.off.back() + (size_t)imgs[i].h * imgs[i].w * 3 + 255) & ~(size_t)255);
+        max_bytes = std::max(max_bytes, t.off.back());
+      } else {
+        max_bytes = std::max(max_bytes, t.idx.size() * (size_t)t.h * t.w * 3);
+      }
       batches.push_back(std::move(t));
     }
+  for (const Batch& b : batches) last_batches.push_back((int32_t)b.idx.size());
   if (!up_stream) {
     TTR_HIP_CHECK(hipStreamCreateWithFlags(&up_stream, hipStreamNonBlocking));
     for (auto& x : up_ev) TTR_HIP_CHECK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
@@ -884,8 +989,19 @@ void Engine::run_images(const std::vector<HostImage>& imgs, std::vector<Result>&
       TTR_HIP_CHECK(hipSetDevice(cfg.device));
       const Batch& b = batches[j];
       const int sl = j % kStageSlots;
-      const size_t page = (size_t)b.h * b.w * 3, row = (size_t)b.w * 3;
       uint8_t* dst = stage_host[sl].as<uint8_t>();
+      if (mixed) {   // every image tightly packed at its own offset; one copy of the slot's used bytes
+        for (size_t k = 0; k < b.idx.size(); ++k) {
+          const HostImage& im = imgs[b.idx[k]];
+          const size_t row = (size_t)im.w * 3;
+          if (im.row_stride == (std::ptrdiff_t)row) memcpy(dst + b.off[k], im.data, row * im.h);
+          else for (int y = 0; y < im.h; ++y) memcpy(dst + b.off[k] + (size_t)y * row, im.data + (std::ptrdiff_t)y * im.row_stride, row);
+        }
+        TTR_HIP_CHECK(hipMemcpyAsync(stage_dev[sl].p, dst, b.off.back(), hipMemcpyHostToDevice, up_stream));
+        TTR_HIP_CHECK(hipEventRecord(up_ev[sl], up_stream));
+        return;
+      }
+      const size_t page = (size_t)b.h * b.w * 3, row = (size_t)b.w * 3;
       for (size_t k = 0; k < b.idx.size(); ++k) {
         const HostImage& im = imgs[b.idx[k]];
         if (im.row_stride == (std::ptrdiff_t)row) memcpy(dst + k * page, im.data, page);
@@ -923,7 +1039,14 @@ void Engine::run_images(const std::vector<HostImage>& imgs, std::vector<Result>&
       TTR_HIP_CHECK(hipStreamWaitEvent(stream, up_ev[j % kStageSlots], 0));
       std::vector<Result> prev; int np = 0;
       try {
-        stream_push(stage_dev[j % kStageSlots].as<uint8_t>(), (int)batches[j].idx.size(), batches[j].h, batches[j].w, prev, np);
+        if (mixed) {
+          const Batch& b = batches[j];
+          std::vector<ttr_page> pg(b.idx.size());
+          for (size_t k = 0; k < b.idx.size(); ++k) pg[k] = ttr_page{stage_dev[j % kStageSlots].as<uint8_t>() + b.off[k], imgs[b.idx[k]].h, imgs[b.idx[k]].w, 0};
+          stream_push_v(pg.data(), (int)pg.size(), prev, np);
+        } else {
+          stream_push(stage_dev[j % kStageSlots].as<uint8_t>(), (int)batches[j].idx.size(), batches[j].h, batches[j].w, prev, np);
+        }
         inflight.push_back(j);
         if (np) { deliver(inflight.front(), prev, np); inflight.pop_front(); }
       } catch (const std::exception& ex) {

@@ -157,6 +157,10 @@ void launch_conv1_split(const uint8_t* canvas, const void* wgt_planes, const flo
 // `pages` equally sized pages in one launch: sources src_page bytes apart, canvases H*W*3 bytes apart
 void launch_resize_pad_u8(const uint8_t* src, int sh, int sw, int sstride, uint8_t* dst, int th, int tw, int H, int W, int swap_rb, hipStream_t s,
                           int pages = 1, size_t src_page = 0);
+// the same for `pages` pages of different sizes that share the H x W canvas: page p's source, stride and ResizeGeom come from row p of the device
+// page table (page_table.h); canvas p is byte for byte what launch_resize_pad_u8 gives that page alone
+struct PageRow;
+void launch_resize_pad_pages(const PageRow* table, uint8_t* dst, int H, int W, int swap_rb, int pages, hipStream_t s);
 // canvas u8 [B,H,W,3] -> first-layer im2col matrix T [B*H*W][32] (27 taps*channels, /255, zero padded)
 void launch_im2col_l1(Precision prec, const uint8_t* canvas, void* out, int B, int H, int W, hipStream_t s);
 // bf16 only: conv1_1 + bias + ReLU straight from the u8 canvas (same arithmetic as im2col_l1 + igemm, no [M][32] round trip)
@@ -295,6 +299,10 @@ void launch_pack_crops(const uint8_t* images, size_t page_bytes, int stride, con
 // kind 0 crops are pack_crops_kernel's, kind 1 crops the affine sampler on pages of h x w
 void launch_pack_crops_rect(const uint8_t* images, size_t page_bytes, int stride, int h, int w, const int* rects5, const int64_t* coef8, uint8_t* out,
                             int N, hipStream_t s);
+// the two packers for a mixed-size batch: image, stride, h and w of a crop come from row rects5[5 n + 4] of the device page table (page_table.h);
+// everything else, and every byte of a crop, as above
+void launch_pack_crops_pages(const PageRow* table, const int* rects5, uint8_t* out, int N, hipStream_t s);
+void launch_pack_crops_rect_pages(const PageRow* table, const int* rects5, const int64_t* coef8, uint8_t* out, int N, hipStream_t s);
 // get_detected_boxes' per-component tail on the GPU (tuatara.cpp:162-179: niter, ROI, dilation, findNonZero + minAreaRect): one lane per candidate, geometry.cpp's
 // arithmetic step for step (float32 calipers, double where OpenCV is double) -> CclBuffers::rects.  After launch_ccl on the same stream.
 void launch_ccl_rects(const CclBuffers& b, int pages, int H, int W, hipStream_t s);

@@ -15,6 +15,7 @@
 // component's first pixel = ascending root index (OpenCV's order).
 #include "common.h"
 #include "kernels.h"
+#include "page_table.h"
 #include "resize_dev.h"
 
 namespace ttr {
@@ -487,11 +488,8 @@ void launch_ccl_rects(const CclBuffers& b, int pages, int H, int W, hipStream_t 
 // One workgroup per crop: OpenCV fixed-point bilinear resample of image[y0:y1, x0:x1] to 32x128.
 // The reference swaps channels before cropping (:349) and again after the resize (:441); the
 // resize is per channel, so the net effect is the caller's channel order — no swap here.
-__global__ void pack_crops_kernel(const uint8_t* __restrict__ images, size_t page_bytes, int stride, const int* __restrict__ rects, uint8_t* __restrict__ out) {
-  const int n = blockIdx.x;
-  const int x0 = rects[5 * n], y0 = rects[5 * n + 1], x1 = rects[5 * n + 2], y1 = rects[5 * n + 3];
-  const uint8_t* image = images + (size_t)rects[5 * n + 4] * page_bytes;
-  uint8_t* o = out + (size_t)n * 32 * 128 * 3;
+__device__ __forceinline__ void pack_crop(const uint8_t* __restrict__ image, int stride, const int* __restrict__ rect, uint8_t* __restrict__ o) {
+  const int x0 = rect[0], y0 = rect[1], x1 = rect[2], y1 = rect[3];
   if (x1 <= x0 || y1 <= y0) {
     for (int p = threadIdx.x; p < 32 * 128 * 3; p += blockDim.x) o[p] = 0;
     return;
@@ -505,9 +503,26 @@ __global__ void pack_crops_kernel(const uint8_t* __restrict__ images, size_t pag
   }
 }
 
+__global__ void pack_crops_kernel(const uint8_t* __restrict__ images, size_t page_bytes, int stride, const int* __restrict__ rects, uint8_t* __restrict__ out) {
+  const int n = blockIdx.x;
+  pack_crop(images + (size_t)rects[5 * n + 4] * page_bytes, stride, rects + 5 * n, out + (size_t)n * 32 * 128 * 3);
+}
+
+// mixed-size batches: the crop's page is row rects[5 n + 4] of the page table (workgroup-uniform)
+__global__ void pack_crops_pages_kernel(const PageRow* __restrict__ table, const int* __restrict__ rects, uint8_t* __restrict__ out) {
+  const int n = blockIdx.x;
+  const PageRow& r = table[rects[5 * n + 4]];
+  pack_crop(r.data, r.stride, rects + 5 * n, out + (size_t)n * 32 * 128 * 3);
+}
+
 void launch_pack_crops(const uint8_t* images, size_t page_bytes, int stride, const int* rects5, uint8_t* out, int N, hipStream_t s) {
   if (N <= 0) return;
   hipLaunchKernelGGL(pack_crops_kernel, dim3(N), dim3(256), 0, s, images, page_bytes, stride, rects5, out);
+}
+
+void launch_pack_crops_pages(const PageRow* table, const int* rects5, uint8_t* out, int N, hipStream_t s) {
+  if (N <= 0) return;
+  hipLaunchKernelGGL(pack_crops_pages_kernel, dim3(N), dim3(256), 0, s, table, rects5, out);
 }
 
 // ------------------------------------------------------------------ rectified crop-batch packer (crop_mode = TTR_CROP_RECTIFIED)
@@ -531,17 +546,14 @@ __device__ __forceinline__ void affine_pixel_u8c3(const uint8_t* __restrict__ im
   }
 }
 
-__global__ __launch_bounds__(256) void pack_crops_rect_kernel(const uint8_t* __restrict__ images, size_t page_bytes, int stride, int h, int w,
-                                                              const int* __restrict__ rects, const int64_t* __restrict__ coef, uint8_t* __restrict__ out) {
-  const int n = blockIdx.x;
-  const int x0 = rects[5 * n], y0 = rects[5 * n + 1], x1 = rects[5 * n + 2], y1 = rects[5 * n + 3];
-  const uint8_t* image = images + (size_t)rects[5 * n + 4] * page_bytes;
-  uint32_t* o = reinterpret_cast<uint32_t*>(out + (size_t)n * 32 * 128 * 3);   // 12288 bytes per crop: dword aligned
+__device__ __forceinline__ void pack_crop_rect(const uint8_t* __restrict__ image, int stride, int h, int w, const int* __restrict__ rect,
+                                               const int64_t* __restrict__ cf, uint8_t* __restrict__ out) {
+  const int x0 = rect[0], y0 = rect[1], x1 = rect[2], y1 = rect[3];
+  uint32_t* o = reinterpret_cast<uint32_t*>(out);   // 12288 bytes per crop: dword aligned
   if (x1 <= x0 || y1 <= y0) {
     for (int p = threadIdx.x; p < 32 * 128 * 3 / 4; p += blockDim.x) o[p] = 0;
     return;
   }
-  const int64_t* cf = coef + 8 * n;
   const int kind = (int)cf[0];
   const long long X0 = cf[1], Ax = cf[2], Bx = cf[3], Y0 = cf[4], Ay = cf[5], By = cf[6];
   const ResizeGeom g = make_resize_geom(y1 - y0, x1 - x0, 32, 128);
@@ -563,10 +575,29 @@ __global__ __launch_bounds__(256) void pack_crops_rect_kernel(const uint8_t* __r
   }
 }
 
+__global__ __launch_bounds__(256) void pack_crops_rect_kernel(const uint8_t* __restrict__ images, size_t page_bytes, int stride, int h, int w,
+                                                              const int* __restrict__ rects, const int64_t* __restrict__ coef, uint8_t* __restrict__ out) {
+  const int n = blockIdx.x;
+  pack_crop_rect(images + (size_t)rects[5 * n + 4] * page_bytes, stride, h, w, rects + 5 * n, coef + 8 * n, out + (size_t)n * 32 * 128 * 3);
+}
+
+// mixed-size batches: image, stride, h and w of the crop's page from row rects[5 n + 4] of the page table (workgroup-uniform)
+__global__ __launch_bounds__(256) void pack_crops_rect_pages_kernel(const PageRow* __restrict__ table, const int* __restrict__ rects,
+                                                                    const int64_t* __restrict__ coef, uint8_t* __restrict__ out) {
+  const int n = blockIdx.x;
+  const PageRow& r = table[rects[5 * n + 4]];
+  pack_crop_rect(r.data, r.stride, r.h, r.w, rects + 5 * n, coef + 8 * n, out + (size_t)n * 32 * 128 * 3);
+}
+
 void launch_pack_crops_rect(const uint8_t* images, size_t page_bytes, int stride, int h, int w, const int* rects5, const int64_t* coef8, uint8_t* out,
                             int N, hipStream_t s) {
   if (N <= 0) return;
   hipLaunchKernelGGL(pack_crops_rect_kernel, dim3(N), dim3(256), 0, s, images, page_bytes, stride, h, w, rects5, coef8, out);
+}
+
+void launch_pack_crops_rect_pages(const PageRow* table, const int* rects5, const int64_t* coef8, uint8_t* out, int N, hipStream_t s) {
+  if (N <= 0) return;
+  hipLaunchKernelGGL(pack_crops_rect_pages_kernel, dim3(N), dim3(256), 0, s, table, rects5, coef8, out);
 }
 
 }  // namespace ttr

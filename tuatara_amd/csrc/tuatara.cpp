@@ -14,8 +14,10 @@ std::map<std::string, ttr_engine*> g_engines;  // one engine per (weights_dir, p
 
 // crop_mode < 0: the process default (TUATARA_CROP_MODE, else TTR_CROP_BOUNDING); orient < 0: the process default (TUATARA_ORIENT=flip|quarter, else off);
 // lines < 0: the process default (TUATARA_LINES=1, else off); chars < 0: the process default (TUATARA_CHARS=1, else off); blocks < 0: the process
-// default (TUATARA_BLOCKS=1, else off).  Blocks are made of lines: with blocks on, lines are on
-ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int orient = -1, int orient_page = 0, int lines = -1, int chars = -1, int blocks = -1) {
+// default (TUATARA_BLOCKS=1, else off).  Blocks are made of lines: with blocks on, lines are on.  mixed < 0: the process default
+// (TUATARA_MIXED_BATCHES=1, else off)
+ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int orient = -1, int orient_page = 0, int lines = -1, int chars = -1, int blocks = -1,
+                       int mixed = -1) {
   std::lock_guard<std::mutex> lk(g_mu);
   ttr_config cfg;
   ttr_config_default(&cfg);
@@ -34,6 +36,8 @@ ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int o
   if (const char* p = std::getenv("TUATARA_BLOCKS")) cfg.blocks = std::string(p) == "1" ? 1 : 0;
   if (blocks >= 0) cfg.blocks = blocks;
   if (cfg.blocks) cfg.lines = 1;
+  if (const char* p = std::getenv("TUATARA_MIXED_BATCHES")) cfg.mixed_batches = std::string(p) == "1" ? 1 : 0;
+  if (mixed >= 0) cfg.mixed_batches = mixed;
   if (const char* p = std::getenv("TUATARA_PRECISION")) {   // default: TTR_PREC_F16X4 (fp32-equivalent, the reference computes in fp32)
     const std::string v(p);
     cfg.precision = v == "f32" ? TTR_PREC_F32 : v == "bf16" ? TTR_PREC_BF16 : TTR_PREC_F16X4;
@@ -42,7 +46,7 @@ ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int o
   if (const char* p = std::getenv("TUATARA_DEVICE")) cfg.device = std::atoi(p);
   std::string key = weights_dir + "#" + std::to_string(cfg.precision) + "#" + std::to_string(cfg.device) + "#" + std::to_string(cfg.crop_mode) + "#" +
                     std::to_string(cfg.orient) + "#" + std::to_string(cfg.orient_page) + "#" + std::to_string(cfg.lines) + "#" + std::to_string(cfg.chars) + "#" +
-                    std::to_string(cfg.blocks);
+                    std::to_string(cfg.blocks) + "#" + std::to_string(cfg.mixed_batches);
   auto it = g_engines.find(key);
   if (it != g_engines.end()) return it->second;
   ttr_engine* e = ttr_create(weights_dir.c_str(), &cfg);
@@ -88,10 +92,10 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
 
 // the checks in front of both calls, then the cached engine; null once the reference's message is printed
 ttr_engine* open_engine(const std::string& weights_dir, const std::string& outputs_dir, int crop_mode, int orient, int orient_page, int lines, int chars,
-                        int blocks) {
+                        int blocks, int mixed = -1) {
   if (weights_dir.empty()) { std::cerr << "Please provide a value for weights_dir" << std::endl; return nullptr; }   // tuatara.cpp:315-318
   if (outputs_dir.empty()) { std::cerr << "Please provide a value for outputs_dir" << std::endl; return nullptr; }   // tuatara.cpp:320-323 (never used afterwards, there or here)
-  ttr_engine* e = engine_for(weights_dir, crop_mode, orient, orient_page, lines, chars, blocks);
+  ttr_engine* e = engine_for(weights_dir, crop_mode, orient, orient_page, lines, chars, blocks, mixed);
   if (!e) std::cerr << "error loading craft/parseq model: " << ttr_last_error() << std::endl;                       // tuatara.cpp:337-340, :429-432
   return e;
 }
@@ -120,8 +124,8 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
 template <class Item>
 std::vector<std::vector<Item>> run_many(const std::vector<ImageView>& images, const std::string& weights_dir, const std::string& outputs_dir, int crop_mode,
                                         int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
-                                        int blocks = -1) {
-  ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks);
+                                        int blocks = -1, int mixed = -1) {
+  ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks, mixed);
   if (!e) return {};
   const int n = (int)images.size();
   std::vector<const uint8_t*> ptr(n);
@@ -208,4 +212,10 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
                                                          bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks) {
   return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
                                 blocks ? 1 : -1);
+}
+
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches) {
+  return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
+                                blocks ? 1 : -1, mixed_batches ? 1 : -1);
 }

@@ -26,7 +26,13 @@ class Config(C.Structure):
     _fields_ = [("precision", C.c_int), ("device", C.c_int), ("canvas_size", C.c_int), ("mag_ratio", C.c_float),
                 ("text_threshold", C.c_float), ("link_threshold", C.c_float), ("low_text", C.c_float), ("min_area", C.c_int),
                 ("strict_crops", C.c_int), ("max_components", C.c_int), ("verbose", C.c_int), ("crop_mode", C.c_int),
-                ("orient", C.c_int), ("orient_page", C.c_int), ("lines", C.c_int), ("chars", C.c_int), ("blocks", C.c_int)]
+                ("orient", C.c_int), ("orient_page", C.c_int), ("lines", C.c_int), ("chars", C.c_int), ("blocks", C.c_int),
+                ("mixed_batches", C.c_int)]
+
+
+class Page(C.Structure):
+    """ttr_page: one page in device memory, u8 HWC 3 channels; row_stride in bytes, 0 = 3 * w"""
+    _fields_ = [("data", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("row_stride", C.c_int)]
 
 
 # every symbol include/tuatara_hip.h declares: (name, restype, argtypes)
@@ -43,6 +49,13 @@ SYMBOLS = [
     ("ttr_stream_push", _I, [_VP, _VP, _I, _I, _I, C.POINTER(_VP), C.POINTER(C.c_int)]),
     ("ttr_stream_flush", _I, [_VP, C.POINTER(_VP), C.POINTER(C.c_int)]),
     ("ttr_images_to_data", _I, [_VP, C.POINTER(_VP), _PI, _PI, _PI, _I, C.POINTER(_VP)]),
+    ("ttr_canvas_geometry", _I, [_VP, _I, _I, _PI, _PI, _PF]),
+    ("ttr_pages_to_data_dev_v", _I, [_VP, C.POINTER(Page), _I, C.POINTER(_VP)]),
+    ("ttr_stream_push_v", _I, [_VP, C.POINTER(Page), _I, C.POINTER(_VP), C.POINTER(C.c_int)]),
+    ("ttr_last_images_batches", _I, [_VP, _PI, _I]),
+    ("ttr_resize_canvas_batch", _I, [_VP, C.POINTER(_VP), _PI, _PI, _PI, _I, _PU8, C.c_size_t, _PI, _PI, _PF]),
+    ("ttr_pack_crops_batch", _I, [_VP, C.POINTER(_VP), _PI, _PI, _PI, _I, _PF, _PI, _I, _I, _I, _PU8, _PF]),
+    ("ttr_dbg_canvas_geometry", _I, [_I, _I, _I, _F, _PI, _PI, _PF, _PI, _PI]),
     ("ttr_result_count", _I, [_VP]),
     ("ttr_result_text", C.c_char_p, [_VP, _I]),
     ("ttr_result_bbox", _PF, [_VP, _I]),
@@ -257,6 +270,33 @@ def orient_quad(rect5, h: int, w: int, crop_mode: int, turn: int):
     if load().ttr_dbg_orient_quad(_f(r), int(h), int(w), int(crop_mode), int(turn), _f(quad), fixed.ctypes.data_as(C.POINTER(C.c_int64))) != 0:
         raise EngineError(load().ttr_last_error().decode())
     return quad.reshape(4, 2), fixed
+
+
+def canvas_geometry(h: int, w: int, canvas_size: int = 1024, mag_ratio: float = 1.0):
+    """The detector canvas of an h x w page on the host (ttr_dbg_canvas_geometry, no GPU; DESIGN.md "Mixed-size batches") ->
+    (H, W, ratio, target_h, target_w): the page scaled by ratio to target_h x target_w, each side rounded up to a multiple of 32."""
+    H, W, th, tw, ratio = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_float()
+    if load().ttr_dbg_canvas_geometry(int(h), int(w), int(canvas_size), float(mag_ratio), C.byref(H), C.byref(W), C.byref(ratio), C.byref(th), C.byref(tw)) != 0:
+        raise EngineError("ttr_dbg_canvas_geometry: h and w must be positive")
+    return H.value, W.value, ratio.value, th.value, tw.value
+
+
+def _host_images(images):
+    """a list of host images [h, w, 3] u8 (C-contiguous rows: a view into a wider array keeps its row stride) -> ctypes pointer, h, w, stride arrays + keep-alives"""
+    keep = []
+    for im in images:
+        a = np.asarray(im)
+        if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+            raise EngineError("Input array should have 3 dimensions")
+        if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
+            a = np.ascontiguousarray(a)
+        keep.append(a)
+    n = len(keep)
+    ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in keep])
+    hs = (C.c_int32 * n)(*[a.shape[0] for a in keep])
+    ws = (C.c_int32 * n)(*[a.shape[1] for a in keep])
+    st = (C.c_int32 * n)(*[a.strides[0] for a in keep])
+    return ptrs, hs, ws, st, keep
 
 
 def confidence_from_probs(ids, probs):
@@ -704,7 +744,8 @@ class Engine:
         return list(self._take_many(arr, 1, conf)[0])
 
     def images_to_data(self, images, keep: bool = True, conf: bool = False):
-        """image_to_data over a list of host images [H, W, 3] u8 of any sizes (ttr_images_to_data): one result list per image, input order."""
+        """image_to_data over a list of host images [H, W, 3] u8 of any sizes (ttr_images_to_data): one result list per image, input order.
+        Engine(..., mixed_batches=True) batches images that share one detector canvas instead of one size (DESIGN.md "Mixed-size batches")."""
         arrs = []
         for im in images:
             a = np.asarray(im)
@@ -748,6 +789,74 @@ class Engine:
         n_prev = C.c_int(0)
         self._check(self.lib.ttr_stream_flush(self.h, arr, C.byref(n_prev)))
         return self._results(arr, n_prev.value, keep, conf)
+
+    def canvas_geometry(self, h: int, w: int):
+        """ttr_canvas_geometry: the detector canvas this engine gives an h x w page -> (H, W, ratio).  Pages with equal (H, W) can share a batch."""
+        H, W, ratio = C.c_int32(), C.c_int32(), C.c_float()
+        self._check(self.lib.ttr_canvas_geometry(self.h, int(h), int(w), C.byref(H), C.byref(W), C.byref(ratio)))
+        return H.value, W.value, ratio.value
+
+    @staticmethod
+    def _page_array(pages):
+        """a list of (ptr | DeviceBuffer, h, w[, row_stride]) -> ttr_page array"""
+        arr = (Page * max(len(pages), 1))()
+        for i, p in enumerate(pages):
+            d = p[0].ptr if isinstance(p[0], DeviceBuffer) else p[0]
+            arr[i] = Page(d, int(p[1]), int(p[2]), int(p[3]) if len(p) > 3 else 0)
+        return arr
+
+    def pages_to_data_dev_v(self, pages, keep: bool = True, conf: bool = False):
+        """ttr_pages_to_data_dev_v: a batch of device-resident pages of different sizes and row strides that share one canvas (DESIGN.md "Mixed-size
+        batches"); pages: a list of (ptr | DeviceBuffer, h, w, row_stride), row_stride in bytes (0 or absent = 3 * w)."""
+        n = len(pages)
+        arr = (C.c_void_p * max(n, 1))()
+        self._check(self.lib.ttr_pages_to_data_dev_v(self.h, self._page_array(pages), n, arr))
+        return self._results(arr, n, keep, conf)
+
+    def stream_push_v(self, pages, keep: bool = True, max_batch: int = 0, conf: bool = False):
+        """ttr_stream_push_v: stream_push for such a batch; mixes freely with stream_push, the same stream_flush returns both kinds."""
+        n = len(pages)
+        self._max_pushed = max(getattr(self, "_max_pushed", 1), n, max_batch)
+        arr = (C.c_void_p * self._max_pushed)()
+        n_prev = C.c_int(0)
+        self._check(self.lib.ttr_stream_push_v(self.h, self._page_array(pages), n, arr, C.byref(n_prev)))
+        return self._results(arr, n_prev.value, keep, conf)
+
+    def last_images_batches(self) -> List[int]:
+        """ttr_last_images_batches: the pages per batch of the last images_to_data call, in run order."""
+        n = self.lib.ttr_last_images_batches(self.h, None, 0)
+        if n < 0:
+            self._check(n)
+        out = np.zeros(max(n, 1), np.int32)
+        self.lib.ttr_last_images_batches(self.h, _i(out), n)
+        return out[:n].tolist()
+
+    def resize_canvas_batch(self, images):
+        """ttr_resize_canvas_batch: host images of different sizes that share one canvas through ONE launch of resize_pad_pages_kernel ->
+        (canvases u8 [n, H, W, 3], ratios f32 [n]).  A view into a wider array keeps its row stride on the device."""
+        ptrs, hs, ws, st, keep = _host_images(images)
+        n = len(keep)
+        H, W, _ = self.canvas_geometry(keep[0].shape[0], keep[0].shape[1])
+        buf = np.zeros((n, H, W, 3), np.uint8)
+        ratios = np.zeros(n, np.float32)
+        Ho, Wo = C.c_int32(), C.c_int32()
+        self._check(self.lib.ttr_resize_canvas_batch(self.h, ptrs, hs, ws, st, n, _u8(buf), buf.nbytes, C.byref(Ho), C.byref(Wo), _f(ratios)))
+        assert (Ho.value, Wo.value) == (H, W)
+        return buf, ratios
+
+    def pack_crops_batch(self, images, rects, page_of, crop_mode: int, turn: int):
+        """ttr_pack_crops_batch: heat-map rects f32 [n, 5], rect i on page page_of[i] of `images` (different sizes, one canvas), through ONE launch of the
+        table packer -> (crops u8 [n, 32, 128, 3], turned quads f32 [n, 4, 2]).  Crop i is pack_crops_oriented's on its page alone."""
+        ptrs, hs, ws, st, keep = _host_images(images)
+        rects = np.ascontiguousarray(rects, dtype=np.float32).reshape(-1, 5)
+        page_of = np.ascontiguousarray(page_of, dtype=np.int32).reshape(-1)
+        n = len(rects)
+        if len(page_of) != n:
+            raise ValueError("page_of must hold one entry per rect")
+        crops = np.zeros((n, 32, 128, 3), np.uint8)
+        quads = np.zeros((n, 4, 2), np.float32)
+        self._check(self.lib.ttr_pack_crops_batch(self.h, ptrs, hs, ws, st, len(keep), _f(rects), _i(page_of), n, int(crop_mode), int(turn), _u8(crops), _f(quads)))
+        return crops, quads
 
     def last_stage_ms(self):
         ms = (C.c_float * 4)()
