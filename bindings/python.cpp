@@ -12,6 +12,9 @@
 // {"char", "quad", "bbox"} with one entry per character of "text" (DESIGN.md "Character boxes").  And a keyword-only blocks=False: blocks=True
 // groups each page's text lines into blocks in reading order, a column read to its end before the next (DESIGN.md "Text blocks"); it turns lines
 // on, and every dict gains "block" beside "line" and "word".  With all of them off every dict is the reference's {text, bbox}.
+// And keyword-only allowlist=None, blocklist=None: the characters the recogniser may / may not emit (DESIGN.md "Character sets"), set on the cached
+// engine for the call and reset afterwards, also when the call raises.  A character the recogniser has no class for ('~', a blank, non-ASCII) or a
+// set that leaves nothing raises ValueError, naming the character, before anything runs.  The dicts' keys do not change.
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -22,6 +25,7 @@
 #include <stdexcept>
 
 #include "../include/tuatara.h"
+#include "../include/tuatara_hip.h"
 
 namespace py = pybind11;
 
@@ -71,10 +75,21 @@ static int orient_mode(const py::object& orient) {
   throw std::invalid_argument("orient must be None, \"flip\" or \"quarter\"");
 }
 
+// allowlist / blocklist = None | str -> the string ("" = not given); a bad list raises ValueError with the engine's message (ttr_charset_mask: host only)
+static void charset_args(const py::object& allow_kw, const py::object& deny_kw, std::string& allow, std::string& deny) {
+  allow = allow_kw.is_none() ? std::string() : allow_kw.cast<std::string>();
+  deny = deny_kw.is_none() ? std::string() : deny_kw.cast<std::string>();
+  uint32_t mask[3];
+  if ((!allow.empty() || !deny.empty()) && ttr_charset_mask(allow.c_str(), deny.c_str(), mask) < 0) throw std::invalid_argument(ttr_last_error());
+}
+
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
-                                      bool blocks) {
+                                      bool blocks, py::object allowlist, py::object blocklist) {
   const int orient = orient_mode(orient_kw);
+  std::string allow, deny;
+  charset_args(allowlist, blocklist, allow, deny);
+  const bool cset = !allow.empty() || !deny.empty();
   lines = lines || blocks;   // blocks are made of lines
   py::buffer_info buf = image.request();
   if (buf.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
@@ -84,7 +99,8 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   std::vector<OutputItemEx> items;
   {
     py::gil_scoped_release nogil;   // (orient = None: the 7-argument call, which leaves the orientation to TUATARA_ORIENT)
-    items = blocks   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
+    items = cset     ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny)
+            : blocks ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
             : chars  ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, true)
             : lines  ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true)
             : orient ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
@@ -100,8 +116,11 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
 // on one cached engine: same-sized images travel as batches, the host-to-device copies run beside the GPU's work, the GIL is released meanwhile.
 // Keyword-only mixed_batches=False: True batches images that share one detector canvas, whatever their sizes (DESIGN.md "Mixed-size batches"); same results.
 static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf, py::object orient_kw,
-                                       bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches) {
+                                       bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches, py::object allowlist, py::object blocklist) {
   const int orient = orient_mode(orient_kw);
+  std::string allow, deny;
+  charset_args(allowlist, blocklist, allow, deny);
+  const bool cset = !allow.empty() || !deny.empty();
   lines = lines || blocks;   // blocks are made of lines
   std::vector<py::array_t<unsigned char, py::array::c_style | py::array::forcecast>> keep;   // contiguous uint8 views / copies, alive for the call
   std::vector<ImageView> views;
@@ -117,7 +136,8 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   std::vector<std::vector<OutputItemEx>> pages;
   {
     py::gil_scoped_release nogil;
-    pages = mixed_batches ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, true)
+    pages = cset ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny)
+            : mixed_batches ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, true)
             : blocks ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
             : chars  ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, true)
             : lines  ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true)
@@ -137,8 +157,8 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
 }

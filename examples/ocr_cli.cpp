@@ -14,10 +14,13 @@
 // character, "c x1 y1 x2 y2" with the character's bbox as integers, the words in item order.
 //   ocr_cli --blocks <image.png> <weights_dir> <outputs_dir>    groups the text lines into blocks (DESIGN.md "Text blocks") and prints the page's text block
 // after block in reading order - a column to its end before the next -, one line of the page per output line and an empty line between blocks.
+//   ocr_cli --allowlist S --blocklist S ...                      in front of any form above: the characters the recogniser may / may not emit (DESIGN.md
+// "Character sets"), e.g. --allowlist 0123456789 for a field of digits.  They reach the call as TUATARA_ALLOWLIST / TUATARA_BLOCKLIST.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <iostream>
 
 #include "../include/tuatara.h"
@@ -25,6 +28,10 @@
 
 int main(int argc, const char** argv) {
   try {
+    while (argc >= 3 && (std::string(argv[1]) == "--allowlist" || std::string(argv[1]) == "--blocklist")) {   // leading options, any order
+      setenv(std::string(argv[1]) == "--allowlist" ? "TUATARA_ALLOWLIST" : "TUATARA_BLOCKLIST", argv[2], 1);
+      argv[2] = argv[0]; argv += 2; argc -= 2;
+    }
     if (argc == 4 && std::string(argv[1]) == "--decode-only") {
       pngdec::Image img = pngdec::read(argv[2]);
       FILE* f = fopen(argv[3], "wb");
@@ -96,7 +103,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--rectify | --conf | --orient | --lines | --chars | --blocks] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--rectify | --conf | --orient | --lines | --chars | --blocks] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

@@ -95,6 +95,19 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
 // images_to_data and every images_to_data_ex.  The other arguments as above.
 std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
                                                          bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches);
+// Character sets (opt-in; DESIGN.md "Character sets"): allowlist = the characters the recogniser may emit ("" = all), blocklist = characters it may
+// not ("" = none) - "this field holds digits", "never emit |".  The set acts where each character is chosen, so the rest of the word is read in its
+// light, and conf / char_conf are probabilities over the allowed characters.  It is set on the cached engine for the call and reset afterwards.  A
+// character the recogniser has no class for ('~', a blank, non-ASCII bytes), a set that leaves nothing, or a bf16 engine (TUATARA_PRECISION=bf16) with
+// a restricting set: the message is printed and the result is empty.  Two empty strings are the calls above, unless TUATARA_ALLOWLIST /
+// TUATARA_BLOCKLIST are set in the environment, which then apply to image_to_data / images_to_data / every call above; a non-empty argument
+// takes precedence over its variable.  The other arguments as above.
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

@@ -383,6 +383,23 @@ int ttr_parseq_logits(ttr_engine* e, const uint8_t* crops, int n, float* logits,
 /* The recogniser's final decode on host logits f32 [n][26][95] (uploaded, decode_conf_kernel, downloaded): ids [n][26] as the engine forms
  * them, probs [n][26] and conf [n] as ttr_result_prob / ttr_result_conf give them.  Any output may be NULL. */
 int ttr_logits_confidence(ttr_engine* e, const float* logits, int n, int32_t* ids, float* probs, float* conf);
+/* Character sets (DESIGN.md "Character sets"): restrict what the recogniser may emit - "this field holds digits", "never emit |" - where each token is
+ * chosen (the AR steps' argmax, the refinement pass's inputs, the final decode), not on the finished strings.
+ * The class mask has 95 bits, one per logit class: class c is bit c & 31 of mask[c >> 5].  Bit 0 (the end of the text) is always set; for 1 <= i <= 94 bit
+ * i is set iff the engine's tokenizer table has at i a character that occurs in allow (NULL or "": every character) and not in deny (NULL or "": none).
+ * The table reproduces the reference's quirks: a backslash sets ids 69 and 87; ']' sets id 88, which decodes to nothing; '~', a blank and any non-ASCII
+ * byte name no class - a list that holds one fails, and the message names the character.  A set that leaves only the end of the text fails too.
+ * ttr_charset_mask: the rule on the host, no engine needed; returns the number of character classes set (1..94), or -1 (ttr_last_error).
+ * ttr_engine_set_charset: the engine's set, one at a time, honoured by ttr_parseq_logits and every page entry point (ids, text, prob and conf are those
+ * of the constrained choice: prob = 1 / sum over the allowed classes; the logits themselves are never altered).  NULL, NULL resets it; all 95 bits set is
+ * "off": the kernels, launches and bits of an engine that never had a set.  It fails, and leaves the previous set in place, while streamed batches are in
+ * flight, on a bad list, and - a restricting set only - on a bf16 engine (f16x4 and f32 engines take sets).
+ * ttr_engine_get_charset: the mask in force (all 95 bits when none).
+ * ttr_logits_confidence_masked: ttr_logits_confidence under a mask of the caller's (bit 0 must be set); the engine's own set is not consulted. */
+int ttr_charset_mask(const char* allow, const char* deny, uint32_t mask[3]);
+int ttr_engine_set_charset(ttr_engine* e, const char* allow, const char* deny);
+int ttr_engine_get_charset(const ttr_engine* e, uint32_t mask[3]);
+int ttr_logits_confidence_masked(ttr_engine* e, const float* logits, int n, const uint32_t mask[3], int32_t* ids, float* probs, float* conf);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

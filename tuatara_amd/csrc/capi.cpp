@@ -801,6 +801,62 @@ int ttr_logits_confidence(ttr_engine* e, const float* logits, int n, int32_t* id
   TTR_GUARD_END(-1)
 }
 
+int ttr_logits_confidence_masked(ttr_engine* e, const float* logits, int n, const uint32_t mask[3], int32_t* ids, float* probs, float* conf) {
+  TTR_GUARD_BEGIN
+  if (!e || !mask || n < 0 || (n > 0 && !logits)) throw std::runtime_error("null argument");
+  if (!(mask[0] & 1u)) throw std::runtime_error("ttr_logits_confidence_masked: bit 0 (the end of the text) must be set");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_logits_confidence_masked");
+  if (n == 0) return 0;
+  ClassMask cm{};
+  for (int i = 0; i < 3; ++i) cm.blocked[i] = ~mask[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);   // 95 classes
+  E.logits.ensure((size_t)n * 26 * 95 * 4);
+  const Engine::RecOut o = E.rec_out(n);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, cm);
+  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, o.ids, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (probs) TTR_HIP_CHECK(hipMemcpyAsync(probs, o.prob, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (conf) TTR_HIP_CHECK(hipMemcpyAsync(conf, o.conf, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_charset_mask(const char* allow, const char* deny, uint32_t mask[3]) {
+  TTR_GUARD_BEGIN
+  if (!mask) throw std::runtime_error("null argument");
+  static const Tokenizer tok;
+  return charset_mask(tok, allow, deny, mask);
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_set_charset(ttr_engine* e, const char* allow, const char* deny) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_engine_set_charset");
+  uint32_t m[3];
+  charset_mask(E.tok, allow, deny, m);            // (throws before anything changes: a failed call leaves the previous set in place)
+  ClassMask cm{};
+  for (int i = 0; i < 3; ++i) cm.blocked[i] = ~m[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);
+  if (cm.restricts() && E.prec == kBF16)
+    throw std::runtime_error("ttr_engine_set_charset: a character set needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which take no class mask");
+  E.charset = cm;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_get_charset(const ttr_engine* e, uint32_t mask[3]) {
+  TTR_GUARD_BEGIN
+  if (!e || !mask) throw std::runtime_error("null argument");
+  const Engine& E = *e->e;
+  for (int i = 0; i < 3; ++i) mask[i] = ~E.charset.blocked[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_confidence_from_probs(const int32_t* ids, const float* probs, int n_pos, float* char_conf, int* n_chars, float* conf) {
   if (!ids || !probs || n_pos < 0) return -1;
   const int k = confidence_from_probs(ids, probs, n_pos, char_conf, conf);

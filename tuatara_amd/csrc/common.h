@@ -15,6 +15,15 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 enum Precision { kBF16 = 0, kF32 = 1, kSplit = 2 };   // kSplit: fp32 tensors, matrix products as four f16 MFMAs (split.h)
 enum Act { kActNone = 0, kActRelu = 1, kActGelu = 2 };
 
+// The recogniser's class mask (DESIGN.md "Character sets"): which of PARSeq's 95 logit classes may be chosen where a token is chosen.  It travels by
+// value (a kernel argument, or ConvParams::tok_mask) and is held as its COMPLEMENT - bit c & 31 of blocked[c >> 5] set = class c takes no part - so that
+// a zero-initialised mask (ConvParams p{}) restricts nothing.  Classes from 96 on are never blocked.
+struct ClassMask {
+  uint32_t blocked[3];
+  __host__ __device__ __forceinline__ bool allows(int c) const { return (unsigned)c >= 96u || !((blocked[c >> 5] >> (c & 31)) & 1u); }
+  __host__ __device__ __forceinline__ bool restricts() const { return (blocked[0] | blocked[1] | blocked[2]) != 0u; }
+};
+
 // Implicit-GEMM convolution / linear layer.  Activations are NHWC, weights are
 // [Cout][taps][Cin] (K contiguous), so both MFMA operands are read K-major.
 struct ConvParams {
@@ -44,6 +53,7 @@ struct ConvParams {
   // tok[m * tok_ld + tok_col], or, when tok_logits is given, the first maximal index of the f32 row tok_logits[m * tok_logits_ld ..+ tok_C),
   // which column-tile 0 also writes to tok[m * tok_ld + tok_col] (argmax + dec_embed_ln folded into the self_kv GEMM)
   int* tok; int tok_ld, tok_col; const float* tok_logits; int tok_logits_ld, tok_C; const float* tok_emb; const float* tok_pos; int tok_max;
+  ClassMask tok_mask;        // gemm_skx.hip's token prologue: classes that take no part in the argmax of tok_logits (zero = every class does)
   unsigned long long* dbg;   // gemm_ws diagnostics: shader-clock stamps of workgroup 0 (null = off)
   int store_policy;          // set by the launchers: 0 default, 1 nt, 2 sc0 sc1 nt on the big streaming output stores
   int dbg_flags;             // gemm_ws diagnostics (timing experiments only, results are wrong): 1 = no output stores, 2 = no activation loads

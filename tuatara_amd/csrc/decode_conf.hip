@@ -4,6 +4,7 @@
 //   ids  [N][26]   first maximal index of each row - the comparison and the wave reduction of argmax_kernel (parseq_ops.hip), so the ids
 //                  are bit-identical to it
 //   prob [N][26]   1 / sum_c expf(x[c] - x[id]) in fp32 (full-precision expf)
+//   cm             the class mask (DESIGN.md "Character sets"): the maximum and the sum run over the allowed classes only; none blocked = the bits of before
 //   conf [N]       fp32 product, in position order from 1.0f, of prob over the characters of the text (positions before the first EOS,
 //                  id 0, whose id is not 88 and lies in [0, 98): Tokenizer::filter + decode), times prob[EOS] when there is one
 //
@@ -21,11 +22,12 @@ constexpr int kPos = 26, kCls = 95, kCrops = 4;   // positions, classes, crops (
 }
 
 __global__ void __launch_bounds__(256) decode_conf_kernel(const float* __restrict__ logits, int N, int* __restrict__ ids, float* __restrict__ prob,
-                                                          float* __restrict__ conf) {
+                                                          float* __restrict__ conf, ClassMask cm) {
   const int n = blockIdx.x * kCrops + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (n >= N) return;
   const float* x = logits + (int64_t)n * kPos * kCls;
   const bool hi = lane + 64 < kCls;
+  const bool a0 = cm.allows(lane), a1 = hi && cm.allows(lane + 64);   // a blocked class: -inf in the comparison, exactly 0 in the sum (same lanes, same butterflies)
   float v0[kPos], v1[kPos];
 #pragma unroll
   for (int p = 0; p < kPos; ++p) {
@@ -39,14 +41,14 @@ __global__ void __launch_bounds__(256) decode_conf_kernel(const float* __restric
 #pragma unroll
   for (int p = 0; p < kPos; ++p) {
     float best = -INFINITY; int bi = 0x7fffffff;                 // argmax_kernel's per-lane loop: c = lane, then c = lane + 64
-    if (v0[p] > best) { best = v0[p]; bi = lane; }
-    if (hi && v1[p] > best) { best = v1[p]; bi = lane + 64; }
+    if (a0 && v0[p] > best) { best = v0[p]; bi = lane; }
+    if (a1 && v1[p] > best) { best = v1[p]; bi = lane + 64; }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o);
       if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
     }
-    float s = expf(v0[p] - best) + (hi ? expf(v1[p] - best) : 0.f);
+    float s = (a0 ? expf(v0[p] - best) : 0.f) + (a1 ? expf(v1[p] - best) : 0.f);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     const float pr = 1.f / s;
@@ -63,9 +65,9 @@ __global__ void __launch_bounds__(256) decode_conf_kernel(const float* __restric
   if (lane == 0) conf[n] = cf;
 }
 
-void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s) {
+void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s, ClassMask cm) {
   if (N <= 0) return;
-  hipLaunchKernelGGL(decode_conf_kernel, dim3((N + kCrops - 1) / kCrops), dim3(256), 0, s, logits, N, ids, prob, conf);
+  hipLaunchKernelGGL(decode_conf_kernel, dim3((N + kCrops - 1) / kCrops), dim3(256), 0, s, logits, N, ids, prob, conf, cm);
 }
 
 }  // namespace ttr

@@ -395,6 +395,7 @@ struct Engine {
   std::vector<hipEvent_t> group_ev;               // per page group: component counters are on the host
   std::mutex mu;
   Tokenizer tok;
+  ClassMask charset{};                            // classes the recogniser may not choose (ttr_engine_set_charset; DESIGN.md "Character sets"); zero = no set
 
   // CRAFT
   std::map<std::string, Linear> craft;

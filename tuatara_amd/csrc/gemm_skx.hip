@@ -135,6 +135,7 @@ __global__ __launch_bounds__(256) void gemm_skx_kernel(ConvParams p) {
         float best[4]; int bi[4];
         if (p.tok_C <= 128) {                                                // (PARSeq: 95 classes) two values per lane, the four rows' loads in flight together
           float t0[4], t1[4];
+          const bool ok0 = lane < p.tok_C && p.tok_mask.allows(lane), ok1 = lane + 64 < p.tok_C && p.tok_mask.allows(lane + 64);   // (a blocked class takes no part)
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {
             const float* lg = p.tok_logits + (int64_t)(live[rr] ? mrow[rr] : m0) * p.tok_logits_ld;
@@ -144,15 +145,15 @@ __global__ __launch_bounds__(256) void gemm_skx_kernel(ConvParams p) {
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {                                   // (the loop's order: cc = lane, then lane + 64; strict > keeps the first maximum)
             best[rr] = -INFINITY; bi[rr] = 0x7fffffff;
-            if (lane < p.tok_C && t0[rr] > best[rr]) { best[rr] = t0[rr]; bi[rr] = lane; }
-            if (lane + 64 < p.tok_C && t1[rr] > best[rr]) { best[rr] = t1[rr]; bi[rr] = lane + 64; }
+            if (ok0 && t0[rr] > best[rr]) { best[rr] = t0[rr]; bi[rr] = lane; }
+            if (ok1 && t1[rr] > best[rr]) { best[rr] = t1[rr]; bi[rr] = lane + 64; }
           }
         } else {
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {
             const float* lg = p.tok_logits + (int64_t)(live[rr] ? mrow[rr] : m0) * p.tok_logits_ld;
             best[rr] = -INFINITY; bi[rr] = 0x7fffffff;
-            for (int cc = lane; cc < p.tok_C; cc += 64) { const float t = lg[cc]; if (t > best[rr]) { best[rr] = t; bi[rr] = cc; } }
+            for (int cc = lane; cc < p.tok_C; cc += 64) { const float t = lg[cc]; if (p.tok_mask.allows(cc) && t > best[rr]) { best[rr] = t; bi[rr] = cc; } }
           }
         }
 #pragma unroll

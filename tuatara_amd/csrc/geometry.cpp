@@ -8,6 +8,8 @@
 #include <cmath>
 #include <cfloat>
 #include <map>
+#include <stdexcept>
+#include <cstdio>
 
 namespace ttr {
 
@@ -699,6 +701,34 @@ std::string Tokenizer::decode(const int* ids, int n) const {
     s.push_back(ch);
   }
   return s;
+}
+
+int charset_mask(const Tokenizer& tok, const char* allow, const char* deny, uint32_t mask[3]) {
+  constexpr int kClasses = 95;
+  auto quote = [](unsigned char ch) {           // ASCII as itself, anything else as \xNN
+    char b[16];
+    if (ch >= 0x20 && ch < 0x7f) snprintf(b, sizeof b, "'%c'", ch); else snprintf(b, sizeof b, "'\\x%02x'", ch);
+    return std::string(b);
+  };
+  auto classes_of = [&](const char* set, const char* which, bool in[kClasses]) {
+    for (int i = 0; i < kClasses; ++i) in[i] = false;
+    for (const char* q = set; *q; ++q) {
+      bool any = false;
+      for (int i = 1; i < kClasses; ++i) if (tok.itos[i] == *q) { in[i] = true; any = true; }
+      if (!any) throw std::runtime_error(std::string("charset: ") + which + " holds " + quote((unsigned char)*q) + ", which names no recogniser class");
+    }
+  };
+  const bool has_allow = allow && *allow, has_deny = deny && *deny;
+  bool a[kClasses], d[kClasses];
+  if (has_allow) classes_of(allow, "allow", a);
+  if (has_deny) classes_of(deny, "deny", d);
+  uint32_t m[3] = {1u, 0u, 0u};                  // EOS
+  int n = 0;
+  for (int i = 1; i < kClasses; ++i)
+    if ((!has_allow || a[i]) && !(has_deny && d[i])) { m[i >> 5] |= 1u << (i & 31); ++n; }
+  if (n == 0) throw std::runtime_error("charset: deny removes every character of allow: only the end of the text would be left");
+  for (int i = 0; i < 3; ++i) mask[i] = m[i];
+  return n;
 }
 
 int confidence_from_probs(const int* ids, const float* probs, int n, float* char_conf, float* conf) {

@@ -110,6 +110,12 @@ struct Tokenizer {
   std::string decode(const int* ids, int n) const;
 };
 
+// The class mask of a character set (DESIGN.md "Character sets"): bit c & 31 of mask[c >> 5] = logit class c may be chosen.  Bit 0 (EOS) is always set; for
+// 1 <= i <= 94 bit i is set iff Tokenizer::itos[i] occurs in allow (null or empty: every character) and not in deny (null or empty: none).  Through the
+// table's quirks: a backslash sets ids 69 and 87, ']' sets id 88 (which decodes to nothing).  Throws std::runtime_error, naming the character, when
+// allow or deny holds one that names no class in 1..94 ('~', a blank, any non-ASCII byte), or when only EOS is left.  Returns the character classes set.
+int charset_mask(const Tokenizer& tok, const char* allow, const char* deny, uint32_t mask[3]);
+
 // The confidence rule (DESIGN.md "Recognition confidence") on the host, for any ids: the characters of decode(ids) are the positions before the
 // first id 0 (the EOS) whose id is not 88 and lies in [0, 98); char_conf (n entries suffice) receives their probs in position order, *conf the fp32
 // product from 1.0f of those probs, in order, times probs[EOS] when there is an EOS.  decode_conf_kernel forms the same product.  Returns the

@@ -215,12 +215,12 @@ void launch_attn_enc(Precision prec, const void* qkv, void* out, int N, hipStrea
 // token i of crop n: i == 0 -> emb[tok] (null context, no position), else pos_q[i-1] + emb[tok].
 // emb is pre-scaled by sqrt(384) at export.  One wave per row.
 // prev_logits (an AR step, i1 == i0 + 1 >= 2): the token of column i0 is not there yet - it is the first maximal index of the previous step's
-// logits row (argmax_kernel's rule), which the row's wave finds first, writes to tokens[n][i0] and counts (done_count: crops whose FIRST EOS
+// logits row (argmax_kernel's rule, among the classes cm allows), which the row's wave finds first, writes to tokens[n][i0] and counts (done_count: crops whose FIRST EOS
 // this is): the argmax launch between two AR steps folded into the next step's first kernel.
 template <typename T>
 __global__ void dec_embed_ln_kernel(int* __restrict__ tokens, const float* __restrict__ emb, const float* __restrict__ pos_q,
                                     const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* __restrict__ out, int N, int i0, int i1,
-                                    const int* skip, int skip_n, int planes, const float* __restrict__ prev_logits, int prev_ld, int C, int* done_count, int eos, unsigned* range_flag, unsigned range_tag) {
+                                    const int* skip, int skip_n, int planes, const float* __restrict__ prev_logits, int prev_ld, int C, int* done_count, int eos, ClassMask cm, unsigned* range_flag, unsigned range_tag) {
   RangeWatch rw;   // (split.h)
   if (skip && __builtin_nontemporal_load(skip) >= skip_n) return;   // AR early exit (see ConvParams::skip)
   const int R = i1 - i0;
@@ -231,7 +231,7 @@ __global__ void dec_embed_ln_kernel(int* __restrict__ tokens, const float* __res
   if (prev_logits) {
     const float* x = prev_logits + (int64_t)n * prev_ld;
     float best = -INFINITY; int bi = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) { float v = x[c]; if (v > best) { best = v; bi = c; } }
+    for (int c = lane; c < C; c += 64) { float v = x[c]; if (cm.allows(c) && v > best) { best = v; bi = c; } }   // (a blocked class takes no part: DESIGN.md "Character sets")
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       float ov = __shfl_xor(best, o); int oi = __shfl_xor(bi, o);
@@ -276,7 +276,7 @@ template <int NPL>
 __global__ __launch_bounds__(256) void dec_embed_ln_planes_kernel(int* __restrict__ tokens, const float* __restrict__ emb, const float* __restrict__ pos_q,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta, float eps, f16* __restrict__ out, int N,
                                                                   int i0, int i1, const int* skip, int skip_n, const float* __restrict__ prev_logits, int prev_ld, int C,
-                                                                  int* done_count, int eos, unsigned* range_flag, unsigned range_tag) {
+                                                                  int* done_count, int eos, ClassMask cm, unsigned* range_flag, unsigned range_tag) {
   RangeWatch rw;   // (split.h)
   if (skip && __builtin_nontemporal_load(skip) >= skip_n) return;
   const int R = i1 - i0;
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256) void dec_embed_ln_planes_kernel(int* __restric
   if (prev_logits) {
     const float* x = prev_logits + (int64_t)n * prev_ld;
     float best = -INFINITY; int bi = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) { float v = x[c]; if (v > best) { best = v; bi = c; } }
+    for (int c = lane; c < C; c += 64) { float v = x[c]; if (cm.allows(c) && v > best) { best = v; bi = c; } }   // (a blocked class takes no part: DESIGN.md "Character sets")
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       float ov = __shfl_xor(best, o); int oi = __shfl_xor(bi, o);
@@ -330,15 +330,15 @@ __global__ __launch_bounds__(256) void dec_embed_ln_planes_kernel(int* __restric
 
 void launch_dec_embed_ln(Precision prec, int* tokens, const float* emb, const float* pos_q, const float* gamma, const float* beta, float eps,
                          void* out, int N, int i0, int i1, hipStream_t s, const int* skip, int skip_n, int planes,
-                         const float* prev_logits, int prev_ld, int C, int* done_count, int eos) {
+                         const float* prev_logits, int prev_ld, int C, int* done_count, int eos, ClassMask cm) {
   int rows = N * (i1 - i0);
   if (rows <= 0) return;
   if (prev_logits && (i1 != i0 + 1 || i0 < 1)) throw std::runtime_error("dec_embed_ln: the folded argmax belongs to one AR step's column");
   dim3 grid((rows + 3) / 4);
   if (prec != kBF16 && planes == 3 && !(((uintptr_t)emb | (uintptr_t)pos_q | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15))
-    hipLaunchKernelGGL(dec_embed_ln_planes_kernel<3>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (f16*)out, N, i0, i1, skip, skip_n, prev_logits, prev_ld, C, done_count, eos, range_ctx().flag, range_ctx().tag);
-  else if (prec == kBF16) hipLaunchKernelGGL(dec_embed_ln_kernel<bf16>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (bf16*)out, N, i0, i1, skip, skip_n, 0, prev_logits, prev_ld, C, done_count, eos, range_ctx().flag, range_ctx().tag);
-  else hipLaunchKernelGGL(dec_embed_ln_kernel<float>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (float*)out, N, i0, i1, skip, skip_n, planes, prev_logits, prev_ld, C, done_count, eos, range_ctx().flag, range_ctx().tag);
+    hipLaunchKernelGGL(dec_embed_ln_planes_kernel<3>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (f16*)out, N, i0, i1, skip, skip_n, prev_logits, prev_ld, C, done_count, eos, cm, range_ctx().flag, range_ctx().tag);
+  else if (prec == kBF16) hipLaunchKernelGGL(dec_embed_ln_kernel<bf16>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (bf16*)out, N, i0, i1, skip, skip_n, 0, prev_logits, prev_ld, C, done_count, eos, cm, range_ctx().flag, range_ctx().tag);
+  else hipLaunchKernelGGL(dec_embed_ln_kernel<float>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (float*)out, N, i0, i1, skip, skip_n, planes, prev_logits, prev_ld, C, done_count, eos, cm, range_ctx().flag, range_ctx().tag);
 }
 
 // ------------------------------------------------------------------ decoder self attention
@@ -749,15 +749,15 @@ void launch_dec_cross_attn(Precision prec, const void* q, const void* kvmem, voi
 #undef TTR_CROSS_ROWS
 }
 
-// ------------------------------------------------------------------ argmax (first maximal index, like torch.argmax on CPU)
+// ------------------------------------------------------------------ argmax (first maximal index, like torch.argmax on CPU; among the classes cm allows)
 __global__ void argmax_kernel(const float* __restrict__ logits, int ld, int C, int* __restrict__ tokens, int tok_ld, int col, int N,
-                              const int* skip, int skip_n, int* done_count, int eos) {
+                              const int* skip, int skip_n, int* done_count, int eos, ClassMask cm) {
   if (skip && __builtin_nontemporal_load(skip) >= skip_n) return;   // AR early exit (see ConvParams::skip)
   int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (n >= N) return;
   const float* x = logits + (int64_t)n * ld;
   float best = -INFINITY; int bi = 0x7fffffff;
-  for (int c = lane; c < C; c += 64) { float v = x[c]; if (v > best) { best = v; bi = c; } }
+  for (int c = lane; c < C; c += 64) { float v = x[c]; if (cm.allows(c) && v > best) { best = v; bi = c; } }   // (a blocked class takes no part: DESIGN.md "Character sets")
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     float ov = __shfl_xor(best, o); int oi = __shfl_xor(bi, o);
@@ -773,9 +773,9 @@ __global__ void argmax_kernel(const float* __restrict__ logits, int ld, int C, i
   }
 }
 
-void launch_argmax(const float* logits, int ld, int C, int* tokens, int tok_ld, int col, int N, hipStream_t s, const int* skip, int skip_n, int* done_count, int eos) {
+void launch_argmax(const float* logits, int ld, int C, int* tokens, int tok_ld, int col, int N, hipStream_t s, const int* skip, int skip_n, int* done_count, int eos, ClassMask cm) {
   if (N <= 0) return;
-  hipLaunchKernelGGL(argmax_kernel, dim3((N + 3) / 4), dim3(256), 0, s, logits, ld, C, tokens, tok_ld, col, N, skip, skip_n, done_count, eos);
+  hipLaunchKernelGGL(argmax_kernel, dim3((N + 3) / 4), dim3(256), 0, s, logits, ld, C, tokens, tok_ld, col, N, skip, skip_n, done_count, eos, cm);
 }
 
 __global__ void fill_i32_kernel(int* p, int value, int n, int stride) {

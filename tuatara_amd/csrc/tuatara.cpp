@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <iostream>
 #include <map>
+#include <memory>
 #include <mutex>
 
 #include "../../include/tuatara_hip.h"
@@ -54,6 +55,30 @@ ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int o
   return e;
 }
 
+// A call's character set on the cached engine (DESIGN.md "Character sets"): set when the call begins, reset when it ends, also when it throws.  An empty
+// argument falls back on TUATARA_ALLOWLIST / TUATARA_BLOCKLIST.  Calls that share an engine take turns, so that none runs under another's set.
+std::map<ttr_engine*, std::unique_ptr<std::mutex>> g_call_mu;
+struct CharsetScope {
+  ttr_engine* e;
+  std::unique_lock<std::mutex> turn;
+  bool set = false, ok = true;
+  CharsetScope(ttr_engine* e_, std::string allow, std::string deny) : e(e_) {
+    {
+      std::lock_guard<std::mutex> lk(g_mu);
+      auto& m = g_call_mu[e];
+      if (!m) m.reset(new std::mutex);
+      turn = std::unique_lock<std::mutex>(*m, std::defer_lock);
+    }
+    turn.lock();
+    if (allow.empty()) if (const char* p = std::getenv("TUATARA_ALLOWLIST")) allow = p;
+    if (deny.empty()) if (const char* p = std::getenv("TUATARA_BLOCKLIST")) deny = p;
+    if (allow.empty() && deny.empty()) return;
+    if (ttr_engine_set_charset(e, allow.c_str(), deny.c_str()) != 0) { std::cerr << "tuatara: " << ttr_last_error() << std::endl; ok = false; return; }
+    set = true;
+  }
+  ~CharsetScope() { if (set) ttr_engine_set_charset(e, nullptr, nullptr); }
+};
+
 template <class Item>
 void fill(Item& o, const ttr_result* r, int i) {   // text and bbox: OutputItem, and the start of OutputItemEx
   o.text = ttr_result_text(r, i);
@@ -103,9 +128,11 @@ ttr_engine* open_engine(const std::string& weights_dir, const std::string& outpu
 template <class Item>
 std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
                           const std::string& outputs_dir, int crop_mode, int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
-                                        int blocks = -1) {
+                                        int blocks = -1, const std::string& allow = std::string(), const std::string& deny = std::string()) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks);
   if (!e) return {};
+  CharsetScope cs(e, allow, deny);
+  if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
     return {};
@@ -124,9 +151,11 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
 template <class Item>
 std::vector<std::vector<Item>> run_many(const std::vector<ImageView>& images, const std::string& weights_dir, const std::string& outputs_dir, int crop_mode,
                                         int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
-                                        int blocks = -1, int mixed = -1) {
+                                        int blocks = -1, int mixed = -1, const std::string& allow = std::string(), const std::string& deny = std::string()) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks, mixed);
   if (!e) return {};
+  CharsetScope cs(e, allow, deny);
+  if (!cs.ok) return {};
   const int n = (int)images.size();
   std::vector<const uint8_t*> ptr(n);
   std::vector<int> hs(n), ws(n), st(n);
@@ -218,4 +247,18 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
                                                          bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches) {
   return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
                                 blocks ? 1 : -1, mixed_batches ? 1 : -1);
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist) {
+  return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1,
+                               chars ? 1 : -1, blocks ? 1 : -1, allowlist, blocklist);
+}
+
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist) {
+  return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
+                                blocks ? 1 : -1, mixed_batches ? 1 : -1, allowlist, blocklist);
 }

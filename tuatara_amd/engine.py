@@ -117,6 +117,10 @@ SYMBOLS = [
     ("ttr_results_gather_conf", _I, [C.POINTER(_VP), _I, _PF, _PF]),
     ("ttr_confidence_from_probs", _I, [_PI, _PF, _I, _PF, C.POINTER(C.c_int), _PF]),
     ("ttr_logits_confidence", _I, [_VP, _PF, _I, _PI, _PF, _PF]),
+    ("ttr_charset_mask", _I, [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
+    ("ttr_engine_set_charset", _I, [_VP, C.c_char_p, C.c_char_p]),
+    ("ttr_engine_get_charset", _I, [_VP, C.POINTER(C.c_uint32)]),
+    ("ttr_logits_confidence_masked", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _PI, _PF, _PF]),
     ("ttr_craft_heatmap", _I, [_VP, _PU8, _I, _I, _PF]),
     ("ttr_ccl_boxes", _I, [_VP, _PF, _I, _I, _PF, _I, _PI]),
     ("ttr_resize_canvas", _I, [_VP, _PU8, _I, _I, _I, _PU8, C.c_size_t, _PI, _PI, _PF]),
@@ -310,6 +314,26 @@ def confidence_from_probs(ids, probs):
     if load().ttr_confidence_from_probs(_i(ids), _f(probs), len(ids), _f(cc), C.byref(nc), C.byref(conf)) < 0:
         raise EngineError("ttr_confidence_from_probs: bad arguments")
     return cc[:nc.value].copy(), np.float32(conf.value)
+
+
+def _charlist(s):
+    """A character list for the C ABI: None stays None; str travels as bytes (one byte per character where latin-1 can)."""
+    if s is None or isinstance(s, bytes):
+        return s
+    try:
+        return s.encode("latin1")
+    except UnicodeEncodeError:
+        return s.encode("utf-8")
+
+
+def charset_mask(allow=None, deny=None) -> np.ndarray:
+    """The class mask of a character set on the host (ttr_charset_mask, no GPU; DESIGN.md "Character sets"): uint32 [3], class c = bit c & 31 of
+    word c >> 5.  Bit 0 (EOS) is always set; None or "" mean every character (allow) / none (deny).  A character that names no class ('~', a blank,
+    non-ASCII) or a set that leaves only EOS raises EngineError."""
+    m = (C.c_uint32 * 3)()
+    if load().ttr_charset_mask(_charlist(allow), _charlist(deny), m) < 0:
+        raise EngineError(load().ttr_last_error().decode("latin1"))
+    return np.array(list(m), dtype=np.uint32)
 
 
 def orient_select(conf, ids, per_page: bool = False):
@@ -572,6 +596,21 @@ class Engine:
     def set_tuning(self, key, value: int) -> int:
         """Per-engine kernel-selection knob (ttr_engine_set_tuning); keys it does not know go to the process-wide diagnostics setter."""
         return self.lib.ttr_engine_set_tuning(self.h, key if isinstance(key, bytes) else key.encode(), int(value))
+
+    def set_charset(self, allow=None, deny=None):
+        """Restrict what the recogniser may emit (ttr_engine_set_charset; DESIGN.md "Character sets"): allow = the characters it may choose (None or
+        "": all), deny = characters it may not (None or "": none).  set_charset() resets.  The set acts where each token is chosen - AR steps,
+        refinement inputs, the final decode - on parseq_logits and every page call; prob / conf are over the allowed classes.  Raises EngineError,
+        and keeps the previous set, on a character that names no class, between a stream_push and its flush, and on a bf16 engine."""
+        if self.lib.ttr_engine_set_charset(self.h, _charlist(allow), _charlist(deny)) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def charset(self) -> np.ndarray:
+        """The class mask in force: uint32 [3] (charset_mask's form); all 95 bits set when there is no set."""
+        m = (C.c_uint32 * 3)()
+        self._check(self.lib.ttr_engine_get_charset(self.h, m))
+        return np.array(list(m), dtype=np.uint32)
 
     def close(self):
         if getattr(self, "h", None):
@@ -1022,13 +1061,18 @@ class Engine:
         self._check(self.lib.ttr_parseq_logits(self.h, _u8(crops), n, _f(logits), _f(ar) if want_ar else None, _i(ids)))
         return (logits, ar, ids) if want_ar else (logits, ids)
 
-    def logits_confidence(self, logits: np.ndarray):
+    def logits_confidence(self, logits: np.ndarray, mask=None):
         """The recogniser's final decode on host logits f32 [n, 26, 95] (ttr_logits_confidence: decode_conf_kernel) -> (ids i32 [n, 26],
-        prob f32 [n, 26], conf f32 [n])."""
+        prob f32 [n, 26], conf f32 [n]).  mask (uint32 [3], charset_mask's form): the decode among the allowed classes only
+        (ttr_logits_confidence_masked); the engine's own set is not consulted either way."""
         logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, 26, 95)
         n = len(logits)
         ids, prob, conf = np.zeros((n, 26), np.int32), np.zeros((n, 26), np.float32), np.zeros(n, np.float32)
-        self._check(self.lib.ttr_logits_confidence(self.h, _f(logits), n, _i(ids), _f(prob), _f(conf)))
+        if mask is None:
+            self._check(self.lib.ttr_logits_confidence(self.h, _f(logits), n, _i(ids), _f(prob), _f(conf)))
+        else:
+            m = (C.c_uint32 * 3)(*[int(v) for v in np.asarray(mask).ravel()[:3]])
+            self._check(self.lib.ttr_logits_confidence_masked(self.h, _f(logits), n, m, _i(ids), _f(prob), _f(conf)))
         return ids, prob, conf
 
     def dbg_conv_pool(self, x0: np.ndarray, w: np.ndarray, bias: Optional[np.ndarray], ks: int, act: int = 0, pool_relu: bool = False,
