@@ -15,6 +15,10 @@
 // And keyword-only allowlist=None, blocklist=None: the characters the recogniser may / may not emit (DESIGN.md "Character sets"), set on the cached
 // engine for the call and reset afterwards, also when the call raises.  A character the recogniser has no class for ('~', a blank, non-ASCII) or a
 // set that leaves nothing raises ValueError, naming the character, before anything runs.  The dicts' keys do not change.
+// And a keyword-only regions=None on image_to_data: a list of dicts {"quad": 8 floats (or 4 pairs) tl, tr, br, bl | "rect": (x0, y0, x1, y1), optional
+// "allowlist" / "blocklist"} reads those regions with no detector, each under its own character set, in one recogniser pass (DESIGN.md "Regions and
+// per-row character sets"); a region without lists reads under the call's allowlist / blocklist.  One dict per region, in order: "text", "bbox", "quad" (the
+// caller's floats), "region" (its index) and - conf=True - "conf" / "char_conf".  A bad list raises ValueError before anything runs.
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -83,14 +87,79 @@ static void charset_args(const py::object& allow_kw, const py::object& deny_kw, 
   if ((!allow.empty() || !deny.empty()) && ttr_charset_mask(allow.c_str(), deny.c_str(), mask) < 0) throw std::invalid_argument(ttr_last_error());
 }
 
+// regions=[{...}, ...] -> RegionSpecs; every entry is checked here, on the host, so a bad list raises ValueError before anything runs
+static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
+  std::vector<RegionSpec> out;
+  if (!py::isinstance<py::sequence>(regions_kw) || py::isinstance<py::str>(regions_kw)) throw std::invalid_argument("regions must be a list of dicts");
+  size_t i = 0;
+  for (py::handle h : regions_kw) {
+    const std::string at = "regions[" + std::to_string(i++) + "]: ";
+    if (!py::isinstance<py::dict>(h)) throw std::invalid_argument(at + "a region is a dict with \"quad\" or \"rect\"");
+    py::dict d = py::reinterpret_borrow<py::dict>(h);
+    for (auto kv : d) {
+      const std::string k = py::str(kv.first);
+      if (k != "quad" && k != "rect" && k != "allowlist" && k != "blocklist") throw std::invalid_argument(at + "unknown key \"" + k + "\"");
+    }
+    if (d.contains("quad") == d.contains("rect")) throw std::invalid_argument(at + "give \"quad\" or \"rect\" (one of them)");
+    RegionSpec s;
+    try {
+      if (d.contains("quad")) {
+        py::array_t<double, py::array::c_style | py::array::forcecast> q = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(d["quad"]);
+        if (!q || q.size() != 8) throw std::invalid_argument("");
+        for (int k = 0; k < 8; ++k) s.quad.push_back((float)q.data()[k]);
+      } else {
+        std::vector<long long> r = d["rect"].cast<std::vector<long long>>();
+        if (r.size() != 4) throw std::invalid_argument("");
+        s.quad.assign(8, 0.f);
+        if (ttr_region_from_rect((int)r[0], (int)r[1], (int)r[2], (int)r[3], s.quad.data()) != 0) throw std::invalid_argument(at + ttr_last_error());
+      }
+    } catch (const py::cast_error&) {
+      throw std::invalid_argument(at + "\"quad\" is 8 floats (tl, tr, br, bl), \"rect\" four integers (x0, y0, x1, y1)");
+    } catch (const std::invalid_argument& ex) {
+      if (*ex.what()) throw;
+      throw std::invalid_argument(at + "\"quad\" is 8 floats (tl, tr, br, bl), \"rect\" four integers (x0, y0, x1, y1)");
+    }
+    for (int k = 0; k < 8; ++k)
+      if (!(s.quad[k] == s.quad[k]) || !(s.quad[k] > -32768.f && s.quad[k] < 32768.f)) throw std::invalid_argument(at + "a coordinate is not finite or has |x| >= 32768");
+    try {
+      if (d.contains("allowlist") && !d["allowlist"].is_none()) s.allowlist = d["allowlist"].cast<std::string>();
+      if (d.contains("blocklist") && !d["blocklist"].is_none()) s.blocklist = d["blocklist"].cast<std::string>();
+    } catch (const py::cast_error&) { throw std::invalid_argument(at + "\"allowlist\" / \"blocklist\" are strings"); }
+    uint32_t mask[3];
+    if ((!s.allowlist.empty() || !s.blocklist.empty()) && ttr_charset_mask(s.allowlist.c_str(), s.blocklist.c_str(), mask) < 0) throw std::invalid_argument(at + ttr_last_error());
+    out.push_back(std::move(s));
+  }
+  return out;
+}
+
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
-                                      bool blocks, py::object allowlist, py::object blocklist) {
+                                      bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw) {
   const int orient = orient_mode(orient_kw);
   std::string allow, deny;
   charset_args(allowlist, blocklist, allow, deny);
   const bool cset = !allow.empty() || !deny.empty();
   lines = lines || blocks;   // blocks are made of lines
+  if (!regions_kw.is_none()) {   // regions: no detector; every check before anything runs
+    if (rectify || orient || orient_page || lines || chars || blocks) throw std::invalid_argument("regions do not combine with rectify, orient, lines, chars or blocks: a region is read as the quad it is");
+    std::vector<RegionSpec> regs = region_args(regions_kw);
+    for (RegionSpec& s : regs) if (s.allowlist.empty() && s.blocklist.empty()) { s.allowlist = allow; s.blocklist = deny; }   // the call's own lists where a region has none
+    py::buffer_info rb = image.request();
+    if (rb.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
+    if (rb.shape[2] != 3) throw std::runtime_error("Input array should have 3 channels");
+    std::vector<OutputItemEx> got;
+    {
+      py::gil_scoped_release nogil;
+      got = image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs);
+    }
+    py::list res;
+    for (const auto& item : got) {
+      py::dict d = item_dict(item, Keys{true, conf, false, false, false, false});
+      d["region"] = item.region;
+      res.append(d);
+    }
+    return res;
+  }
   py::buffer_info buf = image.request();
   if (buf.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
   if (buf.shape[2] != 3) throw std::runtime_error("Input array should have 3 channels");
@@ -157,7 +226,7 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
         py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");

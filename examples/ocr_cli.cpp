@@ -16,15 +16,58 @@
 // after block in reading order - a column to its end before the next -, one line of the page per output line and an empty line between blocks.
 //   ocr_cli --allowlist S --blocklist S ...                      in front of any form above: the characters the recogniser may / may not emit (DESIGN.md
 // "Character sets"), e.g. --allowlist 0123456789 for a field of digits.  They reach the call as TUATARA_ALLOWLIST / TUATARA_BLOCKLIST.
+//   ocr_cli --regions FILE <image.png> <weights_dir> <outputs_dir>   reads the regions FILE lists, with no detector, each under its own character set
+// (DESIGN.md "Regions and per-row character sets").  One region per line: "x0 y0 x1 y1 [allow [deny]]" - the pixels [x0, x1) x [y0, y1) - or eight floats
+// "tl.x tl.y tr.x tr.y br.x br.y bl.x bl.y [allow [deny]]"; '#' starts a comment.  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per region, in the file's
+// order, every number to 9 significant digits (a float read back is the float that was printed).  A malformed file fails, naming the line, before the image is read.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
+#include <sstream>
 
 #include "../include/tuatara.h"
 #include "png_decode.h"
+
+// --regions FILE: one RegionSpec per line (see the top of the file); throws, naming the line, on anything else
+static std::vector<RegionSpec> read_regions(const char* path) {
+  std::ifstream f(path);
+  if (!f) throw std::runtime_error(std::string("cannot read regions file ") + path);
+  std::vector<RegionSpec> out;
+  std::string line;
+  for (int ln = 1; std::getline(f, line); ++ln) {
+    const size_t hash = line.find('#');
+    if (hash != std::string::npos) line.resize(hash);
+    std::istringstream ss(line);
+    std::vector<std::string> tok;
+    for (std::string t; ss >> t;) tok.push_back(t);
+    if (tok.empty()) continue;
+    const std::string at = std::string(path) + ":" + std::to_string(ln) + ": ";
+    const size_t nnum = tok.size() >= 8 ? 8 : 4;
+    if (tok.size() < 4 || tok.size() > nnum + 2) throw std::runtime_error(at + "a region is \"x0 y0 x1 y1 [allow [deny]]\" or eight floats \"tl tr br bl [allow [deny]]\"");
+    double v[8];
+    for (size_t k = 0; k < nnum; ++k) {
+      char* end = nullptr;
+      v[k] = std::strtod(tok[k].c_str(), &end);
+      if (end == tok[k].c_str() || *end || !std::isfinite(v[k]) || std::fabs(v[k]) >= 32768.) throw std::runtime_error(at + "\"" + tok[k] + "\" is not a coordinate");
+    }
+    RegionSpec r;
+    if (nnum == 4) {
+      for (int k = 0; k < 4; ++k) if (v[k] != std::floor(v[k])) throw std::runtime_error(at + "a rectangle's corners are integers");
+      if (v[2] <= v[0] || v[3] <= v[1]) throw std::runtime_error(at + "the rectangle is empty");
+      r = region_from_rect((int)v[0], (int)v[1], (int)v[2], (int)v[3]);
+    } else {
+      for (int k = 0; k < 8; ++k) r.quad.push_back((float)v[k]);
+    }
+    if (tok.size() > nnum) r.allowlist = tok[nnum];
+    if (tok.size() > nnum + 1) r.blocklist = tok[nnum + 1];
+    out.push_back(std::move(r));
+  }
+  return out;
+}
 
 int main(int argc, const char** argv) {
   try {
@@ -39,6 +82,14 @@ int main(int argc, const char** argv) {
       fwrite(img.bgr.data(), 1, img.bgr.size(), f);
       fclose(f);
       printf("%d %d\n", img.rows, img.cols);
+      return 0;
+    }
+    if (argc == 6 && std::string(argv[1]) == "--regions") {
+      const std::vector<RegionSpec> regions = read_regions(argv[2]);   // (before the image and the engine: a malformed file costs nothing)
+      pngdec::Image img = pngdec::read(argv[3]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[4], argv[5], regions);
+      if (items.size() != regions.size()) return 1;                    // (the message is on stderr)
+      for (const OutputItemEx& it : items) printf("%.9g %.9g %.9g %.9g\t%.9g\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.conf, it.text.c_str());
       return 0;
     }
     if (argc == 5 && std::string(argv[1]) == "--rectify") {
@@ -103,7 +154,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--rectify | --conf | --orient | --lines | --chars | --blocks] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

@@ -49,6 +49,7 @@ struct OutputItemEx {
   int orient = 0;                  // word orientation: the turn the word was read at, in degrees clockwise (0, 90, 180, 270; DESIGN.md "Word orientation")
   std::vector<CharBox> chars;      // character boxes: one per character of `text`, in text order; empty when chars are off (DESIGN.md "Character boxes")
   int line = -1, word = -1;        // text lines: the item's line of its page, in reading order, and its position inside that line; -1 when lines are off (DESIGN.md "Text lines")
+  int region = -1;                 // regions: the index of the caller's region this item reads; -1 for items the detector found (DESIGN.md "Regions and per-row character sets")
   int block = -1, block_line = -1;  // text blocks: the item's block of its page, in reading order, and its line's position inside that block (what a caller sorts by: block, block_line, word); -1 when blocks are off (DESIGN.md "Text blocks")
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
@@ -108,6 +109,20 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
 std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
                                                          bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
                                                          std::string allowlist, std::string blocklist);
+
+// Regions (DESIGN.md "Regions and per-row character sets"): read quadrilaterals the caller already knows - the fields of a form - with no detector, each
+// under its own character set, in one recogniser pass.  A region is a quad tl, tr, br, bl in image pixels (pixel centres at integers, as OutputItemEx::quad
+// gives it), or the pixel rectangle [x0, x1) x [y0, y1) through region_from_rect; allowlist / blocklist as above, both empty = the engine's own set
+// (TUATARA_ALLOWLIST / TUATARA_BLOCKLIST, else every character).  One item per region, in the caller's order: `region` its index, `quad` the caller's floats,
+// `bbox` the corners' extremes, text / conf / char_conf as above.  A bad region or list, or an engine with orientation, lines, character boxes or blocks
+// turned on through the environment: the message is printed and the result is empty.
+struct RegionSpec {
+  std::vector<float> quad;          // 8: tl.x, tl.y, tr.x, tr.y, br.x, br.y, bl.x, bl.y
+  std::string allowlist, blocklist;
+};
+RegionSpec region_from_rect(int x0, int y0, int x1, int y1, std::string allowlist = std::string(), std::string blocklist = std::string());
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

@@ -400,6 +400,40 @@ int ttr_charset_mask(const char* allow, const char* deny, uint32_t mask[3]);
 int ttr_engine_set_charset(ttr_engine* e, const char* allow, const char* deny);
 int ttr_engine_get_charset(const ttr_engine* e, uint32_t mask[3]);
 int ttr_logits_confidence_masked(ttr_engine* e, const float* logits, int n, const uint32_t mask[3], int32_t* ids, float* probs, float* conf);
+/* Regions and per-row character sets (DESIGN.md "Regions and per-row character sets"): read quadrilaterals the caller already knows - a form's fields -
+ * with no detector, each under its own character set, in ONE recogniser pass.
+ * A ttr_region is a quad tl, tr, br, bl in image pixels (pixel centres at integers, as ttr_result_quad returns it) on page `page` of the call, read
+ * under set `set`: an index into the call's masks sets[n_sets][3] (ttr_charset_mask's form; bit 0 must be set), or -1 for the engine's own set
+ * (ttr_engine_set_charset).  The crop is the rectified sampler's (the kind-1 crop of "Rectified crops") whatever the engine's crop_mode; outside the page
+ * the border pixel is replicated.  ttr_region_from_rect: the pixel-edge quad of the pixels [x0, x1) x [y0, y1) (host; -1 for an empty rectangle).
+ * ttr_region_geometry (host, no engine): what a region call derives from one quad - fixed[6] = the sampler's coefficients {X0, Ax, Bx, Y0, Ay, By} in 2^-16 px
+ * (output pixel (u, v) of the 32 x 128 crop samples (X0 + u Ax + v Bx, Y0 + u Ay + v By)), bbox[4], and *inside = 1 when every corner lies within the pixel
+ * edges of an h x w page (the strict_crops test); any output may be NULL.  -1, naming the reason, for a quad the calls refuse.
+ * ttr_regions_to_data_dev: n regions on n_pages device pages of ANY sizes and strides (no canvas is shared: no detector runs) -> out[n_pages]; page
+ * p's result holds its regions in the caller's order (count 0 for a page without regions): quad = the caller's floats verbatim, bbox = {min x, min y,
+ * max x, max y} of the corners, ids / text / prob / conf as on every page entry point, and the item's set index (ttr_result_sets).
+ * ttr_image_regions_to_data: the same for one host image (every region's page must be 0) -> *out.
+ * Both are synchronous and refuse - before anything is enqueued, the engine stays as it was - while streamed batches are in flight, with a
+ * communicator attached, with orient, lines, chars or blocks set (group regions with ttr_group_lines / ttr_group_blocks on their quads), on a
+ * coordinate that is not finite or has |x| >= 32768, on a page or set index out of range, on a mask without bit 0, on a restricting mask on a bf16
+ * engine, and - strict_crops = 1 - on a region with a corner outside the page's pixel edges [-0.5, w - 0.5] x [-0.5, h - 0.5].
+ * ttr_result_sets: [count] each item's set index; NULL for results of the detecting entry points.
+ * Stage twins (each refuses while batches stream): ttr_pack_regions - a host image and quads [n][8] -> crops [n][32][128][3]; ttr_parseq_logits_sets -
+ * ttr_parseq_logits where crop i chooses under sets[set_of[i]] (-1: the engine's own set); ttr_logits_confidence_sets - ttr_logits_confidence_masked
+ * where row i decodes under sets[set_of[i]] (-1: the engine's own set; set_of is not NULL). */
+typedef struct ttr_region { float quad[8]; int32_t page; int32_t set; } ttr_region;
+int ttr_region_from_rect(int x0, int y0, int x1, int y1, float quad[8]);
+int ttr_region_geometry(const float quad[8], int h, int w, int64_t fixed[6], float bbox[4], int* inside);
+int ttr_regions_to_data_dev(ttr_engine* e, const ttr_page* pages, int n_pages, const ttr_region* regions, int n, const uint32_t* sets, int n_sets,
+                            ttr_result** out);
+int ttr_image_regions_to_data(ttr_engine* e, const uint8_t* hwc_u8, int h, int w, int row_stride, const ttr_region* regions, int n, const uint32_t* sets,
+                              int n_sets, ttr_result** out);
+const int32_t* ttr_result_sets(const ttr_result* r);
+int ttr_pack_regions(ttr_engine* e, const uint8_t* hwc_u8, int h, int w, int row_stride, const float* quads, int n, uint8_t* crops_out);
+int ttr_parseq_logits_sets(ttr_engine* e, const uint8_t* crops, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, float* logits,
+                           float* ar_logits, int32_t* ids);
+int ttr_logits_confidence_sets(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* ids,
+                               float* probs, float* conf);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

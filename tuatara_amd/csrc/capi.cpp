@@ -823,6 +823,146 @@ int ttr_logits_confidence_masked(ttr_engine* e, const float* logits, int n, cons
   TTR_GUARD_END(-1)
 }
 
+int ttr_region_from_rect(int x0, int y0, int x1, int y1, float quad[8]) {
+  TTR_GUARD_BEGIN
+  if (!quad) throw std::runtime_error("null argument");
+  if (x1 <= x0 || y1 <= y0) throw std::runtime_error("ttr_region_from_rect: the rectangle is empty");
+  Pt2f q[4];
+  box_edge_quad(x0, y0, x1, y1, q);
+  for (int k = 0; k < 4; ++k) { quad[2 * k] = q[k].x; quad[2 * k + 1] = q[k].y; }
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_region_geometry(const float quad[8], int h, int w, int64_t fixed[6], float bbox[4], int* inside) {
+  TTR_GUARD_BEGIN
+  if (!quad) throw std::runtime_error("null argument");
+  if (!region_quad_ok(quad)) throw std::runtime_error("regions: a coordinate is not finite or has |x| >= 32768");
+  if (fixed) region_coef(quad, fixed);
+  if (bbox) region_bbox(quad, bbox);
+  if (inside) *inside = region_inside(quad, h, w) ? 1 : 0;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_regions_to_data_dev(ttr_engine* e, const ttr_page* pages, int n_pages, const ttr_region* regions, int n, const uint32_t* sets, int n_sets,
+                            ttr_result** out) {
+  TTR_GUARD_BEGIN
+  if (!e || (n_pages > 0 && !out)) throw std::runtime_error("null argument");
+  EngineScope lk(*e->e);
+  std::vector<Result> res;
+  e->e->run_regions(pages, n_pages, regions, n, sets, n_sets, res);
+  hand_out(res, n_pages, out);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_image_regions_to_data(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const ttr_region* regions, int n, const uint32_t* sets,
+                              int n_sets, ttr_result** out) {
+  TTR_GUARD_BEGIN
+  if (!e || !out) throw std::runtime_error("null argument");
+  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("regions");                    // (before the staging buffer, which streamed batches may still read, is touched)
+  E.staging_img.ensure((size_t)h * w * 3);
+  const ttr_page page{E.staging_img.as<uint8_t>(), h, w, w * 3};
+  // the copy is enqueued first (a refused call costs a copy, changes nothing: the staging image is scratch of the synchronous entry points)
+  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
+  std::vector<Result> res;
+  struct Drain { Engine& E; ~Drain() { (void)hipStreamSynchronize(E.stream); } } drain{E};   // (the caller's image is pageable: the copy ends inside the call, refused or not)
+  E.run_regions(&page, 1, regions, n, sets, n_sets, res);
+  hand_out(res, 1, out);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+const int32_t* ttr_result_sets(const ttr_result* r) { return r && !r->r.set.empty() ? r->r.set.data() : nullptr; }
+
+int ttr_pack_regions(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const float* quads, int n, uint8_t* crops_out) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && (!quads || !crops_out))) throw std::runtime_error("null argument");
+  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_pack_regions");
+  if (n == 0) return 0;
+  std::vector<int> rects((size_t)n * 5, 0);
+  std::vector<int64_t> coef((size_t)n * 8, 0);
+  for (int i = 0; i < n; ++i) {
+    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error("ttr_pack_regions: region " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+    rects[5 * (size_t)i + 2] = 1; rects[5 * (size_t)i + 3] = 1;   // (kind 1 reads the coefficients alone; the rectangle only has to be non-empty)
+    coef[8 * (size_t)i] = 1;
+    region_coef(quads + 8 * (size_t)i, &coef[8 * (size_t)i + 1]);
+  }
+  E.staging_img.ensure((size_t)h * w * 3);
+  E.rects_dev.ensure(rects.size() * 4);
+  E.coef_dev.ensure(coef.size() * 8);
+  E.crops.ensure((size_t)n * 32 * 128 * 3);
+  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(E.coef_dev.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice, E.stream));
+  launch_pack_crops_rect(E.staging_img.as<uint8_t>(), 0, w * 3, h, w, E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_parseq_logits_sets(ttr_engine* e, const uint8_t* crops, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, float* logits,
+                           float* ar_logits, int32_t* ids) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && (!crops || !logits))) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_parseq_logits_sets");
+  std::vector<uint32_t> table;
+  ClassMask one{};
+  E.resolve_row_masks("ttr_parseq_logits_sets", set_of, n, sets, n_sets, table, one);
+  if (n == 0) return 0;
+  E.crops.ensure((size_t)n * 32 * 128 * 3);
+  E.logits.ensure((size_t)n * 26 * 95 * 4);
+  const Engine::RecOut o = E.rec_out(n);
+  if (ar_logits) E.ar_logits.ensure((size_t)n * 26 * 95 * 4);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.crops.p, crops, (size_t)n * 32 * 128 * 3, hipMemcpyHostToDevice, E.stream));
+  {
+    struct SetScope { ClassMask& c; ClassMask old; ~SetScope() { c = old; } } set_scope{E.charset, E.charset};   // (one shared mask: by value, the engine's own path)
+    E.charset = one;
+    E.parseq_forward(E.crops.as<uint8_t>(), n, E.logits.as<float>(), ar_logits ? E.ar_logits.as<float>() : nullptr, o.ids, o.prob, o.conf, E.stage_row_masks(table, 0));
+  }
+  TTR_HIP_CHECK(hipMemcpyAsync(logits, E.logits.p, (size_t)n * 26 * 95 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (ar_logits) TTR_HIP_CHECK(hipMemcpyAsync(ar_logits, E.ar_logits.p, (size_t)n * 26 * 95 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, E.ids_dev.p, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  E.range_fetch(Engine::kRangeStage);
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  E.range_verify(Engine::kRangeStage, "ttr_parseq_logits_sets");
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_logits_confidence_sets(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* ids,
+                               float* probs, float* conf) {
+  TTR_GUARD_BEGIN
+  if (!e || !set_of || n < 0 || (n > 0 && !logits)) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_logits_confidence_sets");
+  std::vector<uint32_t> table;
+  ClassMask one{};
+  E.resolve_row_masks("ttr_logits_confidence_sets", set_of, n, sets, n_sets, table, one);
+  if (n == 0) return 0;
+  E.logits.ensure((size_t)n * 26 * 95 * 4);
+  const Engine::RecOut o = E.rec_out(n);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, one, E.stage_row_masks(table, 0));
+  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, o.ids, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (probs) TTR_HIP_CHECK(hipMemcpyAsync(probs, o.prob, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (conf) TTR_HIP_CHECK(hipMemcpyAsync(conf, o.conf, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_charset_mask(const char* allow, const char* deny, uint32_t mask[3]) {
   TTR_GUARD_BEGIN
   if (!mask) throw std::runtime_error("null argument");

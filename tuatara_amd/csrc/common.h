@@ -24,6 +24,25 @@ struct ClassMask {
   __host__ __device__ __forceinline__ bool restricts() const { return (blocked[0] | blocked[1] | blocked[2]) != 0u; }
 };
 
+// Per-row class masks (DESIGN.md "Regions and per-row character sets"): a device table of one mask per recogniser row, 16 bytes a row - {blocked[0],
+// blocked[1], blocked[2], 0}, ClassMask's convention, one aligned load.  It travels as one nullable pointer beside the by-value mask (a kernel argument, or
+// ConvParams::tok_row_masks): null = the by-value mask holds for every row, as before.  `row` must be wave-uniform (every place that chooses a token gives a
+// wave one row at a time): the load is a scalar one and the three words stay in scalar registers - RowClassMask picks the word by comparison, not by an index
+// into a private copy of the struct (which the compiler would park in LDS or scratch).  Same test as ClassMask::allows, so the same choices.
+typedef uint4 RowMask;
+struct RowClassMask {
+  uint32_t b0, b1, b2;
+  __device__ __forceinline__ bool allows(int c) const { return (unsigned)c >= 96u || !(((c < 32 ? b0 : (c < 64 ? b1 : b2)) >> (c & 31)) & 1u); }
+};
+__device__ __forceinline__ RowClassMask row_class_mask(const ClassMask& cm, const RowMask* __restrict__ rows, int row) {
+  RowClassMask m{cm.blocked[0], cm.blocked[1], cm.blocked[2]};
+  if (rows) {
+    const RowMask r = rows[__builtin_amdgcn_readfirstlane(row)];
+    m.b0 = r.x; m.b1 = r.y; m.b2 = r.z;
+  }
+  return m;
+}
+
 // Implicit-GEMM convolution / linear layer.  Activations are NHWC, weights are
 // [Cout][taps][Cin] (K contiguous), so both MFMA operands are read K-major.
 struct ConvParams {
@@ -54,6 +73,7 @@ struct ConvParams {
   // which column-tile 0 also writes to tok[m * tok_ld + tok_col] (argmax + dec_embed_ln folded into the self_kv GEMM)
   int* tok; int tok_ld, tok_col; const float* tok_logits; int tok_logits_ld, tok_C; const float* tok_emb; const float* tok_pos; int tok_max;
   ClassMask tok_mask;        // gemm_skx.hip's token prologue: classes that take no part in the argmax of tok_logits (zero = every class does)
+  const RowMask* tok_row_masks;   // ... or, when not null, row m's own mask (RowMask table [M]; the launcher then picks the row-table instantiation)
   unsigned long long* dbg;   // gemm_ws diagnostics: shader-clock stamps of workgroup 0 (null = off)
   int store_policy;          // set by the launchers: 0 default, 1 nt, 2 sc0 sc1 nt on the big streaming output stores
   int dbg_flags;             // gemm_ws diagnostics (timing experiments only, results are wrong): 1 = no output stores, 2 = no activation loads

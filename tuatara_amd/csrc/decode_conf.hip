@@ -5,6 +5,7 @@
 //                  are bit-identical to it
 //   prob [N][26]   1 / sum_c expf(x[c] - x[id]) in fp32 (full-precision expf)
 //   cm             the class mask (DESIGN.md "Character sets"): the maximum and the sum run over the allowed classes only; none blocked = the bits of before
+//   row_masks      optional [N] table of per-crop masks (common.h: RowMask) that replaces cm crop by crop; null = cm for every crop
 //   conf [N]       fp32 product, in position order from 1.0f, of prob over the characters of the text (positions before the first EOS,
 //                  id 0, whose id is not 88 and lies in [0, 98): Tokenizer::filter + decode), times prob[EOS] when there is one
 //
@@ -22,12 +23,13 @@ constexpr int kPos = 26, kCls = 95, kCrops = 4;   // positions, classes, crops (
 }
 
 __global__ void __launch_bounds__(256) decode_conf_kernel(const float* __restrict__ logits, int N, int* __restrict__ ids, float* __restrict__ prob,
-                                                          float* __restrict__ conf, ClassMask cm) {
+                                                          float* __restrict__ conf, ClassMask cm, const RowMask* __restrict__ row_masks) {
   const int n = blockIdx.x * kCrops + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (n >= N) return;
+  const RowClassMask rm = row_class_mask(cm, row_masks, n);   // (crop n's own set, when a row table travels with the launch: a block's four waves may hold four sets)
   const float* x = logits + (int64_t)n * kPos * kCls;
   const bool hi = lane + 64 < kCls;
-  const bool a0 = cm.allows(lane), a1 = hi && cm.allows(lane + 64);   // a blocked class: -inf in the comparison, exactly 0 in the sum (same lanes, same butterflies)
+  const bool a0 = rm.allows(lane), a1 = hi && rm.allows(lane + 64);   // a blocked class: -inf in the comparison, exactly 0 in the sum (same lanes, same butterflies)
   float v0[kPos], v1[kPos];
 #pragma unroll
   for (int p = 0; p < kPos; ++p) {
@@ -65,9 +67,9 @@ __global__ void __launch_bounds__(256) decode_conf_kernel(const float* __restric
   if (lane == 0) conf[n] = cf;
 }
 
-void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s, ClassMask cm) {
+void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s, ClassMask cm, const RowMask* row_masks) {
   if (N <= 0) return;
-  hipLaunchKernelGGL(decode_conf_kernel, dim3((N + kCrops - 1) / kCrops), dim3(256), 0, s, logits, N, ids, prob, conf, cm);
+  hipLaunchKernelGGL(decode_conf_kernel, dim3((N + kCrops - 1) / kCrops), dim3(256), 0, s, logits, N, ids, prob, conf, cm, row_masks);
 }
 
 }  // namespace ttr

@@ -262,6 +262,7 @@ struct Result {
   std::vector<float> quad;   // 8 per item: the word's corners tl, tr, br, bl in image pixels (geometry.h: deskew_quad), every crop mode
   std::vector<float> prob;   // 26 per item: softmax probability of each argmax id (decode_conf.hip)
   std::vector<float> conf;   // 1 per item: the word's confidence (DESIGN.md "Recognition confidence")
+  std::vector<int32_t> set;  // 1 per item: the caller's set index (results of the region entry points only; DESIGN.md "Regions and per-row character sets")
   // word orientation (cfg.orient != TTR_ORIENT_OFF; DESIGN.md "Word orientation"): empty when off
   std::vector<int32_t> orient;      // 1 per item: the chosen turn 0..3
   std::vector<float> orient_conf;   // orient_k per item: every candidate's conf, ascending turn
@@ -622,7 +623,8 @@ struct Engine {
                     const void* kvmem, float* logits_out, int logits_ld, const int* done_tok = nullptr, int done_col = 0);
 
   // crops u8 [N][32][128][3] (device) -> logits f32 [N][26][95], ids i32 [N][26], prob f32 [N][26], conf f32 [N] (device); d_ar optional
-  void parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf);
+  // row_masks (device, [N] RowMask; DESIGN.md "Regions and per-row character sets"): crop n chooses its tokens under row_masks[n] instead of `charset`; null = charset
+  void parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks = nullptr);
   // The recogniser's outputs of `rows` crops share one device buffer (ids_dev), laid out [rows][26] ids | [rows][26] prob | [rows] conf, so that
   // one device-to-host copy and one collective carry all three.  Ensures the buffer (never inside a launch function).
   struct RecOut { int* ids; float* prob; float* conf; };
@@ -682,6 +684,14 @@ struct Engine {
     std::vector<int32_t> all_counts;   // with a communicator: crops per page of every rank [world][n]
     int cap = 0;                       // ... and the largest rank total (rows of the gathered payload per rank)
     int rows = 0;                      // rows of the recogniser's output block (RecOut) staged in h_ids[slot]: max(N, cap)
+    // regions (run_regions; DESIGN.md "Regions and per-row character sets"): the boxes are the caller's quads - no detector ran, `boxes` stays empty, every crop is
+    // a kind-1 crop of the table packer.  Crop c (page order, then the caller's order): its quad verbatim, its set index, and - when the sets differ - its row
+    // of the class-mask table ({blocked[3], 0}); row_masks empty = every crop reads under region_mask, by value
+    bool regions = false;
+    std::vector<float> region_quad;    // [N][8]
+    std::vector<int32_t> region_set;   // [N]
+    std::vector<uint32_t> row_masks;   // [N][4], or empty
+    ClassMask region_mask{};
   };
   PageBatch q1, q2;        // streamed batches: q1 = boxes known (recogniser enqueued or not), q2 = older, recogniser enqueued, results not yet returned
 
@@ -747,6 +757,16 @@ struct Engine {
   void run_pages(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results);
   void run_pages_v(const ttr_page* pages, int n, std::vector<Result>& results);   // pages of different sizes and strides that share one canvas
   void run_batch(PageBatch& B, std::vector<Result>& results);
+  // Regions (DESIGN.md "Regions and per-row character sets"): n caller-given quads on n_pages device pages of any sizes -> the packer and the recogniser, no
+  // detector; synchronous.  Every refusal happens before anything is enqueued.
+  void run_regions(const ttr_page* pages, int n_pages, const ttr_region* regions, int n, const uint32_t* sets, int n_sets, std::vector<Result>& results);
+  // set_of[n] (-1 = the engine's own set) over sets[n_sets][3] -> the rows' blocked-complement masks: `table` [n][4] when they differ, else empty and `one` = the
+  // mask they share (the by-value path).  Refuses a set index out of range, a mask without bit 0 and - a row that restricts - a bf16 engine.
+  void resolve_row_masks(const char* what, const int32_t* set_of, int n, const uint32_t* sets, int n_sets, std::vector<uint32_t>& table, ClassMask& one) const;
+  // the table through the pinned staging of slot sl to row_masks_dev (one copy on `stream`); returns the device table, or null for an empty one
+  const RowMask* stage_row_masks(const std::vector<uint32_t>& table, int sl);
+  DevBuf row_masks_dev;
+  PinnedBuf h_row_masks[2];
 
   // Latency mode (the reference's 6-thread fan-out over chunks of the crop batch, tuatara.cpp:450-485, across
   // GPUs): rank 0 detects and packs the crop batch, the batch is broadcast, rank r recognises the contiguous shard r of

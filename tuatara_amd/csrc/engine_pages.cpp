@@ -363,7 +363,7 @@ void Engine::pack_batch_crops(const PageBatch& B, int sl) {
   const Page& P0 = B.pages[0];
   const size_t page_bytes = (size_t)P0.h * P0.w * 3;
   const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
-  if (cfg.crop_mode != TTR_CROP_RECTIFIED) {
+  if (cfg.crop_mode != TTR_CROP_RECTIFIED && !B.regions) {   // (a region is a kind-1 crop whatever the mode)
     if (B.mixed) { launch_pack_crops_pages(table, rects_dev.as<int>(), crops.as<uint8_t>(), B.N, stream); TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream)); }
     else launch_pack_crops(P0.data, page_bytes, P0.stride, rects_dev.as<int>(), crops.as<uint8_t>(), B.N, stream);
     return;
@@ -605,6 +605,11 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (cfg.lines) group_batch_lines(B, sl, line_words);               // text lines: from the boxes alone, so inside the packing stage (DESIGN.md "Text lines")
     if (cfg.blocks) group_batch_blocks(B, sl, line_words);             // text blocks: directly behind, from the lines' side block on the device (DESIGN.md "Text blocks")
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
+    if (B.regions) {   // the caller's sets: one mask by value (the engine's own path), or the rows' table through the slot's pinned staging (one copy, no launch)
+      struct SetScope { ClassMask& c; ClassMask old; ~SetScope() { c = old; } } set_scope{charset, charset};
+      charset = B.region_mask;
+      parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, stage_row_masks(B.row_masks, sl));
+    } else
     parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf);
     if (T) {   // the twins as a pass of their own (turn 0 keeps its batch, and with it its bits), then the choice, in place in the standard block
       parseq_forward(crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, logits.as<float>(), nullptr, cand.ids, cand.prob, cand.conf);
@@ -679,6 +684,16 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
         r.page_orient = o_page[pg];
       }
     }
+    if (B.regions) {   // the caller's quads verbatim, their corners' extremes, their set indices
+      r.quad.assign(&B.region_quad[(size_t)c0 * 8], &B.region_quad[(size_t)(c0 + cnt) * 8]);
+      r.set.assign(&B.region_set[c0], &B.region_set[c0 + cnt]);
+      for (int k = 0; k < cnt; ++k) {
+        r.text.push_back(tok.decode(&rows.ids[(size_t)(c0 + k) * 26], 26));
+        float bb[4];
+        region_bbox(&r.quad[(size_t)k * 8], bb);
+        r.bbox.insert(r.bbox.end(), bb, bb + 4);
+      }
+    } else
     for (int k = 0; k < cnt; ++k) {
       r.text.push_back(tok.decode(&rows.ids[(size_t)(c0 + k) * 26], 26));   // :486-505
       float bb[4];
@@ -805,6 +820,105 @@ void Engine::run_batch(PageBatch& B, std::vector<Result>& results) {
   if (verbose) std::cout << "Running tokenizer..." << std::endl;
   { RangeScope r("ttr:finish"); finish(B, results); }
   if (verbose) std::cout << "Elapsed time: " << (now_us() - th0) * 1e-6 << " seconds " << std::endl;
+}
+
+void Engine::resolve_row_masks(const char* what, const int32_t* set_of, int n, const uint32_t* sets, int n_sets, std::vector<uint32_t>& table, ClassMask& one) const {
+  const std::string w(what);
+  if (n_sets < 0 || (n_sets > 0 && !sets) || (n > 0 && !set_of)) throw std::runtime_error("null argument");
+  std::vector<ClassMask> cms((size_t)n_sets);
+  for (int s = 0; s < n_sets; ++s) {
+    if (!(sets[3 * (size_t)s] & 1u)) throw std::runtime_error(w + ": set " + std::to_string(s) + ": bit 0 (the end of the text) must be set");
+    for (int i = 0; i < 3; ++i) cms[s].blocked[i] = ~sets[3 * (size_t)s + i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);   // 95 classes
+  }
+  table.assign((size_t)n * 4, 0u);
+  one = charset;
+  bool same = true, restricts = false;
+  for (int i = 0; i < n; ++i) {
+    if (set_of[i] < -1 || set_of[i] >= n_sets)
+      throw std::runtime_error(w + ": item " + std::to_string(i) + " names set " + std::to_string(set_of[i]) + ", the call holds " + std::to_string(n_sets) + " (-1 = the engine's own)");
+    const ClassMask& m = set_of[i] < 0 ? charset : cms[(size_t)set_of[i]];
+    for (int k = 0; k < 3; ++k) table[4 * (size_t)i + k] = m.blocked[k];
+    if (i == 0) one = m;
+    same = same && !memcmp(m.blocked, one.blocked, sizeof one.blocked);
+    restricts = restricts || m.restricts();
+  }
+  if (restricts && prec == kBF16)
+    throw std::runtime_error(w + ": a character set needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which take no class mask");
+  if (same) table.clear();
+}
+
+const RowMask* Engine::stage_row_masks(const std::vector<uint32_t>& table, int sl) {
+  if (table.empty()) return nullptr;
+  const size_t bytes = table.size() * 4;
+  h_row_masks[sl & 1].ensure(bytes); row_masks_dev.ensure(bytes);
+  memcpy(h_row_masks[sl & 1].p, table.data(), bytes);
+  TTR_HIP_CHECK(hipMemcpyAsync(row_masks_dev.p, h_row_masks[sl & 1].p, bytes, hipMemcpyHostToDevice, stream));
+  return row_masks_dev.as<RowMask>();
+}
+
+void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* regions, int n, const uint32_t* sets, int n_sets, std::vector<Result>& results) {
+  const char* what = "regions";
+  // ---- every refusal, before anything is enqueued or changed
+  if (n_pages < 0 || n < 0 || (n_pages > 0 && !pages) || (n > 0 && !regions)) throw std::runtime_error("null argument");
+  refuse_while_streaming(what);
+  if (comm) throw std::runtime_error("regions: a communicator is attached: regions are read by one engine alone (ttr_engine_attach_comm(e, NULL) first)");
+  if (cfg.orient || cfg.lines || cfg.chars || cfg.blocks)
+    throw std::runtime_error(std::string("regions: the engine has ") + (cfg.orient ? "orient" : cfg.lines ? "lines" : cfg.chars ? "chars" : "blocks") +
+                             " set: that layer reads the detector's boxes (group regions with ttr_group_lines / ttr_group_blocks on their quads)");
+  PageBatch B;
+  B.n = n_pages; B.mixed = true; B.regions = true; B.slot = 0;
+  B.pages.resize((size_t)n_pages);
+  for (int i = 0; i < n_pages; ++i) {
+    const long long stride = pages[i].row_stride ? (long long)pages[i].row_stride : (long long)pages[i].w * 3;
+    if (!pages[i].data || pages[i].h <= 0 || pages[i].w <= 0 || stride < (long long)pages[i].w * 3 || stride > 0x7fffffffLL) throw std::runtime_error("Error reading image from file");
+    // (no canvas: the table row's resize geometry is never read by the packers; the identity keeps it well defined)
+    B.pages[i] = Page{pages[i].data, pages[i].h, pages[i].w, (int)stride, CanvasGeom{pages[i].h, pages[i].w, pages[i].h, pages[i].w, 1.f}};
+  }
+  std::vector<int32_t> set_of((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const ttr_region& R = regions[i];
+    if (R.page < 0 || R.page >= n_pages) throw std::runtime_error("regions: region " + std::to_string(i) + " names page " + std::to_string(R.page) + ", the call holds " + std::to_string(n_pages));
+    if (!region_quad_ok(R.quad)) throw std::runtime_error("regions: region " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+    if (cfg.strict_crops && !region_inside(R.quad, pages[R.page].h, pages[R.page].w))
+      throw std::runtime_error("regions: region " + std::to_string(i) + " has a corner outside page " + std::to_string(R.page) + "'s pixel edges (strict_crops = 1)");
+    set_of[i] = R.set;
+  }
+  std::vector<uint32_t> table;
+  ClassMask one{};
+  resolve_row_masks(what, set_of.data(), n, sets, n_sets, table, one);
+  results.assign((size_t)n_pages, Result());
+  if (n_pages == 0) return;
+  // ---- the batch: crops by page, then in the caller's order within the page (a stable counting sort)
+  std::vector<int> first((size_t)n_pages + 1, 0), at;
+  for (int i = 0; i < n; ++i) first[(size_t)regions[i].page + 1]++;
+  for (int p = 0; p < n_pages; ++p) first[p + 1] += first[p];
+  at.assign(first.begin(), first.end() - 1);
+  B.N = n;
+  B.page_of.assign((size_t)n, 0); B.rects.assign((size_t)n * 5, 0); B.coef.assign((size_t)n * 8, 0);
+  B.region_quad.assign((size_t)n * 8, 0.f); B.region_set.assign((size_t)n, 0);
+  if (!table.empty()) B.row_masks.assign((size_t)n * 4, 0u);
+  B.region_mask = one;
+  for (int i = 0; i < n; ++i) {
+    const ttr_region& R = regions[i];
+    const size_t c = (size_t)at[R.page]++;
+    B.page_of[c] = R.page;
+    int* rc = &B.rects[5 * c];
+    rc[0] = 0; rc[1] = 0; rc[2] = 1; rc[3] = 1; rc[4] = R.page;   // (kind 1 reads the coefficients alone; the rectangle only has to be non-empty)
+    int64_t fx[6];
+    region_coef(R.quad, fx);
+    B.coef[8 * c] = 1;
+    for (int k = 0; k < 6; ++k) B.coef[8 * c + 1 + k] = fx[k];
+    memcpy(&B.region_quad[8 * c], R.quad, 8 * sizeof(float));
+    B.region_set[c] = R.set;
+    if (!table.empty()) memcpy(&B.row_masks[4 * c], &table[4 * (size_t)i], 16);
+  }
+  const double th0 = now_us();
+  for (int k = 0; k < 3; ++k) TTR_HIP_CHECK(hipEventRecord(ev[k], stream));   // no detector: its two stage times of this call are zero
+  if (n > 0) upload_page_table(B.pages, 0);
+  host_us[0] = host_us[1] = host_us[2] = host_us[3] = 0.f;
+  { RangeScope r("ttr:recog_enqueue"); recog_enqueue(B); }
+  host_us[4] = (float)(now_us() - th0);
+  { RangeScope r("ttr:finish"); finish(B, results); }
 }
 
 void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results) {

@@ -134,7 +134,7 @@ void Engine::decoder_tail(const void* sa, int N, int R, const float* resid_pos, 
   ln_gemm(tgt, "decoder.norm", 1e-5f, t384, pq.at("head"), rows, nullptr, 0, kActNone, logits_out, logits_ld);
 }
 
-void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf) {
+void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks) {
   if (N <= 0) return;
   // A very large crop batch (64 pages of ~150 boxes) goes through in even groups: the refinement pass's widest planes tensor (26 rows per crop x 1536 x 6 bytes)
   // must stay inside the 2 GiB window of 32-bit buffer offsets (8962 crops), and the workspaces stay bounded.  Crops are independent (batch-invariant logits,
@@ -145,13 +145,13 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
     for (int g0 = 0; g0 < N; g0 += per) {
       const int n = std::min(per, N - g0);
       parseq_forward(d_crops + (size_t)g0 * 32 * 128 * 3, n, d_logits + (size_t)g0 * 26 * 95, d_ar ? d_ar + (size_t)g0 * 26 * 95 : nullptr, d_ids + (size_t)g0 * 26,
-                     d_prob + (size_t)g0 * 26, d_conf + g0);
+                     d_prob + (size_t)g0 * 26, d_conf + g0, row_masks ? row_masks + g0 : nullptr);   // (rows are never permuted: a group's masks start where its crops do)
     }
     return;
   }
   // a character set (DESIGN.md "Character sets") constrains every place below that chooses a token, by value: the argmax launches, the argmax folded into
   // dec_embed_ln / the skinny self_kv linear, and the final decode.  The bf16 engine chooses inside gemm_sk.hip and dec_fused.hip, which take no mask
-  if (charset.restricts() && prec == kBF16) throw std::runtime_error("parseq_forward: a character set needs an f16x4 or f32 engine (the bf16 engine's kernels take no class mask)");
+  if ((charset.restricts() || row_masks) && prec == kBF16) throw std::runtime_error("parseq_forward: a character set needs an f16x4 or f32 engine (the bf16 engine's kernels take no class mask)");
   prof_stage = 1;
   const int M = N * 128, E = 384;
   const int patch_ld = pq.at("patch").k;   // 96, or 128 in bf16 mode (zero-padded)
@@ -367,7 +367,7 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
       ConvParams p{};
       p.tok = tk; p.tok_ld = 26; p.tok_col = i; p.tok_emb = emb; p.tok_max = 96; p.tok_pos = i > 0 ? posq + (size_t)(i - 1) * E : nullptr;
       if (pend_argmax >= 0) {
-        p.tok_logits = ar + (size_t)pend_argmax * 95; p.tok_logits_ld = 26 * 95; p.tok_C = 95; p.done_count = early ? ar_done.as<int>() : nullptr; p.tok_eos = 0; p.tok_mask = charset;
+        p.tok_logits = ar + (size_t)pend_argmax * 95; p.tok_logits_ld = 26 * 95; p.tok_C = 95; p.done_count = early ? ar_done.as<int>() : nullptr; p.tok_eos = 0; p.tok_mask = charset; p.tok_row_masks = row_masks;
         pend_argmax = -1;
       }
       p.ln_gamma = gc; p.ln_beta = bc; p.ln_eps = 1e-5f;
@@ -381,7 +381,7 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
     } else if (dec_split) {
       if (pend_argmax >= 0) {   // column i's token = argmax of step i - 1's logits, found by this kernel's waves (one launch less per step)
         launch_dec_embed_ln(prec, tk, emb, posq, gc, bc, 1e-5f, dpa, N, i, i + 1, stream, cur_skip, cur_skip_n, 3,
-                            ar + (size_t)pend_argmax * 95, 26 * 95, 95, early ? ar_done.as<int>() : nullptr, 0, charset);
+                            ar + (size_t)pend_argmax * 95, 26 * 95, 95, early ? ar_done.as<int>() : nullptr, 0, charset, row_masks);
         pend_argmax = -1;
       } else launch_dec_embed_ln(prec, tk, emb, posq, gc, bc, 1e-5f, dpa, N, i, i + 1, stream, cur_skip, cur_skip_n, 3);
       sgemm(pq.at("self_kv"), dpa, N, (char*)kvcache + (size_t)i * 768 * 4, 26 * 768, kActNone, 0);
@@ -404,7 +404,7 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
     if (i + 1 < 26 && !tok_fuse) {
       // the step's argmax: its own launch where the host is about to look at the counter (or nothing follows), else left to the next step's first kernel
       if (dec_split && tn.argmax_fold && !host_check) pend_argmax = i;
-      else launch_argmax(ar + (size_t)i * 95, 26 * 95, 95, tk, 26, i + 1, N, stream, cur_skip, cur_skip_n, early ? ar_done.as<int>() : nullptr, 0, charset);
+      else launch_argmax(ar + (size_t)i * 95, 26 * 95, 95, tk, 26, i + 1, N, stream, cur_skip, cur_skip_n, early ? ar_done.as<int>() : nullptr, 0, charset, row_masks);
     }
     if (host_check) {
       h_ar_done.ensure(64);
@@ -424,7 +424,7 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
   launch_dec_self_attn(prec, qself.as<float>(), kvcache, tk, att, N, 26, 0, 1, stream);
   decoder_tail(att, N, 26, posq, 26, tgt, t384, d384b, d1536, kvmem, d_logits, 95);
   }
-  launch_decode_conf(d_logits, N, d_ids, d_prob, d_conf, stream, charset);   // the final argmax with each id's probability and the word's confidence (decode_conf.hip)
+  launch_decode_conf(d_logits, N, d_ids, d_prob, d_conf, stream, charset, row_masks);   // the final argmax with each id's probability and the word's confidence (decode_conf.hip)
 }
 
 }  // namespace ttr

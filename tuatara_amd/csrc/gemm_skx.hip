@@ -37,9 +37,12 @@ constexpr int SKX_BN = 32, SKX_DEPTH = 3;
 // parked in LDS by the workgroup itself (its 16 rows: 24 KB of reads, the arithmetic of layernorm_planes_kernel to the operation), while its first
 // weight fragments are on their way.  An AR step's three LayerNorms (norm1 -> cross-attention query, norm2 -> ffn1, the final norm -> head) lose
 // their launches - three of fourteen dependent launches per step, each a kernel of ~5 us and a hand-over of ~4.
-template <int RB, bool LNP = false>
+// ROWM (LNP, the token prologue): every row chooses its token under its own class mask, ConvParams::tok_row_masks[m] (DESIGN.md "Regions and per-row character
+// sets").  An instantiation of its own, picked by the launcher when the table is there: the default one keeps the registers and the code of before.
+template <int RB, bool LNP = false, bool ROWM = false>
 __global__ __launch_bounds__(256) void gemm_skx_kernel(ConvParams p) {
   static_assert(!LNP || RB == 1, "the LayerNorm prologue is the 16-row form's");
+  static_assert(!ROWM || LNP, "row masks belong to the token prologue");
   __shared__ __attribute__((aligned(16))) float part[4][2][RB][64][4];    // the four waves' partial tiles
   __shared__ int skip_now;
   if (p.skip) {   // AR early exit, decided once per WORKGROUP, before the barriers
@@ -136,6 +139,14 @@ __global__ __launch_bounds__(256) void gemm_skx_kernel(ConvParams p) {
         if (p.tok_C <= 128) {                                                // (PARSeq: 95 classes) two values per lane, the four rows' loads in flight together
           float t0[4], t1[4];
           const bool ok0 = lane < p.tok_C && p.tok_mask.allows(lane), ok1 = lane + 64 < p.tok_C && p.tok_mask.allows(lane + 64);   // (a blocked class takes no part)
+          bool rok0[4], rok1[4];                                             // ROWM: the same two tests under each row's own mask (a dead row borrows row m0's)
+          if constexpr (ROWM) {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const RowClassMask rm = row_class_mask(p.tok_mask, p.tok_row_masks, live[rr] ? mrow[rr] : m0);
+              rok0[rr] = lane < p.tok_C && rm.allows(lane); rok1[rr] = lane + 64 < p.tok_C && rm.allows(lane + 64);
+            }
+          }
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {
             const float* lg = p.tok_logits + (int64_t)(live[rr] ? mrow[rr] : m0) * p.tok_logits_ld;
@@ -145,14 +156,19 @@ __global__ __launch_bounds__(256) void gemm_skx_kernel(ConvParams p) {
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {                                   // (the loop's order: cc = lane, then lane + 64; strict > keeps the first maximum)
             best[rr] = -INFINITY; bi[rr] = 0x7fffffff;
-            if (ok0 && t0[rr] > best[rr]) { best[rr] = t0[rr]; bi[rr] = lane; }
-            if (ok1 && t1[rr] > best[rr]) { best[rr] = t1[rr]; bi[rr] = lane + 64; }
+            const bool k0 = ROWM ? rok0[rr] : ok0, k1 = ROWM ? rok1[rr] : ok1;
+            if (k0 && t0[rr] > best[rr]) { best[rr] = t0[rr]; bi[rr] = lane; }
+            if (k1 && t1[rr] > best[rr]) { best[rr] = t1[rr]; bi[rr] = lane + 64; }
           }
         } else {
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {
             const float* lg = p.tok_logits + (int64_t)(live[rr] ? mrow[rr] : m0) * p.tok_logits_ld;
             best[rr] = -INFINITY; bi[rr] = 0x7fffffff;
+            if constexpr (ROWM) {
+              const RowClassMask rm = row_class_mask(p.tok_mask, p.tok_row_masks, live[rr] ? mrow[rr] : m0);
+              for (int cc = lane; cc < p.tok_C; cc += 64) { const float t = lg[cc]; if (rm.allows(cc) && t > best[rr]) { best[rr] = t; bi[rr] = cc; } }
+            } else
             for (int cc = lane; cc < p.tok_C; cc += 64) { const float t = lg[cc]; if (p.tok_mask.allows(cc) && t > best[rr]) { best[rr] = t; bi[rr] = cc; } }
           }
         }
@@ -334,7 +350,9 @@ void launch_gemm_skx(const ConvParams& p_in, hipStream_t s) {
   const ConvParams p = with_range_ctx(p_in);
   if (p.ln_in || p.tok) {
     if (!gemm_skx_ln_eligible(p)) throw std::runtime_error("gemm_skx: LayerNorm prologue: shape not supported");
-    hipLaunchKernelGGL((gemm_skx_kernel<1, true>), dim3((p.Cout + SKX_BN - 1) / SKX_BN, (p.M + 15) / 16), dim3(256), 0, s, p);
+    const dim3 grid((p.Cout + SKX_BN - 1) / SKX_BN, (p.M + 15) / 16);
+    if (p.tok_row_masks && p.tok_logits) hipLaunchKernelGGL((gemm_skx_kernel<1, true, true>), grid, dim3(256), 0, s, p);   // (per-row class masks: their own instantiation)
+    else hipLaunchKernelGGL((gemm_skx_kernel<1, true>), grid, dim3(256), 0, s, p);
     return;
   }
   if (!gemm_skx_eligible(p)) throw std::runtime_error("gemm_skx: shape not supported");

@@ -90,6 +90,33 @@ void deskew_fixed(const double coef[6], int64_t fixed[6]) {
   for (int i = 0; i < 6; ++i) fixed[i] = (int64_t)std::llrint(coef[i] * 65536.);
 }
 
+// ---------------------------------------------------------------- regions (DESIGN.md "Regions and per-row character sets")
+bool region_quad_ok(const float* q) {
+  for (int i = 0; i < 8; ++i) if (!std::isfinite(q[i]) || !(std::fabs(q[i]) < 32768.f)) return false;
+  return true;
+}
+
+void region_coef(const float* q, int64_t fixed[6]) {
+  const Pt2f p[4] = {{q[0], q[1]}, {q[2], q[3]}, {q[4], q[5]}, {q[6], q[7]}};
+  double cf[6];
+  quad_coef(p, cf);
+  deskew_fixed(cf, fixed);
+}
+
+void region_bbox(const float* q, float bbox[4]) {
+  bbox[0] = bbox[2] = q[0]; bbox[1] = bbox[3] = q[1];
+  for (int i = 1; i < 4; ++i) {
+    bbox[0] = std::min(bbox[0], q[2 * i]); bbox[1] = std::min(bbox[1], q[2 * i + 1]);
+    bbox[2] = std::max(bbox[2], q[2 * i]); bbox[3] = std::max(bbox[3], q[2 * i + 1]);
+  }
+}
+
+bool region_inside(const float* q, int h, int w) {
+  for (int i = 0; i < 4; ++i)
+    if (!(q[2 * i] >= -0.5f && q[2 * i] <= (float)w - 0.5f && q[2 * i + 1] >= -0.5f && q[2 * i + 1] <= (float)h - 0.5f)) return false;
+  return true;
+}
+
 // ---------------------------------------------------------------- word orientation (DESIGN.md "Word orientation")
 void box_edge_quad(int x0, int y0, int x1, int y1, Pt2f quad[4]) {
   const float l = (float)x0 - 0.5f, t = (float)y0 - 0.5f, r = (float)x1 - 0.5f, b = (float)y1 - 0.5f;

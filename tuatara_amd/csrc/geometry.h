@@ -31,6 +31,14 @@ void deskew_fixed(const double coef[6], int64_t fixed[6]);
 // the quad -> coefficients step of deskew_quad on its own (any quad tl, tr, br, bl): the sampler's rule in double, in deskew_quad's order
 void quad_coef(const Pt2f quad[4], double coef[6]);
 
+// Regions (DESIGN.md "Regions and per-row character sets"): a caller's quad tl, tr, br, bl as 8 floats in image pixels.  region_quad_ok: every coordinate is
+// finite and has |x| < 32768 (the bound of the other quad rules).  region_coef: quad_coef on the floats, then deskew_fixed - the kind-1 crop's coefficients.
+// region_bbox: {min x, min y, max x, max y} of the four corners.  region_inside: every corner within the page's pixel edges [-0.5, w - 0.5] x [-0.5, h - 0.5].
+bool region_quad_ok(const float* quad8);
+void region_coef(const float* quad8, int64_t fixed[6]);
+void region_bbox(const float* quad8, float bbox[4]);
+bool region_inside(const float* quad8, int h, int w);
+
 // Word orientation (ttr_config.orient; DESIGN.md "Word orientation").  A turn t = the quarter turns clockwise by which the word lies on the
 // page.  box_edge_quad: the crop_mode = 0 quad of a clamped boundingRect [x0, x1) x [y0, y1) as pixel edges (rect_points' coordinates:
 // pixel centres at integers).  turn_coef: the fixed-point coefficients of the turned quad Q_t[k] = Q[(k + t) mod 4] (quad_coef +

@@ -184,7 +184,7 @@ void set_attn_impl(int v);                                                      
 // content token embedding + norm_c.  rows (n, i) for i in [i0,i1): out row n*(i1-i0)+(i-i0)
 void launch_dec_embed_ln(Precision prec, int* tokens, const float* emb, const float* pos_q, const float* gamma, const float* beta, float eps,
                          void* out, int N, int i0, int i1, hipStream_t s, const int* skip = nullptr, int skip_n = 0, int planes = 0,
-                         const float* prev_logits = nullptr, int prev_ld = 0, int C = 0, int* done_count = nullptr, int eos = 0, ClassMask cm = ClassMask{});   // prev_logits: column i0's token = argmax of these rows first (an AR step)   // planes = 3 (fp32 engines): f16 triple planes out
+                         const float* prev_logits = nullptr, int prev_ld = 0, int C = 0, int* done_count = nullptr, int eos = 0, ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);   // row_masks: crop n chooses under row_masks[n] instead of cm (common.h)   // prev_logits: column i0's token = argmax of these rows first (an AR step)   // planes = 3 (fp32 engines): f16 triple planes out
 // self attention of R query rows per crop against the K/V cache [N][26][768].
 // mode 0 (AR): R == 1, query index qi0, keys 0..qi0.  mode 1 (refine): R == 26, cloze mask + EOS key padding.
 // skip / skip_n: the kernel returns at once when *skip >= skip_n (AR early exit, ConvParams::skip); bf16 per-row kernels only
@@ -196,12 +196,13 @@ void launch_dec_cross_attn(Precision prec, const void* q, const void* kvmem, voi
 // tokens[n*tok_ld + col] = argmax over C of logits[n*ld ..]
 // skip / skip_n: AR early exit; done_count: incremented once per crop whose FIRST EOS (id eos, columns 1 .. col) is the token formed here
 void launch_argmax(const float* logits, int ld, int C, int* tokens, int tok_ld, int col, int N, hipStream_t s, const int* skip = nullptr, int skip_n = 0,
-                   int* done_count = nullptr, int eos = 0, ClassMask cm = ClassMask{});   // cm: classes that take no part (DESIGN.md "Character sets")
+                   int* done_count = nullptr, int eos = 0, ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);   // cm: classes that take no part (DESIGN.md "Character sets"); row_masks: row n's own mask instead (common.h)
 void launch_fill_i32(int* p, int value, int n, int stride, hipStream_t s);
 // decode_conf.hip: the refinement pass's final decode - logits f32 [N][26][95] -> ids [N][26] (bit-identical to launch_argmax's), prob f32 [N][26]
 // (softmax value of each id), conf f32 [N] (product over the text's characters and the EOS; DESIGN.md "Recognition confidence")
 // cm (DESIGN.md "Character sets"): a blocked class is -inf in the comparison and adds exactly 0 to the exponential sum; the default blocks none
-void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s, ClassMask cm = ClassMask{});
+// row_masks (DESIGN.md "Regions and per-row character sets"): crop n decodes under row_masks[n] instead of cm
+void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s, ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);
 // orient.hip: word orientation (DESIGN.md "Word orientation") - per page, the chosen candidate of every word and the page vote.  ids / prob / conf: the
 // standard block of the batch (turn 0), overwritten in place with the chosen readings; cids / cprob / cconf: the (K - 1) N twin rows, candidate-major;
 // first [pages + 1]: each page's first word; side: [N] int32 turn | [N][K] f32 candidate conf | [pages] int32 page turn.  K = 2 or 4.

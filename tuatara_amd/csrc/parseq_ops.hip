@@ -220,7 +220,7 @@ void launch_attn_enc(Precision prec, const void* qkv, void* out, int N, hipStrea
 template <typename T>
 __global__ void dec_embed_ln_kernel(int* __restrict__ tokens, const float* __restrict__ emb, const float* __restrict__ pos_q,
                                     const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* __restrict__ out, int N, int i0, int i1,
-                                    const int* skip, int skip_n, int planes, const float* __restrict__ prev_logits, int prev_ld, int C, int* done_count, int eos, ClassMask cm, unsigned* range_flag, unsigned range_tag) {
+                                    const int* skip, int skip_n, int planes, const float* __restrict__ prev_logits, int prev_ld, int C, int* done_count, int eos, ClassMask cm, const RowMask* __restrict__ row_masks, unsigned* range_flag, unsigned range_tag) {
   RangeWatch rw;   // (split.h)
   if (skip && __builtin_nontemporal_load(skip) >= skip_n) return;   // AR early exit (see ConvParams::skip)
   const int R = i1 - i0;
@@ -230,8 +230,9 @@ __global__ void dec_embed_ln_kernel(int* __restrict__ tokens, const float* __res
   int tok;
   if (prev_logits) {
     const float* x = prev_logits + (int64_t)n * prev_ld;
+    const RowClassMask rm = row_class_mask(cm, row_masks, n);   // (the crop's own set, when a row table travels with the launch)
     float best = -INFINITY; int bi = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) { float v = x[c]; if (cm.allows(c) && v > best) { best = v; bi = c; } }   // (a blocked class takes no part: DESIGN.md "Character sets")
+    for (int c = lane; c < C; c += 64) { float v = x[c]; if (rm.allows(c) && v > best) { best = v; bi = c; } }   // (a blocked class takes no part: DESIGN.md "Character sets")
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       float ov = __shfl_xor(best, o); int oi = __shfl_xor(bi, o);
@@ -276,7 +277,7 @@ template <int NPL>
 __global__ __launch_bounds__(256) void dec_embed_ln_planes_kernel(int* __restrict__ tokens, const float* __restrict__ emb, const float* __restrict__ pos_q,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta, float eps, f16* __restrict__ out, int N,
                                                                   int i0, int i1, const int* skip, int skip_n, const float* __restrict__ prev_logits, int prev_ld, int C,
-                                                                  int* done_count, int eos, ClassMask cm, unsigned* range_flag, unsigned range_tag) {
+                                                                  int* done_count, int eos, ClassMask cm, const RowMask* __restrict__ row_masks, unsigned* range_flag, unsigned range_tag) {
   RangeWatch rw;   // (split.h)
   if (skip && __builtin_nontemporal_load(skip) >= skip_n) return;
   const int R = i1 - i0;
@@ -286,8 +287,9 @@ __global__ __launch_bounds__(256) void dec_embed_ln_planes_kernel(int* __restric
   int tok;
   if (prev_logits) {
     const float* x = prev_logits + (int64_t)n * prev_ld;
+    const RowClassMask rm = row_class_mask(cm, row_masks, n);   // (the crop's own set, when a row table travels with the launch)
     float best = -INFINITY; int bi = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) { float v = x[c]; if (cm.allows(c) && v > best) { best = v; bi = c; } }   // (a blocked class takes no part: DESIGN.md "Character sets")
+    for (int c = lane; c < C; c += 64) { float v = x[c]; if (rm.allows(c) && v > best) { best = v; bi = c; } }   // (a blocked class takes no part: DESIGN.md "Character sets")
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       float ov = __shfl_xor(best, o); int oi = __shfl_xor(bi, o);
@@ -330,15 +332,15 @@ __global__ __launch_bounds__(256) void dec_embed_ln_planes_kernel(int* __restric
 
 void launch_dec_embed_ln(Precision prec, int* tokens, const float* emb, const float* pos_q, const float* gamma, const float* beta, float eps,
                          void* out, int N, int i0, int i1, hipStream_t s, const int* skip, int skip_n, int planes,
-                         const float* prev_logits, int prev_ld, int C, int* done_count, int eos, ClassMask cm) {
+                         const float* prev_logits, int prev_ld, int C, int* done_count, int eos, ClassMask cm, const RowMask* row_masks) {
   int rows = N * (i1 - i0);
   if (rows <= 0) return;
   if (prev_logits && (i1 != i0 + 1 || i0 < 1)) throw std::runtime_error("dec_embed_ln: the folded argmax belongs to one AR step's column");
   dim3 grid((rows + 3) / 4);
   if (prec != kBF16 && planes == 3 && !(((uintptr_t)emb | (uintptr_t)pos_q | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15))
-    hipLaunchKernelGGL(dec_embed_ln_planes_kernel<3>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (f16*)out, N, i0, i1, skip, skip_n, prev_logits, prev_ld, C, done_count, eos, cm, range_ctx().flag, range_ctx().tag);
-  else if (prec == kBF16) hipLaunchKernelGGL(dec_embed_ln_kernel<bf16>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (bf16*)out, N, i0, i1, skip, skip_n, 0, prev_logits, prev_ld, C, done_count, eos, cm, range_ctx().flag, range_ctx().tag);
-  else hipLaunchKernelGGL(dec_embed_ln_kernel<float>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (float*)out, N, i0, i1, skip, skip_n, planes, prev_logits, prev_ld, C, done_count, eos, cm, range_ctx().flag, range_ctx().tag);
+    hipLaunchKernelGGL(dec_embed_ln_planes_kernel<3>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (f16*)out, N, i0, i1, skip, skip_n, prev_logits, prev_ld, C, done_count, eos, cm, row_masks, range_ctx().flag, range_ctx().tag);
+  else if (prec == kBF16) hipLaunchKernelGGL(dec_embed_ln_kernel<bf16>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (bf16*)out, N, i0, i1, skip, skip_n, 0, prev_logits, prev_ld, C, done_count, eos, cm, row_masks, range_ctx().flag, range_ctx().tag);
+  else hipLaunchKernelGGL(dec_embed_ln_kernel<float>, grid, dim3(256), 0, s, tokens, emb, pos_q, gamma, beta, eps, (float*)out, N, i0, i1, skip, skip_n, planes, prev_logits, prev_ld, C, done_count, eos, cm, row_masks, range_ctx().flag, range_ctx().tag);
 }
 
 // ------------------------------------------------------------------ decoder self attention
@@ -751,13 +753,14 @@ void launch_dec_cross_attn(Precision prec, const void* q, const void* kvmem, voi
 
 // ------------------------------------------------------------------ argmax (first maximal index, like torch.argmax on CPU; among the classes cm allows)
 __global__ void argmax_kernel(const float* __restrict__ logits, int ld, int C, int* __restrict__ tokens, int tok_ld, int col, int N,
-                              const int* skip, int skip_n, int* done_count, int eos, ClassMask cm) {
+                              const int* skip, int skip_n, int* done_count, int eos, ClassMask cm, const RowMask* __restrict__ row_masks) {
   if (skip && __builtin_nontemporal_load(skip) >= skip_n) return;   // AR early exit (see ConvParams::skip)
   int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (n >= N) return;
+  const RowClassMask rm = row_class_mask(cm, row_masks, n);   // (row n's own set, when a row table travels with the launch)
   const float* x = logits + (int64_t)n * ld;
   float best = -INFINITY; int bi = 0x7fffffff;
-  for (int c = lane; c < C; c += 64) { float v = x[c]; if (cm.allows(c) && v > best) { best = v; bi = c; } }   // (a blocked class takes no part: DESIGN.md "Character sets")
+  for (int c = lane; c < C; c += 64) { float v = x[c]; if (rm.allows(c) && v > best) { best = v; bi = c; } }   // (a blocked class takes no part: DESIGN.md "Character sets")
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     float ov = __shfl_xor(best, o); int oi = __shfl_xor(bi, o);
@@ -773,9 +776,9 @@ __global__ void argmax_kernel(const float* __restrict__ logits, int ld, int C, i
   }
 }
 
-void launch_argmax(const float* logits, int ld, int C, int* tokens, int tok_ld, int col, int N, hipStream_t s, const int* skip, int skip_n, int* done_count, int eos, ClassMask cm) {
+void launch_argmax(const float* logits, int ld, int C, int* tokens, int tok_ld, int col, int N, hipStream_t s, const int* skip, int skip_n, int* done_count, int eos, ClassMask cm, const RowMask* row_masks) {
   if (N <= 0) return;
-  hipLaunchKernelGGL(argmax_kernel, dim3((N + 3) / 4), dim3(256), 0, s, logits, ld, C, tokens, tok_ld, col, N, skip, skip_n, done_count, eos, cm);
+  hipLaunchKernelGGL(argmax_kernel, dim3((N + 3) / 4), dim3(256), 0, s, logits, ld, C, tokens, tok_ld, col, N, skip, skip_n, done_count, eos, cm, row_masks);
 }
 
 __global__ void fill_i32_kernel(int* p, int value, int n, int stride) {

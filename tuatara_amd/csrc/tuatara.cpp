@@ -95,6 +95,7 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
   ttr_confidence_from_probs(ttr_result_ids(r, i), ttr_result_prob(r, i), 26, cc, &nc, nullptr);
   o.char_conf.assign(cc, cc + nc);
   o.orient = 90 * ttr_result_orient(r, i);
+  o.region = ttr_result_sets(r) ? i : -1;   // (a region call returns one page's regions in the caller's order)
   const int32_t *ln = ttr_result_lines(r), *wd = ttr_result_words(r);
   o.line = ln ? ln[i] : -1;
   o.word = wd ? wd[i] : -1;
@@ -261,4 +262,48 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
                                                          std::string allowlist, std::string blocklist) {
   return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
                                 blocks ? 1 : -1, mixed_batches ? 1 : -1, allowlist, blocklist);
+}
+
+RegionSpec region_from_rect(int x0, int y0, int x1, int y1, std::string allowlist, std::string blocklist) {
+  RegionSpec r;
+  r.quad.assign(8, 0.f);
+  if (ttr_region_from_rect(x0, y0, x1, y1, r.quad.data()) != 0) { std::cerr << "tuatara: " << ttr_last_error() << std::endl; r.quad.clear(); }
+  r.allowlist = std::move(allowlist); r.blocklist = std::move(blocklist);
+  return r;
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions) {
+  // every list and quad is checked on the host before an engine is opened
+  std::vector<ttr_region> regs(regions.size());
+  std::vector<uint32_t> sets;
+  for (size_t i = 0; i < regions.size(); ++i) {
+    const RegionSpec& s = regions[i];
+    if (s.quad.size() != 8) { std::cerr << "tuatara: region " << i << ": a region is 8 floats (tl, tr, br, bl)" << std::endl; return {}; }
+    for (int k = 0; k < 8; ++k) regs[i].quad[k] = s.quad[k];
+    regs[i].page = 0; regs[i].set = -1;
+    if (s.allowlist.empty() && s.blocklist.empty()) continue;
+    uint32_t m[3];
+    if (ttr_charset_mask(s.allowlist.c_str(), s.blocklist.c_str(), m) < 0) { std::cerr << "tuatara: region " << i << ": " << ttr_last_error() << std::endl; return {}; }
+    regs[i].set = (int32_t)(sets.size() / 3);
+    sets.insert(sets.end(), m, m + 3);
+  }
+  ttr_engine* e = open_engine(weights_dir, outputs_dir, -1, -1, 0, -1, -1, -1);
+  if (!e) return {};
+  CharsetScope cs(e, std::string(), std::string());   // (the engine's own set for regions without lists: TUATARA_ALLOWLIST / TUATARA_BLOCKLIST; calls that share the engine take turns)
+  if (!cs.ok) return {};
+  if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
+    std::cerr << "Error reading image from file";
+    return {};
+  }
+  ttr_result* r = nullptr;
+  if (ttr_image_regions_to_data(e, image, rows, cols, row_stride ? (int)row_stride : cols * 3, regs.data(), (int)regs.size(), sets.empty() ? nullptr : sets.data(),
+                                (int)(sets.size() / 3), &r) != 0) {
+    std::cerr << "tuatara: " << ttr_last_error() << std::endl;
+    return {};
+  }
+  std::vector<OutputItemEx> out(ttr_result_count(r));
+  for (size_t i = 0; i < out.size(); ++i) fill(out[i], r, (int)i);
+  ttr_result_free(r);
+  return out;
 }

@@ -35,6 +35,11 @@ class Page(C.Structure):
     _fields_ = [("data", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("row_stride", C.c_int)]
 
 
+class Region(C.Structure):
+    """ttr_region: a quad tl, tr, br, bl in image pixels on page `page`, read under set `set` (-1 = the engine's own)"""
+    _fields_ = [("quad", C.c_float * 8), ("page", C.c_int32), ("set", C.c_int32)]
+
+
 # every symbol include/tuatara_hip.h declares: (name, restype, argtypes)
 _VP, _I, _F = C.c_void_p, C.c_int, C.c_float
 _PU8, _PF, _PI = C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int32)
@@ -121,6 +126,14 @@ SYMBOLS = [
     ("ttr_engine_set_charset", _I, [_VP, C.c_char_p, C.c_char_p]),
     ("ttr_engine_get_charset", _I, [_VP, C.POINTER(C.c_uint32)]),
     ("ttr_logits_confidence_masked", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _PI, _PF, _PF]),
+    ("ttr_region_from_rect", _I, [_I, _I, _I, _I, _PF]),
+    ("ttr_region_geometry", _I, [_PF, _I, _I, C.POINTER(C.c_int64), _PF, C.POINTER(C.c_int)]),
+    ("ttr_regions_to_data_dev", _I, [_VP, C.POINTER(Page), _I, C.POINTER(Region), _I, C.POINTER(C.c_uint32), _I, C.POINTER(_VP)]),
+    ("ttr_image_regions_to_data", _I, [_VP, _PU8, _I, _I, _I, C.POINTER(Region), _I, C.POINTER(C.c_uint32), _I, C.POINTER(_VP)]),
+    ("ttr_result_sets", _PI, [_VP]),
+    ("ttr_pack_regions", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _PU8]),
+    ("ttr_parseq_logits_sets", _I, [_VP, _PU8, _I, C.POINTER(C.c_uint32), _I, _PI, _PF, _PF, _PI]),
+    ("ttr_logits_confidence_sets", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _I, _PI, _PI, _PF, _PF]),
     ("ttr_craft_heatmap", _I, [_VP, _PU8, _I, _I, _PF]),
     ("ttr_ccl_boxes", _I, [_VP, _PF, _I, _I, _PF, _I, _PI]),
     ("ttr_resize_canvas", _I, [_VP, _PU8, _I, _I, _I, _PU8, C.c_size_t, _PI, _PI, _PF]),
@@ -334,6 +347,59 @@ def charset_mask(allow=None, deny=None) -> np.ndarray:
     if load().ttr_charset_mask(_charlist(allow), _charlist(deny), m) < 0:
         raise EngineError(load().ttr_last_error().decode("latin1"))
     return np.array(list(m), dtype=np.uint32)
+
+
+def region_from_rect(x0: int, y0: int, x1: int, y1: int) -> np.ndarray:
+    """The pixel-edge quad of the pixels [x0, x1) x [y0, y1) (ttr_region_from_rect, no GPU): f32 [8] tl, tr, br, bl, pixel centres at integers."""
+    q = np.zeros(8, np.float32)
+    if load().ttr_region_from_rect(int(x0), int(y0), int(x1), int(y1), _f(q)) < 0:
+        raise EngineError(load().ttr_last_error().decode("latin1"))
+    return q
+
+
+def region_geometry(quad, h: int = 0, w: int = 0):
+    """What a region call derives from one quad on the host (ttr_region_geometry, no GPU): (fixed int64 [6] - the sampler's coefficients in 2^-16 px -,
+    bbox f32 [4], inside - every corner within the pixel edges of an h x w page).  EngineError for a coordinate that is not finite or has |x| >= 32768."""
+    q = np.ascontiguousarray(quad, dtype=np.float32).ravel()
+    if q.size != 8:
+        raise ValueError("a quad is 8 floats (tl, tr, br, bl)")
+    fixed, bbox, inside = np.zeros(6, np.int64), np.zeros(4, np.float32), C.c_int(0)
+    if load().ttr_region_geometry(_f(q), int(h), int(w), fixed.ctypes.data_as(C.POINTER(C.c_int64)), _f(bbox), C.byref(inside)) < 0:
+        raise EngineError(load().ttr_last_error().decode("latin1"))
+    return fixed, bbox, bool(inside.value)
+
+
+def region_quad(region) -> np.ndarray:
+    """A region as the C ABI takes it: an 8-float quad (or 4 x 2) stays, an (x0, y0, x1, y1) rectangle becomes its pixel-edge quad."""
+    a = np.asarray(region, dtype=np.float64).ravel()
+    if a.size == 8:
+        return a.astype(np.float32)
+    if a.size == 4:
+        if not np.all(a == np.floor(a)):
+            raise ValueError("a rectangle region is four integers (x0, y0, x1, y1)")
+        return region_from_rect(*[int(v) for v in a])
+    raise ValueError("a region is an 8-float quad (tl, tr, br, bl) or an (x0, y0, x1, y1) rectangle")
+
+
+def charset_masks(charsets) -> np.ndarray:
+    """A list of character sets -> uint32 [n, 3]: each entry an (allow, deny) pair (None or "" = every / no character) or a ready-made mask (3 words)."""
+    out = np.zeros((len(charsets), 3), np.uint32)
+    for i, cs in enumerate(charsets):
+        if isinstance(cs, np.ndarray) or (len(cs) == 3 and all(isinstance(v, (int, np.integer)) for v in cs)):
+            out[i] = np.asarray(cs, dtype=np.uint32).ravel()[:3]
+        elif len(cs) == 2:
+            out[i] = charset_mask(cs[0], cs[1])
+        else:
+            raise ValueError("a charset is an (allow, deny) pair or a mask of three words")
+    return out
+
+
+def _sets_arg(sets):
+    """uint32 [n, 3] (or None) -> (pointer, n, keep-alive array)"""
+    if sets is None or len(sets) == 0:
+        return None, 0, None
+    m = np.ascontiguousarray(sets, dtype=np.uint32).reshape(-1, 3)
+    return m.ctypes.data_as(C.POINTER(C.c_uint32)), len(m), m
 
 
 def orient_select(conf, ids, per_page: bool = False):
@@ -829,6 +895,56 @@ class Engine:
         self._check(self.lib.ttr_stream_flush(self.h, arr, C.byref(n_prev)))
         return self._results(arr, n_prev.value, keep, conf)
 
+    def read_regions(self, pages_or_image, regions, charsets=None):
+        """Read regions the caller already knows, each under its own character set, with no detector (DESIGN.md "Regions and per-row character sets").
+        pages_or_image: one host image [H, W, 3] u8 (ttr_image_regions_to_data), or a list of device pages (ptr | DeviceBuffer, h, w[, row_stride]) of
+        any sizes (ttr_regions_to_data_dev).  regions: a list of dicts {"quad": 8 floats | "rect": (x0, y0, x1, y1), "page": index (default 0), "set":
+        index into charsets, or -1 / absent = the engine's own set}, or of bare quads / rectangles (page 0, the engine's set).  charsets: a list of
+        (allow, deny) pairs or ready-made masks.  Returns, per page (for an image: that page alone), the regions in the caller's order as dicts {"text",
+        "bbox", "ids", "quad", "conf", "prob", "set", "region"} - "quad" the caller's floats verbatim, "region" the index into `regions`."""
+        regs = (Region * max(len(regions), 1))()
+        for i, r in enumerate(regions):
+            d = r if isinstance(r, dict) else {"quad" if np.asarray(r).size == 8 else "rect": r}
+            if ("quad" in d) == ("rect" in d):
+                raise ValueError(f"region {i}: give a quad or a rect")
+            q = region_quad(d["quad"] if "quad" in d else d["rect"])
+            regs[i] = Region((C.c_float * 8)(*[float(v) for v in q]), int(d.get("page", 0)), int(d.get("set", -1)))
+        sp, ns, _keep = _sets_arg(charset_masks(charsets) if charsets is not None else None)
+        single = isinstance(pages_or_image, np.ndarray)
+        if single:
+            image = np.ascontiguousarray(pages_or_image, dtype=np.uint8)
+            if image.ndim != 3 or image.shape[2] != 3:
+                raise RuntimeError("Input array should have 3 dimensions")
+            n_pages = 1
+            arr = (C.c_void_p * 1)()
+            self._check(self.lib.ttr_image_regions_to_data(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, regs, len(regions), sp, ns, arr))
+        else:
+            n_pages = len(pages_or_image)
+            arr = (C.c_void_p * max(n_pages, 1))()
+            self._check(self.lib.ttr_regions_to_data_dev(self.h, self._page_array(pages_or_image), n_pages, regs, len(regions), sp, ns, arr))
+        where = [[i for i in range(len(regions)) if regs[i].page == p] for p in range(n_pages)]
+        out = []
+        for p in range(n_pages):
+            c = self.lib.ttr_result_count(arr[p])
+            sets = np.ctypeslib.as_array(self.lib.ttr_result_sets(arr[p]), (c,)).copy() if c else np.zeros(0, np.int32)
+            quads = self._quads(arr[p], c)
+            page = self._take_many((C.c_void_p * 1)(arr[p]), 1)[0]      # (frees the result)
+            items = []
+            for k in range(c):
+                items.append({"text": page.texts[k], "bbox": page.bbox[k].tolist(), "ids": page.ids[k].tolist(), "quad": quads[k].tolist(),
+                              "conf": float(page.conf[k]), "prob": page.prob[k].tolist(), "set": int(sets[k]), "region": where[p][k]})
+            out.append(items)
+        return out[0] if single else out
+
+    def pack_regions(self, image: np.ndarray, quads) -> np.ndarray:
+        """ttr_pack_regions: the crops of caller-given quads f32 [n, 8] (tl, tr, br, bl in image pixels) on a host image -> u8 [n, 32, 128, 3]."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        quads = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+        n = len(quads)
+        crops = np.zeros((n, 32, 128, 3), np.uint8)
+        self._check(self.lib.ttr_pack_regions(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _f(quads), n, _u8(crops)))
+        return crops
+
     def canvas_geometry(self, h: int, w: int):
         """ttr_canvas_geometry: the detector canvas this engine gives an h x w page -> (H, W, ratio).  Pages with equal (H, W) can share a batch."""
         H, W, ratio = C.c_int32(), C.c_int32(), C.c_float()
@@ -1052,23 +1168,38 @@ class Engine:
                                                      C.c_float(ratio), int(crop_mode), int(turn), _u8(crops), _f(quads)))
         return crops, quads
 
-    def parseq_logits(self, crops: np.ndarray, want_ar: bool = False):
+    def parseq_logits(self, crops: np.ndarray, want_ar: bool = False, set_of=None, sets=None):
+        """set_of (i32 [n]) with sets (uint32 [k, 3] masks): crop i chooses under sets[set_of[i]], -1 = the engine's own set (ttr_parseq_logits_sets)."""
         crops = np.ascontiguousarray(crops, dtype=np.uint8)
         n = len(crops)
         logits = np.zeros((n, 26, 95), np.float32)
         ar = np.zeros((n, 26, 95), np.float32) if want_ar else None
         ids = np.zeros((n, 26), np.int32)
-        self._check(self.lib.ttr_parseq_logits(self.h, _u8(crops), n, _f(logits), _f(ar) if want_ar else None, _i(ids)))
+        if set_of is not None:
+            so = np.ascontiguousarray(set_of, dtype=np.int32).ravel()
+            if len(so) != n:
+                raise ValueError("set_of holds one entry per crop")
+            sp, ns, _keep = _sets_arg(sets)
+            self._check(self.lib.ttr_parseq_logits_sets(self.h, _u8(crops), n, sp, ns, _i(so), _f(logits), _f(ar) if want_ar else None, _i(ids)))
+        else:
+            self._check(self.lib.ttr_parseq_logits(self.h, _u8(crops), n, _f(logits), _f(ar) if want_ar else None, _i(ids)))
         return (logits, ar, ids) if want_ar else (logits, ids)
 
-    def logits_confidence(self, logits: np.ndarray, mask=None):
+    def logits_confidence(self, logits: np.ndarray, mask=None, set_of=None, sets=None):
         """The recogniser's final decode on host logits f32 [n, 26, 95] (ttr_logits_confidence: decode_conf_kernel) -> (ids i32 [n, 26],
         prob f32 [n, 26], conf f32 [n]).  mask (uint32 [3], charset_mask's form): the decode among the allowed classes only
-        (ttr_logits_confidence_masked); the engine's own set is not consulted either way."""
+        (ttr_logits_confidence_masked); the engine's own set is not consulted either way.  set_of (i32 [n]) with sets (uint32 [k, 3]): row i
+        decodes under sets[set_of[i]], -1 = the engine's own set (ttr_logits_confidence_sets)."""
         logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, 26, 95)
         n = len(logits)
         ids, prob, conf = np.zeros((n, 26), np.int32), np.zeros((n, 26), np.float32), np.zeros(n, np.float32)
-        if mask is None:
+        if set_of is not None:
+            so = np.ascontiguousarray(set_of, dtype=np.int32).ravel()
+            if len(so) != n:
+                raise ValueError("set_of holds one entry per row")
+            sp, ns, _keep = _sets_arg(sets)
+            self._check(self.lib.ttr_logits_confidence_sets(self.h, _f(logits), n, sp, ns, _i(so), _i(ids), _f(prob), _f(conf)))
+        elif mask is None:
             self._check(self.lib.ttr_logits_confidence(self.h, _f(logits), n, _i(ids), _f(prob), _f(conf)))
         else:
             m = (C.c_uint32 * 3)(*[int(v) for v in np.asarray(mask).ravel()[:3]])
