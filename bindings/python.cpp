@@ -19,6 +19,9 @@
 // "allowlist" / "blocklist"} reads those regions with no detector, each under its own character set, in one recogniser pass (DESIGN.md "Regions and
 // per-row character sets"); a region without lists reads under the call's allowlist / blocklist.  One dict per region, in order: "text", "bbox", "quad" (the
 // caller's floats), "region" (its index) and - conf=True - "conf" / "char_conf".  A bad list raises ValueError before anything runs.
+// And a keyword-only alts=0 on both calls: alts=K (2..8) gives every dict "alternatives", one list per character of "text" holding (char, prob) tuples
+// over that position's K best characters in rank order (DESIGN.md "Character alternatives"); set on the cached engine for the call and reset afterwards.
+// It combines with everything above except orient, which raises the engine's message.
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -39,7 +42,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
@@ -67,7 +70,28 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
     }
     d["chars"] = cs;
   }
+  if (k.alts) {
+    py::list per_char;
+    for (const std::vector<CharAlt>& opts : item.alternatives) {
+      py::list l;
+      for (const CharAlt& a : opts) l.append(py::make_tuple(a.ch, a.prob));
+      per_char.append(l);
+    }
+    d["alternatives"] = per_char;
+  }
   return d;
+}
+
+// alts=0 | 2..8 -> K; anything else raises ValueError before anything runs
+static int alts_arg(int alts) {
+  if (alts != 0 && (alts < 2 || alts > 8)) throw std::invalid_argument("alts must be 0 (off) or lie in 2..8");
+  return alts;
+}
+
+// a call with alts set that came back empty because the engine refused them (orient, a bf16 engine) raises the engine's message
+static void raise_refused() {
+  const std::string msg = last_call_error();
+  if (!msg.empty()) throw std::runtime_error(msg);
 }
 
 // orient=None|"flip"|"quarter" -> TTR_ORIENT_*
@@ -134,8 +158,9 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
 
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
-                                      bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw) {
+                                      bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts) {
   const int orient = orient_mode(orient_kw);
+  alts_arg(alts);
   std::string allow, deny;
   charset_args(allowlist, blocklist, allow, deny);
   const bool cset = !allow.empty() || !deny.empty();
@@ -150,11 +175,12 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     std::vector<OutputItemEx> got;
     {
       py::gil_scoped_release nogil;
-      got = image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs);
+      got = image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts);
     }
+    if (alts && got.empty()) raise_refused();
     py::list res;
     for (const auto& item : got) {
-      py::dict d = item_dict(item, Keys{true, conf, false, false, false, false});
+      py::dict d = item_dict(item, Keys{true, conf, false, false, false, false, alts != 0});
       d["region"] = item.region;
       res.append(d);
     }
@@ -168,15 +194,17 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   std::vector<OutputItemEx> items;
   {
     py::gil_scoped_release nogil;   // (orient = None: the 7-argument call, which leaves the orientation to TUATARA_ORIENT)
-    items = cset     ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny)
+    items = alts     ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts)
+            : cset   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny)
             : blocks ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
             : chars  ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, true)
             : lines  ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true)
             : orient ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
                      : image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
   }
+  if (alts && items.empty()) raise_refused();
   py::list result;
-  for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks}));
+  for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0}));
   return result;
 }
 
@@ -185,8 +213,9 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
 // on one cached engine: same-sized images travel as batches, the host-to-device copies run beside the GPU's work, the GIL is released meanwhile.
 // Keyword-only mixed_batches=False: True batches images that share one detector canvas, whatever their sizes (DESIGN.md "Mixed-size batches"); same results.
 static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf, py::object orient_kw,
-                                       bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches, py::object allowlist, py::object blocklist) {
+                                       bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches, py::object allowlist, py::object blocklist, int alts) {
   const int orient = orient_mode(orient_kw);
+  alts_arg(alts);
   std::string allow, deny;
   charset_args(allowlist, blocklist, allow, deny);
   const bool cset = !allow.empty() || !deny.empty();
@@ -205,7 +234,8 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   std::vector<std::vector<OutputItemEx>> pages;
   {
     py::gil_scoped_release nogil;
-    pages = cset ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny)
+    pages = alts ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts)
+            : cset ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny)
             : mixed_batches ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, true)
             : blocks ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
             : chars  ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, true)
@@ -213,10 +243,11 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
             : orient ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient, orient_page)
                      : images_to_data_ex(views, weights_dir, output_dir, rectify);
   }
+  if (alts && pages.empty() && !views.empty()) raise_refused();
   py::list result;
   for (const auto& items : pages) {
     py::list page;
-    for (const auto& item : items) page.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks}));
+    for (const auto& item : items) page.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0}));
     result.append(page);
   }
   return result;
@@ -226,8 +257,8 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
 }

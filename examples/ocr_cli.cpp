@@ -20,6 +20,9 @@
 // (DESIGN.md "Regions and per-row character sets").  One region per line: "x0 y0 x1 y1 [allow [deny]]" - the pixels [x0, x1) x [y0, y1) - or eight floats
 // "tl.x tl.y tr.x tr.y br.x br.y bl.x bl.y [allow [deny]]"; '#' starts a comment.  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per region, in the file's
 // order, every number to 9 significant digits (a float read back is the float that was printed).  A malformed file fails, naming the line, before the image is read.
+//   ocr_cli --alts K [--nbest M] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: K alternatives per character (2..8; DESIGN.md "Character
+// alternatives").  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item, then one line per character of the text, "<TAB>c: a=p b=p ..." with that position's
+// alternatives in rank order and their probabilities, and - with --nbest M (1..64) - the M likeliest readings of the word, "<TAB>#i score text".
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <algorithm>
 #include <cmath>
@@ -74,6 +77,36 @@ int main(int argc, const char** argv) {
     while (argc >= 3 && (std::string(argv[1]) == "--allowlist" || std::string(argv[1]) == "--blocklist")) {   // leading options, any order
       setenv(std::string(argv[1]) == "--allowlist" ? "TUATARA_ALLOWLIST" : "TUATARA_BLOCKLIST", argv[2], 1);
       argv[2] = argv[0]; argv += 2; argc -= 2;
+    }
+    int alts = 0, nbest_m = 0;
+    while (argc >= 3 && (std::string(argv[1]) == "--alts" || std::string(argv[1]) == "--nbest")) {
+      char* end = nullptr;
+      const long v = std::strtol(argv[2], &end, 10);
+      const bool is_alts = std::string(argv[1]) == "--alts";
+      if (end == argv[2] || *end || (is_alts ? (v < 2 || v > 8) : (v < 1 || v > 64))) throw std::runtime_error(is_alts ? "--alts takes K in 2..8" : "--nbest takes M in 1..64");
+      (is_alts ? alts : nbest_m) = (int)v;
+      argv[2] = argv[0]; argv += 2; argc -= 2;
+    }
+    if (nbest_m && !alts) throw std::runtime_error("--nbest needs --alts K");
+    if (alts) {
+      if (argc != 4) throw std::runtime_error("--alts K [--nbest M] goes in front of <image.png> <weights_dir> <outputs_dir>");
+      pngdec::Image img = pngdec::read(argv[1]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[2], argv[3], false, -1, false, false,
+                                                         false, false, std::string(), std::string(), alts);
+      if (!last_call_error().empty()) return 1;                         // (the message is on stderr)
+      for (const OutputItemEx& it : items) {
+        printf("%g %g %g %g\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.conf, it.text.c_str());
+        for (size_t c = 0; c < it.alternatives.size(); ++c) {
+          printf("\t%c:", c < it.text.size() ? it.text[c] : '?');
+          for (const CharAlt& a : it.alternatives[c]) printf(" %s=%.6f", a.ch.c_str(), a.prob);
+          printf("\n");
+        }
+        if (nbest_m) {
+          const std::vector<WordReading> rd = nbest(it, nbest_m);
+          for (size_t i = 0; i < rd.size(); ++i) printf("\t#%zu %.6f %s\n", i, rd[i].score, rd[i].text.c_str());
+        }
+      }
+      return 0;
     }
     if (argc == 4 && std::string(argv[1]) == "--decode-only") {
       pngdec::Image img = pngdec::read(argv[2]);
@@ -154,7 +187,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--alts K [--nbest M]] [--rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

@@ -40,6 +40,10 @@ struct CharBox {                   // one character of an item's text (character
   std::vector<float> quad;         // 8: tl, tr, br, bl in image pixels, along the word's baseline
   std::vector<float> bbox;         // 4: min x, min y, max x, max y of those corners
 };
+struct CharAlt {                   // one alternative of one character (character alternatives; DESIGN.md "Character alternatives")
+  std::string ch;                  // the character
+  float prob = 0.f;                // its softmax probability among the allowed characters
+};
 struct OutputItemEx {
   std::string text;
   std::vector<float> bbox;  // x1, y1, x2, y2
@@ -50,6 +54,10 @@ struct OutputItemEx {
   std::vector<CharBox> chars;      // character boxes: one per character of `text`, in text order; empty when chars are off (DESIGN.md "Character boxes")
   int line = -1, word = -1;        // text lines: the item's line of its page, in reading order, and its position inside that line; -1 when lines are off (DESIGN.md "Text lines")
   int region = -1;                 // regions: the index of the caller's region this item reads; -1 for items the detector found (DESIGN.md "Regions and per-row character sets")
+  int alt_k = 0;                   // character alternatives: K per position, the winner included; 0 when alternatives are off (DESIGN.md "Character alternatives")
+  std::vector<int32_t> alt_ids;    // [26][alt_k]: the K best classes of every position of the recogniser's row (-1 = none), as ttr_result_alt_ids gives them
+  std::vector<float> alt_prob;     // [26][alt_k]: their probabilities, as ttr_result_alt_probs gives them
+  std::vector<std::vector<CharAlt>> alternatives;   // one list per character of `text`: that position's character options in rank order, the character itself first unless another option ties it
   int block = -1, block_line = -1;  // text blocks: the item's block of its page, in reading order, and its line's position inside that block (what a caller sorts by: block, block_line, word); -1 when blocks are off (DESIGN.md "Text blocks")
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
@@ -123,6 +131,25 @@ struct RegionSpec {
 RegionSpec region_from_rect(int x0, int y0, int x1, int y1, std::string allowlist = std::string(), std::string blocklist = std::string());
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, const std::vector<RegionSpec>& regions);
+
+// Character alternatives (opt-in; DESIGN.md "Character alternatives"): alts = K in 2..8 also gives every item the K best characters of each position with
+// their probabilities - what a spell-checker, a "did you mean" or a checksum repair needs beside `conf`.  `alternatives` holds one ranked list per character
+// of `text`; nbest() reads the M likeliest whole words out of an item (substitutions only; reading 0 is (text, conf)).  K is set on the cached engine for the
+// call and reset afterwards.  alts = 0 is the calls above, unless TUATARA_ALTS=K is set in the environment, which turns them on for every call.  Items,
+// order, boxes, text and conf do not change.  Alternatives do not combine with word orientation or a bf16 engine: the message is printed and the result
+// is empty.  The other arguments as above.
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, int alts);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist, int alts);
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts);
+// the message of this thread's last call above when it refused its character set or alternatives (it is printed too); empty when the call ran
+std::string last_call_error();
+struct WordReading { std::string text; float score = 0.f; };
+std::vector<WordReading> nbest(const OutputItemEx& item, int m);   // the m best readings (1 <= m <= 64) of an item that carries alternatives; empty otherwise
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

@@ -434,6 +434,38 @@ int ttr_parseq_logits_sets(ttr_engine* e, const uint8_t* crops, int n, const uin
                            float* ar_logits, int32_t* ids);
 int ttr_logits_confidence_sets(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* ids,
                                float* probs, float* conf);
+/* Character alternatives (DESIGN.md "Character alternatives"): what else each character could have been.  K = alternatives per position, the winner
+ * included: 0 (off, the default) or 2..8.  For item i and position p (0..25), under the class mask in force for that crop (the engine's set, or the region's
+ * own): alt_ids[p][j], j < K, are the allowed classes in descending order of the refined logit (fp32), ties to the lower class, -1 where fewer than K are
+ * allowed; alt_ids[p][0] is ttr_result_ids' id.  alt_probs[p][j] = expf(x[alt_id] - x[id]) * prob[p] in fp32, 0.f in the empty slots; alt_probs[p][0] is
+ * ttr_result_prob's value bit for bit.  Every other field of a result is bit for bit that of K = 0; with K = 0 no launch, allocation or copy is added.
+ * ttr_engine_set_alternatives: K for every page entry point (the synchronous calls, the list form, the _v forms, streamed batches, the region calls - each
+ * region under its own set); with a communicator attached each rank's own results carry them, the gathered payload does not.  It fails, and changes
+ * nothing, for K outside {0, 2..8}, while streamed batches are in flight, on a bf16 engine (its kernels take no class mask) and on an engine with
+ * orient != 0 (the chosen turn's logits are gone by the time of the choice).  ttr_pages_to_data_dev_sharded refuses an engine with alternatives set.
+ * ttr_result_alt_k: K of a result (0 = off).  ttr_result_alt_ids / _probs: item i's [26][K]; the _all views: [count][26][K], NULL when off or empty.
+ * ttr_results_gather_alts: ttr_results_gather's item order into ids / probs [total][26][K] (either may be NULL); returns the item count, -1 when the
+ * non-empty results differ in K.
+ * ttr_logits_alternatives (stage; refuses while batches stream): host logits [n][26][95] through decode_conf_kernel and decode_alts_kernel ->
+ * alt_ids / alt_probs [n][26][k], k in 2..8.  sets == NULL: every row under the engine's own set; else row i under sets[set_of[i]] (masks as
+ * ttr_charset_mask forms them, bit 0 set), -1 = the engine's own set, as in ttr_logits_confidence_sets.
+ * ttr_nbest_from_alts (host, no engine, exact): the m best readings (1 <= m <= 64) of ONE word from its alt_ids / alt_probs [26][k], k in 2..8.  Readings
+ * differ from the top reading by substitutions only: one option per character position (the positions before the EOS whose slot-0 id is a character; the
+ * options are the slots holding a character - not -1, the EOS or id 88 -, ranked by probability, then slot).  A reading's score is the fp32 product, in
+ * position order from 1.0f, of the picked probabilities, times the EOS's slot-0 probability when there is one: reading 0 is the item's (text, conf) bit
+ * for bit.  Order: score descending, then rank tuple ascending.  texts receives the readings, each followed by '\n' (written only when cap suffices;
+ * *need = the bytes they take), scores [m] their scores (either may be NULL).  Returns the number of readings, or -1 on bad arguments (ttr_last_error). */
+int ttr_engine_set_alternatives(ttr_engine* e, int k);
+int ttr_engine_alternatives(const ttr_engine* e);
+int ttr_result_alt_k(const ttr_result* r);
+const int32_t* ttr_result_alt_ids(const ttr_result* r, int i);
+const float* ttr_result_alt_probs(const ttr_result* r, int i);
+const int32_t* ttr_result_alt_ids_all(const ttr_result* r);
+const float* ttr_result_alt_probs_all(const ttr_result* r);
+int ttr_results_gather_alts(ttr_result* const* rs, int n, int32_t* ids, float* probs);
+int ttr_logits_alternatives(ttr_engine* e, const float* logits, int n, int k, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* alt_ids,
+                            float* alt_probs);
+int ttr_nbest_from_alts(const int32_t* alt_ids, const float* alt_probs, int k, int m, char* texts, size_t cap, float* scores, size_t* need);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

@@ -997,6 +997,99 @@ int ttr_engine_get_charset(const ttr_engine* e, uint32_t mask[3]) {
   TTR_GUARD_END(-1)
 }
 
+int ttr_engine_set_alternatives(ttr_engine* e, int k) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (k != 0 && (k < 2 || k > 8)) throw std::runtime_error("ttr_engine_set_alternatives: k must be 0 (off) or lie in 2..8, got " + std::to_string(k));
+  E.refuse_while_streaming("ttr_engine_set_alternatives");
+  if (k && E.prec == kBF16)
+    throw std::runtime_error("ttr_engine_set_alternatives: character alternatives need an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which take no class mask");
+  if (k && E.cfg.orient != TTR_ORIENT_OFF)
+    throw std::runtime_error("ttr_engine_set_alternatives: character alternatives do not combine with word orientation (the chosen turn's logits are gone by the time of the choice): create the engine with orient = TTR_ORIENT_OFF");
+  E.alts = k;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_alternatives(const ttr_engine* e) { return e ? e->e->alts : 0; }
+
+int ttr_result_alt_k(const ttr_result* r) { return r ? r->r.alt_k : 0; }
+
+const int32_t* ttr_result_alt_ids(const ttr_result* r, int i) { return r && !r->r.alt_ids.empty() ? &r->r.alt_ids[(size_t)26 * r->r.alt_k * (size_t)i] : nullptr; }
+
+const float* ttr_result_alt_probs(const ttr_result* r, int i) { return r && !r->r.alt_prob.empty() ? &r->r.alt_prob[(size_t)26 * r->r.alt_k * (size_t)i] : nullptr; }
+
+const int32_t* ttr_result_alt_ids_all(const ttr_result* r) { return r && !r->r.alt_ids.empty() ? r->r.alt_ids.data() : nullptr; }
+
+const float* ttr_result_alt_probs_all(const ttr_result* r) { return r && !r->r.alt_prob.empty() ? r->r.alt_prob.data() : nullptr; }
+
+int ttr_results_gather_alts(ttr_result* const* rs, int n, int32_t* ids, float* probs) {
+  if (!rs || n < 0) return -1;
+  int k = -1;
+  for (int i = 0; i < n; ++i) {   // (an empty result - an image that failed, a page without words - has no alternatives to disagree with)
+    if (!rs[i] || rs[i]->r.text.empty()) continue;
+    if (k >= 0 && rs[i]->r.alt_k != k) return -1;
+    k = rs[i]->r.alt_k;
+  }
+  size_t total = 0, o = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!rs[i]) continue;
+    const Result& r = rs[i]->r;
+    total += r.text.size();
+    if (ids && !r.alt_ids.empty()) memcpy(ids + o, r.alt_ids.data(), r.alt_ids.size() * 4);
+    if (probs && !r.alt_prob.empty()) memcpy(probs + o, r.alt_prob.data(), r.alt_prob.size() * 4);
+    o += r.alt_ids.size();
+  }
+  return (int)total;
+}
+
+int ttr_logits_alternatives(ttr_engine* e, const float* logits, int n, int k, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* alt_ids,
+                            float* alt_probs) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && !logits) || (sets && n > 0 && !set_of)) throw std::runtime_error("null argument");
+  if (k < 2 || k > 8) throw std::runtime_error("ttr_logits_alternatives: k must lie in 2..8, got " + std::to_string(k));
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_logits_alternatives");
+  std::vector<uint32_t> table;
+  ClassMask one = E.charset;
+  if (sets) E.resolve_row_masks("ttr_logits_alternatives", set_of, n, sets, n_sets, table, one);
+  if (n == 0) return 0;
+  E.logits.ensure((size_t)n * 26 * 95 * 4);
+  const Engine::RecOut o = E.rec_out(n);
+  const Engine::AltOut a = E.alts_out(n, k);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  const RowMask* rows = E.stage_row_masks(table, 0);
+  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, one, rows);
+  launch_decode_alts(E.logits.as<float>(), n, o.ids, o.prob, k, a.ids, a.prob, E.stream, one, rows);
+  if (alt_ids) TTR_HIP_CHECK(hipMemcpyAsync(alt_ids, a.ids, (size_t)n * 26 * k * 4, hipMemcpyDeviceToHost, E.stream));
+  if (alt_probs) TTR_HIP_CHECK(hipMemcpyAsync(alt_probs, a.prob, (size_t)n * 26 * k * 4, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_nbest_from_alts(const int32_t* alt_ids, const float* alt_probs, int k, int m, char* texts, size_t cap, float* scores, size_t* need) {
+  TTR_GUARD_BEGIN
+  if (!alt_ids || !alt_probs) throw std::runtime_error("ttr_nbest_from_alts: null argument");
+  if (k < 2 || k > 8) throw std::runtime_error("ttr_nbest_from_alts: k must lie in 2..8, got " + std::to_string(k));
+  if (m < 1 || m > 64) throw std::runtime_error("ttr_nbest_from_alts: m must lie in 1..64, got " + std::to_string(m));
+  static const Tokenizer tok;
+  const std::vector<Reading> rd = nbest_from_alts(tok, alt_ids, alt_probs, k, m);
+  size_t bytes = 0;
+  for (const Reading& r : rd) bytes += r.text.size() + 1;
+  if (need) *need = bytes;
+  size_t o = 0;
+  for (size_t i = 0; i < rd.size(); ++i) {
+    if (scores) scores[i] = rd[i].score;
+    if (texts && cap >= bytes) { memcpy(texts + o, rd[i].text.data(), rd[i].text.size()); o += rd[i].text.size(); texts[o++] = '\n'; }
+  }
+  return (int)rd.size();
+  TTR_GUARD_END(-1)
+}
+
 int ttr_confidence_from_probs(const int32_t* ids, const float* probs, int n_pos, float* char_conf, int* n_chars, float* conf) {
   if (!ids || !probs || n_pos < 0) return -1;
   const int k = confidence_from_probs(ids, probs, n_pos, char_conf, conf);

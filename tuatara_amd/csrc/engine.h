@@ -263,6 +263,10 @@ struct Result {
   std::vector<float> prob;   // 26 per item: softmax probability of each argmax id (decode_conf.hip)
   std::vector<float> conf;   // 1 per item: the word's confidence (DESIGN.md "Recognition confidence")
   std::vector<int32_t> set;  // 1 per item: the caller's set index (results of the region entry points only; DESIGN.md "Regions and per-row character sets")
+  // character alternatives (ttr_engine_set_alternatives; DESIGN.md "Character alternatives"): 0 / empty when off
+  int alt_k = 0;                   // K: alternatives per position, the winner included
+  std::vector<int32_t> alt_ids;    // 26 K per item: the K best allowed classes of every position, -1 in the empty slots (decode_alts.hip)
+  std::vector<float> alt_prob;     // 26 K per item: their softmax probabilities; slot 0 is `prob`
   // word orientation (cfg.orient != TTR_ORIENT_OFF; DESIGN.md "Word orientation"): empty when off
   std::vector<int32_t> orient;      // 1 per item: the chosen turn 0..3
   std::vector<float> orient_conf;   // orient_k per item: every candidate's conf, ascending turn
@@ -396,6 +400,7 @@ struct Engine {
   std::vector<hipEvent_t> group_ev;               // per page group: component counters are on the host
   std::mutex mu;
   Tokenizer tok;
+  int alts = 0;                                   // alternatives per position, 0 = off or 2..8 (ttr_engine_set_alternatives; DESIGN.md "Character alternatives")
   ClassMask charset{};                            // classes the recogniser may not choose (ttr_engine_set_charset; DESIGN.md "Character sets"); zero = no set
 
   // CRAFT
@@ -428,6 +433,11 @@ struct Engine {
   PinnedBuf h_orient_in[2], h_orient[2];          // ... per slot: staging of orient_in, host copy of the side block
   DevBuf lines_in, lines_side;                    // text lines: the words' cuv | page firsts; the side block (lines.hip)
   PinnedBuf h_lines_in[2], h_lines[2];            // ... per slot: staging of lines_in, host copy of the side block
+  DevBuf alts_side;                               // character alternatives: the side block (decode_alts.hip), [N][26][K] int32 ids | [N][26][K] f32 prob
+  PinnedBuf h_alts[2];                            // ... per slot: its host copy
+  struct AltOut { int* ids; float* prob; };
+  static size_t alts_side_bytes(int N, int K) { return (size_t)N * 26 * K * 8; }
+  AltOut alts_out(int N, int K) { alts_side.ensure(alts_side_bytes(std::max(N, 1), K)); return AltOut{alts_side.as<int>(), alts_side.as<float>() + (size_t)N * 26 * K}; }
   DevBuf blocks_side;                             // text blocks: the side block (blocks.hip)
   PinnedBuf h_blocks[2];                          // ... per slot: its host copy
   DevBuf chars_map[2], chars_in, chars_side;      // character boxes: per slot the batch's region planes (a copy of ccl.tnorm); coef | page_of | turns | nchars; the side block (chars.hip)
@@ -624,7 +634,9 @@ struct Engine {
 
   // crops u8 [N][32][128][3] (device) -> logits f32 [N][26][95], ids i32 [N][26], prob f32 [N][26], conf f32 [N] (device); d_ar optional
   // row_masks (device, [N] RowMask; DESIGN.md "Regions and per-row character sets"): crop n chooses its tokens under row_masks[n] instead of `charset`; null = charset
-  void parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks = nullptr);
+  // d_alt_ids / d_alt_prob (device, [N][26][alts]; DESIGN.md "Character alternatives"): with `alts` set and both given, decode_alts_kernel runs behind the final decode
+  void parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks = nullptr,
+                      int* d_alt_ids = nullptr, float* d_alt_prob = nullptr);
   // The recogniser's outputs of `rows` crops share one device buffer (ids_dev), laid out [rows][26] ids | [rows][26] prob | [rows] conf, so that
   // one device-to-host copy and one collective carry all three.  Ensures the buffer (never inside a launch function).
   struct RecOut { int* ids; float* prob; float* conf; };
@@ -684,6 +696,7 @@ struct Engine {
     std::vector<int32_t> all_counts;   // with a communicator: crops per page of every rank [world][n]
     int cap = 0;                       // ... and the largest rank total (rows of the gathered payload per rank)
     int rows = 0;                      // rows of the recogniser's output block (RecOut) staged in h_ids[slot]: max(N, cap)
+    int alts = 0;                      // the engine's `alts` when the recogniser was enqueued: h_alts[slot] holds [N][26][alts] ids | prob
     // regions (run_regions; DESIGN.md "Regions and per-row character sets"): the boxes are the caller's quads - no detector ran, `boxes` stays empty, every crop is
     // a kind-1 crop of the table packer.  Crop c (page order, then the caller's order): its quad verbatim, its set index, and - when the sets differ - its row
     // of the class-mask table ({blocked[3], 0}); row_masks empty = every crop reads under region_mask, by value
@@ -747,9 +760,9 @@ struct Engine {
   void finish(PageBatch& B, std::vector<Result>& results);
   // results[pg] for every page of B from its boxes and the decoded rows of its crops (crop c is row c); side: the orientation side block
   // of the batch (orient.hip) or null; lines_side: the text lines' side block (lines.hip) or null; chars_side: the characters' (chars.hip) or null;
-  // blocks_side: the text blocks' (blocks.hip) or null
+  // blocks_side: the text blocks' (blocks.hip) or null; alts_side: the alternatives' (decode_alts.hip, B.alts per position) or null
   void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                    std::vector<Result>& results);
+                    std::vector<Result>& results, const void* alts_side = nullptr);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it

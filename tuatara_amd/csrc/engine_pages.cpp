@@ -587,6 +587,7 @@ void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
   const int line_words = cfg.lines && N > 0 ? stage_batch_lines(B, sl) : 0;   // text lines: the host part, before anything of this batch is enqueued
   if (cfg.chars && N > 0) stage_batch_chars(B, sl);                          // character boxes: likewise
+  B.alts = orient_k() > 1 ? 0 : alts;        // character alternatives: fixed for the batch here (the setter refuses while batches stream)
   range_use(kRangeRec0 + (sl & 1));          // the recogniser's kernels of this batch watch the slot's own word
   B.rows = std::max(N, comm ? B.cap : 0);   // the output block's rows (RecOut): with a communicator, the gathered payload's rows per rank
   const size_t block = (size_t)B.rows * kRecWords * 4;
@@ -600,6 +601,9 @@ void Engine::recog_enqueue(PageBatch& B) {
     const RecOut cand = T ? rec_block(orient_cand, T) : RecOut{};
     const size_t side_b = ((size_t)N * (K + 1) + B.n) * 4;   // [N] turn | [N][K] candidate conf | [pages] page turn
     if (T) { orient_side.ensure(side_b); h_orient[sl].ensure(side_b); }
+    // character alternatives: the side block of this batch (the setter refuses an engine with orientation, so T is 0 here)
+    const AltOut alt = B.alts ? alts_out(N, B.alts) : AltOut{nullptr, nullptr};
+    if (B.alts) h_alts[sl].ensure(alts_side_bytes(N, B.alts));
     pack_batch_crops(B, sl);
     if (T) pack_twin_crops(B, sl);
     if (cfg.lines) group_batch_lines(B, sl, line_words);               // text lines: from the boxes alone, so inside the packing stage (DESIGN.md "Text lines")
@@ -608,9 +612,9 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (B.regions) {   // the caller's sets: one mask by value (the engine's own path), or the rows' table through the slot's pinned staging (one copy, no launch)
       struct SetScope { ClassMask& c; ClassMask old; ~SetScope() { c = old; } } set_scope{charset, charset};
       charset = B.region_mask;
-      parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, stage_row_masks(B.row_masks, sl));
+      parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, stage_row_masks(B.row_masks, sl), alt.ids, alt.prob);
     } else
-    parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf);
+    parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, nullptr, alt.ids, alt.prob);
     if (T) {   // the twins as a pass of their own (turn 0 keeps its batch, and with it its bits), then the choice, in place in the standard block
       parseq_forward(crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, logits.as<float>(), nullptr, cand.ids, cand.prob, cand.conf);
       const size_t first_off = (size_t)T * 84;
@@ -621,6 +625,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
     TTR_HIP_CHECK(hipMemcpyAsync(h_ids[sl].p, ids_dev.p, block, hipMemcpyDeviceToHost, stream));   // ids, prob and conf in one copy
     if (T) TTR_HIP_CHECK(hipMemcpyAsync(h_orient[sl].p, orient_side.p, side_b, hipMemcpyDeviceToHost, stream));
+    if (B.alts) TTR_HIP_CHECK(hipMemcpyAsync(h_alts[sl].p, alts_side.p, alts_side_bytes(N, B.alts), hipMemcpyDeviceToHost, stream));   // the alternatives' side block, behind the standard block's copy
   } else {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
@@ -657,13 +662,14 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   const int32_t* lines_block = cfg.lines && N > 0 ? h_lines[B.slot].as<int32_t>() : nullptr;   // the side block (lines.hip)
   const void* chars_block = cfg.chars && N > 0 ? h_chars[B.slot].p : nullptr;                   // the side block (chars.hip)
   const int32_t* blocks_block = cfg.blocks && N > 0 ? h_blocks[B.slot].as<int32_t>() : nullptr;   // the side block (blocks.hip)
-  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results);
+  const void* alts_block = B.alts && N > 0 ? h_alts[B.slot].p : nullptr;                        // the side block (decode_alts.hip)
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block);
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
 
 void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                          std::vector<Result>& results) {
+                          std::vector<Result>& results, const void* alts_side) {
   const int n = B.n, N = B.N, K = orient_k();
   const std::vector<int> first = page_first(B.page_of, n);
   // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
@@ -676,6 +682,14 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
     r.ids.assign(&rows.ids[(size_t)c0 * 26], &rows.ids[(size_t)(c0 + cnt) * 26]);
     r.prob.assign(&rows.prob[(size_t)c0 * 26], &rows.prob[(size_t)(c0 + cnt) * 26]);
     r.conf.assign(&rows.conf[c0], &rows.conf[c0 + cnt]);
+    r.alt_k = B.alts;
+    if (alts_side && cnt > 0) {   // [N][26][K] ids | [N][26][K] prob -> the page's rows
+      const size_t w = (size_t)26 * B.alts;
+      const int32_t* ai = static_cast<const int32_t*>(alts_side);
+      const float* ap = reinterpret_cast<const float*>(ai + (size_t)N * w);
+      r.alt_ids.assign(ai + (size_t)c0 * w, ai + (size_t)(c0 + cnt) * w);
+      r.alt_prob.assign(ap + (size_t)c0 * w, ap + (size_t)(c0 + cnt) * w);
+    }
     if (K > 1) {
       r.orient_k = K;
       if (side) {
@@ -927,6 +941,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   if (cfg.blocks) throw std::runtime_error("latency mode does not support text blocks: create the engine with blocks = 0");
   if (cfg.lines) throw std::runtime_error("latency mode does not support text lines: create the engine with lines = 0");
   if (cfg.chars) throw std::runtime_error("latency mode does not support character boxes: create the engine with chars = 0");
+  if (alts) throw std::runtime_error("latency mode does not support character alternatives: ttr_engine_set_alternatives(e, 0) first");
   if (q1.live || q2.live) throw std::runtime_error("streamed batches are in flight: call ttr_stream_flush until it returns none");
   Comm* const c = comm;
   const int world = c->world, rank = c->rank;

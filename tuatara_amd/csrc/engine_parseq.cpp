@@ -134,7 +134,8 @@ void Engine::decoder_tail(const void* sa, int N, int R, const float* resid_pos, 
   ln_gemm(tgt, "decoder.norm", 1e-5f, t384, pq.at("head"), rows, nullptr, 0, kActNone, logits_out, logits_ld);
 }
 
-void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks) {
+void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks,
+                            int* d_alt_ids, float* d_alt_prob) {
   if (N <= 0) return;
   // A very large crop batch (64 pages of ~150 boxes) goes through in even groups: the refinement pass's widest planes tensor (26 rows per crop x 1536 x 6 bytes)
   // must stay inside the 2 GiB window of 32-bit buffer offsets (8962 crops), and the workspaces stay bounded.  Crops are independent (batch-invariant logits,
@@ -145,7 +146,8 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
     for (int g0 = 0; g0 < N; g0 += per) {
       const int n = std::min(per, N - g0);
       parseq_forward(d_crops + (size_t)g0 * 32 * 128 * 3, n, d_logits + (size_t)g0 * 26 * 95, d_ar ? d_ar + (size_t)g0 * 26 * 95 : nullptr, d_ids + (size_t)g0 * 26,
-                     d_prob + (size_t)g0 * 26, d_conf + g0, row_masks ? row_masks + g0 : nullptr);   // (rows are never permuted: a group's masks start where its crops do)
+                     d_prob + (size_t)g0 * 26, d_conf + g0, row_masks ? row_masks + g0 : nullptr,   // (rows are never permuted: a group's masks start where its crops do)
+                     d_alt_ids ? d_alt_ids + (size_t)g0 * 26 * alts : nullptr, d_alt_prob ? d_alt_prob + (size_t)g0 * 26 * alts : nullptr);
     }
     return;
   }
@@ -425,6 +427,8 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
   decoder_tail(att, N, 26, posq, 26, tgt, t384, d384b, d1536, kvmem, d_logits, 95);
   }
   launch_decode_conf(d_logits, N, d_ids, d_prob, d_conf, stream, charset, row_masks);   // the final argmax with each id's probability and the word's confidence (decode_conf.hip)
+  // character alternatives (DESIGN.md "Character alternatives"): the K best allowed classes of every position, from the same logits, mask and standard block
+  if (alts && d_alt_ids && d_alt_prob) launch_decode_alts(d_logits, N, d_ids, d_prob, alts, d_alt_ids, d_alt_prob, stream, charset, row_masks);
 }
 
 }  // namespace ttr

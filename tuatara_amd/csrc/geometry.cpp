@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cfloat>
 #include <map>
+#include <set>
 #include <stdexcept>
 #include <cstdio>
 
@@ -756,6 +757,54 @@ int charset_mask(const Tokenizer& tok, const char* allow, const char* deny, uint
   if (n == 0) throw std::runtime_error("charset: deny removes every character of allow: only the end of the text would be left");
   for (int i = 0; i < 3; ++i) mask[i] = m[i];
   return n;
+}
+
+std::vector<Reading> nbest_from_alts(const Tokenizer& tok, const int32_t* alt_ids, const float* alt_prob, int k, int m) {
+  auto is_char = [](int id) { return id >= 1 && id < 95 && id != 88; };
+  auto pr = [&](int p, int j) { const float v = alt_prob[(size_t)p * k + j]; return v == v ? v : 0.f; };   // (a NaN orders nothing: it counts as 0)
+  int e = -1;
+  for (int p = 0; p < 26 && e < 0; ++p) if (alt_ids[(size_t)p * k] == 0) e = p;
+  std::vector<int> S;
+  std::vector<std::vector<int>> opt;   // per position of S: its option slots in rank order
+  for (int p = 0; p < (e < 0 ? 26 : e); ++p) {
+    if (!is_char(alt_ids[(size_t)p * k])) continue;
+    std::vector<int> o;
+    for (int j = 0; j < k; ++j) if (is_char(alt_ids[(size_t)p * k + j])) o.push_back(j);
+    std::stable_sort(o.begin(), o.end(), [&](int a, int b) { return pr(p, a) > pr(p, b); });
+    S.push_back(p);
+    opt.push_back(std::move(o));
+  }
+  const size_t L = S.size();
+  typedef std::vector<uint8_t> Tuple;
+  auto score = [&](const Tuple& t) {
+    float c = 1.f;
+    for (size_t i = 0; i < L; ++i) c *= pr(S[i], opt[i][t[i]]);
+    if (e >= 0) c *= pr(e, 0);
+    return c;
+  };
+  typedef std::pair<float, Tuple> Node;
+  auto before = [](const Node& a, const Node& b) { return a.first != b.first ? a.first > b.first : a.second < b.second; };   // a is read before b
+  std::set<Node, decltype(before)> open(before);   // the frontier, best first
+  std::set<Tuple> seen;
+  const Tuple zero(L, 0);
+  open.insert(Node(score(zero), zero));
+  seen.insert(zero);
+  std::vector<Reading> out;
+  while ((int)out.size() < m && !open.empty()) {
+    const Node top = *open.begin();
+    open.erase(open.begin());
+    Reading r;
+    r.score = top.first;
+    for (size_t i = 0; i < L; ++i) r.text.push_back(tok.itos[(size_t)alt_ids[(size_t)S[i] * k + opt[i][top.second[i]]]]);
+    out.push_back(std::move(r));
+    for (size_t i = 0; i < L; ++i) {
+      if ((size_t)top.second[i] + 1 >= opt[i].size()) continue;
+      Tuple t = top.second;
+      ++t[i];
+      if (seen.insert(t).second) open.insert(Node(score(t), t));
+    }
+  }
+  return out;
 }
 
 int confidence_from_probs(const int* ids, const float* probs, int n, float* char_conf, float* conf) {

@@ -130,4 +130,14 @@ int charset_mask(const Tokenizer& tok, const char* allow, const char* deny, uint
 // number of characters (= decode(ids, n).size()).
 int confidence_from_probs(const int* ids, const float* probs, int n, float* char_conf, float* conf);
 
+// N-best readings of one word from its alternatives (DESIGN.md "Character alternatives"; host only, exact): alt_ids / alt_prob [26][k].  S = the positions
+// before the first position whose slot-0 id is 0 (the EOS) whose slot-0 id is a character (in [1, 95), not 88): the confidence rule's S.  The options of a
+// position of S are its slots whose id is a character, ranked by (alt_prob descending, slot ascending).  A reading picks one option per position of S: its text
+// is the picked characters in position order, its score the fp32 product, in position order from 1.0f, of the picked probabilities, times the EOS position's
+// slot-0 probability when there is an EOS - so the all-first reading is the item's (text, conf) bit for bit.  Returns the m best (fewer when fewer exist) by
+// (score descending, rank tuple ascending lexicographically), found by a best-first walk over "raise one position's rank by one": lowering one factor never
+// raises an fp32 product, and a tuple's parents sort before it, so the walk is exact; it pushes at most m |S| tuples.
+struct Reading { std::string text; float score; };
+std::vector<Reading> nbest_from_alts(const Tokenizer& tok, const int32_t* alt_ids, const float* alt_prob, int k, int m);
+
 }  // namespace ttr

@@ -203,6 +203,11 @@ void launch_fill_i32(int* p, int value, int n, int stride, hipStream_t s);
 // cm (DESIGN.md "Character sets"): a blocked class is -inf in the comparison and adds exactly 0 to the exponential sum; the default blocks none
 // row_masks (DESIGN.md "Regions and per-row character sets"): crop n decodes under row_masks[n] instead of cm
 void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s, ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);
+// decode_alts.hip: character alternatives (DESIGN.md "Character alternatives"), directly behind launch_decode_conf on the same logits, mask and standard block:
+// alt_ids i32 [N][26][K] the K best allowed classes of every row (slot 0 = ids; -1 where fewer can be chosen), alt_prob f32 [N][26][K] =
+// expf(x[alt_id] - x[id]) * prob (slot 0 = prob bit for bit; 0.f in the empty slots).  K in 2..8.  Reads the logits, ids and prob; writes the two outputs only.
+void launch_decode_alts(const float* logits, int N, const int* ids, const float* prob, int K, int* alt_ids, float* alt_prob, hipStream_t s,
+                        ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);
 // orient.hip: word orientation (DESIGN.md "Word orientation") - per page, the chosen candidate of every word and the page vote.  ids / prob / conf: the
 // standard block of the batch (turn 0), overwritten in place with the chosen readings; cids / cprob / cconf: the (K - 1) N twin rows, candidate-major;
 // first [pages + 1]: each page's first word; side: [N] int32 turn | [N][K] f32 candidate conf | [pages] int32 page turn.  K = 2 or 4.

@@ -1,6 +1,7 @@
 // image_to_data (tuatara.h:13 / tuatara.cpp:314-512) as a thin C++ shim over the C ABI.
 #include "../../include/tuatara.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <iostream>
 #include <map>
@@ -58,11 +59,13 @@ ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int o
 // A call's character set on the cached engine (DESIGN.md "Character sets"): set when the call begins, reset when it ends, also when it throws.  An empty
 // argument falls back on TUATARA_ALLOWLIST / TUATARA_BLOCKLIST.  Calls that share an engine take turns, so that none runs under another's set.
 std::map<ttr_engine*, std::unique_ptr<std::mutex>> g_call_mu;
+thread_local std::string g_call_error;   // last_call_error()
 struct CharsetScope {
   ttr_engine* e;
   std::unique_lock<std::mutex> turn;
   bool set = false, ok = true;
-  CharsetScope(ttr_engine* e_, std::string allow, std::string deny) : e(e_) {
+  bool alts_set = false;
+  CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0) : e(e_) {
     {
       std::lock_guard<std::mutex> lk(g_mu);
       auto& m = g_call_mu[e];
@@ -70,13 +73,22 @@ struct CharsetScope {
       turn = std::unique_lock<std::mutex>(*m, std::defer_lock);
     }
     turn.lock();
+    g_call_error.clear();
     if (allow.empty()) if (const char* p = std::getenv("TUATARA_ALLOWLIST")) allow = p;
     if (deny.empty()) if (const char* p = std::getenv("TUATARA_BLOCKLIST")) deny = p;
+    if (alts <= 0) if (const char* p = std::getenv("TUATARA_ALTS")) alts = std::atoi(p);
+    if (alts > 0) {   // character alternatives (DESIGN.md "Character alternatives"): K for the call, like the set
+      if (ttr_engine_set_alternatives(e, alts) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      alts_set = true;
+    }
     if (allow.empty() && deny.empty()) return;
-    if (ttr_engine_set_charset(e, allow.c_str(), deny.c_str()) != 0) { std::cerr << "tuatara: " << ttr_last_error() << std::endl; ok = false; return; }
+    if (ttr_engine_set_charset(e, allow.c_str(), deny.c_str()) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
     set = true;
   }
-  ~CharsetScope() { if (set) ttr_engine_set_charset(e, nullptr, nullptr); }
+  ~CharsetScope() {
+    if (set) ttr_engine_set_charset(e, nullptr, nullptr);
+    if (alts_set) ttr_engine_set_alternatives(e, 0);
+  }
 };
 
 template <class Item>
@@ -102,6 +114,31 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
   const int32_t *bk = ttr_result_blocks(r), *lp = ttr_result_line_pos(r);
   o.block = bk ? bk[i] : -1;
   o.block_line = bk && lp && ln ? lp[ln[i]] : -1;
+  o.alt_k = ttr_result_alt_k(r);
+  o.alt_ids.clear(); o.alt_prob.clear(); o.alternatives.clear();
+  if (o.alt_k > 0 && ttr_result_alt_ids_all(r)) {
+    const int K = o.alt_k;
+    const int32_t* ai = ttr_result_alt_ids(r, i);
+    const float* ap = ttr_result_alt_probs(r, i);
+    o.alt_ids.assign(ai, ai + 26 * K);
+    o.alt_prob.assign(ap, ap + 26 * K);
+    auto is_char = [](int id) { return id >= 1 && id < 95 && id != 88; };
+    for (int p = 0; p < 26 && ai[p * K] != 0; ++p) {   // the positions of the text's characters (the confidence rule's S)
+      if (!is_char(ai[p * K])) continue;
+      std::vector<int> slots;
+      for (int j = 0; j < K; ++j) if (is_char(ai[p * K + j])) slots.push_back(j);
+      std::stable_sort(slots.begin(), slots.end(), [&](int a, int b) { return ap[p * K + a] > ap[p * K + b]; });
+      std::vector<CharAlt> alts;
+      for (int j : slots) {
+        char buf[32];
+        ttr_decode_ids(&ai[p * K + j], 1, buf);
+        CharAlt a;
+        a.ch = buf; a.prob = ap[p * K + j];
+        alts.push_back(std::move(a));
+      }
+      o.alternatives.push_back(std::move(alts));
+    }
+  }
   o.chars.clear();
   if (const int32_t* cf = ttr_result_char_first(r)) {
     const float *cq = ttr_result_char_quads(r), *cb = ttr_result_char_bboxes(r);
@@ -129,10 +166,10 @@ ttr_engine* open_engine(const std::string& weights_dir, const std::string& outpu
 template <class Item>
 std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
                           const std::string& outputs_dir, int crop_mode, int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
-                                        int blocks = -1, const std::string& allow = std::string(), const std::string& deny = std::string()) {
+                                        int blocks = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny);
+  CharsetScope cs(e, allow, deny, alts);
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
@@ -152,10 +189,10 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
 template <class Item>
 std::vector<std::vector<Item>> run_many(const std::vector<ImageView>& images, const std::string& weights_dir, const std::string& outputs_dir, int crop_mode,
                                         int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
-                                        int blocks = -1, int mixed = -1, const std::string& allow = std::string(), const std::string& deny = std::string()) {
+                                        int blocks = -1, int mixed = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks, mixed);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny);
+  CharsetScope cs(e, allow, deny, alts);
   if (!cs.ok) return {};
   const int n = (int)images.size();
   std::vector<const uint8_t*> ptr(n);
@@ -274,6 +311,47 @@ RegionSpec region_from_rect(int x0, int y0, int x1, int y1, std::string allowlis
 
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, const std::vector<RegionSpec>& regions) {
+  return image_to_data_ex(image, rows, cols, row_stride, weights_dir, outputs_dir, regions, 0);
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, int alts) {
+  return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1,
+                               chars ? 1 : -1, blocks ? 1 : -1, allowlist, blocklist, alts);
+}
+
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist, int alts) {
+  return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
+                                blocks ? 1 : -1, mixed_batches ? 1 : -1, allowlist, blocklist, alts);
+}
+
+std::string last_call_error() { return g_call_error; }
+
+std::vector<WordReading> nbest(const OutputItemEx& item, int m) {
+  std::vector<WordReading> out;
+  if (item.alt_k < 2 || item.alt_ids.size() != (size_t)26 * item.alt_k || item.alt_prob.size() != item.alt_ids.size() || m < 1 || m > 64) return out;
+  size_t need = 0;
+  std::vector<float> scores((size_t)m, 0.f);
+  const int n = ttr_nbest_from_alts(item.alt_ids.data(), item.alt_prob.data(), item.alt_k, m, nullptr, 0, nullptr, &need);
+  if (n <= 0) return out;
+  std::string buf(need, '\0');
+  ttr_nbest_from_alts(item.alt_ids.data(), item.alt_prob.data(), item.alt_k, m, &buf[0], need, scores.data(), nullptr);
+  size_t at = 0;
+  for (int i = 0; i < n; ++i) {
+    const size_t nl = buf.find('\n', at);
+    WordReading w;
+    w.text = buf.substr(at, nl - at); w.score = scores[(size_t)i];
+    out.push_back(std::move(w));
+    at = nl + 1;
+  }
+  return out;
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts) {
   // every list and quad is checked on the host before an engine is opened
   std::vector<ttr_region> regs(regions.size());
   std::vector<uint32_t> sets;
@@ -290,7 +368,7 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
   }
   ttr_engine* e = open_engine(weights_dir, outputs_dir, -1, -1, 0, -1, -1, -1);
   if (!e) return {};
-  CharsetScope cs(e, std::string(), std::string());   // (the engine's own set for regions without lists: TUATARA_ALLOWLIST / TUATARA_BLOCKLIST; calls that share the engine take turns)
+  CharsetScope cs(e, std::string(), std::string(), alts);   // (the engine's own set for regions without lists: TUATARA_ALLOWLIST / TUATARA_BLOCKLIST; calls that share the engine take turns)
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";

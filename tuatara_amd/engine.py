@@ -134,6 +134,16 @@ SYMBOLS = [
     ("ttr_pack_regions", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _PU8]),
     ("ttr_parseq_logits_sets", _I, [_VP, _PU8, _I, C.POINTER(C.c_uint32), _I, _PI, _PF, _PF, _PI]),
     ("ttr_logits_confidence_sets", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _I, _PI, _PI, _PF, _PF]),
+    ("ttr_engine_set_alternatives", _I, [_VP, _I]),
+    ("ttr_engine_alternatives", _I, [_VP]),
+    ("ttr_result_alt_k", _I, [_VP]),
+    ("ttr_result_alt_ids", _PI, [_VP, _I]),
+    ("ttr_result_alt_probs", _PF, [_VP, _I]),
+    ("ttr_result_alt_ids_all", _PI, [_VP]),
+    ("ttr_result_alt_probs_all", _PF, [_VP]),
+    ("ttr_results_gather_alts", _I, [C.POINTER(_VP), _I, _PI, _PF]),
+    ("ttr_logits_alternatives", _I, [_VP, _PF, _I, _I, C.POINTER(C.c_uint32), _I, _PI, _PI, _PF]),
+    ("ttr_nbest_from_alts", _I, [_PI, _PF, _I, _I, C.c_char_p, C.c_size_t, _PF, C.POINTER(C.c_size_t)]),
     ("ttr_craft_heatmap", _I, [_VP, _PU8, _I, _I, _PF]),
     ("ttr_ccl_boxes", _I, [_VP, _PF, _I, _I, _PF, _I, _PI]),
     ("ttr_resize_canvas", _I, [_VP, _PU8, _I, _I, _I, _PU8, C.c_size_t, _PI, _PI, _PF]),
@@ -483,6 +493,46 @@ def char_quads_from_cuts(quad, turn: int, cuts, K: int):
     return oq[:K].copy(), ob[:K].copy()
 
 
+def nbest_from_alts(alt_ids, alt_prob, m: int):
+    """The M best readings of one word from its alternatives (ttr_nbest_from_alts, no GPU, exact; DESIGN.md "Character alternatives"): alt_ids i32 [26, K]
+    and alt_prob f32 [26, K] -> [(text, score f32), ...], at most m (1..64), by (score descending, rank tuple ascending).  Readings differ from the top
+    reading by substitutions only; reading 0 is the item's (text, conf)."""
+    ids = np.ascontiguousarray(alt_ids, dtype=np.int32)
+    prob = np.ascontiguousarray(alt_prob, dtype=np.float32)
+    if ids.ndim != 2 or ids.shape[0] != 26 or prob.shape != ids.shape:
+        raise ValueError("alt_ids and alt_prob are [26, K] arrays")
+    k = ids.shape[1]
+    need = C.c_size_t()
+    scores = np.zeros(max(int(m), 1), np.float32)
+    n = load().ttr_nbest_from_alts(_i(ids), _f(prob), k, int(m), None, 0, _f(scores), C.byref(need))
+    if n < 0:
+        raise EngineError(load().ttr_last_error().decode("latin1"))
+    buf = C.create_string_buffer(max(need.value, 1))
+    load().ttr_nbest_from_alts(_i(ids), _f(prob), k, int(m), buf, need.value, None, None)
+    texts = buf.raw[:need.value].decode("latin1").split("\n")
+    return [(texts[i], np.float32(scores[i])) for i in range(n)]
+
+
+def _is_char(c: int) -> bool:
+    return 1 <= c < 95 and c != 88
+
+
+def char_alternatives(alt_ids, alt_prob) -> list:
+    """One word's alternatives per character of its text: alt_ids i32 [26, K], alt_prob f32 [26, K] -> one list per character (the positions before the EOS
+    whose slot-0 id is a character), holding (char, prob) over that position's character options - slots that are not -1, the EOS or id 88 - ranked by
+    (prob descending, slot ascending)."""
+    out = []
+    for p in range(26):
+        if int(alt_ids[p][0]) == 0:
+            break
+        if not _is_char(int(alt_ids[p][0])):
+            continue
+        slots = [j for j in range(len(alt_ids[p])) if _is_char(int(alt_ids[p][j]))]
+        slots.sort(key=lambda j: -float(alt_prob[p][j]))          # (stable: ties keep slot order)
+        out.append([(decode_ids([int(alt_ids[p][j])]), float(alt_prob[p][j])) for j in slots])
+    return out
+
+
 def _add_conf(d: dict, conf, prob) -> dict:
     """the conf=True keys of a result dict: "conf" (the kernel's word confidence) and "char_conf" (one probability per character of "text")"""
     d["conf"] = float(conf)
@@ -513,16 +563,21 @@ class PageResult(collections.abc.Sequence):
     in reading order and its position in it, `block_order` i32 [n_lines] the lines in block reading order, `block_first` i32 [n_blocks + 1],
     `block_bbox` f32 [n_blocks, 4], `block_mode` (1: ordered by the precedence relation, 0: more than 512 blocks, by key alone); `blocks` the
     list of {"text", "bbox", "lines"} in reading order and `text_blocks` the page read block after block (lines joined by '\\n', blocks by a
-    blank line); block is None, blocks [] and text_blocks "" when blocks are off."""
+    blank line); block is None, blocks [] and text_blocks "" when blocks are off.  Character alternatives (Engine.set_alternatives(K); DESIGN.md
+    "Character alternatives"): `alt_ids` i32 [n, 26, K] the K best allowed classes of every position (-1 = none; slot 0 is `ids`) and `alt_prob` f32
+    [n, 26, K] their probabilities (slot 0 is `prob`); dicts gain "alternatives", one list per character of "text" holding (char, prob) over that
+    position's character options in rank order; nbest(i, m) reads item i's m likeliest whole words; both None when alternatives are off."""
     __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
                  "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad",
-                 "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode")
+                 "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode", "alt_ids", "alt_prob")
 
     def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0,
                  line=None, word=None, order=None, line_first=None, line_bbox=None,
                  char_first=None, char_quad=None, char_bbox=None, char_cuts=None, char_mode=None, char_profile=None, word_quad=None,
-                 block=None, line_block=None, line_pos=None, block_order=None, block_first=None, block_bbox=None, block_mode=0):
+                 block=None, line_block=None, line_pos=None, block_order=None, block_first=None, block_bbox=None, block_mode=0,
+                 alt_ids=None, alt_prob=None):
+        self.alt_ids, self.alt_prob = alt_ids, alt_prob
         self.block, self.line_block, self.line_pos, self.block_order = block, line_block, line_pos, block_order
         self.block_first, self.block_bbox, self.block_mode = block_first, block_bbox, block_mode
         self.char_first, self.char_quad, self.char_bbox = char_first, char_quad, char_bbox
@@ -561,7 +616,15 @@ class PageResult(collections.abc.Sequence):
             text = self.texts[j]
             d["chars"] = [{"char": text[k - a] if k - a < len(text) else "", "quad": _quad_pairs(self.char_quad[k]), "bbox": self.char_bbox[k].tolist()}
                           for k in range(a, b)]
+        if self.alt_ids is not None:
+            d["alternatives"] = char_alternatives(self.alt_ids[j], self.alt_prob[j])
         return d
+
+    def nbest(self, i: int, m: int) -> list:
+        """item i's m likeliest readings [(text, score), ...] (nbest_from_alts); reading 0 is (text, conf)"""
+        if self.alt_ids is None:
+            raise EngineError("nbest: the result carries no alternatives (Engine.set_alternatives)")
+        return nbest_from_alts(self.alt_ids[i], self.alt_prob[i], m)
 
     @property
     def lines(self) -> list:
@@ -648,6 +711,7 @@ class Engine:
                          PREC_F16X4 if precision in ("f16x4", "split", PREC_F16X4) else PREC_BF16)
         cfg.device = device
         cfg.strict_crops = int(strict_crops)
+        alts = int(overrides.pop("alts", 0) or 0)                                         # not a config field either: set_alternatives, below
         tuning = {k: overrides.pop(k) for k in list(overrides) if not hasattr(cfg, k)}     # not a config field: a tuning key (below)
         for k, v in overrides.items():
             setattr(cfg, k, v)
@@ -658,6 +722,37 @@ class Engine:
         for k, v in tuning.items():
             if self.set_tuning(k, int(v)) != 0:
                 raise EngineError(f"unknown engine option {k!r}")
+        if alts:
+            self.set_alternatives(alts)
+
+    def set_alternatives(self, k: int):
+        """K alternatives per character position, the winner included (ttr_engine_set_alternatives; DESIGN.md "Character alternatives"): 0 = off, or
+        2..8.  Every page call's PageResult then carries alt_ids / alt_prob, its dicts "alternatives", and nbest() works; every other field keeps its
+        bits.  Raises EngineError, and changes nothing, for another K, between a stream_push and its flush, on a bf16 engine and with orient set."""
+        if self.lib.ttr_engine_set_alternatives(self.h, int(k)) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def alternatives(self) -> int:
+        """K in force (0 = off)"""
+        return int(self.lib.ttr_engine_alternatives(self.h))
+
+    def logits_alternatives(self, logits: np.ndarray, k: int, set_of=None, sets=None):
+        """decode_conf_kernel and decode_alts_kernel on host logits f32 [n, 26, 95] (ttr_logits_alternatives) -> (alt_ids i32 [n, 26, k], alt_prob f32
+        [n, 26, k]).  sets None: every row under the engine's own set; else row i under sets[set_of[i]] (uint32 [m, 3] masks), -1 = the engine's own."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, 26, 95)
+        n = len(logits)
+        ids, prob = np.zeros((n, 26, max(int(k), 1)), np.int32), np.zeros((n, 26, max(int(k), 1)), np.float32)
+        sp, ns, _keep = _sets_arg(sets)
+        so = None
+        if sp is not None:
+            if set_of is None:
+                raise ValueError("sets need set_of, one entry per row")
+            so = np.ascontiguousarray(set_of, dtype=np.int32).ravel()
+            if len(so) != n:
+                raise ValueError("set_of holds one entry per row")
+        self._check(self.lib.ttr_logits_alternatives(self.h, _f(logits), n, int(k), sp, ns, _i(so) if so is not None else None, _i(ids), _f(prob)))
+        return ids, prob
 
     def set_tuning(self, key, value: int) -> int:
         """Per-engine kernel-selection knob (ttr_engine_set_tuning); keys it does not know go to the process-wide diagnostics setter."""
@@ -797,6 +892,11 @@ class Engine:
             bf, bbx = np.zeros(total + n + 1, np.int32), np.zeros((max(total, 1), 4), np.float32)
             if self.lib.ttr_results_gather_blocks(arr, n, _i(bn), _i(bm), _i(bi), _i(bl), _i(bp), _i(bo), _i(bf), _f(bbx)) < 0:
                 raise EngineError("ttr_results_gather_blocks: bad arguments")
+        K = self.alternatives if total else 0   # (the setter refuses while batches stream: every result in flight was made under the K in force)
+        if K:                                   # every page's alternatives, one call
+            ai, ap = np.zeros((max(total, 1), 26, K), np.int32), np.zeros((max(total, 1), 26, K), np.float32)
+            if self.lib.ttr_results_gather_alts(arr, n, _i(ai), _f(ap)) < 0:
+                raise EngineError("ttr_results_gather_alts: the results differ in K")
         out, k, kl, kc, kbl, kb = [], 0, 0, 0, 0, 0
         for i in range(n):
             c = int(counts[i])
@@ -821,7 +921,8 @@ class Engine:
             elif self.grouping_blocks:              # an empty page: no blocks
                 blocks = (bi[k:k], bl[:0], bp[:0], bo[:0], np.zeros(1, np.int32), bbx[:0], 0)
             out.append(PageResult(texts[k:k + c], bb[k:k + c], ids[k:k + c], self._quads(arr[i], c) if self.rectified else None,
-                                  cf[k:k + c], pr[k:k + c], conf, *orient, *lines, *chars, *blocks))
+                                  cf[k:k + c], pr[k:k + c], conf, *orient, *lines, *chars, *blocks,
+                                  alt_ids=ai[k:k + c] if K else None, alt_prob=ap[k:k + c] if K else None))
             k += c
             self.lib.ttr_result_free(arr[i])
         return out
@@ -901,7 +1002,8 @@ class Engine:
         any sizes (ttr_regions_to_data_dev).  regions: a list of dicts {"quad": 8 floats | "rect": (x0, y0, x1, y1), "page": index (default 0), "set":
         index into charsets, or -1 / absent = the engine's own set}, or of bare quads / rectangles (page 0, the engine's set).  charsets: a list of
         (allow, deny) pairs or ready-made masks.  Returns, per page (for an image: that page alone), the regions in the caller's order as dicts {"text",
-        "bbox", "ids", "quad", "conf", "prob", "set", "region"} - "quad" the caller's floats verbatim, "region" the index into `regions`."""
+        "bbox", "ids", "quad", "conf", "prob", "set", "region"} - "quad" the caller's floats verbatim, "region" the index into `regions`; with set_alternatives(K) also "alt_ids",
+        "alt_prob" ([26, K] arrays) and "alternatives", each region's under its own set."""
         regs = (Region * max(len(regions), 1))()
         for i, r in enumerate(regions):
             d = r if isinstance(r, dict) else {"quad" if np.asarray(r).size == 8 else "rect": r}
@@ -933,6 +1035,8 @@ class Engine:
             for k in range(c):
                 items.append({"text": page.texts[k], "bbox": page.bbox[k].tolist(), "ids": page.ids[k].tolist(), "quad": quads[k].tolist(),
                               "conf": float(page.conf[k]), "prob": page.prob[k].tolist(), "set": int(sets[k]), "region": where[p][k]})
+                if page.alt_ids is not None:        # character alternatives: each region under its own set
+                    items[-1].update({"alt_ids": page.alt_ids[k], "alt_prob": page.alt_prob[k], "alternatives": char_alternatives(page.alt_ids[k], page.alt_prob[k])})
             out.append(items)
         return out[0] if single else out
 
