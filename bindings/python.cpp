@@ -22,6 +22,9 @@
 // And a keyword-only alts=0 on both calls: alts=K (2..8) gives every dict "alternatives", one list per character of "text" holding (char, prob) tuples
 // over that position's K best characters in rank order (DESIGN.md "Character alternatives"); set on the cached engine for the call and reset afterwards.
 // It combines with everything above except orient, which raises the engine's message.
+// And keyword-only lexicon=None, lexicon_m=1 on both calls: lexicon=[words] gives every dict "lexicon", [(word, prob), ...] over the lexicon_m (1..8) best
+// entries of the list for that item, prob = exp(log-probability) in double (DESIGN.md "Lexicon matching"); set on the cached engine for the call and cleared
+// afterwards.  A bad entry raises ValueError naming its index (the engine's own message; nothing is read).  It combines with everything above except orient.
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -42,7 +45,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
@@ -79,6 +82,11 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
     }
     d["alternatives"] = per_char;
   }
+  if (k.lexicon) {
+    py::list l;
+    for (const LexMatch& m : item.lexicon) l.append(py::make_tuple(m.word, std::exp((double)m.logp)));
+    d["lexicon"] = l;
+  }
   return d;
 }
 
@@ -88,9 +96,23 @@ static int alts_arg(int alts) {
   return alts;
 }
 
-// a call with alts set that came back empty because the engine refused them (orient, a bf16 engine) raises the engine's message
+// lexicon=None | a sequence of str, lexicon_m -> the word list (has = a list was given).  lexicon_m out of range, an empty list and a word with a NUL (which
+// would cut it short on the way to the engine) raise ValueError here; the words themselves are checked once, by the engine's setter (raise_refused)
+static bool lexicon_args(const py::object& lexicon, int lexicon_m, std::vector<std::string>& words) {
+  if (lexicon.is_none()) return false;
+  for (py::handle w : lexicon) words.push_back(py::cast<std::string>(w));
+  if (lexicon_m < 1 || lexicon_m > 8) throw std::invalid_argument("lexicon_m must lie in 1..8");
+  if (words.empty()) throw std::invalid_argument("lexicon: the word list is empty");
+  for (size_t i = 0; i < words.size(); ++i)
+    if (words[i].find('\0') != std::string::npos) throw std::invalid_argument("lexicon: word " + std::to_string(i) + " holds '\\x00', which names no recogniser class");
+  return true;
+}
+
+// a call with alts or a lexicon set that came back empty because the engine refused them raises the engine's message: a bad word list (the messages that
+// begin "lexicon:") as ValueError, a refusal of the engine's state (orient, a bf16 engine) as RuntimeError
 static void raise_refused() {
   const std::string msg = last_call_error();
+  if (msg.rfind("lexicon:", 0) == 0) throw std::invalid_argument(msg);
   if (!msg.empty()) throw std::runtime_error(msg);
 }
 
@@ -158,9 +180,11 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
 
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
-                                      bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts) {
+                                      bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m) {
   const int orient = orient_mode(orient_kw);
   alts_arg(alts);
+  std::vector<std::string> words;
+  const bool lex = lexicon_args(lexicon, lexicon_m, words);
   std::string allow, deny;
   charset_args(allowlist, blocklist, allow, deny);
   const bool cset = !allow.empty() || !deny.empty();
@@ -175,12 +199,13 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     std::vector<OutputItemEx> got;
     {
       py::gil_scoped_release nogil;
-      got = image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts);
+      got = lex ? image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts, words, lexicon_m)
+                : image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts);
     }
-    if (alts && got.empty()) raise_refused();
+    if ((alts || lex) && got.empty()) raise_refused();
     py::list res;
     for (const auto& item : got) {
-      py::dict d = item_dict(item, Keys{true, conf, false, false, false, false, alts != 0});
+      py::dict d = item_dict(item, Keys{true, conf, false, false, false, false, alts != 0, lex});
       d["region"] = item.region;
       res.append(d);
     }
@@ -194,7 +219,8 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   std::vector<OutputItemEx> items;
   {
     py::gil_scoped_release nogil;   // (orient = None: the 7-argument call, which leaves the orientation to TUATARA_ORIENT)
-    items = alts     ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts)
+    items = lex      ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts, words, lexicon_m)
+            : alts   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts)
             : cset   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny)
             : blocks ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
             : chars  ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, true)
@@ -202,9 +228,9 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
             : orient ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
                      : image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
   }
-  if (alts && items.empty()) raise_refused();
+  if ((alts || lex) && items.empty()) raise_refused();
   py::list result;
-  for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0}));
+  for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex}));
   return result;
 }
 
@@ -213,9 +239,12 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
 // on one cached engine: same-sized images travel as batches, the host-to-device copies run beside the GPU's work, the GIL is released meanwhile.
 // Keyword-only mixed_batches=False: True batches images that share one detector canvas, whatever their sizes (DESIGN.md "Mixed-size batches"); same results.
 static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf, py::object orient_kw,
-                                       bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches, py::object allowlist, py::object blocklist, int alts) {
+                                       bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches, py::object allowlist, py::object blocklist, int alts,
+                                       py::object lexicon, int lexicon_m) {
   const int orient = orient_mode(orient_kw);
   alts_arg(alts);
+  std::vector<std::string> words;
+  const bool lex = lexicon_args(lexicon, lexicon_m, words);
   std::string allow, deny;
   charset_args(allowlist, blocklist, allow, deny);
   const bool cset = !allow.empty() || !deny.empty();
@@ -234,7 +263,8 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   std::vector<std::vector<OutputItemEx>> pages;
   {
     py::gil_scoped_release nogil;
-    pages = alts ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts)
+    pages = lex ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts, words, lexicon_m)
+            : alts ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts)
             : cset ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny)
             : mixed_batches ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, true)
             : blocks ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
@@ -243,11 +273,11 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
             : orient ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient, orient_page)
                      : images_to_data_ex(views, weights_dir, output_dir, rectify);
   }
-  if (alts && pages.empty() && !views.empty()) raise_refused();
+  if ((alts || lex) && pages.empty() && !views.empty()) raise_refused();
   py::list result;
   for (const auto& items : pages) {
     py::list page;
-    for (const auto& item : items) page.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0}));
+    for (const auto& item : items) page.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex}));
     result.append(page);
   }
   return result;
@@ -257,8 +287,8 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
 }

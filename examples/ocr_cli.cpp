@@ -23,6 +23,9 @@
 //   ocr_cli --alts K [--nbest M] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: K alternatives per character (2..8; DESIGN.md "Character
 // alternatives").  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item, then one line per character of the text, "<TAB>c: a=p b=p ..." with that position's
 // alternatives in rank order and their probabilities, and - with --nbest M (1..64) - the M likeliest readings of the word, "<TAB>#i score text".
+//   ocr_cli --lexicon FILE [--lexicon-m M] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: matches every word that is read against the word
+// list in FILE, one word per line (DESIGN.md "Lexicon matching"; empty lines are skipped).  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item, then its M best
+// entries (1..8, default 1), one line each: "<TAB>=i prob word", prob being exp(log-probability) to 6 decimals.  A bad entry fails, naming its index.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <algorithm>
 #include <cmath>
@@ -108,6 +111,39 @@ int main(int argc, const char** argv) {
       }
       return 0;
     }
+    std::string lex_file;
+    int lex_m = 0;
+    while (argc >= 3 && (std::string(argv[1]) == "--lexicon" || std::string(argv[1]) == "--lexicon-m")) {
+      if (std::string(argv[1]) == "--lexicon") lex_file = argv[2];
+      else {
+        char* end = nullptr;
+        const long v = std::strtol(argv[2], &end, 10);
+        if (end == argv[2] || *end || v < 1 || v > 8) throw std::runtime_error("--lexicon-m takes M in 1..8");
+        lex_m = (int)v;
+      }
+      argv[2] = argv[0]; argv += 2; argc -= 2;
+    }
+    if (lex_m && lex_file.empty()) throw std::runtime_error("--lexicon-m needs --lexicon FILE");
+    if (!lex_file.empty()) {
+      if (argc != 4) throw std::runtime_error("--lexicon FILE [--lexicon-m M] goes in front of <image.png> <weights_dir> <outputs_dir>");
+      std::ifstream f(lex_file);
+      if (!f) throw std::runtime_error("cannot read lexicon file " + lex_file);
+      std::vector<std::string> words;
+      for (std::string line; std::getline(f, line);) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (!line.empty()) words.push_back(line);
+      }
+      if (words.empty()) throw std::runtime_error("the lexicon file " + lex_file + " holds no word");
+      pngdec::Image img = pngdec::read(argv[1]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[2], argv[3], false, -1, false, false,
+                                                         false, false, std::string(), std::string(), 0, words, lex_m ? lex_m : 1);
+      if (!last_call_error().empty()) return 1;                         // (the message is on stderr)
+      for (const OutputItemEx& it : items) {
+        printf("%g %g %g %g\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.conf, it.text.c_str());
+        for (const LexMatch& m : it.lexicon) printf("\t=%d %.6f %s\n", m.index, std::exp((double)m.logp), m.word.c_str());
+      }
+      return 0;
+    }
     if (argc == 4 && std::string(argv[1]) == "--decode-only") {
       pngdec::Image img = pngdec::read(argv[2]);
       FILE* f = fopen(argv[3], "wb");
@@ -187,7 +223,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--alts K [--nbest M]] [--rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--alts K [--nbest M] | --lexicon FILE [--lexicon-m M] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

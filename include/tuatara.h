@@ -44,6 +44,11 @@ struct CharAlt {                   // one alternative of one character (characte
   std::string ch;                  // the character
   float prob = 0.f;                // its softmax probability among the allowed characters
 };
+struct LexMatch {                  // one entry of the caller's word list matched against an item (lexicon matching; DESIGN.md "Lexicon matching")
+  int index = -1;                  // the entry's index in the word list
+  std::string word;                // the entry
+  float logp = 0.f;                // its log-probability under the item's per-position distributions, the EOS behind it included
+};
 struct OutputItemEx {
   std::string text;
   std::vector<float> bbox;  // x1, y1, x2, y2
@@ -58,6 +63,7 @@ struct OutputItemEx {
   std::vector<int32_t> alt_ids;    // [26][alt_k]: the K best classes of every position of the recogniser's row (-1 = none), as ttr_result_alt_ids gives them
   std::vector<float> alt_prob;     // [26][alt_k]: their probabilities, as ttr_result_alt_probs gives them
   std::vector<std::vector<CharAlt>> alternatives;   // one list per character of `text`: that position's character options in rank order, the character itself first unless another option ties it
+  std::vector<LexMatch> lexicon;   // lexicon matching: the M best entries of the call's word list by (logp descending, index ascending); empty when no lexicon was given (DESIGN.md "Lexicon matching")
   int block = -1, block_line = -1;  // text blocks: the item's block of its page, in reading order, and its line's position inside that block (what a caller sorts by: block, block_line, word); -1 when blocks are off (DESIGN.md "Text blocks")
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
@@ -150,6 +156,20 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
 std::string last_call_error();
 struct WordReading { std::string text; float score = 0.f; };
 std::vector<WordReading> nbest(const OutputItemEx& item, int m);   // the m best readings (1 <= m <= 64) of an item that carries alternatives; empty otherwise
+
+// Lexicon matching (opt-in; DESIGN.md "Lexicon matching"): every item also gets `lexicon`, the m best entries (1..8) of `words` with their
+// log-probabilities under the recogniser's per-position distributions - what matching against a catalogue, a list of names or a form's field values needs.
+// Entries are 1..25 characters out of the recogniser's set, without ']' and the backslash; a bad entry prints the message naming its index and the result is
+// empty (last_call_error()).  The list is set on the cached engine for the call and cleared afterwards.  Items, order, boxes, text and conf do not change.
+// Like the alternatives it does not combine with word orientation or a bf16 engine.  alts = 0 leaves the alternatives off; the other arguments as above.
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, int alts, const std::vector<std::string>& words, int m);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist, int alts, const std::vector<std::string>& words, int m);
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>& words, int m);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

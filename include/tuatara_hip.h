@@ -466,6 +466,39 @@ int ttr_results_gather_alts(ttr_result* const* rs, int n, int32_t* ids, float* p
 int ttr_logits_alternatives(ttr_engine* e, const float* logits, int n, int k, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* alt_ids,
                             float* alt_probs);
 int ttr_nbest_from_alts(const int32_t* alt_ids, const float* alt_probs, int k, int m, char* texts, size_t cap, float* scores, size_t* need);
+/* Lexicon matching (DESIGN.md "Lexicon matching"): score a caller's word list against each word that is read.  The lexicon holds V words, 1 <= V <= 2^20,
+ * each of 1..25 bytes; every byte names exactly one recogniser class in [1, 95) other than 88 - the characters ttr_charset_mask accepts, without ']' and
+ * without the backslash (which the table lists twice).  Duplicates are allowed.  M = matches kept per item, 1..8.  For item i, under the class mask in force for
+ * that crop (the engine's set, or the region's own), with x the refined logits and id / prob the standard block, all fp32:
+ *   lp[p][c] = (x[p][c] - x[p][id[p]]) + logf(prob[p]) for an allowed class, -inf for a blocked one
+ *   logp(w)  = the sum, in position order from 0.0f, of lp[p][w_p] for p < L, then + lp[L][0] (the EOS behind the word)
+ * lex_idx[j] / lex_logp[j], j < M, are the entries in the total order (logp descending, index ascending); a score that is -inf or NaN is never returned; the
+ * slots left over hold -1 / -INFINITY.  An item whose text (1..25 characters, no id 88 before its EOS) is an entry gets that entry in slot 0 (or an equal
+ * entry of a lower index), with logp = log(conf) up to rounding.  Every other field of a result is bit for bit that of an engine without a lexicon; with
+ * none set no launch, allocation or copy is added.
+ * ttr_engine_set_lexicon: the lexicon for every page entry point (the synchronous calls, the list form, the _v forms, streamed batches, the region calls -
+ * each region under its own set); words = NULL with n_words = 0 clears it (m is then ignored).  The upload is synchronous; the words are copied.  With a
+ * communicator attached each rank's own results carry matches, the gathered payload does not.  It fails, and changes nothing, for a bad word (the message
+ * names the first offending word's index), V or M out of range, while streamed batches are in flight, on a bf16 engine (its kernels take no class mask) and
+ * on an engine with orient != 0 (the chosen turn's logits are gone by the time of the choice).  ttr_pages_to_data_dev_sharded refuses an engine with a
+ * lexicon set.  ttr_engine_lexicon_size / _m: V and M in force (0 = none).  ttr_engine_lexicon_word: entry idx as the engine holds it, NULL out of range;
+ * valid until the next ttr_engine_set_lexicon.
+ * ttr_result_lex_m: M of a result (0 = none).  ttr_result_lex_idx / _logp: item i's [M]; the _all views: [count][M], NULL when off or empty.
+ * ttr_lexicon_encode (host, no engine): the 32-byte device records of n words into records [n][32] - byte 0 the length, bytes 1..L the classes, zeros behind;
+ * applies the validation above.  Returns 0, or -1 with the message in ttr_last_error.
+ * ttr_logits_lexicon (stage; refuses while batches stream): host logits [n][26][95] through decode_conf_kernel and the scorer under the engine's lexicon ->
+ * idx / logp [n][M] (either may be NULL).  sets / n_sets / set_of as in ttr_logits_alternatives. */
+int ttr_engine_set_lexicon(ttr_engine* e, const char* const* words, int n_words, int m);
+int ttr_engine_lexicon_size(const ttr_engine* e);
+int ttr_engine_lexicon_m(const ttr_engine* e);
+const char* ttr_engine_lexicon_word(const ttr_engine* e, int idx);
+int ttr_result_lex_m(const ttr_result* r);
+const int32_t* ttr_result_lex_idx(const ttr_result* r, int i);
+const float* ttr_result_lex_logp(const ttr_result* r, int i);
+const int32_t* ttr_result_lex_idx_all(const ttr_result* r);
+const float* ttr_result_lex_logp_all(const ttr_result* r);
+int ttr_lexicon_encode(const char* const* words, int n, uint8_t* records);
+int ttr_logits_lexicon(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* idx, float* logp);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

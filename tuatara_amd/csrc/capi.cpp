@@ -1090,6 +1090,90 @@ int ttr_nbest_from_alts(const int32_t* alt_ids, const float* alt_probs, int k, i
   TTR_GUARD_END(-1)
 }
 
+int ttr_lexicon_encode(const char* const* words, int n, uint8_t* records) {
+  TTR_GUARD_BEGIN
+  static const Tokenizer tok;
+  lexicon_encode(tok, words, n, records);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_set_lexicon(ttr_engine* e, const char* const* words, int n_words, int m) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  const bool clear = !words && n_words == 0;
+  if (!clear) {
+    if (!words) throw std::runtime_error("ttr_engine_set_lexicon: null argument");
+    if (n_words < 1 || n_words > kLexMaxWords) throw std::runtime_error("ttr_engine_set_lexicon: the number of words must lie in 1..1048576, got " + std::to_string(n_words));
+    if (m < 1 || m > 8) throw std::runtime_error("ttr_engine_set_lexicon: m must lie in 1..8, got " + std::to_string(m));
+  }
+  E.refuse_while_streaming("ttr_engine_set_lexicon");
+  if (clear) {                                    // (off is always accepted; the device records stay allocated for the next list)
+    E.lex_v = 0; E.lex_m = 0; E.lex_words.clear();
+    return 0;
+  }
+  if (E.prec == kBF16)
+    throw std::runtime_error("ttr_engine_set_lexicon: lexicon matching needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which take no class mask");
+  if (E.cfg.orient != TTR_ORIENT_OFF)
+    throw std::runtime_error("ttr_engine_set_lexicon: lexicon matching does not combine with word orientation (the chosen turn's logits are gone by the time of the choice): create the engine with orient = TTR_ORIENT_OFF");
+  std::vector<uint8_t> rec((size_t)n_words * kLexRecord);
+  lexicon_encode(E.tok, words, n_words, rec.data());           // (throws before anything changes: a failed call leaves the previous lexicon in place)
+  std::vector<std::string> copy((size_t)n_words);
+  for (int i = 0; i < n_words; ++i) copy[(size_t)i] = words[i];
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));                // (no batch is in flight; a stage call's launches may still read the previous records)
+  E.lex_v = 0; E.lex_m = 0; E.lex_words.clear();                // (a failed upload leaves no lexicon rather than half of one)
+  E.lex_records.ensure(rec.size());
+  TTR_HIP_CHECK(hipMemcpy(E.lex_records.p, rec.data(), rec.size(), hipMemcpyHostToDevice));
+  E.lex_words.swap(copy);
+  E.lex_v = n_words; E.lex_m = m;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_lexicon_size(const ttr_engine* e) { return e ? e->e->lex_v : 0; }
+
+int ttr_engine_lexicon_m(const ttr_engine* e) { return e ? e->e->lex_m : 0; }
+
+const char* ttr_engine_lexicon_word(const ttr_engine* e, int idx) { return e && idx >= 0 && idx < e->e->lex_v ? e->e->lex_words[(size_t)idx].c_str() : nullptr; }
+
+int ttr_result_lex_m(const ttr_result* r) { return r ? r->r.lex_m : 0; }
+
+const int32_t* ttr_result_lex_idx(const ttr_result* r, int i) { return r && i >= 0 && (size_t)i < r->r.lex_idx.size() / (size_t)std::max(r->r.lex_m, 1) ? &r->r.lex_idx[(size_t)r->r.lex_m * (size_t)i] : nullptr; }
+
+const float* ttr_result_lex_logp(const ttr_result* r, int i) { return r && i >= 0 && (size_t)i < r->r.lex_logp.size() / (size_t)std::max(r->r.lex_m, 1) ? &r->r.lex_logp[(size_t)r->r.lex_m * (size_t)i] : nullptr; }
+
+const int32_t* ttr_result_lex_idx_all(const ttr_result* r) { return r && !r->r.lex_idx.empty() ? r->r.lex_idx.data() : nullptr; }
+
+const float* ttr_result_lex_logp_all(const ttr_result* r) { return r && !r->r.lex_logp.empty() ? r->r.lex_logp.data() : nullptr; }
+
+int ttr_logits_lexicon(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* idx, float* logp) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && !logits) || (sets && n > 0 && !set_of)) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_logits_lexicon");
+  if (!E.lex_v) throw std::runtime_error("ttr_logits_lexicon: no lexicon is set (ttr_engine_set_lexicon)");
+  std::vector<uint32_t> table;
+  ClassMask one = E.charset;
+  if (sets) E.resolve_row_masks("ttr_logits_lexicon", set_of, n, sets, n_sets, table, one);
+  if (n == 0) return 0;
+  const int M = E.lex_m;
+  E.logits.ensure((size_t)n * 26 * 95 * 4);
+  const Engine::RecOut o = E.rec_out(n);
+  const Engine::LexOut l = E.lex_out(n, M);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  const RowMask* rows = E.stage_row_masks(table, 0);
+  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, one, rows);
+  launch_lexicon(E.logits.as<float>(), n, o.ids, o.prob, E.lex_records.p, E.lex_v, M, l.idx, l.logp, l.part_idx, l.part_logp, E.stream, one, rows);
+  if (idx) TTR_HIP_CHECK(hipMemcpyAsync(idx, l.idx, (size_t)n * M * 4, hipMemcpyDeviceToHost, E.stream));
+  if (logp) TTR_HIP_CHECK(hipMemcpyAsync(logp, l.logp, (size_t)n * M * 4, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_confidence_from_probs(const int32_t* ids, const float* probs, int n_pos, float* char_conf, int* n_chars, float* conf) {
   if (!ids || !probs || n_pos < 0) return -1;
   const int k = confidence_from_probs(ids, probs, n_pos, char_conf, conf);

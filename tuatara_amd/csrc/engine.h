@@ -267,6 +267,10 @@ struct Result {
   int alt_k = 0;                   // K: alternatives per position, the winner included
   std::vector<int32_t> alt_ids;    // 26 K per item: the K best allowed classes of every position, -1 in the empty slots (decode_alts.hip)
   std::vector<float> alt_prob;     // 26 K per item: their softmax probabilities; slot 0 is `prob`
+  // lexicon matches (ttr_engine_set_lexicon; DESIGN.md "Lexicon matching"): 0 / empty when no lexicon is set
+  int lex_m = 0;                   // M: matches kept per item
+  std::vector<int32_t> lex_idx;    // M per item: the M best entries of the engine's word list by (logp descending, index ascending), -1 in the empty slots (lexicon.hip)
+  std::vector<float> lex_logp;     // M per item: their log-probabilities, -INFINITY in the empty slots
   // word orientation (cfg.orient != TTR_ORIENT_OFF; DESIGN.md "Word orientation"): empty when off
   std::vector<int32_t> orient;      // 1 per item: the chosen turn 0..3
   std::vector<float> orient_conf;   // orient_k per item: every candidate's conf, ascending turn
@@ -401,6 +405,10 @@ struct Engine {
   std::mutex mu;
   Tokenizer tok;
   int alts = 0;                                   // alternatives per position, 0 = off or 2..8 (ttr_engine_set_alternatives; DESIGN.md "Character alternatives")
+  // lexicon matching (ttr_engine_set_lexicon; DESIGN.md "Lexicon matching"): the caller's word list, off while lex_v == 0
+  int lex_v = 0, lex_m = 0;                       // V words, M matches kept per item (1..8)
+  DevBuf lex_records;                             // [V] 32-byte records: length | 25 class bytes | zero padding (geometry.h: lexicon_encode)
+  std::vector<std::string> lex_words;             // the host copy of the words (ttr_engine_lexicon_word)
   ClassMask charset{};                            // classes the recogniser may not choose (ttr_engine_set_charset; DESIGN.md "Character sets"); zero = no set
 
   // CRAFT
@@ -438,6 +446,17 @@ struct Engine {
   struct AltOut { int* ids; float* prob; };
   static size_t alts_side_bytes(int N, int K) { return (size_t)N * 26 * K * 8; }
   AltOut alts_out(int N, int K) { alts_side.ensure(alts_side_bytes(std::max(N, 1), K)); return AltOut{alts_side.as<int>(), alts_side.as<float>() + (size_t)N * 26 * K}; }
+  DevBuf lex_side, lex_part;                      // lexicon matching: the side block (lexicon.hip), [N][M] int32 idx | [N][M] f32 logp; the scorer's partials [N][chunks][M] idx | logp
+  PinnedBuf h_lex[2];                             // ... per slot: the side block's host copy
+  struct LexOut { int* idx; float* logp; int* part_idx; float* part_logp; };
+  static size_t lex_side_bytes(int N, int M) { return (size_t)N * M * 8; }
+  LexOut lex_out(int N, int M) {
+    N = std::max(N, 1);
+    lex_side.ensure(lex_side_bytes(N, M));
+    const size_t pe = lexicon_partial_entries(N, lex_v, M);
+    lex_part.ensure(pe * 8);
+    return LexOut{lex_side.as<int>(), lex_side.as<float>() + (size_t)N * M, lex_part.as<int>(), lex_part.as<float>() + pe};
+  }
   DevBuf blocks_side;                             // text blocks: the side block (blocks.hip)
   PinnedBuf h_blocks[2];                          // ... per slot: its host copy
   DevBuf chars_map[2], chars_in, chars_side;      // character boxes: per slot the batch's region planes (a copy of ccl.tnorm); coef | page_of | turns | nchars; the side block (chars.hip)
@@ -635,8 +654,10 @@ struct Engine {
   // crops u8 [N][32][128][3] (device) -> logits f32 [N][26][95], ids i32 [N][26], prob f32 [N][26], conf f32 [N] (device); d_ar optional
   // row_masks (device, [N] RowMask; DESIGN.md "Regions and per-row character sets"): crop n chooses its tokens under row_masks[n] instead of `charset`; null = charset
   // d_alt_ids / d_alt_prob (device, [N][26][alts]; DESIGN.md "Character alternatives"): with `alts` set and both given, decode_alts_kernel runs behind the final decode
+  // lex (device; DESIGN.md "Lexicon matching"): with a lexicon set and lex given, the scorer and its merge run behind the final decode; lex->idx / logp are
+  // [N][lex_m], the partials as lex_out sizes them for these N crops
   void parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks = nullptr,
-                      int* d_alt_ids = nullptr, float* d_alt_prob = nullptr);
+                      int* d_alt_ids = nullptr, float* d_alt_prob = nullptr, const LexOut* lex = nullptr);
   // The recogniser's outputs of `rows` crops share one device buffer (ids_dev), laid out [rows][26] ids | [rows][26] prob | [rows] conf, so that
   // one device-to-host copy and one collective carry all three.  Ensures the buffer (never inside a launch function).
   struct RecOut { int* ids; float* prob; float* conf; };
@@ -697,6 +718,7 @@ struct Engine {
     int cap = 0;                       // ... and the largest rank total (rows of the gathered payload per rank)
     int rows = 0;                      // rows of the recogniser's output block (RecOut) staged in h_ids[slot]: max(N, cap)
     int alts = 0;                      // the engine's `alts` when the recogniser was enqueued: h_alts[slot] holds [N][26][alts] ids | prob
+    int lex_m = 0;                     // the engine's `lex_m` when the recogniser was enqueued with a lexicon set (0 = none): h_lex[slot] holds [N][lex_m] idx | logp
     // regions (run_regions; DESIGN.md "Regions and per-row character sets"): the boxes are the caller's quads - no detector ran, `boxes` stays empty, every crop is
     // a kind-1 crop of the table packer.  Crop c (page order, then the caller's order): its quad verbatim, its set index, and - when the sets differ - its row
     // of the class-mask table ({blocked[3], 0}); row_masks empty = every crop reads under region_mask, by value
@@ -760,9 +782,10 @@ struct Engine {
   void finish(PageBatch& B, std::vector<Result>& results);
   // results[pg] for every page of B from its boxes and the decoded rows of its crops (crop c is row c); side: the orientation side block
   // of the batch (orient.hip) or null; lines_side: the text lines' side block (lines.hip) or null; chars_side: the characters' (chars.hip) or null;
-  // blocks_side: the text blocks' (blocks.hip) or null; alts_side: the alternatives' (decode_alts.hip, B.alts per position) or null
+  // blocks_side: the text blocks' (blocks.hip) or null; alts_side: the alternatives' (decode_alts.hip, B.alts per position) or null; lex_side: the
+  // lexicon matches' (lexicon.hip, B.lex_m per item) or null
   void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                    std::vector<Result>& results, const void* alts_side = nullptr);
+                    std::vector<Result>& results, const void* alts_side = nullptr, const void* lex_side = nullptr);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it

@@ -588,6 +588,7 @@ void Engine::recog_enqueue(PageBatch& B) {
   const int line_words = cfg.lines && N > 0 ? stage_batch_lines(B, sl) : 0;   // text lines: the host part, before anything of this batch is enqueued
   if (cfg.chars && N > 0) stage_batch_chars(B, sl);                          // character boxes: likewise
   B.alts = orient_k() > 1 ? 0 : alts;        // character alternatives: fixed for the batch here (the setter refuses while batches stream)
+  B.lex_m = lex_v && orient_k() <= 1 ? lex_m : 0;   // lexicon matching: likewise (0 = no lexicon set)
   range_use(kRangeRec0 + (sl & 1));          // the recogniser's kernels of this batch watch the slot's own word
   B.rows = std::max(N, comm ? B.cap : 0);   // the output block's rows (RecOut): with a communicator, the gathered payload's rows per rank
   const size_t block = (size_t)B.rows * kRecWords * 4;
@@ -604,6 +605,10 @@ void Engine::recog_enqueue(PageBatch& B) {
     // character alternatives: the side block of this batch (the setter refuses an engine with orientation, so T is 0 here)
     const AltOut alt = B.alts ? alts_out(N, B.alts) : AltOut{nullptr, nullptr};
     if (B.alts) h_alts[sl].ensure(alts_side_bytes(N, B.alts));
+    // lexicon matching: the side block and the scorer's partials of this batch
+    const LexOut lexo = B.lex_m ? lex_out(N, B.lex_m) : LexOut{};
+    const LexOut* const lex = B.lex_m ? &lexo : nullptr;
+    if (B.lex_m) h_lex[sl].ensure(lex_side_bytes(N, B.lex_m));
     pack_batch_crops(B, sl);
     if (T) pack_twin_crops(B, sl);
     if (cfg.lines) group_batch_lines(B, sl, line_words);               // text lines: from the boxes alone, so inside the packing stage (DESIGN.md "Text lines")
@@ -612,9 +617,9 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (B.regions) {   // the caller's sets: one mask by value (the engine's own path), or the rows' table through the slot's pinned staging (one copy, no launch)
       struct SetScope { ClassMask& c; ClassMask old; ~SetScope() { c = old; } } set_scope{charset, charset};
       charset = B.region_mask;
-      parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, stage_row_masks(B.row_masks, sl), alt.ids, alt.prob);
+      parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, stage_row_masks(B.row_masks, sl), alt.ids, alt.prob, lex);
     } else
-    parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, nullptr, alt.ids, alt.prob);
+    parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, nullptr, alt.ids, alt.prob, lex);
     if (T) {   // the twins as a pass of their own (turn 0 keeps its batch, and with it its bits), then the choice, in place in the standard block
       parseq_forward(crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, logits.as<float>(), nullptr, cand.ids, cand.prob, cand.conf);
       const size_t first_off = (size_t)T * 84;
@@ -626,6 +631,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     TTR_HIP_CHECK(hipMemcpyAsync(h_ids[sl].p, ids_dev.p, block, hipMemcpyDeviceToHost, stream));   // ids, prob and conf in one copy
     if (T) TTR_HIP_CHECK(hipMemcpyAsync(h_orient[sl].p, orient_side.p, side_b, hipMemcpyDeviceToHost, stream));
     if (B.alts) TTR_HIP_CHECK(hipMemcpyAsync(h_alts[sl].p, alts_side.p, alts_side_bytes(N, B.alts), hipMemcpyDeviceToHost, stream));   // the alternatives' side block, behind the standard block's copy
+    if (B.lex_m) TTR_HIP_CHECK(hipMemcpyAsync(h_lex[sl].p, lex_side.p, lex_side_bytes(N, B.lex_m), hipMemcpyDeviceToHost, stream));   // the lexicon matches' side block, likewise
   } else {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
@@ -663,13 +669,14 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   const void* chars_block = cfg.chars && N > 0 ? h_chars[B.slot].p : nullptr;                   // the side block (chars.hip)
   const int32_t* blocks_block = cfg.blocks && N > 0 ? h_blocks[B.slot].as<int32_t>() : nullptr;   // the side block (blocks.hip)
   const void* alts_block = B.alts && N > 0 ? h_alts[B.slot].p : nullptr;                        // the side block (decode_alts.hip)
-  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block);
+  const void* lex_block = B.lex_m && N > 0 ? h_lex[B.slot].p : nullptr;                         // the side block (lexicon.hip)
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block);
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
 
 void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                          std::vector<Result>& results, const void* alts_side) {
+                          std::vector<Result>& results, const void* alts_side, const void* lex_side) {
   const int n = B.n, N = B.N, K = orient_k();
   const std::vector<int> first = page_first(B.page_of, n);
   // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
@@ -689,6 +696,14 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
       const float* ap = reinterpret_cast<const float*>(ai + (size_t)N * w);
       r.alt_ids.assign(ai + (size_t)c0 * w, ai + (size_t)(c0 + cnt) * w);
       r.alt_prob.assign(ap + (size_t)c0 * w, ap + (size_t)(c0 + cnt) * w);
+    }
+    r.lex_m = B.lex_m;
+    if (lex_side && cnt > 0) {   // [N][M] idx | [N][M] logp -> the page's rows
+      const size_t w = (size_t)B.lex_m;
+      const int32_t* li = static_cast<const int32_t*>(lex_side);
+      const float* ll = reinterpret_cast<const float*>(li + (size_t)N * w);
+      r.lex_idx.assign(li + (size_t)c0 * w, li + (size_t)(c0 + cnt) * w);
+      r.lex_logp.assign(ll + (size_t)c0 * w, ll + (size_t)(c0 + cnt) * w);
     }
     if (K > 1) {
       r.orient_k = K;
@@ -942,6 +957,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   if (cfg.lines) throw std::runtime_error("latency mode does not support text lines: create the engine with lines = 0");
   if (cfg.chars) throw std::runtime_error("latency mode does not support character boxes: create the engine with chars = 0");
   if (alts) throw std::runtime_error("latency mode does not support character alternatives: ttr_engine_set_alternatives(e, 0) first");
+  if (lex_v) throw std::runtime_error("latency mode does not support lexicon matching: ttr_engine_set_lexicon(e, NULL, 0, 0) first");
   if (q1.live || q2.live) throw std::runtime_error("streamed batches are in flight: call ttr_stream_flush until it returns none");
   Comm* const c = comm;
   const int world = c->world, rank = c->rank;

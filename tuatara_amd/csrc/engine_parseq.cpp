@@ -135,7 +135,7 @@ void Engine::decoder_tail(const void* sa, int N, int R, const float* resid_pos, 
 }
 
 void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks,
-                            int* d_alt_ids, float* d_alt_prob) {
+                            int* d_alt_ids, float* d_alt_prob, const LexOut* lex) {
   if (N <= 0) return;
   // A very large crop batch (64 pages of ~150 boxes) goes through in even groups: the refinement pass's widest planes tensor (26 rows per crop x 1536 x 6 bytes)
   // must stay inside the 2 GiB window of 32-bit buffer offsets (8962 crops), and the workspaces stay bounded.  Crops are independent (batch-invariant logits,
@@ -143,11 +143,13 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
   constexpr int kMaxCrops = 4096;
   if (N > kMaxCrops) {
     const int groups = (N + kMaxCrops - 1) / kMaxCrops, per = (N + groups - 1) / groups;
+    LexOut lex_g{};
     for (int g0 = 0; g0 < N; g0 += per) {
       const int n = std::min(per, N - g0);
       parseq_forward(d_crops + (size_t)g0 * 32 * 128 * 3, n, d_logits + (size_t)g0 * 26 * 95, d_ar ? d_ar + (size_t)g0 * 26 * 95 : nullptr, d_ids + (size_t)g0 * 26,
                      d_prob + (size_t)g0 * 26, d_conf + g0, row_masks ? row_masks + g0 : nullptr,   // (rows are never permuted: a group's masks start where its crops do)
-                     d_alt_ids ? d_alt_ids + (size_t)g0 * 26 * alts : nullptr, d_alt_prob ? d_alt_prob + (size_t)g0 * 26 * alts : nullptr);
+                     d_alt_ids ? d_alt_ids + (size_t)g0 * 26 * alts : nullptr, d_alt_prob ? d_alt_prob + (size_t)g0 * 26 * alts : nullptr,
+                     lex ? &(lex_g = LexOut{lex->idx + (size_t)g0 * lex_m, lex->logp + (size_t)g0 * lex_m, lex->part_idx, lex->part_logp}) : nullptr);   // (the groups run one after another on the stream: they share the partials)
     }
     return;
   }
@@ -429,6 +431,8 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
   launch_decode_conf(d_logits, N, d_ids, d_prob, d_conf, stream, charset, row_masks);   // the final argmax with each id's probability and the word's confidence (decode_conf.hip)
   // character alternatives (DESIGN.md "Character alternatives"): the K best allowed classes of every position, from the same logits, mask and standard block
   if (alts && d_alt_ids && d_alt_prob) launch_decode_alts(d_logits, N, d_ids, d_prob, alts, d_alt_ids, d_alt_prob, stream, charset, row_masks);
+  // lexicon matching (DESIGN.md "Lexicon matching"): every word of the caller's list against every crop, from the same logits, mask and standard block
+  if (lex_v && lex) launch_lexicon(d_logits, N, d_ids, d_prob, lex_records.p, lex_v, lex_m, lex->idx, lex->logp, lex->part_idx, lex->part_logp, stream, charset, row_masks);
 }
 
 }  // namespace ttr

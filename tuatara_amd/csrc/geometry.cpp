@@ -11,6 +11,7 @@
 #include <set>
 #include <stdexcept>
 #include <cstdio>
+#include <cstring>
 
 namespace ttr {
 
@@ -819,6 +820,39 @@ int confidence_from_probs(const int* ids, const float* probs, int n, float* char
   }
   if (conf) *conf = c;
   return k;
+}
+
+void lexicon_encode(const Tokenizer& tok, const char* const* words, int n, uint8_t* records) {
+  if (!words || !records) throw std::runtime_error("lexicon: null argument");
+  if (n < 1 || n > kLexMaxWords) throw std::runtime_error("lexicon: the number of words must lie in 1..1048576, got " + std::to_string(n));
+  int cls[256];                                 // byte -> its one class, -1 = none, -2 = more than one
+  for (int b = 0; b < 256; ++b) cls[b] = -1;
+  for (int i = 1; i < 95; ++i) {
+    if (i == 88) continue;                      // ']' : the id that decodes to nothing
+    int& c = cls[(unsigned char)tok.itos[(size_t)i]];
+    c = c == -1 ? i : -2;
+  }
+  cls[(unsigned char)']'] = -1;
+  for (int w = 0; w < n; ++w) {
+    const char* s = words[w];
+    const std::string at = "lexicon: word " + std::to_string(w);
+    if (!s) throw std::runtime_error(at + " is null");
+    const size_t L = strnlen(s, (size_t)kLexMaxLen + 1);
+    if (L == 0) throw std::runtime_error(at + " is empty");
+    if (L > (size_t)kLexMaxLen) throw std::runtime_error(at + " is longer than 25 bytes");
+    uint8_t* r = records + (size_t)w * kLexRecord;
+    memset(r, 0, kLexRecord);
+    r[0] = (uint8_t)L;
+    for (size_t p = 0; p < L; ++p) {
+      const unsigned char ch = (unsigned char)s[p];
+      if (cls[ch] < 0) {
+        char b[16];
+        if (ch >= 0x20 && ch < 0x7f) snprintf(b, sizeof b, "'%c'", ch); else snprintf(b, sizeof b, "'\\x%02x'", ch);
+        throw std::runtime_error(at + " holds " + b + (cls[ch] == -2 ? ", which names two recogniser classes (ids 69 and 87)" : ", which names no recogniser class"));
+      }
+      r[1 + p] = (uint8_t)cls[ch];
+    }
+  }
 }
 
 }  // namespace ttr

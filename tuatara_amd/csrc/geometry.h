@@ -140,4 +140,12 @@ int confidence_from_probs(const int* ids, const float* probs, int n, float* char
 struct Reading { std::string text; float score; };
 std::vector<Reading> nbest_from_alts(const Tokenizer& tok, const int32_t* alt_ids, const float* alt_prob, int k, int m);
 
+// The device records of a word list (DESIGN.md "Lexicon matching"; host only): records receives n records of 32 bytes - byte 0 the word's length L (1..25),
+// bytes 1..L its classes, the rest zero (so the byte behind the last class reads as the EOS, class 0).  Every byte of a word must name exactly one class in
+// [1, 95) other than 88: Tokenizer::itos as charset_mask reads it, without ']' (ids 0 and 88) and without the backslash, which the table lists twice (ids 69 and
+// 87) - a lexicon entry has to say which position class it means, and a backslash cannot.  Throws std::runtime_error naming the first offending word's index
+// for an empty or null word, a word over 25 bytes, and a byte that names no such class; n must lie in 1..2^20.
+constexpr int kLexMaxWords = 1 << 20, kLexMaxLen = 25, kLexRecord = 32;
+void lexicon_encode(const Tokenizer& tok, const char* const* words, int n, uint8_t* records);
+
 }  // namespace ttr

@@ -208,6 +208,15 @@ void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float
 // expf(x[alt_id] - x[id]) * prob (slot 0 = prob bit for bit; 0.f in the empty slots).  K in 2..8.  Reads the logits, ids and prob; writes the two outputs only.
 void launch_decode_alts(const float* logits, int N, const int* ids, const float* prob, int K, int* alt_ids, float* alt_prob, hipStream_t s,
                         ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);
+// lexicon.hip: lexicon matching (DESIGN.md "Lexicon matching"), behind launch_decode_conf on the same logits, mask and standard block.  records: [V] 32-byte
+// records (geometry.h: lexicon_encode).  idx i32 [N][M] / logp f32 [N][M]: per crop the M best words by (logp descending, index ascending), -1 / -INFINITY in
+// the empty slots; a score of -inf or NaN is never returned.  part_idx / part_logp: at least lexicon_partial_entries(N, V, M) entries each, the scorer's
+// per-(crop, chunk) top-M, merged by a second launch.  1 <= V <= 2^20, 1 <= M <= 8.  Reads the logits, ids, prob and records; writes the partials and the two outputs only.
+constexpr int kLexChunk = 1024;        // words per workgroup of the scorer, unless the partials would pass kLexPartialCap
+size_t lexicon_chunk_words(int N, int V, int M);        // the words per workgroup the launcher uses for these sizes: kLexChunk times a power of two
+size_t lexicon_partial_entries(int N, int V, int M);    // entries that hold the partials of any launch of up to N crops
+void launch_lexicon(const float* logits, int N, const int* ids, const float* prob, const void* records, int V, int M, int* idx, float* logp, int* part_idx,
+                    float* part_logp, hipStream_t s, ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);
 // orient.hip: word orientation (DESIGN.md "Word orientation") - per page, the chosen candidate of every word and the page vote.  ids / prob / conf: the
 // standard block of the batch (turn 0), overwritten in place with the chosen readings; cids / cprob / cconf: the (K - 1) N twin rows, candidate-major;
 // first [pages + 1]: each page's first word; side: [N] int32 turn | [N][K] f32 candidate conf | [pages] int32 page turn.  K = 2 or 4.

@@ -64,8 +64,8 @@ struct CharsetScope {
   ttr_engine* e;
   std::unique_lock<std::mutex> turn;
   bool set = false, ok = true;
-  bool alts_set = false;
-  CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0) : e(e_) {
+  bool alts_set = false, lex_set = false;
+  CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0) : e(e_) {
     {
       std::lock_guard<std::mutex> lk(g_mu);
       auto& m = g_call_mu[e];
@@ -81,6 +81,15 @@ struct CharsetScope {
       if (ttr_engine_set_alternatives(e, alts) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
       alts_set = true;
     }
+    if (words) {      // lexicon matching (DESIGN.md "Lexicon matching"): the word list for the call, like the set
+      std::vector<const char*> ptr(words->size());
+      for (size_t i = 0; i < words->size(); ++i) ptr[i] = (*words)[i].c_str();
+      if (ttr_engine_set_lexicon(e, ptr.empty() ? nullptr : ptr.data(), (int)ptr.size(), lex_m) != 0 || ptr.empty()) {
+        g_call_error = ptr.empty() ? "lexicon: the word list is empty" : ttr_last_error();
+        std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return;
+      }
+      lex_set = true;
+    }
     if (allow.empty() && deny.empty()) return;
     if (ttr_engine_set_charset(e, allow.c_str(), deny.c_str()) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
     set = true;
@@ -88,8 +97,15 @@ struct CharsetScope {
   ~CharsetScope() {
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
     if (alts_set) ttr_engine_set_alternatives(e, 0);
+    if (lex_set) ttr_engine_set_lexicon(e, nullptr, 0, 0);
   }
 };
+
+// lexicon matching: the matches' words, read from the engine while the call's list is still set on it (fill() leaves them empty)
+inline void name_matches(ttr_engine*, OutputItem&) {}
+inline void name_matches(ttr_engine* e, OutputItemEx& o) {
+  for (LexMatch& m : o.lexicon) if (const char* w = ttr_engine_lexicon_word(e, m.index)) m.word = w;
+}
 
 template <class Item>
 void fill(Item& o, const ttr_result* r, int i) {   // text and bbox: OutputItem, and the start of OutputItemEx
@@ -139,6 +155,15 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
       o.alternatives.push_back(std::move(alts));
     }
   }
+  o.lexicon.clear();
+  if (const int32_t* li = ttr_result_lex_idx(r, i)) {
+    const float* ll = ttr_result_lex_logp(r, i);
+    for (int j = 0, M = ttr_result_lex_m(r); j < M && li[j] >= 0; ++j) {
+      LexMatch mt;
+      mt.index = li[j]; mt.logp = ll[j];
+      o.lexicon.push_back(std::move(mt));
+    }
+  }
   o.chars.clear();
   if (const int32_t* cf = ttr_result_char_first(r)) {
     const float *cq = ttr_result_char_quads(r), *cb = ttr_result_char_bboxes(r);
@@ -166,10 +191,11 @@ ttr_engine* open_engine(const std::string& weights_dir, const std::string& outpu
 template <class Item>
 std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
                           const std::string& outputs_dir, int crop_mode, int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
-                                        int blocks = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0) {
+                                        int blocks = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0,
+                                        const std::vector<std::string>* words = nullptr, int lex_m = 0) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny, alts);
+  CharsetScope cs(e, allow, deny, alts, words, lex_m);
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
@@ -181,7 +207,7 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
     return {};
   }
   std::vector<Item> out(ttr_result_count(r));
-  for (size_t i = 0; i < out.size(); ++i) fill(out[i], r, (int)i);
+  for (size_t i = 0; i < out.size(); ++i) { fill(out[i], r, (int)i); name_matches(e, out[i]); }
   ttr_result_free(r);
   return out;
 }
@@ -189,10 +215,11 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
 template <class Item>
 std::vector<std::vector<Item>> run_many(const std::vector<ImageView>& images, const std::string& weights_dir, const std::string& outputs_dir, int crop_mode,
                                         int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
-                                        int blocks = -1, int mixed = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0) {
+                                        int blocks = -1, int mixed = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0,
+                                        const std::vector<std::string>* words = nullptr, int lex_m = 0) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks, mixed);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny, alts);
+  CharsetScope cs(e, allow, deny, alts, words, lex_m);
   if (!cs.ok) return {};
   const int n = (int)images.size();
   std::vector<const uint8_t*> ptr(n);
@@ -212,7 +239,7 @@ std::vector<std::vector<Item>> run_many(const std::vector<ImageView>& images, co
   std::vector<std::vector<Item>> out(n);
   for (int i = 0; i < n; ++i) {
     out[i].resize(ttr_result_count(rs[i]));
-    for (size_t k = 0; k < out[i].size(); ++k) fill(out[i][k], rs[i], (int)k);
+    for (size_t k = 0; k < out[i].size(); ++k) { fill(out[i][k], rs[i], (int)k); name_matches(e, out[i][k]); }
     ttr_result_free(rs[i]);
   }
   return out;
@@ -328,6 +355,20 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
                                 blocks ? 1 : -1, mixed_batches ? 1 : -1, allowlist, blocklist, alts);
 }
 
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, int alts, const std::vector<std::string>& words, int m) {
+  return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1,
+                               chars ? 1 : -1, blocks ? 1 : -1, allowlist, blocklist, alts, &words, m);
+}
+
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist, int alts, const std::vector<std::string>& words, int m) {
+  return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
+                                blocks ? 1 : -1, mixed_batches ? 1 : -1, allowlist, blocklist, alts, &words, m);
+}
+
 std::string last_call_error() { return g_call_error; }
 
 std::vector<WordReading> nbest(const OutputItemEx& item, int m) {
@@ -350,8 +391,9 @@ std::vector<WordReading> nbest(const OutputItemEx& item, int m) {
   return out;
 }
 
-std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
-                                           std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts) {
+namespace {
+std::vector<OutputItemEx> read_regions(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
+                                       const std::string& outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>* words, int lex_m) {
   // every list and quad is checked on the host before an engine is opened
   std::vector<ttr_region> regs(regions.size());
   std::vector<uint32_t> sets;
@@ -368,7 +410,7 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
   }
   ttr_engine* e = open_engine(weights_dir, outputs_dir, -1, -1, 0, -1, -1, -1);
   if (!e) return {};
-  CharsetScope cs(e, std::string(), std::string(), alts);   // (the engine's own set for regions without lists: TUATARA_ALLOWLIST / TUATARA_BLOCKLIST; calls that share the engine take turns)
+  CharsetScope cs(e, std::string(), std::string(), alts, words, lex_m);   // (the engine's own set for regions without lists: TUATARA_ALLOWLIST / TUATARA_BLOCKLIST; calls that share the engine take turns)
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
@@ -381,7 +423,18 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
     return {};
   }
   std::vector<OutputItemEx> out(ttr_result_count(r));
-  for (size_t i = 0; i < out.size(); ++i) fill(out[i], r, (int)i);
+  for (size_t i = 0; i < out.size(); ++i) { fill(out[i], r, (int)i); name_matches(e, out[i]); }
   ttr_result_free(r);
   return out;
+}
+}  // namespace
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts) {
+  return read_regions(image, rows, cols, row_stride, weights_dir, outputs_dir, regions, alts, nullptr, 0);
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>& words, int m) {
+  return read_regions(image, rows, cols, row_stride, weights_dir, outputs_dir, regions, alts, &words, m);
 }

@@ -144,6 +144,17 @@ SYMBOLS = [
     ("ttr_results_gather_alts", _I, [C.POINTER(_VP), _I, _PI, _PF]),
     ("ttr_logits_alternatives", _I, [_VP, _PF, _I, _I, C.POINTER(C.c_uint32), _I, _PI, _PI, _PF]),
     ("ttr_nbest_from_alts", _I, [_PI, _PF, _I, _I, C.c_char_p, C.c_size_t, _PF, C.POINTER(C.c_size_t)]),
+    ("ttr_engine_set_lexicon", _I, [_VP, C.POINTER(C.c_char_p), _I, _I]),
+    ("ttr_engine_lexicon_size", _I, [_VP]),
+    ("ttr_engine_lexicon_m", _I, [_VP]),
+    ("ttr_engine_lexicon_word", C.c_char_p, [_VP, _I]),
+    ("ttr_result_lex_m", _I, [_VP]),
+    ("ttr_result_lex_idx", _PI, [_VP, _I]),
+    ("ttr_result_lex_logp", _PF, [_VP, _I]),
+    ("ttr_result_lex_idx_all", _PI, [_VP]),
+    ("ttr_result_lex_logp_all", _PF, [_VP]),
+    ("ttr_lexicon_encode", _I, [C.POINTER(C.c_char_p), _I, _PU8]),
+    ("ttr_logits_lexicon", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _I, _PI, _PI, _PF]),
     ("ttr_craft_heatmap", _I, [_VP, _PU8, _I, _I, _PF]),
     ("ttr_ccl_boxes", _I, [_VP, _PF, _I, _I, _PF, _I, _PI]),
     ("ttr_resize_canvas", _I, [_VP, _PU8, _I, _I, _I, _PU8, C.c_size_t, _PI, _PI, _PF]),
@@ -513,6 +524,38 @@ def nbest_from_alts(alt_ids, alt_prob, m: int):
     return [(texts[i], np.float32(scores[i])) for i in range(n)]
 
 
+def _words_arg(words):
+    """a word list -> (char* array, count, the bytes objects kept alive).  A str travels as _charlist sends it - latin1 where it can, else UTF-8 - so a
+    character outside ASCII reaches the library as bytes that name no class and is refused there, naming the word.  An entry that cannot be encoded or
+    holds a NUL (which would cut it short on the way) is refused here, likewise."""
+    bs = []
+    for i, w in enumerate(words):
+        try:
+            b = bytes(w) if isinstance(w, (bytes, bytearray)) else _charlist(str(w))
+        except UnicodeEncodeError:
+            raise EngineError(f"lexicon: word {i} cannot be encoded") from None
+        if b"\0" in b:
+            raise EngineError(f"lexicon: word {i} holds '\\x00', which names no recogniser class")
+        bs.append(b)
+    arr = (C.c_char_p * max(len(bs), 1))(*bs)
+    return arr, len(bs), bs
+
+
+def lexicon_encode(words) -> np.ndarray:
+    """The 32-byte device records of a word list (ttr_lexicon_encode, no GPU; DESIGN.md "Lexicon matching"): u8 [n, 32] - byte 0 the length, bytes 1..L the
+    classes, zeros behind.  Raises EngineError naming the first offending word's index."""
+    arr, n, _keep = _words_arg(words)
+    rec = np.zeros((max(n, 1), 32), np.uint8)
+    if load().ttr_lexicon_encode(arr, n, _u8(rec)) != 0:
+        raise EngineError(load().ttr_last_error().decode("latin1"))
+    return rec[:n]
+
+
+def lexicon_matches(words, idx, logp) -> list:
+    """one item's matches [(word, prob), ...]: the filled slots of idx / logp [M], prob = exp(logp) in float64"""
+    return [(words[int(i)], float(np.exp(np.float64(l)))) for i, l in zip(idx, logp) if int(i) >= 0]
+
+
 def _is_char(c: int) -> bool:
     return 1 <= c < 95 and c != 88
 
@@ -566,18 +609,23 @@ class PageResult(collections.abc.Sequence):
     blank line); block is None, blocks [] and text_blocks "" when blocks are off.  Character alternatives (Engine.set_alternatives(K); DESIGN.md
     "Character alternatives"): `alt_ids` i32 [n, 26, K] the K best allowed classes of every position (-1 = none; slot 0 is `ids`) and `alt_prob` f32
     [n, 26, K] their probabilities (slot 0 is `prob`); dicts gain "alternatives", one list per character of "text" holding (char, prob) over that
-    position's character options in rank order; nbest(i, m) reads item i's m likeliest whole words; both None when alternatives are off."""
+    position's character options in rank order; nbest(i, m) reads item i's m likeliest whole words; both None when alternatives are off.  Lexicon
+    matching (Engine.set_lexicon(words, m); DESIGN.md "Lexicon matching"): `lex_idx` i32 [n, M] the M best entries of the word list by (logp descending,
+    index ascending), -1 = none, and `lex_logp` f32 [n, M] their log-probabilities (-inf = none); dicts gain "lexicon", [(word, prob), ...] with
+    prob = exp(logp); both None when no lexicon is set."""
     __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
                  "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad",
-                 "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode", "alt_ids", "alt_prob")
+                 "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode", "alt_ids", "alt_prob",
+                 "lex_idx", "lex_logp", "lex_words")
 
     def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0,
                  line=None, word=None, order=None, line_first=None, line_bbox=None,
                  char_first=None, char_quad=None, char_bbox=None, char_cuts=None, char_mode=None, char_profile=None, word_quad=None,
                  block=None, line_block=None, line_pos=None, block_order=None, block_first=None, block_bbox=None, block_mode=0,
-                 alt_ids=None, alt_prob=None):
+                 alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None):
         self.alt_ids, self.alt_prob = alt_ids, alt_prob
+        self.lex_idx, self.lex_logp, self.lex_words = lex_idx, lex_logp, lex_words
         self.block, self.line_block, self.line_pos, self.block_order = block, line_block, line_pos, block_order
         self.block_first, self.block_bbox, self.block_mode = block_first, block_bbox, block_mode
         self.char_first, self.char_quad, self.char_bbox = char_first, char_quad, char_bbox
@@ -618,6 +666,8 @@ class PageResult(collections.abc.Sequence):
                           for k in range(a, b)]
         if self.alt_ids is not None:
             d["alternatives"] = char_alternatives(self.alt_ids[j], self.alt_prob[j])
+        if self.lex_idx is not None:
+            d["lexicon"] = lexicon_matches(self.lex_words, self.lex_idx[j], self.lex_logp[j])
         return d
 
     def nbest(self, i: int, m: int) -> list:
@@ -712,6 +762,8 @@ class Engine:
         cfg.device = device
         cfg.strict_crops = int(strict_crops)
         alts = int(overrides.pop("alts", 0) or 0)                                         # not a config field either: set_alternatives, below
+        lexicon, lexicon_m = overrides.pop("lexicon", None), int(overrides.pop("lexicon_m", 1))   # nor these: set_lexicon, below
+        self._lex_words = []
         tuning = {k: overrides.pop(k) for k in list(overrides) if not hasattr(cfg, k)}     # not a config field: a tuning key (below)
         for k, v in overrides.items():
             setattr(cfg, k, v)
@@ -724,6 +776,55 @@ class Engine:
                 raise EngineError(f"unknown engine option {k!r}")
         if alts:
             self.set_alternatives(alts)
+        if lexicon is not None:
+            self.set_lexicon(lexicon, lexicon_m)
+
+    def set_lexicon(self, words=None, m: int = 1):
+        """The word list every read word is scored against (ttr_engine_set_lexicon; DESIGN.md "Lexicon matching"): words of 1..25 characters out of the
+        recogniser's set (without ']' and the backslash), at most 2^20 of them, duplicates allowed; m = matches kept per item, 1..8.  None clears it.
+        Every page call's PageResult then carries lex_idx / lex_logp and its dicts "lexicon"; every other field keeps its bits.  Raises EngineError, and
+        changes nothing, for a bad word (naming its index), between a stream_push and its flush, on a bf16 engine and with orient set."""
+        if words is None:
+            rc = self.lib.ttr_engine_set_lexicon(self.h, None, 0, 0)
+        else:
+            words = list(words)
+            arr, n, _keep = _words_arg(words)
+            rc = self.lib.ttr_engine_set_lexicon(self.h, arr, n, int(m))
+        if rc != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+        self._lex_words = [] if words is None else [w.decode("latin1") if isinstance(w, bytes) else str(w) for w in words]
+
+    @property
+    def lexicon_size(self) -> int:
+        """V in force (0 = no lexicon)"""
+        return int(self.lib.ttr_engine_lexicon_size(self.h))
+
+    @property
+    def lexicon_m(self) -> int:
+        """M in force (0 = no lexicon)"""
+        return int(self.lib.ttr_engine_lexicon_m(self.h))
+
+    def lexicon_word(self, idx: int):
+        """entry idx as the engine holds it (ttr_engine_lexicon_word), None out of range"""
+        w = self.lib.ttr_engine_lexicon_word(self.h, int(idx))
+        return None if w is None else w.decode("latin1")
+
+    def logits_lexicon(self, logits: np.ndarray, set_of=None, sets=None):
+        """decode_conf_kernel and the lexicon scorer on host logits f32 [n, 26, 95] under the engine's lexicon (ttr_logits_lexicon) -> (idx i32 [n, M],
+        logp f32 [n, M]).  sets None: every row under the engine's own set; else row i under sets[set_of[i]] (uint32 [m, 3] masks), -1 = the engine's own."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, 26, 95)
+        n, M = len(logits), max(self.lexicon_m, 1)
+        idx, logp = np.full((n, M), -1, np.int32), np.full((n, M), -np.inf, np.float32)
+        sp, ns, _keep = _sets_arg(sets)
+        so = None
+        if sp is not None:
+            if set_of is None:
+                raise ValueError("sets need set_of, one entry per row")
+            so = np.ascontiguousarray(set_of, dtype=np.int32).ravel()
+            if len(so) != n:
+                raise ValueError("set_of holds one entry per row")
+        self._check(self.lib.ttr_logits_lexicon(self.h, _f(logits), n, sp, ns, _i(so) if so is not None else None, _i(idx), _f(logp)))
+        return idx, logp
 
     def set_alternatives(self, k: int):
         """K alternatives per character position, the winner included (ttr_engine_set_alternatives; DESIGN.md "Character alternatives"): 0 = off, or
@@ -900,6 +1001,12 @@ class Engine:
         out, k, kl, kc, kbl, kb = [], 0, 0, 0, 0, 0
         for i in range(n):
             c = int(counts[i])
+            lex = {}
+            M = int(self.lib.ttr_result_lex_m(arr[i]))
+            if M:                               # the page's matches (the setter refuses while batches stream: the word list is the one in force)
+                li, ll = self.lib.ttr_result_lex_idx_all(arr[i]), self.lib.ttr_result_lex_logp_all(arr[i])
+                lex = dict(lex_idx=np.ctypeslib.as_array(li, (c, M)).copy() if li else np.zeros((0, M), np.int32),
+                           lex_logp=np.ctypeslib.as_array(ll, (c, M)).copy() if ll else np.zeros((0, M), np.float32), lex_words=self._lex_words)
             orient = (ot[k:k + c], oc[k:k + c], int(op[i])) if self.orienting else (None, None, 0)
             lines = (None,) * 5
             if self.grouping_lines:
@@ -922,7 +1029,7 @@ class Engine:
                 blocks = (bi[k:k], bl[:0], bp[:0], bo[:0], np.zeros(1, np.int32), bbx[:0], 0)
             out.append(PageResult(texts[k:k + c], bb[k:k + c], ids[k:k + c], self._quads(arr[i], c) if self.rectified else None,
                                   cf[k:k + c], pr[k:k + c], conf, *orient, *lines, *chars, *blocks,
-                                  alt_ids=ai[k:k + c] if K else None, alt_prob=ap[k:k + c] if K else None))
+                                  alt_ids=ai[k:k + c] if K else None, alt_prob=ap[k:k + c] if K else None, **lex))
             k += c
             self.lib.ttr_result_free(arr[i])
         return out
@@ -1003,7 +1110,7 @@ class Engine:
         index into charsets, or -1 / absent = the engine's own set}, or of bare quads / rectangles (page 0, the engine's set).  charsets: a list of
         (allow, deny) pairs or ready-made masks.  Returns, per page (for an image: that page alone), the regions in the caller's order as dicts {"text",
         "bbox", "ids", "quad", "conf", "prob", "set", "region"} - "quad" the caller's floats verbatim, "region" the index into `regions`; with set_alternatives(K) also "alt_ids",
-        "alt_prob" ([26, K] arrays) and "alternatives", each region's under its own set."""
+        "alt_prob" ([26, K] arrays) and "alternatives", each region's under its own set; with set_lexicon also "lex_idx", "lex_logp" ([M] arrays) and "lexicon"."""
         regs = (Region * max(len(regions), 1))()
         for i, r in enumerate(regions):
             d = r if isinstance(r, dict) else {"quad" if np.asarray(r).size == 8 else "rect": r}
@@ -1037,6 +1144,8 @@ class Engine:
                               "conf": float(page.conf[k]), "prob": page.prob[k].tolist(), "set": int(sets[k]), "region": where[p][k]})
                 if page.alt_ids is not None:        # character alternatives: each region under its own set
                     items[-1].update({"alt_ids": page.alt_ids[k], "alt_prob": page.alt_prob[k], "alternatives": char_alternatives(page.alt_ids[k], page.alt_prob[k])})
+                if page.lex_idx is not None:        # lexicon matching: each region under its own set
+                    items[-1].update({"lex_idx": page.lex_idx[k], "lex_logp": page.lex_logp[k], "lexicon": lexicon_matches(page.lex_words, page.lex_idx[k], page.lex_logp[k])})
             out.append(items)
         return out[0] if single else out
 
