@@ -67,6 +67,12 @@ int ttr_dbg_attn_enc(ttr_engine* e, const float* qkv, int N, float* out);
  * tuning keys "cross_split", "cross_crop", "cross_rows_hsplit"): q f32 [N * R][384] (R query rows per crop), kvmem f32 [N * 128][768] (K | V of a crop's 128
  * memory tokens) -> out f32 [N * R][384], joined from the exact triples the kernels write */
 int ttr_dbg_cross_attn(ttr_engine* e, const float* q, const float* kvmem, int N, int R, float* out);
+/* test hook for the decoder's self-attention kernel of the split-operand / fp32 engines (parseq_ops.hip: dec_self_attn_kernel), launched the way the engine's
+ * precision launches it (f16x4: exact triples out, joined here; f32: fp32 rows) and without the AR loop's skip counter: q f32 [26][384] (the projected position
+ * queries), kvcache f32 [N][26][768] (K | V per context slot), tokens i32 [N][26] (read in mode 1: id 0 = EOS) -> out f32 [N * R][384].  mode 0 = AR step qi0
+ * (R = 1: keys 0 .. qi0), mode 1 = the refinement pass (R query rows 0 .. R - 1 per crop, R <= 26: cloze mask + key padding from the first EOS on).  K / V rows of
+ * masked keys are not read.  A row the kernel did not write comes back as NaN. */
+int ttr_dbg_dec_self_attn(ttr_engine* e, const float* q, const float* kvcache, const int32_t* tokens, int N, int R, int qi0, int mode, float* out);
 /* test hook for qkv_attn.hip (bf16 engines): x f32 [N][128][384], w [1152][384], b [1152] -> self-attention output [N][128][384] */
 int ttr_dbg_qkv_attn(ttr_engine* e, const float* x, int N, const float* w, const float* b, float* out);
 /* test hook for mlp_fused.hip (bf16 engines): x_out = x + fc2(GELU(fc1(LayerNorm(x)))) over f32 rows [M][384] with weights

@@ -114,3 +114,55 @@ def oracle_logits(parseq, crops, batch=64):
         _oracle_memo[key] = (np.concatenate(refs), np.concatenate(ars))
     r, a = _oracle_memo[key]
     return r.copy(), a.copy()
+
+
+# ---- the same network evaluated in float64: the yardstick of the error-budget tests (|engine - fp64| against |fp32 oracle - fp64|)
+_fp64_models = {}
+_oracle_memo_fp64 = {}
+
+
+def oracle_logits_fp64(parseq, crops, batch=64):
+    """(refined, AR) logits [N, 26, 95] of a float64 deep copy of `parseq`, evaluated under torch's MATH attention backend; memoised like oracle_logits.
+
+    Why the backend is pinned: seen with torch 2.10 on the CPU, the float64 copy on torch's default scaled-dot-product path returns AR logits that are off by
+    0.5 - 1.3 at every AR step whose single query row sees 16 or more keys (steps 15 .. 25); the fp32 model is the same on both paths, and under
+    sdpa_kernel(SDPBackend.MATH) the float64 model agrees with it to ~1e-4 at all 26 steps (tests/test_long_words_cpu.py holds that).  Words of up to ten
+    characters never read those steps, so the default path went unnoticed; any float64 comparison beyond step 14 has to come through here."""
+    import copy
+    import hashlib
+    import torch
+    from torch.nn.attention import SDPBackend, sdpa_kernel
+    key = (id(parseq), batch, crops.shape, hashlib.sha1(np.ascontiguousarray(crops).tobytes()).hexdigest())
+    if key not in _oracle_memo_fp64:
+        if id(parseq) not in _fp64_models:
+            _fp64_models[id(parseq)] = (parseq, copy.deepcopy(parseq).double())          # (the fp32 model is kept alive: its id is the key)
+        p64 = _fp64_models[id(parseq)][1]
+        refs, ars = [], []
+        with torch.no_grad(), sdpa_kernel(SDPBackend.MATH):
+            for i in range(0, len(crops), batch):
+                x = torch.from_numpy(crops[i:i + batch]).permute(0, 3, 1, 2).double().div(255.0)
+                r, a = p64(x, return_ar=True)
+                refs.append(r.numpy())
+                ars.append(a.numpy())
+        _oracle_memo_fp64[key] = (np.concatenate(refs), np.concatenate(ars))
+    r, a = _oracle_memo_fp64[key]
+    return r.copy(), a.copy()
+
+
+# ---- long words: the synthetic PARSeq built with max_len = 30 (tuatara_amd/weights.py: dfa_tables) reads strings of every length 0 .. 25 and beyond
+def long_word_crops() -> np.ndarray:
+    """the 128 noise crops the long-word tests share"""
+    return np.random.default_rng(0).integers(0, 256, (128, 32, 128, 3), dtype=np.uint8)
+
+
+def long_word_lengths(ref: np.ndarray, label: str = "long words") -> dict:
+    """ref: the oracle's refined logits of a long-word batch -> the length figures, printed; ASSERTS what keeps the long-word tests from being vacuous:
+    >= 8 crops with no EOS, >= 4 with the EOS in column 25, >= 1 empty string, >= 500 positions >= 11 up to EOS."""
+    ids = ref.argmax(-1)
+    has, up = (ids == 0).any(1), upto_eos(ids)
+    late = (np.arange(ids.shape[1])[None, :] < up[:, None]) & (np.arange(ids.shape[1])[None, :] >= 11)
+    st = dict(no_eos=int((~has).sum()), eos_25=int((has & (up == 26)).sum()), empty=int((up == 1).sum()), late_positions=int(late.sum()))
+    print(f"{label}: {len(ids)} crops, {st['no_eos']} with no EOS, {st['eos_25']} with the EOS in column 25, {st['empty']} empty strings, {st['late_positions']} positions >= 11 up to EOS; "
+          f"first-EOS columns (26 = none) {np.bincount(np.where(has, up - 1, 26), minlength=27).tolist()}")
+    assert st["no_eos"] >= 8 and st["eos_25"] >= 4 and st["empty"] >= 1 and st["late_positions"] >= 500, st
+    return st

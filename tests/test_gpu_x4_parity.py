@@ -96,15 +96,11 @@ def test_x4_error_budget_against_fp64_parseq(eng_x4, oracle_models):
     128 crops.  The engine's error must stay within 1.5 x the fp32 evaluation's own - in the maximum and at the 99.99th percentile - i.e. the split-operand
     mode behaves like one more fp32 implementation (another summation order), not like a lower precision.  Crops whose fp64 greedy path differs from
     the fp32 one (a near-tie decided the other way: every later logit then belongs to another sentence) are left out and counted."""
-    import torch
     _, parseq = oracle_models
-    p64 = _fp64(parseq)
     rng = np.random.default_rng(64)
     crops = rng.integers(0, 256, (128, 32, 128, 3), dtype=np.uint8)
     ref32, ar32 = _oracle_logits(parseq, crops)
-    with torch.no_grad():
-        r64, a64 = p64(torch.from_numpy(crops).permute(0, 3, 1, 2).double().div(255.0), return_ar=True)
-    r64, a64 = r64.numpy(), a64.numpy()
+    r64, a64 = R.oracle_logits_fp64(parseq, crops)               # (under the math attention backend: see its docstring)
     got, got_ar, ids = eng_x4.parseq_logits(crops, want_ar=True)
     up = R.upto_eos(r64.argmax(-1))
     mask = np.arange(26)[None, :] < up[:, None]

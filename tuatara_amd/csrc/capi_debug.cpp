@@ -235,6 +235,33 @@ int ttr_dbg_cross_attn(ttr_engine* e, const float* q, const float* kvmem, int N,
   TTR_GUARD_END(-1)
 }
 
+int ttr_dbg_dec_self_attn(ttr_engine* e, const float* q, const float* kvcache, const int32_t* tokens, int N, int R, int qi0, int mode, float* out) {
+  TTR_GUARD_BEGIN
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (E.prec == kBF16) throw std::runtime_error("ttr_dbg_dec_self_attn: split-operand / fp32 engines");
+  if (N <= 0 || (mode != 0 && mode != 1)) throw std::runtime_error("ttr_dbg_dec_self_attn: N >= 1, mode 0 or 1");
+  if (mode == 0 ? (R != 1 || qi0 < 0 || qi0 > 25) : (R < 1 || R > 26)) throw std::runtime_error("ttr_dbg_dec_self_attn: mode 0 takes R = 1 and qi0 in 0 .. 25, mode 1 takes R in 1 .. 26");
+  const int planes = E.prec == kSplit ? 3 : 0;   // what the engine's decoder hands its tail: exact triples on f16x4, fp32 rows on f32
+  const size_t nq = (size_t)26 * 384, nkv = (size_t)N * 26 * 768, ntk = (size_t)N * 26, nout = (size_t)N * R * 384, out_bytes = nout * (planes ? 6 : 4);
+  DevBuf dq, dkv, dtk, dout;
+  dq.ensure(nq * 4); dkv.ensure(nkv * 4); dtk.ensure(ntk * 4); dout.ensure(out_bytes);
+  TTR_HIP_CHECK(hipMemcpy(dq.p, q, nq * 4, hipMemcpyHostToDevice));
+  TTR_HIP_CHECK(hipMemcpy(dkv.p, kvcache, nkv * 4, hipMemcpyHostToDevice));
+  TTR_HIP_CHECK(hipMemcpy(dtk.p, tokens, ntk * 4, hipMemcpyHostToDevice));
+  TTR_HIP_CHECK(hipMemsetAsync(dout.p, 0xFF, out_bytes, E.stream));   // a row the kernel leaves out comes back as NaN
+  launch_dec_self_attn(E.prec, dq.as<float>(), dkv.p, dtk.as<int>(), dout.p, N, R, qi0, mode, E.stream, nullptr, 0, planes);   // no skip counter: every row is written
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  if (!planes) { TTR_HIP_CHECK(hipMemcpy(out, dout.p, nout * 4, hipMemcpyDeviceToHost)); return 0; }
+  std::vector<_Float16> h(nout * 3);
+  TTR_HIP_CHECK(hipMemcpy(h.data(), dout.p, out_bytes, hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < (size_t)N * R; ++r)
+    for (int c = 0; c < 384; ++c)
+      out[r * 384 + c] = (float)h[r * 1152 + c] + ((float)h[r * 1152 + 384 + c] + (float)h[r * 1152 + 768 + c]) * (1.f / 2048.f);   // split.h: join3
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_dbg_conv_pool(ttr_engine* e, const float* in0, int C0, int B, int H, int W, int ks, const float* wgt, const float* bias, int Cout, int act,
                       int pool_relu, float* out_full, float* out_pool) {
   TTR_GUARD_BEGIN

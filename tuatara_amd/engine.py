@@ -190,6 +190,7 @@ SYMBOLS = [
     ("ttr_last_host_us", None, [_VP, _PF]),
     ("ttr_dbg_attn_enc", _I, [_VP, _PF, _I, _PF]),
     ("ttr_dbg_cross_attn", _I, [_VP, _PF, _PF, _I, _I, _PF]),
+    ("ttr_dbg_dec_self_attn", _I, [_VP, _PF, _PF, _PI, _I, _I, _I, _I, _PF]),
     ("ttr_dbg_qkv_attn", _I, [_VP, _PF, _I, _PF, _PF, _PF]),
     ("ttr_dbg_mlp", _I, [_VP, _PF, _I, _PF, _PF, C.c_float, _PF, _PF, _PF, _PF, _PF, _PF, _PF, _PF, _PF, _PF, _PF]),
     ("ttr_dbg_dec_stamps", _I, [C.POINTER(C.c_ulonglong)]),
@@ -1245,6 +1246,17 @@ class Engine:
         N, R = q.shape[0], q.shape[1]
         out = np.zeros((N, R, 384), np.float32)
         self._check(self.lib.ttr_dbg_cross_attn(self.h, _f(q), _f(kvmem), N, R, _f(out)))
+        return out
+
+    def dbg_dec_self_attn(self, q, kvcache, tokens, R: int, qi0: int, mode: int):
+        """The decoder's self-attention kernel on its own: q [26, 384], kvcache [N, 26, 768] (K | V), tokens i32 [N, 26]; mode 0 = AR step qi0 (R = 1),
+        mode 1 = refinement (R rows per crop) -> [N, R, 384] (split / fp32 engines; a row the kernel left out is NaN)."""
+        q = np.ascontiguousarray(q, np.float32); kvcache = np.ascontiguousarray(kvcache, np.float32); tokens = np.ascontiguousarray(tokens, np.int32)
+        N = kvcache.shape[0]
+        if q.shape != (26, 384) or kvcache.shape != (N, 26, 768) or tokens.shape != (N, 26):
+            raise ValueError("q [26, 384], kvcache [N, 26, 768], tokens [N, 26]")
+        out = np.zeros((N, int(R), 384), np.float32)
+        self._check(self.lib.ttr_dbg_dec_self_attn(self.h, _f(q), _f(kvcache), _i(tokens), N, int(R), int(qi0), int(mode), _f(out)))
         return out
 
     def dbg_qkv_attn(self, x, w, b):

@@ -199,7 +199,7 @@ def _wire_ink_pathway(st: State, gain: float = 6.0) -> None:
     st["conv_cls.8.bias"][:] = 1.0
 
 
-def synth_parseq(seed: int = 0, eos_shift: float = 1.7, head_gain: float = 6.0, sharp: float = 3.0, structured: bool = True) -> State:
+def synth_parseq(seed: int = 0, eos_shift: float = 1.7, head_gain: float = 6.0, sharp: float = 3.0, structured: bool = True, max_len: int = 10) -> State:
     """Seeded PARSeq weights.  1/sqrt(fan_in) linears (O(1) residual updates),
     LayerNorm near identity, q/k projections scaled by ``sharp`` so attention is
     peaked, a head gain so logits have std ~``head_gain`` and an EOS shift.
@@ -210,7 +210,7 @@ def synth_parseq(seed: int = 0, eos_shift: float = 1.7, head_gain: float = 6.0, 
     crops and string equality says little.  ``structured`` (the default) therefore
     wires a confident, "trained-like" read-out on 64 reserved channels on top of
     the random model (``_wire_parseq_dfa``) and turns the random head down to a
-    texture of std ~0.5."""
+    texture of std ~0.5.  ``max_len``: the longest designed string (``dfa_tables``)."""
     rng = np.random.default_rng(seed + 1000)
     st: State = {}
     E = EMBED
@@ -237,7 +237,7 @@ def synth_parseq(seed: int = 0, eos_shift: float = 1.7, head_gain: float = 6.0, 
         st[name] = v
     if structured:
         st["head.weight"] *= np.float32(0.5)          # texture: logit std ~0.5 under the designed read-out
-        _wire_parseq_dfa(st)
+        _wire_parseq_dfa(st, max_len=max_len)
     else:
         st["head.weight"] *= np.float32(head_gain)
         st["head.bias"][0] += np.float32(eos_shift * head_gain)
@@ -264,7 +264,7 @@ A_ONE, A_POS, A_TOK = 2.0, 3.0, 1.0
 DFA_FIRST_BITS = 6                     # content bits 0..5 choose the first character (bits 6..7 are computed and not read)
 
 
-def dfa_tables(seed: int = 0):
+def dfa_tables(seed: int = 0, max_len: int = 10):
     """The string a crop decodes to under the designed read-out: first[v] (v = content bits 0..5 as an integer) is
     the first class id, nxt[t] the class that follows class t; class 0 is EOS.  first is Gray-like in the content bits -
     flipping one content bit flips exactly one bit of the 7-bit class code (first[v] = v) - so that near a content-bit
@@ -272,11 +272,12 @@ def dfa_tables(seed: int = 0):
     reference tokenizer's shifted ids 69..94 and its eos_id 88 (tuatara.cpp:31-48) all occur in decoded strings."""
     rng = np.random.default_rng(seed + 4242)
     first = np.arange(64, dtype=np.int64)
-    # every class has a level 1..10 = the length of the string that starts with it (config 5 draws words of 3-10 characters);
-    # nxt[t] is a random class one level down, level-1 classes end the string: every chain reaches EOS within 10 steps, so a
-    # batch's autoregressive loop can stop early the way upstream PARSeq's does
+    # every class has a level 1..max_len (10 by default) = the length of the string that starts with it (config 5 draws words of 3-10 characters);
+    # nxt[t] is a random class one level down, level-1 classes end the string: every chain reaches EOS within max_len steps, so at the default a
+    # batch's autoregressive loop can stop early the way upstream PARSeq's does.  max_len > 25 (tests/test_gpu_long_words.py): some chains are longer
+    # than the 26 positions a crop has - such a crop never emits EOS and the AR loop runs to its last step
     level = np.zeros(95, np.int64)
-    level[1:] = 1 + rng.permutation(94) % 10
+    level[1:] = 1 + rng.permutation(94) % max_len
     nxt = np.zeros(95, np.int64)
     for t in range(1, 95):
         if level[t] > 1:
@@ -288,7 +289,7 @@ def _code(c: int) -> np.ndarray:
     return np.array([1.0 if (c >> k) & 1 else -1.0 for k in range(N_CODE)], np.float32)
 
 
-def _wire_parseq_dfa(st: State, seed: int = 0) -> None:
+def _wire_parseq_dfa(st: State, seed: int = 0, max_len: int = 10) -> None:
     """Hand-wired confident read-out (the PARSeq counterpart of ``_wire_ink_pathway``), every stage through the
     same kernels as the random part:
 
@@ -308,7 +309,7 @@ def _wire_parseq_dfa(st: State, seed: int = 0) -> None:
     logit margin shrinks continuously, so a decision that bf16 noise can flip shows a small fp32 margin."""
     E = EMBED
     R = slice(RES0, E)
-    first, nxt = dfa_tables(seed)
+    first, nxt = dfa_tables(seed, max_len)
 
     def put(w: np.ndarray, row: int, cols: Dict[int, float]) -> None:
         """w[row, c] = v for the reserved input channels c, and minus their sum on ZERO (mean-free row)."""
@@ -613,9 +614,10 @@ def export_parseq(st: State, weights_dir: str) -> str:
     return path
 
 
-def make_synthetic_weights(weights_dir: str, seed: int = 0, structured: bool = True) -> Tuple[State, State]:
-    """Write ``craft.ttrw`` + ``parseq.ttrw`` for ``seed`` (idempotent) and return the raw state dicts."""
-    c, p = synth_craft(seed, structured), synth_parseq(seed, structured=structured)
+def make_synthetic_weights(weights_dir: str, seed: int = 0, structured: bool = True, max_len: int = 10) -> Tuple[State, State]:
+    """Write ``craft.ttrw`` + ``parseq.ttrw`` for ``seed`` (idempotent) and return the raw state dicts.  ``max_len``: the longest string of the designed PARSeq
+    read-out (``dfa_tables``); the default is the benchmark's and the golden files' model."""
+    c, p = synth_craft(seed, structured), synth_parseq(seed, structured=structured, max_len=max_len)
     export_craft(c, weights_dir)
     export_parseq(p, weights_dir)
     return c, p
