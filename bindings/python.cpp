@@ -25,6 +25,10 @@
 // And keyword-only lexicon=None, lexicon_m=1 on both calls: lexicon=[words] gives every dict "lexicon", [(word, prob), ...] over the lexicon_m (1..8) best
 // entries of the list for that item, prob = exp(log-probability) in double (DESIGN.md "Lexicon matching"); set on the cached engine for the call and cleared
 // afterwards.  A bad entry raises ValueError naming its index (the engine's own message; nothing is read).  It combines with everything above except orient.
+// And a keyword-only pattern=None on both calls: a regular expression every word must match (DESIGN.md "Patterns"; the subset of Python's re that
+// include/tuatara_hip.h lists), set on the cached engine for the call and reset afterwards, also when the call raises; calls that share the engine take turns.
+// "pattern" is also a key of a regions= dict: that region's own.  A bad pattern raises ValueError, naming the offset or the character, before anything runs;
+// a pattern with orient, alts or lexicon raises ValueError too.  The dicts' keys do not change.
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -133,6 +137,21 @@ static void charset_args(const py::object& allow_kw, const py::object& deny_kw, 
   if ((!allow.empty() || !deny.empty()) && ttr_charset_mask(allow.c_str(), deny.c_str(), mask) < 0) throw std::invalid_argument(ttr_last_error());
 }
 
+// pattern = None | str -> the string ("" = not given), compiled on the host under the call's lists (ttr_pattern_compile): a bad one raises ValueError
+static std::string pattern_arg(const py::object& pattern_kw, const std::string& allow, const std::string& deny, const std::string& at = std::string()) {
+  if (pattern_kw.is_none()) return std::string();
+  std::string p;
+  try { p = pattern_kw.cast<std::string>(); } catch (const py::cast_error&) { throw std::invalid_argument(at + "pattern must be None or a string"); }
+  if (p.empty()) return p;
+  uint32_t mask[3];
+  const bool cset = !allow.empty() || !deny.empty();
+  if (cset && ttr_charset_mask(allow.c_str(), deny.c_str(), mask) < 0) throw std::invalid_argument(at + ttr_last_error());
+  ttr_pattern* cp = nullptr;
+  if (ttr_pattern_compile(p.c_str(), cset ? mask : nullptr, &cp) != 0) throw std::invalid_argument(at + ttr_last_error());
+  ttr_pattern_free(cp);
+  return p;
+}
+
 // regions=[{...}, ...] -> RegionSpecs; every entry is checked here, on the host, so a bad list raises ValueError before anything runs
 static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
   std::vector<RegionSpec> out;
@@ -144,7 +163,7 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
     py::dict d = py::reinterpret_borrow<py::dict>(h);
     for (auto kv : d) {
       const std::string k = py::str(kv.first);
-      if (k != "quad" && k != "rect" && k != "allowlist" && k != "blocklist") throw std::invalid_argument(at + "unknown key \"" + k + "\"");
+      if (k != "quad" && k != "rect" && k != "allowlist" && k != "blocklist" && k != "pattern") throw std::invalid_argument(at + "unknown key \"" + k + "\"");
     }
     if (d.contains("quad") == d.contains("rect")) throw std::invalid_argument(at + "give \"quad\" or \"rect\" (one of them)");
     RegionSpec s;
@@ -173,6 +192,7 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
     } catch (const py::cast_error&) { throw std::invalid_argument(at + "\"allowlist\" / \"blocklist\" are strings"); }
     uint32_t mask[3];
     if ((!s.allowlist.empty() || !s.blocklist.empty()) && ttr_charset_mask(s.allowlist.c_str(), s.blocklist.c_str(), mask) < 0) throw std::invalid_argument(at + ttr_last_error());
+    if (d.contains("pattern")) s.pattern = pattern_arg(py::reinterpret_borrow<py::object>(d["pattern"]), s.allowlist, s.blocklist, at);
     out.push_back(std::move(s));
   }
   return out;
@@ -180,19 +200,28 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
 
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
-                                      bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m) {
+                                      bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
+                                      py::object pattern_kw) {
   const int orient = orient_mode(orient_kw);
   alts_arg(alts);
   std::vector<std::string> words;
   const bool lex = lexicon_args(lexicon, lexicon_m, words);
   std::string allow, deny;
   charset_args(allowlist, blocklist, allow, deny);
+  const std::string pattern = pattern_arg(pattern_kw, allow, deny);
+  if (!pattern.empty() && (orient || alts || lex)) throw std::invalid_argument("pattern does not combine with orient, alts or lexicon");
   const bool cset = !allow.empty() || !deny.empty();
   lines = lines || blocks;   // blocks are made of lines
   if (!regions_kw.is_none()) {   // regions: no detector; every check before anything runs
     if (rectify || orient || orient_page || lines || chars || blocks) throw std::invalid_argument("regions do not combine with rectify, orient, lines, chars or blocks: a region is read as the quad it is");
     std::vector<RegionSpec> regs = region_args(regions_kw);
     for (RegionSpec& s : regs) if (s.allowlist.empty() && s.blocklist.empty()) { s.allowlist = allow; s.blocklist = deny; }   // the call's own lists where a region has none
+    for (RegionSpec& s : regs) {
+      if (s.pattern.empty()) s.pattern = pattern;                                                                              // ... and its pattern
+      if (!s.pattern.empty() && (alts || lex)) throw std::invalid_argument("pattern does not combine with orient, alts or lexicon");
+    }
+    bool with_pattern = false;
+    for (const RegionSpec& s : regs) with_pattern = with_pattern || !s.pattern.empty();
     py::buffer_info rb = image.request();
     if (rb.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
     if (rb.shape[2] != 3) throw std::runtime_error("Input array should have 3 channels");
@@ -202,7 +231,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
       got = lex ? image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts, words, lexicon_m)
                 : image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts);
     }
-    if ((alts || lex) && got.empty()) raise_refused();
+    if ((alts || lex || with_pattern) && got.empty()) raise_refused();
     py::list res;
     for (const auto& item : got) {
       py::dict d = item_dict(item, Keys{true, conf, false, false, false, false, alts != 0, lex});
@@ -219,7 +248,8 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   std::vector<OutputItemEx> items;
   {
     py::gil_scoped_release nogil;   // (orient = None: the 7-argument call, which leaves the orientation to TUATARA_ORIENT)
-    items = lex      ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts, words, lexicon_m)
+    items = !pattern.empty() ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, pattern)
+            : lex    ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts, words, lexicon_m)
             : alts   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts)
             : cset   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny)
             : blocks ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, true, chars, true)
@@ -228,7 +258,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
             : orient ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
                      : image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
   }
-  if ((alts || lex) && items.empty()) raise_refused();
+  if ((alts || lex || !pattern.empty()) && items.empty()) raise_refused();
   py::list result;
   for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex}));
   return result;
@@ -240,13 +270,15 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
 // Keyword-only mixed_batches=False: True batches images that share one detector canvas, whatever their sizes (DESIGN.md "Mixed-size batches"); same results.
 static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf, py::object orient_kw,
                                        bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches, py::object allowlist, py::object blocklist, int alts,
-                                       py::object lexicon, int lexicon_m) {
+                                       py::object lexicon, int lexicon_m, py::object pattern_kw) {
   const int orient = orient_mode(orient_kw);
   alts_arg(alts);
   std::vector<std::string> words;
   const bool lex = lexicon_args(lexicon, lexicon_m, words);
   std::string allow, deny;
   charset_args(allowlist, blocklist, allow, deny);
+  const std::string pattern = pattern_arg(pattern_kw, allow, deny);
+  if (!pattern.empty() && (orient || alts || lex)) throw std::invalid_argument("pattern does not combine with orient, alts or lexicon");
   const bool cset = !allow.empty() || !deny.empty();
   lines = lines || blocks;   // blocks are made of lines
   std::vector<py::array_t<unsigned char, py::array::c_style | py::array::forcecast>> keep;   // contiguous uint8 views / copies, alive for the call
@@ -263,7 +295,8 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   std::vector<std::vector<OutputItemEx>> pages;
   {
     py::gil_scoped_release nogil;
-    pages = lex ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts, words, lexicon_m)
+    pages = !pattern.empty() ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, pattern)
+            : lex ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts, words, lexicon_m)
             : alts ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts)
             : cset ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny)
             : mixed_batches ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, true)
@@ -273,7 +306,7 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
             : orient ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient, orient_page)
                      : images_to_data_ex(views, weights_dir, output_dir, rectify);
   }
-  if ((alts || lex) && pages.empty() && !views.empty()) raise_refused();
+  if ((alts || lex || !pattern.empty()) && pages.empty() && !views.empty()) raise_refused();
   py::list result;
   for (const auto& items : pages) {
     py::list page;
@@ -287,8 +320,8 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
 }

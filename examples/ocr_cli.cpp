@@ -16,6 +16,9 @@
 // after block in reading order - a column to its end before the next -, one line of the page per output line and an empty line between blocks.
 //   ocr_cli --allowlist S --blocklist S ...                      in front of any form above: the characters the recogniser may / may not emit (DESIGN.md
 // "Character sets"), e.g. --allowlist 0123456789 for a field of digits.  They reach the call as TUATARA_ALLOWLIST / TUATARA_BLOCKLIST.
+//   ocr_cli --pattern P ...                                      in front of any form above: a regular expression every word must match (DESIGN.md "Patterns"),
+// e.g. --pattern '\d{2}/\d{2}/\d{4}' for dates.  It reaches the call as TUATARA_PATTERN; a bad pattern fails, naming the offset or the character, before the
+// image is read.
 //   ocr_cli --regions FILE <image.png> <weights_dir> <outputs_dir>   reads the regions FILE lists, with no detector, each under its own character set
 // (DESIGN.md "Regions and per-row character sets").  One region per line: "x0 y0 x1 y1 [allow [deny]]" - the pixels [x0, x1) x [y0, y1) - or eight floats
 // "tl.x tl.y tr.x tr.y br.x br.y bl.x bl.y [allow [deny]]"; '#' starts a comment.  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per region, in the file's
@@ -36,6 +39,7 @@
 #include <sstream>
 
 #include "../include/tuatara.h"
+#include "../include/tuatara_hip.h"
 #include "png_decode.h"
 
 // --regions FILE: one RegionSpec per line (see the top of the file); throws, naming the line, on anything else
@@ -77,8 +81,14 @@ static std::vector<RegionSpec> read_regions(const char* path) {
 
 int main(int argc, const char** argv) {
   try {
-    while (argc >= 3 && (std::string(argv[1]) == "--allowlist" || std::string(argv[1]) == "--blocklist")) {   // leading options, any order
-      setenv(std::string(argv[1]) == "--allowlist" ? "TUATARA_ALLOWLIST" : "TUATARA_BLOCKLIST", argv[2], 1);
+    while (argc >= 3 && (std::string(argv[1]) == "--allowlist" || std::string(argv[1]) == "--blocklist" || std::string(argv[1]) == "--pattern")) {   // leading options, any order
+      const std::string opt = argv[1];
+      if (opt == "--pattern") {   // checked here, on the host, under every class: the engine compiles it again under the set in force
+        ttr_pattern* p = nullptr;
+        if (ttr_pattern_compile(argv[2], nullptr, &p) != 0) throw std::runtime_error(std::string("--pattern: ") + ttr_last_error());
+        ttr_pattern_free(p);
+      }
+      setenv(opt == "--allowlist" ? "TUATARA_ALLOWLIST" : opt == "--blocklist" ? "TUATARA_BLOCKLIST" : "TUATARA_PATTERN", argv[2], 1);
       argv[2] = argv[0]; argv += 2; argc -= 2;
     }
     int alts = 0, nbest_m = 0;
@@ -223,7 +233,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--alts K [--nbest M] | --lexicon FILE [--lexicon-m M] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--pattern P] [--alts K [--nbest M] | --lexicon FILE [--lexicon-m M] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

@@ -133,6 +133,7 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
 struct RegionSpec {
   std::vector<float> quad;          // 8: tl.x, tl.y, tr.x, tr.y, br.x, br.y, bl.x, bl.y
   std::string allowlist, blocklist;
+  std::string pattern;              // the region's own pattern (below); empty = the call's own (TUATARA_PATTERN, else none)
 };
 RegionSpec region_from_rect(int x0, int y0, int x1, int y1, std::string allowlist = std::string(), std::string blocklist = std::string());
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
@@ -170,6 +171,18 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
                                                          std::string allowlist, std::string blocklist, int alts, const std::vector<std::string>& words, int m);
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>& words, int m);
+
+// Patterns (opt-in; DESIGN.md "Patterns"): pattern = a regular expression every word must match - "\\d{2}/\\d{2}/\\d{4}" for a date, "[A-Z]{2}\\d{2,6}" for
+// a plate; the syntax is the subset of Python's re that include/tuatara_hip.h lists.  The pattern acts where each character is chosen: every returned text is
+// a member of its language, and conf / char_conf are probabilities over the choices it left open.  It is set on the cached engine for the call and reset
+// afterwards.  An empty string is the call above, unless TUATARA_PATTERN is set in the environment, which then applies to every call here.  A bad pattern, a
+// bf16 engine, or an engine with word orientation, alternatives or a lexicon turned on: the message is printed and the result is empty (last_call_error()).
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, std::string pattern);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist, std::string pattern);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

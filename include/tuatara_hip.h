@@ -434,6 +434,49 @@ int ttr_parseq_logits_sets(ttr_engine* e, const uint8_t* crops, int n, const uin
                            float* ar_logits, int32_t* ids);
 int ttr_logits_confidence_sets(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* ids,
                                float* probs, float* conf);
+/* Patterns (DESIGN.md "Patterns"): constrain each word to a regular expression - a date \d{2}/\d{2}/\d{4}, an amount \d+\.\d{2}, a plate
+ * [A-Z]{2}\d{2,6} - where each token is chosen: with a pattern in force every returned text (of at most 25 characters, under the character set in
+ * force) is a member of the pattern's language, and prob / conf are probabilities over the choices the pattern left open.
+ * The syntax is a strict subset of Python's re / POSIX ERE, so re.fullmatch checks a text independently: literals; `\` + a punctuation character as that
+ * literal; \d = [0-9]; \w = [A-Za-z0-9_]; `.` = every usable class; [...] with ranges and a leading ^; ( ... ) groups with |; the quantifiers ? * +
+ * {m} {m,n} {m,} with 0 <= m <= n <= 25 on an atom or group.  Anchors, back-references, lazy and possessive quantifiers are refused.  The alphabet is the
+ * recogniser's classes 1..94 without 88 (which decodes to nothing); a backslash stands for ids 69 and 87; a blank, '~', a non-ASCII byte and a ']' outside
+ * its role as the set terminator name no class and are refused by name.  A pattern is compiled under a class mask (ttr_charset_mask's form; NULL = every
+ * class): a transition on a blocked class does not exist.  Refused, naming the figure: more than 255 bytes, more than 256 states after minimisation, an
+ * empty language, a shortest member of more than 25 characters.
+ * ttr_pattern_compile: host only, no engine; *out is freed by ttr_pattern_free.  ttr_pattern_states: states of the minimal automaton (its DONE state not
+ * counted); ttr_pattern_min_length: characters of the shortest member; ttr_pattern_table: delta u16 [states + 1][96] (0xFFFF = none; column 0 = the end of
+ * the text, which leads from an accepting state to the DONE state; the DONE row holds itself on every class of the mask), mind u8 [states + 1] (characters
+ * to acceptance; 255 for DONE), the start state and the DONE state; ttr_pattern_matches: 1 = member, 0 = not, -1 = text names no class somewhere.
+ * The choice rule, at character position p (0..25) in state s: class c with t = delta[s][c] may be chosen iff t != 0xFFFF and (c == 0 or mind[t] == 255
+ * or p + 1 + mind[t] <= 25); the token is the first maximal index among those classes, then s = t.
+ * ttr_engine_set_pattern: the engine's pattern (NULL or "": none), compiled under the engine's character set and recompiled when ttr_engine_set_charset
+ * changes it (a set that would leave the pattern an empty language fails and leaves both as they were).  Every page entry point, ttr_parseq_logits and the
+ * region calls (each region under its own set) then read every word under it.  It fails, and changes nothing, while streamed batches are in flight, on a
+ * bf16 engine, and on an engine with orient, alternatives or a lexicon set; ttr_engine_set_alternatives and ttr_engine_set_lexicon refuse while a pattern
+ * is set.  With a communicator attached every rank must be given the same pattern.  Without a pattern no launch, upload or bit differs from before.
+ * ttr_regions_to_data_dev_p / ttr_image_regions_to_data_p: the region calls with a pattern per region - region i reads under patterns[pattern_of[i]], -1 =
+ * the engine's own pattern (or none); each distinct (pattern, resolved mask) pair is compiled once into one table of at most 1024 states.  They refuse what
+ * the region calls refuse, and a pattern index out of range, a bad pattern (naming the region) and a table over 1024 states (naming the total).
+ * Stage twins: ttr_parseq_logits_patterns - ttr_parseq_logits_sets with patterns; ttr_logits_decode_patterns - the final decode under patterns alone, row
+ * by row: host logits [n][26][95] -> ids, probs [n][26], conf [n] (set_of may be NULL: every row under the engine's set). */
+typedef struct ttr_pattern ttr_pattern;
+int ttr_pattern_compile(const char* pattern, const uint32_t* mask /* [3] or NULL */, ttr_pattern** out);
+void ttr_pattern_free(ttr_pattern* p);
+int ttr_pattern_states(const ttr_pattern* p);
+int ttr_pattern_min_length(const ttr_pattern* p);
+int ttr_pattern_table(const ttr_pattern* p, const uint16_t** delta, const uint8_t** mind, int* start, int* done);
+int ttr_pattern_matches(const ttr_pattern* p, const char* text);
+int ttr_engine_set_pattern(ttr_engine* e, const char* pattern);
+const char* ttr_engine_get_pattern(const ttr_engine* e);
+int ttr_regions_to_data_dev_p(ttr_engine* e, const ttr_page* pages, int n_pages, const ttr_region* regions, int n, const uint32_t* sets, int n_sets,
+                              const char* const* patterns, int n_patterns, const int32_t* pattern_of, ttr_result** out);
+int ttr_image_regions_to_data_p(ttr_engine* e, const uint8_t* hwc_u8, int h, int w, int row_stride, const ttr_region* regions, int n, const uint32_t* sets,
+                                int n_sets, const char* const* patterns, int n_patterns, const int32_t* pattern_of, ttr_result** out);
+int ttr_parseq_logits_patterns(ttr_engine* e, const uint8_t* crops, int n, const uint32_t* sets, int n_sets, const int32_t* set_of,
+                               const char* const* patterns, int n_patterns, const int32_t* pattern_of, float* logits, float* ar_logits, int32_t* ids);
+int ttr_logits_decode_patterns(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of,
+                               const char* const* patterns, int n_patterns, const int32_t* pattern_of, int32_t* ids, float* probs, float* conf);
 /* Character alternatives (DESIGN.md "Character alternatives"): what else each character could have been.  K = alternatives per position, the winner
  * included: 0 (off, the default) or 2..8.  For item i and position p (0..25), under the class mask in force for that crop (the engine's set, or the region's
  * own): alt_ids[p][j], j < K, are the allowed classes in descending order of the refined logit (fp32), ties to the lower class, -1 where fewer than K are

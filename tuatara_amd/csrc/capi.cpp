@@ -857,8 +857,25 @@ int ttr_regions_to_data_dev(ttr_engine* e, const ttr_page* pages, int n_pages, c
   TTR_GUARD_END(-1)
 }
 
+int ttr_regions_to_data_dev_p(ttr_engine* e, const ttr_page* pages, int n_pages, const ttr_region* regions, int n, const uint32_t* sets, int n_sets,
+                              const char* const* patterns, int n_patterns, const int32_t* pattern_of, ttr_result** out) {
+  TTR_GUARD_BEGIN
+  if (!e || (n_pages > 0 && !out)) throw std::runtime_error("null argument");
+  EngineScope lk(*e->e);
+  std::vector<Result> res;
+  e->e->run_regions(pages, n_pages, regions, n, sets, n_sets, res, patterns, n_patterns, pattern_of);
+  hand_out(res, n_pages, out);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_image_regions_to_data(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const ttr_region* regions, int n, const uint32_t* sets,
                               int n_sets, ttr_result** out) {
+  return ttr_image_regions_to_data_p(e, img, h, w, row_stride, regions, n, sets, n_sets, nullptr, 0, nullptr, out);
+}
+
+int ttr_image_regions_to_data_p(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const ttr_region* regions, int n, const uint32_t* sets,
+                                int n_sets, const char* const* patterns, int n_patterns, const int32_t* pattern_of, ttr_result** out) {
   TTR_GUARD_BEGIN
   if (!e || !out) throw std::runtime_error("null argument");
   if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
@@ -871,7 +888,7 @@ int ttr_image_regions_to_data(ttr_engine* e, const uint8_t* img, int h, int w, i
   TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
   std::vector<Result> res;
   struct Drain { Engine& E; ~Drain() { (void)hipStreamSynchronize(E.stream); } } drain{E};   // (the caller's image is pageable: the copy ends inside the call, refused or not)
-  E.run_regions(&page, 1, regions, n, sets, n_sets, res);
+  E.run_regions(&page, 1, regions, n, sets, n_sets, res, patterns, n_patterns, pattern_of);
   hand_out(res, 1, out);
   return 0;
   TTR_GUARD_END(-1)
@@ -911,14 +928,22 @@ int ttr_pack_regions(ttr_engine* e, const uint8_t* img, int h, int w, int row_st
 
 int ttr_parseq_logits_sets(ttr_engine* e, const uint8_t* crops, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, float* logits,
                            float* ar_logits, int32_t* ids) {
+  return ttr_parseq_logits_patterns(e, crops, n, sets, n_sets, set_of, nullptr, 0, nullptr, logits, ar_logits, ids);
+}
+
+int ttr_parseq_logits_patterns(ttr_engine* e, const uint8_t* crops, int n, const uint32_t* sets, int n_sets, const int32_t* set_of,
+                               const char* const* patterns, int n_patterns, const int32_t* pattern_of, float* logits, float* ar_logits, int32_t* ids) {
   TTR_GUARD_BEGIN
   if (!e || n < 0 || (n > 0 && (!crops || !logits))) throw std::runtime_error("null argument");
   Engine& E = *e->e;
   EngineScope lk(E);
-  E.refuse_while_streaming("ttr_parseq_logits_sets");
+  const char* what = n_patterns > 0 || pattern_of ? "ttr_parseq_logits_patterns" : "ttr_parseq_logits_sets";
+  E.refuse_while_streaming(what);
   std::vector<uint32_t> table;
-  ClassMask one{};
-  E.resolve_row_masks("ttr_parseq_logits_sets", set_of, n, sets, n_sets, table, one);
+  ClassMask one = E.charset;
+  if (set_of || n_sets > 0 || !(n_patterns > 0 || pattern_of)) E.resolve_row_masks(what, set_of, n, sets, n_sets, table, one);   // (the patterns twin takes set_of == NULL: the engine's own set)
+  Engine::PatRows pats;
+  const bool with_pats = E.resolve_row_patterns(what, patterns, n_patterns, pattern_of, n, table, one, pats);
   if (n == 0) return 0;
   E.crops.ensure((size_t)n * 32 * 128 * 3);
   E.logits.ensure((size_t)n * 26 * 95 * 4);
@@ -928,14 +953,17 @@ int ttr_parseq_logits_sets(ttr_engine* e, const uint8_t* crops, int n, const uin
   {
     struct SetScope { ClassMask& c; ClassMask old; ~SetScope() { c = old; } } set_scope{E.charset, E.charset};   // (one shared mask: by value, the engine's own path)
     E.charset = one;
-    E.parseq_forward(E.crops.as<uint8_t>(), n, E.logits.as<float>(), ar_logits ? E.ar_logits.as<float>() : nullptr, o.ids, o.prob, o.conf, E.stage_row_masks(table, 0));
+    PatDev pd{};
+    if (with_pats) pd = E.stage_row_patterns(pats, 0);
+    E.parseq_forward(E.crops.as<uint8_t>(), n, E.logits.as<float>(), ar_logits ? E.ar_logits.as<float>() : nullptr, o.ids, o.prob, o.conf, E.stage_row_masks(table, 0), nullptr, nullptr,
+                     nullptr, with_pats ? &pd : nullptr);
   }
   TTR_HIP_CHECK(hipMemcpyAsync(logits, E.logits.p, (size_t)n * 26 * 95 * 4, hipMemcpyDeviceToHost, E.stream));
   if (ar_logits) TTR_HIP_CHECK(hipMemcpyAsync(ar_logits, E.ar_logits.p, (size_t)n * 26 * 95 * 4, hipMemcpyDeviceToHost, E.stream));
   if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, E.ids_dev.p, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
   E.range_fetch(Engine::kRangeStage);
   TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
-  E.range_verify(Engine::kRangeStage, "ttr_parseq_logits_sets");
+  E.range_verify(Engine::kRangeStage, what);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -983,7 +1011,107 @@ int ttr_engine_set_charset(ttr_engine* e, const char* allow, const char* deny) {
   for (int i = 0; i < 3; ++i) cm.blocked[i] = ~m[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);
   if (cm.restricts() && E.prec == kBF16)
     throw std::runtime_error("ttr_engine_set_charset: a character set needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which take no class mask");
+  if (!E.pattern_src.empty()) {                  // the stored pattern under the new set (DESIGN.md "Patterns"): compiled first - a set that empties its language leaves both as they were
+    try { E.set_engine_pattern(E.pattern_src.c_str(), cm); }
+    catch (const std::runtime_error& ex) { throw std::runtime_error(std::string("ttr_engine_set_charset: the engine's pattern does not survive this set: ") + ex.what()); }
+  }
   E.charset = cm;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+struct ttr_pattern { ttr::Pattern p; };
+
+int ttr_pattern_compile(const char* pattern, const uint32_t* mask, ttr_pattern** out) {
+  TTR_GUARD_BEGIN
+  if (!out) throw std::runtime_error("null argument");
+  *out = nullptr;
+  if (mask && !(mask[0] & 1u)) throw std::runtime_error("ttr_pattern_compile: the mask's bit 0 (the end of the text) must be set");
+  static const Tokenizer tok;
+  std::unique_ptr<ttr_pattern> p(new ttr_pattern{pattern_compile(tok, pattern, mask)});
+  *out = p.release();
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+void ttr_pattern_free(ttr_pattern* p) { delete p; }
+
+int ttr_pattern_states(const ttr_pattern* p) { return p ? p->p.states : -1; }
+
+int ttr_pattern_min_length(const ttr_pattern* p) { return p ? (int)p->p.mind[(size_t)p->p.start] : -1; }
+
+int ttr_pattern_table(const ttr_pattern* p, const uint16_t** delta, const uint8_t** mind, int* start, int* done) {
+  if (!p) return -1;
+  if (delta) *delta = p->p.delta.data();
+  if (mind) *mind = p->p.mind.data();
+  if (start) *start = p->p.start;
+  if (done) *done = p->p.done;
+  return p->p.rows();
+}
+
+int ttr_pattern_matches(const ttr_pattern* p, const char* text) {
+  if (!p || !text) return -1;
+  static const Tokenizer tok;
+  return pattern_matches(tok, p->p, text);
+}
+
+int ttr_engine_set_pattern(ttr_engine* e, const char* pattern) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_engine_set_pattern");
+  if (pattern && *pattern) {
+    if (E.prec == kBF16)
+      throw std::runtime_error("ttr_engine_set_pattern: a pattern needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which know no automaton");
+    if (E.cfg.orient != TTR_ORIENT_OFF)
+      throw std::runtime_error("ttr_engine_set_pattern: a pattern does not combine with word orientation (every turn would be forced into the pattern, and their confidences no longer tell them apart): create the engine with orient = TTR_ORIENT_OFF");
+    if (E.alts) throw std::runtime_error("ttr_engine_set_pattern: a pattern does not combine with character alternatives: ttr_engine_set_alternatives(e, 0) first");
+    if (E.lex_v) throw std::runtime_error("ttr_engine_set_pattern: a pattern does not combine with a lexicon: ttr_engine_set_lexicon(e, NULL, 0, 0) first");
+  }
+  try { E.set_engine_pattern(pattern, E.charset); }
+  catch (const std::runtime_error& ex) { throw std::runtime_error(std::string("ttr_engine_set_pattern: ") + ex.what()); }
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+const char* ttr_engine_get_pattern(const ttr_engine* e) { return e ? e->e->pattern_src.c_str() : nullptr; }
+
+int ttr_logits_decode_patterns(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of,
+                               const char* const* patterns, int n_patterns, const int32_t* pattern_of, int32_t* ids, float* probs, float* conf) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && !logits)) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  const char* what = "ttr_logits_decode_patterns";
+  E.refuse_while_streaming(what);
+  std::vector<uint32_t> table;
+  ClassMask one = E.charset;
+  if (set_of || n_sets > 0) E.resolve_row_masks(what, set_of, n, sets, n_sets, table, one);
+  Engine::PatRows pats;
+  const bool with_pats = E.resolve_row_patterns(what, patterns, n_patterns, pattern_of, n, table, one, pats);
+  if (n == 0) return 0;
+  if (!with_pats) {   // (no row has a pattern: every row a DONE state under its mask, so that the kernel this stage is about still runs)
+    uint32_t m[3];
+    std::map<std::vector<uint32_t>, int> start;
+    pats.start_of.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      const uint32_t* b = table.empty() ? one.blocked : &table[4 * (size_t)i];
+      for (int j = 0; j < 3; ++j) m[j] = ~b[j] & (j == 2 ? 0x7fffffffu : 0xffffffffu);
+      const std::vector<uint32_t> key(m, m + 3);
+      auto it = start.find(key);
+      if (it == start.end()) it = start.emplace(key, pats.t.add(pattern_none(m), what)).first;
+      pats.start_of[(size_t)i] = it->second;
+    }
+  }
+  E.logits.ensure((size_t)n * 26 * 95 * 4);
+  const Engine::RecOut o = E.rec_out(n);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  launch_decode_pat(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, E.stage_row_patterns(pats, 0));
+  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, o.ids, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (probs) TTR_HIP_CHECK(hipMemcpyAsync(probs, o.prob, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (conf) TTR_HIP_CHECK(hipMemcpyAsync(conf, o.conf, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -1006,6 +1134,8 @@ int ttr_engine_set_alternatives(ttr_engine* e, int k) {
   E.refuse_while_streaming("ttr_engine_set_alternatives");
   if (k && E.prec == kBF16)
     throw std::runtime_error("ttr_engine_set_alternatives: character alternatives need an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which take no class mask");
+  if (k && !E.pattern_src.empty())
+    throw std::runtime_error("ttr_engine_set_alternatives: character alternatives do not combine with a pattern, and one is set: ttr_engine_set_pattern(e, NULL) first");
   if (k && E.cfg.orient != TTR_ORIENT_OFF)
     throw std::runtime_error("ttr_engine_set_alternatives: character alternatives do not combine with word orientation (the chosen turn's logits are gone by the time of the choice): create the engine with orient = TTR_ORIENT_OFF");
   E.alts = k;
@@ -1116,6 +1246,8 @@ int ttr_engine_set_lexicon(ttr_engine* e, const char* const* words, int n_words,
   }
   if (E.prec == kBF16)
     throw std::runtime_error("ttr_engine_set_lexicon: lexicon matching needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which take no class mask");
+  if (!E.pattern_src.empty())
+    throw std::runtime_error("ttr_engine_set_lexicon: lexicon matching does not combine with a pattern, and one is set: ttr_engine_set_pattern(e, NULL) first");
   if (E.cfg.orient != TTR_ORIENT_OFF)
     throw std::runtime_error("ttr_engine_set_lexicon: lexicon matching does not combine with word orientation (the chosen turn's logits are gone by the time of the choice): create the engine with orient = TTR_ORIENT_OFF");
   std::vector<uint8_t> rec((size_t)n_words * kLexRecord);

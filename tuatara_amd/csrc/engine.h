@@ -50,6 +50,7 @@
 #include "geometry.h"
 #include "host_util.h"
 #include "kernels.h"
+#include "pattern.h"
 
 namespace ttr {
 
@@ -410,6 +411,13 @@ struct Engine {
   DevBuf lex_records;                             // [V] 32-byte records: length | 25 class bytes | zero padding (geometry.h: lexicon_encode)
   std::vector<std::string> lex_words;             // the host copy of the words (ttr_engine_lexicon_word)
   ClassMask charset{};                            // classes the recogniser may not choose (ttr_engine_set_charset; DESIGN.md "Character sets"); zero = no set
+  // the engine's pattern (ttr_engine_set_pattern; DESIGN.md "Patterns"): empty = none.  `pattern` is pattern_src compiled under `charset`; its table lives in
+  // pattern_dev (delta | mind, uploaded once by set_engine_pattern: nothing travels per call)
+  std::string pattern_src;
+  Pattern pattern;
+  DevBuf pattern_dev;
+  struct PatRows { PatternTable t; std::vector<int32_t> start_of; };   // a call's table and each row's start state (resolve_row_patterns)
+  PatDev pattern_own{};                           // the device form of `pattern`; delta == null while there is none
 
   // CRAFT
   std::map<std::string, Linear> craft;
@@ -657,7 +665,7 @@ struct Engine {
   // lex (device; DESIGN.md "Lexicon matching"): with a lexicon set and lex given, the scorer and its merge run behind the final decode; lex->idx / logp are
   // [N][lex_m], the partials as lex_out sizes them for these N crops
   void parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks = nullptr,
-                      int* d_alt_ids = nullptr, float* d_alt_prob = nullptr, const LexOut* lex = nullptr);
+                      int* d_alt_ids = nullptr, float* d_alt_prob = nullptr, const LexOut* lex = nullptr, const PatDev* pat = nullptr);
   // The recogniser's outputs of `rows` crops share one device buffer (ids_dev), laid out [rows][26] ids | [rows][26] prob | [rows] conf, so that
   // one device-to-host copy and one collective carry all three.  Ensures the buffer (never inside a launch function).
   struct RecOut { int* ids; float* prob; float* conf; };
@@ -727,6 +735,7 @@ struct Engine {
     std::vector<int32_t> region_set;   // [N]
     std::vector<uint32_t> row_masks;   // [N][4], or empty
     ClassMask region_mask{};
+    PatRows region_pats;               // the regions' patterns in crop order (DESIGN.md "Patterns"); start_of empty = none
   };
   PageBatch q1, q2;        // streamed batches: q1 = boxes known (recogniser enqueued or not), q2 = older, recogniser enqueued, results not yet returned
 
@@ -795,7 +804,8 @@ struct Engine {
   void run_batch(PageBatch& B, std::vector<Result>& results);
   // Regions (DESIGN.md "Regions and per-row character sets"): n caller-given quads on n_pages device pages of any sizes -> the packer and the recogniser, no
   // detector; synchronous.  Every refusal happens before anything is enqueued.
-  void run_regions(const ttr_page* pages, int n_pages, const ttr_region* regions, int n, const uint32_t* sets, int n_sets, std::vector<Result>& results);
+  void run_regions(const ttr_page* pages, int n_pages, const ttr_region* regions, int n, const uint32_t* sets, int n_sets, std::vector<Result>& results,
+                   const char* const* patterns = nullptr, int n_patterns = 0, const int32_t* pattern_of = nullptr);   // (pattern_of: one entry per region; DESIGN.md "Patterns")
   // set_of[n] (-1 = the engine's own set) over sets[n_sets][3] -> the rows' blocked-complement masks: `table` [n][4] when they differ, else empty and `one` = the
   // mask they share (the by-value path).  Refuses a set index out of range, a mask without bit 0 and - a row that restricts - a bf16 engine.
   void resolve_row_masks(const char* what, const int32_t* set_of, int n, const uint32_t* sets, int n_sets, std::vector<uint32_t>& table, ClassMask& one) const;
@@ -803,6 +813,18 @@ struct Engine {
   const RowMask* stage_row_masks(const std::vector<uint32_t>& table, int sl);
   DevBuf row_masks_dev;
   PinnedBuf h_row_masks[2];
+  // Patterns (DESIGN.md "Patterns").  set_engine_pattern: compiles src under the mask `cm` allows and, when it compiles, replaces the engine's pattern and
+  // its device table (null or empty src: none); throws and changes nothing otherwise.
+  void set_engine_pattern(const char* src, const ClassMask& cm);
+  // a call's rows -> one table: row i reads under patterns[pattern_of[i]] (pattern_of null or -1: the engine's own pattern, or none), compiled under the row's
+  // mask - row i of `table` ([n][4], blocked complements), or `one` when the table is empty.  Each distinct (pattern, mask) pair is compiled once.  Returns false
+  // - nothing built - when no row has a pattern.  Refuses a bad index, a bad pattern (naming the row) and more than 1024 states in all (naming the total).
+  bool resolve_row_patterns(const char* what, const char* const* patterns, int n_patterns, const int32_t* pattern_of, int n, const std::vector<uint32_t>& table,
+                            const ClassMask& one, PatRows& out) const;
+  // the call's table and start states through the pinned staging of slot sl to pat_rows_dev (one copy on `stream`)
+  PatDev stage_row_patterns(const PatRows& r, int sl);
+  DevBuf pat_rows_dev, pat_state;
+  PinnedBuf h_pat_rows[2];
 
   // Latency mode (the reference's 6-thread fan-out over chunks of the crop batch, tuatara.cpp:450-485, across
   // GPUs): rank 0 detects and packs the crop batch, the batch is broadcast, rank r recognises the contiguous shard r of

@@ -617,7 +617,9 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (B.regions) {   // the caller's sets: one mask by value (the engine's own path), or the rows' table through the slot's pinned staging (one copy, no launch)
       struct SetScope { ClassMask& c; ClassMask old; ~SetScope() { c = old; } } set_scope{charset, charset};
       charset = B.region_mask;
-      parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, stage_row_masks(B.row_masks, sl), alt.ids, alt.prob, lex);
+      PatDev pd{};                 // ... and the regions' patterns: the call's table the same way (one more copy, no launch)
+      if (!B.region_pats.start_of.empty()) pd = stage_row_patterns(B.region_pats, sl);
+      parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, stage_row_masks(B.row_masks, sl), alt.ids, alt.prob, lex, pd.delta ? &pd : nullptr);
     } else
     parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, nullptr, alt.ids, alt.prob, lex);
     if (T) {   // the twins as a pass of their own (turn 0 keeps its batch, and with it its bits), then the choice, in place in the standard block
@@ -885,7 +887,83 @@ const RowMask* Engine::stage_row_masks(const std::vector<uint32_t>& table, int s
   return row_masks_dev.as<RowMask>();
 }
 
-void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* regions, int n, const uint32_t* sets, int n_sets, std::vector<Result>& results) {
+void Engine::set_engine_pattern(const char* src_, const ClassMask& cm) {
+  if (!src_ || !*src_) { pattern_src.clear(); pattern = Pattern(); pattern_own = PatDev{}; return; }
+  const std::string src(src_);   // (a copy: the caller may pass pattern_src itself)
+  uint32_t m[3];
+  for (int i = 0; i < 3; ++i) m[i] = ~cm.blocked[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);
+  Pattern p = pattern_compile(tok, src.c_str(), m);   // (throws before anything changes)
+  const size_t db = p.delta.size() * sizeof(uint16_t), mb = p.mind.size();
+  pattern_dev.ensure(db + mb);
+  TTR_HIP_CHECK(hipMemcpyAsync(pattern_dev.p, p.delta.data(), db, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(pattern_dev.as<uint8_t>() + db, p.mind.data(), mb, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));        // (the host vectors are pageable; a setter may wait)
+  pattern_own = PatDev{pattern_dev.as<uint16_t>(), pattern_dev.as<uint8_t>() + db, nullptr, p.start};
+  pattern = std::move(p);
+  pattern_src = src;
+}
+
+bool Engine::resolve_row_patterns(const char* what, const char* const* patterns, int n_patterns, const int32_t* pattern_of, int n, const std::vector<uint32_t>& table,
+                                  const ClassMask& one, PatRows& out) const {
+  const std::string w(what);
+  if (n_patterns < 0 || (n_patterns > 0 && !patterns)) throw std::runtime_error("null argument");
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    const int k = pattern_of ? pattern_of[i] : -1;
+    if (k < -1 || k >= n_patterns)
+      throw std::runtime_error(w + ": item " + std::to_string(i) + " names pattern " + std::to_string(k) + ", the call holds " + std::to_string(n_patterns) + " (-1 = the engine's own)");
+    any = any || k >= 0 || !pattern_src.empty();
+  }
+  out.t = PatternTable(); out.start_of.clear();
+  if (!any) return false;
+  if (prec == kBF16) throw std::runtime_error(w + ": a pattern needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which know no automaton");
+  if (alts || lex_v) throw std::runtime_error(w + ": patterns do not combine with character alternatives or a lexicon (ttr_engine_set_alternatives(e, 0) / ttr_engine_set_lexicon(e, NULL, 0, 0) first)");
+  // each distinct (pattern, mask) pair once; a row without a pattern: a DONE state alone under its mask
+  struct Key { int k; uint32_t m[3]; bool operator<(const Key& o) const { return k != o.k ? k < o.k : memcmp(m, o.m, sizeof m) < 0; } };
+  std::map<Key, int> index;
+  std::vector<Pattern> autos;
+  std::vector<int> of((size_t)n);
+  int total = 0;
+  for (int i = 0; i < n; ++i) {
+    Key key{};
+    const uint32_t* b = table.empty() ? one.blocked : &table[4 * (size_t)i];
+    for (int j = 0; j < 3; ++j) key.m[j] = ~b[j] & (j == 2 ? 0x7fffffffu : 0xffffffffu);
+    const int k = pattern_of ? pattern_of[i] : -1;
+    const char* src = k >= 0 ? patterns[k] : (pattern_src.empty() ? nullptr : pattern_src.c_str());
+    key.k = k >= 0 ? k : (src ? -1 : -2);
+    auto it = index.find(key);
+    if (it == index.end()) {
+      try {
+        autos.push_back(key.k == -2 ? pattern_none(key.m) : pattern_compile(tok, src ? src : "", key.m));
+      } catch (const std::runtime_error& e) { throw std::runtime_error(w + ": item " + std::to_string(i) + ": " + e.what()); }
+      total += autos.back().rows();
+      it = index.emplace(key, (int)autos.size() - 1).first;
+    }
+    of[(size_t)i] = it->second;
+  }
+  if (total > kPatMaxTable) throw std::runtime_error(w + ": the call's patterns need " + std::to_string(total) + " automaton states in all: at most 1024 fit one table");
+  std::vector<int> start(autos.size());
+  for (size_t a = 0; a < autos.size(); ++a) start[a] = out.t.add(autos[a], what);
+  out.start_of.resize((size_t)n);
+  for (int i = 0; i < n; ++i) out.start_of[(size_t)i] = start[(size_t)of[(size_t)i]];
+  return true;
+}
+
+PatDev Engine::stage_row_patterns(const PatRows& r, int sl) {
+  // delta | start_of | mind, in this order so that each part is aligned to its element
+  const size_t db = r.t.delta.size() * sizeof(uint16_t), sb = r.start_of.size() * 4, mb = r.t.mind.size();
+  PinnedBuf& h = h_pat_rows[sl & 1];
+  h.ensure(db + sb + mb); pat_rows_dev.ensure(db + sb + mb);
+  memcpy(h.p, r.t.delta.data(), db);
+  memcpy(h.as<uint8_t>() + db, r.start_of.data(), sb);
+  memcpy(h.as<uint8_t>() + db + sb, r.t.mind.data(), mb);
+  TTR_HIP_CHECK(hipMemcpyAsync(pat_rows_dev.p, h.p, db + sb + mb, hipMemcpyHostToDevice, stream));
+  uint8_t* d = pat_rows_dev.as<uint8_t>();
+  return PatDev{reinterpret_cast<const uint16_t*>(d), d + db + sb, reinterpret_cast<const int32_t*>(d + db), 0};
+}
+
+void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* regions, int n, const uint32_t* sets, int n_sets, std::vector<Result>& results,
+                         const char* const* patterns, int n_patterns, const int32_t* pattern_of) {
   const char* what = "regions";
   // ---- every refusal, before anything is enqueued or changed
   if (n_pages < 0 || n < 0 || (n_pages > 0 && !pages) || (n > 0 && !regions)) throw std::runtime_error("null argument");
@@ -915,6 +993,9 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
   std::vector<uint32_t> table;
   ClassMask one{};
   resolve_row_masks(what, set_of.data(), n, sets, n_sets, table, one);
+  if (n_patterns > 0 && n > 0 && !pattern_of) throw std::runtime_error("null argument");
+  PatRows pats;   // (in the caller's order; the batch holds them in crop order)
+  const bool with_pats = resolve_row_patterns(what, patterns, n_patterns, pattern_of, n, table, one, pats);
   results.assign((size_t)n_pages, Result());
   if (n_pages == 0) return;
   // ---- the batch: crops by page, then in the caller's order within the page (a stable counting sort)
@@ -926,6 +1007,7 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
   B.page_of.assign((size_t)n, 0); B.rects.assign((size_t)n * 5, 0); B.coef.assign((size_t)n * 8, 0);
   B.region_quad.assign((size_t)n * 8, 0.f); B.region_set.assign((size_t)n, 0);
   if (!table.empty()) B.row_masks.assign((size_t)n * 4, 0u);
+  if (with_pats) { B.region_pats.t = std::move(pats.t); B.region_pats.start_of.assign((size_t)n, 0); }
   B.region_mask = one;
   for (int i = 0; i < n; ++i) {
     const ttr_region& R = regions[i];
@@ -940,6 +1022,7 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
     memcpy(&B.region_quad[8 * c], R.quad, 8 * sizeof(float));
     B.region_set[c] = R.set;
     if (!table.empty()) memcpy(&B.row_masks[4 * c], &table[4 * (size_t)i], 16);
+    if (with_pats) B.region_pats.start_of[c] = pats.start_of[(size_t)i];
   }
   const double th0 = now_us();
   for (int k = 0; k < 3; ++k) TTR_HIP_CHECK(hipEventRecord(ev[k], stream));   // no detector: its two stage times of this call are zero

@@ -135,7 +135,7 @@ void Engine::decoder_tail(const void* sa, int N, int R, const float* resid_pos, 
 }
 
 void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks,
-                            int* d_alt_ids, float* d_alt_prob, const LexOut* lex) {
+                            int* d_alt_ids, float* d_alt_prob, const LexOut* lex, const PatDev* pat) {
   if (N <= 0) return;
   // A very large crop batch (64 pages of ~150 boxes) goes through in even groups: the refinement pass's widest planes tensor (26 rows per crop x 1536 x 6 bytes)
   // must stay inside the 2 GiB window of 32-bit buffer offsets (8962 crops), and the workspaces stay bounded.  Crops are independent (batch-invariant logits,
@@ -144,18 +144,33 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
   if (N > kMaxCrops) {
     const int groups = (N + kMaxCrops - 1) / kMaxCrops, per = (N + groups - 1) / groups;
     LexOut lex_g{};
+    PatDev pat_g{};
     for (int g0 = 0; g0 < N; g0 += per) {
       const int n = std::min(per, N - g0);
       parseq_forward(d_crops + (size_t)g0 * 32 * 128 * 3, n, d_logits + (size_t)g0 * 26 * 95, d_ar ? d_ar + (size_t)g0 * 26 * 95 : nullptr, d_ids + (size_t)g0 * 26,
                      d_prob + (size_t)g0 * 26, d_conf + g0, row_masks ? row_masks + g0 : nullptr,   // (rows are never permuted: a group's masks start where its crops do)
                      d_alt_ids ? d_alt_ids + (size_t)g0 * 26 * alts : nullptr, d_alt_prob ? d_alt_prob + (size_t)g0 * 26 * alts : nullptr,
-                     lex ? &(lex_g = LexOut{lex->idx + (size_t)g0 * lex_m, lex->logp + (size_t)g0 * lex_m, lex->part_idx, lex->part_logp}) : nullptr);   // (the groups run one after another on the stream: they share the partials)
+                     lex ? &(lex_g = LexOut{lex->idx + (size_t)g0 * lex_m, lex->logp + (size_t)g0 * lex_m, lex->part_idx, lex->part_logp}) : nullptr,   // (the groups run one after another on the stream: they share the partials)
+                     pat ? &(pat_g = PatDev{pat->delta, pat->mind, pat->start_of ? pat->start_of + g0 : nullptr, pat->start}) : nullptr);   // (a group's start states start where its crops do)
     }
     return;
   }
   // a character set (DESIGN.md "Character sets") constrains every place below that chooses a token, by value: the argmax launches, the argmax folded into
   // dec_embed_ln / the skinny self_kv linear, and the final decode.  The bf16 engine chooses inside gemm_sk.hip and dec_fused.hip, which take no mask
   if ((charset.restricts() || row_masks) && prec == kBF16) throw std::runtime_error("parseq_forward: a character set needs an f16x4 or f32 engine (the bf16 engine's kernels take no class mask)");
+  // a pattern (DESIGN.md "Patterns"): the call's table, or the engine's own - compiled under `charset`, so it holds for the by-value mask alone.  With one in
+  // force the AR steps' argmax is launch_argmax_pat, always as its own launch, and the final decode launch_decode_pat; without one nothing below differs
+  const PatDev* const pt = pat ? pat : (pattern_own.delta ? &pattern_own : nullptr);
+  if (pt) {
+    if (prec == kBF16) throw std::runtime_error("parseq_forward: a pattern needs an f16x4 or f32 engine (the bf16 engine's kernels choose their tokens themselves)");
+    if ((alts && d_alt_ids && d_alt_prob) || (lex_v && lex)) throw std::runtime_error("parseq_forward: a pattern does not combine with character alternatives or a lexicon");
+    if (!pat) {
+      uint32_t m[3];
+      for (int i = 0; i < 3; ++i) m[i] = ~charset.blocked[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);
+      if (row_masks || memcmp(m, pattern.mask, sizeof m)) throw std::runtime_error("parseq_forward: the engine's pattern was compiled under another character set than this pass reads under");
+    }
+    pat_state.ensure((size_t)N * 4);
+  }
   prof_stage = 1;
   const int M = N * 128, E = 384;
   const int patch_ld = pq.at("patch").k;   // 96, or 128 in bf16 mode (zero-padded)
@@ -407,7 +422,8 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
     const bool host_check = early && !tok_fuse && !streaming_recog && tn.ar_host_check > 0 && N <= 256 && i >= tn.ar_host_check && (i - tn.ar_host_check) % 4 == 0 && i + 1 < nsteps;
     if (i + 1 < 26 && !tok_fuse) {
       // the step's argmax: its own launch where the host is about to look at the counter (or nothing follows), else left to the next step's first kernel
-      if (dec_split && tn.argmax_fold && !host_check) pend_argmax = i;
+      if (pt) launch_argmax_pat(ar + (size_t)i * 95, 26 * 95, 95, tk, 26, i + 1, N, stream, cur_skip, cur_skip_n, early ? ar_done.as<int>() : nullptr, 0, *pt, pat_state.as<int>());   // (never folded: the folded kernels know no automaton)
+      else if (dec_split && tn.argmax_fold && !host_check) pend_argmax = i;
       else launch_argmax(ar + (size_t)i * 95, 26 * 95, 95, tk, 26, i + 1, N, stream, cur_skip, cur_skip_n, early ? ar_done.as<int>() : nullptr, 0, charset, row_masks);
     }
     if (host_check) {
@@ -428,6 +444,8 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
   launch_dec_self_attn(prec, qself.as<float>(), kvcache, tk, att, N, 26, 0, 1, stream);
   decoder_tail(att, N, 26, posq, 26, tgt, t384, d384b, d1536, kvmem, d_logits, 95);
   }
+  if (pt) launch_decode_pat(d_logits, N, d_ids, d_prob, d_conf, stream, *pt);           // ... under a pattern: the same, walked position by position through the automaton (pattern.hip)
+  else
   launch_decode_conf(d_logits, N, d_ids, d_prob, d_conf, stream, charset, row_masks);   // the final argmax with each id's probability and the word's confidence (decode_conf.hip)
   // character alternatives (DESIGN.md "Character alternatives"): the K best allowed classes of every position, from the same logits, mask and standard block
   if (alts && d_alt_ids && d_alt_prob) launch_decode_alts(d_logits, N, d_ids, d_prob, alts, d_alt_ids, d_alt_prob, stream, charset, row_masks);

@@ -203,6 +203,18 @@ void launch_fill_i32(int* p, int value, int n, int stride, hipStream_t s);
 // cm (DESIGN.md "Character sets"): a blocked class is -inf in the comparison and adds exactly 0 to the exponential sum; the default blocks none
 // row_masks (DESIGN.md "Regions and per-row character sets"): crop n decodes under row_masks[n] instead of cm
 void launch_decode_conf(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s, ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);
+// pattern.hip: the two places that choose a token when a pattern is in force (DESIGN.md "Patterns").  PatDev: the call's automaton table on the device -
+// delta u16 [S][96] (0xFFFF = none; column 0 = EOS), mind u8 [S] (255 = a DONE state), and each crop's start state: start_of[n], or `start` for every crop
+// when start_of is null.  Class c is allowed at character position p in state s iff t = delta[s][c] exists and (c == 0 or mind[t] == 255 or
+// p + 1 + mind[t] <= 25); the token is the first maximal index among the allowed classes (argmax_kernel's comparison and butterfly).
+struct PatDev { const uint16_t* delta; const uint8_t* mind; const int32_t* start_of; int start; };
+// launch_argmax under a pattern: column `col` holds character position col - 1; crop n's state is its start state at col == 1 and state[n] later, and
+// state[n] receives the successor.  skip / skip_n / done_count / eos and the token layout: launch_argmax's
+void launch_argmax_pat(const float* logits, int ld, int C, int* tokens, int tok_ld, int col, int N, hipStream_t s, const int* skip, int skip_n, int* done_count,
+                       int eos, PatDev pt, int* state);
+// launch_decode_conf under a pattern: positions 0..25 walked in order from the start state; the maximum and the exponential sum run over the allowed classes
+// only; ids / prob / conf in launch_decode_conf's layouts, conf the same sequential fp32 product
+void launch_decode_pat(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s, PatDev pt);
 // decode_alts.hip: character alternatives (DESIGN.md "Character alternatives"), directly behind launch_decode_conf on the same logits, mask and standard block:
 // alt_ids i32 [N][26][K] the K best allowed classes of every row (slot 0 = ids; -1 where fewer can be chosen), alt_prob f32 [N][26][K] =
 // expf(x[alt_id] - x[id]) * prob (slot 0 = prob bit for bit; 0.f in the empty slots).  K in 2..8.  Reads the logits, ids and prob; writes the two outputs only.

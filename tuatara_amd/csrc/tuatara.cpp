@@ -64,8 +64,9 @@ struct CharsetScope {
   ttr_engine* e;
   std::unique_lock<std::mutex> turn;
   bool set = false, ok = true;
-  bool alts_set = false, lex_set = false;
-  CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0) : e(e_) {
+  bool alts_set = false, lex_set = false, pattern_set = false;
+  CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
+               std::string pattern = std::string()) : e(e_) {
     {
       std::lock_guard<std::mutex> lk(g_mu);
       auto& m = g_call_mu[e];
@@ -90,11 +91,18 @@ struct CharsetScope {
       }
       lex_set = true;
     }
-    if (allow.empty() && deny.empty()) return;
-    if (ttr_engine_set_charset(e, allow.c_str(), deny.c_str()) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
-    set = true;
+    if (pattern.empty()) if (const char* p = std::getenv("TUATARA_PATTERN")) pattern = p;
+    if (!allow.empty() || !deny.empty()) {
+      if (ttr_engine_set_charset(e, allow.c_str(), deny.c_str()) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      set = true;
+    }
+    if (!pattern.empty()) {   // the call's pattern (DESIGN.md "Patterns"): behind the set, under which it is compiled
+      if (ttr_engine_set_pattern(e, pattern.c_str()) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      pattern_set = true;
+    }
   }
   ~CharsetScope() {
+    if (pattern_set) ttr_engine_set_pattern(e, nullptr);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
     if (alts_set) ttr_engine_set_alternatives(e, 0);
     if (lex_set) ttr_engine_set_lexicon(e, nullptr, 0, 0);
@@ -192,10 +200,10 @@ template <class Item>
 std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
                           const std::string& outputs_dir, int crop_mode, int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
                                         int blocks = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0,
-                                        const std::vector<std::string>* words = nullptr, int lex_m = 0) {
+                                        const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string()) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny, alts, words, lex_m);
+  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern);
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
@@ -216,10 +224,10 @@ template <class Item>
 std::vector<std::vector<Item>> run_many(const std::vector<ImageView>& images, const std::string& weights_dir, const std::string& outputs_dir, int crop_mode,
                                         int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
                                         int blocks = -1, int mixed = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0,
-                                        const std::vector<std::string>* words = nullptr, int lex_m = 0) {
+                                        const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string()) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks, mixed);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny, alts, words, lex_m);
+  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern);
   if (!cs.ok) return {};
   const int n = (int)images.size();
   std::vector<const uint8_t*> ptr(n);
@@ -369,6 +377,20 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
                                 blocks ? 1 : -1, mixed_batches ? 1 : -1, allowlist, blocklist, alts, &words, m);
 }
 
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, std::string pattern) {
+  return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1,
+                               chars ? 1 : -1, blocks ? 1 : -1, allowlist, blocklist, 0, nullptr, 0, pattern);
+}
+
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist, std::string pattern) {
+  return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
+                                blocks ? 1 : -1, mixed_batches ? 1 : -1, allowlist, blocklist, 0, nullptr, 0, pattern);
+}
+
 std::string last_call_error() { return g_call_error; }
 
 std::vector<WordReading> nbest(const OutputItemEx& item, int m) {
@@ -397,8 +419,19 @@ std::vector<OutputItemEx> read_regions(const uint8_t* image, int rows, int cols,
   // every list and quad is checked on the host before an engine is opened
   std::vector<ttr_region> regs(regions.size());
   std::vector<uint32_t> sets;
+  std::vector<const char*> pats;            // the regions' own patterns (DESIGN.md "Patterns"), each once
+  std::vector<int32_t> pattern_of(regions.size(), -1);
   for (size_t i = 0; i < regions.size(); ++i) {
     const RegionSpec& s = regions[i];
+    if (!s.pattern.empty()) {
+      ttr_pattern* cp = nullptr;              // (checked on the host, under every class: a pattern that only its region's set empties is refused by the call)
+      if (ttr_pattern_compile(s.pattern.c_str(), nullptr, &cp) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: region " << i << ": " << g_call_error << std::endl; return {}; }
+      ttr_pattern_free(cp);
+      size_t k = 0;
+      while (k < pats.size() && s.pattern != pats[k]) ++k;
+      if (k == pats.size()) pats.push_back(s.pattern.c_str());
+      pattern_of[i] = (int32_t)k;
+    }
     if (s.quad.size() != 8) { std::cerr << "tuatara: region " << i << ": a region is 8 floats (tl, tr, br, bl)" << std::endl; return {}; }
     for (int k = 0; k < 8; ++k) regs[i].quad[k] = s.quad[k];
     regs[i].page = 0; regs[i].set = -1;
@@ -417,9 +450,10 @@ std::vector<OutputItemEx> read_regions(const uint8_t* image, int rows, int cols,
     return {};
   }
   ttr_result* r = nullptr;
-  if (ttr_image_regions_to_data(e, image, rows, cols, row_stride ? (int)row_stride : cols * 3, regs.data(), (int)regs.size(), sets.empty() ? nullptr : sets.data(),
-                                (int)(sets.size() / 3), &r) != 0) {
-    std::cerr << "tuatara: " << ttr_last_error() << std::endl;
+  if (ttr_image_regions_to_data_p(e, image, rows, cols, row_stride ? (int)row_stride : cols * 3, regs.data(), (int)regs.size(), sets.empty() ? nullptr : sets.data(),
+                                  (int)(sets.size() / 3), pats.empty() ? nullptr : pats.data(), (int)pats.size(), pats.empty() ? nullptr : pattern_of.data(), &r) != 0) {
+    g_call_error = ttr_last_error();
+    std::cerr << "tuatara: " << g_call_error << std::endl;
     return {};
   }
   std::vector<OutputItemEx> out(ttr_result_count(r));

@@ -134,6 +134,18 @@ SYMBOLS = [
     ("ttr_pack_regions", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _PU8]),
     ("ttr_parseq_logits_sets", _I, [_VP, _PU8, _I, C.POINTER(C.c_uint32), _I, _PI, _PF, _PF, _PI]),
     ("ttr_logits_confidence_sets", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _I, _PI, _PI, _PF, _PF]),
+    ("ttr_pattern_compile", _I, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(_VP)]),
+    ("ttr_pattern_free", None, [_VP]),
+    ("ttr_pattern_states", _I, [_VP]),
+    ("ttr_pattern_min_length", _I, [_VP]),
+    ("ttr_pattern_table", _I, [_VP, C.POINTER(C.POINTER(C.c_uint16)), C.POINTER(_PU8), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("ttr_pattern_matches", _I, [_VP, C.c_char_p]),
+    ("ttr_engine_set_pattern", _I, [_VP, C.c_char_p]),
+    ("ttr_engine_get_pattern", C.c_char_p, [_VP]),
+    ("ttr_regions_to_data_dev_p", _I, [_VP, C.POINTER(Page), _I, C.POINTER(Region), _I, C.POINTER(C.c_uint32), _I, C.POINTER(C.c_char_p), _I, _PI, C.POINTER(_VP)]),
+    ("ttr_image_regions_to_data_p", _I, [_VP, _PU8, _I, _I, _I, C.POINTER(Region), _I, C.POINTER(C.c_uint32), _I, C.POINTER(C.c_char_p), _I, _PI, C.POINTER(_VP)]),
+    ("ttr_parseq_logits_patterns", _I, [_VP, _PU8, _I, C.POINTER(C.c_uint32), _I, _PI, C.POINTER(C.c_char_p), _I, _PI, _PF, _PF, _PI]),
+    ("ttr_logits_decode_patterns", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _I, _PI, C.POINTER(C.c_char_p), _I, _PI, _PI, _PF, _PF]),
     ("ttr_engine_set_alternatives", _I, [_VP, _I]),
     ("ttr_engine_alternatives", _I, [_VP]),
     ("ttr_result_alt_k", _I, [_VP]),
@@ -369,6 +381,69 @@ def charset_mask(allow=None, deny=None) -> np.ndarray:
     if load().ttr_charset_mask(_charlist(allow), _charlist(deny), m) < 0:
         raise EngineError(load().ttr_last_error().decode("latin1"))
     return np.array(list(m), dtype=np.uint32)
+
+
+class Pattern:
+    """A compiled pattern (ttr_pattern_compile, no GPU; DESIGN.md "Patterns"): .states - states of the minimal automaton, its DONE state not counted;
+    .min_length - characters of the shortest member; .table() -> (delta uint16 [states + 1, 96], mind uint8 [states + 1], start, done); .matches(text) ->
+    True / False, or None for a text that names no class somewhere."""
+
+    def __init__(self, pattern, mask=None):
+        self.lib = load()
+        self.h = None
+        self.pattern = pattern
+        m = None if mask is None else (C.c_uint32 * 3)(*[int(v) for v in np.asarray(mask).ravel()[:3]])
+        h = C.c_void_p()
+        if self.lib.ttr_pattern_compile(_charlist(pattern), m, C.byref(h)) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+        self.h = h
+
+    @property
+    def states(self) -> int:
+        return int(self.lib.ttr_pattern_states(self.h))
+
+    @property
+    def min_length(self) -> int:
+        return int(self.lib.ttr_pattern_min_length(self.h))
+
+    def table(self):
+        d, m, s, e = C.POINTER(C.c_uint16)(), _PU8(), C.c_int(), C.c_int()
+        rows = self.lib.ttr_pattern_table(self.h, C.byref(d), C.byref(m), C.byref(s), C.byref(e))
+        return (np.ctypeslib.as_array(d, (rows, 96)).copy(), np.ctypeslib.as_array(m, (rows,)).copy(), s.value, e.value)
+
+    def matches(self, text):
+        r = self.lib.ttr_pattern_matches(self.h, _charlist(text))
+        return None if r < 0 else bool(r)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.lib.ttr_pattern_free(self.h)
+            self.h = None
+
+
+def pattern_compile(pattern, mask=None) -> Pattern:
+    """Compile a pattern under a class mask (charset_mask's form; None = every class) on the host.  EngineError for a refused pattern."""
+    return Pattern(pattern, mask)
+
+
+def _patterns_arg(patterns):
+    """a list of pattern strings (or None) -> (char* array or None, n, keep-alive)"""
+    if patterns is None or len(patterns) == 0:
+        return None, 0, None
+    enc = [_charlist(p) for p in patterns]
+    return (C.c_char_p * len(enc))(*enc), len(enc), enc
+
+
+def _pattern_rows(patterns):
+    """a list parallel to the rows, None = no pattern of its own -> (distinct patterns, pattern_of i32 [n])"""
+    distinct, of = [], np.full(len(patterns), -1, np.int32)
+    for i, p in enumerate(patterns):
+        if p is None:
+            continue
+        if p not in distinct:
+            distinct.append(p)
+        of[i] = distinct.index(p)
+    return distinct, of
 
 
 def region_from_rect(x0: int, y0: int, x1: int, y1: int) -> np.ndarray:
@@ -764,6 +839,7 @@ class Engine:
         cfg.strict_crops = int(strict_crops)
         alts = int(overrides.pop("alts", 0) or 0)                                         # not a config field either: set_alternatives, below
         lexicon, lexicon_m = overrides.pop("lexicon", None), int(overrides.pop("lexicon_m", 1))   # nor these: set_lexicon, below
+        pattern = overrides.pop("pattern", None)                                          # nor this: set_pattern, below
         self._lex_words = []
         tuning = {k: overrides.pop(k) for k in list(overrides) if not hasattr(cfg, k)}     # not a config field: a tuning key (below)
         for k, v in overrides.items():
@@ -779,6 +855,8 @@ class Engine:
             self.set_alternatives(alts)
         if lexicon is not None:
             self.set_lexicon(lexicon, lexicon_m)
+        if pattern:
+            self.set_pattern(pattern)
 
     def set_lexicon(self, words=None, m: int = 1):
         """The word list every read word is scored against (ttr_engine_set_lexicon; DESIGN.md "Lexicon matching"): words of 1..25 characters out of the
@@ -874,6 +952,39 @@ class Engine:
         m = (C.c_uint32 * 3)()
         self._check(self.lib.ttr_engine_get_charset(self.h, m))
         return np.array(list(m), dtype=np.uint32)
+
+    def set_pattern(self, pattern=None):
+        """Constrain every word to a regular expression (ttr_engine_set_pattern; DESIGN.md "Patterns"): the subset of Python's re that include/tuatara_hip.h
+        lists, compiled under the engine's character set and recompiled when set_charset changes it.  set_pattern() resets.  Every returned text (of at most
+        25 characters) then matches the pattern; prob / conf are over the choices it left open.  Raises EngineError, and changes nothing, on a bad pattern,
+        between a stream_push and its flush, on a bf16 engine and with orient, alternatives or a lexicon set.  In sharded mode give every rank the same one."""
+        if self.lib.ttr_engine_set_pattern(self.h, _charlist(pattern)) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def pattern(self):
+        """The pattern in force, None when there is none."""
+        p = self.lib.ttr_engine_get_pattern(self.h)
+        return p.decode("latin1") if p else None
+
+    def logits_decode_patterns(self, logits: np.ndarray, patterns, pattern_of, set_of=None, sets=None):
+        """decode_pat_kernel alone on host logits f32 [n, 26, 95] (ttr_logits_decode_patterns) -> (ids i32 [n, 26], prob f32 [n, 26], conf f32 [n]): row i
+        decodes under patterns[pattern_of[i]] (-1: the engine's own pattern, or none) compiled under sets[set_of[i]] (set_of None: the engine's own set)."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, 26, 95)
+        n = len(logits)
+        ids, prob, conf = np.zeros((n, 26), np.int32), np.zeros((n, 26), np.float32), np.zeros(n, np.float32)
+        po = np.ascontiguousarray(pattern_of, dtype=np.int32).ravel()
+        if len(po) != n:
+            raise ValueError("pattern_of holds one entry per row")
+        so = None
+        if set_of is not None:
+            so = np.ascontiguousarray(set_of, dtype=np.int32).ravel()
+            if len(so) != n:
+                raise ValueError("set_of holds one entry per row")
+        sp, ns, _keep = _sets_arg(sets)
+        pp, npat, _keep2 = _patterns_arg(patterns)
+        self._check(self.lib.ttr_logits_decode_patterns(self.h, _f(logits), n, sp, ns, _i(so) if so is not None else None, pp, npat, _i(po), _i(ids), _f(prob), _f(conf)))
+        return ids, prob, conf
 
     def close(self):
         if getattr(self, "h", None):
@@ -1104,14 +1215,21 @@ class Engine:
         self._check(self.lib.ttr_stream_flush(self.h, arr, C.byref(n_prev)))
         return self._results(arr, n_prev.value, keep, conf)
 
-    def read_regions(self, pages_or_image, regions, charsets=None):
+    def read_regions(self, pages_or_image, regions, charsets=None, patterns=None):
         """Read regions the caller already knows, each under its own character set, with no detector (DESIGN.md "Regions and per-row character sets").
         pages_or_image: one host image [H, W, 3] u8 (ttr_image_regions_to_data), or a list of device pages (ptr | DeviceBuffer, h, w[, row_stride]) of
         any sizes (ttr_regions_to_data_dev).  regions: a list of dicts {"quad": 8 floats | "rect": (x0, y0, x1, y1), "page": index (default 0), "set":
         index into charsets, or -1 / absent = the engine's own set}, or of bare quads / rectangles (page 0, the engine's set).  charsets: a list of
         (allow, deny) pairs or ready-made masks.  Returns, per page (for an image: that page alone), the regions in the caller's order as dicts {"text",
         "bbox", "ids", "quad", "conf", "prob", "set", "region"} - "quad" the caller's floats verbatim, "region" the index into `regions`; with set_alternatives(K) also "alt_ids",
-        "alt_prob" ([26, K] arrays) and "alternatives", each region's under its own set; with set_lexicon also "lex_idx", "lex_logp" ([M] arrays) and "lexicon"."""
+        "alt_prob" ([26, K] arrays) and "alternatives", each region's under its own set; with set_lexicon also "lex_idx", "lex_logp" ([M] arrays) and "lexicon".
+        patterns (DESIGN.md "Patterns"): a list parallel to `regions`, each entry the region's own pattern or None (the engine's own pattern, or none)."""
+        pp, npat, po = None, 0, None
+        if patterns is not None:
+            if len(patterns) != len(regions):
+                raise ValueError("patterns holds one entry per region (None = no pattern of its own)")
+            distinct, po = _pattern_rows(patterns)
+            pp, npat, _keep_p = _patterns_arg(distinct)
         regs = (Region * max(len(regions), 1))()
         for i, r in enumerate(regions):
             d = r if isinstance(r, dict) else {"quad" if np.asarray(r).size == 8 else "rect": r}
@@ -1127,11 +1245,17 @@ class Engine:
                 raise RuntimeError("Input array should have 3 dimensions")
             n_pages = 1
             arr = (C.c_void_p * 1)()
-            self._check(self.lib.ttr_image_regions_to_data(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, regs, len(regions), sp, ns, arr))
+            if po is not None:
+                self._check(self.lib.ttr_image_regions_to_data_p(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, regs, len(regions), sp, ns, pp, npat, _i(po), arr))
+            else:
+                self._check(self.lib.ttr_image_regions_to_data(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, regs, len(regions), sp, ns, arr))
         else:
             n_pages = len(pages_or_image)
             arr = (C.c_void_p * max(n_pages, 1))()
-            self._check(self.lib.ttr_regions_to_data_dev(self.h, self._page_array(pages_or_image), n_pages, regs, len(regions), sp, ns, arr))
+            if po is not None:
+                self._check(self.lib.ttr_regions_to_data_dev_p(self.h, self._page_array(pages_or_image), n_pages, regs, len(regions), sp, ns, pp, npat, _i(po), arr))
+            else:
+                self._check(self.lib.ttr_regions_to_data_dev(self.h, self._page_array(pages_or_image), n_pages, regs, len(regions), sp, ns, arr))
         where = [[i for i in range(len(regions)) if regs[i].page == p] for p in range(n_pages)]
         out = []
         for p in range(n_pages):
@@ -1393,14 +1517,24 @@ class Engine:
                                                      C.c_float(ratio), int(crop_mode), int(turn), _u8(crops), _f(quads)))
         return crops, quads
 
-    def parseq_logits(self, crops: np.ndarray, want_ar: bool = False, set_of=None, sets=None):
-        """set_of (i32 [n]) with sets (uint32 [k, 3] masks): crop i chooses under sets[set_of[i]], -1 = the engine's own set (ttr_parseq_logits_sets)."""
+    def parseq_logits(self, crops: np.ndarray, want_ar: bool = False, set_of=None, sets=None, pattern_of=None, patterns=None):
+        """set_of (i32 [n]) with sets (uint32 [k, 3] masks): crop i chooses under sets[set_of[i]], -1 = the engine's own set (ttr_parseq_logits_sets).
+        pattern_of (i32 [n]) with patterns (strings): crop i reads under patterns[pattern_of[i]], -1 = the engine's own pattern or none (ttr_parseq_logits_patterns)."""
         crops = np.ascontiguousarray(crops, dtype=np.uint8)
         n = len(crops)
         logits = np.zeros((n, 26, 95), np.float32)
         ar = np.zeros((n, 26, 95), np.float32) if want_ar else None
         ids = np.zeros((n, 26), np.int32)
-        if set_of is not None:
+        if pattern_of is not None:
+            po = np.ascontiguousarray(pattern_of, dtype=np.int32).ravel()
+            so = np.ascontiguousarray(set_of, dtype=np.int32).ravel() if set_of is not None else None
+            if len(po) != n or (so is not None and len(so) != n):
+                raise ValueError("pattern_of and set_of hold one entry per crop")
+            sp, ns, _keep = _sets_arg(sets)
+            pp, npat, _keep2 = _patterns_arg(patterns)
+            self._check(self.lib.ttr_parseq_logits_patterns(self.h, _u8(crops), n, sp, ns, _i(so) if so is not None else None, pp, npat, _i(po), _f(logits),
+                                                            _f(ar) if want_ar else None, _i(ids)))
+        elif set_of is not None:
             so = np.ascontiguousarray(set_of, dtype=np.int32).ravel()
             if len(so) != n:
                 raise ValueError("set_of holds one entry per crop")
