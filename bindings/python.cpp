@@ -29,6 +29,10 @@
 // include/tuatara_hip.h lists), set on the cached engine for the call and reset afterwards, also when the call raises; calls that share the engine take turns.
 // "pattern" is also a key of a regions= dict: that region's own.  A bad pattern raises ValueError, naming the offset or the character, before anything runs;
 // a pattern with orient, alts or lexicon raises ValueError too.  The dicts' keys do not change.
+// And a keyword-only wide=False on image_to_data: wide=True (a piece is at most 8 times as wide as high) or wide=A (2..64) reads words wider than that in
+// pieces cut at ink gaps and joins the readings (DESIGN.md "Wide words"); every dict gains "pieces", a list of {"text", "conf", "quad"} (one, the item itself,
+// for a word that is not wide).  It turns rectify on.  A value out of range raises RuntimeError before anything runs; wide with orient, chars, alts, lexicon,
+// pattern or regions raises ValueError.
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -49,7 +53,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
@@ -86,6 +90,17 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
     }
     d["alternatives"] = per_char;
   }
+  if (k.pieces) {
+    py::list ps;
+    for (const WordPiece& p : item.pieces) {
+      py::dict pd;
+      pd["text"] = p.text;
+      pd["conf"] = p.conf;
+      pd["quad"] = quad_pairs(p.quad);
+      ps.append(pd);
+    }
+    d["pieces"] = ps;
+  }
   if (k.lexicon) {
     py::list l;
     for (const LexMatch& m : item.lexicon) l.append(py::make_tuple(m.word, std::exp((double)m.logp)));
@@ -98,6 +113,16 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
 static int alts_arg(int alts) {
   if (alts != 0 && (alts < 2 || alts > 8)) throw std::invalid_argument("alts must be 0 (off) or lie in 2..8");
   return alts;
+}
+
+// wide=False | True | a number -> max_aspect (0 = off); a number outside [2, 64] raises RuntimeError, anything else TypeError, before anything runs
+static float wide_arg(const py::object& wide) {
+  if (wide.is_none()) return 0.f;
+  if (py::isinstance<py::bool_>(wide)) return wide.cast<bool>() ? 8.f : 0.f;
+  if (!py::isinstance<py::float_>(wide) && !py::isinstance<py::int_>(wide)) throw py::type_error("wide must be False, True or a number in [2, 64]");
+  const double a = wide.cast<double>();
+  if (!(a >= 2. && a <= 64.)) throw std::runtime_error("wide must be False, True or a number in [2, 64]");
+  return (float)a;
 }
 
 // lexicon=None | a sequence of str, lexicon_m -> the word list (has = a list was given).  lexicon_m out of range, an empty list and a word with a NUL (which
@@ -201,8 +226,9 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
-                                      py::object pattern_kw) {
+                                      py::object pattern_kw, py::object wide_kw) {
   const int orient = orient_mode(orient_kw);
+  const float wide = wide_arg(wide_kw);
   alts_arg(alts);
   std::vector<std::string> words;
   const bool lex = lexicon_args(lexicon, lexicon_m, words);
@@ -210,8 +236,25 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   charset_args(allowlist, blocklist, allow, deny);
   const std::string pattern = pattern_arg(pattern_kw, allow, deny);
   if (!pattern.empty() && (orient || alts || lex)) throw std::invalid_argument("pattern does not combine with orient, alts or lexicon");
+  if (wide != 0.f && (orient || chars || alts || lex || !pattern.empty() || !regions_kw.is_none()))
+    throw std::invalid_argument("wide does not combine with orient, chars, alts, lexicon, pattern or regions");
   const bool cset = !allow.empty() || !deny.empty();
   lines = lines || blocks;   // blocks are made of lines
+  if (wide != 0.f) {   // wide words: rectified crops, the engine's setting for the call
+    py::buffer_info wb = image.request();
+    if (wb.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
+    if (wb.shape[2] != 3) throw std::runtime_error("Input array should have 3 channels");
+    std::vector<OutputItemEx> got;
+    {
+      py::gil_scoped_release nogil;
+      got = image_to_data_ex(static_cast<const uint8_t*>(wb.ptr), (int)wb.shape[0], (int)wb.shape[1], (std::ptrdiff_t)wb.shape[1] * 3, weights_dir, output_dir, true, -1, orient_page,
+                             lines, false, blocks, allow, deny, Wide{wide});
+    }
+    if (got.empty()) raise_refused();
+    py::list res;
+    for (const auto& item : got) res.append(item_dict(item, Keys{true, conf, false, lines, false, blocks, false, false, true}));
+    return res;
+  }
   if (!regions_kw.is_none()) {   // regions: no detector; every check before anything runs
     if (rectify || orient || orient_page || lines || chars || blocks) throw std::invalid_argument("regions do not combine with rectify, orient, lines, chars or blocks: a region is read as the quad it is");
     std::vector<RegionSpec> regs = region_args(regions_kw);
@@ -320,7 +363,7 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
         py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");

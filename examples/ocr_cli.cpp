@@ -29,6 +29,9 @@
 //   ocr_cli --lexicon FILE [--lexicon-m M] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: matches every word that is read against the word
 // list in FILE, one word per line (DESIGN.md "Lexicon matching"; empty lines are skipped).  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item, then its M best
 // entries (1..8, default 1), one line each: "<TAB>=i prob word", prob being exp(log-probability) to 6 decimals.  A bad entry fails, naming its index.
+//   ocr_cli --wide [A] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: reads words wider than A times their height (2..64, default 8) in
+// pieces cut at ink gaps, on rectified crops (DESIGN.md "Wide words").  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item and, under a wide item, one line per
+// piece: "<TAB>|conf text".  A value that is no number in [2, 64] fails before the image is read.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <algorithm>
 #include <cmath>
@@ -90,6 +93,27 @@ int main(int argc, const char** argv) {
       }
       setenv(opt == "--allowlist" ? "TUATARA_ALLOWLIST" : opt == "--blocklist" ? "TUATARA_BLOCKLIST" : "TUATARA_PATTERN", argv[2], 1);
       argv[2] = argv[0]; argv += 2; argc -= 2;
+    }
+    if (argc >= 2 && std::string(argv[1]) == "--wide") {
+      float a = 8.f;
+      if (argc == 6) {
+        char* end = nullptr;
+        const double v = std::strtod(argv[2], &end);
+        if (end == argv[2] || *end || !(v >= 2. && v <= 64.)) throw std::runtime_error("--wide takes an aspect in [2, 64] (default 8)");
+        a = (float)v;
+      }
+      if (argc != 5 && argc != 6) throw std::runtime_error("--wide [A] goes in front of <image.png> <weights_dir> <outputs_dir>");
+      const char* const* rest = argv + (argc - 3);                      // <image.png> <weights_dir> <outputs_dir>
+      pngdec::Image img = pngdec::read(rest[0]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, rest[1], rest[2], true, -1, false, false,
+                                                         false, false, std::string(), std::string(), Wide{a});
+      if (!last_call_error().empty()) return 1;                         // (the message is on stderr)
+      for (const OutputItemEx& it : items) {
+        printf("%g %g %g %g\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.conf, it.text.c_str());
+        if (it.pieces.size() > 1)
+          for (const WordPiece& p : it.pieces) printf("\t|%.6f %s\n", p.conf, p.text.c_str());
+      }
+      return 0;
     }
     int alts = 0, nbest_m = 0;
     while (argc >= 3 && (std::string(argv[1]) == "--alts" || std::string(argv[1]) == "--nbest")) {
@@ -233,7 +257,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--pattern P] [--alts K [--nbest M] | --lexicon FILE [--lexicon-m M] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--pattern P] [--wide [A] | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

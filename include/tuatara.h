@@ -49,6 +49,11 @@ struct LexMatch {                  // one entry of the caller's word list matche
   std::string word;                // the entry
   float logp = 0.f;                // its log-probability under the item's per-position distributions, the EOS behind it included
 };
+struct WordPiece {                 // one piece of a wide word (wide words; DESIGN.md "Wide words")
+  std::string text;                // the piece's reading
+  float conf = 0.f;                // the recogniser's confidence in it
+  std::vector<float> quad;         // 8: tl, tr, br, bl in image pixels
+};
 struct OutputItemEx {
   std::string text;
   std::vector<float> bbox;  // x1, y1, x2, y2
@@ -64,6 +69,7 @@ struct OutputItemEx {
   std::vector<float> alt_prob;     // [26][alt_k]: their probabilities, as ttr_result_alt_probs gives them
   std::vector<std::vector<CharAlt>> alternatives;   // one list per character of `text`: that position's character options in rank order, the character itself first unless another option ties it
   std::vector<LexMatch> lexicon;   // lexicon matching: the M best entries of the call's word list by (logp descending, index ascending); empty when no lexicon was given (DESIGN.md "Lexicon matching")
+  std::vector<WordPiece> pieces;   // wide words: the item's pieces in order (one, the item itself, when it is not wide); empty when wide is off (DESIGN.md "Wide words")
   int block = -1, block_line = -1;  // text blocks: the item's block of its page, in reading order, and its line's position inside that block (what a caller sorts by: block, block_line, word); -1 when blocks are off (DESIGN.md "Text blocks")
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
@@ -183,6 +189,18 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
 std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
                                                          bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
                                                          std::string allowlist, std::string blocklist, std::string pattern);
+
+// Wide words (opt-in; DESIGN.md "Wide words"): a word whose quad is wider than wide.max_aspect times its height - a URL, an IBAN, a serial number - is cut
+// into pieces at the gaps between characters, every piece is read as a crop of its own in the same recogniser pass, and the readings are joined: `text` is
+// the pieces' texts concatenated, `conf` the product of their conf, `pieces` lists them; char_conf covers the first piece.  Items, order, bbox and quad do not
+// change, and a word that is not wide keeps every bit.  The call reads on rectified crops whatever `rectify` says (a piece is a crop of the word's quad).
+// wide.max_aspect: a value in [2, 64]; Wide{} is 8, which nobody has tuned on documents.  It is set on the cached engine for the call and reset afterwards;
+// TUATARA_WIDE=A (or 1 for the default) in the environment turns it - and with it rectified crops - on for every call here.  With orient or chars, or a value
+// out of range: the message is printed and the result is empty (last_call_error()).
+struct Wide { float max_aspect = 8.f; };
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, Wide wide);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

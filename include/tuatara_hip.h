@@ -542,6 +542,47 @@ const int32_t* ttr_result_lex_idx_all(const ttr_result* r);
 const float* ttr_result_lex_logp_all(const ttr_result* r);
 int ttr_lexicon_encode(const char* const* words, int n, uint8_t* records);
 int ttr_logits_lexicon(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* idx, float* logp);
+/* ---- wide words (opt-in; DESIGN.md "Wide words") ---------------------------------------------
+ * Every recogniser row is one crop stretched to 32 x 128, and the recogniser emits at most 25 characters: a URL, an IBAN or a whole line handed in as one region
+ * reaches it with a few columns per character.  With ttr_engine_set_wide(e, max_aspect) a word whose quad is wider than max_aspect times its height is cut into
+ * n = min(16, ceil(aspect / max_aspect)) pieces at the gaps between characters, found in the page's own pixels (wide.hip), every piece is read as one more
+ * recogniser row of the same pass, and the readings are joined: the item's text is the pieces' texts concatenated (nothing between them), its conf the fp32
+ * product of the pieces' conf in order from 1.0f; its ids and prob rows are its first piece's.  bbox, quad, item count and order never change; a word with
+ * n = 1 keeps every bit.  Past 16 max_aspect the pieces are simply wider than max_aspect.
+ * max_aspect: 0 = off (the default), else a finite value in [2, 64]; anything else fails and changes nothing.  The setter also refuses, naming the reason: while
+ * streamed batches are in flight; on an engine whose crop_mode is not TTR_CROP_RECTIFIED; with orient or chars set; with alternatives, a lexicon or a pattern
+ * set; with a communicator attached.  The other way round ttr_engine_set_alternatives / _set_lexicon / _set_pattern, ttr_engine_attach_comm, a region call with
+ * patterns and ttr_pages_to_data_dev_sharded refuse while wide is on.  Character sets apply: the engine's on page calls, a region's own on each of its pieces.
+ * Result views (NULL / 0 with wide off and for an empty result): ttr_result_piece_first [count + 1] - item i owns pieces [first[i], first[i + 1]), an item that
+ * is not wide owns one, itself; ttr_result_piece_ids / _piece_probs [P][26]; _piece_confs [P]; _piece_quads [P][8] (tl, tr, br, bl); _piece_cuts [count][17] -
+ * c_0 = 0 < ... < c_n = 128 n in columns of the word's frame, -1 beyond n.  ttr_results_gather_pieces: the views of n results back to back - first
+ * [sum(count) + n] (each page's offsets from 0), ids / probs / confs / quads by piece, cuts by item; any pointer may be NULL; returns the total piece count, -1
+ * for bad arguments.
+ * The rule on the host, no engine (each returns 0 or the value named, -1 with the message in ttr_last_error):
+ *   ttr_wide_plan             quad [8], max_aspect (in [2, 64]) -> returns n; frame [6] = {X0f, Axf, Bxf, Y0f, Ayf, Byf} in 2^-16 px over 128 n columns x 32 rows
+ *   ttr_wide_profile          a host image u8 [h][w][3] (row_stride bytes, 0 = 3 w), frame, n -> q u16 [128 n]
+ *   ttr_wide_cuts_from_profile  q [128 n], n -> cuts [17]
+ *   ttr_wide_piece_coef       frame, c0, c1 -> the packer row [8] = {1, X0, Ax, Bx, Y0, Ay, By, 0} of the piece over columns [c0, c1)
+ *   ttr_wide_piece_quads      quad [8], cuts, n -> quads [n][8]
+ * ttr_wide_cuts (stage; refuses while batches stream): a host image and nq quads through wide_cut_kernel, whatever the engine's setting; use_table != 0 reads
+ * the page through the device page table as mixed-size batches do.  n_out [nq], cuts [nq][17], profiles [nq][2048] (0 beyond 128 n), coef [nq][16][8] (piece
+ * j of quad i at row 16 i + j, zeros beyond n); any output may be NULL. */
+int ttr_engine_set_wide(ttr_engine* e, float max_aspect);
+float ttr_engine_wide(const ttr_engine* e);
+const int32_t* ttr_result_piece_first(const ttr_result* r);
+const int32_t* ttr_result_piece_ids(const ttr_result* r);
+const float* ttr_result_piece_probs(const ttr_result* r);
+const float* ttr_result_piece_confs(const ttr_result* r);
+const float* ttr_result_piece_quads(const ttr_result* r);
+const int32_t* ttr_result_piece_cuts(const ttr_result* r);
+int ttr_results_gather_pieces(ttr_result* const* rs, int n, int32_t* first, int32_t* ids, float* probs, float* confs, float* quads, int32_t* cuts);
+int ttr_wide_plan(const float quad[8], float max_aspect, int64_t frame[6]);
+int ttr_wide_profile(const uint8_t* img, int h, int w, int row_stride, const int64_t frame[6], int n, uint16_t* q);
+int ttr_wide_cuts_from_profile(const uint16_t* q, int n, int32_t cuts[17]);
+int ttr_wide_piece_coef(const int64_t frame[6], int c0, int c1, int64_t row[8]);
+int ttr_wide_piece_quads(const float quad[8], const int32_t* cuts, int n, float* quads);
+int ttr_wide_cuts(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, float max_aspect, int use_table, int32_t* n_out,
+                  int32_t* cuts, uint16_t* profiles, int64_t* coef);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

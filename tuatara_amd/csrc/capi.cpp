@@ -1062,6 +1062,7 @@ int ttr_engine_set_pattern(ttr_engine* e, const char* pattern) {
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_engine_set_pattern");
   if (pattern && *pattern) {
+    if (E.wide != 0.f) throw std::runtime_error("ttr_engine_set_pattern: a pattern does not combine with wide words (a pattern spans the whole text, a piece reads a part of it): ttr_engine_set_wide(e, 0) first");
     if (E.prec == kBF16)
       throw std::runtime_error("ttr_engine_set_pattern: a pattern needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which know no automaton");
     if (E.cfg.orient != TTR_ORIENT_OFF)
@@ -1132,6 +1133,7 @@ int ttr_engine_set_alternatives(ttr_engine* e, int k) {
   EngineScope lk(E);
   if (k != 0 && (k < 2 || k > 8)) throw std::runtime_error("ttr_engine_set_alternatives: k must be 0 (off) or lie in 2..8, got " + std::to_string(k));
   E.refuse_while_streaming("ttr_engine_set_alternatives");
+  if (k && E.wide != 0.f) throw std::runtime_error("ttr_engine_set_alternatives: character alternatives do not combine with wide words (an item's positions span several rows): ttr_engine_set_wide(e, 0) first");
   if (k && E.prec == kBF16)
     throw std::runtime_error("ttr_engine_set_alternatives: character alternatives need an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which take no class mask");
   if (k && !E.pattern_src.empty())
@@ -1144,6 +1146,122 @@ int ttr_engine_set_alternatives(ttr_engine* e, int k) {
 }
 
 int ttr_engine_alternatives(const ttr_engine* e) { return e ? e->e->alts : 0; }
+
+// ---- wide words (DESIGN.md "Wide words")
+int ttr_engine_set_wide(ttr_engine* e, float max_aspect) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (!wide_aspect_ok(max_aspect)) throw std::runtime_error("ttr_engine_set_wide: max_aspect must be 0 (off) or a finite value in [2, 64]");
+  E.refuse_while_streaming("ttr_engine_set_wide");
+  if (max_aspect != 0.f) {
+    if (E.cfg.crop_mode != TTR_CROP_RECTIFIED)
+      throw std::runtime_error("ttr_engine_set_wide: wide words need crop_mode = TTR_CROP_RECTIFIED (a piece is a kind-1 crop of the word's quad): create the engine with it");
+    if (E.cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("ttr_engine_set_wide: wide words do not combine with word orientation: create the engine with orient = TTR_ORIENT_OFF");
+    if (E.cfg.chars) throw std::runtime_error("ttr_engine_set_wide: wide words do not combine with character boxes: create the engine with chars = 0");
+    if (E.alts) throw std::runtime_error("ttr_engine_set_wide: wide words do not combine with character alternatives: ttr_engine_set_alternatives(e, 0) first");
+    if (E.lex_v) throw std::runtime_error("ttr_engine_set_wide: wide words do not combine with a lexicon: ttr_engine_set_lexicon(e, NULL, 0, 0) first");
+    if (!E.pattern_src.empty()) throw std::runtime_error("ttr_engine_set_wide: wide words do not combine with a pattern: ttr_engine_set_pattern(e, NULL) first");
+    if (E.comm) throw std::runtime_error("ttr_engine_set_wide: wide words are read by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
+  }
+  E.wide = max_aspect;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+float ttr_engine_wide(const ttr_engine* e) { return e ? e->e->wide : 0.f; }
+
+const int32_t* ttr_result_piece_first(const ttr_result* r) { return r && !r->r.piece_first.empty() ? r->r.piece_first.data() : nullptr; }
+
+const int32_t* ttr_result_piece_ids(const ttr_result* r) { return r && !r->r.piece_ids.empty() ? r->r.piece_ids.data() : nullptr; }
+
+const float* ttr_result_piece_probs(const ttr_result* r) { return r && !r->r.piece_prob.empty() ? r->r.piece_prob.data() : nullptr; }
+
+const float* ttr_result_piece_confs(const ttr_result* r) { return r && !r->r.piece_conf.empty() ? r->r.piece_conf.data() : nullptr; }
+
+const float* ttr_result_piece_quads(const ttr_result* r) { return r && !r->r.piece_quad.empty() ? r->r.piece_quad.data() : nullptr; }
+
+const int32_t* ttr_result_piece_cuts(const ttr_result* r) { return r && !r->r.piece_cuts.empty() ? r->r.piece_cuts.data() : nullptr; }
+
+int ttr_results_gather_pieces(ttr_result* const* rs, int n, int32_t* first, int32_t* ids, float* probs, float* confs, float* quads, int32_t* cuts) {
+  if (!rs || n < 0) return -1;
+  size_t oi = 0, op = 0, of = 0;   // items, pieces, first entries so far
+  for (int i = 0; i < n; ++i) {
+    if (!rs[i]) { if (first) first[of] = 0; of += 1; continue; }
+    const Result& r = rs[i]->r;
+    const size_t cnt = r.text.size();
+    const bool has = cnt > 0 && r.piece_first.size() == cnt + 1;
+    const size_t np = has ? (size_t)r.piece_first[cnt] : 0;
+    if (first) { if (has) std::copy(r.piece_first.begin(), r.piece_first.end(), first + of); else std::fill(first + of, first + of + cnt + 1, 0); }
+    if (ids && np) std::copy(r.piece_ids.begin(), r.piece_ids.end(), ids + 26 * op);
+    if (probs && np) std::copy(r.piece_prob.begin(), r.piece_prob.end(), probs + 26 * op);
+    if (confs && np) std::copy(r.piece_conf.begin(), r.piece_conf.end(), confs + op);
+    if (quads && np) std::copy(r.piece_quad.begin(), r.piece_quad.end(), quads + 8 * op);
+    if (cuts) { if (has) std::copy(r.piece_cuts.begin(), r.piece_cuts.end(), cuts + 17 * oi); else std::fill(cuts + 17 * oi, cuts + 17 * (oi + cnt), -1); }
+    oi += cnt; op += np; of += cnt + 1;
+  }
+  return (int)op;
+}
+
+int ttr_wide_plan(const float quad[8], float max_aspect, int64_t frame[6]) {
+  TTR_GUARD_BEGIN
+  if (!quad || !frame) throw std::runtime_error("null argument");
+  if (!wide_aspect_ok(max_aspect) || max_aspect == 0.f) throw std::runtime_error("ttr_wide_plan: max_aspect must be a finite value in [2, 64]");
+  if (!region_quad_ok(quad)) throw std::runtime_error("ttr_wide_plan: a coordinate is not finite or has |x| >= 32768");
+  return wide_plan(quad, max_aspect, frame);
+  TTR_GUARD_END(-1)
+}
+
+int ttr_wide_profile(const uint8_t* img, int h, int w, int row_stride, const int64_t frame[6], int n, uint16_t* q) {
+  TTR_GUARD_BEGIN
+  if (!img || !frame || !q) throw std::runtime_error("null argument");
+  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("ttr_wide_profile: bad image size");
+  if (n < 1 || n > kWideMaxPieces) throw std::runtime_error("ttr_wide_profile: n must lie in 1..16");
+  wide_profile(img, h, w, row_stride ? row_stride : w * 3, frame, n, q);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_wide_cuts_from_profile(const uint16_t* q, int n, int32_t cuts[17]) {
+  TTR_GUARD_BEGIN
+  if (!q || !cuts) throw std::runtime_error("null argument");
+  if (n < 1 || n > kWideMaxPieces) throw std::runtime_error("ttr_wide_cuts_from_profile: n must lie in 1..16");
+  wide_cuts_from_profile(q, n, cuts);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_wide_piece_coef(const int64_t frame[6], int c0, int c1, int64_t row[8]) {
+  TTR_GUARD_BEGIN
+  if (!frame || !row) throw std::runtime_error("null argument");
+  if (c0 < 0 || c1 <= c0 || c1 > kWideMaxU) throw std::runtime_error("ttr_wide_piece_coef: the columns must satisfy 0 <= c0 < c1 <= 2048");
+  wide_piece_coef(frame, c0, c1, row);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_wide_piece_quads(const float quad[8], const int32_t* cuts, int n, float* quads) {
+  TTR_GUARD_BEGIN
+  if (!quad || !cuts || !quads) throw std::runtime_error("null argument");
+  if (n < 1 || n > kWideMaxPieces) throw std::runtime_error("ttr_wide_piece_quads: n must lie in 1..16");
+  wide_piece_quads(quad, cuts, n, quads);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_wide_cuts(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, float max_aspect, int use_table, int32_t* n_out,
+                  int32_t* cuts, uint16_t* profiles, int64_t* coef) {
+  TTR_GUARD_BEGIN
+  if (!e || nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
+  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_wide_cuts");
+  E.wide_cuts(img, h, w, row_stride, quads, nq, max_aspect, use_table != 0, n_out, cuts, profiles, coef);
+  return 0;
+  TTR_GUARD_END(-1)
+}
 
 int ttr_result_alt_k(const ttr_result* r) { return r ? r->r.alt_k : 0; }
 
@@ -1244,6 +1362,7 @@ int ttr_engine_set_lexicon(ttr_engine* e, const char* const* words, int n_words,
     E.lex_v = 0; E.lex_m = 0; E.lex_words.clear();
     return 0;
   }
+  if (E.wide != 0.f) throw std::runtime_error("ttr_engine_set_lexicon: lexicon matching does not combine with wide words (an entry spans the whole text, a piece reads a part of it): ttr_engine_set_wide(e, 0) first");
   if (E.prec == kBF16)
     throw std::runtime_error("ttr_engine_set_lexicon: lexicon matching needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which take no class mask");
   if (!E.pattern_src.empty())

@@ -323,6 +323,7 @@ int ttr_engine_attach_comm(ttr_engine* e, ttr_comm* c) {
   EngineScope lk(*e->e);
   if (e->e->q1.live || e->e->q2.live) throw std::runtime_error("streamed batches are in flight");
   if (c && c->c->E != e->e.get()) throw std::runtime_error("the communicator belongs to another engine");
+  if (c && e->e->wide != 0.f) throw std::runtime_error("ttr_engine_attach_comm: wide words are read by one engine alone, and wide is on: ttr_engine_set_wide(e, 0) first");
   e->e->comm = c ? c->c.get() : nullptr;
   return 0;
   TTR_GUARD_END(-1)

@@ -288,6 +288,11 @@ struct Result {
   std::vector<float> char_quad, char_bbox;  // 8 / 4 per character: tl, tr, br, bl; min x, min y, max x, max y
   std::vector<int32_t> char_cuts, char_mode;   // 27 / 1 per item: the cuts b[0..K] in 1/256 column (-1 beyond K); 0 uniform, 1 valley cuts
   std::vector<uint8_t> char_profile;        // 128 per item: the word's profile q
+  // wide words (ttr_engine_set_wide; DESIGN.md "Wide words"): empty when off
+  std::vector<int32_t> piece_first;         // [items + 1]: item i owns pieces [piece_first[i], piece_first[i + 1]); an item that is not wide owns one, itself
+  std::vector<int32_t> piece_ids;           // 26 per piece
+  std::vector<float> piece_prob, piece_conf, piece_quad;   // 26 / 1 / 8 per piece
+  std::vector<int32_t> piece_cuts;          // 17 per item: c_0 = 0 < ... < c_n = 128 n in frame columns, -1 beyond n
   // text blocks (cfg.blocks = 1; DESIGN.md "Text blocks"): empty / 0 when off
   std::vector<int32_t> line_block, line_pos;     // 1 per line: its block in reading order, its position inside that block
   std::vector<int32_t> block;                    // 1 per item: its line's block
@@ -410,6 +415,7 @@ struct Engine {
   int lex_v = 0, lex_m = 0;                       // V words, M matches kept per item (1..8)
   DevBuf lex_records;                             // [V] 32-byte records: length | 25 class bytes | zero padding (geometry.h: lexicon_encode)
   std::vector<std::string> lex_words;             // the host copy of the words (ttr_engine_lexicon_word)
+  float wide = 0.f;                               // wide words: the largest aspect a piece may have, 0 = off or 2..64 (ttr_engine_set_wide; DESIGN.md "Wide words")
   ClassMask charset{};                            // classes the recogniser may not choose (ttr_engine_set_charset; DESIGN.md "Character sets"); zero = no set
   // the engine's pattern (ttr_engine_set_pattern; DESIGN.md "Patterns"): empty = none.  `pattern` is pattern_src compiled under `charset`; its table lives in
   // pattern_dev (delta | mind, uploaded once by set_engine_pattern: nothing travels per call)
@@ -465,6 +471,8 @@ struct Engine {
     lex_part.ensure(pe * 8);
     return LexOut{lex_side.as<int>(), lex_side.as<float>() + (size_t)N * M, lex_part.as<int>(), lex_part.as<float>() + pe};
   }
+  DevBuf wide_side;                               // wide words: the side block (wide.hip), [Wn][17] int32 cuts | [Wn][2048] u16 profile
+  PinnedBuf h_wide[2];                            // ... per slot: the cuts' host copy
   DevBuf blocks_side;                             // text blocks: the side block (blocks.hip)
   PinnedBuf h_blocks[2];                          // ... per slot: its host copy
   DevBuf chars_map[2], chars_in, chars_side;      // character boxes: per slot the batch's region planes (a copy of ccl.tnorm); coef | page_of | turns | nchars; the side block (chars.hip)
@@ -720,6 +728,12 @@ struct Engine {
     std::vector<int64_t> coef;         // crop_mode = TTR_CROP_RECTIFIED: {kind, X0, Ax, Bx, Y0, Ay, By, 0} per crop, beside rects
     std::vector<int64_t> twin;         // orient != 0: {1, X0, Ax, Bx, Y0, Ay, By, 0} of the (K - 1) N twin crops, candidate-major (row (j - 1) N + c)
     int N = 0, slot = 0, group = 16;
+    // wide words (plan_wide; DESIGN.md "Wide words"): with wide_aspect != 0, rects / coef (and row_masks, when not empty) hold N + X rows - the pieces 1..n - 1 of
+    // all wide items behind the batch's N, in (item, piece) order; wide_of[c] = the item's entry of `wide`, or -1
+    float wide_aspect = 0.f;
+    int X = 0;
+    std::vector<WideWord> wide;
+    std::vector<int32_t> wide_of;
     int det_groups = -1;               // CRAFT groups enqueued for it (group_ev[det_groups]: behind the copy of its detector range word)
     bool live = false, enqueued = false;
     std::vector<int32_t> all_counts;   // with a communicator: crops per page of every rank [world][n]
@@ -758,6 +772,12 @@ struct Engine {
   void detect_collect_local(PageBatch& B);
 
   void recog_enqueue(PageBatch& B);
+  // wide words: plans every crop of B from quads [N][8] (the word's quad: deskew_quad's on page calls, the caller's on region calls) under the engine's `wide`;
+  // appends the extra rows to rects / coef / row_masks and fills wide / wide_of / X.  Host only; a no-op with wide off.
+  void plan_wide(PageBatch& B, const float* quads);
+  // the stage form (ttr_wide_cuts): a host image and host quads through wide_cut_kernel -> n [nq], cuts [nq][17], profiles [nq][2048], coef [nq][16][8]
+  void wide_cuts(const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, float max_aspect, bool use_table, int32_t* n_out, int32_t* cuts,
+                 uint16_t* profiles, int64_t* coef);
   // the crop packer of a batch whose rects / coef are known: copies them through the pinned staging of slot sl and enqueues
   // pack_crops_kernel (crop_mode 0) or pack_crops_rect_kernel (crop_mode 1) into `crops`
   void pack_batch_crops(const PageBatch& B, int sl);
@@ -794,7 +814,7 @@ struct Engine {
   // blocks_side: the text blocks' (blocks.hip) or null; alts_side: the alternatives' (decode_alts.hip, B.alts per position) or null; lex_side: the
   // lexicon matches' (lexicon.hip, B.lex_m per item) or null
   void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                    std::vector<Result>& results, const void* alts_side = nullptr, const void* lex_side = nullptr);
+                    std::vector<Result>& results, const void* alts_side = nullptr, const void* lex_side = nullptr, const int32_t* wide_cuts = nullptr);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it

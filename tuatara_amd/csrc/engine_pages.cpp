@@ -298,6 +298,7 @@ void Engine::detect_collect_local(PageBatch& B) {
   B.rects.clear(); B.page_of.clear(); B.coef.clear(); B.twin.clear();   // x0,y0,x1,y1,page per crop; page index per crop; rectified crops' coefficients; twins'
   const int K = orient_k();
   std::vector<Pt2f> oq;                                        // orient != 0: each word's quad Q (DESIGN.md "Word orientation")
+  std::vector<float> wq;                                       // wide != 0: each word's quad (DESIGN.md "Wide words")
   host_us[1] = host_us[2] = host_us[3] = 0.f;
   for (int gi = 0; gi < groups; ++gi) ccl_collect(gi * GP, std::min(GP, n - gi * GP), gi, B.H2, B.W2, dets);
   // the detector's range word of THIS batch, before any of its boxes is used: a saturated heat map fails this batch and no other
@@ -337,6 +338,7 @@ void Engine::detect_collect_local(PageBatch& B) {
         const int kind = deskew_quad(b, q, cf);
         deskew_fixed(cf, fx);
         B.coef.insert(B.coef.end(), {(int64_t)kind, fx[0], fx[1], fx[2], fx[3], fx[4], fx[5], 0});
+        if (wide != 0.f) for (int k = 0; k < 4; ++k) { wq.push_back(q[k].x); wq.push_back(q[k].y); }
       } else if (K > 1) {
         box_edge_quad(x0, y0, x1, y1, q);
       }
@@ -344,6 +346,7 @@ void Engine::detect_collect_local(PageBatch& B) {
     }
   }
   B.N = (int)B.page_of.size();
+  plan_wide(B, wq.data());
   for (int j = 1; j < K; ++j) {                                 // the twins, candidate-major in ascending turn
     const int t = K == 2 ? 2 * j : j;
     for (int c = 0; c < B.N; ++c) {
@@ -354,7 +357,36 @@ void Engine::detect_collect_local(PageBatch& B) {
   }
 }
 
+void Engine::plan_wide(PageBatch& B, const float* quads) {
+  B.wide_aspect = wide; B.X = 0; B.wide.clear(); B.wide_of.clear();
+  if (wide == 0.f) return;
+  const int N = B.N;
+  if (B.coef.size() != (size_t)N * 8 || B.rects.size() != (size_t)N * 5) throw std::runtime_error("wide words: coefficient count does not match the crop count");
+  B.wide_of.assign((size_t)N, -1);
+  for (int c = 0; c < N; ++c) {
+    WideWord W{};
+    const int n = wide_plan(quads + 8 * (size_t)c, wide, W.f);
+    if (n < 2) continue;                                       // keeps its crop of today in every bit
+    W.n = n; W.page = B.page_of[(size_t)c]; W.row = c; W.extra = N + B.X;
+    B.wide_of[(size_t)c] = (int32_t)B.wide.size();
+    B.wide.push_back(W);
+    B.X += n - 1;
+    B.coef[8 * (size_t)c] = 1;                                 // its first piece: the kind-1 sampler (wide_cut_kernel writes the row)
+  }
+  // the extra rows: each piece under its item's rectangle (kind 1 reads the coefficients alone) and mask
+  const bool masks = !B.row_masks.empty();
+  for (const WideWord& W : B.wide)
+    for (int j = 1; j < W.n; ++j) {
+      int rc[5];
+      memcpy(rc, &B.rects[5 * (size_t)W.row], sizeof rc);
+      B.rects.insert(B.rects.end(), rc, rc + 5);
+      B.coef.insert(B.coef.end(), {(int64_t)1, 0, 0, 0, 0, 0, 0, 0});
+      if (masks) { uint32_t m[4]; memcpy(m, &B.row_masks[4 * (size_t)W.row], sizeof m); B.row_masks.insert(B.row_masks.end(), m, m + 4); }
+    }
+}
+
 void Engine::pack_batch_crops(const PageBatch& B, int sl) {
+  const int rows = B.N + B.X;                                  // wide words: X more rows behind the batch's N
   rects_dev.ensure(B.rects.size() * 4);
   h_rects[sl].ensure(B.rects.size() * 4);
   memcpy(h_rects[sl].p, B.rects.data(), B.rects.size() * 4);
@@ -368,13 +400,22 @@ void Engine::pack_batch_crops(const PageBatch& B, int sl) {
     else launch_pack_crops(P0.data, page_bytes, P0.stride, rects_dev.as<int>(), crops.as<uint8_t>(), B.N, stream);
     return;
   }
-  if (B.coef.size() != (size_t)B.N * 8) throw std::runtime_error("rectified crops: coefficient count does not match the crop count");
-  coef_dev.ensure(B.coef.size() * 8);
-  h_coef[sl].ensure(B.coef.size() * 8);
-  memcpy(h_coef[sl].p, B.coef.data(), B.coef.size() * 8);
-  TTR_HIP_CHECK(hipMemcpyAsync(coef_dev.p, h_coef[sl].p, B.coef.size() * 8, hipMemcpyHostToDevice, stream));
-  if (B.mixed) { launch_pack_crops_rect_pages(table, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), B.N, stream); TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream)); }
-  else launch_pack_crops_rect(P0.data, page_bytes, P0.stride, P0.h, P0.w, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), B.N, stream);
+  if (B.coef.size() != (size_t)rows * 8 || B.rects.size() != (size_t)rows * 5) throw std::runtime_error("rectified crops: coefficient count does not match the crop count");
+  // wide words: the table of the batch's wide words travels behind the coefficients, in the same copy
+  const size_t coef_b = B.coef.size() * 8, words_b = B.wide.size() * sizeof(WideWord);
+  coef_dev.ensure(coef_b + words_b);
+  h_coef[sl].ensure(coef_b + words_b);
+  memcpy(h_coef[sl].p, B.coef.data(), coef_b);
+  if (words_b) memcpy(h_coef[sl].as<uint8_t>() + coef_b, B.wide.data(), words_b);
+  TTR_HIP_CHECK(hipMemcpyAsync(coef_dev.p, h_coef[sl].p, coef_b + words_b, hipMemcpyHostToDevice, stream));
+  if (words_b) {   // the cuts, and every piece's packer row straight into coef_dev (wide.hip)
+    const int Wn = (int)B.wide.size();
+    wide_side.ensure(wide_side_bytes(Wn));
+    launch_wide_cut(reinterpret_cast<const WideWord*>(coef_dev.as<uint8_t>() + coef_b), Wn, P0.data, page_bytes, P0.stride, P0.h, P0.w, table, coef_dev.as<int64_t>(), rows,
+                    wide_side.as<int>(), stream);
+  }
+  if (B.mixed) { launch_pack_crops_rect_pages(table, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), rows, stream); TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream)); }
+  else launch_pack_crops_rect(P0.data, page_bytes, P0.stride, P0.h, P0.w, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), rows, stream);
 }
 
 void Engine::pack_twin_crops(const PageBatch& B, int sl) {
@@ -583,6 +624,44 @@ void Engine::char_cuts(const float* tnorm, int H2, int W2, float ratio, float lo
   if (profiles) memcpy(profiles, side + (size_t)n * 28, (size_t)n * 128);
 }
 
+void Engine::wide_cuts(const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, float max_aspect, bool use_table, int32_t* n_out, int32_t* cuts,
+                       uint16_t* profiles, int64_t* coef) {
+  if (nq <= 0) return;
+  if (!wide_aspect_ok(max_aspect) || max_aspect == 0.f) throw std::runtime_error("ttr_wide_cuts: max_aspect must be a finite value in [2, 64]");
+  if ((size_t)h * w > ((size_t)1 << 28)) throw std::runtime_error("ttr_wide_cuts: bad image size");
+  // coef_dev: coef int64 [nq][16][8] | words [nq]: word i owns rows 16 i .. 16 i + 15 (its row, then its extra rows)
+  const int rows = nq * kWideMaxPieces;
+  const size_t coef_b = (size_t)rows * 64, words_b = (size_t)nq * sizeof(WideWord), side_b = wide_side_bytes(nq), img_b = (size_t)h * w * 3;
+  h_coef[0].ensure(coef_b + words_b); coef_dev.ensure(coef_b + words_b); wide_side.ensure(side_b); staging_img.ensure(img_b);
+  std::vector<uint8_t> side(side_b);
+  memset(h_coef[0].p, 0, coef_b);
+  WideWord* words = reinterpret_cast<WideWord*>(h_coef[0].as<uint8_t>() + coef_b);
+  for (int i = 0; i < nq; ++i) {
+    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error("ttr_wide_cuts: quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+    WideWord W{};
+    W.n = wide_plan(quads + 8 * (size_t)i, max_aspect, W.f);
+    W.page = 0; W.row = i * kWideMaxPieces; W.extra = W.row + 1;
+    words[i] = W;
+    if (n_out) n_out[i] = W.n;
+  }
+  TTR_HIP_CHECK(hipMemcpy2DAsync(staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(coef_dev.p, h_coef[0].p, coef_b + words_b, hipMemcpyHostToDevice, stream));
+  const PageRow* table = nullptr;
+  if (use_table) {
+    std::vector<Page> pages(1, Page{staging_img.as<uint8_t>(), h, w, w * 3, CanvasGeom{h, w, h, w, 1.f}});
+    upload_page_table(pages, 0);
+    table = page_table[0].as<PageRow>();
+  }
+  launch_wide_cut(reinterpret_cast<const WideWord*>(coef_dev.as<uint8_t>() + coef_b), nq, staging_img.as<uint8_t>(), 0, w * 3, h, w, table, coef_dev.as<int64_t>(), rows,
+                  wide_side.as<int>(), stream);
+  if (use_table) TTR_HIP_CHECK(hipEventRecord(table_ev[0], stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(side.data(), wide_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  if (coef) TTR_HIP_CHECK(hipMemcpyAsync(coef, coef_dev.p, coef_b, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  if (cuts) memcpy(cuts, side.data(), (size_t)nq * 17 * 4);
+  if (profiles) memcpy(profiles, side.data() + (size_t)nq * 17 * 4, (size_t)nq * 2048 * 2);
+}
+
 void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
   const int line_words = cfg.lines && N > 0 ? stage_batch_lines(B, sl) : 0;   // text lines: the host part, before anything of this batch is enqueued
@@ -590,15 +669,17 @@ void Engine::recog_enqueue(PageBatch& B) {
   B.alts = orient_k() > 1 ? 0 : alts;        // character alternatives: fixed for the batch here (the setter refuses while batches stream)
   B.lex_m = lex_v && orient_k() <= 1 ? lex_m : 0;   // lexicon matching: likewise (0 = no lexicon set)
   range_use(kRangeRec0 + (sl & 1));          // the recogniser's kernels of this batch watch the slot's own word
-  B.rows = std::max(N, comm ? B.cap : 0);   // the output block's rows (RecOut): with a communicator, the gathered payload's rows per rank
+  const int X = B.X;                         // wide words: the pieces behind the batch's N, read as a pass of their own (DESIGN.md "Wide words"); 0 with wide off
+  B.rows = std::max(N + X, comm ? B.cap : 0);   // the output block's rows (RecOut): with a communicator, the gathered payload's rows per rank
   const size_t block = (size_t)B.rows * kRecWords * 4;
   h_ids[sl].ensure(block + 4);
   const RecOut out = rec_out(B.rows);
   TTR_HIP_CHECK(hipEventRecord(evr[sl][0], stream));
   if (N > 0) {
     const int K = orient_k(), T = (K - 1) * N;                 // word orientation: T twin crops behind the batch's N (DESIGN.md "Word orientation")
-    crops.ensure((size_t)(N + T) * 32 * 128 * 3);
-    logits.ensure((size_t)std::max(N, T) * kLogitWords * 4);
+    crops.ensure((size_t)(N + T + X) * 32 * 128 * 3);
+    logits.ensure((size_t)std::max(std::max(N, X), T) * kLogitWords * 4);
+    if (X) h_wide[sl].ensure(B.wide.size() * 17 * 4);
     const RecOut cand = T ? rec_block(orient_cand, T) : RecOut{};
     const size_t side_b = ((size_t)N * (K + 1) + B.n) * 4;   // [N] turn | [N][K] candidate conf | [pages] page turn
     if (T) { orient_side.ensure(side_b); h_orient[sl].ensure(side_b); }
@@ -619,9 +700,15 @@ void Engine::recog_enqueue(PageBatch& B) {
       charset = B.region_mask;
       PatDev pd{};                 // ... and the regions' patterns: the call's table the same way (one more copy, no launch)
       if (!B.region_pats.start_of.empty()) pd = stage_row_patterns(B.region_pats, sl);
-      parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, stage_row_masks(B.row_masks, sl), alt.ids, alt.prob, lex, pd.delta ? &pd : nullptr);
-    } else
+      const RowMask* masks = stage_row_masks(B.row_masks, sl);
+      parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, masks, alt.ids, alt.prob, lex, pd.delta ? &pd : nullptr);
+      // wide words: the X other pieces as a pass of their own, into rows N.. of the same block - the batch's N rows keep their batch, and with it every bit of
+      // the words that are not wide (the recogniser picks its kernels by the row count)
+      if (X) parseq_forward(crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, X, logits.as<float>(), nullptr, out.ids + (size_t)N * 26, out.prob + (size_t)N * 26, out.conf + N, masks ? masks + N : nullptr);
+    } else {
     parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, nullptr, alt.ids, alt.prob, lex);
+    if (X) parseq_forward(crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, X, logits.as<float>(), nullptr, out.ids + (size_t)N * 26, out.prob + (size_t)N * 26, out.conf + N);
+    }
     if (T) {   // the twins as a pass of their own (turn 0 keeps its batch, and with it its bits), then the choice, in place in the standard block
       parseq_forward(crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, logits.as<float>(), nullptr, cand.ids, cand.prob, cand.conf);
       const size_t first_off = (size_t)T * 84;
@@ -634,6 +721,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (T) TTR_HIP_CHECK(hipMemcpyAsync(h_orient[sl].p, orient_side.p, side_b, hipMemcpyDeviceToHost, stream));
     if (B.alts) TTR_HIP_CHECK(hipMemcpyAsync(h_alts[sl].p, alts_side.p, alts_side_bytes(N, B.alts), hipMemcpyDeviceToHost, stream));   // the alternatives' side block, behind the standard block's copy
     if (B.lex_m) TTR_HIP_CHECK(hipMemcpyAsync(h_lex[sl].p, lex_side.p, lex_side_bytes(N, B.lex_m), hipMemcpyDeviceToHost, stream));   // the lexicon matches' side block, likewise
+    if (X) TTR_HIP_CHECK(hipMemcpyAsync(h_wide[sl].p, wide_side.p, B.wide.size() * 17 * 4, hipMemcpyDeviceToHost, stream));   // the wide words' cuts (the profile stays on the device)
   } else {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
@@ -672,13 +760,14 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   const int32_t* blocks_block = cfg.blocks && N > 0 ? h_blocks[B.slot].as<int32_t>() : nullptr;   // the side block (blocks.hip)
   const void* alts_block = B.alts && N > 0 ? h_alts[B.slot].p : nullptr;                        // the side block (decode_alts.hip)
   const void* lex_block = B.lex_m && N > 0 ? h_lex[B.slot].p : nullptr;                         // the side block (lexicon.hip)
-  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block);
+  const int32_t* wide_block = B.X && N > 0 ? h_wide[B.slot].as<int32_t>() : nullptr;            // the cuts of the side block (wide.hip)
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block, wide_block);
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
 
 void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                          std::vector<Result>& results, const void* alts_side, const void* lex_side) {
+                          std::vector<Result>& results, const void* alts_side, const void* lex_side, const int32_t* wide_cuts) {
   const int n = B.n, N = B.N, K = orient_k();
   const std::vector<int> first = page_first(B.page_of, n);
   // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
@@ -731,6 +820,47 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
       tesseract_bbox(B.boxes[pg][k], bb);                                    // :511
       r.bbox.insert(r.bbox.end(), bb, bb + 4);
       push_quad(B.boxes[pg][k], r.quad);
+    }
+    if (B.wide_aspect != 0.f && cnt > 0) {   // wide words: every item's pieces; a wide item's text and conf joined from them (its ids and prob stay its first piece's)
+      r.piece_first.assign((size_t)cnt + 1, 0);
+      r.piece_cuts.assign((size_t)cnt * 17, -1);
+      for (int k = 0; k < cnt; ++k) {
+        const int wi = B.wide_of[(size_t)(c0 + k)];
+        r.piece_first[(size_t)k + 1] = r.piece_first[k] + (wi < 0 ? 1 : B.wide[(size_t)wi].n);
+      }
+      const size_t P = (size_t)r.piece_first[cnt];
+      r.piece_ids.reserve(P * 26); r.piece_prob.reserve(P * 26); r.piece_conf.reserve(P); r.piece_quad.assign(P * 8, 0.f);
+      for (int k = 0; k < cnt; ++k) {
+        const int c = c0 + k, wi = B.wide_of[(size_t)c];
+        int32_t* cuts = &r.piece_cuts[(size_t)k * 17];
+        float* pq = &r.piece_quad[8 * (size_t)r.piece_first[k]];
+        if (wi < 0) {
+          cuts[0] = 0; cuts[1] = kWideCols;
+          r.piece_ids.insert(r.piece_ids.end(), &rows.ids[(size_t)c * 26], &rows.ids[(size_t)(c + 1) * 26]);
+          r.piece_prob.insert(r.piece_prob.end(), &rows.prob[(size_t)c * 26], &rows.prob[(size_t)(c + 1) * 26]);
+          r.piece_conf.push_back(rows.conf[c]);
+          std::copy(&r.quad[(size_t)k * 8], &r.quad[(size_t)k * 8 + 8], pq);
+          continue;
+        }
+        const WideWord& W = B.wide[(size_t)wi];
+        if (!wide_cuts || !wide_cuts_valid(wide_cuts + 17 * (size_t)wi, W.n))
+          throw std::runtime_error("wide words: the side block of word " + std::to_string(k) + " of page " + std::to_string(pg) + " does not hold " + std::to_string(W.n) +
+                                   " ascending pieces of 64 to 192 columns");
+        std::copy(wide_cuts + 17 * (size_t)wi, wide_cuts + 17 * (size_t)wi + 17, cuts);
+        wide_piece_quads(&r.quad[(size_t)k * 8], cuts, W.n, pq);
+        std::string text;
+        float conf = 1.0f;
+        for (int j = 0; j < W.n; ++j) {
+          const size_t row = j == 0 ? (size_t)c : (size_t)W.extra + (size_t)j - 1;
+          r.piece_ids.insert(r.piece_ids.end(), &rows.ids[row * 26], &rows.ids[(row + 1) * 26]);
+          r.piece_prob.insert(r.piece_prob.end(), &rows.prob[row * 26], &rows.prob[(row + 1) * 26]);
+          r.piece_conf.push_back(rows.conf[row]);
+          text += tok.decode(&rows.ids[row * 26], 26);
+          conf = conf * rows.conf[row];
+        }
+        r.text[(size_t)k] = text;
+        r.conf[(size_t)k] = conf;
+      }
     }
     if (lines_side && cnt > 0) {   // [N] line | [N] word | [pages] n_lines -> the page's lines in reading order
       r.line.assign(&lines_side[c0], &lines_side[c0 + cnt]);
@@ -996,6 +1126,7 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
   if (n_patterns > 0 && n > 0 && !pattern_of) throw std::runtime_error("null argument");
   PatRows pats;   // (in the caller's order; the batch holds them in crop order)
   const bool with_pats = resolve_row_patterns(what, patterns, n_patterns, pattern_of, n, table, one, pats);
+  if (with_pats && wide != 0.f) throw std::runtime_error("regions: patterns do not combine with wide words (a pattern spans the whole text, a piece reads a part of it): ttr_engine_set_wide(e, 0) first");
   results.assign((size_t)n_pages, Result());
   if (n_pages == 0) return;
   // ---- the batch: crops by page, then in the caller's order within the page (a stable counting sort)
@@ -1024,6 +1155,7 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
     if (!table.empty()) memcpy(&B.row_masks[4 * c], &table[4 * (size_t)i], 16);
     if (with_pats) B.region_pats.start_of[c] = pats.start_of[(size_t)i];
   }
+  plan_wide(B, B.region_quad.data());   // wide words: the pieces' rows behind the call's n (DESIGN.md "Wide words")
   const double th0 = now_us();
   for (int k = 0; k < 3; ++k) TTR_HIP_CHECK(hipEventRecord(ev[k], stream));   // no detector: its two stage times of this call are zero
   if (n > 0) upload_page_table(B.pages, 0);
@@ -1034,6 +1166,7 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
 }
 
 void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results) {
+  if (wide != 0.f) throw std::runtime_error("latency mode does not support wide words: ttr_engine_set_wide(e, 0) first");
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");
   if (cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("latency mode does not support word orientation: create the engine with orient = TTR_ORIENT_OFF");
   if (cfg.blocks) throw std::runtime_error("latency mode does not support text blocks: create the engine with blocks = 0");

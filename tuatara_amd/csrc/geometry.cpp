@@ -119,6 +119,112 @@ bool region_inside(const float* q, int h, int w) {
   return true;
 }
 
+// ---------------------------------------------------------------- wide words (DESIGN.md "Wide words")
+bool wide_aspect_ok(float a) { return a == 0.f || (std::isfinite(a) && a >= 2.f && a <= 64.f); }
+
+int wide_plan(const float* q, float max_aspect, int64_t frame[6]) {
+  const double Ax = (double)q[2] - (double)q[0], Ay = (double)q[3] - (double)q[1];
+  const double Bx = (double)q[6] - (double)q[0], By = (double)q[7] - (double)q[1];
+  const double a2 = Ax * Ax + Ay * Ay, b2 = Bx * Bx + By * By;
+  int n = 1;
+  if (b2 != 0. && max_aspect > 0.f) {
+    const double r = std::ceil(std::sqrt(a2 / b2) / (double)max_aspect);
+    n = !(r >= 1.) ? 1 : r >= (double)kWideMaxPieces ? kWideMaxPieces : (int)r;
+  }
+  const double U = (double)(kWideCols * n);
+  const double Axf = Ax / U, Bxf = Bx / 32., Ayf = Ay / U, Byf = By / 32.;
+  double x0 = (double)q[0] + 0.5 * Axf;
+  x0 = x0 + 0.5 * Bxf;
+  double y0 = (double)q[1] + 0.5 * Ayf;
+  y0 = y0 + 0.5 * Byf;
+  const double cf[6] = {x0, Axf, Bxf, y0, Ayf, Byf};
+  deskew_fixed(cf, frame);
+  return n;
+}
+
+void wide_profile(const uint8_t* image, int h, int w, int stride, const int64_t f[6], int n, uint16_t* q) {
+  const int U = kWideCols * n;
+  for (int u = 0; u < U; ++u) {
+    int lo = 0, hi = 0;
+    for (int v = 0; v < kWideV; ++v) {
+      int64_t ix = (f[0] + u * f[1] + v * f[2] + 32768) >> 16, iy = (f[3] + u * f[4] + v * f[5] + 32768) >> 16;
+      ix = ix < 0 ? 0 : ix > w - 1 ? w - 1 : ix;
+      iy = iy < 0 ? 0 : iy > h - 1 ? h - 1 : iy;
+      const uint8_t* p = image + (size_t)iy * (size_t)stride + (size_t)ix * 3;
+      const int y = p[0] + 2 * p[1] + p[2];
+      if (v == 0) lo = hi = y;
+      else { lo = std::min(lo, y); hi = std::max(hi, y); }
+    }
+    q[u] = (uint16_t)(hi - lo);
+  }
+}
+
+void wide_cuts_from_profile(const uint16_t* q, int n, int32_t cuts[17]) {
+  for (int i = 0; i <= kWideMaxPieces; ++i) cuts[i] = -1;
+  if (n < 1 || n > kWideMaxPieces) return;
+  const int U = kWideCols * n;
+  std::vector<int32_t> D[2] = {std::vector<int32_t>((size_t)U + 1, kWideInf), std::vector<int32_t>((size_t)U + 1, kWideInf)};
+  std::vector<uint8_t> arg((size_t)(n + 1) * ((size_t)U + 1), 0);
+  D[0][0] = 0;
+  for (int j = 1; j <= n; ++j) {
+    const std::vector<int32_t>& prev = D[(j - 1) & 1];
+    std::vector<int32_t>& cur = D[j & 1];
+    std::fill(cur.begin(), cur.end(), kWideInf);
+    for (int c = (j < n ? 1 : U); c <= (j < n ? U - 1 : U); ++c) {
+      int32_t best = kWideInf; int bw = kWideWLo;
+      const int32_t gap = j < n ? (int32_t)q[c - 1] + (int32_t)q[c] : 0;
+      for (int wd = kWideWLo; wd <= kWideWHi && c - wd >= 0; ++wd) {
+        const int32_t d = prev[(size_t)(c - wd)];
+        if (d >= kWideInf) continue;
+        const int32_t cost = d + 2 * std::abs(wd - kWideCols) + gap;
+        if (cost < best) { best = cost; bw = wd; }
+      }
+      cur[(size_t)c] = best;
+      arg[(size_t)j * ((size_t)U + 1) + (size_t)c] = (uint8_t)(bw - kWideWLo);
+    }
+  }
+  int c = U;
+  for (int j = n; j >= 1; --j) {
+    cuts[j] = c;
+    c -= (int)arg[(size_t)j * ((size_t)U + 1) + (size_t)c] + kWideWLo;
+    if (c < 0) c = 0;   // (never: the all-128 path exists; keeps the walk inside the table whatever the input)
+  }
+  cuts[0] = c;
+}
+
+void wide_piece_coef(const int64_t f[6], int c0, int c1, int64_t row[8]) {
+  const int64_t wd = c1 - c0;
+  const int64_t Axp = (f[1] * wd + 64) >> 7, Ayp = (f[4] * wd + 64) >> 7;
+  row[0] = 1;
+  row[1] = f[0] + f[1] * c0 + ((Axp - f[1]) >> 1); row[2] = Axp; row[3] = f[2];
+  row[4] = f[3] + f[4] * c0 + ((Ayp - f[4]) >> 1); row[5] = Ayp; row[6] = f[5];
+  row[7] = 0;
+}
+
+void wide_piece_quads(const float* q, const int32_t* cuts, int n, float* quads) {
+  const double U = (double)(kWideCols * n);
+  const double tlx = q[0], tly = q[1], blx = q[6], bly = q[7];
+  const double Ax = (double)q[2] - tlx, Ay = (double)q[3] - tly, Cx = (double)q[4] - blx, Cy = (double)q[5] - bly;
+  for (int j = 0; j < n; ++j) {
+    const double t0 = (double)cuts[j] / U, t1 = (double)cuts[j + 1] / U;
+    float* o = quads + 8 * (size_t)j;
+    o[0] = (float)(tlx + t0 * Ax); o[1] = (float)(tly + t0 * Ay);
+    o[2] = (float)(tlx + t1 * Ax); o[3] = (float)(tly + t1 * Ay);
+    o[4] = (float)(blx + t1 * Cx); o[5] = (float)(bly + t1 * Cy);
+    o[6] = (float)(blx + t0 * Cx); o[7] = (float)(bly + t0 * Cy);
+  }
+}
+
+bool wide_cuts_valid(const int32_t cuts[17], int n) {
+  if (n < 1 || n > kWideMaxPieces || cuts[0] != 0 || cuts[n] != kWideCols * n) return false;
+  for (int j = 0; j < n; ++j) {
+    const int wd = cuts[j + 1] - cuts[j];
+    if (wd < kWideWLo || wd > kWideWHi) return false;
+  }
+  for (int j = n + 1; j <= kWideMaxPieces; ++j) if (cuts[j] != -1) return false;
+  return true;
+}
+
 // ---------------------------------------------------------------- word orientation (DESIGN.md "Word orientation")
 void box_edge_quad(int x0, int y0, int x1, int y1, Pt2f quad[4]) {
   const float l = (float)x0 - 0.5f, t = (float)y0 - 0.5f, r = (float)x1 - 0.5f, b = (float)y1 - 0.5f;

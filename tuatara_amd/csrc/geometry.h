@@ -95,6 +95,26 @@ void chars_quads_from_cuts(const float* quad8, int turn, const int32_t* cuts, in
 // what decode_pages accepts from the device: K + 1 ascending entries in [0, 32768], then -1
 bool chars_cuts_valid(const int32_t cuts[27], int K);
 
+// Wide words (ttr_engine_set_wide; DESIGN.md "Wide words").  A quad far wider than the recogniser's 4:1 crop is read in n pieces cut at ink gaps found in
+// the page's own pixels.  Constants of the rule: at most kWideMaxPieces pieces, kWideV rows, kWideCols nominal columns per piece, widths in [kWideWLo, kWideWHi].
+constexpr int kWideMaxPieces = 16, kWideV = 32, kWideCols = 128, kWideWLo = 64, kWideWHi = 192, kWideMaxU = kWideMaxPieces * kWideCols, kWideInf = 0x3fffffff;
+// the setter's domain: 0 (off) or a finite value in [2, 64]
+bool wide_aspect_ok(float max_aspect);
+// one quad (8 floats tl, tr, br, bl) -> n, the pieces (1 = not wide), and frame = {X0f, Axf, Bxf, Y0f, Ayf, Byf} in 2^-16 px over U = 128 n columns and 32 rows:
+// double, one rounding per statement, then llrint(65536 x).  For n = 1 the frame is region_coef's.
+int wide_plan(const float* quad8, float max_aspect, int64_t frame[6]);
+// the contrast profile q[128 n] of the frame on a page u8 [h][w][3] (row stride in bytes): per column max - min over the 32 rows of R + 2 G + B at the nearest
+// pixel, clamped to the page (wide_cut_kernel, wide.hip, computes the same words)
+void wide_profile(const uint8_t* image, int h, int w, int stride, const int64_t frame[6], int n, uint16_t* q);
+// q[128 n], n (1..16) -> cuts[17]: c_0 = 0 < ... < c_n = 128 n, -1 beyond n.  int32 arithmetic only; ties go to the smallest width.
+void wide_cuts_from_profile(const uint16_t* q, int n, int32_t cuts[17]);
+// the packer row {1, X0_p, Ax_p, Bx_p, Y0_p, Ay_p, By_p, 0} of the piece over columns [c0, c1) of the frame (int64, arithmetic shifts)
+void wide_piece_coef(const int64_t frame[6], int c0, int c1, int64_t row[8]);
+// the n pieces' quads [n][8] of a word's quad from its cuts, in double, cast to float
+void wide_piece_quads(const float* quad8, const int32_t* cuts, int n, float* quads);
+// what decode_pages accepts from the device: c_0 = 0, ascending, c_n = 128 n, every width in [64, 192], -1 beyond n
+bool wide_cuts_valid(const int32_t cuts[17], int n);
+
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.
 struct Component {

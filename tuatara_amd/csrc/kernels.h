@@ -331,6 +331,17 @@ void launch_pack_crops_rect(const uint8_t* images, size_t page_bytes, int stride
 // everything else, and every byte of a crop, as above
 void launch_pack_crops_pages(const PageRow* table, const int* rects5, uint8_t* out, int N, hipStream_t s);
 void launch_pack_crops_rect_pages(const PageRow* table, const int* rects5, const int64_t* coef8, uint8_t* out, int N, hipStream_t s);
+// ---- wide.hip (DESIGN.md "Wide words")
+// one wide word of a batch: its frame (geometry.h: wide_plan), its pieces, its page (the rects' page index / the PageRow index), its row of the coefficient
+// table and the first of its n - 1 extra rows
+struct WideWord { int64_t f[6]; int32_t n, page, row, extra; };
+static_assert(sizeof(WideWord) == 64, "WideWord is one 64-byte entry");
+// the side block of Wn words: [Wn][17] int32 cuts | [Wn][2048] u16 profile
+inline size_t wide_side_bytes(int Wn) { return (size_t)Wn * (17 * 4 + 2048 * 2); }
+// wide_cut_kernel: profile, cuts and the pieces' packer rows (written into coef8 [rows][8]) of every word; the pages as the rect packers take them - table
+// null: images / page_bytes / stride / h / w of a uniform batch, else the device page table
+void launch_wide_cut(const WideWord* words, int Wn, const uint8_t* images, size_t page_bytes, int stride, int h, int w, const PageRow* table, int64_t* coef8,
+                     int rows, int* side, hipStream_t s);
 // get_detected_boxes' per-component tail on the GPU (tuatara.cpp:162-179: niter, ROI, dilation, findNonZero + minAreaRect): one lane per candidate, geometry.cpp's
 // arithmetic step for step (float32 calipers, double where OpenCV is double) -> CclBuffers::rects.  After launch_ccl on the same stream.
 void launch_ccl_rects(const CclBuffers& b, int pages, int H, int W, hipStream_t s);

@@ -24,6 +24,7 @@ ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int o
   ttr_config cfg;
   ttr_config_default(&cfg);
   if (const char* p = std::getenv("TUATARA_CROP_MODE")) cfg.crop_mode = std::atoi(p);
+  if (std::getenv("TUATARA_WIDE")) cfg.crop_mode = TTR_CROP_RECTIFIED;   // wide words read on rectified crops (DESIGN.md "Wide words")
   if (crop_mode >= 0) cfg.crop_mode = crop_mode;
   if (const char* p = std::getenv("TUATARA_ORIENT")) {
     const std::string v(p);
@@ -64,9 +65,9 @@ struct CharsetScope {
   ttr_engine* e;
   std::unique_lock<std::mutex> turn;
   bool set = false, ok = true;
-  bool alts_set = false, lex_set = false, pattern_set = false;
+  bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false;
   CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
-               std::string pattern = std::string()) : e(e_) {
+               std::string pattern = std::string(), float wide = 0.f) : e(e_) {
     {
       std::lock_guard<std::mutex> lk(g_mu);
       auto& m = g_call_mu[e];
@@ -91,6 +92,11 @@ struct CharsetScope {
       }
       lex_set = true;
     }
+    if (wide == 0.f) if (const char* p = std::getenv("TUATARA_WIDE")) wide = std::string(p) == "1" ? 8.f : (float)std::atof(p);
+    if (wide != 0.f) {   // wide words (DESIGN.md "Wide words"): the largest aspect of a piece for the call, like the set
+      if (ttr_engine_set_wide(e, wide) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      wide_set = true;
+    }
     if (pattern.empty()) if (const char* p = std::getenv("TUATARA_PATTERN")) pattern = p;
     if (!allow.empty() || !deny.empty()) {
       if (ttr_engine_set_charset(e, allow.c_str(), deny.c_str()) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
@@ -103,6 +109,7 @@ struct CharsetScope {
   }
   ~CharsetScope() {
     if (pattern_set) ttr_engine_set_pattern(e, nullptr);
+    if (wide_set) ttr_engine_set_wide(e, 0.f);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
     if (alts_set) ttr_engine_set_alternatives(e, 0);
     if (lex_set) ttr_engine_set_lexicon(e, nullptr, 0, 0);
@@ -172,6 +179,19 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
       o.lexicon.push_back(std::move(mt));
     }
   }
+  o.pieces.clear();
+  if (const int32_t* pf = ttr_result_piece_first(r)) {
+    const int32_t* pi = ttr_result_piece_ids(r);
+    const float *pc = ttr_result_piece_confs(r), *pq = ttr_result_piece_quads(r);
+    for (int32_t k = pf[i]; k < pf[i + 1]; ++k) {
+      WordPiece p;
+      char buf[32];
+      ttr_decode_ids(pi + 26 * (size_t)k, 26, buf);
+      p.text = buf; p.conf = pc[k];
+      p.quad.assign(pq + 8 * (size_t)k, pq + 8 * (size_t)k + 8);
+      o.pieces.push_back(std::move(p));
+    }
+  }
   o.chars.clear();
   if (const int32_t* cf = ttr_result_char_first(r)) {
     const float *cq = ttr_result_char_quads(r), *cb = ttr_result_char_bboxes(r);
@@ -200,10 +220,10 @@ template <class Item>
 std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
                           const std::string& outputs_dir, int crop_mode, int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
                                         int blocks = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0,
-                                        const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string()) {
+                                        const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string(), float wide = 0.f) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern);
+  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern, wide);
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
@@ -389,6 +409,18 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
                                                          std::string allowlist, std::string blocklist, std::string pattern) {
   return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
                                 blocks ? 1 : -1, mixed_batches ? 1 : -1, allowlist, blocklist, 0, nullptr, 0, pattern);
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool /*rectify*/, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, Wide wide) {
+  if (!(wide.max_aspect >= 2.f && wide.max_aspect <= 64.f)) {   // (before an engine is opened; 0 would read as "off")
+    g_call_error = "wide: max_aspect must be a finite value in [2, 64]";
+    std::cerr << "tuatara: " << g_call_error << std::endl;
+    return {};
+  }
+  return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, TTR_CROP_RECTIFIED, orient, orient_page ? 1 : 0, lines ? 1 : -1,
+                               chars ? 1 : -1, blocks ? 1 : -1, allowlist, blocklist, 0, nullptr, 0, std::string(), wide.max_aspect);
 }
 
 std::string last_call_error() { return g_call_error; }

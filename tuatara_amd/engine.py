@@ -225,6 +225,21 @@ SYMBOLS = [
     ("ttr_comm_allgather_host", _I, [_VP, _VP, C.c_size_t, _VP]),
     ("ttr_gather_layout", _I, [_PI, _I, _I, C.POINTER(C.c_int), _PI, C.POINTER(C.c_int64)]),
     ("ttr_pages_to_data_dev_sharded", _I, [_VP, _VP, _I, _I, _I, C.POINTER(_VP)]),
+    ("ttr_engine_set_wide", _I, [_VP, _F]),
+    ("ttr_engine_wide", _F, [_VP]),
+    ("ttr_result_piece_first", _PI, [_VP]),
+    ("ttr_result_piece_ids", _PI, [_VP]),
+    ("ttr_result_piece_probs", _PF, [_VP]),
+    ("ttr_result_piece_confs", _PF, [_VP]),
+    ("ttr_result_piece_quads", _PF, [_VP]),
+    ("ttr_result_piece_cuts", _PI, [_VP]),
+    ("ttr_results_gather_pieces", _I, [C.POINTER(_VP), _I, _PI, _PI, _PF, _PF, _PF, _PI]),
+    ("ttr_wide_plan", _I, [_PF, _F, C.POINTER(C.c_int64)]),
+    ("ttr_wide_profile", _I, [_PU8, _I, _I, _I, C.POINTER(C.c_int64), _I, C.POINTER(C.c_uint16)]),
+    ("ttr_wide_cuts_from_profile", _I, [C.POINTER(C.c_uint16), _I, _PI]),
+    ("ttr_wide_piece_coef", _I, [C.POINTER(C.c_int64), _I, _I, C.POINTER(C.c_int64)]),
+    ("ttr_wide_piece_quads", _I, [_PF, _PI, _I, _PF]),
+    ("ttr_wide_cuts", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _F, _I, _PI, _PI, C.POINTER(C.c_uint16), C.POINTER(C.c_int64)]),
 ]
 
 
@@ -659,6 +674,81 @@ def _add_conf(d: dict, conf, prob) -> dict:
     return d
 
 
+WIDE_DEFAULT = 8.0   # wide=True: the largest aspect a piece may have (DESIGN.md "Wide words": untuned on documents)
+
+
+def _wide_arg(wide) -> float:
+    """False / None / 0 -> 0.0 (off), True -> WIDE_DEFAULT, a number -> itself"""
+    if wide is None or wide is False:
+        return 0.0
+    if wide is True:
+        return WIDE_DEFAULT
+    return float(wide)
+
+
+def _i64(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _u16(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint16))
+
+
+def _lib_check(rc):
+    if rc < 0:
+        raise EngineError(load().ttr_last_error().decode("latin1"))
+    return rc
+
+
+def wide_plan(quad, max_aspect: float):
+    """The wide-word plan of one quad (ttr_wide_plan, no GPU; DESIGN.md "Wide words"): 8 floats tl, tr, br, bl -> (n, frame i64 [6]): n pieces (1 = not wide)
+    and the frame {X0f, Axf, Bxf, Y0f, Ayf, Byf} in 2^-16 px over 128 n columns x 32 rows."""
+    q = np.ascontiguousarray(quad, dtype=np.float32).reshape(8)
+    frame = np.zeros(6, np.int64)
+    n = _lib_check(load().ttr_wide_plan(_f(q), float(max_aspect), _i64(frame)))
+    return int(n), frame
+
+
+def wide_profile(image, frame, n: int) -> np.ndarray:
+    """The contrast profile of a frame on a host image u8 [H, W, 3] (ttr_wide_profile, no GPU) -> u16 [128 n]."""
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("image is [H, W, 3] u8")
+    f = np.ascontiguousarray(frame, dtype=np.int64).reshape(6)
+    q = np.zeros(128 * max(int(n), 1), np.uint16)
+    _lib_check(load().ttr_wide_profile(_u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _i64(f), int(n), _u16(q)))
+    return q
+
+
+def wide_cuts_from_profile(q, n: int) -> np.ndarray:
+    """The cuts of a profile u16 [128 n] (ttr_wide_cuts_from_profile, no GPU) -> i32 [17]: c_0 = 0 < ... < c_n = 128 n, -1 beyond n."""
+    q = np.ascontiguousarray(q, dtype=np.uint16).ravel()
+    if 1 <= int(n) <= 16 and len(q) < 128 * int(n):
+        raise ValueError("the profile holds 128 n columns")
+    cuts = np.full(17, -1, np.int32)
+    _lib_check(load().ttr_wide_cuts_from_profile(_u16(q), int(n), _i(cuts)))
+    return cuts
+
+
+def wide_piece_coef(frame, c0: int, c1: int) -> np.ndarray:
+    """The packer row of the piece over columns [c0, c1) of a frame (ttr_wide_piece_coef, no GPU) -> i64 [8] = {1, X0, Ax, Bx, Y0, Ay, By, 0}."""
+    f = np.ascontiguousarray(frame, dtype=np.int64).reshape(6)
+    row = np.zeros(8, np.int64)
+    _lib_check(load().ttr_wide_piece_coef(_i64(f), int(c0), int(c1), _i64(row)))
+    return row
+
+
+def wide_piece_quads(quad, cuts, n: int) -> np.ndarray:
+    """The n pieces' quads of a word's quad from its cuts (ttr_wide_piece_quads, no GPU) -> f32 [n, 8]."""
+    q = np.ascontiguousarray(quad, dtype=np.float32).reshape(8)
+    c = np.ascontiguousarray(cuts, dtype=np.int32).ravel()
+    if 1 <= int(n) <= 16 and len(c) < int(n) + 1:
+        raise ValueError("cuts holds n + 1 entries")
+    out = np.zeros((max(int(n), 1), 8), np.float32)
+    _lib_check(load().ttr_wide_piece_quads(_f(q), _i(c), int(n), _f(out)))
+    return out[:int(n)]
+
+
 def _quad_pairs(q8) -> list:
     """8 floats tl, tr, br, bl -> [[x, y], ...] (4 pairs)"""
     q = [float(v) for v in q8]
@@ -688,18 +778,23 @@ class PageResult(collections.abc.Sequence):
     position's character options in rank order; nbest(i, m) reads item i's m likeliest whole words; both None when alternatives are off.  Lexicon
     matching (Engine.set_lexicon(words, m); DESIGN.md "Lexicon matching"): `lex_idx` i32 [n, M] the M best entries of the word list by (logp descending,
     index ascending), -1 = none, and `lex_logp` f32 [n, M] their log-probabilities (-inf = none); dicts gain "lexicon", [(word, prob), ...] with
-    prob = exp(logp); both None when no lexicon is set."""
+    prob = exp(logp); both None when no lexicon is set.  Wide words (Engine.set_wide(a); DESIGN.md "Wide words"): `piece_first` i32 [n + 1] the items' offsets
+    into `piece_ids` i32 [P, 26], `piece_prob` f32 [P, 26], `piece_conf` f32 [P] and `piece_quad` f32 [P, 8] (an item that is not wide owns one piece, itself),
+    `piece_cuts` i32 [n, 17] each item's cuts in columns of its frame; dicts gain "pieces", a list of {"text", "conf", "quad"}; all None when wide is off."""
     __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
                  "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad",
                  "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode", "alt_ids", "alt_prob",
-                 "lex_idx", "lex_logp", "lex_words")
+                 "lex_idx", "lex_logp", "lex_words", "piece_first", "piece_ids", "piece_prob", "piece_conf", "piece_quad", "piece_cuts")
 
     def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0,
                  line=None, word=None, order=None, line_first=None, line_bbox=None,
                  char_first=None, char_quad=None, char_bbox=None, char_cuts=None, char_mode=None, char_profile=None, word_quad=None,
                  block=None, line_block=None, line_pos=None, block_order=None, block_first=None, block_bbox=None, block_mode=0,
-                 alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None):
+                 alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None,
+                 piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None):
+        self.piece_first, self.piece_ids, self.piece_prob = piece_first, piece_ids, piece_prob
+        self.piece_conf, self.piece_quad, self.piece_cuts = piece_conf, piece_quad, piece_cuts
         self.alt_ids, self.alt_prob = alt_ids, alt_prob
         self.lex_idx, self.lex_logp, self.lex_words = lex_idx, lex_logp, lex_words
         self.block, self.line_block, self.line_pos, self.block_order = block, line_block, line_pos, block_order
@@ -744,7 +839,16 @@ class PageResult(collections.abc.Sequence):
             d["alternatives"] = char_alternatives(self.alt_ids[j], self.alt_prob[j])
         if self.lex_idx is not None:
             d["lexicon"] = lexicon_matches(self.lex_words, self.lex_idx[j], self.lex_logp[j])
+        if self.piece_first is not None:
+            d["pieces"] = self.pieces(j)
         return d
+
+    def pieces(self, j: int) -> list:
+        """item j's pieces in order: [{"text", "conf", "quad"}, ...] (one, the item itself, when it is not wide)"""
+        if self.piece_first is None:
+            raise EngineError("pieces: the result carries no pieces (Engine.set_wide)")
+        a, b = int(self.piece_first[j]), int(self.piece_first[j + 1])
+        return [{"text": decode_ids(self.piece_ids[k]), "conf": float(self.piece_conf[k]), "quad": _quad_pairs(self.piece_quad[k])} for k in range(a, b)]
 
     def nbest(self, i: int, m: int) -> list:
         """item i's m likeliest readings [(text, score), ...] (nbest_from_alts); reading 0 is (text, conf)"""
@@ -840,6 +944,7 @@ class Engine:
         alts = int(overrides.pop("alts", 0) or 0)                                         # not a config field either: set_alternatives, below
         lexicon, lexicon_m = overrides.pop("lexicon", None), int(overrides.pop("lexicon_m", 1))   # nor these: set_lexicon, below
         pattern = overrides.pop("pattern", None)                                          # nor this: set_pattern, below
+        wide = _wide_arg(overrides.pop("wide", None))                                     # nor this: set_wide, below
         self._lex_words = []
         tuning = {k: overrides.pop(k) for k in list(overrides) if not hasattr(cfg, k)}     # not a config field: a tuning key (below)
         for k, v in overrides.items():
@@ -857,6 +962,35 @@ class Engine:
             self.set_lexicon(lexicon, lexicon_m)
         if pattern:
             self.set_pattern(pattern)
+        if wide:
+            self.set_wide(wide)
+
+    def set_wide(self, max_aspect=True):
+        """Read words wider than max_aspect times their height in pieces cut at ink gaps (ttr_engine_set_wide; DESIGN.md "Wide words"): 0 / False = off, True
+        = WIDE_DEFAULT (8.0), else a value in [2, 64].  Every page and region call's PageResult then carries piece_*, its dicts "pieces"; a wide item's text is
+        its pieces' texts joined, its conf their product; words that are not wide keep every bit.  Raises EngineError, and changes nothing, for another value,
+        between a stream_push and its flush, on an engine without crop_mode=1, and with orient, chars, alternatives, a lexicon, a pattern or a communicator."""
+        if self.lib.ttr_engine_set_wide(self.h, _wide_arg(max_aspect)) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def wide(self) -> float:
+        """max_aspect in force (0.0 = off)"""
+        return float(self.lib.ttr_engine_wide(self.h))
+
+    def wide_cuts(self, image, quads, max_aspect: float = WIDE_DEFAULT, table: bool = False):
+        """ttr_wide_cuts: wide_cut_kernel on a host image u8 [H, W, 3] and host quads f32 [nq, 8], whatever the engine's setting; table=True reads the page
+        through the device page table -> (n i32 [nq], cuts i32 [nq, 17], profiles u16 [nq, 2048], coef i64 [nq, 16, 8])."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise RuntimeError("Input array should have 3 dimensions")
+        q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+        nq = len(q)
+        n, cuts = np.zeros(max(nq, 1), np.int32), np.full((max(nq, 1), 17), -1, np.int32)
+        prof, coef = np.zeros((max(nq, 1), 2048), np.uint16), np.zeros((max(nq, 1), 16, 8), np.int64)
+        self._check(self.lib.ttr_wide_cuts(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _f(q), nq, float(max_aspect), int(bool(table)),
+                                           _i(n), _i(cuts), _u16(prof), _i64(coef)))
+        return n[:nq].copy(), cuts[:nq].copy(), prof[:nq].copy(), coef[:nq].copy()
 
     def set_lexicon(self, words=None, m: int = 1):
         """The word list every read word is scored against (ttr_engine_set_lexicon; DESIGN.md "Lexicon matching"): words of 1..25 characters out of the
@@ -1110,10 +1244,22 @@ class Engine:
             ai, ap = np.zeros((max(total, 1), 26, K), np.int32), np.zeros((max(total, 1), 26, K), np.float32)
             if self.lib.ttr_results_gather_alts(arr, n, _i(ai), _f(ap)) < 0:
                 raise EngineError("ttr_results_gather_alts: the results differ in K")
-        out, k, kl, kc, kbl, kb = [], 0, 0, 0, 0, 0
+        ptot = self.lib.ttr_results_gather_pieces(arr, n, None, None, None, None, None, None) if total else 0   # wide words: every page's pieces, one call
+        if ptot < 0:
+            raise EngineError("ttr_results_gather_pieces: bad arguments")
+        if ptot:
+            pf, pi, pp = np.zeros(total + n + 1, np.int32), np.zeros((ptot, 26), np.int32), np.zeros((ptot, 26), np.float32)
+            pc, pq, pcu = np.zeros(ptot, np.float32), np.zeros((ptot, 8), np.float32), np.full((max(total, 1), 17), -1, np.int32)
+            self.lib.ttr_results_gather_pieces(arr, n, _i(pf), _i(pi), _f(pp), _f(pc), _f(pq), _i(pcu))
+        out, k, kl, kc, kbl, kb, kp = [], 0, 0, 0, 0, 0, 0
         for i in range(n):
             c = int(counts[i])
             lex = {}
+            if ptot and self.lib.ttr_result_piece_first(arr[i]):
+                first = pf[k + i:k + i + c + 1]
+                m = int(first[-1])
+                lex.update(piece_first=first, piece_ids=pi[kp:kp + m], piece_prob=pp[kp:kp + m], piece_conf=pc[kp:kp + m], piece_quad=pq[kp:kp + m], piece_cuts=pcu[k:k + c])
+                kp += m
             M = int(self.lib.ttr_result_lex_m(arr[i]))
             if M:                               # the page's matches (the setter refuses while batches stream: the word list is the one in force)
                 li, ll = self.lib.ttr_result_lex_idx_all(arr[i]), self.lib.ttr_result_lex_logp_all(arr[i])
@@ -1269,6 +1415,10 @@ class Engine:
                               "conf": float(page.conf[k]), "prob": page.prob[k].tolist(), "set": int(sets[k]), "region": where[p][k]})
                 if page.alt_ids is not None:        # character alternatives: each region under its own set
                     items[-1].update({"alt_ids": page.alt_ids[k], "alt_prob": page.alt_prob[k], "alternatives": char_alternatives(page.alt_ids[k], page.alt_prob[k])})
+                if page.piece_first is not None:    # wide words: each region's pieces under its own set
+                    a, b = int(page.piece_first[k]), int(page.piece_first[k + 1])
+                    items[-1].update({"pieces": page.pieces(k), "piece_ids": page.piece_ids[a:b], "piece_prob": page.piece_prob[a:b], "piece_conf": page.piece_conf[a:b],
+                                      "piece_quad": page.piece_quad[a:b], "piece_cuts": page.piece_cuts[k]})
                 if page.lex_idx is not None:        # lexicon matching: each region under its own set
                     items[-1].update({"lex_idx": page.lex_idx[k], "lex_logp": page.lex_logp[k], "lexicon": lexicon_matches(page.lex_words, page.lex_idx[k], page.lex_logp[k])})
             out.append(items)
