@@ -31,8 +31,9 @@ static RRect stage_crop_rect(const float* r5, float ratio, int h, int w, int* re
   return b;
 }
 
-// ttr_pack_crops_oriented's rule for one rect on an h x w page: the clamped crop rectangle rc[0..4), the packer's coefficients coef8 and the turned quad
-static void oriented_crop(const float* r5, float ratio, int h, int w, int crop_mode, int turn, int* rc, int64_t* coef8, float* quad8) {
+// the crop calls' rule for one rect on an h x w page: the clamped crop rectangle rc[0..4), the packer's coefficients coef8 and the turned quad; returns the
+// rect in image pixels.  BOUNDING at turn 0 is ttr_pack_crops's crop (rc alone: the plain packer reads no coefficients), RECTIFIED at turn 0 ttr_pack_crops_rectified's
+static RRect oriented_crop(const float* r5, float ratio, int h, int w, int crop_mode, int turn, int* rc, int64_t* coef8, float* quad8) {
   const RRect b = stage_crop_rect(r5, ratio, h, w, rc);
   Pt2f q[4], qt[4]; double cf[6]; int64_t fx[6];
   const int kind = deskew_quad(b, q, cf);                       // Q: the deskewed quad (crop_mode 1) ...
@@ -47,6 +48,7 @@ static void oriented_crop(const float* r5, float ratio, int h, int w, int crop_m
   for (int k = 0; k < 6; ++k) coef8[1 + k] = fx[k];
   for (int k = 0; k < 4; ++k) qt[k] = q[(k + turn) & 3];
   if (quad8) for (int k = 0; k < 4; ++k) { quad8[2 * k] = qt[k].x; quad8[2 * k + 1] = qt[k].y; }
+  return b;
 }
 
 // the stage calls of the table kernels: n host images, each with its own row stride kept, one after another in staging_img at offsets rounded up to 256
@@ -70,6 +72,75 @@ static std::vector<Engine::Page> stage_host_pages(Engine& E, const uint8_t* cons
     TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.as<uint8_t>() + off[i], (size_t)pages[i].stride, images[i], (size_t)pages[i].stride, (size_t)ws[i] * 3, hs[i], hipMemcpyHostToDevice, E.stream));
   E.upload_page_table(pages, 0);
   return pages;
+}
+
+// ---- the shared bodies of the host-staged stage calls: all of their work goes onto E.stream, and each ends with a wait (the caller's arrays and the calls'
+// own host vectors are pageable: they live until that wait)
+
+// the image arguments of the calls that take one host image with row_stride 0 = packed rows (tuatara.cpp:344-347's message)
+static void check_host_image(const uint8_t* img, int h, int w, int row_stride) {
+  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
+}
+
+// the decode calls, host logits [n][26][95]: E.logits and the RecOut block made large enough, the logits' upload enqueued
+static Engine::RecOut stage_logits(Engine& E, const float* logits, int n) {
+  const size_t bytes = (size_t)n * Engine::kLogitWords * 4;
+  E.logits.ensure(bytes);
+  const Engine::RecOut o = E.rec_out(n);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, bytes, hipMemcpyHostToDevice, E.stream));
+  return o;
+}
+
+// ... and their end: each RecOut field the caller gave a place for, then the wait (known: no range guard here or in the crop calls, unlike fetch_logits - none of
+// their kernels watches a range word)
+static void fetch_decoded(Engine& E, const Engine::RecOut& o, int n, int32_t* ids, float* probs, float* conf) {
+  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, o.ids, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (probs) TTR_HIP_CHECK(hipMemcpyAsync(probs, o.prob, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  if (conf) TTR_HIP_CHECK(hipMemcpyAsync(conf, o.conf, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+}
+
+// the crop calls: n crops under the finished host rects [n][5] and coef [n][8] (the rect packer alone reads and uploads coef), cut from one host image, uploaded
+// here with its rows image->row_stride bytes apart, or - image == nullptr - from the pages of slot 0's table as stage_host_pages left them; crops_out [n][32][128][3]
+enum CropPacker { kPackPlain, kPackRect };
+static void pack_stage(Engine& E, const Engine::HostImage* image, const std::vector<int>& rects, const std::vector<int64_t>& coef, CropPacker packer, uint8_t* crops_out) {
+  const int n = (int)(rects.size() / 5);
+  const bool rect = packer == kPackRect;
+  if (image) E.staging_img.ensure((size_t)image->h * image->w * 3);
+  E.rects_dev.ensure(rects.size() * 4);
+  if (rect) E.coef_dev.ensure(coef.size() * 8);
+  E.crops.ensure((size_t)n * Engine::kCropBytes);
+  if (image) TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)image->w * 3, image->data, (size_t)image->row_stride, (size_t)image->w * 3, image->h, hipMemcpyHostToDevice, E.stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
+  if (rect) TTR_HIP_CHECK(hipMemcpyAsync(E.coef_dev.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice, E.stream));
+  const uint8_t* src = E.staging_img.as<uint8_t>();
+  const PageRow* table = E.page_table[0].as<PageRow>();
+  if (image && rect) launch_pack_crops_rect(src, 0, image->w * 3, image->h, image->w, E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
+  else if (image) launch_pack_crops(src, 0, image->w * 3, E.rects_dev.as<int>(), E.crops.as<uint8_t>(), n, E.stream);
+  else if (rect) launch_pack_crops_rect_pages(table, E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
+  else launch_pack_crops_pages(table, E.rects_dev.as<int>(), E.crops.as<uint8_t>(), n, E.stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * Engine::kCropBytes, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+}
+
+// the recogniser calls, host crops [n][32][128][3]: the buffers of a forward made large enough (the AR logits' only where they are asked for), the crops' upload enqueued
+static Engine::RecOut stage_crops(Engine& E, const uint8_t* crops, int n, bool with_ar) {
+  E.crops.ensure((size_t)n * Engine::kCropBytes);
+  E.logits.ensure((size_t)n * Engine::kLogitWords * 4);
+  const Engine::RecOut o = E.rec_out(n);
+  if (with_ar) E.ar_logits.ensure((size_t)n * Engine::kLogitWords * 4);
+  TTR_HIP_CHECK(hipMemcpyAsync(E.crops.p, crops, (size_t)n * Engine::kCropBytes, hipMemcpyHostToDevice, E.stream));
+  return o;
+}
+
+// ... and their end: the logits, the AR logits and the ids where there is a place for them, then the range guard's word of the forward, the wait and its verdict under the call's name
+static void fetch_logits(Engine& E, const Engine::RecOut& o, int n, float* logits, float* ar_logits, int32_t* ids, const char* what) {
+  TTR_HIP_CHECK(hipMemcpyAsync(logits, E.logits.p, (size_t)n * Engine::kLogitWords * 4, hipMemcpyDeviceToHost, E.stream));
+  if (ar_logits) TTR_HIP_CHECK(hipMemcpyAsync(ar_logits, E.ar_logits.p, (size_t)n * Engine::kLogitWords * 4, hipMemcpyDeviceToHost, E.stream));
+  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, o.ids, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
+  E.range_fetch(Engine::kRangeStage);
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  E.range_verify(Engine::kRangeStage, what);
 }
 
 extern "C" {
@@ -625,18 +696,13 @@ int ttr_pack_crops(ttr_engine* e, const uint8_t* img, int h, int w, int row_stri
   E.refuse_while_streaming("ttr_pack_crops");
   if (n <= 0) return 0;
   std::vector<int> rects((size_t)n * 5, 0);
+  std::vector<int64_t> coef((size_t)n * 8, 0);
   for (int i = 0; i < n; ++i) {
-    RRect b = stage_crop_rect(rects5 + 5 * i, ratio, h, w, &rects[5 * i]);
-    if (boxes_out) { boxes_out[5 * i] = b.cx; boxes_out[5 * i + 1] = b.cy; boxes_out[5 * i + 2] = b.w; boxes_out[5 * i + 3] = b.h; boxes_out[5 * i + 4] = b.angle; }
+    const RRect b = oriented_crop(rects5 + 5 * (size_t)i, ratio, h, w, TTR_CROP_BOUNDING, 0, &rects[5 * (size_t)i], &coef[8 * (size_t)i], nullptr);
+    if (boxes_out) { float* o = boxes_out + 5 * (size_t)i; o[0] = b.cx; o[1] = b.cy; o[2] = b.w; o[3] = b.h; o[4] = b.angle; }
   }
-  E.staging_img.ensure((size_t)h * w * 3);
-  E.rects_dev.ensure(rects.size() * 4);
-  E.crops.ensure((size_t)n * 32 * 128 * 3);
-  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
-  TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
-  launch_pack_crops(E.staging_img.as<uint8_t>(), 0, w * 3, E.rects_dev.as<int>(), E.crops.as<uint8_t>(), n, E.stream);
-  TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  const Engine::HostImage image{img, h, w, row_stride};   // (known: no image check here, and row_stride is taken as given - 0 does not mean packed rows, as it does for ttr_pack_regions)
+  pack_stage(E, &image, rects, coef, kPackPlain, crops_out);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -650,24 +716,10 @@ int ttr_pack_crops_rectified(ttr_engine* e, const uint8_t* img, int h, int w, in
   if (n <= 0) return 0;
   std::vector<int> rects((size_t)n * 5, 0);
   std::vector<int64_t> coef((size_t)n * 8, 0);
-  for (int i = 0; i < n; ++i) {
-    const RRect b = stage_crop_rect(rects5 + 5 * i, ratio, h, w, &rects[5 * i]);
-    Pt2f q[4]; double cf[6]; int64_t fx[6];
-    coef[8 * i] = deskew_quad(b, q, cf);
-    deskew_fixed(cf, fx);
-    for (int k = 0; k < 6; ++k) coef[8 * i + 1 + k] = fx[k];
-    if (quads_out) for (int k = 0; k < 4; ++k) { quads_out[8 * i + 2 * k] = q[k].x; quads_out[8 * i + 2 * k + 1] = q[k].y; }
-  }
-  E.staging_img.ensure((size_t)h * w * 3);
-  E.rects_dev.ensure(rects.size() * 4);
-  E.coef_dev.ensure(coef.size() * 8);
-  E.crops.ensure((size_t)n * 32 * 128 * 3);
-  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
-  TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
-  TTR_HIP_CHECK(hipMemcpyAsync(E.coef_dev.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice, E.stream));
-  launch_pack_crops_rect(E.staging_img.as<uint8_t>(), 0, w * 3, h, w, E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
-  TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  for (int i = 0; i < n; ++i)
+    oriented_crop(rects5 + 5 * (size_t)i, ratio, h, w, TTR_CROP_RECTIFIED, 0, &rects[5 * (size_t)i], &coef[8 * (size_t)i], quads_out ? quads_out + 8 * (size_t)i : nullptr);
+  const Engine::HostImage image{img, h, w, row_stride};   // (known: as ttr_pack_crops - no image check, row_stride as given)
+  pack_stage(E, &image, rects, coef, kPackRect, crops_out);   // (always the rect packer: a rect at a multiple of 90 degrees is its kind-0 crop)
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -685,20 +737,8 @@ int ttr_pack_crops_oriented(ttr_engine* e, const uint8_t* img, int h, int w, int
   std::vector<int64_t> coef((size_t)n * 8, 0);
   for (int i = 0; i < n; ++i)
     oriented_crop(rects5 + 5 * (size_t)i, ratio, h, w, crop_mode, turn, &rects[5 * (size_t)i], &coef[8 * (size_t)i], quads_out ? quads_out + 8 * (size_t)i : nullptr);
-  E.staging_img.ensure((size_t)h * w * 3);
-  E.rects_dev.ensure(rects.size() * 4);
-  E.coef_dev.ensure(coef.size() * 8);
-  E.crops.ensure((size_t)n * 32 * 128 * 3);
-  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
-  TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
-  if (turn == 0 && crop_mode == TTR_CROP_BOUNDING) {              // ttr_pack_crops's crop
-    launch_pack_crops(E.staging_img.as<uint8_t>(), 0, w * 3, E.rects_dev.as<int>(), E.crops.as<uint8_t>(), n, E.stream);
-  } else {
-    TTR_HIP_CHECK(hipMemcpyAsync(E.coef_dev.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice, E.stream));
-    launch_pack_crops_rect(E.staging_img.as<uint8_t>(), 0, w * 3, h, w, E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
-  }
-  TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  const Engine::HostImage image{img, h, w, row_stride};   // (known: as ttr_pack_crops - no image check, row_stride as given)
+  pack_stage(E, &image, rects, coef, turn == 0 && crop_mode == TTR_CROP_BOUNDING ? kPackPlain : kPackRect, crops_out);   // (plain: ttr_pack_crops's crop, by its packer)
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -744,18 +784,7 @@ int ttr_pack_crops_batch(ttr_engine* e, const uint8_t* const* images, const int*
     oriented_crop(rects5 + 5 * (size_t)i, P.g.ratio, P.h, P.w, crop_mode, turn, &rects[5 * (size_t)i], &coef[8 * (size_t)i], quads_out ? quads_out + 8 * (size_t)i : nullptr);
     rects[5 * (size_t)i + 4] = page_of[i];
   }
-  E.rects_dev.ensure(rects.size() * 4);
-  E.coef_dev.ensure(coef.size() * 8);
-  E.crops.ensure((size_t)n * 32 * 128 * 3);
-  TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
-  if (turn == 0 && crop_mode == TTR_CROP_BOUNDING) {
-    launch_pack_crops_pages(E.page_table[0].as<PageRow>(), E.rects_dev.as<int>(), E.crops.as<uint8_t>(), n, E.stream);
-  } else {
-    TTR_HIP_CHECK(hipMemcpyAsync(E.coef_dev.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice, E.stream));
-    launch_pack_crops_rect_pages(E.page_table[0].as<PageRow>(), E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
-  }
-  TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));   // (rects and coef are pageable host vectors: they live until here)
+  pack_stage(E, nullptr, rects, coef, turn == 0 && crop_mode == TTR_CROP_BOUNDING ? kPackPlain : kPackRect, crops_out);   // (the pages are staged: stage_host_pages checked each image and stride)
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -766,18 +795,10 @@ int ttr_parseq_logits(ttr_engine* e, const uint8_t* crops, int n, float* logits,
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_parseq_logits");
   if (n <= 0) return 0;
-  E.crops.ensure((size_t)n * 32 * 128 * 3);
-  E.logits.ensure((size_t)n * 26 * 95 * 4);
-  const Engine::RecOut o = E.rec_out(n);
-  if (ar_logits) E.ar_logits.ensure((size_t)n * 26 * 95 * 4);
-  TTR_HIP_CHECK(hipMemcpyAsync(E.crops.p, crops, (size_t)n * 32 * 128 * 3, hipMemcpyHostToDevice, E.stream));
+  // (not ttr_parseq_logits_patterns with nothing given: where the engine has a pattern that call compiles and stages a table of its own, this one reads under pattern_own)
+  const Engine::RecOut o = stage_crops(E, crops, n, ar_logits != nullptr);
   E.parseq_forward(E.crops.as<uint8_t>(), n, E.logits.as<float>(), ar_logits ? E.ar_logits.as<float>() : nullptr, o.ids, o.prob, o.conf);
-  TTR_HIP_CHECK(hipMemcpyAsync(logits, E.logits.p, (size_t)n * 26 * 95 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (ar_logits) TTR_HIP_CHECK(hipMemcpyAsync(ar_logits, E.ar_logits.p, (size_t)n * 26 * 95 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, E.ids_dev.p, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
-  E.range_fetch(Engine::kRangeStage);
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
-  E.range_verify(Engine::kRangeStage, "ttr_parseq_logits");
+  fetch_logits(E, o, n, logits, ar_logits, ids, "ttr_parseq_logits");
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -789,14 +810,9 @@ int ttr_logits_confidence(ttr_engine* e, const float* logits, int n, int32_t* id
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_logits_confidence");
   if (n == 0) return 0;
-  E.logits.ensure((size_t)n * 26 * 95 * 4);
-  const Engine::RecOut o = E.rec_out(n);
-  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  const Engine::RecOut o = stage_logits(E, logits, n);
   launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream);
-  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, o.ids, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (probs) TTR_HIP_CHECK(hipMemcpyAsync(probs, o.prob, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (conf) TTR_HIP_CHECK(hipMemcpyAsync(conf, o.conf, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  fetch_decoded(E, o, n, ids, probs, conf);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -809,16 +825,9 @@ int ttr_logits_confidence_masked(ttr_engine* e, const float* logits, int n, cons
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_logits_confidence_masked");
   if (n == 0) return 0;
-  ClassMask cm{};
-  for (int i = 0; i < 3; ++i) cm.blocked[i] = ~mask[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);   // 95 classes
-  E.logits.ensure((size_t)n * 26 * 95 * 4);
-  const Engine::RecOut o = E.rec_out(n);
-  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
-  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, cm);
-  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, o.ids, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (probs) TTR_HIP_CHECK(hipMemcpyAsync(probs, o.prob, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (conf) TTR_HIP_CHECK(hipMemcpyAsync(conf, o.conf, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  const Engine::RecOut o = stage_logits(E, logits, n);
+  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, ClassMask::from_allowed(mask));
+  fetch_decoded(E, o, n, ids, probs, conf);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -878,7 +887,7 @@ int ttr_image_regions_to_data_p(ttr_engine* e, const uint8_t* img, int h, int w,
                                 int n_sets, const char* const* patterns, int n_patterns, const int32_t* pattern_of, ttr_result** out) {
   TTR_GUARD_BEGIN
   if (!e || !out) throw std::runtime_error("null argument");
-  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
+  check_host_image(img, h, w, row_stride);
   Engine& E = *e->e;
   EngineScope lk(E);
   E.refuse_while_streaming("regions");                    // (before the staging buffer, which streamed batches may still read, is touched)
@@ -899,7 +908,7 @@ const int32_t* ttr_result_sets(const ttr_result* r) { return r && !r->r.set.empt
 int ttr_pack_regions(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const float* quads, int n, uint8_t* crops_out) {
   TTR_GUARD_BEGIN
   if (!e || n < 0 || (n > 0 && (!quads || !crops_out))) throw std::runtime_error("null argument");
-  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
+  check_host_image(img, h, w, row_stride);
   Engine& E = *e->e;
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_pack_regions");
@@ -912,16 +921,8 @@ int ttr_pack_regions(ttr_engine* e, const uint8_t* img, int h, int w, int row_st
     coef[8 * (size_t)i] = 1;
     region_coef(quads + 8 * (size_t)i, &coef[8 * (size_t)i + 1]);
   }
-  E.staging_img.ensure((size_t)h * w * 3);
-  E.rects_dev.ensure(rects.size() * 4);
-  E.coef_dev.ensure(coef.size() * 8);
-  E.crops.ensure((size_t)n * 32 * 128 * 3);
-  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
-  TTR_HIP_CHECK(hipMemcpyAsync(E.rects_dev.p, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, E.stream));
-  TTR_HIP_CHECK(hipMemcpyAsync(E.coef_dev.p, coef.data(), coef.size() * 8, hipMemcpyHostToDevice, E.stream));
-  launch_pack_crops_rect(E.staging_img.as<uint8_t>(), 0, w * 3, h, w, E.rects_dev.as<int>(), E.coef_dev.as<int64_t>(), E.crops.as<uint8_t>(), n, E.stream);
-  TTR_HIP_CHECK(hipMemcpyAsync(crops_out, E.crops.p, (size_t)n * 32 * 128 * 3, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  const Engine::HostImage image{img, h, w, row_stride ? row_stride : w * 3};   // (known: the one crop call that checks its image, and whose row_stride 0 means packed rows)
+  pack_stage(E, &image, rects, coef, kPackRect, crops_out);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -945,11 +946,7 @@ int ttr_parseq_logits_patterns(ttr_engine* e, const uint8_t* crops, int n, const
   Engine::PatRows pats;
   const bool with_pats = E.resolve_row_patterns(what, patterns, n_patterns, pattern_of, n, table, one, pats);
   if (n == 0) return 0;
-  E.crops.ensure((size_t)n * 32 * 128 * 3);
-  E.logits.ensure((size_t)n * 26 * 95 * 4);
-  const Engine::RecOut o = E.rec_out(n);
-  if (ar_logits) E.ar_logits.ensure((size_t)n * 26 * 95 * 4);
-  TTR_HIP_CHECK(hipMemcpyAsync(E.crops.p, crops, (size_t)n * 32 * 128 * 3, hipMemcpyHostToDevice, E.stream));
+  const Engine::RecOut o = stage_crops(E, crops, n, ar_logits != nullptr);
   {
     struct SetScope { ClassMask& c; ClassMask old; ~SetScope() { c = old; } } set_scope{E.charset, E.charset};   // (one shared mask: by value, the engine's own path)
     E.charset = one;
@@ -958,12 +955,7 @@ int ttr_parseq_logits_patterns(ttr_engine* e, const uint8_t* crops, int n, const
     E.parseq_forward(E.crops.as<uint8_t>(), n, E.logits.as<float>(), ar_logits ? E.ar_logits.as<float>() : nullptr, o.ids, o.prob, o.conf, E.stage_row_masks(table, 0), nullptr, nullptr,
                      nullptr, with_pats ? &pd : nullptr);
   }
-  TTR_HIP_CHECK(hipMemcpyAsync(logits, E.logits.p, (size_t)n * 26 * 95 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (ar_logits) TTR_HIP_CHECK(hipMemcpyAsync(ar_logits, E.ar_logits.p, (size_t)n * 26 * 95 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, E.ids_dev.p, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
-  E.range_fetch(Engine::kRangeStage);
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
-  E.range_verify(Engine::kRangeStage, what);
+  fetch_logits(E, o, n, logits, ar_logits, ids, what);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -979,14 +971,9 @@ int ttr_logits_confidence_sets(ttr_engine* e, const float* logits, int n, const 
   ClassMask one{};
   E.resolve_row_masks("ttr_logits_confidence_sets", set_of, n, sets, n_sets, table, one);
   if (n == 0) return 0;
-  E.logits.ensure((size_t)n * 26 * 95 * 4);
-  const Engine::RecOut o = E.rec_out(n);
-  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  const Engine::RecOut o = stage_logits(E, logits, n);
   launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, one, E.stage_row_masks(table, 0));
-  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, o.ids, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (probs) TTR_HIP_CHECK(hipMemcpyAsync(probs, o.prob, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (conf) TTR_HIP_CHECK(hipMemcpyAsync(conf, o.conf, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  fetch_decoded(E, o, n, ids, probs, conf);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -1007,8 +994,7 @@ int ttr_engine_set_charset(ttr_engine* e, const char* allow, const char* deny) {
   E.refuse_while_streaming("ttr_engine_set_charset");
   uint32_t m[3];
   charset_mask(E.tok, allow, deny, m);            // (throws before anything changes: a failed call leaves the previous set in place)
-  ClassMask cm{};
-  for (int i = 0; i < 3; ++i) cm.blocked[i] = ~m[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);
+  const ClassMask cm = ClassMask::from_allowed(m);
   if (cm.restricts() && E.prec == kBF16)
     throw std::runtime_error("ttr_engine_set_charset: a character set needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which take no class mask");
   if (!E.pattern_src.empty()) {                  // the stored pattern under the new set (DESIGN.md "Patterns"): compiled first - a set that empties its language leaves both as they were
@@ -1098,21 +1084,16 @@ int ttr_logits_decode_patterns(ttr_engine* e, const float* logits, int n, const 
     pats.start_of.resize((size_t)n);
     for (int i = 0; i < n; ++i) {
       const uint32_t* b = table.empty() ? one.blocked : &table[4 * (size_t)i];
-      for (int j = 0; j < 3; ++j) m[j] = ~b[j] & (j == 2 ? 0x7fffffffu : 0xffffffffu);
+      ClassMask{{b[0], b[1], b[2]}}.allowed(m);
       const std::vector<uint32_t> key(m, m + 3);
       auto it = start.find(key);
       if (it == start.end()) it = start.emplace(key, pats.t.add(pattern_none(m), what)).first;
       pats.start_of[(size_t)i] = it->second;
     }
   }
-  E.logits.ensure((size_t)n * 26 * 95 * 4);
-  const Engine::RecOut o = E.rec_out(n);
-  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  const Engine::RecOut o = stage_logits(E, logits, n);
   launch_decode_pat(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, E.stage_row_patterns(pats, 0));
-  if (ids) TTR_HIP_CHECK(hipMemcpyAsync(ids, o.ids, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (probs) TTR_HIP_CHECK(hipMemcpyAsync(probs, o.prob, (size_t)n * 26 * 4, hipMemcpyDeviceToHost, E.stream));
-  if (conf) TTR_HIP_CHECK(hipMemcpyAsync(conf, o.conf, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  fetch_decoded(E, o, n, ids, probs, conf);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -1121,7 +1102,7 @@ int ttr_engine_get_charset(const ttr_engine* e, uint32_t mask[3]) {
   TTR_GUARD_BEGIN
   if (!e || !mask) throw std::runtime_error("null argument");
   const Engine& E = *e->e;
-  for (int i = 0; i < 3; ++i) mask[i] = ~E.charset.blocked[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);
+  E.charset.allowed(mask);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -1254,7 +1235,7 @@ int ttr_wide_cuts(ttr_engine* e, const uint8_t* img, int h, int w, int row_strid
                   int32_t* cuts, uint16_t* profiles, int64_t* coef) {
   TTR_GUARD_BEGIN
   if (!e || nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
-  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
+  check_host_image(img, h, w, row_stride);
   Engine& E = *e->e;
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_wide_cuts");
@@ -1305,16 +1286,14 @@ int ttr_logits_alternatives(ttr_engine* e, const float* logits, int n, int k, co
   ClassMask one = E.charset;
   if (sets) E.resolve_row_masks("ttr_logits_alternatives", set_of, n, sets, n_sets, table, one);
   if (n == 0) return 0;
-  E.logits.ensure((size_t)n * 26 * 95 * 4);
-  const Engine::RecOut o = E.rec_out(n);
   const Engine::AltOut a = E.alts_out(n, k);
-  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  const Engine::RecOut o = stage_logits(E, logits, n);
   const RowMask* rows = E.stage_row_masks(table, 0);
   launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, one, rows);
   launch_decode_alts(E.logits.as<float>(), n, o.ids, o.prob, k, a.ids, a.prob, E.stream, one, rows);
   if (alt_ids) TTR_HIP_CHECK(hipMemcpyAsync(alt_ids, a.ids, (size_t)n * 26 * k * 4, hipMemcpyDeviceToHost, E.stream));
   if (alt_probs) TTR_HIP_CHECK(hipMemcpyAsync(alt_probs, a.prob, (size_t)n * 26 * k * 4, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));   // (the side block alone comes back: no RecOut field, so no fetch_decoded)
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -1411,16 +1390,14 @@ int ttr_logits_lexicon(ttr_engine* e, const float* logits, int n, const uint32_t
   if (sets) E.resolve_row_masks("ttr_logits_lexicon", set_of, n, sets, n_sets, table, one);
   if (n == 0) return 0;
   const int M = E.lex_m;
-  E.logits.ensure((size_t)n * 26 * 95 * 4);
-  const Engine::RecOut o = E.rec_out(n);
   const Engine::LexOut l = E.lex_out(n, M);
-  TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, (size_t)n * 26 * 95 * 4, hipMemcpyHostToDevice, E.stream));
+  const Engine::RecOut o = stage_logits(E, logits, n);
   const RowMask* rows = E.stage_row_masks(table, 0);
   launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, one, rows);
   launch_lexicon(E.logits.as<float>(), n, o.ids, o.prob, E.lex_records.p, E.lex_v, M, l.idx, l.logp, l.part_idx, l.part_logp, E.stream, one, rows);
   if (idx) TTR_HIP_CHECK(hipMemcpyAsync(idx, l.idx, (size_t)n * M * 4, hipMemcpyDeviceToHost, E.stream));
   if (logp) TTR_HIP_CHECK(hipMemcpyAsync(logp, l.logp, (size_t)n * M * 4, hipMemcpyDeviceToHost, E.stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));   // (as ttr_logits_alternatives: the side block alone)
   return 0;
   TTR_GUARD_END(-1)
 }

@@ -22,6 +22,10 @@ struct ClassMask {
   uint32_t blocked[3];
   __host__ __device__ __forceinline__ bool allows(int c) const { return (unsigned)c >= 96u || !((blocked[c >> 5] >> (c & 31)) & 1u); }
   __host__ __device__ __forceinline__ bool restricts() const { return (blocked[0] | blocked[1] | blocked[2]) != 0u; }
+  // host side: to and from the form the ABI passes (charset_mask's) - bit c & 31 of m[c >> 5] set = class c may be chosen
+  static constexpr uint32_t kLastWord = 0x7fffffffu;   // 95 classes: the third word holds 31 of them, its bit 31 is never set in either form
+  static ClassMask from_allowed(const uint32_t m[3]) { return ClassMask{{~m[0], ~m[1], ~m[2] & kLastWord}}; }
+  void allowed(uint32_t m[3]) const { m[0] = ~blocked[0]; m[1] = ~blocked[1]; m[2] = ~blocked[2] & kLastWord; }
 };
 
 // Per-row class masks (DESIGN.md "Regions and per-row character sets"): a device table of one mask per recogniser row, 16 bytes a row - {blocked[0],

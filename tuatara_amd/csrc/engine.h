@@ -679,6 +679,7 @@ struct Engine {
   struct RecOut { int* ids; float* prob; float* conf; };
   static constexpr int kRecWords = 26 + 26 + 1;   // 4-byte words per crop
   static constexpr int kLogitWords = 26 * 95;     // 4-byte words of a crop's logits
+  static constexpr int kCropBytes = 32 * 128 * 3; // bytes of a crop: 32 x 128 RGB
   RecOut rec_out(int rows) { return rec_block(ids_dev, rows); }
   static RecOut rec_block(DevBuf& d, int rows) {
     d.ensure((size_t)std::max(rows, 1) * kRecWords * 4);

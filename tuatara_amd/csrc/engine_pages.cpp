@@ -989,7 +989,7 @@ void Engine::resolve_row_masks(const char* what, const int32_t* set_of, int n, c
   std::vector<ClassMask> cms((size_t)n_sets);
   for (int s = 0; s < n_sets; ++s) {
     if (!(sets[3 * (size_t)s] & 1u)) throw std::runtime_error(w + ": set " + std::to_string(s) + ": bit 0 (the end of the text) must be set");
-    for (int i = 0; i < 3; ++i) cms[s].blocked[i] = ~sets[3 * (size_t)s + i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);   // 95 classes
+    cms[s] = ClassMask::from_allowed(sets + 3 * (size_t)s);
   }
   table.assign((size_t)n * 4, 0u);
   one = charset;
@@ -1021,8 +1021,8 @@ void Engine::set_engine_pattern(const char* src_, const ClassMask& cm) {
   if (!src_ || !*src_) { pattern_src.clear(); pattern = Pattern(); pattern_own = PatDev{}; return; }
   const std::string src(src_);   // (a copy: the caller may pass pattern_src itself)
   uint32_t m[3];
-  for (int i = 0; i < 3; ++i) m[i] = ~cm.blocked[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);
-  Pattern p = pattern_compile(tok, src.c_str(), m);   // (throws before anything changes)
+  cm.allowed(m);
+  Pattern p =pattern_compile(tok, src.c_str(), m);   // (throws before anything changes)
   const size_t db = p.delta.size() * sizeof(uint16_t), mb = p.mind.size();
   pattern_dev.ensure(db + mb);
   TTR_HIP_CHECK(hipMemcpyAsync(pattern_dev.p, p.delta.data(), db, hipMemcpyHostToDevice, stream));
@@ -1057,7 +1057,7 @@ bool Engine::resolve_row_patterns(const char* what, const char* const* patterns,
   for (int i = 0; i < n; ++i) {
     Key key{};
     const uint32_t* b = table.empty() ? one.blocked : &table[4 * (size_t)i];
-    for (int j = 0; j < 3; ++j) key.m[j] = ~b[j] & (j == 2 ? 0x7fffffffu : 0xffffffffu);
+    ClassMask{{b[0], b[1], b[2]}}.allowed(key.m);
     const int k = pattern_of ? pattern_of[i] : -1;
     const char* src = k >= 0 ? patterns[k] : (pattern_src.empty() ? nullptr : pattern_src.c_str());
     key.k = k >= 0 ? k : (src ? -1 : -2);

@@ -166,7 +166,7 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
     if ((alts && d_alt_ids && d_alt_prob) || (lex_v && lex)) throw std::runtime_error("parseq_forward: a pattern does not combine with character alternatives or a lexicon");
     if (!pat) {
       uint32_t m[3];
-      for (int i = 0; i < 3; ++i) m[i] = ~charset.blocked[i] & (i == 2 ? 0x7fffffffu : 0xffffffffu);
+      charset.allowed(m);
       if (row_masks || memcmp(m, pattern.mask, sizeof m)) throw std::runtime_error("parseq_forward: the engine's pattern was compiled under another character set than this pass reads under");
     }
     pat_state.ensure((size_t)N * 4);
