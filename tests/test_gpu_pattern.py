@@ -434,3 +434,32 @@ def test_pytuatara_keyword_region_key_environment_and_ocr_cli(weights, pages, fu
     assert len(lines) == len(want_bgr) > 20
     for (bb, text), g in zip(lines, want_bgr):
         assert [float(v) for v in bb.split()] == g["bbox"] and text == g["text"] and re.fullmatch(pattern, text)
+
+
+# ------------------------------------------------------------------------------------------------- 8. more rows than one recogniser group
+def test_4097_crops_under_sets_and_patterns_equal_their_two_groups(eng_x4):
+    """The recogniser takes more than 4096 rows in even groups (4097 = 2049 + 2048), and each group's row masks and start states must start where its crops
+    do.  A crop's outputs do not depend on its batch and a group has the row count of the matching call of its own, so the one call equals the two calls on
+    [:2049] and [2049:] bit for bit."""
+    from tuatara_amd.engine import Pattern, charset_mask, decode_ids
+    n, cut = 4097, 2049
+    lower = "abcdefghijklmnopqrstuvwxyz"
+    crops = np.random.default_rng(131).integers(0, 256, (n, 32, 128, 3), dtype=np.uint8)
+    sets = np.stack([charset_mask(DIGITS + lower), charset_mask(DIGITS + lower + UPPER)])       # (both patterns have members under either set)
+    patterns = [r"[0-9]+", r"[a-z]{2,8}"]
+    set_of = np.array([i % 3 - 1 for i in range(n)], np.int32)                                   # two sets and the engine's own, period 3 ...
+    pattern_of = np.array([i % 5 % 3 - 1 for i in range(n)], np.int32)                           # ... two patterns and none, period 5
+    run = lambda s: eng_x4.parseq_logits(crops[s], set_of=set_of[s], sets=sets, pattern_of=pattern_of[s], patterns=patterns)
+    lg, ids = run(slice(None))
+    lg_a, ids_a = run(slice(0, cut))
+    lg_b, ids_b = run(slice(cut, n))
+    assert lg.tobytes() == np.concatenate([lg_a, lg_b]).tobytes()
+    assert ids.tobytes() == np.concatenate([ids_a, ids_b]).tobytes()
+    # the test bites: every row under a pattern matches it, and the two patterns read differently
+    compiled = [Pattern(p) for p in patterns]
+    texts = [decode_ids(r) for r in np.asarray(ids).reshape(n, 26)]
+    for k in range(2):
+        rows = np.nonzero(pattern_of == k)[0]
+        assert len(rows) > 800 and all(compiled[k].matches(texts[i]) is True for i in rows), k
+    assert {texts[i] for i in np.nonzero(pattern_of == 0)[0]} != {texts[i] for i in np.nonzero(pattern_of == 1)[0]}
+    assert any(not compiled[0].matches(texts[i]) for i in np.nonzero(pattern_of == 1)[0])

@@ -451,3 +451,41 @@ def test_bf16_takes_full_masks_and_refuses_a_restricting_one(eng_bf16, funsd):
         eng_bf16.logits_confidence(np.zeros((1, 26, 95), np.float32), set_of=[0], sets=np.array([[0x7FF, 0, 0]], np.uint32))
     again = eng_bf16.read_regions(funsd, regions, full)
     assert [g["ids"] for g in again] == [g["ids"] for g in got]
+
+
+# ------------------------------------------------------------------------------------------------- 8. more rows than one recogniser group
+def test_a_call_of_4097_regions_equals_its_two_groups(eng_x4):
+    """The recogniser takes more than 4096 rows in even groups (4097 = 2049 + 2048), and each group's row masks, alternatives and lexicon matches must
+    start where its crops do.  A crop's outputs do not depend on its batch (test_x4_parseq_batch_invariance) and a group has the row count of the matching
+    call of its own, so the one call equals the two calls on regions[:2049] and regions[2049:] bit for bit, row for row."""
+    n, cut, classes = 4097, 2049, 1021                                          # 1021: prime, so the positions' cycle and the sets' meet in every combination
+    rng = np.random.default_rng(97)
+    img = rng.integers(0, 256, (96, 640, 3), dtype=np.uint8)
+    regions = []
+    for i in range(n):
+        c = i % classes                                                          # the position class: regions c, c + 1021, ... share a rectangle, not a set
+        x0, y0 = (c * 37) % 500, (c * 11) % 60
+        regions.append({"rect": (x0, y0, x0 + 48 + c % 90, y0 + 14 + c % 21), "set": i % 4 - 1})
+    charsets = [(DIGITS, None), (UPPER, None), ("abcdefghijklmnopqrstuvwxyz", None)]
+    alphabets = [DIGITS, UPPER, "abcdefghijklmnopqrstuvwxyz", DIGITS + UPPER + "abcdefghijklmnopqrstuvwxyz"]
+    words = sorted({"".join(rng.choice(list(alphabets[k % 4]), int(rng.integers(1, 9)))) for k in range(80)})[:64]
+    assert len(words) >= 48
+    eng_x4.set_alternatives(3)
+    eng_x4.set_lexicon(words, 2)
+    try:
+        whole = eng_x4.read_regions(img, regions, charsets)
+        halves = eng_x4.read_regions(img, regions[:cut], charsets) + eng_x4.read_regions(img, regions[cut:], charsets)
+    finally:
+        eng_x4.set_lexicon(None)
+        eng_x4.set_alternatives(0)
+    assert len(whole) == len(halves) == n
+    for i, (a, b) in enumerate(zip(whole, halves)):
+        assert a["ids"] == b["ids"] and a["text"] == b["text"] and a["set"] == b["set"] == i % 4 - 1, i
+        for k in ("prob", "conf"):
+            assert np.asarray(a[k], np.float32).tobytes() == np.asarray(b[k], np.float32).tobytes(), (i, k)
+        for k in ("alt_ids", "alt_prob", "lex_idx", "lex_logp"):
+            assert a[k].tobytes() == b[k].tobytes(), (i, k)
+    # the test bites: the sets matter, and both side blocks hold something
+    assert any(whole[c]["ids"] != whole[c + classes]["ids"] for c in range(classes))        # one rectangle, two sets, two readings
+    assert whole[0]["alt_ids"].shape == (26, 3) and any((r["alt_ids"][:, 1:] >= 0).any() for r in whole)
+    assert whole[0]["lex_idx"].shape == (2,) and any((r["lex_idx"] >= 0).any() for r in whole)

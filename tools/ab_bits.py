@@ -1,5 +1,7 @@
 """GPU box tool: are two builds of the library the same arithmetic?  Heat maps (random CRAFT weights, four canvas sizes), recogniser logits and ids (400 crops, some
-scaled so that planes near the f16 range occur) and whole-page results under TUATARA_LIB=<a> and <b>, each in its own process; compared bit for bit.
+scaled so that planes near the f16 range occur) and whole-page results on the f16x4 engine, logits and ids of 64 crops on a bf16 and an f32 engine, and -
+per precision - the launches per kernel kind of a recogniser pass over 40 and over 300 crops, under TUATARA_LIB=<a> and <b>, each in its own process;
+compared bit for bit.
     python3 tools/ab_bits.py <lib a> <lib b>            (parent: starts the two dumps, compares)
     python3 tools/ab_bits.py --dump out.npz            (child)"""
 import os, subprocess, sys, tempfile
@@ -31,6 +33,15 @@ def dump(path):
     res = eng2.image_to_data(page)
     out["page_boxes"] = np.array([r["bbox"] for r in res], dtype=np.float64).reshape(-1, 4)
     out["page_ids"] = np.array([r["ids"] for r in res], dtype=np.int64).reshape(-1, 26)
+    for prec in ("f16x4", "bf16", "f32"):
+        e = eng2 if prec == "f16x4" else Engine(d2, precision=prec)
+        if prec != "f16x4":
+            out[f"logits_{prec}"], out[f"ids_{prec}"] = e.parseq_logits(crops[:64])
+        for n in (40, 300):
+            e.set_profiling(2)                                          # (resets the tallies) every timed launch: the same kernels, the same number of times
+            e.parseq_logits(crops[:n])
+            out[f"kinds_{prec}_{n}"] = np.array([f"{k['kind']} | stage {k['stage']} | {k['launches']} launches" for k in e.get_profile_kinds()])
+        e.set_profiling(0)
     np.savez(path, **out)
 
 

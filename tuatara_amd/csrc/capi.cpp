@@ -82,13 +82,15 @@ static void check_host_image(const uint8_t* img, int h, int w, int row_stride) {
   if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
 }
 
-// the decode calls, host logits [n][26][95]: E.logits and the RecOut block made large enough, the logits' upload enqueued
-static Engine::RecOut stage_logits(Engine& E, const float* logits, int n) {
+// the decode calls, host logits [n][26][95]: E.logits and the RecOut block made large enough, the logits' upload enqueued; returns the pass over them, for
+// parseq_decode (no crops; no constraint until the call names one)
+static Engine::RecPass stage_logits(Engine& E, const float* logits, int n) {
   const size_t bytes = (size_t)n * Engine::kLogitWords * 4;
   E.logits.ensure(bytes);
-  const Engine::RecOut o = E.rec_out(n);
+  Engine::RecPass p;
+  p.N = n; p.logits = E.logits.as<float>(); p.out = E.rec_out(n);
   TTR_HIP_CHECK(hipMemcpyAsync(E.logits.p, logits, bytes, hipMemcpyHostToDevice, E.stream));
-  return o;
+  return p;
 }
 
 // ... and their end: each RecOut field the caller gave a place for, then the wait (known: no range guard here or in the crop calls, unlike fetch_logits - none of
@@ -123,14 +125,16 @@ static void pack_stage(Engine& E, const Engine::HostImage* image, const std::vec
   TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
 }
 
-// the recogniser calls, host crops [n][32][128][3]: the buffers of a forward made large enough (the AR logits' only where they are asked for), the crops' upload enqueued
-static Engine::RecOut stage_crops(Engine& E, const uint8_t* crops, int n, bool with_ar) {
+// the recogniser calls, host crops [n][32][128][3]: the buffers of a forward made large enough (the AR logits' only where they are asked for), the crops' upload
+// enqueued; returns the pass over them, under the engine's own set until the call names another
+static Engine::RecPass stage_crops(Engine& E, const uint8_t* crops, int n, bool with_ar) {
   E.crops.ensure((size_t)n * Engine::kCropBytes);
   E.logits.ensure((size_t)n * Engine::kLogitWords * 4);
-  const Engine::RecOut o = E.rec_out(n);
-  if (with_ar) E.ar_logits.ensure((size_t)n * Engine::kLogitWords * 4);
+  Engine::RecPass p;
+  p.crops = E.crops.as<uint8_t>(); p.N = n; p.logits = E.logits.as<float>(); p.out = E.rec_out(n); p.mask = E.charset;
+  if (with_ar) { E.ar_logits.ensure((size_t)n * Engine::kLogitWords * 4); p.ar = E.ar_logits.as<float>(); }
   TTR_HIP_CHECK(hipMemcpyAsync(E.crops.p, crops, (size_t)n * Engine::kCropBytes, hipMemcpyHostToDevice, E.stream));
-  return o;
+  return p;
 }
 
 // ... and their end: the logits, the AR logits and the ids where there is a place for them, then the range guard's word of the forward, the wait and its verdict under the call's name
@@ -796,9 +800,9 @@ int ttr_parseq_logits(ttr_engine* e, const uint8_t* crops, int n, float* logits,
   E.refuse_while_streaming("ttr_parseq_logits");
   if (n <= 0) return 0;
   // (not ttr_parseq_logits_patterns with nothing given: where the engine has a pattern that call compiles and stages a table of its own, this one reads under pattern_own)
-  const Engine::RecOut o = stage_crops(E, crops, n, ar_logits != nullptr);
-  E.parseq_forward(E.crops.as<uint8_t>(), n, E.logits.as<float>(), ar_logits ? E.ar_logits.as<float>() : nullptr, o.ids, o.prob, o.conf);
-  fetch_logits(E, o, n, logits, ar_logits, ids, "ttr_parseq_logits");
+  const Engine::RecPass p = stage_crops(E, crops, n, ar_logits != nullptr);
+  E.parseq_forward(p);
+  fetch_logits(E, p.out, n, logits, ar_logits, ids, "ttr_parseq_logits");
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -810,9 +814,9 @@ int ttr_logits_confidence(ttr_engine* e, const float* logits, int n, int32_t* id
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_logits_confidence");
   if (n == 0) return 0;
-  const Engine::RecOut o = stage_logits(E, logits, n);
-  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream);
-  fetch_decoded(E, o, n, ids, probs, conf);
+  const Engine::RecPass p = stage_logits(E, logits, n);
+  E.parseq_decode(p);
+  fetch_decoded(E, p.out, n, ids, probs, conf);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -825,9 +829,10 @@ int ttr_logits_confidence_masked(ttr_engine* e, const float* logits, int n, cons
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_logits_confidence_masked");
   if (n == 0) return 0;
-  const Engine::RecOut o = stage_logits(E, logits, n);
-  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, ClassMask::from_allowed(mask));
-  fetch_decoded(E, o, n, ids, probs, conf);
+  Engine::RecPass p = stage_logits(E, logits, n);
+  p.mask = ClassMask::from_allowed(mask);
+  E.parseq_decode(p);
+  fetch_decoded(E, p.out, n, ids, probs, conf);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -946,16 +951,12 @@ int ttr_parseq_logits_patterns(ttr_engine* e, const uint8_t* crops, int n, const
   Engine::PatRows pats;
   const bool with_pats = E.resolve_row_patterns(what, patterns, n_patterns, pattern_of, n, table, one, pats);
   if (n == 0) return 0;
-  const Engine::RecOut o = stage_crops(E, crops, n, ar_logits != nullptr);
-  {
-    struct SetScope { ClassMask& c; ClassMask old; ~SetScope() { c = old; } } set_scope{E.charset, E.charset};   // (one shared mask: by value, the engine's own path)
-    E.charset = one;
-    PatDev pd{};
-    if (with_pats) pd = E.stage_row_patterns(pats, 0);
-    E.parseq_forward(E.crops.as<uint8_t>(), n, E.logits.as<float>(), ar_logits ? E.ar_logits.as<float>() : nullptr, o.ids, o.prob, o.conf, E.stage_row_masks(table, 0), nullptr, nullptr,
-                     nullptr, with_pats ? &pd : nullptr);
-  }
-  fetch_logits(E, o, n, logits, ar_logits, ids, what);
+  Engine::RecPass p = stage_crops(E, crops, n, ar_logits != nullptr);
+  p.mask = one;   // (one shared mask: by value, the engine's own path)
+  if (with_pats) p.pat = E.stage_row_patterns(pats, 0);
+  p.row_masks = E.stage_row_masks(table, 0);
+  E.parseq_forward(p);
+  fetch_logits(E, p.out, n, logits, ar_logits, ids, what);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -971,9 +972,10 @@ int ttr_logits_confidence_sets(ttr_engine* e, const float* logits, int n, const 
   ClassMask one{};
   E.resolve_row_masks("ttr_logits_confidence_sets", set_of, n, sets, n_sets, table, one);
   if (n == 0) return 0;
-  const Engine::RecOut o = stage_logits(E, logits, n);
-  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, one, E.stage_row_masks(table, 0));
-  fetch_decoded(E, o, n, ids, probs, conf);
+  Engine::RecPass p = stage_logits(E, logits, n);
+  p.mask = one; p.row_masks = E.stage_row_masks(table, 0);
+  E.parseq_decode(p);
+  fetch_decoded(E, p.out, n, ids, probs, conf);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -1091,9 +1093,10 @@ int ttr_logits_decode_patterns(ttr_engine* e, const float* logits, int n, const 
       pats.start_of[(size_t)i] = it->second;
     }
   }
-  const Engine::RecOut o = stage_logits(E, logits, n);
-  launch_decode_pat(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, E.stage_row_patterns(pats, 0));
-  fetch_decoded(E, o, n, ids, probs, conf);
+  Engine::RecPass p = stage_logits(E, logits, n);
+  p.pat = E.stage_row_patterns(pats, 0);
+  E.parseq_decode(p);
+  fetch_decoded(E, p.out, n, ids, probs, conf);
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -1287,12 +1290,12 @@ int ttr_logits_alternatives(ttr_engine* e, const float* logits, int n, int k, co
   if (sets) E.resolve_row_masks("ttr_logits_alternatives", set_of, n, sets, n_sets, table, one);
   if (n == 0) return 0;
   const Engine::AltOut a = E.alts_out(n, k);
-  const Engine::RecOut o = stage_logits(E, logits, n);
-  const RowMask* rows = E.stage_row_masks(table, 0);
-  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, one, rows);
-  launch_decode_alts(E.logits.as<float>(), n, o.ids, o.prob, k, a.ids, a.prob, E.stream, one, rows);
-  if (alt_ids) TTR_HIP_CHECK(hipMemcpyAsync(alt_ids, a.ids, (size_t)n * 26 * k * 4, hipMemcpyDeviceToHost, E.stream));
-  if (alt_probs) TTR_HIP_CHECK(hipMemcpyAsync(alt_probs, a.prob, (size_t)n * 26 * k * 4, hipMemcpyDeviceToHost, E.stream));
+  Engine::RecPass p = stage_logits(E, logits, n);
+  p.mask = one; p.row_masks = E.stage_row_masks(table, 0); p.alt = a;
+  E.parseq_decode(p);
+  const size_t side = Engine::alts_side_bytes(n, k) / 2;   // bytes of either half of the side block
+  if (alt_ids) TTR_HIP_CHECK(hipMemcpyAsync(alt_ids, a.ids, side, hipMemcpyDeviceToHost, E.stream));
+  if (alt_probs) TTR_HIP_CHECK(hipMemcpyAsync(alt_probs, a.prob, side, hipMemcpyDeviceToHost, E.stream));
   TTR_HIP_CHECK(hipStreamSynchronize(E.stream));   // (the side block alone comes back: no RecOut field, so no fetch_decoded)
   return 0;
   TTR_GUARD_END(-1)
@@ -1391,10 +1394,9 @@ int ttr_logits_lexicon(ttr_engine* e, const float* logits, int n, const uint32_t
   if (n == 0) return 0;
   const int M = E.lex_m;
   const Engine::LexOut l = E.lex_out(n, M);
-  const Engine::RecOut o = stage_logits(E, logits, n);
-  const RowMask* rows = E.stage_row_masks(table, 0);
-  launch_decode_conf(E.logits.as<float>(), n, o.ids, o.prob, o.conf, E.stream, one, rows);
-  launch_lexicon(E.logits.as<float>(), n, o.ids, o.prob, E.lex_records.p, E.lex_v, M, l.idx, l.logp, l.part_idx, l.part_logp, E.stream, one, rows);
+  Engine::RecPass p = stage_logits(E, logits, n);
+  p.mask = one; p.row_masks = E.stage_row_masks(table, 0); p.lex = l;
+  E.parseq_decode(p);
   if (idx) TTR_HIP_CHECK(hipMemcpyAsync(idx, l.idx, (size_t)n * M * 4, hipMemcpyDeviceToHost, E.stream));
   if (logp) TTR_HIP_CHECK(hipMemcpyAsync(logp, l.logp, (size_t)n * M * 4, hipMemcpyDeviceToHost, E.stream));
   TTR_HIP_CHECK(hipStreamSynchronize(E.stream));   // (as ttr_logits_alternatives: the side block alone)

@@ -449,7 +449,11 @@ struct Engine {
   hipEvent_t lane_go = nullptr, lane_done = nullptr, resize_done = nullptr;
   bool lane_go_pending = false;                   // craft_forward_split records lane_go behind slice3.20 when set
   int craft_ws_npl = 0;                           // planes per value the split CRAFT workspaces were laid out for
-  DevBuf pq_ws[24];
+  // the recogniser's workspaces, by what they hold (a group's pointers into them: PqWork, engine_parseq.cpp)
+  enum PqWs { kWsPatches, kWsX, kWsT384, kWsTbig, kWsAtt, kWsKvmem, kWsKvcache, kWsTgt, kWsD384b, kWsD1536, kWsStepLogits,
+              kWsLnPlanes, kWsBigPlanes, kWsAttPlanes, kWsDecPlanesA, kWsDecPlanesB, kWsDecPlanes1536, kWsDecPlanesSa, kWsCount };
+  DevBuf pq_ws[kWsCount];
+  template <typename U = void> U* pq_buf(PqWs i, size_t bytes) { pq_ws[i].ensure(bytes); return pq_ws[i].as<U>(); }
   DevBuf canvas, heat, staging_img, crops, rects_dev, coef_dev, logits, ar_logits, ids_dev, tokens;
   DevBuf orient_in, orient_cand, orient_side;     // word orientation: the twins' coef | rects | page firsts; their recogniser block; the side block (orient.hip)
   PinnedBuf h_orient_in[2], h_orient[2];          // ... per slot: staging of orient_in, host copy of the side block
@@ -457,19 +461,19 @@ struct Engine {
   PinnedBuf h_lines_in[2], h_lines[2];            // ... per slot: staging of lines_in, host copy of the side block
   DevBuf alts_side;                               // character alternatives: the side block (decode_alts.hip), [N][26][K] int32 ids | [N][26][K] f32 prob
   PinnedBuf h_alts[2];                            // ... per slot: its host copy
-  struct AltOut { int* ids; float* prob; };
+  struct AltOut { int* ids; float* prob; int k; };   // k: the block's alternatives per position, 0 = none
   static size_t alts_side_bytes(int N, int K) { return (size_t)N * 26 * K * 8; }
-  AltOut alts_out(int N, int K) { alts_side.ensure(alts_side_bytes(std::max(N, 1), K)); return AltOut{alts_side.as<int>(), alts_side.as<float>() + (size_t)N * 26 * K}; }
+  AltOut alts_out(int N, int K) { alts_side.ensure(alts_side_bytes(std::max(N, 1), K)); return AltOut{alts_side.as<int>(), alts_side.as<float>() + (size_t)N * 26 * K, K}; }
   DevBuf lex_side, lex_part;                      // lexicon matching: the side block (lexicon.hip), [N][M] int32 idx | [N][M] f32 logp; the scorer's partials [N][chunks][M] idx | logp
   PinnedBuf h_lex[2];                             // ... per slot: the side block's host copy
-  struct LexOut { int* idx; float* logp; int* part_idx; float* part_logp; };
+  struct LexOut { int* idx; float* logp; int* part_idx; float* part_logp; int m; };   // m: the block's matches per item, 0 = none
   static size_t lex_side_bytes(int N, int M) { return (size_t)N * M * 8; }
   LexOut lex_out(int N, int M) {
     N = std::max(N, 1);
     lex_side.ensure(lex_side_bytes(N, M));
     const size_t pe = lexicon_partial_entries(N, lex_v, M);
     lex_part.ensure(pe * 8);
-    return LexOut{lex_side.as<int>(), lex_side.as<float>() + (size_t)N * M, lex_part.as<int>(), lex_part.as<float>() + pe};
+    return LexOut{lex_side.as<int>(), lex_side.as<float>() + (size_t)N * M, lex_part.as<int>(), lex_part.as<float>() + pe, M};
   }
   DevBuf wide_side;                               // wide words: the side block (wide.hip), [Wn][17] int32 cuts | [Wn][2048] u16 profile
   PinnedBuf h_wide[2];                            // ... per slot: the cuts' host copy
@@ -667,16 +671,12 @@ struct Engine {
   void decoder_tail(const void* sa, int N, int R, const float* resid_pos, int resid_mod, float* tgt, void* t384, void* t384b, void* t1536,
                     const void* kvmem, float* logits_out, int logits_ld, const int* done_tok = nullptr, int done_col = 0);
 
-  // crops u8 [N][32][128][3] (device) -> logits f32 [N][26][95], ids i32 [N][26], prob f32 [N][26], conf f32 [N] (device); d_ar optional
-  // row_masks (device, [N] RowMask; DESIGN.md "Regions and per-row character sets"): crop n chooses its tokens under row_masks[n] instead of `charset`; null = charset
-  // d_alt_ids / d_alt_prob (device, [N][26][alts]; DESIGN.md "Character alternatives"): with `alts` set and both given, decode_alts_kernel runs behind the final decode
-  // lex (device; DESIGN.md "Lexicon matching"): with a lexicon set and lex given, the scorer and its merge run behind the final decode; lex->idx / logp are
-  // [N][lex_m], the partials as lex_out sizes them for these N crops
-  void parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks = nullptr,
-                      int* d_alt_ids = nullptr, float* d_alt_prob = nullptr, const LexOut* lex = nullptr, const PatDev* pat = nullptr);
   // The recogniser's outputs of `rows` crops share one device buffer (ids_dev), laid out [rows][26] ids | [rows][26] prob | [rows] conf, so that
   // one device-to-host copy and one collective carry all three.  Ensures the buffer (never inside a launch function).
-  struct RecOut { int* ids; float* prob; float* conf; };
+  struct RecOut {
+    int* ids; float* prob; float* conf;
+    RecOut at(size_t row) const { return RecOut{ids + row * 26, prob + row * 26, conf + row}; }   // the block's rows from `row` on
+  };
   static constexpr int kRecWords = 26 + 26 + 1;   // 4-byte words per crop
   static constexpr int kLogitWords = 26 * 95;     // 4-byte words of a crop's logits
   static constexpr int kCropBytes = 32 * 128 * 3; // bytes of a crop: 32 x 128 RGB
@@ -686,6 +686,52 @@ struct Engine {
     int* b = d.as<int>();
     return RecOut{b, reinterpret_cast<float*>(b + (size_t)rows * 26), reinterpret_cast<float*>(b + (size_t)rows * 52)};
   }
+  // One recogniser pass, everything on the device.  Reads `crops` u8 [N][32][128][3]; writes `logits` f32 [N][26][95], the AR steps' logits `ar` (same
+  // shape; null = not kept) and `out`: ids i32 [N][26], prob f32 [N][26], conf f32 [N].  What constrains it travels with it, by value:
+  //   mask / row_masks  the character set (DESIGN.md "Character sets"): every crop chooses its tokens under `mask`, or - row_masks not null ([N] RowMask;
+  //                     DESIGN.md "Regions and per-row character sets") - crop n under row_masks[n]
+  //   alt               (DESIGN.md "Character alternatives") with alt.k set and both blocks given ([N][26][k]), decode_alts_kernel runs behind the final decode
+  //   lex               (DESIGN.md "Lexicon matching") with lex.m set and the blocks given (idx / logp [N][m], the partials as lex_out sizes them for these N
+  //                     crops), the scorer and its merge run behind the final decode, on the engine's word list
+  //   pat               (DESIGN.md "Patterns") the call's table; an empty one (delta null) = the engine's own pattern, or none
+  struct RecPass {
+    const uint8_t* crops = nullptr; int N = 0;
+    float *logits = nullptr, *ar = nullptr;
+    RecOut out{};
+    ClassMask mask{}; const RowMask* row_masks = nullptr;
+    AltOut alt{}; LexOut lex{}; PatDev pat{};
+    bool with_alts() const { return alt.k && alt.ids && alt.prob; }
+    bool with_lex() const { return lex.m && lex.idx && lex.logp; }
+    // the same pass over rows [r0, r0 + n): every per-row pointer moves by its own width (rows are never permuted: a row's crop, mask, start state and
+    // outputs share its index), null stays null; the mask, the pattern's tables and the lexicon's partials (passes run one after another on the stream) are shared
+    RecPass rows(int r0, int n) const {
+      auto at = [r0](auto* p, size_t width) { return p ? p + (size_t)r0 * width : nullptr; };
+      RecPass g = *this;
+      g.N = n;
+      g.crops = at(crops, kCropBytes); g.logits = at(logits, kLogitWords); g.ar = at(ar, kLogitWords);
+      g.out = out.at(r0);
+      g.row_masks = at(row_masks, 1);
+      g.alt.ids = at(alt.ids, 26 * (size_t)alt.k); g.alt.prob = at(alt.prob, 26 * (size_t)alt.k);
+      g.lex.idx = at(lex.idx, lex.m); g.lex.logp = at(lex.logp, lex.m);
+      g.pat.start_of = at(pat.start_of, 1);
+      return g;
+    }
+  };
+  // A batch of more than 4096 crops goes through in even groups (rows()); each group is parseq_group: the four steps below, which hand each other the
+  // group's workspaces (PqWork, engine_parseq.cpp).  parseq_decode is also the whole of the decode stage calls (a pass over logits alone): the pattern or
+  // confidence decode, then the alternatives, then the lexicon - under pass.pat as it stands (the engine's own pattern is parseq_forward's to fill in)
+  struct PqWork;
+  void parseq_forward(const RecPass& pass);
+  void parseq_group(const RecPass& p);
+  void parseq_encode(const RecPass& p, PqWork& w);
+  void encoder_split(int N, PqWork& w);   // the 12 blocks and the final norm on planes (split-operand engines) ...
+  void encoder_plain(int N, PqWork& w);   // ... and on T tensors (bf16, fp32)
+  bool enc_split() const { return prec == kSplit && tn.split_gemm && tn.split_planes; }
+  bool dec_split() const { return enc_split() && tn.dec_planes; }   // the decoder's layers hand each other planes (decoder_tail_split)
+  DecArParams dec_ar_params(const RecPass& p, const PqWork& w);
+  void parseq_ar(const RecPass& p, PqWork& w);
+  void parseq_refine(const RecPass& p, PqWork& w);
+  void parseq_decode(const RecPass& p);
   // the host's view of such a block of `rows` rows, as it lands in h_ids[slot] or as rank r's share of h_gath[slot]
   struct RecRows { const int32_t* ids; const float* prob; const float* conf; };
   static RecRows rec_rows(const void* block, int rows) {

@@ -434,11 +434,11 @@ void Engine::pack_twin_crops(const PageBatch& B, int sl) {
   const Page& P0 = B.pages[0];
   if (B.mixed) {
     launch_pack_crops_rect_pages(page_table[sl & 1].as<PageRow>(), reinterpret_cast<const int*>(orient_in.as<uint8_t>() + coef_b), orient_in.as<int64_t>(),
-                                 crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, stream);
+                                 crops.as<uint8_t>() + (size_t)N * kCropBytes, T, stream);
     TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the batch's last reader of the slot's table)
   } else {
     launch_pack_crops_rect(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, reinterpret_cast<const int*>(orient_in.as<uint8_t>() + coef_b), orient_in.as<int64_t>(),
-                           crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, stream);
+                           crops.as<uint8_t>() + (size_t)N * kCropBytes, T, stream);
   }
 }
 
@@ -677,40 +677,43 @@ void Engine::recog_enqueue(PageBatch& B) {
   TTR_HIP_CHECK(hipEventRecord(evr[sl][0], stream));
   if (N > 0) {
     const int K = orient_k(), T = (K - 1) * N;                 // word orientation: T twin crops behind the batch's N (DESIGN.md "Word orientation")
-    crops.ensure((size_t)(N + T + X) * 32 * 128 * 3);
+    crops.ensure((size_t)(N + T + X) * kCropBytes);
     logits.ensure((size_t)std::max(std::max(N, X), T) * kLogitWords * 4);
     if (X) h_wide[sl].ensure(B.wide.size() * 17 * 4);
     const RecOut cand = T ? rec_block(orient_cand, T) : RecOut{};
     const size_t side_b = ((size_t)N * (K + 1) + B.n) * 4;   // [N] turn | [N][K] candidate conf | [pages] page turn
     if (T) { orient_side.ensure(side_b); h_orient[sl].ensure(side_b); }
+    RecPass main;   // the batch's N rows: the scratch logits, the standard block, the engine's own set
+    main.crops = crops.as<uint8_t>(); main.N = N; main.logits = logits.as<float>(); main.out = out; main.mask = charset;
     // character alternatives: the side block of this batch (the setter refuses an engine with orientation, so T is 0 here)
-    const AltOut alt = B.alts ? alts_out(N, B.alts) : AltOut{nullptr, nullptr};
-    if (B.alts) h_alts[sl].ensure(alts_side_bytes(N, B.alts));
+    if (B.alts) { main.alt = alts_out(N, B.alts); h_alts[sl].ensure(alts_side_bytes(N, B.alts)); }
     // lexicon matching: the side block and the scorer's partials of this batch
-    const LexOut lexo = B.lex_m ? lex_out(N, B.lex_m) : LexOut{};
-    const LexOut* const lex = B.lex_m ? &lexo : nullptr;
-    if (B.lex_m) h_lex[sl].ensure(lex_side_bytes(N, B.lex_m));
+    if (B.lex_m) { main.lex = lex_out(N, B.lex_m); h_lex[sl].ensure(lex_side_bytes(N, B.lex_m)); }
     pack_batch_crops(B, sl);
     if (T) pack_twin_crops(B, sl);
     if (cfg.lines) group_batch_lines(B, sl, line_words);               // text lines: from the boxes alone, so inside the packing stage (DESIGN.md "Text lines")
     if (cfg.blocks) group_batch_blocks(B, sl, line_words);             // text blocks: directly behind, from the lines' side block on the device (DESIGN.md "Text blocks")
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     if (B.regions) {   // the caller's sets: one mask by value (the engine's own path), or the rows' table through the slot's pinned staging (one copy, no launch)
-      struct SetScope { ClassMask& c; ClassMask old; ~SetScope() { c = old; } } set_scope{charset, charset};
-      charset = B.region_mask;
-      PatDev pd{};                 // ... and the regions' patterns: the call's table the same way (one more copy, no launch)
-      if (!B.region_pats.start_of.empty()) pd = stage_row_patterns(B.region_pats, sl);
-      const RowMask* masks = stage_row_masks(B.row_masks, sl);
-      parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, masks, alt.ids, alt.prob, lex, pd.delta ? &pd : nullptr);
-      // wide words: the X other pieces as a pass of their own, into rows N.. of the same block - the batch's N rows keep their batch, and with it every bit of
-      // the words that are not wide (the recogniser picks its kernels by the row count)
-      if (X) parseq_forward(crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, X, logits.as<float>(), nullptr, out.ids + (size_t)N * 26, out.prob + (size_t)N * 26, out.conf + N, masks ? masks + N : nullptr);
-    } else {
-    parseq_forward(crops.as<uint8_t>(), N, logits.as<float>(), nullptr, out.ids, out.prob, out.conf, nullptr, alt.ids, alt.prob, lex);
-    if (X) parseq_forward(crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, X, logits.as<float>(), nullptr, out.ids + (size_t)N * 26, out.prob + (size_t)N * 26, out.conf + N);
+      main.mask = B.region_mask;
+      if (!B.region_pats.start_of.empty()) main.pat = stage_row_patterns(B.region_pats, sl);   // ... and the regions' patterns: the call's table the same way (one more copy, no launch)
+      main.row_masks = stage_row_masks(B.row_masks, sl);
     }
+    parseq_forward(main);
+    // the passes behind the batch's own read the crops from row N on.  The logits are scratch: every pass starts at their base, so they are named here and not
+    // sliced; the side blocks and the call's pattern table belong to the batch's N rows alone
+    auto behind = [&](int n) {
+      RecPass r = main.rows(N, n);
+      r.logits = logits.as<float>(); r.alt = AltOut{}; r.lex = LexOut{}; r.pat = PatDev{};
+      return r;
+    };
+    // wide words: the X other pieces as a pass of their own, into rows N.. of the same block - the batch's N rows keep their batch, and with it every bit of
+    // the words that are not wide (the recogniser picks its kernels by the row count)
+    if (X) parseq_forward(behind(X));
     if (T) {   // the twins as a pass of their own (turn 0 keeps its batch, and with it its bits), then the choice, in place in the standard block
-      parseq_forward(crops.as<uint8_t>() + (size_t)N * 32 * 128 * 3, T, logits.as<float>(), nullptr, cand.ids, cand.prob, cand.conf);
+      RecPass twin = behind(T);
+      twin.out = cand; twin.mask = charset; twin.row_masks = nullptr;   // a block of their own, under the engine's own set
+      parseq_forward(twin);
       const size_t first_off = (size_t)T * 84;
       launch_orient_select(out.ids, out.prob, out.conf, cand.ids, cand.prob, cand.conf, reinterpret_cast<const int*>(orient_in.as<uint8_t>() + first_off), B.n, N, K,
                            cfg.orient_page, orient_side.as<int>(), stream);
@@ -1198,16 +1201,20 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   if (N == 0) return;
   const int per = (N + world - 1) / world;
   const int lo = std::min(N, rank * per), hi = std::min(N, lo + per);
-  crops.ensure((size_t)world * per * 32 * 128 * 3);           // (the last shard may be ragged: the buffer holds world * per crops)
+  crops.ensure((size_t)world * per * kCropBytes);           // (the last shard may be ragged: the buffer holds world * per crops)
   if (rank == 0) {
     pack_batch_crops(B, 0);
   }
-  c->tr->broadcast(crops.p, (size_t)N * 32 * 128 * 3, 0, stream);
+  c->tr->broadcast(crops.p, (size_t)N * kCropBytes, 0, stream);
   logits.ensure((size_t)per * kLogitWords * 4);
   const RecOut out = rec_out(per);                              // per rank: [per][26] ids | [per][26] prob | [per] conf, one collective
   const size_t block = (size_t)per * kRecWords * 4;
   range_use(kRangeRec0);
-  if (hi > lo) parseq_forward(crops.as<uint8_t>() + (size_t)lo * 32 * 128 * 3, hi - lo, logits.as<float>(), nullptr, out.ids, out.prob, out.conf);
+  RecPass shard;   // this rank's rows of the broadcast crops, into the base of its own logits and block
+  shard.crops = crops.as<uint8_t>(); shard.mask = charset;
+  shard = shard.rows(lo, hi - lo);
+  shard.logits = logits.as<float>(); shard.out = out;
+  parseq_forward(shard);
   gath_dev[0].ensure((size_t)world * block);
   h_gath[0].ensure((size_t)world * block);
   c->tr->all_gather(ids_dev.p, gath_dev[0].p, block, false, stream);

@@ -134,108 +134,139 @@ void Engine::decoder_tail(const void* sa, int N, int R, const float* resid_pos, 
   ln_gemm(tgt, "decoder.norm", 1e-5f, t384, pq.at("head"), rows, nullptr, 0, kActNone, logits_out, logits_ld);
 }
 
-void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, float* d_ar, int* d_ids, float* d_prob, float* d_conf, const RowMask* row_masks,
-                            int* d_alt_ids, float* d_alt_prob, const LexOut* lex, const PatDev* pat) {
-  if (N <= 0) return;
+// what one group's steps hand each other: pointers into pq_ws (sized for the group by the step that fills them in) and the decoder's constants
+struct Engine::PqWork {
+  // parseq_encode: the fp32 residual stream [M][384]; LayerNorm output / the decoder's scratch rows; qkv and the MLP hidden; attention output; the split-operand
+  // encoder's LayerNorm output planes of the whole group (its final norm = the decoder's memory); the cross-attention's K | V of the memory [M][768]
+  float* x; void *t384, *tbig, *att, *ln_planes, *kvmem;
+  // parseq_ar: the K/V cache, the decoder's residual stream and scratch rows; the split-operand decoder's planes (decoder_tail_split; null otherwise); tokens
+  // [N][26]; token embedding, position queries, norm_c; where the AR steps' logits go (the pass's `ar`, or a workspace) and how many steps run
+  void* kvcache; float* tgt; void *d384b, *d1536, *dpa, *dpb, *dp1536, *dsa; int* tk;
+  const float *emb, *posq, *gc, *bc; float* ar; int nsteps;
+};
+
+void Engine::parseq_forward(const RecPass& pass) {
+  if (pass.N <= 0) return;
+  // a character set (DESIGN.md "Character sets") constrains every place below that chooses a token, by value: the argmax launches, the argmax folded into
+  // dec_embed_ln / the skinny self_kv linear, and the final decode.  The bf16 engine chooses inside gemm_sk.hip and dec_fused.hip, which take no mask
+  if ((pass.mask.restricts() || pass.row_masks) && prec == kBF16) throw std::runtime_error("parseq_forward: a character set needs an f16x4 or f32 engine (the bf16 engine's kernels take no class mask)");
+  // a pattern (DESIGN.md "Patterns"): the call's table, or the engine's own - compiled under `charset`, so it holds for that mask by value alone.  With one in
+  // force the AR steps' argmax is launch_argmax_pat, always as its own launch, and the final decode launch_decode_pat; without one nothing below differs
+  RecPass p = pass;
+  const bool own = !p.pat.delta && pattern_own.delta;
+  if (own) p.pat = pattern_own;
+  if (p.pat.delta) {
+    if (prec == kBF16) throw std::runtime_error("parseq_forward: a pattern needs an f16x4 or f32 engine (the bf16 engine's kernels choose their tokens themselves)");
+    if (p.with_alts() || (lex_v && p.with_lex())) throw std::runtime_error("parseq_forward: a pattern does not combine with character alternatives or a lexicon");
+    if (own) {
+      uint32_t m[3];
+      p.mask.allowed(m);
+      if (p.row_masks || memcmp(m, pattern.mask, sizeof m)) throw std::runtime_error("parseq_forward: the engine's pattern was compiled under another character set than this pass reads under");
+    }
+  }
   // A very large crop batch (64 pages of ~150 boxes) goes through in even groups: the refinement pass's widest planes tensor (26 rows per crop x 1536 x 6 bytes)
   // must stay inside the 2 GiB window of 32-bit buffer offsets (8962 crops), and the workspaces stay bounded.  Crops are independent (batch-invariant logits,
   // tests): grouping changes nothing but the kernels' shapes; the AR loop's early exit then applies per group.
   constexpr int kMaxCrops = 4096;
-  if (N > kMaxCrops) {
-    const int groups = (N + kMaxCrops - 1) / kMaxCrops, per = (N + groups - 1) / groups;
-    LexOut lex_g{};
-    PatDev pat_g{};
-    for (int g0 = 0; g0 < N; g0 += per) {
-      const int n = std::min(per, N - g0);
-      parseq_forward(d_crops + (size_t)g0 * 32 * 128 * 3, n, d_logits + (size_t)g0 * 26 * 95, d_ar ? d_ar + (size_t)g0 * 26 * 95 : nullptr, d_ids + (size_t)g0 * 26,
-                     d_prob + (size_t)g0 * 26, d_conf + g0, row_masks ? row_masks + g0 : nullptr,   // (rows are never permuted: a group's masks start where its crops do)
-                     d_alt_ids ? d_alt_ids + (size_t)g0 * 26 * alts : nullptr, d_alt_prob ? d_alt_prob + (size_t)g0 * 26 * alts : nullptr,
-                     lex ? &(lex_g = LexOut{lex->idx + (size_t)g0 * lex_m, lex->logp + (size_t)g0 * lex_m, lex->part_idx, lex->part_logp}) : nullptr,   // (the groups run one after another on the stream: they share the partials)
-                     pat ? &(pat_g = PatDev{pat->delta, pat->mind, pat->start_of ? pat->start_of + g0 : nullptr, pat->start}) : nullptr);   // (a group's start states start where its crops do)
-    }
-    return;
-  }
-  // a character set (DESIGN.md "Character sets") constrains every place below that chooses a token, by value: the argmax launches, the argmax folded into
-  // dec_embed_ln / the skinny self_kv linear, and the final decode.  The bf16 engine chooses inside gemm_sk.hip and dec_fused.hip, which take no mask
-  if ((charset.restricts() || row_masks) && prec == kBF16) throw std::runtime_error("parseq_forward: a character set needs an f16x4 or f32 engine (the bf16 engine's kernels take no class mask)");
-  // a pattern (DESIGN.md "Patterns"): the call's table, or the engine's own - compiled under `charset`, so it holds for the by-value mask alone.  With one in
-  // force the AR steps' argmax is launch_argmax_pat, always as its own launch, and the final decode launch_decode_pat; without one nothing below differs
-  const PatDev* const pt = pat ? pat : (pattern_own.delta ? &pattern_own : nullptr);
-  if (pt) {
-    if (prec == kBF16) throw std::runtime_error("parseq_forward: a pattern needs an f16x4 or f32 engine (the bf16 engine's kernels choose their tokens themselves)");
-    if ((alts && d_alt_ids && d_alt_prob) || (lex_v && lex)) throw std::runtime_error("parseq_forward: a pattern does not combine with character alternatives or a lexicon");
-    if (!pat) {
-      uint32_t m[3];
-      charset.allowed(m);
-      if (row_masks || memcmp(m, pattern.mask, sizeof m)) throw std::runtime_error("parseq_forward: the engine's pattern was compiled under another character set than this pass reads under");
-    }
-    pat_state.ensure((size_t)N * 4);
-  }
+  const int groups = (p.N + kMaxCrops - 1) / kMaxCrops, per = (p.N + groups - 1) / groups;
+  for (int g0 = 0; g0 < p.N; g0 += per) parseq_group(p.rows(g0, std::min(per, p.N - g0)));
+}
+
+void Engine::parseq_group(const RecPass& p) {
+  if (p.pat.delta) pat_state.ensure((size_t)p.N * 4);
   prof_stage = 1;
-  const int M = N * 128, E = 384;
+  PqWork w{};
+  parseq_encode(p, w);
+  range_scope = "decoder.";
+  struct ScopeReset { std::string& s; ~ScopeReset() { s.clear(); } } scope_reset{range_scope};
+  parseq_ar(p, w);
+  parseq_refine(p, w);
+  parseq_decode(p);
+}
+
+// ---- encoder: patch embedding, the 12 blocks and the final norm (the decoder's memory), then the cross-attention's K | V of that memory
+void Engine::parseq_encode(const RecPass& p, PqWork& w) {
+  const int N = p.N, M = N * 128, E = 384;
   const int patch_ld = pq.at("patch").k;   // 96, or 128 in bf16 mode (zero-padded)
   range_tag("parseq.encoder.patch_embed");
-  void* patches = (pq_ws[0].ensure((size_t)M * patch_ld * es), pq_ws[0].p);
-  float* x = (float*)(pq_ws[1].ensure((size_t)M * E * 4), pq_ws[1].p);
-  void* t384 = (pq_ws[2].ensure((size_t)std::max(M, N * 26) * E * es), pq_ws[2].p);
-  void* tbig = (pq_ws[3].ensure((size_t)M * 1536 * es), pq_ws[3].p);
-  void* att = (pq_ws[4].ensure((size_t)std::max(M, N * 26) * E * es), pq_ws[4].p);
-  launch_patchify(prec, d_crops, patches, N, patch_ld, stream);
-  gemm(pq.at("patch"), patches, M, nullptr, 0, kActNone, x, E, pqf.at("encoder.pos_embed").as<float>(), E, 128);
-  const bool enc_split = prec == kSplit && tn.split_gemm && tn.split_planes;
-  if (enc_split) {
-    // split-operand engines: LayerNorm, GEMM epilogues and the attention kernel hand each other planes (split.h); only the residual
-    // stream x is fp32.  Crop groups keep the widest planes tensor (the MLP hidden: 1536 x 6 bytes per row) inside the 2 GiB window.
-    int CHS = std::max(1, std::min(N, (int)((((size_t)1 << 31) - 1) / ((size_t)128 * 1536 * 6))));
-    if (tn.enc_chunk > 0) CHS = std::min(CHS, tn.enc_chunk);   // (experiment knob: crop groups whose residual stream and LayerNorm planes stay in the Infinity Cache)
-    if (N > CHS) { const int groups = (N + CHS - 1) / CHS; CHS = (N + groups - 1) / groups; }   // even groups: 2560 crops = 1280 + 1280, not 1820 + 740
-    void* lnp = (pq_ws[11].ensure((size_t)M * E * 6), pq_ws[11].p);                       // LayerNorm output planes (whole batch: the memory at the end)
-    void* bigp = (pq_ws[12].ensure((size_t)std::min(N, CHS) * 128 * 1536 * 6), pq_ws[12].p);   // qkv / MLP hidden planes
-    void* attp = (pq_ws[13].ensure((size_t)std::min(N, CHS) * 128 * E * 6), pq_ws[13].p);      // attention output planes
-    auto lnp_at = [&](int c0) { return (char*)lnp + (size_t)c0 * 128 * E * 6; };
-    const int lnpl = tn.enc_ln_pairs ? 2 : 3;        // planes of the LayerNorm outputs that feed qkv / fc1 (pairs: three MFMAs per product there)
-    // the planes the encoder's GEMMs hand each other as their loaders' 1-KiB pieces (ConvParams::x_tiled): a wave instruction of the LDS-DMA fetches one
-    // contiguous KiB instead of eight 128-byte rows 1.5 - 6 KB apart - 71 against 31 GB/s per CU for a lone four-wave workgroup (tools/micro/dma_depth.hip)
-    // (measured: the recogniser pass at 1280 crops 34.96 -> 34.22 ms; a single page's 40 crops unchanged.  Groups small enough for the skinny projection keep the rows.)
-    const int xt = tn.sp_tiled_x && tn.qkv_attn_split && lnpl == 2 && tn.enc_fc2_pairs && std::min(CHS, N) * 128 > tn.skinny_max_rows ? 1 : 0;
-    for (int c0 = 0; c0 < N; c0 += CHS) {
-      const int nc = std::min(CHS, N - c0), Mc = nc * 128;
-      float* xc = x + (size_t)c0 * 128 * E;
-      for (int l = 0; l < 12; ++l) {
-        const std::string p = "encoder.blocks." + std::to_string(l) + ".";
-        range_scope = p;
-        range_tag("parseq." + p + "norm1");
-        launch_layernorm_planes(xc, E, pqf.at(p + "norm1.weight").as<float>(), pqf.at(p + "norm1.bias").as<float>(), 1e-6f, lnp_at(c0), Mc, stream, lnpl, nullptr, 0, xt);
-        if (tn.qkv_attn_split && lnpl == 2) {   // one launch: the attention of a (crop, head) is the epilogue of its 128 x 192 qkv tile
-          const Linear& L = pq.at(p + "qkv_hm");
-          range_tag("parseq." + p + "attn (qkv + attention)");
-          // executed flops: qkv on pairs (x 3), Q K^T on a triple and a pair (x 4), P V on pairs (x 3)
-          const double qa = 2.0 * Mc * 3 * E * E, aa = 2.0 * 2 * nc * 6 * 128.0 * 128 * 64;
-          timed("enc.qkv+attention: gemm_sp_kernel<128,192,NP=3,EPI=1>", qa + aa, qa * 3 + aa * 3.5,
-                [&] { launch_qkv_attn_split(lnp_at(c0), L.ws.p, L.b.as<float>(), L.inv_scale, attp, nc, stream, tn.sp_tiled_w ? L.wst.p : nullptr, xt, xt); });
-        } else {
+  void* patches = pq_buf(kWsPatches, (size_t)M * patch_ld * es);
+  w.x = pq_buf<float>(kWsX, (size_t)M * E * 4);
+  w.t384 = pq_buf(kWsT384, (size_t)std::max(M, N * 26) * E * es);
+  w.tbig = pq_buf(kWsTbig, (size_t)M * 1536 * es);
+  w.att = pq_buf(kWsAtt, (size_t)std::max(M, N * 26) * E * es);
+  launch_patchify(prec, p.crops, patches, N, patch_ld, stream);
+  gemm(pq.at("patch"), patches, M, nullptr, 0, kActNone, w.x, E, pqf.at("encoder.pos_embed").as<float>(), E, 128);
+  if (enc_split()) encoder_split(N, w);
+  else encoder_plain(N, w);
+  w.kvmem = pq_buf(kWsKvmem, (size_t)M * 768 * es);
+  if (enc_split()) {
+    const int rows_max = (int)((((size_t)1 << 31) - 1) / ((size_t)E * 6));
+    for (int r0 = 0; r0 < M; r0 += rows_max) {
+      const int rr = std::min(rows_max, M - r0);
+      sgemm(pq.at("cross_kv"), (char*)w.ln_planes + (size_t)r0 * E * 6, rr, (char*)w.kvmem + (size_t)r0 * 768 * 4, 768, kActNone, 0);
+    }
+  } else gemm(pq.at("cross_kv"), w.t384, M, w.kvmem, 768, kActNone);
+}
+
+// split-operand engines: LayerNorm, GEMM epilogues and the attention kernel hand each other planes (split.h); only the residual
+// stream x is fp32.  Crop groups keep the widest planes tensor (the MLP hidden: 1536 x 6 bytes per row) inside the 2 GiB window.
+void Engine::encoder_split(int N, PqWork& w) {
+  const int M = N * 128, E = 384;
+  int CHS = std::max(1, std::min(N, (int)((((size_t)1 << 31) - 1) / ((size_t)128 * 1536 * 6))));
+  if (tn.enc_chunk > 0) CHS = std::min(CHS, tn.enc_chunk);   // (experiment knob: crop groups whose residual stream and LayerNorm planes stay in the Infinity Cache)
+  if (N > CHS) { const int groups = (N + CHS - 1) / CHS; CHS = (N + groups - 1) / groups; }   // even groups: 2560 crops = 1280 + 1280, not 1820 + 740
+  void* lnp = w.ln_planes = pq_buf(kWsLnPlanes, (size_t)M * E * 6);                    // LayerNorm output planes (whole batch: the memory at the end)
+  void* bigp = pq_buf(kWsBigPlanes, (size_t)std::min(N, CHS) * 128 * 1536 * 6);        // qkv / MLP hidden planes
+  void* attp = pq_buf(kWsAttPlanes, (size_t)std::min(N, CHS) * 128 * E * 6);           // attention output planes
+  auto lnp_at = [&](int c0) { return (char*)lnp + (size_t)c0 * 128 * E * 6; };
+  const int lnpl = tn.enc_ln_pairs ? 2 : 3;        // planes of the LayerNorm outputs that feed qkv / fc1 (pairs: three MFMAs per product there)
+  // the planes the encoder's GEMMs hand each other as their loaders' 1-KiB pieces (ConvParams::x_tiled): a wave instruction of the LDS-DMA fetches one
+  // contiguous KiB instead of eight 128-byte rows 1.5 - 6 KB apart - 71 against 31 GB/s per CU for a lone four-wave workgroup (tools/micro/dma_depth.hip)
+  // (measured: the recogniser pass at 1280 crops 34.96 -> 34.22 ms; a single page's 40 crops unchanged.  Groups small enough for the skinny projection keep the rows.)
+  const int xt = tn.sp_tiled_x && tn.qkv_attn_split && lnpl == 2 && tn.enc_fc2_pairs && std::min(CHS, N) * 128 > tn.skinny_max_rows ? 1 : 0;
+  for (int c0 = 0; c0 < N; c0 += CHS) {
+    const int nc = std::min(CHS, N - c0), Mc = nc * 128;
+    float* xc = w.x + (size_t)c0 * 128 * E;
+    for (int l = 0; l < 12; ++l) {
+      const std::string p = "encoder.blocks." + std::to_string(l) + ".";
+      range_scope = p;
+      range_tag("parseq." + p + "norm1");
+      launch_layernorm_planes(xc, E, pqf.at(p + "norm1.weight").as<float>(), pqf.at(p + "norm1.bias").as<float>(), 1e-6f, lnp_at(c0), Mc, stream, lnpl, nullptr, 0, xt);
+      if (tn.qkv_attn_split && lnpl == 2) {   // one launch: the attention of a (crop, head) is the epilogue of its 128 x 192 qkv tile
+        const Linear& L = pq.at(p + "qkv_hm");
+        range_tag("parseq." + p + "attn (qkv + attention)");
+        // executed flops: qkv on pairs (x 3), Q K^T on a triple and a pair (x 4), P V on pairs (x 3)
+        const double qa = 2.0 * Mc * 3 * E * E, aa = 2.0 * 2 * nc * 6 * 128.0 * 128 * 64;
+        timed("enc.qkv+attention: gemm_sp_kernel<128,192,NP=3,EPI=1>", qa + aa, qa * 3 + aa * 3.5,
+              [&] { launch_qkv_attn_split(lnp_at(c0), L.ws.p, L.b.as<float>(), L.inv_scale, attp, nc, stream, tn.sp_tiled_w ? L.wst.p : nullptr, xt, xt); });
+      } else {
         sgemm(pq.at(p + "qkv"), lnp_at(c0), Mc, bigp, 3 * E, kActNone, 1, nullptr, 0, nullptr, 0, lnpl + 1, 0, tn.qkv_kv_pairs ? E : 0, "enc.qkv");   // (K, V: read as pairs)
         range_tag("parseq." + p + "attn.qkv"), launch_attn_enc_split(bigp, attp, nc, stream);
-        }
-        sgemm(pq.at(p + "proj"), attp, Mc, nullptr, 0, kActNone, 0, xc, E, xc, E, 4, 0, 0, "enc.proj", xt, 0);
-        range_tag("parseq." + p + "norm2");
-        launch_layernorm_planes(xc, E, pqf.at(p + "norm2.weight").as<float>(), pqf.at(p + "norm2.bias").as<float>(), 1e-6f, lnp_at(c0), Mc, stream, lnpl, nullptr, 0, xt);
-        const int hpl = tn.enc_fc2_pairs ? 2 : 3;                                      // planes of the MLP's hidden activation
-        const int hx = xt && tn.sp_hidden16 && hpl == 2 ? 2 : xt;                       // layout of the hidden planes (ConvParams::out_tiled / x_tiled)
-        sgemm(pq.at(p + "fc1"), lnp_at(c0), Mc, bigp, 4 * E, kActGelu, hpl, nullptr, 0, nullptr, 0, lnpl + 1, 0, 0, "enc.fc1 + GELU", xt, hx);
-        sgemm(pq.at(p + "fc2"), bigp, Mc, nullptr, 0, kActNone, 0, xc, E, xc, E, hpl + 1, 0, 0, "enc.fc2", hx, 0);
       }
-      range_scope.clear();
-      range_tag("parseq.encoder.norm");
-      launch_layernorm_planes(xc, E, pqf.at("encoder.norm.weight").as<float>(), pqf.at("encoder.norm.bias").as<float>(), 1e-6f, lnp_at(c0), Mc, stream);
+      sgemm(pq.at(p + "proj"), attp, Mc, nullptr, 0, kActNone, 0, xc, E, xc, E, 4, 0, 0, "enc.proj", xt, 0);
+      range_tag("parseq." + p + "norm2");
+      launch_layernorm_planes(xc, E, pqf.at(p + "norm2.weight").as<float>(), pqf.at(p + "norm2.bias").as<float>(), 1e-6f, lnp_at(c0), Mc, stream, lnpl, nullptr, 0, xt);
+      const int hpl = tn.enc_fc2_pairs ? 2 : 3;                                      // planes of the MLP's hidden activation
+      const int hx = xt && tn.sp_hidden16 && hpl == 2 ? 2 : xt;                       // layout of the hidden planes (ConvParams::out_tiled / x_tiled)
+      sgemm(pq.at(p + "fc1"), lnp_at(c0), Mc, bigp, 4 * E, kActGelu, hpl, nullptr, 0, nullptr, 0, lnpl + 1, 0, 0, "enc.fc1 + GELU", xt, hx);
+      sgemm(pq.at(p + "fc2"), bigp, Mc, nullptr, 0, kActNone, 0, xc, E, xc, E, hpl + 1, 0, 0, "enc.fc2", hx, 0);
     }
+    range_scope.clear();
+    range_tag("parseq.encoder.norm");
+    launch_layernorm_planes(xc, E, pqf.at("encoder.norm.weight").as<float>(), pqf.at("encoder.norm.bias").as<float>(), 1e-6f, lnp_at(c0), Mc, stream);
   }
-  // The 12 encoder blocks run over groups of crops so that a group's widest intermediates (qkv, the MLP hidden) are
-  // re-read from the 256 MiB Infinity Cache rather than from HBM (tn.enc_chunk crops per group; 0 = one group).
+}
+
+// bf16 and fp32 engines.  The 12 encoder blocks run over groups of crops so that a group's widest intermediates (qkv, the MLP hidden) are
+// re-read from the 256 MiB Infinity Cache rather than from HBM (tn.enc_chunk crops per group; 0 = one group).
+void Engine::encoder_plain(int N, PqWork& w) {
+  const int M = N * 128, E = 384;
+  float* const x = w.x;
+  void *const t384 = w.t384, *const tbig = w.tbig, *const att = w.att;
   // the fused MLP block needs a panel of 128 rows per CU to fill the chip: below ~2 panels per CU the separate GEMMs win
   const bool mlp_fused = prec == kBF16 && gemm_config() >= 0 && (tn.mlp_fused == 2 || (tn.mlp_fused == 1 && M >= tn.mlp_min_rows));
   const int CH = (tn.enc_chunk > 0 && !mlp_fused) ? tn.enc_chunk : N;
-  for (int c0 = 0; c0 < N && !enc_split; c0 += CH) {
+  for (int c0 = 0; c0 < N; c0 += CH) {
     const int nc = std::min(CH, N - c0), Mc = nc * 128;
     float* xc = x + (size_t)c0 * 128 * E;
     if (mlp_fused) ln(xc, "encoder.blocks.0.norm1", 1e-6f, t384, Mc);
@@ -272,76 +303,68 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
       gemm(pq.at(p + "fc2"), tbig, Mc, nullptr, 0, kActNone, xc, E, xc, E, 0);
     }
   }
-  if (!mlp_fused && !enc_split) ln(x, "encoder.norm", 1e-6f, t384, M);       // memory
-  void* kvmem = (pq_ws[5].ensure((size_t)M * 768 * es), pq_ws[5].p);
-  if (enc_split) {
-    const int rows_max = (int)((((size_t)1 << 31) - 1) / ((size_t)E * 6));
-    for (int r0 = 0; r0 < M; r0 += rows_max) {
-      const int rr = std::min(rows_max, M - r0);
-      sgemm(pq.at("cross_kv"), (char*)pq_ws[11].p + (size_t)r0 * E * 6, rr, (char*)kvmem + (size_t)r0 * 768 * 4, 768, kActNone, 0);
-    }
-  } else
-  gemm(pq.at("cross_kv"), t384, M, kvmem, 768, kActNone);
+  if (!mlp_fused) ln(x, "encoder.norm", 1e-6f, t384, M);       // memory
+}
 
-  // ---- decoder
-  range_scope = "decoder.";
-  struct ScopeReset { std::string& s; ~ScopeReset() { s.clear(); } } scope_reset{range_scope};
-  void* kvcache = (pq_ws[6].ensure((size_t)N * 26 * 768 * es), pq_ws[6].p);
-  if (kvcache_zeroed != pq_ws[6].cap) {   // slots behind an early exit keep older (finite) rows; they are masked, but 0 x NaN is not 0
-    TTR_HIP_CHECK(hipMemsetAsync(kvcache, 0, pq_ws[6].cap, stream));
-    kvcache_zeroed = pq_ws[6].cap;
+// the fused persistent AR kernel's arguments (dec_fused.hip): all steps, or - first_step set by the caller - the AR loop's tail
+DecArParams Engine::dec_ar_params(const RecPass& p, const PqWork& w) {
+  DecArParams q{};
+  const std::string d = "decoder.layers.0.";
+  auto W = [&](const char* k) { return pq.at(k).w.as<bf16>(); };
+  auto Bv = [&](const char* k) { return pq.at(k).b.as<float>(); };
+  auto V = [&](const std::string& k) { return pqf.at(k).as<float>(); };
+  q.w_selfkv = W("self_kv"); q.w_selfout = W("self_out"); q.w_crossq = W("cross_q"); q.w_crossout = W("cross_out");
+  q.w_ffn1 = W("ffn1"); q.w_ffn2 = W("ffn2"); q.w_head = W("head");
+  q.b_selfkv = Bv("self_kv"); q.b_selfout = Bv("self_out"); q.b_crossq = Bv("cross_q"); q.b_crossout = Bv("cross_out");
+  q.b_ffn1 = Bv("ffn1"); q.b_ffn2 = Bv("ffn2"); q.b_head = Bv("head");
+  q.emb = w.emb; q.posq = w.posq; q.qself = qself.as<float>();
+  q.g_c = w.gc; q.b_c = w.bc;
+  q.g_1 = V(d + "norm1.weight"); q.b_1 = V(d + "norm1.bias"); q.g_2 = V(d + "norm2.weight"); q.b_2 = V(d + "norm2.bias");
+  q.g_f = V("decoder.norm.weight"); q.b_f = V("decoder.norm.bias");
+  q.kvmem = (const bf16*)w.kvmem; q.kvcache = (bf16*)w.kvcache; q.tokens = w.tk; q.ar_logits = p.ar;
+  q.gelu_lut = gelu_lut_for_current_device();
+  q.dbg = g_dec_dbg;
+  q.N = p.N; q.nsteps = w.nsteps;
+  return q;
+}
+
+// ---- decoder, AR steps: the K/V cache of the 26 positions and the tokens the refinement pass reads
+void Engine::parseq_ar(const RecPass& p, PqWork& w) {
+  const int N = p.N, E = 384;
+  const PatDev* const pt = p.pat.delta ? &p.pat : nullptr;
+  void* const kvcache = w.kvcache = pq_buf(kWsKvcache, (size_t)N * 26 * 768 * es);
+  if (kvcache_zeroed != pq_ws[kWsKvcache].cap) {   // slots behind an early exit keep older (finite) rows; they are masked, but 0 x NaN is not 0
+    TTR_HIP_CHECK(hipMemsetAsync(kvcache, 0, pq_ws[kWsKvcache].cap, stream));
+    kvcache_zeroed = pq_ws[kWsKvcache].cap;
   }
-  float* tgt = (float*)(pq_ws[7].ensure((size_t)N * 26 * E * 4), pq_ws[7].p);
-  void* d384b = (pq_ws[8].ensure((size_t)N * 26 * E * es), pq_ws[8].p);
-  void* d1536 = (pq_ws[9].ensure((size_t)N * 26 * 1536 * es), pq_ws[9].p);
-  float* step_logits = (float*)(pq_ws[10].ensure((size_t)N * 26 * 95 * 4), pq_ws[10].p);
-  // split-operand engines: the decoder's layers hand each other planes (decoder_tail_split)
-  const bool dec_split = prec == kSplit && tn.split_gemm && tn.split_planes && tn.dec_planes;
-  void *dpa = nullptr, *dpb = nullptr, *dp1536 = nullptr, *dsa = nullptr;
-  if (dec_split) {
-    dpa = (pq_ws[14].ensure((size_t)N * 26 * E * 6), pq_ws[14].p); dpb = (pq_ws[15].ensure((size_t)N * 26 * E * 6), pq_ws[15].p);
-    dp1536 = (pq_ws[16].ensure((size_t)N * 26 * 1536 * 6), pq_ws[16].p); dsa = (pq_ws[17].ensure((size_t)N * 26 * E * 6), pq_ws[17].p);
+  w.tgt = pq_buf<float>(kWsTgt, (size_t)N * 26 * E * 4);
+  w.d384b = pq_buf(kWsD384b, (size_t)N * 26 * E * es);
+  w.d1536 = pq_buf(kWsD1536, (size_t)N * 26 * 1536 * es);
+  float* step_logits = pq_buf<float>(kWsStepLogits, (size_t)N * 26 * 95 * 4);
+  if (dec_split()) {
+    w.dpa = pq_buf(kWsDecPlanesA, (size_t)N * 26 * E * 6); w.dpb = pq_buf(kWsDecPlanesB, (size_t)N * 26 * E * 6);
+    w.dp1536 = pq_buf(kWsDecPlanes1536, (size_t)N * 26 * 1536 * 6); w.dsa = pq_buf(kWsDecPlanesSa, (size_t)N * 26 * E * 6);
   }
   tokens.ensure((size_t)N * 26 * 4);
-  int* tk = tokens.as<int>();
+  int* const tk = w.tk = tokens.as<int>();
   launch_fill_i32(tk, 96, N * 26, 1, stream);   // PAD
   launch_fill_i32(tk, 95, N, 26, stream);       // BOS at position 0
-  const float* emb = pqf.at("text_embed.embedding.weight").as<float>();
-  const float* posq = pqf.at("pos_queries").as<float>();
-  const std::string d = "decoder.layers.0.";
-  const float* gc = pqf.at(d + "norm_c.weight").as<float>();
-  const float* bc = pqf.at(d + "norm_c.bias").as<float>();
-  float* ar = d_ar ? d_ar : step_logits;
-  const int nsteps = d_ar ? 26 : 25;  // the 26th AR step only feeds logits the refinement pass discards
+  const float* const emb = w.emb = pqf.at("text_embed.embedding.weight").as<float>();
+  const float* const posq = w.posq = pqf.at("pos_queries").as<float>();
+  const float* const gc = w.gc = pqf.at("decoder.layers.0.norm_c.weight").as<float>();
+  const float* const bc = w.bc = pqf.at("decoder.layers.0.norm_c.bias").as<float>();
+  float* const ar = w.ar = p.ar ? p.ar : step_logits;
+  const int nsteps = w.nsteps = p.ar ? 26 : 25;  // the 26th AR step only feeds logits the refinement pass discards
   // Fused persistent AR kernel (dec_fused.hip): ~150 us per step whatever N is (every workgroup is bound by its own
   // ~12 B/clk fetch rate on the weight and K/V streams).  With the skinny per-step GEMMs (gemm_sk.hip) the kernel-per-op
   // loop is faster up to ~1200 crops (measured at 40 / 320 / 614 crops), so the fused kernel is only picked beyond that.
-  const bool fused_ar = prec == kBF16 && tn.decoder_mode != 0 && (tn.decoder_mode == 4 || tn.decoder_mode == 8 || tn.decoder_mode == 16 || N > 2048);
-  auto dec_params = [&]() {
-    DecArParams q{};
-    auto W = [&](const char* k) { return pq.at(k).w.as<bf16>(); };
-    auto Bv = [&](const char* k) { return pq.at(k).b.as<float>(); };
-    auto V = [&](const std::string& k) { return pqf.at(k).as<float>(); };
-    q.w_selfkv = W("self_kv"); q.w_selfout = W("self_out"); q.w_crossq = W("cross_q"); q.w_crossout = W("cross_out");
-    q.w_ffn1 = W("ffn1"); q.w_ffn2 = W("ffn2"); q.w_head = W("head");
-    q.b_selfkv = Bv("self_kv"); q.b_selfout = Bv("self_out"); q.b_crossq = Bv("cross_q"); q.b_crossout = Bv("cross_out");
-    q.b_ffn1 = Bv("ffn1"); q.b_ffn2 = Bv("ffn2"); q.b_head = Bv("head");
-    q.emb = emb; q.posq = posq; q.qself = qself.as<float>();
-    q.g_c = gc; q.b_c = bc;
-    q.g_1 = V(d + "norm1.weight"); q.b_1 = V(d + "norm1.bias"); q.g_2 = V(d + "norm2.weight"); q.b_2 = V(d + "norm2.bias");
-    q.g_f = V("decoder.norm.weight"); q.b_f = V("decoder.norm.bias");
-    q.kvmem = (const bf16*)kvmem; q.kvcache = (bf16*)kvcache; q.tokens = tk; q.ar_logits = d_ar;
-    q.gelu_lut = gelu_lut_for_current_device();
-    q.dbg = g_dec_dbg;
-    q.N = N; q.nsteps = nsteps;
-    return q;
-  };
-  if (fused_ar) {
-    DecArParams q = dec_params();
+  if (prec == kBF16 && tn.decoder_mode != 0 && (tn.decoder_mode == 4 || tn.decoder_mode == 8 || tn.decoder_mode == 16 || N > 2048)) {
+    DecArParams q = dec_ar_params(p, w);
     int G = tn.decoder_mode;
     if (G != 4 && G != 8 && G != 16) G = N <= 1024 ? 4 : 8;
     launch_dec_ar(q, G, stream);
-  } else {
+    return;
+  }
   prof_stage = 2;
   const bool tok_fuse = tn.tok_fuse && tn.ln_fuse && prec == kBF16 && N <= skinny_max_rows();
   // upstream PARSeq leaves its AR loop once every crop of the batch has emitted EOS (system.py): the bf16 engine counts them in the skinny
@@ -352,7 +375,7 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
   if (early) {
     ar_done.ensure(64);
     TTR_HIP_CHECK(hipMemsetAsync(ar_done.p, 0, 4, stream));
-    if (d_ar) TTR_HIP_CHECK(hipMemsetAsync(d_ar, 0, (size_t)N * 26 * 95 * 4, stream));   // steps behind the exit stay zero
+    if (p.ar) TTR_HIP_CHECK(hipMemsetAsync(p.ar, 0, (size_t)N * 26 * 95 * 4, stream));   // steps behind the exit stay zero
     cur_skip = ar_done.as<int>(); cur_skip_n = N;
   }
   // with the early exit, the steps from ar_tail_step on are ONE launch of the fused kernel in its tail form: when every crop
@@ -362,60 +385,60 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
   int pend_argmax = -1;   // AR step whose logits still await their argmax (dec_embed_ln of the next step takes it)
   for (int i = 0; i < 26; ++i) {
     if (i == tail_at) {
-      DecArParams q = dec_params();
+      DecArParams q = dec_ar_params(p, w);
       q.first_step = i; q.prev_logits = ar + (size_t)(i - 1) * 95; q.prev_ld = 26 * 95; q.skip = cur_skip; q.skip_n = cur_skip_n;
-      if (!d_ar) q.ar_logits = nullptr;
+      if (!p.ar) q.ar_logits = nullptr;
       launch_dec_ar(q, N <= 1024 ? 4 : 8, stream);
       break;
     }
     if (tok_fuse) {   // token of step i = argmax of step i-1's logits, embedded and normalised in the GEMM's loader
       const Linear& L = pq.at("self_kv");
-      ConvParams p{};
-      p.ln_in = emb; p.ln_ld = 384; p.ln_gamma = gc; p.ln_beta = bc; p.ln_eps = 1e-5f;
-      p.tok = tk; p.tok_ld = 26; p.tok_col = i; p.tok_emb = emb; p.tok_max = 96;
-      if (i > 0) { p.tok_logits = ar + (size_t)(i - 1) * 95; p.tok_logits_ld = 26 * 95; p.tok_C = 95; p.tok_pos = posq + (size_t)(i - 1) * E; }
-      if (early) { p.skip = cur_skip; p.skip_n = cur_skip_n; p.done_count = ar_done.as<int>(); p.tok_eos = 0; }
-      p.C0 = L.k; p.B = 1; p.H = 1; p.W = N; p.ks = 1; p.dil = 1;
-      p.wgt = L.w.p; p.bias = L.b.as<float>();
-      p.out = (char*)kvcache + (size_t)i * 768 * es; p.out_ld = 26 * 768;
-      p.Cout = L.cout; p.M = N; p.act = kActNone;
-      igemm(p, 2.0 * N * L.cout * L.k);
-    } else if (dec_split && tn.embed_fold && tn.skinny_split && N <= 256) {
+      ConvParams c{};
+      c.ln_in = emb; c.ln_ld = 384; c.ln_gamma = gc; c.ln_beta = bc; c.ln_eps = 1e-5f;
+      c.tok = tk; c.tok_ld = 26; c.tok_col = i; c.tok_emb = emb; c.tok_max = 96;
+      if (i > 0) { c.tok_logits = ar + (size_t)(i - 1) * 95; c.tok_logits_ld = 26 * 95; c.tok_C = 95; c.tok_pos = posq + (size_t)(i - 1) * E; }
+      if (early) { c.skip = cur_skip; c.skip_n = cur_skip_n; c.done_count = ar_done.as<int>(); c.tok_eos = 0; }
+      c.C0 = L.k; c.B = 1; c.H = 1; c.W = N; c.ks = 1; c.dil = 1;
+      c.wgt = L.w.p; c.bias = L.b.as<float>();
+      c.out = (char*)kvcache + (size_t)i * 768 * es; c.out_ld = 26 * 768;
+      c.Cout = L.cout; c.M = N; c.act = kActNone;
+      igemm(c, 2.0 * N * L.cout * L.k);
+    } else if (dec_split() && tn.embed_fold && tn.skinny_split && N <= 256) {
       // a page's worth of crops: token (or the pending argmax) -> embedding -> norm_c -> self_kv as ONE skinny launch (gemm_skx.hip, token prologue)
       const Linear& L = pq.at("self_kv");
-      ConvParams p{};
-      p.tok = tk; p.tok_ld = 26; p.tok_col = i; p.tok_emb = emb; p.tok_max = 96; p.tok_pos = i > 0 ? posq + (size_t)(i - 1) * E : nullptr;
+      ConvParams c{};
+      c.tok = tk; c.tok_ld = 26; c.tok_col = i; c.tok_emb = emb; c.tok_max = 96; c.tok_pos = i > 0 ? posq + (size_t)(i - 1) * E : nullptr;
       if (pend_argmax >= 0) {
-        p.tok_logits = ar + (size_t)pend_argmax * 95; p.tok_logits_ld = 26 * 95; p.tok_C = 95; p.done_count = early ? ar_done.as<int>() : nullptr; p.tok_eos = 0; p.tok_mask = charset; p.tok_row_masks = row_masks;
+        c.tok_logits = ar + (size_t)pend_argmax * 95; c.tok_logits_ld = 26 * 95; c.tok_C = 95; c.done_count = early ? ar_done.as<int>() : nullptr; c.tok_eos = 0; c.tok_mask = p.mask; c.tok_row_masks = p.row_masks;
         pend_argmax = -1;
       }
-      p.ln_gamma = gc; p.ln_beta = bc; p.ln_eps = 1e-5f;
-      p.C0 = L.k; p.B = 1; p.H = 1; p.W = N; p.ks = 1; p.dil = 1;
-      p.wgt = L.ws.p; p.bias = L.b.as<float>(); p.split = 4; p.out_scale = L.inv_scale;
-      p.out = (char*)kvcache + (size_t)i * 768 * 4; p.out_ld = 26 * 768;
-      p.Cout = L.cout; p.M = N; p.act = kActNone;
-      p.skip = cur_skip; p.skip_n = cur_skip_n;
-      if (!gemm_skx_ln_eligible(p)) throw std::runtime_error("AR step: the token prologue does not take this shape");
-      timed("dec.embed + norm_c + self_kv (skinny)", 2.0 * N * L.cout * L.k, 2.0 * N * L.cout * L.k * 4, [&] { launch_gemm_skx(p, stream); });
-    } else if (dec_split) {
+      c.ln_gamma = gc; c.ln_beta = bc; c.ln_eps = 1e-5f;
+      c.C0 = L.k; c.B = 1; c.H = 1; c.W = N; c.ks = 1; c.dil = 1;
+      c.wgt = L.ws.p; c.bias = L.b.as<float>(); c.split = 4; c.out_scale = L.inv_scale;
+      c.out = (char*)kvcache + (size_t)i * 768 * 4; c.out_ld = 26 * 768;
+      c.Cout = L.cout; c.M = N; c.act = kActNone;
+      c.skip = cur_skip; c.skip_n = cur_skip_n;
+      if (!gemm_skx_ln_eligible(c)) throw std::runtime_error("AR step: the token prologue does not take this shape");
+      timed("dec.embed + norm_c + self_kv (skinny)", 2.0 * N * L.cout * L.k, 2.0 * N * L.cout * L.k * 4, [&] { launch_gemm_skx(c, stream); });
+    } else if (dec_split()) {
       if (pend_argmax >= 0) {   // column i's token = argmax of step i - 1's logits, found by this kernel's waves (one launch less per step)
-        launch_dec_embed_ln(prec, tk, emb, posq, gc, bc, 1e-5f, dpa, N, i, i + 1, stream, cur_skip, cur_skip_n, 3,
-                            ar + (size_t)pend_argmax * 95, 26 * 95, 95, early ? ar_done.as<int>() : nullptr, 0, charset, row_masks);
+        launch_dec_embed_ln(prec, tk, emb, posq, gc, bc, 1e-5f, w.dpa, N, i, i + 1, stream, cur_skip, cur_skip_n, 3,
+                            ar + (size_t)pend_argmax * 95, 26 * 95, 95, early ? ar_done.as<int>() : nullptr, 0, p.mask, p.row_masks);
         pend_argmax = -1;
-      } else launch_dec_embed_ln(prec, tk, emb, posq, gc, bc, 1e-5f, dpa, N, i, i + 1, stream, cur_skip, cur_skip_n, 3);
-      sgemm(pq.at("self_kv"), dpa, N, (char*)kvcache + (size_t)i * 768 * 4, 26 * 768, kActNone, 0);
+      } else launch_dec_embed_ln(prec, tk, emb, posq, gc, bc, 1e-5f, w.dpa, N, i, i + 1, stream, cur_skip, cur_skip_n, 3);
+      sgemm(pq.at("self_kv"), w.dpa, N, (char*)kvcache + (size_t)i * 768 * 4, 26 * 768, kActNone, 0);
     } else {
-      launch_dec_embed_ln(prec, tk, emb, posq, gc, bc, 1e-5f, t384, N, i, i + 1, stream, cur_skip, cur_skip_n);
-      gemm(pq.at("self_kv"), t384, N, (char*)kvcache + (size_t)i * 768 * es, 26 * 768, kActNone);
+      launch_dec_embed_ln(prec, tk, emb, posq, gc, bc, 1e-5f, w.t384, N, i, i + 1, stream, cur_skip, cur_skip_n);
+      gemm(pq.at("self_kv"), w.t384, N, (char*)kvcache + (size_t)i * 768 * es, 26 * 768, kActNone);
     }
     if (i >= nsteps) break;
     const int* crop_done = early && tn.ar_early_exit >= 1 && tn.ar_crop_exit ? tk : nullptr;
-    if (dec_split) {
-      launch_dec_self_attn(prec, qself.as<float>(), kvcache, tk, dsa, N, 1, i, 0, stream, cur_skip, cur_skip_n, 3);
-      decoder_tail_split(dsa, N, 1, posq + (size_t)i * E, 1, tgt, dpa, dpb, dp1536, (float*)d384b, t384, kvmem, ar + (size_t)i * 95, 26 * 95, crop_done, i);
+    if (dec_split()) {
+      launch_dec_self_attn(prec, qself.as<float>(), kvcache, tk, w.dsa, N, 1, i, 0, stream, cur_skip, cur_skip_n, 3);
+      decoder_tail_split(w.dsa, N, 1, posq + (size_t)i * E, 1, w.tgt, w.dpa, w.dpb, w.dp1536, (float*)w.d384b, w.t384, w.kvmem, ar + (size_t)i * 95, 26 * 95, crop_done, i);
     } else {
-    launch_dec_self_attn(prec, qself.as<float>(), kvcache, tk, att, N, 1, i, 0, stream, cur_skip, cur_skip_n);
-    decoder_tail(att, N, 1, posq + (size_t)i * E, 1, tgt, t384, d384b, d1536, kvmem, ar + (size_t)i * 95, 26 * 95, crop_done, i);
+      launch_dec_self_attn(prec, qself.as<float>(), kvcache, tk, w.att, N, 1, i, 0, stream, cur_skip, cur_skip_n);
+      decoder_tail(w.att, N, 1, posq + (size_t)i * E, 1, w.tgt, w.t384, w.d384b, w.d1536, w.kvmem, ar + (size_t)i * 95, 26 * 95, crop_done, i);
     }
     // the latency regime (a page or two of crops): every remaining step is ~11 launches that return at once when the batch is done - half a
     // millisecond of them for ten-character words.  The host looks at the counter (one small synchronous read) and stops enqueuing instead
@@ -423,8 +446,8 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
     if (i + 1 < 26 && !tok_fuse) {
       // the step's argmax: its own launch where the host is about to look at the counter (or nothing follows), else left to the next step's first kernel
       if (pt) launch_argmax_pat(ar + (size_t)i * 95, 26 * 95, 95, tk, 26, i + 1, N, stream, cur_skip, cur_skip_n, early ? ar_done.as<int>() : nullptr, 0, *pt, pat_state.as<int>());   // (never folded: the folded kernels know no automaton)
-      else if (dec_split && tn.argmax_fold && !host_check) pend_argmax = i;
-      else launch_argmax(ar + (size_t)i * 95, 26 * 95, 95, tk, 26, i + 1, N, stream, cur_skip, cur_skip_n, early ? ar_done.as<int>() : nullptr, 0, charset, row_masks);
+      else if (dec_split() && tn.argmax_fold && !host_check) pend_argmax = i;
+      else launch_argmax(ar + (size_t)i * 95, 26 * 95, 95, tk, 26, i + 1, N, stream, cur_skip, cur_skip_n, early ? ar_done.as<int>() : nullptr, 0, p.mask, p.row_masks);
     }
     if (host_check) {
       h_ar_done.ensure(64);
@@ -435,22 +458,28 @@ void Engine::parseq_forward(const uint8_t* d_crops, int N, float* d_logits, floa
   }
   cur_skip = nullptr; cur_skip_n = 0;
   prof_stage = 1;
-  }
-  // ---- refinement pass (cloze mask + EOS key padding), R = 26 query rows per crop
-  if (dec_split) {
-    launch_dec_self_attn(prec, qself.as<float>(), kvcache, tk, dsa, N, 26, 0, 1, stream, nullptr, 0, 3);
-    decoder_tail_split(dsa, N, 26, posq, 26, tgt, dpa, dpb, dp1536, (float*)d384b, t384, kvmem, d_logits, 95);
+}
+
+// ---- decoder, refinement pass (cloze mask + EOS key padding), R = 26 query rows per crop: the pass's logits
+void Engine::parseq_refine(const RecPass& p, PqWork& w) {
+  const int N = p.N;
+  if (dec_split()) {
+    launch_dec_self_attn(prec, qself.as<float>(), w.kvcache, w.tk, w.dsa, N, 26, 0, 1, stream, nullptr, 0, 3);
+    decoder_tail_split(w.dsa, N, 26, w.posq, 26, w.tgt, w.dpa, w.dpb, w.dp1536, (float*)w.d384b, w.t384, w.kvmem, p.logits, 95);
   } else {
-  launch_dec_self_attn(prec, qself.as<float>(), kvcache, tk, att, N, 26, 0, 1, stream);
-  decoder_tail(att, N, 26, posq, 26, tgt, t384, d384b, d1536, kvmem, d_logits, 95);
+    launch_dec_self_attn(prec, qself.as<float>(), w.kvcache, w.tk, w.att, N, 26, 0, 1, stream);
+    decoder_tail(w.att, N, 26, w.posq, 26, w.tgt, w.t384, w.d384b, w.d1536, w.kvmem, p.logits, 95);
   }
-  if (pt) launch_decode_pat(d_logits, N, d_ids, d_prob, d_conf, stream, *pt);           // ... under a pattern: the same, walked position by position through the automaton (pattern.hip)
-  else
-  launch_decode_conf(d_logits, N, d_ids, d_prob, d_conf, stream, charset, row_masks);   // the final argmax with each id's probability and the word's confidence (decode_conf.hip)
+}
+
+// ---- the final decode, from the pass's logits alone
+void Engine::parseq_decode(const RecPass& p) {
+  if (p.pat.delta) launch_decode_pat(p.logits, p.N, p.out.ids, p.out.prob, p.out.conf, stream, p.pat);   // under a pattern: walked position by position through the automaton (pattern.hip)
+  else launch_decode_conf(p.logits, p.N, p.out.ids, p.out.prob, p.out.conf, stream, p.mask, p.row_masks);   // the final argmax with each id's probability and the word's confidence (decode_conf.hip)
   // character alternatives (DESIGN.md "Character alternatives"): the K best allowed classes of every position, from the same logits, mask and standard block
-  if (alts && d_alt_ids && d_alt_prob) launch_decode_alts(d_logits, N, d_ids, d_prob, alts, d_alt_ids, d_alt_prob, stream, charset, row_masks);
+  if (p.with_alts()) launch_decode_alts(p.logits, p.N, p.out.ids, p.out.prob, p.alt.k, p.alt.ids, p.alt.prob, stream, p.mask, p.row_masks);
   // lexicon matching (DESIGN.md "Lexicon matching"): every word of the caller's list against every crop, from the same logits, mask and standard block
-  if (lex_v && lex) launch_lexicon(d_logits, N, d_ids, d_prob, lex_records.p, lex_v, lex_m, lex->idx, lex->logp, lex->part_idx, lex->part_logp, stream, charset, row_masks);
+  if (lex_v && p.with_lex()) launch_lexicon(p.logits, p.N, p.out.ids, p.out.prob, lex_records.p, lex_v, p.lex.m, p.lex.idx, p.lex.logp, p.lex.part_idx, p.lex.part_logp, stream, p.mask, p.row_masks);
 }
 
 }  // namespace ttr
