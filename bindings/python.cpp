@@ -29,6 +29,9 @@
 // include/tuatara_hip.h lists), set on the cached engine for the call and reset afterwards, also when the call raises; calls that share the engine take turns.
 // "pattern" is also a key of a regions= dict: that region's own.  A bad pattern raises ValueError, naming the offset or the character, before anything runs;
 // a pattern with orient, alts or lexicon raises ValueError too.  The dicts' keys do not change.
+// And a keyword-only pattern_best=False on both calls: True reads every word that has a pattern as the LIKELIEST member of its language under the
+// recogniser's per-position distributions (DESIGN.md "Patterns", best mode) and adds "pattern_logp" to every dict; the mode is set for the call and reset
+// afterwards, also when the call raises.  Without a pattern (the call's, a region's or TUATARA_PATTERN) it has no effect.
 // And a keyword-only wide=False on image_to_data: wide=True (a piece is at most 8 times as wide as high) or wide=A (2..64) reads words wider than that in
 // pieces cut at ink gaps and joins the readings (DESIGN.md "Wide words"); every dict gains "pieces", a list of {"text", "conf", "quad"} (one, the item itself,
 // for a word that is not wide).  It turns rectify on.  A value out of range raises RuntimeError before anything runs; wide with orient, chars, alts, lexicon,
@@ -53,7 +56,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
@@ -101,6 +104,7 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
     }
     d["pieces"] = ps;
   }
+  if (k.pattern_logp && item.has_pattern_logp) d["pattern_logp"] = item.pattern_logp;
   if (k.lexicon) {
     py::list l;
     for (const LexMatch& m : item.lexicon) l.append(py::make_tuple(m.word, std::exp((double)m.logp)));
@@ -226,7 +230,7 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
-                                      py::object pattern_kw, py::object wide_kw) {
+                                      py::object pattern_kw, py::object wide_kw, bool pattern_best) {
   const int orient = orient_mode(orient_kw);
   const float wide = wide_arg(wide_kw);
   alts_arg(alts);
@@ -238,6 +242,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   if (!pattern.empty() && (orient || alts || lex)) throw std::invalid_argument("pattern does not combine with orient, alts or lexicon");
   if (wide != 0.f && (orient || chars || alts || lex || !pattern.empty() || !regions_kw.is_none()))
     throw std::invalid_argument("wide does not combine with orient, chars, alts, lexicon, pattern or regions");
+  if (pattern_best && (orient || alts || lex || wide != 0.f)) throw std::invalid_argument("pattern_best does not combine with orient, alts, lexicon or wide");
   const bool cset = !allow.empty() || !deny.empty();
   lines = lines || blocks;   // blocks are made of lines
   if (wide != 0.f) {   // wide words: rectified crops, the engine's setting for the call
@@ -272,12 +277,13 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     {
       py::gil_scoped_release nogil;
       got = lex ? image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts, words, lexicon_m)
+                : pattern_best ? image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts, true)
                 : image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts);
     }
     if ((alts || lex || with_pattern) && got.empty()) raise_refused();
     py::list res;
     for (const auto& item : got) {
-      py::dict d = item_dict(item, Keys{true, conf, false, false, false, false, alts != 0, lex});
+      py::dict d = item_dict(item, Keys{true, conf, false, false, false, false, alts != 0, lex, false, pattern_best});
       d["region"] = item.region;
       res.append(d);
     }
@@ -291,7 +297,8 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   std::vector<OutputItemEx> items;
   {
     py::gil_scoped_release nogil;   // (orient = None: the 7-argument call, which leaves the orientation to TUATARA_ORIENT)
-    items = !pattern.empty() ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, pattern)
+    items = pattern_best     ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, pattern, true)
+            : !pattern.empty() ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, pattern)
             : lex    ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts, words, lexicon_m)
             : alts   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts)
             : cset   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny)
@@ -303,7 +310,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   }
   if ((alts || lex || !pattern.empty()) && items.empty()) raise_refused();
   py::list result;
-  for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex}));
+  for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best}));
   return result;
 }
 
@@ -313,7 +320,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
 // Keyword-only mixed_batches=False: True batches images that share one detector canvas, whatever their sizes (DESIGN.md "Mixed-size batches"); same results.
 static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf, py::object orient_kw,
                                        bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches, py::object allowlist, py::object blocklist, int alts,
-                                       py::object lexicon, int lexicon_m, py::object pattern_kw) {
+                                       py::object lexicon, int lexicon_m, py::object pattern_kw, bool pattern_best) {
   const int orient = orient_mode(orient_kw);
   alts_arg(alts);
   std::vector<std::string> words;
@@ -322,6 +329,7 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   charset_args(allowlist, blocklist, allow, deny);
   const std::string pattern = pattern_arg(pattern_kw, allow, deny);
   if (!pattern.empty() && (orient || alts || lex)) throw std::invalid_argument("pattern does not combine with orient, alts or lexicon");
+  if (pattern_best && (orient || alts || lex)) throw std::invalid_argument("pattern_best does not combine with orient, alts or lexicon");
   const bool cset = !allow.empty() || !deny.empty();
   lines = lines || blocks;   // blocks are made of lines
   std::vector<py::array_t<unsigned char, py::array::c_style | py::array::forcecast>> keep;   // contiguous uint8 views / copies, alive for the call
@@ -338,7 +346,8 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   std::vector<std::vector<OutputItemEx>> pages;
   {
     py::gil_scoped_release nogil;
-    pages = !pattern.empty() ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, pattern)
+    pages = pattern_best ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, pattern, true)
+            : !pattern.empty() ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, pattern)
             : lex ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts, words, lexicon_m)
             : alts ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts)
             : cset ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny)
@@ -353,7 +362,7 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   py::list result;
   for (const auto& items : pages) {
     py::list page;
-    for (const auto& item : items) page.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex}));
+    for (const auto& item : items) page.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best}));
     result.append(page);
   }
   return result;
@@ -363,8 +372,8 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("pattern_best") = false, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
 }

@@ -19,6 +19,9 @@
 //   ocr_cli --pattern P ...                                      in front of any form above: a regular expression every word must match (DESIGN.md "Patterns"),
 // e.g. --pattern '\d{2}/\d{2}/\d{4}' for dates.  It reaches the call as TUATARA_PATTERN; a bad pattern fails, naming the offset or the character, before the
 // image is read.
+//   ocr_cli --pattern P --pattern-best <image.png> <weights_dir> <outputs_dir>   in front of the plain form, with --pattern: reads every word as the LIKELIEST
+// member of the pattern's language (DESIGN.md "Patterns", best mode) and prints "x1 y1 x2 y2<TAB>text<TAB>logp" per item, logp being the log-probability of
+// the text under the recogniser's per-position distributions, to 6 decimals.
 //   ocr_cli --regions FILE <image.png> <weights_dir> <outputs_dir>   reads the regions FILE lists, with no detector, each under its own character set
 // (DESIGN.md "Regions and per-row character sets").  One region per line: "x0 y0 x1 y1 [allow [deny]]" - the pixels [x0, x1) x [y0, y1) - or eight floats
 // "tl.x tl.y tr.x tr.y br.x br.y bl.x bl.y [allow [deny]]"; '#' starts a comment.  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per region, in the file's
@@ -93,6 +96,16 @@ int main(int argc, const char** argv) {
       }
       setenv(opt == "--allowlist" ? "TUATARA_ALLOWLIST" : opt == "--blocklist" ? "TUATARA_BLOCKLIST" : "TUATARA_PATTERN", argv[2], 1);
       argv[2] = argv[0]; argv += 2; argc -= 2;
+    }
+    if (argc >= 2 && std::string(argv[1]) == "--pattern-best") {
+      if (argc != 5) throw std::runtime_error("--pattern-best goes in front of <image.png> <weights_dir> <outputs_dir>");
+      if (!std::getenv("TUATARA_PATTERN")) throw std::runtime_error("--pattern-best needs --pattern P in front of it");
+      pngdec::Image img = pngdec::read(argv[2]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[3], argv[4], false, -1, false, false,
+                                                         false, false, std::string(), std::string(), std::string(), true);
+      if (!last_call_error().empty()) return 1;                         // (the message is on stderr)
+      for (const OutputItemEx& it : items) printf("%g %g %g %g\t%s\t%.6f\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.text.c_str(), it.has_pattern_logp ? it.pattern_logp : -INFINITY);
+      return 0;
     }
     if (argc >= 2 && std::string(argv[1]) == "--wide") {
       float a = 8.f;
@@ -257,7 +270,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--pattern P] [--wide [A] | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

@@ -69,6 +69,8 @@ struct OutputItemEx {
   std::vector<float> alt_prob;     // [26][alt_k]: their probabilities, as ttr_result_alt_probs gives them
   std::vector<std::vector<CharAlt>> alternatives;   // one list per character of `text`: that position's character options in rank order, the character itself first unless another option ties it
   std::vector<LexMatch> lexicon;   // lexicon matching: the M best entries of the call's word list by (logp descending, index ascending); empty when no lexicon was given (DESIGN.md "Lexicon matching")
+  bool has_pattern_logp = false;   // patterns in best mode: the call read under a pattern as the likeliest member of its language (DESIGN.md "Patterns") ...
+  float pattern_logp = 0.f;        // ... and this is the log-probability of `text` under the recogniser's per-position distributions (-inf for an item without a pattern)
   std::vector<WordPiece> pieces;   // wide words: the item's pieces in order (one, the item itself, when it is not wide); empty when wide is off (DESIGN.md "Wide words")
   int block = -1, block_line = -1;  // text blocks: the item's block of its page, in reading order, and its line's position inside that block (what a caller sorts by: block, block_line, word); -1 when blocks are off (DESIGN.md "Text blocks")
 };
@@ -189,6 +191,18 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
 std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
                                                          bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
                                                          std::string allowlist, std::string blocklist, std::string pattern);
+// ... in best mode: pattern_best = true reads every word as the LIKELIEST member of the pattern's language under the recogniser's refined per-position
+// distributions, instead of the member a position-by-position walk reaches, and every item carries pattern_logp (has_pattern_logp set).  The mode is set on
+// the cached engine for the call and reset afterwards, also when the call fails.  pattern_best = false is the calls above, unless TUATARA_PATTERN_BEST=1 is
+// set in the environment, which turns the mode on for every call here that reads under a pattern.  It needs what a pattern needs.
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, std::string pattern, bool pattern_best);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist, std::string pattern, bool pattern_best);
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts, bool pattern_best);   // (each region under its own pattern)
 
 // Wide words (opt-in; DESIGN.md "Wide words"): a word whose quad is wider than wide.max_aspect times its height - a URL, an IBAN, a serial number - is cut
 // into pieces at the gaps between characters, every piece is read as a crop of its own in the same recogniser pass, and the readings are joined: `text` is

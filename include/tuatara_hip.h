@@ -459,7 +459,30 @@ int ttr_logits_confidence_sets(ttr_engine* e, const float* logits, int n, const 
  * the engine's own pattern (or none); each distinct (pattern, resolved mask) pair is compiled once into one table of at most 1024 states.  They refuse what
  * the region calls refuse, and a pattern index out of range, a bad pattern (naming the region) and a table over 1024 states (naming the total).
  * Stage twins: ttr_parseq_logits_patterns - ttr_parseq_logits_sets with patterns; ttr_logits_decode_patterns - the final decode under patterns alone, row
- * by row: host logits [n][26][95] -> ids, probs [n][26], conf [n] (set_of may be NULL: every row under the engine's set). */
+ * by row: host logits [n][26][95] -> ids, probs [n][26], conf [n] (set_of may be NULL: every row under the engine's set).
+ *
+ * The decode mode of patterns.  TTR_PATTERN_GREEDY (the default): the text is the one the choice rule above reaches position by position.
+ * TTR_PATTERN_BEST: the final decode of every row that has a pattern returns the LIKELIEST member of its language - at most 25 characters, under the row's
+ * character set - under the refined per-position distributions.  All fp32: lp[p][c] = (x[p][c] - x[p][id0[p]]) + logf(prob0[p]) for an allowed class, -inf
+ * for a blocked one, id0 / prob0 the masked argmax's block on these logits (the lexicon's table, ttr_logits_lexicon); score(w) = the sum in position order
+ * from 0.0f of lp[p][w_p], p < L, then + lp[L][0]; the returned w has the largest score by the recurrence V[0][start] = 0, V[p + 1][t] = max over (s, c >= 1,
+ * delta[s][c] == t) of V[p][s] + lp[p][c] (ties: lower class, then lower state), the end the maximum over (L <= 25, accepting s) of V[L][s] + lp[L][0]
+ * (ties: smaller L, then lower state); -inf and NaN are never chosen.  ids[0 .. L - 1] = w, ids[L] = 0, the positions behind hold the masked argmax; probs[p],
+ * p <= L, is expf(x[p][ids[p]] - max_A) / sum_A expf(x - max_A) over the set A the choice rule allows in the path's state - the greedy value 1 / sum where
+ * the class is the maximum; conf is the same sequential product (ttr_confidence_from_probs reproduces it).  A row without a pattern, or one in which no
+ * member has a finite score, keeps the greedy reading bit for bit.  Where the greedy reading is the likeliest member every bit is greedy mode's; always
+ * score(best) >= score(greedy).  The AR loop does not change: its tokens stay the greedy-constrained ones, so a pass's logits are the same bits in both modes
+ * and the best path is exact under distributions that were conditioned on the greedy context.
+ * ttr_engine_set_pattern_decode: the mode of every page entry point, ttr_parseq_logits and the region calls, fixed for a batch when its recogniser is
+ * enqueued; it fails, and changes nothing, for another value, while streamed batches are in flight, and for TTR_PATTERN_BEST on a bf16 engine; without a
+ * pattern in force it has no effect, and in greedy mode no launch, allocation, copy or bit differs from before.  ttr_pages_to_data_dev_sharded refuses best
+ * mode while a pattern is set.  ttr_result_pattern_logp: [count] floats - score of every item's reading, -inf for an item without a pattern - NULL unless the
+ * call ran in best mode with a pattern, and NULL for a result without items (a page on which nothing was found), as the other per-item views are; ttr_results_gather_pattern_logp: the same in ttr_results_gather's item order, -inf for the items of results without
+ * the view (logp may be NULL); returns the total.  ttr_logits_decode_patterns_best: ttr_logits_decode_patterns in best mode, whatever the engine's mode, and
+ * logp [n].  ttr_pattern_best_from_lp (host only, no engine): the recurrence on a given table lp [26][96] (row p = position p, column 0 = the end of the
+ * text, column 95 unused) -> path [26] (the L classes, zeros behind), *len = L, *logp = score; returns 0, 1 when no member has a finite score (path zeros,
+ * len -1, logp -inf), -1 for a null argument. */
+enum { TTR_PATTERN_GREEDY = 0, TTR_PATTERN_BEST = 1 };
 typedef struct ttr_pattern ttr_pattern;
 int ttr_pattern_compile(const char* pattern, const uint32_t* mask /* [3] or NULL */, ttr_pattern** out);
 void ttr_pattern_free(ttr_pattern* p);
@@ -477,6 +500,13 @@ int ttr_parseq_logits_patterns(ttr_engine* e, const uint8_t* crops, int n, const
                                const char* const* patterns, int n_patterns, const int32_t* pattern_of, float* logits, float* ar_logits, int32_t* ids);
 int ttr_logits_decode_patterns(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of,
                                const char* const* patterns, int n_patterns, const int32_t* pattern_of, int32_t* ids, float* probs, float* conf);
+int ttr_engine_set_pattern_decode(ttr_engine* e, int mode);
+int ttr_engine_pattern_decode(const ttr_engine* e);
+const float* ttr_result_pattern_logp(const ttr_result* r);
+int ttr_results_gather_pattern_logp(ttr_result* const* rs, int n, float* logp);
+int ttr_logits_decode_patterns_best(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of,
+                                    const char* const* patterns, int n_patterns, const int32_t* pattern_of, int32_t* ids, float* probs, float* conf, float* logp);
+int ttr_pattern_best_from_lp(const ttr_pattern* p, const float* lp /* [26][96] */, int32_t* path /* [26] */, int32_t* len, float* logp);
 /* Character alternatives (DESIGN.md "Character alternatives"): what else each character could have been.  K = alternatives per position, the winner
  * included: 0 (off, the default) or 2..8.  For item i and position p (0..25), under the class mask in force for that crop (the engine's set, or the region's
  * own): alt_ids[p][j], j < K, are the allowed classes in descending order of the refined logit (fp32), ties to the lower class, -1 where fewer than K are

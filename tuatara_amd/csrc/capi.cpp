@@ -800,7 +800,8 @@ int ttr_parseq_logits(ttr_engine* e, const uint8_t* crops, int n, float* logits,
   E.refuse_while_streaming("ttr_parseq_logits");
   if (n <= 0) return 0;
   // (not ttr_parseq_logits_patterns with nothing given: where the engine has a pattern that call compiles and stages a table of its own, this one reads under pattern_own)
-  const Engine::RecPass p = stage_crops(E, crops, n, ar_logits != nullptr);
+  Engine::RecPass p = stage_crops(E, crops, n, ar_logits != nullptr);
+  if (E.pattern_decode == TTR_PATTERN_BEST && E.pattern_own.delta) p.best = E.pat_best_out(n);   // (the ids are then the likeliest member's; the logits are the same bits)
   E.parseq_forward(p);
   fetch_logits(E, p.out, n, logits, ar_logits, ids, "ttr_parseq_logits");
   return 0;
@@ -953,7 +954,9 @@ int ttr_parseq_logits_patterns(ttr_engine* e, const uint8_t* crops, int n, const
   if (n == 0) return 0;
   Engine::RecPass p = stage_crops(E, crops, n, ar_logits != nullptr);
   p.mask = one;   // (one shared mask: by value, the engine's own path)
-  if (with_pats) p.pat = E.stage_row_patterns(pats, 0);
+  const bool best = with_pats && E.pattern_decode == TTR_PATTERN_BEST;   // (the ids are then the likeliest members'; the logits are the same bits)
+  if (best) p.best = E.pat_best_out(n);
+  if (with_pats) p.pat = E.stage_row_patterns(pats, 0, best ? &p.best.ext : nullptr);
   p.row_masks = E.stage_row_masks(table, 0);
   E.parseq_forward(p);
   fetch_logits(E, p.out, n, logits, ar_logits, ids, what);
@@ -1066,24 +1069,22 @@ int ttr_engine_set_pattern(ttr_engine* e, const char* pattern) {
 
 const char* ttr_engine_get_pattern(const ttr_engine* e) { return e ? e->e->pattern_src.c_str() : nullptr; }
 
-int ttr_logits_decode_patterns(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of,
-                               const char* const* patterns, int n_patterns, const int32_t* pattern_of, int32_t* ids, float* probs, float* conf) {
-  TTR_GUARD_BEGIN
-  if (!e || n < 0 || (n > 0 && !logits)) throw std::runtime_error("null argument");
-  Engine& E = *e->e;
-  EngineScope lk(E);
-  const char* what = "ttr_logits_decode_patterns";
+// the final decode under patterns alone, greedy (logp == nullptr) or best
+static void decode_patterns_stage(Engine& E, const char* what, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of,
+                                  const char* const* patterns, int n_patterns, const int32_t* pattern_of, int32_t* ids, float* probs, float* conf, float* logp) {
   E.refuse_while_streaming(what);
   std::vector<uint32_t> table;
   ClassMask one = E.charset;
   if (set_of || n_sets > 0) E.resolve_row_masks(what, set_of, n, sets, n_sets, table, one);
   Engine::PatRows pats;
   const bool with_pats = E.resolve_row_patterns(what, patterns, n_patterns, pattern_of, n, table, one, pats);
-  if (n == 0) return 0;
+  if (logp && E.prec == kBF16) throw std::runtime_error(std::string(what) + ": the best decode needs an f16x4 or f32 engine, as patterns do");
+  if (n == 0) return;
   if (!with_pats) {   // (no row has a pattern: every row a DONE state under its mask, so that the kernel this stage is about still runs)
     uint32_t m[3];
     std::map<std::vector<uint32_t>, int> start;
     pats.start_of.resize((size_t)n);
+    pats.extent_of.assign(2 * (size_t)n, 0);
     for (int i = 0; i < n; ++i) {
       const uint32_t* b = table.empty() ? one.blocked : &table[4 * (size_t)i];
       ClassMask{{b[0], b[1], b[2]}}.allowed(m);
@@ -1091,14 +1092,81 @@ int ttr_logits_decode_patterns(ttr_engine* e, const float* logits, int n, const 
       auto it = start.find(key);
       if (it == start.end()) it = start.emplace(key, pats.t.add(pattern_none(m), what)).first;
       pats.start_of[(size_t)i] = it->second;
+      pats.extent_of[2 * (size_t)i] = it->second;
     }
   }
   Engine::RecPass p = stage_logits(E, logits, n);
-  p.pat = E.stage_row_patterns(pats, 0);
+  if (logp) {   // best mode reads each row's class mask itself (the lexicon's table): the masks travel as in ttr_logits_confidence_sets
+    p.best = E.pat_best_out(n);
+    p.mask = one; p.row_masks = E.stage_row_masks(table, 0);
+  }
+  p.pat = E.stage_row_patterns(pats, 0, logp ? &p.best.ext : nullptr);
   E.parseq_decode(p);
+  if (logp) TTR_HIP_CHECK(hipMemcpyAsync(logp, p.best.logp, (size_t)n * 4, hipMemcpyDeviceToHost, E.stream));
   fetch_decoded(E, p.out, n, ids, probs, conf);
+}
+
+int ttr_logits_decode_patterns(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of,
+                               const char* const* patterns, int n_patterns, const int32_t* pattern_of, int32_t* ids, float* probs, float* conf) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && !logits)) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  decode_patterns_stage(E, "ttr_logits_decode_patterns", logits, n, sets, n_sets, set_of, patterns, n_patterns, pattern_of, ids, probs, conf, nullptr);
   return 0;
   TTR_GUARD_END(-1)
+}
+
+int ttr_logits_decode_patterns_best(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of,
+                                    const char* const* patterns, int n_patterns, const int32_t* pattern_of, int32_t* ids, float* probs, float* conf, float* logp) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && (!logits || !logp))) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  float none = 0.f;
+  decode_patterns_stage(E, "ttr_logits_decode_patterns_best", logits, n, sets, n_sets, set_of, patterns, n_patterns, pattern_of, ids, probs, conf, n > 0 ? logp : &none);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_set_pattern_decode(ttr_engine* e, int mode) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (mode != TTR_PATTERN_GREEDY && mode != TTR_PATTERN_BEST)
+    throw std::runtime_error("ttr_engine_set_pattern_decode: mode " + std::to_string(mode) + " is neither TTR_PATTERN_GREEDY (0) nor TTR_PATTERN_BEST (1)");
+  E.refuse_while_streaming("ttr_engine_set_pattern_decode");
+  if (mode == TTR_PATTERN_BEST && E.prec == kBF16)
+    throw std::runtime_error("ttr_engine_set_pattern_decode: the best decode needs an f16x4 or f32 engine, as patterns do (the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip)");
+  E.pattern_decode = mode;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_pattern_decode(const ttr_engine* e) { return e ? e->e->pattern_decode : -1; }
+
+const float* ttr_result_pattern_logp(const ttr_result* r) { return r && !r->r.pattern_logp.empty() ? r->r.pattern_logp.data() : nullptr; }
+
+int ttr_results_gather_pattern_logp(ttr_result* const* rs, int n, float* logp) {
+  if (!rs || n < 0) return -1;
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!rs[i]) return -1;
+    const Result& r = rs[i]->r;
+    const size_t cnt = r.text.size();
+    if (logp) {
+      if (r.pattern_logp.size() == cnt) std::copy(r.pattern_logp.begin(), r.pattern_logp.end(), logp + total);
+      else std::fill(logp + total, logp + total + cnt, -INFINITY);
+    }
+    total += cnt;
+  }
+  return (int)total;
+}
+
+int ttr_pattern_best_from_lp(const ttr_pattern* p, const float* lp, int32_t* path, int32_t* len, float* logp) {
+  if (!p || !lp) return -1;
+  return pattern_best_from_lp(p->p, lp, path, len, logp);
 }
 
 int ttr_engine_get_charset(const ttr_engine* e, uint32_t mask[3]) {

@@ -272,6 +272,7 @@ struct Result {
   int lex_m = 0;                   // M: matches kept per item
   std::vector<int32_t> lex_idx;    // M per item: the M best entries of the engine's word list by (logp descending, index ascending), -1 in the empty slots (lexicon.hip)
   std::vector<float> lex_logp;     // M per item: their log-probabilities, -INFINITY in the empty slots
+  std::vector<float> pattern_logp; // patterns in best mode: one per item, the log-probability of its reading (-INFINITY for an item without a pattern); empty otherwise
   // word orientation (cfg.orient != TTR_ORIENT_OFF; DESIGN.md "Word orientation"): empty when off
   std::vector<int32_t> orient;      // 1 per item: the chosen turn 0..3
   std::vector<float> orient_conf;   // orient_k per item: every candidate's conf, ascending turn
@@ -422,8 +423,22 @@ struct Engine {
   std::string pattern_src;
   Pattern pattern;
   DevBuf pattern_dev;
-  struct PatRows { PatternTable t; std::vector<int32_t> start_of; };   // a call's table and each row's start state (resolve_row_patterns)
+  // a call's table, each row's start state and the extent of its automaton in the table - {first state, states}, DONE not counted (resolve_row_patterns)
+  struct PatRows { PatternTable t; std::vector<int32_t> start_of, extent_of; };
   PatDev pattern_own{};                           // the device form of `pattern`; delta == null while there is none
+  // the decode mode of patterns (ttr_engine_set_pattern_decode): TTR_PATTERN_GREEDY, or TTR_PATTERN_BEST - every row that has a pattern is read as the
+  // likeliest member of its language (pattern.hip: pattern_best_kernel).  Without a pattern in force the mode has no effect
+  int pattern_decode = 0;
+  // best mode's buffers: the masked argmax's standard block of the pass (launch_decode_conf into scratch: [N][26] id0 | [N][26] prob0 | [N] conf0), and the
+  // side block [N] f32 with its pinned twin per slot
+  DevBuf pat_best_scratch, pat_logp_dev;
+  PinnedBuf h_pat_logp[2];
+  struct PatBestOut { int* id0; float* prob0; float* conf0; float* logp; PatExtent ext; };   // logp null = greedy mode
+  PatBestOut pat_best_out(int N) {
+    const RecOut o = rec_block(pat_best_scratch, N);
+    pat_logp_dev.ensure((size_t)std::max(N, 1) * 4);
+    return PatBestOut{o.ids, o.prob, o.conf, pat_logp_dev.as<float>(), PatExtent{nullptr, 0, 0}};
+  }
 
   // CRAFT
   std::map<std::string, Linear> craft;
@@ -694,12 +709,14 @@ struct Engine {
   //   lex               (DESIGN.md "Lexicon matching") with lex.m set and the blocks given (idx / logp [N][m], the partials as lex_out sizes them for these N
   //                     crops), the scorer and its merge run behind the final decode, on the engine's word list
   //   pat               (DESIGN.md "Patterns") the call's table; an empty one (delta null) = the engine's own pattern, or none
+  //   best              (DESIGN.md "Patterns", best mode) with best.logp given and a pattern in force, the final decode is launch_decode_conf into best.id0 /
+  //                     prob0 / conf0 and launch_pattern_best; best.ext: the rows' extents in the call's table (the engine's own pattern: parseq_forward's to fill in)
   struct RecPass {
     const uint8_t* crops = nullptr; int N = 0;
     float *logits = nullptr, *ar = nullptr;
     RecOut out{};
     ClassMask mask{}; const RowMask* row_masks = nullptr;
-    AltOut alt{}; LexOut lex{}; PatDev pat{};
+    AltOut alt{}; LexOut lex{}; PatDev pat{}; PatBestOut best{};
     bool with_alts() const { return alt.k && alt.ids && alt.prob; }
     bool with_lex() const { return lex.m && lex.idx && lex.logp; }
     // the same pass over rows [r0, r0 + n): every per-row pointer moves by its own width (rows are never permuted: a row's crop, mask, start state and
@@ -714,6 +731,8 @@ struct Engine {
       g.alt.ids = at(alt.ids, 26 * (size_t)alt.k); g.alt.prob = at(alt.prob, 26 * (size_t)alt.k);
       g.lex.idx = at(lex.idx, lex.m); g.lex.logp = at(lex.logp, lex.m);
       g.pat.start_of = at(pat.start_of, 1);
+      g.best.id0 = at(best.id0, 26); g.best.prob0 = at(best.prob0, 26); g.best.conf0 = at(best.conf0, 1); g.best.logp = at(best.logp, 1);
+      g.best.ext.extent_of = at(best.ext.extent_of, 2);
       return g;
     }
   };
@@ -787,6 +806,7 @@ struct Engine {
     int cap = 0;                       // ... and the largest rank total (rows of the gathered payload per rank)
     int rows = 0;                      // rows of the recogniser's output block (RecOut) staged in h_ids[slot]: max(N, cap)
     int alts = 0;                      // the engine's `alts` when the recogniser was enqueued: h_alts[slot] holds [N][26][alts] ids | prob
+    bool pat_best = false;             // patterns in best mode, fixed when the recogniser was enqueued with a pattern in force: h_pat_logp[slot] holds [N] f32
     int lex_m = 0;                     // the engine's `lex_m` when the recogniser was enqueued with a lexicon set (0 = none): h_lex[slot] holds [N][lex_m] idx | logp
     // regions (run_regions; DESIGN.md "Regions and per-row character sets"): the boxes are the caller's quads - no detector ran, `boxes` stays empty, every crop is
     // a kind-1 crop of the table packer.  Crop c (page order, then the caller's order): its quad verbatim, its set index, and - when the sets differ - its row
@@ -859,9 +879,10 @@ struct Engine {
   // results[pg] for every page of B from its boxes and the decoded rows of its crops (crop c is row c); side: the orientation side block
   // of the batch (orient.hip) or null; lines_side: the text lines' side block (lines.hip) or null; chars_side: the characters' (chars.hip) or null;
   // blocks_side: the text blocks' (blocks.hip) or null; alts_side: the alternatives' (decode_alts.hip, B.alts per position) or null; lex_side: the
-  // lexicon matches' (lexicon.hip, B.lex_m per item) or null
+  // lexicon matches' (lexicon.hip, B.lex_m per item) or null; pat_logp: best mode's log-probabilities (pattern.hip, one per item) or null
   void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                    std::vector<Result>& results, const void* alts_side = nullptr, const void* lex_side = nullptr, const int32_t* wide_cuts = nullptr);
+                    std::vector<Result>& results, const void* alts_side = nullptr, const void* lex_side = nullptr, const int32_t* wide_cuts = nullptr,
+                    const float* pat_logp = nullptr);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it
@@ -888,8 +909,9 @@ struct Engine {
   // - nothing built - when no row has a pattern.  Refuses a bad index, a bad pattern (naming the row) and more than 1024 states in all (naming the total).
   bool resolve_row_patterns(const char* what, const char* const* patterns, int n_patterns, const int32_t* pattern_of, int n, const std::vector<uint32_t>& table,
                             const ClassMask& one, PatRows& out) const;
-  // the call's table and start states through the pinned staging of slot sl to pat_rows_dev (one copy on `stream`)
-  PatDev stage_row_patterns(const PatRows& r, int sl);
+  // the call's table and start states through the pinned staging of slot sl to pat_rows_dev (one copy on `stream`); with `ext` given (best mode) the rows'
+  // extents travel in the same copy and *ext names them - without it the bytes are the ones greedy mode always sent
+  PatDev stage_row_patterns(const PatRows& r, int sl, PatExtent* ext = nullptr);
   DevBuf pat_rows_dev, pat_state;
   PinnedBuf h_pat_rows[2];
 

@@ -668,6 +668,7 @@ void Engine::recog_enqueue(PageBatch& B) {
   if (cfg.chars && N > 0) stage_batch_chars(B, sl);                          // character boxes: likewise
   B.alts = orient_k() > 1 ? 0 : alts;        // character alternatives: fixed for the batch here (the setter refuses while batches stream)
   B.lex_m = lex_v && orient_k() <= 1 ? lex_m : 0;   // lexicon matching: likewise (0 = no lexicon set)
+  B.pat_best = pattern_decode == TTR_PATTERN_BEST && N > 0 && (B.regions ? !B.region_pats.start_of.empty() : pattern_own.delta != nullptr);   // patterns in best mode: likewise, and only with a pattern in force
   range_use(kRangeRec0 + (sl & 1));          // the recogniser's kernels of this batch watch the slot's own word
   const int X = B.X;                         // wide words: the pieces behind the batch's N, read as a pass of their own (DESIGN.md "Wide words"); 0 with wide off
   B.rows = std::max(N + X, comm ? B.cap : 0);   // the output block's rows (RecOut): with a communicator, the gathered payload's rows per rank
@@ -689,6 +690,8 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (B.alts) { main.alt = alts_out(N, B.alts); h_alts[sl].ensure(alts_side_bytes(N, B.alts)); }
     // lexicon matching: the side block and the scorer's partials of this batch
     if (B.lex_m) { main.lex = lex_out(N, B.lex_m); h_lex[sl].ensure(lex_side_bytes(N, B.lex_m)); }
+    // patterns in best mode: the scratch block of the masked argmax and the side block of this batch
+    if (B.pat_best) { main.best = pat_best_out(N); h_pat_logp[sl].ensure((size_t)N * 4); }
     pack_batch_crops(B, sl);
     if (T) pack_twin_crops(B, sl);
     if (cfg.lines) group_batch_lines(B, sl, line_words);               // text lines: from the boxes alone, so inside the packing stage (DESIGN.md "Text lines")
@@ -696,7 +699,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     if (B.regions) {   // the caller's sets: one mask by value (the engine's own path), or the rows' table through the slot's pinned staging (one copy, no launch)
       main.mask = B.region_mask;
-      if (!B.region_pats.start_of.empty()) main.pat = stage_row_patterns(B.region_pats, sl);   // ... and the regions' patterns: the call's table the same way (one more copy, no launch)
+      if (!B.region_pats.start_of.empty()) main.pat = stage_row_patterns(B.region_pats, sl, B.pat_best ? &main.best.ext : nullptr);   // ... and the regions' patterns: the call's table the same way (one more copy, no launch)
       main.row_masks = stage_row_masks(B.row_masks, sl);
     }
     parseq_forward(main);
@@ -704,7 +707,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     // sliced; the side blocks and the call's pattern table belong to the batch's N rows alone
     auto behind = [&](int n) {
       RecPass r = main.rows(N, n);
-      r.logits = logits.as<float>(); r.alt = AltOut{}; r.lex = LexOut{}; r.pat = PatDev{};
+      r.logits = logits.as<float>(); r.alt = AltOut{}; r.lex = LexOut{}; r.pat = PatDev{}; r.best = PatBestOut{};
       return r;
     };
     // wide words: the X other pieces as a pass of their own, into rows N.. of the same block - the batch's N rows keep their batch, and with it every bit of
@@ -724,6 +727,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (T) TTR_HIP_CHECK(hipMemcpyAsync(h_orient[sl].p, orient_side.p, side_b, hipMemcpyDeviceToHost, stream));
     if (B.alts) TTR_HIP_CHECK(hipMemcpyAsync(h_alts[sl].p, alts_side.p, alts_side_bytes(N, B.alts), hipMemcpyDeviceToHost, stream));   // the alternatives' side block, behind the standard block's copy
     if (B.lex_m) TTR_HIP_CHECK(hipMemcpyAsync(h_lex[sl].p, lex_side.p, lex_side_bytes(N, B.lex_m), hipMemcpyDeviceToHost, stream));   // the lexicon matches' side block, likewise
+    if (B.pat_best) TTR_HIP_CHECK(hipMemcpyAsync(h_pat_logp[sl].p, pat_logp_dev.p, (size_t)N * 4, hipMemcpyDeviceToHost, stream));   // best mode's log-probabilities, likewise
     if (X) TTR_HIP_CHECK(hipMemcpyAsync(h_wide[sl].p, wide_side.p, B.wide.size() * 17 * 4, hipMemcpyDeviceToHost, stream));   // the wide words' cuts (the profile stays on the device)
   } else {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
@@ -764,13 +768,14 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   const void* alts_block = B.alts && N > 0 ? h_alts[B.slot].p : nullptr;                        // the side block (decode_alts.hip)
   const void* lex_block = B.lex_m && N > 0 ? h_lex[B.slot].p : nullptr;                         // the side block (lexicon.hip)
   const int32_t* wide_block = B.X && N > 0 ? h_wide[B.slot].as<int32_t>() : nullptr;            // the cuts of the side block (wide.hip)
-  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block, wide_block);
+  const float* pat_logp_block = B.pat_best && N > 0 ? h_pat_logp[B.slot].as<float>() : nullptr;  // the side block (pattern.hip, best mode)
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block, wide_block, pat_logp_block);
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
 
 void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                          std::vector<Result>& results, const void* alts_side, const void* lex_side, const int32_t* wide_cuts) {
+                          std::vector<Result>& results, const void* alts_side, const void* lex_side, const int32_t* wide_cuts, const float* pat_logp) {
   const int n = B.n, N = B.N, K = orient_k();
   const std::vector<int> first = page_first(B.page_of, n);
   // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
@@ -799,6 +804,7 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
       r.lex_idx.assign(li + (size_t)c0 * w, li + (size_t)(c0 + cnt) * w);
       r.lex_logp.assign(ll + (size_t)c0 * w, ll + (size_t)(c0 + cnt) * w);
     }
+    if (pat_logp && cnt > 0) r.pattern_logp.assign(pat_logp + c0, pat_logp + c0 + cnt);
     if (K > 1) {
       r.orient_k = K;
       if (side) {
@@ -1021,7 +1027,7 @@ const RowMask* Engine::stage_row_masks(const std::vector<uint32_t>& table, int s
 }
 
 void Engine::set_engine_pattern(const char* src_, const ClassMask& cm) {
-  if (!src_ || !*src_) { pattern_src.clear(); pattern = Pattern(); pattern_own = PatDev{}; return; }
+  if (!src_ || !*src_) { pattern_src.clear(); pattern = Pattern(); pattern_own = PatDev{}; return; }   // (pattern.states = 0: best mode's extent of the engine's own pattern is read from `pattern`)
   const std::string src(src_);   // (a copy: the caller may pass pattern_src itself)
   uint32_t m[3];
   cm.allowed(m);
@@ -1047,7 +1053,7 @@ bool Engine::resolve_row_patterns(const char* what, const char* const* patterns,
       throw std::runtime_error(w + ": item " + std::to_string(i) + " names pattern " + std::to_string(k) + ", the call holds " + std::to_string(n_patterns) + " (-1 = the engine's own)");
     any = any || k >= 0 || !pattern_src.empty();
   }
-  out.t = PatternTable(); out.start_of.clear();
+  out.t = PatternTable(); out.start_of.clear(); out.extent_of.clear();
   if (!any) return false;
   if (prec == kBF16) throw std::runtime_error(w + ": a pattern needs an f16x4 or f32 engine: the bf16 engine chooses its tokens inside gemm_sk.hip and dec_fused.hip, which know no automaton");
   if (alts || lex_v) throw std::runtime_error(w + ": patterns do not combine with character alternatives or a lexicon (ttr_engine_set_alternatives(e, 0) / ttr_engine_set_lexicon(e, NULL, 0, 0) first)");
@@ -1078,20 +1084,29 @@ bool Engine::resolve_row_patterns(const char* what, const char* const* patterns,
   std::vector<int> start(autos.size());
   for (size_t a = 0; a < autos.size(); ++a) start[a] = out.t.add(autos[a], what);
   out.start_of.resize((size_t)n);
-  for (int i = 0; i < n; ++i) out.start_of[(size_t)i] = start[(size_t)of[(size_t)i]];
+  out.extent_of.resize(2 * (size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const size_t a = (size_t)of[(size_t)i];
+    out.start_of[(size_t)i] = start[a];
+    out.extent_of[2 * (size_t)i] = start[a] - autos[a].start; out.extent_of[2 * (size_t)i + 1] = autos[a].states;
+  }
   return true;
 }
 
-PatDev Engine::stage_row_patterns(const PatRows& r, int sl) {
-  // delta | start_of | mind, in this order so that each part is aligned to its element
+PatDev Engine::stage_row_patterns(const PatRows& r, int sl, PatExtent* ext) {
+  // delta | start_of | mind (| extent_of in best mode, behind the mind bytes rounded up to 4), in this order so that each part is aligned to its element
   const size_t db = r.t.delta.size() * sizeof(uint16_t), sb = r.start_of.size() * 4, mb = r.t.mind.size();
+  const size_t eo = (db + sb + mb + 3) & ~(size_t)3, eb = ext ? r.extent_of.size() * 4 : 0, total = ext ? eo + eb : db + sb + mb;
+  if (ext && r.extent_of.size() != 2 * r.start_of.size()) throw std::runtime_error("patterns: the rows' extents are missing");
   PinnedBuf& h = h_pat_rows[sl & 1];
-  h.ensure(db + sb + mb); pat_rows_dev.ensure(db + sb + mb);
+  h.ensure(total); pat_rows_dev.ensure(total);
   memcpy(h.p, r.t.delta.data(), db);
   memcpy(h.as<uint8_t>() + db, r.start_of.data(), sb);
   memcpy(h.as<uint8_t>() + db + sb, r.t.mind.data(), mb);
-  TTR_HIP_CHECK(hipMemcpyAsync(pat_rows_dev.p, h.p, db + sb + mb, hipMemcpyHostToDevice, stream));
+  if (ext) memcpy(h.as<uint8_t>() + eo, r.extent_of.data(), eb);
+  TTR_HIP_CHECK(hipMemcpyAsync(pat_rows_dev.p, h.p, total, hipMemcpyHostToDevice, stream));
   uint8_t* d = pat_rows_dev.as<uint8_t>();
+  if (ext) *ext = PatExtent{reinterpret_cast<const int32_t*>(d + eo), 0, 0};
   return PatDev{reinterpret_cast<const uint16_t*>(d), d + db + sb, reinterpret_cast<const int32_t*>(d + db), 0};
 }
 
@@ -1141,7 +1156,7 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
   B.page_of.assign((size_t)n, 0); B.rects.assign((size_t)n * 5, 0); B.coef.assign((size_t)n * 8, 0);
   B.region_quad.assign((size_t)n * 8, 0.f); B.region_set.assign((size_t)n, 0);
   if (!table.empty()) B.row_masks.assign((size_t)n * 4, 0u);
-  if (with_pats) { B.region_pats.t = std::move(pats.t); B.region_pats.start_of.assign((size_t)n, 0); }
+  if (with_pats) { B.region_pats.t = std::move(pats.t); B.region_pats.start_of.assign((size_t)n, 0); B.region_pats.extent_of.assign(2 * (size_t)n, 0); }
   B.region_mask = one;
   for (int i = 0; i < n; ++i) {
     const ttr_region& R = regions[i];
@@ -1156,7 +1171,10 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
     memcpy(&B.region_quad[8 * c], R.quad, 8 * sizeof(float));
     B.region_set[c] = R.set;
     if (!table.empty()) memcpy(&B.row_masks[4 * c], &table[4 * (size_t)i], 16);
-    if (with_pats) B.region_pats.start_of[c] = pats.start_of[(size_t)i];
+    if (with_pats) {
+      B.region_pats.start_of[c] = pats.start_of[(size_t)i];
+      B.region_pats.extent_of[2 * c] = pats.extent_of[2 * (size_t)i]; B.region_pats.extent_of[2 * c + 1] = pats.extent_of[2 * (size_t)i + 1];
+    }
   }
   plan_wide(B, B.region_quad.data());   // wide words: the pieces' rows behind the call's n (DESIGN.md "Wide words")
   const double th0 = now_us();
@@ -1177,6 +1195,8 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   if (cfg.chars) throw std::runtime_error("latency mode does not support character boxes: create the engine with chars = 0");
   if (alts) throw std::runtime_error("latency mode does not support character alternatives: ttr_engine_set_alternatives(e, 0) first");
   if (lex_v) throw std::runtime_error("latency mode does not support lexicon matching: ttr_engine_set_lexicon(e, NULL, 0, 0) first");
+  if (pattern_decode == TTR_PATTERN_BEST && !pattern_src.empty())
+    throw std::runtime_error("latency mode does not support the best decode of patterns: ttr_engine_set_pattern_decode(e, TTR_PATTERN_GREEDY) first");
   if (q1.live || q2.live) throw std::runtime_error("streamed batches are in flight: call ttr_stream_flush until it returns none");
   Comm* const c = comm;
   const int world = c->world, rank = c->rank;

@@ -154,7 +154,8 @@ void Engine::parseq_forward(const RecPass& pass) {
   // force the AR steps' argmax is launch_argmax_pat, always as its own launch, and the final decode launch_decode_pat; without one nothing below differs
   RecPass p = pass;
   const bool own = !p.pat.delta && pattern_own.delta;
-  if (own) p.pat = pattern_own;
+  if (own) { p.pat = pattern_own; p.best.ext = PatExtent{nullptr, 0, pattern.states}; }   // (the engine's own automaton starts the table: states 0 .. states - 1)
+  if (!p.pat.delta) p.best = PatBestOut{};   // best mode is a mode of patterns: without one in force nothing below differs
   if (p.pat.delta) {
     if (prec == kBF16) throw std::runtime_error("parseq_forward: a pattern needs an f16x4 or f32 engine (the bf16 engine's kernels choose their tokens themselves)");
     if (p.with_alts() || (lex_v && p.with_lex())) throw std::runtime_error("parseq_forward: a pattern does not combine with character alternatives or a lexicon");
@@ -474,7 +475,10 @@ void Engine::parseq_refine(const RecPass& p, PqWork& w) {
 
 // ---- the final decode, from the pass's logits alone
 void Engine::parseq_decode(const RecPass& p) {
-  if (p.pat.delta) launch_decode_pat(p.logits, p.N, p.out.ids, p.out.prob, p.out.conf, stream, p.pat);   // under a pattern: walked position by position through the automaton (pattern.hip)
+  if (p.pat.delta && p.best.logp) {   // under a pattern in best mode: the masked argmax into scratch (the lexicon's table is built from it), then the likeliest member of every row's language
+    launch_decode_conf(p.logits, p.N, p.best.id0, p.best.prob0, p.best.conf0, stream, p.mask, p.row_masks);
+    launch_pattern_best(p.logits, p.N, p.best.id0, p.best.prob0, p.out.ids, p.out.prob, p.out.conf, p.best.logp, stream, p.pat, p.best.ext, p.mask, p.row_masks);
+  } else if (p.pat.delta) launch_decode_pat(p.logits, p.N, p.out.ids, p.out.prob, p.out.conf, stream, p.pat);   // under a pattern: walked position by position through the automaton (pattern.hip)
   else launch_decode_conf(p.logits, p.N, p.out.ids, p.out.prob, p.out.conf, stream, p.mask, p.row_masks);   // the final argmax with each id's probability and the word's confidence (decode_conf.hip)
   // character alternatives (DESIGN.md "Character alternatives"): the K best allowed classes of every position, from the same logits, mask and standard block
   if (p.with_alts()) launch_decode_alts(p.logits, p.N, p.out.ids, p.out.prob, p.alt.k, p.alt.ids, p.alt.prob, stream, p.mask, p.row_masks);

@@ -215,6 +215,13 @@ void launch_argmax_pat(const float* logits, int ld, int C, int* tokens, int tok_
 // launch_decode_conf under a pattern: positions 0..25 walked in order from the start state; the maximum and the exponential sum run over the allowed classes
 // only; ids / prob / conf in launch_decode_conf's layouts, conf the same sequential fp32 product
 void launch_decode_pat(const float* logits, int N, int* ids, float* prob, float* conf, hipStream_t s, PatDev pt);
+// launch_decode_pat in best mode (DESIGN.md "Patterns", the likeliest member): id0 / prob0 are the standard block launch_decode_conf wrote for these logits
+// under cm / row_masks (scratch); ids / prob / conf receive the likeliest member's block and logp [N] its log-probability (-inf for a crop without a pattern).
+// PatExtent: the states of each crop's automaton inside the table, DONE state not counted - extent_of[2 n] the first, extent_of[2 n + 1] how many (at most 256;
+// 0 = no pattern), or first / count for every crop when extent_of is null.  A separate argument: the two kernels above receive what they always did.
+struct PatExtent { const int32_t* extent_of; int first, count; };
+void launch_pattern_best(const float* logits, int N, const int* id0, const float* prob0, int* ids, float* prob, float* conf, float* logp, hipStream_t s, PatDev pt,
+                         PatExtent ex, ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);
 // decode_alts.hip: character alternatives (DESIGN.md "Character alternatives"), directly behind launch_decode_conf on the same logits, mask and standard block:
 // alt_ids i32 [N][26][K] the K best allowed classes of every row (slot 0 = ids; -1 where fewer can be chosen), alt_prob f32 [N][26][K] =
 // expf(x[alt_id] - x[id]) * prob (slot 0 = prob bit for bit; 0.f in the empty slots).  K in 2..8.  Reads the logits, ids and prob; writes the two outputs only.

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <bitset>
+#include <cmath>
 #include <cstdio>
 #include <map>
 #include <memory>
@@ -441,6 +442,49 @@ int pattern_matches(const Tokenizer& tok, const Pattern& p, const char* text) {
   }
   if (dead) return 0;
   for (int s : cur) if (s != p.done && p.delta[(size_t)s * kPatCols] != kPatNone) return 1;
+  return 0;
+}
+
+int pattern_best_from_lp(const Pattern& p, const float* lp, int32_t* path, int32_t* len, float* logp) {
+  constexpr int kLevels = kPatMaxChars + 1;   // V[L]: the best score of L characters that end in a state
+  const int S = p.states;
+  if (path) std::fill(path, path + kLevels, 0);
+  if (len) *len = -1;
+  if (logp) *logp = -INFINITY;
+  if (S <= 0) return 1;                        // a DONE state alone: no language to choose from
+  std::vector<float> V((size_t)kLevels * S, -INFINITY);
+  std::vector<uint16_t> bc((size_t)kLevels * S, 0), bs((size_t)kLevels * S, 0);
+  V[(size_t)p.start] = 0.0f;
+  float best = -INFINITY; int best_l = -1, best_s = -1;
+  for (int l = 0; l < kLevels; ++l) {
+    const float* row = lp + (size_t)l * kPatCols;
+    for (int s = 0; s < S; ++s) {
+      const float vs = V[(size_t)l * S + s];
+      if (!(vs > -INFINITY)) continue;         // (never reached; a NaN is never chosen below, so none is stored)
+      if (p.delta[(size_t)s * kPatCols] != kPatNone) {   // s accepts: the word of l characters that ends here, and the EOS behind it
+        const float f = (vs + row[0]) + 0.0f;    // (+ 0.0f: -0.0f becomes +0.0f, as in pattern_best_kernel, whose keys tell the two apart)
+        if (f > best) { best = f; best_l = l; best_s = s; }   // (l, then s ascending: an equal score later never replaces)
+      }
+      if (l == kPatMaxChars) continue;
+      for (int c = 1; c <= 94; ++c) {
+        const int t = p.delta[(size_t)s * kPatCols + c];
+        if (t == kPatNone) continue;
+        const float v = (vs + row[c]) + 0.0f;
+        if (!(v > -INFINITY)) continue;        // -inf and NaN are never chosen
+        const size_t o = (size_t)(l + 1) * S + t;
+        if (v > V[o] || (v == V[o] && (c < bc[o] || (c == bc[o] && s < bs[o])))) { V[o] = v; bc[o] = (uint16_t)c; bs[o] = (uint16_t)s; }
+      }
+    }
+  }
+  if (best_l < 0) return 1;
+  if (len) *len = best_l;
+  if (logp) *logp = best;
+  if (path)
+    for (int l = best_l, s = best_s; l > 0; --l) {
+      const size_t o = (size_t)l * S + s;
+      path[l - 1] = bc[o];
+      s = bs[o];
+    }
   return 0;
 }
 

@@ -50,6 +50,14 @@ inline bool pattern_allows(const uint16_t* delta, const uint8_t* mind, int s, in
   return t != kPatNone && (c == 0 || mind[t] == kPatFree || pos + 1 + mind[t] <= kPatMaxChars);
 }
 
+// The likeliest member (DESIGN.md "Patterns", the best decode): the member w of p's language with at most 25 characters and the largest
+//   score(w) = the sum, in position order from 0.0f, of lp[i][w_i] for i < L, then + lp[L][0]     (lp: [26][96] fp32, row i = character position i, column 0 = EOS)
+// by the Viterbi recurrence over (position, state): V[0][start] = 0, V[i + 1][t] = max over (s, c >= 1, delta[s][c] == t) of V[i][s] + lp[i][c]; ties to the
+// lower class, then the lower state; the result the maximum over (L, accepting s) of V[L][s] + lp[L][0], ties to the smaller L, then the lower state.  fp32
+// addition is monotone, so each maximum is the maximum of the sequentially rounded sums.  A value of -inf or NaN is never chosen.
+// path [26]: the classes w_0 .. w_(L-1), zeros behind; *len = L; *logp = score(w).  Returns 0, or 1 when no member has a finite score (path zeros, len -1, logp -inf).
+int pattern_best_from_lp(const Pattern& p, const float* lp, int32_t* path, int32_t* len, float* logp);
+
 // A call's table: automata appended into one state space.  add() returns the start state of the appended automaton (its rows are shifted by the rows
 // before it); throws, naming the total, beyond 1024 states.
 struct PatternTable {

@@ -65,9 +65,9 @@ struct CharsetScope {
   ttr_engine* e;
   std::unique_lock<std::mutex> turn;
   bool set = false, ok = true;
-  bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false;
+  bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false;
   CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
-               std::string pattern = std::string(), float wide = 0.f) : e(e_) {
+               std::string pattern = std::string(), float wide = 0.f, bool pattern_best = false) : e(e_) {
     {
       std::lock_guard<std::mutex> lk(g_mu);
       auto& m = g_call_mu[e];
@@ -102,6 +102,11 @@ struct CharsetScope {
       if (ttr_engine_set_charset(e, allow.c_str(), deny.c_str()) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
       set = true;
     }
+    if (!pattern_best && !pattern.empty()) if (const char* p = std::getenv("TUATARA_PATTERN_BEST")) pattern_best = std::string(p) == "1";   // (the variable reaches only calls that read under a pattern)
+    if (pattern_best) {       // the decode mode of patterns (DESIGN.md "Patterns"): the likeliest member, for the call; without a pattern it has no effect
+      if (ttr_engine_set_pattern_decode(e, TTR_PATTERN_BEST) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      best_set = true;
+    }
     if (!pattern.empty()) {   // the call's pattern (DESIGN.md "Patterns"): behind the set, under which it is compiled
       if (ttr_engine_set_pattern(e, pattern.c_str()) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
       pattern_set = true;
@@ -109,6 +114,7 @@ struct CharsetScope {
   }
   ~CharsetScope() {
     if (pattern_set) ttr_engine_set_pattern(e, nullptr);
+    if (best_set) ttr_engine_set_pattern_decode(e, TTR_PATTERN_GREEDY);
     if (wide_set) ttr_engine_set_wide(e, 0.f);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
     if (alts_set) ttr_engine_set_alternatives(e, 0);
@@ -179,6 +185,8 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
       o.lexicon.push_back(std::move(mt));
     }
   }
+  o.has_pattern_logp = false; o.pattern_logp = 0.f;
+  if (const float* pl = ttr_result_pattern_logp(r)) { o.has_pattern_logp = true; o.pattern_logp = pl[i]; }
   o.pieces.clear();
   if (const int32_t* pf = ttr_result_piece_first(r)) {
     const int32_t* pi = ttr_result_piece_ids(r);
@@ -220,10 +228,11 @@ template <class Item>
 std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
                           const std::string& outputs_dir, int crop_mode, int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
                                         int blocks = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0,
-                                        const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string(), float wide = 0.f) {
+                                        const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string(), float wide = 0.f,
+                                        bool pattern_best = false) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern, wide);
+  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern, wide, pattern_best);
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
@@ -244,10 +253,10 @@ template <class Item>
 std::vector<std::vector<Item>> run_many(const std::vector<ImageView>& images, const std::string& weights_dir, const std::string& outputs_dir, int crop_mode,
                                         int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
                                         int blocks = -1, int mixed = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0,
-                                        const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string()) {
+                                        const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string(), bool pattern_best = false) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks, mixed);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern);
+  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern, 0.f, pattern_best);
   if (!cs.ok) return {};
   const int n = (int)images.size();
   std::vector<const uint8_t*> ptr(n);
@@ -412,6 +421,20 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
 }
 
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, std::string pattern, bool pattern_best) {
+  return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1,
+                               chars ? 1 : -1, blocks ? 1 : -1, allowlist, blocklist, 0, nullptr, 0, pattern, 0.f, pattern_best);
+}
+
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist, std::string pattern, bool pattern_best) {
+  return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
+                                blocks ? 1 : -1, mixed_batches ? 1 : -1, allowlist, blocklist, 0, nullptr, 0, pattern, pattern_best);
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, bool /*rectify*/, int orient, bool orient_page, bool lines, bool chars, bool blocks,
                                            std::string allowlist, std::string blocklist, Wide wide) {
   if (!(wide.max_aspect >= 2.f && wide.max_aspect <= 64.f)) {   // (before an engine is opened; 0 would read as "off")
@@ -447,7 +470,8 @@ std::vector<WordReading> nbest(const OutputItemEx& item, int m) {
 
 namespace {
 std::vector<OutputItemEx> read_regions(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
-                                       const std::string& outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>* words, int lex_m) {
+                                       const std::string& outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>* words, int lex_m,
+                                       bool pattern_best = false) {
   // every list and quad is checked on the host before an engine is opened
   std::vector<ttr_region> regs(regions.size());
   std::vector<uint32_t> sets;
@@ -475,7 +499,8 @@ std::vector<OutputItemEx> read_regions(const uint8_t* image, int rows, int cols,
   }
   ttr_engine* e = open_engine(weights_dir, outputs_dir, -1, -1, 0, -1, -1, -1);
   if (!e) return {};
-  CharsetScope cs(e, std::string(), std::string(), alts, words, lex_m);   // (the engine's own set for regions without lists: TUATARA_ALLOWLIST / TUATARA_BLOCKLIST; calls that share the engine take turns)
+  if (!pattern_best && !pats.empty()) if (const char* p = std::getenv("TUATARA_PATTERN_BEST")) pattern_best = std::string(p) == "1";   // (regions with patterns of their own)
+  CharsetScope cs(e, std::string(), std::string(), alts, words, lex_m, std::string(), 0.f, pattern_best);   // (the engine's own set for regions without lists: TUATARA_ALLOWLIST / TUATARA_BLOCKLIST; calls that share the engine take turns)
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
@@ -498,6 +523,11 @@ std::vector<OutputItemEx> read_regions(const uint8_t* image, int rows, int cols,
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts) {
   return read_regions(image, rows, cols, row_stride, weights_dir, outputs_dir, regions, alts, nullptr, 0);
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts, bool pattern_best) {
+  return read_regions(image, rows, cols, row_stride, weights_dir, outputs_dir, regions, alts, nullptr, 0, pattern_best);
 }
 
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,

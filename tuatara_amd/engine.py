@@ -146,6 +146,12 @@ SYMBOLS = [
     ("ttr_image_regions_to_data_p", _I, [_VP, _PU8, _I, _I, _I, C.POINTER(Region), _I, C.POINTER(C.c_uint32), _I, C.POINTER(C.c_char_p), _I, _PI, C.POINTER(_VP)]),
     ("ttr_parseq_logits_patterns", _I, [_VP, _PU8, _I, C.POINTER(C.c_uint32), _I, _PI, C.POINTER(C.c_char_p), _I, _PI, _PF, _PF, _PI]),
     ("ttr_logits_decode_patterns", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _I, _PI, C.POINTER(C.c_char_p), _I, _PI, _PI, _PF, _PF]),
+    ("ttr_engine_set_pattern_decode", _I, [_VP, _I]),
+    ("ttr_engine_pattern_decode", _I, [_VP]),
+    ("ttr_result_pattern_logp", _PF, [_VP]),
+    ("ttr_results_gather_pattern_logp", _I, [C.POINTER(_VP), _I, _PF]),
+    ("ttr_logits_decode_patterns_best", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _I, _PI, C.POINTER(C.c_char_p), _I, _PI, _PI, _PF, _PF, _PF]),
+    ("ttr_pattern_best_from_lp", _I, [_VP, _PF, _PI, _PI, _PF]),
     ("ttr_engine_set_alternatives", _I, [_VP, _I]),
     ("ttr_engine_alternatives", _I, [_VP]),
     ("ttr_result_alt_k", _I, [_VP]),
@@ -439,6 +445,23 @@ class Pattern:
 def pattern_compile(pattern, mask=None) -> Pattern:
     """Compile a pattern under a class mask (charset_mask's form; None = every class) on the host.  EngineError for a refused pattern."""
     return Pattern(pattern, mask)
+
+
+PATTERN_GREEDY, PATTERN_BEST = 0, 1
+
+
+def pattern_best_from_lp(pattern, lp, mask=None):
+    """The likeliest member of a pattern's language under a table lp f32 [26, 96] (ttr_pattern_best_from_lp, no GPU; DESIGN.md "Patterns", best mode):
+    -> (path i32 [L] the classes, logp f32), or None when no member has a finite score.  `pattern`: a Pattern, or a string compiled under `mask`."""
+    pat = pattern if isinstance(pattern, Pattern) else Pattern(pattern, mask)
+    lp = np.ascontiguousarray(lp, dtype=np.float32)
+    if lp.shape != (26, 96):
+        raise ValueError("lp is a [26, 96] table: row p = position p, column 0 = the end of the text")
+    path, ln, logp = np.zeros(26, np.int32), C.c_int32(-1), C.c_float(0.0)
+    rc = pat.lib.ttr_pattern_best_from_lp(pat.h, _f(lp), _i(path), C.cast(C.byref(ln), _PI), C.cast(C.byref(logp), _PF))
+    if rc < 0:
+        raise EngineError("ttr_pattern_best_from_lp: null argument")
+    return None if rc else (path[:ln.value].copy(), np.float32(logp.value))
 
 
 def _patterns_arg(patterns):
@@ -778,25 +801,27 @@ class PageResult(collections.abc.Sequence):
     position's character options in rank order; nbest(i, m) reads item i's m likeliest whole words; both None when alternatives are off.  Lexicon
     matching (Engine.set_lexicon(words, m); DESIGN.md "Lexicon matching"): `lex_idx` i32 [n, M] the M best entries of the word list by (logp descending,
     index ascending), -1 = none, and `lex_logp` f32 [n, M] their log-probabilities (-inf = none); dicts gain "lexicon", [(word, prob), ...] with
-    prob = exp(logp); both None when no lexicon is set.  Wide words (Engine.set_wide(a); DESIGN.md "Wide words"): `piece_first` i32 [n + 1] the items' offsets
+    prob = exp(logp); both None when no lexicon is set.  Patterns in best mode (Engine.set_pattern(p, best=True); DESIGN.md "Patterns"): `pattern_logp` f32 [n]
+    the log-probability of every item's reading, -inf for an item without a pattern (dicts gain "pattern_logp"); None in greedy mode, without a pattern, and for a page without items.  Wide words (Engine.set_wide(a); DESIGN.md "Wide words"): `piece_first` i32 [n + 1] the items' offsets
     into `piece_ids` i32 [P, 26], `piece_prob` f32 [P, 26], `piece_conf` f32 [P] and `piece_quad` f32 [P, 8] (an item that is not wide owns one piece, itself),
     `piece_cuts` i32 [n, 17] each item's cuts in columns of its frame; dicts gain "pieces", a list of {"text", "conf", "quad"}; all None when wide is off."""
     __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
                  "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad",
                  "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode", "alt_ids", "alt_prob",
-                 "lex_idx", "lex_logp", "lex_words", "piece_first", "piece_ids", "piece_prob", "piece_conf", "piece_quad", "piece_cuts")
+                 "lex_idx", "lex_logp", "lex_words", "pattern_logp", "piece_first", "piece_ids", "piece_prob", "piece_conf", "piece_quad", "piece_cuts")
 
     def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0,
                  line=None, word=None, order=None, line_first=None, line_bbox=None,
                  char_first=None, char_quad=None, char_bbox=None, char_cuts=None, char_mode=None, char_profile=None, word_quad=None,
                  block=None, line_block=None, line_pos=None, block_order=None, block_first=None, block_bbox=None, block_mode=0,
-                 alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None,
+                 alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None, pattern_logp=None,
                  piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None):
         self.piece_first, self.piece_ids, self.piece_prob = piece_first, piece_ids, piece_prob
         self.piece_conf, self.piece_quad, self.piece_cuts = piece_conf, piece_quad, piece_cuts
         self.alt_ids, self.alt_prob = alt_ids, alt_prob
         self.lex_idx, self.lex_logp, self.lex_words = lex_idx, lex_logp, lex_words
+        self.pattern_logp = pattern_logp
         self.block, self.line_block, self.line_pos, self.block_order = block, line_block, line_pos, block_order
         self.block_first, self.block_bbox, self.block_mode = block_first, block_bbox, block_mode
         self.char_first, self.char_quad, self.char_bbox = char_first, char_quad, char_bbox
@@ -839,6 +864,8 @@ class PageResult(collections.abc.Sequence):
             d["alternatives"] = char_alternatives(self.alt_ids[j], self.alt_prob[j])
         if self.lex_idx is not None:
             d["lexicon"] = lexicon_matches(self.lex_words, self.lex_idx[j], self.lex_logp[j])
+        if self.pattern_logp is not None:
+            d["pattern_logp"] = float(self.pattern_logp[j])
         if self.piece_first is not None:
             d["pieces"] = self.pieces(j)
         return d
@@ -944,6 +971,7 @@ class Engine:
         alts = int(overrides.pop("alts", 0) or 0)                                         # not a config field either: set_alternatives, below
         lexicon, lexicon_m = overrides.pop("lexicon", None), int(overrides.pop("lexicon_m", 1))   # nor these: set_lexicon, below
         pattern = overrides.pop("pattern", None)                                          # nor this: set_pattern, below
+        pattern_best = bool(overrides.pop("pattern_best", False))                         # nor this: set_pattern_decode, below
         wide = _wide_arg(overrides.pop("wide", None))                                     # nor this: set_wide, below
         self._lex_words = []
         tuning = {k: overrides.pop(k) for k in list(overrides) if not hasattr(cfg, k)}     # not a config field: a tuning key (below)
@@ -960,6 +988,8 @@ class Engine:
             self.set_alternatives(alts)
         if lexicon is not None:
             self.set_lexicon(lexicon, lexicon_m)
+        if pattern_best:
+            self.set_pattern_decode(PATTERN_BEST)
         if pattern:
             self.set_pattern(pattern)
         if wide:
@@ -1087,13 +1117,31 @@ class Engine:
         self._check(self.lib.ttr_engine_get_charset(self.h, m))
         return np.array(list(m), dtype=np.uint32)
 
-    def set_pattern(self, pattern=None):
+    def set_pattern(self, pattern=None, best=None):
         """Constrain every word to a regular expression (ttr_engine_set_pattern; DESIGN.md "Patterns"): the subset of Python's re that include/tuatara_hip.h
         lists, compiled under the engine's character set and recompiled when set_charset changes it.  set_pattern() resets.  Every returned text (of at most
         25 characters) then matches the pattern; prob / conf are over the choices it left open.  Raises EngineError, and changes nothing, on a bad pattern,
-        between a stream_push and its flush, on a bf16 engine and with orient, alternatives or a lexicon set.  In sharded mode give every rank the same one."""
+        between a stream_push and its flush, on a bf16 engine and with orient, alternatives or a lexicon set.  In sharded mode give every rank the same one.
+        best: True / False also sets the decode mode (set_pattern_decode) - True reads every word as the likeliest member of the language; None keeps it."""
+        before = self.pattern_decode
+        if best is not None:                    # the mode first (it may refuse: bf16, streaming), put back if the pattern is refused
+            self.set_pattern_decode(PATTERN_BEST if best else PATTERN_GREEDY)
         if self.lib.ttr_engine_set_pattern(self.h, _charlist(pattern)) != 0:
+            err = self.lib.ttr_last_error().decode("latin1")
+            self.lib.ttr_engine_set_pattern_decode(self.h, before)
+            raise EngineError(err)
+
+    def set_pattern_decode(self, mode):
+        """The decode mode of patterns (ttr_engine_set_pattern_decode): PATTERN_GREEDY (0, the default) or PATTERN_BEST (1) - the final decode of every row that
+        has a pattern returns the likeliest member of its language under the refined distributions, and page results carry pattern_logp.  Raises EngineError,
+        and changes nothing, for another value, between a stream_push and its flush, and for best on a bf16 engine; without a pattern it has no effect."""
+        if self.lib.ttr_engine_set_pattern_decode(self.h, int(mode)) != 0:
             raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def pattern_decode(self):
+        """The decode mode of patterns: PATTERN_GREEDY or PATTERN_BEST."""
+        return int(self.lib.ttr_engine_pattern_decode(self.h))
 
     @property
     def pattern(self):
@@ -1101,9 +1149,10 @@ class Engine:
         p = self.lib.ttr_engine_get_pattern(self.h)
         return p.decode("latin1") if p else None
 
-    def logits_decode_patterns(self, logits: np.ndarray, patterns, pattern_of, set_of=None, sets=None):
+    def logits_decode_patterns(self, logits: np.ndarray, patterns, pattern_of, set_of=None, sets=None, best=False):
         """decode_pat_kernel alone on host logits f32 [n, 26, 95] (ttr_logits_decode_patterns) -> (ids i32 [n, 26], prob f32 [n, 26], conf f32 [n]): row i
-        decodes under patterns[pattern_of[i]] (-1: the engine's own pattern, or none) compiled under sets[set_of[i]] (set_of None: the engine's own set)."""
+        decodes under patterns[pattern_of[i]] (-1: the engine's own pattern, or none) compiled under sets[set_of[i]] (set_of None: the engine's own set).
+        best=True: decode_conf_kernel and pattern_best_kernel instead (ttr_logits_decode_patterns_best) -> (ids, prob, conf, logp f32 [n])."""
         logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, 26, 95)
         n = len(logits)
         ids, prob, conf = np.zeros((n, 26), np.int32), np.zeros((n, 26), np.float32), np.zeros(n, np.float32)
@@ -1117,6 +1166,11 @@ class Engine:
                 raise ValueError("set_of holds one entry per row")
         sp, ns, _keep = _sets_arg(sets)
         pp, npat, _keep2 = _patterns_arg(patterns)
+        if best:
+            logp = np.zeros(n, np.float32)
+            self._check(self.lib.ttr_logits_decode_patterns_best(self.h, _f(logits), n, sp, ns, _i(so) if so is not None else None, pp, npat, _i(po), _i(ids), _f(prob),
+                                                                 _f(conf), _f(logp)))
+            return ids, prob, conf, logp
         self._check(self.lib.ttr_logits_decode_patterns(self.h, _f(logits), n, sp, ns, _i(so) if so is not None else None, pp, npat, _i(po), _i(ids), _f(prob), _f(conf)))
         return ids, prob, conf
 
@@ -1265,6 +1319,9 @@ class Engine:
                 li, ll = self.lib.ttr_result_lex_idx_all(arr[i]), self.lib.ttr_result_lex_logp_all(arr[i])
                 lex = dict(lex_idx=np.ctypeslib.as_array(li, (c, M)).copy() if li else np.zeros((0, M), np.int32),
                            lex_logp=np.ctypeslib.as_array(ll, (c, M)).copy() if ll else np.zeros((0, M), np.float32), lex_words=self._lex_words)
+            pl = self.lib.ttr_result_pattern_logp(arr[i])
+            if pl:                              # patterns in best mode: the page's log-probabilities
+                lex["pattern_logp"] = np.ctypeslib.as_array(pl, (c,)).copy()
             orient = (ot[k:k + c], oc[k:k + c], int(op[i])) if self.orienting else (None, None, 0)
             lines = (None,) * 5
             if self.grouping_lines:
@@ -1421,6 +1478,8 @@ class Engine:
                                       "piece_quad": page.piece_quad[a:b], "piece_cuts": page.piece_cuts[k]})
                 if page.lex_idx is not None:        # lexicon matching: each region under its own set
                     items[-1].update({"lex_idx": page.lex_idx[k], "lex_logp": page.lex_logp[k], "lexicon": lexicon_matches(page.lex_words, page.lex_idx[k], page.lex_logp[k])})
+                if page.pattern_logp is not None:   # patterns in best mode: each region under its own pattern and set
+                    items[-1]["pattern_logp"] = float(page.pattern_logp[k])
             out.append(items)
         return out[0] if single else out
 
