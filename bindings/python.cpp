@@ -36,6 +36,9 @@
 // pieces cut at ink gaps and joins the readings (DESIGN.md "Wide words"); every dict gains "pieces", a list of {"text", "conf", "quad"} (one, the item itself,
 // for a word that is not wide).  It turns rectify on.  A value out of range raises RuntimeError before anything runs; wide with orient, chars, alts, lexicon,
 // pattern or regions raises ValueError.
+// And a keyword-only curved=False on image_to_data: True straightens the crops of words set on an arc along a spine found in the page (DESIGN.md "Curved
+// words"); every dict gains "curved" (bool) and "outline" (18 [x, y] points: the top edge left to right, then the bottom edge right to left).  It turns
+// rectify on.  curved with orient, chars, wide, alts, lexicon, pattern or regions raises ValueError (Engine.set_curved combines with the last four).
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -56,7 +59,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false, curved = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
@@ -73,6 +76,12 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
     d["word"] = item.word;
   }
   if (k.blocks) d["block"] = item.block;
+  if (k.curved) {
+    d["curved"] = item.curved;
+    py::list pts;
+    for (size_t j = 0; j + 1 < item.outline.size(); j += 2) pts.append(py::make_tuple(item.outline[j], item.outline[j + 1]).cast<py::list>());
+    d["outline"] = pts;
+  }
   if (k.chars) {
     py::list cs;
     for (const CharBox& c : item.chars) {
@@ -230,7 +239,7 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
-                                      py::object pattern_kw, py::object wide_kw, bool pattern_best) {
+                                      py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved) {
   const int orient = orient_mode(orient_kw);
   const float wide = wide_arg(wide_kw);
   alts_arg(alts);
@@ -243,8 +252,27 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   if (wide != 0.f && (orient || chars || alts || lex || !pattern.empty() || !regions_kw.is_none()))
     throw std::invalid_argument("wide does not combine with orient, chars, alts, lexicon, pattern or regions");
   if (pattern_best && (orient || alts || lex || wide != 0.f)) throw std::invalid_argument("pattern_best does not combine with orient, alts, lexicon or wide");
+  if (curved && (orient || chars || wide != 0.f || alts || lex || !pattern.empty() || pattern_best || !regions_kw.is_none()))
+    throw std::invalid_argument("curved does not combine with orient, chars, wide, alts, lexicon, pattern or regions");
   const bool cset = !allow.empty() || !deny.empty();
   lines = lines || blocks;   // blocks are made of lines
+  if (curved) {   // curved words: rectified crops, the engine's setting for the call
+    py::buffer_info wb = image.request();
+    if (wb.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
+    if (wb.shape[2] != 3) throw std::runtime_error("Input array should have 3 channels");
+    std::vector<OutputItemEx> got;
+    {
+      py::gil_scoped_release nogil;
+      got = image_to_data_ex(static_cast<const uint8_t*>(wb.ptr), (int)wb.shape[0], (int)wb.shape[1], (std::ptrdiff_t)wb.shape[1] * 3, weights_dir, output_dir, true, -1, orient_page,
+                             lines, false, blocks, allow, deny, Curved{});
+    }
+    if (got.empty()) raise_refused();
+    py::list res;
+    Keys keys{true, conf, false, lines, false, blocks};
+    keys.curved = true;
+    for (const auto& item : got) res.append(item_dict(item, keys));
+    return res;
+  }
   if (wide != 0.f) {   // wide words: rectified crops, the engine's setting for the call
     py::buffer_info wb = image.request();
     if (wb.ndim != 3) throw std::runtime_error("Input array should have 3 dimensions");
@@ -372,7 +400,7 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
         py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("pattern_best") = false, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");

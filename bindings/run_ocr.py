@@ -4,7 +4,8 @@
 result, and save an annotated copy (the reference's three panels: boxes on the page, text at the boxes, running text).  Drawing uses PIL only
 (the reference draws with cv2 and opens a window; neither is needed for the results).
 
-  python bindings/run_ocr.py [--rectify] [image] [weights_dir] [outputs_dir]   (--rectify: deskewed crops, words drawn as their quads)
+  python bindings/run_ocr.py [--rectify] [--curved] [image] [weights_dir] [outputs_dir]   (--rectify: deskewed crops, words drawn as their quads;
+  --curved: words set on an arc are straightened along their spines and drawn as their 18-point outlines)
 """
 from __future__ import annotations
 
@@ -39,7 +40,9 @@ def annotate(image: np.ndarray, result, by_lines: bool = False, by_blocks: bool 
     for item in sorted(result, key=key):
         x1, y1, x2, y2 = (int(v) for v in item["bbox"])
         text = item["text"]
-        if "quad" in item:       # rectified crops (pytuatara.image_to_data(..., rectify=True)): the word's own quadrilateral
+        if item.get("curved"):   # curved words (curved=True): the band that was read, top edge and bottom edge
+            db.polygon([tuple(p) for p in item["outline"]], outline=(255, 160, 0), width=2)
+        elif "quad" in item:     # rectified crops (pytuatara.image_to_data(..., rectify=True)): the word's own quadrilateral
             db.polygon([tuple(p) for p in item["quad"]], outline=(0, 255, 0), width=2)
         else:
             db.rectangle([x1, y1, x2, y2], outline=(0, 255, 0), width=2)
@@ -67,8 +70,8 @@ def annotate(image: np.ndarray, result, by_lines: bool = False, by_blocks: bool 
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    rectify, lines, chars, blocks = "--rectify" in argv, "--lines" in argv, "--chars" in argv, "--blocks" in argv
-    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks")]
+    rectify, lines, chars, blocks, curved = "--rectify" in argv, "--lines" in argv, "--chars" in argv, "--blocks" in argv, "--curved" in argv
+    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks", "--curved")]
     image_path = argv[0] if len(argv) > 0 else os.path.join(HERE, "..", "tests", "data", "funsd_0001129658.png")
     weights_dir = argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "weights")
     outputs_dir = argv[2] if len(argv) > 2 else os.path.join(HERE, "..", "outputs")
@@ -82,6 +85,8 @@ def main(argv=None):
         kw["chars"] = True
     if blocks:                      # (blocks are made of lines: blocks=True turns lines on)
         kw["blocks"] = True
+    if curved:                      # (curved words read on rectified crops: curved=True turns rectify on)
+        kw["curved"] = True
     result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir, **kw)
     print(result)
     os.makedirs(outputs_dir, exist_ok=True)

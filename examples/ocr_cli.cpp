@@ -35,6 +35,9 @@
 //   ocr_cli --wide [A] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: reads words wider than A times their height (2..64, default 8) in
 // pieces cut at ink gaps, on rectified crops (DESIGN.md "Wide words").  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item and, under a wide item, one line per
 // piece: "<TAB>|conf text".  A value that is no number in [2, 64] fails before the image is read.
+//   ocr_cli --curved <image.png> <weights_dir> <outputs_dir>   in front of the plain form: straightens the crops of words set on an arc along a spine found in
+// the page, on rectified crops (DESIGN.md "Curved words").  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item and, under a curved item, one line
+// "<TAB>~x y x y ..." with the 18 points of its outline.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <algorithm>
 #include <cmath>
@@ -125,6 +128,22 @@ int main(int argc, const char** argv) {
         printf("%g %g %g %g\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.conf, it.text.c_str());
         if (it.pieces.size() > 1)
           for (const WordPiece& p : it.pieces) printf("\t|%.6f %s\n", p.conf, p.text.c_str());
+      }
+      return 0;
+    }
+    if (argc >= 2 && std::string(argv[1]) == "--curved") {
+      if (argc != 5) throw std::runtime_error("--curved goes in front of <image.png> <weights_dir> <outputs_dir>");
+      pngdec::Image img = pngdec::read(argv[2]);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[3], argv[4], true, -1, false, false,
+                                                         false, false, std::string(), std::string(), Curved{});
+      if (!last_call_error().empty()) return 1;                         // (the message is on stderr)
+      for (const OutputItemEx& it : items) {
+        printf("%g %g %g %g\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.conf, it.text.c_str());
+        if (it.curved) {
+          printf("\t~");
+          for (size_t k = 0; k < it.outline.size(); ++k) printf("%s%.9g", k ? " " : "", it.outline[k]);
+          printf("\n");
+        }
       }
       return 0;
     }
@@ -270,7 +289,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

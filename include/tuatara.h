@@ -72,6 +72,8 @@ struct OutputItemEx {
   bool has_pattern_logp = false;   // patterns in best mode: the call read under a pattern as the likeliest member of its language (DESIGN.md "Patterns") ...
   float pattern_logp = 0.f;        // ... and this is the log-probability of `text` under the recogniser's per-position distributions (-inf for an item without a pattern)
   std::vector<WordPiece> pieces;   // wide words: the item's pieces in order (one, the item itself, when it is not wide); empty when wide is off (DESIGN.md "Wide words")
+  bool curved = false;             // curved words: the item's crop was straightened along a spine found in the page (DESIGN.md "Curved words")
+  std::vector<float> outline;      // curved words: 36 = 18 points x, y - the top edge left to right, then the bottom edge right to left; empty when curved is off
   int block = -1, block_line = -1;  // text blocks: the item's block of its page, in reading order, and its line's position inside that block (what a caller sorts by: block, block_line, word); -1 when blocks are off (DESIGN.md "Text blocks")
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
@@ -215,6 +217,16 @@ struct Wide { float max_aspect = 8.f; };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
                                            std::string allowlist, std::string blocklist, Wide wide);
+
+// Curved words (opt-in; DESIGN.md "Curved words"): a word set on an arc - on a seal, a stamp, a logo - has its crop straightened along a spine found in the
+// page's own pixels inside its quad; `curved` says so and `outline` traces the band that was read (for a word that is not curved, its quad's long sides).
+// Items, order, bbox and quad do not change, and a word that is not curved keeps every bit.  The call reads on rectified crops whatever `rectify` says.  It
+// is set on the cached engine for the call and reset afterwards; TUATARA_CURVED=1 in the environment turns it - and with it rectified crops - on for every call
+// here.  With orient or chars: the message is printed and the result is empty (last_call_error()).
+struct Curved {};
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, Curved curved);
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

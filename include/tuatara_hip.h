@@ -613,6 +613,42 @@ int ttr_wide_piece_coef(const int64_t frame[6], int c0, int c1, int64_t row[8]);
 int ttr_wide_piece_quads(const float quad[8], const int32_t* cuts, int n, float* quads);
 int ttr_wide_cuts(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, float max_aspect, int use_table, int32_t* n_out,
                   int32_t* cuts, uint16_t* profiles, int64_t* coef);
+/* ---- curved words (opt-in; DESIGN.md "Curved words") ------------------------------------------
+ * A word set on an arc - on a seal, a stamp, a logo - is boxed by a quad far taller than its text, and stretched to 32 x 128 its glyphs ride up and down the crop.
+ * With ttr_engine_set_curved(e, 1) every word's spine is sought in the page's own pixels inside its quad (curve.hip, behind the unchanged packer, one launch per
+ * batch); a word whose spine bends by at least half its band has its crop made again along the spine, nine knots and eight straight segments, and the recogniser
+ * reads that.  The row count of a batch does not change, so a word that is not curved keeps ids, prob, conf and text bit for bit; bbox, quad, item count and
+ * order never change.  on: 0 = off (the default) or 1; anything else fails and changes nothing.  The setter also refuses, naming the reason: while streamed
+ * batches are in flight; on an engine whose crop_mode is not TTR_CROP_RECTIFIED; with orient or chars set; with wide words on; with a communicator attached.  The
+ * other way round ttr_engine_set_wide, ttr_engine_attach_comm and ttr_pages_to_data_dev_sharded refuse while curved is on.  Character sets, alternatives, a
+ * lexicon and patterns apply as ever: they act on recogniser rows.
+ * Result views (NULL with curved off and for an empty result): ttr_result_curved [count] (1 = straightened); ttr_result_outlines [count][18][2] - the top edge
+ * C_j - H_j left to right, then the bottom edge C_j + H_j right to left; for a word that is not curved the quad's long sides at the same nine stations;
+ * ttr_result_spine_knots [count][9][4] int64 - {Cx, Cy, Hx, Hy} in 2^-16 px (zeros for a word whose second pass did not run).  ttr_results_gather_curved: the
+ * views of n results back to back, any pointer may be NULL; returns the number of curved items, -1 for bad arguments.
+ * The rule on the host, no engine (each returns 0 or the value named, -1 with the message in ttr_last_error):
+ *   ttr_curve_frame    quad [8] -> frame [6] = {X0, Ax, Bx, Y0, Ay, By} in 2^-16 px over 128 columns x 64 rows
+ *   ttr_curve_columns  a host image u8 [h][w][3] (row_stride bytes, 0 = 3 w), frame, knots (NULL = pass 1 over the frame, else pass 2 over the band of that
+ *                      table [9][4]) -> stats [4][128] = G | M | first | last
+ *   ttr_curve_knots    image, frame -> returns the flag; flag, hb [2], spine [2][9] (1/256 row), knots [9][4], knots1 [9][4] (pass 1's table); any may be NULL
+ *   ttr_curve_crop     image, knots [9][4] -> crop u8 [32][128][3]
+ *   ttr_curve_outline  quad [8], flag, knots -> outline [18][2]
+ * ttr_curve_crops (stage; refuses while batches stream): a host image and nq quads through the kind-1 packer and curve_crop_kernel, whatever the engine's
+ * setting; use_table != 0 reads the page through the device page table as mixed-size batches do.  flag [nq], hb [nq][2], spine [nq][2][9], knots [nq][9][4],
+ * crops [nq][32][128][3] (the kind-1 crop for a quad that is not curved); any output may be NULL. */
+int ttr_engine_set_curved(ttr_engine* e, int on);
+int ttr_engine_curved(const ttr_engine* e);
+const int32_t* ttr_result_curved(const ttr_result* r);
+const float* ttr_result_outlines(const ttr_result* r);
+const int64_t* ttr_result_spine_knots(const ttr_result* r);
+int ttr_results_gather_curved(ttr_result* const* rs, int n, int32_t* curved, float* outlines, int64_t* knots);
+int ttr_curve_frame(const float quad[8], int64_t frame[6]);
+int ttr_curve_columns(const uint8_t* img, int h, int w, int row_stride, const int64_t frame[6], const int64_t* knots, int32_t* stats);
+int ttr_curve_knots(const uint8_t* img, int h, int w, int row_stride, const int64_t frame[6], int32_t* flag, int32_t hb[2], int32_t* spine, int64_t* knots, int64_t* knots1);
+int ttr_curve_crop(const uint8_t* img, int h, int w, int row_stride, const int64_t* knots, uint8_t* crop);
+int ttr_curve_outline(const float quad[8], int flag, const int64_t* knots, float* outline);
+int ttr_curve_crops(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, int use_table, int32_t* flag, int32_t* hb,
+                    int32_t* spine, int64_t* knots, uint8_t* crops);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

@@ -1216,6 +1216,7 @@ int ttr_engine_set_wide(ttr_engine* e, float max_aspect) {
     if (E.lex_v) throw std::runtime_error("ttr_engine_set_wide: wide words do not combine with a lexicon: ttr_engine_set_lexicon(e, NULL, 0, 0) first");
     if (!E.pattern_src.empty()) throw std::runtime_error("ttr_engine_set_wide: wide words do not combine with a pattern: ttr_engine_set_pattern(e, NULL) first");
     if (E.comm) throw std::runtime_error("ttr_engine_set_wide: wide words are read by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
+    if (E.curved) throw std::runtime_error("ttr_engine_set_wide: wide words do not combine with curved words (a piece is a straight cut of the quad): ttr_engine_set_curved(e, 0) first");
   }
   E.wide = max_aspect;
   return 0;
@@ -1311,6 +1312,119 @@ int ttr_wide_cuts(ttr_engine* e, const uint8_t* img, int h, int w, int row_strid
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_wide_cuts");
   E.wide_cuts(img, h, w, row_stride, quads, nq, max_aspect, use_table != 0, n_out, cuts, profiles, coef);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+// ---- curved words (DESIGN.md "Curved words")
+int ttr_engine_set_curved(ttr_engine* e, int on) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (on != 0 && on != 1) throw std::runtime_error("ttr_engine_set_curved: on must be 0 or 1, got " + std::to_string(on));
+  E.refuse_while_streaming("ttr_engine_set_curved");
+  if (on) {
+    if (E.cfg.crop_mode != TTR_CROP_RECTIFIED)
+      throw std::runtime_error("ttr_engine_set_curved: curved words need crop_mode = TTR_CROP_RECTIFIED (the spine is sought inside the word's quad): create the engine with it");
+    if (E.cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("ttr_engine_set_curved: curved words do not combine with word orientation (a twin is a straight crop of the quad): create the engine with orient = TTR_ORIENT_OFF");
+    if (E.cfg.chars) throw std::runtime_error("ttr_engine_set_curved: curved words do not combine with character boxes (they are cut across the straight quad): create the engine with chars = 0");
+    if (E.wide != 0.f) throw std::runtime_error("ttr_engine_set_curved: curved words do not combine with wide words (a piece is a straight cut of the quad): ttr_engine_set_wide(e, 0) first");
+    if (E.comm) throw std::runtime_error("ttr_engine_set_curved: curved words are read by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
+  }
+  E.curved = on != 0;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_curved(const ttr_engine* e) { return e && e->e->curved ? 1 : 0; }
+
+const int32_t* ttr_result_curved(const ttr_result* r) { return r && !r->r.curved.empty() ? r->r.curved.data() : nullptr; }
+
+const float* ttr_result_outlines(const ttr_result* r) { return r && !r->r.outline.empty() ? r->r.outline.data() : nullptr; }
+
+const int64_t* ttr_result_spine_knots(const ttr_result* r) { return r && !r->r.spine_knots.empty() ? r->r.spine_knots.data() : nullptr; }
+
+int ttr_results_gather_curved(ttr_result* const* rs, int n, int32_t* curved, float* outlines, int64_t* knots) {
+  if (!rs || n < 0) return -1;
+  size_t oi = 0, flagged = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!rs[i]) continue;
+    const Result& r = rs[i]->r;
+    const size_t cnt = r.text.size();
+    const bool has = cnt > 0 && r.curved.size() == cnt;
+    if (curved) { if (has) std::copy(r.curved.begin(), r.curved.end(), curved + oi); else std::fill(curved + oi, curved + oi + cnt, 0); }
+    if (outlines) { if (has) std::copy(r.outline.begin(), r.outline.end(), outlines + 36 * oi); else std::fill(outlines + 36 * oi, outlines + 36 * (oi + cnt), 0.f); }
+    if (knots) { if (has) std::copy(r.spine_knots.begin(), r.spine_knots.end(), knots + 36 * oi); else std::fill(knots + 36 * oi, knots + 36 * (oi + cnt), (int64_t)0); }
+    if (has) for (int32_t f : r.curved) flagged += f != 0;
+    oi += cnt;
+  }
+  return (int)flagged;
+}
+
+static void curve_image_ok(const char* what, const uint8_t* img, int h, int w, int row_stride) {
+  if (!img) throw std::runtime_error("null argument");
+  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
+}
+
+int ttr_curve_frame(const float quad[8], int64_t frame[6]) {
+  TTR_GUARD_BEGIN
+  if (!quad || !frame) throw std::runtime_error("null argument");
+  if (!region_quad_ok(quad)) throw std::runtime_error("ttr_curve_frame: a coordinate is not finite or has |x| >= 32768");
+  curve_frame(quad, frame);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_curve_columns(const uint8_t* img, int h, int w, int row_stride, const int64_t frame[6], const int64_t* table, int32_t* stats) {
+  TTR_GUARD_BEGIN
+  if (!frame || !stats) throw std::runtime_error("null argument");
+  curve_image_ok("ttr_curve_columns", img, h, w, row_stride);
+  curve_columns(img, h, w, row_stride ? row_stride : w * 3, frame, table, stats);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_curve_knots(const uint8_t* img, int h, int w, int row_stride, const int64_t frame[6], int32_t* flag, int32_t hb[2], int32_t* spine, int64_t* knots, int64_t* knots1) {
+  TTR_GUARD_BEGIN
+  if (!frame) throw std::runtime_error("null argument");
+  curve_image_ok("ttr_curve_knots", img, h, w, row_stride);
+  CurveWord cw;
+  curve_word(img, h, w, row_stride ? row_stride : w * 3, frame, &cw, knots1);
+  if (flag) *flag = cw.flag;
+  if (hb) { hb[0] = cw.hb[0]; hb[1] = cw.hb[1]; }
+  if (spine) memcpy(spine, cw.spine, sizeof cw.spine);
+  if (knots) memcpy(knots, cw.table, sizeof cw.table);
+  return cw.flag;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_curve_crop(const uint8_t* img, int h, int w, int row_stride, const int64_t* knots, uint8_t* crop) {
+  TTR_GUARD_BEGIN
+  if (!knots || !crop) throw std::runtime_error("null argument");
+  curve_image_ok("ttr_curve_crop", img, h, w, row_stride);
+  curve_crop(img, h, w, row_stride ? row_stride : w * 3, knots, crop);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_curve_outline(const float quad[8], int flag, const int64_t* knots, float* outline) {
+  TTR_GUARD_BEGIN
+  if (!quad || !outline || (flag && !knots)) throw std::runtime_error("null argument");
+  curve_outline(quad, flag, knots, outline);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_curve_crops(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, int use_table, int32_t* flag, int32_t* hb,
+                    int32_t* spine, int64_t* knots, uint8_t* crops) {
+  TTR_GUARD_BEGIN
+  if (!e || nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
+  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_curve_crops");
+  E.curve_crops(img, h, w, row_stride, quads, nq, use_table != 0, flag, hb, spine, knots, crops);
   return 0;
   TTR_GUARD_END(-1)
 }

@@ -294,6 +294,10 @@ struct Result {
   std::vector<int32_t> piece_ids;           // 26 per piece
   std::vector<float> piece_prob, piece_conf, piece_quad;   // 26 / 1 / 8 per piece
   std::vector<int32_t> piece_cuts;          // 17 per item: c_0 = 0 < ... < c_n = 128 n in frame columns, -1 beyond n
+  // curved words (ttr_engine_set_curved; DESIGN.md "Curved words"): empty when off
+  std::vector<int32_t> curved;              // 1 per item: 1 = its crop was straightened along its spine
+  std::vector<float> outline;               // 36 per item: 18 points, the top edge left to right, then the bottom edge right to left
+  std::vector<int64_t> spine_knots;         // 36 per item: the knot table {Cx, Cy, Hx, Hy} x 9 in 2^-16 px (zeros for an item whose second pass did not run)
   // text blocks (cfg.blocks = 1; DESIGN.md "Text blocks"): empty / 0 when off
   std::vector<int32_t> line_block, line_pos;     // 1 per line: its block in reading order, its position inside that block
   std::vector<int32_t> block;                    // 1 per item: its line's block
@@ -417,6 +421,7 @@ struct Engine {
   DevBuf lex_records;                             // [V] 32-byte records: length | 25 class bytes | zero padding (geometry.h: lexicon_encode)
   std::vector<std::string> lex_words;             // the host copy of the words (ttr_engine_lexicon_word)
   float wide = 0.f;                               // wide words: the largest aspect a piece may have, 0 = off or 2..64 (ttr_engine_set_wide; DESIGN.md "Wide words")
+  bool curved = false;                            // curved words: straighten the crops of words set on an arc (ttr_engine_set_curved; DESIGN.md "Curved words")
   ClassMask charset{};                            // classes the recogniser may not choose (ttr_engine_set_charset; DESIGN.md "Character sets"); zero = no set
   // the engine's pattern (ttr_engine_set_pattern; DESIGN.md "Patterns"): empty = none.  `pattern` is pattern_src compiled under `charset`; its table lives in
   // pattern_dev (delta | mind, uploaded once by set_engine_pattern: nothing travels per call)
@@ -492,6 +497,8 @@ struct Engine {
   }
   DevBuf wide_side;                               // wide words: the side block (wide.hip), [Wn][17] int32 cuts | [Wn][2048] u16 profile
   PinnedBuf h_wide[2];                            // ... per slot: the cuts' host copy
+  DevBuf curve_side;                              // curved words: the side block (curve.hip), [N] flag | [N][2] hb | [N][2][9] spine | [N][9][4] int64 knots
+  PinnedBuf h_curve[2];                           // ... per slot: its host copy
   DevBuf blocks_side;                             // text blocks: the side block (blocks.hip)
   PinnedBuf h_blocks[2];                          // ... per slot: its host copy
   DevBuf chars_map[2], chars_in, chars_side;      // character boxes: per slot the batch's region planes (a copy of ccl.tnorm); coef | page_of | turns | nchars; the side block (chars.hip)
@@ -800,6 +807,9 @@ struct Engine {
     int X = 0;
     std::vector<WideWord> wide;
     std::vector<int32_t> wide_of;
+    // curved words (plan_curved; DESIGN.md "Curved words"): with `curved`, one entry per crop - its frame, page and row
+    bool curved = false;
+    std::vector<CurveIn> curve;
     int det_groups = -1;               // CRAFT groups enqueued for it (group_ev[det_groups]: behind the copy of its detector range word)
     bool live = false, enqueued = false;
     std::vector<int32_t> all_counts;   // with a communicator: crops per page of every rank [world][n]
@@ -842,6 +852,12 @@ struct Engine {
   // wide words: plans every crop of B from quads [N][8] (the word's quad: deskew_quad's on page calls, the caller's on region calls) under the engine's `wide`;
   // appends the extra rows to rects / coef / row_masks and fills wide / wide_of / X.  Host only; a no-op with wide off.
   void plan_wide(PageBatch& B, const float* quads);
+  // curved words: one CurveIn per crop of B from quads [N][8] (the quads plan_wide takes) under the engine's `curved`.  Host only; a no-op with curved off.
+  void plan_curved(PageBatch& B, const float* quads);
+  // the stage form (ttr_curve_crops): a host image and host quads through the kind-1 packer and curve_crop_kernel -> flag [nq], hb [nq][2], spine [nq][2][9],
+  // knots [nq][9][4], crops [nq][32][128][3]
+  void curve_crops(const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, bool use_table, int32_t* flag, int32_t* hb, int32_t* spine,
+                   int64_t* knots, uint8_t* crops_out);
   // the stage form (ttr_wide_cuts): a host image and host quads through wide_cut_kernel -> n [nq], cuts [nq][17], profiles [nq][2048], coef [nq][16][8]
   void wide_cuts(const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, float max_aspect, bool use_table, int32_t* n_out, int32_t* cuts,
                  uint16_t* profiles, int64_t* coef);
@@ -882,7 +898,7 @@ struct Engine {
   // lexicon matches' (lexicon.hip, B.lex_m per item) or null; pat_logp: best mode's log-probabilities (pattern.hip, one per item) or null
   void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
                     std::vector<Result>& results, const void* alts_side = nullptr, const void* lex_side = nullptr, const int32_t* wide_cuts = nullptr,
-                    const float* pat_logp = nullptr);
+                    const float* pat_logp = nullptr, const void* curve_block = nullptr);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it

@@ -298,7 +298,7 @@ void Engine::detect_collect_local(PageBatch& B) {
   B.rects.clear(); B.page_of.clear(); B.coef.clear(); B.twin.clear();   // x0,y0,x1,y1,page per crop; page index per crop; rectified crops' coefficients; twins'
   const int K = orient_k();
   std::vector<Pt2f> oq;                                        // orient != 0: each word's quad Q (DESIGN.md "Word orientation")
-  std::vector<float> wq;                                       // wide != 0: each word's quad (DESIGN.md "Wide words")
+  std::vector<float> wq;                                       // wide != 0 or curved: each word's quad (DESIGN.md "Wide words", "Curved words")
   host_us[1] = host_us[2] = host_us[3] = 0.f;
   for (int gi = 0; gi < groups; ++gi) ccl_collect(gi * GP, std::min(GP, n - gi * GP), gi, B.H2, B.W2, dets);
   // the detector's range word of THIS batch, before any of its boxes is used: a saturated heat map fails this batch and no other
@@ -338,7 +338,7 @@ void Engine::detect_collect_local(PageBatch& B) {
         const int kind = deskew_quad(b, q, cf);
         deskew_fixed(cf, fx);
         B.coef.insert(B.coef.end(), {(int64_t)kind, fx[0], fx[1], fx[2], fx[3], fx[4], fx[5], 0});
-        if (wide != 0.f) for (int k = 0; k < 4; ++k) { wq.push_back(q[k].x); wq.push_back(q[k].y); }
+        if (wide != 0.f || curved) for (int k = 0; k < 4; ++k) { wq.push_back(q[k].x); wq.push_back(q[k].y); }
       } else if (K > 1) {
         box_edge_quad(x0, y0, x1, y1, q);
       }
@@ -347,6 +347,7 @@ void Engine::detect_collect_local(PageBatch& B) {
   }
   B.N = (int)B.page_of.size();
   plan_wide(B, wq.data());
+  plan_curved(B, wq.data());
   for (int j = 1; j < K; ++j) {                                 // the twins, candidate-major in ascending turn
     const int t = K == 2 ? 2 * j : j;
     for (int c = 0; c < B.N; ++c) {
@@ -385,6 +386,21 @@ void Engine::plan_wide(PageBatch& B, const float* quads) {
     }
 }
 
+void Engine::plan_curved(PageBatch& B, const float* quads) {
+  B.curved = curved; B.curve.clear();
+  if (!curved) return;
+  const int N = B.N;
+  if (B.coef.size() != (size_t)N * 8 || B.rects.size() != (size_t)N * 5) throw std::runtime_error("curved words: coefficient count does not match the crop count");
+  B.curve.resize((size_t)N);
+  for (int c = 0; c < N; ++c) {
+    if (!region_quad_ok(quads + 8 * (size_t)c)) throw std::runtime_error("curved words: a corner of word " + std::to_string(c) + " is not finite or lies beyond 32768 px");
+    CurveIn W{};
+    curve_frame(quads + 8 * (size_t)c, W.f);
+    W.page = B.page_of[(size_t)c]; W.row = c;
+    B.curve[(size_t)c] = W;
+  }
+}
+
 void Engine::pack_batch_crops(const PageBatch& B, int sl) {
   const int rows = B.N + B.X;                                  // wide words: X more rows behind the batch's N
   rects_dev.ensure(B.rects.size() * 4);
@@ -402,12 +418,14 @@ void Engine::pack_batch_crops(const PageBatch& B, int sl) {
   }
   if (B.coef.size() != (size_t)rows * 8 || B.rects.size() != (size_t)rows * 5) throw std::runtime_error("rectified crops: coefficient count does not match the crop count");
   // wide words: the table of the batch's wide words travels behind the coefficients, in the same copy
-  const size_t coef_b = B.coef.size() * 8, words_b = B.wide.size() * sizeof(WideWord);
-  coef_dev.ensure(coef_b + words_b);
-  h_coef[sl].ensure(coef_b + words_b);
+  // (curved words: the batch's CurveIn entries likewise, behind those)
+  const size_t coef_b = B.coef.size() * 8, words_b = B.wide.size() * sizeof(WideWord), curve_b = B.curve.size() * sizeof(CurveIn);
+  coef_dev.ensure(coef_b + words_b + curve_b);
+  h_coef[sl].ensure(coef_b + words_b + curve_b);
   memcpy(h_coef[sl].p, B.coef.data(), coef_b);
   if (words_b) memcpy(h_coef[sl].as<uint8_t>() + coef_b, B.wide.data(), words_b);
-  TTR_HIP_CHECK(hipMemcpyAsync(coef_dev.p, h_coef[sl].p, coef_b + words_b, hipMemcpyHostToDevice, stream));
+  if (curve_b) memcpy(h_coef[sl].as<uint8_t>() + coef_b + words_b, B.curve.data(), curve_b);
+  TTR_HIP_CHECK(hipMemcpyAsync(coef_dev.p, h_coef[sl].p, coef_b + words_b + curve_b, hipMemcpyHostToDevice, stream));
   if (words_b) {   // the cuts, and every piece's packer row straight into coef_dev (wide.hip)
     const int Wn = (int)B.wide.size();
     wide_side.ensure(wide_side_bytes(Wn));
@@ -416,6 +434,13 @@ void Engine::pack_batch_crops(const PageBatch& B, int sl) {
   }
   if (B.mixed) { launch_pack_crops_rect_pages(table, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), rows, stream); TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream)); }
   else launch_pack_crops_rect(P0.data, page_bytes, P0.stride, P0.h, P0.w, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), rows, stream);
+  if (curve_b) {   // curved words: behind the unchanged packer, the rows of the curved ones are made again along their spines (curve.hip)
+    const int Cn = (int)B.curve.size();
+    curve_side.ensure(curve_side_bytes(Cn));
+    launch_curve_crop(reinterpret_cast<const CurveIn*>(coef_dev.as<uint8_t>() + coef_b + words_b), Cn, P0.data, page_bytes, P0.stride, P0.h, P0.w, table, crops.as<uint8_t>(), rows,
+                      curve_side.as<int>(), stream);
+    if (B.mixed) TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the table's last reader of this batch is now this kernel)
+  }
 }
 
 void Engine::pack_twin_crops(const PageBatch& B, int sl) {
@@ -662,6 +687,55 @@ void Engine::wide_cuts(const uint8_t* img, int h, int w, int row_stride, const f
   if (profiles) memcpy(profiles, side.data() + (size_t)nq * 17 * 4, (size_t)nq * 2048 * 2);
 }
 
+void Engine::curve_crops(const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, bool use_table, int32_t* flag, int32_t* hb, int32_t* spine,
+                         int64_t* knots, uint8_t* crops_out) {
+  if (nq <= 0) return;
+  if ((size_t)h * w > ((size_t)1 << 28)) throw std::runtime_error("ttr_curve_crops: bad image size");
+  // coef_dev: coef int64 [nq][8] | words [nq]; rects_dev: [nq][5] (kind 1 reads the coefficients alone; the rectangle only has to be non-empty)
+  const size_t coef_b = (size_t)nq * 64, words_b = (size_t)nq * sizeof(CurveIn), side_b = curve_side_bytes(nq), img_b = (size_t)h * w * 3, crop_b = (size_t)nq * kCropBytes;
+  h_coef[0].ensure(coef_b + words_b); coef_dev.ensure(coef_b + words_b); h_rects[0].ensure((size_t)nq * 20); rects_dev.ensure((size_t)nq * 20);
+  curve_side.ensure(side_b); staging_img.ensure(img_b); crops.ensure(crop_b);
+  std::vector<uint8_t> side(side_b);
+  int64_t* coef = h_coef[0].as<int64_t>();
+  CurveIn* words = reinterpret_cast<CurveIn*>(h_coef[0].as<uint8_t>() + coef_b);
+  int* rects = h_rects[0].as<int>();
+  for (int i = 0; i < nq; ++i) {
+    const float* q = quads + 8 * (size_t)i;
+    if (!region_quad_ok(q)) throw std::runtime_error("ttr_curve_crops: quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+    int64_t fx[6];
+    region_coef(q, fx);
+    coef[8 * (size_t)i] = 1; coef[8 * (size_t)i + 7] = 0;
+    for (int k = 0; k < 6; ++k) coef[8 * (size_t)i + 1 + k] = fx[k];
+    CurveIn W{};
+    curve_frame(q, W.f);
+    W.page = 0; W.row = i;
+    words[i] = W;
+    const int rc[5] = {0, 0, 1, 1, 0};
+    memcpy(rects + 5 * (size_t)i, rc, sizeof rc);
+  }
+  TTR_HIP_CHECK(hipMemcpy2DAsync(staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(coef_dev.p, h_coef[0].p, coef_b + words_b, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[0].p, (size_t)nq * 20, hipMemcpyHostToDevice, stream));
+  const PageRow* table = nullptr;
+  if (use_table) {
+    std::vector<Page> pages(1, Page{staging_img.as<uint8_t>(), h, w, w * 3, CanvasGeom{h, w, h, w, 1.f}});
+    upload_page_table(pages, 0);
+    table = page_table[0].as<PageRow>();
+  }
+  if (table) launch_pack_crops_rect_pages(table, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), nq, stream);
+  else launch_pack_crops_rect(staging_img.as<uint8_t>(), 0, w * 3, h, w, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), nq, stream);
+  launch_curve_crop(reinterpret_cast<const CurveIn*>(coef_dev.as<uint8_t>() + coef_b), nq, staging_img.as<uint8_t>(), 0, w * 3, h, w, table, crops.as<uint8_t>(), nq,
+                    curve_side.as<int>(), stream);
+  if (use_table) TTR_HIP_CHECK(hipEventRecord(table_ev[0], stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(side.data(), curve_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  if (crops_out) TTR_HIP_CHECK(hipMemcpyAsync(crops_out, crops.p, crop_b, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  if (flag) memcpy(flag, side.data(), (size_t)nq * 4);
+  if (hb) memcpy(hb, side.data() + (size_t)nq * 4, (size_t)nq * 8);
+  if (spine) memcpy(spine, side.data() + (size_t)nq * 12, (size_t)nq * 72);
+  if (knots) memcpy(knots, side.data() + curve_side_table_offset(nq), (size_t)nq * 288);
+}
+
 void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
   const int line_words = cfg.lines && N > 0 ? stage_batch_lines(B, sl) : 0;   // text lines: the host part, before anything of this batch is enqueued
@@ -681,6 +755,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     crops.ensure((size_t)(N + T + X) * kCropBytes);
     logits.ensure((size_t)std::max(std::max(N, X), T) * kLogitWords * 4);
     if (X) h_wide[sl].ensure(B.wide.size() * 17 * 4);
+    if (!B.curve.empty()) h_curve[sl].ensure(curve_side_bytes(N));
     const RecOut cand = T ? rec_block(orient_cand, T) : RecOut{};
     const size_t side_b = ((size_t)N * (K + 1) + B.n) * 4;   // [N] turn | [N][K] candidate conf | [pages] page turn
     if (T) { orient_side.ensure(side_b); h_orient[sl].ensure(side_b); }
@@ -729,6 +804,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (B.lex_m) TTR_HIP_CHECK(hipMemcpyAsync(h_lex[sl].p, lex_side.p, lex_side_bytes(N, B.lex_m), hipMemcpyDeviceToHost, stream));   // the lexicon matches' side block, likewise
     if (B.pat_best) TTR_HIP_CHECK(hipMemcpyAsync(h_pat_logp[sl].p, pat_logp_dev.p, (size_t)N * 4, hipMemcpyDeviceToHost, stream));   // best mode's log-probabilities, likewise
     if (X) TTR_HIP_CHECK(hipMemcpyAsync(h_wide[sl].p, wide_side.p, B.wide.size() * 17 * 4, hipMemcpyDeviceToHost, stream));   // the wide words' cuts (the profile stays on the device)
+    if (!B.curve.empty()) TTR_HIP_CHECK(hipMemcpyAsync(h_curve[sl].p, curve_side.p, curve_side_bytes(N), hipMemcpyDeviceToHost, stream));   // the curved words' side block
   } else {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
@@ -769,13 +845,14 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   const void* lex_block = B.lex_m && N > 0 ? h_lex[B.slot].p : nullptr;                         // the side block (lexicon.hip)
   const int32_t* wide_block = B.X && N > 0 ? h_wide[B.slot].as<int32_t>() : nullptr;            // the cuts of the side block (wide.hip)
   const float* pat_logp_block = B.pat_best && N > 0 ? h_pat_logp[B.slot].as<float>() : nullptr;  // the side block (pattern.hip, best mode)
-  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block, wide_block, pat_logp_block);
+  const void* curve_block = !B.curve.empty() && N > 0 ? h_curve[B.slot].p : nullptr;           // the side block (curve.hip)
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block, wide_block, pat_logp_block, curve_block);
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
 
 void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                          std::vector<Result>& results, const void* alts_side, const void* lex_side, const int32_t* wide_cuts, const float* pat_logp) {
+                          std::vector<Result>& results, const void* alts_side, const void* lex_side, const int32_t* wide_cuts, const float* pat_logp, const void* curve_block) {
   const int n = B.n, N = B.N, K = orient_k();
   const std::vector<int> first = page_first(B.page_of, n);
   // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
@@ -829,6 +906,24 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
       tesseract_bbox(B.boxes[pg][k], bb);                                    // :511
       r.bbox.insert(r.bbox.end(), bb, bb + 4);
       push_quad(B.boxes[pg][k], r.quad);
+    }
+    if (B.curved && cnt > 0) {   // curved words: every item's flag, outline and knot table, checked before anything is built on them
+      if (!curve_block) throw std::runtime_error("curved words: the batch carries no side block");
+      const int32_t* cs = static_cast<const int32_t*>(curve_block);
+      const int64_t* ct = reinterpret_cast<const int64_t*>(static_cast<const uint8_t*>(curve_block) + curve_side_table_offset(N));
+      r.curved.assign((size_t)cnt, 0); r.outline.assign((size_t)cnt * 36, 0.f); r.spine_knots.assign((size_t)cnt * 36, 0);
+      for (int k = 0; k < cnt; ++k) {
+        const size_t c = (size_t)(c0 + k);
+        CurveWord w{};
+        w.flag = cs[c]; w.hb[0] = cs[(size_t)N + 2 * c]; w.hb[1] = cs[(size_t)N + 2 * c + 1];
+        memcpy(w.table, ct + 36 * c, sizeof w.table);
+        if (!curve_word_valid(w))
+          throw std::runtime_error("curved words: the side block of word " + std::to_string(k) + " of page " + std::to_string(pg) +
+                                   " holds a flag that is not 0 or 1, a half band outside 0..32 or a knot outside the int32 pixel range");
+        r.curved[(size_t)k] = w.flag;
+        memcpy(&r.spine_knots[(size_t)k * 36], w.table, sizeof w.table);
+        curve_outline(&r.quad[(size_t)k * 8], w.flag, &w.table[0][0], &r.outline[(size_t)k * 36]);
+      }
     }
     if (B.wide_aspect != 0.f && cnt > 0) {   // wide words: every item's pieces; a wide item's text and conf joined from them (its ids and prob stay its first piece's)
       r.piece_first.assign((size_t)cnt + 1, 0);
@@ -1177,6 +1272,7 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
     }
   }
   plan_wide(B, B.region_quad.data());   // wide words: the pieces' rows behind the call's n (DESIGN.md "Wide words")
+  plan_curved(B, B.region_quad.data());   // curved words: every region is a candidate (DESIGN.md "Curved words")
   const double th0 = now_us();
   for (int k = 0; k < 3; ++k) TTR_HIP_CHECK(hipEventRecord(ev[k], stream));   // no detector: its two stage times of this call are zero
   if (n > 0) upload_page_table(B.pages, 0);
@@ -1188,6 +1284,7 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
 
 void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results) {
   if (wide != 0.f) throw std::runtime_error("latency mode does not support wide words: ttr_engine_set_wide(e, 0) first");
+  if (curved) throw std::runtime_error("latency mode does not support curved words: ttr_engine_set_curved(e, 0) first");
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");
   if (cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("latency mode does not support word orientation: create the engine with orient = TTR_ORIENT_OFF");
   if (cfg.blocks) throw std::runtime_error("latency mode does not support text blocks: create the engine with blocks = 0");

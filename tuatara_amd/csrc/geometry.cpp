@@ -2,6 +2,7 @@
 // after connected-component labelling (tuatara.cpp:162-179, :236-274, :416) and its
 // Tokenizer (tuatara.cpp:25-117).  float32 throughout where OpenCV is float32.
 #include "geometry.h"
+#include "curve_rule.h"
 
 #include <algorithm>
 #include <climits>
@@ -222,6 +223,141 @@ bool wide_cuts_valid(const int32_t cuts[17], int n) {
     if (wd < kWideWLo || wd > kWideWHi) return false;
   }
   for (int j = n + 1; j <= kWideMaxPieces; ++j) if (cuts[j] != -1) return false;
+  return true;
+}
+
+// ---------------------------------------------------------------- curved words (DESIGN.md "Curved words"; the integer steps are curve_rule.h's)
+void curve_frame(const float* q, int64_t frame[6]) {
+  const double Ax = ((double)q[2] - (double)q[0]) / (double)kCurveU, Bx = ((double)q[6] - (double)q[0]) / (double)kCurveV;
+  const double Ay = ((double)q[3] - (double)q[1]) / (double)kCurveU, By = ((double)q[7] - (double)q[1]) / (double)kCurveV;
+  double x0 = (double)q[0] + 0.5 * Ax;
+  x0 = x0 + 0.5 * Bx;
+  double y0 = (double)q[1] + 0.5 * Ay;
+  y0 = y0 + 0.5 * By;
+  const double cf[6] = {x0, Ax, Bx, y0, Ay, By};
+  deskew_fixed(cf, frame);
+}
+
+void curve_columns(const uint8_t* image, int h, int w, int stride, const int64_t frame[6], const int64_t* table, int32_t* stats) {
+  for (int u = 0; u < kCurveU; ++u) {
+    const CurveColumn col = curve_column(frame, table, u);
+    CurveAcc acc{};
+    for (int v = -1; v <= kCurveV; ++v) {
+      int64_t x, y;
+      curve_column_at(col, v, &x, &y);
+      int64_t ix = (x + 32768) >> 16, iy = (y + 32768) >> 16;
+      ix = ix < 0 ? 0 : ix > w - 1 ? w - 1 : ix;
+      iy = iy < 0 ? 0 : iy > h - 1 ? h - 1 : iy;
+      const uint8_t* p = image + (size_t)iy * (size_t)stride + (size_t)ix * 3;
+      curve_acc_step(acc, v, (int32_t)p[0] + 2 * (int32_t)p[1] + (int32_t)p[2]);
+    }
+    stats[u] = acc.G; stats[kCurveU + u] = acc.M; stats[2 * kCurveU + u] = acc.first; stats[3 * kCurveU + u] = acc.last;
+  }
+}
+
+// the statistics of one pass -> the nine spine rows and the half band; returns how many windows hold a valid column
+static int curve_knots(const int32_t* stats, int32_t spine[9], int32_t* hb) {
+  const int32_t *G = stats, *M = stats + kCurveU, *first = stats + 2 * kCurveU, *last = stats + 3 * kCurveU;
+  int64_t gsum = 0;
+  for (int u = 0; u < kCurveU; ++u) gsum += G[u];
+  const int32_t thr = curve_ink_threshold(gsum);
+  uint8_t inked[kCurveU], valid[kCurveU];
+  int32_t emax = 0;
+  for (int u = 0; u < kCurveU; ++u) {
+    inked[u] = curve_inked(G[u], first[u], thr);
+    if (inked[u]) emax = std::max(emax, last[u] - first[u]);
+  }
+  for (int u = 0; u < kCurveU; ++u) valid[u] = curve_valid(inked[u] != 0, first[u], last[u], emax);
+  int32_t r[kCurveK], t[kCurveK], own[kCurveK], carried[kCurveK];
+  int n = 0;
+  for (int j = 0; j < kCurveK; ++j) { curve_window(j, G, M, valid, r, t, own); n += own[j]; }
+  for (int j = 0; j < kCurveK; ++j) { spine[j] = 0; carried[j] = own[j] ? curve_carry(j, r, t, own) : 0; }
+  *hb = 0;
+  if (n == 0) return 0;
+  for (int j = 0; j < kCurveK; ++j) spine[j] = own[j] ? carried[j] : curve_fill(j, carried, own);
+  int32_t reach = 0;
+  for (int u = 0; u < kCurveU; ++u)
+    if (inked[u]) reach = std::max(reach, curve_reach(spine, u, first[u], last[u]));
+  *hb = curve_half_band(reach);
+  return n;
+}
+
+void curve_word(const uint8_t* image, int h, int w, int stride, const int64_t frame[6], CurveWord* out, int64_t* table1_out) {
+  std::memset(out, 0, sizeof(CurveWord));
+  int64_t table1[kCurveK][4] = {};
+  std::vector<int32_t> stats((size_t)4 * kCurveU);
+  int64_t C[kCurveK][2];
+  // pass 1: the frame's columns
+  curve_columns(image, h, w, stride, frame, nullptr, stats.data());
+  const int n1 = curve_knots(stats.data(), out->spine[0], &out->hb[0]);
+  int ok = n1 >= 3;
+  if (ok) {
+    const int64_t L = curve_isqrt(frame[2] * frame[2] + frame[5] * frame[5]);
+    for (int j = 0; j < kCurveK; ++j) curve_centre_frame(frame, j, out->spine[0][j], C[j]);
+    for (int j = 0; j < kCurveK; ++j) ok &= curve_normal(&C[0][0], j, (int64_t)out->hb[0] * L, frame[2], frame[5], table1[j]);
+    if (table1_out) std::memcpy(table1_out, table1, sizeof(table1));
+    if (ok) {
+      // pass 2: the same measurement over the band of pass 1
+      curve_columns(image, h, w, stride, frame, &table1[0][0], stats.data());
+      const int n2 = curve_knots(stats.data(), out->spine[1], &out->hb[1]);
+      ok = n2 >= 3;
+      if (ok) {
+        const int64_t L2 = ((int64_t)out->hb[0] * out->hb[1] * L) >> 5;
+        for (int j = 0; j < kCurveK; ++j) curve_centre_band(&table1[0][0], j, out->spine[1][j], C[j]);
+        for (int j = 0; j < kCurveK; ++j) ok &= curve_normal(&C[0][0], j, L2, frame[2], frame[5], out->table[j]);
+        out->flag = ok && out->hb[0] * out->hb[1] <= 32 * kCurveHbCurved && curve_bent(&out->table[0][0], L2);
+      }
+    }
+  } else if (table1_out) {
+    std::memset(table1_out, 0, sizeof(table1));
+  }
+}
+
+void curve_crop(const uint8_t* image, int h, int w, int stride, const int64_t* table, uint8_t* crop) {
+  for (int v = 0; v < 32; ++v)
+    for (int u = 0; u < kCurveU; ++u) {
+      int64_t sx, sy;
+      curve_sample_at(table, u, v, &sx, &sy);
+      const int64_t ix = sx >> 16, iy = sy >> 16;
+      const int fx = (int)((sx >> 5) & 2047), fy = (int)((sy >> 5) & 2047);
+      const int64_t x0 = std::min<int64_t>(std::max<int64_t>(ix, 0), w - 1), x1 = std::min<int64_t>(std::max<int64_t>(ix + 1, 0), w - 1);
+      const int64_t y0 = std::min<int64_t>(std::max<int64_t>(iy, 0), h - 1), y1 = std::min<int64_t>(std::max<int64_t>(iy + 1, 0), h - 1);
+      const uint8_t *r0 = image + (size_t)y0 * (size_t)stride, *r1 = image + (size_t)y1 * (size_t)stride;
+      for (int c = 0; c < 3; ++c) {
+        const int t = (2048 - fx) * r0[x0 * 3 + c] + fx * r0[x1 * 3 + c];
+        const int b = (2048 - fx) * r1[x0 * 3 + c] + fx * r1[x1 * 3 + c];
+        const int val = ((2048 - fy) * t + fy * b + (1 << 21)) >> 22;
+        crop[((size_t)v * kCurveU + u) * 3 + c] = (uint8_t)(val > 255 ? 255 : val);
+      }
+    }
+}
+
+void curve_outline(const float* q, int flag, const int64_t* table, float* out) {
+  for (int j = 0; j < kCurveK; ++j) {
+    float* top = out + 2 * j;
+    float* bot = out + 2 * (2 * kCurveK - 1 - j);
+    if (flag) {
+      const int64_t* t = table + 4 * j;
+      top[0] = (float)((double)(t[0] - t[2]) / 65536.); top[1] = (float)((double)(t[1] - t[3]) / 65536.);
+      bot[0] = (float)((double)(t[0] + t[2]) / 65536.); bot[1] = (float)((double)(t[1] + t[3]) / 65536.);
+    } else {
+      const double s = (double)j / (double)kCurveS;
+      top[0] = (float)((double)q[0] + s * ((double)q[2] - (double)q[0])); top[1] = (float)((double)q[1] + s * ((double)q[3] - (double)q[1]));
+      bot[0] = (float)((double)q[6] + s * ((double)q[4] - (double)q[6])); bot[1] = (float)((double)q[7] + s * ((double)q[5] - (double)q[7]));
+    }
+  }
+}
+
+bool curve_word_valid(const CurveWord& w) {
+  if (w.flag != 0 && w.flag != 1) return false;
+  for (int p = 0; p < 2; ++p) if (w.hb[p] < 0 || w.hb[p] > kCurveHbMax) return false;
+  if (w.flag)
+    for (int j = 0; j < kCurveK; ++j)
+      for (int c = 0; c < 2; ++c)
+        for (int sgn = -1; sgn <= 1; sgn += 2) {
+          const int64_t px = (w.table[j][c] + sgn * w.table[j][2 + c]) >> 16;
+          if (px < (int64_t)INT32_MIN || px > (int64_t)INT32_MAX) return false;
+        }
   return true;
 }
 

@@ -115,6 +115,28 @@ void wide_piece_quads(const float* quad8, const int32_t* cuts, int n, float* qua
 // what decode_pages accepts from the device: c_0 = 0, ascending, c_n = 128 n, every width in [64, 192], -1 beyond n
 bool wide_cuts_valid(const int32_t cuts[17], int n);
 
+// Curved words (ttr_engine_set_curved; DESIGN.md "Curved words").  A word set on an arc is straightened along a spine found in the page's own pixels; the integer
+// steps live in curve_rule.h, shared with curve_crop_kernel (curve.hip).  What the rule gives for one word:
+struct CurveWord {
+  int32_t flag;                 // 1 = curved: the crop is resampled along the knot table
+  int32_t hb[2];                // the half band of pass 1 (frame rows) and of pass 2 (band rows); 0 = the pass did not run or found no ink
+  int32_t spine[2][9];          // the nine spine rows of either pass, in 1/256 row
+  int64_t table[9][4];          // the knot table {Cx, Cy, Hx, Hy} in 2^-16 px (zeros when pass 2 did not run)
+};
+// quad (8 floats tl, tr, br, bl) -> frame = {X0, Ax, Bx, Y0, Ay, By} in 2^-16 px over 128 columns and 64 rows: double, one rounding per statement, llrint(65536 x)
+void curve_frame(const float* quad8, int64_t frame[6]);
+// the column statistics G | M | first | last, [4][128] int32, of a page u8 [h][w][3] (row stride in bytes): table null = pass 1 over the frame, else pass 2
+// over the band of the knot table [9][4]
+void curve_columns(const uint8_t* image, int h, int w, int stride, const int64_t frame[6], const int64_t* table, int32_t* stats);
+// the whole rule on one frame; table1 (may be null) receives pass 1's knot table [9][4]
+void curve_word(const uint8_t* image, int h, int w, int stride, const int64_t frame[6], CurveWord* out, int64_t* table1 = nullptr);
+// the crop u8 [32][128][3] of a knot table: the kind-1 sampler's arithmetic at the table's positions
+void curve_crop(const uint8_t* image, int h, int w, int stride, const int64_t* table, uint8_t* crop);
+// the outline [18][2]: flag != 0: C_j - H_j left to right, then C_j + H_j right to left; else the quad's long sides at the same nine stations
+void curve_outline(const float* quad8, int flag, const int64_t* table, float* out36);
+// what decode_pages accepts from the device: flag 0 or 1, half bands in 0..32, and with flag 1 every knot's C -+ H inside the int32 pixel range
+bool curve_word_valid(const CurveWord& w);
+
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.
 struct Component {

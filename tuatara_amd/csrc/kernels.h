@@ -349,6 +349,17 @@ inline size_t wide_side_bytes(int Wn) { return (size_t)Wn * (17 * 4 + 2048 * 2);
 // null: images / page_bytes / stride / h / w of a uniform batch, else the device page table
 void launch_wide_cut(const WideWord* words, int Wn, const uint8_t* images, size_t page_bytes, int stride, int h, int w, const PageRow* table, int64_t* coef8,
                      int rows, int* side, hipStream_t s);
+// ---- curve.hip (DESIGN.md "Curved words")
+// one candidate word of a batch: its frame (geometry.h: curve_frame), its page (the rects' page index / the PageRow index) and its row of the crop batch
+struct CurveIn { int64_t f[6]; int32_t page, row, pad[2]; };
+static_assert(sizeof(CurveIn) == 64, "CurveIn is one 64-byte entry");
+// the side block of N words: [N] flag | [N][2] hb | [N][2][9] spine (int32) | 8-byte aligned: [N][9][4] int64 knot table
+constexpr size_t curve_side_table_offset(int N) { return ((size_t)N * 21 * 4 + 7) & ~(size_t)7; }
+constexpr size_t curve_side_bytes(int N) { return curve_side_table_offset(N) + (size_t)N * 36 * 8; }
+// curve_crop_kernel: the rule on every word; the rows of `crops` [rows][32][128][3] of the curved ones are overwritten.  The pages as the rect packers take
+// them - table null: images / page_bytes / stride / h / w of a uniform batch, else the device page table
+void launch_curve_crop(const CurveIn* words, int N, const uint8_t* images, size_t page_bytes, int stride, int h, int w, const PageRow* table, uint8_t* crops,
+                       int rows, int* side, hipStream_t s);
 // get_detected_boxes' per-component tail on the GPU (tuatara.cpp:162-179: niter, ROI, dilation, findNonZero + minAreaRect): one lane per candidate, geometry.cpp's
 // arithmetic step for step (float32 calipers, double where OpenCV is double) -> CclBuffers::rects.  After launch_ccl on the same stream.
 void launch_ccl_rects(const CclBuffers& b, int pages, int H, int W, hipStream_t s);

@@ -25,6 +25,7 @@ ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int o
   ttr_config_default(&cfg);
   if (const char* p = std::getenv("TUATARA_CROP_MODE")) cfg.crop_mode = std::atoi(p);
   if (std::getenv("TUATARA_WIDE")) cfg.crop_mode = TTR_CROP_RECTIFIED;   // wide words read on rectified crops (DESIGN.md "Wide words")
+  if (const char* p = std::getenv("TUATARA_CURVED")) if (std::string(p) == "1") cfg.crop_mode = TTR_CROP_RECTIFIED;   // so do curved words (DESIGN.md "Curved words")
   if (crop_mode >= 0) cfg.crop_mode = crop_mode;
   if (const char* p = std::getenv("TUATARA_ORIENT")) {
     const std::string v(p);
@@ -65,9 +66,9 @@ struct CharsetScope {
   ttr_engine* e;
   std::unique_lock<std::mutex> turn;
   bool set = false, ok = true;
-  bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false;
+  bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false, curved_set = false;
   CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
-               std::string pattern = std::string(), float wide = 0.f, bool pattern_best = false) : e(e_) {
+               std::string pattern = std::string(), float wide = 0.f, bool pattern_best = false, bool curved = false) : e(e_) {
     {
       std::lock_guard<std::mutex> lk(g_mu);
       auto& m = g_call_mu[e];
@@ -97,6 +98,11 @@ struct CharsetScope {
       if (ttr_engine_set_wide(e, wide) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
       wide_set = true;
     }
+    if (!curved) if (const char* p = std::getenv("TUATARA_CURVED")) curved = std::string(p) == "1";
+    if (curved) {   // curved words (DESIGN.md "Curved words"): on for the call, like the set
+      if (ttr_engine_set_curved(e, 1) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      curved_set = true;
+    }
     if (pattern.empty()) if (const char* p = std::getenv("TUATARA_PATTERN")) pattern = p;
     if (!allow.empty() || !deny.empty()) {
       if (ttr_engine_set_charset(e, allow.c_str(), deny.c_str()) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
@@ -116,6 +122,7 @@ struct CharsetScope {
     if (pattern_set) ttr_engine_set_pattern(e, nullptr);
     if (best_set) ttr_engine_set_pattern_decode(e, TTR_PATTERN_GREEDY);
     if (wide_set) ttr_engine_set_wide(e, 0.f);
+    if (curved_set) ttr_engine_set_curved(e, 0);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
     if (alts_set) ttr_engine_set_alternatives(e, 0);
     if (lex_set) ttr_engine_set_lexicon(e, nullptr, 0, 0);
@@ -200,6 +207,12 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
       o.pieces.push_back(std::move(p));
     }
   }
+  o.curved = false; o.outline.clear();
+  if (const int32_t* cv = ttr_result_curved(r)) {
+    const float* ol = ttr_result_outlines(r);
+    o.curved = cv[i] != 0;
+    o.outline.assign(ol + 36 * (size_t)i, ol + 36 * (size_t)i + 36);
+  }
   o.chars.clear();
   if (const int32_t* cf = ttr_result_char_first(r)) {
     const float *cq = ttr_result_char_quads(r), *cb = ttr_result_char_bboxes(r);
@@ -229,10 +242,10 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
                           const std::string& outputs_dir, int crop_mode, int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
                                         int blocks = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0,
                                         const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string(), float wide = 0.f,
-                                        bool pattern_best = false) {
+                                        bool pattern_best = false, bool curved = false) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern, wide, pattern_best);
+  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern, wide, pattern_best, curved);
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
@@ -444,6 +457,13 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
   }
   return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, TTR_CROP_RECTIFIED, orient, orient_page ? 1 : 0, lines ? 1 : -1,
                                chars ? 1 : -1, blocks ? 1 : -1, allowlist, blocklist, 0, nullptr, 0, std::string(), wide.max_aspect);
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool /*rectify*/, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, Curved) {
+  return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, TTR_CROP_RECTIFIED, orient, orient_page ? 1 : 0, lines ? 1 : -1,
+                               chars ? 1 : -1, blocks ? 1 : -1, allowlist, blocklist, 0, nullptr, 0, std::string(), 0.f, false, true);
 }
 
 std::string last_call_error() { return g_call_error; }

@@ -246,6 +246,18 @@ SYMBOLS = [
     ("ttr_wide_piece_coef", _I, [C.POINTER(C.c_int64), _I, _I, C.POINTER(C.c_int64)]),
     ("ttr_wide_piece_quads", _I, [_PF, _PI, _I, _PF]),
     ("ttr_wide_cuts", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _F, _I, _PI, _PI, C.POINTER(C.c_uint16), C.POINTER(C.c_int64)]),
+    ("ttr_engine_set_curved", _I, [_VP, _I]),
+    ("ttr_engine_curved", _I, [_VP]),
+    ("ttr_result_curved", _PI, [_VP]),
+    ("ttr_result_outlines", _PF, [_VP]),
+    ("ttr_result_spine_knots", C.POINTER(C.c_int64), [_VP]),
+    ("ttr_results_gather_curved", _I, [C.POINTER(_VP), _I, _PI, _PF, C.POINTER(C.c_int64)]),
+    ("ttr_curve_frame", _I, [_PF, C.POINTER(C.c_int64)]),
+    ("ttr_curve_columns", _I, [_PU8, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _PI]),
+    ("ttr_curve_knots", _I, [_PU8, _I, _I, _I, C.POINTER(C.c_int64), _PI, _PI, _PI, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("ttr_curve_crop", _I, [_PU8, _I, _I, _I, C.POINTER(C.c_int64), _PU8]),
+    ("ttr_curve_outline", _I, [_PF, _I, C.POINTER(C.c_int64), _PF]),
+    ("ttr_curve_crops", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _I, _PI, _PI, _PI, C.POINTER(C.c_int64), _PU8]),
 ]
 
 
@@ -772,6 +784,61 @@ def wide_piece_quads(quad, cuts, n: int) -> np.ndarray:
     return out[:int(n)]
 
 
+def _curve_image(image) -> np.ndarray:
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("image is [H, W, 3] u8")
+    return image
+
+
+def curve_frame(quad) -> np.ndarray:
+    """The curved-word frame of one quad (ttr_curve_frame, no GPU; DESIGN.md "Curved words"): 8 floats tl, tr, br, bl -> i64 [6] = {X0, Ax, Bx, Y0, Ay, By} in
+    2^-16 px over 128 columns x 64 rows."""
+    q = np.ascontiguousarray(quad, dtype=np.float32).reshape(8)
+    frame = np.zeros(6, np.int64)
+    _lib_check(load().ttr_curve_frame(_f(q), _i64(frame)))
+    return frame
+
+
+def curve_columns(image, frame, knots=None) -> np.ndarray:
+    """The column statistics of a frame on a host image u8 [H, W, 3] (ttr_curve_columns, no GPU) -> i32 [4, 128] = G | M | first | last; knots=None walks
+    the frame's own columns (pass 1), a knot table i64 [9, 4] the columns of its band (pass 2)."""
+    image = _curve_image(image)
+    f = np.ascontiguousarray(frame, dtype=np.int64).reshape(6)
+    t = None if knots is None else np.ascontiguousarray(knots, dtype=np.int64).reshape(36)
+    stats = np.zeros((4, 128), np.int32)
+    _lib_check(load().ttr_curve_columns(_u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _i64(f), None if t is None else _i64(t), _i(stats)))
+    return stats
+
+
+def curve_knots(image, frame) -> dict:
+    """The whole rule on one frame (ttr_curve_knots, no GPU) -> {"flag", "hb" i32 [2], "spine" i32 [2, 9], "knots" i64 [9, 4], "knots1" i64 [9, 4]}."""
+    image = _curve_image(image)
+    f = np.ascontiguousarray(frame, dtype=np.int64).reshape(6)
+    flag, hb, spine = np.zeros(1, np.int32), np.zeros(2, np.int32), np.zeros((2, 9), np.int32)
+    knots, knots1 = np.zeros((9, 4), np.int64), np.zeros((9, 4), np.int64)
+    _lib_check(load().ttr_curve_knots(_u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _i64(f), _i(flag), _i(hb), _i(spine), _i64(knots), _i64(knots1)))
+    return {"flag": int(flag[0]), "hb": hb, "spine": spine, "knots": knots, "knots1": knots1}
+
+
+def curve_crop(image, knots) -> np.ndarray:
+    """The crop of a knot table i64 [9, 4] on a host image (ttr_curve_crop, no GPU) -> u8 [32, 128, 3]."""
+    image = _curve_image(image)
+    t = np.ascontiguousarray(knots, dtype=np.int64).reshape(36)
+    crop = np.zeros((32, 128, 3), np.uint8)
+    _lib_check(load().ttr_curve_crop(_u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _i64(t), _u8(crop)))
+    return crop
+
+
+def curve_outline(quad, flag: int, knots) -> np.ndarray:
+    """The outline of a word (ttr_curve_outline, no GPU) -> f32 [18, 2]: the top edge left to right, then the bottom edge right to left."""
+    q = np.ascontiguousarray(quad, dtype=np.float32).reshape(8)
+    t = np.ascontiguousarray(knots, dtype=np.int64).reshape(36)
+    out = np.zeros((18, 2), np.float32)
+    _lib_check(load().ttr_curve_outline(_f(q), int(flag), _i64(t), _f(out)))
+    return out
+
+
 def _quad_pairs(q8) -> list:
     """8 floats tl, tr, br, bl -> [[x, y], ...] (4 pairs)"""
     q = [float(v) for v in q8]
@@ -804,19 +871,25 @@ class PageResult(collections.abc.Sequence):
     prob = exp(logp); both None when no lexicon is set.  Patterns in best mode (Engine.set_pattern(p, best=True); DESIGN.md "Patterns"): `pattern_logp` f32 [n]
     the log-probability of every item's reading, -inf for an item without a pattern (dicts gain "pattern_logp"); None in greedy mode, without a pattern, and for a page without items.  Wide words (Engine.set_wide(a); DESIGN.md "Wide words"): `piece_first` i32 [n + 1] the items' offsets
     into `piece_ids` i32 [P, 26], `piece_prob` f32 [P, 26], `piece_conf` f32 [P] and `piece_quad` f32 [P, 8] (an item that is not wide owns one piece, itself),
-    `piece_cuts` i32 [n, 17] each item's cuts in columns of its frame; dicts gain "pieces", a list of {"text", "conf", "quad"}; all None when wide is off."""
+    `piece_cuts` i32 [n, 17] each item's cuts in columns of its frame; dicts gain "pieces", a list of {"text", "conf", "quad"}; all None when wide is off.
+    Curved words (Engine.set_curved(True); DESIGN.md "Curved words"): `curved` i32 [n] (1 = the item's crop was straightened along its spine), `outline` f32
+    [n, 18, 2] (the top edge left to right, then the bottom edge right to left) and `spine_knots` i64 [n, 9, 4] the knot tables; dicts gain "curved" and
+    "outline"; all None when curved is off."""
     __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
                  "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad",
                  "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode", "alt_ids", "alt_prob",
-                 "lex_idx", "lex_logp", "lex_words", "pattern_logp", "piece_first", "piece_ids", "piece_prob", "piece_conf", "piece_quad", "piece_cuts")
+                 "lex_idx", "lex_logp", "lex_words", "pattern_logp", "piece_first", "piece_ids", "piece_prob", "piece_conf", "piece_quad", "piece_cuts",
+                 "curved", "outline", "spine_knots")
 
     def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0,
                  line=None, word=None, order=None, line_first=None, line_bbox=None,
                  char_first=None, char_quad=None, char_bbox=None, char_cuts=None, char_mode=None, char_profile=None, word_quad=None,
                  block=None, line_block=None, line_pos=None, block_order=None, block_first=None, block_bbox=None, block_mode=0,
                  alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None, pattern_logp=None,
-                 piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None):
+                 piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None,
+                 curved=None, outline=None, spine_knots=None):
+        self.curved, self.outline, self.spine_knots = curved, outline, spine_knots
         self.piece_first, self.piece_ids, self.piece_prob = piece_first, piece_ids, piece_prob
         self.piece_conf, self.piece_quad, self.piece_cuts = piece_conf, piece_quad, piece_cuts
         self.alt_ids, self.alt_prob = alt_ids, alt_prob
@@ -868,6 +941,8 @@ class PageResult(collections.abc.Sequence):
             d["pattern_logp"] = float(self.pattern_logp[j])
         if self.piece_first is not None:
             d["pieces"] = self.pieces(j)
+        if self.curved is not None:
+            d["curved"], d["outline"] = int(self.curved[j]), self.outline[j].tolist()
         return d
 
     def pieces(self, j: int) -> list:
@@ -973,6 +1048,7 @@ class Engine:
         pattern = overrides.pop("pattern", None)                                          # nor this: set_pattern, below
         pattern_best = bool(overrides.pop("pattern_best", False))                         # nor this: set_pattern_decode, below
         wide = _wide_arg(overrides.pop("wide", None))                                     # nor this: set_wide, below
+        curved = bool(overrides.pop("curved", False))                                     # nor this: set_curved, below
         self._lex_words = []
         tuning = {k: overrides.pop(k) for k in list(overrides) if not hasattr(cfg, k)}     # not a config field: a tuning key (below)
         for k, v in overrides.items():
@@ -994,6 +1070,37 @@ class Engine:
             self.set_pattern(pattern)
         if wide:
             self.set_wide(wide)
+        if curved:
+            self.set_curved(True)
+
+    def set_curved(self, on=True):
+        """Straighten the crops of words set on an arc along a spine found in the page's pixels (ttr_engine_set_curved; DESIGN.md "Curved words").  Every page
+        and region call's PageResult then carries curved / outline / spine_knots, its dicts "curved" and "outline"; words that are not curved keep every bit.
+        Raises EngineError, and changes nothing, between a stream_push and its flush, on an engine without crop_mode=1, and with orient, chars, wide words or
+        a communicator."""
+        if on not in (True, False, 0, 1):
+            raise EngineError("set_curved: on must be True or False")
+        if self.lib.ttr_engine_set_curved(self.h, int(bool(on))) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def curved(self) -> bool:
+        return bool(self.lib.ttr_engine_curved(self.h))
+
+    def curve_crops(self, image, quads, table: bool = False):
+        """ttr_curve_crops: the kind-1 packer and curve_crop_kernel on a host image u8 [H, W, 3] and host quads f32 [nq, 8], whatever the engine's setting;
+        table=True reads the page through the device page table -> (flag i32 [nq], hb i32 [nq, 2], spine i32 [nq, 2, 9], knots i64 [nq, 9, 4], crops u8
+        [nq, 32, 128, 3])."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise RuntimeError("Input array should have 3 dimensions")
+        q = np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+        nq, m = len(q), max(len(q), 1)
+        flag, hb, spine = np.zeros(m, np.int32), np.zeros((m, 2), np.int32), np.zeros((m, 2, 9), np.int32)
+        knots, crops = np.zeros((m, 9, 4), np.int64), np.zeros((m, 32, 128, 3), np.uint8)
+        self._check(self.lib.ttr_curve_crops(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _f(q), nq, int(bool(table)),
+                                             _i(flag), _i(hb), _i(spine), _i64(knots), _u8(crops)))
+        return flag[:nq].copy(), hb[:nq].copy(), spine[:nq].copy(), knots[:nq].copy(), crops[:nq].copy()
 
     def set_wide(self, max_aspect=True):
         """Read words wider than max_aspect times their height in pieces cut at ink gaps (ttr_engine_set_wide; DESIGN.md "Wide words"): 0 / False = off, True
@@ -1305,6 +1412,11 @@ class Engine:
             pf, pi, pp = np.zeros(total + n + 1, np.int32), np.zeros((ptot, 26), np.int32), np.zeros((ptot, 26), np.float32)
             pc, pq, pcu = np.zeros(ptot, np.float32), np.zeros((ptot, 8), np.float32), np.full((max(total, 1), 17), -1, np.int32)
             self.lib.ttr_results_gather_pieces(arr, n, _i(pf), _i(pi), _f(pp), _f(pc), _f(pq), _i(pcu))
+        with_curved = bool(total) and any(bool(self.lib.ttr_result_curved(arr[i])) for i in range(n))   # curved words: every page's flags, outlines and knots, one call
+        if with_curved:
+            cvf, cvo, cvk = np.zeros(total, np.int32), np.zeros((total, 18, 2), np.float32), np.zeros((total, 9, 4), np.int64)
+            if self.lib.ttr_results_gather_curved(arr, n, _i(cvf), _f(cvo), _i64(cvk)) < 0:
+                raise EngineError("ttr_results_gather_curved: bad arguments")
         out, k, kl, kc, kbl, kb, kp = [], 0, 0, 0, 0, 0, 0
         for i in range(n):
             c = int(counts[i])
@@ -1314,10 +1426,12 @@ class Engine:
                 m = int(first[-1])
                 lex.update(piece_first=first, piece_ids=pi[kp:kp + m], piece_prob=pp[kp:kp + m], piece_conf=pc[kp:kp + m], piece_quad=pq[kp:kp + m], piece_cuts=pcu[k:k + c])
                 kp += m
+            if with_curved and self.lib.ttr_result_curved(arr[i]):
+                lex.update(curved=cvf[k:k + c], outline=cvo[k:k + c], spine_knots=cvk[k:k + c])
             M = int(self.lib.ttr_result_lex_m(arr[i]))
             if M:                               # the page's matches (the setter refuses while batches stream: the word list is the one in force)
                 li, ll = self.lib.ttr_result_lex_idx_all(arr[i]), self.lib.ttr_result_lex_logp_all(arr[i])
-                lex = dict(lex_idx=np.ctypeslib.as_array(li, (c, M)).copy() if li else np.zeros((0, M), np.int32),
+                lex.update(lex_idx=np.ctypeslib.as_array(li, (c, M)).copy() if li else np.zeros((0, M), np.int32),
                            lex_logp=np.ctypeslib.as_array(ll, (c, M)).copy() if ll else np.zeros((0, M), np.float32), lex_words=self._lex_words)
             pl = self.lib.ttr_result_pattern_logp(arr[i])
             if pl:                              # patterns in best mode: the page's log-probabilities
@@ -1476,6 +1590,8 @@ class Engine:
                     a, b = int(page.piece_first[k]), int(page.piece_first[k + 1])
                     items[-1].update({"pieces": page.pieces(k), "piece_ids": page.piece_ids[a:b], "piece_prob": page.piece_prob[a:b], "piece_conf": page.piece_conf[a:b],
                                       "piece_quad": page.piece_quad[a:b], "piece_cuts": page.piece_cuts[k]})
+                if page.curved is not None:         # curved words: each region's flag, outline and knot table
+                    items[-1].update({"curved": int(page.curved[k]), "outline": page.outline[k].tolist(), "spine_knots": page.spine_knots[k]})
                 if page.lex_idx is not None:        # lexicon matching: each region under its own set
                     items[-1].update({"lex_idx": page.lex_idx[k], "lex_logp": page.lex_logp[k], "lexicon": lexicon_matches(page.lex_words, page.lex_idx[k], page.lex_logp[k])})
                 if page.pattern_logp is not None:   # patterns in best mode: each region under its own pattern and set

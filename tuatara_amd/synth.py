@@ -138,3 +138,36 @@ def synthetic_rotated_page(seed: int, h: int = 1024, w: int = 768, n_words: int 
                       "tile": np.asarray(tile, dtype=np.uint8).copy()})
     a = np.asarray(page, dtype=np.uint8)
     return np.ascontiguousarray(np.repeat(a[:, :, None], 3, 2)), words
+
+
+def synthetic_arched_page(seed: int, h: int = 512, w: int = 640, n_words: int = 6):
+    """Arched words for "Curved words": every word a band of seeded black-and-white noise (the dark "words" the synthetic detector boxes one by one, as
+    synthetic_columns_page's bars) laid along a circular arc - chord 150 to 210 px at a seeded tilt within 12 degrees, 14 to 18 px thick along the arc's
+    normal, sagitta 1.5 to 2.5 thicknesses, arching up or down in turn - one per cell of a 2-column grid; every third word is a straight bar of the same
+    make.  Returns (page u8 [h, w, 3], words): per word a dict {"centre": (cx, cy), "chord", "thick", "sagitta" (0 for a straight bar), "up", "angle"}."""
+    rng = np.random.default_rng(seed)
+    page = np.full((h, w), 255, np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    rows = (n_words + 1) // 2
+    words = []
+    for k in range(n_words):
+        r, c = divmod(k, 2)
+        cx, cy = (c + 0.5) * w / 2.0 + float(rng.uniform(-12, 12)), (r + 0.5) * h / rows + float(rng.uniform(-6, 6))
+        chord, thick = float(rng.uniform(150, 210)), float(rng.uniform(14, 18))
+        sag = 0.0 if k % 3 == 2 else thick * float(rng.uniform(1.5, 2.5))
+        up, ang = k % 2 == 0, float(rng.uniform(-12, 12))
+        a = np.radians(ang)
+        lx, ly = (xx - cx) * np.cos(a) + (yy - cy) * np.sin(a), -(xx - cx) * np.sin(a) + (yy - cy) * np.cos(a)
+        if sag == 0.0:
+            inside = (np.abs(lx) <= chord / 2.0) & (np.abs(ly) <= thick / 2.0)
+        else:
+            R = (chord * chord / 4.0 + sag * sag) / (2.0 * sag)
+            sgn = 1.0 if up else -1.0
+            oy = sgn * (R - sag / 2.0)
+            rad = np.hypot(lx, ly - oy)
+            th = np.arctan2(lx, -sgn * (ly - oy))
+            inside = (np.abs(rad - R) <= thick / 2.0) & (np.abs(th) <= np.arcsin(chord / 2.0 / R))
+        noise = (rng.integers(0, 2, (h // 2 + 1, w // 2 + 1), dtype=np.uint8) * 255).repeat(2, 0).repeat(2, 1)[:h, :w]
+        page[inside] = noise[inside]
+        words.append({"centre": (cx, cy), "chord": chord, "thick": thick, "sagitta": sag, "up": up, "angle": ang})
+    return np.ascontiguousarray(np.repeat(page[:, :, None], 3, 2)), words
