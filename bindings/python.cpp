@@ -28,6 +28,9 @@
 // And a keyword-only pattern=None on both calls: a regular expression every word must match (DESIGN.md "Patterns"; the subset of Python's re that
 // include/tuatara_hip.h lists), set on the cached engine for the call and reset afterwards, also when the call raises; calls that share the engine take turns.
 // "pattern" is also a key of a regions= dict: that region's own.  A bad pattern raises ValueError, naming the offset or the character, before anything runs;
+// And keyword-only lexicon_fuzzy=None, lexicon_gap=-6.9077554 (ln 1e-3) on both calls: lexicon_fuzzy=B (0..3) aligns the entries instead of indexing them
+// (DESIGN.md "Lexicon matching", Fuzzy alignment) and every dict gains "lexicon_edits", one int per pair of "lexicon"; it needs a lexicon.  Neither default has
+// been tuned on documents.
 // a pattern with orient, alts or lexicon raises ValueError too.  The dicts' keys do not change.
 // And a keyword-only pattern_best=False on both calls: True reads every word that has a pattern as the LIKELIEST member of its language under the
 // recogniser's per-position distributions (DESIGN.md "Patterns", best mode) and adds "pattern_logp" to every dict; the mode is set for the call and reset
@@ -46,6 +49,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cmath>
 #include <stdexcept>
 
 #include "../include/tuatara.h"
@@ -59,7 +63,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false, curved = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false, curved = false, lex_edits = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
@@ -118,6 +122,11 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
     py::list l;
     for (const LexMatch& m : item.lexicon) l.append(py::make_tuple(m.word, std::exp((double)m.logp)));
     d["lexicon"] = l;
+    if (k.lex_edits) {   // fuzzy alignment: each match's edits, beside the (word, prob) pairs
+      py::list ed;
+      for (const LexMatch& m : item.lexicon) ed.append(m.edits);
+      d["lexicon_edits"] = ed;
+    }
   }
   return d;
 }
@@ -148,6 +157,16 @@ static bool lexicon_args(const py::object& lexicon, int lexicon_m, std::vector<s
   for (size_t i = 0; i < words.size(); ++i)
     if (words[i].find('\0') != std::string::npos) throw std::invalid_argument("lexicon: word " + std::to_string(i) + " holds '\\x00', which names no recogniser class");
   return true;
+}
+
+// lexicon_fuzzy=None | a band 0..3, lexicon_gap -> the band (-1 = off).  A band or gap out of range, and a band without a lexicon, raise ValueError.
+static int fuzzy_args(const py::object& fuzzy, double gap, bool lex) {
+  if (fuzzy.is_none()) return -1;
+  const int band = py::cast<int>(fuzzy);
+  if (band < 0 || band > 3) throw std::invalid_argument("lexicon_fuzzy must lie in 0..3");
+  if (!std::isfinite(gap) || gap > 0.0) throw std::invalid_argument("lexicon_gap must be finite and <= 0");
+  if (!lex) throw std::invalid_argument("lexicon_fuzzy needs a lexicon");
+  return band;
 }
 
 // a call with alts or a lexicon set that came back empty because the engine refused them raises the engine's message: a bad word list (the messages that
@@ -239,12 +258,14 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
-                                      py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved) {
+                                      py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved, py::object lexicon_fuzzy, double lexicon_gap) {
   const int orient = orient_mode(orient_kw);
   const float wide = wide_arg(wide_kw);
   alts_arg(alts);
   std::vector<std::string> words;
   const bool lex = lexicon_args(lexicon, lexicon_m, words);
+  const int band = fuzzy_args(lexicon_fuzzy, lexicon_gap, lex);
+  const float gap = (float)lexicon_gap;
   std::string allow, deny;
   charset_args(allowlist, blocklist, allow, deny);
   const std::string pattern = pattern_arg(pattern_kw, allow, deny);
@@ -304,14 +325,17 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     std::vector<OutputItemEx> got;
     {
       py::gil_scoped_release nogil;
-      got = lex ? image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts, words, lexicon_m)
+      got = band >= 0 ? image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts, words, lexicon_m, band, gap)
+                : lex ? image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts, words, lexicon_m)
                 : pattern_best ? image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts, true)
                 : image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts);
     }
     if ((alts || lex || with_pattern) && got.empty()) raise_refused();
     py::list res;
     for (const auto& item : got) {
-      py::dict d = item_dict(item, Keys{true, conf, false, false, false, false, alts != 0, lex, false, pattern_best});
+      Keys keys{true, conf, false, false, false, false, alts != 0, lex, false, pattern_best};
+      keys.lex_edits = band >= 0;
+      py::dict d = item_dict(item, keys);
       d["region"] = item.region;
       res.append(d);
     }
@@ -327,6 +351,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     py::gil_scoped_release nogil;   // (orient = None: the 7-argument call, which leaves the orientation to TUATARA_ORIENT)
     items = pattern_best     ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, pattern, true)
             : !pattern.empty() ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, pattern)
+            : band >= 0 ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts, words, lexicon_m, band, gap)
             : lex    ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts, words, lexicon_m)
             : alts   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny, alts)
             : cset   ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, allow, deny)
@@ -338,7 +363,9 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   }
   if ((alts || lex || !pattern.empty()) && items.empty()) raise_refused();
   py::list result;
-  for (const auto& item : items) result.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best}));
+  Keys keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best};
+  keys.lex_edits = band >= 0;
+  for (const auto& item : items) result.append(item_dict(item, keys));
   return result;
 }
 
@@ -348,11 +375,13 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
 // Keyword-only mixed_batches=False: True batches images that share one detector canvas, whatever their sizes (DESIGN.md "Mixed-size batches"); same results.
 static py::list images_to_data_wrapper(py::sequence images, std::string weights_dir, std::string output_dir, bool rectify, bool conf, py::object orient_kw,
                                        bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches, py::object allowlist, py::object blocklist, int alts,
-                                       py::object lexicon, int lexicon_m, py::object pattern_kw, bool pattern_best) {
+                                       py::object lexicon, int lexicon_m, py::object pattern_kw, bool pattern_best, py::object lexicon_fuzzy, double lexicon_gap) {
   const int orient = orient_mode(orient_kw);
   alts_arg(alts);
   std::vector<std::string> words;
   const bool lex = lexicon_args(lexicon, lexicon_m, words);
+  const int band = fuzzy_args(lexicon_fuzzy, lexicon_gap, lex);
+  const float gap = (float)lexicon_gap;
   std::string allow, deny;
   charset_args(allowlist, blocklist, allow, deny);
   const std::string pattern = pattern_arg(pattern_kw, allow, deny);
@@ -376,6 +405,7 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
     py::gil_scoped_release nogil;
     pages = pattern_best ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, pattern, true)
             : !pattern.empty() ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, pattern)
+            : band >= 0 ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts, words, lexicon_m, band, gap)
             : lex ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts, words, lexicon_m)
             : alts ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny, alts)
             : cset ? images_to_data_ex(views, weights_dir, output_dir, rectify, orient ? orient : -1, orient_page, lines, chars, blocks, mixed_batches, allow, deny)
@@ -390,7 +420,9 @@ static py::list images_to_data_wrapper(py::sequence images, std::string weights_
   py::list result;
   for (const auto& items : pages) {
     py::list page;
-    for (const auto& item : items) page.append(item_dict(item, Keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best}));
+    Keys keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best};
+    keys.lex_edits = band >= 0;
+    for (const auto& item : items) page.append(item_dict(item, keys));
     result.append(page);
   }
   return result;
@@ -400,8 +432,8 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("pattern_best") = false, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("pattern_best") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");
 }

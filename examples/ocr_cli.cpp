@@ -32,6 +32,8 @@
 //   ocr_cli --lexicon FILE [--lexicon-m M] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: matches every word that is read against the word
 // list in FILE, one word per line (DESIGN.md "Lexicon matching"; empty lines are skipped).  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item, then its M best
 // entries (1..8, default 1), one line each: "<TAB>=i prob word", prob being exp(log-probability) to 6 decimals.  A bad entry fails, naming its index.
+// With --lexicon-fuzzy B [--lexicon-gap G] (B in 0..3; G <= 0, default ln 1e-3 = -6.9077554, not tuned on documents) the entries are aligned against the
+// reading instead of indexed (DESIGN.md "Lexicon matching", Fuzzy alignment) and each match's line gains its edits: "<TAB>=i prob word edits".
 //   ocr_cli --wide [A] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: reads words wider than A times their height (2..64, default 8) in
 // pieces cut at ink gaps, on rectified crops (DESIGN.md "Wide words").  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item and, under a wide item, one line per
 // piece: "<TAB>|conf text".  A value that is no number in [2, 64] fails before the image is read.
@@ -178,10 +180,23 @@ int main(int argc, const char** argv) {
       return 0;
     }
     std::string lex_file;
-    int lex_m = 0;
-    while (argc >= 3 && (std::string(argv[1]) == "--lexicon" || std::string(argv[1]) == "--lexicon-m")) {
+    int lex_m = 0, lex_band = -1;
+    float lex_gap = LexFuzzy{}.gap;
+    bool lex_gap_set = false;
+    while (argc >= 3 && (std::string(argv[1]) == "--lexicon" || std::string(argv[1]) == "--lexicon-m" || std::string(argv[1]) == "--lexicon-fuzzy" ||
+                         std::string(argv[1]) == "--lexicon-gap")) {
       if (std::string(argv[1]) == "--lexicon") lex_file = argv[2];
-      else {
+      else if (std::string(argv[1]) == "--lexicon-fuzzy") {
+        char* end = nullptr;
+        const long v = std::strtol(argv[2], &end, 10);
+        if (end == argv[2] || *end || v < 0 || v > 3) throw std::runtime_error("--lexicon-fuzzy takes a band B in 0..3");
+        lex_band = (int)v;
+      } else if (std::string(argv[1]) == "--lexicon-gap") {
+        char* end = nullptr;
+        const double v = std::strtod(argv[2], &end);
+        if (end == argv[2] || *end || !std::isfinite(v) || v > 0.0) throw std::runtime_error("--lexicon-gap takes a finite log-probability G <= 0");
+        lex_gap = (float)v; lex_gap_set = true;
+      } else {
         char* end = nullptr;
         const long v = std::strtol(argv[2], &end, 10);
         if (end == argv[2] || *end || v < 1 || v > 8) throw std::runtime_error("--lexicon-m takes M in 1..8");
@@ -190,8 +205,10 @@ int main(int argc, const char** argv) {
       argv[2] = argv[0]; argv += 2; argc -= 2;
     }
     if (lex_m && lex_file.empty()) throw std::runtime_error("--lexicon-m needs --lexicon FILE");
+    if (lex_band >= 0 && lex_file.empty()) throw std::runtime_error("--lexicon-fuzzy needs --lexicon FILE");
+    if (lex_gap_set && lex_band < 0) throw std::runtime_error("--lexicon-gap needs --lexicon-fuzzy B");
     if (!lex_file.empty()) {
-      if (argc != 4) throw std::runtime_error("--lexicon FILE [--lexicon-m M] goes in front of <image.png> <weights_dir> <outputs_dir>");
+      if (argc != 4) throw std::runtime_error("--lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] goes in front of <image.png> <weights_dir> <outputs_dir>");
       std::ifstream f(lex_file);
       if (!f) throw std::runtime_error("cannot read lexicon file " + lex_file);
       std::vector<std::string> words;
@@ -201,12 +218,18 @@ int main(int argc, const char** argv) {
       }
       if (words.empty()) throw std::runtime_error("the lexicon file " + lex_file + " holds no word");
       pngdec::Image img = pngdec::read(argv[1]);
-      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[2], argv[3], false, -1, false, false,
-                                                         false, false, std::string(), std::string(), 0, words, lex_m ? lex_m : 1);
+      std::vector<OutputItemEx> items =
+          lex_band >= 0 ? image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[2], argv[3], false, -1, false, false, false, false,
+                                           std::string(), std::string(), 0, words, lex_m ? lex_m : 1, lex_band, lex_gap)
+                        : image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[2], argv[3], false, -1, false, false,
+                                           false, false, std::string(), std::string(), 0, words, lex_m ? lex_m : 1);
       if (!last_call_error().empty()) return 1;                         // (the message is on stderr)
       for (const OutputItemEx& it : items) {
         printf("%g %g %g %g\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.conf, it.text.c_str());
-        for (const LexMatch& m : it.lexicon) printf("\t=%d %.6f %s\n", m.index, std::exp((double)m.logp), m.word.c_str());
+        for (const LexMatch& m : it.lexicon) {
+          if (lex_band >= 0) printf("\t=%d %.6f %s %d\n", m.index, std::exp((double)m.logp), m.word.c_str(), m.edits);
+          else printf("\t=%d %.6f %s\n", m.index, std::exp((double)m.logp), m.word.c_str());
+        }
       }
       return 0;
     }
@@ -289,7 +312,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

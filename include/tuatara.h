@@ -48,6 +48,7 @@ struct LexMatch {                  // one entry of the caller's word list matche
   int index = -1;                  // the entry's index in the word list
   std::string word;                // the entry
   float logp = 0.f;                // its log-probability under the item's per-position distributions, the EOS behind it included
+  int edits = 0;                   // fuzzy alignment: the dropped and extra characters of the entry's best alignment (0 when the mode is off)
 };
 struct WordPiece {                 // one piece of a wide word (wide words; DESIGN.md "Wide words")
   std::string text;                // the piece's reading
@@ -181,6 +182,21 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
                                                          std::string allowlist, std::string blocklist, int alts, const std::vector<std::string>& words, int m);
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>& words, int m);
+// ... with fuzzy alignment (DESIGN.md "Lexicon matching", Fuzzy alignment): band = 0..3 aligns every entry against the reading instead of indexing it, so an
+// entry still matches a reading with up to `band` more dropped than extra characters (or the other way round) at any point; gap (finite, <= 0) is the
+// log-probability charged for each, and LexMatch::edits says how many the best alignment took.  band = -1 is the calls above.  LexFuzzy{} is band 1 with
+// gap = ln 1e-3, which nobody has tuned on documents.  The mode is set on the cached engine for the call and cleared afterwards.
+struct LexFuzzy { int band = 1; float gap = -6.9077554f; };
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, int alts, const std::vector<std::string>& words, int m, int band, float gap);
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist, int alts, const std::vector<std::string>& words, int m,
+                                                         int band, float gap);
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>& words, int m,
+                                           int band, float gap);
 
 // Patterns (opt-in; DESIGN.md "Patterns"): pattern = a regular expression every word must match - "\\d{2}/\\d{2}/\\d{4}" for a date, "[A-Z]{2}\\d{2,6}" for
 // a plate; the syntax is the subset of Python's re that include/tuatara_hip.h lists.  The pattern acts where each character is chosen: every returned text is

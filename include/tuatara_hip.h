@@ -572,6 +572,43 @@ const int32_t* ttr_result_lex_idx_all(const ttr_result* r);
 const float* ttr_result_lex_logp_all(const ttr_result* r);
 int ttr_lexicon_encode(const char* const* words, int n, uint8_t* records);
 int ttr_logits_lexicon(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, int32_t* idx, float* logp);
+/* Fuzzy alignment (opt-in; DESIGN.md "Lexicon matching", Fuzzy alignment): the rule above indexes - character j of an entry is looked up at position j - so
+ * it covers substitutions and nothing else; a reading with one character dropped or doubled shifts every position behind the slip.  With a band B in 0..3 and
+ * a gap g (fp32, finite, <= 0: the log-probability charged for one dropped or one extra character) an entry w of L characters is aligned instead.  lp is the
+ * table above, unchanged.  A cell D[j][p] stands for "j characters of the entry and p positions of the reading consumed"; it exists for 0 <= j <= L,
+ * 0 <= p <= 25, |j - p| <= B, and holds a pair (score fp32, edits int).
+ *   D[0][0] = (0.0f, 0); every other cell starts at (-inf, 0)
+ *   a candidate replaces the cell's value iff cand.score > cur.score, or cand.score == cur.score and cand.edits < cur.edits (comparisons with NaN are
+ *   false: a NaN is never taken up and never spreads)
+ *   the candidates of D[j][p], each only from a cell that exists:
+ *     match                                                  (D[j-1][p-1].score + lp[p-1][w[j-1]], edits)
+ *     extra character in the reading (position p-1 skipped)  (D[j][p-1].score + g, edits + 1)
+ *     dropped character (entry character j-1 skipped)        (D[j-1][p].score + g, edits + 1)
+ *   the end: over the cells D[L][p] that exist, the candidates (D[L][p].score + lp[p][0], edits) under the same rule from (-inf, 0): the winner is logp(w)
+ *   and edits(w)
+ * Every operation is one fp32 addition or one comparison, and the order of the additions along a path is the path's own: the result is a function of (table,
+ * entry, B, g) alone.  At B = 0 the only path is the diagonal: logp is the rigid rule's value bit for bit, edits 0.  logp never decreases as B grows.
+ * Ranking, the empty slots and "never -inf or NaN" are the lexicon's own; lex_edits [count][M] int32 holds each match's edits, -1 in the empty slots.
+ * ttr_engine_set_lexicon_fuzzy: the mode for everything that carries a lexicon (the synchronous calls, the list form, the _v forms, streamed batches, the
+ * region calls - each region under its own set); band = -1 switches it off (gap is then ignored).  It may be set with no lexicon in place and survives
+ * ttr_engine_set_lexicon.  It fails, and changes nothing, for a band outside -1..3, a gap that is not finite or is > 0, and while streamed batches are in
+ * flight.  With the mode off no launch, allocation, copy or bit differs from an engine that never heard of it.  The convenience layers default to band 1
+ * with g = -6.9077554f (ln 1e-3); neither has been tuned on documents.  ttr_engine_lexicon_fuzzy: the band (-1 = off) and gap in force; either may be NULL.
+ * ttr_result_lex_band: the band a result's matches were scored under, -1 when off.  ttr_result_lex_edits: item i's [M]; the _all view: [count][M]; NULL when
+ * the mode is off or the result is empty.
+ * ttr_lexicon_fuzzy_from_lp (host, no engine): the rule for n records [n][32] (ttr_lexicon_encode's) against one table lp [26][96] -> logp [n], edits [n].
+ * Returns 0, or -1 for a null argument, a band outside 0..3, a gap that is not finite or is > 0, or a record whose length byte is outside 1..25 or that holds
+ * a class byte >= 96.
+ * ttr_logits_lexicon_fuzzy (stage; refuses while batches stream): ttr_logits_lexicon through the fuzzy scorer under (band, gap), whatever the engine's mode
+ * -> idx / logp / edits [n][M] (any may be NULL). */
+int ttr_engine_set_lexicon_fuzzy(ttr_engine* e, int band, float gap);
+int ttr_engine_lexicon_fuzzy(const ttr_engine* e, int* band, float* gap);
+int ttr_result_lex_band(const ttr_result* r);
+const int32_t* ttr_result_lex_edits(const ttr_result* r, int i);
+const int32_t* ttr_result_lex_edits_all(const ttr_result* r);
+int ttr_lexicon_fuzzy_from_lp(const float* lp, const uint8_t* records, int n, int band, float gap, float* logp, int32_t* edits);
+int ttr_logits_lexicon_fuzzy(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, int band, float gap,
+                             int32_t* idx, float* logp, int32_t* edits);
 /* ---- wide words (opt-in; DESIGN.md "Wide words") ---------------------------------------------
  * Every recogniser row is one crop stretched to 32 x 128, and the recogniser emits at most 25 characters: a URL, an IBAN or a whole line handed in as one region
  * reaches it with a few columns per character.  With ttr_engine_set_wide(e, max_aspect) a word whose quad is wider than max_aspect times its height is cut into

@@ -72,6 +72,11 @@ int ttr_dbg_cross_attn(ttr_engine* e, const float* q, const float* kvmem, int N,
  * queries), kvcache f32 [N][26][768] (K | V per context slot), tokens i32 [N][26] (read in mode 1: id 0 = EOS) -> out f32 [N * R][384].  mode 0 = AR step qi0
  * (R = 1: keys 0 .. qi0), mode 1 = the refinement pass (R query rows 0 .. R - 1 per crop, R <= 26: cloze mask + key padding from the first EOS on).  K / V rows of
  * masked keys are not read.  A row the kernel did not write comes back as NaN. */
+/* test hook for the lexicon scorers' tables (lexicon_fuzzy.hip: lex_tile_tables, the function both the fuzzy scorer and this dump build them with): host logits
+ * [n][26][95] through decode_conf_kernel, then lp f32 [n][26][96] as a workgroup forms it in LDS - lp[p][c] = (x[p][c] - x[p][id[p]]) + logf(prob[p]) for an
+ * allowed class, -inf for a blocked one and for column 95.  sets / n_sets / set_of as in ttr_logits_lexicon.  So that a test can hold the fuzzy kernel to
+ * ttr_lexicon_fuzzy_from_lp bit for bit.  Refuses while batches stream. */
+int ttr_debug_lexicon_tables(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, float* lp);
 int ttr_dbg_dec_self_attn(ttr_engine* e, const float* q, const float* kvcache, const int32_t* tokens, int N, int R, int qi0, int mode, float* out);
 /* test hook for qkv_attn.hip (bf16 engines): x f32 [N][128][384], w [1152][384], b [1152] -> self-attention output [N][128][384] */
 int ttr_dbg_qkv_attn(ttr_engine* e, const float* x, int N, const float* w, const float* b, float* out);

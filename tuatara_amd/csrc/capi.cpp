@@ -1586,6 +1586,89 @@ int ttr_logits_lexicon(ttr_engine* e, const float* logits, int n, const uint32_t
   TTR_GUARD_END(-1)
 }
 
+// fuzzy alignment of the lexicon (DESIGN.md "Lexicon matching", Fuzzy alignment)
+static void check_lex_fuzzy(const char* who, int band, float gap, int min_band) {
+  if (band < min_band || band > kLexMaxBand) throw std::runtime_error(std::string(who) + ": the band must lie in " + std::to_string(min_band) + "..3, got " + std::to_string(band));
+  if (band >= 0 && (!std::isfinite(gap) || gap > 0.f)) throw std::runtime_error(std::string(who) + ": the gap must be finite and <= 0 (the log-probability of one dropped or extra character)");
+}
+
+int ttr_engine_set_lexicon_fuzzy(ttr_engine* e, int band, float gap) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  check_lex_fuzzy("ttr_engine_set_lexicon_fuzzy", band, gap, -1);
+  E.refuse_while_streaming("ttr_engine_set_lexicon_fuzzy");
+  E.lex_band = band; E.lex_gap = band >= 0 ? gap : 0.f;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_lexicon_fuzzy(const ttr_engine* e, int* band, float* gap) {
+  if (!e) return -1;
+  if (band) *band = e->e->lex_band;
+  if (gap) *gap = e->e->lex_gap;
+  return 0;
+}
+
+int ttr_result_lex_band(const ttr_result* r) { return r ? r->r.lex_band : -1; }
+
+const int32_t* ttr_result_lex_edits(const ttr_result* r, int i) { return r && i >= 0 && (size_t)i < r->r.lex_edits.size() / (size_t)std::max(r->r.lex_m, 1) ? &r->r.lex_edits[(size_t)r->r.lex_m * (size_t)i] : nullptr; }
+
+const int32_t* ttr_result_lex_edits_all(const ttr_result* r) { return r && !r->r.lex_edits.empty() ? r->r.lex_edits.data() : nullptr; }
+
+int ttr_lexicon_fuzzy_from_lp(const float* lp, const uint8_t* records, int n, int band, float gap, float* logp, int32_t* edits) {
+  return lexicon_fuzzy_from_lp(lp, records, n, band, gap, logp, edits);
+}
+
+int ttr_logits_lexicon_fuzzy(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, int band, float gap,
+                             int32_t* idx, float* logp, int32_t* edits) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && !logits) || (sets && n > 0 && !set_of)) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  check_lex_fuzzy("ttr_logits_lexicon_fuzzy", band, gap, 0);
+  E.refuse_while_streaming("ttr_logits_lexicon_fuzzy");
+  if (!E.lex_v) throw std::runtime_error("ttr_logits_lexicon_fuzzy: no lexicon is set (ttr_engine_set_lexicon)");
+  std::vector<uint32_t> table;
+  ClassMask one = E.charset;
+  if (sets) E.resolve_row_masks("ttr_logits_lexicon_fuzzy", set_of, n, sets, n_sets, table, one);
+  if (n == 0) return 0;
+  const int M = E.lex_m;
+  const Engine::LexOut l = E.lex_out(n, M, band, gap);
+  Engine::RecPass p = stage_logits(E, logits, n);
+  p.mask = one; p.row_masks = E.stage_row_masks(table, 0); p.lex = l;
+  E.parseq_decode(p);
+  if (idx) TTR_HIP_CHECK(hipMemcpyAsync(idx, l.idx, (size_t)n * M * 4, hipMemcpyDeviceToHost, E.stream));
+  if (logp) TTR_HIP_CHECK(hipMemcpyAsync(logp, l.logp, (size_t)n * M * 4, hipMemcpyDeviceToHost, E.stream));
+  if (edits) TTR_HIP_CHECK(hipMemcpyAsync(edits, l.edits, (size_t)n * M * 4, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_debug_lexicon_tables(ttr_engine* e, const float* logits, int n, const uint32_t* sets, int n_sets, const int32_t* set_of, float* lp) {
+  TTR_GUARD_BEGIN
+  if (!e || n < 0 || (n > 0 && (!logits || !lp)) || (sets && n > 0 && !set_of)) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_debug_lexicon_tables");
+  std::vector<uint32_t> table;
+  ClassMask one = E.charset;
+  if (sets) E.resolve_row_masks("ttr_debug_lexicon_tables", set_of, n, sets, n_sets, table, one);
+  if (n == 0) return 0;
+  Engine::RecPass p = stage_logits(E, logits, n);
+  p.mask = one; p.row_masks = E.stage_row_masks(table, 0);
+  E.parseq_decode(p);                                              // the masked argmax: the standard block the tables are formed from
+  const size_t bytes = (size_t)n * 26 * 96 * 4;
+  E.lex_part.ensure(bytes);                                        // (the scorer's partials are scratch between launches)
+  launch_lexicon_tables(p.logits, n, p.out.ids, p.out.prob, E.lex_part.as<float>(), E.stream, p.mask, p.row_masks);
+  TTR_HIP_CHECK(hipMemcpyAsync(lp, E.lex_part.p, bytes, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_confidence_from_probs(const int32_t* ids, const float* probs, int n_pos, float* char_conf, int* n_chars, float* conf) {
   if (!ids || !probs || n_pos < 0) return -1;
   const int k = confidence_from_probs(ids, probs, n_pos, char_conf, conf);

@@ -272,6 +272,8 @@ struct Result {
   int lex_m = 0;                   // M: matches kept per item
   std::vector<int32_t> lex_idx;    // M per item: the M best entries of the engine's word list by (logp descending, index ascending), -1 in the empty slots (lexicon.hip)
   std::vector<float> lex_logp;     // M per item: their log-probabilities, -INFINITY in the empty slots
+  int lex_band = -1;               // fuzzy alignment (ttr_engine_set_lexicon_fuzzy): the band the matches were scored under, -1 = off (the rigid scorer)
+  std::vector<int32_t> lex_edits;  // ... M per item: the edits of each match's alignment, -1 in the empty slots; empty when the mode is off (lexicon_fuzzy.hip)
   std::vector<float> pattern_logp; // patterns in best mode: one per item, the log-probability of its reading (-INFINITY for an item without a pattern); empty otherwise
   // word orientation (cfg.orient != TTR_ORIENT_OFF; DESIGN.md "Word orientation"): empty when off
   std::vector<int32_t> orient;      // 1 per item: the chosen turn 0..3
@@ -420,6 +422,7 @@ struct Engine {
   int lex_v = 0, lex_m = 0;                       // V words, M matches kept per item (1..8)
   DevBuf lex_records;                             // [V] 32-byte records: length | 25 class bytes | zero padding (geometry.h: lexicon_encode)
   std::vector<std::string> lex_words;             // the host copy of the words (ttr_engine_lexicon_word)
+  int lex_band = -1; float lex_gap = 0.f;         // fuzzy alignment (ttr_engine_set_lexicon_fuzzy): the band 0..3 (-1 = off: the rigid scorer) and the gap's log-probability
   float wide = 0.f;                               // wide words: the largest aspect a piece may have, 0 = off or 2..64 (ttr_engine_set_wide; DESIGN.md "Wide words")
   bool curved = false;                            // curved words: straighten the crops of words set on an arc (ttr_engine_set_curved; DESIGN.md "Curved words")
   ClassMask charset{};                            // classes the recogniser may not choose (ttr_engine_set_charset; DESIGN.md "Character sets"); zero = no set
@@ -486,14 +489,17 @@ struct Engine {
   AltOut alts_out(int N, int K) { alts_side.ensure(alts_side_bytes(std::max(N, 1), K)); return AltOut{alts_side.as<int>(), alts_side.as<float>() + (size_t)N * 26 * K, K}; }
   DevBuf lex_side, lex_part;                      // lexicon matching: the side block (lexicon.hip), [N][M] int32 idx | [N][M] f32 logp; the scorer's partials [N][chunks][M] idx | logp
   PinnedBuf h_lex[2];                             // ... per slot: the side block's host copy
-  struct LexOut { int* idx; float* logp; int* part_idx; float* part_logp; int m; };   // m: the block's matches per item, 0 = none
-  static size_t lex_side_bytes(int N, int M) { return (size_t)N * M * 8; }
-  LexOut lex_out(int N, int M) {
+  // m: the block's matches per item, 0 = none; band >= 0: the fuzzy scorer under (band, gap) in the rigid one's place, edits [N][m] behind the two blocks
+  struct LexOut { int* idx; float* logp; int* part_idx; float* part_logp; int m; int band = -1; float gap = 0.f; int* edits = nullptr; };
+  static size_t lex_side_bytes(int N, int M, int band = -1) { return (size_t)N * M * (band >= 0 ? 12 : 8); }
+  LexOut lex_out(int N, int M, int band = -1, float gap = 0.f) {
     N = std::max(N, 1);
-    lex_side.ensure(lex_side_bytes(N, M));
+    lex_side.ensure(lex_side_bytes(N, M, band));
     const size_t pe = lexicon_partial_entries(N, lex_v, M);
     lex_part.ensure(pe * 8);
-    return LexOut{lex_side.as<int>(), lex_side.as<float>() + (size_t)N * M, lex_part.as<int>(), lex_part.as<float>() + pe, M};
+    LexOut l{lex_side.as<int>(), lex_side.as<float>() + (size_t)N * M, lex_part.as<int>(), lex_part.as<float>() + pe, M};
+    if (band >= 0) { l.band = band; l.gap = gap; l.edits = lex_side.as<int>() + (size_t)N * M * 2; }
+    return l;
   }
   DevBuf wide_side;                               // wide words: the side block (wide.hip), [Wn][17] int32 cuts | [Wn][2048] u16 profile
   PinnedBuf h_wide[2];                            // ... per slot: the cuts' host copy
@@ -736,7 +742,7 @@ struct Engine {
       g.out = out.at(r0);
       g.row_masks = at(row_masks, 1);
       g.alt.ids = at(alt.ids, 26 * (size_t)alt.k); g.alt.prob = at(alt.prob, 26 * (size_t)alt.k);
-      g.lex.idx = at(lex.idx, lex.m); g.lex.logp = at(lex.logp, lex.m);
+      g.lex.idx = at(lex.idx, lex.m); g.lex.logp = at(lex.logp, lex.m); g.lex.edits = at(lex.edits, lex.m);
       g.pat.start_of = at(pat.start_of, 1);
       g.best.id0 = at(best.id0, 26); g.best.prob0 = at(best.prob0, 26); g.best.conf0 = at(best.conf0, 1); g.best.logp = at(best.logp, 1);
       g.best.ext.extent_of = at(best.ext.extent_of, 2);
@@ -818,6 +824,7 @@ struct Engine {
     int alts = 0;                      // the engine's `alts` when the recogniser was enqueued: h_alts[slot] holds [N][26][alts] ids | prob
     bool pat_best = false;             // patterns in best mode, fixed when the recogniser was enqueued with a pattern in force: h_pat_logp[slot] holds [N] f32
     int lex_m = 0;                     // the engine's `lex_m` when the recogniser was enqueued with a lexicon set (0 = none): h_lex[slot] holds [N][lex_m] idx | logp
+    int lex_band = -1;                 // ... and the engine's `lex_band` then (-1 = the rigid scorer): >= 0, [N][lex_m] int32 edits follow the two blocks
     // regions (run_regions; DESIGN.md "Regions and per-row character sets"): the boxes are the caller's quads - no detector ran, `boxes` stays empty, every crop is
     // a kind-1 crop of the table packer.  Crop c (page order, then the caller's order): its quad verbatim, its set index, and - when the sets differ - its row
     // of the class-mask table ({blocked[3], 0}); row_masks empty = every crop reads under region_mask, by value

@@ -742,6 +742,7 @@ void Engine::recog_enqueue(PageBatch& B) {
   if (cfg.chars && N > 0) stage_batch_chars(B, sl);                          // character boxes: likewise
   B.alts = orient_k() > 1 ? 0 : alts;        // character alternatives: fixed for the batch here (the setter refuses while batches stream)
   B.lex_m = lex_v && orient_k() <= 1 ? lex_m : 0;   // lexicon matching: likewise (0 = no lexicon set)
+  B.lex_band = B.lex_m ? lex_band : -1;             // ... and its fuzzy alignment: likewise (-1 = the rigid scorer); every test of the mode below is on the host
   B.pat_best = pattern_decode == TTR_PATTERN_BEST && N > 0 && (B.regions ? !B.region_pats.start_of.empty() : pattern_own.delta != nullptr);   // patterns in best mode: likewise, and only with a pattern in force
   range_use(kRangeRec0 + (sl & 1));          // the recogniser's kernels of this batch watch the slot's own word
   const int X = B.X;                         // wide words: the pieces behind the batch's N, read as a pass of their own (DESIGN.md "Wide words"); 0 with wide off
@@ -764,7 +765,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     // character alternatives: the side block of this batch (the setter refuses an engine with orientation, so T is 0 here)
     if (B.alts) { main.alt = alts_out(N, B.alts); h_alts[sl].ensure(alts_side_bytes(N, B.alts)); }
     // lexicon matching: the side block and the scorer's partials of this batch
-    if (B.lex_m) { main.lex = lex_out(N, B.lex_m); h_lex[sl].ensure(lex_side_bytes(N, B.lex_m)); }
+    if (B.lex_m) { main.lex = lex_out(N, B.lex_m, B.lex_band, lex_gap); h_lex[sl].ensure(lex_side_bytes(N, B.lex_m, B.lex_band)); }
     // patterns in best mode: the scratch block of the masked argmax and the side block of this batch
     if (B.pat_best) { main.best = pat_best_out(N); h_pat_logp[sl].ensure((size_t)N * 4); }
     pack_batch_crops(B, sl);
@@ -801,7 +802,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     TTR_HIP_CHECK(hipMemcpyAsync(h_ids[sl].p, ids_dev.p, block, hipMemcpyDeviceToHost, stream));   // ids, prob and conf in one copy
     if (T) TTR_HIP_CHECK(hipMemcpyAsync(h_orient[sl].p, orient_side.p, side_b, hipMemcpyDeviceToHost, stream));
     if (B.alts) TTR_HIP_CHECK(hipMemcpyAsync(h_alts[sl].p, alts_side.p, alts_side_bytes(N, B.alts), hipMemcpyDeviceToHost, stream));   // the alternatives' side block, behind the standard block's copy
-    if (B.lex_m) TTR_HIP_CHECK(hipMemcpyAsync(h_lex[sl].p, lex_side.p, lex_side_bytes(N, B.lex_m), hipMemcpyDeviceToHost, stream));   // the lexicon matches' side block, likewise
+    if (B.lex_m) TTR_HIP_CHECK(hipMemcpyAsync(h_lex[sl].p, lex_side.p, lex_side_bytes(N, B.lex_m, B.lex_band), hipMemcpyDeviceToHost, stream));   // the lexicon matches' side block, likewise
     if (B.pat_best) TTR_HIP_CHECK(hipMemcpyAsync(h_pat_logp[sl].p, pat_logp_dev.p, (size_t)N * 4, hipMemcpyDeviceToHost, stream));   // best mode's log-probabilities, likewise
     if (X) TTR_HIP_CHECK(hipMemcpyAsync(h_wide[sl].p, wide_side.p, B.wide.size() * 17 * 4, hipMemcpyDeviceToHost, stream));   // the wide words' cuts (the profile stays on the device)
     if (!B.curve.empty()) TTR_HIP_CHECK(hipMemcpyAsync(h_curve[sl].p, curve_side.p, curve_side_bytes(N), hipMemcpyDeviceToHost, stream));   // the curved words' side block
@@ -873,13 +874,17 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
       r.alt_ids.assign(ai + (size_t)c0 * w, ai + (size_t)(c0 + cnt) * w);
       r.alt_prob.assign(ap + (size_t)c0 * w, ap + (size_t)(c0 + cnt) * w);
     }
-    r.lex_m = B.lex_m;
+    r.lex_m = B.lex_m; r.lex_band = B.lex_band;
     if (lex_side && cnt > 0) {   // [N][M] idx | [N][M] logp -> the page's rows
       const size_t w = (size_t)B.lex_m;
       const int32_t* li = static_cast<const int32_t*>(lex_side);
       const float* ll = reinterpret_cast<const float*>(li + (size_t)N * w);
       r.lex_idx.assign(li + (size_t)c0 * w, li + (size_t)(c0 + cnt) * w);
       r.lex_logp.assign(ll + (size_t)c0 * w, ll + (size_t)(c0 + cnt) * w);
+      if (B.lex_band >= 0) {     // fuzzy alignment: [N][M] edits behind the two blocks
+        const int32_t* le = li + (size_t)N * w * 2;
+        r.lex_edits.assign(le + (size_t)c0 * w, le + (size_t)(c0 + cnt) * w);
+      }
     }
     if (pat_logp && cnt > 0) r.pattern_logp.assign(pat_logp + c0, pat_logp + c0 + cnt);
     if (K > 1) {

@@ -483,7 +483,10 @@ void Engine::parseq_decode(const RecPass& p) {
   // character alternatives (DESIGN.md "Character alternatives"): the K best allowed classes of every position, from the same logits, mask and standard block
   if (p.with_alts()) launch_decode_alts(p.logits, p.N, p.out.ids, p.out.prob, p.alt.k, p.alt.ids, p.alt.prob, stream, p.mask, p.row_masks);
   // lexicon matching (DESIGN.md "Lexicon matching"): every word of the caller's list against every crop, from the same logits, mask and standard block
-  if (lex_v && p.with_lex()) launch_lexicon(p.logits, p.N, p.out.ids, p.out.prob, lex_records.p, lex_v, p.lex.m, p.lex.idx, p.lex.logp, p.lex.part_idx, p.lex.part_logp, stream, p.mask, p.row_masks);
+  // ... with fuzzy alignment (lex.band >= 0, decided on the host by whoever built the pass): the fuzzy scorer in the rigid one's place, its merge, the edits
+  if (lex_v && p.with_lex() && p.lex.band >= 0)
+    launch_lexicon_fuzzy(p.logits, p.N, p.out.ids, p.out.prob, lex_records.p, lex_v, p.lex.m, p.lex.band, p.lex.gap, p.lex.idx, p.lex.logp, p.lex.edits, p.lex.part_idx, p.lex.part_logp, stream, p.mask, p.row_masks);
+  else if (lex_v && p.with_lex()) launch_lexicon(p.logits, p.N, p.out.ids, p.out.prob, lex_records.p, lex_v, p.lex.m, p.lex.idx, p.lex.logp, p.lex.part_idx, p.lex.part_logp, stream, p.mask, p.row_masks);
 }
 
 }  // namespace ttr

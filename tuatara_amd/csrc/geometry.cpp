@@ -8,6 +8,7 @@
 #include <climits>
 #include <cmath>
 #include <cfloat>
+#include <limits>
 #include <map>
 #include <set>
 #include <stdexcept>
@@ -1095,6 +1096,42 @@ void lexicon_encode(const Tokenizer& tok, const char* const* words, int n, uint8
       r[1 + p] = (uint8_t)cls[ch];
     }
   }
+}
+
+int lexicon_fuzzy_from_lp(const float* lp, const uint8_t* records, int n, int band, float gap, float* logp, int32_t* edits) {
+  constexpr int kP = 26, kStride = 96;          // positions and floats per row of the table
+  if (!lp || !records || !logp || !edits || n < 0) return -1;
+  if (band < 0 || band > kLexMaxBand) return -1;
+  if (!std::isfinite(gap) || gap > 0.f) return -1;
+  for (int i = 0; i < n; ++i) {                 // everything is checked before anything is written
+    const uint8_t* r = records + (size_t)i * kLexRecord;
+    if (r[0] < 1 || r[0] > kLexMaxLen) return -1;
+    for (int k = 1; k <= kLexMaxLen; ++k) if (r[k] >= kStride) return -1;
+  }
+  struct Cell { float s; int e; };
+  const float ninf = -std::numeric_limits<float>::infinity();
+  auto take = [](Cell& cur, float s, int e) { if (s > cur.s || (s == cur.s && e < cur.e)) cur = Cell{s, e}; };
+  for (int i = 0; i < n; ++i) {
+    const uint8_t* r = records + (size_t)i * kLexRecord;
+    const int L = r[0];
+    Cell D[kLexMaxLen + 1][kP];
+    auto exists = [&](int j, int p) { return j >= 0 && j <= L && p >= 0 && p < kP && std::abs(j - p) <= band; };
+    for (int j = 0; j <= L; ++j) {
+      for (int p = 0; p < kP; ++p) {
+        Cell& c = D[j][p];
+        c = Cell{ninf, 0};
+        if (!exists(j, p)) continue;
+        if (j == 0 && p == 0) { c = Cell{0.0f, 0}; continue; }
+        if (exists(j - 1, p - 1)) take(c, D[j - 1][p - 1].s + lp[(p - 1) * kStride + r[j]], D[j - 1][p - 1].e);   // match: r[j] is entry character j-1
+        if (exists(j, p - 1)) take(c, D[j][p - 1].s + gap, D[j][p - 1].e + 1);                                     // extra character in the reading
+        if (exists(j - 1, p)) take(c, D[j - 1][p].s + gap, D[j - 1][p].e + 1);                                     // dropped character
+      }
+    }
+    Cell best{ninf, 0};
+    for (int p = 0; p < kP; ++p) if (exists(L, p)) take(best, D[L][p].s + lp[p * kStride], D[L][p].e);
+    logp[i] = best.s; edits[i] = best.e;
+  }
+  return 0;
 }
 
 }  // namespace ttr

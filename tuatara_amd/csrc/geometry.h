@@ -190,4 +190,15 @@ std::vector<Reading> nbest_from_alts(const Tokenizer& tok, const int32_t* alt_id
 constexpr int kLexMaxWords = 1 << 20, kLexMaxLen = 25, kLexRecord = 32;
 void lexicon_encode(const Tokenizer& tok, const char* const* words, int n, uint8_t* records);
 
+// Fuzzy alignment of lexicon entries (DESIGN.md "Lexicon matching", Fuzzy alignment; host only): the rule of lexicon_fuzzy.hip for n records against one
+// table lp f32 [26][96] (a crop's, as the scorers form it).  A cell D[j][p] - j characters of the entry and p positions of the reading consumed - exists for
+// 0 <= j <= L, 0 <= p <= 25, |j - p| <= band, and holds a pair (score fp32, edits int): D[0][0] = (0.0f, 0), every other cell starts at (-inf, 0); a candidate
+// replaces a cell's value iff its score is greater, or equal with fewer edits (a NaN is never taken up).  Candidates of D[j][p], each only from a cell that
+// exists: match (D[j-1][p-1].score + lp[p-1][w[j-1]], edits), extra character in the reading (D[j][p-1].score + gap, edits + 1), dropped character
+// (D[j-1][p].score + gap, edits + 1).  The end: over the cells D[L][p] that exist, (D[L][p].score + lp[p][0], edits) under the same rule from (-inf, 0): the
+// winner is logp[i] / edits[i].  Every operation is one fp32 addition or comparison.  Returns 0, -1 for a null argument, a band outside 0..3, a gap that is
+// not finite or is > 0, or a record whose length byte is outside 1..25 (nothing is written then).
+constexpr int kLexMaxBand = 3;
+int lexicon_fuzzy_from_lp(const float* lp, const uint8_t* records, int n, int band, float gap, float* logp, int32_t* edits);
+
 }  // namespace ttr

@@ -236,6 +236,16 @@ size_t lexicon_chunk_words(int N, int V, int M);        // the words per workgro
 size_t lexicon_partial_entries(int N, int V, int M);    // entries that hold the partials of any launch of up to N crops
 void launch_lexicon(const float* logits, int N, const int* ids, const float* prob, const void* records, int V, int M, int* idx, float* logp, int* part_idx,
                     float* part_logp, hipStream_t s, ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);
+// the merge of launch_lexicon on its own (lexicon_merge_kernel): the partials [N][chunks][M] of any scorer into idx / logp [N][M]
+void launch_lexicon_merge(const int* part_idx, const float* part_logp, int N, int chunks, int M, int* idx, float* logp, hipStream_t s);
+// lexicon_fuzzy.hip: the fuzzy scorer (DESIGN.md "Lexicon matching", Fuzzy alignment) in launch_lexicon's place: the same arguments, partials and outputs, a
+// word's score by the banded alignment rule (geometry.h: lexicon_fuzzy_from_lp) under band 0..3 and gap (finite, <= 0), then the merge, then - edits not
+// null - edits i32 [N][M]: the edits of each returned match, -1 in the empty slots.
+void launch_lexicon_fuzzy(const float* logits, int N, const int* ids, const float* prob, const void* records, int V, int M, int band, float gap, int* idx,
+                          float* logp, int* edits, int* part_idx, float* part_logp, hipStream_t s, ClassMask cm = ClassMask{}, const RowMask* row_masks = nullptr);
+// the tables lp f32 [N][26][96] as both scorers form them in LDS (column 95 -inf), for tests
+void launch_lexicon_tables(const float* logits, int N, const int* ids, const float* prob, float* lp, hipStream_t s, ClassMask cm = ClassMask{},
+                           const RowMask* row_masks = nullptr);
 // orient.hip: word orientation (DESIGN.md "Word orientation") - per page, the chosen candidate of every word and the page vote.  ids / prob / conf: the
 // standard block of the batch (turn 0), overwritten in place with the chosen readings; cids / cprob / cconf: the (K - 1) N twin rows, candidate-major;
 // first [pages + 1]: each page's first word; side: [N] int32 turn | [N][K] f32 candidate conf | [pages] int32 page turn.  K = 2 or 4.

@@ -66,9 +66,9 @@ struct CharsetScope {
   ttr_engine* e;
   std::unique_lock<std::mutex> turn;
   bool set = false, ok = true;
-  bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false, curved_set = false;
+  bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false, curved_set = false, fuzzy_set = false;
   CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
-               std::string pattern = std::string(), float wide = 0.f, bool pattern_best = false, bool curved = false) : e(e_) {
+               std::string pattern = std::string(), float wide = 0.f, bool pattern_best = false, bool curved = false, LexFuzzy fuzzy = LexFuzzy{-1, 0.f}) : e(e_) {
     {
       std::lock_guard<std::mutex> lk(g_mu);
       auto& m = g_call_mu[e];
@@ -92,6 +92,10 @@ struct CharsetScope {
         std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return;
       }
       lex_set = true;
+      if (fuzzy.band >= 0) {   // ... and its fuzzy alignment (DESIGN.md "Lexicon matching", Fuzzy alignment): the band and gap for the call, like the list
+        if (ttr_engine_set_lexicon_fuzzy(e, fuzzy.band, fuzzy.gap) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+        fuzzy_set = true;
+      }
     }
     if (wide == 0.f) if (const char* p = std::getenv("TUATARA_WIDE")) wide = std::string(p) == "1" ? 8.f : (float)std::atof(p);
     if (wide != 0.f) {   // wide words (DESIGN.md "Wide words"): the largest aspect of a piece for the call, like the set
@@ -125,6 +129,7 @@ struct CharsetScope {
     if (curved_set) ttr_engine_set_curved(e, 0);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
     if (alts_set) ttr_engine_set_alternatives(e, 0);
+    if (fuzzy_set) ttr_engine_set_lexicon_fuzzy(e, -1, 0.f);
     if (lex_set) ttr_engine_set_lexicon(e, nullptr, 0, 0);
   }
 };
@@ -186,9 +191,10 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
   o.lexicon.clear();
   if (const int32_t* li = ttr_result_lex_idx(r, i)) {
     const float* ll = ttr_result_lex_logp(r, i);
+    const int32_t* le = ttr_result_lex_edits(r, i);   // fuzzy alignment: null when the mode is off
     for (int j = 0, M = ttr_result_lex_m(r); j < M && li[j] >= 0; ++j) {
       LexMatch mt;
-      mt.index = li[j]; mt.logp = ll[j];
+      mt.index = li[j]; mt.logp = ll[j]; mt.edits = le ? le[j] : 0;
       o.lexicon.push_back(std::move(mt));
     }
   }
@@ -242,10 +248,10 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
                           const std::string& outputs_dir, int crop_mode, int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
                                         int blocks = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0,
                                         const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string(), float wide = 0.f,
-                                        bool pattern_best = false, bool curved = false) {
+                                        bool pattern_best = false, bool curved = false, LexFuzzy fuzzy = LexFuzzy{-1, 0.f}) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern, wide, pattern_best, curved);
+  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern, wide, pattern_best, curved, fuzzy);
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
@@ -266,10 +272,11 @@ template <class Item>
 std::vector<std::vector<Item>> run_many(const std::vector<ImageView>& images, const std::string& weights_dir, const std::string& outputs_dir, int crop_mode,
                                         int orient = -1, int orient_page = 0, int lines = -1, int chars = -1,
                                         int blocks = -1, int mixed = -1, const std::string& allow = std::string(), const std::string& deny = std::string(), int alts = 0,
-                                        const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string(), bool pattern_best = false) {
+                                        const std::vector<std::string>* words = nullptr, int lex_m = 0, const std::string& pattern = std::string(), bool pattern_best = false,
+                                        LexFuzzy fuzzy = LexFuzzy{-1, 0.f}) {
   ttr_engine* e = open_engine(weights_dir, outputs_dir, crop_mode, orient, orient_page, lines, chars, blocks, mixed);
   if (!e) return {};
-  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern, 0.f, pattern_best);
+  CharsetScope cs(e, allow, deny, alts, words, lex_m, pattern, 0.f, pattern_best, false, fuzzy);
   if (!cs.ok) return {};
   const int n = (int)images.size();
   std::vector<const uint8_t*> ptr(n);
@@ -421,6 +428,21 @@ std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<Image
 
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
+                                           std::string allowlist, std::string blocklist, int alts, const std::vector<std::string>& words, int m, int band, float gap) {
+  return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1,
+                               chars ? 1 : -1, blocks ? 1 : -1, allowlist, blocklist, alts, &words, m, std::string(), 0.f, false, false, LexFuzzy{band, gap});
+}
+
+std::vector<std::vector<OutputItemEx>> images_to_data_ex(const std::vector<ImageView>& images, std::string weights_dir, std::string outputs_dir,
+                                                         bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks, bool mixed_batches,
+                                                         std::string allowlist, std::string blocklist, int alts, const std::vector<std::string>& words, int m,
+                                                         int band, float gap) {
+  return run_many<OutputItemEx>(images, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1, chars ? 1 : -1,
+                                blocks ? 1 : -1, mixed_batches ? 1 : -1, allowlist, blocklist, alts, &words, m, std::string(), false, LexFuzzy{band, gap});
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
                                            std::string allowlist, std::string blocklist, std::string pattern) {
   return run_one<OutputItemEx>(image, rows, cols, row_stride, weights_dir, outputs_dir, rectify ? TTR_CROP_RECTIFIED : -1, orient, orient_page ? 1 : 0, lines ? 1 : -1,
                                chars ? 1 : -1, blocks ? 1 : -1, allowlist, blocklist, 0, nullptr, 0, pattern);
@@ -491,7 +513,7 @@ std::vector<WordReading> nbest(const OutputItemEx& item, int m) {
 namespace {
 std::vector<OutputItemEx> read_regions(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, const std::string& weights_dir,
                                        const std::string& outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>* words, int lex_m,
-                                       bool pattern_best = false) {
+                                       bool pattern_best = false, LexFuzzy fuzzy = LexFuzzy{-1, 0.f}) {
   // every list and quad is checked on the host before an engine is opened
   std::vector<ttr_region> regs(regions.size());
   std::vector<uint32_t> sets;
@@ -520,7 +542,7 @@ std::vector<OutputItemEx> read_regions(const uint8_t* image, int rows, int cols,
   ttr_engine* e = open_engine(weights_dir, outputs_dir, -1, -1, 0, -1, -1, -1);
   if (!e) return {};
   if (!pattern_best && !pats.empty()) if (const char* p = std::getenv("TUATARA_PATTERN_BEST")) pattern_best = std::string(p) == "1";   // (regions with patterns of their own)
-  CharsetScope cs(e, std::string(), std::string(), alts, words, lex_m, std::string(), 0.f, pattern_best);   // (the engine's own set for regions without lists: TUATARA_ALLOWLIST / TUATARA_BLOCKLIST; calls that share the engine take turns)
+  CharsetScope cs(e, std::string(), std::string(), alts, words, lex_m, std::string(), 0.f, pattern_best, false, fuzzy);   // (the engine's own set for regions without lists: TUATARA_ALLOWLIST / TUATARA_BLOCKLIST; calls that share the engine take turns)
   if (!cs.ok) return {};
   if (!image || rows <= 0 || cols <= 0) {  // tuatara.cpp:344-347
     std::cerr << "Error reading image from file";
@@ -553,4 +575,10 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
                                            std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>& words, int m) {
   return read_regions(image, rows, cols, row_stride, weights_dir, outputs_dir, regions, alts, &words, m);
+}
+
+std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
+                                           std::string outputs_dir, const std::vector<RegionSpec>& regions, int alts, const std::vector<std::string>& words, int m,
+                                           int band, float gap) {
+  return read_regions(image, rows, cols, row_stride, weights_dir, outputs_dir, regions, alts, &words, m, false, LexFuzzy{band, gap});
 }

@@ -173,6 +173,14 @@ SYMBOLS = [
     ("ttr_result_lex_logp_all", _PF, [_VP]),
     ("ttr_lexicon_encode", _I, [C.POINTER(C.c_char_p), _I, _PU8]),
     ("ttr_logits_lexicon", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _I, _PI, _PI, _PF]),
+    ("ttr_engine_set_lexicon_fuzzy", _I, [_VP, _I, C.c_float]),
+    ("ttr_engine_lexicon_fuzzy", _I, [_VP, _PI, _PF]),
+    ("ttr_result_lex_band", _I, [_VP]),
+    ("ttr_result_lex_edits", _PI, [_VP, _I]),
+    ("ttr_result_lex_edits_all", _PI, [_VP]),
+    ("ttr_lexicon_fuzzy_from_lp", _I, [_PF, _PU8, _I, _I, C.c_float, _PF, _PI]),
+    ("ttr_logits_lexicon_fuzzy", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _I, _PI, _I, C.c_float, _PI, _PF, _PI]),
+    ("ttr_debug_lexicon_tables", _I, [_VP, _PF, _I, C.POINTER(C.c_uint32), _I, _PI, _PF]),
     ("ttr_craft_heatmap", _I, [_VP, _PU8, _I, _I, _PF]),
     ("ttr_ccl_boxes", _I, [_VP, _PF, _I, _I, _PF, _I, _PI]),
     ("ttr_resize_canvas", _I, [_VP, _PU8, _I, _I, _I, _PU8, C.c_size_t, _PI, _PI, _PF]),
@@ -682,6 +690,24 @@ def lexicon_matches(words, idx, logp) -> list:
     return [(words[int(i)], float(np.exp(np.float64(l)))) for i, l in zip(idx, logp) if int(i) >= 0]
 
 
+LEXICON_GAP = float(np.float32(-6.9077554))   # ln 1e-3: the default gap of fuzzy alignment, at band 1; neither has been tuned on documents
+
+
+def lexicon_fuzzy_from_lp(lp, records, band: int, gap: float = LEXICON_GAP):
+    """Fuzzy alignment of lexicon entries on the host (ttr_lexicon_fuzzy_from_lp, no GPU; DESIGN.md "Lexicon matching", Fuzzy alignment): one table lp f32
+    [26, 96] and records u8 [n, 32] (lexicon_encode's) -> (logp f32 [n], edits i32 [n]) under a band 0..3 and a gap (finite, <= 0).  Raises EngineError for a
+    band or gap out of range and for a record whose length byte is outside 1..25."""
+    lp = np.ascontiguousarray(lp, dtype=np.float32)
+    if lp.shape != (26, 96):
+        raise ValueError("lp is one crop's table, f32 [26, 96]")
+    records = np.ascontiguousarray(records, dtype=np.uint8).reshape(-1, 32)
+    n = len(records)
+    logp, edits = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32)
+    if load().ttr_lexicon_fuzzy_from_lp(_f(lp), _u8(records) if n else _u8(np.zeros(32, np.uint8)), n, int(band), float(gap), _f(logp), _i(edits)) != 0:
+        raise EngineError("lexicon_fuzzy_from_lp: the band must lie in 0..3, the gap be finite and <= 0, every record's length in 1..25")
+    return logp[:n], edits[:n]
+
+
 def _is_char(c: int) -> bool:
     return 1 <= c < 95 and c != 88
 
@@ -879,7 +905,7 @@ class PageResult(collections.abc.Sequence):
                  "line", "word", "order", "line_first", "line_bbox",
                  "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad",
                  "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode", "alt_ids", "alt_prob",
-                 "lex_idx", "lex_logp", "lex_words", "pattern_logp", "piece_first", "piece_ids", "piece_prob", "piece_conf", "piece_quad", "piece_cuts",
+                 "lex_idx", "lex_logp", "lex_words", "lex_edits", "lex_band", "pattern_logp", "piece_first", "piece_ids", "piece_prob", "piece_conf", "piece_quad", "piece_cuts",
                  "curved", "outline", "spine_knots")
 
     def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0,
@@ -888,7 +914,8 @@ class PageResult(collections.abc.Sequence):
                  block=None, line_block=None, line_pos=None, block_order=None, block_first=None, block_bbox=None, block_mode=0,
                  alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None, pattern_logp=None,
                  piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None,
-                 curved=None, outline=None, spine_knots=None):
+                 curved=None, outline=None, spine_knots=None, lex_edits=None, lex_band=-1):
+        self.lex_edits, self.lex_band = lex_edits, lex_band
         self.curved, self.outline, self.spine_knots = curved, outline, spine_knots
         self.piece_first, self.piece_ids, self.piece_prob = piece_first, piece_ids, piece_prob
         self.piece_conf, self.piece_quad, self.piece_cuts = piece_conf, piece_quad, piece_cuts
@@ -937,6 +964,8 @@ class PageResult(collections.abc.Sequence):
             d["alternatives"] = char_alternatives(self.alt_ids[j], self.alt_prob[j])
         if self.lex_idx is not None:
             d["lexicon"] = lexicon_matches(self.lex_words, self.lex_idx[j], self.lex_logp[j])
+            if self.lex_edits is not None:      # fuzzy alignment: each match's edits, beside the (word, prob) pairs
+                d["lexicon_edits"] = [int(e) for i, e in zip(self.lex_idx[j], self.lex_edits[j]) if int(i) >= 0]
         if self.pattern_logp is not None:
             d["pattern_logp"] = float(self.pattern_logp[j])
         if self.piece_first is not None:
@@ -1045,6 +1074,7 @@ class Engine:
         cfg.strict_crops = int(strict_crops)
         alts = int(overrides.pop("alts", 0) or 0)                                         # not a config field either: set_alternatives, below
         lexicon, lexicon_m = overrides.pop("lexicon", None), int(overrides.pop("lexicon_m", 1))   # nor these: set_lexicon, below
+        lexicon_fuzzy, lexicon_gap = overrides.pop("lexicon_fuzzy", None), float(overrides.pop("lexicon_gap", LEXICON_GAP))   # nor these: set_lexicon_fuzzy, below
         pattern = overrides.pop("pattern", None)                                          # nor this: set_pattern, below
         pattern_best = bool(overrides.pop("pattern_best", False))                         # nor this: set_pattern_decode, below
         wide = _wide_arg(overrides.pop("wide", None))                                     # nor this: set_wide, below
@@ -1064,6 +1094,8 @@ class Engine:
             self.set_alternatives(alts)
         if lexicon is not None:
             self.set_lexicon(lexicon, lexicon_m)
+        if lexicon_fuzzy is not None:
+            self.set_lexicon_fuzzy(lexicon_fuzzy, lexicon_gap)
         if pattern_best:
             self.set_pattern_decode(PATTERN_BEST)
         if pattern:
@@ -1144,6 +1176,22 @@ class Engine:
             raise EngineError(self.lib.ttr_last_error().decode("latin1"))
         self._lex_words = [] if words is None else [w.decode("latin1") if isinstance(w, bytes) else str(w) for w in words]
 
+    def set_lexicon_fuzzy(self, band, gap: float = LEXICON_GAP):
+        """Fuzzy alignment of the lexicon's entries (ttr_engine_set_lexicon_fuzzy; DESIGN.md "Lexicon matching", Fuzzy alignment): band 0..3 aligns every
+        entry against the reading instead of indexing it - a dropped or an extra character costs `gap` (a log-probability, finite, <= 0; the default ln 1e-3
+        at band 1 has not been tuned on documents) - and every PageResult then carries lex_edits beside lex_idx / lex_logp, its dicts "lexicon_edits".
+        None or -1 switches it off.  It may be set with no lexicon in place and survives set_lexicon.  Raises EngineError, and changes nothing, for a band or
+        gap out of range and between a stream_push and its flush."""
+        if self.lib.ttr_engine_set_lexicon_fuzzy(self.h, -1 if band is None else int(band), float(gap)) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def lexicon_fuzzy(self):
+        """(band, gap) in force, None when fuzzy alignment is off"""
+        b, g = C.c_int(-1), C.c_float(0.0)
+        self.lib.ttr_engine_lexicon_fuzzy(self.h, C.byref(b), C.byref(g))
+        return None if b.value < 0 else (int(b.value), float(g.value))
+
     @property
     def lexicon_size(self) -> int:
         """V in force (0 = no lexicon)"""
@@ -1175,6 +1223,37 @@ class Engine:
                 raise ValueError("set_of holds one entry per row")
         self._check(self.lib.ttr_logits_lexicon(self.h, _f(logits), n, sp, ns, _i(so) if so is not None else None, _i(idx), _f(logp)))
         return idx, logp
+
+    def _rows_sets(self, n, set_of, sets):
+        sp, ns, keep = _sets_arg(sets)
+        so = None
+        if sp is not None:
+            if set_of is None:
+                raise ValueError("sets need set_of, one entry per row")
+            so = np.ascontiguousarray(set_of, dtype=np.int32).ravel()
+            if len(so) != n:
+                raise ValueError("set_of holds one entry per row")
+        return sp, ns, so, keep
+
+    def logits_lexicon_fuzzy(self, logits: np.ndarray, band: int, gap: float = LEXICON_GAP, set_of=None, sets=None):
+        """logits_lexicon through the fuzzy scorer under (band, gap), whatever the engine's mode (ttr_logits_lexicon_fuzzy) -> (idx i32 [n, M], logp f32
+        [n, M], edits i32 [n, M]; -1 / -inf / -1 in the empty slots)."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, 26, 95)
+        n, M = len(logits), max(self.lexicon_m, 1)
+        idx, logp, edits = np.full((n, M), -1, np.int32), np.full((n, M), -np.inf, np.float32), np.full((n, M), -1, np.int32)
+        sp, ns, so, _keep = self._rows_sets(n, set_of, sets)
+        self._check(self.lib.ttr_logits_lexicon_fuzzy(self.h, _f(logits), n, sp, ns, _i(so) if so is not None else None, int(band), float(gap), _i(idx), _f(logp),
+                                                      _i(edits)))
+        return idx, logp, edits
+
+    def debug_lexicon_tables(self, logits: np.ndarray, set_of=None, sets=None) -> np.ndarray:
+        """the lexicon's tables as the device forms them (ttr_debug_lexicon_tables): host logits f32 [n, 26, 95] -> lp f32 [n, 26, 96], column 95 -inf"""
+        logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1, 26, 95)
+        n = len(logits)
+        lp = np.zeros((n, 26, 96), np.float32)
+        sp, ns, so, _keep = self._rows_sets(n, set_of, sets)
+        self._check(self.lib.ttr_debug_lexicon_tables(self.h, _f(logits), n, sp, ns, _i(so) if so is not None else None, _f(lp)))
+        return lp
 
     def set_alternatives(self, k: int):
         """K alternatives per character position, the winner included (ttr_engine_set_alternatives; DESIGN.md "Character alternatives"): 0 = off, or
@@ -1433,6 +1512,10 @@ class Engine:
                 li, ll = self.lib.ttr_result_lex_idx_all(arr[i]), self.lib.ttr_result_lex_logp_all(arr[i])
                 lex.update(lex_idx=np.ctypeslib.as_array(li, (c, M)).copy() if li else np.zeros((0, M), np.int32),
                            lex_logp=np.ctypeslib.as_array(ll, (c, M)).copy() if ll else np.zeros((0, M), np.float32), lex_words=self._lex_words)
+                band = int(self.lib.ttr_result_lex_band(arr[i]))
+                if band >= 0:                   # fuzzy alignment: the matches' edits
+                    le = self.lib.ttr_result_lex_edits_all(arr[i])
+                    lex.update(lex_band=band, lex_edits=np.ctypeslib.as_array(le, (c, M)).copy() if le else np.zeros((0, M), np.int32))
             pl = self.lib.ttr_result_pattern_logp(arr[i])
             if pl:                              # patterns in best mode: the page's log-probabilities
                 lex["pattern_logp"] = np.ctypeslib.as_array(pl, (c,)).copy()
@@ -1594,6 +1677,8 @@ class Engine:
                     items[-1].update({"curved": int(page.curved[k]), "outline": page.outline[k].tolist(), "spine_knots": page.spine_knots[k]})
                 if page.lex_idx is not None:        # lexicon matching: each region under its own set
                     items[-1].update({"lex_idx": page.lex_idx[k], "lex_logp": page.lex_logp[k], "lexicon": lexicon_matches(page.lex_words, page.lex_idx[k], page.lex_logp[k])})
+                    if page.lex_edits is not None:  # fuzzy alignment: likewise
+                        items[-1].update({"lex_edits": page.lex_edits[k], "lexicon_edits": [int(e) for i, e in zip(page.lex_idx[k], page.lex_edits[k]) if int(i) >= 0]})
                 if page.pattern_logp is not None:   # patterns in best mode: each region under its own pattern and set
                     items[-1]["pattern_logp"] = float(page.pattern_logp[k])
             out.append(items)
