@@ -120,6 +120,23 @@ int ttr_dbg_orient_quad(const float* rect5, int h, int w, int crop_mode, int tur
 /* canvas_geometry on the host for any canvas_size / mag_ratio (what ttr_canvas_geometry answers for an engine of that config): h32 x w32, the ratio and
  * the resized page's target_h x target_w inside the canvas.  Any output may be NULL.  Returns 0, -1 for h <= 0 or w <= 0. */
 int ttr_dbg_canvas_geometry(int h, int w, int canvas_size, float mag_ratio, int* H, int* W, float* ratio, int* target_h, int* target_w);
+/* launch groups of the f16x4 engine on the host (DESIGN.md "Launch groups"): pages per CRAFT group for a batch of n_pages canvases of H x W (multiples of 32) and
+ * crops per encoder group for n_crops crops, under the tuning values given - craft_group, first_fused (the effective switch), craft_products, up_commute; enc_chunk
+ * (0 = the engine's default cap of 1820 crops; larger values lift it up to the window), enc_fc2_pairs, qkv_attn_split, enc_ln_pairs, sp_hidden16 - with the bytes
+ * per page / per crop of the widest tensor the kernels address with 32-bit offsets.
+ * group x bytes never exceeds 2^31 - 1, except where ONE page is already wider than that (2560 x 2560 as triples): the group is then 1 and the forward pass
+ * refuses the page.  Any output may be NULL.  Returns 0, -1 on bad arguments. */
+int ttr_dbg_launch_groups(int H, int W, int n_pages, int n_crops, int craft_group, int first_fused, int craft_products, int up_commute, int enc_chunk,
+                          int enc_fc2_pairs, int qkv_attn_split, int enc_ln_pairs, int sp_hidden16, int* craft_pages, int* enc_crops, int64_t* page_bytes,
+                          int64_t* crop_bytes);
+/* the shape checks of the f16x4 layer launchers on the host (no GPU, nothing is launched): kernel 0 = the patch-stationary 3x3 kernel, 1 = the split GEMM loop, 2 = the 3x3 kernel with conv1_1 fused in front (pooled output only), on a
+ * layer of B x H x W pixels, C0 -> Cout channels, ks x ks taps, products 3 (pairs) / 4 (triples), out_planes 0 / 2 / 3, pooled != 0 = with the fused 2x2 max-pool
+ * output.  Returns 0 when the launcher takes the layer, 1 when it refuses (text, may be NULL, receives its reason), -1 on bad arguments. */
+int ttr_dbg_split_layer_check(int kernel, int B, int H, int W, int C0, int Cout, int ks, int products, int out_planes, int pooled, char* text, size_t cap);
+/* what the engine's last batch of pages and last recogniser pass ran with: pages per CRAFT launch group, crops per encoder group (0 = none yet) */
+int ttr_dbg_last_groups(ttr_engine* e, int* craft_pages, int* enc_crops);
+/* the heat maps of the engine's last batch of n pages, f32 [n][H/2][W/2][2], as its detector left them on the device.  Refuses while batches stream. */
+int ttr_dbg_last_heat(ttr_engine* e, float* heat, size_t floats);
 
 
 #ifdef __cplusplus

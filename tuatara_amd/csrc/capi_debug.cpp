@@ -547,6 +547,55 @@ int ttr_dbg_canvas_geometry(int h, int w, int canvas_size, float mag_ratio, int*
   return 0;
 }
 
+int ttr_dbg_launch_groups(int H, int W, int n_pages, int n_crops, int craft_group, int first_fused, int craft_products, int up_commute, int enc_chunk,
+                          int enc_fc2_pairs, int qkv_attn_split, int enc_ln_pairs, int sp_hidden16, int* craft_pages, int* enc_crops, int64_t* page_bytes,
+                          int64_t* crop_bytes) {
+  if (H <= 0 || W <= 0 || H % 32 || W % 32 || n_pages < 1 || n_crops < 1 || craft_group < 1) return -1;
+  const int products = craft_products == 4 ? 4 : 3;
+  const CraftGroupCfg cc{first_fused && products != 4 ? 1 : 0, products, up_commute};
+  const EncGroupCfg ec{enc_fc2_pairs, qkv_attn_split, enc_ln_pairs, sp_hidden16};
+  if (craft_pages) *craft_pages = craft_group_pages(H, W, n_pages, std::min(craft_group, 32), cc);
+  if (enc_crops) *enc_crops = encoder_group_crops(n_crops, enc_chunk, ec);
+  if (page_bytes) *page_bytes = (int64_t)craft_widest_per_page(H, W, cc).bytes;
+  if (crop_bytes) *crop_bytes = (int64_t)encoder_bytes_per_crop(ec).widest().bytes;
+  return 0;
+}
+
+int ttr_dbg_split_layer_check(int kernel, int B, int H, int W, int C0, int Cout, int ks, int products, int out_planes, int pooled, char* text, size_t cap) {
+  if (B < 1 || H < 1 || W < 1 || (int64_t)B * H * W > 0x7fffffff || (products != 3 && products != 4)) return -1;
+  ConvParams p{};
+  void* const any = reinterpret_cast<void*>((uintptr_t)4096);   // (aligned and never dereferenced: the checks read shapes and alignments only)
+  p.in0 = any; p.C0 = C0; p.B = B; p.H = H; p.W = W; p.ks = ks; p.dil = 1;
+  p.wgt = any; p.bias = reinterpret_cast<const float*>(any); p.split = products; p.out_scale = 1.f; p.out_planes = out_planes;
+  p.out = any; p.out_ld = Cout; p.out_pool = pooled ? any : nullptr; p.Cout = Cout; p.M = B * H * W; p.act = kActRelu;
+  if (kernel == 2) { p.pre_wgt = any; p.pre_bias = reinterpret_cast<const float*>(any); p.pre_scale = 1.f; p.out = nullptr; p.out_pool = any; }   // conv1_1 fused in front: in0 is the u8 canvas
+  const char* e = kernel == 1 ? gemm2_check(p) : conv3p_check(p);
+  if (text && cap) { const std::string s = e ? e : ""; memcpy(text, s.c_str(), std::min(cap - 1, s.size())); text[std::min(cap - 1, s.size())] = 0; }
+  return e ? 1 : 0;
+}
+
+int ttr_dbg_last_groups(ttr_engine* e, int* craft_pages, int* enc_crops) {
+  TTR_GUARD_BEGIN
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (craft_pages) *craft_pages = E.last_craft_group;
+  if (enc_crops) *enc_crops = E.last_enc_group;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_dbg_last_heat(ttr_engine* e, float* heat, size_t floats) {
+  TTR_GUARD_BEGIN
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_dbg_last_heat");
+  if (!heat || floats == 0 || floats * 4 > E.heat.cap) throw std::runtime_error("ttr_dbg_last_heat: more floats than the last batch's heat maps hold");
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  TTR_HIP_CHECK(hipMemcpy(heat, E.heat.p, floats * 4, hipMemcpyDeviceToHost));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_dbg_orient_quad(const float* r5, int h, int w, int crop_mode, int turn, float* quad8, int64_t* fixed6) {
   TTR_GUARD_BEGIN
   if (turn < 0 || turn > 3 || (crop_mode != TTR_CROP_BOUNDING && crop_mode != TTR_CROP_RECTIFIED)) throw std::runtime_error("bad turn or crop_mode");

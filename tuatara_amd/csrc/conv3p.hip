@@ -340,6 +340,7 @@ __global__ __launch_bounds__(WM * WN * 64, (XS == 1 && BN <= 128 && !(BN == 128 
   // BN = 128 on FOUR waves (WN = 1: wave tiles of 64 pixels x all 128 channels, 64 MFMAs per tap and wave, 24 fragment reads instead of 32 per 64 MFMAs; two
   // workgroups per CU = two waves per SIMD with 256 registers each) takes this loop too: the experiment behind the tuning key c3_c128_waves.
   constexpr bool STATIC_ADDR = XS == 1 && (BN <= 64 || (BN == 128 && WN == 1)) && C::TM == 64 && (!FIRST || SP);
+  static_assert(!(FIRST && SP) || STATIC_ADDR, "the fused first layer on pairs runs this loop, which never requests its input through stage_x (conv3p_check sizes it by the u8 canvas, not by the 64 channels)");
   if constexpr (STATIC_ADDR) {
     const int pib = ((wm * C::TM) >> LPW) * HW2 + fr;
     int xbase[8];                                          // byte offsets from smem (32-bit LDS arithmetic)
@@ -1230,6 +1231,7 @@ void set_conv3p_force_bn128(int v) { g_force_bn128 = v; }
 static int g_xs1_max_cin = 1 << 20;   // layers with Cout <= 128 and Cin up to this use one patch stage and two workgroups per CU
 void set_conv3p_single_stage_max_cin(int c) { g_xs1_max_cin = c; }
 
+// (reads shapes and the operands' alignments only and never dereferences a pointer: ttr_dbg_split_layer_check runs it on the host with placeholder addresses)
 const char* conv3p_check(const ConvParams& p) {
   if (p.split) {   // f16 planes in; fp32 or planes out
     if (p.ks != 3 || p.dil != 1 || p.C1 || p.relu0 || p.relu1) return "conv3p: 3x3, dilation 1, single source";
@@ -1250,7 +1252,13 @@ const char* conv3p_check(const ConvParams& p) {
     if (p.split != 2 && p.split != 3 && p.split != 4) return "conv3p: split must be 2 (packed pairs), 3 or 4";
     if (p.split == 2 && (p.C0 != 64 || p.Cout > 32)) return "conv3p: packed pairs are the 32-channel layers' form (64 halves per pixel, Cout <= 32)";
     if (p.out_planes != 0 && p.out_planes != 2 && p.out_planes != 3) return "conv3p: out_planes must be 0, 2 or 3";
-    if ((size_t)p.M * p.C0 * (p.split == 4 ? 6 : p.split == 3 ? 4 : 2) >= lim || (size_t)p.Cout * 27 * p.C0 * 2 >= lim) return "conv3p: tensor too large for 32-bit buffer offsets";
+    // (the fused first pair reads the u8 canvas - 3 bytes per pixel, through 64-bit pointers, sized above - and never forms its 64-channel input: the patch loader's
+    // offsets, which 16 pages of 1024 x 768 would put past 2^31, are not part of that kernel: FIRST on pairs runs the one-stage loop and never calls stage_x)
+    const size_t in_bytes = p.pre_wgt ? (size_t)p.M * 3 : (size_t)p.M * p.C0 * (p.split == 4 ? 6 : p.split == 3 ? 4 : 2);
+    if (in_bytes >= lim || (size_t)p.Cout * 27 * p.C0 * 2 >= lim) return "conv3p: tensor too large for 32-bit buffer offsets";
+    // (the epilogue stores through 64-bit pointers, but what it writes is the next layer's input: a tensor past the window is refused where it would be made)
+    const size_t out_row = (size_t)p.out_ld * (p.out_planes ? 2 * p.out_planes : 4);
+    if ((p.out && (size_t)p.M * out_row >= lim) || (p.out_pool && (size_t)(p.M / 4) * out_row >= lim)) return "conv3p: output too large for 32-bit buffer offsets";
     if (p.M != p.B * p.H * p.W || p.M <= 0 || !(p.out_scale > 0.f)) return "conv3p: bad shape";
     return nullptr;
   }

@@ -80,7 +80,9 @@ struct Tuning {
   int sp_tiled_w = 1;         // split engines: gemm_sp.hip reads the recogniser's weight planes as contiguous 1-KiB pieces (Linear::wst)
   int ar_host_check = 10;     // split / fp32 engines, batches of <= 256 crops (the latency regime): from this AR step on the host looks at the done counter every fourth
                               // step and stops enqueuing steps once every crop has emitted EOS (upstream's loop does that check every step); 0 = never
-  int enc_chunk = 0;          // crops per encoder group (0 = all crops at once)
+  int enc_chunk = 0;          // crops per encoder group, at most.  f16x4: capped by what the widest tensor of the configuration allows inside the 2 GiB window
+                              // (encoder_group_crops below: 2730 on the default path), 0 = 1820 (kEncGroupDefault: 2560 crops = 1280 + 1280; enc_chunk = 4096 runs them
+                              // as one group).  bf16 / f32: 0 = all crops at once
   int enc_ln_pairs = 1;       // split-operand engines, PARSeq encoder: LayerNorm outputs as pairs (qkv and fc1 on three MFMAs per product: their inputs tolerate ~23.5 bits - 3 x 1280 crops: max |dlogit| 7.6e-4 vs 6.9e-4 with triples; proj and fc2 keep exact triples); 0 = triples
   int dec_planes = 1;         // split-operand engines: the decoder's layers hand each other planes (13 launches per AR step instead of 20); 0 = fp32 tensors + split passes
   int qkv_kv_pairs = 1;       // the qkv GEMM leaves the third plane of its K and V columns unwritten (the attention kernel reads them as pairs)
@@ -100,7 +102,9 @@ struct Tuning {
   int split_planes = 1;       // split-operand engines: activations stay in planes between the layers (0: fp32 tensors + a split pass in front of every GEMM)
   int split_conv3p = 1;       // split-operand engines: 3x3 layers on the patch-stationary kernel (0: gemm2)
   int split_gemm = 1;         // split-operand engines: 0 = every layer on the fp32 MFMA kernel (A/B and tests)
-  int craft_group = 16;       // pages per CRAFT launch group (activation workspace ~0.5 GB/page; every tensor must stay inside the 2 GiB window of 32-bit buffer offsets)
+  int craft_group = 16;       // pages per CRAFT launch group, at most (1 .. 32).  f16x4: capped by what the widest tensor of the configuration allows inside the 2 GiB
+                              // window of 32-bit buffer offsets (craft_group_pages below: 21 pages of 1024 x 768 with first_fused, 10 without, 7 as triples), then evened
+                              // to 16 or 8; activation workspace ~0.35 GB/page.  craft_group = 8 is the schedule of before the cap followed the configuration
   int ar_tail_step = 12;      // with ar_early_exit: AR steps from this one on run as ONE launch of the fused kernel (which returns at once when the batch is done)
   int ar_crop_exit = 1;       // ... and, per crop, the two attention kernels of a step return for crops that have emitted EOS
   int ar_early_exit = 1;      // bf16 kernel-per-op AR loop: the steps' kernels return at once when every crop of the batch has emitted EOS (upstream's break)
@@ -167,6 +171,35 @@ struct Tuning {
   }
 };
 extern Tuning g_tuning_default;   // engine.cpp
+
+// ------------------------------------------------------------------ launch groups (DESIGN.md section d / e: "Launch groups")
+// The f16x4 kernels address their plane tensors with 32-bit buffer offsets: a tensor of a launch must end below 2^31 bytes (0x80000000 is the loaders'
+// out-of-range marker).  The detector therefore walks a batch in groups of pages and the encoder one in groups of crops, as large as the WIDEST tensor of the
+// configuration in force allows.  These functions are that figure, pure host arithmetic (ttr_dbg_launch_groups): the caps, the workspaces and the forward
+// passes' own refusals all come from them, so that none can drift from the others.
+constexpr size_t kOffsetWindow = ((size_t)1 << 31) - 1;   // most bytes a tensor addressed with 32-bit offsets may hold
+struct Widest { size_t bytes; const char* layer; };       // bytes per page / per crop of the widest tensor, and the layer that writes it
+// CRAFT on a canvas of H x W (a multiple of 32 each), f16x4: every tensor craft_forward_split hands a kernel.  first_fused is the EFFECTIVE switch (the tuning key,
+// pairs and the split 3x3 tiles on); craft_products 3 = pairs (4 bytes per value), 4 = triples (6)
+struct CraftGroupCfg { int first_fused = 1, craft_products = 3, up_commute = 1; };
+Widest craft_widest_per_page(int H, int W, const CraftGroupCfg& c);
+// pages per CRAFT launch group for a batch of n: min(craft_group, window / per page), then evened - 16 when n % 16 == 0, else 8 when n % 8 == 0 (64 pages = 4 x 16
+// rather than 21 + 21 + 21 + 1)
+int craft_group_pages(int H, int W, int n, int craft_group, const CraftGroupCfg& c);
+// the split encoder's tensors per crop (128 rows): LayerNorm planes, the qkv planes of the unfused path (0 when qkv + attention are one launch), the MLP hidden,
+// the attention output; sp_hidden16 moves the hidden's layout, not its size
+struct EncGroupCfg { int enc_fc2_pairs = 1, qkv_attn_split = 1, enc_ln_pairs = 1, sp_hidden16 = 0; };
+struct EncTensors {
+  size_t ln, qkv, hidden, att;
+  size_t big() const { return std::max(qkv, hidden); }   // kWsBigPlanes holds either
+  Widest widest() const;
+};
+EncTensors encoder_bytes_per_crop(const EncGroupCfg& c);
+// crops per encoder group for N crops: min(window / per crop, enc_chunk), then even groups (2731 crops = 1366 + 1365 under enc_chunk = 4096).  enc_chunk = 0 stands
+// for kEncGroupDefault: one group of the benchmark's 2560 crops fits the window of the default path, but measured against 1280 + 1280 on the same box it was never
+// ahead (-1.3 % pages/s beside 8-page CRAFT groups, +-0.3 % beside 16-page ones: profiles/groups.md), so the groups of before stay the default and the key lifts them
+constexpr int kEncGroupDefault = 1820;
+int encoder_group_crops(int N, int enc_chunk, const EncGroupCfg& c);
 
 // ------------------------------------------------------------------ small utilities
 // roctx ranges around the host phases of a batch (rocprofv3 --marker-trace shows them next to the kernels).
@@ -472,6 +505,10 @@ struct Engine {
   hipEvent_t lane_go = nullptr, lane_done = nullptr, resize_done = nullptr;
   bool lane_go_pending = false;                   // craft_forward_split records lane_go behind slice3.20 when set
   int craft_ws_npl = 0;                           // planes per value the split CRAFT workspaces were laid out for
+  // launch groups (above): the configuration in force, and what the last batch / recogniser pass ran with (ttr_dbg_last_groups)
+  CraftGroupCfg craft_group_cfg() const { return CraftGroupCfg{tn.first_fused && tn.craft_products != 4 && tn.split_conv3p ? 1 : 0, tn.craft_products, tn.up_commute}; }
+  EncGroupCfg enc_group_cfg() const { return EncGroupCfg{tn.enc_fc2_pairs, tn.qkv_attn_split, tn.enc_ln_pairs, tn.sp_hidden16}; }
+  int last_craft_group = 0, last_enc_group = 0;
   // the recogniser's workspaces, by what they hold (a group's pointers into them: PqWork, engine_parseq.cpp)
   enum PqWs { kWsPatches, kWsX, kWsT384, kWsTbig, kWsAtt, kWsKvmem, kWsKvcache, kWsTgt, kWsD384b, kWsD1536, kWsStepLogits,
               kWsLnPlanes, kWsBigPlanes, kWsAttPlanes, kWsDecPlanesA, kWsDecPlanesB, kWsDecPlanes1536, kWsDecPlanesSa, kWsCount };

@@ -235,8 +235,44 @@ void Engine::upconv_commuted(const char* name, const void* y_lo, int C0, const v
         (double)Mhi * C1 * 2.0 * (np - 1) + (double)Mlo * Cout * 4.0 + (double)Mhi * Cout * 2.0 * (np - 1) + (double)Cout * C1 * 6.0);
 }
 
+// The tensors craft_forward_split below hands its kernels, per page of an H x W canvas (engine.h: launch groups): level = log4 of the rows' divisor (0: full
+// resolution), channels, bytes per value.  Without first_fused the widest is conv1_1's output (64 channels at full resolution: 201 MB per 1024 x 768 page as
+// pairs); with it that tensor is never written and slice1.7 / slice1.10's 128 channels at half resolution lead (100.7 MB).  The upsampled tensors of the
+// uncommuted up-convolutions are listed too: none is wider than its level's skip tensor.
+Widest craft_widest_per_page(int H, int W, const CraftGroupCfg& c) {
+  const size_t bpv = c.craft_products == 4 ? 6 : 4, M0 = (size_t)H * W;
+  Widest w{M0 * 3, "slice1.0"};   // the u8 canvas
+  auto t = [&](const char* layer, int level, size_t C, size_t bytes) { const size_t b = (M0 >> (2 * level)) * C * bytes; if (b > w.bytes) w = Widest{b, layer}; };
+  if (!c.first_fused) t("slice1.0", 0, 64, bpv);
+  t("slice1.3", 1, 64, bpv); t("slice1.7", 1, 128, bpv); t("slice1.10", 1, 128, bpv);
+  t("slice2.14", 2, 256, bpv); t("slice2.17", 2, 256, bpv); t("slice3.20", 3, 256, bpv);
+  t("slice3.24", 3, 512, bpv); t("slice3.27", 3, 512, bpv); t("slice4.30", 4, 512, bpv);
+  t("slice4.34", 4, 512, bpv); t("slice4.37", 4, 512, bpv); t("slice5.1", 4, 1024, bpv); t("slice5.2", 4, 1024, bpv);
+  t("upconv1.0", 4, 512, bpv); t("upconv1.3", 4, 256, bpv);
+  if (c.up_commute) { t("upconv2.0", 4, 256, 4); t("upconv3.0", 3, 128, 4); t("upconv4.0", 2, 64, 4); }         // z: fp32 at the low resolution
+  else { t("upconv2.0.upsample", 3, 256, bpv); t("upconv3.0.upsample", 2, 128, bpv); t("upconv4.0.upsample", 1, 64, bpv); }
+  t("upconv2.0", 3, 256, bpv); t("upconv2.3", 3, 128, bpv); t("upconv3.0", 2, 128, bpv); t("upconv3.3", 2, 64, bpv); t("upconv4.0", 1, 64, bpv);
+  t("upconv4.3", 1, 64, bpv); t("conv_cls.0", 1, 64, bpv); t("conv_cls.2", 1, 64, bpv);                          // (rows of 64 halves per plane when not packed)
+  t("conv_cls.4", 1, 32, 4); t("conv_cls.6", 1, 32, 4); t("conv_cls.8", 1, 2, 4);
+  return w;
+}
+
+int craft_group_pages(int H, int W, int n, int craft_group, const CraftGroupCfg& c) {
+  const size_t per_page = craft_widest_per_page(H, W, c).bytes;
+  int GP = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(craft_group, 1), kOffsetWindow / per_page));
+  if (GP >= 16 && n % 16 == 0) GP = 16;       // even groups: 64 pages = 4 x 16 rather than 21 + 21 + 21 + 1
+  else if (GP >= 8 && n % 8 == 0) GP = 8;     // ... 24 pages = 3 x 8 rather than 16 + 8
+  return GP;
+}
+
 void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, float* d_heat) {
   prof_stage = 0;
+  // before anything is enqueued: a tensor past the window of 32-bit offsets must not reach a kernel (buffer loads would read zeros past 2^31)
+  const Widest widest = craft_widest_per_page(H, W, craft_group_cfg());
+  if ((size_t)B * widest.bytes > kOffsetWindow)
+    throw std::runtime_error(std::string(widest.layer) + ": " + std::to_string(B) + " pages of " + std::to_string(H) + " x " + std::to_string(W) + " put its widest tensor at " +
+                             std::to_string((size_t)B * widest.bytes) + " bytes, past the 2 GiB window of 32-bit buffer offsets (at most " +
+                             std::to_string(kOffsetWindow / widest.bytes) + " pages per launch group in this configuration)");
   craft_taps.clear();   // (records of an earlier pass point into workspaces this one rewrites)
   const size_t M0 = (size_t)B * H * W, M1 = M0 / 4, M2 = M1 / 4, M3 = M2 / 4, M4 = M3 / 4;
   const int H1 = H / 2, W1 = W / 2, H2 = H / 4, W2 = W / 4, H3 = H / 8, W3 = W / 8, H4 = H / 16, W4 = W / 16;
@@ -250,8 +286,10 @@ void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, f
     craft_ws_set[0].clear(); craft_ws_set[1].clear();
     craft_ws_npl = layout;
   }
-  auto pbuf = [&](size_t rows, int C) -> void* { return ws(k++, rows * C * 2 * npl).p; };   // planes
-  auto fbuf = [&](size_t rows, int C) -> void* { return ws(k++, rows * C * 4).p; };   // fp32
+  // (every tensor of this pass is one craft_widest_per_page accounts for: an allocation wider than the figure the group size came from is a bug, not a shape)
+  auto sized = [&](size_t bytes) { if (bytes > (size_t)B * widest.bytes) throw std::logic_error("craft_forward_split: a tensor wider than craft_widest_per_page states"); return bytes; };
+  auto pbuf = [&](size_t rows, int C) -> void* { return ws(k++, sized(rows * C * 2 * npl)).p; };   // planes
+  auto fbuf = [&](size_t rows, int C) -> void* { return ws(k++, sized(rows * C * 4)).p; };   // fp32
   // conv1_1: a launch of its own (conv1_split_kernel: the 64-channel tensor at full resolution goes out and comes back), or - pairs, 8 x 32 patches, the split
   // 3x3 tiles on - evaluated inside conv1_2's kernel on each halo patch: same arithmetic, same bits, the tensor never exists (tuning key first_fused)
   const bool fuse_first = tn.first_fused && npl == 2 && tn.split_conv3p && H % 8 == 0 && W % 32 == 0 && M0 * 3 < ((size_t)1 << 31);
@@ -325,7 +363,7 @@ void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, f
     }
     h4 = fbuf(M1, 32);  sconv("conv_cls.4", h2, 64, nullptr, 0, B, H1, W1, h4, kActRelu, nullptr, nullptr, 0, /*out_planes=*/0, 0, true);   // fp32, 16 real + 16 zero channels
   } else {
-  auto zbuf = [&](size_t rows) -> void* { return ws(k++, rows * 64 * 2 * npl, true).p; };
+  auto zbuf = [&](size_t rows) -> void* { return ws(k++, sized(rows * 64 * 2 * npl), true).p; };
   u4b = zbuf(M1); sconv("upconv4.3", u4a, 64, nullptr, 0, B, H1, W1, u4b, kActRelu, nullptr, nullptr, 0, -1, 64);
   h0 = zbuf(M1);  sconv("conv_cls.0", u4b, 64, nullptr, 0, B, H1, W1, h0, kActRelu, nullptr, nullptr, 0, -1, 64);
   h2 = zbuf(M1);  sconv("conv_cls.2", h0, 64, nullptr, 0, B, H1, W1, h2, kActRelu, nullptr, nullptr, 0, -1, 64);

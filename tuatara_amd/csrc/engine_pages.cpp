@@ -219,16 +219,13 @@ void Engine::detect_enqueue(PageBatch& B) {
   TTR_HIP_CHECK(hipEventRecord(ev[0], stream));
   if (B.mixed) launch_resize_pad_pages(page_table[B.slot & 1].as<PageRow>(), canvas.as<uint8_t>(), H, W, 1, n, stream);
   else launch_resize_pad_u8(P0.data, P0.h, P0.w, P0.stride, canvas.as<uint8_t>(), P0.g.target_h, P0.g.target_w, H, W, 1, stream, n, (size_t)P0.h * P0.w * 3);
-  // CRAFT in groups of <= 16 pages: bounds the activation workspace (~0.5 GB/page) and keeps every tensor
-  // inside the 2 GiB window gemm2's 32-bit buffer offsets address.  Each group's CCL follows its CRAFT, so the host reads
-  // group g's components back (and runs its calipers) while the GPU is busy with group g + 1.
+  // CRAFT in groups of <= craft_group pages: bounds the activation workspace and keeps every tensor inside the 2 GiB window the kernels' 32-bit buffer
+  // offsets address.  Each group's CCL follows its CRAFT, so the host reads group g's components back (and runs its calipers) while the GPU is busy with group g + 1.
+  // f16x4 (planes of f16: four or six bytes per value): the cap is what the widest tensor of the configuration in force allows - with first_fused 128 channels at half
+  // resolution as pairs, 100.7 MB per 1024 x 768 page: 16-page groups, half the launches of 8-page ones (engine.h: craft_group_pages)
   int GP = tn.craft_group;
-  if (prec == kSplit) {   // three f16 planes per value: the widest tensor (64 channels at full resolution) must stay inside the 2 GiB window
-    const size_t per_page = (size_t)H * W * 64 * (tn.craft_products == 4 ? 6 : 4);
-    GP = (int)std::max<size_t>(1, std::min<size_t>(GP, (((size_t)1 << 31) - 1) / per_page));
-    if (GP >= 8 && n % 8 == 0 && tn.craft_group >= 8) GP = 8;   // (even groups: 32 pages = 4 x 8 rather than 10 + 10 + 10 + 2)
-  }
-  B.group = GP;
+  if (prec == kSplit) GP = craft_group_pages(H, W, n, tn.craft_group, craft_group_cfg());
+  B.group = last_craft_group = GP;
   const int groups = (n + GP - 1) / GP;
   // Two detector lanes (tn.craft_lanes, engine.h): odd groups on lane_stream with their own workspaces, half a group behind the even ones, so that a lane's
   // matrix-bound full-resolution layers run beside the other lane's HBM-bound U-Net tail and head (a group alone: 9.7 ms of the one, 2.8 of the other)

@@ -209,16 +209,45 @@ void Engine::parseq_encode(const RecPass& p, PqWork& w) {
   } else gemm(pq.at("cross_kv"), w.t384, M, w.kvmem, 768, kActNone);
 }
 
+// The planes tensors encoder_split below hands its kernels, per crop of 128 rows (engine.h: launch groups).  The MLP hidden is the widest: 1536 values per row as
+// triples (6 bytes: 1820 crops fit the window) or - enc_fc2_pairs, the default - as pairs (4 bytes: 2730 crops).  The unfused qkv path writes qkv as triples,
+// 3 x 384 x 6 bytes per row, wider than a hidden of pairs (2427 crops).  The fp32 residual stream is addressed with 64-bit pointers and does not count.
+Widest EncTensors::widest() const {
+  Widest w{ln, "encoder.norm (LayerNorm planes)"};
+  if (qkv > w.bytes) w = Widest{qkv, "enc.qkv"};
+  if (hidden > w.bytes) w = Widest{hidden, "enc.fc1 + GELU (MLP hidden)"};
+  if (att > w.bytes) w = Widest{att, "enc.attn (attention output)"};
+  return w;
+}
+EncTensors encoder_bytes_per_crop(const EncGroupCfg& c) {
+  const size_t rows = 128, E = 384;
+  const size_t hpl = c.enc_fc2_pairs ? 2 : 3;                    // planes of the hidden, in either layout (sp_hidden16: 16-row pieces of the same bytes)
+  const bool fused_qkv = c.qkv_attn_split && c.enc_ln_pairs;    // qkv + attention as one launch: the qkv tensor is never written
+  EncTensors t;
+  t.ln = rows * E * 2 * 3;                                       // (the final norm writes triples whatever enc_ln_pairs says)
+  t.qkv = fused_qkv ? 0 : rows * 3 * E * 2 * 3;
+  t.hidden = rows * 4 * E * 2 * hpl;
+  t.att = rows * E * 2 * 3;
+  return t;
+}
+int encoder_group_crops(int N, int enc_chunk, const EncGroupCfg& c) {
+  const size_t per_crop = encoder_bytes_per_crop(c).widest().bytes;
+  int CHS = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(N, 1), kOffsetWindow / per_crop));
+  CHS = std::min(CHS, enc_chunk > 0 ? enc_chunk : kEncGroupDefault);
+  if (N > CHS) { const int groups = (N + CHS - 1) / CHS; CHS = (N + groups - 1) / groups; }   // even groups: 2731 crops = 1366 + 1365, not 2730 + 1
+  return CHS;
+}
+
 // split-operand engines: LayerNorm, GEMM epilogues and the attention kernel hand each other planes (split.h); only the residual
-// stream x is fp32.  Crop groups keep the widest planes tensor (the MLP hidden: 1536 x 6 bytes per row) inside the 2 GiB window.
+// stream x is fp32.  Crop groups keep the widest planes tensor of the configuration in force inside the 2 GiB window (above); tn.enc_chunk caps them further
+// (0 = 1820, the groups of before the cap followed enc_fc2_pairs; larger: up to the window; smaller: groups whose planes stay in the Infinity Cache).
 void Engine::encoder_split(int N, PqWork& w) {
   const int M = N * 128, E = 384;
-  int CHS = std::max(1, std::min(N, (int)((((size_t)1 << 31) - 1) / ((size_t)128 * 1536 * 6))));
-  if (tn.enc_chunk > 0) CHS = std::min(CHS, tn.enc_chunk);   // (experiment knob: crop groups whose residual stream and LayerNorm planes stay in the Infinity Cache)
-  if (N > CHS) { const int groups = (N + CHS - 1) / CHS; CHS = (N + groups - 1) / groups; }   // even groups: 2560 crops = 1280 + 1280, not 1820 + 740
+  const EncTensors per_crop = encoder_bytes_per_crop(enc_group_cfg());
+  const int CHS = last_enc_group = encoder_group_crops(N, tn.enc_chunk, enc_group_cfg());
   void* lnp = w.ln_planes = pq_buf(kWsLnPlanes, (size_t)M * E * 6);                    // LayerNorm output planes (whole batch: the memory at the end)
-  void* bigp = pq_buf(kWsBigPlanes, (size_t)std::min(N, CHS) * 128 * 1536 * 6);        // qkv / MLP hidden planes
-  void* attp = pq_buf(kWsAttPlanes, (size_t)std::min(N, CHS) * 128 * E * 6);           // attention output planes
+  void* bigp = pq_buf(kWsBigPlanes, (size_t)std::min(N, CHS) * per_crop.big());        // qkv / MLP hidden planes
+  void* attp = pq_buf(kWsAttPlanes, (size_t)std::min(N, CHS) * per_crop.att);          // attention output planes
   auto lnp_at = [&](int c0) { return (char*)lnp + (size_t)c0 * 128 * E * 6; };
   const int lnpl = tn.enc_ln_pairs ? 2 : 3;        // planes of the LayerNorm outputs that feed qkv / fc1 (pairs: three MFMAs per product there)
   // the planes the encoder's GEMMs hand each other as their loaders' 1-KiB pieces (ConvParams::x_tiled): a wave instruction of the LDS-DMA fetches one

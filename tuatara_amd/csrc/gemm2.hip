@@ -652,6 +652,7 @@ void set_gemm2_split_cfg(int v) { g_split_cfg = v; }
 static int g_split_reuse = 1;   // split mode: 1 = reuse-order K loop (X0 and W0b staged once per k0), 0 = plane-major order with a two-slot X ring
 void set_gemm2_split_reuse(int v) { g_split_reuse = v; }
 
+// (reads shapes and the operands' alignments only and never dereferences a pointer: ttr_dbg_split_layer_check runs it on the host with placeholder addresses)
 const char* gemm2_check(const ConvParams& p) {
   const int Ctot = p.C0 + p.C1;
   const int es_in = p.split == 4 ? 6 : p.split == 3 ? 4 : 2;          // bytes per activation element (three / two f16 planes when split)
@@ -673,6 +674,11 @@ const char* gemm2_check(const ConvParams& p) {
   const size_t lim = (size_t)1 << 31;   // buffer offsets: valid lanes < 2^31, 0x80000000 is the out-of-range marker
   const int K = p.ks * p.ks * Ctot * (p.split ? 3 : 1);
   if ((size_t)p.M * p.C0 * es_in >= lim || (size_t)p.M * p.C1 * es_in >= lim || (size_t)p.Cout * K * 2 >= lim) return "gemm2: tensor too large for 32-bit buffer offsets";
+  if (p.split) {   // (the split epilogues store through 64-bit pointers, but what they write is the next layer's input: a tensor past the window is refused where it would be made)
+    const size_t out_row = (size_t)p.out_ld * es_out * (p.out_planes ? p.out_planes : 1);
+    if ((p.out && (size_t)p.M * out_row >= lim) || (p.out_pool && (size_t)(p.M / 4) * out_row >= lim) || (p.up_z && (size_t)(p.M / 4) * p.up_ld * 4 >= lim))
+      return "gemm2: output too large for 32-bit buffer offsets";
+  }
   if (p.M != p.B * p.H * p.W || p.M <= 0 || p.Cout <= 0) return "gemm2: bad shape";
   if (p.split && !(p.out_scale > 0.f)) return "gemm2: split mode needs out_scale";
   if (p.up_z && (!p.split || p.ks != 1 || p.C1 || (p.H & 1) || (p.W & 1) || p.up_ld % 4 || p.up_ld < p.Cout || ((uintptr_t)p.up_z & 15) || p.out_pool || p.resid))

@@ -265,6 +265,8 @@ __global__ __launch_bounds__(256, NPL == 2 ? 4 : 3) void conv1_split_kernel(cons
 
 void launch_maxpool3x3s1_planes(const void* in, void* out, int B, int H, int W, int C, hipStream_t s, int planes) {
   if (C % 8) throw std::runtime_error("maxpool3x3 (planes): C % 8");
+  // (64-bit pointers here, but the planes written are a 32-bit-offset loader's input: a tensor past that window is refused where it would be made)
+  if ((int64_t)B * H * W * C * 2 * planes >= ((int64_t)1 << 31)) throw std::runtime_error("maxpool3x3 (planes): tensor too large for 32-bit buffer offsets; the caller groups the pages");
   const int64_t total = (int64_t)B * H * W * (C >> 3);
   const dim3 g((unsigned)((total + 255) / 256));
   if (planes == 2) hipLaunchKernelGGL(maxpool3x3s1_planes_kernel<2>, g, dim3(256), 0, s, (const f16*)in, (f16*)out, B, H, W, C);
@@ -328,6 +330,8 @@ void launch_layernorm_planes(const float* in, int in_ld, const float* gamma, con
   if (M <= 0) return;
   if (in_ld % 4 || (((uintptr_t)in | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15)) throw std::runtime_error("layernorm (planes): 16-byte alignment");
   if (tiled && M % 8) throw std::runtime_error("layernorm (planes): the tiled layout wants a multiple of 8 rows");
+  // (64-bit pointers here, but the planes written are a 32-bit-offset loader's input: a tensor past that window is refused where it would be made)
+  if ((int64_t)M * 384 * 2 * planes >= ((int64_t)1 << 31)) throw std::runtime_error("layernorm (planes): tensor too large for 32-bit buffer offsets; the caller groups the crops");
   if (planes == 2) hipLaunchKernelGGL(layernorm_planes_kernel<2>, dim3((M + 3) / 4), dim3(256), 0, s, in, in_ld, gamma, beta, eps, (f16*)out, M, skip, skip_n, tiled, range_ctx().flag, range_ctx().tag);
   else hipLaunchKernelGGL(layernorm_planes_kernel<3>, dim3((M + 3) / 4), dim3(256), 0, s, in, in_ld, gamma, beta, eps, (f16*)out, M, skip, skip_n, tiled, range_ctx().flag, range_ctx().tag);
 }

@@ -61,6 +61,10 @@ SYMBOLS = [
     ("ttr_resize_canvas_batch", _I, [_VP, C.POINTER(_VP), _PI, _PI, _PI, _I, _PU8, C.c_size_t, _PI, _PI, _PF]),
     ("ttr_pack_crops_batch", _I, [_VP, C.POINTER(_VP), _PI, _PI, _PI, _I, _PF, _PI, _I, _I, _I, _PU8, _PF]),
     ("ttr_dbg_canvas_geometry", _I, [_I, _I, _I, _F, _PI, _PI, _PF, _PI, _PI]),
+    ("ttr_dbg_launch_groups", _I, [_I] * 13 + [_PI, _PI, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("ttr_dbg_split_layer_check", _I, [_I] * 10 + [C.c_char_p, C.c_size_t]),
+    ("ttr_dbg_last_groups", _I, [_VP, _PI, _PI]),
+    ("ttr_dbg_last_heat", _I, [_VP, _PF, C.c_size_t]),
     ("ttr_result_count", _I, [_VP]),
     ("ttr_result_text", C.c_char_p, [_VP, _I]),
     ("ttr_result_bbox", _PF, [_VP, _I]),
@@ -371,6 +375,33 @@ def canvas_geometry(h: int, w: int, canvas_size: int = 1024, mag_ratio: float = 
     if load().ttr_dbg_canvas_geometry(int(h), int(w), int(canvas_size), float(mag_ratio), C.byref(H), C.byref(W), C.byref(ratio), C.byref(th), C.byref(tw)) != 0:
         raise EngineError("ttr_dbg_canvas_geometry: h and w must be positive")
     return H.value, W.value, ratio.value, th.value, tw.value
+
+
+OFFSET_WINDOW = (1 << 31) - 1              # most bytes a tensor the f16x4 kernels address with 32-bit buffer offsets may hold
+
+
+def launch_groups(H: int, W: int, n_pages: int, n_crops: int, craft_group: int = 16, first_fused: int = 1, craft_products: int = 3, up_commute: int = 1,
+                  enc_chunk: int = 0, enc_fc2_pairs: int = 1, qkv_attn_split: int = 1, enc_ln_pairs: int = 1, sp_hidden16: int = 0):
+    """The f16x4 engine's launch groups on the host (ttr_dbg_launch_groups, no GPU; DESIGN.md "Launch groups") for a batch of n_pages canvases of H x W and
+    n_crops crops under the tuning values given -> (pages per CRAFT group, crops per encoder group, bytes per page, bytes per crop of the widest tensor)."""
+    gp, ge, bp, bc = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+    rc = load().ttr_dbg_launch_groups(int(H), int(W), int(n_pages), int(n_crops), int(craft_group), int(first_fused), int(craft_products), int(up_commute),
+                                      int(enc_chunk), int(enc_fc2_pairs), int(qkv_attn_split), int(enc_ln_pairs), int(sp_hidden16),
+                                      C.byref(gp), C.byref(ge), C.byref(bp), C.byref(bc))
+    if rc != 0:
+        raise EngineError("ttr_dbg_launch_groups: H and W must be positive multiples of 32, the counts and craft_group at least 1")
+    return gp.value, ge.value, bp.value, bc.value
+
+
+def split_layer_check(kernel: str, B: int, H: int, W: int, C0: int, Cout: int, ks: int = 3, products: int = 3, out_planes: int = 2, pooled: bool = False):
+    """The shape check of an f16x4 layer launcher on the host (ttr_dbg_split_layer_check, no GPU, nothing is launched): kernel "conv3p", "gemm2" or "conv3p_first" (conv1_1 fused in front) ->
+    None when the launcher takes the layer, else its reason."""
+    text = C.create_string_buffer(256)
+    rc = load().ttr_dbg_split_layer_check({"conv3p": 0, "gemm2": 1, "conv3p_first": 2}[kernel], int(B), int(H), int(W), int(C0), int(Cout), int(ks), int(products), int(out_planes),
+                                          int(bool(pooled)), text, 256)
+    if rc < 0:
+        raise EngineError("ttr_dbg_split_layer_check: bad arguments")
+    return text.value.decode() if rc else None
 
 
 def _host_images(images):
@@ -1760,6 +1791,18 @@ class Engine:
         quads = np.zeros((n, 4, 2), np.float32)
         self._check(self.lib.ttr_pack_crops_batch(self.h, ptrs, hs, ws, st, len(keep), _f(rects), _i(page_of), n, int(crop_mode), int(turn), _u8(crops), _f(quads)))
         return crops, quads
+
+    def last_groups(self):
+        """(pages per CRAFT launch group of the last batch, crops per encoder group of the last recogniser pass); 0 = none yet."""
+        gp, ge = C.c_int32(), C.c_int32()
+        self._check(self.lib.ttr_dbg_last_groups(self.h, C.byref(gp), C.byref(ge)))
+        return gp.value, ge.value
+
+    def last_heat(self, n: int, H: int, W: int) -> np.ndarray:
+        """The heat maps the detector left for the last batch of n pages on a canvas of H x W: f32 [n, H/2, W/2, 2] (ttr_dbg_last_heat)."""
+        heat = np.zeros((n, H // 2, W // 2, 2), np.float32)
+        self._check(self.lib.ttr_dbg_last_heat(self.h, _f(heat), heat.size))
+        return heat
 
     def last_stage_ms(self):
         ms = (C.c_float * 4)()
