@@ -35,6 +35,9 @@
 // And a keyword-only pattern_best=False on both calls: True reads every word that has a pattern as the LIKELIEST member of its language under the
 // recogniser's per-position distributions (DESIGN.md "Patterns", best mode) and adds "pattern_logp" to every dict; the mode is set for the call and reset
 // afterwards, also when the call raises.  Without a pattern (the call's, a region's or TUATARA_PATTERN) it has no effect.
+// And a keyword-only tiled=False on image_to_data: tiled=True (overlap 128) or tiled=O (a multiple of 32 in [64, 256]) reads a page larger than the detector
+// canvas at full size, as overlapping tiles whose heat maps are stitched into one page map (DESIGN.md "Tiled pages"); it combines with every keyword but
+// regions (no detector runs there: ValueError).  A value out of range raises RuntimeError before anything runs, as does a page the tile plan refuses.
 // And a keyword-only wide=False on image_to_data: wide=True (a piece is at most 8 times as wide as high) or wide=A (2..64) reads words wider than that in
 // pieces cut at ink gaps and joins the readings (DESIGN.md "Wide words"); every dict gains "pieces", a list of {"text", "conf", "quad"} (one, the item itself,
 // for a word that is not wide).  It turns rectify on.  A value out of range raises RuntimeError before anything runs; wide with orient, chars, alts, lexicon,
@@ -258,7 +261,21 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
-                                      py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved, py::object lexicon_fuzzy, double lexicon_gap) {
+                                      py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved, py::object lexicon_fuzzy, double lexicon_gap,
+                                      py::object tiled_kw) {
+  // tiled=False | True (128) | an overlap: tiled pages for this call (DESIGN.md "Tiled pages"); the engine checks the value, a refusal raises RuntimeError
+  struct TiledScope {
+    explicit TiledScope(int o) { set_tiled(o); }
+    ~TiledScope() { set_tiled(0); }
+  };
+  int tiled_overlap = 0;
+  if (py::isinstance<py::bool_>(tiled_kw)) tiled_overlap = tiled_kw.cast<bool>() ? 128 : 0;
+  else if (py::isinstance<py::int_>(tiled_kw)) tiled_overlap = tiled_kw.cast<int>();
+  else if (!tiled_kw.is_none()) throw py::type_error("tiled must be False, True or an overlap in pixels");
+  if (tiled_overlap != 0 && !regions_kw.is_none()) throw std::invalid_argument("tiled does not combine with regions (no detector runs)");
+  if (tiled_overlap != 0 && (tiled_overlap % 32 || tiled_overlap < 64 || tiled_overlap > 256))
+    throw std::runtime_error("tiled must be False, True or an overlap that is a multiple of 32 in [64, 256]");
+  TiledScope tiled_scope(tiled_overlap);
   const int orient = orient_mode(orient_kw);
   const float wide = wide_arg(wide_kw);
   alts_arg(alts);
@@ -361,7 +378,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
             : orient ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
                      : image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
   }
-  if ((alts || lex || !pattern.empty()) && items.empty()) raise_refused();
+  if ((alts || lex || !pattern.empty() || tiled_overlap) && items.empty()) raise_refused();
   py::list result;
   Keys keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best};
   keys.lex_edits = band >= 0;
@@ -432,7 +449,7 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
         py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("pattern_best") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");

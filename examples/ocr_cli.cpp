@@ -40,11 +40,15 @@
 //   ocr_cli --curved <image.png> <weights_dir> <outputs_dir>   in front of the plain form: straightens the crops of words set on an arc along a spine found in
 // the page, on rectified crops (DESIGN.md "Curved words").  Prints "x1 y1 x2 y2<TAB>conf<TAB>text" per item and, under a curved item, one line
 // "<TAB>~x y x y ..." with the 18 points of its outline.
+//   ocr_cli --tiled [O] ...   in front of any form above that runs the detector, options included: a page larger than the detector canvas is read at full size,
+// as overlapping tiles whose heat maps are stitched into one page map (DESIGN.md "Tiled pages"); O = the overlap in pixels, a multiple of 32 in [64, 256]
+// (default 128, not tuned on documents).  A page of more than 64 tiles or with a side above 8192 fails with the rule's message.
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -92,6 +96,15 @@ static std::vector<RegionSpec> read_regions(const char* path) {
 
 int main(int argc, const char** argv) {
   try {
+    if (argc >= 2 && std::string(argv[1]) == "--tiled") {   // a leading option of every form that runs the detector: the overlap for the calls that follow
+      int overlap = 128, used = 1;
+      if (argc >= 3 && argv[2][0] >= '0' && argv[2][0] <= '9' && std::string(argv[2]).find_first_not_of("0123456789") == std::string::npos && std::strlen(argv[2]) <= 4) {
+        overlap = std::atoi(argv[2]); used = 2;
+      }
+      if (overlap % 32 || overlap < 64 || overlap > 256) throw std::runtime_error("--tiled takes an overlap that is a multiple of 32 in [64, 256] (default 128)");
+      set_tiled(overlap);
+      argv[used] = argv[0]; argv += used; argc -= used;
+    }
     while (argc >= 3 && (std::string(argv[1]) == "--allowlist" || std::string(argv[1]) == "--blocklist" || std::string(argv[1]) == "--pattern")) {   // leading options, any order
       const std::string opt = argv[1];
       if (opt == "--pattern") {   // checked here, on the host, under every class: the engine compiles it again under the set in force
@@ -312,11 +325,12 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli [--tiled [O]] [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);
     std::vector<OutputItem> items = image_to_data(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[2], argv[3]);
+    if (tiled() && !last_call_error().empty()) return 1;              // (--tiled refused: the message is on stderr)
     for (const OutputItem& it : items) printf("%g %g %g %g\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.text.c_str());
     return 0;
   } catch (const std::exception& ex) {

@@ -244,6 +244,15 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
                                            std::string outputs_dir, bool rectify, int orient, bool orient_page, bool lines, bool chars, bool blocks,
                                            std::string allowlist, std::string blocklist, Curved curved);
 
+// Tiled pages (opt-in; DESIGN.md "Tiled pages"): a page larger than the detector canvas (1024 pixels on its longer side) is read at full size, as overlapping
+// tiles whose heat maps are stitched into one page map, instead of being shrunk onto the canvas.  set_tiled(overlap) turns it on for every call of THIS THREAD
+// that follows (a multiple of 32 in [64, 256]; 128 is the default of the other layers, which nobody has tuned on documents), set_tiled(0) off again; with it
+// off, TUATARA_TILED=O (or 1 for 128) in the environment turns it on for every call here.  It is set on the cached engine for the call and reset afterwards.
+// A bad value, a page side above 8192 or more than 64 tiles: the message is printed and the result is empty (last_call_error()).  A page that fits the
+// canvas keeps every bit.
+void set_tiled(int overlap);
+int tiled();
+
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)
 #include <opencv2/core.hpp>

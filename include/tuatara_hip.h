@@ -686,6 +686,34 @@ int ttr_curve_crop(const uint8_t* img, int h, int w, int row_stride, const int64
 int ttr_curve_outline(const float quad[8], int flag, const int64_t* knots, float* outline);
 int ttr_curve_crops(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, int use_table, int32_t* flag, int32_t* hb,
                     int32_t* spine, int64_t* knots, uint8_t* crops);
+/* ---- tiled pages (opt-in; DESIGN.md "Tiled pages") -----------------------------------------------------------------------------------------------
+ * The detector sees a canvas of at most canvas_size pixels on its longer side: a 300 dpi A4 scan is shrunk 3.4 times before it is looked at.  With
+ * ttr_engine_set_tiled(e, overlap) a page keeps its own scale (ratio 1, page canvas c32(h) x c32(w), c32 = rounded up to a multiple of 32); one larger than
+ * canvas_size is cut into overlapping tiles that share one canvas and run as one detector batch, and their heat maps are stitched into one page map
+ * (tile_stitch_kernel, one launch per batch) that everything behind the detector reads as ever.  overlap: 0 = off (the default), else a multiple of 32 in
+ * [64, canvas_size / 4].  The setter fails and changes nothing on another value, on an engine whose canvas_size is no multiple of 32 or whose mag_ratio is
+ * not 1.0, while streamed batches are in flight and with a communicator attached; ttr_engine_attach_comm and ttr_pages_to_data_dev_sharded refuse while it is
+ * on.  A call refuses, naming the figure, a page side above 8192 and a page of more than 16 tiles on an axis or 64 in all.  A page that fits one tile gives
+ * the bits of the engine with tiling off; with tiling off nothing differs from before.  The pages of a batch must share the page canvas, which
+ * ttr_canvas_geometry reports (ttr_images_to_data buckets by it when mixed_batches is set).  Neither the overlap nor the 16-pixel feather has been tuned on
+ * documents.  ttr_result_tiles: the tiles a page's detector ran as, 0 when off.
+ * The rule on the host, no engine (each returns 0, or -1 with the message in ttr_last_error):
+ *   ttr_tile_plan     one page of h x w under (canvas_size, overlap, mag_ratio): *ny x *nx tiles, origins oy / ox and extents ey / ex (16 ints each, image
+ *                     pixels), the tiles' shared canvas *Hc x *Wc, the page map *H2 x *W2.  Any output may be NULL
+ *   ttr_stitch_tiles  tiles f32 [pages][ny nx][Hc / 2][Wc / 2][2] (a page's tiles in (ty, tx) order) -> out f32 [pages][H2][W2][2] under the given origins,
+ *                     which are checked (multiples of 32, ascending, overlaps of at least 32, the last tile ending at the map's end).  Outside the feather bands
+ *                     a copy, inside lerp(a, b, t) = a + t (b - a), x first, then y, every operation rounded on its own
+ * Stage calls (refuse while batches stream): ttr_stitch_heat - the same through tile_stitch_kernel, bit for bit; ttr_craft_heatmap_tiled - a host image under
+ * `overlap`, whatever the engine's setting -> the page map f32 [*H2][*W2][2] (cap = floats heat_out holds; heat_out NULL: sizes only); ttr_tile_canvases - the
+ * tiles' canvases u8 [ny nx][Hc][Wc][3] as the detector gets them (cap = bytes). */
+int ttr_engine_set_tiled(ttr_engine* e, int overlap);
+int ttr_engine_tiled(const ttr_engine* e);
+int ttr_result_tiles(const ttr_result* r);
+int ttr_tile_plan(int h, int w, int canvas_size, int overlap, float mag_ratio, int* ny, int* nx, int* oy, int* ox, int* ey, int* ex, int* Hc, int* Wc, int* H2, int* W2);
+int ttr_stitch_tiles(const float* tiles, int pages, int ny, int nx, const int* oy, const int* ox, int Hc, int Wc, int H2, int W2, float* out);
+int ttr_stitch_heat(ttr_engine* e, const float* tiles, int pages, int ny, int nx, const int* oy, const int* ox, int Hc, int Wc, int H2, int W2, float* out);
+int ttr_craft_heatmap_tiled(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int overlap, float* heat_out, size_t cap, int* H2, int* W2);
+int ttr_tile_canvases(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int overlap, uint8_t* canvases, size_t cap);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

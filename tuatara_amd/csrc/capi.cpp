@@ -201,7 +201,7 @@ int ttr_canvas_geometry(const ttr_engine* e, int h, int w, int* H, int* W, float
   ttr_config c;
   if (e) c = e->e->cfg; else ttr_config_default(&c);
   if (h <= 0 || w <= 0) throw std::runtime_error("Error reading image from file");
-  const CanvasGeom g = canvas_geometry(h, w, c.canvas_size, c.mag_ratio);
+  const CanvasGeom g = e ? e->e->page_geometry(h, w) : canvas_geometry(h, w, c.canvas_size, c.mag_ratio);   // (tiled pages: the page canvas c32(h) x c32(w), ratio 1)
   if (g.target_h <= 0 || g.target_w <= 0) throw std::runtime_error("image too thin to resize");
   if (H) *H = g.h32;
   if (W) *W = g.w32;
@@ -1224,6 +1224,94 @@ int ttr_engine_set_wide(ttr_engine* e, float max_aspect) {
 }
 
 float ttr_engine_wide(const ttr_engine* e) { return e ? e->e->wide : 0.f; }
+
+// ---- tiled pages (DESIGN.md "Tiled pages")
+int ttr_engine_set_tiled(ttr_engine* e, int overlap) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_engine_set_tiled");
+  if (overlap != 0) {
+    try { (void)tile_plan(32, 32, E.cfg.canvas_size, overlap, E.cfg.mag_ratio); }   // the conditions on (canvas_size, overlap, mag_ratio), by name
+    catch (const std::exception& ex) { throw std::runtime_error(std::string("ttr_engine_set_tiled: ") + ex.what()); }
+    if (E.comm) throw std::runtime_error("ttr_engine_set_tiled: tiled pages are read by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
+  }
+  E.tiled = overlap;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_tiled(const ttr_engine* e) { return e ? e->e->tiled : 0; }
+
+int ttr_result_tiles(const ttr_result* r) { return r ? r->r.tiles : 0; }
+
+int ttr_tile_plan(int h, int w, int canvas_size, int overlap, float mag_ratio, int* ny, int* nx, int* oy, int* ox, int* ey, int* ex, int* Hc, int* Wc, int* H2, int* W2) {
+  TTR_GUARD_BEGIN
+  const TilePlan p = tile_plan(h, w, canvas_size, overlap, mag_ratio);
+  if (ny) *ny = p.ny;
+  if (nx) *nx = p.nx;
+  for (int k = 0; k < kTileMaxAxis; ++k) {
+    if (oy) oy[k] = k < p.ny ? p.oy[k] : 0;
+    if (ey) ey[k] = k < p.ny ? p.ey[k] : 0;
+    if (ox) ox[k] = k < p.nx ? p.ox[k] : 0;
+    if (ex) ex[k] = k < p.nx ? p.ex[k] : 0;
+  }
+  if (Hc) *Hc = p.Hc;
+  if (Wc) *Wc = p.Wc;
+  if (H2) *H2 = p.H2;
+  if (W2) *W2 = p.W2;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_stitch_tiles(const float* tiles, int pages, int ny, int nx, const int* oy, const int* ox, int Hc, int Wc, int H2, int W2, float* out) {
+  TTR_GUARD_BEGIN
+  if (!tiles || !out) throw std::runtime_error("null argument");
+  if (pages < 1) throw std::runtime_error("ttr_stitch_tiles: pages must be positive");
+  stitch_tiles(tiles, pages, tile_plan_from_origins(ny, nx, oy, ox, Hc, Wc, H2, W2), out);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_stitch_heat(ttr_engine* e, const float* tiles, int pages, int ny, int nx, const int* oy, const int* ox, int Hc, int Wc, int H2, int W2, float* out) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_stitch_heat");
+  E.stitch_heat(tiles, pages, tile_plan_from_origins(ny, nx, oy, ox, Hc, Wc, H2, W2), out);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_craft_heatmap_tiled(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int overlap, float* heat_out, size_t cap, int* H2, int* W2) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_craft_heatmap_tiled");
+  if (!heat_out) {   // sizes only
+    const TilePlan p = tile_plan(h, w, E.cfg.canvas_size, overlap, E.cfg.mag_ratio);
+    if (H2) *H2 = p.H2;
+    if (W2) *W2 = p.W2;
+    return 0;
+  }
+  E.craft_heatmap_tiled(img, h, w, row_stride, overlap, heat_out, cap, H2, W2, nullptr, 0);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_tile_canvases(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int overlap, uint8_t* canvases, size_t cap) {
+  TTR_GUARD_BEGIN
+  if (!e || !canvases) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_tile_canvases");
+  E.craft_heatmap_tiled(img, h, w, row_stride, overlap, nullptr, 0, nullptr, nullptr, canvases, cap);
+  return 0;
+  TTR_GUARD_END(-1)
+}
 
 const int32_t* ttr_result_piece_first(const ttr_result* r) { return r && !r->r.piece_first.empty() ? r->r.piece_first.data() : nullptr; }
 

@@ -339,6 +339,7 @@ struct Result {
   std::vector<int32_t> block_order, block_first; // the lines in block reading order; [n_blocks + 1] the blocks' offsets into `block_order`
   std::vector<float> block_bbox;                 // 4 per block: min / max of the member lines' bbox
   int n_blocks = 0, block_mode = 0;              // block_mode 1: ordered by the precedence relation; 0: more than 512 blocks, by key alone
+  int tiles = 0;                                 // tiled pages (ttr_engine_set_tiled; DESIGN.md "Tiled pages"): the tiles the page's detector ran as, 0 when off
   std::string block_text(int b) const;           // the block's lines joined by '\n'
   std::string page_text_blocks() const;          // the blocks in reading order, joined by "\n\n"
 };
@@ -458,6 +459,18 @@ struct Engine {
   int lex_band = -1; float lex_gap = 0.f;         // fuzzy alignment (ttr_engine_set_lexicon_fuzzy): the band 0..3 (-1 = off: the rigid scorer) and the gap's log-probability
   float wide = 0.f;                               // wide words: the largest aspect a piece may have, 0 = off or 2..64 (ttr_engine_set_wide; DESIGN.md "Wide words")
   bool curved = false;                            // curved words: straighten the crops of words set on an arc (ttr_engine_set_curved; DESIGN.md "Curved words")
+  // tiled pages (ttr_engine_set_tiled; DESIGN.md "Tiled pages"): the tiles' overlap in pixels, 0 = off.  On, a page keeps its own scale (ratio 1, page canvas
+  // c32(h) x c32(w)); one larger than the detector canvas goes through CRAFT as overlapping tiles whose maps tile_stitch_kernel joins into `heat`
+  int tiled = 0;
+  DevBuf tile_heat;                               // ... the tile canvases' maps [n T][Hc / 2][Wc / 2][2] (allocated by the first tiled batch)
+  DevBuf tile_table[2];                           // ... the tiles as rows of a second page table, per slot (the packers go on reading page_table: the real pages)
+  PinnedBuf h_tile_table[2];
+  // the canvas and ratio this engine gives an h x w page: canvas_geometry, or - tiled - the page's own size rounded up to 32 (throws tile_plan's refusals)
+  CanvasGeom page_geometry(int h, int w) const {
+    if (!tiled) return canvas_geometry(h, w, cfg.canvas_size, cfg.mag_ratio);
+    const TilePlan p = tile_plan(h, w, cfg.canvas_size, tiled, cfg.mag_ratio);
+    return CanvasGeom{h, w, p.hp, p.wp, 1.f};
+  }
   ClassMask charset{};                            // classes the recogniser may not choose (ttr_engine_set_charset; DESIGN.md "Character sets"); zero = no set
   // the engine's pattern (ttr_engine_set_pattern; DESIGN.md "Patterns"): empty = none.  `pattern` is pattern_src compiled under `charset`; its table lives in
   // pattern_dev (delta | mind, uploaded once by set_engine_pattern: nothing travels per call)
@@ -853,7 +866,9 @@ struct Engine {
     // curved words (plan_curved; DESIGN.md "Curved words"): with `curved`, one entry per crop - its frame, page and row
     bool curved = false;
     std::vector<CurveIn> curve;
-    int det_groups = -1;               // CRAFT groups enqueued for it (group_ev[det_groups]: behind the copy of its detector range word)
+    int tiles = 0;                     // tiled pages: tiles per page (0 = the engine's tiling was off when the detector was enqueued), and their plan
+    TilePlan plan{};
+    int det_groups = -1;               // CCL groups enqueued for it (group_ev[det_groups]: behind the copy of its detector range word)
     bool live = false, enqueued = false;
     std::vector<int32_t> all_counts;   // with a communicator: crops per page of every rank [world][n]
     int cap = 0;                       // ... and the largest rank total (rows of the gathered payload per rank)
@@ -875,6 +890,14 @@ struct Engine {
   PageBatch q1, q2;        // streamed batches: q1 = boxes known (recogniser enqueued or not), q2 = older, recogniser enqueued, results not yet returned
 
   void detect_enqueue(PageBatch& B);
+  // tiled pages: the tiles of every page of B (B.plan's windows, each page's own extents) as rows of the slot's tile table, one copy on `stream`
+  void upload_tile_table(const PageBatch& B, int sl);
+  // the stage forms: ttr_stitch_heat - host tile maps -> tile_heat, tile_stitch_kernel once, the page maps back; ttr_craft_heatmap_tiled - a host image under
+  // overlap O (whatever the engine's setting): its tiles' canvases, CRAFT in launch groups, the stitch -> the page map [H2][W2][2] (cap: floats `out` holds)
+  void stitch_heat(const float* tiles, int pages, const TilePlan& plan, float* out);
+  void craft_heatmap_tiled(const uint8_t* img, int h, int w, int row_stride, int overlap, float* out, size_t cap, int* H2, int* W2, uint8_t* canvases_out, size_t canvases_cap);
+  // CRAFT over nc canvases of H x W in launch groups (no CCL), on `stream`: the tiled path's detector; returns the group size
+  int craft_groups_plain(const uint8_t* d_canvas, int nc, int H, int W, float* d_heat);
   // Mixed-size batches: the device page table of a batch (page_table.h), one per pipeline slot - the resize of batch j reads its table on the main stream while
   // the packers of batch j - 1 read theirs on the recogniser's.  upload_page_table writes the rows into the slot's pinned buffer and copies them once, on
   // `stream`, behind table_ev[sl] (recorded behind the last packer that read the slot's previous table; a no-op before the first).

@@ -177,7 +177,7 @@ void Engine::check_pages(std::vector<Page>& pages) const {
   for (size_t i = 0; i < pages.size(); ++i) {
     Page& P = pages[i];
     if (!P.data || P.h <= 0 || P.w <= 0 || P.stride < P.w * 3) throw std::runtime_error("Error reading image from file");  // image.empty(), tuatara.cpp:344
-    P.g = canvas_geometry(P.h, P.w, cfg.canvas_size, cfg.mag_ratio);
+    P.g = page_geometry(P.h, P.w);
     if (P.g.target_h <= 0 || P.g.target_w <= 0) throw std::runtime_error("image too thin to resize");
     if (P.g.h32 != pages[0].g.h32 || P.g.w32 != pages[0].g.w32)
       throw std::runtime_error("mixed-size batch: page " + std::to_string(i) + " (" + std::to_string(P.h) + " x " + std::to_string(P.w) + ") has canvas " + std::to_string(P.g.h32) + " x " +
@@ -199,11 +199,29 @@ void Engine::upload_page_table(const std::vector<Page>& pages, int sl) {
   TTR_HIP_CHECK(hipMemcpyAsync(page_table[sl].p, rows, bytes, hipMemcpyHostToDevice, stream));
 }
 
+void Engine::upload_tile_table(const PageBatch& B, int sl) {
+  const TilePlan& P = B.plan;
+  const int T = P.tiles();
+  const size_t bytes = (size_t)B.n * T * sizeof(PageRow);
+  h_tile_table[sl].ensure(bytes); tile_table[sl].ensure(bytes);
+  PageRow* rows = h_tile_table[sl].as<PageRow>();
+  for (int i = 0; i < B.n; ++i) {
+    const Page& Pg = B.pages[(size_t)i];
+    for (int ty = 0; ty < P.ny; ++ty)
+      for (int tx = 0; tx < P.nx; ++tx) {
+        const int eh = std::min(P.Hc, Pg.h - P.oy[ty]), ew = std::min(P.Wc, Pg.w - P.ox[tx]);   // the page's own extents (pages of a batch share the canvas, not the size)
+        if (eh <= 0 || ew <= 0) throw std::logic_error("tiled pages: an empty tile");
+        rows[(size_t)i * T + ty * P.nx + tx] = PageRow{Pg.data + (size_t)P.oy[ty] * Pg.stride + (size_t)P.ox[tx] * 3, eh, ew, Pg.stride, 0, make_resize_geom(eh, ew, eh, ew)};
+      }
+  }
+  TTR_HIP_CHECK(hipMemcpyAsync(tile_table[sl].p, rows, bytes, hipMemcpyHostToDevice, stream));   // (read by this batch's resize alone, on this stream)
+}
+
 void Engine::detect_enqueue(PageBatch& B) {
   range_use(kRangeDet0 + (B.slot & 1));   // the detector's kernels of this batch watch its own word (engine.h)
   if (!B.mixed) {                         // a uniform batch: every page is its entry point's scalars
     if (B.h <= 0 || B.w <= 0) throw std::runtime_error("Error reading image from file");  // image.empty(), tuatara.cpp:344
-    const CanvasGeom g = canvas_geometry(B.h, B.w, cfg.canvas_size, cfg.mag_ratio);
+    const CanvasGeom g = page_geometry(B.h, B.w);
     if (g.target_h <= 0 || g.target_w <= 0) throw std::runtime_error("image too thin to resize");
     B.pages.resize((size_t)B.n);
     for (int i = 0; i < B.n; ++i) B.pages[i] = Page{B.d_pages + (size_t)i * B.h * B.w * 3, B.h, B.w, B.w * 3, g};
@@ -213,24 +231,36 @@ void Engine::detect_enqueue(PageBatch& B) {
   const Page& P0 = B.pages[0];
   B.H = P0.g.h32; B.W = P0.g.w32; B.H2 = B.H / 2; B.W2 = B.W / 2;
   const int n = B.n, H = B.H, W = B.W, H2 = B.H2, W2 = B.W2;
-  canvas.ensure((size_t)n * H * W * 3);
+  // Tiled pages (DESIGN.md "Tiled pages"): the pages above keep their own scale; one larger than the detector canvas goes through the detector as T overlapping
+  // tiles on a canvas of Hc x Wc (nc = n T canvases into tile_heat), and tile_stitch_kernel joins their maps into `heat` behind the last group.  A page of one
+  // tile IS its canvas: it takes the path below as it stands.  Off: nc, Hc, Wc are n, H, W and nothing here differs.
+  B.tiles = 0;
+  if (tiled) { B.plan = tile_plan(P0.h, P0.w, cfg.canvas_size, tiled, cfg.mag_ratio); B.tiles = B.plan.tiles(); }
+  const bool til = B.tiles > 1;
+  const int T = til ? B.tiles : 1, nc = n * T, Hc = til ? B.plan.Hc : H, Wc = til ? B.plan.Wc : W, Hc2 = Hc / 2, Wc2 = Wc / 2;
+  canvas.ensure((size_t)nc * Hc * Wc * 3);
   heat.ensure((size_t)n * H2 * W2 * 2 * 4);
+  if (til) tile_heat.ensure((size_t)nc * Hc2 * Wc2 * 2 * 4);
+  float* const craft_out = til ? tile_heat.as<float>() : heat.as<float>();
   if (B.mixed) upload_page_table(B.pages, B.slot & 1);   // ahead of the resize; the batch's packers read it later (engine.h)
+  if (til) upload_tile_table(B, B.slot & 1);
   TTR_HIP_CHECK(hipEventRecord(ev[0], stream));
-  if (B.mixed) launch_resize_pad_pages(page_table[B.slot & 1].as<PageRow>(), canvas.as<uint8_t>(), H, W, 1, n, stream);
+  if (til) launch_resize_pad_pages(tile_table[B.slot & 1].as<PageRow>(), canvas.as<uint8_t>(), Hc, Wc, 1, nc, stream);   // the identity path: a tile's canvas is its window's bytes
+  else if (B.mixed) launch_resize_pad_pages(page_table[B.slot & 1].as<PageRow>(), canvas.as<uint8_t>(), H, W, 1, n, stream);
   else launch_resize_pad_u8(P0.data, P0.h, P0.w, P0.stride, canvas.as<uint8_t>(), P0.g.target_h, P0.g.target_w, H, W, 1, stream, n, (size_t)P0.h * P0.w * 3);
   // CRAFT in groups of <= craft_group pages: bounds the activation workspace and keeps every tensor inside the 2 GiB window the kernels' 32-bit buffer
   // offsets address.  Each group's CCL follows its CRAFT, so the host reads group g's components back (and runs its calipers) while the GPU is busy with group g + 1.
   // f16x4 (planes of f16: four or six bytes per value): the cap is what the widest tensor of the configuration in force allows - with first_fused 128 channels at half
   // resolution as pairs, 100.7 MB per 1024 x 768 page: 16-page groups, half the launches of 8-page ones (engine.h: craft_group_pages)
   int GP = tn.craft_group;
-  if (prec == kSplit) GP = craft_group_pages(H, W, n, tn.craft_group, craft_group_cfg());
-  B.group = last_craft_group = GP;
-  const int groups = (n + GP - 1) / GP;
+  if (prec == kSplit) GP = craft_group_pages(Hc, Wc, nc, tn.craft_group, craft_group_cfg());
+  last_craft_group = GP;
+  B.group = til ? n : GP;                 // (tiled: the pages' CCL is one group behind the stitch)
+  const int groups = (nc + GP - 1) / GP;
   // Two detector lanes (tn.craft_lanes, engine.h): odd groups on lane_stream with their own workspaces, half a group behind the even ones, so that a lane's
   // matrix-bound full-resolution layers run beside the other lane's HBM-bound U-Net tail and head (a group alone: 9.7 ms of the one, 2.8 of the other)
   const bool two = prec == kSplit && tn.craft_lanes == 2 && groups >= 2;
-  ccl.split_pool = two;
+  ccl.split_pool = two && !til;
   if (two) {
     TTR_HIP_CHECK(hipEventRecord(resize_done, stream));
     TTR_HIP_CHECK(hipStreamWaitEvent(lane_stream, resize_done, 0));     // (the canvas; and everything the main stream held before it: the previous batch's detector)
@@ -243,27 +273,87 @@ void Engine::detect_enqueue(PageBatch& B) {
     ~LaneGuard() { if (on) { std::swap(E.stream, E.lane_stream); E.ws_sel = 0; } E.lane_go_pending = false; }
   } lane_guard{*this};
   for (int gi = 0; gi < groups; ++gi) {
-    const int p0 = gi * GP, cnt = std::min(GP, n - p0);
+    const int p0 = gi * GP, cnt = std::min(GP, nc - p0);
     const int lane = two ? (gi & 1) : 0;
     if (lane) {
       lane_guard.enter();
       if (gi == 1) TTR_HIP_CHECK(hipStreamWaitEvent(stream, lane_go, 0));   // (recorded inside group 0's forward pass, behind slice3.20)
     }
-    craft_forward(canvas.as<uint8_t>() + (size_t)p0 * H * W * 3, cnt, H, W, heat.as<float>() + (size_t)p0 * H2 * W2 * 2);
-    if (gi == groups - 1) TTR_HIP_CHECK(hipEventRecord(ev[1], stream));
-    ccl_launch(heat.as<float>() + (size_t)p0 * H2 * W2 * 2, p0, cnt, n, gi, H2, W2, lane);
+    craft_forward(canvas.as<uint8_t>() + (size_t)p0 * Hc * Wc * 3, cnt, Hc, Wc, craft_out + (size_t)p0 * Hc2 * Wc2 * 2);
+    if (!til) {
+      if (gi == groups - 1) TTR_HIP_CHECK(hipEventRecord(ev[1], stream));
+      ccl_launch(heat.as<float>() + (size_t)p0 * H2 * W2 * 2, p0, cnt, n, gi, H2, W2, lane);
+    }
     if (lane) {
       if (gi + 2 >= groups) TTR_HIP_CHECK(hipEventRecord(lane_done, stream));   // this lane's last group
       lane_guard.leave();
     }
   }
   if (two) TTR_HIP_CHECK(hipStreamWaitEvent(stream, lane_done, 0));       // the batch's detector is complete when the main stream gets here
+  int ccl_groups = groups;
+  if (til) {                                                              // every tile map is written (both lanes are through): the page maps, then the pages' CCL
+    prof_break();
+    launch_tile_stitch(tile_heat.as<float>(), heat.as<float>(), B.plan, n, stream);
+    TTR_HIP_CHECK(hipEventRecord(ev[1], stream));
+    ccl_launch(heat.as<float>(), 0, n, n, 0, H2, W2, 0);
+    ccl_groups = 1;
+  }
   if (cfg.chars) keep_batch_map(B);                                       // character boxes: the next batch's detector overwrites tnorm before this batch's recogniser runs
   range_fetch(kRangeDet0 + (B.slot & 1));
-  while ((int)group_ev.size() <= groups) { hipEvent_t e; TTR_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); group_ev.push_back(e); }
-  TTR_HIP_CHECK(hipEventRecord(group_ev[groups], stream));                // (behind the word's copy: detect_collect_local waits for it)
-  B.det_groups = groups;
+  while ((int)group_ev.size() <= ccl_groups) { hipEvent_t e; TTR_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); group_ev.push_back(e); }
+  TTR_HIP_CHECK(hipEventRecord(group_ev[ccl_groups], stream));                // (behind the word's copy: detect_collect_local waits for it)
+  B.det_groups = ccl_groups;
   TTR_HIP_CHECK(hipEventRecord(ev[2], stream));
+}
+
+int Engine::craft_groups_plain(const uint8_t* d_canvas, int nc, int H, int W, float* d_heat) {
+  int GP = tn.craft_group;
+  if (prec == kSplit) GP = craft_group_pages(H, W, nc, tn.craft_group, craft_group_cfg());
+  for (int p0 = 0; p0 < nc; p0 += GP)
+    craft_forward(d_canvas + (size_t)p0 * H * W * 3, std::min(GP, nc - p0), H, W, d_heat + (size_t)p0 * (H / 2) * (W / 2) * 2);
+  return GP;
+}
+
+void Engine::stitch_heat(const float* tiles, int pages, const TilePlan& plan, float* out) {
+  if (!tiles || !out) throw std::runtime_error("ttr_stitch_heat: null argument");
+  if (pages < 1 || pages > 256) throw std::runtime_error("ttr_stitch_heat: pages must lie in 1..256, got " + std::to_string(pages));
+  const size_t in_bytes = (size_t)pages * plan.tiles() * (plan.Hc / 2) * (plan.Wc / 2) * 8, out_bytes = (size_t)pages * plan.H2 * plan.W2 * 8;
+  tile_heat.ensure(in_bytes); heat.ensure(out_bytes);
+  TTR_HIP_CHECK(hipMemcpyAsync(tile_heat.p, tiles, in_bytes, hipMemcpyHostToDevice, stream));
+  launch_tile_stitch(tile_heat.as<float>(), heat.as<float>(), plan, pages, stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(out, heat.p, out_bytes, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+void Engine::craft_heatmap_tiled(const uint8_t* img, int h, int w, int row_stride, int overlap, float* out, size_t cap, int* H2, int* W2, uint8_t* canvases_out,
+                                 size_t canvases_cap) {
+  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("Error reading image from file");
+  PageBatch B;
+  B.n = 1;
+  B.plan = tile_plan(h, w, cfg.canvas_size, overlap, cfg.mag_ratio);   // (every refusal before anything is enqueued)
+  const TilePlan& P = B.plan;
+  const int T = P.tiles();
+  const size_t canvas_bytes = (size_t)T * P.Hc * P.Wc * 3, map_floats = (size_t)P.H2 * P.W2 * 2;
+  if (H2) *H2 = P.H2;
+  if (W2) *W2 = P.W2;
+  if (out && cap < map_floats) throw std::runtime_error("tiled heat map: the buffer holds " + std::to_string(cap) + " floats, the page map has " + std::to_string(map_floats));
+  if (canvases_out && canvases_cap < canvas_bytes) throw std::runtime_error("tile canvases: the buffer holds " + std::to_string(canvases_cap) + " bytes, the tiles have " + std::to_string(canvas_bytes));
+  staging_img.ensure((size_t)h * w * 3);
+  TTR_HIP_CHECK(hipMemcpy2DAsync(staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  B.pages.assign(1, Page{staging_img.as<uint8_t>(), h, w, w * 3, CanvasGeom{h, w, P.hp, P.wp, 1.f}});
+  canvas.ensure(canvas_bytes);
+  upload_tile_table(B, 0);
+  launch_resize_pad_pages(tile_table[0].as<PageRow>(), canvas.as<uint8_t>(), P.Hc, P.Wc, 1, T, stream);
+  if (canvases_out) TTR_HIP_CHECK(hipMemcpyAsync(canvases_out, canvas.p, canvas_bytes, hipMemcpyDeviceToHost, stream));
+  if (out) {
+    tile_heat.ensure((size_t)T * (P.Hc / 2) * (P.Wc / 2) * 8); heat.ensure(map_floats * 4);
+    craft_groups_plain(canvas.as<uint8_t>(), T, P.Hc, P.Wc, tile_heat.as<float>());
+    launch_tile_stitch(tile_heat.as<float>(), heat.as<float>(), P, 1, stream);
+    TTR_HIP_CHECK(hipMemcpyAsync(out, heat.p, map_floats * 4, hipMemcpyDeviceToHost, stream));
+    range_fetch(kRangeStage);
+  }
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  if (out) range_verify(kRangeStage, "ttr_craft_heatmap_tiled");
 }
 
 void Engine::detect_collect(PageBatch& B, std::exception_ptr pre) {
@@ -845,6 +935,7 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   const float* pat_logp_block = B.pat_best && N > 0 ? h_pat_logp[B.slot].as<float>() : nullptr;  // the side block (pattern.hip, best mode)
   const void* curve_block = !B.curve.empty() && N > 0 ? h_curve[B.slot].p : nullptr;           // the side block (curve.hip)
   decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block, wide_block, pat_logp_block, curve_block);
+  for (Result& r : results) r.tiles = B.tiles;                                                  // tiled pages: the tiles each page's detector ran as (0: off)
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
@@ -1287,6 +1378,7 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
 void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results) {
   if (wide != 0.f) throw std::runtime_error("latency mode does not support wide words: ttr_engine_set_wide(e, 0) first");
   if (curved) throw std::runtime_error("latency mode does not support curved words: ttr_engine_set_curved(e, 0) first");
+  if (tiled) throw std::runtime_error("latency mode does not support tiled pages: ttr_engine_set_tiled(e, 0) first");
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");
   if (cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("latency mode does not support word orientation: create the engine with orient = TTR_ORIENT_OFF");
   if (cfg.blocks) throw std::runtime_error("latency mode does not support text blocks: create the engine with blocks = 0");
@@ -1424,6 +1516,13 @@ void Engine::run_images(const std::vector<HostImage>& imgs, std::vector<Result>&
       std::cerr << "Error reading image from file";
       bad[i] = 1; failed.push_back(i);
       if (first_error.empty()) first_error = "Error reading image from file (image " + std::to_string(i) + ")";
+    } else if (tiled) {   // tiled pages: a page the tile plan refuses (a side above 8192, too many tiles) fails alone, with the plan's message
+      try { (void)page_geometry(im.h, im.w); }
+      catch (const std::exception& ex) {
+        std::cerr << "tuatara: " << ex.what() << std::endl;
+        bad[i] = 1; failed.push_back(i);
+        if (first_error.empty()) first_error = std::string(ex.what()) + " (image " + std::to_string(i) + ")";
+      }
     } else if (mixed) {   // a page the resize cannot take would fail its whole batch: it fails alone, here, and its canvas-mates go on
       const CanvasGeom g = canvas_geometry(im.h, im.w, cfg.canvas_size, cfg.mag_ratio);
       if (g.target_h <= 0 || g.target_w <= 0) {
@@ -1438,13 +1537,13 @@ void Engine::run_images(const std::vector<HostImage>& imgs, std::vector<Result>&
   std::map<std::pair<int, int>, std::vector<int>> by_size;
   for (int i = 0; i < n; ++i) {
     if (bad[i]) continue;
-    if (mixed) { const CanvasGeom g = canvas_geometry(imgs[i].h, imgs[i].w, cfg.canvas_size, cfg.mag_ratio); by_size[{g.h32, g.w32}].push_back(i); }
+    if (mixed) { const CanvasGeom g = page_geometry(imgs[i].h, imgs[i].w); by_size[{g.h32, g.w32}].push_back(i); }
     else by_size[{imgs[i].h, imgs[i].w}].push_back(i);
   }
   std::vector<std::pair<std::pair<int, int>, std::vector<int>>> buckets(by_size.begin(), by_size.end());
   std::stable_sort(buckets.begin(), buckets.end(), [&](const auto& a, const auto& b) {
     if (mixed) return (size_t)a.first.first * a.first.second > (size_t)b.first.first * b.first.second;
-    const CanvasGeom ga = canvas_geometry(a.first.first, a.first.second, cfg.canvas_size, cfg.mag_ratio), gb = canvas_geometry(b.first.first, b.first.second, cfg.canvas_size, cfg.mag_ratio);
+    const CanvasGeom ga = page_geometry(a.first.first, a.first.second), gb = page_geometry(b.first.first, b.first.second);
     return (size_t)ga.h32 * ga.w32 > (size_t)gb.h32 * gb.w32;
   });
   struct Batch { int h, w; std::vector<int> idx; std::vector<size_t> off; };   // off (mixed): [idx.size() + 1] every image's offset in the staging slot, rounded up to 256 bytes

@@ -1134,4 +1134,105 @@ int lexicon_fuzzy_from_lp(const float* lp, const uint8_t* records, int n, int ba
   return 0;
 }
 
+// ---- tiled pages (geometry.h; DESIGN.md "Tiled pages")
+static inline int c32(int x) { return (x + 31) / 32 * 32; }
+
+static int tile_axis(const char* side, int L, int S, int O, int* o, int* e, int* canvas) {
+  if (L <= S) { o[0] = 0; e[0] = L; *canvas = c32(L); return 1; }
+  const int D = S - O, n = (L - S + D - 1) / D + 1;
+  if (n > kTileMaxAxis)
+    throw std::runtime_error(std::string("tiled pages: at most 16 tiles per axis, the ") + side + " " + std::to_string(L) + " needs " + std::to_string(n));
+  for (int k = 0; k < n - 1; ++k) o[k] = k * D;
+  o[n - 1] = c32(L - S);
+  for (int k = 0; k < n; ++k) e[k] = std::min(S, L - o[k]);
+  *canvas = S;
+  return n;
+}
+
+TilePlan tile_plan(int h, int w, int S, int O, float mag_ratio) {
+  if (S <= 0 || S % 32) throw std::runtime_error("tiled pages: canvas_size must be a positive multiple of 32, got " + std::to_string(S));
+  if (O % 32 || O < 64 || O > S / 4)
+    throw std::runtime_error("tiled pages: the overlap must be a multiple of 32 in [64, canvas_size / 4 = " + std::to_string(S / 4) + "], got " + std::to_string(O));
+  if (!(mag_ratio == 1.0f)) throw std::runtime_error("tiled pages: mag_ratio must be 1.0 (tiles are cut at the page's own scale), got " + std::to_string(mag_ratio));
+  if (h <= 0 || w <= 0) throw std::runtime_error("Error reading image from file");
+  if (h > kTileMaxSide || w > kTileMaxSide)
+    throw std::runtime_error("tiled pages: a page side may be at most 8192 pixels, got " + std::to_string(std::max(h, w)));
+  TilePlan p{};
+  p.ny = tile_axis("height", h, S, O, p.oy, p.ey, &p.Hc);
+  p.nx = tile_axis("width", w, S, O, p.ox, p.ex, &p.Wc);
+  if (p.ny * p.nx > kTileMaxPage)
+    throw std::runtime_error("tiled pages: at most 64 tiles per page, " + std::to_string(h) + " x " + std::to_string(w) + " needs " + std::to_string(p.ny) + " x " +
+                             std::to_string(p.nx) + " = " + std::to_string(p.ny * p.nx));
+  p.hp = c32(h); p.wp = c32(w); p.H2 = p.hp / 2; p.W2 = p.wp / 2;
+  return p;
+}
+
+static void tile_axis_check(const char* axis, const int* o, int n, int canvas, int map_len) {
+  const std::string at = std::string("tile plan, ") + axis + ": ";
+  if (n < 1 || n > kTileMaxAxis) throw std::runtime_error(at + "the number of tiles must lie in 1..16, got " + std::to_string(n));
+  if (canvas <= 0 || canvas % 32 || canvas > kTileMaxSide) throw std::runtime_error(at + "the tile canvas must be a multiple of 32 in 32..8192, got " + std::to_string(canvas));
+  if (map_len <= 0 || map_len > kTileMaxSide / 2) throw std::runtime_error(at + "the page map must have 1..4096 pixels, got " + std::to_string(map_len));
+  if (!o) throw std::runtime_error(at + "null origins");
+  if (o[0] != 0) throw std::runtime_error(at + "the first origin must be 0, got " + std::to_string(o[0]));
+  const int s = canvas / 2;
+  int prev_c = 0;
+  for (int k = 0; k < n; ++k) {
+    if (o[k] < 0 || o[k] % 32 || o[k] > kTileMaxSide) throw std::runtime_error(at + "origin " + std::to_string(k) + " must be a multiple of 32 in 0..8192, got " + std::to_string(o[k]));
+    if (k + 1 == n) break;
+    if (o[k + 1] <= o[k]) throw std::runtime_error(at + "origins must ascend, origin " + std::to_string(k + 1) + " is " + std::to_string(o[k + 1]) + " after " + std::to_string(o[k]));
+    const int lap = o[k] + canvas - o[k + 1];
+    if (lap < 2 * kTileBand) throw std::runtime_error(at + "tiles " + std::to_string(k) + " and " + std::to_string(k + 1) + " overlap by " + std::to_string(lap) + " pixels, a feather band needs 32");
+    const int c = (o[k + 1] / 2 + o[k] / 2 + s) / 2;
+    if (k > 0 && c - kTileBand / 2 < prev_c + kTileBand / 2)
+      throw std::runtime_error(at + "the feather bands of seams " + std::to_string(k - 1) + " and " + std::to_string(k) + " touch (centres " + std::to_string(prev_c) + " and " + std::to_string(c) + ")");
+    prev_c = c;
+  }
+  if (o[n - 1] / 2 + s != map_len)
+    throw std::runtime_error(at + "the last tile must end at the map's end " + std::to_string(map_len) + ", it ends at " + std::to_string(o[n - 1] / 2 + s));
+}
+
+TilePlan tile_plan_from_origins(int ny, int nx, const int* oy, const int* ox, int Hc, int Wc, int H2, int W2) {
+  tile_axis_check("y", oy, ny, Hc, H2);
+  tile_axis_check("x", ox, nx, Wc, W2);
+  if (ny * nx > kTileMaxPage) throw std::runtime_error("tile plan: at most 64 tiles per page, got " + std::to_string(ny * nx));
+  TilePlan p{};
+  p.ny = ny; p.nx = nx; p.Hc = Hc; p.Wc = Wc; p.H2 = H2; p.W2 = W2; p.hp = 2 * H2; p.wp = 2 * W2;
+  for (int k = 0; k < ny; ++k) { p.oy[k] = oy[k]; p.ey[k] = std::min(Hc, p.hp - oy[k]); }
+  for (int k = 0; k < nx; ++k) { p.ox[k] = ox[k]; p.ex[k] = std::min(Wc, p.wp - ox[k]); }
+  return p;
+}
+
+// a + t (b - a) in three roundings: no step may be contracted into an FMA (tile_stitch_kernel uses __fsub_rn / __fmul_rn / __fadd_rn)
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#elif defined(__GNUC__)
+#pragma GCC optimize("fp-contract=off")
+#endif
+static inline float tile_lerp(float a, float b, float t) {
+  const float d = b - a;
+  const float m = t * d;
+  return a + m;
+}
+
+void stitch_tiles(const float* tiles, int pages, const TilePlan& P, float* out) {
+  if (!tiles || !out || pages < 0) throw std::runtime_error("stitch_tiles: null argument");
+  const int sy = P.Hc / 2, sx = P.Wc / 2, T = P.ny * P.nx;
+  const size_t tile_floats = (size_t)sy * sx * 2;
+  for (int pg = 0; pg < pages; ++pg) {
+    const float* tp = tiles + (size_t)pg * T * tile_floats;
+    float* op = out + (size_t)pg * P.H2 * P.W2 * 2;
+    for (int y = 0; y < P.H2; ++y) {
+      const TileSeg gy = tile_seg(P.oy, P.ny, sy, y);
+      for (int x = 0; x < P.W2; ++x) {
+        const TileSeg gx = tile_seg(P.ox, P.nx, sx, x);
+        for (int ch = 0; ch < 2; ++ch) {
+          auto at = [&](int ty, int tx) { return tp[(size_t)(ty * P.nx + tx) * tile_floats + ((size_t)(y - P.oy[ty] / 2) * sx + (x - P.ox[tx] / 2)) * 2 + ch]; };
+          auto row = [&](int ty) { return gx.blend ? tile_lerp(at(ty, gx.k), at(ty, gx.k + 1), gx.t) : at(ty, gx.k); };
+          op[((size_t)y * P.W2 + x) * 2 + ch] = gy.blend ? tile_lerp(row(gy.k), row(gy.k + 1), gy.t) : row(gy.k);
+        }
+      }
+    }
+  }
+}
+
 }  // namespace ttr

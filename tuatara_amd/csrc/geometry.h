@@ -4,6 +4,8 @@
 #include <string>
 #include <vector>
 
+#include "tile_plan.h"
+
 namespace ttr {
 
 // cv::RotatedRect stand-in: centre, size, angle in degrees, all float32.
@@ -150,6 +152,19 @@ bool component_to_rect(const Component& c, int H, int W, RRect* out);
 // resize_aspect_ratio's integer/float bookkeeping (tuatara.cpp:206-234)
 struct CanvasGeom { int target_h, target_w, h32, w32; float ratio; };
 CanvasGeom canvas_geometry(int height, int width, int square_size, float mag_ratio);
+
+// Tiled pages (ttr_engine_set_tiled; DESIGN.md "Tiled pages"): a page larger than the detector canvas is read at full size as overlapping tiles that share one
+// canvas; their heat maps are stitched into one page map.  Integers only.  With S = canvas_size, O = overlap, c32(x) = x rounded up to a multiple of 32, one
+// axis of length L: L <= S gives one tile at 0 on a canvas of c32(L); otherwise D = S - O, n = ceil((L - S) / D) + 1, origins k D for k < n - 1, the last one
+// c32(L - S), canvas S.  tile_plan throws std::runtime_error naming the condition and the figure: S % 32, O % 32 or O outside [64, S / 4], mag_ratio != 1,
+// a side above 8192, more than 16 tiles on an axis or 64 on the page.
+TilePlan tile_plan(int h, int w, int canvas_size, int overlap, float mag_ratio);
+// a plan from given origins (the stage calls): every condition the stitch relies on is checked - at most 16 origins per axis, multiples of 32, ascending, an
+// overlap of at least 32 between neighbours, feather bands that do not touch, the last tile ending at the map's end.  Throws naming the axis and the figure.
+TilePlan tile_plan_from_origins(int ny, int nx, const int* oy, const int* ox, int Hc, int Wc, int H2, int W2);
+// the stitch on the host: tiles f32 [pages][ny nx][Hc / 2][Wc / 2][2] -> out f32 [pages][H2][W2][2].  Outside the bands a copy, bit for bit; inside
+// lerp(a, b, t) = a + t (b - a), x first, then y, every operation rounded on its own (no FMA) - what tile_stitch_kernel computes (tiles.hip)
+void stitch_tiles(const float* tiles, int pages, const TilePlan& plan, float* out);
 
 // Tokenizer (tuatara.cpp:25-117) with the reference's id table quirks.
 struct Tokenizer {

@@ -2,6 +2,7 @@
 #pragma once
 #include <stdexcept>
 #include "common.h"
+#include "tile_plan.h"
 
 namespace ttr {
 
@@ -161,6 +162,9 @@ void launch_resize_pad_u8(const uint8_t* src, int sh, int sw, int sstride, uint8
 // page table (page_table.h); canvas p is byte for byte what launch_resize_pad_u8 gives that page alone
 struct PageRow;
 void launch_resize_pad_pages(const PageRow* table, uint8_t* dst, int H, int W, int swap_rb, int pages, hipStream_t s);
+// tiled pages (tiles.hip): tile maps f32 [pages][ny nx][Hc / 2][Wc / 2][2] -> page maps f32 [pages][H2][W2][2], one launch; the plan (tile_plan.h) must come
+// from tile_plan / tile_plan_from_origins, which check every bound the kernel relies on
+void launch_tile_stitch(const float* tiles, float* out, const TilePlan& plan, int pages, hipStream_t s);
 // canvas u8 [B,H,W,3] -> first-layer im2col matrix T [B*H*W][32] (27 taps*channels, /255, zero padded)
 void launch_im2col_l1(Precision prec, const uint8_t* canvas, void* out, int B, int H, int W, hipStream_t s);
 // bf16 only: conv1_1 + bias + ReLU straight from the u8 canvas (same arithmetic as im2col_l1 + igemm, no [M][32] round trip)

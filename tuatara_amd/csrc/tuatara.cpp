@@ -62,11 +62,12 @@ ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int o
 // argument falls back on TUATARA_ALLOWLIST / TUATARA_BLOCKLIST.  Calls that share an engine take turns, so that none runs under another's set.
 std::map<ttr_engine*, std::unique_ptr<std::mutex>> g_call_mu;
 thread_local std::string g_call_error;   // last_call_error()
+thread_local int g_call_tiled = 0;       // set_tiled(): the overlap of this thread's calls, 0 = off (then TUATARA_TILED decides)
 struct CharsetScope {
   ttr_engine* e;
   std::unique_lock<std::mutex> turn;
   bool set = false, ok = true;
-  bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false, curved_set = false, fuzzy_set = false;
+  bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false, curved_set = false, fuzzy_set = false, tiled_set = false;
   CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
                std::string pattern = std::string(), float wide = 0.f, bool pattern_best = false, bool curved = false, LexFuzzy fuzzy = LexFuzzy{-1, 0.f}) : e(e_) {
     {
@@ -102,6 +103,12 @@ struct CharsetScope {
       if (ttr_engine_set_wide(e, wide) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
       wide_set = true;
     }
+    int tiled = g_call_tiled;
+    if (tiled == 0) if (const char* p = std::getenv("TUATARA_TILED")) tiled = std::string(p) == "1" ? 128 : std::atoi(p);
+    if (tiled != 0) {   // tiled pages (DESIGN.md "Tiled pages"): the overlap for the call, like the set
+      if (ttr_engine_set_tiled(e, tiled) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      tiled_set = true;
+    }
     if (!curved) if (const char* p = std::getenv("TUATARA_CURVED")) curved = std::string(p) == "1";
     if (curved) {   // curved words (DESIGN.md "Curved words"): on for the call, like the set
       if (ttr_engine_set_curved(e, 1) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
@@ -127,6 +134,7 @@ struct CharsetScope {
     if (best_set) ttr_engine_set_pattern_decode(e, TTR_PATTERN_GREEDY);
     if (wide_set) ttr_engine_set_wide(e, 0.f);
     if (curved_set) ttr_engine_set_curved(e, 0);
+    if (tiled_set) ttr_engine_set_tiled(e, 0);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
     if (alts_set) ttr_engine_set_alternatives(e, 0);
     if (fuzzy_set) ttr_engine_set_lexicon_fuzzy(e, -1, 0.f);
@@ -260,6 +268,7 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
   ttr_result* r = nullptr;
   if (ttr_image_to_data(e, image, rows, cols, row_stride ? (int)row_stride : cols * 3, &r) != 0) {
     std::cerr << "tuatara: " << ttr_last_error() << std::endl;
+    if (cs.tiled_set) g_call_error = ttr_last_error();   // tiled pages: a page the tile plan refuses (DESIGN.md "Tiled pages") - the caller can tell it from an empty page
     return {};
   }
   std::vector<Item> out(ttr_result_count(r));
@@ -489,6 +498,9 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
 }
 
 std::string last_call_error() { return g_call_error; }
+
+void set_tiled(int overlap) { g_call_tiled = overlap; }
+int tiled() { return g_call_tiled; }
 
 std::vector<WordReading> nbest(const OutputItemEx& item, int m) {
   std::vector<WordReading> out;

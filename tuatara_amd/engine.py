@@ -270,6 +270,14 @@ SYMBOLS = [
     ("ttr_curve_crop", _I, [_PU8, _I, _I, _I, C.POINTER(C.c_int64), _PU8]),
     ("ttr_curve_outline", _I, [_PF, _I, C.POINTER(C.c_int64), _PF]),
     ("ttr_curve_crops", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _I, _PI, _PI, _PI, C.POINTER(C.c_int64), _PU8]),
+    ("ttr_engine_set_tiled", _I, [_VP, _I]),
+    ("ttr_engine_tiled", _I, [_VP]),
+    ("ttr_result_tiles", _I, [_VP]),
+    ("ttr_tile_plan", _I, [_I, _I, _I, _I, _F] + [_PI] * 10),
+    ("ttr_stitch_tiles", _I, [_PF, _I, _I, _I, _PI, _PI, _I, _I, _I, _I, _PF]),
+    ("ttr_stitch_heat", _I, [_VP, _PF, _I, _I, _I, _PI, _PI, _I, _I, _I, _I, _PF]),
+    ("ttr_craft_heatmap_tiled", _I, [_VP, _PU8, _I, _I, _I, _I, _PF, C.c_size_t, _PI, _PI]),
+    ("ttr_tile_canvases", _I, [_VP, _PU8, _I, _I, _I, _I, _PU8, C.c_size_t]),
 ]
 
 
@@ -792,6 +800,70 @@ def _lib_check(rc):
     return rc
 
 
+TILED_DEFAULT = 128   # tiled=True: the tiles' overlap in pixels (DESIGN.md "Tiled pages": untuned on documents)
+
+
+def _tiled_arg(tiled) -> int:
+    """tiled=None / False / 0 -> 0 (off), True -> TILED_DEFAULT, else the overlap itself (the setter checks it)."""
+    if tiled is None or tiled is False:
+        return 0
+    if tiled is True:
+        return TILED_DEFAULT
+    if isinstance(tiled, (int, np.integer)):
+        return int(tiled)
+    raise EngineError(f"tiled must be True, False or an overlap in pixels, got {tiled!r}")
+
+
+class TilePlan:
+    """ttr_tile_plan's answer for one page: ny x nx tiles at origins oy / ox (image pixels) with extents ey / ex on a shared canvas Hc x Wc; the page map is
+    H2 x W2.  Tile (ty, tx) is the window [oy[ty], oy[ty] + ey[ty]) x [ox[tx], ox[tx] + ex[tx]); a page's tiles travel in (ty, tx) order."""
+    __slots__ = ("ny", "nx", "oy", "ox", "ey", "ex", "Hc", "Wc", "H2", "W2")
+
+    def __init__(self, ny, nx, oy, ox, ey, ex, Hc, Wc, H2, W2):
+        self.ny, self.nx, self.oy, self.ox, self.ey, self.ex, self.Hc, self.Wc, self.H2, self.W2 = ny, nx, oy, ox, ey, ex, Hc, Wc, H2, W2
+
+    @property
+    def tiles(self) -> int:
+        return self.ny * self.nx
+
+    def __repr__(self):
+        return f"TilePlan({self.ny} x {self.nx}, oy={self.oy}, ox={self.ox}, canvas={self.Hc} x {self.Wc}, map={self.H2} x {self.W2})"
+
+
+def tile_plan(h: int, w: int, canvas_size: int = 1024, overlap: int = TILED_DEFAULT, mag_ratio: float = 1.0) -> TilePlan:
+    """The tile plan of an h x w page on the host (ttr_tile_plan, no GPU; DESIGN.md "Tiled pages").  Raises EngineError with the rule's message."""
+    v = [C.c_int() for _ in range(6)]
+    a = [np.zeros(16, np.int32) for _ in range(4)]
+    if load().ttr_tile_plan(int(h), int(w), int(canvas_size), int(overlap), float(mag_ratio), C.byref(v[0]), C.byref(v[1]), _i(a[0]), _i(a[1]), _i(a[2]), _i(a[3]),
+                            C.byref(v[2]), C.byref(v[3]), C.byref(v[4]), C.byref(v[5])) != 0:
+        raise EngineError(load().ttr_last_error().decode("latin1"))
+    ny, nx = v[0].value, v[1].value
+    return TilePlan(ny, nx, a[0][:ny].tolist(), a[1][:nx].tolist(), a[2][:ny].tolist(), a[3][:nx].tolist(), v[2].value, v[3].value, v[4].value, v[5].value)
+
+
+def _stitch_args(tiles, oy, ox, Hc, Wc, H2, W2):
+    oy, ox = np.ascontiguousarray(oy, dtype=np.int32).ravel(), np.ascontiguousarray(ox, dtype=np.int32).ravel()
+    ny, nx = len(oy), len(ox)
+    t = np.ascontiguousarray(tiles, dtype=np.float32)
+    if t.ndim == 4 and t.shape[1:] == (int(Hc) // 2, int(Wc) // 2, 2) and ny * nx and t.shape[0] % (ny * nx) == 0:
+        t = t.reshape(t.shape[0] // (ny * nx), ny * nx, int(Hc) // 2, int(Wc) // 2, 2)
+    elif not (t.ndim == 5 and t.shape[1:] == (ny * nx, int(Hc) // 2, int(Wc) // 2, 2)):
+        raise EngineError(f"stitch: tiles must be f32 [pages * {ny * nx}, {int(Hc) // 2}, {int(Wc) // 2}, 2], got {t.shape}")
+    pages = t.shape[0]
+    if pages < 1 or int(H2) < 1 or int(W2) < 1 or int(H2) > 4096 or int(W2) > 4096:
+        raise EngineError("stitch: bad sizes")
+    return t, pages, ny, nx, oy, ox, np.zeros((pages, int(H2), int(W2), 2), np.float32)
+
+
+def stitch_tiles(tiles, oy, ox, Hc: int, Wc: int, H2: int, W2: int):
+    """ttr_stitch_tiles: the stitch on the host (no GPU; DESIGN.md "Tiled pages").  tiles f32 [pages * ny * nx, Hc / 2, Wc / 2, 2], a page's tiles in (ty, tx)
+    order; oy / ox the origins in image pixels -> f32 [pages, H2, W2, 2].  Raises EngineError for origins the stitch cannot take."""
+    t, pages, ny, nx, oy, ox, out = _stitch_args(tiles, oy, ox, Hc, Wc, H2, W2)
+    if load().ttr_stitch_tiles(_f(t), pages, ny, nx, _i(oy), _i(ox), int(Hc), int(Wc), int(H2), int(W2), _f(out)) != 0:
+        raise EngineError(load().ttr_last_error().decode("latin1"))
+    return out
+
+
 def wide_plan(quad, max_aspect: float):
     """The wide-word plan of one quad (ttr_wide_plan, no GPU; DESIGN.md "Wide words"): 8 floats tl, tr, br, bl -> (n, frame i64 [6]): n pieces (1 = not wide)
     and the frame {X0f, Axf, Bxf, Y0f, Ayf, Byf} in 2^-16 px over 128 n columns x 32 rows."""
@@ -931,13 +1003,14 @@ class PageResult(collections.abc.Sequence):
     `piece_cuts` i32 [n, 17] each item's cuts in columns of its frame; dicts gain "pieces", a list of {"text", "conf", "quad"}; all None when wide is off.
     Curved words (Engine.set_curved(True); DESIGN.md "Curved words"): `curved` i32 [n] (1 = the item's crop was straightened along its spine), `outline` f32
     [n, 18, 2] (the top edge left to right, then the bottom edge right to left) and `spine_knots` i64 [n, 9, 4] the knot tables; dicts gain "curved" and
-    "outline"; all None when curved is off."""
+    "outline"; all None when curved is off.  Tiled pages (Engine.set_tiled(O); DESIGN.md "Tiled pages"): `tiles` = the tiles the page's detector ran as,
+    0 when tiling is off."""
     __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
                  "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad",
                  "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode", "alt_ids", "alt_prob",
                  "lex_idx", "lex_logp", "lex_words", "lex_edits", "lex_band", "pattern_logp", "piece_first", "piece_ids", "piece_prob", "piece_conf", "piece_quad", "piece_cuts",
-                 "curved", "outline", "spine_knots")
+                 "curved", "outline", "spine_knots", "tiles")
 
     def __init__(self, texts, bbox, ids, quad=None, conf=None, prob=None, with_conf=False, orient=None, orient_conf=None, page_orient=0,
                  line=None, word=None, order=None, line_first=None, line_bbox=None,
@@ -945,7 +1018,8 @@ class PageResult(collections.abc.Sequence):
                  block=None, line_block=None, line_pos=None, block_order=None, block_first=None, block_bbox=None, block_mode=0,
                  alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None, pattern_logp=None,
                  piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None,
-                 curved=None, outline=None, spine_knots=None, lex_edits=None, lex_band=-1):
+                 curved=None, outline=None, spine_knots=None, lex_edits=None, lex_band=-1, tiles=0):
+        self.tiles = tiles
         self.lex_edits, self.lex_band = lex_edits, lex_band
         self.curved, self.outline, self.spine_knots = curved, outline, spine_knots
         self.piece_first, self.piece_ids, self.piece_prob = piece_first, piece_ids, piece_prob
@@ -1110,6 +1184,7 @@ class Engine:
         pattern_best = bool(overrides.pop("pattern_best", False))                         # nor this: set_pattern_decode, below
         wide = _wide_arg(overrides.pop("wide", None))                                     # nor this: set_wide, below
         curved = bool(overrides.pop("curved", False))                                     # nor this: set_curved, below
+        tiled = _tiled_arg(overrides.pop("tiled", None))                                  # nor this: set_tiled, below
         self._lex_words = []
         tuning = {k: overrides.pop(k) for k in list(overrides) if not hasattr(cfg, k)}     # not a config field: a tuning key (below)
         for k, v in overrides.items():
@@ -1135,6 +1210,53 @@ class Engine:
             self.set_wide(wide)
         if curved:
             self.set_curved(True)
+        if tiled:
+            self.set_tiled(tiled)
+
+    def set_tiled(self, overlap=True):
+        """Read pages larger than the detector canvas at full size, as overlapping tiles whose heat maps are stitched into one page map (ttr_engine_set_tiled;
+        DESIGN.md "Tiled pages"): 0 / False = off, True = TILED_DEFAULT (128), else the overlap in pixels - a multiple of 32 in [64, canvas_size / 4].  A page
+        that fits one tile keeps every bit.  Raises EngineError, and changes nothing, for another value, on an engine whose mag_ratio is not 1.0, between a
+        stream_push and its flush, and with a communicator attached."""
+        if self.lib.ttr_engine_set_tiled(self.h, _tiled_arg(overlap)) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def tiled(self) -> int:
+        """the overlap in force (0 = off)"""
+        return int(self.lib.ttr_engine_tiled(self.h))
+
+    def tile_plan(self, h: int, w: int, overlap=None) -> TilePlan:
+        """the tile plan this engine gives an h x w page under `overlap` (None: the engine's own, or TILED_DEFAULT when tiling is off)"""
+        return tile_plan(h, w, self.cfg.canvas_size, self.tiled or TILED_DEFAULT if overlap is None else _tiled_arg(overlap), self.cfg.mag_ratio)
+
+    def stitch_heat(self, tiles, oy, ox, Hc: int, Wc: int, H2: int, W2: int):
+        """ttr_stitch_heat: engine.stitch_tiles through tile_stitch_kernel (one launch for all pages), bit for bit the host rule's result."""
+        t, pages, ny, nx, oy, ox, out = _stitch_args(tiles, oy, ox, Hc, Wc, H2, W2)
+        self._check(self.lib.ttr_stitch_heat(self.h, _f(t), pages, ny, nx, _i(oy), _i(ox), int(Hc), int(Wc), int(H2), int(W2), _f(out)))
+        return out
+
+    def craft_heatmap_tiled(self, image, overlap=True):
+        """ttr_craft_heatmap_tiled: a host image u8 [H, W, 3] at full size under `overlap`, whatever the engine's setting -> the page map f32 [H2, W2, 2]."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise RuntimeError("Input array should have 3 dimensions")
+        p = self.tile_plan(image.shape[0], image.shape[1], overlap)
+        out = np.zeros((p.H2, p.W2, 2), np.float32)
+        H2, W2 = C.c_int(), C.c_int()
+        self._check(self.lib.ttr_craft_heatmap_tiled(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _tiled_arg(overlap), _f(out), out.size,
+                                                     C.byref(H2), C.byref(W2)))
+        return out
+
+    def tile_canvases(self, image, overlap=True):
+        """ttr_tile_canvases: the canvases of a host image's tiles as the detector gets them -> u8 [ny * nx, Hc, Wc, 3]."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise RuntimeError("Input array should have 3 dimensions")
+        p = self.tile_plan(image.shape[0], image.shape[1], overlap)
+        out = np.zeros((p.tiles, p.Hc, p.Wc, 3), np.uint8)
+        self._check(self.lib.ttr_tile_canvases(self.h, _u8(image), image.shape[0], image.shape[1], image.shape[1] * 3, _tiled_arg(overlap), _u8(out), out.size))
+        return out
 
     def set_curved(self, on=True):
         """Straighten the crops of words set on an arc along a spine found in the page's pixels (ttr_engine_set_curved; DESIGN.md "Curved words").  Every page
@@ -1547,6 +1669,7 @@ class Engine:
                 if band >= 0:                   # fuzzy alignment: the matches' edits
                     le = self.lib.ttr_result_lex_edits_all(arr[i])
                     lex.update(lex_band=band, lex_edits=np.ctypeslib.as_array(le, (c, M)).copy() if le else np.zeros((0, M), np.int32))
+            lex["tiles"] = int(self.lib.ttr_result_tiles(arr[i]))
             pl = self.lib.ttr_result_pattern_logp(arr[i])
             if pl:                              # patterns in best mode: the page's log-probabilities
                 lex["pattern_logp"] = np.ctypeslib.as_array(pl, (c,)).copy()
