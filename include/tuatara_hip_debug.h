@@ -24,6 +24,19 @@ int ttr_dbg_split_gemm(ttr_engine* e, const float* x, int M, int K, const float*
                        const float* resid, int cfg, float* out);
 int ttr_dbg_conv_pool(ttr_engine* e, const float* in0, int C0, int B, int H, int W, int ks, const float* wgt, const float* bias,
                       int Cout, int act, int pool_relu, float* out_full, float* out_pool);
+/* The row kernels under every f16x4 recogniser layer on their own (f16x4 engines; they refuse while batches stream, add no kernel and change no pass).
+ * ttr_dbg_split_planes: split_planes_kernel over host rows x f32 [M][ld] (C <= ld channels of each, C % 8 == 0, ld % 4 == 0; relu != 0 = ReLU first) ->
+ * raw_out u16 [M][planes * C], the f16 bits of the planes x0 | x1 (| x2) as the kernel wrote them (planes 2 = pair, 3 = exact triple).  The launch watches
+ * a zeroed range word of its own: *tripped (may be NULL) = 1 when a value it split was not below 65504, and the engine's own words never see it.
+ * ttr_dbg_layernorm_planes: layernorm_planes_kernel over x f32 [M][ld] (384 channels, ld >= 384), gamma / beta f32 [384] -> raw_out u16 [M * planes * 384]
+ * exactly as the kernel laid it out: rows [M][planes][384], or with tiled != 0 (M % 8 == 0) the GEMM loader's pieces [M / 8][plane][6 blocks of 64][8 rows][64].
+ * ttr_dbg_ln_linear: the decoder's LayerNorm + linear pair, K = 384: x f32 [M][384], w f32 [N][384], bias f32 [N] (may be NULL) -> out f32 [M][N];
+ * fused = 0: the LayerNorm kernel (triples) followed by the skinny whole-K linear, fused = 1: the skinny linear with the LayerNorm as its prologue. */
+int ttr_dbg_split_planes(ttr_engine* e, const float* x, int M, int C, int ld, int planes, int relu, uint16_t* raw_out, int* tripped);
+int ttr_dbg_layernorm_planes(ttr_engine* e, const float* x, int M, int ld, const float* gamma, const float* beta, float eps, int planes, int tiled,
+                             uint16_t* raw_out);
+int ttr_dbg_ln_linear(ttr_engine* e, const float* x, int M, const float* gamma, const float* beta, float eps, const float* w, const float* bias, int N,
+                      int fused, float* out);
 /* The tap on the split detector (f16x4 engines): one forward pass over B canvases u8 [B][H][W][3] with every launch noting where its tensors live (inputs,
  * out, out_relu, out_pool, the low-resolution z of a commuted up-convolution, the heat map; tensors a fusion never writes have no record).  Returns the number
  * of records (-1 on error); heat_out (may be NULL) f32 [B][H/2][W/2][2].  Nothing is copied during the pass and no kernel is added; a pass without the tap is

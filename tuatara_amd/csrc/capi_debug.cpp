@@ -102,6 +102,93 @@ int ttr_dbg_split_gemm(ttr_engine* e, const float* x, int M, int K, const float*
   TTR_GUARD_END(-1)
 }
 
+// The split kernel on its own (tests): split_planes_kernel over host rows, the f16 planes back as the bits the kernel wrote.  The launch watches a word of its
+// own (tag 1: a tag of 0, the scope's default, would leave a tripped word at 0), so that the engine's sticky words never see a test's out-of-range value.
+int ttr_dbg_split_planes(ttr_engine* e, const float* x, int M, int C, int ld, int planes, int relu, uint16_t* raw_out, int* tripped) {
+  TTR_GUARD_BEGIN
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_dbg_split_planes");
+  if (E.prec != kSplit) throw std::runtime_error("ttr_dbg_split_planes: f16x4 engines only");
+  if (!x || !raw_out || M < 1 || C < 8 || C % 8 || ld < C || ld % 4 || (planes != 2 && planes != 3)) throw std::runtime_error("ttr_dbg_split_planes: M >= 1, C a multiple of 8, ld >= C a multiple of 4, planes 2 or 3");
+  const size_t nin = (size_t)M * ld, nout = (size_t)M * planes * C;
+  DevBuf dx, dout, dflag;
+  dx.ensure(nin * 4); dout.ensure(nout * 2); dflag.ensure(4);
+  TTR_HIP_CHECK(hipMemcpy(dx.p, x, nin * 4, hipMemcpyHostToDevice));
+  TTR_HIP_CHECK(hipMemsetAsync(dflag.p, 0, 4, E.stream));
+  {
+    struct Restore { RangeCtx saved; ~Restore() { range_ctx() = saved; } } restore{range_ctx()};
+    range_ctx().flag = dflag.as<unsigned>(); range_ctx().tag = 1;
+    launch_split_planes(dx.as<float>(), ld, dout.p, M, C, relu, E.stream, planes);
+  }
+  unsigned word = 0;
+  TTR_HIP_CHECK(hipMemcpyAsync(raw_out, dout.p, nout * 2, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(&word, dflag.p, 4, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  if (tripped) *tripped = word != 0;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+// layernorm_planes_kernel on its own (tests): the planes buffer back exactly as the kernel laid it out (row-major [M][planes][384], or gemm_sp.hip's loader pieces)
+int ttr_dbg_layernorm_planes(ttr_engine* e, const float* x, int M, int ld, const float* gamma, const float* beta, float eps, int planes, int tiled, uint16_t* raw_out) {
+  TTR_GUARD_BEGIN
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_dbg_layernorm_planes");
+  if (E.prec != kSplit) throw std::runtime_error("ttr_dbg_layernorm_planes: f16x4 engines only");
+  if (!x || !gamma || !beta || !raw_out || M < 1 || ld < 384 || ld % 4 || (planes != 2 && planes != 3)) throw std::runtime_error("ttr_dbg_layernorm_planes: M >= 1, ld >= 384 a multiple of 4, planes 2 or 3");
+  const size_t nin = (size_t)M * ld, nout = (size_t)M * planes * 384;
+  DevBuf dx, dg, db, dout;
+  dx.ensure(nin * 4); dg.ensure(384 * 4); db.ensure(384 * 4); dout.ensure(nout * 2);
+  TTR_HIP_CHECK(hipMemcpy(dx.p, x, nin * 4, hipMemcpyHostToDevice));
+  TTR_HIP_CHECK(hipMemcpy(dg.p, gamma, 384 * 4, hipMemcpyHostToDevice));
+  TTR_HIP_CHECK(hipMemcpy(db.p, beta, 384 * 4, hipMemcpyHostToDevice));
+  launch_layernorm_planes(dx.as<float>(), ld, dg.as<float>(), db.as<float>(), eps, dout.p, M, E.stream, planes, nullptr, 0, tiled ? 1 : 0);
+  TTR_HIP_CHECK(hipMemcpyAsync(raw_out, dout.p, nout * 2, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+// The decoder's LayerNorm + linear pair (K = 384) on its own (tests), both ways Engine::decoder_tail_split runs it: the LayerNorm kernel (triples) followed by the
+// skinny linear, or the skinny linear with the LayerNorm as its prologue.
+int ttr_dbg_ln_linear(ttr_engine* e, const float* x, int M, const float* gamma, const float* beta, float eps, const float* w, const float* bias, int N, int fused,
+                      float* out) {
+  TTR_GUARD_BEGIN
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_dbg_ln_linear");
+  if (E.prec != kSplit) throw std::runtime_error("ttr_dbg_ln_linear: f16x4 engines only");
+  if (!x || !gamma || !beta || !w || !out || M < 1 || N < 1) throw std::runtime_error("ttr_dbg_ln_linear: M, N >= 1");
+  const int K = 384;
+  DevBuf dx, dg, db, dxp, dout;
+  Linear L;
+  dx.ensure((size_t)M * K * 4); dg.ensure(K * 4); db.ensure(K * 4); dout.ensure((size_t)M * N * 4);
+  TTR_HIP_CHECK(hipMemcpy(dx.p, x, (size_t)M * K * 4, hipMemcpyHostToDevice));
+  TTR_HIP_CHECK(hipMemcpy(dg.p, gamma, K * 4, hipMemcpyHostToDevice));
+  TTR_HIP_CHECK(hipMemcpy(db.p, beta, K * 4, hipMemcpyHostToDevice));
+  E.upload_linear(L, w, N, K, bias, (N + 7) / 8 * 8, K, nullptr, false);   // (the skinny kernel takes any channel count: zero rows pad the planes)
+  if (!L.ws.p) throw std::runtime_error("ttr_dbg_ln_linear: the layer has no weight planes");
+  ConvParams p{};
+  p.C0 = K; p.B = 1; p.H = 1; p.W = M; p.ks = 1; p.dil = 1;
+  p.wgt = L.ws.p; p.bias = bias ? L.b.as<float>() : nullptr; p.split = 4; p.out_scale = L.inv_scale;
+  p.out_f32 = dout.as<float>(); p.out_f32_ld = N; p.Cout = N; p.M = M; p.act = kActNone;
+  if (fused) {
+    p.ln_in = dx.as<float>(); p.ln_ld = K; p.ln_gamma = dg.as<float>(); p.ln_beta = db.as<float>(); p.ln_eps = eps;
+    if (!gemm_skx_ln_eligible(p)) throw std::runtime_error("ttr_dbg_ln_linear: the LayerNorm prologue does not take this shape");
+  } else {
+    dxp.ensure((size_t)M * K * 6);
+    launch_layernorm_planes(dx.as<float>(), K, dg.as<float>(), db.as<float>(), eps, dxp.p, M, E.stream, 3);
+    p.in0 = dxp.p;
+  }
+  launch_gemm_skx(p, E.stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t)M * N * 4, hipMemcpyDeviceToHost, E.stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_dbg_mlp(ttr_engine* e, const float* x, int M, const float* ln_g, const float* ln_b, float eps, const float* w1, const float* b1, const float* w2,
                 const float* b2, const float* nln_g, const float* nln_b, float* x_out, float* nln_out, const float* att, const float* wp, const float* bp) {
   TTR_GUARD_BEGIN

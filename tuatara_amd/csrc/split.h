@@ -176,13 +176,16 @@ __host__ __device__ __forceinline__ constexpr int split_wplane(int q) { return q
 // two passes over the registers, every multiply-add spelled out so that the kernels which share this (layernorm_planes_kernel, gemm_skx.hip's
 // LayerNorm prologue) round identically whatever the compiler would contract on its own.  All 64 lanes must call it (wave reductions).
 __device__ __forceinline__ void ln384_row8(const float (&v)[8], bool act, const float* gamma8, const float* beta8, float eps, float (&y)[8]) {
+  // No contraction beyond the fmaf calls written out (__fmul_rn is a plain product to this compiler): with the default, layernorm_planes_kernel<2> folded the mean's
+  // product into the subtractions, v - mean -> fma(s, -1 / D, v), and <3> and the prologue did not - a constant row came out as beta from one and not from the other.
+#pragma clang fp contract(off)
   constexpr int D = 384;
   float s = 0.f;
 #pragma unroll
   for (int e = 0; e < 8; ++e) s += act ? v[e] : 0.f;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  const float mean = s * (1.0f / D);
+  const float mean = s * (1.0f / D);           // (rounded on its own, see the pragma)
   float q = 0.f;
 #pragma unroll
   for (int e = 0; e < 8; ++e) { const float d = act ? v[e] - mean : 0.f; q = fmaf(d, d, q); }

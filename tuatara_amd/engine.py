@@ -210,6 +210,9 @@ SYMBOLS = [
     ("ttr_set_profiling", _I, [_VP, _I]),
     ("ttr_dbg_conv_pool", _I, [_VP, _PF, _I, _I, _I, _I, _I, _PF, _PF, _I, _I, _I, _PF, _PF]),
     ("ttr_dbg_split_gemm", _I, [_VP, _PF, _I, _I, _PF, _PF, _I, _I, _I, _I, _PF, _I, _PF]),
+    ("ttr_dbg_split_planes", _I, [_VP, _PF, _I, _I, _I, _I, _I, C.POINTER(C.c_uint16), _PI]),
+    ("ttr_dbg_layernorm_planes", _I, [_VP, _PF, _I, _I, _PF, _PF, _F, _I, _I, C.POINTER(C.c_uint16)]),
+    ("ttr_dbg_ln_linear", _I, [_VP, _PF, _I, _PF, _PF, _F, _PF, _PF, _I, _I, _PF]),
     ("ttr_dbg_craft_taps", _I, [_VP, _PU8, _I, _I, _I, _PF]),
     ("ttr_dbg_craft_tap_count", _I, [_VP]),
     ("ttr_dbg_craft_tap_info", _I, [_VP, _I, C.c_char_p, C.c_size_t, _PI]),
@@ -2183,6 +2186,42 @@ class Engine:
         r = np.ascontiguousarray(resid, dtype=np.float32) if resid is not None else None
         self._check(self.lib.ttr_dbg_split_gemm(self.h, _f(x), M, K, _f(w), _f(b) if b is not None else None, N, np_products, act, out_planes,
                                                 _f(r) if r is not None else None, cfg, _f(out)))
+        return out
+
+    def dbg_split_planes(self, x: np.ndarray, C_: int, planes: int = 3, relu: int = 0):
+        """f16x4 engines: split_planes_kernel on host rows x f32 [M, ld] (the first C_ channels of each) -> (the f16 bit planes u16 [M, planes, C_] as the kernel
+        wrote them, whether the launch's own range word tripped) (tests)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        M, ld = x.shape
+        raw = np.zeros((M, int(planes), int(C_)), np.uint16)
+        tripped = C.c_int32(0)
+        self._check(self.lib.ttr_dbg_split_planes(self.h, _f(x), M, int(C_), ld, int(planes), int(relu), raw.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(tripped)))
+        return raw, bool(tripped.value)
+
+    def dbg_layernorm_planes(self, x: np.ndarray, gamma: np.ndarray, beta: np.ndarray, eps: float, planes: int = 3, tiled: int = 0) -> np.ndarray:
+        """f16x4 engines: layernorm_planes_kernel on host rows x f32 [M, ld] (384 channels) -> the raw planes buffer u16 [M * planes * 384] in the kernel's own
+        layout: rows [M][planes][384], or (tiled) [M / 8][plane][6 blocks of 64][8 rows][64] (tests)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        g = np.ascontiguousarray(gamma, dtype=np.float32); b = np.ascontiguousarray(beta, dtype=np.float32)
+        if g.shape != (384,) or b.shape != (384,) or x.ndim != 2:
+            raise ValueError("x [M, ld], gamma [384], beta [384]")
+        M, ld = x.shape
+        raw = np.zeros(M * int(planes) * 384, np.uint16)
+        self._check(self.lib.ttr_dbg_layernorm_planes(self.h, _f(x), M, ld, _f(g), _f(b), float(eps), int(planes), int(tiled), raw.ctypes.data_as(C.POINTER(C.c_uint16))))
+        return raw
+
+    def dbg_ln_linear(self, x: np.ndarray, gamma: np.ndarray, beta: np.ndarray, eps: float, w: np.ndarray, bias: Optional[np.ndarray] = None,
+                      fused: int = 0) -> np.ndarray:
+        """f16x4 engines: the decoder's LayerNorm + linear pair, x f32 [M, 384], w f32 [N, 384] -> f32 [M, N]; fused = 0: the LayerNorm kernel then the skinny
+        linear, 1: the skinny linear with the LayerNorm as its prologue (tests)."""
+        x = np.ascontiguousarray(x, dtype=np.float32); w = np.ascontiguousarray(w, dtype=np.float32)
+        g = np.ascontiguousarray(gamma, dtype=np.float32); b = np.ascontiguousarray(beta, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != 384 or w.ndim != 2 or w.shape[1] != 384 or g.shape != (384,) or b.shape != (384,):
+            raise ValueError("x [M, 384], w [N, 384], gamma [384], beta [384]")
+        M, N = x.shape[0], w.shape[0]
+        bs = np.ascontiguousarray(bias, dtype=np.float32) if bias is not None else None
+        out = np.zeros((M, N), np.float32)
+        self._check(self.lib.ttr_dbg_ln_linear(self.h, _f(x), M, _f(g), _f(b), float(eps), _f(w), _f(bs) if bs is not None else None, N, int(fused), _f(out)))
         return out
 
 
