@@ -45,6 +45,9 @@
 // And a keyword-only curved=False on image_to_data: True straightens the crops of words set on an arc along a spine found in the page (DESIGN.md "Curved
 // words"); every dict gains "curved" (bool) and "outline" (18 [x, y] points: the top edge left to right, then the bottom edge right to left).  It turns
 // rectify on.  curved with orient, chars, wide, alts, lexicon, pattern or regions raises ValueError (Engine.set_curved combines with the last four).
+// And a keyword-only tables=False on image_to_data: tables=True (min_len 48, ink 128) or tables=(min_len, ink) finds ruling lines, tables, grids and merged
+// cells in the page's pixels (DESIGN.md "Tables"); every dict gains "table" and "cell" (-1 / -1 for an item in no cell).  It combines with every keyword but
+// regions (ValueError); a value out of range raises RuntimeError before anything runs.
 // image: uint8 array with 3 dimensions (else RuntimeError("Input array should have 3 dimensions"),
 // python.cpp:15-17).  Unlike the reference this copy honours strides and rejects != 3 channels
 // instead of silently mis-copying, and the GIL is released while the GPU works.
@@ -66,7 +69,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false, curved = false, lex_edits = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false, curved = false, lex_edits = false, tables = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
@@ -83,6 +86,7 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
     d["word"] = item.word;
   }
   if (k.blocks) d["block"] = item.block;
+  if (k.tables) { d["table"] = item.table; d["cell"] = item.cell; }
   if (k.curved) {
     d["curved"] = item.curved;
     py::list pts;
@@ -262,7 +266,20 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
                                       py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved, py::object lexicon_fuzzy, double lexicon_gap,
-                                      py::object tiled_kw) {
+                                      py::object tiled_kw, py::object tables_kw) {
+  // tables=False | True (48, 128) | (min_len, ink): tables for this call (DESIGN.md "Tables")
+  struct TablesScope {
+    TablesScope(int m, int i) { set_tables(m, i); }
+    ~TablesScope() { set_tables(0); }
+  };
+  int tab_min_len = 0, tab_ink = 128;
+  if (py::isinstance<py::bool_>(tables_kw)) tab_min_len = tables_kw.cast<bool>() ? 48 : 0;
+  else if (py::isinstance<py::tuple>(tables_kw) && py::len(tables_kw) == 2) { tab_min_len = tables_kw.cast<py::tuple>()[0].cast<int>(); tab_ink = tables_kw.cast<py::tuple>()[1].cast<int>(); }
+  else if (!tables_kw.is_none()) throw py::type_error("tables must be False, True or (min_len, ink)");
+  if (tab_min_len != 0 && !regions_kw.is_none()) throw std::invalid_argument("tables does not combine with regions (the views stay empty)");
+  if (tab_min_len != 0 && (tab_min_len < 16 || tab_min_len > 4096 || tab_ink < 1 || tab_ink > 255))
+    throw std::runtime_error("tables must be False, True or (min_len, ink) with min_len in 16..4096 and ink in 1..255");
+  TablesScope tables_scope(tab_min_len, tab_ink);
   // tiled=False | True (128) | an overlap: tiled pages for this call (DESIGN.md "Tiled pages"); the engine checks the value, a refusal raises RuntimeError
   struct TiledScope {
     explicit TiledScope(int o) { set_tiled(o); }
@@ -308,6 +325,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     py::list res;
     Keys keys{true, conf, false, lines, false, blocks};
     keys.curved = true;
+    keys.tables = tab_min_len != 0;
     for (const auto& item : got) res.append(item_dict(item, keys));
     return res;
   }
@@ -323,7 +341,9 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     }
     if (got.empty()) raise_refused();
     py::list res;
-    for (const auto& item : got) res.append(item_dict(item, Keys{true, conf, false, lines, false, blocks, false, false, true}));
+    Keys wkeys{true, conf, false, lines, false, blocks, false, false, true};
+    wkeys.tables = tab_min_len != 0;
+    for (const auto& item : got) res.append(item_dict(item, wkeys));
     return res;
   }
   if (!regions_kw.is_none()) {   // regions: no detector; every check before anything runs
@@ -382,6 +402,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   py::list result;
   Keys keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best};
   keys.lex_edits = band >= 0;
+  keys.tables = tab_min_len != 0;
   for (const auto& item : items) result.append(item_dict(item, keys));
   return result;
 }
@@ -449,7 +470,7 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, py::arg("tables") = false, "Extract text and bounding boxes from an image");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
         py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("pattern_best") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");

@@ -5,7 +5,9 @@ result, and save an annotated copy (the reference's three panels: boxes on the p
 (the reference draws with cv2 and opens a window; neither is needed for the results).
 
   python bindings/run_ocr.py [--rectify] [--curved] [image] [weights_dir] [outputs_dir]   (--rectify: deskewed crops, words drawn as their quads;
-  --curved: words set on an arc are straightened along their spines and drawn as their 18-point outlines)
+  --curved: words set on an arc are straightened along their spines and drawn as their 18-point outlines; --tables: every item carries its table and cell, and
+  the page's rulings and cells are drawn over the first panel - the geometry from the host rule tuatara_amd.engine.tables_from_page, which the engine's kernels
+  equal bit for bit)
 """
 from __future__ import annotations
 
@@ -71,7 +73,8 @@ def annotate(image: np.ndarray, result, by_lines: bool = False, by_blocks: bool 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     rectify, lines, chars, blocks, curved = "--rectify" in argv, "--lines" in argv, "--chars" in argv, "--blocks" in argv, "--curved" in argv
-    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks", "--curved")]
+    tables = "--tables" in argv
+    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks", "--curved", "--tables")]
     image_path = argv[0] if len(argv) > 0 else os.path.join(HERE, "..", "tests", "data", "funsd_0001129658.png")
     weights_dir = argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "weights")
     outputs_dir = argv[2] if len(argv) > 2 else os.path.join(HERE, "..", "outputs")
@@ -87,11 +90,23 @@ def main(argv=None):
         kw["blocks"] = True
     if curved:                      # (curved words read on rectified crops: curved=True turns rectify on)
         kw["curved"] = True
+    if tables:                      # (DESIGN.md "Tables": min_len 48, ink 128)
+        kw["tables"] = True
     result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir, **kw)
     print(result)
     os.makedirs(outputs_dir, exist_ok=True)
     stem = os.path.splitext(os.path.basename(image_path))[0]
-    annotate(numpy_image, result, by_lines=lines, by_blocks=blocks).save(os.path.join(outputs_dir, stem + "_annotated_with_ocr_results.png"))
+    out = annotate(numpy_image, result, by_lines=lines, by_blocks=blocks)
+    if tables:
+        sys.path.insert(0, os.path.join(HERE, ".."))
+        from tuatara_amd.engine import tables_from_page
+        t = tables_from_page(numpy_image)
+        d = ImageDraw.Draw(out)
+        for c in t["cells"]:       # cells first, rulings over them
+            d.rectangle([int(c[5]), int(c[6]), int(c[7]), int(c[8])], outline=(0, 160, 255), width=2)
+        for r in t["rulings"]:
+            d.rectangle([int(r[1]), int(r[2]), int(r[3]), int(r[4])], outline=(255, 0, 255) if r[5] >= 0 else (255, 160, 0))
+    out.save(os.path.join(outputs_dir, stem + "_annotated_with_ocr_results.png"))
     return result
 
 

@@ -43,6 +43,9 @@
 //   ocr_cli --tiled [O] ...   in front of any form above that runs the detector, options included: a page larger than the detector canvas is read at full size,
 // as overlapping tiles whose heat maps are stitched into one page map (DESIGN.md "Tiled pages"); O = the overlap in pixels, a multiple of 32 in [64, 256]
 // (default 128, not tuned on documents).  A page of more than 64 tiles or with a side above 8192 fails with the rule's message.
+//   ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: finds ruling lines, tables, grids and merged cells in the
+// page's pixels (DESIGN.md "Tables"; MIN_LEN = the shortest ruling in px, 16..4096, default 48, not tuned on documents) and prints each table as "# table T x0 y0
+// x1 y1 rows cols" followed by its rows, the cells' texts separated by tabs (a merged cell's text at its first base cell; a line break inside a cell as " / ").
 //   ocr_cli --decode-only <image.png> <out.raw>   writes the decoded BGR bytes (tests of the PNG reader; no GPU).
 #include <algorithm>
 #include <cmath>
@@ -143,6 +146,35 @@ int main(int argc, const char** argv) {
         printf("%g %g %g %g\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.conf, it.text.c_str());
         if (it.pieces.size() > 1)
           for (const WordPiece& p : it.pieces) printf("\t|%.6f %s\n", p.conf, p.text.c_str());
+      }
+      return 0;
+    }
+    if (argc >= 2 && std::string(argv[1]) == "--tables") {
+      int min_len = 48, used = 1;
+      if (argc == 6) {
+        char* end = nullptr;
+        const long v = std::strtol(argv[2], &end, 10);
+        if (!end || *end || v < 16 || v > 4096) throw std::runtime_error("--tables takes a shortest ruling in 16..4096 px (default 48)");
+        min_len = (int)v; used = 2;
+      }
+      if (argc - used != 4) throw std::runtime_error("--tables [MIN_LEN] goes in front of <image.png> <weights_dir> <outputs_dir>");
+      pngdec::Image img = pngdec::read(argv[used + 1]);
+      set_tables(min_len);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[used + 2], argv[used + 3], false);
+      set_tables(0);
+      if (!last_call_error().empty()) return 1;                         // (the message is on stderr)
+      const std::vector<TableGrid> tabs = last_call_tables();
+      for (size_t t = 0; t < tabs.size(); ++t) {
+        const TableGrid& g = tabs[t];
+        printf("# table %zu %d %d %d %d %d %d\n", t, g.bbox[0], g.bbox[1], g.bbox[2], g.bbox[3], g.rows, g.cols);
+        for (int i = 0; i < g.rows; ++i) {
+          for (int j = 0; j < g.cols; ++j) {
+            std::string s = g.text[(size_t)i * g.cols + j];
+            for (size_t p = 0; (p = s.find('\n', p)) != std::string::npos;) s.replace(p, 1, " / ");
+            printf("%s%s", j ? "\t" : "", s.c_str());
+          }
+          printf("\n");
+        }
       }
       return 0;
     }
@@ -325,7 +357,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli [--tiled [O]] [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir> | ocr_cli [--tiled [O]] [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

@@ -75,6 +75,7 @@ struct OutputItemEx {
   std::vector<WordPiece> pieces;   // wide words: the item's pieces in order (one, the item itself, when it is not wide); empty when wide is off (DESIGN.md "Wide words")
   bool curved = false;             // curved words: the item's crop was straightened along a spine found in the page (DESIGN.md "Curved words")
   std::vector<float> outline;      // curved words: 36 = 18 points x, y - the top edge left to right, then the bottom edge right to left; empty when curved is off
+  int table = -1, cell = -1;       // tables: the table of its page and the cell of that page's cell list the item lies in; -1 / -1 in no cell and when tables are off (DESIGN.md "Tables")
   int block = -1, block_line = -1;  // text blocks: the item's block of its page, in reading order, and its line's position inside that block (what a caller sorts by: block, block_line, word); -1 when blocks are off (DESIGN.md "Text blocks")
 };
 std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int cols, std::ptrdiff_t row_stride, std::string weights_dir,
@@ -252,6 +253,21 @@ std::vector<OutputItemEx> image_to_data_ex(const uint8_t* image, int rows, int c
 // canvas keeps every bit.
 void set_tiled(int overlap);
 int tiled();
+
+// Tables (opt-in; DESIGN.md "Tables"): ruling lines are found in the page's own pixels, grouped into tables, each table's grid and merged cells derived, and
+// every item given its table and cell (OutputItemEx::table, ::cell).  Items, order, boxes and text keep their bits.  set_tables(min_len, ink) turns it on for
+// every call of THIS THREAD that follows (min_len 16..4096 px, the shortest ruling; ink 1..255; the other layers use 48 and 128, which nobody has tuned on
+// documents), set_tables(0) off again; with it off, TUATARA_TABLES=MIN_LEN (or 1 for 48) in the environment turns it on for every call here.  It is set on the
+// cached engine for the call and reset afterwards.  A bad value: the message is printed and the result is empty (last_call_error()).  last_call_tables(): the
+// tables of this thread's latest single-image call - rows x cols strings, a merged cell's text at its first base cell, its items joined by the line rule.
+struct TableGrid {
+  int bbox[4] = {0, 0, 0, 0};       // x0, y0, x1, y1 in image pixels
+  int rows = 0, cols = 0;
+  std::vector<std::string> text;    // rows x cols, row-major
+};
+void set_tables(int min_len, int ink = 128);
+int tables();
+std::vector<TableGrid> last_call_tables();
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)

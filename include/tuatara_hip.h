@@ -714,6 +714,48 @@ int ttr_stitch_tiles(const float* tiles, int pages, int ny, int nx, const int* o
 int ttr_stitch_heat(ttr_engine* e, const float* tiles, int pages, int ny, int nx, const int* oy, const int* ox, int Hc, int Wc, int H2, int W2, float* out);
 int ttr_craft_heatmap_tiled(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int overlap, float* heat_out, size_t cap, int* H2, int* W2);
 int ttr_tile_canvases(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int overlap, uint8_t* canvases, size_t cap);
+/* ---- tables (opt-in; DESIGN.md "Tables") ---------------------------------------------------------
+ * With ttr_engine_set_tables(e, min_len, ink) every page call also finds the ruling lines in the page's own pixels (table_ink_kernel, tables.hip: one bit per
+ * pixel), groups them into tables, derives each table's grid and merged cells (table_grid_kernel, one workgroup per page) and says for every item which table
+ * and cell it lies in.  Items, order, boxes, text, ids, conf and every other layer's outputs keep their bits; with tables off nothing runs.  min_len = 0 is off
+ * (the default), else min_len in 16..4096 (the shortest ruling, px) and ink in 1..255 (a pixel is ink iff the mean of its three bytes is below it); the
+ * convenience layers use 48 and 128, and neither value has been tuned on documents.  The setter refuses while streamed batches are in flight and with a
+ * communicator attached; ttr_engine_attach_comm and ttr_pages_to_data_dev_sharded refuse while tables are on; region calls leave the views empty.
+ * Caps (a page beyond one reports mode = -(step of the rule) and nothing else): 8192 runs and 256 rulings per direction, 32 tables, 64 lines per axis and
+ * table, 1024 cells.
+ * Result views (NULL / 0 with tables off and for an empty result):
+ *   ttr_result_table_mode      1, or -2 / -4 / -6 / -7; 0 when off
+ *   ttr_result_rulings         [ruling_count][6] int32: dir (0 horizontal, 1 vertical), x0, y0, x1, y1 (inclusive px), table (-1 = loose)
+ *   ttr_result_tables          [table_count][8]: x0, y0, x1, y1, rows, cols, first cell, cell count
+ *   ttr_result_table_lines     per table its rows + 1 row lines, then its cols + 1 column lines, back to back, in doubled px; *n receives their number
+ *   ttr_result_cells           [cell_count][9]: table, row, col, rowspan, colspan, x0, y0, x1, y1
+ *   ttr_result_item_table / ttr_result_item_cell   [count]: -1 for an item in no cell
+ *   ttr_result_cell_text       the items of cell c through the host line rule, words joined by a space, lines by '\n'; returns the length (without the
+ *                              terminator) and writes at most cap bytes, terminator included; -1 for a bad cell
+ * ttr_results_gather_tables: item_table / item_cell of n results back to back (-1 where a result has none); returns the number of items in a cell.
+ * ttr_tables_from_page: the rule on the host, no engine.  A host image u8 [h][w][3] (row_stride bytes, 0 = 3 w) and nq quads [nq][8] -> mode, counts [6] =
+ * {rulings, tables, cells, line values, horizontal runs, vertical runs} (all 0 for a page beyond a cap), rulings [512][6], tables [32][8], lines [32 * 130], cells [1024][9] (capacities; counts says how much is valid),
+ * item_table [nq], item_cell [nq]; any output may be NULL.  Returns 0, -1 with the message in ttr_last_error (min_len outside 16..4096, ink outside 1..255, a
+ * quad with a coordinate that is not finite or has |x| >= 32768, a page side of 32768 or more).
+ * ttr_tables_page (stage; refuses while batches stream): the same through the two kernels, whatever the engine's setting. */
+int ttr_engine_set_tables(ttr_engine* e, int min_len, int ink);
+int ttr_engine_tables(const ttr_engine* e, int* ink);
+int ttr_result_table_mode(const ttr_result* r);
+int ttr_result_ruling_count(const ttr_result* r);
+const int32_t* ttr_result_rulings(const ttr_result* r);
+int ttr_result_table_count(const ttr_result* r);
+const int32_t* ttr_result_tables(const ttr_result* r);
+const int32_t* ttr_result_table_lines(const ttr_result* r, int* n);
+int ttr_result_cell_count(const ttr_result* r);
+const int32_t* ttr_result_cells(const ttr_result* r);
+const int32_t* ttr_result_item_table(const ttr_result* r);
+const int32_t* ttr_result_item_cell(const ttr_result* r);
+int ttr_result_cell_text(const ttr_result* r, int c, char* buf, int cap);
+int ttr_results_gather_tables(ttr_result* const* rs, int n, int32_t* item_table, int32_t* item_cell);
+int ttr_tables_from_page(const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq, int32_t* mode, int32_t* counts,
+                         int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell);
+int ttr_tables_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq, int32_t* mode,
+                    int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

@@ -130,6 +130,12 @@ int ttr_dbg_deskew(const float* rect5, float* quad8, double* coef6, int64_t* fix
  * (crop_mode 1: the deskewed quad; 0: the clamped boundingRect's pixel edges) turned by `turn` quarter turns, quad8 = Q_t, fixed6 its
  * coefficients as the engine hands them to pack_crops_rect_kernel.  Returns 0, -1 on bad arguments. */
 int ttr_dbg_orient_quad(const float* rect5, int h, int w, int crop_mode, int turn, float* quad8, int64_t* fixed6);
+/* tables (DESIGN.md "Tables"): table_ink_kernel and table_grid_kernel on a host image u8 [h][w][3] (row_stride bytes, 0 = 3 w), placed dev_offset bytes into a
+ * device buffer with dev_stride bytes from row to row (0 = 3 w) - an offset or stride that is no multiple of 4 takes the kernel's byte-load path.  bits
+ * [h][ceil(w / 64)] uint64 the ink bitmap, runs [2][8192][3] int32 the horizontal {y, x0, x1} and vertical {x, y0, y1} run lists (zero beyond their counts),
+ * n_runs [2] (0, 0 for a page beyond the run cap), mode; any output may be NULL.  Refuses while batches stream.  Returns 0, -1 on error. */
+int ttr_dbg_tables(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_len, int ink, uint64_t* bits, int32_t* runs,
+                   int32_t* n_runs, int32_t* mode);
 /* canvas_geometry on the host for any canvas_size / mag_ratio (what ttr_canvas_geometry answers for an engine of that config): h32 x w32, the ratio and
  * the resized page's target_h x target_w inside the canvas.  Any output may be NULL.  Returns 0, -1 for h <= 0 or w <= 0. */
 int ttr_dbg_canvas_geometry(int h, int w, int canvas_size, float mag_ratio, int* H, int* W, float* ratio, int* target_h, int* target_w);

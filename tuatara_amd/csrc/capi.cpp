@@ -1,6 +1,7 @@
 // The C ABI of include/tuatara_hip.h: extern "C", plain pointers and sizes, no exceptions across it.
 #include "engine.h"
 #include "page_table.h"
+#include "tables_rule.h"
 
 namespace ttr {
 
@@ -1513,6 +1514,132 @@ int ttr_curve_crops(ttr_engine* e, const uint8_t* img, int h, int w, int row_str
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_curve_crops");
   E.curve_crops(img, h, w, row_stride, quads, nq, use_table != 0, flag, hb, spine, knots, crops);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+// ---- tables (DESIGN.md "Tables")
+int ttr_engine_set_tables(ttr_engine* e, int min_len, int ink) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (min_len != 0 && !tables_args_ok(min_len, ink))
+    throw std::runtime_error("ttr_engine_set_tables: min_len must be 0 (off) or lie in 16..4096 and ink in 1..255, got " + std::to_string(min_len) + " and " + std::to_string(ink));
+  E.refuse_while_streaming("ttr_engine_set_tables");
+  if (min_len && E.comm) throw std::runtime_error("ttr_engine_set_tables: tables are found by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
+  E.tables_min_len = min_len;
+  if (min_len) E.tables_ink = ink;
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_tables(const ttr_engine* e, int* ink) {
+  if (!e) return 0;
+  if (ink) *ink = e->e->tables_ink;
+  return e->e->tables_min_len;
+}
+
+int ttr_result_table_mode(const ttr_result* r) { return r ? r->r.table_mode : 0; }
+int ttr_result_ruling_count(const ttr_result* r) { return r ? (int)(r->r.rulings.size() / 6) : 0; }
+const int32_t* ttr_result_rulings(const ttr_result* r) { return r && !r->r.rulings.empty() ? r->r.rulings.data() : nullptr; }
+int ttr_result_table_count(const ttr_result* r) { return r ? (int)(r->r.tables.size() / 8) : 0; }
+const int32_t* ttr_result_tables(const ttr_result* r) { return r && !r->r.tables.empty() ? r->r.tables.data() : nullptr; }
+const int32_t* ttr_result_table_lines(const ttr_result* r, int* n) {
+  if (n) *n = r ? (int)r->r.table_lines.size() : 0;
+  return r && !r->r.table_lines.empty() ? r->r.table_lines.data() : nullptr;
+}
+int ttr_result_cell_count(const ttr_result* r) { return r ? (int)(r->r.cells.size() / 9) : 0; }
+const int32_t* ttr_result_cells(const ttr_result* r) { return r && !r->r.cells.empty() ? r->r.cells.data() : nullptr; }
+const int32_t* ttr_result_item_table(const ttr_result* r) { return r && !r->r.item_table.empty() ? r->r.item_table.data() : nullptr; }
+const int32_t* ttr_result_item_cell(const ttr_result* r) { return r && !r->r.item_cell.empty() ? r->r.item_cell.data() : nullptr; }
+
+int ttr_result_cell_text(const ttr_result* r, int c, char* buf, int cap) {
+  TTR_GUARD_BEGIN
+  if (!r || c < 0 || c >= (int)(r->r.cells.size() / 9) || cap < 0 || (cap > 0 && !buf)) throw std::runtime_error("ttr_result_cell_text: bad cell or buffer");
+  const Result& R = r->r;
+  std::vector<int> members;
+  for (size_t k = 0; k < R.item_cell.size(); ++k) if (R.item_cell[k] == c) members.push_back((int)k);
+  std::string text;
+  if (!members.empty()) {   // the cell's items through the host line rule (DESIGN.md "Text lines")
+    const int m = (int)members.size();
+    std::vector<int32_t> cuv((size_t)m * 6), line(m), word(m), order(m), first(m + 1);
+    for (int k = 0; k < m; ++k)
+      if (!lines_cuv(&R.quad[(size_t)members[k] * 8], &cuv[(size_t)k * 6])) throw std::runtime_error("ttr_result_cell_text: a quad outside the line rule's domain");
+    int32_t nl = 0;
+    lines_from_cuv(cuv.data(), m, line.data(), word.data(), &nl);
+    if (!lines_reading_order(line.data(), word.data(), m, nl, order.data(), first.data())) throw std::runtime_error("ttr_result_cell_text: the line rule gave no numbering");
+    for (int l = 0; l < nl; ++l) {
+      if (l) text += '\n';
+      for (int k = first[l]; k < first[l + 1]; ++k) { if (k > first[l]) text += ' '; text += R.text[(size_t)members[(size_t)order[k]]]; }
+    }
+  }
+  if (cap > 0) { const size_t n = std::min(text.size(), (size_t)cap - 1); memcpy(buf, text.data(), n); buf[n] = 0; }
+  return (int)text.size();
+  TTR_GUARD_END(-1)
+}
+
+int ttr_results_gather_tables(ttr_result* const* rs, int n, int32_t* item_table, int32_t* item_cell) {
+  if (!rs || n < 0) return -1;
+  size_t oi = 0, inside = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!rs[i]) continue;
+    const Result& r = rs[i]->r;
+    const size_t cnt = r.text.size();
+    const bool has = cnt > 0 && r.item_table.size() == cnt;
+    if (item_table) { if (has) std::copy(r.item_table.begin(), r.item_table.end(), item_table + oi); else std::fill(item_table + oi, item_table + oi + cnt, -1); }
+    if (item_cell) { if (has) std::copy(r.item_cell.begin(), r.item_cell.end(), item_cell + oi); else std::fill(item_cell + oi, item_cell + oi + cnt, -1); }
+    if (has) for (int32_t c : r.item_cell) inside += c >= 0;
+    oi += cnt;
+  }
+  return (int)inside;
+}
+
+static void tables_out(const int32_t* side, const int32_t* items, int nq, int32_t* mode, int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells,
+                       int32_t* item_table, int32_t* item_cell) {
+  if (mode) *mode = side[0];
+  int32_t c4[4];
+  tables_export(side, c4, rulings, tables, lines, cells);
+  if (counts) { std::copy(c4, c4 + 4, counts); counts[4] = side[0] == 1 ? side[5] : 0; counts[5] = side[0] == 1 ? side[6] : 0; }
+  for (int i = 0; i < nq; ++i) {
+    if (item_table) item_table[i] = items[2 * (size_t)i];
+    if (item_cell) item_cell[i] = items[2 * (size_t)i + 1];
+  }
+}
+
+static void tables_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq) {
+  if (!img || nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
+  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
+  if (h >= 32768 || w >= 32768) throw std::runtime_error(std::string(what) + ": a page side of 32768 px or more");
+  if (!tables_args_ok(min_len, ink)) throw std::runtime_error(std::string(what) + ": min_len must lie in 16..4096 and ink in 1..255, got " + std::to_string(min_len) + " and " + std::to_string(ink));
+  for (int i = 0; i < nq; ++i)
+    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error(std::string(what) + ": quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+}
+
+int ttr_tables_from_page(const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq, int32_t* mode, int32_t* counts,
+                         int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell) {
+  TTR_GUARD_BEGIN
+  tables_in_ok("ttr_tables_from_page", img, h, w, row_stride, min_len, ink, quads, nq);
+  std::vector<int32_t> side(kTabSideInts), centres((size_t)nq * 2), items((size_t)nq * 2);
+  tables_from_page(img, h, w, row_stride ? row_stride : w * 3, min_len, ink, side.data());
+  for (int i = 0; i < nq; ++i) tables_word_centre(quads + 8 * (size_t)i, &centres[2 * (size_t)i]);
+  tables_words(side.data(), centres.data(), nq, items.data());
+  tables_out(side.data(), items.data(), nq, mode, counts, rulings, tables, lines, cells, item_table, item_cell);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_tables_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq, int32_t* mode,
+                    int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  tables_in_ok("ttr_tables_page", img, h, w, row_stride, min_len, ink, quads, nq);
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_tables_page");
+  std::vector<int32_t> side(kTabSideInts), items((size_t)nq * 2);
+  E.tables_stage(img, h, w, row_stride, 0, 0, min_len, ink, quads, nq, side.data(), items.data(), nullptr, nullptr);
+  tables_out(side.data(), items.data(), nq, mode, counts, rulings, tables, lines, cells, item_table, item_cell);
   return 0;
   TTR_GUARD_END(-1)
 }

@@ -1,5 +1,6 @@
 // Developer hooks of include/tuatara_hip_debug.h: single-kernel test entry points, micro-benchmarks, the tuning registry.
 #include "engine.h"
+#include "tables_rule.h"
 
 using namespace ttr;
 
@@ -679,6 +680,23 @@ int ttr_dbg_last_heat(ttr_engine* e, float* heat, size_t floats) {
   if (!heat || floats == 0 || floats * 4 > E.heat.cap) throw std::runtime_error("ttr_dbg_last_heat: more floats than the last batch's heat maps hold");
   TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
   TTR_HIP_CHECK(hipMemcpy(heat, E.heat.p, floats * 4, hipMemcpyDeviceToHost));
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+// tables (DESIGN.md "Tables"): the ink bitmap and the run lists as the device formed them
+int ttr_dbg_tables(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_len, int ink, uint64_t* bits, int32_t* runs,
+                   int32_t* n_runs, int32_t* mode) {
+  TTR_GUARD_BEGIN
+  if (!e || !img) throw std::runtime_error("null argument");
+  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("ttr_dbg_tables: bad image size");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_dbg_tables");
+  std::vector<int32_t> side(kTabSideInts);
+  E.tables_stage(img, h, w, row_stride, dev_offset, dev_stride, min_len, ink, nullptr, 0, side.data(), nullptr, bits, runs);
+  if (n_runs) { n_runs[0] = side[5]; n_runs[1] = side[6]; }
+  if (mode) *mode = side[0];
   return 0;
   TTR_GUARD_END(-1)
 }

@@ -333,6 +333,13 @@ struct Result {
   std::vector<int32_t> curved;              // 1 per item: 1 = its crop was straightened along its spine
   std::vector<float> outline;               // 36 per item: 18 points, the top edge left to right, then the bottom edge right to left
   std::vector<int64_t> spine_knots;         // 36 per item: the knot table {Cx, Cy, Hx, Hy} x 9 in 2^-16 px (zeros for an item whose second pass did not run)
+  // tables (ttr_engine_set_tables; DESIGN.md "Tables"): 0 / empty when off and for a page without items
+  int table_mode = 0;                       // 1, or -(step) of the cap the page overflowed
+  std::vector<int32_t> rulings;             // 6 per ruling: dir, x0, y0, x1, y1, table
+  std::vector<int32_t> tables;              // 8 per table: x0, y0, x1, y1, rows, cols, first cell, cell count
+  std::vector<int32_t> table_lines;         // per table its rows + 1 row lines, then its cols + 1 column lines, in doubled px
+  std::vector<int32_t> cells;               // 9 per cell: table, row, col, rowspan, colspan, x0, y0, x1, y1
+  std::vector<int32_t> item_table, item_cell;   // 1 per item: -1 = in no cell
   // text blocks (cfg.blocks = 1; DESIGN.md "Text blocks"): empty / 0 when off
   std::vector<int32_t> line_block, line_pos;     // 1 per line: its block in reading order, its position inside that block
   std::vector<int32_t> block;                    // 1 per item: its line's block
@@ -459,6 +466,7 @@ struct Engine {
   int lex_band = -1; float lex_gap = 0.f;         // fuzzy alignment (ttr_engine_set_lexicon_fuzzy): the band 0..3 (-1 = off: the rigid scorer) and the gap's log-probability
   float wide = 0.f;                               // wide words: the largest aspect a piece may have, 0 = off or 2..64 (ttr_engine_set_wide; DESIGN.md "Wide words")
   bool curved = false;                            // curved words: straighten the crops of words set on an arc (ttr_engine_set_curved; DESIGN.md "Curved words")
+  int tables_min_len = 0, tables_ink = 128;       // tables: the shortest ruling in px, 0 = off or 16..4096, and the ink threshold 1..255 (ttr_engine_set_tables; DESIGN.md "Tables")
   // tiled pages (ttr_engine_set_tiled; DESIGN.md "Tiled pages"): the tiles' overlap in pixels, 0 = off.  On, a page keeps its own scale (ratio 1, page canvas
   // c32(h) x c32(w)); one larger than the detector canvas goes through CRAFT as overlapping tiles whose maps tile_stitch_kernel joins into `heat`
   int tiled = 0;
@@ -555,6 +563,8 @@ struct Engine {
   PinnedBuf h_wide[2];                            // ... per slot: the cuts' host copy
   DevBuf curve_side;                              // curved words: the side block (curve.hip), [N] flag | [N][2] hb | [N][2][9] spine | [N][9][4] int64 knots
   PinnedBuf h_curve[2];                           // ... per slot: its host copy
+  DevBuf tab_bits, tab_bitsT, tab_runs, tab_side; // tables: the two bitmaps and the run lists (workspaces), and the side blocks [pages][kTabSideInts] | [N][2] table, cell (tables.hip)
+  PinnedBuf h_tab[2];                             // ... per slot: the side blocks' host copy
   DevBuf blocks_side;                             // text blocks: the side block (blocks.hip)
   PinnedBuf h_blocks[2];                          // ... per slot: its host copy
   DevBuf chars_map[2], chars_in, chars_side;      // character boxes: per slot the batch's region planes (a copy of ccl.tnorm); coef | page_of | turns | nchars; the side block (chars.hip)
@@ -866,6 +876,9 @@ struct Engine {
     // curved words (plan_curved; DESIGN.md "Curved words"): with `curved`, one entry per crop - its frame, page and row
     bool curved = false;
     std::vector<CurveIn> curve;
+    // tables (DESIGN.md "Tables"): the engine's setting when the boxes were made (0 = off, and for region calls), and 64 x every word's centre [N][2]
+    int tab_min_len = 0, tab_ink = 0;
+    std::vector<int32_t> tab_centres;
     int tiles = 0;                     // tiled pages: tiles per page (0 = the engine's tiling was off when the detector was enqueued), and their plan
     TilePlan plan{};
     int det_groups = -1;               // CCL groups enqueued for it (group_ev[det_groups]: behind the copy of its detector range word)
@@ -921,6 +934,12 @@ struct Engine {
   void plan_wide(PageBatch& B, const float* quads);
   // curved words: one CurveIn per crop of B from quads [N][8] (the quads plan_wide takes) under the engine's `curved`.  Host only; a no-op with curved off.
   void plan_curved(PageBatch& B, const float* quads);
+  // tables: the two kernels of batch B behind its packer (the centres and page offsets travelled with the rectangles' upload); a no-op with tables off
+  void tables_enqueue(const PageBatch& B, int sl);
+  // the stage form (ttr_tables_page, and the developer hook): a host image, placed dev_offset bytes into a device buffer with dev_stride bytes from row to row
+  // (0 = 3 w), and host quads through table_ink_kernel and table_grid_kernel -> side [kTabSideInts], items [nq][2], bits [h][ceil(w / 64)], runs [2][8192][3]
+  void tables_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_len, int ink, const float* quads, int nq, int32_t* side_out,
+                    int32_t* items_out, uint64_t* bits_out, int32_t* runs_out);
   // the stage form (ttr_curve_crops): a host image and host quads through the kind-1 packer and curve_crop_kernel -> flag [nq], hb [nq][2], spine [nq][2][9],
   // knots [nq][9][4], crops [nq][32][128][3]
   void curve_crops(const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, bool use_table, int32_t* flag, int32_t* hb, int32_t* spine,
@@ -965,7 +984,7 @@ struct Engine {
   // lexicon matches' (lexicon.hip, B.lex_m per item) or null; pat_logp: best mode's log-probabilities (pattern.hip, one per item) or null
   void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
                     std::vector<Result>& results, const void* alts_side = nullptr, const void* lex_side = nullptr, const int32_t* wide_cuts = nullptr,
-                    const float* pat_logp = nullptr, const void* curve_block = nullptr);
+                    const float* pat_logp = nullptr, const void* curve_block = nullptr, const int32_t* tab_block = nullptr);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it

@@ -5,6 +5,7 @@
 
 #include "engine.h"
 #include "page_table.h"
+#include "tables_rule.h"
 
 namespace ttr {
 
@@ -228,6 +229,9 @@ void Engine::detect_enqueue(PageBatch& B) {
   } else {
     check_pages(B.pages);                 // (before anything is enqueued)
   }
+  if (tables_min_len)                     // tables: the rule's coordinates are below 32768 (likewise before anything is enqueued)
+    for (const Page& P : B.pages)
+      if (P.h >= 32768 || P.w >= 32768) throw std::runtime_error("tables: a page side of 32768 px or more: ttr_engine_set_tables(e, 0, 0) first");
   const Page& P0 = B.pages[0];
   B.H = P0.g.h32; B.W = P0.g.w32; B.H2 = B.H / 2; B.W2 = B.W / 2;
   const int n = B.n, H = B.H, W = B.W, H2 = B.H2, W2 = B.W2;
@@ -387,6 +391,8 @@ void Engine::detect_collect_local(PageBatch& B) {
   std::vector<Pt2f> oq;                                        // orient != 0: each word's quad Q (DESIGN.md "Word orientation")
   std::vector<float> wq;                                       // wide != 0 or curved: each word's quad (DESIGN.md "Wide words", "Curved words")
   host_us[1] = host_us[2] = host_us[3] = 0.f;
+  B.tab_min_len = tables_min_len; B.tab_ink = tables_ink; B.tab_centres.clear();   // tables: fixed for the batch here (the setter refuses while batches stream)
+  std::vector<float> tq;
   for (int gi = 0; gi < groups; ++gi) ccl_collect(gi * GP, std::min(GP, n - gi * GP), gi, B.H2, B.W2, dets);
   // the detector's range word of THIS batch, before any of its boxes is used: a saturated heat map fails this batch and no other
   if (range_flag_ptr() && B.det_groups == groups) { spin_event(group_ev[groups]); range_verify(kRangeDet0 + (B.slot & 1), "the detector of a batch of pages"); }
@@ -419,6 +425,14 @@ void Engine::detect_collect_local(PageBatch& B) {
       B.boxes[i].push_back(b);
       B.rects.insert(B.rects.end(), {x0, y0, x1, y1, i});
       B.page_of.push_back(i);
+      if (B.tab_min_len) {   // tables: 64 x the centre of the quad the result will carry (DESIGN.md "Tables", step 8)
+        tq.clear();
+        push_quad(b, tq);
+        if (!region_quad_ok(tq.data())) throw std::runtime_error("tables: a corner of a word of page " + std::to_string(i) + " is not finite or lies beyond 32768 px");
+        int32_t c[2];
+        tables_word_centre(tq.data(), c);
+        B.tab_centres.insert(B.tab_centres.end(), c, c + 2);
+      }
       Pt2f q[4];
       if (cfg.crop_mode == TTR_CROP_RECTIFIED) {                    // DESIGN.md "Rectified crops": same items, other pixels
         double cf[6]; int64_t fx[6];
@@ -490,10 +504,19 @@ void Engine::plan_curved(PageBatch& B, const float* quads) {
 
 void Engine::pack_batch_crops(const PageBatch& B, int sl) {
   const int rows = B.N + B.X;                                  // wide words: X more rows behind the batch's N
-  rects_dev.ensure(B.rects.size() * 4);
-  h_rects[sl].ensure(B.rects.size() * 4);
-  memcpy(h_rects[sl].p, B.rects.data(), B.rects.size() * 4);
-  TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[sl].p, B.rects.size() * 4, hipMemcpyHostToDevice, stream));
+  // (tables: every word's centre [N][2] and the pages' offsets [n + 1] travel behind the rectangles, in the same copy)
+  const size_t rect_ints = B.rects.size(), tab_ints = B.tab_min_len ? B.tab_centres.size() + (size_t)B.n + 1 : 0;
+  rects_dev.ensure((rect_ints + tab_ints) * 4);
+  h_rects[sl].ensure((rect_ints + tab_ints) * 4);
+  memcpy(h_rects[sl].p, B.rects.data(), rect_ints * 4);
+  if (tab_ints) {
+    if (B.tab_centres.size() != (size_t)B.N * 2) throw std::runtime_error("tables: centre count does not match the crop count");
+    int32_t* t = h_rects[sl].as<int32_t>() + rect_ints;
+    std::copy(B.tab_centres.begin(), B.tab_centres.end(), t);
+    const std::vector<int> first = page_first(B.page_of, B.n);
+    std::copy(first.begin(), first.end(), t + B.tab_centres.size());
+  }
+  TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[sl].p, (rect_ints + tab_ints) * 4, hipMemcpyHostToDevice, stream));
   // (a uniform batch: its pages are page_bytes apart behind the first; a mixed one: each crop's page from the slot's table)
   const Page& P0 = B.pages[0];
   const size_t page_bytes = (size_t)P0.h * P0.w * 3;
@@ -823,6 +846,57 @@ void Engine::curve_crops(const uint8_t* img, int h, int w, int row_stride, const
   if (knots) memcpy(knots, side.data() + curve_side_table_offset(nq), (size_t)nq * 288);
 }
 
+void Engine::tables_enqueue(const PageBatch& B, int sl) {
+  const int n = B.n, N = B.N;
+  int Hcap = 0, Wcap = 0;
+  for (const Page& P : B.pages) { Hcap = std::max(Hcap, P.h); Wcap = std::max(Wcap, P.w); }
+  // (detect_enqueue refused a page side of 32768 or more before anything of the batch was enqueued)
+  tab_bits.ensure(tables_bits_slot(Hcap, Wcap) * 8 * n); tab_bitsT.ensure(tables_bitsT_slot(Hcap, Wcap) * 8 * n);
+  tab_runs.ensure((size_t)n * 2 * kTabRunCap * 3 * 4);
+  const size_t side_b = ((size_t)n * kTabSideInts + (size_t)N * 2) * 4;
+  tab_side.ensure(side_b); h_tab[sl].ensure(side_b);
+  const Page& P0 = B.pages[0];
+  const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
+  const int* centres = rects_dev.as<int>() + B.rects.size();
+  launch_table_ink(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, table, n, Hcap, Wcap, B.tab_ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  launch_table_grid(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), P0.h, P0.w, table, n, Hcap, Wcap, B.tab_min_len, centres, centres + (size_t)N * 2, tab_runs.as<int>(),
+                    tab_side.as<int>(), tab_side.as<int>() + (size_t)n * kTabSideInts, stream);
+  if (B.mixed) TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the table's last reader of this batch is now this kernel)
+}
+
+void Engine::tables_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_len, int ink, const float* quads, int nq,
+                          int32_t* side_out, int32_t* items_out, uint64_t* bits_out, int32_t* runs_out) {
+  if (h >= 32768 || w >= 32768) throw std::runtime_error("ttr_tables_page: a page side of 32768 px or more");
+  if (!tables_args_ok(min_len, ink)) throw std::runtime_error("ttr_tables_page: min_len must lie in 16..4096 and ink in 1..255");
+  const int ds = dev_stride ? dev_stride : w * 3;
+  if (dev_offset < 0 || ds < w * 3) throw std::runtime_error("ttr_tables_page: bad device offset or stride");
+  const size_t img_b = (size_t)dev_offset + (size_t)ds * h, in_ints = (size_t)nq * 2 + 2, side_b = ((size_t)kTabSideInts + (size_t)nq * 2) * 4;
+  staging_img.ensure(img_b); rects_dev.ensure(in_ints * 4); h_rects[0].ensure(in_ints * 4);
+  tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8); tab_runs.ensure((size_t)2 * kTabRunCap * 3 * 4); tab_side.ensure(side_b);
+  int32_t* in = h_rects[0].as<int32_t>();
+  for (int i = 0; i < nq; ++i) {
+    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error("ttr_tables_page: quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+    tables_word_centre(quads + 8 * (size_t)i, in + 2 * (size_t)i);
+  }
+  in[2 * (size_t)nq] = 0; in[2 * (size_t)nq + 1] = nq;
+  uint8_t* d_img = staging_img.as<uint8_t>() + dev_offset;
+  TTR_HIP_CHECK(hipMemcpy2DAsync(d_img, (size_t)ds, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, in, in_ints * 4, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipMemsetAsync(tab_runs.p, 0, (size_t)2 * kTabRunCap * 3 * 4, stream));   // (the hook returns whole lists)
+  launch_table_ink(d_img, 0, ds, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  launch_table_grid(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), h, w, nullptr, 1, h, w, min_len, rects_dev.as<int>(), rects_dev.as<int>() + (size_t)nq * 2, tab_runs.as<int>(),
+                    tab_side.as<int>(), tab_side.as<int>() + kTabSideInts, stream);
+  std::vector<int32_t> side(side_b / 4);
+  TTR_HIP_CHECK(hipMemcpyAsync(side.data(), tab_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  if (bits_out) TTR_HIP_CHECK(hipMemcpyAsync(bits_out, tab_bits.p, tables_bits_slot(h, w) * 8, hipMemcpyDeviceToHost, stream));
+  if (runs_out) TTR_HIP_CHECK(hipMemcpyAsync(runs_out, tab_runs.p, (size_t)2 * kTabRunCap * 3 * 4, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  std::string why;
+  if (!tables_side_valid(side.data(), &why)) throw std::runtime_error("ttr_tables_page: the side block holds " + why);
+  if (side_out) std::copy(side.begin(), side.begin() + kTabSideInts, side_out);   // (validated: the counted part is what callers read)
+  if (items_out) std::copy(side.begin() + kTabSideInts, side.end(), items_out);
+}
+
 void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
   const int line_words = cfg.lines && N > 0 ? stage_batch_lines(B, sl) : 0;   // text lines: the host part, before anything of this batch is enqueued
@@ -859,6 +933,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (T) pack_twin_crops(B, sl);
     if (cfg.lines) group_batch_lines(B, sl, line_words);               // text lines: from the boxes alone, so inside the packing stage (DESIGN.md "Text lines")
     if (cfg.blocks) group_batch_blocks(B, sl, line_words);             // text blocks: directly behind, from the lines' side block on the device (DESIGN.md "Text blocks")
+    if (B.tab_min_len) tables_enqueue(B, sl);                          // tables: the pages' own pixels and the boxes just made (DESIGN.md "Tables")
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     if (B.regions) {   // the caller's sets: one mask by value (the engine's own path), or the rows' table through the slot's pinned staging (one copy, no launch)
       main.mask = B.region_mask;
@@ -893,6 +968,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (B.pat_best) TTR_HIP_CHECK(hipMemcpyAsync(h_pat_logp[sl].p, pat_logp_dev.p, (size_t)N * 4, hipMemcpyDeviceToHost, stream));   // best mode's log-probabilities, likewise
     if (X) TTR_HIP_CHECK(hipMemcpyAsync(h_wide[sl].p, wide_side.p, B.wide.size() * 17 * 4, hipMemcpyDeviceToHost, stream));   // the wide words' cuts (the profile stays on the device)
     if (!B.curve.empty()) TTR_HIP_CHECK(hipMemcpyAsync(h_curve[sl].p, curve_side.p, curve_side_bytes(N), hipMemcpyDeviceToHost, stream));   // the curved words' side block
+    if (B.tab_min_len) TTR_HIP_CHECK(hipMemcpyAsync(h_tab[sl].p, tab_side.p, ((size_t)B.n * kTabSideInts + (size_t)N * 2) * 4, hipMemcpyDeviceToHost, stream));   // the tables' side blocks and the words' cells
   } else {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
@@ -934,14 +1010,17 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   const int32_t* wide_block = B.X && N > 0 ? h_wide[B.slot].as<int32_t>() : nullptr;            // the cuts of the side block (wide.hip)
   const float* pat_logp_block = B.pat_best && N > 0 ? h_pat_logp[B.slot].as<float>() : nullptr;  // the side block (pattern.hip, best mode)
   const void* curve_block = !B.curve.empty() && N > 0 ? h_curve[B.slot].p : nullptr;           // the side block (curve.hip)
-  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block, wide_block, pat_logp_block, curve_block);
+  const int32_t* tab_block = B.tab_min_len && N > 0 ? h_tab[B.slot].as<int32_t>() : nullptr;    // the side blocks (tables.hip)
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block, wide_block, pat_logp_block, curve_block,
+               tab_block);
   for (Result& r : results) r.tiles = B.tiles;                                                  // tiled pages: the tiles each page's detector ran as (0: off)
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
 
 void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                          std::vector<Result>& results, const void* alts_side, const void* lex_side, const int32_t* wide_cuts, const float* pat_logp, const void* curve_block) {
+                          std::vector<Result>& results, const void* alts_side, const void* lex_side, const int32_t* wide_cuts, const float* pat_logp, const void* curve_block,
+                          const int32_t* tab_block) {
   const int n = B.n, N = B.N, K = orient_k();
   const std::vector<int> first = page_first(B.page_of, n);
   // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
@@ -999,6 +1078,26 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
       tesseract_bbox(B.boxes[pg][k], bb);                                    // :511
       r.bbox.insert(r.bbox.end(), bb, bb + 4);
       push_quad(B.boxes[pg][k], r.quad);
+    }
+    if (B.tab_min_len && !B.regions && cnt > 0) {   // tables: the page's side block and its words' cells, checked before anything is built on them
+      if (!tab_block) throw std::runtime_error("tables: the batch carries no side block");
+      const int32_t* ts = tab_block + (size_t)pg * kTabSideInts;
+      const int32_t* ti = tab_block + (size_t)n * kTabSideInts + 2 * (size_t)c0;
+      std::string why;
+      if (!tables_side_valid(ts, &why)) throw std::runtime_error("tables: the side block of page " + std::to_string(pg) + " holds " + why);
+      int32_t counts[4];
+      tables_export(ts, counts, nullptr, nullptr, nullptr, nullptr);
+      r.table_mode = ts[0];
+      r.rulings.assign((size_t)counts[0] * 6, 0); r.tables.assign((size_t)counts[1] * 8, 0); r.cells.assign((size_t)counts[2] * 9, 0); r.table_lines.assign((size_t)counts[3], 0);
+      tables_export(ts, counts, r.rulings.data(), r.tables.data(), r.table_lines.data(), r.cells.data());
+      r.item_table.assign((size_t)cnt, -1); r.item_cell.assign((size_t)cnt, -1);
+      for (int k = 0; k < cnt; ++k) {
+        const int t = ti[2 * k], c = ti[2 * k + 1];
+        const bool none = t == -1 && c == -1;
+        if (!none && (t < 0 || t >= counts[1] || c < r.tables[(size_t)t * 8 + 6] || c >= r.tables[(size_t)t * 8 + 6] + r.tables[(size_t)t * 8 + 7]))
+          throw std::runtime_error("tables: word " + std::to_string(k) + " of page " + std::to_string(pg) + " names a table or cell that does not exist");
+        r.item_table[(size_t)k] = t; r.item_cell[(size_t)k] = c;
+      }
     }
     if (B.curved && cnt > 0) {   // curved words: every item's flag, outline and knot table, checked before anything is built on them
       if (!curve_block) throw std::runtime_error("curved words: the batch carries no side block");
@@ -1378,6 +1477,7 @@ void Engine::run_regions(const ttr_page* pages, int n_pages, const ttr_region* r
 void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& results) {
   if (wide != 0.f) throw std::runtime_error("latency mode does not support wide words: ttr_engine_set_wide(e, 0) first");
   if (curved) throw std::runtime_error("latency mode does not support curved words: ttr_engine_set_curved(e, 0) first");
+  if (tables_min_len) throw std::runtime_error("latency mode does not support tables: ttr_engine_set_tables(e, 0, 0) first");
   if (tiled) throw std::runtime_error("latency mode does not support tiled pages: ttr_engine_set_tiled(e, 0) first");
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");
   if (cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("latency mode does not support word orientation: create the engine with orient = TTR_ORIENT_OFF");

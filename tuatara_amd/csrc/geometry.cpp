@@ -3,6 +3,7 @@
 // Tokenizer (tuatara.cpp:25-117).  float32 throughout where OpenCV is float32.
 #include "geometry.h"
 #include "curve_rule.h"
+#include "tables_rule.h"
 
 #include <algorithm>
 #include <climits>
@@ -1233,6 +1234,168 @@ void stitch_tiles(const float* tiles, int pages, const TilePlan& P, float* out) 
       }
     }
   }
+}
+
+// ---- tables (DESIGN.md "Tables"): the host rule; integers only.  The predicates and steps 6 - 7 are tables_rule.h's.
+bool tables_args_ok(int min_len, int ink) { return min_len >= kTabMinLenLo && min_len <= kTabMinLenHi && ink >= 1 && ink <= 255; }
+
+void tables_ink(const uint8_t* image, int h, int w, int stride, int ink, uint64_t* bits) {
+  const int nw = (w + 63) / 64;
+  for (int y = 0; y < h; ++y) {
+    const uint8_t* row = image + (size_t)y * stride;
+    uint64_t* out = bits + (size_t)y * nw;
+    for (int k = 0; k < nw; ++k) out[k] = 0;
+    for (int x = 0; x < w; ++x)
+      if (tab_ink((int)row[3 * x] + (int)row[3 * x + 1] + (int)row[3 * x + 2], ink)) out[x >> 6] |= (uint64_t)1 << (x & 63);
+  }
+}
+
+int tables_runs(const uint64_t* bits, int h, int w, int dir, int32_t* runs) {
+  const int nw = (w + 63) / 64, lines = dir ? w : h, len = dir ? h : w;
+  int n = 0;
+  for (int l = 0; l < lines; ++l) {
+    int start = -1;
+    for (int p = 0; p <= len; ++p) {
+      const bool on = p < len && (dir ? (bits[(size_t)p * nw + (l >> 6)] >> (l & 63)) & 1 : (bits[(size_t)l * nw + (p >> 6)] >> (p & 63)) & 1);
+      if (on) { if (start < 0) start = p; continue; }
+      if (start >= 0 && p - start >= kTabR) {
+        if (n == kTabRunCap) return kTabRunCap + 1;
+        runs[3 * n] = l; runs[3 * n + 1] = start; runs[3 * n + 2] = p - 1;
+        ++n;
+      }
+      start = -1;
+    }
+  }
+  return n;
+}
+
+int tables_from_page(const uint8_t* image, int h, int w, int stride, int min_len, int ink, int32_t* side, int32_t* runs_out, uint64_t* bits_out) {
+  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !tables_args_ok(min_len, ink))
+    throw std::runtime_error("tables_from_page: bad argument");
+  std::vector<uint64_t> own_bits;
+  uint64_t* bits = bits_out;
+  if (!bits) { own_bits.resize(tables_bitmap_words(h, w)); bits = own_bits.data(); }
+  tables_ink(image, h, w, stride, ink, bits);
+  std::fill(side, side + kTabSideInts, 0);
+  std::vector<int32_t> own_runs;
+  int32_t* runs = runs_out;
+  if (!runs) { own_runs.resize((size_t)2 * kTabRunCap * 3); runs = own_runs.data(); }
+  else std::fill(runs, runs + (size_t)2 * kTabRunCap * 3, 0);
+  int nr[2];
+  for (int dir = 0; dir < 2; ++dir) {   // 2
+    nr[dir] = tables_runs(bits, h, w, dir, runs + (size_t)dir * kTabRunCap * 3);
+    if (nr[dir] > kTabRunCap) { tables_clear(side, -2); return -2; }
+  }
+  std::vector<int32_t> parent(kTabRunCap), stat((size_t)kTabRunCap * 4);
+  int count[2] = {0, 0};
+  for (int dir = 0; dir < 2; ++dir) {   // 3, 4
+    const int32_t* rn = runs + (size_t)dir * kTabRunCap * 3;
+    const int n = nr[dir];
+    for (int i = 0; i < n; ++i) parent[i] = i;
+    for (int i = 0, j = 0; i < n; ++i) {   // j: the first run of the next line that may still link
+      while (j < n && (rn[3 * j] < rn[3 * i] + 1)) ++j;
+      for (int k = j; k < n && rn[3 * k] == rn[3 * i] + 1 && rn[3 * k + 1] <= rn[3 * i + 2] + 1; ++k)
+        if (tab_link(rn[3 * i + 1], rn[3 * i + 2], rn[3 * k + 1], rn[3 * k + 2])) tab_union(parent.data(), i, k);
+    }
+    for (int i = 0; i < n; ++i) { stat[4 * i] = 32768; stat[4 * i + 1] = -1; stat[4 * i + 2] = -1; stat[4 * i + 3] = 0; }
+    for (int i = 0; i < n; ++i) {   // per root: smallest a0, largest a1, last line, area
+      const int r = tab_find(parent.data(), i);
+      stat[4 * r] = std::min(stat[4 * r], rn[3 * i + 1]); stat[4 * r + 1] = std::max(stat[4 * r + 1], rn[3 * i + 2]);
+      stat[4 * r + 2] = std::max(stat[4 * r + 2], rn[3 * i]); stat[4 * r + 3] += rn[3 * i + 2] - rn[3 * i + 1] + 1;
+    }
+    for (int i = 0; i < n; ++i) {
+      if (parent[i] != i) continue;
+      const int L = stat[4 * i + 1] - stat[4 * i] + 1, T = stat[4 * i + 2] - rn[3 * i] + 1;   // (the root is the component's first run: its line is the first)
+      if (!tab_is_ruling(L, T, stat[4 * i + 3], min_len)) continue;
+      if (count[dir] == kTabRulingCap) { tables_clear(side, -4); return -4; }
+      int32_t* q = side + kTabRulings + 6 * (count[0] + count[1]);
+      q[0] = dir;
+      if (dir == 0) { q[1] = stat[4 * i]; q[2] = rn[3 * i]; q[3] = stat[4 * i + 1]; q[4] = stat[4 * i + 2]; }
+      else { q[1] = rn[3 * i]; q[2] = stat[4 * i]; q[3] = stat[4 * i + 2]; q[4] = stat[4 * i + 1]; }
+      q[5] = -1;
+      ++count[dir];
+    }
+  }
+  const int nh = count[0], nv = count[1];
+  side[1] = nh; side[2] = nv; side[5] = nr[0]; side[6] = nr[1];
+  int32_t* rul = side + kTabRulings;
+  for (int r = 0; r < nh + nv; ++r) parent[r] = r;   // 5
+  for (int a = 0; a < nh; ++a)
+    for (int b = nh; b < nh + nv; ++b)
+      if (tab_meet(rul + 6 * a, rul + 6 * b)) tab_union(parent.data(), a, b);
+  for (int r = 0; r < nh + nv; ++r) rul[6 * r + 5] = tab_find(parent.data(), r);
+  std::vector<int32_t> scratch(kTabScratchInts);
+  const int mode = tables_grid(side, scratch.data());   // 6, 7
+  if (mode != 1) { tables_clear(side, mode); return mode; }
+  side[0] = 1;
+  return 1;
+}
+
+void tables_word_centre(const float* q, int32_t c[2]) {
+  long long cx = 0, cy = 0;
+  for (int k = 0; k < 4; ++k) { cx += std::llrint(16.0 * (double)q[2 * k]); cy += std::llrint(16.0 * (double)q[2 * k + 1]); }
+  c[0] = (int32_t)cx; c[1] = (int32_t)cy;
+}
+
+void tables_words(const int32_t* side, const int32_t* centres, int n, int32_t* out) {
+  for (int i = 0; i < n; ++i) tab_word_cell(side, centres[2 * i], centres[2 * i + 1], out + 2 * (size_t)i);
+}
+
+void tables_export(const int32_t* s, int32_t counts[4], int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells) {
+  const bool ok = s[0] == 1;
+  const int nr = ok ? s[1] + s[2] : 0, nt = ok ? s[3] : 0, nc = ok ? s[4] : 0;
+  int nl = 0;
+  for (int t = 0; t < nt; ++t) {
+    const int32_t* T = s + kTabTables + 8 * t;
+    const int32_t* Y = s + kTabLines + 2 * kTabLineCap * t;
+    if (lines) {
+      std::copy(Y, Y + T[4] + 1, lines + nl);
+      std::copy(Y + kTabLineCap, Y + kTabLineCap + T[5] + 1, lines + nl + T[4] + 1);
+    }
+    nl += T[4] + T[5] + 2;
+  }
+  if (counts) { counts[0] = nr; counts[1] = nt; counts[2] = nc; counts[3] = nl; }
+  if (rulings) std::copy(s + kTabRulings, s + kTabRulings + 6 * nr, rulings);
+  if (tables) std::copy(s + kTabTables, s + kTabTables + 8 * nt, tables);
+  if (cells) std::copy(s + kTabCells, s + kTabCells + 9 * nc, cells);
+}
+
+bool tables_side_valid(const int32_t* s, std::string* why) {
+  auto bad = [&](const char* m) { if (why) *why = m; return false; };
+  const int mode = s[0];
+  if (mode != 1 && mode != -2 && mode != -4 && mode != -6 && mode != -7) return bad("a mode that is none of 1, -2, -4, -6, -7");
+  if (mode != 1) { for (int k = 1; k < 5; ++k) if (s[k] != 0) return bad("counts beside an overflow mode"); return true; }
+  const int nh = s[1], nv = s[2], nt = s[3], nc = s[4];
+  if (nh < 0 || nh > kTabRulingCap || nv < 0 || nv > kTabRulingCap || nt < 0 || nt > kTabTableCap || nc < 0 || nc > kTabCellCap) return bad("a count beyond its cap");
+  for (int r = 0; r < nh + nv; ++r) {
+    const int32_t* q = s + kTabRulings + 6 * r;
+    if (q[0] != (r < nh ? 0 : 1) || q[1] < 0 || q[2] < 0 || q[3] < q[1] || q[4] < q[2] || q[3] >= 32768 || q[4] >= 32768 || q[5] < -1 || q[5] >= nt) return bad("a ruling out of range");
+  }
+  int next = 0;
+  std::vector<uint8_t> seen;
+  for (int t = 0; t < nt; ++t) {
+    const int32_t* T = s + kTabTables + 8 * t;
+    const int rows = T[4], cols = T[5];
+    if (rows < 1 || rows >= kTabLineCap || cols < 1 || cols >= kTabLineCap || T[6] != next || T[7] < 1 || T[7] > rows * cols || T[6] + T[7] > nc) return bad("a table out of range");
+    const int32_t* Y = s + kTabLines + 2 * kTabLineCap * t;
+    const int32_t* X = Y + kTabLineCap;
+    for (int i = 0; i <= rows; ++i) if (Y[i] < 0 || Y[i] >= 65536 || (i && Y[i] <= Y[i - 1])) return bad("row lines that do not ascend");
+    for (int j = 0; j <= cols; ++j) if (X[j] < 0 || X[j] >= 65536 || (j && X[j] <= X[j - 1])) return bad("column lines that do not ascend");
+    seen.assign((size_t)rows * cols, 0);
+    for (int c = T[6]; c < T[6] + T[7]; ++c) {
+      const int32_t* C = s + kTabCells + 9 * c;
+      if (C[0] != t || C[1] < 0 || C[2] < 0 || C[3] < 1 || C[4] < 1 || C[1] + C[3] > rows || C[2] + C[4] > cols) return bad("a cell out of range");
+      for (int i = C[1]; i < C[1] + C[3]; ++i)
+        for (int j = C[2]; j < C[2] + C[4]; ++j) {
+          if (seen[(size_t)i * cols + j]) return bad("two cells over one base cell");
+          seen[(size_t)i * cols + j] = 1;
+        }
+    }
+    for (uint8_t v : seen) if (!v) return bad("a base cell in no cell");
+    next += T[7];
+  }
+  if (next != nc) return bad("cells that belong to no table");
+  return true;
 }
 
 }  // namespace ttr

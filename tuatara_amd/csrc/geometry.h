@@ -139,6 +139,29 @@ void curve_outline(const float* quad8, int flag, const int64_t* table, float* ou
 // what decode_pages accepts from the device: flag 0 or 1, half bands in 0..32, and with flag 1 every knot's C -+ H inside the int32 pixel range
 bool curve_word_valid(const CurveWord& w);
 
+// Tables (ttr_engine_set_tables; DESIGN.md "Tables").  Ruling lines are found in the page's own pixels, grouped into tables, each table's grid and merged cells
+// derived, and every word given its cell.  The integer steps live in tables_rule.h, shared with table_ink_kernel and table_grid_kernel (tables.hip); the side
+// block's layout (kTabSideInts int32) is described there.  All of it is integer arithmetic; min_len must lie in 16..4096 and ink in 1..255.
+bool tables_args_ok(int min_len, int ink);
+inline size_t tables_bitmap_words(int h, int w) { return (size_t)h * (size_t)((w + 63) / 64); }
+// 1: the ink bitmap of a page u8 [h][w][3] (row stride in bytes): bits [h][ceil(w / 64)] uint64, bit x % 64 of word x / 64, zero beyond w
+void tables_ink(const uint8_t* image, int h, int w, int stride, int ink, uint64_t* bits);
+// 2: the runs of one direction (dir 0: rows, listed in (y, x0) order as {y, x0, x1}; dir 1: columns, in (x, y0) order as {x, y0, y1}) into runs [cap][3];
+// returns their number, or kTabRunCap + 1 when there are more than the cap
+int tables_runs(const uint64_t* bits, int h, int w, int dir, int32_t* runs);
+// 1 - 7 on one page: side receives the block (kTabSideInts int32), runs (may be null) [2][kTabRunCap][3] the run lists, bits (may be null) the bitmap.  Returns
+// the mode: 1, or -(step) of the cap that overflowed (the block then holds the mode alone).
+int tables_from_page(const uint8_t* image, int h, int w, int stride, int min_len, int ink, int32_t* side, int32_t* runs = nullptr, uint64_t* bits = nullptr);
+// 8: {cx, cy} = 64 x the centre of a quad (8 floats): the sums of llrint(16 x) over its corners; then the words' cells, out [n][2] = table, cell (-1, -1 outside)
+void tables_word_centre(const float* quad8, int32_t c[2]);
+void tables_words(const int32_t* side, const int32_t* centres, int n, int32_t* out);
+// what decode_pages accepts from the device: a legal mode, counts within the caps, every index in range, lines ascending, and each table's cells tiling its
+// base grid exactly once.  why (may be null) receives the reason.
+bool tables_side_valid(const int32_t* side, std::string* why = nullptr);
+// the counted part of a block as flat arrays: counts [4] = {rulings, tables, cells, line values}, rulings [..][6], tables [..][8], lines (per table its rows + 1
+// row lines, then its cols + 1 column lines), cells [..][9]; any output may be null
+void tables_export(const int32_t* side, int32_t counts[4], int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells);
+
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.
 struct Component {

@@ -374,6 +374,19 @@ constexpr size_t curve_side_bytes(int N) { return curve_side_table_offset(N) + (
 // them - table null: images / page_bytes / stride / h / w of a uniform batch, else the device page table
 void launch_curve_crop(const CurveIn* words, int N, const uint8_t* images, size_t page_bytes, int stride, int h, int w, const PageRow* table, uint8_t* crops,
                        int rows, int* side, hipStream_t s);
+// ---- tables.hip (DESIGN.md "Tables")
+// The bitmaps of a launch: every page has a slot sized for the launch's largest page (Hcap x Wcap); a page's own rows are ceil(w / 64) (bits) and ceil(h / 64)
+// (bitsT) words apart inside its slot.
+inline size_t tables_bits_slot(int Hcap, int Wcap) { return (size_t)Hcap * (size_t)((Wcap + 63) / 64); }
+inline size_t tables_bitsT_slot(int Hcap, int Wcap) { return (size_t)Wcap * (size_t)((Hcap + 63) / 64); }
+// table_ink_kernel: step 1 on every page.  The pages as the rect packers take them - table null: images / page_bytes / stride / h / w of a uniform batch, else
+// the device page table (Hcap / Wcap then its largest h and w)
+void launch_table_ink(const uint8_t* images, size_t page_bytes, int stride, int h, int w, const PageRow* table, int pages, int Hcap, int Wcap, int ink, uint64_t* bits,
+                      uint64_t* bitsT, hipStream_t s);
+// table_grid_kernel: steps 2 - 8, one workgroup per page.  centres int32 [N][2] and first int32 [pages + 1] (the words of page p are first[p] .. first[p + 1]);
+// runs int32 [pages][2][8192][3] (workspace: the run lists); side int32 [pages][kTabSideInts] (tables_rule.h); items int32 [N][2] = table, cell
+void launch_table_grid(const uint64_t* bits, const uint64_t* bitsT, int h, int w, const PageRow* table, int pages, int Hcap, int Wcap, int min_len, const int* centres,
+                       const int* first, int* runs, int* side, int* items, hipStream_t s);
 // get_detected_boxes' per-component tail on the GPU (tuatara.cpp:162-179: niter, ROI, dilation, findNonZero + minAreaRect): one lane per candidate, geometry.cpp's
 // arithmetic step for step (float32 calipers, double where OpenCV is double) -> CclBuffers::rects.  After launch_ccl on the same stream.
 void launch_ccl_rects(const CclBuffers& b, int pages, int H, int W, hipStream_t s);

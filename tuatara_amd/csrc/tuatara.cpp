@@ -63,11 +63,14 @@ ttr_engine* engine_for(const std::string& weights_dir, int crop_mode = -1, int o
 std::map<ttr_engine*, std::unique_ptr<std::mutex>> g_call_mu;
 thread_local std::string g_call_error;   // last_call_error()
 thread_local int g_call_tiled = 0;       // set_tiled(): the overlap of this thread's calls, 0 = off (then TUATARA_TILED decides)
+thread_local int g_call_tables = 0, g_call_tables_ink = 128;   // set_tables(): min_len and ink of this thread's calls, 0 = off (then TUATARA_TABLES decides)
+thread_local std::vector<TableGrid> g_call_table_out;          // last_call_tables()
 struct CharsetScope {
   ttr_engine* e;
   std::unique_lock<std::mutex> turn;
   bool set = false, ok = true;
   bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false, curved_set = false, fuzzy_set = false, tiled_set = false;
+  bool tables_set = false;
   CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
                std::string pattern = std::string(), float wide = 0.f, bool pattern_best = false, bool curved = false, LexFuzzy fuzzy = LexFuzzy{-1, 0.f}) : e(e_) {
     {
@@ -109,6 +112,13 @@ struct CharsetScope {
       if (ttr_engine_set_tiled(e, tiled) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
       tiled_set = true;
     }
+    int tab = g_call_tables;
+    if (tab == 0) if (const char* p = std::getenv("TUATARA_TABLES")) tab = std::string(p) == "1" ? 48 : std::atoi(p);
+    g_call_table_out.clear();
+    if (tab != 0) {   // tables (DESIGN.md "Tables"): min_len and ink for the call, like the set
+      if (ttr_engine_set_tables(e, tab, g_call_tables_ink) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      tables_set = true;
+    }
     if (!curved) if (const char* p = std::getenv("TUATARA_CURVED")) curved = std::string(p) == "1";
     if (curved) {   // curved words (DESIGN.md "Curved words"): on for the call, like the set
       if (ttr_engine_set_curved(e, 1) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
@@ -135,6 +145,7 @@ struct CharsetScope {
     if (wide_set) ttr_engine_set_wide(e, 0.f);
     if (curved_set) ttr_engine_set_curved(e, 0);
     if (tiled_set) ttr_engine_set_tiled(e, 0);
+    if (tables_set) ttr_engine_set_tables(e, 0, 0);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
     if (alts_set) ttr_engine_set_alternatives(e, 0);
     if (fuzzy_set) ttr_engine_set_lexicon_fuzzy(e, -1, 0.f);
@@ -221,6 +232,9 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
       o.pieces.push_back(std::move(p));
     }
   }
+  const int32_t *it = ttr_result_item_table(r), *ic = ttr_result_item_cell(r);
+  o.table = it ? it[i] : -1;
+  o.cell = ic ? ic[i] : -1;
   o.curved = false; o.outline.clear();
   if (const int32_t* cv = ttr_result_curved(r)) {
     const float* ol = ttr_result_outlines(r);
@@ -273,6 +287,24 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
   }
   std::vector<Item> out(ttr_result_count(r));
   for (size_t i = 0; i < out.size(); ++i) { fill(out[i], r, (int)i); name_matches(e, out[i]); }
+  if (const int32_t* tb = ttr_result_tables(r)) {   // tables: every table as rows x cols strings (last_call_tables())
+    const int32_t* cl = ttr_result_cells(r);
+    for (int t = 0; t < ttr_result_table_count(r); ++t) {
+      TableGrid g;
+      for (int k = 0; k < 4; ++k) g.bbox[k] = tb[8 * t + k];
+      g.rows = tb[8 * t + 4]; g.cols = tb[8 * t + 5];
+      g.text.assign((size_t)g.rows * g.cols, std::string());
+      for (int c = tb[8 * t + 6]; c < tb[8 * t + 6] + tb[8 * t + 7]; ++c) {
+        const int need = ttr_result_cell_text(r, c, nullptr, 0);
+        if (need <= 0) continue;
+        std::string s((size_t)need + 1, '\0');
+        ttr_result_cell_text(r, c, &s[0], need + 1);
+        s.resize((size_t)need);
+        g.text[(size_t)cl[9 * c + 1] * g.cols + cl[9 * c + 2]] = std::move(s);
+      }
+      g_call_table_out.push_back(std::move(g));
+    }
+  }
   ttr_result_free(r);
   return out;
 }
@@ -501,6 +533,9 @@ std::string last_call_error() { return g_call_error; }
 
 void set_tiled(int overlap) { g_call_tiled = overlap; }
 int tiled() { return g_call_tiled; }
+void set_tables(int min_len, int ink) { g_call_tables = min_len; g_call_tables_ink = ink; }
+int tables() { return g_call_tables; }
+std::vector<TableGrid> last_call_tables() { return g_call_table_out; }
 
 std::vector<WordReading> nbest(const OutputItemEx& item, int m) {
   std::vector<WordReading> out;

@@ -273,6 +273,23 @@ SYMBOLS = [
     ("ttr_curve_crop", _I, [_PU8, _I, _I, _I, C.POINTER(C.c_int64), _PU8]),
     ("ttr_curve_outline", _I, [_PF, _I, C.POINTER(C.c_int64), _PF]),
     ("ttr_curve_crops", _I, [_VP, _PU8, _I, _I, _I, _PF, _I, _I, _PI, _PI, _PI, C.POINTER(C.c_int64), _PU8]),
+    ("ttr_engine_set_tables", _I, [_VP, _I, _I]),
+    ("ttr_engine_tables", _I, [_VP, _PI]),
+    ("ttr_result_table_mode", _I, [_VP]),
+    ("ttr_result_ruling_count", _I, [_VP]),
+    ("ttr_result_rulings", _PI, [_VP]),
+    ("ttr_result_table_count", _I, [_VP]),
+    ("ttr_result_tables", _PI, [_VP]),
+    ("ttr_result_table_lines", _PI, [_VP, _PI]),
+    ("ttr_result_cell_count", _I, [_VP]),
+    ("ttr_result_cells", _PI, [_VP]),
+    ("ttr_result_item_table", _PI, [_VP]),
+    ("ttr_result_item_cell", _PI, [_VP]),
+    ("ttr_result_cell_text", _I, [_VP, _I, C.c_char_p, _I]),
+    ("ttr_results_gather_tables", _I, [C.POINTER(_VP), _I, _PI, _PI]),
+    ("ttr_tables_from_page", _I, [_PU8, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI, _PI, _PI, _PI, _PI]),
+    ("ttr_tables_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI, _PI, _PI, _PI, _PI]),
+    ("ttr_dbg_tables", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_uint64), _PI, _PI, _PI]),
     ("ttr_engine_set_tiled", _I, [_VP, _I]),
     ("ttr_engine_tiled", _I, [_VP]),
     ("ttr_result_tiles", _I, [_VP]),
@@ -977,6 +994,61 @@ def _quad_pairs(q8) -> list:
     return [q[0:2], q[2:4], q[4:6], q[6:8]]
 
 
+TABLES_MIN_LEN, TABLES_INK = 48, 128   # what tables=True means (DESIGN.md "Tables": neither value has been tuned on documents)
+
+
+def _tables_arg(tables):
+    """False / None / 0 -> (0, TABLES_INK); True -> the defaults; (min_len, ink) or a bare min_len otherwise"""
+    if tables is None or tables is False or (isinstance(tables, int) and not isinstance(tables, bool) and tables == 0):
+        return 0, TABLES_INK
+    if tables is True:
+        return TABLES_MIN_LEN, TABLES_INK
+    if isinstance(tables, (tuple, list)) and len(tables) == 2:
+        return int(tables[0]), int(tables[1])
+    if isinstance(tables, int):
+        return int(tables), TABLES_INK
+    raise EngineError("tables must be False, True or (min_len, ink)")
+
+
+def _tables_call(fn, image, quads, min_len, ink, row_stride=0):
+    """the shared body of tables_from_page and Engine.tables_page: fn(image..., outputs...) -> the dict both return"""
+    image = np.asarray(image, dtype=np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise RuntimeError("Input array should have 3 dimensions")
+    if not row_stride:
+        image = np.ascontiguousarray(image)
+    q = np.zeros((0, 8), np.float32) if quads is None else np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+    nq, m = len(q), max(len(q), 1)
+    mode, counts = np.zeros(1, np.int32), np.zeros(6, np.int32)
+    rul, tab, lin, cel = np.zeros((512, 6), np.int32), np.zeros((32, 8), np.int32), np.zeros(32 * 130, np.int32), np.zeros((1024, 9), np.int32)
+    it, ic = np.full(m, -1, np.int32), np.full(m, -1, np.int32)
+    fn(_u8(image), image.shape[0], image.shape[1], int(row_stride) or image.shape[1] * 3, int(min_len), int(ink), _f(q), nq, _i(mode), _i(counts), _i(rul), _i(tab), _i(lin),
+       _i(cel), _i(it), _i(ic))
+    return {"mode": int(mode[0]), "rulings": rul[:counts[0]].copy(), "tables": tab[:counts[1]].copy(), "lines": lin[:counts[3]].copy(), "cells": cel[:counts[2]].copy(),
+            "item_table": it[:nq].copy(), "item_cell": ic[:nq].copy(), "runs": (int(counts[4]), int(counts[5]))}
+
+
+def table_line_lists(tables, lines) -> list:
+    """the flat line values of a result split per table: [(row lines i32 [rows + 1], column lines i32 [cols + 1]), ...] in doubled px"""
+    out, k = [], 0
+    for t in np.asarray(tables).reshape(-1, 8):
+        r, c = int(t[4]) + 1, int(t[5]) + 1
+        out.append((np.asarray(lines[k:k + r]), np.asarray(lines[k + r:k + r + c])))
+        k += r + c
+    return out
+
+
+def tables_from_page(image, quads=None, min_len: int = TABLES_MIN_LEN, ink: int = TABLES_INK, row_stride: int = 0) -> dict:
+    """The tables rule on the host (ttr_tables_from_page, no GPU; DESIGN.md "Tables"): a host image u8 [H, W, 3] (row_stride: the bytes from row to row of a
+    view into a wider buffer) and quads f32 [nq, 8] -> {"mode", "rulings" i32 [nr, 6], "tables" i32 [nt, 8], "lines" i32 (per table its row lines, then its
+    column lines, doubled px), "cells" i32 [nc, 9], "item_table" i32 [nq], "item_cell" i32 [nq], "runs": (horizontal, vertical) run counts, 0 for a page beyond a cap}."""
+    lib = load()
+
+    def fn(*a):
+        _lib_check(lib.ttr_tables_from_page(*a))
+    return _tables_call(fn, image, quads, min_len, ink, row_stride)
+
+
 class PageResult(collections.abc.Sequence):
     """One page's words as the list of {"text", "bbox", "ids"} dicts pytuatara.image_to_data returns, materialised on access:
     the batch hand-over keeps the arrays the C ABI filled (`texts`, `bbox` f32 [n,4], `ids` i32 [n,26]; `quad` f32 [n,8] in the
@@ -1007,8 +1079,13 @@ class PageResult(collections.abc.Sequence):
     Curved words (Engine.set_curved(True); DESIGN.md "Curved words"): `curved` i32 [n] (1 = the item's crop was straightened along its spine), `outline` f32
     [n, 18, 2] (the top edge left to right, then the bottom edge right to left) and `spine_knots` i64 [n, 9, 4] the knot tables; dicts gain "curved" and
     "outline"; all None when curved is off.  Tiled pages (Engine.set_tiled(O); DESIGN.md "Tiled pages"): `tiles` = the tiles the page's detector ran as,
-    0 when tiling is off."""
-    __slots__ = ("texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
+    0 when tiling is off.  Tables (Engine.set_tables; DESIGN.md "Tables"): `table_mode` (1, or -(step) of the cap the page overflowed; 0 = off), `rulings` i32
+    [nr, 6] (dir, x0, y0, x1, y1, table), `table_rects` i32 [nt, 8] (box, rows, cols, first cell, cell count), `table_lines` i32 (doubled px), `cells` i32
+    [nc, 9] (table, row, col, rowspan, colspan, box), `item_table` / `item_cell` i32 [n] (dicts gain "table" and "cell", -1 = in no cell), `cell_texts`;
+    `tables` the list of {"bbox", "rows", "cols", "cells": [{"row", "col", "rowspan", "colspan", "bbox", "items", "text"}]} and table_grid(t) its rows x cols
+    strings; rulings is None, tables [] when tables are off and for a page without items."""
+    __slots__ = ("table_mode", "rulings", "table_rects", "table_lines", "cells", "item_table", "item_cell", "cell_texts",
+                 "texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
                  "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad",
                  "block", "line_block", "line_pos", "block_order", "block_first", "block_bbox", "block_mode", "alt_ids", "alt_prob",
@@ -1021,8 +1098,11 @@ class PageResult(collections.abc.Sequence):
                  block=None, line_block=None, line_pos=None, block_order=None, block_first=None, block_bbox=None, block_mode=0,
                  alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None, pattern_logp=None,
                  piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None,
-                 curved=None, outline=None, spine_knots=None, lex_edits=None, lex_band=-1, tiles=0):
+                 curved=None, outline=None, spine_knots=None, lex_edits=None, lex_band=-1, tiles=0,
+                 table_mode=0, rulings=None, table_rects=None, table_lines=None, cells=None, item_table=None, item_cell=None, cell_texts=None):
         self.tiles = tiles
+        self.table_mode, self.rulings, self.table_rects, self.table_lines, self.cells = table_mode, rulings, table_rects, table_lines, cells
+        self.item_table, self.item_cell, self.cell_texts = item_table, item_cell, cell_texts
         self.lex_edits, self.lex_band = lex_edits, lex_band
         self.curved, self.outline, self.spine_knots = curved, outline, spine_knots
         self.piece_first, self.piece_ids, self.piece_prob = piece_first, piece_ids, piece_prob
@@ -1080,7 +1160,34 @@ class PageResult(collections.abc.Sequence):
             d["pieces"] = self.pieces(j)
         if self.curved is not None:
             d["curved"], d["outline"] = int(self.curved[j]), self.outline[j].tolist()
+        if self.item_table is not None:
+            d["table"], d["cell"] = int(self.item_table[j]), int(self.item_cell[j])
         return d
+
+    @property
+    def tables(self) -> list:
+        """the page's tables in order: {"bbox": [x0, y0, x1, y1], "rows", "cols", "cells": [{"row", "col", "rowspan", "colspan", "bbox", "items", "text"}]}"""
+        if self.table_rects is None:
+            return []
+        out = []
+        for t in self.table_rects:
+            cells = []
+            for c in range(int(t[6]), int(t[6]) + int(t[7])):
+                q = self.cells[c]
+                cells.append({"row": int(q[1]), "col": int(q[2]), "rowspan": int(q[3]), "colspan": int(q[4]), "bbox": [int(v) for v in q[5:9]],
+                              "items": [int(i) for i in np.nonzero(self.item_cell == c)[0]], "text": self.cell_texts[c]})
+            out.append({"bbox": [int(v) for v in t[:4]], "rows": int(t[4]), "cols": int(t[5]), "cells": cells})
+        return out
+
+    def table_grid(self, t: int) -> list:
+        """table t as rows x cols strings: a merged cell's text at its first base cell, "" at its others"""
+        if self.table_rects is None or not 0 <= t < len(self.table_rects):
+            raise EngineError("table_grid: no such table")
+        T = self.table_rects[t]
+        grid = [["" for _ in range(int(T[5]))] for _ in range(int(T[4]))]
+        for c in range(int(T[6]), int(T[6]) + int(T[7])):
+            grid[int(self.cells[c][1])][int(self.cells[c][2])] = self.cell_texts[c]
+        return grid
 
     def pieces(self, j: int) -> list:
         """item j's pieces in order: [{"text", "conf", "quad"}, ...] (one, the item itself, when it is not wide)"""
@@ -1188,6 +1295,7 @@ class Engine:
         wide = _wide_arg(overrides.pop("wide", None))                                     # nor this: set_wide, below
         curved = bool(overrides.pop("curved", False))                                     # nor this: set_curved, below
         tiled = _tiled_arg(overrides.pop("tiled", None))                                  # nor this: set_tiled, below
+        tables = _tables_arg(overrides.pop("tables", None))                               # nor this: set_tables, below
         self._lex_words = []
         tuning = {k: overrides.pop(k) for k in list(overrides) if not hasattr(cfg, k)}     # not a config field: a tuning key (below)
         for k, v in overrides.items():
@@ -1215,6 +1323,43 @@ class Engine:
             self.set_curved(True)
         if tiled:
             self.set_tiled(tiled)
+        if tables[0]:
+            self.set_tables(tables)
+
+    def set_tables(self, tables=True):
+        """Find ruling lines, tables, their grids and merged cells in every page's pixels and give every item its cell (ttr_engine_set_tables; DESIGN.md
+        "Tables"): False / 0 = off, True = (48, 128), else (min_len, ink) with min_len in 16..4096 and ink in 1..255 (neither default has been tuned on
+        documents).  Items, order, boxes, text, ids and conf keep their bits.  Raises EngineError, and changes nothing, for other values, between a stream_push
+        and its flush, and with a communicator attached."""
+        min_len, ink = _tables_arg(tables)
+        if self.lib.ttr_engine_set_tables(self.h, min_len, ink) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def tables(self):
+        """(min_len, ink) in force, or None when tables are off"""
+        ink = C.c_int()
+        m = int(self.lib.ttr_engine_tables(self.h, C.byref(ink)))
+        return (m, int(ink.value)) if m else None
+
+    def tables_page(self, image, quads=None, min_len: int = TABLES_MIN_LEN, ink: int = TABLES_INK) -> dict:
+        """ttr_tables_page: table_ink_kernel and table_grid_kernel on a host image u8 [H, W, 3] and host quads f32 [nq, 8], whatever the engine's setting ->
+        the dict tables_from_page returns."""
+        def fn(*a):
+            self._check(self.lib.ttr_tables_page(self.h, *a))
+        return _tables_call(fn, image, quads, min_len, ink)
+
+    def tables_debug(self, image, min_len: int = TABLES_MIN_LEN, ink: int = TABLES_INK, dev_offset: int = 0, dev_stride: int = 0) -> dict:
+        """ttr_dbg_tables: the ink bitmap u64 [H, ceil(W / 64)] and the run lists i32 [n, 3] of both directions as the device formed them; the image is placed
+        dev_offset bytes into a device buffer with dev_stride bytes from row to row (0 = 3 W)."""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise RuntimeError("Input array should have 3 dimensions")
+        h, w = image.shape[:2]
+        bits, runs, nr, mode = np.zeros((h, (w + 63) // 64), np.uint64), np.zeros((2, 8192, 3), np.int32), np.zeros(2, np.int32), np.zeros(1, np.int32)
+        self._check(self.lib.ttr_dbg_tables(self.h, _u8(image), h, w, w * 3, int(dev_offset), int(dev_stride), int(min_len), int(ink),
+                                            bits.ctypes.data_as(C.POINTER(C.c_uint64)), _i(runs), _i(nr), _i(mode)))
+        return {"bits": bits, "runs_h": runs[0, :nr[0]].copy(), "runs_v": runs[1, :nr[1]].copy(), "mode": int(mode[0])}
 
     def set_tiled(self, overlap=True):
         """Read pages larger than the detector canvas at full size, as overlapping tiles whose heat maps are stitched into one page map (ttr_engine_set_tiled;
@@ -1673,6 +1818,23 @@ class Engine:
                     le = self.lib.ttr_result_lex_edits_all(arr[i])
                     lex.update(lex_band=band, lex_edits=np.ctypeslib.as_array(le, (c, M)).copy() if le else np.zeros((0, M), np.int32))
             lex["tiles"] = int(self.lib.ttr_result_tiles(arr[i]))
+            if self.lib.ttr_result_item_table(arr[i]):   # tables: the page's rulings, tables, lines and cells, its items' cells and the cells' texts
+                r = arr[i]
+                nr_, nt_, nc_, nl_ = self.lib.ttr_result_ruling_count(r), self.lib.ttr_result_table_count(r), self.lib.ttr_result_cell_count(r), C.c_int()
+                lp = self.lib.ttr_result_table_lines(r, C.byref(nl_))
+
+                def view(ptr, shape):
+                    return np.ctypeslib.as_array(ptr, shape).copy() if ptr and shape[0] else np.zeros(shape, np.int32)
+                texts_c = []
+                for cc in range(nc_):
+                    need_c = self.lib.ttr_result_cell_text(r, cc, None, 0)
+                    buf_c = C.create_string_buffer(max(need_c, 0) + 1)
+                    self.lib.ttr_result_cell_text(r, cc, buf_c, need_c + 1)
+                    texts_c.append(buf_c.value.decode("latin1"))
+                lex.update(table_mode=int(self.lib.ttr_result_table_mode(r)), rulings=view(self.lib.ttr_result_rulings(r), (nr_, 6)),
+                           table_rects=view(self.lib.ttr_result_tables(r), (nt_, 8)), table_lines=view(lp, (nl_.value,)),
+                           cells=view(self.lib.ttr_result_cells(r), (nc_, 9)), item_table=view(self.lib.ttr_result_item_table(r), (c,)),
+                           item_cell=view(self.lib.ttr_result_item_cell(r), (c,)), cell_texts=texts_c)
             pl = self.lib.ttr_result_pattern_logp(arr[i])
             if pl:                              # patterns in best mode: the page's log-probabilities
                 lex["pattern_logp"] = np.ctypeslib.as_array(pl, (c,)).copy()
