@@ -45,6 +45,9 @@
 // And a keyword-only curved=False on image_to_data: True straightens the crops of words set on an arc along a spine found in the page (DESIGN.md "Curved
 // words"); every dict gains "curved" (bool) and "outline" (18 [x, y] points: the top edge left to right, then the bottom edge right to left).  It turns
 // rectify on.  curved with orient, chars, wide, alts, lexicon, pattern or regions raises ValueError (Engine.set_curved combines with the last four).
+// And a keyword-only deskew=False on image_to_data: deskew=True (max_slope 64, gain 288, ink 128) or deskew=(max_slope, gain, ink) estimates the page's skew on the
+// GPU and reads the page upright (DESIGN.md "Deskew"); boxes and quads are then the upright page's.  A value out of range raises RuntimeError with the engine's
+// message.  last_call_skew() returns the latest call's record (or None), last_call_to_page(points) maps points of its result to the caller's image.
 // And a keyword-only tables=False on image_to_data: tables=True (min_len 48, ink 128) or tables=(min_len, ink) finds ruling lines, tables, grids and merged
 // cells in the page's pixels (DESIGN.md "Tables"); every dict gains "table" and "cell" (-1 / -1 for an item in no cell).  It combines with every keyword but
 // regions (ValueError); a value out of range raises RuntimeError before anything runs.
@@ -266,7 +269,20 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
                                       py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved, py::object lexicon_fuzzy, double lexicon_gap,
-                                      py::object tiled_kw, py::object tables_kw) {
+                                      py::object tiled_kw, py::object tables_kw, py::object deskew_kw) {
+  // deskew=False | True (64, 288, 128) | (max_slope, gain, ink): the page is read upright for this call (DESIGN.md "Deskew"); boxes and quads are the upright page's
+  struct DeskewScope {
+    DeskewScope(int m, int g, int i) { set_deskew(m, g, i); }
+    ~DeskewScope() { set_deskew(0); }
+  };
+  int dsk_m = 0, dsk_g = 288, dsk_i = 128;
+  if (py::isinstance<py::bool_>(deskew_kw)) dsk_m = deskew_kw.cast<bool>() ? 64 : 0;
+  else if (py::isinstance<py::tuple>(deskew_kw) && py::len(deskew_kw) == 3) {
+    const py::tuple t = deskew_kw.cast<py::tuple>();
+    dsk_m = t[0].cast<int>(); dsk_g = t[1].cast<int>(); dsk_i = t[2].cast<int>();
+  } else if (!deskew_kw.is_none()) throw py::type_error("deskew must be False, True or (max_slope, gain, ink)");
+  // (the ranges are the engine's to check: ttr_engine_set_deskew refuses, the call comes back empty and raise_refused raises its message)
+  DeskewScope deskew_scope(dsk_m, dsk_g, dsk_i);
   // tables=False | True (48, 128) | (min_len, ink): tables for this call (DESIGN.md "Tables")
   struct TablesScope {
     TablesScope(int m, int i) { set_tables(m, i); }
@@ -367,7 +383,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
                 : pattern_best ? image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts, true)
                 : image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts);
     }
-    if ((alts || lex || with_pattern) && got.empty()) raise_refused();
+    if ((alts || lex || with_pattern || dsk_m) && got.empty()) raise_refused();
     py::list res;
     for (const auto& item : got) {
       Keys keys{true, conf, false, false, false, false, alts != 0, lex, false, pattern_best};
@@ -398,7 +414,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
             : orient ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
                      : image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
   }
-  if ((alts || lex || !pattern.empty() || tiled_overlap) && items.empty()) raise_refused();
+  if ((alts || lex || !pattern.empty() || tiled_overlap || dsk_m) && items.empty()) raise_refused();
   py::list result;
   Keys keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best};
   keys.lex_edits = band >= 0;
@@ -470,7 +486,19 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, py::arg("tables") = false, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, py::arg("tables") = false, py::arg("deskew") = false, "Extract text and bounding boxes from an image");
+  m.def("last_call_skew", []() -> py::object {
+    const PageSkew s = last_call_skew();
+    if (!s.on) return py::none();
+    py::dict d;
+    d["slope"] = s.slope; d["found"] = s.found; d["C"] = s.C; d["S"] = s.S; d["w"] = s.w; d["h"] = s.h; d["mode"] = s.mode; d["degrees"] = s.degrees;
+    return d;
+  }, "The skew record of this thread's latest image_to_data call (DESIGN.md \"Deskew\"), or None when deskew was off");
+  m.def("last_call_to_page", [](std::vector<std::pair<float, float>> pts) {
+    const PageSkew s = last_call_skew();
+    for (auto& p : pts) { float x = 0.f, y = 0.f; s.to_page(p.first, p.second, &x, &y); p = {x, y}; }
+    return pts;
+  }, py::arg("points"), "Points (x, y) of the latest call's result -> the caller's image (the identity when deskew was off)");
   m.def("images_to_data", &images_to_data_wrapper, py::arg("images"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
         py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("mixed_batches") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("pattern_best") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, "image_to_data over a sequence of images of any sizes: one list of {text, bbox} per image, in input order");

@@ -5,7 +5,8 @@ result, and save an annotated copy (the reference's three panels: boxes on the p
 (the reference draws with cv2 and opens a window; neither is needed for the results).
 
   python bindings/run_ocr.py [--rectify] [--curved] [image] [weights_dir] [outputs_dir]   (--rectify: deskewed crops, words drawn as their quads;
-  --curved: words set on an arc are straightened along their spines and drawn as their 18-point outlines; --tables: every item carries its table and cell, and
+  --curved: words set on an arc are straightened along their spines and drawn as their 18-point outlines; --deskew: the page's skew is estimated and the page read upright; every box is mapped
+  back through the call's own record (pytuatara.last_call_skew / last_call_to_page; DESIGN.md "Deskew") and drawn on the caller's image; --tables: every item carries its table and cell, and
   the page's rulings and cells are drawn over the first panel - the geometry from the host rule tuatara_amd.engine.tables_from_page, which the engine's kernels
   equal bit for bit)
 """
@@ -73,8 +74,8 @@ def annotate(image: np.ndarray, result, by_lines: bool = False, by_blocks: bool 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     rectify, lines, chars, blocks, curved = "--rectify" in argv, "--lines" in argv, "--chars" in argv, "--blocks" in argv, "--curved" in argv
-    tables = "--tables" in argv
-    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks", "--curved", "--tables")]
+    tables, deskew = "--tables" in argv, "--deskew" in argv
+    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks", "--curved", "--tables", "--deskew")]
     image_path = argv[0] if len(argv) > 0 else os.path.join(HERE, "..", "tests", "data", "funsd_0001129658.png")
     weights_dir = argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "weights")
     outputs_dir = argv[2] if len(argv) > 2 else os.path.join(HERE, "..", "outputs")
@@ -92,6 +93,8 @@ def main(argv=None):
         kw["curved"] = True
     if tables:                      # (DESIGN.md "Tables": min_len 48, ink 128)
         kw["tables"] = True
+    if deskew:                      # (DESIGN.md "Deskew": max_slope 64, gain 288, ink 128; the result is in the upright page's frame)
+        kw["deskew"] = True
     result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir, **kw)
     print(result)
     os.makedirs(outputs_dir, exist_ok=True)
@@ -106,6 +109,13 @@ def main(argv=None):
             d.rectangle([int(c[5]), int(c[6]), int(c[7]), int(c[8])], outline=(0, 160, 255), width=2)
         for r in t["rulings"]:
             d.rectangle([int(r[1]), int(r[2]), int(r[3]), int(r[4])], outline=(255, 0, 255) if r[5] >= 0 else (255, 160, 0))
+    if deskew:                      # every item's box mapped back to the caller's image through the call's own record and drawn there, over the first panel
+        skew = pytuatara.last_call_skew()
+        print(f"# page 0 slope {skew['slope']} degrees {skew['degrees']:.4f}")
+        d = ImageDraw.Draw(out)
+        for item in result:
+            x0, y0, x1, y1 = item["bbox"]
+            d.polygon(pytuatara.last_call_to_page([(x0, y0), (x1, y0), (x1, y1), (x0, y1)]), outline=(0, 200, 0))
     out.save(os.path.join(outputs_dir, stem + "_annotated_with_ocr_results.png"))
     return result
 

@@ -43,6 +43,9 @@
 //   ocr_cli --tiled [O] ...   in front of any form above that runs the detector, options included: a page larger than the detector canvas is read at full size,
 // as overlapping tiles whose heat maps are stitched into one page map (DESIGN.md "Tiled pages"); O = the overlap in pixels, a multiple of 32 in [64, 256]
 // (default 128, not tuned on documents).  A page of more than 64 tiles or with a side above 8192 fails with the rule's message.
+//   ocr_cli --deskew [MAX_SLOPE] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: the page's skew is estimated on the GPU and the page read
+// upright (DESIGN.md "Deskew"; MAX_SLOPE = the largest slope tried, px per 512 px, 1..128, default 64, not tuned on documents); prints "# page 0 slope S degrees D
+// found F" and then the plain form's lines, the boxes in the upright page's frame, each followed by a tab and the box's first corner on the caller's image.
 //   ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: finds ruling lines, tables, grids and merged cells in the
 // page's pixels (DESIGN.md "Tables"; MIN_LEN = the shortest ruling in px, 16..4096, default 48, not tuned on documents) and prints each table as "# table T x0 y0
 // x1 y1 rows cols" followed by its rows, the cells' texts separated by tabs (a merged cell's text at its first base cell; a line break inside a cell as " / ").
@@ -146,6 +149,29 @@ int main(int argc, const char** argv) {
         printf("%g %g %g %g\t%.6f\t%s\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.conf, it.text.c_str());
         if (it.pieces.size() > 1)
           for (const WordPiece& p : it.pieces) printf("\t|%.6f %s\n", p.conf, p.text.c_str());
+      }
+      return 0;
+    }
+    if (argc >= 2 && std::string(argv[1]) == "--deskew") {
+      int max_slope = 64, used = 1;
+      if (argc == 6) {
+        char* end = nullptr;
+        const long v = std::strtol(argv[2], &end, 10);
+        if (!end || *end || v < 1 || v > 128) throw std::runtime_error("--deskew takes a largest slope in 1..128 px per 512 px (default 64)");
+        max_slope = (int)v; used = 2;
+      }
+      if (argc - used != 4) throw std::runtime_error("--deskew [MAX_SLOPE] goes in front of <image.png> <weights_dir> <outputs_dir>");
+      pngdec::Image img = pngdec::read(argv[used + 1]);
+      set_deskew(max_slope);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[used + 2], argv[used + 3], false);
+      set_deskew(0);
+      if (!last_call_error().empty()) return 1;                         // (the message is on stderr)
+      const PageSkew sk = last_call_skew();
+      printf("# page 0 slope %d degrees %.4f found %d\n", sk.slope, sk.degrees, sk.found);
+      for (const OutputItemEx& it : items) {
+        float px = 0.f, py = 0.f;
+        sk.to_page(it.bbox[0], it.bbox[1], &px, &py);
+        printf("%g %g %g %g\t%s\t%.9g %.9g\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.text.c_str(), px, py);
       }
       return 0;
     }
@@ -357,7 +383,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir> | ocr_cli [--tiled [O]] [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli --deskew [MAX_SLOPE] <image.png> <weights_dir> <outputs_dir> | ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir> | ocr_cli [--tiled [O]] [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

@@ -269,6 +269,22 @@ void set_tables(int min_len, int ink = 128);
 int tables();
 std::vector<TableGrid> last_call_tables();
 
+// Deskew (opt-in; DESIGN.md "Deskew"): the page's skew is estimated on the GPU and a page found tilted is read upright; every box and quad of the result is then
+// in the upright page's frame.  set_deskew(max_slope, gain, ink) turns it on for every call of THIS THREAD that follows (max_slope 1..128 px per 512 px, gain
+// 256..65535 in 1/256ths, ink 1..255; the other layers use 64, 288 and 128, which nobody has tuned on documents), set_deskew(0) off again; with it off,
+// TUATARA_DESKEW=MAX_SLOPE (or 1 for 64) in the environment turns it on for every call here.  It is set on the cached engine for the call and reset afterwards.
+// A bad value: the message is printed and the result is empty (last_call_error()).  last_call_skew(): the record of this thread's latest single-image call
+// (on = false when the layer was off); to_page maps a point of the result to the caller's image.
+struct PageSkew {
+  bool on = false;
+  int slope = 0, found = 0, C = 65536, S = 0, w = 0, h = 0, mode = 0;
+  double degrees = 0.0;              // atan(slope / 512)
+  void to_page(float x, float y, float* xs, float* ys) const;   // (ttr_skew_to_page; the identity when the layer was off)
+};
+void set_deskew(int max_slope, int gain = 288, int ink = 128);
+int deskew();
+PageSkew last_call_skew();
+
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)
 #include <opencv2/core.hpp>

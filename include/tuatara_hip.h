@@ -756,6 +756,42 @@ int ttr_tables_from_page(const uint8_t* img, int h, int w, int row_stride, int m
                          int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell);
 int ttr_tables_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq, int32_t* mode,
                     int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell);
+/* ---- deskew (opt-in; DESIGN.md "Deskew") ---------------------------------------------------------
+ * With ttr_engine_set_deskew(e, max_slope, gain, ink) every page of a page call has its skew estimated on the GPU from its own pixels (table_ink_kernel's bitmap,
+ * deskew_score_kernel: one workgroup per page and candidate slope) and is resampled upright about its centre, at its own size, into an engine-owned buffer
+ * (deskew_rotate_kernel) before the detector reads it.  Everything behind - boxes, quads, text, lines, blocks, characters, tables, wide and curved words - is
+ * exactly what the same call returns for that upright page with the layer off, in the upright page's coordinates; ttr_result_to_page maps points back to the
+ * caller's page.  A page found straight (slope 0) keeps every byte.  max_slope = 0 is off (the default: nothing runs), else max_slope in 1..128 - candidate
+ * slopes are k in -max_slope..max_slope, a text line dropping k px per 512 px to the right, 128 = 14 degrees -, gain in 256..65535 (in 1/256ths: a page is
+ * turned only when score[found] * 256 >= score[0] * gain) and ink in 1..255 (as for tables).  The convenience layers use 64, 288 and 128; none of them has been
+ * tuned on documents.  The setter refuses while streamed batches are in flight and with a communicator attached; ttr_engine_attach_comm and
+ * ttr_pages_to_data_dev_sharded refuse while it is on; a page call refuses a page with a side of 8192 px or more.  Region calls run as before and report slope 0.
+ *   ttr_engine_deskew          max_slope in force (0 = off); gain and ink through the pointers (may be NULL)
+ *   ttr_result_skew            the page's record (a ttr_result is one page); returns 1, or 0 when the result carries none (the layer was off)
+ *   ttr_result_to_page         n points (x, y) of the upright page -> the caller's page: xs = (w-1)/2 + (C (x - (w-1)/2) - S (y - (h-1)/2)) / 65536 and
+ *                              ys = (h-1)/2 + (S (x - ..) + C (y - ..)) / 65536, in double, rounded to float; the identity for a result without a record;
+ *                              xy_out may be xy_in.  Returns 0, -1 on a null argument
+ *   ttr_skew_to_page           the same map from a record alone (C, S, w, h are read): what every binding's map back calls
+ *   ttr_results_gather_skew    the records of n results back to back (zeroes where a result has none); returns the number of pages that were resampled
+ * ttr_deskew_from_page: the rule on the host, no engine.  A host image u8 [h][w][3] (row_stride bytes, 0 = 3 w; the rule treats the three channels alike, so
+ * either channel order gives the same record) -> out_img [h][w][3] tightly packed, rec, scores [2 max_slope + 1] (slope k at k + max_slope); any output may be
+ * NULL.  Returns 0, -1 with the message in ttr_last_error (an argument outside its range, a page side of 8192 or more).
+ * ttr_deskew_page (stage; refuses while batches stream): the same through the kernels, whatever the engine's setting. */
+typedef struct ttr_skew {
+  int32_t slope, found;        /* the slope the page was turned by (0: left as it was); the slope of the largest score */
+  int32_t C, S;                /* llrint(65536 cos), llrint(65536 sin) of slope */
+  int32_t w, h;
+  int32_t mode, reserved;      /* 1 resampled, 0 left as it was */
+  uint64_t score0, score_found;
+} ttr_skew;
+int ttr_engine_set_deskew(ttr_engine* e, int max_slope, int gain, int ink);
+int ttr_engine_deskew(const ttr_engine* e, int* gain, int* ink);
+int ttr_result_skew(const ttr_result* r, ttr_skew* rec);
+int ttr_result_to_page(const ttr_result* r, const float* xy_in, int n, float* xy_out);
+int ttr_skew_to_page(const ttr_skew* rec, const float* xy_in, int n, float* xy_out);   /* the same map from a record alone (C, S, w, h are read) */
+int ttr_results_gather_skew(ttr_result* const* rs, int n, ttr_skew* recs);
+int ttr_deskew_from_page(const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink, uint8_t* out_img, ttr_skew* rec, uint64_t* scores);
+int ttr_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink, uint8_t* out_img, ttr_skew* rec, uint64_t* scores);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

@@ -1644,6 +1644,99 @@ int ttr_tables_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_str
   TTR_GUARD_END(-1)
 }
 
+// ---- deskew (DESIGN.md "Deskew")
+static_assert(sizeof(ttr_skew) == sizeof(DeskewRec) && offsetof(ttr_skew, score0) == offsetof(DeskewRec, score0) && offsetof(ttr_skew, mode) == offsetof(DeskewRec, mode),
+              "ttr_skew is the engine's record");
+
+int ttr_engine_set_deskew(ttr_engine* e, int max_slope, int gain, int ink) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (max_slope != 0 && !dsk_args_ok(max_slope, gain, ink))
+    throw std::runtime_error("ttr_engine_set_deskew: max_slope must be 0 (off) or lie in 1..128, gain in 256..65535 and ink in 1..255, got " + std::to_string(max_slope) + ", " +
+                             std::to_string(gain) + " and " + std::to_string(ink));
+  E.refuse_while_streaming("ttr_engine_set_deskew");
+  if (max_slope && E.comm) throw std::runtime_error("ttr_engine_set_deskew: pages are straightened by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
+  if (max_slope) (void)E.deskew_consts_dev();   // the (C, S) table: formed here, on the host, and handed to the kernels
+  E.deskew_M = max_slope;
+  if (max_slope) { E.deskew_gain = gain; E.deskew_ink = ink; }
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_deskew(const ttr_engine* e, int* gain, int* ink) {
+  if (!e) return 0;
+  if (gain) *gain = e->e->deskew_gain;
+  if (ink) *ink = e->e->deskew_ink;
+  return e->e->deskew_M;
+}
+
+int ttr_result_skew(const ttr_result* r, ttr_skew* rec) {
+  if (!r || !r->r.skew_on) return 0;
+  if (rec) memcpy(rec, &r->r.skew, sizeof *rec);
+  return 1;
+}
+
+int ttr_skew_to_page(const ttr_skew* rec, const float* xy_in, int n, float* xy_out) {
+  if (!rec || n < 0 || (n > 0 && (!xy_in || !xy_out))) return -1;
+  DeskewRec d;
+  memcpy(&d, rec, sizeof d);
+  deskew_to_page(d, xy_in, n, xy_out);
+  return 0;
+}
+
+int ttr_result_to_page(const ttr_result* r, const float* xy_in, int n, float* xy_out) {
+  if (!r || n < 0 || (n > 0 && (!xy_in || !xy_out))) return -1;
+  if (!r->r.skew_on) { if (xy_out != xy_in) memmove(xy_out, xy_in, (size_t)n * 8); return 0; }
+  deskew_to_page(r->r.skew, xy_in, n, xy_out);
+  return 0;
+}
+
+int ttr_results_gather_skew(ttr_result* const* rs, int n, ttr_skew* recs) {
+  if (!rs || n < 0) return -1;
+  int turned = 0;
+  for (int i = 0; i < n; ++i) {
+    const bool has = rs[i] && rs[i]->r.skew_on;
+    if (recs) { if (has) memcpy(recs + i, &rs[i]->r.skew, sizeof(ttr_skew)); else memset(recs + i, 0, sizeof(ttr_skew)); }
+    turned += has && rs[i]->r.skew.mode == 1;
+  }
+  return turned;
+}
+
+static void deskew_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink) {
+  if (!img) throw std::runtime_error("null argument");
+  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
+  if (h >= kDskSideCap || w >= kDskSideCap) throw std::runtime_error(std::string(what) + ": a page side of 8192 px or more");
+  if (!dsk_args_ok(max_slope, gain, ink))
+    throw std::runtime_error(std::string(what) + ": max_slope must lie in 1..128, gain in 256..65535 and ink in 1..255, got " + std::to_string(max_slope) + ", " + std::to_string(gain) +
+                             " and " + std::to_string(ink));
+}
+
+int ttr_deskew_from_page(const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink, uint8_t* out_img, ttr_skew* rec, uint64_t* scores) {
+  TTR_GUARD_BEGIN
+  deskew_in_ok("ttr_deskew_from_page", img, h, w, row_stride, max_slope, gain, ink);
+  DeskewRec r;
+  deskew_from_page(img, h, w, row_stride ? row_stride : w * 3, max_slope, gain, ink, out_img, w * 3, &r, scores);
+  if (rec) memcpy(rec, &r, sizeof r);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink, uint8_t* out_img, ttr_skew* rec, uint64_t* scores) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  deskew_in_ok("ttr_deskew_page", img, h, w, row_stride, max_slope, gain, ink);
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_deskew_page");
+  DeskewRec r;
+  E.deskew_stage(img, h, w, row_stride, 0, 0, max_slope, gain, ink, out_img, w * 3, &r, scores);
+  if (rec) memcpy(rec, &r, sizeof r);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_result_alt_k(const ttr_result* r) { return r ? r->r.alt_k : 0; }
 
 const int32_t* ttr_result_alt_ids(const ttr_result* r, int i) { return r && !r->r.alt_ids.empty() ? &r->r.alt_ids[(size_t)26 * r->r.alt_k * (size_t)i] : nullptr; }

@@ -701,6 +701,21 @@ int ttr_dbg_tables(ttr_engine* e, const uint8_t* img, int h, int w, int row_stri
   TTR_GUARD_END(-1)
 }
 
+// deskew (DESIGN.md "Deskew"): the stage call with the image placed anywhere in a device buffer
+int ttr_dbg_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int max_slope, int gain, int ink, uint8_t* out_img,
+                   ttr_skew* rec, uint64_t* scores) {
+  TTR_GUARD_BEGIN
+  if (!e || !img) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_dbg_deskew_page");
+  DeskewRec r;
+  E.deskew_stage(img, h, w, row_stride, dev_offset, dev_stride, max_slope, gain, ink, out_img, w * 3, &r, scores);
+  if (rec) memcpy(rec, &r, sizeof r);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_dbg_orient_quad(const float* r5, int h, int w, int crop_mode, int turn, float* quad8, int64_t* fixed6) {
   TTR_GUARD_BEGIN
   if (turn < 0 || turn > 3 || (crop_mode != TTR_CROP_BOUNDING && crop_mode != TTR_CROP_RECTIFIED)) throw std::runtime_error("bad turn or crop_mode");

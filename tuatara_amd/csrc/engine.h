@@ -47,6 +47,7 @@
 
 #include "../../include/tuatara_hip_debug.h"
 #include "common.h"
+#include "deskew_rule.h"
 #include "geometry.h"
 #include "host_util.h"
 #include "kernels.h"
@@ -347,6 +348,10 @@ struct Result {
   std::vector<float> block_bbox;                 // 4 per block: min / max of the member lines' bbox
   int n_blocks = 0, block_mode = 0;              // block_mode 1: ordered by the precedence relation; 0: more than 512 blocks, by key alone
   int tiles = 0;                                 // tiled pages (ttr_engine_set_tiled; DESIGN.md "Tiled pages"): the tiles the page's detector ran as, 0 when off
+  // deskew (ttr_engine_set_deskew; DESIGN.md "Deskew"): skew_on 0 when the layer was off; else the page's record - every coordinate of this result is in the
+  // upright page's frame, and deskew_to_page maps it to the caller's (a region call: slope 0, the identity)
+  int skew_on = 0;
+  DeskewRec skew{};
   std::string block_text(int b) const;           // the block's lines joined by '\n'
   std::string page_text_blocks() const;          // the blocks in reading order, joined by "\n\n"
 };
@@ -470,6 +475,15 @@ struct Engine {
   // tiled pages (ttr_engine_set_tiled; DESIGN.md "Tiled pages"): the tiles' overlap in pixels, 0 = off.  On, a page keeps its own scale (ratio 1, page canvas
   // c32(h) x c32(w)); one larger than the detector canvas goes through CRAFT as overlapping tiles whose maps tile_stitch_kernel joins into `heat`
   int tiled = 0;
+  // deskew (ttr_engine_set_deskew; DESIGN.md "Deskew"): max_slope 1..128, 0 = off; the gate in 1/256ths; the ink threshold.  On, detect_enqueue estimates every
+  // page's skew and redirects the batch's pages to upright copies in dsk_pages[slot]; everything behind reads those
+  int deskew_M = 0, deskew_gain = 288, deskew_ink = 128;
+  DevBuf dsk_bits, dsk_bitsT, dsk_scores, dsk_rec; // ... workspaces: the ink bitmaps (tables.hip's pixel pass), scores [pages][2 M + 1], the records [pages]
+  DevBuf dsk_cs;                                  // ... the (C, S) table [257][2], uploaded once
+  bool dsk_cs_up = false;
+  std::vector<int32_t> dsk_cs_host;               // ... and on the host: what decode_pages checks a record's constants against
+  DevBuf dsk_table[2], dsk_pages[2];              // ... per slot: the source and upright pages' rows [2][pages] (page_table.h), and the upright pages themselves
+  PinnedBuf h_dsk_table[2], h_dsk[2];             // ... per slot: the rows' staging, and the records' host copy
   DevBuf tile_heat;                               // ... the tile canvases' maps [n T][Hc / 2][Wc / 2][2] (allocated by the first tiled batch)
   DevBuf tile_table[2];                           // ... the tiles as rows of a second page table, per slot (the packers go on reading page_table: the real pages)
   PinnedBuf h_tile_table[2];
@@ -879,6 +893,8 @@ struct Engine {
     // tables (DESIGN.md "Tables"): the engine's setting when the boxes were made (0 = off, and for region calls), and 64 x every word's centre [N][2]
     int tab_min_len = 0, tab_ink = 0;
     std::vector<int32_t> tab_centres;
+    std::vector<DeskewRec> dsk_recs;   // deskew: the pages' records as the device wrote them (detect_collect_local takes them from the slot's pinned copy)
+    int dsk_M = 0;                     // deskew: max_slope when the detector was enqueued (0 = off, and for region calls); the pages of the batch are then upright copies
     int tiles = 0;                     // tiled pages: tiles per page (0 = the engine's tiling was off when the detector was enqueued), and their plan
     TilePlan plan{};
     int det_groups = -1;               // CCL groups enqueued for it (group_ev[det_groups]: behind the copy of its detector range word)
@@ -938,6 +954,13 @@ struct Engine {
   void tables_enqueue(const PageBatch& B, int sl);
   // the stage form (ttr_tables_page, and the developer hook): a host image, placed dev_offset bytes into a device buffer with dev_stride bytes from row to row
   // (0 = 3 w), and host quads through table_ink_kernel and table_grid_kernel -> side [kTabSideInts], items [nq][2], bits [h][ceil(w / 64)], runs [2][8192][3]
+  // deskew: ink, scores, choice and resampling of batch B's pages ahead of its resize, on `stream`; redirects B.pages to the slot's upright copies
+  void deskew_enqueue(PageBatch& B);
+  const int* deskew_consts_dev();     // the (C, S) table on the device (uploaded by the first call)
+  // the stage form (ttr_deskew_page, and the tests): a host image, placed dev_offset bytes into a device buffer with dev_stride bytes from row to row (0 = 3 w),
+  // through the pixel pass and the two kernels -> out [h][w][3] (out_stride bytes from row to row), the record, scores [2 max_slope + 1]; any may be null
+  void deskew_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int max_slope, int gain, int ink, uint8_t* out, int out_stride,
+                    DeskewRec* rec, uint64_t* scores);
   void tables_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_len, int ink, const float* quads, int nq, int32_t* side_out,
                     int32_t* items_out, uint64_t* bits_out, int32_t* runs_out);
   // the stage form (ttr_curve_crops): a host image and host quads through the kind-1 packer and curve_crop_kernel -> flag [nq], hb [nq][2], spine [nq][2][9],

@@ -218,6 +218,82 @@ void Engine::upload_tile_table(const PageBatch& B, int sl) {
   TTR_HIP_CHECK(hipMemcpyAsync(tile_table[sl].p, rows, bytes, hipMemcpyHostToDevice, stream));   // (read by this batch's resize alone, on this stream)
 }
 
+const int* Engine::deskew_consts_dev() {
+  if (!dsk_cs_up) {
+    std::vector<int32_t>& cs = dsk_cs_host;
+    cs.assign(2 * kDskSlopes, 0);
+    deskew_consts(cs.data());
+    dsk_cs.ensure(cs.size() * 4);
+    TTR_HIP_CHECK(hipMemcpy(dsk_cs.p, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));   // (once per engine, from the setter or a stage call: not on the detector's path)
+    dsk_cs_up = true;
+  }
+  return dsk_cs.as<int>();
+}
+
+void Engine::deskew_enqueue(PageBatch& B) {
+  const int n = B.n, sl = B.slot & 1, M = B.dsk_M;
+  int Hcap = 0, Wcap = 0;
+  for (const Page& P : B.pages) { Hcap = std::max(Hcap, P.h); Wcap = std::max(Wcap, P.w); }
+  // the upright copies: a uniform batch keeps its form (pages h w 3 bytes apart, rows 3 w), a mixed one gets tight pages at 256-byte offsets
+  std::vector<size_t> off((size_t)n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    const size_t bytes = (size_t)B.pages[i].h * B.pages[i].w * 3;
+    off[(size_t)i + 1] = B.mixed ? (off[(size_t)i] + bytes + 255) & ~(size_t)255 : off[(size_t)i] + bytes;
+  }
+  const size_t rows_b = (size_t)2 * n * sizeof(PageRow), rec_b = (size_t)n * sizeof(DeskewRec);
+  dsk_pages[sl].ensure(off[(size_t)n]); dsk_table[sl].ensure(rows_b); h_dsk_table[sl].ensure(rows_b); h_dsk[sl].ensure(rec_b);
+  dsk_bits.ensure(tables_bits_slot(Hcap, Wcap) * 8 * n); dsk_bitsT.ensure(tables_bitsT_slot(Hcap, Wcap) * 8 * n);
+  dsk_scores.ensure((size_t)n * (2 * M + 1) * 8); dsk_rec.ensure(rec_b);
+  if (!dsk_cs_up) throw std::logic_error("deskew: the constants table was not uploaded");
+  PageRow* rows = h_dsk_table[sl].as<PageRow>();
+  for (int i = 0; i < n; ++i) {
+    const Page& P = B.pages[i];
+    rows[i] = PageRow{P.data, P.h, P.w, P.stride, 0, ResizeGeom{}};
+    rows[n + i] = PageRow{dsk_pages[sl].as<uint8_t>() + off[(size_t)i], P.h, P.w, P.w * 3, 0, ResizeGeom{}};
+  }
+  // the slot's previous batch: its packers and page layers may still read the slot's upright pages on the recogniser's stream (a no-op before the first)
+  TTR_HIP_CHECK(hipStreamWaitEvent(stream, done_ev[sl], 0));
+  TTR_HIP_CHECK(hipMemcpyAsync(dsk_table[sl].p, rows, rows_b, hipMemcpyHostToDevice, stream));
+  const PageRow* src = dsk_table[sl].as<PageRow>();
+  launch_table_ink(nullptr, 0, 0, 0, 0, src, n, Hcap, Wcap, deskew_ink, dsk_bits.as<uint64_t>(), dsk_bitsT.as<uint64_t>(), stream);   // step 1: the source pages' ink
+  launch_deskew_score(dsk_bits.as<uint64_t>(), src, n, Hcap, Wcap, M, dsk_scores.as<uint64_t>(), stream);
+  launch_deskew_rotate(src, src + n, n, Hcap, Wcap, M, deskew_gain, dsk_scores.as<uint64_t>(), dsk_cs.as<int>(), dsk_rec.as<DeskewRec>(), stream);
+  TTR_HIP_CHECK(hipMemcpyAsync(h_dsk[sl].p, dsk_rec.p, rec_b, hipMemcpyDeviceToHost, stream));   // the records: complete before the batch's components are (same stream, ahead of the detector)
+  for (int i = 0; i < n; ++i) { B.pages[i].data = rows[n + i].data; B.pages[i].stride = B.pages[i].w * 3; }
+}
+
+void Engine::deskew_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int max_slope, int gain, int ink, uint8_t* out, int out_stride,
+                          DeskewRec* rec, uint64_t* scores) {
+  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("ttr_deskew_page: bad image size");
+  if (h >= kDskSideCap || w >= kDskSideCap) throw std::runtime_error("ttr_deskew_page: a page side of 8192 px or more");
+  if (!dsk_args_ok(max_slope, gain, ink)) throw std::runtime_error("ttr_deskew_page: max_slope must lie in 1..128, gain in 256..65535 and ink in 1..255");
+  const int ds = dev_stride ? dev_stride : w * 3;
+  if (dev_offset < 0 || ds < w * 3 || (out && out_stride < w * 3)) throw std::runtime_error("ttr_deskew_page: bad device offset or stride");
+  const size_t img_b = (size_t)dev_offset + (size_t)ds * h, out_b = (size_t)h * w * 3, nsc = (size_t)2 * max_slope + 1;
+  staging_img.ensure(img_b); dsk_pages[0].ensure(out_b); dsk_table[0].ensure(2 * sizeof(PageRow));
+  dsk_bits.ensure(tables_bits_slot(h, w) * 8); dsk_bitsT.ensure(tables_bitsT_slot(h, w) * 8); dsk_scores.ensure(nsc * 8); dsk_rec.ensure(sizeof(DeskewRec));
+  const int* cs = deskew_consts_dev();
+  uint8_t* d_img = staging_img.as<uint8_t>() + dev_offset;
+  const PageRow rows[2] = {PageRow{d_img, h, w, ds, 0, ResizeGeom{}}, PageRow{dsk_pages[0].as<uint8_t>(), h, w, w * 3, 0, ResizeGeom{}}};
+  TTR_HIP_CHECK(hipMemcpy2DAsync(d_img, (size_t)ds, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(dsk_table[0].p, rows, sizeof rows, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));                        // (rows is on the stack)
+  const PageRow* src = dsk_table[0].as<PageRow>();
+  launch_table_ink(nullptr, 0, 0, 0, 0, src, 1, h, w, ink, dsk_bits.as<uint64_t>(), dsk_bitsT.as<uint64_t>(), stream);
+  launch_deskew_score(dsk_bits.as<uint64_t>(), src, 1, h, w, max_slope, dsk_scores.as<uint64_t>(), stream);
+  launch_deskew_rotate(src, src + 1, 1, h, w, max_slope, gain, dsk_scores.as<uint64_t>(), cs, dsk_rec.as<DeskewRec>(), stream);
+  DeskewRec r{};
+  std::vector<uint64_t> sc(nsc);
+  TTR_HIP_CHECK(hipMemcpyAsync(&r, dsk_rec.p, sizeof r, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(sc.data(), dsk_scores.p, nsc * 8, hipMemcpyDeviceToHost, stream));
+  if (out) TTR_HIP_CHECK(hipMemcpy2DAsync(out, (size_t)out_stride, dsk_pages[0].p, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  std::string why;
+  if (!deskew_rec_valid(r, max_slope, h, w, dsk_cs_host.data(), &why)) throw std::runtime_error("ttr_deskew_page: the record holds " + why);
+  if (rec) *rec = r;
+  if (scores) std::copy(sc.begin(), sc.end(), scores);
+}
+
 void Engine::detect_enqueue(PageBatch& B) {
   range_use(kRangeDet0 + (B.slot & 1));   // the detector's kernels of this batch watch its own word (engine.h)
   if (!B.mixed) {                         // a uniform batch: every page is its entry point's scalars
@@ -232,6 +308,14 @@ void Engine::detect_enqueue(PageBatch& B) {
   if (tables_min_len)                     // tables: the rule's coordinates are below 32768 (likewise before anything is enqueued)
     for (const Page& P : B.pages)
       if (P.h >= 32768 || P.w >= 32768) throw std::runtime_error("tables: a page side of 32768 px or more: ttr_engine_set_tables(e, 0, 0) first");
+  // Deskew (DESIGN.md "Deskew"): every page's skew is estimated and the batch's pages become upright copies in the slot's buffer; everything below and behind
+  // reads B.pages as ever.  Off: nothing here runs.
+  B.dsk_M = deskew_M;
+  if (B.dsk_M) {
+    for (const Page& P : B.pages)
+      if (P.h >= kDskSideCap || P.w >= kDskSideCap) throw std::runtime_error("deskew: a page side of 8192 px or more: ttr_engine_set_deskew(e, 0, 0, 0) first");
+    deskew_enqueue(B);
+  }
   const Page& P0 = B.pages[0];
   B.H = P0.g.h32; B.W = P0.g.w32; B.H2 = B.H / 2; B.W2 = B.W / 2;
   const int n = B.n, H = B.H, W = B.W, H2 = B.H2, W2 = B.W2;
@@ -394,6 +478,9 @@ void Engine::detect_collect_local(PageBatch& B) {
   B.tab_min_len = tables_min_len; B.tab_ink = tables_ink; B.tab_centres.clear();   // tables: fixed for the batch here (the setter refuses while batches stream)
   std::vector<float> tq;
   for (int gi = 0; gi < groups; ++gi) ccl_collect(gi * GP, std::min(GP, n - gi * GP), gi, B.H2, B.W2, dets);
+  // deskew: the batch's records were copied ahead of its detector on the same stream, so they are here; taken now, before the slot's next batch overwrites them
+  B.dsk_recs.clear();
+  if (B.dsk_M) B.dsk_recs.assign(h_dsk[B.slot & 1].as<DeskewRec>(), h_dsk[B.slot & 1].as<DeskewRec>() + n);
   // the detector's range word of THIS batch, before any of its boxes is used: a saturated heat map fails this batch and no other
   if (range_flag_ptr() && B.det_groups == groups) { spin_event(group_ev[groups]); range_verify(kRangeDet0 + (B.slot & 1), "the detector of a batch of pages"); }
   if (tn.detector_only) for (auto& d : dets) d.clear();   // profiling (tools/prof_pages.py): the detector and CCL run, nothing goes to the recogniser
@@ -1079,6 +1166,16 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
       r.bbox.insert(r.bbox.end(), bb, bb + 4);
       push_quad(B.boxes[pg][k], r.quad);
     }
+    if (B.dsk_M) {   // deskew: the page's record, checked before anything is built on it
+      if (B.dsk_recs.size() != (size_t)n) throw std::runtime_error("deskew: the batch carries no records");
+      const DeskewRec& d = B.dsk_recs[(size_t)pg];
+      std::string why;
+      if (!deskew_rec_valid(d, B.dsk_M, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, dsk_cs_host.data(), &why))
+        throw std::runtime_error("deskew: the record of page " + std::to_string(pg) + " holds " + why);
+      r.skew_on = 1; r.skew = d;
+    } else if (deskew_M && B.regions) {   // a region call: the caller's quadrilaterals are in the caller's frame
+      r.skew_on = 1; r.skew = DeskewRec{0, 0, 65536, 0, B.pages[(size_t)pg].w, B.pages[(size_t)pg].h, 0, 0, 0, 0};
+    }
     if (B.tab_min_len && !B.regions && cnt > 0) {   // tables: the page's side block and its words' cells, checked before anything is built on them
       if (!tab_block) throw std::runtime_error("tables: the batch carries no side block");
       const int32_t* ts = tab_block + (size_t)pg * kTabSideInts;
@@ -1479,6 +1576,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   if (curved) throw std::runtime_error("latency mode does not support curved words: ttr_engine_set_curved(e, 0) first");
   if (tables_min_len) throw std::runtime_error("latency mode does not support tables: ttr_engine_set_tables(e, 0, 0) first");
   if (tiled) throw std::runtime_error("latency mode does not support tiled pages: ttr_engine_set_tiled(e, 0) first");
+  if (deskew_M) throw std::runtime_error("latency mode does not support deskew: ttr_engine_set_deskew(e, 0, 0, 0) first");
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");
   if (cfg.orient != TTR_ORIENT_OFF) throw std::runtime_error("latency mode does not support word orientation: create the engine with orient = TTR_ORIENT_OFF");
   if (cfg.blocks) throw std::runtime_error("latency mode does not support text blocks: create the engine with blocks = 0");

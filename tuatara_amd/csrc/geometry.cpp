@@ -4,6 +4,7 @@
 #include "geometry.h"
 #include "curve_rule.h"
 #include "tables_rule.h"
+#include "deskew_rule.h"
 
 #include <algorithm>
 #include <climits>
@@ -1396,6 +1397,81 @@ bool tables_side_valid(const int32_t* s, std::string* why) {
   }
   if (next != nc) return bad("cells that belong to no table");
   return true;
+}
+
+// ---- deskew (DESIGN.md "Deskew"): the host rule; the steps themselves are deskew_rule.h's
+void deskew_consts(int32_t* cs) {
+  for (int k = -kDskMaxSlope; k <= kDskMaxSlope; ++k) {
+    const double d = std::sqrt(262144.0 + (double)(k * k));
+    cs[2 * (k + kDskMaxSlope)] = (int32_t)std::llrint(33554432.0 / d);
+    cs[2 * (k + kDskMaxSlope) + 1] = (int32_t)std::llrint(65536.0 * (double)k / d);
+  }
+}
+
+void deskew_scores(const uint64_t* bits, int h, int w, int max_slope, uint64_t* scores) {
+  const int nw = (w + 63) / 64, bias = dsk_bias(w, max_slope);
+  std::vector<uint32_t> bins((size_t)dsk_bins(h, w, max_slope));
+  for (int k = -max_slope; k <= max_slope; ++k) {
+    std::fill(bins.begin(), bins.end(), 0u);
+    for (int y = 0; y < h; ++y)
+      for (int j = 0; j < nw; ++j) {
+        uint64_t v = bits[(size_t)y * nw + j];
+        while (v) {
+          const int x = 64 * j + __builtin_ctzll(v);
+          v &= v - 1;
+          ++bins[(size_t)(y - dsk_off(x, k) + bias)];
+        }
+      }
+    uint64_t s = 0;
+    for (uint32_t c : bins) s += (uint64_t)c * c;
+    scores[k + max_slope] = s;
+  }
+}
+
+void deskew_choose(const uint64_t* scores, int max_slope, int gain, int h, int w, const int32_t* cs, DeskewRec* rec) {
+  int found = 0;
+  for (int k = -max_slope; k <= max_slope; ++k)
+    if (dsk_better(scores[k + max_slope], k, scores[found + max_slope], found)) found = k;
+  const int slope = dsk_slope(found, scores[found + max_slope], scores[max_slope], gain);
+  *rec = DeskewRec{slope, found, cs[2 * (slope + kDskMaxSlope)], cs[2 * (slope + kDskMaxSlope) + 1], w, h, slope != 0 ? 1 : 0, 0, scores[max_slope], scores[found + max_slope]};
+}
+
+void deskew_resample(const uint8_t* image, int h, int w, int stride, int C, int S, uint8_t* out, int out_stride) {
+  for (int y = 0; y < h; ++y)
+    for (int x = 0; x < w; ++x) dsk_pixel(image, h, w, stride, C, S, x, y, out + (size_t)y * out_stride + 3 * (size_t)x);
+}
+
+void deskew_from_page(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, int ink, uint8_t* out, int out_stride, DeskewRec* rec, uint64_t* scores) {
+  std::vector<uint64_t> bits(tables_bitmap_words(h, w)), sc((size_t)2 * max_slope + 1);
+  std::vector<int32_t> cs(2 * kDskSlopes);
+  tables_ink(image, h, w, stride, ink, bits.data());
+  deskew_scores(bits.data(), h, w, max_slope, sc.data());
+  deskew_consts(cs.data());
+  DeskewRec r;
+  deskew_choose(sc.data(), max_slope, gain, h, w, cs.data(), &r);
+  if (out) deskew_resample(image, h, w, stride, r.C, r.S, out, out_stride);
+  if (rec) *rec = r;
+  if (scores) std::copy(sc.begin(), sc.end(), scores);
+}
+
+bool deskew_rec_valid(const DeskewRec& r, int max_slope, int h, int w, const int32_t* cs, std::string* why) {
+  auto bad = [&](const char* m) { if (why) *why = m; return false; };
+  if (r.found < -max_slope || r.found > max_slope) return bad("a found slope outside -max_slope..max_slope");
+  if (r.slope != 0 && r.slope != r.found) return bad("a slope that is neither 0 nor the found one");
+  if (r.C != cs[2 * (r.slope + kDskMaxSlope)] || r.S != cs[2 * (r.slope + kDskMaxSlope) + 1]) return bad("constants that are not the table's for its slope");
+  if (r.w != w || r.h != h) return bad("another page's size");
+  if (r.mode != (r.slope != 0 ? 1 : 0)) return bad("a mode that does not match its slope");
+  if (r.score_found < r.score0) return bad("a found score below the score of slope 0");
+  return true;
+}
+
+void deskew_to_page(const DeskewRec& r, const float* xy_in, int n, float* xy_out) {
+  const double cx = (r.w - 1) / 2.0, cy = (r.h - 1) / 2.0;
+  for (int i = 0; i < n; ++i) {
+    const double x = (double)xy_in[2 * (size_t)i] - cx, y = (double)xy_in[2 * (size_t)i + 1] - cy;
+    xy_out[2 * (size_t)i] = (float)(cx + ((double)r.C * x - (double)r.S * y) / 65536.0);
+    xy_out[2 * (size_t)i + 1] = (float)(cy + ((double)r.S * x + (double)r.C * y) / 65536.0);
+  }
 }
 
 }  // namespace ttr

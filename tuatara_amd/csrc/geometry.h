@@ -162,6 +162,25 @@ bool tables_side_valid(const int32_t* side, std::string* why = nullptr);
 // row lines, then its cols + 1 column lines), cells [..][9]; any output may be null
 void tables_export(const int32_t* side, int32_t counts[4], int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells);
 
+// Deskew (ttr_engine_set_deskew; DESIGN.md "Deskew").  A page's skew is estimated from its ink bitmap - the slope k in -M..M (px per 512 px) under which the
+// ink's row profile is sharpest - and a page found tilted is resampled upright about its centre, at its own size.  The steps live in deskew_rule.h, shared
+// with deskew_score_kernel and deskew_rotate_kernel (deskew.hip); integers throughout, but for the table below.
+struct DeskewRec;
+// 4: the 257 (C, S) pairs, cs [257][2], pair k + 128 for slope k: llrint(65536 * 512 / d), llrint(65536 k / d), d = sqrt(512^2 + k^2) in double
+void deskew_consts(int32_t* cs);
+// 2: scores [2 M + 1] of a bitmap as tables_ink forms it (score of slope k at k + M)
+void deskew_scores(const uint64_t* bits, int h, int w, int max_slope, uint64_t* scores);
+// 3: the record of a page from its scores
+void deskew_choose(const uint64_t* scores, int max_slope, int gain, int h, int w, const int32_t* cs, DeskewRec* rec);
+// 5: out u8 [h][w][3] (rows out_stride bytes apart) = the page turned by the slope whose constants are C, S
+void deskew_resample(const uint8_t* image, int h, int w, int stride, int C, int S, uint8_t* out, int out_stride);
+// 1 - 5 on one page; out, rec, scores may be null
+void deskew_from_page(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, int ink, uint8_t* out, int out_stride, DeskewRec* rec, uint64_t* scores);
+// what decode_pages accepts from the device; why (may be null) receives the reason
+bool deskew_rec_valid(const DeskewRec& r, int max_slope, int h, int w, const int32_t* cs, std::string* why = nullptr);
+// 6: n points (x, y) of the upright page -> the caller's page, computed in double
+void deskew_to_page(const DeskewRec& r, const float* xy_in, int n, float* xy_out);
+
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.
 struct Component {

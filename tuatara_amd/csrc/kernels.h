@@ -387,6 +387,15 @@ void launch_table_ink(const uint8_t* images, size_t page_bytes, int stride, int 
 // runs int32 [pages][2][8192][3] (workspace: the run lists); side int32 [pages][kTabSideInts] (tables_rule.h); items int32 [N][2] = table, cell
 void launch_table_grid(const uint64_t* bits, const uint64_t* bitsT, int h, int w, const PageRow* table, int pages, int Hcap, int Wcap, int min_len, const int* centres,
                        const int* first, int* runs, int* side, int* items, hipStream_t s);
+// ---- deskew.hip (DESIGN.md "Deskew")
+struct DeskewRec;
+// deskew_score_kernel: step 2 on every page, one workgroup per (slope, page).  bits as table_ink_kernel wrote them for a launch of Hcap x Wcap (both below 8192);
+// table: the source pages' rows (h and w are read); scores uint64 [pages][2 max_slope + 1], slope k at k + max_slope
+void launch_deskew_score(const uint64_t* bits, const PageRow* table, int pages, int Hcap, int Wcap, int max_slope, uint64_t* scores, hipStream_t s);
+// deskew_rotate_kernel: steps 3 and 5.  Page p of src_table, turned by the slope its scores choose, into page p of dst_table (same h and w; any stride >= 3 w);
+// cs int32 [257][2] the host's (C, S) table (geometry.h: deskew_consts); recs [pages] the pages' records
+void launch_deskew_rotate(const PageRow* src_table, const PageRow* dst_table, int pages, int Hcap, int Wcap, int max_slope, int gain, const uint64_t* scores, const int* cs,
+                          DeskewRec* recs, hipStream_t s);
 // get_detected_boxes' per-component tail on the GPU (tuatara.cpp:162-179: niter, ROI, dilation, findNonZero + minAreaRect): one lane per candidate, geometry.cpp's
 // arithmetic step for step (float32 calipers, double where OpenCV is double) -> CclBuffers::rects.  After launch_ccl on the same stream.
 void launch_ccl_rects(const CclBuffers& b, int pages, int H, int W, hipStream_t s);

@@ -65,12 +65,15 @@ thread_local std::string g_call_error;   // last_call_error()
 thread_local int g_call_tiled = 0;       // set_tiled(): the overlap of this thread's calls, 0 = off (then TUATARA_TILED decides)
 thread_local int g_call_tables = 0, g_call_tables_ink = 128;   // set_tables(): min_len and ink of this thread's calls, 0 = off (then TUATARA_TABLES decides)
 thread_local std::vector<TableGrid> g_call_table_out;          // last_call_tables()
+thread_local int g_call_deskew = 0, g_call_deskew_gain = 288, g_call_deskew_ink = 128;   // set_deskew(): this thread's calls, 0 = off (then TUATARA_DESKEW decides)
+thread_local PageSkew g_call_skew_out;                         // last_call_skew()
 struct CharsetScope {
   ttr_engine* e;
   std::unique_lock<std::mutex> turn;
   bool set = false, ok = true;
   bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false, curved_set = false, fuzzy_set = false, tiled_set = false;
   bool tables_set = false;
+  bool deskew_set = false;
   CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
                std::string pattern = std::string(), float wide = 0.f, bool pattern_best = false, bool curved = false, LexFuzzy fuzzy = LexFuzzy{-1, 0.f}) : e(e_) {
     {
@@ -119,6 +122,13 @@ struct CharsetScope {
       if (ttr_engine_set_tables(e, tab, g_call_tables_ink) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
       tables_set = true;
     }
+    int dsk = g_call_deskew;
+    if (dsk == 0) if (const char* p = std::getenv("TUATARA_DESKEW")) dsk = std::string(p) == "1" ? 64 : std::atoi(p);
+    g_call_skew_out = PageSkew();
+    if (dsk != 0) {   // deskew (DESIGN.md "Deskew"): max_slope, gain and ink for the call, like the set
+      if (ttr_engine_set_deskew(e, dsk, g_call_deskew_gain, g_call_deskew_ink) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      deskew_set = true;
+    }
     if (!curved) if (const char* p = std::getenv("TUATARA_CURVED")) curved = std::string(p) == "1";
     if (curved) {   // curved words (DESIGN.md "Curved words"): on for the call, like the set
       if (ttr_engine_set_curved(e, 1) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
@@ -146,6 +156,7 @@ struct CharsetScope {
     if (curved_set) ttr_engine_set_curved(e, 0);
     if (tiled_set) ttr_engine_set_tiled(e, 0);
     if (tables_set) ttr_engine_set_tables(e, 0, 0);
+    if (deskew_set) ttr_engine_set_deskew(e, 0, 0, 0);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
     if (alts_set) ttr_engine_set_alternatives(e, 0);
     if (fuzzy_set) ttr_engine_set_lexicon_fuzzy(e, -1, 0.f);
@@ -287,6 +298,14 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
   }
   std::vector<Item> out(ttr_result_count(r));
   for (size_t i = 0; i < out.size(); ++i) { fill(out[i], r, (int)i); name_matches(e, out[i]); }
+  {   // deskew: the page's record (last_call_skew())
+    ttr_skew sk;
+    if (ttr_result_skew(r, &sk)) {
+      PageSkew& o = g_call_skew_out;
+      o.on = true; o.slope = sk.slope; o.found = sk.found; o.C = sk.C; o.S = sk.S; o.w = sk.w; o.h = sk.h; o.mode = sk.mode;
+      o.degrees = std::atan((double)sk.slope / 512.0) * 180.0 / 3.14159265358979323846;
+    }
+  }
   if (const int32_t* tb = ttr_result_tables(r)) {   // tables: every table as rows x cols strings (last_call_tables())
     const int32_t* cl = ttr_result_cells(r);
     for (int t = 0; t < ttr_result_table_count(r); ++t) {
@@ -536,6 +555,15 @@ int tiled() { return g_call_tiled; }
 void set_tables(int min_len, int ink) { g_call_tables = min_len; g_call_tables_ink = ink; }
 int tables() { return g_call_tables; }
 std::vector<TableGrid> last_call_tables() { return g_call_table_out; }
+void set_deskew(int max_slope, int gain, int ink) { g_call_deskew = max_slope; g_call_deskew_gain = gain; g_call_deskew_ink = ink; }
+int deskew() { return g_call_deskew; }
+PageSkew last_call_skew() { return g_call_skew_out; }
+void PageSkew::to_page(float x, float y, float* xs, float* ys) const {
+  const float in[2] = {x, y};
+  float out[2] = {x, y};
+  if (on) { ttr_skew sk{}; sk.slope = slope; sk.found = found; sk.C = C; sk.S = S; sk.w = w; sk.h = h; sk.mode = mode; ttr_skew_to_page(&sk, in, 1, out); }
+  *xs = out[0]; *ys = out[1];
+}
 
 std::vector<WordReading> nbest(const OutputItemEx& item, int m) {
   std::vector<WordReading> out;

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import collections.abc
 import ctypes as C
+import math
 import os
 import sys
 from typing import List, Optional, Sequence
@@ -290,6 +291,15 @@ SYMBOLS = [
     ("ttr_tables_from_page", _I, [_PU8, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI, _PI, _PI, _PI, _PI]),
     ("ttr_tables_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI, _PI, _PI, _PI, _PI]),
     ("ttr_dbg_tables", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_uint64), _PI, _PI, _PI]),
+    ("ttr_engine_set_deskew", _I, [_VP, _I, _I, _I]),
+    ("ttr_engine_deskew", _I, [_VP, _PI, _PI]),
+    ("ttr_result_skew", _I, [_VP, C.c_void_p]),
+    ("ttr_result_to_page", _I, [_VP, _PF, _I, _PF]),
+    ("ttr_skew_to_page", _I, [C.c_void_p, _PF, _I, _PF]),
+    ("ttr_results_gather_skew", _I, [C.POINTER(_VP), _I, C.c_void_p]),
+    ("ttr_deskew_from_page", _I, [_PU8, _I, _I, _I, _I, _I, _I, _PU8, C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("ttr_deskew_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _PU8, C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("ttr_dbg_deskew_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, _I, _PU8, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("ttr_engine_set_tiled", _I, [_VP, _I]),
     ("ttr_engine_tiled", _I, [_VP]),
     ("ttr_result_tiles", _I, [_VP]),
@@ -1028,6 +1038,70 @@ def _tables_call(fn, image, quads, min_len, ink, row_stride=0):
             "item_table": it[:nq].copy(), "item_cell": ic[:nq].copy(), "runs": (int(counts[4]), int(counts[5]))}
 
 
+DESKEW_MAX_SLOPE, DESKEW_GAIN, DESKEW_INK = 64, 288, 128   # what deskew=True means (DESIGN.md "Deskew": none of them has been tuned on documents)
+
+
+class Skew(C.Structure):
+    """ttr_skew: one page's skew record"""
+    _fields_ = [("slope", C.c_int32), ("found", C.c_int32), ("C", C.c_int32), ("S", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("mode", C.c_int32),
+                ("reserved", C.c_int32), ("score0", C.c_uint64), ("score_found", C.c_uint64)]
+
+
+def _deskew_arg(deskew):
+    """False / None / 0 -> (0, DESKEW_GAIN, DESKEW_INK); True -> the defaults; (max_slope, gain, ink) or a bare max_slope otherwise"""
+    if deskew is None or deskew is False or (isinstance(deskew, int) and not isinstance(deskew, bool) and deskew == 0):
+        return 0, DESKEW_GAIN, DESKEW_INK
+    if deskew is True:
+        return DESKEW_MAX_SLOPE, DESKEW_GAIN, DESKEW_INK
+    if isinstance(deskew, (tuple, list)) and len(deskew) == 3:
+        return int(deskew[0]), int(deskew[1]), int(deskew[2])
+    if isinstance(deskew, int):
+        return int(deskew), DESKEW_GAIN, DESKEW_INK
+    raise EngineError("deskew must be False, True or (max_slope, gain, ink)")
+
+
+def _skew_dict(rec) -> dict:
+    """a ttr_skew as the dict PageResult.skew carries: the record's fields and degrees = atan(slope / 512)"""
+    d = {k: int(getattr(rec, k)) for k in ("slope", "found", "C", "S", "w", "h", "mode", "score0", "score_found")}
+    d["degrees"] = math.degrees(math.atan(d["slope"] / 512.0))
+    return d
+
+
+def skew_to_page(skew: dict, points) -> np.ndarray:
+    """the map back of a skew record (ttr_skew_to_page; DESIGN.md "Deskew", step 6): points [..., 2] of the upright page -> the caller's page, float32 of the
+    double map.  skew: a dict with "C", "S", "w", "h" (PageResult.skew is one)."""
+    p = np.ascontiguousarray(points, dtype=np.float32)
+    if p.shape[-1:] != (2,):
+        raise EngineError("to_page takes points [..., 2]")
+    rec = Skew(C=int(skew["C"]), S=int(skew["S"]), w=int(skew["w"]), h=int(skew["h"]))
+    out = np.zeros_like(p)
+    _lib_check(load().ttr_skew_to_page(C.addressof(rec), _f(p), p.size // 2, _f(out)))
+    return out
+
+
+def _deskew_call(fn, image, max_slope, gain, ink, row_stride=0):
+    """the shared body of deskew_from_page and Engine.deskew_page: fn(image..., outputs...) -> the dict both return"""
+    image = np.asarray(image, dtype=np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise RuntimeError("Input array should have 3 dimensions")
+    if not row_stride:
+        image = np.ascontiguousarray(image)
+    h, w = image.shape[:2]
+    out, rec, scores = np.zeros((h, w, 3), np.uint8), Skew(), np.zeros(2 * max(int(max_slope), 0) + 1, np.uint64)
+    fn(_u8(image), h, w, int(row_stride) or w * 3, int(max_slope), int(gain), int(ink), _u8(out), C.addressof(rec), scores.ctypes.data_as(C.POINTER(C.c_uint64)))
+    return {"image": out, "skew": _skew_dict(rec), "scores": scores}
+
+
+def deskew_from_page(image, max_slope: int = DESKEW_MAX_SLOPE, gain: int = DESKEW_GAIN, ink: int = DESKEW_INK, row_stride: int = 0) -> dict:
+    """The deskew rule on the host (ttr_deskew_from_page, no GPU; DESIGN.md "Deskew"): a host image u8 [H, W, 3] (row_stride: the bytes from row to row of a view
+    into a wider buffer) -> {"image" u8 [H, W, 3] the upright page, "skew" the record as PageResult.skew carries it, "scores" u64 [2 max_slope + 1]}."""
+    lib = load()
+
+    def fn(*a):
+        _lib_check(lib.ttr_deskew_from_page(*a))
+    return _deskew_call(fn, image, max_slope, gain, ink, row_stride)
+
+
 def table_line_lists(tables, lines) -> list:
     """the flat line values of a result split per table: [(row lines i32 [rows + 1], column lines i32 [cols + 1]), ...] in doubled px"""
     out, k = [], 0
@@ -1083,8 +1157,11 @@ class PageResult(collections.abc.Sequence):
     [nr, 6] (dir, x0, y0, x1, y1, table), `table_rects` i32 [nt, 8] (box, rows, cols, first cell, cell count), `table_lines` i32 (doubled px), `cells` i32
     [nc, 9] (table, row, col, rowspan, colspan, box), `item_table` / `item_cell` i32 [n] (dicts gain "table" and "cell", -1 = in no cell), `cell_texts`;
     `tables` the list of {"bbox", "rows", "cols", "cells": [{"row", "col", "rowspan", "colspan", "bbox", "items", "text"}]} and table_grid(t) its rows x cols
-    strings; rulings is None, tables [] when tables are off and for a page without items."""
-    __slots__ = ("table_mode", "rulings", "table_rects", "table_lines", "cells", "item_table", "item_cell", "cell_texts",
+    strings; rulings is None, tables [] when tables are off and for a page without items.  Deskew (Engine.set_deskew; DESIGN.md "Deskew"): `skew` = the page's
+    record {"slope", "found", "C", "S", "w", "h", "mode", "score0", "score_found", "degrees"} or None when the layer is off; every coordinate of the result is
+    in the upright page's frame, to_page(points) maps points to the caller's page and every dict gains "quad_page"."""
+    __slots__ = ("skew", "quad_page",
+                 "table_mode", "rulings", "table_rects", "table_lines", "cells", "item_table", "item_cell", "cell_texts",
                  "texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
                  "char_first", "char_quad", "char_bbox", "char_cuts", "char_mode", "char_profile", "word_quad",
@@ -1099,8 +1176,9 @@ class PageResult(collections.abc.Sequence):
                  alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None, pattern_logp=None,
                  piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None,
                  curved=None, outline=None, spine_knots=None, lex_edits=None, lex_band=-1, tiles=0,
-                 table_mode=0, rulings=None, table_rects=None, table_lines=None, cells=None, item_table=None, item_cell=None, cell_texts=None):
+                 table_mode=0, rulings=None, table_rects=None, table_lines=None, cells=None, item_table=None, item_cell=None, cell_texts=None, skew=None, quad_page=None):
         self.tiles = tiles
+        self.skew, self.quad_page = skew, quad_page     # quad_page f32 [n, 8]: every quad on the caller's page (ttr_result_to_page), None without deskew or quads
         self.table_mode, self.rulings, self.table_rects, self.table_lines, self.cells = table_mode, rulings, table_rects, table_lines, cells
         self.item_table, self.item_cell, self.cell_texts = item_table, item_cell, cell_texts
         self.lex_edits, self.lex_band = lex_edits, lex_band
@@ -1162,7 +1240,15 @@ class PageResult(collections.abc.Sequence):
             d["curved"], d["outline"] = int(self.curved[j]), self.outline[j].tolist()
         if self.item_table is not None:
             d["table"], d["cell"] = int(self.item_table[j]), int(self.item_cell[j])
+        if self.quad_page is not None:
+            d["quad_page"] = _quad_pairs(self.quad_page[j])
         return d
+
+    def to_page(self, points) -> np.ndarray:
+        """points [..., 2] of this result's frame -> the caller's page (the identity when deskew is off), float32"""
+        if self.skew is None:
+            return np.asarray(points, dtype=np.float32).copy()
+        return skew_to_page(self.skew, points)
 
     @property
     def tables(self) -> list:
@@ -1296,6 +1382,7 @@ class Engine:
         curved = bool(overrides.pop("curved", False))                                     # nor this: set_curved, below
         tiled = _tiled_arg(overrides.pop("tiled", None))                                  # nor this: set_tiled, below
         tables = _tables_arg(overrides.pop("tables", None))                               # nor this: set_tables, below
+        deskew = _deskew_arg(overrides.pop("deskew", None))                               # nor this: set_deskew, below
         self._lex_words = []
         tuning = {k: overrides.pop(k) for k in list(overrides) if not hasattr(cfg, k)}     # not a config field: a tuning key (below)
         for k, v in overrides.items():
@@ -1325,6 +1412,35 @@ class Engine:
             self.set_tiled(tiled)
         if tables[0]:
             self.set_tables(tables)
+        if deskew[0]:
+            self.set_deskew(deskew)
+
+    def set_deskew(self, deskew=True):
+        """Estimate every page's skew on the GPU and read the page upright (ttr_engine_set_deskew; DESIGN.md "Deskew"): False / 0 = off, True = (64, 288, 128),
+        else (max_slope, gain, ink) with max_slope in 1..128 (px per 512 px; 128 = 14 degrees), gain in 256..65535 (1/256ths) and ink in 1..255 (none of the
+        defaults has been tuned on documents).  Results are those of the upright page, in its frame; PageResult.skew / to_page / "quad_page" lead back to the
+        caller's.  Raises EngineError, and changes nothing, for other values, between a stream_push and its flush, and with a communicator attached."""
+        m, g, i = _deskew_arg(deskew)
+        if self.lib.ttr_engine_set_deskew(self.h, m, g, i) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def deskew(self):
+        """(max_slope, gain, ink) in force, or None when deskew is off"""
+        g, i = C.c_int(), C.c_int()
+        m = int(self.lib.ttr_engine_deskew(self.h, C.byref(g), C.byref(i)))
+        return (m, int(g.value), int(i.value)) if m else None
+
+    def deskew_page(self, image, max_slope: int = DESKEW_MAX_SLOPE, gain: int = DESKEW_GAIN, ink: int = DESKEW_INK, dev_offset: int = 0, dev_stride: int = 0) -> dict:
+        """ttr_deskew_page: the pixel pass, deskew_score_kernel and deskew_rotate_kernel on a host image u8 [H, W, 3], whatever the engine's setting -> the dict
+        deskew_from_page returns.  dev_offset / dev_stride (ttr_dbg_deskew_page): the image is placed dev_offset bytes into a device buffer with dev_stride
+        bytes from row to row (0 = 3 W)."""
+        def fn(*a):
+            if dev_offset or dev_stride:
+                self._check(self.lib.ttr_dbg_deskew_page(self.h, *a[:4], int(dev_offset), int(dev_stride), *a[4:]))
+            else:
+                self._check(self.lib.ttr_deskew_page(self.h, *a))
+        return _deskew_call(fn, image, max_slope, gain, ink)
 
     def set_tables(self, tables=True):
         """Find ruling lines, tables, their grids and merged cells in every page's pixels and give every item its cell (ttr_engine_set_tables; DESIGN.md
@@ -1797,6 +1913,8 @@ class Engine:
             cvf, cvo, cvk = np.zeros(total, np.int32), np.zeros((total, 18, 2), np.float32), np.zeros((total, 9, 4), np.int64)
             if self.lib.ttr_results_gather_curved(arr, n, _i(cvf), _f(cvo), _i64(cvk)) < 0:
                 raise EngineError("ttr_results_gather_curved: bad arguments")
+        skews = (Skew * max(n, 1))()            # deskew: every page's record, one call (zeroes where a result has none)
+        self.lib.ttr_results_gather_skew(arr, n, C.addressof(skews))
         out, k, kl, kc, kbl, kb, kp = [], 0, 0, 0, 0, 0, 0
         for i in range(n):
             c = int(counts[i])
@@ -1818,6 +1936,14 @@ class Engine:
                     le = self.lib.ttr_result_lex_edits_all(arr[i])
                     lex.update(lex_band=band, lex_edits=np.ctypeslib.as_array(le, (c, M)).copy() if le else np.zeros((0, M), np.int32))
             lex["tiles"] = int(self.lib.ttr_result_tiles(arr[i]))
+            if self.lib.ttr_result_skew(arr[i], None):   # deskew: the page's record, and its quads on the caller's page
+                lex["skew"] = _skew_dict(skews[i])
+                if self.rectified:
+                    q = self._quads(arr[i], c)
+                    qp = np.zeros_like(q)
+                    if c:
+                        self._check(self.lib.ttr_result_to_page(arr[i], _f(q), 4 * c, _f(qp)))
+                    lex["quad_page"] = qp
             if self.lib.ttr_result_item_table(arr[i]):   # tables: the page's rulings, tables, lines and cells, its items' cells and the cells' texts
                 r = arr[i]
                 nr_, nt_, nc_, nl_ = self.lib.ttr_result_ruling_count(r), self.lib.ttr_result_table_count(r), self.lib.ttr_result_cell_count(r), C.c_int()
