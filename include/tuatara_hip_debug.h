@@ -160,6 +160,16 @@ int ttr_dbg_split_layer_check(int kernel, int B, int H, int W, int C0, int Cout,
 int ttr_dbg_last_groups(ttr_engine* e, int* craft_pages, int* enc_crops);
 /* the heat maps of the engine's last batch of n pages, f32 [n][H/2][W/2][2], as its detector left them on the device.  Refuses while batches stream. */
 int ttr_dbg_last_heat(ttr_engine* e, float* heat, size_t floats);
+/* History invariance (tests/test_gpu_history.py): the engine's device buffers as the table of tuatara_amd/csrc/engine.h classifies them.
+ * ttr_dbg_scratch_table: host only, no engine - one buffer per line, "name class kind" and, behind them, the row's note (for a kept row: the contract that makes it
+ * so); class scratch / kept, kind f32 / f16 / u8 / i32 / addr.  Returns the text's length (what fits `cap` is copied, terminated).
+ * ttr_dbg_poison_scratch (f16x4 engines; refuses while batches stream): synchronises the engine's streams, then fills every allocated scratch buffer to its full
+ * capacity - pattern 0 zeros, 1 quiet NaN (f32 0x7FC00000, f16 0x7E00, u8 0xA5), 2 large finite (f32 1e4, f16 8192, u8 0x5A); i32 buffers always with zeros, addr
+ * buffers not at all - with plain memsets and one synchronise: no kernel is added and no pass changes.  also_kept_once != 0 poisons the two write-once float
+ * buffers as well (the detector's zero-padded head slots, the decoder's K/V cache): such an engine computes garbage from then on and is only good for showing that
+ * the poison reaches memory the kernels read.  Returns the bytes filled, -1 on error. */
+int ttr_dbg_scratch_table(char* text, size_t cap);
+int64_t ttr_dbg_poison_scratch(ttr_engine* e, int pattern, int also_kept_once);
 
 
 #ifdef __cplusplus

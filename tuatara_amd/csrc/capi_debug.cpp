@@ -684,6 +684,72 @@ int ttr_dbg_last_heat(ttr_engine* e, float* heat, size_t floats) {
   TTR_GUARD_END(-1)
 }
 
+// ---- the device buffers' table (engine.h: kDevBufTable) as text, and the poison over its scratch rows
+static const char* buf_kind_name(BufKind k) { return k == kElF32 ? "f32" : k == kElF16 ? "f16" : k == kElU8 ? "u8" : k == kElI32 ? "i32" : "addr"; }
+
+int ttr_dbg_scratch_table(char* text, size_t cap) {
+  TTR_GUARD_BEGIN
+  std::string s;
+  for (const BufRow& r : kDevBufTable) {
+    s += std::string(r.name) + " " + (r.kept ? "kept" : "scratch") + " " + buf_kind_name(r.kind);
+    if (r.note[0]) s += std::string(" ") + r.note;
+    s += "\n";
+  }
+  if (text && cap) { const size_t n = std::min(cap - 1, s.size()); memcpy(text, s.data(), n); text[n] = 0; }
+  return (int)s.size();
+  TTR_GUARD_END(-1)
+}
+
+int64_t ttr_dbg_poison_scratch(ttr_engine* e, int pattern, int also_kept_once) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  if (pattern < 0 || pattern > 2) throw std::runtime_error("ttr_dbg_poison_scratch: pattern must be 0 (zeros), 1 (quiet NaN) or 2 (large finite)");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (E.prec != kSplit) throw std::runtime_error("ttr_dbg_poison_scratch: an f16x4 engine only (the table's kinds are that engine's)");
+  E.refuse_while_streaming("ttr_dbg_poison_scratch");
+  for (hipStream_t st : {E.stream, E.recog_stream, E.lane_stream, E.copy_stream, E.up_stream}) if (st) TTR_HIP_CHECK(hipStreamSynchronize(st));
+  static const uint32_t v32[3] = {0u, 0x7FC00000u, 0x461C4000u};   // 0, quiet NaN, 1e4
+  static const uint16_t v16[3] = {0, 0x7E00, 0x7000};              // 0, quiet NaN, 8192
+  static const uint8_t v8[3] = {0, 0xA5, 0x5A};
+  size_t filled = 0;
+  auto fill = [&](DevBuf& d, BufKind kind) {
+    if (!d.p || !d.cap || kind == kElAddr) return;   // (capacities are whole MiB: every element width divides them)
+    if (kind == kElF32) TTR_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)d.p, (int)v32[pattern], d.cap / 4, E.stream));
+    else if (kind == kElF16) TTR_HIP_CHECK(hipMemsetD16Async((hipDeviceptr_t)d.p, v16[pattern], d.cap / 2, E.stream));
+    else if (kind == kElU8) TTR_HIP_CHECK(hipMemsetD8Async((hipDeviceptr_t)d.p, v8[pattern], d.cap, E.stream));
+    else TTR_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)d.p, 0, d.cap / 4, E.stream));
+    filled += d.cap;
+  };
+  std::vector<std::string> seen;
+  size_t craft_slot = 0; int craft_set = 0, pq_slot = 0;
+  E.for_scratch([&](const char* name, DevBuf& d, BufKind kind) {
+    if (seen.empty() || seen.back() != name) seen.push_back(name);
+    if (!strcmp(name, "craft_ws_set")) {   // the slot's own kind, and the write-once slots only on request
+      while (craft_set < 2 && craft_slot >= E.craft_ws_set[craft_set].size()) { ++craft_set; craft_slot = 0; }
+      const auto& meta = E.craft_ws_meta[craft_set];
+      const uint8_t m = craft_slot < meta.size() ? meta[craft_slot] : (uint8_t)kElF16;
+      ++craft_slot;
+      if ((m & Engine::kWsZeroedOnce) && !also_kept_once) return;
+      kind = (BufKind)(m & Engine::kWsKindMask);
+    } else if (!strcmp(name, "pq_ws")) {
+      const int i = pq_slot++;
+      if (i == Engine::kWsKvcache && !also_kept_once) return;
+      kind = i >= Engine::kWsLnPlanes ? kElF16 : kElF32;
+    }
+    fill(d, kind);
+  });
+  // the visit and the table must name the same scratch rows, in the same order
+  std::vector<std::string> want;
+  const bool no_craft = E.craft_ws_set[0].empty() && E.craft_ws_set[1].empty();   // (before the first detector pass the sets hold no slot to visit)
+  for (const BufRow& r : kDevBufTable)
+    if (!r.kept && (E.comm || strncmp(r.name, "comm.", 5) != 0) && !(no_craft && !strcmp(r.name, "craft_ws_set"))) want.push_back(r.name);
+  if (seen != want) throw std::logic_error("ttr_dbg_poison_scratch: Engine::for_scratch and kDevBufTable name different scratch buffers");
+  TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+  return (int64_t)filled;
+  TTR_GUARD_END(-1)
+}
+
 // tables (DESIGN.md "Tables"): the ink bitmap and the run lists as the device formed them
 int ttr_dbg_tables(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_len, int ink, uint64_t* bits, int32_t* runs,
                    int32_t* n_runs, int32_t* mode) {

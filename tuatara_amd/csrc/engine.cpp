@@ -455,9 +455,12 @@ Engine::~Engine() {
   if (stream) (void)hipStreamDestroy(stream);
 }
 
-DevBuf& Engine::ws(size_t idx, size_t bytes, bool zero_new) {
+DevBuf& Engine::ws(size_t idx, size_t bytes, bool zero_new, BufKind kind) {
   auto& craft_ws = craft_ws_cur();
   while (craft_ws.size() <= idx) craft_ws.emplace_back(new DevBuf());
+  auto& meta = craft_ws_meta[ws_sel];
+  if (meta.size() <= idx) meta.resize(idx + 1, (uint8_t)kElF16);
+  meta[idx] = (uint8_t)(kind | (zero_new ? kWsZeroedOnce : 0));
   DevBuf& d = *craft_ws[idx];
   const size_t cap_before = d.cap;          // (not the pointer: the allocator may hand the grown block the old address)
   d.ensure(bytes);

@@ -441,6 +441,110 @@ struct GatherLayout {
   }
 };
 
+// ------------------------------------------------------------------ the engine's device buffers, classified (ttr_dbg_scratch_table, ttr_dbg_poison_scratch)
+// Every DevBuf declared in this header has one row here (tests/test_scratch_table_cpu.py holds the two lists together; members of the helper structs carry their
+// owner's name: ccl. / linear. / head_tail. / comm.).
+//   scratch  wholly rewritten by each call that reads it, before it is read: what it holds between calls is nobody's business, and the poison hook may fill it
+//   kept     its contents must survive from call to call; the row says why
+// kind: what the poison hook writes - f32 / f16 (16-bit planes) / u8 patterns, and ALWAYS zeros into i32 (indices, counters, integer records and blocks that mix
+// integers with floats: a stale index that gets read must come out as a wrong value, never as a wild address) and nothing at all into addr (rows that hold device
+// addresses: a zero address is no safer than a stale one)
+enum BufKind : uint8_t { kElF32 = 0, kElF16 = 1, kElU8 = 2, kElI32 = 3, kElAddr = 4 };
+struct BufRow { const char* name; bool kept; BufKind kind; const char* note; };
+constexpr BufRow kDevBufTable[] = {
+    // ---- weights and other uploads
+    {"linear.w", true, kElF32, "a layer's weight in the engine's type, uploaded once by the constructor"},
+    {"linear.b", true, kElF32, "a layer's fp32 bias, uploaded once by the constructor"},
+    {"linear.ws", true, kElF16, "a layer's f16 weight planes, written once by upload_linear"},
+    {"linear.wst", true, kElF16, "the same planes as gemm_sp's loader pieces, written once by tile_planes"},
+    {"linear.wsp", true, kElF16, "the packed-pairs form of a 32-channel 3x3 layer's planes, written once by load_craft"},
+    {"head_tail.w6", true, kElF32, "conv_cls.6's weight for the fused head tail, uploaded once by load_head_tail"},
+    {"head_tail.w8", true, kElF32, "conv_cls.8's weight for the fused head tail, uploaded once by load_head_tail"},
+    {"head_tail.b6", true, kElF32, "conv_cls.6's bias, uploaded once by load_head_tail"},
+    {"head_tail.b8", true, kElF32, "conv_cls.8's bias, uploaded once by load_head_tail"},
+    {"pqf", true, kElF32, "the recogniser's fp32 vectors (LayerNorm parameters, embeddings, position queries), uploaded once by load_parseq"},
+    {"fc1_packed", true, kElF16, "bf16 engines: encoder fc1 weights as mlp_fused's LDS images, uploaded once"},
+    {"proj_packed", true, kElF16, "bf16 engines: encoder attn.proj weights k-step-major, uploaded once"},
+    {"fc2_packed", true, kElF16, "bf16 engines: encoder fc2 weights chunk-major, uploaded once"},
+    {"dec_ffn1_packed", true, kElF16, "bf16 engines: the decoder's linear1 as an mlp_fused image, uploaded once"},
+    {"dec_ffn2_packed", true, kElF16, "bf16 engines: the decoder's linear2 as an mlp_fused image, uploaded once"},
+    {"dec_co_packed", true, kElF16, "bf16 engines: the decoder's cross_attn.out_proj as an mlp_fused image, uploaded once"},
+    {"qself", true, kElF32, "the projected position queries, computed on the host and uploaded once by load_parseq"},
+    {"lex_records", true, kElU8, "the caller's word list as 32-byte records, uploaded by ttr_engine_set_lexicon and read by every pass until the next one"},
+    {"pattern_dev", true, kElI32, "the engine's pattern table, uploaded by set_engine_pattern: nothing travels per call"},
+    {"dsk_cs", true, kElI32, "deskew's (C, S) table, uploaded by the first call that needs it (dsk_cs_up)"},
+    {"range_word", true, kElI32, "the range guard's sticky words: zeroed by the constructor, and each is cleared again by the stream that fetched it"},
+    {"ar_done", true, kElI32, "the AR loop's done counter: its first word is cleared on the stream in front of every loop, the host reads it between steps"},
+    // ---- the detector
+    {"craft_ws_set", false, kElF16, "per slot as ws() noted it: planes or fp32; the slots ws() zeroed once (zero_new: the unpacked head tensors' padding channels) are kept and left alone"},
+    {"canvas", false, kElU8, ""},
+    {"heat", false, kElF32, ""},
+    {"tile_heat", false, kElF32, ""},
+    {"tile_table", false, kElAddr, ""},
+    {"page_table", false, kElAddr, ""},
+    {"staging_img", false, kElU8, ""},
+    {"stage_dev", false, kElU8, ""},
+    {"split_in", false, kElF16, ""},
+    {"dsk_bits", false, kElU8, ""},
+    {"dsk_bitsT", false, kElU8, ""},
+    {"dsk_scores", false, kElI32, ""},
+    {"dsk_rec", false, kElI32, ""},
+    {"dsk_table", false, kElAddr, ""},
+    {"dsk_pages", false, kElU8, ""},
+    // ---- post-processing
+    {"ccl.tnorm", false, kElF32, ""},
+    {"ccl.flags", false, kElU8, ""},
+    {"ccl.parent", false, kElI32, ""},
+    {"ccl.mm", false, kElI32, ""},
+    {"ccl.area", false, kElI32, ""},
+    {"ccl.bbox", false, kElI32, ""},
+    {"ccl.maxt", false, kElI32, ""},
+    {"ccl.cand_slot", false, kElI32, ""},
+    {"ccl.cand", false, kElI32, ""},
+    {"ccl.counters", false, kElI32, ""},
+    {"ccl.rows", false, kElI32, ""},
+    {"ccl.rects", false, kElI32, "a kind word in front of seven floats per candidate"},
+    {"ccl.cal_pool", false, kElF32, ""},
+    {"ccl.cal_ctr", false, kElI32, ""},
+    {"crops", false, kElU8, ""},
+    {"rects_dev", false, kElI32, ""},
+    {"coef_dev", false, kElI32, ""},
+    // ---- the recogniser
+    {"pq_ws", false, kElF32, "per slot: fp32 tensors up to kWsStepLogits, f16 planes from kWsLnPlanes on; kWsKvcache is kept: zeroed once per capacity by parseq_ar (kvcache_zeroed), "
+                             "slots behind an early exit keep older finite rows, which the attention kernels mask"},
+    {"logits", false, kElF32, ""},
+    {"ar_logits", false, kElF32, ""},
+    {"ids_dev", false, kElI32, "ids | prob | conf"},
+    {"tokens", false, kElI32, ""},
+    {"row_masks_dev", false, kElI32, ""},
+    {"pat_rows_dev", false, kElI32, ""},
+    {"pat_state", false, kElI32, ""},
+    {"pat_best_scratch", false, kElI32, "ids | prob | conf"},
+    {"pat_logp_dev", false, kElF32, ""},
+    {"gath_dev", false, kElI32, "the ranks' ids | prob | conf blocks"},
+    {"comm.d_in", false, kElU8, ""},
+    {"comm.d_out", false, kElU8, ""},
+    // ---- the opt-in layers' inputs and side blocks
+    {"orient_in", false, kElI32, ""},
+    {"orient_cand", false, kElI32, "ids | prob | conf"},
+    {"orient_side", false, kElI32, ""},
+    {"lines_in", false, kElI32, ""},
+    {"lines_side", false, kElI32, ""},
+    {"alts_side", false, kElI32, "ids | prob"},
+    {"lex_side", false, kElI32, "idx | logp | edits"},
+    {"lex_part", false, kElI32, "idx | logp"},
+    {"wide_side", false, kElI32, "cuts | u16 profiles"},
+    {"curve_side", false, kElI32, ""},
+    {"tab_bits", false, kElU8, ""},
+    {"tab_bitsT", false, kElU8, ""},
+    {"tab_runs", false, kElI32, ""},
+    {"tab_side", false, kElI32, ""},
+    {"blocks_side", false, kElI32, ""},
+    {"chars_map", false, kElF32, ""},
+    {"chars_in", false, kElI32, ""},
+    {"chars_side", false, kElI32, "cuts | modes | u8 profiles"},
+};
+
 struct Engine {
   ttr_config cfg;
   Tuning tn = g_tuning_default;
@@ -531,6 +635,8 @@ struct Engine {
 
   // workspaces
   std::vector<std::unique_ptr<DevBuf>> craft_ws_set[2];   // per-layer activations; [1]: the second detector lane's (tn.craft_lanes)
+  enum { kWsKindMask = 7, kWsZeroedOnce = 8 };
+  std::vector<uint8_t> craft_ws_meta[2];          // per slot of the set, as ws() last handed it out: its BufKind, | kWsZeroedOnce for a zero_new slot (host bookkeeping of the poison hook)
   int ws_sel = 0;                                 // which set ws() hands out
   std::vector<std::unique_ptr<DevBuf>>& craft_ws_cur() { return craft_ws_set[ws_sel]; }
   // tn.craft_lanes = 2: a batch's CRAFT launch groups alternate between the main stream and lane_stream, the second lane half a group behind the first
@@ -712,7 +818,7 @@ struct Engine {
   ~Engine();
 
   // ---- CRAFT
-  DevBuf& ws(size_t idx, size_t bytes, bool zero_new = false);
+  DevBuf& ws(size_t idx, size_t bytes, bool zero_new = false, BufKind kind = kElF16);
 
   void conv(const char* name, const void* in0, int C0, const void* in1, int C1, int relu0, int B, int H, int W, void* out, int act,
             float* out_f32 = nullptr, void* out_relu = nullptr, void* out_pool = nullptr, int pool_relu = 0);
@@ -1071,6 +1177,39 @@ struct Engine {
   // 256 bytes and run through the table path; an image whose geometry is invalid fails alone, before bucketing.
   void run_images(const std::vector<HostImage>& imgs, std::vector<Result>& results, std::vector<int>& failed, std::string& first_error);
   std::vector<int32_t> last_batches;   // pages per batch of the last run_images call, in run order (ttr_last_images_batches)
+
+  // ---- the scratch rows of kDevBufTable above as this engine's buffers: f(name, buffer, kind) for each, in the table's order.  Per-slot exceptions to a row's
+  // kind and class (craft_ws_set, pq_ws) are the poison hook's to apply (capi_debug.cpp), which also checks that the names visited are the table's scratch rows
+  template <class F> void for_scratch(F&& f) {
+    for (auto& set : craft_ws_set) for (auto& d : set) f("craft_ws_set", *d, kElF16);
+    f("canvas", canvas, kElU8); f("heat", heat, kElF32); f("tile_heat", tile_heat, kElF32);
+    for (auto& d : tile_table) f("tile_table", d, kElAddr);
+    for (auto& d : page_table) f("page_table", d, kElAddr);
+    f("staging_img", staging_img, kElU8);
+    for (auto& d : stage_dev) f("stage_dev", d, kElU8);
+    for (auto& d : split_in) f("split_in", d, kElF16);
+    f("dsk_bits", dsk_bits, kElU8); f("dsk_bitsT", dsk_bitsT, kElU8); f("dsk_scores", dsk_scores, kElI32); f("dsk_rec", dsk_rec, kElI32);
+    for (auto& d : dsk_table) f("dsk_table", d, kElAddr);
+    for (auto& d : dsk_pages) f("dsk_pages", d, kElU8);
+    f("ccl.tnorm", ccl.tnorm, kElF32); f("ccl.flags", ccl.flags, kElU8); f("ccl.parent", ccl.parent, kElI32); f("ccl.mm", ccl.mm, kElI32);
+    f("ccl.area", ccl.area, kElI32); f("ccl.bbox", ccl.bbox, kElI32); f("ccl.maxt", ccl.maxt, kElI32); f("ccl.cand_slot", ccl.cand_slot, kElI32);
+    f("ccl.cand", ccl.cand, kElI32); f("ccl.counters", ccl.counters, kElI32); f("ccl.rows", ccl.rows, kElI32); f("ccl.rects", ccl.rects, kElI32);
+    f("ccl.cal_pool", ccl.cal_pool, kElF32); f("ccl.cal_ctr", ccl.cal_ctr, kElI32);
+    f("crops", crops, kElU8); f("rects_dev", rects_dev, kElI32); f("coef_dev", coef_dev, kElI32);
+    for (auto& d : pq_ws) f("pq_ws", d, kElF32);
+    f("logits", logits, kElF32); f("ar_logits", ar_logits, kElF32); f("ids_dev", ids_dev, kElI32); f("tokens", tokens, kElI32);
+    f("row_masks_dev", row_masks_dev, kElI32); f("pat_rows_dev", pat_rows_dev, kElI32); f("pat_state", pat_state, kElI32);
+    f("pat_best_scratch", pat_best_scratch, kElI32); f("pat_logp_dev", pat_logp_dev, kElF32);
+    for (auto& d : gath_dev) f("gath_dev", d, kElI32);
+    if (comm) { f("comm.d_in", comm->d_in, kElU8); f("comm.d_out", comm->d_out, kElU8); }
+    f("orient_in", orient_in, kElI32); f("orient_cand", orient_cand, kElI32); f("orient_side", orient_side, kElI32);
+    f("lines_in", lines_in, kElI32); f("lines_side", lines_side, kElI32); f("alts_side", alts_side, kElI32);
+    f("lex_side", lex_side, kElI32); f("lex_part", lex_part, kElI32); f("wide_side", wide_side, kElI32); f("curve_side", curve_side, kElI32);
+    f("tab_bits", tab_bits, kElU8); f("tab_bitsT", tab_bitsT, kElU8); f("tab_runs", tab_runs, kElI32); f("tab_side", tab_side, kElI32);
+    f("blocks_side", blocks_side, kElI32);
+    for (auto& d : chars_map) f("chars_map", d, kElF32);
+    f("chars_in", chars_in, kElI32); f("chars_side", chars_side, kElI32);
+  }
   int stream_fail_age = 0;   // set by stream_push / stream_flush before they throw: 0 = the batch being pushed never entered the pipeline, 2 = the batch whose results were due failed and has left it
 };
 

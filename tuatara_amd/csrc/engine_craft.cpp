@@ -283,13 +283,13 @@ void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, f
   const int layout = npl * 2 + (head_packed ? 1 : 0);   // (plane count and the head tensors' row form AS THIS PAGE TAKES IT: both move the zero padding channels)
   if (layout != craft_ws_npl) {   // another plane count: the zero padding channels of the head tensors sit elsewhere - start from fresh buffers
     TTR_HIP_CHECK(hipStreamSynchronize(stream)); TTR_HIP_CHECK(hipStreamSynchronize(lane_stream));
-    craft_ws_set[0].clear(); craft_ws_set[1].clear();
+    craft_ws_set[0].clear(); craft_ws_set[1].clear(); craft_ws_meta[0].clear(); craft_ws_meta[1].clear();
     craft_ws_npl = layout;
   }
   // (every tensor of this pass is one craft_widest_per_page accounts for: an allocation wider than the figure the group size came from is a bug, not a shape)
   auto sized = [&](size_t bytes) { if (bytes > (size_t)B * widest.bytes) throw std::logic_error("craft_forward_split: a tensor wider than craft_widest_per_page states"); return bytes; };
   auto pbuf = [&](size_t rows, int C) -> void* { return ws(k++, sized(rows * C * 2 * npl)).p; };   // planes
-  auto fbuf = [&](size_t rows, int C) -> void* { return ws(k++, sized(rows * C * 4)).p; };   // fp32
+  auto fbuf = [&](size_t rows, int C) -> void* { return ws(k++, sized(rows * C * 4), false, kElF32).p; };   // fp32
   // conv1_1: a launch of its own (conv1_split_kernel: the 64-channel tensor at full resolution goes out and comes back), or - pairs, 8 x 32 patches, the split
   // 3x3 tiles on - evaluated inside conv1_2's kernel on each halo patch: same arithmetic, same bits, the tensor never exists (tuning key first_fused)
   const bool fuse_first = tn.first_fused && npl == 2 && tn.split_conv3p && H % 8 == 0 && W % 32 == 0 && M0 * 3 < ((size_t)1 << 31);

@@ -66,6 +66,8 @@ SYMBOLS = [
     ("ttr_dbg_split_layer_check", _I, [_I] * 10 + [C.c_char_p, C.c_size_t]),
     ("ttr_dbg_last_groups", _I, [_VP, _PI, _PI]),
     ("ttr_dbg_last_heat", _I, [_VP, _PF, C.c_size_t]),
+    ("ttr_dbg_scratch_table", _I, [C.c_char_p, C.c_size_t]),
+    ("ttr_dbg_poison_scratch", C.c_int64, [_VP, _I, _I]),
     ("ttr_result_count", _I, [_VP]),
     ("ttr_result_text", C.c_char_p, [_VP, _I]),
     ("ttr_result_bbox", _PF, [_VP, _I]),
@@ -440,6 +442,20 @@ def split_layer_check(kernel: str, B: int, H: int, W: int, C0: int, Cout: int, k
     if rc < 0:
         raise EngineError("ttr_dbg_split_layer_check: bad arguments")
     return text.value.decode() if rc else None
+
+
+def scratch_table():
+    """The engine's device buffers as engine.h classifies them (ttr_dbg_scratch_table, no GPU) -> a list of (name, class, kind, note): class "scratch" /
+    "kept", kind "f32" / "f16" / "u8" / "i32" / "addr"; a kept row's note is the contract that makes it so."""
+    buf = C.create_string_buffer(1 << 16)
+    n = load().ttr_dbg_scratch_table(buf, len(buf))
+    if n < 0 or n >= len(buf):
+        raise EngineError("ttr_dbg_scratch_table: the table does not fit the buffer")
+    rows = []
+    for line in buf.value.decode().splitlines():
+        f = line.split(None, 3)
+        rows.append((f[0], f[1], f[2], f[3] if len(f) > 3 else ""))
+    return rows
 
 
 def _host_images(images):
@@ -2217,6 +2233,15 @@ class Engine:
         heat = np.zeros((n, H // 2, W // 2, 2), np.float32)
         self._check(self.lib.ttr_dbg_last_heat(self.h, _f(heat), heat.size))
         return heat
+
+    def poison_scratch(self, pattern: int, also_kept_once: bool = False) -> int:
+        """f16x4 engines, developer hook (ttr_dbg_poison_scratch): every allocated scratch buffer of the engine filled to its capacity with pattern
+        0 (zeros) / 1 (quiet NaN) / 2 (large finite); integer buffers always with zeros.  also_kept_once poisons the two write-once float buffers too:
+        close such an engine afterwards.  Returns the bytes filled."""
+        n = self.lib.ttr_dbg_poison_scratch(self.h, int(pattern), int(bool(also_kept_once)))
+        if n < 0:
+            raise EngineError(self.lib.ttr_last_error().decode())
+        return int(n)
 
     def last_stage_ms(self):
         ms = (C.c_float * 4)()
