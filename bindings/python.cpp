@@ -48,6 +48,9 @@
 // And a keyword-only deskew=False on image_to_data: deskew=True (max_slope 64, gain 288, ink 128) or deskew=(max_slope, gain, ink) estimates the page's skew on the
 // GPU and reads the page upright (DESIGN.md "Deskew"); boxes and quads are then the upright page's.  A value out of range raises RuntimeError with the engine's
 // message.  last_call_skew() returns the latest call's record (or None), last_call_to_page(points) maps points of its result to the caller's image.
+// And a keyword-only local_ink=False on image_to_data: local_ink=True (radius 16, drop 38, polarity 2 = auto) or local_ink=(radius, drop, polarity) makes tables and
+// deskew take their ink bitmap from the adaptive threshold (DESIGN.md "Local ink"), so shaded, grey or inverted pages keep their rulings and their skew; with
+// neither of the two on nothing runs.  A value out of range raises RuntimeError with the engine's message.
 // And a keyword-only tables=False on image_to_data: tables=True (min_len 48, ink 128) or tables=(min_len, ink) finds ruling lines, tables, grids and merged
 // cells in the page's pixels (DESIGN.md "Tables"); every dict gains "table" and "cell" (-1 / -1 for an item in no cell).  It combines with every keyword but
 // regions (ValueError); a value out of range raises RuntimeError before anything runs.
@@ -269,7 +272,20 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
                                       py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved, py::object lexicon_fuzzy, double lexicon_gap,
-                                      py::object tiled_kw, py::object tables_kw, py::object deskew_kw) {
+                                      py::object tiled_kw, py::object tables_kw, py::object deskew_kw, py::object local_ink_kw) {
+  // local_ink=False | True (16, 38, 2) | (radius, drop, polarity): the ink rule of tables and deskew for this call (DESIGN.md "Local ink")
+  struct InkScope {
+    InkScope(int r, int d, int p) { set_local_ink(r, d, p); }
+    ~InkScope() { set_local_ink(0); }
+  };
+  int ink_r = 0, ink_d = 38, ink_p = 2;
+  if (py::isinstance<py::bool_>(local_ink_kw)) ink_r = local_ink_kw.cast<bool>() ? 16 : 0;
+  else if (py::isinstance<py::tuple>(local_ink_kw) && py::len(local_ink_kw) == 3) {
+    const py::tuple t = local_ink_kw.cast<py::tuple>();
+    ink_r = t[0].cast<int>(); ink_d = t[1].cast<int>(); ink_p = t[2].cast<int>();
+  } else if (!local_ink_kw.is_none()) throw py::type_error("local_ink must be False, True or (radius, drop, polarity)");
+  // (the ranges are the engine's to check: ttr_engine_set_ink refuses, the call comes back empty and raise_refused raises its message)
+  InkScope ink_scope(ink_r, ink_d, ink_p);
   // deskew=False | True (64, 288, 128) | (max_slope, gain, ink): the page is read upright for this call (DESIGN.md "Deskew"); boxes and quads are the upright page's
   struct DeskewScope {
     DeskewScope(int m, int g, int i) { set_deskew(m, g, i); }
@@ -383,7 +399,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
                 : pattern_best ? image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts, true)
                 : image_to_data_ex(static_cast<const uint8_t*>(rb.ptr), (int)rb.shape[0], (int)rb.shape[1], (std::ptrdiff_t)rb.shape[1] * 3, weights_dir, output_dir, regs, alts);
     }
-    if ((alts || lex || with_pattern || dsk_m) && got.empty()) raise_refused();
+    if ((alts || lex || with_pattern || dsk_m || ink_r) && got.empty()) raise_refused();
     py::list res;
     for (const auto& item : got) {
       Keys keys{true, conf, false, false, false, false, alts != 0, lex, false, pattern_best};
@@ -414,7 +430,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
             : orient ? image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify, orient, orient_page)
                      : image_to_data_ex(data, rows, cols, (std::ptrdiff_t)cols * 3, weights_dir, output_dir, rectify);
   }
-  if ((alts || lex || !pattern.empty() || tiled_overlap || dsk_m) && items.empty()) raise_refused();
+  if ((alts || lex || !pattern.empty() || tiled_overlap || dsk_m || ink_r) && items.empty()) raise_refused();
   py::list result;
   Keys keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best};
   keys.lex_edits = band >= 0;
@@ -486,7 +502,7 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, py::arg("tables") = false, py::arg("deskew") = false, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, py::arg("tables") = false, py::arg("deskew") = false, py::arg("local_ink") = false, "Extract text and bounding boxes from an image");
   m.def("last_call_skew", []() -> py::object {
     const PageSkew s = last_call_skew();
     if (!s.on) return py::none();

@@ -43,6 +43,9 @@
 //   ocr_cli --tiled [O] ...   in front of any form above that runs the detector, options included: a page larger than the detector canvas is read at full size,
 // as overlapping tiles whose heat maps are stitched into one page map (DESIGN.md "Tiled pages"); O = the overlap in pixels, a multiple of 32 in [64, 256]
 // (default 128, not tuned on documents).  A page of more than 64 tiles or with a side above 8192 fails with the rule's message.
+//   ocr_cli --local-ink [R] ...   in front of --tables or --deskew (and of --tiled): the two layers take their ink bitmap from the adaptive threshold - a pixel
+// darker than its neighbourhood's mean - so shaded, grey or inverted pages keep their rulings and their skew (DESIGN.md "Local ink"; R = the window's radius in
+// px, 1..64, default 16, with drop 38 and automatic polarity, none of them tuned on documents).
 //   ocr_cli --deskew [MAX_SLOPE] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: the page's skew is estimated on the GPU and the page read
 // upright (DESIGN.md "Deskew"; MAX_SLOPE = the largest slope tried, px per 512 px, 1..128, default 64, not tuned on documents); prints "# page 0 slope S degrees D
 // found F" and then the plain form's lines, the boxes in the upright page's frame, each followed by a tab and the box's first corner on the caller's image.
@@ -102,6 +105,15 @@ static std::vector<RegionSpec> read_regions(const char* path) {
 
 int main(int argc, const char** argv) {
   try {
+    if (argc >= 2 && std::string(argv[1]) == "--local-ink") {   // a leading option of the forms that read the page's ink (--tables, --deskew): the radius for the calls that follow
+      int radius = 16, used = 1;
+      if (argc >= 3 && argv[2][0] != '-' && std::string(argv[2]).find_first_not_of("0123456789") == std::string::npos && std::strlen(argv[2]) <= 4) {
+        radius = std::atoi(argv[2]); used = 2;
+        if (radius < 1 || radius > 64) throw std::runtime_error("--local-ink takes a radius in 1..64 px (default 16)");
+      }
+      set_local_ink(radius);
+      argv[used] = argv[0]; argv += used; argc -= used;
+    }
     if (argc >= 2 && std::string(argv[1]) == "--tiled") {   // a leading option of every form that runs the detector: the overlap for the calls that follow
       int overlap = 128, used = 1;
       if (argc >= 3 && argv[2][0] >= '0' && argv[2][0] <= '9' && std::string(argv[2]).find_first_not_of("0123456789") == std::string::npos && std::strlen(argv[2]) <= 4) {

@@ -285,6 +285,14 @@ void set_deskew(int max_slope, int gain = 288, int ink = 128);
 int deskew();
 PageSkew last_call_skew();
 
+// Local ink (opt-in; DESIGN.md "Local ink"): tables and deskew take their ink bitmap from an adaptive threshold - a pixel darker than its neighbourhood's mean -
+// instead of the global one, so shaded, grey or inverted pages keep their rulings and their skew.  set_local_ink(radius, drop, polarity) turns it on for every
+// call of THIS THREAD that follows (radius 1..64 px, drop 1..255 in 1/256ths, polarity 0 dark / 1 light / 2 auto; the defaults 16, 38 and 2 are untuned),
+// set_local_ink(0) off again; with it off, TUATARA_LOCAL_INK=RADIUS (or 1 for 16) in the environment turns it on for every call here.  It is set on the cached
+// engine for the call and reset afterwards; with neither tables nor deskew on nothing runs.  A bad value: the message is printed and the result is empty.
+void set_local_ink(int radius, int drop = 38, int polarity = 2);
+int local_ink();
+
 #if defined(__has_include)
 #if __has_include(<opencv2/core.hpp>)
 #include <opencv2/core.hpp>

@@ -792,6 +792,39 @@ int ttr_skew_to_page(const ttr_skew* rec, const float* xy_in, int n, float* xy_o
 int ttr_results_gather_skew(ttr_result* const* rs, int n, ttr_skew* recs);
 int ttr_deskew_from_page(const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink, uint8_t* out_img, ttr_skew* rec, uint64_t* scores);
 int ttr_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink, uint8_t* out_img, ttr_skew* rec, uint64_t* scores);
+/* ---- local ink (opt-in; DESIGN.md "Local ink") --------------------------------------------------
+ * Tables and deskew start from one ink bitmap, by default a global threshold (b0 + b1 + b2 < 3 ink): dark ink on light paper only.  With
+ * ttr_engine_set_ink(e, radius, drop, polarity) the engine's tables and deskew passes take that bitmap from an adaptive threshold instead: with s = b0 + b1 + b2,
+ * n and S the area and the sum of s of the window [x - radius, x + radius] x [y - radius, y + radius] clipped to the page, a pixel is ink iff
+ * s n 256 < S (256 - drop) - darker than its neighbourhood's mean by drop 256ths -, in integers (ink_rows_kernel and ink_local_kernel; the layout of the bitmaps
+ * and everything behind them is unchanged).  radius = 0 is off (the default: nothing runs, and every launch and bit is as before), else radius in 1..64, drop
+ * in 1..255 and polarity 0 (dark ink), 1 (light ink: s becomes 765 - s) or 2 (auto: light iff twice the page's sum of s is below 765 h w; a tie stays dark).
+ * The convenience layers use 16, 38 and 2, which nobody has tuned on documents.  On, the `ink` of ttr_engine_set_tables / ttr_engine_set_deskew is not consulted.
+ * A blank or all-black page carries no ink; a solid region thicker than the window loses its interior; the bitmap of 255 - page under light ink is that of page
+ * under dark ink, bit for bit.  The setter refuses values outside the ranges and while streamed batches are in flight; with neither tables nor deskew on it is
+ * accepted and nothing runs.  The stage calls ttr_tables_page / ttr_deskew_page keep the fixed rule, whatever the engine's setting.
+ *   ttr_engine_ink             radius in force (0 = off); drop and polarity through the pointers (may be NULL)
+ *   ttr_result_ink             the page's record - that of the tables pass when tables ran, else that of the deskew pass; returns 1, or 0 when the result carries none
+ *   ttr_results_gather_ink     the records of n results back to back (zeroes where a result has none); returns the number of pages read as light ink
+ * ttr_ink_from_page: the rule on the host, no engine.  A host image u8 [h][w][3] (row_stride bytes, 0 = 3 w) -> bits [h][ceil(w / 64)] uint64 (bit x % 64 of word
+ * x / 64), bitsT [w][ceil(h / 64)] the same bits along y, rec; any output may be NULL.  Returns 0, -1 with the message in ttr_last_error.
+ * ttr_ink_page (stage; refuses while batches stream): the same through the kernels, whatever the engine's setting.
+ * ttr_tables_from_page_ink / ttr_deskew_from_page_ink: ttr_tables_from_page / ttr_deskew_from_page with (radius, drop, polarity) in the place of ink. */
+typedef struct ttr_ink {
+  int32_t radius, drop, polarity, inverted;   /* inverted: 1 = the page was read as light ink on dark paper */
+  uint64_t sum;                               /* the page's sum of b0 + b1 + b2 */
+  int32_t w, h;
+} ttr_ink;
+int ttr_engine_set_ink(ttr_engine* e, int radius, int drop, int polarity);
+int ttr_engine_ink(const ttr_engine* e, int* drop, int* polarity);
+int ttr_result_ink(const ttr_result* r, ttr_ink* rec);
+int ttr_results_gather_ink(ttr_result* const* rs, int n, ttr_ink* recs);
+int ttr_ink_from_page(const uint8_t* img, int h, int w, int row_stride, int radius, int drop, int polarity, uint64_t* bits, uint64_t* bitsT, ttr_ink* rec);
+int ttr_ink_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int radius, int drop, int polarity, uint64_t* bits, uint64_t* bitsT, ttr_ink* rec);
+int ttr_tables_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int min_len, int radius, int drop, int polarity, const float* quads, int nq, int32_t* mode,
+                             int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell);
+int ttr_deskew_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int radius, int drop, int polarity, uint8_t* out_img, ttr_skew* rec,
+                             uint64_t* scores);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

@@ -140,6 +140,10 @@ int ttr_dbg_tables(ttr_engine* e, const uint8_t* img, int h, int w, int row_stri
  * so that the kernels see a window whose base and stride are no multiples of 4.  Outputs as ttr_deskew_page.  Refuses while batches stream.  Returns 0, -1 on error. */
 int ttr_dbg_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int max_slope, int gain, int ink, uint8_t* out_img,
                    ttr_skew* rec, uint64_t* scores);
+/* local ink (DESIGN.md "Local ink"): ttr_ink_page with the host image placed dev_offset bytes into a device buffer with dev_stride bytes from row to row (0 = 3 w),
+ * as ttr_dbg_tables takes it.  Outputs as ttr_ink_page.  Refuses while batches stream.  Returns 0, -1 on error. */
+int ttr_dbg_ink_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int radius, int drop, int polarity, uint64_t* bits,
+                     uint64_t* bitsT, ttr_ink* rec);
 /* canvas_geometry on the host for any canvas_size / mag_ratio (what ttr_canvas_geometry answers for an engine of that config): h32 x w32, the ratio and
  * the resized page's target_h x target_w inside the canvas.  Any output may be NULL.  Returns 0, -1 for h <= 0 or w <= 0. */
 int ttr_dbg_canvas_geometry(int h, int w, int canvas_size, float mag_ratio, int* H, int* W, float* ratio, int* target_h, int* target_w);

@@ -1737,6 +1737,107 @@ int ttr_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_str
   TTR_GUARD_END(-1)
 }
 
+// ---- local ink (DESIGN.md "Local ink")
+static_assert(sizeof(ttr_ink) == sizeof(InkRec) && offsetof(ttr_ink, sum) == offsetof(InkRec, sum) && offsetof(ttr_ink, w) == offsetof(InkRec, w), "ttr_ink is the engine's record");
+
+static std::string ink_ranges(int radius, int drop, int polarity) {
+  return "drop in 1..255 and polarity in 0..2, got " + std::to_string(radius) + ", " + std::to_string(drop) + " and " + std::to_string(polarity);
+}
+
+int ttr_engine_set_ink(ttr_engine* e, int radius, int drop, int polarity) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (radius != 0 && !ink_args_ok(radius, drop, polarity)) throw std::runtime_error("ttr_engine_set_ink: radius must be 0 (off) or lie in 1..64, " + ink_ranges(radius, drop, polarity));
+  E.refuse_while_streaming("ttr_engine_set_ink");
+  E.ink_radius = radius;
+  if (radius) { E.ink_drop = drop; E.ink_polarity = polarity; }
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_ink(const ttr_engine* e, int* drop, int* polarity) {
+  if (!e) return 0;
+  if (drop) *drop = e->e->ink_drop;
+  if (polarity) *polarity = e->e->ink_polarity;
+  return e->e->ink_radius;
+}
+
+int ttr_result_ink(const ttr_result* r, ttr_ink* rec) {
+  if (!r || !r->r.ink_on) return 0;
+  if (rec) memcpy(rec, &r->r.ink, sizeof *rec);
+  return 1;
+}
+
+int ttr_results_gather_ink(ttr_result* const* rs, int n, ttr_ink* recs) {
+  if (!rs || n < 0) return -1;
+  int light = 0;
+  for (int i = 0; i < n; ++i) {
+    const bool has = rs[i] && rs[i]->r.ink_on;
+    if (recs) { if (has) memcpy(recs + i, &rs[i]->r.ink, sizeof(ttr_ink)); else memset(recs + i, 0, sizeof(ttr_ink)); }
+    light += has && rs[i]->r.ink.inverted == 1;
+  }
+  return light;
+}
+
+static void ink_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int radius, int drop, int polarity) {
+  if (!img) throw std::runtime_error("null argument");
+  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
+  if (h >= 32768 || w >= 32768) throw std::runtime_error(std::string(what) + ": a page side of 32768 px or more");
+  if (!ink_args_ok(radius, drop, polarity)) throw std::runtime_error(std::string(what) + ": radius must lie in 1..64, " + ink_ranges(radius, drop, polarity));
+}
+
+int ttr_ink_from_page(const uint8_t* img, int h, int w, int row_stride, int radius, int drop, int polarity, uint64_t* bits, uint64_t* bitsT, ttr_ink* rec) {
+  TTR_GUARD_BEGIN
+  ink_in_ok("ttr_ink_from_page", img, h, w, row_stride, radius, drop, polarity);
+  InkRec r;
+  ink_from_page(img, h, w, row_stride ? row_stride : w * 3, radius, drop, polarity, bits, bitsT, &r);
+  if (rec) memcpy(rec, &r, sizeof r);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_ink_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int radius, int drop, int polarity, uint64_t* bits, uint64_t* bitsT, ttr_ink* rec) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  ink_in_ok("ttr_ink_page", img, h, w, row_stride, radius, drop, polarity);
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_ink_page");
+  InkRec r;
+  E.ink_stage(img, h, w, row_stride, 0, 0, radius, drop, polarity, bits, bitsT, &r);
+  if (rec) memcpy(rec, &r, sizeof r);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_tables_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int min_len, int radius, int drop, int polarity, const float* quads, int nq, int32_t* mode,
+                             int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell) {
+  TTR_GUARD_BEGIN
+  tables_in_ok("ttr_tables_from_page_ink", img, h, w, row_stride, min_len, 128, quads, nq);
+  ink_in_ok("ttr_tables_from_page_ink", img, h, w, row_stride, radius, drop, polarity);
+  std::vector<int32_t> side(kTabSideInts), centres((size_t)nq * 2), items((size_t)nq * 2);
+  tables_from_page_ink(img, h, w, row_stride ? row_stride : w * 3, min_len, radius, drop, polarity, side.data());
+  for (int i = 0; i < nq; ++i) tables_word_centre(quads + 8 * (size_t)i, &centres[2 * (size_t)i]);
+  tables_words(side.data(), centres.data(), nq, items.data());
+  tables_out(side.data(), items.data(), nq, mode, counts, rulings, tables, lines, cells, item_table, item_cell);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_deskew_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int radius, int drop, int polarity, uint8_t* out_img, ttr_skew* rec,
+                             uint64_t* scores) {
+  TTR_GUARD_BEGIN
+  deskew_in_ok("ttr_deskew_from_page_ink", img, h, w, row_stride, max_slope, gain, 128);
+  ink_in_ok("ttr_deskew_from_page_ink", img, h, w, row_stride, radius, drop, polarity);
+  DeskewRec r;
+  deskew_from_page_ink(img, h, w, row_stride ? row_stride : w * 3, max_slope, gain, radius, drop, polarity, out_img, w * 3, &r, scores);
+  if (rec) memcpy(rec, &r, sizeof r);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_result_alt_k(const ttr_result* r) { return r ? r->r.alt_k : 0; }
 
 const int32_t* ttr_result_alt_ids(const ttr_result* r, int i) { return r && !r->r.alt_ids.empty() ? &r->r.alt_ids[(size_t)26 * r->r.alt_k * (size_t)i] : nullptr; }

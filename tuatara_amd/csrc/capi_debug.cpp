@@ -782,6 +782,20 @@ int ttr_dbg_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row
   TTR_GUARD_END(-1)
 }
 
+int ttr_dbg_ink_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int radius, int drop, int polarity, uint64_t* bits,
+                     uint64_t* bitsT, ttr_ink* rec) {
+  TTR_GUARD_BEGIN
+  if (!e || !img) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_dbg_ink_page");
+  InkRec r;
+  E.ink_stage(img, h, w, row_stride, dev_offset, dev_stride, radius, drop, polarity, bits, bitsT, &r);
+  if (rec) memcpy(rec, &r, sizeof r);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
 int ttr_dbg_orient_quad(const float* r5, int h, int w, int crop_mode, int turn, float* quad8, int64_t* fixed6) {
   TTR_GUARD_BEGIN
   if (turn < 0 || turn > 3 || (crop_mode != TTR_CROP_BOUNDING && crop_mode != TTR_CROP_RECTIFIED)) throw std::runtime_error("bad turn or crop_mode");

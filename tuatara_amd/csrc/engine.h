@@ -48,6 +48,7 @@
 #include "../../include/tuatara_hip_debug.h"
 #include "common.h"
 #include "deskew_rule.h"
+#include "ink_rule.h"
 #include "geometry.h"
 #include "host_util.h"
 #include "kernels.h"
@@ -352,6 +353,10 @@ struct Result {
   // upright page's frame, and deskew_to_page maps it to the caller's (a region call: slope 0, the identity)
   int skew_on = 0;
   DeskewRec skew{};
+  // local ink (ttr_engine_set_ink; DESIGN.md "Local ink"): ink_on 0 when no pass of this page ran under it; else the record of the tables pass when tables ran,
+  // else that of the deskew pass
+  int ink_on = 0;
+  InkRec ink{};
   std::string block_text(int b) const;           // the block's lines joined by '\n'
   std::string page_text_blocks() const;          // the blocks in reading order, joined by "\n\n"
 };
@@ -489,6 +494,8 @@ constexpr BufRow kDevBufTable[] = {
     {"dsk_bitsT", false, kElU8, ""},
     {"dsk_scores", false, kElI32, ""},
     {"dsk_rec", false, kElI32, ""},
+    {"dsk_ink_h", false, kElU8, ""},
+    {"dsk_ink_rec", false, kElI32, ""},
     {"dsk_table", false, kElAddr, ""},
     {"dsk_pages", false, kElU8, ""},
     // ---- post-processing
@@ -539,6 +546,8 @@ constexpr BufRow kDevBufTable[] = {
     {"tab_bitsT", false, kElU8, ""},
     {"tab_runs", false, kElI32, ""},
     {"tab_side", false, kElI32, ""},
+    {"tab_ink_h", false, kElU8, ""},
+    {"tab_ink_rec", false, kElI32, ""},
     {"blocks_side", false, kElI32, ""},
     {"chars_map", false, kElF32, ""},
     {"chars_in", false, kElI32, ""},
@@ -588,6 +597,12 @@ struct Engine {
   std::vector<int32_t> dsk_cs_host;               // ... and on the host: what decode_pages checks a record's constants against
   DevBuf dsk_table[2], dsk_pages[2];              // ... per slot: the source and upright pages' rows [2][pages] (page_table.h), and the upright pages themselves
   PinnedBuf h_dsk_table[2], h_dsk[2];             // ... per slot: the rows' staging, and the records' host copy
+  // local ink (ttr_engine_set_ink; DESIGN.md "Local ink"): radius 1..64, 0 = off; the drop in 1/256ths; the polarity 0 dark, 1 light, 2 auto.  On, the engine's
+  // tables and deskew passes take their bitmaps from ink.hip's two kernels instead of table_ink_kernel (their own `ink` is then not consulted); the stage calls
+  // and ttr_dbg_tables keep the fixed rule.  Tables and deskew run on different streams: each has its own workspace and records
+  int ink_radius = 0, ink_drop = 38, ink_polarity = kInkAuto;
+  DevBuf dsk_ink_h, dsk_ink_rec;                  // ... deskew's: the horizontal sums [pages][Hcap][Wcap] uint32, the records [pages]
+  PinnedBuf h_dsk_ink[2], h_tab_ink[2];           // ... per slot: the records' host copies
   DevBuf tile_heat;                               // ... the tile canvases' maps [n T][Hc / 2][Wc / 2][2] (allocated by the first tiled batch)
   DevBuf tile_table[2];                           // ... the tiles as rows of a second page table, per slot (the packers go on reading page_table: the real pages)
   PinnedBuf h_tile_table[2];
@@ -685,6 +700,7 @@ struct Engine {
   PinnedBuf h_curve[2];                           // ... per slot: its host copy
   DevBuf tab_bits, tab_bitsT, tab_runs, tab_side; // tables: the two bitmaps and the run lists (workspaces), and the side blocks [pages][kTabSideInts] | [N][2] table, cell (tables.hip)
   PinnedBuf h_tab[2];                             // ... per slot: the side blocks' host copy
+  DevBuf tab_ink_h, tab_ink_rec;                  // local ink under tables (and ttr_ink_page): the horizontal sums [pages][Hcap][Wcap] uint32, the records [pages]
   DevBuf blocks_side;                             // text blocks: the side block (blocks.hip)
   PinnedBuf h_blocks[2];                          // ... per slot: its host copy
   DevBuf chars_map[2], chars_in, chars_side;      // character boxes: per slot the batch's region planes (a copy of ccl.tnorm); coef | page_of | turns | nchars; the side block (chars.hip)
@@ -1000,6 +1016,9 @@ struct Engine {
     int tab_min_len = 0, tab_ink = 0;
     std::vector<int32_t> tab_centres;
     std::vector<DeskewRec> dsk_recs;   // deskew: the pages' records as the device wrote them (detect_collect_local takes them from the slot's pinned copy)
+    // local ink (DESIGN.md "Local ink"): the engine's setting when the detector was enqueued (radius 0 = off), and the records of the deskew pass, taken with dsk_recs
+    int ink_radius = 0, ink_drop = 0, ink_polarity = 0;
+    std::vector<InkRec> dsk_ink_recs;
     int dsk_M = 0;                     // deskew: max_slope when the detector was enqueued (0 = off, and for region calls); the pages of the batch are then upright copies
     int tiles = 0;                     // tiled pages: tiles per page (0 = the engine's tiling was off when the detector was enqueued), and their plan
     TilePlan plan{};
@@ -1067,6 +1086,10 @@ struct Engine {
   // through the pixel pass and the two kernels -> out [h][w][3] (out_stride bytes from row to row), the record, scores [2 max_slope + 1]; any may be null
   void deskew_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int max_slope, int gain, int ink, uint8_t* out, int out_stride,
                     DeskewRec* rec, uint64_t* scores);
+  // local ink's stage form (ttr_ink_page, ttr_dbg_ink_page): a host image, placed as above, through ink_rows_kernel and ink_local_kernel -> bits
+  // [h][ceil(w / 64)], bitsT [w][ceil(h / 64)], the record; any may be null
+  void ink_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int radius, int drop, int polarity, uint64_t* bits_out,
+                 uint64_t* bitsT_out, InkRec* rec);
   void tables_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_len, int ink, const float* quads, int nq, int32_t* side_out,
                     int32_t* items_out, uint64_t* bits_out, int32_t* runs_out);
   // the stage form (ttr_curve_crops): a host image and host quads through the kind-1 packer and curve_crop_kernel -> flag [nq], hb [nq][2], spine [nq][2][9],
@@ -1189,6 +1212,7 @@ struct Engine {
     for (auto& d : stage_dev) f("stage_dev", d, kElU8);
     for (auto& d : split_in) f("split_in", d, kElF16);
     f("dsk_bits", dsk_bits, kElU8); f("dsk_bitsT", dsk_bitsT, kElU8); f("dsk_scores", dsk_scores, kElI32); f("dsk_rec", dsk_rec, kElI32);
+    f("dsk_ink_h", dsk_ink_h, kElU8); f("dsk_ink_rec", dsk_ink_rec, kElI32);
     for (auto& d : dsk_table) f("dsk_table", d, kElAddr);
     for (auto& d : dsk_pages) f("dsk_pages", d, kElU8);
     f("ccl.tnorm", ccl.tnorm, kElF32); f("ccl.flags", ccl.flags, kElU8); f("ccl.parent", ccl.parent, kElI32); f("ccl.mm", ccl.mm, kElI32);
@@ -1206,6 +1230,7 @@ struct Engine {
     f("lines_in", lines_in, kElI32); f("lines_side", lines_side, kElI32); f("alts_side", alts_side, kElI32);
     f("lex_side", lex_side, kElI32); f("lex_part", lex_part, kElI32); f("wide_side", wide_side, kElI32); f("curve_side", curve_side, kElI32);
     f("tab_bits", tab_bits, kElU8); f("tab_bitsT", tab_bitsT, kElU8); f("tab_runs", tab_runs, kElI32); f("tab_side", tab_side, kElI32);
+    f("tab_ink_h", tab_ink_h, kElU8); f("tab_ink_rec", tab_ink_rec, kElI32);
     f("blocks_side", blocks_side, kElI32);
     for (auto& d : chars_map) f("chars_map", d, kElF32);
     f("chars_in", chars_in, kElI32); f("chars_side", chars_side, kElI32);

@@ -244,6 +244,8 @@ void Engine::deskew_enqueue(PageBatch& B) {
   dsk_pages[sl].ensure(off[(size_t)n]); dsk_table[sl].ensure(rows_b); h_dsk_table[sl].ensure(rows_b); h_dsk[sl].ensure(rec_b);
   dsk_bits.ensure(tables_bits_slot(Hcap, Wcap) * 8 * n); dsk_bitsT.ensure(tables_bitsT_slot(Hcap, Wcap) * 8 * n);
   dsk_scores.ensure((size_t)n * (2 * M + 1) * 8); dsk_rec.ensure(rec_b);
+  const size_t ink_b = (size_t)n * sizeof(InkRec);
+  if (B.ink_radius) { dsk_ink_h.ensure(ink_ws_bytes(Hcap, Wcap, n)); dsk_ink_rec.ensure(ink_b); h_dsk_ink[sl].ensure(ink_b); }   // local ink: its workspace and records
   if (!dsk_cs_up) throw std::logic_error("deskew: the constants table was not uploaded");
   PageRow* rows = h_dsk_table[sl].as<PageRow>();
   for (int i = 0; i < n; ++i) {
@@ -255,10 +257,14 @@ void Engine::deskew_enqueue(PageBatch& B) {
   TTR_HIP_CHECK(hipStreamWaitEvent(stream, done_ev[sl], 0));
   TTR_HIP_CHECK(hipMemcpyAsync(dsk_table[sl].p, rows, rows_b, hipMemcpyHostToDevice, stream));
   const PageRow* src = dsk_table[sl].as<PageRow>();
-  launch_table_ink(nullptr, 0, 0, 0, 0, src, n, Hcap, Wcap, deskew_ink, dsk_bits.as<uint64_t>(), dsk_bitsT.as<uint64_t>(), stream);   // step 1: the source pages' ink
+  // step 1: the source pages' ink - under the local rule when the engine's radius is set (DESIGN.md "Local ink"), the same bitmaps either way
+  if (B.ink_radius) launch_ink_local(nullptr, 0, 0, 0, 0, src, n, Hcap, Wcap, B.ink_radius, B.ink_drop, B.ink_polarity, dsk_ink_h.as<uint32_t>(), dsk_ink_rec.as<InkRec>(),
+                                     dsk_bits.as<uint64_t>(), dsk_bitsT.as<uint64_t>(), stream);
+  else launch_table_ink(nullptr, 0, 0, 0, 0, src, n, Hcap, Wcap, deskew_ink, dsk_bits.as<uint64_t>(), dsk_bitsT.as<uint64_t>(), stream);
   launch_deskew_score(dsk_bits.as<uint64_t>(), src, n, Hcap, Wcap, M, dsk_scores.as<uint64_t>(), stream);
   launch_deskew_rotate(src, src + n, n, Hcap, Wcap, M, deskew_gain, dsk_scores.as<uint64_t>(), dsk_cs.as<int>(), dsk_rec.as<DeskewRec>(), stream);
   TTR_HIP_CHECK(hipMemcpyAsync(h_dsk[sl].p, dsk_rec.p, rec_b, hipMemcpyDeviceToHost, stream));   // the records: complete before the batch's components are (same stream, ahead of the detector)
+  if (B.ink_radius) TTR_HIP_CHECK(hipMemcpyAsync(h_dsk_ink[sl].p, dsk_ink_rec.p, ink_b, hipMemcpyDeviceToHost, stream));   // ... and the ink records with them
   for (int i = 0; i < n; ++i) { B.pages[i].data = rows[n + i].data; B.pages[i].stride = B.pages[i].w * 3; }
 }
 
@@ -310,6 +316,7 @@ void Engine::detect_enqueue(PageBatch& B) {
       if (P.h >= 32768 || P.w >= 32768) throw std::runtime_error("tables: a page side of 32768 px or more: ttr_engine_set_tables(e, 0, 0) first");
   // Deskew (DESIGN.md "Deskew"): every page's skew is estimated and the batch's pages become upright copies in the slot's buffer; everything below and behind
   // reads B.pages as ever.  Off: nothing here runs.
+  B.ink_radius = ink_radius; B.ink_drop = ink_drop; B.ink_polarity = ink_polarity;   // local ink: fixed for the batch here (the setter refuses while batches stream)
   B.dsk_M = deskew_M;
   if (B.dsk_M) {
     for (const Page& P : B.pages)
@@ -481,6 +488,8 @@ void Engine::detect_collect_local(PageBatch& B) {
   // deskew: the batch's records were copied ahead of its detector on the same stream, so they are here; taken now, before the slot's next batch overwrites them
   B.dsk_recs.clear();
   if (B.dsk_M) B.dsk_recs.assign(h_dsk[B.slot & 1].as<DeskewRec>(), h_dsk[B.slot & 1].as<DeskewRec>() + n);
+  B.dsk_ink_recs.clear();
+  if (B.dsk_M && B.ink_radius) B.dsk_ink_recs.assign(h_dsk_ink[B.slot & 1].as<InkRec>(), h_dsk_ink[B.slot & 1].as<InkRec>() + n);
   // the detector's range word of THIS batch, before any of its boxes is used: a saturated heat map fails this batch and no other
   if (range_flag_ptr() && B.det_groups == groups) { spin_event(group_ev[groups]); range_verify(kRangeDet0 + (B.slot & 1), "the detector of a batch of pages"); }
   if (tn.detector_only) for (auto& d : dets) d.clear();   // profiling (tools/prof_pages.py): the detector and CCL run, nothing goes to the recogniser
@@ -945,6 +954,11 @@ void Engine::tables_enqueue(const PageBatch& B, int sl) {
   const Page& P0 = B.pages[0];
   const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
   const int* centres = rects_dev.as<int>() + B.rects.size();
+  if (B.ink_radius) {   // local ink (DESIGN.md "Local ink"): the same bitmaps under the adaptive rule, and the pages' records beside the side blocks
+    tab_ink_h.ensure(ink_ws_bytes(Hcap, Wcap, n)); tab_ink_rec.ensure((size_t)n * sizeof(InkRec)); h_tab_ink[sl].ensure((size_t)n * sizeof(InkRec));
+    launch_ink_local(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, table, n, Hcap, Wcap, B.ink_radius, B.ink_drop, B.ink_polarity, tab_ink_h.as<uint32_t>(),
+                     tab_ink_rec.as<InkRec>(), tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  } else
   launch_table_ink(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, table, n, Hcap, Wcap, B.tab_ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
   launch_table_grid(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), P0.h, P0.w, table, n, Hcap, Wcap, B.tab_min_len, centres, centres + (size_t)N * 2, tab_runs.as<int>(),
                     tab_side.as<int>(), tab_side.as<int>() + (size_t)n * kTabSideInts, stream);
@@ -982,6 +996,30 @@ void Engine::tables_stage(const uint8_t* img, int h, int w, int row_stride, int 
   if (!tables_side_valid(side.data(), &why)) throw std::runtime_error("ttr_tables_page: the side block holds " + why);
   if (side_out) std::copy(side.begin(), side.begin() + kTabSideInts, side_out);   // (validated: the counted part is what callers read)
   if (items_out) std::copy(side.begin() + kTabSideInts, side.end(), items_out);
+}
+
+void Engine::ink_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int radius, int drop, int polarity, uint64_t* bits_out,
+                       uint64_t* bitsT_out, InkRec* rec) {
+  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("ttr_ink_page: bad image size");
+  if (h >= 32768 || w >= 32768) throw std::runtime_error("ttr_ink_page: a page side of 32768 px or more");
+  if (!ink_args_ok(radius, drop, polarity)) throw std::runtime_error("ttr_ink_page: radius must lie in 1..64, drop in 1..255 and polarity in 0..2");
+  const int ds = dev_stride ? dev_stride : w * 3;
+  if (dev_offset < 0 || ds < w * 3) throw std::runtime_error("ttr_ink_page: bad device offset or stride");
+  const size_t img_b = (size_t)dev_offset + (size_t)ds * h;
+  staging_img.ensure(img_b); tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8);
+  tab_ink_h.ensure(ink_ws_bytes(h, w, 1)); tab_ink_rec.ensure(sizeof(InkRec));
+  uint8_t* d_img = staging_img.as<uint8_t>() + dev_offset;
+  TTR_HIP_CHECK(hipMemcpy2DAsync(d_img, (size_t)ds, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  launch_ink_local(d_img, 0, ds, h, w, nullptr, 1, h, w, radius, drop, polarity, tab_ink_h.as<uint32_t>(), tab_ink_rec.as<InkRec>(), tab_bits.as<uint64_t>(),
+                   tab_bitsT.as<uint64_t>(), stream);
+  InkRec r{};
+  TTR_HIP_CHECK(hipMemcpyAsync(&r, tab_ink_rec.p, sizeof r, hipMemcpyDeviceToHost, stream));
+  if (bits_out) TTR_HIP_CHECK(hipMemcpyAsync(bits_out, tab_bits.p, tables_bits_slot(h, w) * 8, hipMemcpyDeviceToHost, stream));
+  if (bitsT_out) TTR_HIP_CHECK(hipMemcpyAsync(bitsT_out, tab_bitsT.p, tables_bitsT_slot(h, w) * 8, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  std::string why;
+  if (!ink_rec_valid(r, radius, drop, polarity, h, w, &why)) throw std::runtime_error("ttr_ink_page: the record holds " + why);
+  if (rec) *rec = r;
 }
 
 void Engine::recog_enqueue(PageBatch& B) {
@@ -1056,6 +1094,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (X) TTR_HIP_CHECK(hipMemcpyAsync(h_wide[sl].p, wide_side.p, B.wide.size() * 17 * 4, hipMemcpyDeviceToHost, stream));   // the wide words' cuts (the profile stays on the device)
     if (!B.curve.empty()) TTR_HIP_CHECK(hipMemcpyAsync(h_curve[sl].p, curve_side.p, curve_side_bytes(N), hipMemcpyDeviceToHost, stream));   // the curved words' side block
     if (B.tab_min_len) TTR_HIP_CHECK(hipMemcpyAsync(h_tab[sl].p, tab_side.p, ((size_t)B.n * kTabSideInts + (size_t)N * 2) * 4, hipMemcpyDeviceToHost, stream));   // the tables' side blocks and the words' cells
+    if (B.tab_min_len && B.ink_radius) TTR_HIP_CHECK(hipMemcpyAsync(h_tab_ink[sl].p, tab_ink_rec.p, (size_t)B.n * sizeof(InkRec), hipMemcpyDeviceToHost, stream));   // ... and their ink records
   } else {
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
@@ -1175,6 +1214,20 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
       r.skew_on = 1; r.skew = d;
     } else if (deskew_M && B.regions) {   // a region call: the caller's quadrilaterals are in the caller's frame
       r.skew_on = 1; r.skew = DeskewRec{0, 0, 65536, 0, B.pages[(size_t)pg].w, B.pages[(size_t)pg].h, 0, 0, 0, 0};
+    }
+    if (B.ink_radius && !B.regions && ((B.tab_min_len && N > 0) || B.dsk_M)) {   // local ink: the page's record - the tables pass's when it ran, else the deskew pass's - checked before anything is built on it
+      const bool from_tab = B.tab_min_len && N > 0;
+      if (!from_tab && B.dsk_ink_recs.size() != (size_t)n) throw std::runtime_error("local ink: the batch carries no records");
+      const InkRec k = from_tab ? h_tab_ink[B.slot].as<InkRec>()[pg] : B.dsk_ink_recs[(size_t)pg];
+      std::string why;
+      if (!ink_rec_valid(k, B.ink_radius, B.ink_drop, B.ink_polarity, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, &why))
+        throw std::runtime_error("local ink: the record of page " + std::to_string(pg) + " holds " + why);
+      if (from_tab && B.dsk_M) {   // both passes ran: the deskew pass's record is checked as well (its page is the caller's, of the same size)
+        if (B.dsk_ink_recs.size() != (size_t)n) throw std::runtime_error("local ink: the batch carries no records");
+        if (!ink_rec_valid(B.dsk_ink_recs[(size_t)pg], B.ink_radius, B.ink_drop, B.ink_polarity, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, &why))
+          throw std::runtime_error("local ink: the deskew pass's record of page " + std::to_string(pg) + " holds " + why);
+      }
+      r.ink_on = 1; r.ink = k;
     }
     if (B.tab_min_len && !B.regions && cnt > 0) {   // tables: the page's side block and its words' cells, checked before anything is built on them
       if (!tab_block) throw std::runtime_error("tables: the batch carries no side block");

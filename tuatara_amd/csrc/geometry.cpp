@@ -5,6 +5,7 @@
 #include "curve_rule.h"
 #include "tables_rule.h"
 #include "deskew_rule.h"
+#include "ink_rule.h"
 
 #include <algorithm>
 #include <climits>
@@ -1277,6 +1278,19 @@ int tables_from_page(const uint8_t* image, int h, int w, int stride, int min_len
   uint64_t* bits = bits_out;
   if (!bits) { own_bits.resize(tables_bitmap_words(h, w)); bits = own_bits.data(); }
   tables_ink(image, h, w, stride, ink, bits);
+  return tables_from_bits(bits, h, w, min_len, side, runs_out);
+}
+
+int tables_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_len, int radius, int drop, int polarity, int32_t* side) {
+  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !tables_args_ok(min_len, 128) || !ink_args_ok(radius, drop, polarity))
+    throw std::runtime_error("tables_from_page_ink: bad argument");
+  std::vector<uint64_t> bits(tables_bitmap_words(h, w));
+  ink_from_page(image, h, w, stride, radius, drop, polarity, bits.data(), nullptr, nullptr);
+  return tables_from_bits(bits.data(), h, w, min_len, side, nullptr);
+}
+
+// steps 2 - 7 behind a ready bitmap: the one body of the rule, whichever ink rule made the bits
+int tables_from_bits(const uint64_t* bits, int h, int w, int min_len, int32_t* side, int32_t* runs_out) {
   std::fill(side, side + kTabSideInts, 0);
   std::vector<int32_t> own_runs;
   int32_t* runs = runs_out;
@@ -1442,10 +1456,23 @@ void deskew_resample(const uint8_t* image, int h, int w, int stride, int C, int 
 }
 
 void deskew_from_page(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, int ink, uint8_t* out, int out_stride, DeskewRec* rec, uint64_t* scores) {
-  std::vector<uint64_t> bits(tables_bitmap_words(h, w)), sc((size_t)2 * max_slope + 1);
-  std::vector<int32_t> cs(2 * kDskSlopes);
+  std::vector<uint64_t> bits(tables_bitmap_words(h, w));
   tables_ink(image, h, w, stride, ink, bits.data());
-  deskew_scores(bits.data(), h, w, max_slope, sc.data());
+  deskew_from_bits(bits.data(), image, h, w, stride, max_slope, gain, out, out_stride, rec, scores);
+}
+
+void deskew_from_page_ink(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, int radius, int drop, int polarity, uint8_t* out, int out_stride,
+                          DeskewRec* rec, uint64_t* scores) {
+  std::vector<uint64_t> bits(tables_bitmap_words(h, w));
+  ink_from_page(image, h, w, stride, radius, drop, polarity, bits.data(), nullptr, nullptr);
+  deskew_from_bits(bits.data(), image, h, w, stride, max_slope, gain, out, out_stride, rec, scores);
+}
+
+// steps 2 - 5 behind a ready bitmap: the one body of the rule, whichever ink rule made the bits
+void deskew_from_bits(const uint64_t* bits, const uint8_t* image, int h, int w, int stride, int max_slope, int gain, uint8_t* out, int out_stride, DeskewRec* rec, uint64_t* scores) {
+  std::vector<uint64_t> sc((size_t)2 * max_slope + 1);
+  std::vector<int32_t> cs(2 * kDskSlopes);
+  deskew_scores(bits, h, w, max_slope, sc.data());
   deskew_consts(cs.data());
   DeskewRec r;
   deskew_choose(sc.data(), max_slope, gain, h, w, cs.data(), &r);
@@ -1472,6 +1499,52 @@ void deskew_to_page(const DeskewRec& r, const float* xy_in, int n, float* xy_out
     xy_out[2 * (size_t)i] = (float)(cx + ((double)r.C * x - (double)r.S * y) / 65536.0);
     xy_out[2 * (size_t)i + 1] = (float)(cy + ((double)r.S * x + (double)r.C * y) / 65536.0);
   }
+}
+
+// ---- local ink (DESIGN.md "Local ink"): the host rule; the steps themselves are ink_rule.h's
+void ink_from_page(const uint8_t* image, int h, int w, int stride, int radius, int drop, int polarity, uint64_t* bits, uint64_t* bitsT, InkRec* rec) {
+  if (!image || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !ink_args_ok(radius, drop, polarity)) throw std::runtime_error("ink_from_page: bad argument");
+  const int R = radius, nwx = (w + 63) / 64, nwy = (h + 63) / 64;
+  // 1, 3: s and its horizontal window sums, by a prefix sum along each row; the page's sum
+  std::vector<uint16_t> s((size_t)h * w);
+  std::vector<uint32_t> H((size_t)h * w), pre((size_t)w + 1);
+  uint64_t sum = 0;
+  for (int y = 0; y < h; ++y) {
+    const uint8_t* row = image + (size_t)y * stride;
+    uint16_t* sr = &s[(size_t)y * w];
+    pre[0] = 0;
+    for (int x = 0; x < w; ++x) { sr[x] = (uint16_t)((int)row[3 * x] + (int)row[3 * x + 1] + (int)row[3 * x + 2]); pre[(size_t)x + 1] = pre[x] + sr[x]; }
+    sum += pre[(size_t)w];
+    for (int x = 0; x < w; ++x) H[(size_t)y * w + x] = pre[(size_t)std::min(x + R, w - 1) + 1] - pre[(size_t)std::max(x - R, 0)];
+  }
+  const int inverted = ink_inverted(polarity, sum, h, w);   // 2
+  if (rec) *rec = InkRec{radius, drop, polarity, inverted, sum, w, h};
+  if (bits) std::fill(bits, bits + (size_t)h * nwx, (uint64_t)0);
+  if (bitsT) std::fill(bitsT, bitsT + (size_t)w * nwy, (uint64_t)0);
+  // 3, 4: the vertical sums by a running add and subtract down the columns, then the rule
+  std::vector<uint32_t> S((size_t)w, 0u);
+  for (int yy = 0; yy <= std::min(R, h - 1); ++yy)
+    for (int x = 0; x < w; ++x) S[x] += H[(size_t)yy * w + x];
+  for (int y = 0; y < h; ++y) {
+    const int ny = ink_span(y, R, h);
+    for (int x = 0; x < w; ++x) {
+      if (!ink_local(s[(size_t)y * w + x], ink_span(x, R, w) * ny, S[x], drop, inverted)) continue;
+      if (bits) bits[(size_t)y * nwx + (x >> 6)] |= (uint64_t)1 << (x & 63);
+      if (bitsT) bitsT[(size_t)x * nwy + (y >> 6)] |= (uint64_t)1 << (y & 63);
+    }
+    if (y + 1 + R <= h - 1) for (int x = 0; x < w; ++x) S[x] += H[(size_t)(y + 1 + R) * w + x];
+    if (y - R >= 0) for (int x = 0; x < w; ++x) S[x] -= H[(size_t)(y - R) * w + x];
+  }
+}
+
+bool ink_rec_valid(const InkRec& r, int radius, int drop, int polarity, int h, int w, std::string* why) {
+  auto bad = [&](const char* m) { if (why) *why = m; return false; };
+  if (r.radius != radius || r.drop != drop || r.polarity != polarity) return bad("parameters that are not the engine's");
+  if (r.w != w || r.h != h) return bad("another page's size");
+  if (r.sum > (uint64_t)kInkSMax * (uint64_t)h * (uint64_t)w) return bad("a sum beyond 765 h w");
+  if (r.inverted != 0 && r.inverted != 1) return bad("an inverted flag that is neither 0 nor 1");
+  if (r.inverted != ink_inverted(polarity, r.sum, h, w)) return bad("an inverted flag that does not follow from polarity and sum");
+  return true;
 }
 
 }  // namespace ttr

@@ -181,6 +181,21 @@ bool deskew_rec_valid(const DeskewRec& r, int max_slope, int h, int w, const int
 // 6: n points (x, y) of the upright page -> the caller's page, computed in double
 void deskew_to_page(const DeskewRec& r, const float* xy_in, int n, float* xy_out);
 
+// Local ink (ttr_engine_set_ink; DESIGN.md "Local ink").  The adaptive threshold of ink_rule.h, shared with ink_rows_kernel and ink_local_kernel (ink.hip):
+// a pixel is ink when it is darker - or, inverted, lighter - than its window's mean by `drop` 256ths.  radius 1..64, drop 1..255, polarity 0 dark, 1 light, 2 auto.
+struct InkRec;
+// the bitmap of a page u8 [h][w][3] in tables_ink's layout; bitsT (may be null) [w][ceil(h / 64)] the same bits along y; rec (may be null) the page's record
+void ink_from_page(const uint8_t* image, int h, int w, int stride, int radius, int drop, int polarity, uint64_t* bits, uint64_t* bitsT, InkRec* rec);
+// what decode_pages accepts from the device: the parameters asked for, the page's size, and an `inverted` that follows from polarity and sum
+bool ink_rec_valid(const InkRec& r, int radius, int drop, int polarity, int h, int w, std::string* why = nullptr);
+// tables_from_page and deskew_from_page behind a ready bitmap (tables_ink's layout): the one body of each rule
+int tables_from_bits(const uint64_t* bits, int h, int w, int min_len, int32_t* side, int32_t* runs = nullptr);
+void deskew_from_bits(const uint64_t* bits, const uint8_t* image, int h, int w, int stride, int max_slope, int gain, uint8_t* out, int out_stride, DeskewRec* rec, uint64_t* scores);
+// ... and under the local rule in the place of `ink`
+int tables_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_len, int radius, int drop, int polarity, int32_t* side);
+void deskew_from_page_ink(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, int radius, int drop, int polarity, uint8_t* out, int out_stride,
+                          DeskewRec* rec, uint64_t* scores);
+
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.
 struct Component {

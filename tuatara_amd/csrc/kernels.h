@@ -387,6 +387,14 @@ void launch_table_ink(const uint8_t* images, size_t page_bytes, int stride, int 
 // runs int32 [pages][2][8192][3] (workspace: the run lists); side int32 [pages][kTabSideInts] (tables_rule.h); items int32 [N][2] = table, cell
 void launch_table_grid(const uint64_t* bits, const uint64_t* bitsT, int h, int w, const PageRow* table, int pages, int Hcap, int Wcap, int min_len, const int* centres,
                        const int* first, int* runs, int* side, int* items, hipStream_t s);
+// ---- ink.hip (DESIGN.md "Local ink")
+struct InkRec;
+// the workspace of a launch: one uint32 per pixel of every page's Hcap x Wcap slot
+inline size_t ink_ws_bytes(int Hcap, int Wcap, int pages) { return (size_t)Hcap * (size_t)Wcap * 4 * (size_t)pages; }
+// ink_rows_kernel + ink_local_kernel: launch_table_ink's pages, bitmaps and layout under the local rule of ink_rule.h (radius 1..64, drop 1..255, polarity 0..2).
+// Hws: ink_ws_bytes of workspace; recs [pages]: zeroed here on the stream, then each page's sum and record
+void launch_ink_local(const uint8_t* images, size_t page_bytes, int stride, int h, int w, const PageRow* table, int pages, int Hcap, int Wcap, int radius, int drop,
+                      int polarity, uint32_t* Hws, InkRec* recs, uint64_t* bits, uint64_t* bitsT, hipStream_t s);
 // ---- deskew.hip (DESIGN.md "Deskew")
 struct DeskewRec;
 // deskew_score_kernel: step 2 on every page, one workgroup per (slope, page).  bits as table_ink_kernel wrote them for a launch of Hcap x Wcap (both below 8192);

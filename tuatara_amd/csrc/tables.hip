@@ -6,6 +6,7 @@
 //                    so a wave reads 768 contiguous bytes of a row; the four ink bits of a lane are shifted to their place and OR-ed over 16 lanes (shuffles)
 //                    into the row's four words; a wave issues the loads of its 16 rows before it uses the first.  Any other page (a window into a larger image) is read by bytes, a lane a pixel, and __ballot forms the word.
 //                    The tile's 64 x 4 words go through LDS once: out as they are, and transposed (thread x collects bit x of the 64 rows).
+//                    (ink_tile.h: ink_tile_store - the local rule's ink_local_kernel, ink.hip, leaves its tiles through the same function.)
 // table_grid_kernel  everything behind the bitmaps, one workgroup of 1024 threads per page.  First the runs of both directions, by per-line count, block scan and write (the
 //                    rule's order, no atomics), into the launch's run lists in global memory; then per direction union-find in LDS by compare-and-swap, the smaller root winning
 //                    (the scheme of block_group_kernel); the components' extents and areas by LDS atomics on integers; rulings numbered by a block scan over
@@ -15,24 +16,11 @@
 // Integer arithmetic only: the outputs are the host rule's (geometry.cpp: tables_from_page) bit for bit.
 #include "common.h"
 #include "kernels.h"
+#include "ink_tile.h"
 #include "page_table.h"
 #include "tables_rule.h"
 
 namespace ttr {
-
-namespace {
-
-struct __attribute__((aligned(4))) TabPx4 { uint32_t a, b, c; };   // four pixels
-
-struct TabPage { const uint8_t* data; int h, w, stride; };
-__device__ __forceinline__ TabPage tab_page(const uint8_t* images, size_t page_bytes, int stride, int h, int w, const PageRow* table, int pg) {
-  if (table) { const PageRow r = table[pg]; return TabPage{r.data, r.h, r.w, r.stride}; }
-  return TabPage{images + (size_t)pg * page_bytes, h, w, stride};
-}
-
-constexpr int kInkTileW = 256, kInkTileH = 64;
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void table_ink_kernel(const uint8_t* __restrict__ images, size_t page_bytes, int stride_, int h_, int w_, const PageRow* __restrict__ table,
                                                         int Hcap, int Wcap, int ink, unsigned long long* __restrict__ bits, unsigned long long* __restrict__ bitsT) {
@@ -88,18 +76,7 @@ __global__ __launch_bounds__(256) void table_ink_kernel(const uint8_t* __restric
     }
   }
   __syncthreads();
-  const int nwx = (P.w + 63) >> 6, nwy = (P.h + 63) >> 6;
-  {
-    const int row = tid >> 2, k = tid & 3, y = y0 + row, wx = (int)blockIdx.x * 4 + k;
-    if (y < P.h && wx < nwx) bits[(size_t)pg * ((size_t)Hcap * (size_t)((Wcap + 63) >> 6)) + (size_t)y * nwx + wx] = tile[row][k];
-  }
-  const int x = x0 + tid;
-  if (x < P.w) {
-    const int k = tid >> 6, b = tid & 63;
-    unsigned long long col = 0;
-    for (int r = 0; r < kInkTileH; ++r) col |= ((tile[r][k] >> b) & 1ull) << r;
-    bitsT[(size_t)pg * ((size_t)Wcap * (size_t)((Hcap + 63) >> 6)) + (size_t)x * nwy + (int)blockIdx.y] = col;
-  }
+  ink_tile_store(tile, P.w, P.h, pg, Hcap, Wcap, bits, bitsT);   // (ink_tile.h: the layout every ink rule writes)
 }
 
 namespace {

@@ -65,6 +65,7 @@ thread_local std::string g_call_error;   // last_call_error()
 thread_local int g_call_tiled = 0;       // set_tiled(): the overlap of this thread's calls, 0 = off (then TUATARA_TILED decides)
 thread_local int g_call_tables = 0, g_call_tables_ink = 128;   // set_tables(): min_len and ink of this thread's calls, 0 = off (then TUATARA_TABLES decides)
 thread_local std::vector<TableGrid> g_call_table_out;          // last_call_tables()
+thread_local int g_call_ink = 0, g_call_ink_drop = 38, g_call_ink_polarity = 2;   // set_local_ink(): this thread's calls, 0 = off (then TUATARA_LOCAL_INK decides)
 thread_local int g_call_deskew = 0, g_call_deskew_gain = 288, g_call_deskew_ink = 128;   // set_deskew(): this thread's calls, 0 = off (then TUATARA_DESKEW decides)
 thread_local PageSkew g_call_skew_out;                         // last_call_skew()
 struct CharsetScope {
@@ -74,6 +75,7 @@ struct CharsetScope {
   bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false, curved_set = false, fuzzy_set = false, tiled_set = false;
   bool tables_set = false;
   bool deskew_set = false;
+  bool ink_set = false;
   CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
                std::string pattern = std::string(), float wide = 0.f, bool pattern_best = false, bool curved = false, LexFuzzy fuzzy = LexFuzzy{-1, 0.f}) : e(e_) {
     {
@@ -129,6 +131,12 @@ struct CharsetScope {
       if (ttr_engine_set_deskew(e, dsk, g_call_deskew_gain, g_call_deskew_ink) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
       deskew_set = true;
     }
+    int link = g_call_ink;
+    if (link == 0) if (const char* p = std::getenv("TUATARA_LOCAL_INK")) link = std::string(p) == "1" ? 16 : std::atoi(p);
+    if (link != 0) {   // local ink (DESIGN.md "Local ink"): radius, drop and polarity for the call, like the set
+      if (ttr_engine_set_ink(e, link, g_call_ink_drop, g_call_ink_polarity) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      ink_set = true;
+    }
     if (!curved) if (const char* p = std::getenv("TUATARA_CURVED")) curved = std::string(p) == "1";
     if (curved) {   // curved words (DESIGN.md "Curved words"): on for the call, like the set
       if (ttr_engine_set_curved(e, 1) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
@@ -157,6 +165,7 @@ struct CharsetScope {
     if (tiled_set) ttr_engine_set_tiled(e, 0);
     if (tables_set) ttr_engine_set_tables(e, 0, 0);
     if (deskew_set) ttr_engine_set_deskew(e, 0, 0, 0);
+    if (ink_set) ttr_engine_set_ink(e, 0, 0, 0);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
     if (alts_set) ttr_engine_set_alternatives(e, 0);
     if (fuzzy_set) ttr_engine_set_lexicon_fuzzy(e, -1, 0.f);
@@ -557,6 +566,8 @@ int tables() { return g_call_tables; }
 std::vector<TableGrid> last_call_tables() { return g_call_table_out; }
 void set_deskew(int max_slope, int gain, int ink) { g_call_deskew = max_slope; g_call_deskew_gain = gain; g_call_deskew_ink = ink; }
 int deskew() { return g_call_deskew; }
+void set_local_ink(int radius, int drop, int polarity) { g_call_ink = radius; g_call_ink_drop = drop; g_call_ink_polarity = polarity; }
+int local_ink() { return g_call_ink; }
 PageSkew last_call_skew() { return g_call_skew_out; }
 void PageSkew::to_page(float x, float y, float* xs, float* ys) const {
   const float in[2] = {x, y};

@@ -302,6 +302,15 @@ SYMBOLS = [
     ("ttr_deskew_from_page", _I, [_PU8, _I, _I, _I, _I, _I, _I, _PU8, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("ttr_deskew_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _PU8, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("ttr_dbg_deskew_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, _I, _PU8, C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("ttr_engine_set_ink", _I, [_VP, _I, _I, _I]),
+    ("ttr_engine_ink", _I, [_VP, _PI, _PI]),
+    ("ttr_result_ink", _I, [_VP, C.c_void_p]),
+    ("ttr_results_gather_ink", _I, [C.POINTER(_VP), _I, C.c_void_p]),
+    ("ttr_ink_from_page", _I, [_PU8, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    ("ttr_ink_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    ("ttr_dbg_ink_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    ("ttr_tables_from_page_ink", _I, [_PU8, _I, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI, _PI, _PI, _PI, _PI]),
+    ("ttr_deskew_from_page_ink", _I, [_PU8, _I, _I, _I, _I, _I, _I, _I, _I, _PU8, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("ttr_engine_set_tiled", _I, [_VP, _I]),
     ("ttr_engine_tiled", _I, [_VP]),
     ("ttr_result_tiles", _I, [_VP]),
@@ -1118,6 +1127,78 @@ def deskew_from_page(image, max_slope: int = DESKEW_MAX_SLOPE, gain: int = DESKE
     return _deskew_call(fn, image, max_slope, gain, ink, row_stride)
 
 
+LOCAL_INK_RADIUS, LOCAL_INK_DROP, LOCAL_INK_POLARITY = 16, 38, 2   # what local_ink=True means (DESIGN.md "Local ink": none of them has been tuned on documents)
+INK_DARK, INK_LIGHT, INK_AUTO = 0, 1, 2
+
+
+class Ink(C.Structure):
+    """ttr_ink: one page's local-ink record"""
+    _fields_ = [("radius", C.c_int32), ("drop", C.c_int32), ("polarity", C.c_int32), ("inverted", C.c_int32), ("sum", C.c_uint64), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+def _local_ink_arg(local_ink):
+    """False / None / 0 -> (0, drop, polarity defaults); True -> the defaults; (radius, drop, polarity) or a bare radius otherwise"""
+    if local_ink is None or local_ink is False or (isinstance(local_ink, int) and not isinstance(local_ink, bool) and local_ink == 0):
+        return 0, LOCAL_INK_DROP, LOCAL_INK_POLARITY
+    if local_ink is True:
+        return LOCAL_INK_RADIUS, LOCAL_INK_DROP, LOCAL_INK_POLARITY
+    if isinstance(local_ink, (tuple, list)) and len(local_ink) == 3:
+        return int(local_ink[0]), int(local_ink[1]), int(local_ink[2])
+    if isinstance(local_ink, int):
+        return int(local_ink), LOCAL_INK_DROP, LOCAL_INK_POLARITY
+    raise EngineError("local_ink must be False, True or (radius, drop, polarity)")
+
+
+def _ink_dict(rec) -> dict:
+    """a ttr_ink as the dict PageResult.ink carries"""
+    return {k: int(getattr(rec, k)) for k in ("radius", "drop", "polarity", "inverted", "sum", "w", "h")}
+
+
+def _ink_call(fn, image, radius, drop, polarity, row_stride=0):
+    """the shared body of ink_from_page and Engine.ink_page: fn(image..., outputs...) -> the dict both return"""
+    image = np.asarray(image, dtype=np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise RuntimeError("Input array should have 3 dimensions")
+    if not row_stride:
+        image = np.ascontiguousarray(image)
+    h, w = image.shape[:2]
+    bits, bitsT, rec = np.zeros((h, (w + 63) // 64), np.uint64), np.zeros((w, (h + 63) // 64), np.uint64), Ink()
+    u64 = C.POINTER(C.c_uint64)
+    fn(_u8(image), h, w, int(row_stride) or w * 3, int(radius), int(drop), int(polarity), bits.ctypes.data_as(u64), bitsT.ctypes.data_as(u64), C.addressof(rec))
+    return {"bits": bits, "bitsT": bitsT, "ink": _ink_dict(rec)}
+
+
+def ink_from_page(image, radius: int = LOCAL_INK_RADIUS, drop: int = LOCAL_INK_DROP, polarity: int = LOCAL_INK_POLARITY, row_stride: int = 0) -> dict:
+    """The local ink rule on the host (ttr_ink_from_page, no GPU; DESIGN.md "Local ink"): a host image u8 [H, W, 3] (row_stride: the bytes from row to row of a
+    view into a wider buffer) -> {"bits" u64 [H, ceil(W / 64)] (bit x % 64 of word x / 64), "bitsT" u64 [W, ceil(H / 64)] the same bits along y, "ink" the
+    record as PageResult.ink carries it}."""
+    lib = load()
+
+    def fn(*a):
+        _lib_check(lib.ttr_ink_from_page(*a))
+    return _ink_call(fn, image, radius, drop, polarity, row_stride)
+
+
+def tables_from_page_ink(image, quads=None, min_len: int = TABLES_MIN_LEN, local_ink=True, row_stride: int = 0) -> dict:
+    """tables_from_page under the local ink rule (ttr_tables_from_page_ink): local_ink = True or (radius, drop, polarity) in the place of ink"""
+    lib = load()
+    r, d, p = _local_ink_arg(local_ink)
+
+    def fn(img, h, w, stride, min_len_, _ink, *rest):
+        _lib_check(lib.ttr_tables_from_page_ink(img, h, w, stride, min_len_, r, d, p, *rest))
+    return _tables_call(fn, image, quads, min_len, 0, row_stride)
+
+
+def deskew_from_page_ink(image, max_slope: int = DESKEW_MAX_SLOPE, gain: int = DESKEW_GAIN, local_ink=True, row_stride: int = 0) -> dict:
+    """deskew_from_page under the local ink rule (ttr_deskew_from_page_ink): local_ink = True or (radius, drop, polarity) in the place of ink"""
+    lib = load()
+    r, d, p = _local_ink_arg(local_ink)
+
+    def fn(img, h, w, stride, max_slope_, gain_, _ink, *rest):
+        _lib_check(lib.ttr_deskew_from_page_ink(img, h, w, stride, max_slope_, gain_, r, d, p, *rest))
+    return _deskew_call(fn, image, max_slope, gain, 0, row_stride)
+
+
 def table_line_lists(tables, lines) -> list:
     """the flat line values of a result split per table: [(row lines i32 [rows + 1], column lines i32 [cols + 1]), ...] in doubled px"""
     out, k = [], 0
@@ -1175,8 +1256,10 @@ class PageResult(collections.abc.Sequence):
     `tables` the list of {"bbox", "rows", "cols", "cells": [{"row", "col", "rowspan", "colspan", "bbox", "items", "text"}]} and table_grid(t) its rows x cols
     strings; rulings is None, tables [] when tables are off and for a page without items.  Deskew (Engine.set_deskew; DESIGN.md "Deskew"): `skew` = the page's
     record {"slope", "found", "C", "S", "w", "h", "mode", "score0", "score_found", "degrees"} or None when the layer is off; every coordinate of the result is
-    in the upright page's frame, to_page(points) maps points to the caller's page and every dict gains "quad_page"."""
-    __slots__ = ("skew", "quad_page",
+    in the upright page's frame, to_page(points) maps points to the caller's page and every dict gains "quad_page".  Local ink (Engine.set_local_ink; DESIGN.md
+    "Local ink"): `ink` = the page's record {"radius", "drop", "polarity", "inverted", "sum", "w", "h"} - the tables pass's when tables ran, else the deskew
+    pass's - or None when no pass of the page ran under it."""
+    __slots__ = ("skew", "quad_page", "ink",
                  "table_mode", "rulings", "table_rects", "table_lines", "cells", "item_table", "item_cell", "cell_texts",
                  "texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
@@ -1192,8 +1275,9 @@ class PageResult(collections.abc.Sequence):
                  alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None, pattern_logp=None,
                  piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None,
                  curved=None, outline=None, spine_knots=None, lex_edits=None, lex_band=-1, tiles=0,
-                 table_mode=0, rulings=None, table_rects=None, table_lines=None, cells=None, item_table=None, item_cell=None, cell_texts=None, skew=None, quad_page=None):
+                 table_mode=0, rulings=None, table_rects=None, table_lines=None, cells=None, item_table=None, item_cell=None, cell_texts=None, skew=None, quad_page=None, ink=None):
         self.tiles = tiles
+        self.ink = ink
         self.skew, self.quad_page = skew, quad_page     # quad_page f32 [n, 8]: every quad on the caller's page (ttr_result_to_page), None without deskew or quads
         self.table_mode, self.rulings, self.table_rects, self.table_lines, self.cells = table_mode, rulings, table_rects, table_lines, cells
         self.item_table, self.item_cell, self.cell_texts = item_table, item_cell, cell_texts
@@ -1399,6 +1483,7 @@ class Engine:
         tiled = _tiled_arg(overrides.pop("tiled", None))                                  # nor this: set_tiled, below
         tables = _tables_arg(overrides.pop("tables", None))                               # nor this: set_tables, below
         deskew = _deskew_arg(overrides.pop("deskew", None))                               # nor this: set_deskew, below
+        local_ink = _local_ink_arg(overrides.pop("local_ink", None))                      # nor this: set_local_ink, below
         self._lex_words = []
         tuning = {k: overrides.pop(k) for k in list(overrides) if not hasattr(cfg, k)}     # not a config field: a tuning key (below)
         for k, v in overrides.items():
@@ -1430,6 +1515,39 @@ class Engine:
             self.set_tables(tables)
         if deskew[0]:
             self.set_deskew(deskew)
+        if local_ink[0]:
+            self.set_local_ink(local_ink)
+
+    def set_local_ink(self, local_ink=True):
+        """Take the ink bitmap of the engine's tables and deskew passes from the adaptive threshold (ttr_engine_set_ink; DESIGN.md "Local ink"): False / 0 = off,
+        True = (16, 38, 2), else (radius, drop, polarity) with radius in 1..64 px, drop in 1..255 (1/256ths) and polarity 0 dark / 1 light / 2 auto (none of the
+        defaults has been tuned on documents).  With neither tables nor deskew on nothing runs; the stage calls keep the fixed rule.  PageResult.ink carries the
+        page's record.  Raises EngineError, and changes nothing, for other values and between a stream_push and its flush."""
+        r, d, p = _local_ink_arg(local_ink)
+        if self.lib.ttr_engine_set_ink(self.h, r, d, p) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    @property
+    def local_ink(self):
+        """(radius, drop, polarity) in force, or None when local ink is off"""
+        d, p = C.c_int(), C.c_int()
+        r = int(self.lib.ttr_engine_ink(self.h, C.byref(d), C.byref(p)))
+        return (r, int(d.value), int(p.value)) if r else None
+
+    @staticmethod
+    def ink_from_page(image, radius: int = LOCAL_INK_RADIUS, drop: int = LOCAL_INK_DROP, polarity: int = LOCAL_INK_POLARITY, row_stride: int = 0) -> dict:
+        """the module's ink_from_page: the local ink rule on the host, no GPU"""
+        return ink_from_page(image, radius, drop, polarity, row_stride)
+
+    def ink_page(self, image, radius: int = LOCAL_INK_RADIUS, drop: int = LOCAL_INK_DROP, polarity: int = LOCAL_INK_POLARITY, dev_offset: int = 0, dev_stride: int = 0) -> dict:
+        """ttr_ink_page: ink_rows_kernel and ink_local_kernel on a host image u8 [H, W, 3], whatever the engine's setting -> the dict ink_from_page returns.
+        dev_offset / dev_stride (ttr_dbg_ink_page): the image is placed dev_offset bytes into a device buffer with dev_stride bytes from row to row (0 = 3 W)."""
+        def fn(*a):
+            if dev_offset or dev_stride:
+                self._check(self.lib.ttr_dbg_ink_page(self.h, *a[:4], int(dev_offset), int(dev_stride), *a[4:]))
+            else:
+                self._check(self.lib.ttr_ink_page(self.h, *a))
+        return _ink_call(fn, image, radius, drop, polarity)
 
     def set_deskew(self, deskew=True):
         """Estimate every page's skew on the GPU and read the page upright (ttr_engine_set_deskew; DESIGN.md "Deskew"): False / 0 = off, True = (64, 288, 128),
@@ -1931,6 +2049,8 @@ class Engine:
                 raise EngineError("ttr_results_gather_curved: bad arguments")
         skews = (Skew * max(n, 1))()            # deskew: every page's record, one call (zeroes where a result has none)
         self.lib.ttr_results_gather_skew(arr, n, C.addressof(skews))
+        inks = (Ink * max(n, 1))()              # local ink: likewise
+        self.lib.ttr_results_gather_ink(arr, n, C.addressof(inks))
         out, k, kl, kc, kbl, kb, kp = [], 0, 0, 0, 0, 0, 0
         for i in range(n):
             c = int(counts[i])
@@ -1952,6 +2072,8 @@ class Engine:
                     le = self.lib.ttr_result_lex_edits_all(arr[i])
                     lex.update(lex_band=band, lex_edits=np.ctypeslib.as_array(le, (c, M)).copy() if le else np.zeros((0, M), np.int32))
             lex["tiles"] = int(self.lib.ttr_result_tiles(arr[i]))
+            if self.lib.ttr_result_ink(arr[i], None):    # local ink: the page's record
+                lex["ink"] = _ink_dict(inks[i])
             if self.lib.ttr_result_skew(arr[i], None):   # deskew: the page's record, and its quads on the caller's page
                 lex["skew"] = _skew_dict(skews[i])
                 if self.rectified:
