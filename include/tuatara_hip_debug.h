@@ -48,6 +48,12 @@ int ttr_dbg_craft_tap_count(ttr_engine* e);
 int ttr_dbg_craft_tap_info(ttr_engine* e, int i, char* text, size_t cap, int dims[7]);
 /* tensor i joined to fp32 on the host (split.h: join2 / join3, every step exact), f32 [B][H][W][row length]: padding channels included */
 int ttr_dbg_craft_tap_read(ttr_engine* e, int i, float* out);
+/* With the tuning key fc7_fold on (the default) the pass proper runs upconv1.0 as slice5.1 + slice5.2 + upconv1.0 folded into one 3x3 plus the skip half's 1x1;
+ * a tapped pass additionally runs the three layers themselves into side workspaces nothing reads, and the records above are THEIRS.  The folded launches'
+ * records are a second list: layer "upconv1.0", roles in0 (the 3x3 max-pool's output), in1 (relu5_3), z (the skip half, fp32) and out.  Same calls as above. */
+int ttr_dbg_craft_fold_tap_count(ttr_engine* e);
+int ttr_dbg_craft_fold_tap_info(ttr_engine* e, int i, char* text, size_t cap, int dims[7]);
+int ttr_dbg_craft_fold_tap_read(ttr_engine* e, int i, float* out);
 /* Which kernel serves bf16 layers: -1 = first-generation igemm only, 0 = automatic (default),
  * 1..6 = force that gemm2 tile configuration where it applies.  Process-wide; for tuning and tests. */
 void ttr_set_gemm_config(int cfg);

@@ -408,12 +408,14 @@ int ttr_dbg_craft_taps(ttr_engine* e, const uint8_t* canvas, int B, int H, int W
 
 int ttr_dbg_craft_tap_count(ttr_engine* e) { return e ? (int)e->e->craft_taps.size() : -1; }
 
-int ttr_dbg_craft_tap_info(ttr_engine* e, int i, char* text, size_t cap, int dims[7]) {
+// (list 0: craft_taps, the pass's layers; list 1: craft_fold_taps, the folded upconv1.0 launches of a tapped pass with fc7_fold on)
+static int craft_tap_info(ttr_engine* e, int list, int i, char* text, size_t cap, int dims[7]) {
   TTR_GUARD_BEGIN
   Engine& E = *e->e;
   EngineScope lk(E);
-  if (i < 0 || i >= (int)E.craft_taps.size()) throw std::runtime_error("ttr_dbg_craft_tap_info: no such record");
-  const Engine::CraftTap& t = E.craft_taps[i];
+  const std::vector<Engine::CraftTap>& taps = list ? E.craft_fold_taps : E.craft_taps;
+  if (i < 0 || i >= (int)taps.size()) throw std::runtime_error("ttr_dbg_craft_tap_info: no such record");
+  const Engine::CraftTap& t = taps[i];
   const std::string s = t.layer + "\n" + t.role + "\n" + t.kind;
   if (!text || cap < s.size() + 1) throw std::runtime_error("ttr_dbg_craft_tap_info: text buffer too small");
   memcpy(text, s.c_str(), s.size() + 1);
@@ -423,12 +425,13 @@ int ttr_dbg_craft_tap_info(ttr_engine* e, int i, char* text, size_t cap, int dim
   TTR_GUARD_END(-1)
 }
 
-int ttr_dbg_craft_tap_read(ttr_engine* e, int i, float* out) {
+static int craft_tap_read(ttr_engine* e, int list, int i, float* out) {
   TTR_GUARD_BEGIN
   Engine& E = *e->e;
   EngineScope lk(E);
-  if (i < 0 || i >= (int)E.craft_taps.size()) throw std::runtime_error("ttr_dbg_craft_tap_read: no such record");
-  const Engine::CraftTap& t = E.craft_taps[i];
+  const std::vector<Engine::CraftTap>& taps = list ? E.craft_fold_taps : E.craft_taps;
+  if (i < 0 || i >= (int)taps.size()) throw std::runtime_error("ttr_dbg_craft_tap_read: no such record");
+  const Engine::CraftTap& t = taps[i];
   const size_t M = (size_t)t.B * t.H * t.W, ld = (size_t)t.ld;
   TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
   if (t.form == Engine::kTapF32) { TTR_HIP_CHECK(hipMemcpy(out, t.p, M * ld * 4, hipMemcpyDeviceToHost)); return 0; }
@@ -450,6 +453,12 @@ int ttr_dbg_craft_tap_read(ttr_engine* e, int i, float* out) {
   return 0;
   TTR_GUARD_END(-1)
 }
+
+int ttr_dbg_craft_tap_info(ttr_engine* e, int i, char* text, size_t cap, int dims[7]) { return craft_tap_info(e, 0, i, text, cap, dims); }
+int ttr_dbg_craft_tap_read(ttr_engine* e, int i, float* out) { return craft_tap_read(e, 0, i, out); }
+int ttr_dbg_craft_fold_tap_count(ttr_engine* e) { return e ? (int)e->e->craft_fold_taps.size() : -1; }
+int ttr_dbg_craft_fold_tap_info(ttr_engine* e, int i, char* text, size_t cap, int dims[7]) { return craft_tap_info(e, 1, i, text, cap, dims); }
+int ttr_dbg_craft_fold_tap_read(ttr_engine* e, int i, float* out) { return craft_tap_read(e, 1, i, out); }
 
 void ttr_set_gemm_config(int cfg) { set_gemm_config(cfg); }
 

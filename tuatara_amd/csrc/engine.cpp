@@ -227,6 +227,8 @@ void Engine::load_craft(const std::string& dir) {
     struct DropScope { bool& f; ~DropScope() { f = false; } } drop_scope{drop_w1};
     { const char* ev = getenv("TUATARA_CRAFT_PRODUCTS"); drop_w1 = ev && std::string(ev) == "2" && c.cin >= 64 && nm.rfind("conv_cls", 0) != 0; }
     upload_linear(L, w.data.data(), c.cout, taps * c.cin, b.data.data(), cout_pad, taps * cin_pad, &kmap);
+    L.dil = c.dil;
+    if (prec == kSplit && nm == "upconv1.0") load_fc7_fold(wf);
     if (prec == kSplit && nm == "conv_cls.8") load_head_tail(wf);
     if (prec == kSplit && (nm == "upconv2.0" || nm == "upconv3.0" || nm == "upconv4.0")) {
       // the layer's two column blocks as linears of their own (tn.up_commute): [0, C0) multiplies the upsampled tensor, [C0, cin) the skip tensor (+ the bias)
@@ -256,6 +258,55 @@ void Engine::load_craft(const std::string& dir) {
       TTR_HIP_CHECK(hipMemcpy(L.wsp.p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
     }
   }
+}
+
+// slice5.1 (3x3, dilation 6, 512 -> 1024), slice5.2 (1x1, 1024 -> 1024) and the fc7 columns of upconv1.0 (1x1, 1536 -> 512) have no activation between them
+// (oracle/models.py: 72-76, 124-127) and fc7 has no other reader: three linear maps are one.  With Wu = upconv1.0's weight,
+//   A = Wu[:, :1024] . W52 (512 x 1024),   Wf = A . W51 (a 3x3 of 512 -> 512, rows [tap][Cin] like W51's),   bf = A . b51 + Wu[:, :1024] . b52 + bu,
+//   upconv1.0 = ReLU(conv3x3_dil6(mp; Wf) + Wu[:, 1024:] . relu5_3 + bf)
+// - also at the borders: the zero padding touches the taps of mp only and the biases are constants.  Formed in float64 from the BN-folded fp32 weights, rounded
+// once to fp32, then through upload_linear like every layer (their own scale S and planes): "upconv1.0.fold" and "upconv1.0.skip" beside the three originals,
+// which stay (tn.fc7_fold = 0, the tap).  2.9 G float64 multiply-adds, on the host pool in blocks of eight output rows; a row's sums run in one fixed order
+// whatever the thread count, so the planes are the same bits on every box.
+void Engine::load_fc7_fold(WeightFile& wf) {
+  constexpr int C5 = 512, C6 = 1024, C7 = 1024, CU = 512, CS = 512, K5 = 9 * C5, KU = C7 + CS, RB = 8;
+  const auto& w51 = wf.get("slice5.1.w", (size_t)C6 * K5).data; const auto& b51 = wf.get("slice5.1.b", C6).data;
+  const auto& w52 = wf.get("slice5.2.w", (size_t)C7 * C6).data; const auto& b52 = wf.get("slice5.2.b", C7).data;
+  const auto& wu = wf.get("upconv1.0.w", (size_t)CU * KU).data; const auto& bu = wf.get("upconv1.0.b", CU).data;
+  std::vector<float> wfold((size_t)CU * K5), bfold(CU);
+  host_pool->run(CU / RB, [&](int blk) {
+    std::vector<double> A((size_t)RB * C6, 0.0), F((size_t)RB * K5, 0.0);
+    for (int i = 0; i < C7; ++i) {
+      const float* w52r = &w52[(size_t)i * C6];
+      for (int r = 0; r < RB; ++r) {
+        const double a = wu[(size_t)(blk * RB + r) * KU + i];
+        double* Ar = &A[(size_t)r * C6];
+        for (int j = 0; j < C6; ++j) Ar[j] += a * (double)w52r[j];
+      }
+    }
+    for (int j = 0; j < C6; ++j) {
+      const float* w51r = &w51[(size_t)j * K5];
+      for (int r = 0; r < RB; ++r) {
+        const double a = A[(size_t)r * C6 + j];
+        double* Fr = &F[(size_t)r * K5];
+        for (int k = 0; k < K5; ++k) Fr[k] += a * (double)w51r[k];
+      }
+    }
+    for (int r = 0; r < RB; ++r) {
+      const int o = blk * RB + r;
+      double s = bu[o];
+      for (int j = 0; j < C6; ++j) s += A[(size_t)r * C6 + j] * (double)b51[j];
+      for (int i = 0; i < C7; ++i) s += (double)wu[(size_t)o * KU + i] * (double)b52[i];
+      bfold[o] = (float)s;
+      for (int k = 0; k < K5; ++k) wfold[(size_t)o * K5 + k] = (float)F[(size_t)r * K5 + k];
+    }
+  });
+  Linear& Lf = craft["upconv1.0.fold"];
+  upload_linear(Lf, wfold.data(), CU, K5, bfold.data(), CU, K5);
+  Lf.dil = craft.at("slice5.1").dil;
+  std::vector<int> ks(CS);
+  for (int i = 0; i < CS; ++i) ks[i] = C7 + i;
+  upload_linear(craft["upconv1.0.skip"], wu.data(), CU, KU, nullptr, CU, CS, &ks);
 }
 
 // conv_cls.6 (16 -> 16) and conv_cls.8 (16 -> 2) as weight pairs in the fragment rows conv3p.hip's fused head tail multiplies from

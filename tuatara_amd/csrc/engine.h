@@ -94,6 +94,9 @@ struct Tuning {
                               // the host then reads 24 bytes per candidate instead of its row extremes and runs no calipers; 0 = geometry.cpp on the host
   int up_commute = 1;         // split engines, CRAFT's upconv2.0 / 3.0 / 4.0 (1x1 over cat(upsample(y), skip)): W_up . y at the low resolution, its bilinear upsample added in the
                               // epilogue of the skip half's 1x1 (gemm2.hip, ConvParams::up_z) - the upsampled tensors are never written; 0 = upsample kernel + two-source 1x1
+  int fc7_fold = 1;           // split engines, CRAFT: slice5.1 (3x3, dilation 6) -> slice5.2 (1x1) -> upconv1.0's fc7 half (1x1), three linear maps with no activation between
+                              // them, as ONE 3x3 of 512 -> 512 folded at load time (Engine::load_craft), upconv1.0's skip half as a 1x1 into an fp32 addend of that launch's
+                              // epilogue (Engine::fc7_folded): the two 1024-channel tensors are neither computed nor stored; 0 = the three layers as the reference runs them
   int head_tail = 1;          // ... and the two 1x1 layers behind conv_cls.4 inside its epilogue (no 16-channel tensors, two launches less); 0 = fp32 MFMA launches
   int first_fused = 1;        // pairs, pages that tile into 8 x 32 patches: conv1_1 evaluated inside conv1_2's kernel on the halo patch (conv3p.hip, FIRST on pairs) - the
                               // 64-channel full-resolution tensor is neither written nor read; bit-identical to the two launches (0: conv1_split_kernel + the plain tile)
@@ -130,6 +133,7 @@ struct Tuning {
     else if (k == "sp_hidden16") sp_hidden16 = value;
     else if (k == "images_batch") images_batch = value < 1 ? 1 : (value > 256 ? 256 : value);
     else if (k == "up_commute") up_commute = value;
+    else if (k == "fc7_fold") fc7_fold = value;
     else if (k == "gpu_calipers") gpu_calipers = value;
     else if (k == "skinny_split") skinny_split = value;
     else if (k == "skinny_max_rows") skinny_max_rows = value;
@@ -183,7 +187,8 @@ constexpr size_t kOffsetWindow = ((size_t)1 << 31) - 1;   // most bytes a tensor
 struct Widest { size_t bytes; const char* layer; };       // bytes per page / per crop of the widest tensor, and the layer that writes it
 // CRAFT on a canvas of H x W (a multiple of 32 each), f16x4: every tensor craft_forward_split hands a kernel.  first_fused is the EFFECTIVE switch (the tuning key,
 // pairs and the split 3x3 tiles on); craft_products 3 = pairs (4 bytes per value), 4 = triples (6)
-struct CraftGroupCfg { int first_fused = 1, craft_products = 3, up_commute = 1; };
+// fc7_fold = 1: the pass allocates no slice5.1 / slice5.2 tensors (tn.fc7_fold outside a tapped pass) and upconv1.0 has an fp32 addend of 512 channels
+struct CraftGroupCfg { int first_fused = 1, craft_products = 3, up_commute = 1, fc7_fold = 0; };
 Widest craft_widest_per_page(int H, int W, const CraftGroupCfg& c);
 // pages per CRAFT launch group for a batch of n: min(craft_group, window / per page), then evened - 16 when n % 16 == 0, else 8 when n % 8 == 0 (64 pages = 4 x 16
 // rather than 21 + 21 + 21 + 1)
@@ -286,6 +291,7 @@ struct Linear {
   DevBuf wsp;           // ... CRAFT's 3x3 layers of 32 input channels, PACKED pairs form (conv3p.hip, NP = 2): f16 [cout][3][taps * 64], per tap
                         // plane 0 = [w0 (32) | w0 / 2^11 (32)], plane 1 unused, plane 2 = [w1 (32) | 0]; multiplies pixel rows [x0 (32) | x1 (32)]
   float inv_scale = 0;  // 1 / S
+  int dil = 1;          // CRAFT's 3x3 layers: the dilation (CraftConv::dil; 6 for slice5.1 and the layer folded from it)
 };
 
 // ------------------------------------------------------------------ the engine
@@ -662,7 +668,7 @@ struct Engine {
   bool lane_go_pending = false;                   // craft_forward_split records lane_go behind slice3.20 when set
   int craft_ws_npl = 0;                           // planes per value the split CRAFT workspaces were laid out for
   // launch groups (above): the configuration in force, and what the last batch / recogniser pass ran with (ttr_dbg_last_groups)
-  CraftGroupCfg craft_group_cfg() const { return CraftGroupCfg{tn.first_fused && tn.craft_products != 4 && tn.split_conv3p ? 1 : 0, tn.craft_products, tn.up_commute}; }
+  CraftGroupCfg craft_group_cfg() const { return CraftGroupCfg{tn.first_fused && tn.craft_products != 4 && tn.split_conv3p ? 1 : 0, tn.craft_products, tn.up_commute, tn.fc7_fold && !craft_tap_on ? 1 : 0}; }
   EncGroupCfg enc_group_cfg() const { return EncGroupCfg{tn.enc_fc2_pairs, tn.qkv_attn_split, tn.enc_ln_pairs, tn.sp_hidden16}; }
   int last_craft_group = 0, last_enc_group = 0;
   // the recogniser's workspaces, by what they hold (a group's pointers into them: PqWork, engine_parseq.cpp)
@@ -804,6 +810,7 @@ struct Engine {
   }
 
   void load_head_tail(WeightFile& wf);
+  void load_fc7_fold(WeightFile& wf);   // the derived layers "upconv1.0.fold" / "upconv1.0.skip" (tn.fc7_fold)
   void load_parseq(const std::string& dir);
 
   bool verbose = false;
@@ -847,6 +854,8 @@ struct Engine {
   // value); the convolutions' epilogues write them (bias, ReLU, ReLU copy, 2x2 max-pool fused), so no fp32 tensor and no separate
   // split pass exists up to the 32-channel head, which stays on the fp32 MFMA kernel (thin layers: 3 % of the FLOPs).
   void upconv_commuted(const char* name, const void* y_lo, int C0, const void* skip, int C1, int B, int H, int W, float* z, void* out);
+  // upconv1.0 with slice5.1 and slice5.2 folded into it (tn.fc7_fold): z = W_skip . relu5_3 (fp32, no bias), out = ReLU(conv3x3_dil6(mp; Wf) + bf + z)
+  void fc7_folded(const void* mp, const void* skip, int B, int H, int W, float* z, void* out);
   const uint8_t* sconv_canvas = nullptr;   // set around the sconv of slice1.3: its input tensor does not exist, conv1_1 is evaluated from this canvas inside the kernel (tn.first_fused)
   void sconv(const char* name, const void* in0, int C0, const void* in1, int C1, int B, int H, int W, void* out, int act,
              void* out_relu = nullptr, void* out_pool = nullptr, int pool_relu = 0, int out_planes = -1, int out_ld = 0, bool packed = false, float* tail_heat = nullptr);
@@ -861,6 +870,7 @@ struct Engine {
   };
   bool craft_tap_on = false;
   std::vector<CraftTap> craft_taps;
+  std::vector<CraftTap> craft_fold_taps;   // the folded upconv1.0 launches of a tapped pass (roles in0 = mp, in1 = relu5_3, z, out): a list of their own, craft_taps keeps the three original layers' records
   void tap(const char* layer, const char* role, const void* p, int B, int H, int W, int C, int ld, int form, const char* kind = "") {
     if (craft_tap_on && p) craft_taps.push_back(CraftTap{layer, role, kind, p, B, H, W, C, ld, form});
   }

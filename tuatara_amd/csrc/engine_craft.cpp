@@ -12,7 +12,7 @@ void Engine::conv(const char* name, const void* in0, int C0, const void* in1, in
   const int Ct = C0 + C1;
   p.ks = (L.k == Ct) ? 1 : 3;
   if (L.k != p.ks * p.ks * Ct) throw std::runtime_error(std::string("conv shape mismatch at ") + name);
-  p.dil = std::string(name) == "slice5.1" ? 6 : 1;
+  p.dil = L.dil;
   p.wgt = L.w.p; p.bias = L.b.as<float>();
   p.out = out; p.out_ld = L.cout; p.out_f32 = out_f32; p.out_f32_ld = L.cout; p.out_relu = out_relu; p.out_pool = out_pool; p.pool_relu = pool_relu;
   p.Cout = L.cout; p.M = B * H * W; p.act = act;
@@ -153,7 +153,7 @@ void Engine::sconv(const char* name, const void* in0, int C0, const void* in1, i
   const int Ct = C0 + C1;
   p.ks = (L.k == Ct) ? 1 : 3;
   if (L.k != p.ks * p.ks * Ct || !L.ws.p) throw std::runtime_error(std::string("split conv shape mismatch at ") + name);
-  p.dil = std::string(name) == "slice5.1" ? 6 : 1;
+  p.dil = L.dil;
   p.wgt = L.ws.p; p.bias = L.b.as<float>(); p.split = np; p.out_scale = L.inv_scale; p.out_planes = out_planes;
   p.out = out; p.out_ld = out_ld ? out_ld : L.cout; p.out_relu = out_relu; p.out_pool = out_pool; p.pool_relu = pool_relu;
   p.Cout = L.cout; p.M = B * H * W; p.act = act;
@@ -235,6 +235,41 @@ void Engine::upconv_commuted(const char* name, const void* y_lo, int C0, const v
         (double)Mhi * C1 * 2.0 * (np - 1) + (double)Mlo * Cout * 4.0 + (double)Mhi * Cout * 2.0 * (np - 1) + (double)Cout * C1 * 6.0);
 }
 
+// upconv1.0 with slice5.1 and slice5.2 folded into it (Engine::load_fc7_fold has the identity): z = W_skip . relu5_3 as a 1x1 with fp32 rows out, then the folded
+// 3x3 at slice5.1's dilation over mp with z as its epilogue's fp32 addend: out = ReLU(acc / S + bf + z).  The 3x3 runs where slice5.1 runs - gemm_sp.hip's
+// per-tap loop (tuning key gsp_ks3), gemm2.hip's for triples - and the sums differ from the three layers' at fp32 rounding level only.
+void Engine::fc7_folded(const void* mp, const void* skip, int B, int H, int W, float* z, void* out) {
+  range_tag("craft.upconv1.0");
+  const Linear& Lf = craft.at("upconv1.0.fold");
+  const Linear& Ls = craft.at("upconv1.0.skip");
+  const int np = tn.craft_products == 4 ? 4 : 3, C = 512, Cout = Lf.cout;
+  if (Lf.k != 9 * C || Ls.k != C || Ls.cout != Cout || !Lf.ws.p || !Ls.ws.p) throw std::runtime_error("folded upconv1.0: shape mismatch");
+  const int64_t M = (int64_t)B * H * W;
+  ConvParams a{};
+  a.in0 = skip; a.C0 = C; a.B = B; a.H = H; a.W = W; a.ks = 1; a.dil = 1;
+  a.wgt = Ls.ws.p; a.bias = Ls.b.as<float>(); a.split = np; a.out_scale = Ls.inv_scale; a.out_planes = 0;
+  a.out = z; a.out_ld = Cout; a.Cout = Cout; a.M = (int)M; a.act = kActNone;
+  if (const char* e = gemm2_check(a)) throw std::runtime_error(std::string("upconv1.0 (skip half): ") + e);
+  ConvParams b{};
+  b.in0 = mp; b.C0 = C; b.B = B; b.H = H; b.W = W; b.ks = 3; b.dil = Lf.dil;
+  b.wgt = Lf.ws.p; b.bias = Lf.b.as<float>(); b.split = np; b.out_scale = Lf.inv_scale; b.out_planes = np - 1;
+  b.out = out; b.out_ld = Cout; b.Cout = Cout; b.M = (int)M; b.act = kActRelu;
+  b.resid = z; b.resid_ld = Cout;
+  if (const char* e = gemm2_check(b)) throw std::runtime_error(std::string("upconv1.0 (folded 3x3): ") + e);
+  const char* kind = np == 3 ? "gemm2_kernel<SP,NP=3> (CRAFT 1x1 / dilated)" : "gemm2_kernel<SP,NP=4> (CRAFT 1x1 / dilated)";
+  if (craft_tap_on) {
+    auto rec = [&](const char* role, const void* p, int form, const char* k) { craft_fold_taps.push_back(CraftTap{"upconv1.0", role, k, p, B, H, W, C, C, form}); };
+    rec("in0", mp, np - 1, ""); rec("in1", skip, np - 1, ""); rec("z", z, kTapF32, kind); rec("out", out, np - 1, kind);
+  }
+  // algorithmic flops: those of the layers the reference runs - slice5.1 + slice5.2 + upconv1.0's fc7 half on the folded launch, the skip
+  // half on its own; executed flops and bytes: what the two launches multiply and move
+  const std::string la = std::string("upconv1.0 (skip half -> z) | ") + kind, lb = std::string("slice5.1 + slice5.2 + upconv1.0 (folded 3x3) | ") + kind;
+  timed(profiling == 2 ? la.c_str() : kind, 2.0 * M * Cout * C, 2.0 * M * Cout * C * np, [&] { launch_gemm2(a, 0, stream); },
+        (double)M * C * 2.0 * (np - 1) + (double)M * Cout * 4.0 + (double)Cout * C * 6.0);
+  timed(profiling == 2 ? lb.c_str() : kind, 2.0 * M * (1024.0 * 9 * C + 1024.0 * 1024 + (double)Cout * 1024), 2.0 * M * Cout * 9 * C * np, [&] { launch_gemm2(b, 0, stream); },
+        (double)M * C * 2.0 * (np - 1) + (double)M * Cout * 4.0 + (double)M * Cout * 2.0 * (np - 1) + (double)Cout * 9 * C * 6.0);
+}
+
 // The tensors craft_forward_split below hands its kernels, per page of an H x W canvas (engine.h: launch groups): level = log4 of the rows' divisor (0: full
 // resolution), channels, bytes per value.  Without first_fused the widest is conv1_1's output (64 channels at full resolution: 201 MB per 1024 x 768 page as
 // pairs); with it that tensor is never written and slice1.7 / slice1.10's 128 channels at half resolution lead (100.7 MB).  The upsampled tensors of the
@@ -247,7 +282,9 @@ Widest craft_widest_per_page(int H, int W, const CraftGroupCfg& c) {
   t("slice1.3", 1, 64, bpv); t("slice1.7", 1, 128, bpv); t("slice1.10", 1, 128, bpv);
   t("slice2.14", 2, 256, bpv); t("slice2.17", 2, 256, bpv); t("slice3.20", 3, 256, bpv);
   t("slice3.24", 3, 512, bpv); t("slice3.27", 3, 512, bpv); t("slice4.30", 4, 512, bpv);
-  t("slice4.34", 4, 512, bpv); t("slice4.37", 4, 512, bpv); t("slice5.1", 4, 1024, bpv); t("slice5.2", 4, 1024, bpv);
+  t("slice4.34", 4, 512, bpv); t("slice4.37", 4, 512, bpv);
+  if (c.fc7_fold) t("upconv1.0", 4, 512, 4);                                                                      // z: fp32 (the 1024-channel tensors do not exist)
+  else { t("slice5.1", 4, 1024, bpv); t("slice5.2", 4, 1024, bpv); }
   t("upconv1.0", 4, 512, bpv); t("upconv1.3", 4, 256, bpv);
   if (c.up_commute) { t("upconv2.0", 4, 256, 4); t("upconv3.0", 3, 128, 4); t("upconv4.0", 2, 64, 4); }         // z: fp32 at the low resolution
   else { t("upconv2.0.upsample", 3, 256, bpv); t("upconv3.0.upsample", 2, 128, bpv); t("upconv4.0.upsample", 1, 64, bpv); }
@@ -325,9 +362,23 @@ void Engine::craft_forward_split(const uint8_t* d_canvas, int B, int H, int W, f
   void* mp = pbuf(M4, 512);  prof_break(), launch_maxpool3x3s1_planes(c52, mp, B, H4, W4, 512, stream, npl);
   tap("maxpool3x3", "in0", c52, B, H4, W4, 512, 512, npl);
   tap("maxpool3x3", "out", mp, B, H4, W4, 512, 512, npl, "maxpool3x3s1_planes");
-  void* c6 = pbuf(M4, 1024); sconv("slice5.1", mp, 512, nullptr, 0, B, H4, W4, c6, kActNone);
-  void* fc7 = pbuf(M4, 1024); sconv("slice5.2", c6, 1024, nullptr, 0, B, H4, W4, fc7, kActNone);
-  void* u1a = pbuf(M4, 512); sconv("upconv1.0", fc7, 1024, c52, 512, B, H4, W4, u1a, kActRelu);
+  // slice5.1 -> slice5.2 -> upconv1.0: the three layers, or (tn.fc7_fold) the 3x3 folded from them + the skip half's 1x1, which never write the 1024-channel
+  // tensors.  A tapped pass with the fold on runs BOTH: the folded launches feed the pass (same heat map as untapped, their records in craft_fold_taps), the three
+  // layers run into side workspaces nothing reads, with their usual records.  Each tensor keeps its workspace slot whichever way the pass goes.
+  const bool fold = tn.fc7_fold && craft.count("upconv1.0.fold") != 0;
+  const bool chain = !fold || craft_tap_on;
+  craft_fold_taps.clear();
+  void *c6 = nullptr, *fc7 = nullptr, *u1a = nullptr, *u1s = nullptr; float* z = nullptr;
+  if (chain) { c6 = pbuf(M4, 1024); fc7 = pbuf(M4, 1024); } else k += 2;
+  if (fold) z = (float*)fbuf(M4, 512); else k++;
+  u1a = pbuf(M4, 512);
+  if (fold && chain) u1s = pbuf(M4, 512); else k++;
+  if (fold) fc7_folded(mp, c52, B, H4, W4, z, u1a);
+  if (chain) {
+    sconv("slice5.1", mp, 512, nullptr, 0, B, H4, W4, c6, kActNone);
+    sconv("slice5.2", c6, 1024, nullptr, 0, B, H4, W4, fc7, kActNone);
+    sconv("upconv1.0", fc7, 1024, c52, 512, B, H4, W4, fold ? u1s : u1a, kActRelu);
+  }
   void* u1b = pbuf(M4, 256); sconv("upconv1.3", u1a, 512, nullptr, 0, B, H4, W4, u1b, kActRelu);
   // upconvN.0 over cat(upsample(y), skip): the upsample kernel + a two-source 1x1, or (tn.up_commute) the commuted form that never writes the upsampled tensor
   auto upconv = [&](const char* name, const void* y_lo, int C0, const void* skip, int C1, int Cout, size_t Mhi, int Hh, int Wh) -> void* {

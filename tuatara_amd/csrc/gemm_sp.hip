@@ -969,7 +969,9 @@ static int g_sp_ks3 = 1;   // 0: gemm2.hip's loop; 1: this file's (tile by launc
 void set_gemm_sp_ks3(int v) { g_sp_ks3 = v; }
 bool gemm_sp_ks3_eligible(const ConvParams& p) {
   if (!g_sp_ks3 || p.split != 3 || p.ks != 3 || p.dil < 1 || p.C1 != 0 || p.out_pool || p.out_relu || p.C0 % 64 != 0 || p.Cout % 8 != 0) return false;
-  if (p.x_tiled || p.out_tiled || p.wgt_tiled || p.up_z || p.resid || p.out_full_cols || p.skip) return false;
+  if (p.x_tiled || p.out_tiled || p.wgt_tiled || p.up_z || p.out_full_cols || p.skip) return false;
+  // an fp32 addend of one row per pixel (CRAFT's folded upconv1.0: the skip half's 1x1) goes through the general epilogue's residual pass, which reads it by buffer descriptor
+  if (p.resid && (p.resid_mod || p.resid_ld < p.Cout || p.resid_ld % 4 != 0 || (size_t)p.M * p.resid_ld * 4 >= ((size_t)1 << 31))) return false;
   if (p.M != p.B * p.H * p.W || p.H >= 32768 || p.W >= 65536) return false;
   return (size_t)p.M * p.C0 * 4 < ((size_t)1 << 31) && (size_t)((p.Cout + 31) / 32 * 32) * 9 * p.C0 * 6 < ((size_t)1 << 31);
 }

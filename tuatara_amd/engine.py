@@ -220,6 +220,9 @@ SYMBOLS = [
     ("ttr_dbg_craft_tap_count", _I, [_VP]),
     ("ttr_dbg_craft_tap_info", _I, [_VP, _I, C.c_char_p, C.c_size_t, _PI]),
     ("ttr_dbg_craft_tap_read", _I, [_VP, _I, _PF]),
+    ("ttr_dbg_craft_fold_tap_count", _I, [_VP]),
+    ("ttr_dbg_craft_fold_tap_info", _I, [_VP, _I, C.c_char_p, C.c_size_t, _PI]),
+    ("ttr_dbg_craft_fold_tap_read", _I, [_VP, _I, _PF]),
     ("ttr_set_gemm_config", None, [_I]),
     ("ttr_set_decoder_mode", None, [_I]),
     ("ttr_set_tuning", _I, [C.c_char_p, _I]),
@@ -2475,10 +2478,24 @@ class Engine:
                              form=int(dims[5])))
         return heat, recs
 
+    def craft_fold_taps(self):
+        """The records of the folded upconv1.0 launches of the last craft_taps pass (tuning key fc7_fold on; empty with it off): layer "upconv1.0", roles in0
+        (the 3x3 max-pool's output), in1 (relu5_3), z (the skip half's 1x1, fp32) and out.  craft_taps' own records are those of the three original layers,
+        which a tapped pass runs beside the folded launches into workspaces nothing reads.  Read with craft_tap_read."""
+        recs = []
+        text, dims = C.create_string_buffer(512), np.zeros(7, np.int32)
+        for i in range(max(0, self.lib.ttr_dbg_craft_fold_tap_count(self.h))):
+            self._check(self.lib.ttr_dbg_craft_fold_tap_info(self.h, i, text, 512, _i(dims)))
+            layer, role, kind = text.value.decode().split("\n")
+            recs.append(dict(index=i, layer=layer, role=role, kind=kind, B=int(dims[0]), H=int(dims[1]), W=int(dims[2]), C=int(dims[3]), ld=int(dims[4]),
+                             form=int(dims[5]), fold=True))
+        return recs
+
     def craft_tap_read(self, rec) -> np.ndarray:
-        """Tensor of a craft_taps record joined to fp32 on the host, every step exact: f32 [B, H, W, ld], padding channels included."""
+        """Tensor of a craft_taps (or craft_fold_taps) record joined to fp32 on the host, every step exact: f32 [B, H, W, ld], padding channels included."""
         out = np.zeros((rec["B"], rec["H"], rec["W"], rec["ld"]), np.float32)
-        self._check(self.lib.ttr_dbg_craft_tap_read(self.h, rec["index"], _f(out)))
+        read = self.lib.ttr_dbg_craft_fold_tap_read if rec.get("fold") else self.lib.ttr_dbg_craft_tap_read
+        self._check(read(self.h, rec["index"], _f(out)))
         return out
 
     def ccl_boxes(self, heat: np.ndarray, max_rects: int = 8192) -> np.ndarray:
