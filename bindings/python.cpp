@@ -51,6 +51,9 @@
 // And a keyword-only local_ink=False on image_to_data: local_ink=True (radius 16, drop 38, polarity 2 = auto) or local_ink=(radius, drop, polarity) makes tables and
 // deskew take their ink bitmap from the adaptive threshold (DESIGN.md "Local ink"), so shaded, grey or inverted pages keep their rulings and their skew; with
 // neither of the two on nothing runs.  A value out of range raises RuntimeError with the engine's message.
+// And a keyword-only marks=False on image_to_data: marks=True (min_side 10, max_side 64, fill 24, ink 128) or marks=(min_side, max_side, fill, ink) finds the page's
+// checkboxes and their state (DESIGN.md "Selection marks"); every dict gains "mark" (-1 for an item in no mark), and last_call_marks() returns the marks of the
+// latest call as dicts {"box", "interior", "selected", "fill", "label", "text"}.  It does not combine with regions.
 // And a keyword-only tables=False on image_to_data: tables=True (min_len 48, ink 128) or tables=(min_len, ink) finds ruling lines, tables, grids and merged
 // cells in the page's pixels (DESIGN.md "Tables"); every dict gains "table" and "cell" (-1 / -1 for an item in no cell).  It combines with every keyword but
 // regions (ValueError); a value out of range raises RuntimeError before anything runs.
@@ -75,7 +78,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false, curved = false, lex_edits = false, tables = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false, curved = false, lex_edits = false, tables = false, marks = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
@@ -93,6 +96,7 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
   }
   if (k.blocks) d["block"] = item.block;
   if (k.tables) { d["table"] = item.table; d["cell"] = item.cell; }
+  if (k.marks) d["mark"] = item.mark;
   if (k.curved) {
     d["curved"] = item.curved;
     py::list pts;
@@ -272,7 +276,22 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
                                       py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved, py::object lexicon_fuzzy, double lexicon_gap,
-                                      py::object tiled_kw, py::object tables_kw, py::object deskew_kw, py::object local_ink_kw) {
+                                      py::object tiled_kw, py::object tables_kw, py::object deskew_kw, py::object local_ink_kw, py::object marks_kw) {
+  // marks=False | True (10, 64, 24, 128) | (min_side, max_side, fill, ink): selection marks for this call (DESIGN.md "Selection marks")
+  struct MarksScope {
+    MarksScope(int a, int b, int f, int i) { set_marks(a, b, f, i); }
+    ~MarksScope() { set_marks(0); }
+  };
+  int mk_min = 0, mk_max = 64, mk_fill = 24, mk_ink = 128;
+  if (py::isinstance<py::bool_>(marks_kw)) mk_min = marks_kw.cast<bool>() ? 10 : 0;
+  else if (py::isinstance<py::tuple>(marks_kw) && py::len(marks_kw) == 4) {
+    const py::tuple t = marks_kw.cast<py::tuple>();
+    mk_min = t[0].cast<int>(); mk_max = t[1].cast<int>(); mk_fill = t[2].cast<int>(); mk_ink = t[3].cast<int>();
+  } else if (!marks_kw.is_none()) throw py::type_error("marks must be False, True or (min_side, max_side, fill, ink)");
+  if (mk_min != 0 && !regions_kw.is_none()) throw std::invalid_argument("marks does not combine with regions (the views stay empty)");
+  if (mk_min != 0 && (mk_min < 8 || mk_min > 64 || mk_max < mk_min || mk_max > 128 || mk_fill < 1 || mk_fill > 255 || mk_ink < 1 || mk_ink > 255))
+    throw std::runtime_error("marks must be False, True or (min_side, max_side, fill, ink) with min_side in 8..64, max_side in min_side..128, fill and ink in 1..255");
+  MarksScope marks_scope(mk_min, mk_max, mk_fill, mk_ink);
   // local_ink=False | True (16, 38, 2) | (radius, drop, polarity): the ink rule of tables and deskew for this call (DESIGN.md "Local ink")
   struct InkScope {
     InkScope(int r, int d, int p) { set_local_ink(r, d, p); }
@@ -358,6 +377,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     Keys keys{true, conf, false, lines, false, blocks};
     keys.curved = true;
     keys.tables = tab_min_len != 0;
+    keys.marks = mk_min != 0;
     for (const auto& item : got) res.append(item_dict(item, keys));
     return res;
   }
@@ -375,6 +395,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     py::list res;
     Keys wkeys{true, conf, false, lines, false, blocks, false, false, true};
     wkeys.tables = tab_min_len != 0;
+    wkeys.marks = mk_min != 0;
     for (const auto& item : got) res.append(item_dict(item, wkeys));
     return res;
   }
@@ -435,6 +456,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   Keys keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best};
   keys.lex_edits = band >= 0;
   keys.tables = tab_min_len != 0;
+  keys.marks = mk_min != 0;
   for (const auto& item : items) result.append(item_dict(item, keys));
   return result;
 }
@@ -502,7 +524,18 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, py::arg("tables") = false, py::arg("deskew") = false, py::arg("local_ink") = false, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, py::arg("tables") = false, py::arg("deskew") = false, py::arg("local_ink") = false, py::arg("marks") = false, "Extract text and bounding boxes from an image");
+  m.def("last_call_marks", []() {
+    py::list out;
+    for (const SelectionMark& s : last_call_marks()) {
+      py::dict d;
+      d["box"] = py::make_tuple(s.box[0], s.box[1], s.box[2], s.box[3]);
+      d["interior"] = py::make_tuple(s.interior[0], s.interior[1], s.interior[2], s.interior[3]);
+      d["selected"] = s.selected; d["fill"] = s.area ? (double)s.inked / (double)s.area : 0.0; d["label"] = s.label; d["text"] = s.text;
+      out.append(d);
+    }
+    return out;
+  }, "The selection marks of this thread's latest image_to_data call (DESIGN.md \"Selection marks\"), [] when marks were off");
   m.def("last_call_skew", []() -> py::object {
     const PageSkew s = last_call_skew();
     if (!s.on) return py::none();

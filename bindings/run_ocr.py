@@ -74,8 +74,8 @@ def annotate(image: np.ndarray, result, by_lines: bool = False, by_blocks: bool 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     rectify, lines, chars, blocks, curved = "--rectify" in argv, "--lines" in argv, "--chars" in argv, "--blocks" in argv, "--curved" in argv
-    tables, deskew = "--tables" in argv, "--deskew" in argv
-    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks", "--curved", "--tables", "--deskew")]
+    tables, deskew, marks = "--tables" in argv, "--deskew" in argv, "--marks" in argv
+    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks", "--curved", "--tables", "--deskew", "--marks")]
     image_path = argv[0] if len(argv) > 0 else os.path.join(HERE, "..", "tests", "data", "funsd_0001129658.png")
     weights_dir = argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "weights")
     outputs_dir = argv[2] if len(argv) > 2 else os.path.join(HERE, "..", "outputs")
@@ -93,6 +93,8 @@ def main(argv=None):
         kw["curved"] = True
     if tables:                      # (DESIGN.md "Tables": min_len 48, ink 128)
         kw["tables"] = True
+    if marks:                       # (DESIGN.md "Selection marks": sides 10..64, fill 24, ink 128)
+        kw["marks"] = True
     if deskew:                      # (DESIGN.md "Deskew": max_slope 64, gain 288, ink 128; the result is in the upright page's frame)
         kw["deskew"] = True
     result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir, **kw)
@@ -109,6 +111,11 @@ def main(argv=None):
             d.rectangle([int(c[5]), int(c[6]), int(c[7]), int(c[8])], outline=(0, 160, 255), width=2)
         for r in t["rulings"]:
             d.rectangle([int(r[1]), int(r[2]), int(r[3]), int(r[4])], outline=(255, 0, 255) if r[5] >= 0 else (255, 160, 0))
+    if marks:                       # every mark's frame over the first panel: green when selected, red when not, and its label's text beside it
+        d = ImageDraw.Draw(out)
+        for m in pytuatara.last_call_marks():
+            print(("[x] " if m["selected"] else "[ ] ") + " ".join(str(v) for v in m["box"]) + "\t" + m["text"])
+            d.rectangle([int(v) for v in m["box"]], outline=(0, 170, 0) if m["selected"] else (220, 0, 0), width=2)
     if deskew:                      # every item's box mapped back to the caller's image through the call's own record and drawn there, over the first panel
         skew = pytuatara.last_call_skew()
         print(f"# page 0 slope {skew['slope']} degrees {skew['degrees']:.4f}")

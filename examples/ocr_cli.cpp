@@ -49,6 +49,9 @@
 //   ocr_cli --deskew [MAX_SLOPE] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: the page's skew is estimated on the GPU and the page read
 // upright (DESIGN.md "Deskew"; MAX_SLOPE = the largest slope tried, px per 512 px, 1..128, default 64, not tuned on documents); prints "# page 0 slope S degrees D
 // found F" and then the plain form's lines, the boxes in the upright page's frame, each followed by a tab and the box's first corner on the caller's image.
+//   ocr_cli --marks [MIN_SIDE] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: finds the page's checkboxes (DESIGN.md "Selection marks";
+//                                 sides MIN_SIDE..64 px, default 10) and prints one line per mark - "[x]" or "[ ]", the frame x0 y0 x1 y1, a tab, the text of
+//                                 the word it stands in front of - in (y, x) order
 //   ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: finds ruling lines, tables, grids and merged cells in the
 // page's pixels (DESIGN.md "Tables"; MIN_LEN = the shortest ruling in px, 16..4096, default 48, not tuned on documents) and prints each table as "# table T x0 y0
 // x1 y1 rows cols" followed by its rows, the cells' texts separated by tabs (a merged cell's text at its first base cell; a line break inside a cell as " / ").
@@ -185,6 +188,24 @@ int main(int argc, const char** argv) {
         sk.to_page(it.bbox[0], it.bbox[1], &px, &py);
         printf("%g %g %g %g\t%s\t%.9g %.9g\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.text.c_str(), px, py);
       }
+      return 0;
+    }
+    if (argc >= 2 && std::string(argv[1]) == "--marks") {
+      int min_side = 10, used = 1;
+      if (argc == 6) {
+        char* end = nullptr;
+        const long v = std::strtol(argv[2], &end, 10);
+        if (!end || *end || v < 8 || v > 64) throw std::runtime_error("--marks takes a smallest side in 8..64 px (default 10)");
+        min_side = (int)v; used = 2;
+      }
+      if (argc - used != 4) throw std::runtime_error("--marks [MIN_SIDE] goes in front of <image.png> <weights_dir> <outputs_dir>");
+      pngdec::Image img = pngdec::read(argv[used + 1]);
+      set_marks(min_side);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[used + 2], argv[used + 3], false);
+      set_marks(0);
+      if (!last_call_error().empty()) return 1;                         // (the message is on stderr)
+      for (const SelectionMark& m : last_call_marks())                  // one line per mark: its state, its frame, the word it stands in front of
+        printf("%s %d %d %d %d\t%s\n", m.selected ? "[x]" : "[ ]", m.box[0], m.box[1], m.box[2], m.box[3], m.text.c_str());
       return 0;
     }
     if (argc >= 2 && std::string(argv[1]) == "--tables") {
@@ -395,7 +416,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli --deskew [MAX_SLOPE] <image.png> <weights_dir> <outputs_dir> | ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir> | ocr_cli [--tiled [O]] [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli --marks [MIN_SIDE] <image.png> <weights_dir> <outputs_dir> | ocr_cli --deskew [MAX_SLOPE] <image.png> <weights_dir> <outputs_dir> | ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir> | ocr_cli [--tiled [O]] [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

@@ -75,6 +75,7 @@ struct OutputItemEx {
   std::vector<WordPiece> pieces;   // wide words: the item's pieces in order (one, the item itself, when it is not wide); empty when wide is off (DESIGN.md "Wide words")
   bool curved = false;             // curved words: the item's crop was straightened along a spine found in the page (DESIGN.md "Curved words")
   std::vector<float> outline;      // curved words: 36 = 18 points x, y - the top edge left to right, then the bottom edge right to left; empty when curved is off
+  int mark = -1;                   // selection marks: the mark of its page the item's centre lies in (the `x` read inside a ticked box); -1 for none and when marks are off (DESIGN.md "Selection marks")
   int table = -1, cell = -1;       // tables: the table of its page and the cell of that page's cell list the item lies in; -1 / -1 in no cell and when tables are off (DESIGN.md "Tables")
   int block = -1, block_line = -1;  // text blocks: the item's block of its page, in reading order, and its line's position inside that block (what a caller sorts by: block, block_line, word); -1 when blocks are off (DESIGN.md "Text blocks")
 };
@@ -268,6 +269,25 @@ struct TableGrid {
 void set_tables(int min_len, int ink = 128);
 int tables();
 std::vector<TableGrid> last_call_tables();
+
+// Selection marks (opt-in; DESIGN.md "Selection marks"): the page's checkboxes - small square frames - are found on the ink bitmap of the page's own pixels, each
+// one's state read from the ink inside it, every item given the mark its centre lies in (OutputItemEx::mark) and every mark the item it stands in front of.
+// Items, order, boxes and text keep their bits.  set_marks(min_side, max_side, fill, ink) turns it on for every call of THIS THREAD that follows (min_side 8..64
+// and max_side min_side..128 px, fill 1..255 in 1/256ths of the interior, ink 1..255; the other layers use 10, 64, 24 and 128, which nobody has tuned on
+// documents), set_marks(0) off again; with it off, TUATARA_MARKS=MIN_SIDE (or 1 for 10) in the environment turns it on for every call here.  It is set on the
+// cached engine for the call and reset afterwards.  A bad value: the message is printed and the result is empty (last_call_error()).  last_call_marks(): the
+// marks of this thread's latest single-image call, in (y, x) order; a page without words has marks too.
+struct SelectionMark {
+  int box[4] = {0, 0, 0, 0};        // x0, y0, x1, y1 of the frame in image pixels, inclusive (the upright page's under deskew)
+  int interior[4] = {0, 0, 0, 0};   // the pixels inside the frame that were counted
+  int inked = 0, area = 0;          // ink pixels of the interior, and its size
+  bool selected = false;            // 256 inked >= fill area
+  int label = -1;                   // the item the box stands in front of, -1 = none
+  std::string text;                 // that item's text
+};
+void set_marks(int min_side, int max_side = 64, int fill = 24, int ink = 128);
+int marks();
+std::vector<SelectionMark> last_call_marks();
 
 // Deskew (opt-in; DESIGN.md "Deskew"): the page's skew is estimated on the GPU and a page found tilted is read upright; every box and quad of the result is then
 // in the upright page's frame.  set_deskew(max_slope, gain, ink) turns it on for every call of THIS THREAD that follows (max_slope 1..128 px per 512 px, gain

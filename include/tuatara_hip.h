@@ -825,6 +825,41 @@ int ttr_tables_from_page_ink(const uint8_t* img, int h, int w, int row_stride, i
                              int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell);
 int ttr_deskew_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int radius, int drop, int polarity, uint8_t* out_img, ttr_skew* rec,
                              uint64_t* scores);
+/* ---- selection marks (opt-in; DESIGN.md "Selection marks") ----------------------------------------------
+ * With ttr_engine_set_marks(e, min_side, max_side, fill, ink) every page call also finds the page's checkboxes - small square frames - on the ink bitmap of
+ * the page's own pixels (mark_cand_kernel, marks.hip: pages x row bands), reads each one's state from the ink inside it, and says for every item which mark
+ * its centre lies in and for every mark which item stands to its right (mark_page_kernel, one workgroup per page).  Items, order, boxes, text, ids, conf and
+ * every other layer's outputs keep their bits; with marks off nothing runs.  min_side = 0 is off (the default), else min_side in 8..64 and max_side in
+ * min_side..128 (the frame's sides, px), fill in 1..255 (selected iff 256 inked >= fill area over the interior) and ink in 1..255 (as for tables); the
+ * convenience layers use 10, 64, 24 and 128, and none of these values has been tuned on documents.  With tables on under the same ink rule the bitmaps are
+ * formed once for both layers; with local ink on they are local ink's.  Unlike tables the layer runs for a page without words.  The setter refuses while
+ * streamed batches are in flight and with a communicator attached; ttr_engine_attach_comm and ttr_pages_to_data_dev_sharded refuse while marks are on;
+ * region calls leave the views empty.  Under deskew the coordinates are the upright page's.  Cap: 512 marks a page; a page beyond it reports mode -6, no
+ * marks and -1 for every item.
+ * Result views (NULL / 0 with marks off):
+ *   ttr_result_mark_mode       1, or -6; 0 when off
+ *   ttr_result_marks           [mark_count][12] int32: x0, y0, x1, y1 (the frame, inclusive px), ix0, iy0, ix1, iy1 (the interior), inked, area, state (1 =
+ *                              selected), label (the item the box stands in front of, -1 = none); in (y0, x0) order
+ *   ttr_result_item_mark       [count]: the mark an item's centre lies in (the `x` read inside a ticked box), -1 for none
+ * ttr_results_gather_marks: item_mark of n results back to back (-1 where a result has none); returns the number of items inside a mark.
+ * ttr_marks_from_page: the rule on the host, no engine.  A host image u8 [h][w][3] (row_stride bytes, 0 = 3 w) and nq quads [nq][8] -> mode, counts [3] =
+ * {marks, corners examined, candidates kept (beyond 512 on a page of mode -6)}, marks [512][12] (capacity; counts[0] says how much is valid), item_mark [nq];
+ * any output may be NULL.  Returns 0, -1 with the message in ttr_last_error (a parameter outside its range, a quad with a coordinate that is not finite or
+ * has |x| >= 32768, a page side of 32768 or more).  ttr_marks_from_page_ink: the same with local ink's (radius, drop, polarity) in the place of ink.
+ * ttr_marks_page (stage; refuses while batches stream): the same through the kernels under the fixed ink rule, whatever the engine's setting. */
+int ttr_engine_set_marks(ttr_engine* e, int min_side, int max_side, int fill, int ink);
+int ttr_engine_marks(const ttr_engine* e, int* max_side, int* fill, int* ink);
+int ttr_result_mark_mode(const ttr_result* r);
+int ttr_result_mark_count(const ttr_result* r);
+const int32_t* ttr_result_marks(const ttr_result* r);
+const int32_t* ttr_result_item_mark(const ttr_result* r);
+int ttr_results_gather_marks(ttr_result* const* rs, int n, int32_t* item_mark);
+int ttr_marks_from_page(const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int ink, const float* quads, int nq, int32_t* mode,
+                        int32_t* counts, int32_t* marks, int32_t* item_mark);
+int ttr_marks_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int radius, int drop, int polarity, const float* quads,
+                            int nq, int32_t* mode, int32_t* counts, int32_t* marks, int32_t* item_mark);
+int ttr_marks_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int ink, const float* quads, int nq, int32_t* mode,
+                   int32_t* counts, int32_t* marks, int32_t* item_mark);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

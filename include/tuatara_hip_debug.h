@@ -150,6 +150,14 @@ int ttr_dbg_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row
  * as ttr_dbg_tables takes it.  Outputs as ttr_ink_page.  Refuses while batches stream.  Returns 0, -1 on error. */
 int ttr_dbg_ink_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int radius, int drop, int polarity, uint64_t* bits,
                      uint64_t* bitsT, ttr_ink* rec);
+/* selection marks (DESIGN.md "Selection marks"): table_ink_kernel, mark_cand_kernel and mark_page_kernel on a host image placed as ttr_dbg_tables takes it.
+ * corners: the corners examined; band_counts [ceil(h / 32)][2]: per band of 32 rows the candidates kept and the corners examined, as the candidate pass wrote
+ * them; mode; marks [512][12] (zero beyond the count); any output may be NULL.  Refuses while batches stream.  Returns 0, -1 on error. */
+int ttr_dbg_marks(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_side, int max_side, int fill, int ink,
+                  int32_t* corners, int32_t* band_counts, int32_t* mode, int32_t* marks);
+/* the ink passes (table_ink_kernel, or local ink's two kernels) the engine has enqueued for its batches' page layers since it was created: tables and selection
+ * marks in one batch under one ink rule share one.  -1 for a null engine. */
+int64_t ttr_dbg_page_ink_passes(const ttr_engine* e);
 /* canvas_geometry on the host for any canvas_size / mag_ratio (what ttr_canvas_geometry answers for an engine of that config): h32 x w32, the ratio and
  * the resized page's target_h x target_w inside the canvas.  Any output may be NULL.  Returns 0, -1 for h <= 0 or w <= 0. */
 int ttr_dbg_canvas_geometry(int h, int w, int canvas_size, float mag_ratio, int* H, int* W, float* ratio, int* target_h, int* target_w);

@@ -2,6 +2,7 @@
 #include "engine.h"
 #include "page_table.h"
 #include "tables_rule.h"
+#include "marks_rule.h"
 
 namespace ttr {
 
@@ -1834,6 +1835,116 @@ int ttr_deskew_from_page_ink(const uint8_t* img, int h, int w, int row_stride, i
   DeskewRec r;
   deskew_from_page_ink(img, h, w, row_stride ? row_stride : w * 3, max_slope, gain, radius, drop, polarity, out_img, w * 3, &r, scores);
   if (rec) memcpy(rec, &r, sizeof r);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+// ---- selection marks (DESIGN.md "Selection marks")
+static std::string marks_ranges(int min_side, int max_side, int fill, int ink) {
+  return "min_side must lie in 8..64, max_side in min_side..128, fill and ink in 1..255, got " + std::to_string(min_side) + ", " + std::to_string(max_side) + ", " +
+         std::to_string(fill) + " and " + std::to_string(ink);
+}
+
+int ttr_engine_set_marks(ttr_engine* e, int min_side, int max_side, int fill, int ink) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (min_side != 0 && !marks_args_ok(min_side, max_side, fill, ink)) throw std::runtime_error("ttr_engine_set_marks: min_side must be 0 (off), or " + marks_ranges(min_side, max_side, fill, ink));
+  E.refuse_while_streaming("ttr_engine_set_marks");
+  if (min_side && E.comm) throw std::runtime_error("ttr_engine_set_marks: selection marks are found by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
+  E.marks_min = min_side;
+  if (min_side) { E.marks_max = max_side; E.marks_fill = fill; E.marks_ink = ink; }
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_marks(const ttr_engine* e, int* max_side, int* fill, int* ink) {
+  if (!e) return 0;
+  if (max_side) *max_side = e->e->marks_max;
+  if (fill) *fill = e->e->marks_fill;
+  if (ink) *ink = e->e->marks_ink;
+  return e->e->marks_min;
+}
+
+int ttr_result_mark_mode(const ttr_result* r) { return r ? r->r.mark_mode : 0; }
+int ttr_result_mark_count(const ttr_result* r) { return r ? (int)(r->r.marks.size() / kMarkRec) : 0; }
+const int32_t* ttr_result_marks(const ttr_result* r) { return r && !r->r.marks.empty() ? r->r.marks.data() : nullptr; }
+const int32_t* ttr_result_item_mark(const ttr_result* r) { return r && !r->r.item_mark.empty() ? r->r.item_mark.data() : nullptr; }
+
+int ttr_results_gather_marks(ttr_result* const* rs, int n, int32_t* item_mark) {
+  if (!rs || n < 0) return -1;
+  size_t oi = 0, inside = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!rs[i]) continue;
+    const Result& r = rs[i]->r;
+    const size_t cnt = r.text.size();
+    const bool has = cnt > 0 && r.item_mark.size() == cnt;
+    if (item_mark) { if (has) std::copy(r.item_mark.begin(), r.item_mark.end(), item_mark + oi); else std::fill(item_mark + oi, item_mark + oi + cnt, -1); }
+    if (has) for (int32_t m : r.item_mark) inside += m >= 0;
+    oi += cnt;
+  }
+  return (int)inside;
+}
+
+static void marks_out(const int32_t* side, const int32_t* items, int nq, int32_t* mode, int32_t* counts, int32_t* marks, int32_t* item_mark) {
+  if (mode) *mode = side[0];
+  if (counts) { counts[0] = side[1]; counts[1] = side[2]; counts[2] = side[3]; }
+  if (marks) std::copy(side + kMarkHdr, side + kMarkHdr + (size_t)kMarkRec * side[1], marks);
+  if (item_mark) std::copy(items, items + nq, item_mark);
+}
+
+static void marks_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int ink, const float* quads, int nq) {
+  if (!img || nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
+  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
+  if (h >= 32768 || w >= 32768) throw std::runtime_error(std::string(what) + ": a page side of 32768 px or more");
+  if (!marks_args_ok(min_side, max_side, fill, ink)) throw std::runtime_error(std::string(what) + ": " + marks_ranges(min_side, max_side, fill, ink));
+  for (int i = 0; i < nq; ++i)
+    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error(std::string(what) + ": quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+}
+
+static void marks_host_items(int32_t* side, const float* quads, int nq, int32_t* items) {
+  std::vector<int32_t> centres((size_t)nq * 2);
+  for (int i = 0; i < nq; ++i) tables_word_centre(quads + 8 * (size_t)i, &centres[2 * (size_t)i]);
+  marks_items(side, centres.data(), nq, items);
+}
+
+int ttr_marks_from_page(const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int ink, const float* quads, int nq, int32_t* mode,
+                        int32_t* counts, int32_t* marks, int32_t* item_mark) {
+  TTR_GUARD_BEGIN
+  marks_in_ok("ttr_marks_from_page", img, h, w, row_stride, min_side, max_side, fill, ink, quads, nq);
+  std::vector<int32_t> side(kMarkSideInts), items((size_t)nq);
+  marks_from_page(img, h, w, row_stride ? row_stride : w * 3, min_side, max_side, fill, ink, side.data());
+  marks_host_items(side.data(), quads, nq, items.data());
+  marks_out(side.data(), items.data(), nq, mode, counts, marks, item_mark);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_marks_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int radius, int drop, int polarity, const float* quads,
+                            int nq, int32_t* mode, int32_t* counts, int32_t* marks, int32_t* item_mark) {
+  TTR_GUARD_BEGIN
+  marks_in_ok("ttr_marks_from_page_ink", img, h, w, row_stride, min_side, max_side, fill, 128, quads, nq);
+  ink_in_ok("ttr_marks_from_page_ink", img, h, w, row_stride, radius, drop, polarity);
+  std::vector<int32_t> side(kMarkSideInts), items((size_t)nq);
+  marks_from_page_ink(img, h, w, row_stride ? row_stride : w * 3, min_side, max_side, fill, radius, drop, polarity, side.data());
+  marks_host_items(side.data(), quads, nq, items.data());
+  marks_out(side.data(), items.data(), nq, mode, counts, marks, item_mark);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_marks_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int ink, const float* quads, int nq, int32_t* mode,
+                   int32_t* counts, int32_t* marks, int32_t* item_mark) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  marks_in_ok("ttr_marks_page", img, h, w, row_stride, min_side, max_side, fill, ink, quads, nq);
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_marks_page");
+  std::vector<int32_t> side(kMarkSideInts), items((size_t)nq);
+  E.marks_stage(img, h, w, row_stride, 0, 0, min_side, max_side, fill, ink, quads, nq, side.data(), items.data(), nullptr);
+  marks_out(side.data(), items.data(), nq, mode, counts, marks, item_mark);
   return 0;
   TTR_GUARD_END(-1)
 }

@@ -1,6 +1,7 @@
 // Developer hooks of include/tuatara_hip_debug.h: single-kernel test entry points, micro-benchmarks, the tuning registry.
 #include "engine.h"
 #include "tables_rule.h"
+#include "marks_rule.h"
 
 using namespace ttr;
 
@@ -801,6 +802,25 @@ int ttr_dbg_ink_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_st
   InkRec r;
   E.ink_stage(img, h, w, row_stride, dev_offset, dev_stride, radius, drop, polarity, bits, bitsT, &r);
   if (rec) memcpy(rec, &r, sizeof r);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int64_t ttr_dbg_page_ink_passes(const ttr_engine* e) { return e ? e->e->page_ink_passes : -1; }
+
+// selection marks (DESIGN.md "Selection marks"): the corner count and the band counts as the device formed them
+int ttr_dbg_marks(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_side, int max_side, int fill, int ink,
+                  int32_t* corners, int32_t* band_counts, int32_t* mode, int32_t* marks) {
+  TTR_GUARD_BEGIN
+  if (!e || !img) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_dbg_marks");
+  std::vector<int32_t> side(kMarkSideInts);
+  E.marks_stage(img, h, w, row_stride, dev_offset, dev_stride, min_side, max_side, fill, ink, nullptr, 0, side.data(), nullptr, band_counts);
+  if (corners) *corners = side[2];
+  if (mode) *mode = side[0];
+  if (marks) std::copy(side.begin() + kMarkHdr, side.end(), marks);
   return 0;
   TTR_GUARD_END(-1)
 }

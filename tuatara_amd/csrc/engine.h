@@ -348,6 +348,10 @@ struct Result {
   std::vector<int32_t> table_lines;         // per table its rows + 1 row lines, then its cols + 1 column lines, in doubled px
   std::vector<int32_t> cells;               // 9 per cell: table, row, col, rowspan, colspan, x0, y0, x1, y1
   std::vector<int32_t> item_table, item_cell;   // 1 per item: -1 = in no cell
+  // selection marks (ttr_engine_set_marks; DESIGN.md "Selection marks"): 0 / empty when off and for region calls
+  int mark_mode = 0;                        // 1, or -6 for a page of more than 512 marks
+  std::vector<int32_t> marks;               // 12 per mark: x0, y0, x1, y1, ix0, iy0, ix1, iy1, inked, area, state, label
+  std::vector<int32_t> item_mark;           // 1 per item: the mark its centre lies in, -1 = none
   // text blocks (cfg.blocks = 1; DESIGN.md "Text blocks"): empty / 0 when off
   std::vector<int32_t> line_block, line_pos;     // 1 per line: its block in reading order, its position inside that block
   std::vector<int32_t> block;                    // 1 per item: its line's block
@@ -554,6 +558,9 @@ constexpr BufRow kDevBufTable[] = {
     {"tab_side", false, kElI32, ""},
     {"tab_ink_h", false, kElU8, ""},
     {"tab_ink_rec", false, kElI32, ""},
+    {"mark_cand", false, kElI32, ""},
+    {"mark_counts", false, kElI32, ""},
+    {"mark_side", false, kElI32, ""},
     {"blocks_side", false, kElI32, ""},
     {"chars_map", false, kElF32, ""},
     {"chars_in", false, kElI32, ""},
@@ -590,6 +597,9 @@ struct Engine {
   int lex_band = -1; float lex_gap = 0.f;         // fuzzy alignment (ttr_engine_set_lexicon_fuzzy): the band 0..3 (-1 = off: the rigid scorer) and the gap's log-probability
   float wide = 0.f;                               // wide words: the largest aspect a piece may have, 0 = off or 2..64 (ttr_engine_set_wide; DESIGN.md "Wide words")
   bool curved = false;                            // curved words: straighten the crops of words set on an arc (ttr_engine_set_curved; DESIGN.md "Curved words")
+  // selection marks: the smallest side in px, 0 = off or 8..64; the largest side, min..128; the fill threshold in 256ths, 1..255; the ink threshold 1..255
+  // (ttr_engine_set_marks; DESIGN.md "Selection marks")
+  int marks_min = 0, marks_max = 64, marks_fill = 24, marks_ink = 128;
   int tables_min_len = 0, tables_ink = 128;       // tables: the shortest ruling in px, 0 = off or 16..4096, and the ink threshold 1..255 (ttr_engine_set_tables; DESIGN.md "Tables")
   // tiled pages (ttr_engine_set_tiled; DESIGN.md "Tiled pages"): the tiles' overlap in pixels, 0 = off.  On, a page keeps its own scale (ratio 1, page canvas
   // c32(h) x c32(w)); one larger than the detector canvas goes through CRAFT as overlapping tiles whose maps tile_stitch_kernel joins into `heat`
@@ -706,6 +716,11 @@ struct Engine {
   PinnedBuf h_curve[2];                           // ... per slot: its host copy
   DevBuf tab_bits, tab_bitsT, tab_runs, tab_side; // tables: the two bitmaps and the run lists (workspaces), and the side blocks [pages][kTabSideInts] | [N][2] table, cell (tables.hip)
   PinnedBuf h_tab[2];                             // ... per slot: the side blocks' host copy
+  // selection marks (marks.hip): the bands' record slots and counters (workspaces), and the side blocks [pages][kMarkSideInts] | [N] item_mark.  The bitmaps are
+  // the tables pass's (tab_bits / tab_bitsT), formed once per batch whichever of the two layers is on
+  DevBuf mark_cand, mark_counts, mark_side;
+  PinnedBuf h_mark[2];                            // ... per slot: the side blocks' host copy
+  int64_t page_ink_passes = 0;                    // the ink passes page_ink_enqueue has enqueued for batches (ttr_dbg_page_ink_passes: one per batch, whichever layers are on)
   DevBuf tab_ink_h, tab_ink_rec;                  // local ink under tables (and ttr_ink_page): the horizontal sums [pages][Hcap][Wcap] uint32, the records [pages]
   DevBuf blocks_side;                             // text blocks: the side block (blocks.hip)
   PinnedBuf h_blocks[2];                          // ... per slot: its host copy
@@ -1025,6 +1040,8 @@ struct Engine {
     // tables (DESIGN.md "Tables"): the engine's setting when the boxes were made (0 = off, and for region calls), and 64 x every word's centre [N][2]
     int tab_min_len = 0, tab_ink = 0;
     std::vector<int32_t> tab_centres;
+    // selection marks (DESIGN.md "Selection marks"): the engine's setting when the boxes were made (mark_min 0 = off, and for region calls); they share the centres
+    int mark_min = 0, mark_max = 0, mark_fill = 0, mark_ink = 0;
     std::vector<DeskewRec> dsk_recs;   // deskew: the pages' records as the device wrote them (detect_collect_local takes them from the slot's pinned copy)
     // local ink (DESIGN.md "Local ink"): the engine's setting when the detector was enqueued (radius 0 = off), and the records of the deskew pass, taken with dsk_recs
     int ink_radius = 0, ink_drop = 0, ink_polarity = 0;
@@ -1087,6 +1104,16 @@ struct Engine {
   void plan_curved(PageBatch& B, const float* quads);
   // tables: the two kernels of batch B behind its packer (the centres and page offsets travelled with the rectangles' upload); a no-op with tables off
   void tables_enqueue(const PageBatch& B, int sl);
+  // the ink pass of batch B into tab_bits / tab_bitsT (the fixed rule under `ink`, or the local rule and its records when the batch has a radius): tables_enqueue's
+  // and marks_enqueue's first step, run once per batch
+  void page_ink_enqueue(const PageBatch& B, int sl, int ink);
+  // selection marks: the two kernels of batch B behind its packer, or - for a batch without words - on their own; the ink pass first unless tables_enqueue ran it.
+  // A no-op with marks off
+  void marks_enqueue(const PageBatch& B, int sl);
+  // the stage form (ttr_marks_page, and the developer hook): as tables_stage, through table_ink_kernel, mark_cand_kernel and mark_page_kernel -> side
+  // [kMarkSideInts], item_mark [nq], counts [ceil(h / 32)][2]
+  void marks_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_side, int max_side, int fill, int ink, const float* quads,
+                   int nq, int32_t* side_out, int32_t* item_mark_out, int32_t* counts_out);
   // the stage form (ttr_tables_page, and the developer hook): a host image, placed dev_offset bytes into a device buffer with dev_stride bytes from row to row
   // (0 = 3 w), and host quads through table_ink_kernel and table_grid_kernel -> side [kTabSideInts], items [nq][2], bits [h][ceil(w / 64)], runs [2][8192][3]
   // deskew: ink, scores, choice and resampling of batch B's pages ahead of its resize, on `stream`; redirects B.pages to the slot's upright copies
@@ -1146,7 +1173,8 @@ struct Engine {
   // lexicon matches' (lexicon.hip, B.lex_m per item) or null; pat_logp: best mode's log-probabilities (pattern.hip, one per item) or null
   void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
                     std::vector<Result>& results, const void* alts_side = nullptr, const void* lex_side = nullptr, const int32_t* wide_cuts = nullptr,
-                    const float* pat_logp = nullptr, const void* curve_block = nullptr, const int32_t* tab_block = nullptr);
+                    const float* pat_logp = nullptr, const void* curve_block = nullptr, const int32_t* tab_block = nullptr,
+                    const int32_t* mark_block = nullptr);
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it
@@ -1241,6 +1269,7 @@ struct Engine {
     f("lex_side", lex_side, kElI32); f("lex_part", lex_part, kElI32); f("wide_side", wide_side, kElI32); f("curve_side", curve_side, kElI32);
     f("tab_bits", tab_bits, kElU8); f("tab_bitsT", tab_bitsT, kElU8); f("tab_runs", tab_runs, kElI32); f("tab_side", tab_side, kElI32);
     f("tab_ink_h", tab_ink_h, kElU8); f("tab_ink_rec", tab_ink_rec, kElI32);
+    f("mark_cand", mark_cand, kElI32); f("mark_counts", mark_counts, kElI32); f("mark_side", mark_side, kElI32);
     f("blocks_side", blocks_side, kElI32);
     for (auto& d : chars_map) f("chars_map", d, kElF32);
     f("chars_in", chars_in, kElI32); f("chars_side", chars_side, kElI32);

@@ -6,6 +6,7 @@
 #include "engine.h"
 #include "page_table.h"
 #include "tables_rule.h"
+#include "marks_rule.h"
 
 namespace ttr {
 
@@ -314,6 +315,9 @@ void Engine::detect_enqueue(PageBatch& B) {
   if (tables_min_len)                     // tables: the rule's coordinates are below 32768 (likewise before anything is enqueued)
     for (const Page& P : B.pages)
       if (P.h >= 32768 || P.w >= 32768) throw std::runtime_error("tables: a page side of 32768 px or more: ttr_engine_set_tables(e, 0, 0) first");
+  if (marks_min)                          // selection marks: likewise
+    for (const Page& P : B.pages)
+      if (P.h >= 32768 || P.w >= 32768) throw std::runtime_error("marks: a page side of 32768 px or more: ttr_engine_set_marks(e, 0, 0, 0, 0) first");
   // Deskew (DESIGN.md "Deskew"): every page's skew is estimated and the batch's pages become upright copies in the slot's buffer; everything below and behind
   // reads B.pages as ever.  Off: nothing here runs.
   B.ink_radius = ink_radius; B.ink_drop = ink_drop; B.ink_polarity = ink_polarity;   // local ink: fixed for the batch here (the setter refuses while batches stream)
@@ -483,6 +487,7 @@ void Engine::detect_collect_local(PageBatch& B) {
   std::vector<float> wq;                                       // wide != 0 or curved: each word's quad (DESIGN.md "Wide words", "Curved words")
   host_us[1] = host_us[2] = host_us[3] = 0.f;
   B.tab_min_len = tables_min_len; B.tab_ink = tables_ink; B.tab_centres.clear();   // tables: fixed for the batch here (the setter refuses while batches stream)
+  B.mark_min = marks_min; B.mark_max = marks_max; B.mark_fill = marks_fill; B.mark_ink = marks_ink;   // selection marks: likewise
   std::vector<float> tq;
   for (int gi = 0; gi < groups; ++gi) ccl_collect(gi * GP, std::min(GP, n - gi * GP), gi, B.H2, B.W2, dets);
   // deskew: the batch's records were copied ahead of its detector on the same stream, so they are here; taken now, before the slot's next batch overwrites them
@@ -521,10 +526,10 @@ void Engine::detect_collect_local(PageBatch& B) {
       B.boxes[i].push_back(b);
       B.rects.insert(B.rects.end(), {x0, y0, x1, y1, i});
       B.page_of.push_back(i);
-      if (B.tab_min_len) {   // tables: 64 x the centre of the quad the result will carry (DESIGN.md "Tables", step 8)
+      if (B.tab_min_len || B.mark_min) {   // tables, selection marks: 64 x the centre of the quad the result will carry (DESIGN.md "Tables", step 8)
         tq.clear();
         push_quad(b, tq);
-        if (!region_quad_ok(tq.data())) throw std::runtime_error("tables: a corner of a word of page " + std::to_string(i) + " is not finite or lies beyond 32768 px");
+        if (!region_quad_ok(tq.data())) throw std::runtime_error(std::string(B.tab_min_len ? "tables" : "marks") + ": a corner of a word of page " + std::to_string(i) + " is not finite or lies beyond 32768 px");
         int32_t c[2];
         tables_word_centre(tq.data(), c);
         B.tab_centres.insert(B.tab_centres.end(), c, c + 2);
@@ -600,13 +605,13 @@ void Engine::plan_curved(PageBatch& B, const float* quads) {
 
 void Engine::pack_batch_crops(const PageBatch& B, int sl) {
   const int rows = B.N + B.X;                                  // wide words: X more rows behind the batch's N
-  // (tables: every word's centre [N][2] and the pages' offsets [n + 1] travel behind the rectangles, in the same copy)
-  const size_t rect_ints = B.rects.size(), tab_ints = B.tab_min_len ? B.tab_centres.size() + (size_t)B.n + 1 : 0;
+  // (tables, selection marks: every word's centre [N][2] and the pages' offsets [n + 1] travel behind the rectangles, in the same copy)
+  const size_t rect_ints = B.rects.size(), tab_ints = B.tab_min_len || B.mark_min ? B.tab_centres.size() + (size_t)B.n + 1 : 0;
   rects_dev.ensure((rect_ints + tab_ints) * 4);
   h_rects[sl].ensure((rect_ints + tab_ints) * 4);
   memcpy(h_rects[sl].p, B.rects.data(), rect_ints * 4);
   if (tab_ints) {
-    if (B.tab_centres.size() != (size_t)B.N * 2) throw std::runtime_error("tables: centre count does not match the crop count");
+    if (B.tab_centres.size() != (size_t)B.N * 2) throw std::runtime_error(std::string(B.tab_min_len ? "tables" : "marks") + ": centre count does not match the crop count");
     int32_t* t = h_rects[sl].as<int32_t>() + rect_ints;
     std::copy(B.tab_centres.begin(), B.tab_centres.end(), t);
     const std::vector<int> first = page_first(B.page_of, B.n);
@@ -942,24 +947,34 @@ void Engine::curve_crops(const uint8_t* img, int h, int w, int row_stride, const
   if (knots) memcpy(knots, side.data() + curve_side_table_offset(nq), (size_t)nq * 288);
 }
 
+void Engine::page_ink_enqueue(const PageBatch& B, int sl, int ink) {
+  const int n = B.n;
+  ++page_ink_passes;
+  int Hcap = 0, Wcap = 0;
+  for (const Page& P : B.pages) { Hcap = std::max(Hcap, P.h); Wcap = std::max(Wcap, P.w); }
+  tab_bits.ensure(tables_bits_slot(Hcap, Wcap) * 8 * n); tab_bitsT.ensure(tables_bitsT_slot(Hcap, Wcap) * 8 * n);
+  const Page& P0 = B.pages[0];
+  const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
+  if (B.ink_radius) {   // local ink (DESIGN.md "Local ink"): the same bitmaps under the adaptive rule, and the pages' records beside the side blocks
+    tab_ink_h.ensure(ink_ws_bytes(Hcap, Wcap, n)); tab_ink_rec.ensure((size_t)n * sizeof(InkRec)); h_tab_ink[sl].ensure((size_t)n * sizeof(InkRec));
+    launch_ink_local(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, table, n, Hcap, Wcap, B.ink_radius, B.ink_drop, B.ink_polarity, tab_ink_h.as<uint32_t>(),
+                     tab_ink_rec.as<InkRec>(), tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  } else
+  launch_table_ink(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, table, n, Hcap, Wcap, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+}
+
 void Engine::tables_enqueue(const PageBatch& B, int sl) {
   const int n = B.n, N = B.N;
   int Hcap = 0, Wcap = 0;
   for (const Page& P : B.pages) { Hcap = std::max(Hcap, P.h); Wcap = std::max(Wcap, P.w); }
   // (detect_enqueue refused a page side of 32768 or more before anything of the batch was enqueued)
-  tab_bits.ensure(tables_bits_slot(Hcap, Wcap) * 8 * n); tab_bitsT.ensure(tables_bitsT_slot(Hcap, Wcap) * 8 * n);
   tab_runs.ensure((size_t)n * 2 * kTabRunCap * 3 * 4);
   const size_t side_b = ((size_t)n * kTabSideInts + (size_t)N * 2) * 4;
   tab_side.ensure(side_b); h_tab[sl].ensure(side_b);
   const Page& P0 = B.pages[0];
   const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
   const int* centres = rects_dev.as<int>() + B.rects.size();
-  if (B.ink_radius) {   // local ink (DESIGN.md "Local ink"): the same bitmaps under the adaptive rule, and the pages' records beside the side blocks
-    tab_ink_h.ensure(ink_ws_bytes(Hcap, Wcap, n)); tab_ink_rec.ensure((size_t)n * sizeof(InkRec)); h_tab_ink[sl].ensure((size_t)n * sizeof(InkRec));
-    launch_ink_local(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, table, n, Hcap, Wcap, B.ink_radius, B.ink_drop, B.ink_polarity, tab_ink_h.as<uint32_t>(),
-                     tab_ink_rec.as<InkRec>(), tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
-  } else
-  launch_table_ink(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, table, n, Hcap, Wcap, B.tab_ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  page_ink_enqueue(B, sl, B.tab_ink);
   launch_table_grid(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), P0.h, P0.w, table, n, Hcap, Wcap, B.tab_min_len, centres, centres + (size_t)N * 2, tab_runs.as<int>(),
                     tab_side.as<int>(), tab_side.as<int>() + (size_t)n * kTabSideInts, stream);
   if (B.mixed) TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the table's last reader of this batch is now this kernel)
@@ -996,6 +1011,72 @@ void Engine::tables_stage(const uint8_t* img, int h, int w, int row_stride, int 
   if (!tables_side_valid(side.data(), &why)) throw std::runtime_error("ttr_tables_page: the side block holds " + why);
   if (side_out) std::copy(side.begin(), side.begin() + kTabSideInts, side_out);   // (validated: the counted part is what callers read)
   if (items_out) std::copy(side.begin() + kTabSideInts, side.end(), items_out);
+}
+
+void Engine::marks_enqueue(const PageBatch& B, int sl) {
+  const int n = B.n, N = B.N;
+  int Hcap = 0, Wcap = 0;
+  for (const Page& P : B.pages) { Hcap = std::max(Hcap, P.h); Wcap = std::max(Wcap, P.w); }
+  // (detect_enqueue refused a page side of 32768 or more before anything of the batch was enqueued)
+  mark_cand.ensure(marks_cand_ints(Hcap, n) * 4); mark_counts.ensure(marks_count_ints(Hcap, n) * 4);
+  const size_t side_b = ((size_t)n * kMarkSideInts + (size_t)N) * 4;
+  mark_side.ensure(side_b); h_mark[sl].ensure(side_b);
+  const Page& P0 = B.pages[0];
+  const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
+  const int* centres = rects_dev.as<int>() + B.rects.size();
+  if (N == 0) {   // a batch without words has no packer and so no upload: the pages' offsets [n + 1], all 0, go up here
+    rects_dev.ensure(((size_t)n + 1) * 4); h_rects[sl].ensure(((size_t)n + 1) * 4);
+    std::fill(h_rects[sl].as<int32_t>(), h_rects[sl].as<int32_t>() + n + 1, 0);
+    TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[sl].p, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, stream));
+    centres = rects_dev.as<int>();
+  }
+  // the bitmaps: the tables pass's when it ran in this batch under the same rule (the local one, or the fixed one with the same `ink`), else formed here
+  const bool shared = B.tab_min_len && N > 0 && (B.ink_radius || B.tab_ink == B.mark_ink);
+  if (!shared) page_ink_enqueue(B, sl, B.mark_ink);
+  launch_mark_cand(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), P0.h, P0.w, table, n, Hcap, Wcap, B.mark_min, B.mark_max, B.mark_fill, mark_cand.as<int>(),
+                   mark_counts.as<int>(), stream);
+  launch_mark_page(mark_cand.as<int>(), mark_counts.as<int>(), n, Hcap, centres, centres + (size_t)N * 2, mark_side.as<int>(), mark_side.as<int>() + (size_t)n * kMarkSideInts, stream);
+  if (B.mixed) TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the table's last reader of this batch is now this kernel)
+}
+
+void Engine::marks_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_side, int max_side, int fill, int ink, const float* quads,
+                         int nq, int32_t* side_out, int32_t* item_mark_out, int32_t* counts_out) {
+  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("ttr_marks_page: bad image size");
+  if (h >= 32768 || w >= 32768) throw std::runtime_error("ttr_marks_page: a page side of 32768 px or more");
+  if (!marks_args_ok(min_side, max_side, fill, ink)) throw std::runtime_error("ttr_marks_page: min_side must lie in 8..64, max_side in min_side..128, fill and ink in 1..255");
+  const int ds = dev_stride ? dev_stride : w * 3;
+  if (dev_offset < 0 || ds < w * 3) throw std::runtime_error("ttr_marks_page: bad device offset or stride");
+  const size_t img_b = (size_t)dev_offset + (size_t)ds * h, in_ints = (size_t)nq * 2 + 2, side_b = ((size_t)kMarkSideInts + (size_t)nq) * 4;
+  const size_t cnt_b = marks_count_ints(h, 1) * 4;
+  staging_img.ensure(img_b); rects_dev.ensure(in_ints * 4); h_rects[0].ensure(in_ints * 4);
+  tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8);
+  mark_cand.ensure(marks_cand_ints(h, 1) * 4); mark_counts.ensure(cnt_b); mark_side.ensure(side_b);
+  int32_t* in = h_rects[0].as<int32_t>();
+  for (int i = 0; i < nq; ++i) {
+    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error("ttr_marks_page: quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+    tables_word_centre(quads + 8 * (size_t)i, in + 2 * (size_t)i);
+  }
+  in[2 * (size_t)nq] = 0; in[2 * (size_t)nq + 1] = nq;
+  uint8_t* d_img = staging_img.as<uint8_t>() + dev_offset;
+  TTR_HIP_CHECK(hipMemcpy2DAsync(d_img, (size_t)ds, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, in, in_ints * 4, hipMemcpyHostToDevice, stream));
+  launch_table_ink(d_img, 0, ds, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  launch_mark_cand(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), h, w, nullptr, 1, h, w, min_side, max_side, fill, mark_cand.as<int>(), mark_counts.as<int>(), stream);
+  launch_mark_page(mark_cand.as<int>(), mark_counts.as<int>(), 1, h, rects_dev.as<int>(), rects_dev.as<int>() + (size_t)nq * 2, mark_side.as<int>(),
+                   mark_side.as<int>() + kMarkSideInts, stream);
+  std::vector<int32_t> side(side_b / 4);
+  TTR_HIP_CHECK(hipMemcpyAsync(side.data(), mark_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  if (counts_out) TTR_HIP_CHECK(hipMemcpyAsync(counts_out, mark_counts.p, cnt_b, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  std::string why;
+  if (!marks_side_valid(side.data(), h, w, fill, nq, &why)) throw std::runtime_error("ttr_marks_page: the side block holds " + why);
+  for (int i = 0; i < nq; ++i)
+    if (side[kMarkSideInts + (size_t)i] < -1 || side[kMarkSideInts + (size_t)i] >= side[1]) throw std::runtime_error("ttr_marks_page: an item names a mark that does not exist");
+  if (side_out) {   // (validated: the counted part is what callers read; the rest is zero as on the host)
+    std::fill(side_out, side_out + kMarkSideInts, 0);
+    std::copy(side.begin(), side.begin() + kMarkHdr + (size_t)kMarkRec * side[1], side_out);
+  }
+  if (item_mark_out) std::copy(side.begin() + kMarkSideInts, side.end(), item_mark_out);
 }
 
 void Engine::ink_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int radius, int drop, int polarity, uint64_t* bits_out,
@@ -1059,6 +1140,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (cfg.lines) group_batch_lines(B, sl, line_words);               // text lines: from the boxes alone, so inside the packing stage (DESIGN.md "Text lines")
     if (cfg.blocks) group_batch_blocks(B, sl, line_words);             // text blocks: directly behind, from the lines' side block on the device (DESIGN.md "Text blocks")
     if (B.tab_min_len) tables_enqueue(B, sl);                          // tables: the pages' own pixels and the boxes just made (DESIGN.md "Tables")
+    if (B.mark_min) marks_enqueue(B, sl);                              // selection marks: likewise, on the bitmaps tables formed when it is on (DESIGN.md "Selection marks")
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     if (B.regions) {   // the caller's sets: one mask by value (the engine's own path), or the rows' table through the slot's pinned staging (one copy, no launch)
       main.mask = B.region_mask;
@@ -1094,10 +1176,16 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (X) TTR_HIP_CHECK(hipMemcpyAsync(h_wide[sl].p, wide_side.p, B.wide.size() * 17 * 4, hipMemcpyDeviceToHost, stream));   // the wide words' cuts (the profile stays on the device)
     if (!B.curve.empty()) TTR_HIP_CHECK(hipMemcpyAsync(h_curve[sl].p, curve_side.p, curve_side_bytes(N), hipMemcpyDeviceToHost, stream));   // the curved words' side block
     if (B.tab_min_len) TTR_HIP_CHECK(hipMemcpyAsync(h_tab[sl].p, tab_side.p, ((size_t)B.n * kTabSideInts + (size_t)N * 2) * 4, hipMemcpyDeviceToHost, stream));   // the tables' side blocks and the words' cells
-    if (B.tab_min_len && B.ink_radius) TTR_HIP_CHECK(hipMemcpyAsync(h_tab_ink[sl].p, tab_ink_rec.p, (size_t)B.n * sizeof(InkRec), hipMemcpyDeviceToHost, stream));   // ... and their ink records
+    if ((B.tab_min_len || B.mark_min) && B.ink_radius) TTR_HIP_CHECK(hipMemcpyAsync(h_tab_ink[sl].p, tab_ink_rec.p, (size_t)B.n * sizeof(InkRec), hipMemcpyDeviceToHost, stream));   // ... and their ink records
+    if (B.mark_min) TTR_HIP_CHECK(hipMemcpyAsync(h_mark[sl].p, mark_side.p, ((size_t)B.n * kMarkSideInts + (size_t)N) * 4, hipMemcpyDeviceToHost, stream));   // the marks' side blocks and the items' marks
   } else {
+    if (B.mark_min && !B.regions) marks_enqueue(B, sl);                // selection marks: a batch of pages without words - boxes only - is a legitimate form
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
+    if (B.mark_min && !B.regions) {
+      if (B.ink_radius) TTR_HIP_CHECK(hipMemcpyAsync(h_tab_ink[sl].p, tab_ink_rec.p, (size_t)B.n * sizeof(InkRec), hipMemcpyDeviceToHost, stream));
+      TTR_HIP_CHECK(hipMemcpyAsync(h_mark[sl].p, mark_side.p, (size_t)B.n * kMarkSideInts * 4, hipMemcpyDeviceToHost, stream));
+    }
   }
   if (comm && B.cap > 0) {   // the payload: the output block of cap rows per rank - [cap][26] ids | [cap][26] prob | [cap] conf -, straight from the recogniser's device buffer
     gath_dev[sl].ensure(block * comm->world);
@@ -1137,8 +1225,9 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   const float* pat_logp_block = B.pat_best && N > 0 ? h_pat_logp[B.slot].as<float>() : nullptr;  // the side block (pattern.hip, best mode)
   const void* curve_block = !B.curve.empty() && N > 0 ? h_curve[B.slot].p : nullptr;           // the side block (curve.hip)
   const int32_t* tab_block = B.tab_min_len && N > 0 ? h_tab[B.slot].as<int32_t>() : nullptr;    // the side blocks (tables.hip)
+  const int32_t* mark_block = B.mark_min && !B.regions ? h_mark[B.slot].as<int32_t>() : nullptr;   // the side blocks (marks.hip): there for a batch without words too
   decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block, wide_block, pat_logp_block, curve_block,
-               tab_block);
+               tab_block, mark_block);
   for (Result& r : results) r.tiles = B.tiles;                                                  // tiled pages: the tiles each page's detector ran as (0: off)
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
@@ -1146,7 +1235,7 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
 
 void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
                           std::vector<Result>& results, const void* alts_side, const void* lex_side, const int32_t* wide_cuts, const float* pat_logp, const void* curve_block,
-                          const int32_t* tab_block) {
+                          const int32_t* tab_block, const int32_t* mark_block) {
   const int n = B.n, N = B.N, K = orient_k();
   const std::vector<int> first = page_first(B.page_of, n);
   // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
@@ -1215,8 +1304,8 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
     } else if (deskew_M && B.regions) {   // a region call: the caller's quadrilaterals are in the caller's frame
       r.skew_on = 1; r.skew = DeskewRec{0, 0, 65536, 0, B.pages[(size_t)pg].w, B.pages[(size_t)pg].h, 0, 0, 0, 0};
     }
-    if (B.ink_radius && !B.regions && ((B.tab_min_len && N > 0) || B.dsk_M)) {   // local ink: the page's record - the tables pass's when it ran, else the deskew pass's - checked before anything is built on it
-      const bool from_tab = B.tab_min_len && N > 0;
+    if (B.ink_radius && !B.regions && ((B.tab_min_len && N > 0) || B.mark_min || B.dsk_M)) {   // local ink: the page's record - the tables or marks pass's when one ran, else the deskew pass's - checked before anything is built on it
+      const bool from_tab = (B.tab_min_len && N > 0) || B.mark_min;
       if (!from_tab && B.dsk_ink_recs.size() != (size_t)n) throw std::runtime_error("local ink: the batch carries no records");
       const InkRec k = from_tab ? h_tab_ink[B.slot].as<InkRec>()[pg] : B.dsk_ink_recs[(size_t)pg];
       std::string why;
@@ -1247,6 +1336,21 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t
         if (!none && (t < 0 || t >= counts[1] || c < r.tables[(size_t)t * 8 + 6] || c >= r.tables[(size_t)t * 8 + 6] + r.tables[(size_t)t * 8 + 7]))
           throw std::runtime_error("tables: word " + std::to_string(k) + " of page " + std::to_string(pg) + " names a table or cell that does not exist");
         r.item_table[(size_t)k] = t; r.item_cell[(size_t)k] = c;
+      }
+    }
+    if (B.mark_min && !B.regions) {   // selection marks: the page's side block and its items' marks, checked before anything is built on them
+      if (!mark_block) throw std::runtime_error("marks: the batch carries no side block");
+      const int32_t* ms = mark_block + (size_t)pg * kMarkSideInts;
+      const int32_t* mi = mark_block + (size_t)n * kMarkSideInts + (size_t)c0;
+      std::string why;
+      if (!marks_side_valid(ms, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, B.mark_fill, cnt, &why))
+        throw std::runtime_error("marks: the side block of page " + std::to_string(pg) + " holds " + why);
+      r.mark_mode = ms[0];
+      r.marks.assign(ms + kMarkHdr, ms + kMarkHdr + (size_t)kMarkRec * ms[1]);
+      r.item_mark.assign((size_t)cnt, -1);
+      for (int k = 0; k < cnt; ++k) {
+        if (mi[k] < -1 || mi[k] >= ms[1]) throw std::runtime_error("marks: word " + std::to_string(k) + " of page " + std::to_string(pg) + " names a mark that does not exist");
+        r.item_mark[(size_t)k] = mi[k];
       }
     }
     if (B.curved && cnt > 0) {   // curved words: every item's flag, outline and knot table, checked before anything is built on them
@@ -1628,6 +1732,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   if (wide != 0.f) throw std::runtime_error("latency mode does not support wide words: ttr_engine_set_wide(e, 0) first");
   if (curved) throw std::runtime_error("latency mode does not support curved words: ttr_engine_set_curved(e, 0) first");
   if (tables_min_len) throw std::runtime_error("latency mode does not support tables: ttr_engine_set_tables(e, 0, 0) first");
+  if (marks_min) throw std::runtime_error("latency mode does not support selection marks: ttr_engine_set_marks(e, 0, 0, 0, 0) first");
   if (tiled) throw std::runtime_error("latency mode does not support tiled pages: ttr_engine_set_tiled(e, 0) first");
   if (deskew_M) throw std::runtime_error("latency mode does not support deskew: ttr_engine_set_deskew(e, 0, 0, 0) first");
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");

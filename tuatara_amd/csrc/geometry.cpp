@@ -6,6 +6,7 @@
 #include "tables_rule.h"
 #include "deskew_rule.h"
 #include "ink_rule.h"
+#include "marks_rule.h"
 
 #include <algorithm>
 #include <climits>
@@ -1544,6 +1545,93 @@ bool ink_rec_valid(const InkRec& r, int radius, int drop, int polarity, int h, i
   if (r.sum > (uint64_t)kInkSMax * (uint64_t)h * (uint64_t)w) return bad("a sum beyond 765 h w");
   if (r.inverted != 0 && r.inverted != 1) return bad("an inverted flag that is neither 0 nor 1");
   if (r.inverted != ink_inverted(polarity, r.sum, h, w)) return bad("an inverted flag that does not follow from polarity and sum");
+  return true;
+}
+
+// ---- selection marks (DESIGN.md "Selection marks"): the host rule; integers only.  Every step is marks_rule.h's.
+void marks_transpose(const uint64_t* bits, int h, int w, uint64_t* bitsT) {
+  const int nwx = (w + 63) / 64, nwy = (h + 63) / 64;
+  std::fill(bitsT, bitsT + (size_t)w * nwy, (uint64_t)0);
+  for (int y = 0; y < h; ++y)
+    for (int k = 0; k < nwx; ++k)
+      for (uint64_t v = bits[(size_t)y * nwx + k]; v; v &= v - 1) {
+        const int x = 64 * k + mark_ctz(v);
+        if (x < w) bitsT[(size_t)x * nwy + (y >> 6)] |= (uint64_t)1 << (y & 63);
+      }
+}
+
+int marks_from_bits(const uint64_t* bits, const uint64_t* bitsT, int h, int w, int min_side, int max_side, int fill, int32_t* side, int32_t* counts) {
+  if (!bits || !bitsT || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || !marks_args_ok(min_side, max_side, fill, 128)) throw std::runtime_error("marks_from_bits: bad argument");
+  std::fill(side, side + kMarkSideInts, 0);
+  const int nwx = (w + 63) / 64, nwy = (h + 63) / 64;
+  if (counts) std::fill(counts, counts + 2 * (size_t)((h + 31) / 32), 0);
+  int n = 0, corners = 0;
+  int32_t rec[kMarkRec];
+  for (int y = 0; y < h; ++y) {   // 2 - 5, in (y, x) order
+    const uint64_t* row = bits + (size_t)y * nwx;
+    for (int k = 0; k < nwx; ++k)
+      for (uint64_t c = mark_corners(row, y ? row - nwx : nullptr, k); c; c &= c - 1) {
+        ++corners;
+        if (counts) counts[2 * (y / 32) + 1]++;
+        if (!mark_test(bits, nwx, bitsT, nwy, 64 * k + mark_ctz(c), y, min_side, max_side, fill, rec)) continue;
+        if (counts) counts[2 * (y / 32)]++;
+        if (n < kMarkCap) std::copy(rec, rec + kMarkRec, side + kMarkHdr + kMarkRec * n);
+        ++n;
+      }
+  }
+  side[2] = corners; side[3] = n;
+  if (n > kMarkCap) {   // 6: the cap
+    std::fill(side + kMarkHdr, side + kMarkSideInts, 0);
+    side[0] = -6;
+    return -6;
+  }
+  side[0] = 1; side[1] = n;
+  return 1;
+}
+
+void marks_items(int32_t* side, const int32_t* centres, int n, int32_t* item_mark) {
+  std::vector<int32_t> own;
+  if (!item_mark) { own.resize((size_t)n); item_mark = own.data(); }
+  for (int i = 0; i < n; ++i) item_mark[i] = mark_item(side, centres[2 * (size_t)i], centres[2 * (size_t)i + 1]);
+  if (side[0] != 1) return;
+  for (int m = 0; m < side[1]; ++m) {
+    int32_t* r = side + kMarkHdr + kMarkRec * m;
+    r[11] = mark_label(r, centres, item_mark, n);
+  }
+}
+
+int marks_from_page(const uint8_t* image, int h, int w, int stride, int min_side, int max_side, int fill, int ink, int32_t* side, int32_t* counts) {
+  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !marks_args_ok(min_side, max_side, fill, ink))
+    throw std::runtime_error("marks_from_page: bad argument");
+  std::vector<uint64_t> bits(tables_bitmap_words(h, w)), bitsT(tables_bitmap_words(w, h));
+  tables_ink(image, h, w, stride, ink, bits.data());
+  marks_transpose(bits.data(), h, w, bitsT.data());
+  return marks_from_bits(bits.data(), bitsT.data(), h, w, min_side, max_side, fill, side, counts);
+}
+
+int marks_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_side, int max_side, int fill, int radius, int drop, int polarity, int32_t* side) {
+  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !marks_args_ok(min_side, max_side, fill, 128) || !ink_args_ok(radius, drop, polarity))
+    throw std::runtime_error("marks_from_page_ink: bad argument");
+  std::vector<uint64_t> bits(tables_bitmap_words(h, w)), bitsT(tables_bitmap_words(w, h));
+  ink_from_page(image, h, w, stride, radius, drop, polarity, bits.data(), bitsT.data(), nullptr);
+  return marks_from_bits(bits.data(), bitsT.data(), h, w, min_side, max_side, fill, side, nullptr);
+}
+
+bool marks_side_valid(const int32_t* s, int h, int w, int fill, int items, std::string* why) {
+  auto bad = [&](const char* m) { if (why) *why = m; return false; };
+  if (s[0] != 1 && s[0] != -6) return bad("a mode that is neither 1 nor -6");
+  if (s[1] < 0 || s[1] > kMarkCap) return bad("a mark count beyond the cap");
+  if (s[0] == -6 && s[1] != 0) return bad("marks on a page beyond the cap");
+  if (s[2] < 0 || s[3] < s[1] || (s[0] == 1 && s[3] != s[1]) || (s[0] == -6 && s[3] <= kMarkCap)) return bad("counters that do not match its mode");
+  for (int m = 0; m < s[1]; ++m) {
+    const int32_t* r = s + kMarkHdr + kMarkRec * m;
+    if (r[0] < 0 || r[1] < 0 || r[2] >= w || r[3] >= h || r[0] > r[2] || r[1] > r[3]) return bad("a box outside the page");
+    if (r[4] <= r[0] || r[5] <= r[1] || r[6] >= r[2] || r[7] >= r[3] || r[4] > r[6] || r[5] > r[7]) return bad("an interior outside its box");
+    if (r[9] != (r[6] - r[4] + 1) * (r[7] - r[5] + 1) || r[8] < 0 || r[8] > r[9]) return bad("an ink count beyond its interior");
+    if (r[10] != (256 * r[8] >= fill * r[9] ? 1 : 0)) return bad("a state that is not the rule's");
+    if (r[11] < -1 || r[11] >= items) return bad("a label that is no item");
+    if (m && (r[1] < r[-kMarkRec + 1] || (r[1] == r[-kMarkRec + 1] && r[0] <= r[-kMarkRec]))) return bad("marks out of (y, x) order");
+  }
   return true;
 }
 

@@ -196,6 +196,24 @@ int tables_from_page_ink(const uint8_t* image, int h, int w, int stride, int min
 void deskew_from_page_ink(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, int radius, int drop, int polarity, uint8_t* out, int out_stride,
                           DeskewRec* rec, uint64_t* scores);
 
+// Selection marks (ttr_engine_set_marks; DESIGN.md "Selection marks").  Checkboxes are found on the ink bitmap as small square frames, their state read from the
+// ink inside, every item given its mark and every mark its label.  Every step lives in marks_rule.h, shared with mark_cand_kernel and mark_page_kernel
+// (marks.hip); the side block's layout (kMarkSideInts int32) is described there.  min_side 8..64, max_side min_side..128, fill 1..255, ink 1..255.
+// bitsT [w][ceil(h / 64)] from bits [h][ceil(w / 64)]: the same bits along y
+void marks_transpose(const uint64_t* bits, int h, int w, uint64_t* bitsT);
+// steps 2 - 6 behind ready bitmaps: side receives the block (labels -1), counts (may be null) [ceil(h / 32)][2] the kept candidates and corners of every band of
+// 32 rows.  Returns the mode: 1, or -6 for a page of more than 512 marks (the block then holds the header alone).
+int marks_from_bits(const uint64_t* bits, const uint64_t* bitsT, int h, int w, int min_side, int max_side, int fill, int32_t* side, int32_t* counts = nullptr);
+// step 7: item_mark [n] from the centres [n][2] (tables_word_centre), and every mark's label into the block
+void marks_items(int32_t* side, const int32_t* centres, int n, int32_t* item_mark);
+// 1 - 6 on one page under the fixed ink rule, and under the local rule in the place of `ink`
+int marks_from_page(const uint8_t* image, int h, int w, int stride, int min_side, int max_side, int fill, int ink, int32_t* side, int32_t* counts = nullptr);
+int marks_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_side, int max_side, int fill, int radius, int drop, int polarity, int32_t* side);
+// what decode_pages accepts from the device: a legal mode, a count within the cap, boxes inside the h x w page with x0 <= x1 and y0 <= y1, interiors inside their
+// boxes, inked <= area = the interior's pixel count, state the rule's on inked / area / fill, labels in -1..items - 1, marks in (y, x) order.  why (may be null)
+// receives the reason.
+bool marks_side_valid(const int32_t* side, int h, int w, int fill, int items, std::string* why = nullptr);
+
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.
 struct Component {

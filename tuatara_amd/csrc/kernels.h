@@ -404,6 +404,19 @@ void launch_deskew_score(const uint64_t* bits, const PageRow* table, int pages, 
 // cs int32 [257][2] the host's (C, S) table (geometry.h: deskew_consts); recs [pages] the pages' records
 void launch_deskew_rotate(const PageRow* src_table, const PageRow* dst_table, int pages, int Hcap, int Wcap, int max_slope, int gain, const uint64_t* scores, const int* cs,
                           DeskewRec* recs, hipStream_t s);
+// ---- marks.hip (DESIGN.md "Selection marks")
+// The candidate pass works on bands of 32 rows; a launch has marks_bands(Hcap) of them per page, and every band 512 record slots and two counters.
+constexpr int kMarkBandRows = 32;
+inline int marks_bands(int Hcap) { return (Hcap + kMarkBandRows - 1) / kMarkBandRows; }
+inline size_t marks_cand_ints(int Hcap, int pages) { return (size_t)pages * (size_t)marks_bands(Hcap) * 512 * 12; }
+inline size_t marks_count_ints(int Hcap, int pages) { return (size_t)pages * (size_t)marks_bands(Hcap) * 2; }
+// mark_cand_kernel: steps 2 - 5 on every page, pages x bands.  bits / bitsT: the bitmaps of a pixel pass of the same launch geometry (table null: h / w of a
+// uniform batch, else the device page table); cand int32 [pages][bands][512][12] (workspace), counts int32 [pages][bands][2] = kept, corners
+void launch_mark_cand(const uint64_t* bits, const uint64_t* bitsT, int h, int w, const PageRow* table, int pages, int Hcap, int Wcap, int min_side, int max_side, int fill,
+                      int* cand, int* counts, hipStream_t s);
+// mark_page_kernel: steps 6 - 7, one workgroup per page.  centres int32 [N][2] and first int32 [pages + 1] as launch_table_grid takes them; side int32
+// [pages][kMarkSideInts] (marks_rule.h); item_mark int32 [N]
+void launch_mark_page(const int* cand, const int* counts, int pages, int Hcap, const int* centres, const int* first, int* side, int* item_mark, hipStream_t s);
 // get_detected_boxes' per-component tail on the GPU (tuatara.cpp:162-179: niter, ROI, dilation, findNonZero + minAreaRect): one lane per candidate, geometry.cpp's
 // arithmetic step for step (float32 calipers, double where OpenCV is double) -> CclBuffers::rects.  After launch_ccl on the same stream.
 void launch_ccl_rects(const CclBuffers& b, int pages, int H, int W, hipStream_t s);

@@ -65,6 +65,8 @@ thread_local std::string g_call_error;   // last_call_error()
 thread_local int g_call_tiled = 0;       // set_tiled(): the overlap of this thread's calls, 0 = off (then TUATARA_TILED decides)
 thread_local int g_call_tables = 0, g_call_tables_ink = 128;   // set_tables(): min_len and ink of this thread's calls, 0 = off (then TUATARA_TABLES decides)
 thread_local std::vector<TableGrid> g_call_table_out;          // last_call_tables()
+thread_local int g_call_marks = 0, g_call_marks_max = 64, g_call_marks_fill = 24, g_call_marks_ink = 128;   // set_marks(): this thread's calls, 0 = off (then TUATARA_MARKS decides)
+thread_local std::vector<SelectionMark> g_call_mark_out;       // last_call_marks()
 thread_local int g_call_ink = 0, g_call_ink_drop = 38, g_call_ink_polarity = 2;   // set_local_ink(): this thread's calls, 0 = off (then TUATARA_LOCAL_INK decides)
 thread_local int g_call_deskew = 0, g_call_deskew_gain = 288, g_call_deskew_ink = 128;   // set_deskew(): this thread's calls, 0 = off (then TUATARA_DESKEW decides)
 thread_local PageSkew g_call_skew_out;                         // last_call_skew()
@@ -74,6 +76,7 @@ struct CharsetScope {
   bool set = false, ok = true;
   bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false, curved_set = false, fuzzy_set = false, tiled_set = false;
   bool tables_set = false;
+  bool marks_set = false;
   bool deskew_set = false;
   bool ink_set = false;
   CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
@@ -124,6 +127,13 @@ struct CharsetScope {
       if (ttr_engine_set_tables(e, tab, g_call_tables_ink) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
       tables_set = true;
     }
+    int mk = g_call_marks;
+    if (mk == 0) if (const char* p = std::getenv("TUATARA_MARKS")) mk = std::string(p) == "1" ? 10 : std::atoi(p);
+    g_call_mark_out.clear();
+    if (mk != 0) {   // selection marks (DESIGN.md "Selection marks"): the four parameters for the call, like the set
+      if (ttr_engine_set_marks(e, mk, g_call_marks_max, g_call_marks_fill, g_call_marks_ink) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      marks_set = true;
+    }
     int dsk = g_call_deskew;
     if (dsk == 0) if (const char* p = std::getenv("TUATARA_DESKEW")) dsk = std::string(p) == "1" ? 64 : std::atoi(p);
     g_call_skew_out = PageSkew();
@@ -164,6 +174,7 @@ struct CharsetScope {
     if (curved_set) ttr_engine_set_curved(e, 0);
     if (tiled_set) ttr_engine_set_tiled(e, 0);
     if (tables_set) ttr_engine_set_tables(e, 0, 0);
+    if (marks_set) ttr_engine_set_marks(e, 0, 0, 0, 0);
     if (deskew_set) ttr_engine_set_deskew(e, 0, 0, 0);
     if (ink_set) ttr_engine_set_ink(e, 0, 0, 0);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
@@ -255,6 +266,8 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
   const int32_t *it = ttr_result_item_table(r), *ic = ttr_result_item_cell(r);
   o.table = it ? it[i] : -1;
   o.cell = ic ? ic[i] : -1;
+  const int32_t* im = ttr_result_item_mark(r);
+  o.mark = im ? im[i] : -1;
   o.curved = false; o.outline.clear();
   if (const int32_t* cv = ttr_result_curved(r)) {
     const float* ol = ttr_result_outlines(r);
@@ -313,6 +326,16 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
       PageSkew& o = g_call_skew_out;
       o.on = true; o.slope = sk.slope; o.found = sk.found; o.C = sk.C; o.S = sk.S; o.w = sk.w; o.h = sk.h; o.mode = sk.mode;
       o.degrees = std::atan((double)sk.slope / 512.0) * 180.0 / 3.14159265358979323846;
+    }
+  }
+  if (const int32_t* mk = ttr_result_marks(r)) {    // selection marks: every mark of the page (last_call_marks())
+    for (int m = 0; m < ttr_result_mark_count(r); ++m) {
+      const int32_t* q = mk + 12 * (size_t)m;
+      SelectionMark s;
+      for (int k = 0; k < 4; ++k) { s.box[k] = q[k]; s.interior[k] = q[4 + k]; }
+      s.inked = q[8]; s.area = q[9]; s.selected = q[10] != 0; s.label = q[11];
+      if (s.label >= 0 && (size_t)s.label < out.size()) s.text = out[(size_t)s.label].text;
+      g_call_mark_out.push_back(std::move(s));
     }
   }
   if (const int32_t* tb = ttr_result_tables(r)) {   // tables: every table as rows x cols strings (last_call_tables())
@@ -561,6 +584,9 @@ std::string last_call_error() { return g_call_error; }
 
 void set_tiled(int overlap) { g_call_tiled = overlap; }
 int tiled() { return g_call_tiled; }
+void set_marks(int min_side, int max_side, int fill, int ink) { g_call_marks = min_side; g_call_marks_max = max_side; g_call_marks_fill = fill; g_call_marks_ink = ink; }
+int marks() { return g_call_marks; }
+std::vector<SelectionMark> last_call_marks() { return g_call_mark_out; }
 void set_tables(int min_len, int ink) { g_call_tables = min_len; g_call_tables_ink = ink; }
 int tables() { return g_call_tables; }
 std::vector<TableGrid> last_call_tables() { return g_call_table_out; }

@@ -312,6 +312,18 @@ SYMBOLS = [
     ("ttr_ink_from_page", _I, [_PU8, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
     ("ttr_ink_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
     ("ttr_dbg_ink_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    ("ttr_engine_set_marks", _I, [_VP, _I, _I, _I, _I]),
+    ("ttr_engine_marks", _I, [_VP, _PI, _PI, _PI]),
+    ("ttr_result_mark_mode", _I, [_VP]),
+    ("ttr_result_mark_count", _I, [_VP]),
+    ("ttr_result_marks", _PI, [_VP]),
+    ("ttr_result_item_mark", _PI, [_VP]),
+    ("ttr_results_gather_marks", _I, [C.POINTER(_VP), _I, _PI]),
+    ("ttr_marks_from_page", _I, [_PU8, _I, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI]),
+    ("ttr_marks_from_page_ink", _I, [_PU8, _I, _I, _I, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI]),
+    ("ttr_marks_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI]),
+    ("ttr_dbg_marks", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, _I, _I, _PI, _PI, _PI, _PI]),
+    ("ttr_dbg_page_ink_passes", C.c_int64, [_VP]),
     ("ttr_tables_from_page_ink", _I, [_PU8, _I, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI, _PI, _PI, _PI, _PI]),
     ("ttr_deskew_from_page_ink", _I, [_PU8, _I, _I, _I, _I, _I, _I, _I, _I, _PU8, C.c_void_p, C.POINTER(C.c_uint64)]),
     ("ttr_engine_set_tiled", _I, [_VP, _I]),
@@ -1066,6 +1078,70 @@ def _tables_call(fn, image, quads, min_len, ink, row_stride=0):
             "item_table": it[:nq].copy(), "item_cell": ic[:nq].copy(), "runs": (int(counts[4]), int(counts[5]))}
 
 
+MARKS_MIN_SIDE, MARKS_MAX_SIDE, MARKS_FILL, MARKS_INK = 10, 64, 24, 128   # what marks=True means (DESIGN.md "Selection marks": none of them has been tuned on documents)
+MARK_FIELDS = ("x0", "y0", "x1", "y1", "ix0", "iy0", "ix1", "iy1", "inked", "area", "state", "label")
+
+
+def _marks_arg(marks):
+    """False / None / 0 -> off; True -> the defaults; (min_side, max_side, fill, ink) or a bare min_side otherwise"""
+    if marks is None or marks is False or (isinstance(marks, int) and not isinstance(marks, bool) and marks == 0):
+        return 0, MARKS_MAX_SIDE, MARKS_FILL, MARKS_INK
+    if marks is True:
+        return MARKS_MIN_SIDE, MARKS_MAX_SIDE, MARKS_FILL, MARKS_INK
+    if isinstance(marks, (tuple, list)) and len(marks) == 4:
+        return tuple(int(v) for v in marks)
+    if isinstance(marks, int):
+        return int(marks), MARKS_MAX_SIDE, MARKS_FILL, MARKS_INK
+    raise EngineError("marks must be False, True or (min_side, max_side, fill, ink)")
+
+
+def _marks_call(fn, image, quads, params, row_stride=0):
+    """the shared body of marks_from_page and Engine.marks_page: fn(image..., params..., quads, outputs...) -> the dict both return"""
+    image = np.asarray(image, dtype=np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise RuntimeError("Input array should have 3 dimensions")
+    if not row_stride:
+        image = np.ascontiguousarray(image)
+    q = np.zeros((0, 8), np.float32) if quads is None else np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+    nq = len(q)
+    mode, counts, marks, im = np.zeros(1, np.int32), np.zeros(3, np.int32), np.zeros((512, 12), np.int32), np.full(max(nq, 1), -1, np.int32)
+    fn(_u8(image), image.shape[0], image.shape[1], int(row_stride) or image.shape[1] * 3, *[int(v) for v in params], _f(q), nq, _i(mode), _i(counts), _i(marks), _i(im))
+    return {"mode": int(mode[0]), "marks": marks[:counts[0]].copy(), "item_mark": im[:nq].copy(), "corners": int(counts[1]), "kept": int(counts[2])}
+
+
+def marks_from_page(image, quads=None, min_side: int = MARKS_MIN_SIDE, max_side: int = MARKS_MAX_SIDE, fill: int = MARKS_FILL, ink: int = MARKS_INK,
+                    row_stride: int = 0) -> dict:
+    """The selection-marks rule on the host (ttr_marks_from_page, no GPU; DESIGN.md "Selection marks"): a host image u8 [H, W, 3] (row_stride: the bytes from
+    row to row of a view into a wider buffer) and quads f32 [nq, 8] -> {"mode" (1, or -6 beyond 512 marks), "marks" i32 [n, 12] (MARK_FIELDS), "item_mark" i32
+    [nq], "corners" (examined), "kept" (candidates, beyond 512 on a page of mode -6)}."""
+    lib = load()
+
+    def fn(*a):
+        _lib_check(lib.ttr_marks_from_page(*a))
+    return _marks_call(fn, image, quads, (min_side, max_side, fill, ink), row_stride)
+
+
+def marks_from_page_ink(image, quads=None, min_side: int = MARKS_MIN_SIDE, max_side: int = MARKS_MAX_SIDE, fill: int = MARKS_FILL, local_ink=True,
+                        row_stride: int = 0) -> dict:
+    """marks_from_page under the local ink rule (ttr_marks_from_page_ink): local_ink = True or (radius, drop, polarity) in the place of ink"""
+    lib = load()
+    r, d, p = _local_ink_arg(local_ink)
+
+    def fn(*a):
+        _lib_check(lib.ttr_marks_from_page_ink(*a))
+    return _marks_call(fn, image, quads, (min_side, max_side, fill, r, d, p), row_stride)
+
+
+def mark_dicts(marks, texts=None) -> list:
+    """mark records i32 [n, 12] -> [{"box", "interior", "selected", "fill", "label", "text"}] (text: the label's, "" without one or without texts)"""
+    out = []
+    for m in np.asarray(marks, np.int32).reshape(-1, 12):
+        lab = int(m[11])
+        out.append({"box": [int(v) for v in m[0:4]], "interior": [int(v) for v in m[4:8]], "selected": bool(m[10]), "fill": float(m[8]) / float(m[9]),
+                    "label": lab, "text": texts[lab] if texts is not None and lab >= 0 else ""})
+    return out
+
+
 DESKEW_MAX_SLOPE, DESKEW_GAIN, DESKEW_INK = 64, 288, 128   # what deskew=True means (DESIGN.md "Deskew": none of them has been tuned on documents)
 
 
@@ -1261,8 +1337,10 @@ class PageResult(collections.abc.Sequence):
     record {"slope", "found", "C", "S", "w", "h", "mode", "score0", "score_found", "degrees"} or None when the layer is off; every coordinate of the result is
     in the upright page's frame, to_page(points) maps points to the caller's page and every dict gains "quad_page".  Local ink (Engine.set_local_ink; DESIGN.md
     "Local ink"): `ink` = the page's record {"radius", "drop", "polarity", "inverted", "sum", "w", "h"} - the tables pass's when tables ran, else the deskew
-    pass's - or None when no pass of the page ran under it."""
-    __slots__ = ("skew", "quad_page", "ink",
+    pass's - or None when no pass of the page ran under it.  Selection marks (Engine.set_marks; DESIGN.md "Selection marks"): `mark_mode` (1, or -6 beyond 512
+    marks; 0 = off), `mark_recs` i32 [n, 12] (MARK_FIELDS) and `item_mark` i32 [items], None when off; `marks` the list of {"box", "interior", "selected",
+    "fill", "label", "text"}; every dict gains "mark"; a page without items has its marks too."""
+    __slots__ = ("skew", "quad_page", "ink", "mark_mode", "mark_recs", "item_mark",
                  "table_mode", "rulings", "table_rects", "table_lines", "cells", "item_table", "item_cell", "cell_texts",
                  "texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
@@ -1278,8 +1356,12 @@ class PageResult(collections.abc.Sequence):
                  alt_ids=None, alt_prob=None, lex_idx=None, lex_logp=None, lex_words=None, pattern_logp=None,
                  piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None,
                  curved=None, outline=None, spine_knots=None, lex_edits=None, lex_band=-1, tiles=0,
-                 table_mode=0, rulings=None, table_rects=None, table_lines=None, cells=None, item_table=None, item_cell=None, cell_texts=None, skew=None, quad_page=None, ink=None):
+                 table_mode=0, rulings=None, table_rects=None, table_lines=None, cells=None, item_table=None, item_cell=None, cell_texts=None, skew=None, quad_page=None, ink=None,
+                 mark_mode=0, mark_recs=None, item_mark=None):
         self.tiles = tiles
+        # selection marks (Engine.set_marks; DESIGN.md "Selection marks"): mark_mode 1, or -6 beyond 512 marks, 0 = off; mark_recs i32 [n, 12] (MARK_FIELDS), in
+        # the upright page's frame under deskew; item_mark i32 [items] the mark every item's centre lies in (-1 = none); None when marks are off
+        self.mark_mode, self.mark_recs, self.item_mark = mark_mode, mark_recs, item_mark
         self.ink = ink
         self.skew, self.quad_page = skew, quad_page     # quad_page f32 [n, 8]: every quad on the caller's page (ttr_result_to_page), None without deskew or quads
         self.table_mode, self.rulings, self.table_rects, self.table_lines, self.cells = table_mode, rulings, table_rects, table_lines, cells
@@ -1343,9 +1425,17 @@ class PageResult(collections.abc.Sequence):
             d["curved"], d["outline"] = int(self.curved[j]), self.outline[j].tolist()
         if self.item_table is not None:
             d["table"], d["cell"] = int(self.item_table[j]), int(self.item_cell[j])
+        if self.item_mark is not None:
+            d["mark"] = int(self.item_mark[j])
         if self.quad_page is not None:
             d["quad_page"] = _quad_pairs(self.quad_page[j])
         return d
+
+    @property
+    def marks(self) -> list:
+        """the page's selection marks in (y, x) order: {"box": [x0, y0, x1, y1], "interior", "selected", "fill" (inked / area), "label" (an item or -1), "text"
+        (the label's)}; [] when marks are off"""
+        return [] if self.mark_recs is None else mark_dicts(self.mark_recs, self.texts)
 
     def to_page(self, points) -> np.ndarray:
         """points [..., 2] of this result's frame -> the caller's page (the identity when deskew is off), float32"""
@@ -1484,6 +1574,7 @@ class Engine:
         wide = _wide_arg(overrides.pop("wide", None))                                     # nor this: set_wide, below
         curved = bool(overrides.pop("curved", False))                                     # nor this: set_curved, below
         tiled = _tiled_arg(overrides.pop("tiled", None))                                  # nor this: set_tiled, below
+        marks = _marks_arg(overrides.pop("marks", None))                                  # nor this: set_marks, below
         tables = _tables_arg(overrides.pop("tables", None))                               # nor this: set_tables, below
         deskew = _deskew_arg(overrides.pop("deskew", None))                               # nor this: set_deskew, below
         local_ink = _local_ink_arg(overrides.pop("local_ink", None))                      # nor this: set_local_ink, below
@@ -1516,6 +1607,8 @@ class Engine:
             self.set_tiled(tiled)
         if tables[0]:
             self.set_tables(tables)
+        if marks[0]:
+            self.set_marks(marks)
         if deskew[0]:
             self.set_deskew(deskew)
         if local_ink[0]:
@@ -1594,6 +1687,44 @@ class Engine:
         ink = C.c_int()
         m = int(self.lib.ttr_engine_tables(self.h, C.byref(ink)))
         return (m, int(ink.value)) if m else None
+
+    def set_marks(self, marks=True):
+        """Find every page's checkboxes and their state and give every item its mark (ttr_engine_set_marks; DESIGN.md "Selection marks"): False / 0 = off,
+        True = (10, 64, 24, 128), else (min_side 8..64, max_side min_side..128, fill 1..255, ink 1..255) or a bare min_side; none of the defaults has been
+        tuned on documents.  Refused while batches stream and with a communicator attached."""
+        a = _marks_arg(marks)
+        if self.lib.ttr_engine_set_marks(self.h, *a) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode())
+
+    @property
+    def marks(self):
+        """(min_side, max_side, fill, ink) in force, or None when marks are off"""
+        mx, fl, ink = C.c_int(), C.c_int(), C.c_int()
+        m = int(self.lib.ttr_engine_marks(self.h, C.byref(mx), C.byref(fl), C.byref(ink)))
+        return (m, mx.value, fl.value, ink.value) if m else None
+
+    def marks_page(self, image, quads=None, min_side: int = MARKS_MIN_SIDE, max_side: int = MARKS_MAX_SIDE, fill: int = MARKS_FILL, ink: int = MARKS_INK) -> dict:
+        """ttr_marks_page: table_ink_kernel, mark_cand_kernel and mark_page_kernel on a host image u8 [H, W, 3] and host quads f32 [nq, 8], whatever the
+        engine's setting -> the dict marks_from_page returns."""
+        def fn(*a):
+            self._check(self.lib.ttr_marks_page(self.h, *a))
+        return _marks_call(fn, image, quads, (min_side, max_side, fill, ink))
+
+    def marks_debug(self, image, min_side: int = MARKS_MIN_SIDE, max_side: int = MARKS_MAX_SIDE, fill: int = MARKS_FILL, ink: int = MARKS_INK, dev_offset: int = 0,
+                    dev_stride: int = 0) -> dict:
+        """ttr_dbg_marks: the corner count, the band counts i32 [ceil(H / 32), 2] (kept, corners) and the marks as the device formed them; the image is placed
+        dev_offset bytes into a device buffer with dev_stride bytes from row to row (0 = 3 W)"""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        h, w = image.shape[:2]
+        corners, mode, bands, marks = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(((h + 31) // 32, 2), np.int32), np.zeros((512, 12), np.int32)
+        self._check(self.lib.ttr_dbg_marks(self.h, _u8(image), h, w, w * 3, int(dev_offset), int(dev_stride), int(min_side), int(max_side), int(fill), int(ink),
+                                           _i(corners), _i(bands), _i(mode), _i(marks)))
+        n = int(bands[:, 0].sum()) if mode[0] == 1 else 0
+        return {"mode": int(mode[0]), "corners": int(corners[0]), "bands": bands, "marks": marks[:n].copy()}
+
+    def page_ink_passes(self) -> int:
+        """ttr_dbg_page_ink_passes: the ink passes enqueued for the batches' page layers so far (tables and marks in one batch share one)"""
+        return int(self.lib.ttr_dbg_page_ink_passes(self.h))
 
     def tables_page(self, image, quads=None, min_len: int = TABLES_MIN_LEN, ink: int = TABLES_INK) -> dict:
         """ttr_tables_page: table_ink_kernel and table_grid_kernel on a host image u8 [H, W, 3] and host quads f32 [nq, 8], whatever the engine's setting ->
@@ -2102,6 +2233,12 @@ class Engine:
                            table_rects=view(self.lib.ttr_result_tables(r), (nt_, 8)), table_lines=view(lp, (nl_.value,)),
                            cells=view(self.lib.ttr_result_cells(r), (nc_, 9)), item_table=view(self.lib.ttr_result_item_table(r), (c,)),
                            item_cell=view(self.lib.ttr_result_item_cell(r), (c,)), cell_texts=texts_c)
+            if self.lib.ttr_result_mark_mode(arr[i]):    # selection marks: the page's marks and its items' marks (there for a page without items too)
+                nm_ = int(self.lib.ttr_result_mark_count(arr[i]))
+                mp, ip = self.lib.ttr_result_marks(arr[i]), self.lib.ttr_result_item_mark(arr[i])
+                lex.update(mark_mode=int(self.lib.ttr_result_mark_mode(arr[i])),
+                           mark_recs=np.ctypeslib.as_array(mp, (nm_, 12)).copy() if mp and nm_ else np.zeros((0, 12), np.int32),
+                           item_mark=np.ctypeslib.as_array(ip, (c,)).copy() if ip and c else np.full(c, -1, np.int32))
             pl = self.lib.ttr_result_pattern_logp(arr[i])
             if pl:                              # patterns in best mode: the page's log-probabilities
                 lex["pattern_logp"] = np.ctypeslib.as_array(pl, (c,)).copy()
