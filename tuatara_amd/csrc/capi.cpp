@@ -265,9 +265,7 @@ int ttr_image_to_data(ttr_engine* e, const uint8_t* img, int h, int w, int row_s
   if (!img || h <= 0 || w <= 0) throw std::runtime_error("Error reading image from file");  // tuatara.cpp:344-347
   Engine& E = *e->e;
   EngineScope lk(E);
-  E.staging_img.ensure((size_t)h * w * 3);
-  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
-  run_locked(e, E.staging_img.as<uint8_t>(), 1, h, w, out);
+  run_locked(e, E.stage_page("ttr_image_to_data", img, h, w, row_stride, 0, 0, 0, nullptr, false).data, 1, h, w, out);   // (checked above, under the reference's text)
   return 0;
   TTR_GUARD_END(-1)
 }
@@ -684,10 +682,9 @@ int ttr_resize_canvas(ttr_engine* e, const uint8_t* img, int h, int w, int row_s
   *H = g.h32; *W = g.w32; *ratio = g.ratio;
   const size_t need = (size_t)g.h32 * g.w32 * 3;
   if (cap < need) throw std::runtime_error("canvas buffer too small");
-  E.staging_img.ensure((size_t)h * w * 3);
   E.canvas.ensure(need);
-  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
-  launch_resize_pad_u8(E.staging_img.as<uint8_t>(), h, w, w * 3, E.canvas.as<uint8_t>(), g.target_h, g.target_w, g.h32, g.w32, 1, E.stream);
+  const Engine::StagedPage pg = E.stage_page("ttr_resize_canvas", img, h, w, row_stride, 0, 0, 0, nullptr, false);   // (this call has never checked its image)
+  launch_resize_pad_u8(pg.data, h, w, pg.stride, E.canvas.as<uint8_t>(), g.target_h, g.target_w, g.h32, g.w32, 1, E.stream);
   TTR_HIP_CHECK(hipMemcpyAsync(canvas, E.canvas.p, need, hipMemcpyDeviceToHost, E.stream));
   TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
   return 0;
@@ -899,10 +896,9 @@ int ttr_image_regions_to_data_p(ttr_engine* e, const uint8_t* img, int h, int w,
   Engine& E = *e->e;
   EngineScope lk(E);
   E.refuse_while_streaming("regions");                    // (before the staging buffer, which streamed batches may still read, is touched)
-  E.staging_img.ensure((size_t)h * w * 3);
-  const ttr_page page{E.staging_img.as<uint8_t>(), h, w, w * 3};
   // the copy is enqueued first (a refused call costs a copy, changes nothing: the staging image is scratch of the synchronous entry points)
-  TTR_HIP_CHECK(hipMemcpy2DAsync(E.staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, E.stream));
+  const Engine::StagedPage pg = E.stage_page("regions", img, h, w, row_stride, 0, 0, 0, nullptr, false);   // (checked above, under the reference's text)
+  const ttr_page page{pg.data, h, w, pg.stride};
   std::vector<Result> res;
   struct Drain { Engine& E; ~Drain() { (void)hipStreamSynchronize(E.stream); } } drain{E};   // (the caller's image is pageable: the copy ends inside the call, refused or not)
   E.run_regions(&page, 1, regions, n, sets, n_sets, res, patterns, n_patterns, pattern_of);
@@ -1608,13 +1604,22 @@ static void tables_out(const int32_t* side, const int32_t* items, int nq, int32_
   }
 }
 
-static void tables_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq) {
-  if (!img || nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
+// the checks the one-page calls of tables, deskew, local ink and marks share: the image (a side of side_cap px or more is refused), and the words' quads
+static void page_image_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int side_cap) {
+  if (!img) throw std::runtime_error("null argument");
   if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
-  if (h >= 32768 || w >= 32768) throw std::runtime_error(std::string(what) + ": a page side of 32768 px or more");
-  if (!tables_args_ok(min_len, ink)) throw std::runtime_error(std::string(what) + ": min_len must lie in 16..4096 and ink in 1..255, got " + std::to_string(min_len) + " and " + std::to_string(ink));
+  if (h >= side_cap || w >= side_cap) throw std::runtime_error(std::string(what) + ": a page side of " + std::to_string(side_cap) + " px or more");
+}
+static void page_quads_ok(const char* what, const float* quads, int nq) {
   for (int i = 0; i < nq; ++i)
     if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error(std::string(what) + ": quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+}
+
+static void tables_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq) {
+  if (nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
+  page_image_ok(what, img, h, w, row_stride, 32768);
+  if (!tables_args_ok(min_len, ink)) throw std::runtime_error(std::string(what) + ": min_len must lie in 16..4096 and ink in 1..255, got " + std::to_string(min_len) + " and " + std::to_string(ink));
+  page_quads_ok(what, quads, nq);
 }
 
 int ttr_tables_from_page(const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq, int32_t* mode, int32_t* counts,
@@ -1706,9 +1711,7 @@ int ttr_results_gather_skew(ttr_result* const* rs, int n, ttr_skew* recs) {
 }
 
 static void deskew_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink) {
-  if (!img) throw std::runtime_error("null argument");
-  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
-  if (h >= kDskSideCap || w >= kDskSideCap) throw std::runtime_error(std::string(what) + ": a page side of 8192 px or more");
+  page_image_ok(what, img, h, w, row_stride, kDskSideCap);
   if (!dsk_args_ok(max_slope, gain, ink))
     throw std::runtime_error(std::string(what) + ": max_slope must lie in 1..128, gain in 256..65535 and ink in 1..255, got " + std::to_string(max_slope) + ", " + std::to_string(gain) +
                              " and " + std::to_string(ink));
@@ -1732,7 +1735,7 @@ int ttr_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_str
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_deskew_page");
   DeskewRec r;
-  E.deskew_stage(img, h, w, row_stride, 0, 0, max_slope, gain, ink, out_img, w * 3, &r, scores);
+  E.deskew_stage(img, h, w, row_stride, 0, 0, max_slope, gain, ink, out_img, &r, scores);
   if (rec) memcpy(rec, &r, sizeof r);
   return 0;
   TTR_GUARD_END(-1)
@@ -1783,9 +1786,7 @@ int ttr_results_gather_ink(ttr_result* const* rs, int n, ttr_ink* recs) {
 }
 
 static void ink_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int radius, int drop, int polarity) {
-  if (!img) throw std::runtime_error("null argument");
-  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
-  if (h >= 32768 || w >= 32768) throw std::runtime_error(std::string(what) + ": a page side of 32768 px or more");
+  page_image_ok(what, img, h, w, row_stride, 32768);
   if (!ink_args_ok(radius, drop, polarity)) throw std::runtime_error(std::string(what) + ": radius must lie in 1..64, " + ink_ranges(radius, drop, polarity));
 }
 
@@ -1895,12 +1896,10 @@ static void marks_out(const int32_t* side, const int32_t* items, int nq, int32_t
 }
 
 static void marks_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int ink, const float* quads, int nq) {
-  if (!img || nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
-  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
-  if (h >= 32768 || w >= 32768) throw std::runtime_error(std::string(what) + ": a page side of 32768 px or more");
+  if (nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
+  page_image_ok(what, img, h, w, row_stride, 32768);
   if (!marks_args_ok(min_side, max_side, fill, ink)) throw std::runtime_error(std::string(what) + ": " + marks_ranges(min_side, max_side, fill, ink));
-  for (int i = 0; i < nq; ++i)
-    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error(std::string(what) + ": quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+  page_quads_ok(what, quads, nq);
 }
 
 static void marks_host_items(int32_t* side, const float* quads, int nq, int32_t* items) {

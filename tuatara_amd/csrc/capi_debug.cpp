@@ -786,7 +786,7 @@ int ttr_dbg_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row
   EngineScope lk(E);
   E.refuse_while_streaming("ttr_dbg_deskew_page");
   DeskewRec r;
-  E.deskew_stage(img, h, w, row_stride, dev_offset, dev_stride, max_slope, gain, ink, out_img, w * 3, &r, scores);
+  E.deskew_stage(img, h, w, row_stride, dev_offset, dev_stride, max_slope, gain, ink, out_img, &r, scores);
   if (rec) memcpy(rec, &r, sizeof r);
   return 0;
   TTR_GUARD_END(-1)

@@ -281,6 +281,18 @@ struct PinnedBuf {
   PinnedBuf& operator=(const PinnedBuf&) = delete;
 };
 
+// The host half of an opt-in page layer's side block, per pipeline slot: the pinned copy and the bytes the slot's batch fetches into it, 0 = the layer did not
+// run for that batch.  recog_enqueue disarms the slot's records; each layer arms its own where it sizes its device block; fetch copies exactly the armed bytes;
+// finish reads through view(), so that a layer that did not run has no block to misread.  The device half stays a DevBuf member of the engine (kDevBufTable).
+struct SideCopy {
+  PinnedBuf host[2];
+  size_t bytes[2] = {0, 0};
+  void arm(int sl, size_t b) { host[sl].ensure(b); bytes[sl] = b; }
+  void disarm(int sl) { bytes[sl] = 0; }
+  void fetch(int sl, const DevBuf& dev, hipStream_t s) const { if (bytes[sl]) TTR_HIP_CHECK(hipMemcpyAsync(host[sl].p, dev.p, bytes[sl], hipMemcpyDeviceToHost, s)); }
+  template <typename U> const U* view(int sl) const { return bytes[sl] ? host[sl].as<U>() : nullptr; }
+};
+
 // A GEMM-shaped weight on the device: T [Cout_pad][K_pad] + f32 bias
 struct Linear {
   DevBuf w, b;
@@ -618,7 +630,8 @@ struct Engine {
   // and ttr_dbg_tables keep the fixed rule.  Tables and deskew run on different streams: each has its own workspace and records
   int ink_radius = 0, ink_drop = 38, ink_polarity = kInkAuto;
   DevBuf dsk_ink_h, dsk_ink_rec;                  // ... deskew's: the horizontal sums [pages][Hcap][Wcap] uint32, the records [pages]
-  PinnedBuf h_dsk_ink[2], h_tab_ink[2];           // ... per slot: the records' host copies
+  static size_t ink_recs_bytes(int pages) { return (size_t)pages * sizeof(InkRec); }   // a pass's records: [pages] InkRec
+  PinnedBuf h_dsk_ink[2]; SideCopy h_tab_ink;     // ... the records' host copies: the deskew pass's (the detector's stream; detect_collect takes them), the tables / marks pass's
   DevBuf tile_heat;                               // ... the tile canvases' maps [n T][Hc / 2][Wc / 2][2] (allocated by the first tiled batch)
   DevBuf tile_table[2];                           // ... the tiles as rows of a second page table, per slot (the packers go on reading page_table: the real pages)
   PinnedBuf h_tile_table[2];
@@ -643,11 +656,12 @@ struct Engine {
   // best mode's buffers: the masked argmax's standard block of the pass (launch_decode_conf into scratch: [N][26] id0 | [N][26] prob0 | [N] conf0), and the
   // side block [N] f32 with its pinned twin per slot
   DevBuf pat_best_scratch, pat_logp_dev;
-  PinnedBuf h_pat_logp[2];
+  SideCopy h_pat_logp;
+  static size_t pat_logp_bytes(int N) { return (size_t)N * 4; }   // the side block: [N] f32
   struct PatBestOut { int* id0; float* prob0; float* conf0; float* logp; PatExtent ext; };   // logp null = greedy mode
   PatBestOut pat_best_out(int N) {
     const RecOut o = rec_block(pat_best_scratch, N);
-    pat_logp_dev.ensure((size_t)std::max(N, 1) * 4);
+    pat_logp_dev.ensure(pat_logp_bytes(std::max(N, 1)));
     return PatBestOut{o.ids, o.prob, o.conf, pat_logp_dev.as<float>(), PatExtent{nullptr, 0, 0}};
   }
 
@@ -688,16 +702,18 @@ struct Engine {
   template <typename U = void> U* pq_buf(PqWs i, size_t bytes) { pq_ws[i].ensure(bytes); return pq_ws[i].as<U>(); }
   DevBuf canvas, heat, staging_img, crops, rects_dev, coef_dev, logits, ar_logits, ids_dev, tokens;
   DevBuf orient_in, orient_cand, orient_side;     // word orientation: the twins' coef | rects | page firsts; their recogniser block; the side block (orient.hip)
-  PinnedBuf h_orient_in[2], h_orient[2];          // ... per slot: staging of orient_in, host copy of the side block
+  PinnedBuf h_orient_in[2]; SideCopy h_orient;    // ... per slot: staging of orient_in; the side block's host copy, [N] turn | [N][K] candidate conf | [pages] page turn
+  static size_t orient_side_bytes(int N, int K, int pages) { return ((size_t)N * (K + 1) + pages) * 4; }
   DevBuf lines_in, lines_side;                    // text lines: the words' cuv | page firsts; the side block (lines.hip)
-  PinnedBuf h_lines_in[2], h_lines[2];            // ... per slot: staging of lines_in, host copy of the side block
+  PinnedBuf h_lines_in[2]; SideCopy h_lines;      // ... per slot: staging of lines_in; the side block's host copy, [N] line | [N] word | [pages] n_lines
+  static size_t lines_side_bytes(int N, int pages) { return ((size_t)2 * N + pages) * 4; }
   DevBuf alts_side;                               // character alternatives: the side block (decode_alts.hip), [N][26][K] int32 ids | [N][26][K] f32 prob
-  PinnedBuf h_alts[2];                            // ... per slot: its host copy
+  SideCopy h_alts;                                // ... its host copy
   struct AltOut { int* ids; float* prob; int k; };   // k: the block's alternatives per position, 0 = none
   static size_t alts_side_bytes(int N, int K) { return (size_t)N * 26 * K * 8; }
   AltOut alts_out(int N, int K) { alts_side.ensure(alts_side_bytes(std::max(N, 1), K)); return AltOut{alts_side.as<int>(), alts_side.as<float>() + (size_t)N * 26 * K, K}; }
   DevBuf lex_side, lex_part;                      // lexicon matching: the side block (lexicon.hip), [N][M] int32 idx | [N][M] f32 logp; the scorer's partials [N][chunks][M] idx | logp
-  PinnedBuf h_lex[2];                             // ... per slot: the side block's host copy
+  SideCopy h_lex;                                 // ... the side block's host copy
   // m: the block's matches per item, 0 = none; band >= 0: the fuzzy scorer under (band, gap) in the rigid one's place, edits [N][m] behind the two blocks
   struct LexOut { int* idx; float* logp; int* part_idx; float* part_logp; int m; int band = -1; float gap = 0.f; int* edits = nullptr; };
   static size_t lex_side_bytes(int N, int M, int band = -1) { return (size_t)N * M * (band >= 0 ? 12 : 8); }
@@ -711,21 +727,21 @@ struct Engine {
     return l;
   }
   DevBuf wide_side;                               // wide words: the side block (wide.hip), [Wn][17] int32 cuts | [Wn][2048] u16 profile
-  PinnedBuf h_wide[2];                            // ... per slot: the cuts' host copy
+  SideCopy h_wide;                                // ... the cuts' host copy (wide_cuts_bytes: the profile stays on the device)
   DevBuf curve_side;                              // curved words: the side block (curve.hip), [N] flag | [N][2] hb | [N][2][9] spine | [N][9][4] int64 knots
-  PinnedBuf h_curve[2];                           // ... per slot: its host copy
+  SideCopy h_curve;                               // ... its host copy
   DevBuf tab_bits, tab_bitsT, tab_runs, tab_side; // tables: the two bitmaps and the run lists (workspaces), and the side blocks [pages][kTabSideInts] | [N][2] table, cell (tables.hip)
-  PinnedBuf h_tab[2];                             // ... per slot: the side blocks' host copy
+  SideCopy h_tab;                                 // ... the side blocks' host copy
   // selection marks (marks.hip): the bands' record slots and counters (workspaces), and the side blocks [pages][kMarkSideInts] | [N] item_mark.  The bitmaps are
   // the tables pass's (tab_bits / tab_bitsT), formed once per batch whichever of the two layers is on
   DevBuf mark_cand, mark_counts, mark_side;
-  PinnedBuf h_mark[2];                            // ... per slot: the side blocks' host copy
+  SideCopy h_mark;                                // ... the side blocks' host copy
   int64_t page_ink_passes = 0;                    // the ink passes page_ink_enqueue has enqueued for batches (ttr_dbg_page_ink_passes: one per batch, whichever layers are on)
   DevBuf tab_ink_h, tab_ink_rec;                  // local ink under tables (and ttr_ink_page): the horizontal sums [pages][Hcap][Wcap] uint32, the records [pages]
   DevBuf blocks_side;                             // text blocks: the side block (blocks.hip)
-  PinnedBuf h_blocks[2];                          // ... per slot: its host copy
+  SideCopy h_blocks;                              // ... its host copy
   DevBuf chars_map[2], chars_in, chars_side;      // character boxes: per slot the batch's region planes (a copy of ccl.tnorm); coef | page_of | turns | nchars; the side block (chars.hip)
-  PinnedBuf h_chars_in[2], h_chars[2];            // ... per slot: staging of chars_in, host copy of the side block
+  PinnedBuf h_chars_in[2]; SideCopy h_chars;      // ... per slot: staging of chars_in; the side block's host copy
   hipEvent_t chars_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // ... per slot: the planes are copied; char_cut_kernel has read them (created with the first chars batch)
   CclBatch ccl;
   PinnedBuf h_counters, h_cand, h_rows, h_rects_f, h_rects[2], h_coef[2], h_ids[2];   // (h_coef: crop_mode = TTR_CROP_RECTIFIED only)   // pinned staging of the small host <-> device transfers
@@ -1023,6 +1039,8 @@ struct Engine {
     bool mixed = false;                // the pages came one by one (ttr_page) and may differ in size and stride: the table kernels run (DESIGN.md "Mixed-size batches")
     std::vector<Page> pages;           // [n] every page by itself; filled by detect_enqueue from the scalars above for a uniform batch
     int H = 0, W = 0, H2 = 0, W2 = 0;  // the canvas all pages share
+    struct Extent { int h = 0, w = 0; };   // the tallest and the widest page: what the page layers' per-page workspaces are sized and strided by
+    Extent extent() const { Extent e; for (const Page& P : pages) { e.h = std::max(e.h, P.h); e.w = std::max(e.w, P.w); } return e; }
     std::vector<std::vector<RRect>> boxes;
     std::vector<int> rects, page_of;
     std::vector<int64_t> coef;         // crop_mode = TTR_CROP_RECTIFIED: {kind, X0, Ax, Bx, Y0, Ay, By, 0} per crop, beside rects
@@ -1054,9 +1072,9 @@ struct Engine {
     std::vector<int32_t> all_counts;   // with a communicator: crops per page of every rank [world][n]
     int cap = 0;                       // ... and the largest rank total (rows of the gathered payload per rank)
     int rows = 0;                      // rows of the recogniser's output block (RecOut) staged in h_ids[slot]: max(N, cap)
-    int alts = 0;                      // the engine's `alts` when the recogniser was enqueued: h_alts[slot] holds [N][26][alts] ids | prob
-    bool pat_best = false;             // patterns in best mode, fixed when the recogniser was enqueued with a pattern in force: h_pat_logp[slot] holds [N] f32
-    int lex_m = 0;                     // the engine's `lex_m` when the recogniser was enqueued with a lexicon set (0 = none): h_lex[slot] holds [N][lex_m] idx | logp
+    int alts = 0;                      // the engine's `alts` when the recogniser was enqueued: h_alts's copy of the slot holds [N][26][alts] ids | prob
+    bool pat_best = false;             // patterns in best mode, fixed when the recogniser was enqueued with a pattern in force: h_pat_logp's copy of the slot holds [N] f32
+    int lex_m = 0;                     // the engine's `lex_m` when the recogniser was enqueued with a lexicon set (0 = none): h_lex's copy of the slot holds [N][lex_m] idx | logp
     int lex_band = -1;                 // ... and the engine's `lex_band` then (-1 = the rigid scorer): >= 0, [N][lex_m] int32 edits follow the two blocks
     // regions (run_regions; DESIGN.md "Regions and per-row character sets"): the boxes are the caller's quads - no detector ran, `boxes` stays empty, every crop is
     // a kind-1 crop of the table packer.  Crop c (page order, then the caller's order): its quad verbatim, its set index, and - when the sets differ - its row
@@ -1110,6 +1128,15 @@ struct Engine {
   // selection marks: the two kernels of batch B behind its packer, or - for a batch without words - on their own; the ink pass first unless tables_enqueue ran it.
   // A no-op with marks off
   void marks_enqueue(const PageBatch& B, int sl);
+  // The opening every one-page stage call shares.  stage_page: a host image (row_stride 0 = packed rows) checked under the caller's `what` - "bad image size",
+  // a page side of side_cap px or more (0 = no cap), `bad_args` (the layer's own range refusal, null = in range), "bad device offset or stride" - then copied
+  // dev_offset bytes into staging_img with dev_stride bytes from row to row (0 = 3 w), on `stream`; returns where it lies.  check = false: the caller has made
+  // the image check under a text of its own.  stage_centres: host quads checked, 64 x their centres [nq][2] and the page's offsets {0, nq} -> rects_dev
+  struct StagedPage { uint8_t* data; int stride; };
+  StagedPage stage_page(const char* what, const uint8_t* img, int h, int w, int row_stride, int dev_offset = 0, int dev_stride = 0, int side_cap = 0,
+                        const char* bad_args = nullptr, bool check = true);
+  void stage_centres(const char* what, const float* quads, int nq);
+  const PageRow* staged_page_table(const StagedPage& pg, int h, int w);   // ... and the staged page as the one row of slot 0's page table (the stage calls' use_table)
   // the stage form (ttr_marks_page, and the developer hook): as tables_stage, through table_ink_kernel, mark_cand_kernel and mark_page_kernel -> side
   // [kMarkSideInts], item_mark [nq], counts [ceil(h / 32)][2]
   void marks_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_side, int max_side, int fill, int ink, const float* quads,
@@ -1120,8 +1147,8 @@ struct Engine {
   void deskew_enqueue(PageBatch& B);
   const int* deskew_consts_dev();     // the (C, S) table on the device (uploaded by the first call)
   // the stage form (ttr_deskew_page, and the tests): a host image, placed dev_offset bytes into a device buffer with dev_stride bytes from row to row (0 = 3 w),
-  // through the pixel pass and the two kernels -> out [h][w][3] (out_stride bytes from row to row), the record, scores [2 max_slope + 1]; any may be null
-  void deskew_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int max_slope, int gain, int ink, uint8_t* out, int out_stride,
+  // through the pixel pass and the two kernels -> out [h][w][3] (packed rows), the record, scores [2 max_slope + 1]; any may be null
+  void deskew_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int max_slope, int gain, int ink, uint8_t* out,
                     DeskewRec* rec, uint64_t* scores);
   // local ink's stage form (ttr_ink_page, ttr_dbg_ink_page): a host image, placed as above, through ink_rows_kernel and ink_local_kernel -> bits
   // [h][ceil(w / 64)], bitsT [w][ceil(h / 64)], the record; any may be null
@@ -1144,21 +1171,21 @@ struct Engine {
   void pack_twin_crops(const PageBatch& B, int sl);
 
   // text lines: the words' fixed-point c, u, v and the pages' first words into the pinned staging of slot sl (host only; returns the largest
-  // word count of a page), then one copy of them, line_group_kernel into the side block and its copy to h_lines[sl]
+  // word count of a page), then one copy of them, line_group_kernel into the side block and its copy to the host (h_lines)
   int stage_batch_lines(const PageBatch& B, int sl);
   void group_batch_lines(const PageBatch& B, int sl, int max_words);
   // the stage form (ttr_group_lines): host quads [first[pages]][8] of several pages -> line, word [first[pages]], n_lines [pages]
   void group_lines(const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines);
   // text blocks: block_group_kernel behind line_group_kernel of the same batch (it reads lines_in and lines_side on the device) and the copy of its
-  // side block to h_blocks[sl]; the stage form (ttr_group_blocks): both kernels on host quads, block / pos [first[pages]] indexed by line within
-  // each page's range, n_blocks / mode [pages]; any output may be null
+  // side block to the host (h_blocks); the stage form (ttr_group_blocks): both kernels on host quads, block / pos [first[pages]] indexed by line within
+  // each page's range, n_blocks / mode [pages]; any output may be null.  blocks = false: the lines' kernel alone, under ttr_group_lines' name (group_lines)
   void group_batch_blocks(const PageBatch& B, int sl, int max_words);
   void group_blocks(const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines, int32_t* block, int32_t* pos,
-                    int32_t* n_blocks, int32_t* mode);
+                    int32_t* n_blocks, int32_t* mode, bool blocks = true);
 
   // character boxes: detect_enqueue keeps the batch's region planes (keep_batch_map, behind its CCL); stage_batch_chars writes every word's coefficients
   // (all four turns when orientation is on) and page into the pinned staging of slot sl (host only); cut_batch_chars copies them, runs char_cut_kernel
-  // behind the recogniser (K and the turn are read on the device) and copies the side block to h_chars[sl]
+  // behind the recogniser (K and the turn are read on the device) and copies the side block to the host (h_chars)
   void keep_batch_map(const PageBatch& B);
   void stage_batch_chars(const PageBatch& B, int sl);
   void cut_batch_chars(const PageBatch& B, int sl, const int* ids, const int* turns);
@@ -1167,14 +1194,19 @@ struct Engine {
                  int32_t* cuts, int32_t* modes, uint8_t* profiles);
 
   void finish(PageBatch& B, std::vector<Result>& results);
-  // results[pg] for every page of B from its boxes and the decoded rows of its crops (crop c is row c); side: the orientation side block
-  // of the batch (orient.hip) or null; lines_side: the text lines' side block (lines.hip) or null; chars_side: the characters' (chars.hip) or null;
-  // blocks_side: the text blocks' (blocks.hip) or null; alts_side: the alternatives' (decode_alts.hip, B.alts per position) or null; lex_side: the
-  // lexicon matches' (lexicon.hip, B.lex_m per item) or null; pat_logp: best mode's log-probabilities (pattern.hip, one per item) or null
-  void decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                    std::vector<Result>& results, const void* alts_side = nullptr, const void* lex_side = nullptr, const int32_t* wide_cuts = nullptr,
-                    const float* pat_logp = nullptr, const void* curve_block = nullptr, const int32_t* tab_block = nullptr,
-                    const int32_t* mark_block = nullptr);
+  // the host copies of a batch's side blocks as finish takes them from the SideCopy records (view(slot)): null = the layer did not run for the batch
+  struct SideViews {
+    const int32_t *orient = nullptr, *lines = nullptr, *blocks = nullptr, *chars = nullptr, *alts = nullptr, *lex = nullptr, *wide_cuts = nullptr, *curve = nullptr, *tab = nullptr, *mark = nullptr;
+    const float* pat_logp = nullptr; const InkRec* tab_ink = nullptr;
+  };
+  // results[pg] for every page of B from its boxes, the decoded rows of its crops (crop c is row c) and the side blocks: one function per layer, run page by
+  // page in the order below - later layers read what earlier ones wrote (blocks the lines, chars `quad` and `orient`, wide rewrites `text` and `conf`)
+  struct PageCtx { const PageBatch& B; const RecRows& rows; const SideViews& V; int pg, c0, cnt; };   // page pg owns crops [c0, c0 + cnt)
+  void decode_pages(const PageBatch& B, const RecRows& rows, const SideViews& views, std::vector<Result>& results);
+  // words: ids, prob, conf, alternatives, lexicon matches, pattern_logp, orientation, text, bbox, quad; records: the page's skew and ink records
+  void decode_words(const PageCtx&, Result&) const, decode_records(const PageCtx&, Result&) const, decode_tables(const PageCtx&, Result&) const,
+      decode_marks(const PageCtx&, Result&) const, decode_curved(const PageCtx&, Result&) const, decode_wide(const PageCtx&, Result&) const,
+      decode_lines(const PageCtx&, Result&) const, decode_blocks(const PageCtx&, Result&) const, decode_chars(const PageCtx&, Result&) const;
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
   // its own they would race with it

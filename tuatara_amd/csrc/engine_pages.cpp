@@ -52,6 +52,16 @@ std::string Result::page_text_blocks() const {
   return t;
 }
 
+// o = the union of boxes[order[k]] (4 floats each: min x, min y, max x, max y) over k in [k0, k1): a line's box from its words', a block's from its lines'
+static void bbox_union(const std::vector<float>& boxes, const std::vector<int32_t>& order, int k0, int k1, float* o) {
+  const float inf = std::numeric_limits<float>::infinity();
+  o[0] = o[1] = inf; o[2] = o[3] = -inf;
+  for (int k = k0; k < k1; ++k) {
+    const float* b = &boxes[4 * (size_t)order[k]];
+    o[0] = std::min(o[0], b[0]); o[1] = std::min(o[1], b[1]); o[2] = std::max(o[2], b[2]); o[3] = std::max(o[3], b[3]);
+  }
+}
+
 // crops are ordered by page: page pg owns crops [first[pg], first[pg + 1])
 static std::vector<int> page_first(const std::vector<int>& page_of, int pages) {
   std::vector<int> first(pages + 1, 0);
@@ -233,8 +243,7 @@ const int* Engine::deskew_consts_dev() {
 
 void Engine::deskew_enqueue(PageBatch& B) {
   const int n = B.n, sl = B.slot & 1, M = B.dsk_M;
-  int Hcap = 0, Wcap = 0;
-  for (const Page& P : B.pages) { Hcap = std::max(Hcap, P.h); Wcap = std::max(Wcap, P.w); }
+  const auto [Hcap, Wcap] = B.extent();
   // the upright copies: a uniform batch keeps its form (pages h w 3 bytes apart, rows 3 w), a mixed one gets tight pages at 256-byte offsets
   std::vector<size_t> off((size_t)n + 1, 0);
   for (int i = 0; i < n; ++i) {
@@ -245,7 +254,7 @@ void Engine::deskew_enqueue(PageBatch& B) {
   dsk_pages[sl].ensure(off[(size_t)n]); dsk_table[sl].ensure(rows_b); h_dsk_table[sl].ensure(rows_b); h_dsk[sl].ensure(rec_b);
   dsk_bits.ensure(tables_bits_slot(Hcap, Wcap) * 8 * n); dsk_bitsT.ensure(tables_bitsT_slot(Hcap, Wcap) * 8 * n);
   dsk_scores.ensure((size_t)n * (2 * M + 1) * 8); dsk_rec.ensure(rec_b);
-  const size_t ink_b = (size_t)n * sizeof(InkRec);
+  const size_t ink_b = ink_recs_bytes(n);
   if (B.ink_radius) { dsk_ink_h.ensure(ink_ws_bytes(Hcap, Wcap, n)); dsk_ink_rec.ensure(ink_b); h_dsk_ink[sl].ensure(ink_b); }   // local ink: its workspace and records
   if (!dsk_cs_up) throw std::logic_error("deskew: the constants table was not uploaded");
   PageRow* rows = h_dsk_table[sl].as<PageRow>();
@@ -269,20 +278,46 @@ void Engine::deskew_enqueue(PageBatch& B) {
   for (int i = 0; i < n; ++i) { B.pages[i].data = rows[n + i].data; B.pages[i].stride = B.pages[i].w * 3; }
 }
 
-void Engine::deskew_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int max_slope, int gain, int ink, uint8_t* out, int out_stride,
-                          DeskewRec* rec, uint64_t* scores) {
-  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("ttr_deskew_page: bad image size");
-  if (h >= kDskSideCap || w >= kDskSideCap) throw std::runtime_error("ttr_deskew_page: a page side of 8192 px or more");
-  if (!dsk_args_ok(max_slope, gain, ink)) throw std::runtime_error("ttr_deskew_page: max_slope must lie in 1..128, gain in 256..65535 and ink in 1..255");
+Engine::StagedPage Engine::stage_page(const char* what_, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int side_cap, const char* bad_args,
+                                      bool check) {
+  const std::string what(what_);
+  if (check && (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3))) throw std::runtime_error(what + ": bad image size");
+  if (side_cap && (h >= side_cap || w >= side_cap)) throw std::runtime_error(what + ": a page side of " + std::to_string(side_cap) + " px or more");
+  if (bad_args) throw std::runtime_error(what + ": " + bad_args);
   const int ds = dev_stride ? dev_stride : w * 3;
-  if (dev_offset < 0 || ds < w * 3 || (out && out_stride < w * 3)) throw std::runtime_error("ttr_deskew_page: bad device offset or stride");
-  const size_t img_b = (size_t)dev_offset + (size_t)ds * h, out_b = (size_t)h * w * 3, nsc = (size_t)2 * max_slope + 1;
-  staging_img.ensure(img_b); dsk_pages[0].ensure(out_b); dsk_table[0].ensure(2 * sizeof(PageRow));
+  if (dev_offset < 0 || ds < w * 3) throw std::runtime_error(what + ": bad device offset or stride");
+  staging_img.ensure((size_t)dev_offset + (size_t)ds * h);
+  uint8_t* d_img = staging_img.as<uint8_t>() + dev_offset;
+  TTR_HIP_CHECK(hipMemcpy2DAsync(d_img, (size_t)ds, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  return StagedPage{d_img, ds};
+}
+
+const PageRow* Engine::staged_page_table(const StagedPage& pg, int h, int w) {
+  upload_page_table(std::vector<Page>(1, Page{pg.data, h, w, pg.stride, CanvasGeom{h, w, h, w, 1.f}}), 0);
+  return page_table[0].as<PageRow>();
+}
+
+void Engine::stage_centres(const char* what, const float* quads, int nq) {
+  const size_t in_ints = (size_t)nq * 2 + 2;
+  rects_dev.ensure(in_ints * 4); h_rects[0].ensure(in_ints * 4);
+  int32_t* in = h_rects[0].as<int32_t>();
+  for (int i = 0; i < nq; ++i) {
+    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error(std::string(what) + ": quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+    tables_word_centre(quads + 8 * (size_t)i, in + 2 * (size_t)i);
+  }
+  in[2 * (size_t)nq] = 0; in[2 * (size_t)nq + 1] = nq;
+  TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, in, in_ints * 4, hipMemcpyHostToDevice, stream));
+}
+
+void Engine::deskew_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int max_slope, int gain, int ink, uint8_t* out,
+                          DeskewRec* rec, uint64_t* scores) {
+  const StagedPage pg = stage_page("ttr_deskew_page", img, h, w, row_stride, dev_offset, dev_stride, kDskSideCap,
+                                   dsk_args_ok(max_slope, gain, ink) ? nullptr : "max_slope must lie in 1..128, gain in 256..65535 and ink in 1..255");
+  const size_t out_b = (size_t)h * w * 3, nsc = (size_t)2 * max_slope + 1;
+  dsk_pages[0].ensure(out_b); dsk_table[0].ensure(2 * sizeof(PageRow));
   dsk_bits.ensure(tables_bits_slot(h, w) * 8); dsk_bitsT.ensure(tables_bitsT_slot(h, w) * 8); dsk_scores.ensure(nsc * 8); dsk_rec.ensure(sizeof(DeskewRec));
   const int* cs = deskew_consts_dev();
-  uint8_t* d_img = staging_img.as<uint8_t>() + dev_offset;
-  const PageRow rows[2] = {PageRow{d_img, h, w, ds, 0, ResizeGeom{}}, PageRow{dsk_pages[0].as<uint8_t>(), h, w, w * 3, 0, ResizeGeom{}}};
-  TTR_HIP_CHECK(hipMemcpy2DAsync(d_img, (size_t)ds, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  const PageRow rows[2] = {PageRow{pg.data, h, w, pg.stride, 0, ResizeGeom{}}, PageRow{dsk_pages[0].as<uint8_t>(), h, w, w * 3, 0, ResizeGeom{}}};
   TTR_HIP_CHECK(hipMemcpyAsync(dsk_table[0].p, rows, sizeof rows, hipMemcpyHostToDevice, stream));
   TTR_HIP_CHECK(hipStreamSynchronize(stream));                        // (rows is on the stack)
   const PageRow* src = dsk_table[0].as<PageRow>();
@@ -293,7 +328,7 @@ void Engine::deskew_stage(const uint8_t* img, int h, int w, int row_stride, int 
   std::vector<uint64_t> sc(nsc);
   TTR_HIP_CHECK(hipMemcpyAsync(&r, dsk_rec.p, sizeof r, hipMemcpyDeviceToHost, stream));
   TTR_HIP_CHECK(hipMemcpyAsync(sc.data(), dsk_scores.p, nsc * 8, hipMemcpyDeviceToHost, stream));
-  if (out) TTR_HIP_CHECK(hipMemcpy2DAsync(out, (size_t)out_stride, dsk_pages[0].p, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost, stream));
+  if (out) TTR_HIP_CHECK(hipMemcpy2DAsync(out, (size_t)w * 3, dsk_pages[0].p, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost, stream));
   TTR_HIP_CHECK(hipStreamSynchronize(stream));
   std::string why;
   if (!deskew_rec_valid(r, max_slope, h, w, dsk_cs_host.data(), &why)) throw std::runtime_error("ttr_deskew_page: the record holds " + why);
@@ -312,19 +347,15 @@ void Engine::detect_enqueue(PageBatch& B) {
   } else {
     check_pages(B.pages);                 // (before anything is enqueued)
   }
-  if (tables_min_len)                     // tables: the rule's coordinates are below 32768 (likewise before anything is enqueued)
-    for (const Page& P : B.pages)
-      if (P.h >= 32768 || P.w >= 32768) throw std::runtime_error("tables: a page side of 32768 px or more: ttr_engine_set_tables(e, 0, 0) first");
-  if (marks_min)                          // selection marks: likewise
-    for (const Page& P : B.pages)
-      if (P.h >= 32768 || P.w >= 32768) throw std::runtime_error("marks: a page side of 32768 px or more: ttr_engine_set_marks(e, 0, 0, 0, 0) first");
+  const int side = std::max(B.extent().h, B.extent().w);   // the longest page side: the tables and marks rules' coordinates are below 32768 (likewise before anything is enqueued)
+  if (tables_min_len && side >= 32768) throw std::runtime_error("tables: a page side of 32768 px or more: ttr_engine_set_tables(e, 0, 0) first");
+  if (marks_min && side >= 32768) throw std::runtime_error("marks: a page side of 32768 px or more: ttr_engine_set_marks(e, 0, 0, 0, 0) first");
   // Deskew (DESIGN.md "Deskew"): every page's skew is estimated and the batch's pages become upright copies in the slot's buffer; everything below and behind
   // reads B.pages as ever.  Off: nothing here runs.
   B.ink_radius = ink_radius; B.ink_drop = ink_drop; B.ink_polarity = ink_polarity;   // local ink: fixed for the batch here (the setter refuses while batches stream)
   B.dsk_M = deskew_M;
   if (B.dsk_M) {
-    for (const Page& P : B.pages)
-      if (P.h >= kDskSideCap || P.w >= kDskSideCap) throw std::runtime_error("deskew: a page side of 8192 px or more: ttr_engine_set_deskew(e, 0, 0, 0) first");
+    if (side >= kDskSideCap) throw std::runtime_error("deskew: a page side of 8192 px or more: ttr_engine_set_deskew(e, 0, 0, 0) first");
     deskew_enqueue(B);
   }
   const Page& P0 = B.pages[0];
@@ -437,9 +468,8 @@ void Engine::craft_heatmap_tiled(const uint8_t* img, int h, int w, int row_strid
   if (W2) *W2 = P.W2;
   if (out && cap < map_floats) throw std::runtime_error("tiled heat map: the buffer holds " + std::to_string(cap) + " floats, the page map has " + std::to_string(map_floats));
   if (canvases_out && canvases_cap < canvas_bytes) throw std::runtime_error("tile canvases: the buffer holds " + std::to_string(canvases_cap) + " bytes, the tiles have " + std::to_string(canvas_bytes));
-  staging_img.ensure((size_t)h * w * 3);
-  TTR_HIP_CHECK(hipMemcpy2DAsync(staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
-  B.pages.assign(1, Page{staging_img.as<uint8_t>(), h, w, w * 3, CanvasGeom{h, w, P.hp, P.wp, 1.f}});
+  const StagedPage pg = stage_page("ttr_craft_heatmap_tiled", img, h, w, row_stride, 0, 0, 0, nullptr, false);   // (checked above, under the reference's text)
+  B.pages.assign(1, Page{pg.data, h, w, pg.stride, CanvasGeom{h, w, P.hp, P.wp, 1.f}});
   canvas.ensure(canvas_bytes);
   upload_tile_table(B, 0);
   launch_resize_pad_pages(tile_table[0].as<PageRow>(), canvas.as<uint8_t>(), P.Hc, P.Wc, 1, T, stream);
@@ -703,39 +733,16 @@ int Engine::stage_batch_lines(const PageBatch& B, int sl) {
 
 void Engine::group_batch_lines(const PageBatch& B, int sl, int max_words) {
   const int N = B.N;
-  const size_t in_b = (size_t)N * 24 + (size_t)(B.n + 1) * 4, side_b = ((size_t)2 * N + B.n) * 4;   // the side block: [N] line | [N] word | [pages] n_lines
+  const size_t in_b = (size_t)N * 24 + (size_t)(B.n + 1) * 4, side_b = lines_side_bytes(N, B.n);
   lines_in.ensure(in_b);
-  h_lines[sl].ensure(side_b); lines_side.ensure(side_b);
+  h_lines.arm(sl, side_b); lines_side.ensure(side_b);
   TTR_HIP_CHECK(hipMemcpyAsync(lines_in.p, h_lines_in[sl].p, in_b, hipMemcpyHostToDevice, stream));
   launch_line_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, B.n, N, max_words, lines_side.as<int>(), stream);
-  TTR_HIP_CHECK(hipMemcpyAsync(h_lines[sl].p, lines_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  h_lines.fetch(sl, lines_side, stream);
 }
 
 void Engine::group_lines(const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines) {
-  if (pages <= 0) return;
-  if (first[0] != 0) throw std::runtime_error("ttr_group_lines: first[0] must be 0");
-  int max_words = 0;
-  for (int pg = 0; pg < pages; ++pg) {
-    if (first[pg + 1] < first[pg]) throw std::runtime_error("ttr_group_lines: first must not decrease");
-    max_words = std::max(max_words, first[pg + 1] - first[pg]);
-  }
-  if (max_words > kLinesMaxWords) throw std::runtime_error("ttr_group_lines: more than " + std::to_string(kLinesMaxWords) + " words on a page");
-  const int N = first[pages];
-  const size_t cuv_b = (size_t)N * 24, in_b = cuv_b + (size_t)(pages + 1) * 4, side_b = ((size_t)2 * N + pages) * 4;
-  h_lines_in[0].ensure(in_b); lines_in.ensure(in_b);
-  h_lines[0].ensure(side_b); lines_side.ensure(side_b);
-  int32_t* cuv = h_lines_in[0].as<int32_t>();
-  for (int c = 0; c < N; ++c)
-    if (!lines_cuv(quads + 8 * (size_t)c, cuv + 6 * (size_t)c)) throw std::runtime_error("ttr_group_lines: a coordinate is not finite or has |x| >= 32768");
-  std::copy(first, first + pages + 1, cuv + 6 * (size_t)N);
-  TTR_HIP_CHECK(hipMemcpyAsync(lines_in.p, cuv, in_b, hipMemcpyHostToDevice, stream));
-  launch_line_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, pages, N, max_words, lines_side.as<int>(), stream);
-  TTR_HIP_CHECK(hipMemcpyAsync(h_lines[0].p, lines_side.p, side_b, hipMemcpyDeviceToHost, stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(stream));
-  const int32_t* side = h_lines[0].as<int32_t>();
-  if (line && N) std::copy(side, side + N, line);
-  if (word && N) std::copy(side + N, side + 2 * (size_t)N, word);
-  if (n_lines) std::copy(side + 2 * (size_t)N, side + 2 * (size_t)N + pages, n_lines);
+  group_blocks(quads, first, pages, line, word, n_lines, nullptr, nullptr, nullptr, nullptr, false);
 }
 
 static size_t blocks_side_bytes(int N, int pages) { return ((size_t)2 * N + (size_t)2 * pages) * 4; }   // [N] block | [N] pos | [pages] n_blocks | [pages] mode
@@ -743,37 +750,38 @@ static size_t blocks_side_bytes(int N, int pages) { return ((size_t)2 * N + (siz
 void Engine::group_batch_blocks(const PageBatch& B, int sl, int max_words) {
   const int N = B.N;
   const size_t side_b = blocks_side_bytes(N, B.n);
-  blocks_side.ensure(side_b); h_blocks[sl].ensure(side_b);
+  blocks_side.ensure(side_b); h_blocks.arm(sl, side_b);
   launch_block_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, lines_side.as<int>(), B.n, N, max_words, blocks_side.as<int>(), stream);
-  TTR_HIP_CHECK(hipMemcpyAsync(h_blocks[sl].p, blocks_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  h_blocks.fetch(sl, blocks_side, stream);
 }
 
 void Engine::group_blocks(const float* quads, const int32_t* first, int pages, int32_t* line, int32_t* word, int32_t* n_lines, int32_t* block, int32_t* pos,
-                          int32_t* n_blocks, int32_t* mode) {
+                          int32_t* n_blocks, int32_t* mode, bool blocks) {
   if (pages <= 0) return;
-  if (first[0] != 0) throw std::runtime_error("ttr_group_blocks: first[0] must be 0");
+  const std::string what = blocks ? "ttr_group_blocks" : "ttr_group_lines";
+  if (first[0] != 0) throw std::runtime_error(what + ": first[0] must be 0");
   int max_words = 0;
   for (int pg = 0; pg < pages; ++pg) {
-    if (first[pg + 1] < first[pg]) throw std::runtime_error("ttr_group_blocks: first must not decrease");
+    if (first[pg + 1] < first[pg]) throw std::runtime_error(what + ": first must not decrease");
     max_words = std::max(max_words, first[pg + 1] - first[pg]);
   }
-  if (max_words > kLinesMaxWords) throw std::runtime_error("ttr_group_blocks: more than " + std::to_string(kLinesMaxWords) + " words on a page");
+  if (max_words > kLinesMaxWords) throw std::runtime_error(what + ": more than " + std::to_string(kLinesMaxWords) + " words on a page");
   const int N = first[pages];
-  const size_t in_b = (size_t)N * 24 + (size_t)(pages + 1) * 4, lside_b = ((size_t)2 * N + pages) * 4, side_b = blocks_side_bytes(N, pages);
+  const size_t in_b = (size_t)N * 24 + (size_t)(pages + 1) * 4, lside_b = lines_side_bytes(N, pages), side_b = blocks_side_bytes(N, pages);
   h_lines_in[0].ensure(in_b); lines_in.ensure(in_b);
-  h_lines[0].ensure(lside_b); lines_side.ensure(lside_b);
-  h_blocks[0].ensure(side_b); blocks_side.ensure(side_b);
+  h_lines.arm(0, lside_b); lines_side.ensure(lside_b);
+  if (blocks) { h_blocks.arm(0, side_b); blocks_side.ensure(side_b); }
   int32_t* cuv = h_lines_in[0].as<int32_t>();
   for (int c = 0; c < N; ++c)
-    if (!lines_cuv(quads + 8 * (size_t)c, cuv + 6 * (size_t)c)) throw std::runtime_error("ttr_group_blocks: a coordinate is not finite or has |x| >= 32768");
+    if (!lines_cuv(quads + 8 * (size_t)c, cuv + 6 * (size_t)c)) throw std::runtime_error(what + ": a coordinate is not finite or has |x| >= 32768");
   std::copy(first, first + pages + 1, cuv + 6 * (size_t)N);
   TTR_HIP_CHECK(hipMemcpyAsync(lines_in.p, cuv, in_b, hipMemcpyHostToDevice, stream));
   launch_line_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, pages, N, max_words, lines_side.as<int>(), stream);
-  launch_block_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, lines_side.as<int>(), pages, N, max_words, blocks_side.as<int>(), stream);
-  TTR_HIP_CHECK(hipMemcpyAsync(h_lines[0].p, lines_side.p, lside_b, hipMemcpyDeviceToHost, stream));
-  TTR_HIP_CHECK(hipMemcpyAsync(h_blocks[0].p, blocks_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  if (blocks) launch_block_group(lines_in.as<int>(), lines_in.as<int>() + 6 * (size_t)N, lines_side.as<int>(), pages, N, max_words, blocks_side.as<int>(), stream);
+  h_lines.fetch(0, lines_side, stream);
+  if (blocks) h_blocks.fetch(0, blocks_side, stream);
   TTR_HIP_CHECK(hipStreamSynchronize(stream));
-  const int32_t *ls = h_lines[0].as<int32_t>(), *bs = h_blocks[0].as<int32_t>();
+  const int32_t *ls = h_lines.view<int32_t>(0), *bs = blocks ? h_blocks.view<int32_t>(0) : nullptr;
   if (line && N) std::copy(ls, ls + N, line);
   if (word && N) std::copy(ls + N, ls + 2 * (size_t)N, word);
   if (n_lines) std::copy(ls + 2 * (size_t)N, ls + 2 * (size_t)N + pages, n_lines);
@@ -822,13 +830,13 @@ void Engine::cut_batch_chars(const PageBatch& B, int sl, const int* ids, const i
   const int N = B.N, KT = orient_k() > 1 ? 4 : 1;
   if (!chars_ev[sl & 1][0] || chars_map[sl & 1].cap < (size_t)B.n * B.H2 * B.W2 * 4) throw std::runtime_error("character boxes: the batch's region planes were not kept");
   const size_t in_b = chars_in_bytes(N, KT), side_b = char_side_bytes(N);
-  chars_in.ensure(in_b); chars_side.ensure(side_b); h_chars[sl].ensure(side_b);
+  chars_in.ensure(in_b); chars_side.ensure(side_b); h_chars.arm(sl, side_b);
   TTR_HIP_CHECK(hipMemcpyAsync(chars_in.p, h_chars_in[sl].p, in_b, hipMemcpyHostToDevice, stream));
   TTR_HIP_CHECK(hipStreamWaitEvent(stream, chars_ev[sl & 1][0], 0));
   launch_char_cut(chars_map[sl & 1].as<float>(), B.H2, B.W2, chars_in.as<int64_t>(), KT, reinterpret_cast<const int*>(chars_in.as<int64_t>() + (size_t)N * KT * 6), turns, ids,
                   nullptr, (int)(cfg.low_text * 255.f), N, chars_side.as<int>(), stream);
   TTR_HIP_CHECK(hipEventRecord(chars_ev[sl & 1][1], stream));
-  TTR_HIP_CHECK(hipMemcpyAsync(h_chars[sl].p, chars_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  h_chars.fetch(sl, chars_side, stream);
 }
 
 void Engine::char_cuts(const float* tnorm, int H2, int W2, float ratio, float low_text, const float* quads, const int32_t* turns, const int32_t* nchars, int n,
@@ -838,7 +846,7 @@ void Engine::char_cuts(const float* tnorm, int H2, int W2, float ratio, float lo
   const double k = chars_scale(ratio);
   // chars_in: coef int64 [n][4][6] | page_of int32 [n] (all 0) | turns int32 [n] | nchars int32 [n]
   const size_t coef_b = (size_t)n * 192, in_b = coef_b + (size_t)n * 12, side_b = char_side_bytes(n), map_b = (size_t)H2 * W2 * 4;
-  h_chars_in[0].ensure(in_b); chars_in.ensure(in_b); chars_side.ensure(side_b); h_chars[0].ensure(side_b); chars_map[0].ensure(map_b);
+  h_chars_in[0].ensure(in_b); chars_in.ensure(in_b); chars_side.ensure(side_b); h_chars.arm(0, side_b); chars_map[0].ensure(map_b);
   int64_t* coef = h_chars_in[0].as<int64_t>();
   int32_t* tail = reinterpret_cast<int32_t*>(coef + (size_t)n * 24);
   for (int c = 0; c < n; ++c) {
@@ -852,9 +860,9 @@ void Engine::char_cuts(const float* tnorm, int H2, int W2, float ratio, float lo
   TTR_HIP_CHECK(hipMemcpyAsync(chars_in.p, coef, in_b, hipMemcpyHostToDevice, stream));
   const int* d_tail = reinterpret_cast<const int*>(chars_in.as<int64_t>() + (size_t)n * 24);
   launch_char_cut(chars_map[0].as<float>(), H2, W2, chars_in.as<int64_t>(), 4, d_tail, d_tail + n, nullptr, d_tail + 2 * (size_t)n, (int)(low_text * 255.f), n, chars_side.as<int>(), stream);
-  TTR_HIP_CHECK(hipMemcpyAsync(h_chars[0].p, chars_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  h_chars.fetch(0, chars_side, stream);
   TTR_HIP_CHECK(hipStreamSynchronize(stream));
-  const int32_t* side = h_chars[0].as<int32_t>();
+  const int32_t* side = h_chars.view<int32_t>(0);
   if (cuts) std::copy(side, side + (size_t)n * 27, cuts);
   if (modes) std::copy(side + (size_t)n * 27, side + (size_t)n * 28, modes);
   if (profiles) memcpy(profiles, side + (size_t)n * 28, (size_t)n * 128);
@@ -867,8 +875,8 @@ void Engine::wide_cuts(const uint8_t* img, int h, int w, int row_stride, const f
   if ((size_t)h * w > ((size_t)1 << 28)) throw std::runtime_error("ttr_wide_cuts: bad image size");
   // coef_dev: coef int64 [nq][16][8] | words [nq]: word i owns rows 16 i .. 16 i + 15 (its row, then its extra rows)
   const int rows = nq * kWideMaxPieces;
-  const size_t coef_b = (size_t)rows * 64, words_b = (size_t)nq * sizeof(WideWord), side_b = wide_side_bytes(nq), img_b = (size_t)h * w * 3;
-  h_coef[0].ensure(coef_b + words_b); coef_dev.ensure(coef_b + words_b); wide_side.ensure(side_b); staging_img.ensure(img_b);
+  const size_t coef_b = (size_t)rows * 64, words_b = (size_t)nq * sizeof(WideWord), side_b = wide_side_bytes(nq);
+  h_coef[0].ensure(coef_b + words_b); coef_dev.ensure(coef_b + words_b); wide_side.ensure(side_b);
   std::vector<uint8_t> side(side_b);
   memset(h_coef[0].p, 0, coef_b);
   WideWord* words = reinterpret_cast<WideWord*>(h_coef[0].as<uint8_t>() + coef_b);
@@ -880,22 +888,17 @@ void Engine::wide_cuts(const uint8_t* img, int h, int w, int row_stride, const f
     words[i] = W;
     if (n_out) n_out[i] = W.n;
   }
-  TTR_HIP_CHECK(hipMemcpy2DAsync(staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  const StagedPage pg = stage_page("ttr_wide_cuts", img, h, w, row_stride);
   TTR_HIP_CHECK(hipMemcpyAsync(coef_dev.p, h_coef[0].p, coef_b + words_b, hipMemcpyHostToDevice, stream));
-  const PageRow* table = nullptr;
-  if (use_table) {
-    std::vector<Page> pages(1, Page{staging_img.as<uint8_t>(), h, w, w * 3, CanvasGeom{h, w, h, w, 1.f}});
-    upload_page_table(pages, 0);
-    table = page_table[0].as<PageRow>();
-  }
-  launch_wide_cut(reinterpret_cast<const WideWord*>(coef_dev.as<uint8_t>() + coef_b), nq, staging_img.as<uint8_t>(), 0, w * 3, h, w, table, coef_dev.as<int64_t>(), rows,
+  const PageRow* table = use_table ? staged_page_table(pg, h, w) : nullptr;
+  launch_wide_cut(reinterpret_cast<const WideWord*>(coef_dev.as<uint8_t>() + coef_b), nq, pg.data, 0, pg.stride, h, w, table, coef_dev.as<int64_t>(), rows,
                   wide_side.as<int>(), stream);
   if (use_table) TTR_HIP_CHECK(hipEventRecord(table_ev[0], stream));
   TTR_HIP_CHECK(hipMemcpyAsync(side.data(), wide_side.p, side_b, hipMemcpyDeviceToHost, stream));
   if (coef) TTR_HIP_CHECK(hipMemcpyAsync(coef, coef_dev.p, coef_b, hipMemcpyDeviceToHost, stream));
   TTR_HIP_CHECK(hipStreamSynchronize(stream));
-  if (cuts) memcpy(cuts, side.data(), (size_t)nq * 17 * 4);
-  if (profiles) memcpy(profiles, side.data() + (size_t)nq * 17 * 4, (size_t)nq * 2048 * 2);
+  if (cuts) memcpy(cuts, side.data(), wide_cuts_bytes(nq));
+  if (profiles) memcpy(profiles, side.data() + wide_cuts_bytes(nq), (size_t)nq * 2048 * 2);
 }
 
 void Engine::curve_crops(const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, bool use_table, int32_t* flag, int32_t* hb, int32_t* spine,
@@ -903,9 +906,9 @@ void Engine::curve_crops(const uint8_t* img, int h, int w, int row_stride, const
   if (nq <= 0) return;
   if ((size_t)h * w > ((size_t)1 << 28)) throw std::runtime_error("ttr_curve_crops: bad image size");
   // coef_dev: coef int64 [nq][8] | words [nq]; rects_dev: [nq][5] (kind 1 reads the coefficients alone; the rectangle only has to be non-empty)
-  const size_t coef_b = (size_t)nq * 64, words_b = (size_t)nq * sizeof(CurveIn), side_b = curve_side_bytes(nq), img_b = (size_t)h * w * 3, crop_b = (size_t)nq * kCropBytes;
+  const size_t coef_b = (size_t)nq * 64, words_b = (size_t)nq * sizeof(CurveIn), side_b = curve_side_bytes(nq), crop_b = (size_t)nq * kCropBytes;
   h_coef[0].ensure(coef_b + words_b); coef_dev.ensure(coef_b + words_b); h_rects[0].ensure((size_t)nq * 20); rects_dev.ensure((size_t)nq * 20);
-  curve_side.ensure(side_b); staging_img.ensure(img_b); crops.ensure(crop_b);
+  curve_side.ensure(side_b); crops.ensure(crop_b);
   std::vector<uint8_t> side(side_b);
   int64_t* coef = h_coef[0].as<int64_t>();
   CurveIn* words = reinterpret_cast<CurveIn*>(h_coef[0].as<uint8_t>() + coef_b);
@@ -924,18 +927,13 @@ void Engine::curve_crops(const uint8_t* img, int h, int w, int row_stride, const
     const int rc[5] = {0, 0, 1, 1, 0};
     memcpy(rects + 5 * (size_t)i, rc, sizeof rc);
   }
-  TTR_HIP_CHECK(hipMemcpy2DAsync(staging_img.p, (size_t)w * 3, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
+  const StagedPage pg = stage_page("ttr_curve_crops", img, h, w, row_stride);
   TTR_HIP_CHECK(hipMemcpyAsync(coef_dev.p, h_coef[0].p, coef_b + words_b, hipMemcpyHostToDevice, stream));
   TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[0].p, (size_t)nq * 20, hipMemcpyHostToDevice, stream));
-  const PageRow* table = nullptr;
-  if (use_table) {
-    std::vector<Page> pages(1, Page{staging_img.as<uint8_t>(), h, w, w * 3, CanvasGeom{h, w, h, w, 1.f}});
-    upload_page_table(pages, 0);
-    table = page_table[0].as<PageRow>();
-  }
+  const PageRow* table = use_table ? staged_page_table(pg, h, w) : nullptr;
   if (table) launch_pack_crops_rect_pages(table, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), nq, stream);
-  else launch_pack_crops_rect(staging_img.as<uint8_t>(), 0, w * 3, h, w, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), nq, stream);
-  launch_curve_crop(reinterpret_cast<const CurveIn*>(coef_dev.as<uint8_t>() + coef_b), nq, staging_img.as<uint8_t>(), 0, w * 3, h, w, table, crops.as<uint8_t>(), nq,
+  else launch_pack_crops_rect(pg.data, 0, pg.stride, h, w, rects_dev.as<int>(), coef_dev.as<int64_t>(), crops.as<uint8_t>(), nq, stream);
+  launch_curve_crop(reinterpret_cast<const CurveIn*>(coef_dev.as<uint8_t>() + coef_b), nq, pg.data, 0, pg.stride, h, w, table, crops.as<uint8_t>(), nq,
                     curve_side.as<int>(), stream);
   if (use_table) TTR_HIP_CHECK(hipEventRecord(table_ev[0], stream));
   TTR_HIP_CHECK(hipMemcpyAsync(side.data(), curve_side.p, side_b, hipMemcpyDeviceToHost, stream));
@@ -950,13 +948,12 @@ void Engine::curve_crops(const uint8_t* img, int h, int w, int row_stride, const
 void Engine::page_ink_enqueue(const PageBatch& B, int sl, int ink) {
   const int n = B.n;
   ++page_ink_passes;
-  int Hcap = 0, Wcap = 0;
-  for (const Page& P : B.pages) { Hcap = std::max(Hcap, P.h); Wcap = std::max(Wcap, P.w); }
+  const auto [Hcap, Wcap] = B.extent();
   tab_bits.ensure(tables_bits_slot(Hcap, Wcap) * 8 * n); tab_bitsT.ensure(tables_bitsT_slot(Hcap, Wcap) * 8 * n);
   const Page& P0 = B.pages[0];
   const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
   if (B.ink_radius) {   // local ink (DESIGN.md "Local ink"): the same bitmaps under the adaptive rule, and the pages' records beside the side blocks
-    tab_ink_h.ensure(ink_ws_bytes(Hcap, Wcap, n)); tab_ink_rec.ensure((size_t)n * sizeof(InkRec)); h_tab_ink[sl].ensure((size_t)n * sizeof(InkRec));
+    tab_ink_h.ensure(ink_ws_bytes(Hcap, Wcap, n)); tab_ink_rec.ensure(ink_recs_bytes(n)); h_tab_ink.arm(sl, ink_recs_bytes(n));
     launch_ink_local(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, table, n, Hcap, Wcap, B.ink_radius, B.ink_drop, B.ink_polarity, tab_ink_h.as<uint32_t>(),
                      tab_ink_rec.as<InkRec>(), tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
   } else
@@ -965,12 +962,11 @@ void Engine::page_ink_enqueue(const PageBatch& B, int sl, int ink) {
 
 void Engine::tables_enqueue(const PageBatch& B, int sl) {
   const int n = B.n, N = B.N;
-  int Hcap = 0, Wcap = 0;
-  for (const Page& P : B.pages) { Hcap = std::max(Hcap, P.h); Wcap = std::max(Wcap, P.w); }
+  const auto [Hcap, Wcap] = B.extent();
   // (detect_enqueue refused a page side of 32768 or more before anything of the batch was enqueued)
   tab_runs.ensure((size_t)n * 2 * kTabRunCap * 3 * 4);
-  const size_t side_b = ((size_t)n * kTabSideInts + (size_t)N * 2) * 4;
-  tab_side.ensure(side_b); h_tab[sl].ensure(side_b);
+  const size_t side_b = tables_side_bytes(n, N);
+  tab_side.ensure(side_b); h_tab.arm(sl, side_b);
   const Page& P0 = B.pages[0];
   const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
   const int* centres = rects_dev.as<int>() + B.rects.size();
@@ -982,24 +978,14 @@ void Engine::tables_enqueue(const PageBatch& B, int sl) {
 
 void Engine::tables_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_len, int ink, const float* quads, int nq,
                           int32_t* side_out, int32_t* items_out, uint64_t* bits_out, int32_t* runs_out) {
-  if (h >= 32768 || w >= 32768) throw std::runtime_error("ttr_tables_page: a page side of 32768 px or more");
-  if (!tables_args_ok(min_len, ink)) throw std::runtime_error("ttr_tables_page: min_len must lie in 16..4096 and ink in 1..255");
-  const int ds = dev_stride ? dev_stride : w * 3;
-  if (dev_offset < 0 || ds < w * 3) throw std::runtime_error("ttr_tables_page: bad device offset or stride");
-  const size_t img_b = (size_t)dev_offset + (size_t)ds * h, in_ints = (size_t)nq * 2 + 2, side_b = ((size_t)kTabSideInts + (size_t)nq * 2) * 4;
-  staging_img.ensure(img_b); rects_dev.ensure(in_ints * 4); h_rects[0].ensure(in_ints * 4);
+  // (the image check is stage_page's: both routes here - ttr_tables_page and the developer hook - have made it under their own names before.  The page's copy
+  // is enqueued before stage_centres looks at the quads; no quad can fail there: ttr_tables_page has checked them and the hook passes none - likewise in marks_stage)
+  const StagedPage pg = stage_page("ttr_tables_page", img, h, w, row_stride, dev_offset, dev_stride, 32768, tables_args_ok(min_len, ink) ? nullptr : "min_len must lie in 16..4096 and ink in 1..255");
+  stage_centres("ttr_tables_page", quads, nq);
+  const size_t side_b = tables_side_bytes(1, nq);
   tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8); tab_runs.ensure((size_t)2 * kTabRunCap * 3 * 4); tab_side.ensure(side_b);
-  int32_t* in = h_rects[0].as<int32_t>();
-  for (int i = 0; i < nq; ++i) {
-    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error("ttr_tables_page: quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
-    tables_word_centre(quads + 8 * (size_t)i, in + 2 * (size_t)i);
-  }
-  in[2 * (size_t)nq] = 0; in[2 * (size_t)nq + 1] = nq;
-  uint8_t* d_img = staging_img.as<uint8_t>() + dev_offset;
-  TTR_HIP_CHECK(hipMemcpy2DAsync(d_img, (size_t)ds, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
-  TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, in, in_ints * 4, hipMemcpyHostToDevice, stream));
   TTR_HIP_CHECK(hipMemsetAsync(tab_runs.p, 0, (size_t)2 * kTabRunCap * 3 * 4, stream));   // (the hook returns whole lists)
-  launch_table_ink(d_img, 0, ds, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  launch_table_ink(pg.data, 0, pg.stride, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
   launch_table_grid(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), h, w, nullptr, 1, h, w, min_len, rects_dev.as<int>(), rects_dev.as<int>() + (size_t)nq * 2, tab_runs.as<int>(),
                     tab_side.as<int>(), tab_side.as<int>() + kTabSideInts, stream);
   std::vector<int32_t> side(side_b / 4);
@@ -1015,12 +1001,11 @@ void Engine::tables_stage(const uint8_t* img, int h, int w, int row_stride, int 
 
 void Engine::marks_enqueue(const PageBatch& B, int sl) {
   const int n = B.n, N = B.N;
-  int Hcap = 0, Wcap = 0;
-  for (const Page& P : B.pages) { Hcap = std::max(Hcap, P.h); Wcap = std::max(Wcap, P.w); }
+  const auto [Hcap, Wcap] = B.extent();
   // (detect_enqueue refused a page side of 32768 or more before anything of the batch was enqueued)
   mark_cand.ensure(marks_cand_ints(Hcap, n) * 4); mark_counts.ensure(marks_count_ints(Hcap, n) * 4);
-  const size_t side_b = ((size_t)n * kMarkSideInts + (size_t)N) * 4;
-  mark_side.ensure(side_b); h_mark[sl].ensure(side_b);
+  const size_t side_b = marks_side_bytes(n, N);
+  mark_side.ensure(side_b); h_mark.arm(sl, side_b);
   const Page& P0 = B.pages[0];
   const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
   const int* centres = rects_dev.as<int>() + B.rects.size();
@@ -1041,26 +1026,13 @@ void Engine::marks_enqueue(const PageBatch& B, int sl) {
 
 void Engine::marks_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_side, int max_side, int fill, int ink, const float* quads,
                          int nq, int32_t* side_out, int32_t* item_mark_out, int32_t* counts_out) {
-  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("ttr_marks_page: bad image size");
-  if (h >= 32768 || w >= 32768) throw std::runtime_error("ttr_marks_page: a page side of 32768 px or more");
-  if (!marks_args_ok(min_side, max_side, fill, ink)) throw std::runtime_error("ttr_marks_page: min_side must lie in 8..64, max_side in min_side..128, fill and ink in 1..255");
-  const int ds = dev_stride ? dev_stride : w * 3;
-  if (dev_offset < 0 || ds < w * 3) throw std::runtime_error("ttr_marks_page: bad device offset or stride");
-  const size_t img_b = (size_t)dev_offset + (size_t)ds * h, in_ints = (size_t)nq * 2 + 2, side_b = ((size_t)kMarkSideInts + (size_t)nq) * 4;
-  const size_t cnt_b = marks_count_ints(h, 1) * 4;
-  staging_img.ensure(img_b); rects_dev.ensure(in_ints * 4); h_rects[0].ensure(in_ints * 4);
+  const StagedPage pg = stage_page("ttr_marks_page", img, h, w, row_stride, dev_offset, dev_stride, 32768,
+                                   marks_args_ok(min_side, max_side, fill, ink) ? nullptr : "min_side must lie in 8..64, max_side in min_side..128, fill and ink in 1..255");
+  stage_centres("ttr_marks_page", quads, nq);
+  const size_t side_b = marks_side_bytes(1, nq), cnt_b = marks_count_ints(h, 1) * 4;
   tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8);
   mark_cand.ensure(marks_cand_ints(h, 1) * 4); mark_counts.ensure(cnt_b); mark_side.ensure(side_b);
-  int32_t* in = h_rects[0].as<int32_t>();
-  for (int i = 0; i < nq; ++i) {
-    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error("ttr_marks_page: quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
-    tables_word_centre(quads + 8 * (size_t)i, in + 2 * (size_t)i);
-  }
-  in[2 * (size_t)nq] = 0; in[2 * (size_t)nq + 1] = nq;
-  uint8_t* d_img = staging_img.as<uint8_t>() + dev_offset;
-  TTR_HIP_CHECK(hipMemcpy2DAsync(d_img, (size_t)ds, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
-  TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, in, in_ints * 4, hipMemcpyHostToDevice, stream));
-  launch_table_ink(d_img, 0, ds, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  launch_table_ink(pg.data, 0, pg.stride, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
   launch_mark_cand(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), h, w, nullptr, 1, h, w, min_side, max_side, fill, mark_cand.as<int>(), mark_counts.as<int>(), stream);
   launch_mark_page(mark_cand.as<int>(), mark_counts.as<int>(), 1, h, rects_dev.as<int>(), rects_dev.as<int>() + (size_t)nq * 2, mark_side.as<int>(),
                    mark_side.as<int>() + kMarkSideInts, stream);
@@ -1081,17 +1053,11 @@ void Engine::marks_stage(const uint8_t* img, int h, int w, int row_stride, int d
 
 void Engine::ink_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int radius, int drop, int polarity, uint64_t* bits_out,
                        uint64_t* bitsT_out, InkRec* rec) {
-  if (!img || h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error("ttr_ink_page: bad image size");
-  if (h >= 32768 || w >= 32768) throw std::runtime_error("ttr_ink_page: a page side of 32768 px or more");
-  if (!ink_args_ok(radius, drop, polarity)) throw std::runtime_error("ttr_ink_page: radius must lie in 1..64, drop in 1..255 and polarity in 0..2");
-  const int ds = dev_stride ? dev_stride : w * 3;
-  if (dev_offset < 0 || ds < w * 3) throw std::runtime_error("ttr_ink_page: bad device offset or stride");
-  const size_t img_b = (size_t)dev_offset + (size_t)ds * h;
-  staging_img.ensure(img_b); tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8);
-  tab_ink_h.ensure(ink_ws_bytes(h, w, 1)); tab_ink_rec.ensure(sizeof(InkRec));
-  uint8_t* d_img = staging_img.as<uint8_t>() + dev_offset;
-  TTR_HIP_CHECK(hipMemcpy2DAsync(d_img, (size_t)ds, img, row_stride ? row_stride : w * 3, (size_t)w * 3, h, hipMemcpyHostToDevice, stream));
-  launch_ink_local(d_img, 0, ds, h, w, nullptr, 1, h, w, radius, drop, polarity, tab_ink_h.as<uint32_t>(), tab_ink_rec.as<InkRec>(), tab_bits.as<uint64_t>(),
+  const StagedPage pg = stage_page("ttr_ink_page", img, h, w, row_stride, dev_offset, dev_stride, 32768,
+                                   ink_args_ok(radius, drop, polarity) ? nullptr : "radius must lie in 1..64, drop in 1..255 and polarity in 0..2");
+  tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8);
+  tab_ink_h.ensure(ink_ws_bytes(h, w, 1)); tab_ink_rec.ensure(ink_recs_bytes(1));
+  launch_ink_local(pg.data, 0, pg.stride, h, w, nullptr, 1, h, w, radius, drop, polarity, tab_ink_h.as<uint32_t>(), tab_ink_rec.as<InkRec>(), tab_bits.as<uint64_t>(),
                    tab_bitsT.as<uint64_t>(), stream);
   InkRec r{};
   TTR_HIP_CHECK(hipMemcpyAsync(&r, tab_ink_rec.p, sizeof r, hipMemcpyDeviceToHost, stream));
@@ -1105,6 +1071,8 @@ void Engine::ink_stage(const uint8_t* img, int h, int w, int row_stride, int dev
 
 void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
+  // the slot's side-block records: disarmed, then armed by each layer that runs for this batch (engine.h: SideCopy)
+  for (SideCopy* c : {&h_orient, &h_lines, &h_blocks, &h_chars, &h_alts, &h_lex, &h_pat_logp, &h_wide, &h_curve, &h_tab, &h_tab_ink, &h_mark}) c->disarm(sl);
   const int line_words = cfg.lines && N > 0 ? stage_batch_lines(B, sl) : 0;   // text lines: the host part, before anything of this batch is enqueued
   if (cfg.chars && N > 0) stage_batch_chars(B, sl);                          // character boxes: likewise
   B.alts = orient_k() > 1 ? 0 : alts;        // character alternatives: fixed for the batch here (the setter refuses while batches stream)
@@ -1122,19 +1090,18 @@ void Engine::recog_enqueue(PageBatch& B) {
     const int K = orient_k(), T = (K - 1) * N;                 // word orientation: T twin crops behind the batch's N (DESIGN.md "Word orientation")
     crops.ensure((size_t)(N + T + X) * kCropBytes);
     logits.ensure((size_t)std::max(std::max(N, X), T) * kLogitWords * 4);
-    if (X) h_wide[sl].ensure(B.wide.size() * 17 * 4);
-    if (!B.curve.empty()) h_curve[sl].ensure(curve_side_bytes(N));
+    if (X) h_wide.arm(sl, wide_cuts_bytes((int)B.wide.size()));
+    if (!B.curve.empty()) h_curve.arm(sl, curve_side_bytes(N));
     const RecOut cand = T ? rec_block(orient_cand, T) : RecOut{};
-    const size_t side_b = ((size_t)N * (K + 1) + B.n) * 4;   // [N] turn | [N][K] candidate conf | [pages] page turn
-    if (T) { orient_side.ensure(side_b); h_orient[sl].ensure(side_b); }
+    if (T) { orient_side.ensure(orient_side_bytes(N, K, B.n)); h_orient.arm(sl, orient_side_bytes(N, K, B.n)); }
     RecPass main;   // the batch's N rows: the scratch logits, the standard block, the engine's own set
     main.crops = crops.as<uint8_t>(); main.N = N; main.logits = logits.as<float>(); main.out = out; main.mask = charset;
     // character alternatives: the side block of this batch (the setter refuses an engine with orientation, so T is 0 here)
-    if (B.alts) { main.alt = alts_out(N, B.alts); h_alts[sl].ensure(alts_side_bytes(N, B.alts)); }
+    if (B.alts) { main.alt = alts_out(N, B.alts); h_alts.arm(sl, alts_side_bytes(N, B.alts)); }
     // lexicon matching: the side block and the scorer's partials of this batch
-    if (B.lex_m) { main.lex = lex_out(N, B.lex_m, B.lex_band, lex_gap); h_lex[sl].ensure(lex_side_bytes(N, B.lex_m, B.lex_band)); }
+    if (B.lex_m) { main.lex = lex_out(N, B.lex_m, B.lex_band, lex_gap); h_lex.arm(sl, lex_side_bytes(N, B.lex_m, B.lex_band)); }
     // patterns in best mode: the scratch block of the masked argmax and the side block of this batch
-    if (B.pat_best) { main.best = pat_best_out(N); h_pat_logp[sl].ensure((size_t)N * 4); }
+    if (B.pat_best) { main.best = pat_best_out(N); h_pat_logp.arm(sl, pat_logp_bytes(N)); }
     pack_batch_crops(B, sl);
     if (T) pack_twin_crops(B, sl);
     if (cfg.lines) group_batch_lines(B, sl, line_words);               // text lines: from the boxes alone, so inside the packing stage (DESIGN.md "Text lines")
@@ -1169,24 +1136,16 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (cfg.chars) cut_batch_chars(B, sl, out.ids, T ? orient_side.as<int>() : nullptr);   // character boxes: K and the turn are the chosen reading's, read on the device
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
     TTR_HIP_CHECK(hipMemcpyAsync(h_ids[sl].p, ids_dev.p, block, hipMemcpyDeviceToHost, stream));   // ids, prob and conf in one copy
-    if (T) TTR_HIP_CHECK(hipMemcpyAsync(h_orient[sl].p, orient_side.p, side_b, hipMemcpyDeviceToHost, stream));
-    if (B.alts) TTR_HIP_CHECK(hipMemcpyAsync(h_alts[sl].p, alts_side.p, alts_side_bytes(N, B.alts), hipMemcpyDeviceToHost, stream));   // the alternatives' side block, behind the standard block's copy
-    if (B.lex_m) TTR_HIP_CHECK(hipMemcpyAsync(h_lex[sl].p, lex_side.p, lex_side_bytes(N, B.lex_m, B.lex_band), hipMemcpyDeviceToHost, stream));   // the lexicon matches' side block, likewise
-    if (B.pat_best) TTR_HIP_CHECK(hipMemcpyAsync(h_pat_logp[sl].p, pat_logp_dev.p, (size_t)N * 4, hipMemcpyDeviceToHost, stream));   // best mode's log-probabilities, likewise
-    if (X) TTR_HIP_CHECK(hipMemcpyAsync(h_wide[sl].p, wide_side.p, B.wide.size() * 17 * 4, hipMemcpyDeviceToHost, stream));   // the wide words' cuts (the profile stays on the device)
-    if (!B.curve.empty()) TTR_HIP_CHECK(hipMemcpyAsync(h_curve[sl].p, curve_side.p, curve_side_bytes(N), hipMemcpyDeviceToHost, stream));   // the curved words' side block
-    if (B.tab_min_len) TTR_HIP_CHECK(hipMemcpyAsync(h_tab[sl].p, tab_side.p, ((size_t)B.n * kTabSideInts + (size_t)N * 2) * 4, hipMemcpyDeviceToHost, stream));   // the tables' side blocks and the words' cells
-    if ((B.tab_min_len || B.mark_min) && B.ink_radius) TTR_HIP_CHECK(hipMemcpyAsync(h_tab_ink[sl].p, tab_ink_rec.p, (size_t)B.n * sizeof(InkRec), hipMemcpyDeviceToHost, stream));   // ... and their ink records
-    if (B.mark_min) TTR_HIP_CHECK(hipMemcpyAsync(h_mark[sl].p, mark_side.p, ((size_t)B.n * kMarkSideInts + (size_t)N) * 4, hipMemcpyDeviceToHost, stream));   // the marks' side blocks and the items' marks
   } else {
     if (B.mark_min && !B.regions) marks_enqueue(B, sl);                // selection marks: a batch of pages without words - boxes only - is a legitimate form
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
-    if (B.mark_min && !B.regions) {
-      if (B.ink_radius) TTR_HIP_CHECK(hipMemcpyAsync(h_tab_ink[sl].p, tab_ink_rec.p, (size_t)B.n * sizeof(InkRec), hipMemcpyDeviceToHost, stream));
-      TTR_HIP_CHECK(hipMemcpyAsync(h_mark[sl].p, mark_side.p, (size_t)B.n * kMarkSideInts * 4, hipMemcpyDeviceToHost, stream));
-    }
   }
+  // the side blocks that are not copied inside their layer's own enqueue function, behind the standard block's copy: each a no-op unless its layer armed it
+  // (h_wide: the cuts, the profile stays on the device; h_tab_ink: the tables / marks pass's ink records; h_mark: there for a batch without words too)
+  const std::pair<SideCopy*, const DevBuf*> tail[] = {{&h_orient, &orient_side}, {&h_alts, &alts_side}, {&h_lex, &lex_side}, {&h_pat_logp, &pat_logp_dev}, {&h_wide, &wide_side},
+                                                      {&h_curve, &curve_side}, {&h_tab, &tab_side}, {&h_tab_ink, &tab_ink_rec}, {&h_mark, &mark_side}};
+  for (const auto& t : tail) t.first->fetch(sl, *t.second, stream);
   if (comm && B.cap > 0) {   // the payload: the output block of cap rows per rank - [cap][26] ids | [cap][26] prob | [cap] conf -, straight from the recogniser's device buffer
     gath_dev[sl].ensure(block * comm->world);
     h_gath[sl].ensure(block * comm->world);
@@ -1199,7 +1158,7 @@ void Engine::recog_enqueue(PageBatch& B) {
 }
 
 void Engine::finish(PageBatch& B, std::vector<Result>& results) {
-  const int n = B.n, N = B.N;
+  const int n = B.n;
   results.assign(n, Result());
   const double th2 = now_us();
   spin_event(done_ev[B.slot]);
@@ -1215,274 +1174,278 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
     last_gathered.world = L.world; last_gathered.pages = n; last_gathered.counts = B.all_counts;
     compact_gathered(h_gath[B.slot].as<int32_t>(), B.cap, L.total, last_gathered);
   }
-  const int32_t* side = orient_k() > 1 && N > 0 ? h_orient[B.slot].as<int32_t>() : nullptr;
-  const int32_t* lines_block = cfg.lines && N > 0 ? h_lines[B.slot].as<int32_t>() : nullptr;   // the side block (lines.hip)
-  const void* chars_block = cfg.chars && N > 0 ? h_chars[B.slot].p : nullptr;                   // the side block (chars.hip)
-  const int32_t* blocks_block = cfg.blocks && N > 0 ? h_blocks[B.slot].as<int32_t>() : nullptr;   // the side block (blocks.hip)
-  const void* alts_block = B.alts && N > 0 ? h_alts[B.slot].p : nullptr;                        // the side block (decode_alts.hip)
-  const void* lex_block = B.lex_m && N > 0 ? h_lex[B.slot].p : nullptr;                         // the side block (lexicon.hip)
-  const int32_t* wide_block = B.X && N > 0 ? h_wide[B.slot].as<int32_t>() : nullptr;            // the cuts of the side block (wide.hip)
-  const float* pat_logp_block = B.pat_best && N > 0 ? h_pat_logp[B.slot].as<float>() : nullptr;  // the side block (pattern.hip, best mode)
-  const void* curve_block = !B.curve.empty() && N > 0 ? h_curve[B.slot].p : nullptr;           // the side block (curve.hip)
-  const int32_t* tab_block = B.tab_min_len && N > 0 ? h_tab[B.slot].as<int32_t>() : nullptr;    // the side blocks (tables.hip)
-  const int32_t* mark_block = B.mark_min && !B.regions ? h_mark[B.slot].as<int32_t>() : nullptr;   // the side blocks (marks.hip): there for a batch without words too
-  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), side, lines_block, chars_block, blocks_block, results, alts_block, lex_block, wide_block, pat_logp_block, curve_block,
-               tab_block, mark_block);
+  SideViews V;   // null where the layer did not run for this batch
+  V.orient = h_orient.view<int32_t>(B.slot); V.lines = h_lines.view<int32_t>(B.slot); V.blocks = h_blocks.view<int32_t>(B.slot); V.chars = h_chars.view<int32_t>(B.slot);
+  V.alts = h_alts.view<int32_t>(B.slot); V.lex = h_lex.view<int32_t>(B.slot); V.pat_logp = h_pat_logp.view<float>(B.slot); V.wide_cuts = h_wide.view<int32_t>(B.slot);
+  V.curve = h_curve.view<int32_t>(B.slot); V.tab = h_tab.view<int32_t>(B.slot); V.tab_ink = h_tab_ink.view<InkRec>(B.slot); V.mark = h_mark.view<int32_t>(B.slot);
+  decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), V, results);
   for (Result& r : results) r.tiles = B.tiles;                                                  // tiled pages: the tiles each page's detector ran as (0: off)
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
   B.live = false; B.enqueued = false;
 }
 
-void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const int32_t* side, const int32_t* lines_side, const void* chars_side, const int32_t* blocks_side,
-                          std::vector<Result>& results, const void* alts_side, const void* lex_side, const int32_t* wide_cuts, const float* pat_logp, const void* curve_block,
-                          const int32_t* tab_block, const int32_t* mark_block) {
-  const int n = B.n, N = B.N, K = orient_k();
-  const std::vector<int> first = page_first(B.page_of, n);
-  // side: [N] chosen turn | [N][K] candidate conf | [pages] page turn
-  const float* o_conf = side ? reinterpret_cast<const float*>(side + N) : nullptr;
-  const int32_t* o_page = side ? side + (size_t)N * (K + 1) : nullptr;
-  auto decode_page = [&](int pg) {
-    Result& r = results[pg];
-    const int c0 = first[pg], cnt = first[pg + 1] - c0;
-    r.text.reserve(cnt); r.bbox.reserve((size_t)cnt * 4); r.quad.reserve((size_t)cnt * 8);
-    r.ids.assign(&rows.ids[(size_t)c0 * 26], &rows.ids[(size_t)(c0 + cnt) * 26]);
-    r.prob.assign(&rows.prob[(size_t)c0 * 26], &rows.prob[(size_t)(c0 + cnt) * 26]);
-    r.conf.assign(&rows.conf[c0], &rows.conf[c0 + cnt]);
-    r.alt_k = B.alts;
-    if (alts_side && cnt > 0) {   // [N][26][K] ids | [N][26][K] prob -> the page's rows
-      const size_t w = (size_t)26 * B.alts;
-      const int32_t* ai = static_cast<const int32_t*>(alts_side);
-      const float* ap = reinterpret_cast<const float*>(ai + (size_t)N * w);
-      r.alt_ids.assign(ai + (size_t)c0 * w, ai + (size_t)(c0 + cnt) * w);
-      r.alt_prob.assign(ap + (size_t)c0 * w, ap + (size_t)(c0 + cnt) * w);
+void Engine::decode_words(const PageCtx& at, Result& r) const {
+  const auto& [B, rows, V, pg, c0, cnt] = at; const int N = B.N, K = orient_k();
+  r.text.reserve(cnt); r.bbox.reserve((size_t)cnt * 4); r.quad.reserve((size_t)cnt * 8);
+  r.ids.assign(&rows.ids[(size_t)c0 * 26], &rows.ids[(size_t)(c0 + cnt) * 26]);
+  r.prob.assign(&rows.prob[(size_t)c0 * 26], &rows.prob[(size_t)(c0 + cnt) * 26]);
+  r.conf.assign(&rows.conf[c0], &rows.conf[c0 + cnt]);
+  r.alt_k = B.alts;
+  if (V.alts && cnt > 0) {   // [N][26][K] ids | [N][26][K] prob -> the page's rows
+    const size_t w = (size_t)26 * B.alts;
+    const int32_t* ai = V.alts;
+    const float* ap = reinterpret_cast<const float*>(ai + (size_t)N * w);
+    r.alt_ids.assign(ai + (size_t)c0 * w, ai + (size_t)(c0 + cnt) * w);
+    r.alt_prob.assign(ap + (size_t)c0 * w, ap + (size_t)(c0 + cnt) * w);
+  }
+  r.lex_m = B.lex_m; r.lex_band = B.lex_band;
+  if (V.lex && cnt > 0) {   // [N][M] idx | [N][M] logp -> the page's rows
+    const size_t w = (size_t)B.lex_m;
+    const int32_t* li = V.lex;
+    const float* ll = reinterpret_cast<const float*>(li + (size_t)N * w);
+    r.lex_idx.assign(li + (size_t)c0 * w, li + (size_t)(c0 + cnt) * w);
+    r.lex_logp.assign(ll + (size_t)c0 * w, ll + (size_t)(c0 + cnt) * w);
+    if (B.lex_band >= 0) {     // fuzzy alignment: [N][M] edits behind the two blocks
+      const int32_t* le = li + (size_t)N * w * 2;
+      r.lex_edits.assign(le + (size_t)c0 * w, le + (size_t)(c0 + cnt) * w);
     }
-    r.lex_m = B.lex_m; r.lex_band = B.lex_band;
-    if (lex_side && cnt > 0) {   // [N][M] idx | [N][M] logp -> the page's rows
-      const size_t w = (size_t)B.lex_m;
-      const int32_t* li = static_cast<const int32_t*>(lex_side);
-      const float* ll = reinterpret_cast<const float*>(li + (size_t)N * w);
-      r.lex_idx.assign(li + (size_t)c0 * w, li + (size_t)(c0 + cnt) * w);
-      r.lex_logp.assign(ll + (size_t)c0 * w, ll + (size_t)(c0 + cnt) * w);
-      if (B.lex_band >= 0) {     // fuzzy alignment: [N][M] edits behind the two blocks
-        const int32_t* le = li + (size_t)N * w * 2;
-        r.lex_edits.assign(le + (size_t)c0 * w, le + (size_t)(c0 + cnt) * w);
-      }
+  }
+  if (V.pat_logp && cnt > 0) r.pattern_logp.assign(V.pat_logp + c0, V.pat_logp + c0 + cnt);
+  if (K > 1) {
+    r.orient_k = K;
+    if (const int32_t* side = V.orient) {   // [N] chosen turn | [N][K] candidate conf | [pages] page turn
+      const float* o_conf = reinterpret_cast<const float*>(side + N);
+      const int32_t* o_page = side + (size_t)N * (K + 1);
+      r.orient.assign(&side[c0], &side[c0 + cnt]);
+      r.orient_conf.assign(&o_conf[(size_t)c0 * K], &o_conf[(size_t)(c0 + cnt) * K]);
+      r.page_orient = o_page[pg];
     }
-    if (pat_logp && cnt > 0) r.pattern_logp.assign(pat_logp + c0, pat_logp + c0 + cnt);
-    if (K > 1) {
-      r.orient_k = K;
-      if (side) {
-        r.orient.assign(&side[c0], &side[c0 + cnt]);
-        r.orient_conf.assign(&o_conf[(size_t)c0 * K], &o_conf[(size_t)(c0 + cnt) * K]);
-        r.page_orient = o_page[pg];
-      }
+  }
+  if (B.regions) {   // the caller's quads verbatim, their corners' extremes, their set indices
+    r.quad.assign(&B.region_quad[(size_t)c0 * 8], &B.region_quad[(size_t)(c0 + cnt) * 8]);
+    r.set.assign(&B.region_set[c0], &B.region_set[c0 + cnt]);
+  }
+  for (int k = 0; k < cnt; ++k) {
+    r.text.push_back(tok.decode(&rows.ids[(size_t)(c0 + k) * 26], 26));   // :486-505
+    float bb[4];
+    if (B.regions) region_bbox(&r.quad[(size_t)k * 8], bb);
+    else { tesseract_bbox(B.boxes[pg][k], bb); push_quad(B.boxes[pg][k], r.quad); }   // :511
+    r.bbox.insert(r.bbox.end(), bb, bb + 4);
+  }
+}
+
+void Engine::decode_records(const PageCtx& at, Result& r) const {
+  const auto& [B, rows, V, pg, c0, cnt] = at; const int n = B.n, N = B.N;
+  if (B.dsk_M) {   // deskew: the page's record, checked before anything is built on it
+    if (B.dsk_recs.size() != (size_t)n) throw std::runtime_error("deskew: the batch carries no records");
+    const DeskewRec& d = B.dsk_recs[(size_t)pg];
+    std::string why;
+    if (!deskew_rec_valid(d, B.dsk_M, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, dsk_cs_host.data(), &why))
+      throw std::runtime_error("deskew: the record of page " + std::to_string(pg) + " holds " + why);
+    r.skew_on = 1; r.skew = d;
+  } else if (deskew_M && B.regions) {   // a region call: the caller's quadrilaterals are in the caller's frame
+    r.skew_on = 1; r.skew = DeskewRec{0, 0, 65536, 0, B.pages[(size_t)pg].w, B.pages[(size_t)pg].h, 0, 0, 0, 0};
+  }
+  if (B.ink_radius && !B.regions && ((B.tab_min_len && N > 0) || B.mark_min || B.dsk_M)) {   // local ink: the page's record - the tables or marks pass's when one ran, else the deskew pass's - checked before anything is built on it
+    const bool from_tab = (B.tab_min_len && N > 0) || B.mark_min;
+    if (from_tab ? !V.tab_ink : B.dsk_ink_recs.size() != (size_t)n) throw std::runtime_error("local ink: the batch carries no records");
+    const InkRec k = from_tab ? V.tab_ink[pg] : B.dsk_ink_recs[(size_t)pg];
+    std::string why;
+    if (!ink_rec_valid(k, B.ink_radius, B.ink_drop, B.ink_polarity, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, &why))
+      throw std::runtime_error("local ink: the record of page " + std::to_string(pg) + " holds " + why);
+    if (from_tab && B.dsk_M) {   // both passes ran: the deskew pass's record is checked as well (its page is the caller's, of the same size)
+      if (B.dsk_ink_recs.size() != (size_t)n) throw std::runtime_error("local ink: the batch carries no records");
+      if (!ink_rec_valid(B.dsk_ink_recs[(size_t)pg], B.ink_radius, B.ink_drop, B.ink_polarity, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, &why))
+        throw std::runtime_error("local ink: the deskew pass's record of page " + std::to_string(pg) + " holds " + why);
     }
-    if (B.regions) {   // the caller's quads verbatim, their corners' extremes, their set indices
-      r.quad.assign(&B.region_quad[(size_t)c0 * 8], &B.region_quad[(size_t)(c0 + cnt) * 8]);
-      r.set.assign(&B.region_set[c0], &B.region_set[c0 + cnt]);
-      for (int k = 0; k < cnt; ++k) {
-        r.text.push_back(tok.decode(&rows.ids[(size_t)(c0 + k) * 26], 26));
-        float bb[4];
-        region_bbox(&r.quad[(size_t)k * 8], bb);
-        r.bbox.insert(r.bbox.end(), bb, bb + 4);
-      }
-    } else
+    r.ink_on = 1; r.ink = k;
+  }
+}
+
+void Engine::decode_tables(const PageCtx& at, Result& r) const {
+  const auto& [B, rows, V, pg, c0, cnt] = at; const int n = B.n;
+  if (B.tab_min_len && !B.regions && cnt > 0) {   // tables: the page's side block and its words' cells, checked before anything is built on them
+    if (!V.tab) throw std::runtime_error("tables: the batch carries no side block");
+    const int32_t* ts = V.tab + (size_t)pg * kTabSideInts;
+    const int32_t* ti = V.tab + (size_t)n * kTabSideInts + 2 * (size_t)c0;
+    std::string why;
+    if (!tables_side_valid(ts, &why)) throw std::runtime_error("tables: the side block of page " + std::to_string(pg) + " holds " + why);
+    int32_t counts[4];
+    tables_export(ts, counts, nullptr, nullptr, nullptr, nullptr);
+    r.table_mode = ts[0];
+    r.rulings.assign((size_t)counts[0] * 6, 0); r.tables.assign((size_t)counts[1] * 8, 0); r.cells.assign((size_t)counts[2] * 9, 0); r.table_lines.assign((size_t)counts[3], 0);
+    tables_export(ts, counts, r.rulings.data(), r.tables.data(), r.table_lines.data(), r.cells.data());
+    r.item_table.assign((size_t)cnt, -1); r.item_cell.assign((size_t)cnt, -1);
     for (int k = 0; k < cnt; ++k) {
-      r.text.push_back(tok.decode(&rows.ids[(size_t)(c0 + k) * 26], 26));   // :486-505
-      float bb[4];
-      tesseract_bbox(B.boxes[pg][k], bb);                                    // :511
-      r.bbox.insert(r.bbox.end(), bb, bb + 4);
-      push_quad(B.boxes[pg][k], r.quad);
+      const int t = ti[2 * k], c = ti[2 * k + 1];
+      const bool none = t == -1 && c == -1;
+      if (!none && (t < 0 || t >= counts[1] || c < r.tables[(size_t)t * 8 + 6] || c >= r.tables[(size_t)t * 8 + 6] + r.tables[(size_t)t * 8 + 7]))
+        throw std::runtime_error("tables: word " + std::to_string(k) + " of page " + std::to_string(pg) + " names a table or cell that does not exist");
+      r.item_table[(size_t)k] = t; r.item_cell[(size_t)k] = c;
     }
-    if (B.dsk_M) {   // deskew: the page's record, checked before anything is built on it
-      if (B.dsk_recs.size() != (size_t)n) throw std::runtime_error("deskew: the batch carries no records");
-      const DeskewRec& d = B.dsk_recs[(size_t)pg];
-      std::string why;
-      if (!deskew_rec_valid(d, B.dsk_M, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, dsk_cs_host.data(), &why))
-        throw std::runtime_error("deskew: the record of page " + std::to_string(pg) + " holds " + why);
-      r.skew_on = 1; r.skew = d;
-    } else if (deskew_M && B.regions) {   // a region call: the caller's quadrilaterals are in the caller's frame
-      r.skew_on = 1; r.skew = DeskewRec{0, 0, 65536, 0, B.pages[(size_t)pg].w, B.pages[(size_t)pg].h, 0, 0, 0, 0};
+  }
+}
+
+void Engine::decode_marks(const PageCtx& at, Result& r) const {
+  const auto& [B, rows, V, pg, c0, cnt] = at; const int n = B.n;
+  if (B.mark_min && !B.regions) {   // selection marks: the page's side block and its items' marks, checked before anything is built on them
+    if (!V.mark) throw std::runtime_error("marks: the batch carries no side block");
+    const int32_t* ms = V.mark + (size_t)pg * kMarkSideInts;
+    const int32_t* mi = V.mark + (size_t)n * kMarkSideInts + (size_t)c0;
+    std::string why;
+    if (!marks_side_valid(ms, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, B.mark_fill, cnt, &why))
+      throw std::runtime_error("marks: the side block of page " + std::to_string(pg) + " holds " + why);
+    r.mark_mode = ms[0];
+    r.marks.assign(ms + kMarkHdr, ms + kMarkHdr + (size_t)kMarkRec * ms[1]);
+    r.item_mark.assign((size_t)cnt, -1);
+    for (int k = 0; k < cnt; ++k) {
+      if (mi[k] < -1 || mi[k] >= ms[1]) throw std::runtime_error("marks: word " + std::to_string(k) + " of page " + std::to_string(pg) + " names a mark that does not exist");
+      r.item_mark[(size_t)k] = mi[k];
     }
-    if (B.ink_radius && !B.regions && ((B.tab_min_len && N > 0) || B.mark_min || B.dsk_M)) {   // local ink: the page's record - the tables or marks pass's when one ran, else the deskew pass's - checked before anything is built on it
-      const bool from_tab = (B.tab_min_len && N > 0) || B.mark_min;
-      if (!from_tab && B.dsk_ink_recs.size() != (size_t)n) throw std::runtime_error("local ink: the batch carries no records");
-      const InkRec k = from_tab ? h_tab_ink[B.slot].as<InkRec>()[pg] : B.dsk_ink_recs[(size_t)pg];
-      std::string why;
-      if (!ink_rec_valid(k, B.ink_radius, B.ink_drop, B.ink_polarity, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, &why))
-        throw std::runtime_error("local ink: the record of page " + std::to_string(pg) + " holds " + why);
-      if (from_tab && B.dsk_M) {   // both passes ran: the deskew pass's record is checked as well (its page is the caller's, of the same size)
-        if (B.dsk_ink_recs.size() != (size_t)n) throw std::runtime_error("local ink: the batch carries no records");
-        if (!ink_rec_valid(B.dsk_ink_recs[(size_t)pg], B.ink_radius, B.ink_drop, B.ink_polarity, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, &why))
-          throw std::runtime_error("local ink: the deskew pass's record of page " + std::to_string(pg) + " holds " + why);
-      }
-      r.ink_on = 1; r.ink = k;
+  }
+}
+
+void Engine::decode_curved(const PageCtx& at, Result& r) const {
+  const auto& [B, rows, V, pg, c0, cnt] = at; const int N = B.N;
+  if (B.curved && cnt > 0) {   // curved words: every item's flag, outline and knot table, checked before anything is built on them
+    if (!V.curve) throw std::runtime_error("curved words: the batch carries no side block");
+    const int32_t* cs = V.curve;
+    const int64_t* ct = reinterpret_cast<const int64_t*>(reinterpret_cast<const uint8_t*>(V.curve) + curve_side_table_offset(N));
+    r.curved.assign((size_t)cnt, 0); r.outline.assign((size_t)cnt * 36, 0.f); r.spine_knots.assign((size_t)cnt * 36, 0);
+    for (int k = 0; k < cnt; ++k) {
+      const size_t c = (size_t)(c0 + k);
+      CurveWord w{};
+      w.flag = cs[c]; w.hb[0] = cs[(size_t)N + 2 * c]; w.hb[1] = cs[(size_t)N + 2 * c + 1];
+      memcpy(w.table, ct + 36 * c, sizeof w.table);
+      if (!curve_word_valid(w))
+        throw std::runtime_error("curved words: the side block of word " + std::to_string(k) + " of page " + std::to_string(pg) +
+                                 " holds a flag that is not 0 or 1, a half band outside 0..32 or a knot outside the int32 pixel range");
+      r.curved[(size_t)k] = w.flag;
+      memcpy(&r.spine_knots[(size_t)k * 36], w.table, sizeof w.table);
+      curve_outline(&r.quad[(size_t)k * 8], w.flag, &w.table[0][0], &r.outline[(size_t)k * 36]);
     }
-    if (B.tab_min_len && !B.regions && cnt > 0) {   // tables: the page's side block and its words' cells, checked before anything is built on them
-      if (!tab_block) throw std::runtime_error("tables: the batch carries no side block");
-      const int32_t* ts = tab_block + (size_t)pg * kTabSideInts;
-      const int32_t* ti = tab_block + (size_t)n * kTabSideInts + 2 * (size_t)c0;
-      std::string why;
-      if (!tables_side_valid(ts, &why)) throw std::runtime_error("tables: the side block of page " + std::to_string(pg) + " holds " + why);
-      int32_t counts[4];
-      tables_export(ts, counts, nullptr, nullptr, nullptr, nullptr);
-      r.table_mode = ts[0];
-      r.rulings.assign((size_t)counts[0] * 6, 0); r.tables.assign((size_t)counts[1] * 8, 0); r.cells.assign((size_t)counts[2] * 9, 0); r.table_lines.assign((size_t)counts[3], 0);
-      tables_export(ts, counts, r.rulings.data(), r.tables.data(), r.table_lines.data(), r.cells.data());
-      r.item_table.assign((size_t)cnt, -1); r.item_cell.assign((size_t)cnt, -1);
-      for (int k = 0; k < cnt; ++k) {
-        const int t = ti[2 * k], c = ti[2 * k + 1];
-        const bool none = t == -1 && c == -1;
-        if (!none && (t < 0 || t >= counts[1] || c < r.tables[(size_t)t * 8 + 6] || c >= r.tables[(size_t)t * 8 + 6] + r.tables[(size_t)t * 8 + 7]))
-          throw std::runtime_error("tables: word " + std::to_string(k) + " of page " + std::to_string(pg) + " names a table or cell that does not exist");
-        r.item_table[(size_t)k] = t; r.item_cell[(size_t)k] = c;
-      }
+  }
+}
+
+void Engine::decode_wide(const PageCtx& at, Result& r) const {
+  const auto& [B, rows, V, pg, c0, cnt] = at;
+  if (B.wide_aspect != 0.f && cnt > 0) {   // wide words: every item's pieces; a wide item's text and conf joined from them (its ids and prob stay its first piece's)
+    r.piece_first.assign((size_t)cnt + 1, 0);
+    r.piece_cuts.assign((size_t)cnt * 17, -1);
+    for (int k = 0; k < cnt; ++k) {
+      const int wi = B.wide_of[(size_t)(c0 + k)];
+      r.piece_first[(size_t)k + 1] = r.piece_first[k] + (wi < 0 ? 1 : B.wide[(size_t)wi].n);
     }
-    if (B.mark_min && !B.regions) {   // selection marks: the page's side block and its items' marks, checked before anything is built on them
-      if (!mark_block) throw std::runtime_error("marks: the batch carries no side block");
-      const int32_t* ms = mark_block + (size_t)pg * kMarkSideInts;
-      const int32_t* mi = mark_block + (size_t)n * kMarkSideInts + (size_t)c0;
-      std::string why;
-      if (!marks_side_valid(ms, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, B.mark_fill, cnt, &why))
-        throw std::runtime_error("marks: the side block of page " + std::to_string(pg) + " holds " + why);
-      r.mark_mode = ms[0];
-      r.marks.assign(ms + kMarkHdr, ms + kMarkHdr + (size_t)kMarkRec * ms[1]);
-      r.item_mark.assign((size_t)cnt, -1);
-      for (int k = 0; k < cnt; ++k) {
-        if (mi[k] < -1 || mi[k] >= ms[1]) throw std::runtime_error("marks: word " + std::to_string(k) + " of page " + std::to_string(pg) + " names a mark that does not exist");
-        r.item_mark[(size_t)k] = mi[k];
+    const size_t P = (size_t)r.piece_first[cnt];
+    r.piece_ids.reserve(P * 26); r.piece_prob.reserve(P * 26); r.piece_conf.reserve(P); r.piece_quad.assign(P * 8, 0.f);
+    for (int k = 0; k < cnt; ++k) {
+      const int c = c0 + k, wi = B.wide_of[(size_t)c];
+      int32_t* cuts = &r.piece_cuts[(size_t)k * 17];
+      float* pq = &r.piece_quad[8 * (size_t)r.piece_first[k]];
+      if (wi < 0) {
+        cuts[0] = 0; cuts[1] = kWideCols;
+        r.piece_ids.insert(r.piece_ids.end(), &rows.ids[(size_t)c * 26], &rows.ids[(size_t)(c + 1) * 26]);
+        r.piece_prob.insert(r.piece_prob.end(), &rows.prob[(size_t)c * 26], &rows.prob[(size_t)(c + 1) * 26]);
+        r.piece_conf.push_back(rows.conf[c]);
+        std::copy(&r.quad[(size_t)k * 8], &r.quad[(size_t)k * 8 + 8], pq);
+        continue;
       }
+      const WideWord& W = B.wide[(size_t)wi];
+      if (!V.wide_cuts || !wide_cuts_valid(V.wide_cuts + 17 * (size_t)wi, W.n))
+        throw std::runtime_error("wide words: the side block of word " + std::to_string(k) + " of page " + std::to_string(pg) + " does not hold " + std::to_string(W.n) +
+                                 " ascending pieces of 64 to 192 columns");
+      std::copy(V.wide_cuts + 17 * (size_t)wi, V.wide_cuts + 17 * (size_t)wi + 17, cuts);
+      wide_piece_quads(&r.quad[(size_t)k * 8], cuts, W.n, pq);
+      std::string text;
+      float conf = 1.0f;
+      for (int j = 0; j < W.n; ++j) {
+        const size_t row = j == 0 ? (size_t)c : (size_t)W.extra + (size_t)j - 1;
+        r.piece_ids.insert(r.piece_ids.end(), &rows.ids[row * 26], &rows.ids[(row + 1) * 26]);
+        r.piece_prob.insert(r.piece_prob.end(), &rows.prob[row * 26], &rows.prob[(row + 1) * 26]);
+        r.piece_conf.push_back(rows.conf[row]);
+        text += tok.decode(&rows.ids[row * 26], 26);
+        conf = conf * rows.conf[row];
+      }
+      r.text[(size_t)k] = text;
+      r.conf[(size_t)k] = conf;
     }
-    if (B.curved && cnt > 0) {   // curved words: every item's flag, outline and knot table, checked before anything is built on them
-      if (!curve_block) throw std::runtime_error("curved words: the batch carries no side block");
-      const int32_t* cs = static_cast<const int32_t*>(curve_block);
-      const int64_t* ct = reinterpret_cast<const int64_t*>(static_cast<const uint8_t*>(curve_block) + curve_side_table_offset(N));
-      r.curved.assign((size_t)cnt, 0); r.outline.assign((size_t)cnt * 36, 0.f); r.spine_knots.assign((size_t)cnt * 36, 0);
-      for (int k = 0; k < cnt; ++k) {
-        const size_t c = (size_t)(c0 + k);
-        CurveWord w{};
-        w.flag = cs[c]; w.hb[0] = cs[(size_t)N + 2 * c]; w.hb[1] = cs[(size_t)N + 2 * c + 1];
-        memcpy(w.table, ct + 36 * c, sizeof w.table);
-        if (!curve_word_valid(w))
-          throw std::runtime_error("curved words: the side block of word " + std::to_string(k) + " of page " + std::to_string(pg) +
-                                   " holds a flag that is not 0 or 1, a half band outside 0..32 or a knot outside the int32 pixel range");
-        r.curved[(size_t)k] = w.flag;
-        memcpy(&r.spine_knots[(size_t)k * 36], w.table, sizeof w.table);
-        curve_outline(&r.quad[(size_t)k * 8], w.flag, &w.table[0][0], &r.outline[(size_t)k * 36]);
-      }
+  }
+}
+
+void Engine::decode_lines(const PageCtx& at, Result& r) const {
+  const auto& [B, rows, V, pg, c0, cnt] = at; const int N = B.N;
+  if (V.lines && cnt > 0) {   // [N] line | [N] word | [pages] n_lines -> the page's lines in reading order
+    r.line.assign(&V.lines[c0], &V.lines[c0 + cnt]);
+    r.word.assign(&V.lines[(size_t)N + c0], &V.lines[(size_t)N + c0 + cnt]);
+    r.n_lines = V.lines[2 * (size_t)N + pg];
+    r.order.assign(cnt, 0);
+    r.line_first.assign((size_t)std::max(r.n_lines, 0) + 1, 0);
+    if (!lines_reading_order(r.line.data(), r.word.data(), cnt, r.n_lines, r.order.data(), r.line_first.data()))
+      throw std::runtime_error("text lines: the side block of page " + std::to_string(pg) + " is not a numbering of its lines");
+    r.line_bbox.assign((size_t)r.n_lines * 4, 0.f);
+    for (int l = 0; l < r.n_lines; ++l) bbox_union(r.bbox, r.order, r.line_first[l], r.line_first[l + 1], &r.line_bbox[4 * (size_t)l]);
+  }
+}
+
+void Engine::decode_blocks(const PageCtx& at, Result& r) const {
+  const auto& [B, rows, V, pg, c0, cnt] = at; const int n = B.n, N = B.N;
+  if (V.blocks && V.lines && cnt > 0) {   // [N] block | [N] pos | [pages] n_blocks | [pages] mode, per line -> the page's blocks in reading order
+    const int nl = r.n_lines;
+    r.line_block.assign(&V.blocks[c0], &V.blocks[c0 + nl]);
+    r.line_pos.assign(&V.blocks[(size_t)N + c0], &V.blocks[(size_t)N + c0 + nl]);
+    r.n_blocks = V.blocks[2 * (size_t)N + pg];
+    r.block_mode = V.blocks[2 * (size_t)N + n + pg];
+    if (r.n_blocks < 1 || r.n_blocks > nl)   // (checked before anything is sized by it)
+      throw std::runtime_error("text blocks: the side block of page " + std::to_string(pg) + " is not a numbering of its blocks");
+    r.block_order.assign((size_t)nl, 0);
+    r.block_first.assign((size_t)r.n_blocks + 1, 0);
+    if ((r.block_mode != 0 && r.block_mode != 1) ||
+        !blocks_reading_order(r.line_block.data(), r.line_pos.data(), nl, r.n_blocks, r.block_order.data(), r.block_first.data()))
+      throw std::runtime_error("text blocks: the side block of page " + std::to_string(pg) + " is not a numbering of its blocks");
+    r.block.resize((size_t)cnt);
+    for (int k = 0; k < cnt; ++k) r.block[k] = r.line_block[r.line[k]];
+    r.block_bbox.assign((size_t)r.n_blocks * 4, 0.f);
+    for (int b = 0; b < r.n_blocks; ++b) bbox_union(r.line_bbox, r.block_order, r.block_first[b], r.block_first[b + 1], &r.block_bbox[4 * (size_t)b]);
+  }
+}
+
+void Engine::decode_chars(const PageCtx& at, Result& r) const {
+  const auto& [B, rows, V, pg, c0, cnt] = at; const int N = B.N;
+  if (V.chars && cnt > 0) {   // [N][27] cuts | [N] mode | [N][128] u8 profile -> the page's characters
+    const int32_t* cuts = V.chars;
+    const int32_t* modes = cuts + (size_t)N * 27;
+    const uint8_t* prof = reinterpret_cast<const uint8_t*>(cuts + (size_t)N * 28);
+    r.char_cuts.assign(&cuts[(size_t)c0 * 27], &cuts[(size_t)(c0 + cnt) * 27]);
+    r.char_mode.assign(&modes[c0], &modes[c0 + cnt]);
+    r.char_profile.assign(&prof[(size_t)c0 * 128], &prof[(size_t)(c0 + cnt) * 128]);
+    r.char_first.assign((size_t)cnt + 1, 0);
+    for (int k = 0; k < cnt; ++k) {
+      const int K = text_chars(&r.ids[(size_t)k * 26]);
+      if (!chars_cuts_valid(&r.char_cuts[(size_t)k * 27], K) || (r.char_mode[k] != 0 && r.char_mode[k] != 1))
+        throw std::runtime_error("character boxes: the side block of word " + std::to_string(k) + " of page " + std::to_string(pg) + " does not hold " + std::to_string(K) + " ascending cells");
+      r.char_first[(size_t)k + 1] = r.char_first[k] + K;
     }
-    if (B.wide_aspect != 0.f && cnt > 0) {   // wide words: every item's pieces; a wide item's text and conf joined from them (its ids and prob stay its first piece's)
-      r.piece_first.assign((size_t)cnt + 1, 0);
-      r.piece_cuts.assign((size_t)cnt * 17, -1);
-      for (int k = 0; k < cnt; ++k) {
-        const int wi = B.wide_of[(size_t)(c0 + k)];
-        r.piece_first[(size_t)k + 1] = r.piece_first[k] + (wi < 0 ? 1 : B.wide[(size_t)wi].n);
-      }
-      const size_t P = (size_t)r.piece_first[cnt];
-      r.piece_ids.reserve(P * 26); r.piece_prob.reserve(P * 26); r.piece_conf.reserve(P); r.piece_quad.assign(P * 8, 0.f);
-      for (int k = 0; k < cnt; ++k) {
-        const int c = c0 + k, wi = B.wide_of[(size_t)c];
-        int32_t* cuts = &r.piece_cuts[(size_t)k * 17];
-        float* pq = &r.piece_quad[8 * (size_t)r.piece_first[k]];
-        if (wi < 0) {
-          cuts[0] = 0; cuts[1] = kWideCols;
-          r.piece_ids.insert(r.piece_ids.end(), &rows.ids[(size_t)c * 26], &rows.ids[(size_t)(c + 1) * 26]);
-          r.piece_prob.insert(r.piece_prob.end(), &rows.prob[(size_t)c * 26], &rows.prob[(size_t)(c + 1) * 26]);
-          r.piece_conf.push_back(rows.conf[c]);
-          std::copy(&r.quad[(size_t)k * 8], &r.quad[(size_t)k * 8 + 8], pq);
-          continue;
-        }
-        const WideWord& W = B.wide[(size_t)wi];
-        if (!wide_cuts || !wide_cuts_valid(wide_cuts + 17 * (size_t)wi, W.n))
-          throw std::runtime_error("wide words: the side block of word " + std::to_string(k) + " of page " + std::to_string(pg) + " does not hold " + std::to_string(W.n) +
-                                   " ascending pieces of 64 to 192 columns");
-        std::copy(wide_cuts + 17 * (size_t)wi, wide_cuts + 17 * (size_t)wi + 17, cuts);
-        wide_piece_quads(&r.quad[(size_t)k * 8], cuts, W.n, pq);
-        std::string text;
-        float conf = 1.0f;
-        for (int j = 0; j < W.n; ++j) {
-          const size_t row = j == 0 ? (size_t)c : (size_t)W.extra + (size_t)j - 1;
-          r.piece_ids.insert(r.piece_ids.end(), &rows.ids[row * 26], &rows.ids[(row + 1) * 26]);
-          r.piece_prob.insert(r.piece_prob.end(), &rows.prob[row * 26], &rows.prob[(row + 1) * 26]);
-          r.piece_conf.push_back(rows.conf[row]);
-          text += tok.decode(&rows.ids[row * 26], 26);
-          conf = conf * rows.conf[row];
-        }
-        r.text[(size_t)k] = text;
-        r.conf[(size_t)k] = conf;
-      }
+    const size_t total = (size_t)r.char_first[cnt];
+    r.char_quad.assign(total * 8, 0.f); r.char_bbox.assign(total * 4, 0.f);
+    for (int k = 0; k < cnt; ++k) {
+      const int K = r.char_first[(size_t)k + 1] - r.char_first[k];
+      chars_quads_from_cuts(&r.quad[(size_t)k * 8], r.orient.empty() ? 0 : r.orient[k], &r.char_cuts[(size_t)k * 27], K, r.char_quad.data() + 8 * (size_t)r.char_first[k],
+                            r.char_bbox.data() + 4 * (size_t)r.char_first[k]);
     }
-    if (lines_side && cnt > 0) {   // [N] line | [N] word | [pages] n_lines -> the page's lines in reading order
-      r.line.assign(&lines_side[c0], &lines_side[c0 + cnt]);
-      r.word.assign(&lines_side[(size_t)N + c0], &lines_side[(size_t)N + c0 + cnt]);
-      r.n_lines = lines_side[2 * (size_t)N + pg];
-      r.order.assign(cnt, 0);
-      r.line_first.assign((size_t)std::max(r.n_lines, 0) + 1, 0);
-      if (!lines_reading_order(r.line.data(), r.word.data(), cnt, r.n_lines, r.order.data(), r.line_first.data()))
-        throw std::runtime_error("text lines: the side block of page " + std::to_string(pg) + " is not a numbering of its lines");
-      const float inf = std::numeric_limits<float>::infinity();
-      r.line_bbox.assign((size_t)r.n_lines * 4, 0.f);
-      for (int l = 0; l < r.n_lines; ++l) {
-        float* lb = &r.line_bbox[4 * (size_t)l];
-        lb[0] = lb[1] = inf; lb[2] = lb[3] = -inf;
-        for (int k = r.line_first[l]; k < r.line_first[l + 1]; ++k) {
-          const float* bb = &r.bbox[4 * (size_t)r.order[k]];
-          lb[0] = std::min(lb[0], bb[0]); lb[1] = std::min(lb[1], bb[1]); lb[2] = std::max(lb[2], bb[2]); lb[3] = std::max(lb[3], bb[3]);
-        }
-      }
-    }
-    if (blocks_side && lines_side && cnt > 0) {   // [N] block | [N] pos | [pages] n_blocks | [pages] mode, per line -> the page's blocks in reading order
-      const int nl = r.n_lines;
-      r.line_block.assign(&blocks_side[c0], &blocks_side[c0 + nl]);
-      r.line_pos.assign(&blocks_side[(size_t)N + c0], &blocks_side[(size_t)N + c0 + nl]);
-      r.n_blocks = blocks_side[2 * (size_t)N + pg];
-      r.block_mode = blocks_side[2 * (size_t)N + n + pg];
-      if (r.n_blocks < 1 || r.n_blocks > nl)   // (checked before anything is sized by it)
-        throw std::runtime_error("text blocks: the side block of page " + std::to_string(pg) + " is not a numbering of its blocks");
-      r.block_order.assign((size_t)nl, 0);
-      r.block_first.assign((size_t)r.n_blocks + 1, 0);
-      if ((r.block_mode != 0 && r.block_mode != 1) ||
-          !blocks_reading_order(r.line_block.data(), r.line_pos.data(), nl, r.n_blocks, r.block_order.data(), r.block_first.data()))
-        throw std::runtime_error("text blocks: the side block of page " + std::to_string(pg) + " is not a numbering of its blocks");
-      r.block.resize((size_t)cnt);
-      for (int k = 0; k < cnt; ++k) r.block[k] = r.line_block[r.line[k]];
-      const float inf = std::numeric_limits<float>::infinity();
-      r.block_bbox.assign((size_t)r.n_blocks * 4, 0.f);
-      for (int b = 0; b < r.n_blocks; ++b) {
-        float* o = &r.block_bbox[4 * (size_t)b];
-        o[0] = o[1] = inf; o[2] = o[3] = -inf;
-        for (int k = r.block_first[b]; k < r.block_first[b + 1]; ++k) {
-          const float* lb = &r.line_bbox[4 * (size_t)r.block_order[k]];
-          o[0] = std::min(o[0], lb[0]); o[1] = std::min(o[1], lb[1]); o[2] = std::max(o[2], lb[2]); o[3] = std::max(o[3], lb[3]);
-        }
-      }
-    }
-    if (chars_side && cnt > 0) {   // [N][27] cuts | [N] mode | [N][128] u8 profile -> the page's characters
-      const int32_t* cuts = static_cast<const int32_t*>(chars_side);
-      const int32_t* modes = cuts + (size_t)N * 27;
-      const uint8_t* prof = reinterpret_cast<const uint8_t*>(cuts + (size_t)N * 28);
-      r.char_cuts.assign(&cuts[(size_t)c0 * 27], &cuts[(size_t)(c0 + cnt) * 27]);
-      r.char_mode.assign(&modes[c0], &modes[c0 + cnt]);
-      r.char_profile.assign(&prof[(size_t)c0 * 128], &prof[(size_t)(c0 + cnt) * 128]);
-      r.char_first.assign((size_t)cnt + 1, 0);
-      for (int k = 0; k < cnt; ++k) {
-        const int K = text_chars(&r.ids[(size_t)k * 26]);
-        if (!chars_cuts_valid(&r.char_cuts[(size_t)k * 27], K) || (r.char_mode[k] != 0 && r.char_mode[k] != 1))
-          throw std::runtime_error("character boxes: the side block of word " + std::to_string(k) + " of page " + std::to_string(pg) + " does not hold " + std::to_string(K) + " ascending cells");
-        r.char_first[(size_t)k + 1] = r.char_first[k] + K;
-      }
-      const size_t total = (size_t)r.char_first[cnt];
-      r.char_quad.assign(total * 8, 0.f); r.char_bbox.assign(total * 4, 0.f);
-      for (int k = 0; k < cnt; ++k) {
-        const int K = r.char_first[(size_t)k + 1] - r.char_first[k];
-        chars_quads_from_cuts(&r.quad[(size_t)k * 8], r.orient.empty() ? 0 : r.orient[k], &r.char_cuts[(size_t)k * 27], K, r.char_quad.data() + 8 * (size_t)r.char_first[k],
-                              r.char_bbox.data() + 4 * (size_t)r.char_first[k]);
-      }
-    }
+  }
+}
+
+void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const SideViews& views, std::vector<Result>& results) {
+  const std::vector<int> first = page_first(B.page_of, B.n);
+  auto decode_page = [&](int pg) {
+    const PageCtx at{B, rows, views, pg, first[pg], first[pg + 1] - first[pg]};
+    Result& r = results[pg];
+    decode_words(at, r); decode_records(at, r); decode_tables(at, r); decode_marks(at, r); decode_curved(at, r); decode_wide(at, r);
+    decode_lines(at, r); decode_blocks(at, r); decode_chars(at, r);
   };
   // pages decode independently
-  if (N >= 256) parallel_pages(n, decode_page);
-  else for (int pg = 0; pg < n; ++pg) decode_page(pg);
+  if (B.N >= 256) parallel_pages(B.n, decode_page);
+  else for (int pg = 0; pg < B.n; ++pg) decode_page(pg);
 }
 
 Engine::PageBatch Engine::mixed_batch(const ttr_page* pages, int n) {
@@ -1796,7 +1759,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   for (int r = 0; r < world; ++r) total[r] = std::max(0, std::min(per, N - r * per));
   Gathered g;
   compact_gathered(h_gath[0].as<int32_t>(), per, total, g);
-  decode_pages(B, RecRows{g.ids.data(), g.prob.data(), g.conf.data()}, nullptr, nullptr, nullptr, nullptr, results);
+  decode_pages(B, RecRows{g.ids.data(), g.prob.data(), g.conf.data()}, SideViews{}, results);
 }
 
 void Engine::stream_push(const uint8_t* d_pages, int n, int h, int w, std::vector<Result>& prev_results, int& prev_n) {

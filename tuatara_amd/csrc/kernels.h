@@ -359,6 +359,7 @@ struct WideWord { int64_t f[6]; int32_t n, page, row, extra; };
 static_assert(sizeof(WideWord) == 64, "WideWord is one 64-byte entry");
 // the side block of Wn words: [Wn][17] int32 cuts | [Wn][2048] u16 profile
 inline size_t wide_side_bytes(int Wn) { return (size_t)Wn * (17 * 4 + 2048 * 2); }
+inline size_t wide_cuts_bytes(int Wn) { return (size_t)Wn * 17 * 4; }   // ... its cuts: the part a batch brings to the host
 // wide_cut_kernel: profile, cuts and the pieces' packer rows (written into coef8 [rows][8]) of every word; the pages as the rect packers take them - table
 // null: images / page_bytes / stride / h / w of a uniform batch, else the device page table
 void launch_wide_cut(const WideWord* words, int Wn, const uint8_t* images, size_t page_bytes, int stride, int h, int w, const PageRow* table, int64_t* coef8,

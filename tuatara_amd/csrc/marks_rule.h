@@ -28,6 +28,8 @@ constexpr int kMarkLabelSides = 8;                                 // a label st
 //   marks   [512][12]  in (y0, x0) order
 constexpr int kMarkHdr = 8;
 constexpr int kMarkSideInts = kMarkHdr + kMarkCap * kMarkRec;
+// a batch's side blocks: [pages][kMarkSideInts] | [N] every item's mark
+constexpr size_t marks_side_bytes(int pages, int N) { return ((size_t)pages * kMarkSideInts + (size_t)N) * 4; }
 
 TTR_MARK_HD bool marks_args_ok(int min_side, int max_side, int fill, int ink) {
   return min_side >= kMarkMinLo && min_side <= kMarkMinHi && max_side >= min_side && max_side <= kMarkMaxHi && fill >= 1 && fill <= 255 && ink >= 1 && ink <= 255;

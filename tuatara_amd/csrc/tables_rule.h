@@ -30,6 +30,8 @@ constexpr int kTabHdr = 16;
 constexpr int kTabRulings = kTabHdr, kTabTables = kTabRulings + 2 * kTabRulingCap * 6, kTabLines = kTabTables + kTabTableCap * 8;
 constexpr int kTabCells = kTabLines + kTabTableCap * 2 * kTabLineCap, kTabSideInts = kTabCells + kTabCellCap * 9;
 constexpr int kTabScratchInts = 32768;                     // what tables_grid needs beside the block
+// a batch's side blocks: [pages][kTabSideInts] | [N][2] every word's table, cell
+constexpr size_t tables_side_bytes(int pages, int N) { return ((size_t)pages * kTabSideInts + (size_t)N * 2) * 4; }
 
 // 1: ink.  s = the sum of a pixel's three bytes
 TTR_TAB_HD bool tab_ink(int s, int ink) { return s < 3 * ink; }
