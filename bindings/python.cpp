@@ -54,6 +54,9 @@
 // And a keyword-only marks=False on image_to_data: marks=True (min_side 10, max_side 64, fill 24, ink 128) or marks=(min_side, max_side, fill, ink) finds the page's
 // checkboxes and their state (DESIGN.md "Selection marks"); every dict gains "mark" (-1 for an item in no mark), and last_call_marks() returns the marks of the
 // latest call as dicts {"box", "interior", "selected", "fill", "label", "text"}.  It does not combine with regions.
+// And a keyword-only barcodes=False on image_to_data: barcodes=True (min_lines 8, ink 128, symbologies 3) or barcodes=(min_lines, ink, symbologies) reads the
+// page's Code 128 and Code 39 barcodes (DESIGN.md "Barcodes"); every dict gains "barcode" (-1 for an item in no barcode), and last_call_barcodes() returns the
+// barcodes of the latest call as dicts {"box", "symbology", "direction", "text", "data", "lines", "module", "gs1"}.  It does not combine with regions.
 // And a keyword-only tables=False on image_to_data: tables=True (min_len 48, ink 128) or tables=(min_len, ink) finds ruling lines, tables, grids and merged
 // cells in the page's pixels (DESIGN.md "Tables"); every dict gains "table" and "cell" (-1 / -1 for an item in no cell).  It combines with every keyword but
 // regions (ValueError); a value out of range raises RuntimeError before anything runs.
@@ -78,7 +81,7 @@ static py::list quad_pairs(const std::vector<float>& q) {
   return l;
 }
 
-struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false, curved = false, lex_edits = false, tables = false, marks = false; };   // the optional keys of an OutputItemEx's dict
+struct Keys { bool quad = false, conf = false, orient = false, lines = false, chars = false, blocks = false, alts = false, lexicon = false, pieces = false, pattern_logp = false, curved = false, lex_edits = false, tables = false, marks = false, barcodes = false; };   // the optional keys of an OutputItemEx's dict
 
 static py::dict item_dict(const OutputItemEx& item, Keys k) {
   py::dict d;
@@ -97,6 +100,7 @@ static py::dict item_dict(const OutputItemEx& item, Keys k) {
   if (k.blocks) d["block"] = item.block;
   if (k.tables) { d["table"] = item.table; d["cell"] = item.cell; }
   if (k.marks) d["mark"] = item.mark;
+  if (k.barcodes) d["barcode"] = item.barcode;
   if (k.curved) {
     d["curved"] = item.curved;
     py::list pts;
@@ -276,7 +280,22 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
                                       py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved, py::object lexicon_fuzzy, double lexicon_gap,
-                                      py::object tiled_kw, py::object tables_kw, py::object deskew_kw, py::object local_ink_kw, py::object marks_kw) {
+                                      py::object tiled_kw, py::object tables_kw, py::object deskew_kw, py::object local_ink_kw, py::object marks_kw, py::object barcodes_kw) {
+  // barcodes=False | True (8, 128, 3) | (min_lines, ink, symbologies): barcodes for this call (DESIGN.md "Barcodes")
+  struct BarcodesScope {
+    BarcodesScope(int a, int i, int s) { set_barcodes(a, i, s); }
+    ~BarcodesScope() { set_barcodes(0); }
+  };
+  int bc_min = 0, bc_ink = 128, bc_sym = 3;
+  if (py::isinstance<py::bool_>(barcodes_kw)) bc_min = barcodes_kw.cast<bool>() ? 8 : 0;
+  else if (py::isinstance<py::tuple>(barcodes_kw) && py::len(barcodes_kw) == 3) {
+    const py::tuple t = barcodes_kw.cast<py::tuple>();
+    bc_min = t[0].cast<int>(); bc_ink = t[1].cast<int>(); bc_sym = t[2].cast<int>();
+  } else if (!barcodes_kw.is_none()) throw py::type_error("barcodes must be False, True or (min_lines, ink, symbologies)");
+  if (bc_min != 0 && !regions_kw.is_none()) throw std::invalid_argument("barcodes does not combine with regions (the views stay empty)");
+  if (bc_min != 0 && (bc_min < 4 || bc_min > 256 || bc_ink < 1 || bc_ink > 255 || bc_sym < 1 || bc_sym > 3))
+    throw std::runtime_error("barcodes must be False, True or (min_lines, ink, symbologies) with min_lines in 4..256, ink in 1..255 and symbologies in 1..3");
+  BarcodesScope barcodes_scope(bc_min, bc_ink, bc_sym);
   // marks=False | True (10, 64, 24, 128) | (min_side, max_side, fill, ink): selection marks for this call (DESIGN.md "Selection marks")
   struct MarksScope {
     MarksScope(int a, int b, int f, int i) { set_marks(a, b, f, i); }
@@ -377,7 +396,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     Keys keys{true, conf, false, lines, false, blocks};
     keys.curved = true;
     keys.tables = tab_min_len != 0;
-    keys.marks = mk_min != 0;
+    keys.marks = mk_min != 0; keys.barcodes = bc_min != 0;
     for (const auto& item : got) res.append(item_dict(item, keys));
     return res;
   }
@@ -395,7 +414,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
     py::list res;
     Keys wkeys{true, conf, false, lines, false, blocks, false, false, true};
     wkeys.tables = tab_min_len != 0;
-    wkeys.marks = mk_min != 0;
+    wkeys.marks = mk_min != 0; wkeys.barcodes = bc_min != 0;
     for (const auto& item : got) res.append(item_dict(item, wkeys));
     return res;
   }
@@ -456,7 +475,7 @@ static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_st
   Keys keys{rectify, conf, orient != 0, lines, chars, blocks, alts != 0, lex, false, pattern_best};
   keys.lex_edits = band >= 0;
   keys.tables = tab_min_len != 0;
-  keys.marks = mk_min != 0;
+  keys.marks = mk_min != 0; keys.barcodes = bc_min != 0;
   for (const auto& item : items) result.append(item_dict(item, keys));
   return result;
 }
@@ -524,7 +543,7 @@ PYBIND11_MODULE(pytuatara, m) {
   m.doc() = "Tuatara ocr (MI355X-native engine)";
   m.def("image_to_data", &image_to_data_wrapper, py::arg("image"), py::arg("weights_dir"), py::arg("outputs_dir"), py::kw_only(),
         py::arg("rectify") = false, py::arg("conf") = false, py::arg("orient") = py::none(), py::arg("orient_page") = false,
-        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, py::arg("tables") = false, py::arg("deskew") = false, py::arg("local_ink") = false, py::arg("marks") = false, "Extract text and bounding boxes from an image");
+        py::arg("lines") = false, py::arg("chars") = false, py::arg("blocks") = false, py::arg("allowlist") = py::none(), py::arg("blocklist") = py::none(), py::arg("regions") = py::none(), py::arg("alts") = 0, py::arg("lexicon") = py::none(), py::arg("lexicon_m") = 1, py::arg("pattern") = py::none(), py::arg("wide") = false, py::arg("pattern_best") = false, py::arg("curved") = false, py::arg("lexicon_fuzzy") = py::none(), py::arg("lexicon_gap") = -6.9077554, py::arg("tiled") = false, py::arg("tables") = false, py::arg("deskew") = false, py::arg("local_ink") = false, py::arg("marks") = false, py::arg("barcodes") = false, "Extract text and bounding boxes from an image");
   m.def("last_call_marks", []() {
     py::list out;
     for (const SelectionMark& s : last_call_marks()) {
@@ -536,6 +555,18 @@ PYBIND11_MODULE(pytuatara, m) {
     }
     return out;
   }, "The selection marks of this thread's latest image_to_data call (DESIGN.md \"Selection marks\"), [] when marks were off");
+  m.def("last_call_barcodes", []() {
+    py::list out;
+    for (const Barcode& b : last_call_barcodes()) {
+      py::dict d;
+      d["box"] = py::make_tuple(b.box[0], b.box[1], b.box[2], b.box[3]);
+      d["symbology"] = b.symbology == 1 ? "code128" : "code39"; d["direction"] = b.direction; d["data"] = py::bytes(b.data);
+      d["text"] = py::reinterpret_steal<py::object>(PyUnicode_DecodeLatin1(b.data.data(), (Py_ssize_t)b.data.size(), nullptr));
+      d["lines"] = b.lines; d["module"] = b.module; d["gs1"] = b.gs1;
+      out.append(d);
+    }
+    return out;
+  }, "The barcodes of this thread's latest image_to_data call (DESIGN.md \"Barcodes\"), [] when barcodes were off");
   m.def("last_call_skew", []() -> py::object {
     const PageSkew s = last_call_skew();
     if (!s.on) return py::none();

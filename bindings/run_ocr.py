@@ -74,8 +74,8 @@ def annotate(image: np.ndarray, result, by_lines: bool = False, by_blocks: bool 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     rectify, lines, chars, blocks, curved = "--rectify" in argv, "--lines" in argv, "--chars" in argv, "--blocks" in argv, "--curved" in argv
-    tables, deskew, marks = "--tables" in argv, "--deskew" in argv, "--marks" in argv
-    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks", "--curved", "--tables", "--deskew", "--marks")]
+    tables, deskew, marks, barcodes = "--tables" in argv, "--deskew" in argv, "--marks" in argv, "--barcodes" in argv
+    argv = [a for a in argv if a not in ("--rectify", "--lines", "--chars", "--blocks", "--curved", "--tables", "--deskew", "--marks", "--barcodes")]
     image_path = argv[0] if len(argv) > 0 else os.path.join(HERE, "..", "tests", "data", "funsd_0001129658.png")
     weights_dir = argv[1] if len(argv) > 1 else os.path.join(HERE, "..", "weights")
     outputs_dir = argv[2] if len(argv) > 2 else os.path.join(HERE, "..", "outputs")
@@ -95,6 +95,8 @@ def main(argv=None):
         kw["tables"] = True
     if marks:                       # (DESIGN.md "Selection marks": sides 10..64, fill 24, ink 128)
         kw["marks"] = True
+    if barcodes:                    # (DESIGN.md "Barcodes": 8 lines, ink 128, Code 128 and Code 39)
+        kw["barcodes"] = True
     if deskew:                      # (DESIGN.md "Deskew": max_slope 64, gain 288, ink 128; the result is in the upright page's frame)
         kw["deskew"] = True
     result = pytuatara.image_to_data(numpy_image, weights_dir, outputs_dir, **kw)
@@ -116,6 +118,11 @@ def main(argv=None):
         for m in pytuatara.last_call_marks():
             print(("[x] " if m["selected"] else "[ ] ") + " ".join(str(v) for v in m["box"]) + "\t" + m["text"])
             d.rectangle([int(v) for v in m["box"]], outline=(0, 170, 0) if m["selected"] else (220, 0, 0), width=2)
+    if barcodes:                    # every barcode's box over the first panel in blue, and a line per barcode
+        d = ImageDraw.Draw(out)
+        for b in pytuatara.last_call_barcodes():
+            print(b["symbology"] + " " + str(b["direction"]) + " " + " ".join(str(v) for v in b["box"]) + "\t" + b["text"])
+            d.rectangle([int(v) for v in b["box"]], outline=(0, 0, 230), width=2)
     if deskew:                      # every item's box mapped back to the caller's image through the call's own record and drawn there, over the first panel
         skew = pytuatara.last_call_skew()
         print(f"# page 0 slope {skew['slope']} degrees {skew['degrees']:.4f}")

@@ -52,6 +52,9 @@
 //   ocr_cli --marks [MIN_SIDE] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: finds the page's checkboxes (DESIGN.md "Selection marks";
 //                                 sides MIN_SIDE..64 px, default 10) and prints one line per mark - "[x]" or "[ ]", the frame x0 y0 x1 y1, a tab, the text of
 //                                 the word it stands in front of - in (y, x) order
+//   ocr_cli --barcodes [MIN_LINES] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: reads the page's Code 128 and Code 39 barcodes (DESIGN.md
+//                                 "Barcodes"; MIN_LINES = the scan lines that must agree, 4..256, default 8) and prints one line per barcode - "code128" or
+//                                 "code39", the direction 0..3, the box x0 y0 x1 y1, a tab, the text (bytes outside 32..126 as \xHH) - in (y0, x0) order
 //   ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir>   in front of the plain form: finds ruling lines, tables, grids and merged cells in the
 // page's pixels (DESIGN.md "Tables"; MIN_LEN = the shortest ruling in px, 16..4096, default 48, not tuned on documents) and prints each table as "# table T x0 y0
 // x1 y1 rows cols" followed by its rows, the cells' texts separated by tabs (a merged cell's text at its first base cell; a line break inside a cell as " / ").
@@ -187,6 +190,27 @@ int main(int argc, const char** argv) {
         float px = 0.f, py = 0.f;
         sk.to_page(it.bbox[0], it.bbox[1], &px, &py);
         printf("%g %g %g %g\t%s\t%.9g %.9g\n", it.bbox[0], it.bbox[1], it.bbox[2], it.bbox[3], it.text.c_str(), px, py);
+      }
+      return 0;
+    }
+    if (argc >= 2 && std::string(argv[1]) == "--barcodes") {
+      int min_lines = 8, used = 1;
+      if (argc == 6) {
+        char* end = nullptr;
+        const long v = std::strtol(argv[2], &end, 10);
+        if (!end || *end || v < 4 || v > 256) throw std::runtime_error("--barcodes takes the scan lines that must agree, 4..256 (default 8)");
+        min_lines = (int)v; used = 2;
+      }
+      if (argc - used != 4) throw std::runtime_error("--barcodes [MIN_LINES] goes in front of <image.png> <weights_dir> <outputs_dir>");
+      pngdec::Image img = pngdec::read(argv[used + 1]);
+      set_barcodes(min_lines);
+      std::vector<OutputItemEx> items = image_to_data_ex(img.bgr.data(), img.rows, img.cols, (std::ptrdiff_t)img.cols * 3, argv[used + 2], argv[used + 3], false);
+      set_barcodes(0);
+      if (!last_call_error().empty()) return 1;                         // (the message is on stderr)
+      for (const Barcode& b : last_call_barcodes()) {                   // one line per barcode: its symbology, direction and box, then its text
+        printf("%s %d %d %d %d %d\t", b.symbology == 1 ? "code128" : "code39", b.direction, b.box[0], b.box[1], b.box[2], b.box[3]);
+        for (unsigned char c : b.data) { if (c >= 32 && c < 127 && c != '\\') putchar(c); else printf("\\x%02X", c); }
+        putchar('\n');
       }
       return 0;
     }
@@ -416,7 +440,7 @@ int main(int argc, const char** argv) {
       return 0;
     }
     if (argc != 4) {
-      std::cerr << "usage: ocr_cli --marks [MIN_SIDE] <image.png> <weights_dir> <outputs_dir> | ocr_cli --deskew [MAX_SLOPE] <image.png> <weights_dir> <outputs_dir> | ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir> | ocr_cli [--tiled [O]] [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
+      std::cerr << "usage: ocr_cli --barcodes [MIN_LINES] <image.png> <weights_dir> <outputs_dir> | ocr_cli --marks [MIN_SIDE] <image.png> <weights_dir> <outputs_dir> | ocr_cli --deskew [MAX_SLOPE] <image.png> <weights_dir> <outputs_dir> | ocr_cli --tables [MIN_LEN] <image.png> <weights_dir> <outputs_dir> | ocr_cli [--tiled [O]] [--allowlist S] [--blocklist S] [--pattern P [--pattern-best]] [--wide [A] | --curved | --alts K [--nbest M] | --lexicon FILE [--lexicon-m M] [--lexicon-fuzzy B [--lexicon-gap G]] | --rectify | --conf | --orient | --lines | --chars | --blocks | --regions FILE] <image.png> <weights_dir> <outputs_dir>" << std::endl;
       return 2;
     }
     pngdec::Image img = pngdec::read(argv[1]);

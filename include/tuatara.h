@@ -75,6 +75,7 @@ struct OutputItemEx {
   std::vector<WordPiece> pieces;   // wide words: the item's pieces in order (one, the item itself, when it is not wide); empty when wide is off (DESIGN.md "Wide words")
   bool curved = false;             // curved words: the item's crop was straightened along a spine found in the page (DESIGN.md "Curved words")
   std::vector<float> outline;      // curved words: 36 = 18 points x, y - the top edge left to right, then the bottom edge right to left; empty when curved is off
+  int barcode = -1;                // barcodes: the barcode of its page the item's centre lies in (a junk word the detector made of the bars); -1 for none and when barcodes are off (DESIGN.md "Barcodes")
   int mark = -1;                   // selection marks: the mark of its page the item's centre lies in (the `x` read inside a ticked box); -1 for none and when marks are off (DESIGN.md "Selection marks")
   int table = -1, cell = -1;       // tables: the table of its page and the cell of that page's cell list the item lies in; -1 / -1 in no cell and when tables are off (DESIGN.md "Tables")
   int block = -1, block_line = -1;  // text blocks: the item's block of its page, in reading order, and its line's position inside that block (what a caller sorts by: block, block_line, word); -1 when blocks are off (DESIGN.md "Text blocks")
@@ -288,6 +289,27 @@ struct SelectionMark {
 void set_marks(int min_side, int max_side = 64, int fill = 24, int ink = 128);
 int marks();
 std::vector<SelectionMark> last_call_marks();
+
+// Barcodes (opt-in; DESIGN.md "Barcodes"): the page's Code 128 and Code 39 barcodes are read off single lines of the ink bitmap of the page's own pixels, in all
+// four directions, and every item is given the barcode its centre lies in (OutputItemEx::barcode), so that the junk words the detector makes of the bars can be
+// dropped.  Items, order, boxes and text keep their bits.  set_barcodes(min_lines, ink, symbologies) turns it on for every call of THIS THREAD that follows
+// (min_lines 4..256 scan lines that must agree, ink 1..255, symbologies bit 0 Code 128 and bit 1 Code 39; the other layers use 8, 128 and 3, which nobody has
+// tuned on documents), set_barcodes(0) off again; with it off, TUATARA_BARCODES=MIN_LINES (or 1 for 8) in the environment turns it on for every call here.  It
+// is set on the cached engine for the call and reset afterwards.  A bad value: the message is printed and the result is empty (last_call_error()).
+// last_call_barcodes(): the barcodes of this thread's latest single-image call, in (y0, x0, direction) order; a page without words has barcodes too.
+struct Barcode {
+  int box[4] = {0, 0, 0, 0};        // x0, y0, x1, y1 in image pixels, inclusive (the upright page's under deskew)
+  int symbology = 0;                // 1 = Code 128, 2 = Code 39
+  int direction = 0;                // 0 left to right, 1 top to bottom, 2 right to left, 3 bottom to top
+  int lines = 0;                    // the scan lines that agreed
+  double module = 0.0;              // the mean module (Code 128) or narrow-run (Code 39) width in px
+  int flags = 0;                    // bit 0 GS1 (FNC1 first), bit 1 FNC2, bit 2 FNC3, bit 3 FNC4
+  bool gs1 = false;
+  std::string data;                 // the text, at most 48 bytes (Code 128 may hold control characters)
+};
+void set_barcodes(int min_lines, int ink = 128, int symbologies = 3);
+int barcodes();
+std::vector<Barcode> last_call_barcodes();
 
 // Deskew (opt-in; DESIGN.md "Deskew"): the page's skew is estimated on the GPU and a page found tilted is read upright; every box and quad of the result is then
 // in the upright page's frame.  set_deskew(max_slope, gain, ink) turns it on for every call of THIS THREAD that follows (max_slope 1..128 px per 512 px, gain

@@ -860,6 +860,45 @@ int ttr_marks_from_page_ink(const uint8_t* img, int h, int w, int row_stride, in
                             int nq, int32_t* mode, int32_t* counts, int32_t* marks, int32_t* item_mark);
 int ttr_marks_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int ink, const float* quads, int nq, int32_t* mode,
                    int32_t* counts, int32_t* marks, int32_t* item_mark);
+/* ---- barcodes (opt-in; DESIGN.md "Barcodes") --------------------------------------------------------------
+ * With ttr_engine_set_barcodes(e, min_lines, ink, symbologies) every page call also reads the page's Code 128 and Code 39 barcodes off single lines of the ink
+ * bitmaps of the page's own pixels - every row and every column, forwards and backwards (barcode_scan_kernel, barcodes.hip: pages x bands of lines) -, chains
+ * the lines' readings into barcodes and says for every item which barcode its centre lies in, so that the junk words the detector makes of the bars can be
+ * dropped (barcode_page_kernel, one workgroup per page).  Items, order, boxes, text, ids, conf and every other layer's outputs keep their bits; with barcodes
+ * off nothing runs.  min_lines = 0 is off (the default), else min_lines in 4..256 (the scan lines that must agree), ink in 1..255 (as for tables) and
+ * symbologies in 1..3 (bit 0 Code 128, bit 1 Code 39); the convenience layers use 8, 128 and 3, and none of these values has been tuned on documents.  With
+ * tables or marks on under the same ink rule the bitmaps are formed once for all; with local ink on they are local ink's.  Like marks the layer runs for a
+ * page without words.  The setter refuses while streamed batches are in flight and with a communicator attached; ttr_engine_attach_comm and
+ * ttr_pages_to_data_dev_sharded refuse while barcodes are on; region calls leave the views empty.  Under deskew the coordinates are the upright page's.  Cap: 64
+ * barcodes a page; a page beyond it reports mode -7, no barcodes and -1 for every item.  Scope: one scan line must cross every bar (turn deskew on for
+ * tilted pages); no Code 39 check character, no full-ASCII Code 39; quiet zones of half the standards' width are accepted.
+ * Result views (NULL / 0 with barcodes off):
+ *   ttr_result_barcode_mode    1, or -7; 0 when off
+ *   ttr_result_barcodes        [barcode_count][24] int32: x0, y0, x1, y1 (inclusive px), symbology (1 Code 128, 2 Code 39), dir (0 left to right, 1 top to
+ *                              bottom, 2 right to left, 3 bottom to top), lines (the scan lines that agreed), module64 (64 x the mean module or narrow-run
+ *                              width), flags (bit 0 GS1: FNC1 first; bit 1 FNC2, bit 2 FNC3, bit 3 FNC4), len, 0, 0, then 48 bytes of text, zero-filled; in
+ *                              (y0, x0, dir) order
+ *   ttr_result_item_barcode    [count]: the barcode an item's centre lies in, -1 for none
+ * ttr_results_gather_barcodes: item_barcode of n results back to back (-1 where a result has none); returns the number of items inside a barcode.
+ * ttr_barcodes_from_page: the rule on the host, no engine.  A host image u8 [h][w][3] (row_stride bytes, 0 = 3 w) and nq quads [nq][8] -> mode, counts [6] =
+ * {barcodes, candidates examined, start patterns matched, hits kept, hits dropped, chains below min_lines}, barcodes [64][24] (capacity; counts[0] says how
+ * much is valid), item_barcode [nq], and the lines' raw hits [(h + w) 2 8][20] and counters [(h + w) 2][4] as ttr_dbg_barcodes describes them; any output may
+ * be NULL.  Returns 0, -1 with the message in ttr_last_error (a parameter outside its range, a quad with a coordinate that is not finite or has |x| >= 32768,
+ * a page side of 32768 or more).  ttr_barcodes_from_page_ink: the same with local ink's (radius, drop, polarity) in the place of ink.
+ * ttr_barcodes_page (stage; refuses while batches stream): the same through the kernels under the fixed ink rule, whatever the engine's setting. */
+int ttr_engine_set_barcodes(ttr_engine* e, int min_lines, int ink, int symbologies);
+int ttr_engine_barcodes(const ttr_engine* e, int* ink, int* symbologies);
+int ttr_result_barcode_mode(const ttr_result* r);
+int ttr_result_barcode_count(const ttr_result* r);
+const int32_t* ttr_result_barcodes(const ttr_result* r);
+const int32_t* ttr_result_item_barcode(const ttr_result* r);
+int ttr_results_gather_barcodes(ttr_result* const* rs, int n, int32_t* item_barcode);
+int ttr_barcodes_from_page(const uint8_t* img, int h, int w, int row_stride, int min_lines, int ink, int symbologies, const float* quads, int nq, int32_t* mode,
+                           int32_t* counts, int32_t* barcodes, int32_t* item_barcode, int32_t* hits, int32_t* line_counts);
+int ttr_barcodes_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int min_lines, int symbologies, int radius, int drop, int polarity, const float* quads,
+                               int nq, int32_t* mode, int32_t* counts, int32_t* barcodes, int32_t* item_barcode);
+int ttr_barcodes_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_lines, int ink, int symbologies, const float* quads, int nq, int32_t* mode,
+                      int32_t* counts, int32_t* barcodes, int32_t* item_barcode);
 /* Tokenizer::decode + EOS cut (tuatara.cpp:61-78, :497-502) on 26 ids; buf needs >= 27 bytes. */
 int ttr_decode_ids(const int32_t* ids, int n, char* buf);
 

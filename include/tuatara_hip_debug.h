@@ -155,6 +155,13 @@ int ttr_dbg_ink_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_st
  * them; mode; marks [512][12] (zero beyond the count); any output may be NULL.  Refuses while batches stream.  Returns 0, -1 on error. */
 int ttr_dbg_marks(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_side, int max_side, int fill, int ink,
                   int32_t* corners, int32_t* band_counts, int32_t* mode, int32_t* marks);
+/* barcodes (DESIGN.md "Barcodes"): table_ink_kernel, barcode_scan_kernel and barcode_page_kernel on a host image placed as ttr_dbg_tables takes it.  hits
+ * [(h + w) 2 8][20]: the raw hits of every line (rows, then columns) and reading (forwards, backwards), eight slots each, as barcodes_rule.h lays a hit out (p0,
+ * p1, module64, flags, len, symbology, the hit it chains to, its chain's first hit, text [12]; zero beyond a line's count); line_counts [(h + w) 2][4]: hits
+ * kept, hits dropped, candidates, start patterns; side [1544]: the page's side block (zero beyond the count); any output may be NULL.  Refuses while batches
+ * stream.  Returns 0, -1 on error. */
+int ttr_dbg_barcodes(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_lines, int ink, int symbologies, int32_t* hits,
+                     int32_t* line_counts, int32_t* side);
 /* the ink passes (table_ink_kernel, or local ink's two kernels) the engine has enqueued for its batches' page layers since it was created: tables and selection
  * marks in one batch under one ink rule share one.  -1 for a null engine. */
 int64_t ttr_dbg_page_ink_passes(const ttr_engine* e);

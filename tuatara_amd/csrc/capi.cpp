@@ -2,6 +2,7 @@
 #include "engine.h"
 #include "page_table.h"
 #include "tables_rule.h"
+#include "barcodes_rule.h"
 #include "marks_rule.h"
 
 namespace ttr {
@@ -1944,6 +1945,112 @@ int ttr_marks_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stri
   std::vector<int32_t> side(kMarkSideInts), items((size_t)nq);
   E.marks_stage(img, h, w, row_stride, 0, 0, min_side, max_side, fill, ink, quads, nq, side.data(), items.data(), nullptr);
   marks_out(side.data(), items.data(), nq, mode, counts, marks, item_mark);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+// ---- barcodes (DESIGN.md "Barcodes")
+static std::string barcodes_ranges(int min_lines, int ink, int symbologies) {
+  return "min_lines must lie in 4..256, ink in 1..255 and symbologies in 1..3, got " + std::to_string(min_lines) + ", " + std::to_string(ink) + " and " + std::to_string(symbologies);
+}
+
+int ttr_engine_set_barcodes(ttr_engine* e, int min_lines, int ink, int symbologies) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  if (min_lines != 0 && !barcodes_args_ok(min_lines, ink, symbologies)) throw std::runtime_error("ttr_engine_set_barcodes: min_lines must be 0 (off), or " + barcodes_ranges(min_lines, ink, symbologies));
+  E.refuse_while_streaming("ttr_engine_set_barcodes");
+  if (min_lines && E.comm) throw std::runtime_error("ttr_engine_set_barcodes: barcodes are read by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
+  E.barcodes_min = min_lines;
+  if (min_lines) { E.barcodes_ink = ink; E.barcodes_sym = symbologies; }
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_engine_barcodes(const ttr_engine* e, int* ink, int* symbologies) {
+  if (!e) return 0;
+  if (ink) *ink = e->e->barcodes_ink;
+  if (symbologies) *symbologies = e->e->barcodes_sym;
+  return e->e->barcodes_min;
+}
+
+int ttr_result_barcode_mode(const ttr_result* r) { return r ? r->r.barcode_mode : 0; }
+int ttr_result_barcode_count(const ttr_result* r) { return r ? (int)(r->r.barcodes.size() / kBcRec) : 0; }
+const int32_t* ttr_result_barcodes(const ttr_result* r) { return r && !r->r.barcodes.empty() ? r->r.barcodes.data() : nullptr; }
+const int32_t* ttr_result_item_barcode(const ttr_result* r) { return r && !r->r.item_barcode.empty() ? r->r.item_barcode.data() : nullptr; }
+
+int ttr_results_gather_barcodes(ttr_result* const* rs, int n, int32_t* item_barcode) {
+  if (!rs || n < 0) return -1;
+  size_t oi = 0, inside = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!rs[i]) continue;
+    const Result& r = rs[i]->r;
+    const size_t cnt = r.text.size();
+    const bool has = cnt > 0 && r.item_barcode.size() == cnt;
+    if (item_barcode) { if (has) std::copy(r.item_barcode.begin(), r.item_barcode.end(), item_barcode + oi); else std::fill(item_barcode + oi, item_barcode + oi + cnt, -1); }
+    if (has) for (int32_t m : r.item_barcode) inside += m >= 0;
+    oi += cnt;
+  }
+  return (int)inside;
+}
+
+static void barcodes_out(const int32_t* side, const int32_t* items, int nq, int32_t* mode, int32_t* counts, int32_t* barcodes, int32_t* item_barcode) {
+  if (mode) *mode = side[0];
+  if (counts) std::copy(side + 1, side + 7, counts);
+  if (barcodes) std::copy(side + kBcHdr, side + kBcHdr + (size_t)kBcRec * side[1], barcodes);
+  if (item_barcode) std::copy(items, items + nq, item_barcode);
+}
+
+static void barcodes_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int min_lines, int ink, int symbologies, const float* quads, int nq) {
+  if (nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
+  page_image_ok(what, img, h, w, row_stride, 32768);
+  if (!barcodes_args_ok(min_lines, ink, symbologies)) throw std::runtime_error(std::string(what) + ": " + barcodes_ranges(min_lines, ink, symbologies));
+  page_quads_ok(what, quads, nq);
+}
+
+static void barcodes_host_items(const int32_t* side, const float* quads, int nq, int32_t* items) {
+  std::vector<int32_t> centres((size_t)nq * 2);
+  for (int i = 0; i < nq; ++i) tables_word_centre(quads + 8 * (size_t)i, &centres[2 * (size_t)i]);
+  barcodes_items(side, centres.data(), nq, items);
+}
+
+int ttr_barcodes_from_page(const uint8_t* img, int h, int w, int row_stride, int min_lines, int ink, int symbologies, const float* quads, int nq, int32_t* mode,
+                           int32_t* counts, int32_t* barcodes, int32_t* item_barcode, int32_t* hits, int32_t* line_counts) {
+  TTR_GUARD_BEGIN
+  barcodes_in_ok("ttr_barcodes_from_page", img, h, w, row_stride, min_lines, ink, symbologies, quads, nq);
+  std::vector<int32_t> side(kBcSideInts), items((size_t)nq);
+  barcodes_from_page(img, h, w, row_stride ? row_stride : w * 3, min_lines, ink, symbologies, side.data(), hits, line_counts);
+  barcodes_host_items(side.data(), quads, nq, items.data());
+  barcodes_out(side.data(), items.data(), nq, mode, counts, barcodes, item_barcode);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_barcodes_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int min_lines, int symbologies, int radius, int drop, int polarity, const float* quads,
+                               int nq, int32_t* mode, int32_t* counts, int32_t* barcodes, int32_t* item_barcode) {
+  TTR_GUARD_BEGIN
+  barcodes_in_ok("ttr_barcodes_from_page_ink", img, h, w, row_stride, min_lines, 128, symbologies, quads, nq);
+  ink_in_ok("ttr_barcodes_from_page_ink", img, h, w, row_stride, radius, drop, polarity);
+  std::vector<int32_t> side(kBcSideInts), items((size_t)nq);
+  barcodes_from_page_ink(img, h, w, row_stride ? row_stride : w * 3, min_lines, symbologies, radius, drop, polarity, side.data());
+  barcodes_host_items(side.data(), quads, nq, items.data());
+  barcodes_out(side.data(), items.data(), nq, mode, counts, barcodes, item_barcode);
+  return 0;
+  TTR_GUARD_END(-1)
+}
+
+int ttr_barcodes_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_lines, int ink, int symbologies, const float* quads, int nq, int32_t* mode,
+                      int32_t* counts, int32_t* barcodes, int32_t* item_barcode) {
+  TTR_GUARD_BEGIN
+  if (!e) throw std::runtime_error("null argument");
+  barcodes_in_ok("ttr_barcodes_page", img, h, w, row_stride, min_lines, ink, symbologies, quads, nq);
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_barcodes_page");
+  std::vector<int32_t> side(kBcSideInts), items((size_t)nq);
+  E.barcodes_stage(img, h, w, row_stride, 0, 0, min_lines, ink, symbologies, quads, nq, side.data(), items.data(), nullptr, nullptr);
+  barcodes_out(side.data(), items.data(), nq, mode, counts, barcodes, item_barcode);
   return 0;
   TTR_GUARD_END(-1)
 }

@@ -1,6 +1,7 @@
 // Developer hooks of include/tuatara_hip_debug.h: single-kernel test entry points, micro-benchmarks, the tuning registry.
 #include "engine.h"
 #include "tables_rule.h"
+#include "barcodes_rule.h"
 #include "marks_rule.h"
 
 using namespace ttr;
@@ -807,6 +808,19 @@ int ttr_dbg_ink_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_st
 }
 
 int64_t ttr_dbg_page_ink_passes(const ttr_engine* e) { return e ? e->e->page_ink_passes : -1; }
+
+// barcodes (DESIGN.md "Barcodes"): the lines' raw hits and counters as the device formed them
+int ttr_dbg_barcodes(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_lines, int ink, int symbologies, int32_t* hits,
+                     int32_t* line_counts, int32_t* side_out) {
+  TTR_GUARD_BEGIN
+  if (!e || !img) throw std::runtime_error("null argument");
+  Engine& E = *e->e;
+  EngineScope lk(E);
+  E.refuse_while_streaming("ttr_dbg_barcodes");
+  E.barcodes_stage(img, h, w, row_stride, dev_offset, dev_stride, min_lines, ink, symbologies, nullptr, 0, side_out, nullptr, hits, line_counts);
+  return 0;
+  TTR_GUARD_END(-1)
+}
 
 // selection marks (DESIGN.md "Selection marks"): the corner count and the band counts as the device formed them
 int ttr_dbg_marks(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_side, int max_side, int fill, int ink,

@@ -327,6 +327,7 @@ int ttr_engine_attach_comm(ttr_engine* e, ttr_comm* c) {
   if (c && e->e->curved) throw std::runtime_error("ttr_engine_attach_comm: curved words are read by one engine alone, and curved is on: ttr_engine_set_curved(e, 0) first");
   if (c && e->e->deskew_M) throw std::runtime_error("ttr_engine_attach_comm: pages are straightened by one engine alone, and deskew is on: ttr_engine_set_deskew(e, 0, 0, 0) first");
   if (c && e->e->tables_min_len) throw std::runtime_error("ttr_engine_attach_comm: tables are found by one engine alone, and tables are on: ttr_engine_set_tables(e, 0, 0) first");
+  if (c && e->e->barcodes_min) throw std::runtime_error("ttr_engine_attach_comm: barcodes are read by one engine alone, and barcodes are on: ttr_engine_set_barcodes(e, 0, 0, 0) first");
   if (c && e->e->marks_min) throw std::runtime_error("ttr_engine_attach_comm: selection marks are found by one engine alone, and marks are on: ttr_engine_set_marks(e, 0, 0, 0, 0) first");
   if (c && e->e->tiled) throw std::runtime_error("ttr_engine_attach_comm: tiled pages are read by one engine alone, and tiling is on: ttr_engine_set_tiled(e, 0) first");
   e->e->comm = c ? c->c.get() : nullptr;

@@ -364,6 +364,10 @@ struct Result {
   int mark_mode = 0;                        // 1, or -6 for a page of more than 512 marks
   std::vector<int32_t> marks;               // 12 per mark: x0, y0, x1, y1, ix0, iy0, ix1, iy1, inked, area, state, label
   std::vector<int32_t> item_mark;           // 1 per item: the mark its centre lies in, -1 = none
+  // barcodes (ttr_engine_set_barcodes; DESIGN.md "Barcodes"): 0 / empty when off and for region calls
+  int barcode_mode = 0;                     // 1, or -7 for a page of more than 64 barcodes
+  std::vector<int32_t> barcodes;            // 24 per barcode: x0, y0, x1, y1, symbology, dir, lines, module64, flags, len, 0, 0, text [12]
+  std::vector<int32_t> item_barcode;        // 1 per item: the barcode its centre lies in, -1 = none
   // text blocks (cfg.blocks = 1; DESIGN.md "Text blocks"): empty / 0 when off
   std::vector<int32_t> line_block, line_pos;     // 1 per line: its block in reading order, its position inside that block
   std::vector<int32_t> block;                    // 1 per item: its line's block
@@ -573,6 +577,9 @@ constexpr BufRow kDevBufTable[] = {
     {"mark_cand", false, kElI32, ""},
     {"mark_counts", false, kElI32, ""},
     {"mark_side", false, kElI32, ""},
+    {"bc_hits", false, kElI32, ""},
+    {"bc_cnt", false, kElI32, ""},
+    {"bc_side", false, kElI32, ""},
     {"blocks_side", false, kElI32, ""},
     {"chars_map", false, kElF32, ""},
     {"chars_in", false, kElI32, ""},
@@ -612,6 +619,9 @@ struct Engine {
   // selection marks: the smallest side in px, 0 = off or 8..64; the largest side, min..128; the fill threshold in 256ths, 1..255; the ink threshold 1..255
   // (ttr_engine_set_marks; DESIGN.md "Selection marks")
   int marks_min = 0, marks_max = 64, marks_fill = 24, marks_ink = 128;
+  // barcodes: the scan lines that must agree, 0 = off or 4..256; the ink threshold 1..255; the symbologies, bit 0 Code 128, bit 1 Code 39
+  // (ttr_engine_set_barcodes; DESIGN.md "Barcodes")
+  int barcodes_min = 0, barcodes_ink = 128, barcodes_sym = 3;
   int tables_min_len = 0, tables_ink = 128;       // tables: the shortest ruling in px, 0 = off or 16..4096, and the ink threshold 1..255 (ttr_engine_set_tables; DESIGN.md "Tables")
   // tiled pages (ttr_engine_set_tiled; DESIGN.md "Tiled pages"): the tiles' overlap in pixels, 0 = off.  On, a page keeps its own scale (ratio 1, page canvas
   // c32(h) x c32(w)); one larger than the detector canvas goes through CRAFT as overlapping tiles whose maps tile_stitch_kernel joins into `heat`
@@ -736,6 +746,10 @@ struct Engine {
   // the tables pass's (tab_bits / tab_bitsT), formed once per batch whichever of the two layers is on
   DevBuf mark_cand, mark_counts, mark_side;
   SideCopy h_mark;                                // ... the side blocks' host copy
+  // barcodes (barcodes.hip): the lines' hit slots and counters (workspaces), and the side blocks [pages][kBcSideInts] | [N] item_barcode.  The bitmaps are the
+  // tables pass's again, formed once per batch whichever of the three layers is on under one ink rule
+  DevBuf bc_hits, bc_cnt, bc_side;
+  SideCopy h_barcode;                             // ... the side blocks' host copy
   int64_t page_ink_passes = 0;                    // the ink passes page_ink_enqueue has enqueued for batches (ttr_dbg_page_ink_passes: one per batch, whichever layers are on)
   DevBuf tab_ink_h, tab_ink_rec;                  // local ink under tables (and ttr_ink_page): the horizontal sums [pages][Hcap][Wcap] uint32, the records [pages]
   DevBuf blocks_side;                             // text blocks: the side block (blocks.hip)
@@ -1060,6 +1074,8 @@ struct Engine {
     std::vector<int32_t> tab_centres;
     // selection marks (DESIGN.md "Selection marks"): the engine's setting when the boxes were made (mark_min 0 = off, and for region calls); they share the centres
     int mark_min = 0, mark_max = 0, mark_fill = 0, mark_ink = 0;
+    // barcodes (DESIGN.md "Barcodes"): likewise (bc_min 0 = off, and for region calls)
+    int bc_min = 0, bc_ink = 0, bc_sym = 0;
     std::vector<DeskewRec> dsk_recs;   // deskew: the pages' records as the device wrote them (detect_collect_local takes them from the slot's pinned copy)
     // local ink (DESIGN.md "Local ink"): the engine's setting when the detector was enqueued (radius 0 = off), and the records of the deskew pass, taken with dsk_recs
     int ink_radius = 0, ink_drop = 0, ink_polarity = 0;
@@ -1128,6 +1144,13 @@ struct Engine {
   // selection marks: the two kernels of batch B behind its packer, or - for a batch without words - on their own; the ink pass first unless tables_enqueue ran it.
   // A no-op with marks off
   void marks_enqueue(const PageBatch& B, int sl);
+  // barcodes: the two kernels of batch B behind its packer, or - for a batch without words - on their own; the ink pass first unless tables_enqueue or
+  // marks_enqueue left this batch's bitmaps under the same rule.  A no-op with barcodes off
+  void barcodes_enqueue(const PageBatch& B, int sl);
+  // the stage form (ttr_barcodes_page, and the developer hook): through table_ink_kernel, barcode_scan_kernel and barcode_page_kernel -> side [kBcSideInts],
+  // item_barcode [nq], hits [(h + w) 2 8][20], cnt [(h + w) 2][4]
+  void barcodes_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_lines, int ink, int symbologies, const float* quads, int nq,
+                      int32_t* side_out, int32_t* item_out, int32_t* hits_out, int32_t* cnt_out);
   // The opening every one-page stage call shares.  stage_page: a host image (row_stride 0 = packed rows) checked under the caller's `what` - "bad image size",
   // a page side of side_cap px or more (0 = no cap), `bad_args` (the layer's own range refusal, null = in range), "bad device offset or stride" - then copied
   // dev_offset bytes into staging_img with dev_stride bytes from row to row (0 = 3 w), on `stream`; returns where it lies.  check = false: the caller has made
@@ -1196,7 +1219,7 @@ struct Engine {
   void finish(PageBatch& B, std::vector<Result>& results);
   // the host copies of a batch's side blocks as finish takes them from the SideCopy records (view(slot)): null = the layer did not run for the batch
   struct SideViews {
-    const int32_t *orient = nullptr, *lines = nullptr, *blocks = nullptr, *chars = nullptr, *alts = nullptr, *lex = nullptr, *wide_cuts = nullptr, *curve = nullptr, *tab = nullptr, *mark = nullptr;
+    const int32_t *orient = nullptr, *lines = nullptr, *blocks = nullptr, *chars = nullptr, *alts = nullptr, *lex = nullptr, *wide_cuts = nullptr, *curve = nullptr, *tab = nullptr, *mark = nullptr, *barcode = nullptr;
     const float* pat_logp = nullptr; const InkRec* tab_ink = nullptr;
   };
   // results[pg] for every page of B from its boxes, the decoded rows of its crops (crop c is row c) and the side blocks: one function per layer, run page by
@@ -1205,7 +1228,7 @@ struct Engine {
   void decode_pages(const PageBatch& B, const RecRows& rows, const SideViews& views, std::vector<Result>& results);
   // words: ids, prob, conf, alternatives, lexicon matches, pattern_logp, orientation, text, bbox, quad; records: the page's skew and ink records
   void decode_words(const PageCtx&, Result&) const, decode_records(const PageCtx&, Result&) const, decode_tables(const PageCtx&, Result&) const,
-      decode_marks(const PageCtx&, Result&) const, decode_curved(const PageCtx&, Result&) const, decode_wide(const PageCtx&, Result&) const,
+      decode_marks(const PageCtx&, Result&) const, decode_barcodes(const PageCtx&, Result&) const, decode_curved(const PageCtx&, Result&) const, decode_wide(const PageCtx&, Result&) const,
       decode_lines(const PageCtx&, Result&) const, decode_blocks(const PageCtx&, Result&) const, decode_chars(const PageCtx&, Result&) const;
 
   // the stage entry points (ttr_craft_heatmap, ttr_parseq_logits, ...) share workspaces with the batches: with the recogniser of a streamed batch on a stream of
@@ -1302,6 +1325,7 @@ struct Engine {
     f("tab_bits", tab_bits, kElU8); f("tab_bitsT", tab_bitsT, kElU8); f("tab_runs", tab_runs, kElI32); f("tab_side", tab_side, kElI32);
     f("tab_ink_h", tab_ink_h, kElU8); f("tab_ink_rec", tab_ink_rec, kElI32);
     f("mark_cand", mark_cand, kElI32); f("mark_counts", mark_counts, kElI32); f("mark_side", mark_side, kElI32);
+    f("bc_hits", bc_hits, kElI32); f("bc_cnt", bc_cnt, kElI32); f("bc_side", bc_side, kElI32);
     f("blocks_side", blocks_side, kElI32);
     for (auto& d : chars_map) f("chars_map", d, kElF32);
     f("chars_in", chars_in, kElI32); f("chars_side", chars_side, kElI32);

@@ -6,6 +6,7 @@
 #include "engine.h"
 #include "page_table.h"
 #include "tables_rule.h"
+#include "barcodes_rule.h"
 #include "marks_rule.h"
 
 namespace ttr {
@@ -350,6 +351,7 @@ void Engine::detect_enqueue(PageBatch& B) {
   const int side = std::max(B.extent().h, B.extent().w);   // the longest page side: the tables and marks rules' coordinates are below 32768 (likewise before anything is enqueued)
   if (tables_min_len && side >= 32768) throw std::runtime_error("tables: a page side of 32768 px or more: ttr_engine_set_tables(e, 0, 0) first");
   if (marks_min && side >= 32768) throw std::runtime_error("marks: a page side of 32768 px or more: ttr_engine_set_marks(e, 0, 0, 0, 0) first");
+  if (barcodes_min && side >= 32768) throw std::runtime_error("barcodes: a page side of 32768 px or more: ttr_engine_set_barcodes(e, 0, 0, 0) first");
   // Deskew (DESIGN.md "Deskew"): every page's skew is estimated and the batch's pages become upright copies in the slot's buffer; everything below and behind
   // reads B.pages as ever.  Off: nothing here runs.
   B.ink_radius = ink_radius; B.ink_drop = ink_drop; B.ink_polarity = ink_polarity;   // local ink: fixed for the batch here (the setter refuses while batches stream)
@@ -518,6 +520,7 @@ void Engine::detect_collect_local(PageBatch& B) {
   host_us[1] = host_us[2] = host_us[3] = 0.f;
   B.tab_min_len = tables_min_len; B.tab_ink = tables_ink; B.tab_centres.clear();   // tables: fixed for the batch here (the setter refuses while batches stream)
   B.mark_min = marks_min; B.mark_max = marks_max; B.mark_fill = marks_fill; B.mark_ink = marks_ink;   // selection marks: likewise
+  B.bc_min = barcodes_min; B.bc_ink = barcodes_ink; B.bc_sym = barcodes_sym;                           // barcodes: likewise
   std::vector<float> tq;
   for (int gi = 0; gi < groups; ++gi) ccl_collect(gi * GP, std::min(GP, n - gi * GP), gi, B.H2, B.W2, dets);
   // deskew: the batch's records were copied ahead of its detector on the same stream, so they are here; taken now, before the slot's next batch overwrites them
@@ -556,10 +559,10 @@ void Engine::detect_collect_local(PageBatch& B) {
       B.boxes[i].push_back(b);
       B.rects.insert(B.rects.end(), {x0, y0, x1, y1, i});
       B.page_of.push_back(i);
-      if (B.tab_min_len || B.mark_min) {   // tables, selection marks: 64 x the centre of the quad the result will carry (DESIGN.md "Tables", step 8)
+      if (B.tab_min_len || B.mark_min || B.bc_min) {   // tables, selection marks, barcodes: 64 x the centre of the quad the result will carry (DESIGN.md "Tables", step 8)
         tq.clear();
         push_quad(b, tq);
-        if (!region_quad_ok(tq.data())) throw std::runtime_error(std::string(B.tab_min_len ? "tables" : "marks") + ": a corner of a word of page " + std::to_string(i) + " is not finite or lies beyond 32768 px");
+        if (!region_quad_ok(tq.data())) throw std::runtime_error(std::string(B.tab_min_len ? "tables" : B.mark_min ? "marks" : "barcodes") + ": a corner of a word of page " + std::to_string(i) + " is not finite or lies beyond 32768 px");
         int32_t c[2];
         tables_word_centre(tq.data(), c);
         B.tab_centres.insert(B.tab_centres.end(), c, c + 2);
@@ -636,12 +639,12 @@ void Engine::plan_curved(PageBatch& B, const float* quads) {
 void Engine::pack_batch_crops(const PageBatch& B, int sl) {
   const int rows = B.N + B.X;                                  // wide words: X more rows behind the batch's N
   // (tables, selection marks: every word's centre [N][2] and the pages' offsets [n + 1] travel behind the rectangles, in the same copy)
-  const size_t rect_ints = B.rects.size(), tab_ints = B.tab_min_len || B.mark_min ? B.tab_centres.size() + (size_t)B.n + 1 : 0;
+  const size_t rect_ints = B.rects.size(), tab_ints = B.tab_min_len || B.mark_min || B.bc_min ? B.tab_centres.size() + (size_t)B.n + 1 : 0;
   rects_dev.ensure((rect_ints + tab_ints) * 4);
   h_rects[sl].ensure((rect_ints + tab_ints) * 4);
   memcpy(h_rects[sl].p, B.rects.data(), rect_ints * 4);
   if (tab_ints) {
-    if (B.tab_centres.size() != (size_t)B.N * 2) throw std::runtime_error(std::string(B.tab_min_len ? "tables" : "marks") + ": centre count does not match the crop count");
+    if (B.tab_centres.size() != (size_t)B.N * 2) throw std::runtime_error(std::string(B.tab_min_len ? "tables" : B.mark_min ? "marks" : "barcodes") + ": centre count does not match the crop count");
     int32_t* t = h_rects[sl].as<int32_t>() + rect_ints;
     std::copy(B.tab_centres.begin(), B.tab_centres.end(), t);
     const std::vector<int> first = page_first(B.page_of, B.n);
@@ -1051,6 +1054,64 @@ void Engine::marks_stage(const uint8_t* img, int h, int w, int row_stride, int d
   if (item_mark_out) std::copy(side.begin() + kMarkSideInts, side.end(), item_mark_out);
 }
 
+void Engine::barcodes_enqueue(const PageBatch& B, int sl) {
+  const int n = B.n, N = B.N;
+  const auto [Hcap, Wcap] = B.extent();
+  // (detect_enqueue refused a page side of 32768 or more before anything of the batch was enqueued)
+  bc_hits.ensure(barcodes_hit_ints(Hcap, Wcap, n) * 4); bc_cnt.ensure(barcodes_count_ints(Hcap, Wcap, n) * 4);
+  const size_t side_b = barcodes_side_bytes(n, N);
+  bc_side.ensure(side_b); h_barcode.arm(sl, side_b);
+  const Page& P0 = B.pages[0];
+  const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
+  const int* centres = rects_dev.as<int>() + B.rects.size();
+  if (N == 0) {   // a batch without words has no packer and so no upload: the pages' offsets [n + 1], all 0, go up here unless marks_enqueue sent them
+    if (!B.mark_min) {
+      rects_dev.ensure(((size_t)n + 1) * 4); h_rects[sl].ensure(((size_t)n + 1) * 4);
+      std::fill(h_rects[sl].as<int32_t>(), h_rects[sl].as<int32_t>() + n + 1, 0);
+      TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[sl].p, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, stream));
+    }
+    centres = rects_dev.as<int>();
+  }
+  // the bitmaps: those the batch's last ink pass left - marks' when it ran, else tables' - when that pass was under the same rule (the local one, or the fixed
+  // one with the same `ink`), else formed here
+  const bool tabs = B.tab_min_len && N > 0;
+  const bool shared = (B.mark_min || tabs) && (B.ink_radius || (B.mark_min ? B.mark_ink : B.tab_ink) == B.bc_ink);
+  if (!shared) page_ink_enqueue(B, sl, B.bc_ink);
+  launch_barcode_scan(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), P0.h, P0.w, table, n, Hcap, Wcap, B.bc_sym, bc_hits.as<int>(), bc_cnt.as<int>(), stream);
+  launch_barcode_page(bc_hits.as<int>(), bc_cnt.as<int>(), P0.h, P0.w, table, n, Hcap, Wcap, B.bc_min, centres, centres + (size_t)N * 2, bc_side.as<int>(),
+                      bc_side.as<int>() + (size_t)n * kBcSideInts, stream);
+  if (B.mixed) TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the table's last reader of this batch is now this kernel)
+}
+
+void Engine::barcodes_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_lines, int ink, int symbologies, const float* quads,
+                            int nq, int32_t* side_out, int32_t* item_out, int32_t* hits_out, int32_t* cnt_out) {
+  const StagedPage pg = stage_page("ttr_barcodes_page", img, h, w, row_stride, dev_offset, dev_stride, 32768,
+                                   barcodes_args_ok(min_lines, ink, symbologies) ? nullptr : "min_lines must lie in 4..256, ink in 1..255 and symbologies in 1..3");
+  stage_centres("ttr_barcodes_page", quads, nq);
+  const size_t side_b = barcodes_side_bytes(1, nq), hit_b = barcodes_hit_ints(h, w, 1) * 4, cnt_b = barcodes_count_ints(h, w, 1) * 4;
+  tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8);
+  bc_hits.ensure(hit_b); bc_cnt.ensure(cnt_b); bc_side.ensure(side_b);
+  if (hits_out) TTR_HIP_CHECK(hipMemsetAsync(bc_hits.p, 0, hit_b, stream));   // (the hook returns whole slot lists)
+  launch_table_ink(pg.data, 0, pg.stride, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  launch_barcode_scan(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), h, w, nullptr, 1, h, w, symbologies, bc_hits.as<int>(), bc_cnt.as<int>(), stream);
+  launch_barcode_page(bc_hits.as<int>(), bc_cnt.as<int>(), h, w, nullptr, 1, h, w, min_lines, rects_dev.as<int>(), rects_dev.as<int>() + (size_t)nq * 2, bc_side.as<int>(),
+                      bc_side.as<int>() + kBcSideInts, stream);
+  std::vector<int32_t> side(side_b / 4);
+  TTR_HIP_CHECK(hipMemcpyAsync(side.data(), bc_side.p, side_b, hipMemcpyDeviceToHost, stream));
+  if (hits_out) TTR_HIP_CHECK(hipMemcpyAsync(hits_out, bc_hits.p, hit_b, hipMemcpyDeviceToHost, stream));
+  if (cnt_out) TTR_HIP_CHECK(hipMemcpyAsync(cnt_out, bc_cnt.p, cnt_b, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  std::string why;
+  if (!barcodes_side_valid(side.data(), h, w, min_lines, symbologies, &why)) throw std::runtime_error("ttr_barcodes_page: the side block holds " + why);
+  for (int i = 0; i < nq; ++i)
+    if (side[kBcSideInts + (size_t)i] < -1 || side[kBcSideInts + (size_t)i] >= side[1]) throw std::runtime_error("ttr_barcodes_page: an item names a barcode that does not exist");
+  if (side_out) {   // (validated: the counted part is what callers read; the rest is zero as on the host)
+    std::fill(side_out, side_out + kBcSideInts, 0);
+    std::copy(side.begin(), side.begin() + kBcHdr + (size_t)kBcRec * side[1], side_out);
+  }
+  if (item_out) std::copy(side.begin() + kBcSideInts, side.end(), item_out);
+}
+
 void Engine::ink_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int radius, int drop, int polarity, uint64_t* bits_out,
                        uint64_t* bitsT_out, InkRec* rec) {
   const StagedPage pg = stage_page("ttr_ink_page", img, h, w, row_stride, dev_offset, dev_stride, 32768,
@@ -1072,7 +1133,7 @@ void Engine::ink_stage(const uint8_t* img, int h, int w, int row_stride, int dev
 void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
   // the slot's side-block records: disarmed, then armed by each layer that runs for this batch (engine.h: SideCopy)
-  for (SideCopy* c : {&h_orient, &h_lines, &h_blocks, &h_chars, &h_alts, &h_lex, &h_pat_logp, &h_wide, &h_curve, &h_tab, &h_tab_ink, &h_mark}) c->disarm(sl);
+  for (SideCopy* c : {&h_orient, &h_lines, &h_blocks, &h_chars, &h_alts, &h_lex, &h_pat_logp, &h_wide, &h_curve, &h_tab, &h_tab_ink, &h_mark, &h_barcode}) c->disarm(sl);
   const int line_words = cfg.lines && N > 0 ? stage_batch_lines(B, sl) : 0;   // text lines: the host part, before anything of this batch is enqueued
   if (cfg.chars && N > 0) stage_batch_chars(B, sl);                          // character boxes: likewise
   B.alts = orient_k() > 1 ? 0 : alts;        // character alternatives: fixed for the batch here (the setter refuses while batches stream)
@@ -1108,6 +1169,7 @@ void Engine::recog_enqueue(PageBatch& B) {
     if (cfg.blocks) group_batch_blocks(B, sl, line_words);             // text blocks: directly behind, from the lines' side block on the device (DESIGN.md "Text blocks")
     if (B.tab_min_len) tables_enqueue(B, sl);                          // tables: the pages' own pixels and the boxes just made (DESIGN.md "Tables")
     if (B.mark_min) marks_enqueue(B, sl);                              // selection marks: likewise, on the bitmaps tables formed when it is on (DESIGN.md "Selection marks")
+    if (B.bc_min) barcodes_enqueue(B, sl);                             // barcodes: likewise, on the bitmaps tables or marks formed under the same rule (DESIGN.md "Barcodes")
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     if (B.regions) {   // the caller's sets: one mask by value (the engine's own path), or the rows' table through the slot's pinned staging (one copy, no launch)
       main.mask = B.region_mask;
@@ -1138,13 +1200,15 @@ void Engine::recog_enqueue(PageBatch& B) {
     TTR_HIP_CHECK(hipMemcpyAsync(h_ids[sl].p, ids_dev.p, block, hipMemcpyDeviceToHost, stream));   // ids, prob and conf in one copy
   } else {
     if (B.mark_min && !B.regions) marks_enqueue(B, sl);                // selection marks: a batch of pages without words - boxes only - is a legitimate form
+    if (B.bc_min && !B.regions) barcodes_enqueue(B, sl);               // barcodes: likewise - a label is a legitimate page
     TTR_HIP_CHECK(hipEventRecord(evr[sl][1], stream));
     TTR_HIP_CHECK(hipEventRecord(evr[sl][2], stream));
   }
   // the side blocks that are not copied inside their layer's own enqueue function, behind the standard block's copy: each a no-op unless its layer armed it
   // (h_wide: the cuts, the profile stays on the device; h_tab_ink: the tables / marks pass's ink records; h_mark: there for a batch without words too)
   const std::pair<SideCopy*, const DevBuf*> tail[] = {{&h_orient, &orient_side}, {&h_alts, &alts_side}, {&h_lex, &lex_side}, {&h_pat_logp, &pat_logp_dev}, {&h_wide, &wide_side},
-                                                      {&h_curve, &curve_side}, {&h_tab, &tab_side}, {&h_tab_ink, &tab_ink_rec}, {&h_mark, &mark_side}};
+                                                      {&h_curve, &curve_side}, {&h_tab, &tab_side}, {&h_tab_ink, &tab_ink_rec}, {&h_mark, &mark_side},
+                                                      {&h_barcode, &bc_side}};
   for (const auto& t : tail) t.first->fetch(sl, *t.second, stream);
   if (comm && B.cap > 0) {   // the payload: the output block of cap rows per rank - [cap][26] ids | [cap][26] prob | [cap] conf -, straight from the recogniser's device buffer
     gath_dev[sl].ensure(block * comm->world);
@@ -1178,6 +1242,7 @@ void Engine::finish(PageBatch& B, std::vector<Result>& results) {
   V.orient = h_orient.view<int32_t>(B.slot); V.lines = h_lines.view<int32_t>(B.slot); V.blocks = h_blocks.view<int32_t>(B.slot); V.chars = h_chars.view<int32_t>(B.slot);
   V.alts = h_alts.view<int32_t>(B.slot); V.lex = h_lex.view<int32_t>(B.slot); V.pat_logp = h_pat_logp.view<float>(B.slot); V.wide_cuts = h_wide.view<int32_t>(B.slot);
   V.curve = h_curve.view<int32_t>(B.slot); V.tab = h_tab.view<int32_t>(B.slot); V.tab_ink = h_tab_ink.view<InkRec>(B.slot); V.mark = h_mark.view<int32_t>(B.slot);
+  V.barcode = h_barcode.view<int32_t>(B.slot);
   decode_pages(B, rec_rows(h_ids[B.slot].p, B.rows), V, results);
   for (Result& r : results) r.tiles = B.tiles;                                                  // tiled pages: the tiles each page's detector ran as (0: off)
   host_us[5] = (float)(th3 - th2); host_us[6] = (float)(th4 - th3); host_us[7] = (float)(now_us() - th4);
@@ -1246,8 +1311,8 @@ void Engine::decode_records(const PageCtx& at, Result& r) const {
   } else if (deskew_M && B.regions) {   // a region call: the caller's quadrilaterals are in the caller's frame
     r.skew_on = 1; r.skew = DeskewRec{0, 0, 65536, 0, B.pages[(size_t)pg].w, B.pages[(size_t)pg].h, 0, 0, 0, 0};
   }
-  if (B.ink_radius && !B.regions && ((B.tab_min_len && N > 0) || B.mark_min || B.dsk_M)) {   // local ink: the page's record - the tables or marks pass's when one ran, else the deskew pass's - checked before anything is built on it
-    const bool from_tab = (B.tab_min_len && N > 0) || B.mark_min;
+  if (B.ink_radius && !B.regions && ((B.tab_min_len && N > 0) || B.mark_min || B.bc_min || B.dsk_M)) {   // local ink: the page's record - the tables, marks or barcodes pass's when one ran, else the deskew pass's - checked before anything is built on it
+    const bool from_tab = (B.tab_min_len && N > 0) || B.mark_min || B.bc_min;
     if (from_tab ? !V.tab_ink : B.dsk_ink_recs.size() != (size_t)n) throw std::runtime_error("local ink: the batch carries no records");
     const InkRec k = from_tab ? V.tab_ink[pg] : B.dsk_ink_recs[(size_t)pg];
     std::string why;
@@ -1301,6 +1366,25 @@ void Engine::decode_marks(const PageCtx& at, Result& r) const {
     for (int k = 0; k < cnt; ++k) {
       if (mi[k] < -1 || mi[k] >= ms[1]) throw std::runtime_error("marks: word " + std::to_string(k) + " of page " + std::to_string(pg) + " names a mark that does not exist");
       r.item_mark[(size_t)k] = mi[k];
+    }
+  }
+}
+
+void Engine::decode_barcodes(const PageCtx& at, Result& r) const {
+  const auto& [B, rows, V, pg, c0, cnt] = at; const int n = B.n;
+  if (B.bc_min && !B.regions) {   // barcodes: the page's side block and its items' barcodes, checked before anything is built on them
+    if (!V.barcode) throw std::runtime_error("barcodes: the batch carries no side block");
+    const int32_t* bs = V.barcode + (size_t)pg * kBcSideInts;
+    const int32_t* bi = V.barcode + (size_t)n * kBcSideInts + (size_t)c0;
+    std::string why;
+    if (!barcodes_side_valid(bs, B.pages[(size_t)pg].h, B.pages[(size_t)pg].w, B.bc_min, B.bc_sym, &why))
+      throw std::runtime_error("barcodes: the side block of page " + std::to_string(pg) + " holds " + why);
+    r.barcode_mode = bs[0];
+    r.barcodes.assign(bs + kBcHdr, bs + kBcHdr + (size_t)kBcRec * bs[1]);
+    r.item_barcode.assign((size_t)cnt, -1);
+    for (int k = 0; k < cnt; ++k) {
+      if (bi[k] < -1 || bi[k] >= bs[1]) throw std::runtime_error("barcodes: word " + std::to_string(k) + " of page " + std::to_string(pg) + " names a barcode that does not exist");
+      r.item_barcode[(size_t)k] = bi[k];
     }
   }
 }
@@ -1440,7 +1524,7 @@ void Engine::decode_pages(const PageBatch& B, const RecRows& rows, const SideVie
   auto decode_page = [&](int pg) {
     const PageCtx at{B, rows, views, pg, first[pg], first[pg + 1] - first[pg]};
     Result& r = results[pg];
-    decode_words(at, r); decode_records(at, r); decode_tables(at, r); decode_marks(at, r); decode_curved(at, r); decode_wide(at, r);
+    decode_words(at, r); decode_records(at, r); decode_tables(at, r); decode_marks(at, r); decode_barcodes(at, r); decode_curved(at, r); decode_wide(at, r);
     decode_lines(at, r); decode_blocks(at, r); decode_chars(at, r);
   };
   // pages decode independently
@@ -1696,6 +1780,7 @@ void Engine::run_pages_sharded(const uint8_t* d_pages, int n, int h, int w, std:
   if (curved) throw std::runtime_error("latency mode does not support curved words: ttr_engine_set_curved(e, 0) first");
   if (tables_min_len) throw std::runtime_error("latency mode does not support tables: ttr_engine_set_tables(e, 0, 0) first");
   if (marks_min) throw std::runtime_error("latency mode does not support selection marks: ttr_engine_set_marks(e, 0, 0, 0, 0) first");
+  if (barcodes_min) throw std::runtime_error("latency mode does not support barcodes: ttr_engine_set_barcodes(e, 0, 0, 0) first");
   if (tiled) throw std::runtime_error("latency mode does not support tiled pages: ttr_engine_set_tiled(e, 0) first");
   if (deskew_M) throw std::runtime_error("latency mode does not support deskew: ttr_engine_set_deskew(e, 0, 0, 0) first");
   if (!comm) throw std::runtime_error("latency mode needs a communicator (ttr_engine_attach_comm)");

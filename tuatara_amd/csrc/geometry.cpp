@@ -6,6 +6,7 @@
 #include "tables_rule.h"
 #include "deskew_rule.h"
 #include "ink_rule.h"
+#include "barcodes_rule.h"
 #include "marks_rule.h"
 
 #include <algorithm>
@@ -1631,6 +1632,111 @@ bool marks_side_valid(const int32_t* s, int h, int w, int fill, int items, std::
     if (r[10] != (256 * r[8] >= fill * r[9] ? 1 : 0)) return bad("a state that is not the rule's");
     if (r[11] < -1 || r[11] >= items) return bad("a label that is no item");
     if (m && (r[1] < r[-kMarkRec + 1] || (r[1] == r[-kMarkRec + 1] && r[0] <= r[-kMarkRec]))) return bad("marks out of (y, x) order");
+  }
+  return true;
+}
+
+// ---- barcodes (DESIGN.md "Barcodes"): the host rule; integers only.  Every step is barcodes_rule.h's.
+int barcodes_from_bits(const uint64_t* bits, const uint64_t* bitsT, int h, int w, int min_lines, int symbologies, int32_t* side, int32_t* hits_out, int32_t* cnt_out) {
+  if (!bits || !bitsT || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || !barcodes_args_ok(min_lines, 128, symbologies)) throw std::runtime_error("barcodes_from_bits: bad argument");
+  static const std::vector<uint8_t> tab = [] { std::vector<uint8_t> t(kBcTableBytes); bc_tables_clear(t.data(), 0, 1); bc_tables_fill(t.data(), 0, 1); return t; }();
+  std::fill(side, side + kBcSideInts, 0);
+  const int nwx = (w + 63) / 64, nwy = (h + 63) / 64, lines = h + w;
+  std::vector<int32_t> hits((size_t)lines * 2 * kBcLineHits * kBcHit, 0), cnt((size_t)lines * 2 * kBcCnt, 0);
+  // 2 - 6: every line, both readings, the candidates in position order
+  for (int L = 0; L < lines; ++L) {
+    const uint64_t* line = L < h ? bits + (size_t)L * nwx : bitsT + (size_t)(L - h) * nwy;
+    const int len = L < h ? w : h, nw = L < h ? nwx : nwy;
+    for (int rev = 0; rev < 2; ++rev) {
+      int32_t* c = cnt.data() + (size_t)kBcCnt * (2 * L + rev);
+      int32_t* slots = hits.data() + (size_t)(2 * L + rev) * kBcLineHits * kBcHit;
+      for (int k = 0; k < nw; ++k)
+        for (uint64_t m = bc_candidates(line, nw, k, rev); m; m &= m - 1) {
+          const int x = 64 * k + mark_ctz(m), u0 = rev ? len - 1 - x : x;
+          int starts = 0;
+          ++c[2];
+          const bool hit = bc_decode(tab.data(), line, len, rev, u0, symbologies, c[0] < kBcLineHits ? slots + (size_t)c[0] * kBcHit : nullptr, &starts);
+          c[3] += starts;
+          if (hit) { if (c[0] < kBcLineHits) { slots[(size_t)c[0] * kBcHit + 6] = -1; slots[(size_t)c[0] * kBcHit + 7] = -1; ++c[0]; } else ++c[1]; }
+          else if (c[0] < kBcLineHits) std::fill(slots + (size_t)c[0] * kBcHit, slots + (size_t)(c[0] + 1) * kBcHit, 0);   // (a text begun and given up)
+        }
+      side[2] += c[2]; side[3] += c[3]; side[4] += c[0]; side[5] += c[1];
+    }
+  }
+  // 7: every hit's partner, then its chain's first hit
+  auto kind = [&](int L, int& L0, int& L1) { L0 = L < h ? 0 : h; L1 = L < h ? h : lines; };
+  for (int L = 0; L < lines; ++L)
+    for (int rev = 0; rev < 2; ++rev)
+      for (int s = 0; s < cnt[(size_t)kBcCnt * (2 * L + rev)]; ++s) {
+        int L0, L1; kind(L, L0, L1);
+        hits[(size_t)((2 * L + rev) * kBcLineHits + s) * kBcHit + 6] = bc_pred(hits.data(), cnt.data(), L0, L, rev, s);
+      }
+  for (int L = 0; L < lines; ++L)
+    for (int rev = 0; rev < 2; ++rev)
+      for (int s = 0; s < cnt[(size_t)kBcCnt * (2 * L + rev)]; ++s) {
+        int id = (2 * L + rev) * kBcLineHits + s, root = id;
+        while (hits[(size_t)root * kBcHit + 6] >= 0) root = hits[(size_t)root * kBcHit + 6];
+        hits[(size_t)id * kBcHit + 7] = root;
+      }
+  // 7 - 8: the chains of min_lines hits or more, sorted
+  std::vector<std::pair<int, std::vector<int32_t>>> found;
+  for (int L = 0; L < lines; ++L)
+    for (int rev = 0; rev < 2; ++rev)
+      for (int s = 0; s < cnt[(size_t)kBcCnt * (2 * L + rev)]; ++s) {
+        const int id = (2 * L + rev) * kBcLineHits + s;
+        if (hits[(size_t)id * kBcHit + 6] >= 0) continue;
+        int L0, L1; kind(L, L0, L1);
+        std::vector<int32_t> rec(kBcRec, 0);
+        if (bc_chain(hits.data(), cnt.data(), L0, L1, L, rev, s, L >= h, rec.data()) >= min_lines) found.emplace_back(id, std::move(rec)); else ++side[6];
+      }
+  if (hits_out) std::copy(hits.begin(), hits.end(), hits_out);
+  if (cnt_out) std::copy(cnt.begin(), cnt.end(), cnt_out);
+  if ((int)found.size() > kBcCap) { side[0] = -7; return -7; }
+  std::sort(found.begin(), found.end(), [](const auto& a, const auto& b) { return bc_before(a.second.data(), a.first, b.second.data(), b.first); });
+  for (size_t m = 0; m < found.size(); ++m) std::copy(found[m].second.begin(), found[m].second.end(), side + kBcHdr + kBcRec * m);
+  side[0] = 1; side[1] = (int)found.size();
+  return 1;
+}
+
+void barcodes_items(const int32_t* side, const int32_t* centres, int n, int32_t* item_barcode) {
+  for (int i = 0; i < n; ++i) item_barcode[i] = bc_item(side, centres[2 * (size_t)i], centres[2 * (size_t)i + 1]);
+}
+
+int barcodes_from_page(const uint8_t* image, int h, int w, int stride, int min_lines, int ink, int symbologies, int32_t* side, int32_t* hits, int32_t* cnt) {
+  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !barcodes_args_ok(min_lines, ink, symbologies))
+    throw std::runtime_error("barcodes_from_page: bad argument");
+  std::vector<uint64_t> bits(tables_bitmap_words(h, w)), bitsT(tables_bitmap_words(w, h));
+  tables_ink(image, h, w, stride, ink, bits.data());
+  marks_transpose(bits.data(), h, w, bitsT.data());
+  return barcodes_from_bits(bits.data(), bitsT.data(), h, w, min_lines, symbologies, side, hits, cnt);
+}
+
+int barcodes_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_lines, int symbologies, int radius, int drop, int polarity, int32_t* side) {
+  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !barcodes_args_ok(min_lines, 128, symbologies) || !ink_args_ok(radius, drop, polarity))
+    throw std::runtime_error("barcodes_from_page_ink: bad argument");
+  std::vector<uint64_t> bits(tables_bitmap_words(h, w)), bitsT(tables_bitmap_words(w, h));
+  ink_from_page(image, h, w, stride, radius, drop, polarity, bits.data(), bitsT.data(), nullptr);
+  return barcodes_from_bits(bits.data(), bitsT.data(), h, w, min_lines, symbologies, side);
+}
+
+bool barcodes_side_valid(const int32_t* s, int h, int w, int min_lines, int symbologies, std::string* why) {
+  auto bad = [&](const char* m) { if (why) *why = m; return false; };
+  if (s[0] != 1 && s[0] != -7) return bad("a mode that is neither 1 nor -7");
+  if (s[1] < 0 || s[1] > kBcCap) return bad("a barcode count beyond the cap");
+  if (s[0] == -7 && s[1] != 0) return bad("barcodes on a page beyond the cap");
+  for (int i = 2; i < 7; ++i) if (s[i] < 0) return bad("a negative counter");
+  if (s[7] != 0 || s[3] > 2 * s[2] || s[4] > s[2]) return bad("counters that do not match each other");
+  for (int m = 0; m < s[1]; ++m) {
+    const int32_t* r = s + kBcHdr + kBcRec * m;
+    if (r[0] < 0 || r[1] < 0 || r[2] >= w || r[3] >= h || r[0] > r[2] || r[1] > r[3]) return bad("a box outside the page");
+    if ((r[4] != 1 && r[4] != 2) || !(symbologies & r[4])) return bad("a symbology that was not asked for");
+    if (r[5] < 0 || r[5] > 3) return bad("a direction outside 0..3");
+    if (r[6] < min_lines || r[7] < 64) return bad("a line count below min_lines or a module below one pixel");
+    if (r[8] & ~kBcFlagsMask || (r[4] == 2 && r[8])) return bad("flags beyond the mask");
+    if (r[9] < 0 || r[9] > kBcText || r[10] != 0 || r[11] != 0) return bad("a text length beyond 48");
+    const uint8_t* t = reinterpret_cast<const uint8_t*>(r + 12);
+    for (int i = r[9]; i < kBcText; ++i) if (t[i]) return bad("text bytes beyond its length");
+    if (m && bc_before(r, 1, r - kBcRec, 0)) return bad("barcodes out of (y0, x0, dir) order");
   }
   return true;
 }

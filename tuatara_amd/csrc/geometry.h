@@ -214,6 +214,22 @@ int marks_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_
 // receives the reason.
 bool marks_side_valid(const int32_t* side, int h, int w, int fill, int items, std::string* why = nullptr);
 
+// Barcodes (ttr_engine_set_barcodes; DESIGN.md "Barcodes").  Code 128 and Code 39 are read off single lines of the ink bitmaps in all four directions, and the
+// lines' hits chained into barcodes.  Every step lives in barcodes_rule.h, shared with barcode_scan_kernel and barcode_page_kernel (barcodes.hip); the side
+// block's layout (kBcSideInts int32) and the hits' are described there.  min_lines 4..256, ink 1..255, symbologies 1..3.
+// steps 2 - 8 behind ready bitmaps: side receives the block; hits (may be null) [(h + w) 2 8][20] the lines' hit slots and cnt (may be null) [(h + w) 2][4]
+// their counters, rows first, as the scan kernel leaves them.  Returns the mode: 1, or -7 for a page of more than 64 barcodes (the block then holds the header alone).
+int barcodes_from_bits(const uint64_t* bits, const uint64_t* bitsT, int h, int w, int min_lines, int symbologies, int32_t* side, int32_t* hits = nullptr, int32_t* cnt = nullptr);
+// step 9: item_barcode [n] from the centres [n][2] (tables_word_centre)
+void barcodes_items(const int32_t* side, const int32_t* centres, int n, int32_t* item_barcode);
+// 1 - 8 on one page under the fixed ink rule, and under the local rule in the place of `ink`
+int barcodes_from_page(const uint8_t* image, int h, int w, int stride, int min_lines, int ink, int symbologies, int32_t* side, int32_t* hits = nullptr, int32_t* cnt = nullptr);
+int barcodes_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_lines, int symbologies, int radius, int drop, int polarity, int32_t* side);
+// what decode_pages accepts from the device: a legal mode, a count within the cap, boxes inside the h x w page, (y0, x0, dir) order, symbology 1 or 2 and one
+// that was asked for, dir 0..3, lines >= min_lines, flags within the mask, len <= 48 and zero bytes beyond it, counters that are not negative.  why (may be
+// null) receives the reason.
+bool barcodes_side_valid(const int32_t* side, int h, int w, int min_lines, int symbologies, std::string* why = nullptr);
+
 // One CCL candidate as the GPU reports it (post_ops.hip): stats of the combined-map
 // component and the per-row x extremes of its link-masked pixels.
 struct Component {

@@ -418,6 +418,22 @@ void launch_mark_cand(const uint64_t* bits, const uint64_t* bitsT, int h, int w,
 // mark_page_kernel: steps 6 - 7, one workgroup per page.  centres int32 [N][2] and first int32 [pages + 1] as launch_table_grid takes them; side int32
 // [pages][kMarkSideInts] (marks_rule.h); item_mark int32 [N]
 void launch_mark_page(const int* cand, const int* counts, int pages, int Hcap, const int* centres, const int* first, int* side, int* item_mark, hipStream_t s);
+
+// ---- barcodes.hip (DESIGN.md "Barcodes")
+// The line pass works on bands of 32 lines; a page's lines are its Hcap rows, then its Wcap columns.  Every line has, for either reading, 8 hit slots of 20
+// int32 and 4 counters (barcodes_rule.h): 1312 bytes a line, so that a line's hits have fixed places and no atomic is needed.
+constexpr int kBcBandLines = 32;
+inline int barcodes_bands(int Hcap, int Wcap) { return (Hcap + Wcap + kBcBandLines - 1) / kBcBandLines; }
+inline size_t barcodes_hit_ints(int Hcap, int Wcap, int pages) { return (size_t)pages * (size_t)(Hcap + Wcap) * 2 * 8 * 20; }
+inline size_t barcodes_count_ints(int Hcap, int Wcap, int pages) { return (size_t)pages * (size_t)(Hcap + Wcap) * 2 * 4; }
+// barcode_scan_kernel: steps 2 - 6 on every page, pages x bands.  bits / bitsT: the bitmaps of a pixel pass of the same launch geometry (table null: h / w of a
+// uniform batch, else the device page table); hits int32 [pages][Hcap + Wcap][2][8][20] and cnt int32 [pages][Hcap + Wcap][2][4] (workspaces)
+void launch_barcode_scan(const uint64_t* bits, const uint64_t* bitsT, int h, int w, const PageRow* table, int pages, int Hcap, int Wcap, int symbologies, int* hits, int* cnt,
+                         hipStream_t s);
+// barcode_page_kernel: steps 7 - 9, one workgroup per page (it writes the hits' chain fields).  centres int32 [N][2] and first int32 [pages + 1] as
+// launch_table_grid takes them; side int32 [pages][kBcSideInts] (barcodes_rule.h); item_barcode int32 [N]
+void launch_barcode_page(int* hits, const int* cnt, int h, int w, const PageRow* table, int pages, int Hcap, int Wcap, int min_lines, const int* centres, const int* first,
+                         int* side, int* item_barcode, hipStream_t s);
 // get_detected_boxes' per-component tail on the GPU (tuatara.cpp:162-179: niter, ROI, dilation, findNonZero + minAreaRect): one lane per candidate, geometry.cpp's
 // arithmetic step for step (float32 calipers, double where OpenCV is double) -> CclBuffers::rects.  After launch_ccl on the same stream.
 void launch_ccl_rects(const CclBuffers& b, int pages, int H, int W, hipStream_t s);

@@ -67,6 +67,8 @@ thread_local int g_call_tables = 0, g_call_tables_ink = 128;   // set_tables(): 
 thread_local std::vector<TableGrid> g_call_table_out;          // last_call_tables()
 thread_local int g_call_marks = 0, g_call_marks_max = 64, g_call_marks_fill = 24, g_call_marks_ink = 128;   // set_marks(): this thread's calls, 0 = off (then TUATARA_MARKS decides)
 thread_local std::vector<SelectionMark> g_call_mark_out;       // last_call_marks()
+thread_local int g_call_barcodes = 0, g_call_barcodes_ink = 128, g_call_barcodes_sym = 3;   // set_barcodes(): this thread's calls, 0 = off (then TUATARA_BARCODES decides)
+thread_local std::vector<Barcode> g_call_barcode_out;          // last_call_barcodes()
 thread_local int g_call_ink = 0, g_call_ink_drop = 38, g_call_ink_polarity = 2;   // set_local_ink(): this thread's calls, 0 = off (then TUATARA_LOCAL_INK decides)
 thread_local int g_call_deskew = 0, g_call_deskew_gain = 288, g_call_deskew_ink = 128;   // set_deskew(): this thread's calls, 0 = off (then TUATARA_DESKEW decides)
 thread_local PageSkew g_call_skew_out;                         // last_call_skew()
@@ -77,6 +79,7 @@ struct CharsetScope {
   bool alts_set = false, lex_set = false, pattern_set = false, wide_set = false, best_set = false, curved_set = false, fuzzy_set = false, tiled_set = false;
   bool tables_set = false;
   bool marks_set = false;
+  bool barcodes_set = false;
   bool deskew_set = false;
   bool ink_set = false;
   CharsetScope(ttr_engine* e_, std::string allow, std::string deny, int alts = 0, const std::vector<std::string>* words = nullptr, int lex_m = 0,
@@ -134,6 +137,13 @@ struct CharsetScope {
       if (ttr_engine_set_marks(e, mk, g_call_marks_max, g_call_marks_fill, g_call_marks_ink) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
       marks_set = true;
     }
+    int bc = g_call_barcodes;
+    if (bc == 0) if (const char* p = std::getenv("TUATARA_BARCODES")) bc = std::string(p) == "1" ? 8 : std::atoi(p);
+    g_call_barcode_out.clear();
+    if (bc != 0) {   // barcodes (DESIGN.md "Barcodes"): the three parameters for the call, like the set
+      if (ttr_engine_set_barcodes(e, bc, g_call_barcodes_ink, g_call_barcodes_sym) != 0) { g_call_error = ttr_last_error(); std::cerr << "tuatara: " << g_call_error << std::endl; ok = false; return; }
+      barcodes_set = true;
+    }
     int dsk = g_call_deskew;
     if (dsk == 0) if (const char* p = std::getenv("TUATARA_DESKEW")) dsk = std::string(p) == "1" ? 64 : std::atoi(p);
     g_call_skew_out = PageSkew();
@@ -175,6 +185,7 @@ struct CharsetScope {
     if (tiled_set) ttr_engine_set_tiled(e, 0);
     if (tables_set) ttr_engine_set_tables(e, 0, 0);
     if (marks_set) ttr_engine_set_marks(e, 0, 0, 0, 0);
+    if (barcodes_set) ttr_engine_set_barcodes(e, 0, 0, 0);
     if (deskew_set) ttr_engine_set_deskew(e, 0, 0, 0);
     if (ink_set) ttr_engine_set_ink(e, 0, 0, 0);
     if (set) ttr_engine_set_charset(e, nullptr, nullptr);
@@ -268,6 +279,8 @@ void fill(OutputItemEx& o, const ttr_result* r, int i) {
   o.cell = ic ? ic[i] : -1;
   const int32_t* im = ttr_result_item_mark(r);
   o.mark = im ? im[i] : -1;
+  const int32_t* ib = ttr_result_item_barcode(r);
+  o.barcode = ib ? ib[i] : -1;
   o.curved = false; o.outline.clear();
   if (const int32_t* cv = ttr_result_curved(r)) {
     const float* ol = ttr_result_outlines(r);
@@ -336,6 +349,16 @@ std::vector<Item> run_one(const uint8_t* image, int rows, int cols, std::ptrdiff
       s.inked = q[8]; s.area = q[9]; s.selected = q[10] != 0; s.label = q[11];
       if (s.label >= 0 && (size_t)s.label < out.size()) s.text = out[(size_t)s.label].text;
       g_call_mark_out.push_back(std::move(s));
+    }
+  }
+  if (const int32_t* bc = ttr_result_barcodes(r)) {   // barcodes: every barcode of the page (last_call_barcodes())
+    for (int m = 0; m < ttr_result_barcode_count(r); ++m) {
+      const int32_t* q = bc + 24 * (size_t)m;
+      Barcode b;
+      for (int k = 0; k < 4; ++k) b.box[k] = q[k];
+      b.symbology = q[4]; b.direction = q[5]; b.lines = q[6]; b.module = (double)q[7] / 64.0; b.flags = q[8]; b.gs1 = (q[8] & 1) != 0;
+      b.data.assign(reinterpret_cast<const char*>(q + 12), (size_t)q[9]);
+      g_call_barcode_out.push_back(std::move(b));
     }
   }
   if (const int32_t* tb = ttr_result_tables(r)) {   // tables: every table as rows x cols strings (last_call_tables())
@@ -587,6 +610,9 @@ int tiled() { return g_call_tiled; }
 void set_marks(int min_side, int max_side, int fill, int ink) { g_call_marks = min_side; g_call_marks_max = max_side; g_call_marks_fill = fill; g_call_marks_ink = ink; }
 int marks() { return g_call_marks; }
 std::vector<SelectionMark> last_call_marks() { return g_call_mark_out; }
+void set_barcodes(int min_lines, int ink, int symbologies) { g_call_barcodes = min_lines; g_call_barcodes_ink = ink; g_call_barcodes_sym = symbologies; }
+int barcodes() { return g_call_barcodes; }
+std::vector<Barcode> last_call_barcodes() { return g_call_barcode_out; }
 void set_tables(int min_len, int ink) { g_call_tables = min_len; g_call_tables_ink = ink; }
 int tables() { return g_call_tables; }
 std::vector<TableGrid> last_call_tables() { return g_call_table_out; }

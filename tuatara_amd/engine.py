@@ -323,6 +323,17 @@ SYMBOLS = [
     ("ttr_marks_from_page_ink", _I, [_PU8, _I, _I, _I, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI]),
     ("ttr_marks_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI]),
     ("ttr_dbg_marks", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, _I, _I, _PI, _PI, _PI, _PI]),
+    ("ttr_engine_set_barcodes", _I, [_VP, _I, _I, _I]),
+    ("ttr_engine_barcodes", _I, [_VP, _PI, _PI]),
+    ("ttr_result_barcode_mode", _I, [_VP]),
+    ("ttr_result_barcode_count", _I, [_VP]),
+    ("ttr_result_barcodes", _PI, [_VP]),
+    ("ttr_result_item_barcode", _PI, [_VP]),
+    ("ttr_results_gather_barcodes", _I, [C.POINTER(_VP), _I, _PI]),
+    ("ttr_barcodes_from_page", _I, [_PU8, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI, _PI, _PI]),
+    ("ttr_barcodes_from_page_ink", _I, [_PU8, _I, _I, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI]),
+    ("ttr_barcodes_page", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI]),
+    ("ttr_dbg_barcodes", _I, [_VP, _PU8, _I, _I, _I, _I, _I, _I, _I, _I, _PI, _PI, _PI]),
     ("ttr_dbg_page_ink_passes", C.c_int64, [_VP]),
     ("ttr_tables_from_page_ink", _I, [_PU8, _I, _I, _I, _I, _I, _I, _I, _PF, _I, _PI, _PI, _PI, _PI, _PI, _PI, _PI, _PI]),
     ("ttr_deskew_from_page_ink", _I, [_PU8, _I, _I, _I, _I, _I, _I, _I, _I, _PU8, C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -1142,6 +1153,78 @@ def mark_dicts(marks, texts=None) -> list:
     return out
 
 
+BARCODES_MIN_LINES, BARCODES_INK, BARCODES_SYMBOLOGIES = 8, 128, 3   # what barcodes=True means (DESIGN.md "Barcodes": none of them has been tuned on documents)
+BARCODE_FIELDS = ("x0", "y0", "x1", "y1", "symbology", "dir", "lines", "module64", "flags", "len")   # then two zeros and 48 bytes of text
+BARCODE_SYMBOLOGIES = {1: "code128", 2: "code39"}
+BARCODE_DIRECTIONS = ("left-to-right", "top-to-bottom", "right-to-left", "bottom-to-top")
+
+
+def _barcodes_arg(barcodes):
+    """False / None / 0 -> off; True -> the defaults; (min_lines, ink, symbologies) or a bare min_lines otherwise"""
+    if barcodes is None or barcodes is False or (isinstance(barcodes, int) and not isinstance(barcodes, bool) and barcodes == 0):
+        return 0, BARCODES_INK, BARCODES_SYMBOLOGIES
+    if barcodes is True:
+        return BARCODES_MIN_LINES, BARCODES_INK, BARCODES_SYMBOLOGIES
+    if isinstance(barcodes, (tuple, list)) and len(barcodes) == 3:
+        return tuple(int(v) for v in barcodes)
+    if isinstance(barcodes, int):
+        return int(barcodes), BARCODES_INK, BARCODES_SYMBOLOGIES
+    raise EngineError("barcodes must be False, True or (min_lines, ink, symbologies)")
+
+
+def _barcodes_call(fn, image, quads, params, row_stride=0, raw=False):
+    """the shared body of barcodes_from_page and Engine.barcodes_page: fn(image..., params..., quads, outputs...) -> the dict both return"""
+    image = np.asarray(image, dtype=np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise RuntimeError("Input array should have 3 dimensions")
+    if not row_stride:
+        image = np.ascontiguousarray(image)
+    q = np.zeros((0, 8), np.float32) if quads is None else np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
+    nq, lines = len(q), image.shape[0] + image.shape[1]
+    mode, counts, recs, ib = np.zeros(1, np.int32), np.zeros(6, np.int32), np.zeros((64, 24), np.int32), np.full(max(nq, 1), -1, np.int32)
+    extra = [np.zeros((lines, 2, 8, 20), np.int32), np.zeros((lines, 2, 4), np.int32)] if raw else []
+    fn(_u8(image), image.shape[0], image.shape[1], int(row_stride) or image.shape[1] * 3, *[int(v) for v in params], _f(q), nq, _i(mode), _i(counts), _i(recs), _i(ib),
+       *[_i(a) for a in extra])
+    out = {"mode": int(mode[0]), "records": recs[:counts[0]].copy(), "item_barcode": ib[:nq].copy(), "counts": [int(v) for v in counts]}
+    if raw:
+        out["hits"], out["line_counts"] = extra
+    out["barcodes"] = barcode_dicts(out["records"])
+    return out
+
+
+def barcodes_from_page(image, quads=None, min_lines: int = BARCODES_MIN_LINES, ink: int = BARCODES_INK, symbologies: int = BARCODES_SYMBOLOGIES, row_stride: int = 0,
+                       raw: bool = False) -> dict:
+    """The barcode rule on the host (ttr_barcodes_from_page, no GPU; DESIGN.md "Barcodes"): a host image u8 [H, W, 3] (row_stride: the bytes from row to row of
+    a view into a wider buffer) and quads f32 [nq, 8] -> {"mode" (1, or -7 beyond 64 barcodes), "records" i32 [n, 24] (BARCODE_FIELDS, then the text),
+    "barcodes" (barcode_dicts), "item_barcode" i32 [nq], "counts" [6] = barcodes, candidates examined, start patterns matched, hits kept, hits dropped, chains
+    below min_lines}; raw adds "hits" i32 [H + W, 2, 8, 20] and "line_counts" i32 [H + W, 2, 4], the lines' raw hits."""
+    lib = load()
+
+    def fn(*a):
+        _lib_check(lib.ttr_barcodes_from_page(*a) if raw else lib.ttr_barcodes_from_page(*a, None, None))
+    return _barcodes_call(fn, image, quads, (min_lines, ink, symbologies), row_stride, raw)
+
+
+def barcodes_from_page_ink(image, quads=None, min_lines: int = BARCODES_MIN_LINES, symbologies: int = BARCODES_SYMBOLOGIES, local_ink=True, row_stride: int = 0) -> dict:
+    """barcodes_from_page under the local ink rule (ttr_barcodes_from_page_ink): local_ink = True or (radius, drop, polarity) in the place of ink"""
+    lib = load()
+    r, d, p = _local_ink_arg(local_ink)
+
+    def fn(*a):
+        _lib_check(lib.ttr_barcodes_from_page_ink(*a))
+    return _barcodes_call(fn, image, quads, (min_lines, symbologies, r, d, p), row_stride)
+
+
+def barcode_dicts(records) -> list:
+    """barcode records i32 [n, 24] -> [{"box", "symbology", "direction", "text", "data", "lines", "module", "gs1", "flags"}] (text: the data as latin-1)"""
+    out = []
+    for r in np.ascontiguousarray(records, np.int32).reshape(-1, 24):
+        data = r[12:].tobytes()[:int(r[9])]
+        out.append({"box": [int(v) for v in r[0:4]], "symbology": BARCODE_SYMBOLOGIES.get(int(r[4]), "?"), "direction": int(r[5]), "text": data.decode("latin1"),
+                    "data": data, "lines": int(r[6]), "module": float(r[7]) / 64.0, "gs1": bool(r[8] & 1), "flags": int(r[8])})
+    return out
+
+
 DESKEW_MAX_SLOPE, DESKEW_GAIN, DESKEW_INK = 64, 288, 128   # what deskew=True means (DESIGN.md "Deskew": none of them has been tuned on documents)
 
 
@@ -1340,7 +1423,7 @@ class PageResult(collections.abc.Sequence):
     pass's - or None when no pass of the page ran under it.  Selection marks (Engine.set_marks; DESIGN.md "Selection marks"): `mark_mode` (1, or -6 beyond 512
     marks; 0 = off), `mark_recs` i32 [n, 12] (MARK_FIELDS) and `item_mark` i32 [items], None when off; `marks` the list of {"box", "interior", "selected",
     "fill", "label", "text"}; every dict gains "mark"; a page without items has its marks too."""
-    __slots__ = ("skew", "quad_page", "ink", "mark_mode", "mark_recs", "item_mark",
+    __slots__ = ("skew", "quad_page", "ink", "mark_mode", "mark_recs", "item_mark", "barcode_mode", "barcode_recs", "item_barcode",
                  "table_mode", "rulings", "table_rects", "table_lines", "cells", "item_table", "item_cell", "cell_texts",
                  "texts", "bbox", "ids", "quad", "conf", "prob", "with_conf", "orient", "orient_conf", "page_orient",
                  "line", "word", "order", "line_first", "line_bbox",
@@ -1357,8 +1440,11 @@ class PageResult(collections.abc.Sequence):
                  piece_first=None, piece_ids=None, piece_prob=None, piece_conf=None, piece_quad=None, piece_cuts=None,
                  curved=None, outline=None, spine_knots=None, lex_edits=None, lex_band=-1, tiles=0,
                  table_mode=0, rulings=None, table_rects=None, table_lines=None, cells=None, item_table=None, item_cell=None, cell_texts=None, skew=None, quad_page=None, ink=None,
-                 mark_mode=0, mark_recs=None, item_mark=None):
+                 mark_mode=0, mark_recs=None, item_mark=None, barcode_mode=0, barcode_recs=None, item_barcode=None):
         self.tiles = tiles
+        # barcodes (Engine.set_barcodes; DESIGN.md "Barcodes"): barcode_mode 1, or -7 beyond 64 barcodes, 0 = off; barcode_recs i32 [n, 24] (BARCODE_FIELDS, then
+        # the text), in the upright page's frame under deskew; item_barcode i32 [items] the barcode every item's centre lies in (-1 = none); None when off
+        self.barcode_mode, self.barcode_recs, self.item_barcode = barcode_mode, barcode_recs, item_barcode
         # selection marks (Engine.set_marks; DESIGN.md "Selection marks"): mark_mode 1, or -6 beyond 512 marks, 0 = off; mark_recs i32 [n, 12] (MARK_FIELDS), in
         # the upright page's frame under deskew; item_mark i32 [items] the mark every item's centre lies in (-1 = none); None when marks are off
         self.mark_mode, self.mark_recs, self.item_mark = mark_mode, mark_recs, item_mark
@@ -1427,6 +1513,8 @@ class PageResult(collections.abc.Sequence):
             d["table"], d["cell"] = int(self.item_table[j]), int(self.item_cell[j])
         if self.item_mark is not None:
             d["mark"] = int(self.item_mark[j])
+        if self.item_barcode is not None:
+            d["barcode"] = int(self.item_barcode[j])
         if self.quad_page is not None:
             d["quad_page"] = _quad_pairs(self.quad_page[j])
         return d
@@ -1436,6 +1524,12 @@ class PageResult(collections.abc.Sequence):
         """the page's selection marks in (y, x) order: {"box": [x0, y0, x1, y1], "interior", "selected", "fill" (inked / area), "label" (an item or -1), "text"
         (the label's)}; [] when marks are off"""
         return [] if self.mark_recs is None else mark_dicts(self.mark_recs, self.texts)
+
+    @property
+    def barcodes(self) -> list:
+        """the page's barcodes in (y0, x0, dir) order: {"box": [x0, y0, x1, y1], "symbology" ("code128" | "code39"), "direction" (0 left to right, 1 top to
+        bottom, 2 right to left, 3 bottom to top), "text", "data" (bytes), "lines", "module" (px), "gs1", "flags"}; [] when barcodes are off"""
+        return [] if self.barcode_recs is None else barcode_dicts(self.barcode_recs)
 
     def to_page(self, points) -> np.ndarray:
         """points [..., 2] of this result's frame -> the caller's page (the identity when deskew is off), float32"""
@@ -1575,6 +1669,7 @@ class Engine:
         curved = bool(overrides.pop("curved", False))                                     # nor this: set_curved, below
         tiled = _tiled_arg(overrides.pop("tiled", None))                                  # nor this: set_tiled, below
         marks = _marks_arg(overrides.pop("marks", None))                                  # nor this: set_marks, below
+        barcodes = _barcodes_arg(overrides.pop("barcodes", None))                         # nor this: set_barcodes, below
         tables = _tables_arg(overrides.pop("tables", None))                               # nor this: set_tables, below
         deskew = _deskew_arg(overrides.pop("deskew", None))                               # nor this: set_deskew, below
         local_ink = _local_ink_arg(overrides.pop("local_ink", None))                      # nor this: set_local_ink, below
@@ -1609,6 +1704,8 @@ class Engine:
             self.set_tables(tables)
         if marks[0]:
             self.set_marks(marks)
+        if barcodes[0]:
+            self.set_barcodes(barcodes)
         if deskew[0]:
             self.set_deskew(deskew)
         if local_ink[0]:
@@ -1721,6 +1818,39 @@ class Engine:
                                            _i(corners), _i(bands), _i(mode), _i(marks)))
         n = int(bands[:, 0].sum()) if mode[0] == 1 else 0
         return {"mode": int(mode[0]), "corners": int(corners[0]), "bands": bands, "marks": marks[:n].copy()}
+
+    def set_barcodes(self, barcodes=True):
+        """Read every page's Code 128 and Code 39 barcodes and give every item its barcode (ttr_engine_set_barcodes; DESIGN.md "Barcodes"): False / 0 = off,
+        True = (8, 128, 3), else (min_lines 4..256, ink 1..255, symbologies 1..3: bit 0 Code 128, bit 1 Code 39) or a bare min_lines; none of the defaults has
+        been tuned on documents.  Refused while batches stream and with a communicator attached."""
+        a = _barcodes_arg(barcodes)
+        if self.lib.ttr_engine_set_barcodes(self.h, *a) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode())
+
+    @property
+    def barcodes(self):
+        """(min_lines, ink, symbologies) in force, or None when barcodes are off"""
+        ink, sym = C.c_int(), C.c_int()
+        m = int(self.lib.ttr_engine_barcodes(self.h, C.byref(ink), C.byref(sym)))
+        return (m, ink.value, sym.value) if m else None
+
+    def barcodes_page(self, image, quads=None, min_lines: int = BARCODES_MIN_LINES, ink: int = BARCODES_INK, symbologies: int = BARCODES_SYMBOLOGIES) -> dict:
+        """ttr_barcodes_page: table_ink_kernel, barcode_scan_kernel and barcode_page_kernel on a host image u8 [H, W, 3] and host quads f32 [nq, 8], whatever
+        the engine's setting -> the dict barcodes_from_page returns."""
+        def fn(*a):
+            self._check(self.lib.ttr_barcodes_page(self.h, *a))
+        return _barcodes_call(fn, image, quads, (min_lines, ink, symbologies))
+
+    def barcodes_debug(self, image, min_lines: int = BARCODES_MIN_LINES, ink: int = BARCODES_INK, symbologies: int = BARCODES_SYMBOLOGIES, dev_offset: int = 0,
+                       dev_stride: int = 0) -> dict:
+        """ttr_dbg_barcodes: the lines' raw hits i32 [H + W, 2, 8, 20], their counters i32 [H + W, 2, 4] (kept, dropped, candidates, starts) and the side block
+        i32 [1544] as the device formed them; the image is placed dev_offset bytes into a device buffer with dev_stride bytes from row to row (0 = 3 W)"""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        h, w = image.shape[:2]
+        hits, cnt, side = np.zeros((h + w, 2, 8, 20), np.int32), np.zeros((h + w, 2, 4), np.int32), np.zeros(8 + 64 * 24, np.int32)
+        self._check(self.lib.ttr_dbg_barcodes(self.h, _u8(image), h, w, w * 3, int(dev_offset), int(dev_stride), int(min_lines), int(ink), int(symbologies),
+                                              _i(hits), _i(cnt), _i(side)))
+        return {"hits": hits, "line_counts": cnt, "side": side}
 
     def page_ink_passes(self) -> int:
         """ttr_dbg_page_ink_passes: the ink passes enqueued for the batches' page layers so far (tables and marks in one batch share one)"""
@@ -2239,6 +2369,12 @@ class Engine:
                 lex.update(mark_mode=int(self.lib.ttr_result_mark_mode(arr[i])),
                            mark_recs=np.ctypeslib.as_array(mp, (nm_, 12)).copy() if mp and nm_ else np.zeros((0, 12), np.int32),
                            item_mark=np.ctypeslib.as_array(ip, (c,)).copy() if ip and c else np.full(c, -1, np.int32))
+            if self.lib.ttr_result_barcode_mode(arr[i]):    # barcodes: the page's barcodes and its items' barcodes (there for a page without items too)
+                nb_ = int(self.lib.ttr_result_barcode_count(arr[i]))
+                bp, ip = self.lib.ttr_result_barcodes(arr[i]), self.lib.ttr_result_item_barcode(arr[i])
+                lex.update(barcode_mode=int(self.lib.ttr_result_barcode_mode(arr[i])),
+                           barcode_recs=np.ctypeslib.as_array(bp, (nb_, 24)).copy() if bp and nb_ else np.zeros((0, 24), np.int32),
+                           item_barcode=np.ctypeslib.as_array(ip, (c,)).copy() if ip and c else np.full(c, -1, np.int32))
             pl = self.lib.ttr_result_pattern_logp(arr[i])
             if pl:                              # patterns in best mode: the page's log-probabilities
                 lex["pattern_logp"] = np.ctypeslib.as_array(pl, (c,)).copy()
