@@ -67,8 +67,10 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
 #include <cmath>
 #include <stdexcept>
+#include <tuple>
 
 #include "../include/tuatara.h"
 #include "../include/tuatara_hip.h"
@@ -276,80 +278,65 @@ static std::vector<RegionSpec> region_args(const py::object& regions_kw) {
   return out;
 }
 
+// The keywords of the page layers that read ink - tables, deskew, local_ink, marks, barcodes: "False | True | tuple of N ints | None" -> the layer's N ints.  None
+// and False leave the first 0 (off) and the others at their defaults, True is the defaults, a tuple gives all of them
+template <size_t N>
+static std::array<int, N> layer_kw(const py::object& kw, const std::array<int, N>& defaults, const char* name, const char* fields) {
+  std::array<int, N> v = defaults;
+  v[0] = 0;
+  if (py::isinstance<py::bool_>(kw)) v[0] = kw.cast<bool>() ? defaults[0] : 0;
+  else if (py::isinstance<py::tuple>(kw) && py::len(kw) == N) {
+    const py::tuple t = kw.cast<py::tuple>();
+    for (size_t i = 0; i < N; ++i) v[i] = t[i].cast<int>();
+  } else if (!kw.is_none()) throw py::type_error(std::string(name) + " must be False, True or (" + fields + ")");
+  return v;
+}
+// ... and the layer's setting for one call: the values on entry; off - 0, then the defaults - on exit
+template <size_t N, class... A>
+struct LayerScope {
+  void (*set)(A...);
+  std::array<int, N> off;
+  LayerScope(void (*set_)(A...), const std::array<int, N>& v, const std::array<int, N>& defaults) : set(set_), off(defaults) { off[0] = 0; std::apply(set, v); }
+  ~LayerScope() { std::apply(set, off); }
+  LayerScope(const LayerScope&) = delete;
+};
+
 static py::list image_to_data_wrapper(py::array_t<unsigned char, py::array::c_style | py::array::forcecast> image, std::string weights_dir,
                                       std::string output_dir, bool rectify, bool conf, py::object orient_kw, bool orient_page, bool lines, bool chars,
                                       bool blocks, py::object allowlist, py::object blocklist, py::object regions_kw, int alts, py::object lexicon, int lexicon_m,
                                       py::object pattern_kw, py::object wide_kw, bool pattern_best, bool curved, py::object lexicon_fuzzy, double lexicon_gap,
                                       py::object tiled_kw, py::object tables_kw, py::object deskew_kw, py::object local_ink_kw, py::object marks_kw, py::object barcodes_kw) {
   // barcodes=False | True (8, 128, 3) | (min_lines, ink, symbologies): barcodes for this call (DESIGN.md "Barcodes")
-  struct BarcodesScope {
-    BarcodesScope(int a, int i, int s) { set_barcodes(a, i, s); }
-    ~BarcodesScope() { set_barcodes(0); }
-  };
-  int bc_min = 0, bc_ink = 128, bc_sym = 3;
-  if (py::isinstance<py::bool_>(barcodes_kw)) bc_min = barcodes_kw.cast<bool>() ? 8 : 0;
-  else if (py::isinstance<py::tuple>(barcodes_kw) && py::len(barcodes_kw) == 3) {
-    const py::tuple t = barcodes_kw.cast<py::tuple>();
-    bc_min = t[0].cast<int>(); bc_ink = t[1].cast<int>(); bc_sym = t[2].cast<int>();
-  } else if (!barcodes_kw.is_none()) throw py::type_error("barcodes must be False, True or (min_lines, ink, symbologies)");
+  const std::array<int, 3> bc_def{8, 128, 3}, bc = layer_kw(barcodes_kw, bc_def, "barcodes", "min_lines, ink, symbologies");
+  const int bc_min = bc[0];
   if (bc_min != 0 && !regions_kw.is_none()) throw std::invalid_argument("barcodes does not combine with regions (the views stay empty)");
-  if (bc_min != 0 && (bc_min < 4 || bc_min > 256 || bc_ink < 1 || bc_ink > 255 || bc_sym < 1 || bc_sym > 3))
+  if (bc_min != 0 && (bc_min < 4 || bc_min > 256 || bc[1] < 1 || bc[1] > 255 || bc[2] < 1 || bc[2] > 3))
     throw std::runtime_error("barcodes must be False, True or (min_lines, ink, symbologies) with min_lines in 4..256, ink in 1..255 and symbologies in 1..3");
-  BarcodesScope barcodes_scope(bc_min, bc_ink, bc_sym);
+  LayerScope barcodes_scope(set_barcodes, bc, bc_def);
   // marks=False | True (10, 64, 24, 128) | (min_side, max_side, fill, ink): selection marks for this call (DESIGN.md "Selection marks")
-  struct MarksScope {
-    MarksScope(int a, int b, int f, int i) { set_marks(a, b, f, i); }
-    ~MarksScope() { set_marks(0); }
-  };
-  int mk_min = 0, mk_max = 64, mk_fill = 24, mk_ink = 128;
-  if (py::isinstance<py::bool_>(marks_kw)) mk_min = marks_kw.cast<bool>() ? 10 : 0;
-  else if (py::isinstance<py::tuple>(marks_kw) && py::len(marks_kw) == 4) {
-    const py::tuple t = marks_kw.cast<py::tuple>();
-    mk_min = t[0].cast<int>(); mk_max = t[1].cast<int>(); mk_fill = t[2].cast<int>(); mk_ink = t[3].cast<int>();
-  } else if (!marks_kw.is_none()) throw py::type_error("marks must be False, True or (min_side, max_side, fill, ink)");
+  const std::array<int, 4> mk_def{10, 64, 24, 128}, mk = layer_kw(marks_kw, mk_def, "marks", "min_side, max_side, fill, ink");
+  const int mk_min = mk[0];
   if (mk_min != 0 && !regions_kw.is_none()) throw std::invalid_argument("marks does not combine with regions (the views stay empty)");
-  if (mk_min != 0 && (mk_min < 8 || mk_min > 64 || mk_max < mk_min || mk_max > 128 || mk_fill < 1 || mk_fill > 255 || mk_ink < 1 || mk_ink > 255))
+  if (mk_min != 0 && (mk_min < 8 || mk_min > 64 || mk[1] < mk_min || mk[1] > 128 || mk[2] < 1 || mk[2] > 255 || mk[3] < 1 || mk[3] > 255))
     throw std::runtime_error("marks must be False, True or (min_side, max_side, fill, ink) with min_side in 8..64, max_side in min_side..128, fill and ink in 1..255");
-  MarksScope marks_scope(mk_min, mk_max, mk_fill, mk_ink);
+  LayerScope marks_scope(set_marks, mk, mk_def);
   // local_ink=False | True (16, 38, 2) | (radius, drop, polarity): the ink rule of tables and deskew for this call (DESIGN.md "Local ink")
-  struct InkScope {
-    InkScope(int r, int d, int p) { set_local_ink(r, d, p); }
-    ~InkScope() { set_local_ink(0); }
-  };
-  int ink_r = 0, ink_d = 38, ink_p = 2;
-  if (py::isinstance<py::bool_>(local_ink_kw)) ink_r = local_ink_kw.cast<bool>() ? 16 : 0;
-  else if (py::isinstance<py::tuple>(local_ink_kw) && py::len(local_ink_kw) == 3) {
-    const py::tuple t = local_ink_kw.cast<py::tuple>();
-    ink_r = t[0].cast<int>(); ink_d = t[1].cast<int>(); ink_p = t[2].cast<int>();
-  } else if (!local_ink_kw.is_none()) throw py::type_error("local_ink must be False, True or (radius, drop, polarity)");
   // (the ranges are the engine's to check: ttr_engine_set_ink refuses, the call comes back empty and raise_refused raises its message)
-  InkScope ink_scope(ink_r, ink_d, ink_p);
+  const std::array<int, 3> ink_def{16, 38, 2}, ink = layer_kw(local_ink_kw, ink_def, "local_ink", "radius, drop, polarity");
+  const int ink_r = ink[0];
+  LayerScope ink_scope(set_local_ink, ink, ink_def);
   // deskew=False | True (64, 288, 128) | (max_slope, gain, ink): the page is read upright for this call (DESIGN.md "Deskew"); boxes and quads are the upright page's
-  struct DeskewScope {
-    DeskewScope(int m, int g, int i) { set_deskew(m, g, i); }
-    ~DeskewScope() { set_deskew(0); }
-  };
-  int dsk_m = 0, dsk_g = 288, dsk_i = 128;
-  if (py::isinstance<py::bool_>(deskew_kw)) dsk_m = deskew_kw.cast<bool>() ? 64 : 0;
-  else if (py::isinstance<py::tuple>(deskew_kw) && py::len(deskew_kw) == 3) {
-    const py::tuple t = deskew_kw.cast<py::tuple>();
-    dsk_m = t[0].cast<int>(); dsk_g = t[1].cast<int>(); dsk_i = t[2].cast<int>();
-  } else if (!deskew_kw.is_none()) throw py::type_error("deskew must be False, True or (max_slope, gain, ink)");
   // (the ranges are the engine's to check: ttr_engine_set_deskew refuses, the call comes back empty and raise_refused raises its message)
-  DeskewScope deskew_scope(dsk_m, dsk_g, dsk_i);
+  const std::array<int, 3> dsk_def{64, 288, 128}, dsk = layer_kw(deskew_kw, dsk_def, "deskew", "max_slope, gain, ink");
+  const int dsk_m = dsk[0];
+  LayerScope deskew_scope(set_deskew, dsk, dsk_def);
   // tables=False | True (48, 128) | (min_len, ink): tables for this call (DESIGN.md "Tables")
-  struct TablesScope {
-    TablesScope(int m, int i) { set_tables(m, i); }
-    ~TablesScope() { set_tables(0); }
-  };
-  int tab_min_len = 0, tab_ink = 128;
-  if (py::isinstance<py::bool_>(tables_kw)) tab_min_len = tables_kw.cast<bool>() ? 48 : 0;
-  else if (py::isinstance<py::tuple>(tables_kw) && py::len(tables_kw) == 2) { tab_min_len = tables_kw.cast<py::tuple>()[0].cast<int>(); tab_ink = tables_kw.cast<py::tuple>()[1].cast<int>(); }
-  else if (!tables_kw.is_none()) throw py::type_error("tables must be False, True or (min_len, ink)");
+  const std::array<int, 2> tab_def{48, 128}, tab = layer_kw(tables_kw, tab_def, "tables", "min_len, ink");
+  const int tab_min_len = tab[0];
   if (tab_min_len != 0 && !regions_kw.is_none()) throw std::invalid_argument("tables does not combine with regions (the views stay empty)");
-  if (tab_min_len != 0 && (tab_min_len < 16 || tab_min_len > 4096 || tab_ink < 1 || tab_ink > 255))
+  if (tab_min_len != 0 && (tab_min_len < 16 || tab_min_len > 4096 || tab[1] < 1 || tab[1] > 255))
     throw std::runtime_error("tables must be False, True or (min_len, ink) with min_len in 16..4096 and ink in 1..255");
-  TablesScope tables_scope(tab_min_len, tab_ink);
+  LayerScope tables_scope(set_tables, tab, tab_def);
   // tiled=False | True (128) | an overlap: tiled pages for this call (DESIGN.md "Tiled pages"); the engine checks the value, a refusal raises RuntimeError
   struct TiledScope {
     explicit TiledScope(int o) { set_tiled(o); }

@@ -1,5 +1,5 @@
 // The barcode host rule (tuatara_amd/csrc/geometry.cpp + barcodes_rule.h; DESIGN.md "Barcodes") under sanitizers: a stand-alone program, host code only.
-//   barcodes_san <seed> <pages>   drives tables_ink, marks_transpose, barcodes_from_bits, barcodes_from_page, barcodes_from_page_ink, barcodes_items and
+//   barcodes_san <seed> <pages>   drives tables_ink, marks_transpose, barcodes_from_bits, barcodes_from_page (under both ink rules), barcodes_items and
 //                                 barcodes_side_valid over seeded pages of the kinds the tests use - random bits, Code 128 and Code 39 codes of random text,
 //                                 module, place and direction, codes on and cut by the page's edges and across word boundaries, codes cut short, 65 codes on
 //                                 a page (mode -7), widths about the word size, padded strides - with the page, both bitmaps and every output in exactly sized
@@ -114,8 +114,8 @@ int main(int argc, char** argv) {
     for (int i = 0; i < nq; ++i)
       if (item[(size_t)i] < -1 || item[(size_t)i] >= side[1]) return fail("barcodes_items: an index out of range");
     if (h >= 3 && w >= 3) {   // the same under the local rule's bitmap
-      const int lm = barcodes_from_page_ink(page.data(), h, w, stride, min_lines, syms, 1 + (int)(rng() % 64), 1 + (int)(rng() % 255), (int)(rng() % 3), side3.data());
-      if (lm != side3[0] || !barcodes_side_valid(side3.data(), h, w, min_lines, syms, &why)) return fail("barcodes_from_page_ink: a block decode_pages would refuse: " + why);
+      const int lm = barcodes_from_page(page.data(), h, w, stride, min_lines, InkRule::local(1 + (int)(rng() % 64), 1 + (int)(rng() % 255), (int)(rng() % 3)), syms, side3.data());
+      if (lm != side3[0] || !barcodes_side_valid(side3.data(), h, w, min_lines, syms, &why)) return fail("barcodes_from_page under the local rule: a block decode_pages would refuse: " + why);
     }
     if (mode == 1 && side[1] > 0) {   // what decode_pages must refuse
       std::vector<int32_t> bad = side;

@@ -78,15 +78,15 @@ int main(int argc, char** argv) {
     if (ink_rec_valid(bad, R, drop, pol, h, w)) return fail("ink_rec_valid accepts another radius");
     // the ink forms of the two rules equal their bodies behind this bitmap
     std::vector<int32_t> side(kTabSideInts), side2(kTabSideInts);
-    const int m1 = tables_from_page_ink(page.data(), h, w, stride, 16, R, drop, pol, side.data());
+    const int m1 = tables_from_page(page.data(), h, w, stride, 16, InkRule::local(R, drop, pol), side.data());
     const int m2 = tables_from_bits(bits.data(), h, w, 16, side2.data());
-    if (m1 != m2 || side != side2) return fail("tables_from_page_ink is not tables_from_bits behind ink_from_page");
+    if (m1 != m2 || side != side2) return fail("tables_from_page under the local rule is not tables_from_bits behind ink_from_page");
     const int M = 1 + (int)(rng() % 32);
     std::vector<uint8_t> out((size_t)h * w * 3);
     std::vector<uint64_t> scores((size_t)2 * M + 1);
     DeskewRec drec;
-    deskew_from_page_ink(page.data(), h, w, stride, M, 288, R, drop, pol, out.data(), w * 3, &drec, scores.data());
-    if (drec.w != w || drec.h != h) return fail("deskew_from_page_ink: another page's size");
+    deskew_from_page(page.data(), h, w, stride, M, 288, InkRule::local(R, drop, pol), out.data(), w * 3, &drec, scores.data());
+    if (drec.w != w || drec.h != h) return fail("deskew_from_page under the local rule: another page's size");
     light += rec.inverted;
   }
   std::cout << "pages " << pages << " light " << light << " ink " << inked << std::endl;

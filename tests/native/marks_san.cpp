@@ -1,6 +1,6 @@
 // The selection-marks host rule (tuatara_amd/csrc/geometry.cpp + marks_rule.h; DESIGN.md "Selection marks") under sanitizers: a stand-alone program, host code
 // only.
-//   marks_san <seed> <pages>   drives tables_ink, marks_transpose, marks_from_bits, marks_from_page, marks_from_page_ink, marks_items and marks_side_valid over
+//   marks_san <seed> <pages>   drives tables_ink, marks_transpose, marks_from_bits, marks_from_page (under both ink rules), marks_items and marks_side_valid over
 //                              seeded pages of the kinds the tests use - random bits, frames of random side, thickness and aspect with crosses inside, frames on
 //                              the page's edges and across word boundaries, sides up to 128, a grid of 8-px boxes beyond the cap (mode -6), widths about the word
 //                              size, padded strides - with the page, both bitmaps and every output in exactly sized heap buffers, so that any access outside
@@ -87,8 +87,8 @@ int main(int argc, char** argv) {
     for (int i = 0; i < nq; ++i)
       if (item_mark[(size_t)i] < -1 || item_mark[(size_t)i] >= side[1]) return fail("marks_items: an index out of range");
     if (h >= 3 && w >= 3) {   // the same under the local rule's bitmap
-      const int lm = marks_from_page_ink(page.data(), h, w, stride, min_side, max_side, fill, 1 + (int)(rng() % 64), 1 + (int)(rng() % 255), (int)(rng() % 3), side3.data());
-      if (lm != side3[0] || !marks_side_valid(side3.data(), h, w, fill, 0, &why)) return fail("marks_from_page_ink: a block decode_pages would refuse: " + why);
+      const int lm = marks_from_page(page.data(), h, w, stride, min_side, max_side, fill, InkRule::local(1 + (int)(rng() % 64), 1 + (int)(rng() % 255), (int)(rng() % 3)), side3.data());
+      if (lm != side3[0] || !marks_side_valid(side3.data(), h, w, fill, 0, &why)) return fail("marks_from_page under the local rule: a block decode_pages would refuse: " + why);
     }
     if (mode == 1 && side[1] > 0) {   // what decode_pages must refuse
       std::vector<int32_t> bad = side;

@@ -1516,20 +1516,84 @@ int ttr_curve_crops(ttr_engine* e, const uint8_t* img, int h, int w, int row_str
   TTR_GUARD_END(-1)
 }
 
-// ---- tables (DESIGN.md "Tables")
-int ttr_engine_set_tables(ttr_engine* e, int min_len, int ink) {
+// ---- what the page layers that read a page's ink share: tables, deskew, local ink, selection marks, barcodes (DESIGN.md "Adding a page layer")
+// One setter: the guard, the lock, the range refusal (`ranges` behind the function's name, when the layer is being turned on), the streaming refusal, the
+// communicator refusal (`alone`: what one engine alone does; null = the layer runs with a communicator), then the store
+static int engine_set(ttr_engine* e, const char* fn, bool on, bool ok, const std::string& ranges, const char* alone, const std::function<void(Engine&)>& store) {
   TTR_GUARD_BEGIN
   if (!e) throw std::runtime_error("null argument");
   Engine& E = *e->e;
   EngineScope lk(E);
-  if (min_len != 0 && !tables_args_ok(min_len, ink))
-    throw std::runtime_error("ttr_engine_set_tables: min_len must be 0 (off) or lie in 16..4096 and ink in 1..255, got " + std::to_string(min_len) + " and " + std::to_string(ink));
-  E.refuse_while_streaming("ttr_engine_set_tables");
-  if (min_len && E.comm) throw std::runtime_error("ttr_engine_set_tables: tables are found by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
-  E.tables_min_len = min_len;
-  if (min_len) E.tables_ink = ink;
+  if (on && !ok) throw std::runtime_error(std::string(fn) + ": " + ranges);
+  E.refuse_while_streaming(fn);
+  if (on && alone && E.comm) throw std::runtime_error(std::string(fn) + ": " + alone + " by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
+  store(E);
   return 0;
   TTR_GUARD_END(-1)
+}
+
+// the checks of the one-page calls: the image (a side of side_cap px or more is refused), the words' quads, and - page_layer_in_ok - both around the layer's own
+// range refusal (null = in range)
+static void page_image_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int side_cap) {
+  if (!img) throw std::runtime_error("null argument");
+  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
+  if (h >= side_cap || w >= side_cap) throw std::runtime_error(std::string(what) + ": a page side of " + std::to_string(side_cap) + " px or more");
+}
+static void page_quads_ok(const char* what, const float* quads, int nq) {
+  for (int i = 0; i < nq; ++i)
+    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error(std::string(what) + ": quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
+}
+static void page_layer_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, const float* quads, int nq, const char* bad_args) {
+  if (nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
+  page_image_ok(what, img, h, w, row_stride, 32768);
+  if (bad_args) throw std::runtime_error(std::string(what) + ": " + bad_args);
+  page_quads_ok(what, quads, nq);
+}
+static std::string ink_ranges(int radius, int drop, int polarity) {
+  return "drop in 1..255 and polarity in 0..2, got " + std::to_string(radius) + ", " + std::to_string(drop) + " and " + std::to_string(polarity);
+}
+static void ink_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int radius, int drop, int polarity) {
+  page_image_ok(what, img, h, w, row_stride, 32768);
+  if (!ink_args_ok(radius, drop, polarity)) throw std::runtime_error(std::string(what) + ": radius must lie in 1..64, " + ink_ranges(radius, drop, polarity));
+}
+
+// A layer's three one-page entry points share one body: the host rule under the fixed ink rule, the host rule under the local one (the layer's own check
+// then receives 128 in the place of the ink, and fires before the ink rule's), or the engine's stage call
+enum PageVia { kViaHost, kViaHostLocal, kViaEngine };
+static int layer_ink(PageVia via, const InkRule& rule) { return via == kViaHostLocal ? 128 : rule.ink; }
+
+static std::vector<int32_t> quad_centres(const float* quads, int nq) {   // 64 x the quads' centres [nq][2]
+  std::vector<int32_t> centres((size_t)nq * 2);
+  for (int i = 0; i < nq; ++i) tables_word_centre(quads + 8 * (size_t)i, &centres[2 * (size_t)i]);
+  return centres;
+}
+
+// ttr_results_gather_tables / _marks / _barcodes: every result's items (text.size() of them) of each vector into its array (null = not wanted), -1 where a result
+// has none - which the first vector decides; returns how many items the last vector places
+using ItemVec = std::vector<int32_t> Result::*;
+static int items_gather(ttr_result* const* rs, int n, std::initializer_list<std::pair<ItemVec, int32_t*>> outs) {
+  if (!rs || n < 0) return -1;
+  size_t oi = 0, inside = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!rs[i]) continue;
+    const Result& r = rs[i]->r;
+    const size_t cnt = r.text.size();
+    const bool has = cnt > 0 && (r.*outs.begin()->first).size() == cnt;
+    for (const auto& o : outs)
+      if (o.second) { if (has) std::copy((r.*o.first).begin(), (r.*o.first).end(), o.second + oi); else std::fill(o.second + oi, o.second + oi + cnt, -1); }
+    if (has) for (int32_t c : r.*(outs.end() - 1)->first) inside += c >= 0;
+    oi += cnt;
+  }
+  return (int)inside;
+}
+
+// ---- tables (DESIGN.md "Tables")
+int ttr_engine_set_tables(ttr_engine* e, int min_len, int ink) {
+  return engine_set(e, "ttr_engine_set_tables", min_len != 0, tables_args_ok(min_len, ink),
+                    "min_len must be 0 (off) or lie in 16..4096 and ink in 1..255, got " + std::to_string(min_len) + " and " + std::to_string(ink), "tables are found", [&](Engine& E) {
+                      E.tables_min_len = min_len;
+                      if (min_len) E.tables_ink = ink;
+                    });
 }
 
 int ttr_engine_tables(const ttr_engine* e, int* ink) {
@@ -1578,77 +1642,57 @@ int ttr_result_cell_text(const ttr_result* r, int c, char* buf, int cap) {
 }
 
 int ttr_results_gather_tables(ttr_result* const* rs, int n, int32_t* item_table, int32_t* item_cell) {
-  if (!rs || n < 0) return -1;
-  size_t oi = 0, inside = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!rs[i]) continue;
-    const Result& r = rs[i]->r;
-    const size_t cnt = r.text.size();
-    const bool has = cnt > 0 && r.item_table.size() == cnt;
-    if (item_table) { if (has) std::copy(r.item_table.begin(), r.item_table.end(), item_table + oi); else std::fill(item_table + oi, item_table + oi + cnt, -1); }
-    if (item_cell) { if (has) std::copy(r.item_cell.begin(), r.item_cell.end(), item_cell + oi); else std::fill(item_cell + oi, item_cell + oi + cnt, -1); }
-    if (has) for (int32_t c : r.item_cell) inside += c >= 0;
-    oi += cnt;
-  }
-  return (int)inside;
+  return items_gather(rs, n, {{&Result::item_table, item_table}, {&Result::item_cell, item_cell}});
 }
 
-static void tables_out(const int32_t* side, const int32_t* items, int nq, int32_t* mode, int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells,
-                       int32_t* item_table, int32_t* item_cell) {
-  if (mode) *mode = side[0];
+struct TablesOut { int32_t *mode, *counts, *rulings, *tables, *lines, *cells, *item_table, *item_cell; };
+
+static int tables_call(const char* what, PageVia via, ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_len, const InkRule& rule, const float* quads,
+                       int nq, const TablesOut& o) {
+  TTR_GUARD_BEGIN
+  if (via == kViaEngine && !e) throw std::runtime_error("null argument");
+  const int ink = layer_ink(via, rule);
+  page_layer_in_ok(what, img, h, w, row_stride, quads, nq, tables_args_ok(min_len, ink) ? nullptr :
+                   ("min_len must lie in 16..4096 and ink in 1..255, got " + std::to_string(min_len) + " and " + std::to_string(ink)).c_str());
+  if (via == kViaHostLocal) ink_in_ok(what, img, h, w, row_stride, rule.radius, rule.drop, rule.polarity);
+  std::vector<int32_t> side(kTabSideInts), items((size_t)nq * 2);
+  if (via == kViaEngine) {
+    Engine& E = *e->e;
+    EngineScope lk(E);
+    E.refuse_while_streaming(what);
+    E.tables_stage(img, h, w, row_stride, 0, 0, min_len, ink, quads, nq, side.data(), items.data(), nullptr, nullptr);
+  } else {
+    tables_from_page(img, h, w, row_stride ? row_stride : w * 3, min_len, rule, side.data());
+    tables_words(side.data(), quad_centres(quads, nq).data(), nq, items.data());
+  }
+  if (o.mode) *o.mode = side[0];
   int32_t c4[4];
-  tables_export(side, c4, rulings, tables, lines, cells);
-  if (counts) { std::copy(c4, c4 + 4, counts); counts[4] = side[0] == 1 ? side[5] : 0; counts[5] = side[0] == 1 ? side[6] : 0; }
+  tables_export(side.data(), c4, o.rulings, o.tables, o.lines, o.cells);
+  if (o.counts) { std::copy(c4, c4 + 4, o.counts); o.counts[4] = side[0] == 1 ? side[5] : 0; o.counts[5] = side[0] == 1 ? side[6] : 0; }
   for (int i = 0; i < nq; ++i) {
-    if (item_table) item_table[i] = items[2 * (size_t)i];
-    if (item_cell) item_cell[i] = items[2 * (size_t)i + 1];
+    if (o.item_table) o.item_table[i] = items[2 * (size_t)i];
+    if (o.item_cell) o.item_cell[i] = items[2 * (size_t)i + 1];
   }
-}
-
-// the checks the one-page calls of tables, deskew, local ink and marks share: the image (a side of side_cap px or more is refused), and the words' quads
-static void page_image_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int side_cap) {
-  if (!img) throw std::runtime_error("null argument");
-  if (h <= 0 || w <= 0 || (row_stride && row_stride < w * 3)) throw std::runtime_error(std::string(what) + ": bad image size");
-  if (h >= side_cap || w >= side_cap) throw std::runtime_error(std::string(what) + ": a page side of " + std::to_string(side_cap) + " px or more");
-}
-static void page_quads_ok(const char* what, const float* quads, int nq) {
-  for (int i = 0; i < nq; ++i)
-    if (!region_quad_ok(quads + 8 * (size_t)i)) throw std::runtime_error(std::string(what) + ": quad " + std::to_string(i) + " has a coordinate that is not finite or has |x| >= 32768");
-}
-
-static void tables_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq) {
-  if (nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
-  page_image_ok(what, img, h, w, row_stride, 32768);
-  if (!tables_args_ok(min_len, ink)) throw std::runtime_error(std::string(what) + ": min_len must lie in 16..4096 and ink in 1..255, got " + std::to_string(min_len) + " and " + std::to_string(ink));
-  page_quads_ok(what, quads, nq);
+  return 0;
+  TTR_GUARD_END(-1)
 }
 
 int ttr_tables_from_page(const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq, int32_t* mode, int32_t* counts,
                          int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell) {
-  TTR_GUARD_BEGIN
-  tables_in_ok("ttr_tables_from_page", img, h, w, row_stride, min_len, ink, quads, nq);
-  std::vector<int32_t> side(kTabSideInts), centres((size_t)nq * 2), items((size_t)nq * 2);
-  tables_from_page(img, h, w, row_stride ? row_stride : w * 3, min_len, ink, side.data());
-  for (int i = 0; i < nq; ++i) tables_word_centre(quads + 8 * (size_t)i, &centres[2 * (size_t)i]);
-  tables_words(side.data(), centres.data(), nq, items.data());
-  tables_out(side.data(), items.data(), nq, mode, counts, rulings, tables, lines, cells, item_table, item_cell);
-  return 0;
-  TTR_GUARD_END(-1)
+  return tables_call("ttr_tables_from_page", kViaHost, nullptr, img, h, w, row_stride, min_len, ink, quads, nq,
+                     {mode, counts, rulings, tables, lines, cells, item_table, item_cell});
+}
+
+int ttr_tables_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int min_len, int radius, int drop, int polarity, const float* quads, int nq, int32_t* mode,
+                             int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell) {
+  return tables_call("ttr_tables_from_page_ink", kViaHostLocal, nullptr, img, h, w, row_stride, min_len, InkRule::local(radius, drop, polarity), quads, nq,
+                     {mode, counts, rulings, tables, lines, cells, item_table, item_cell});
 }
 
 int ttr_tables_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_len, int ink, const float* quads, int nq, int32_t* mode,
                     int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell) {
-  TTR_GUARD_BEGIN
-  if (!e) throw std::runtime_error("null argument");
-  tables_in_ok("ttr_tables_page", img, h, w, row_stride, min_len, ink, quads, nq);
-  Engine& E = *e->e;
-  EngineScope lk(E);
-  E.refuse_while_streaming("ttr_tables_page");
-  std::vector<int32_t> side(kTabSideInts), items((size_t)nq * 2);
-  E.tables_stage(img, h, w, row_stride, 0, 0, min_len, ink, quads, nq, side.data(), items.data(), nullptr, nullptr);
-  tables_out(side.data(), items.data(), nq, mode, counts, rulings, tables, lines, cells, item_table, item_cell);
-  return 0;
-  TTR_GUARD_END(-1)
+  return tables_call("ttr_tables_page", kViaEngine, e, img, h, w, row_stride, min_len, ink, quads, nq,
+                     {mode, counts, rulings, tables, lines, cells, item_table, item_cell});
 }
 
 // ---- deskew (DESIGN.md "Deskew")
@@ -1656,20 +1700,14 @@ static_assert(sizeof(ttr_skew) == sizeof(DeskewRec) && offsetof(ttr_skew, score0
               "ttr_skew is the engine's record");
 
 int ttr_engine_set_deskew(ttr_engine* e, int max_slope, int gain, int ink) {
-  TTR_GUARD_BEGIN
-  if (!e) throw std::runtime_error("null argument");
-  Engine& E = *e->e;
-  EngineScope lk(E);
-  if (max_slope != 0 && !dsk_args_ok(max_slope, gain, ink))
-    throw std::runtime_error("ttr_engine_set_deskew: max_slope must be 0 (off) or lie in 1..128, gain in 256..65535 and ink in 1..255, got " + std::to_string(max_slope) + ", " +
-                             std::to_string(gain) + " and " + std::to_string(ink));
-  E.refuse_while_streaming("ttr_engine_set_deskew");
-  if (max_slope && E.comm) throw std::runtime_error("ttr_engine_set_deskew: pages are straightened by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
-  if (max_slope) (void)E.deskew_consts_dev();   // the (C, S) table: formed here, on the host, and handed to the kernels
-  E.deskew_M = max_slope;
-  if (max_slope) { E.deskew_gain = gain; E.deskew_ink = ink; }
-  return 0;
-  TTR_GUARD_END(-1)
+  return engine_set(e, "ttr_engine_set_deskew", max_slope != 0, dsk_args_ok(max_slope, gain, ink),
+                    "max_slope must be 0 (off) or lie in 1..128, gain in 256..65535 and ink in 1..255, got " + std::to_string(max_slope) + ", " + std::to_string(gain) + " and " +
+                        std::to_string(ink),
+                    "pages are straightened", [&](Engine& E) {
+                      if (max_slope) (void)E.deskew_consts_dev();   // the (C, S) table: formed here, on the host, and handed to the kernels
+                      E.deskew_M = max_slope;
+                      if (max_slope) { E.deskew_gain = gain; E.deskew_ink = ink; }
+                    });
 }
 
 int ttr_engine_deskew(const ttr_engine* e, int* gain, int* ink) {
@@ -1711,55 +1749,50 @@ int ttr_results_gather_skew(ttr_result* const* rs, int n, ttr_skew* recs) {
   return turned;
 }
 
-static void deskew_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink) {
+static int deskew_call(const char* what, PageVia via, ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, const InkRule& rule,
+                       uint8_t* out_img, ttr_skew* rec, uint64_t* scores) {
+  TTR_GUARD_BEGIN
+  if (via == kViaEngine && !e) throw std::runtime_error("null argument");
+  const int ink = layer_ink(via, rule);
   page_image_ok(what, img, h, w, row_stride, kDskSideCap);
   if (!dsk_args_ok(max_slope, gain, ink))
     throw std::runtime_error(std::string(what) + ": max_slope must lie in 1..128, gain in 256..65535 and ink in 1..255, got " + std::to_string(max_slope) + ", " + std::to_string(gain) +
                              " and " + std::to_string(ink));
+  if (via == kViaHostLocal) ink_in_ok(what, img, h, w, row_stride, rule.radius, rule.drop, rule.polarity);
+  DeskewRec r;
+  if (via == kViaEngine) {
+    Engine& E = *e->e;
+    EngineScope lk(E);
+    E.refuse_while_streaming(what);
+    E.deskew_stage(img, h, w, row_stride, 0, 0, max_slope, gain, ink, out_img, &r, scores);
+  } else deskew_from_page(img, h, w, row_stride ? row_stride : w * 3, max_slope, gain, rule, out_img, w * 3, &r, scores);
+  if (rec) memcpy(rec, &r, sizeof r);
+  return 0;
+  TTR_GUARD_END(-1)
 }
 
 int ttr_deskew_from_page(const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink, uint8_t* out_img, ttr_skew* rec, uint64_t* scores) {
-  TTR_GUARD_BEGIN
-  deskew_in_ok("ttr_deskew_from_page", img, h, w, row_stride, max_slope, gain, ink);
-  DeskewRec r;
-  deskew_from_page(img, h, w, row_stride ? row_stride : w * 3, max_slope, gain, ink, out_img, w * 3, &r, scores);
-  if (rec) memcpy(rec, &r, sizeof r);
-  return 0;
-  TTR_GUARD_END(-1)
+  return deskew_call("ttr_deskew_from_page", kViaHost, nullptr, img, h, w, row_stride, max_slope, gain, ink, out_img, rec, scores);
+}
+
+int ttr_deskew_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int radius, int drop, int polarity, uint8_t* out_img, ttr_skew* rec,
+                             uint64_t* scores) {
+  return deskew_call("ttr_deskew_from_page_ink", kViaHostLocal, nullptr, img, h, w, row_stride, max_slope, gain, InkRule::local(radius, drop, polarity), out_img, rec, scores);
 }
 
 int ttr_deskew_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int ink, uint8_t* out_img, ttr_skew* rec, uint64_t* scores) {
-  TTR_GUARD_BEGIN
-  if (!e) throw std::runtime_error("null argument");
-  deskew_in_ok("ttr_deskew_page", img, h, w, row_stride, max_slope, gain, ink);
-  Engine& E = *e->e;
-  EngineScope lk(E);
-  E.refuse_while_streaming("ttr_deskew_page");
-  DeskewRec r;
-  E.deskew_stage(img, h, w, row_stride, 0, 0, max_slope, gain, ink, out_img, &r, scores);
-  if (rec) memcpy(rec, &r, sizeof r);
-  return 0;
-  TTR_GUARD_END(-1)
+  return deskew_call("ttr_deskew_page", kViaEngine, e, img, h, w, row_stride, max_slope, gain, ink, out_img, rec, scores);
 }
 
 // ---- local ink (DESIGN.md "Local ink")
 static_assert(sizeof(ttr_ink) == sizeof(InkRec) && offsetof(ttr_ink, sum) == offsetof(InkRec, sum) && offsetof(ttr_ink, w) == offsetof(InkRec, w), "ttr_ink is the engine's record");
 
-static std::string ink_ranges(int radius, int drop, int polarity) {
-  return "drop in 1..255 and polarity in 0..2, got " + std::to_string(radius) + ", " + std::to_string(drop) + " and " + std::to_string(polarity);
-}
-
 int ttr_engine_set_ink(ttr_engine* e, int radius, int drop, int polarity) {
-  TTR_GUARD_BEGIN
-  if (!e) throw std::runtime_error("null argument");
-  Engine& E = *e->e;
-  EngineScope lk(E);
-  if (radius != 0 && !ink_args_ok(radius, drop, polarity)) throw std::runtime_error("ttr_engine_set_ink: radius must be 0 (off) or lie in 1..64, " + ink_ranges(radius, drop, polarity));
-  E.refuse_while_streaming("ttr_engine_set_ink");
-  E.ink_radius = radius;
-  if (radius) { E.ink_drop = drop; E.ink_polarity = polarity; }
-  return 0;
-  TTR_GUARD_END(-1)
+  return engine_set(e, "ttr_engine_set_ink", radius != 0, ink_args_ok(radius, drop, polarity), "radius must be 0 (off) or lie in 1..64, " + ink_ranges(radius, drop, polarity), nullptr,
+                    [&](Engine& E) {
+                      E.ink_radius = radius;
+                      if (radius) { E.ink_drop = drop; E.ink_polarity = polarity; }
+                    });
 }
 
 int ttr_engine_ink(const ttr_engine* e, int* drop, int* polarity) {
@@ -1786,11 +1819,6 @@ int ttr_results_gather_ink(ttr_result* const* rs, int n, ttr_ink* recs) {
   return light;
 }
 
-static void ink_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int radius, int drop, int polarity) {
-  page_image_ok(what, img, h, w, row_stride, 32768);
-  if (!ink_args_ok(radius, drop, polarity)) throw std::runtime_error(std::string(what) + ": radius must lie in 1..64, " + ink_ranges(radius, drop, polarity));
-}
-
 int ttr_ink_from_page(const uint8_t* img, int h, int w, int row_stride, int radius, int drop, int polarity, uint64_t* bits, uint64_t* bitsT, ttr_ink* rec) {
   TTR_GUARD_BEGIN
   ink_in_ok("ttr_ink_from_page", img, h, w, row_stride, radius, drop, polarity);
@@ -1815,32 +1843,6 @@ int ttr_ink_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride
   TTR_GUARD_END(-1)
 }
 
-int ttr_tables_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int min_len, int radius, int drop, int polarity, const float* quads, int nq, int32_t* mode,
-                             int32_t* counts, int32_t* rulings, int32_t* tables, int32_t* lines, int32_t* cells, int32_t* item_table, int32_t* item_cell) {
-  TTR_GUARD_BEGIN
-  tables_in_ok("ttr_tables_from_page_ink", img, h, w, row_stride, min_len, 128, quads, nq);
-  ink_in_ok("ttr_tables_from_page_ink", img, h, w, row_stride, radius, drop, polarity);
-  std::vector<int32_t> side(kTabSideInts), centres((size_t)nq * 2), items((size_t)nq * 2);
-  tables_from_page_ink(img, h, w, row_stride ? row_stride : w * 3, min_len, radius, drop, polarity, side.data());
-  for (int i = 0; i < nq; ++i) tables_word_centre(quads + 8 * (size_t)i, &centres[2 * (size_t)i]);
-  tables_words(side.data(), centres.data(), nq, items.data());
-  tables_out(side.data(), items.data(), nq, mode, counts, rulings, tables, lines, cells, item_table, item_cell);
-  return 0;
-  TTR_GUARD_END(-1)
-}
-
-int ttr_deskew_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int max_slope, int gain, int radius, int drop, int polarity, uint8_t* out_img, ttr_skew* rec,
-                             uint64_t* scores) {
-  TTR_GUARD_BEGIN
-  deskew_in_ok("ttr_deskew_from_page_ink", img, h, w, row_stride, max_slope, gain, 128);
-  ink_in_ok("ttr_deskew_from_page_ink", img, h, w, row_stride, radius, drop, polarity);
-  DeskewRec r;
-  deskew_from_page_ink(img, h, w, row_stride ? row_stride : w * 3, max_slope, gain, radius, drop, polarity, out_img, w * 3, &r, scores);
-  if (rec) memcpy(rec, &r, sizeof r);
-  return 0;
-  TTR_GUARD_END(-1)
-}
-
 // ---- selection marks (DESIGN.md "Selection marks")
 static std::string marks_ranges(int min_side, int max_side, int fill, int ink) {
   return "min_side must lie in 8..64, max_side in min_side..128, fill and ink in 1..255, got " + std::to_string(min_side) + ", " + std::to_string(max_side) + ", " +
@@ -1848,17 +1850,11 @@ static std::string marks_ranges(int min_side, int max_side, int fill, int ink) {
 }
 
 int ttr_engine_set_marks(ttr_engine* e, int min_side, int max_side, int fill, int ink) {
-  TTR_GUARD_BEGIN
-  if (!e) throw std::runtime_error("null argument");
-  Engine& E = *e->e;
-  EngineScope lk(E);
-  if (min_side != 0 && !marks_args_ok(min_side, max_side, fill, ink)) throw std::runtime_error("ttr_engine_set_marks: min_side must be 0 (off), or " + marks_ranges(min_side, max_side, fill, ink));
-  E.refuse_while_streaming("ttr_engine_set_marks");
-  if (min_side && E.comm) throw std::runtime_error("ttr_engine_set_marks: selection marks are found by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
-  E.marks_min = min_side;
-  if (min_side) { E.marks_max = max_side; E.marks_fill = fill; E.marks_ink = ink; }
-  return 0;
-  TTR_GUARD_END(-1)
+  return engine_set(e, "ttr_engine_set_marks", min_side != 0, marks_args_ok(min_side, max_side, fill, ink), "min_side must be 0 (off), or " + marks_ranges(min_side, max_side, fill, ink),
+                    "selection marks are found", [&](Engine& E) {
+                      E.marks_min = min_side;
+                      if (min_side) { E.marks_max = max_side; E.marks_fill = fill; E.marks_ink = ink; }
+                    });
 }
 
 int ttr_engine_marks(const ttr_engine* e, int* max_side, int* fill, int* ink) {
@@ -1874,79 +1870,49 @@ int ttr_result_mark_count(const ttr_result* r) { return r ? (int)(r->r.marks.siz
 const int32_t* ttr_result_marks(const ttr_result* r) { return r && !r->r.marks.empty() ? r->r.marks.data() : nullptr; }
 const int32_t* ttr_result_item_mark(const ttr_result* r) { return r && !r->r.item_mark.empty() ? r->r.item_mark.data() : nullptr; }
 
-int ttr_results_gather_marks(ttr_result* const* rs, int n, int32_t* item_mark) {
-  if (!rs || n < 0) return -1;
-  size_t oi = 0, inside = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!rs[i]) continue;
-    const Result& r = rs[i]->r;
-    const size_t cnt = r.text.size();
-    const bool has = cnt > 0 && r.item_mark.size() == cnt;
-    if (item_mark) { if (has) std::copy(r.item_mark.begin(), r.item_mark.end(), item_mark + oi); else std::fill(item_mark + oi, item_mark + oi + cnt, -1); }
-    if (has) for (int32_t m : r.item_mark) inside += m >= 0;
-    oi += cnt;
+int ttr_results_gather_marks(ttr_result* const* rs, int n, int32_t* item_mark) { return items_gather(rs, n, {{&Result::item_mark, item_mark}}); }
+
+struct MarksOut { int32_t *mode, *counts, *marks, *item_mark; };
+
+static int marks_call(const char* what, PageVia via, ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, const InkRule& rule,
+                      const float* quads, int nq, const MarksOut& o) {
+  TTR_GUARD_BEGIN
+  if (via == kViaEngine && !e) throw std::runtime_error("null argument");
+  const int ink = layer_ink(via, rule);
+  page_layer_in_ok(what, img, h, w, row_stride, quads, nq, marks_args_ok(min_side, max_side, fill, ink) ? nullptr : marks_ranges(min_side, max_side, fill, ink).c_str());
+  if (via == kViaHostLocal) ink_in_ok(what, img, h, w, row_stride, rule.radius, rule.drop, rule.polarity);
+  std::vector<int32_t> side(kMarkSideInts), items((size_t)nq);
+  if (via == kViaEngine) {
+    Engine& E = *e->e;
+    EngineScope lk(E);
+    E.refuse_while_streaming(what);
+    E.marks_stage(img, h, w, row_stride, 0, 0, min_side, max_side, fill, ink, quads, nq, side.data(), items.data(), nullptr);
+  } else {
+    marks_from_page(img, h, w, row_stride ? row_stride : w * 3, min_side, max_side, fill, rule, side.data());
+    marks_items(side.data(), quad_centres(quads, nq).data(), nq, items.data());
   }
-  return (int)inside;
-}
-
-static void marks_out(const int32_t* side, const int32_t* items, int nq, int32_t* mode, int32_t* counts, int32_t* marks, int32_t* item_mark) {
-  if (mode) *mode = side[0];
-  if (counts) { counts[0] = side[1]; counts[1] = side[2]; counts[2] = side[3]; }
-  if (marks) std::copy(side + kMarkHdr, side + kMarkHdr + (size_t)kMarkRec * side[1], marks);
-  if (item_mark) std::copy(items, items + nq, item_mark);
-}
-
-static void marks_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int ink, const float* quads, int nq) {
-  if (nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
-  page_image_ok(what, img, h, w, row_stride, 32768);
-  if (!marks_args_ok(min_side, max_side, fill, ink)) throw std::runtime_error(std::string(what) + ": " + marks_ranges(min_side, max_side, fill, ink));
-  page_quads_ok(what, quads, nq);
-}
-
-static void marks_host_items(int32_t* side, const float* quads, int nq, int32_t* items) {
-  std::vector<int32_t> centres((size_t)nq * 2);
-  for (int i = 0; i < nq; ++i) tables_word_centre(quads + 8 * (size_t)i, &centres[2 * (size_t)i]);
-  marks_items(side, centres.data(), nq, items);
+  if (o.mode) *o.mode = side[0];
+  if (o.counts) { o.counts[0] = side[1]; o.counts[1] = side[2]; o.counts[2] = side[3]; }
+  if (o.marks) std::copy(side.begin() + kMarkHdr, side.begin() + kMarkHdr + (size_t)kMarkRec * side[1], o.marks);
+  if (o.item_mark) std::copy(items.begin(), items.end(), o.item_mark);
+  return 0;
+  TTR_GUARD_END(-1)
 }
 
 int ttr_marks_from_page(const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int ink, const float* quads, int nq, int32_t* mode,
                         int32_t* counts, int32_t* marks, int32_t* item_mark) {
-  TTR_GUARD_BEGIN
-  marks_in_ok("ttr_marks_from_page", img, h, w, row_stride, min_side, max_side, fill, ink, quads, nq);
-  std::vector<int32_t> side(kMarkSideInts), items((size_t)nq);
-  marks_from_page(img, h, w, row_stride ? row_stride : w * 3, min_side, max_side, fill, ink, side.data());
-  marks_host_items(side.data(), quads, nq, items.data());
-  marks_out(side.data(), items.data(), nq, mode, counts, marks, item_mark);
-  return 0;
-  TTR_GUARD_END(-1)
+  return marks_call("ttr_marks_from_page", kViaHost, nullptr, img, h, w, row_stride, min_side, max_side, fill, ink, quads, nq, {mode, counts, marks, item_mark});
 }
 
 int ttr_marks_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int radius, int drop, int polarity, const float* quads,
                             int nq, int32_t* mode, int32_t* counts, int32_t* marks, int32_t* item_mark) {
-  TTR_GUARD_BEGIN
-  marks_in_ok("ttr_marks_from_page_ink", img, h, w, row_stride, min_side, max_side, fill, 128, quads, nq);
-  ink_in_ok("ttr_marks_from_page_ink", img, h, w, row_stride, radius, drop, polarity);
-  std::vector<int32_t> side(kMarkSideInts), items((size_t)nq);
-  marks_from_page_ink(img, h, w, row_stride ? row_stride : w * 3, min_side, max_side, fill, radius, drop, polarity, side.data());
-  marks_host_items(side.data(), quads, nq, items.data());
-  marks_out(side.data(), items.data(), nq, mode, counts, marks, item_mark);
-  return 0;
-  TTR_GUARD_END(-1)
+  return marks_call("ttr_marks_from_page_ink", kViaHostLocal, nullptr, img, h, w, row_stride, min_side, max_side, fill, InkRule::local(radius, drop, polarity), quads, nq,
+                    {mode, counts, marks, item_mark});
 }
 
 int ttr_marks_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_side, int max_side, int fill, int ink, const float* quads, int nq, int32_t* mode,
                    int32_t* counts, int32_t* marks, int32_t* item_mark) {
-  TTR_GUARD_BEGIN
-  if (!e) throw std::runtime_error("null argument");
-  marks_in_ok("ttr_marks_page", img, h, w, row_stride, min_side, max_side, fill, ink, quads, nq);
-  Engine& E = *e->e;
-  EngineScope lk(E);
-  E.refuse_while_streaming("ttr_marks_page");
-  std::vector<int32_t> side(kMarkSideInts), items((size_t)nq);
-  E.marks_stage(img, h, w, row_stride, 0, 0, min_side, max_side, fill, ink, quads, nq, side.data(), items.data(), nullptr);
-  marks_out(side.data(), items.data(), nq, mode, counts, marks, item_mark);
-  return 0;
-  TTR_GUARD_END(-1)
+  return marks_call("ttr_marks_page", kViaEngine, e, img, h, w, row_stride, min_side, max_side, fill, ink, quads, nq, {mode, counts, marks, item_mark});
 }
 
 // ---- barcodes (DESIGN.md "Barcodes")
@@ -1955,17 +1921,11 @@ static std::string barcodes_ranges(int min_lines, int ink, int symbologies) {
 }
 
 int ttr_engine_set_barcodes(ttr_engine* e, int min_lines, int ink, int symbologies) {
-  TTR_GUARD_BEGIN
-  if (!e) throw std::runtime_error("null argument");
-  Engine& E = *e->e;
-  EngineScope lk(E);
-  if (min_lines != 0 && !barcodes_args_ok(min_lines, ink, symbologies)) throw std::runtime_error("ttr_engine_set_barcodes: min_lines must be 0 (off), or " + barcodes_ranges(min_lines, ink, symbologies));
-  E.refuse_while_streaming("ttr_engine_set_barcodes");
-  if (min_lines && E.comm) throw std::runtime_error("ttr_engine_set_barcodes: barcodes are read by one engine alone, and a communicator is attached: ttr_engine_attach_comm(e, NULL) first");
-  E.barcodes_min = min_lines;
-  if (min_lines) { E.barcodes_ink = ink; E.barcodes_sym = symbologies; }
-  return 0;
-  TTR_GUARD_END(-1)
+  return engine_set(e, "ttr_engine_set_barcodes", min_lines != 0, barcodes_args_ok(min_lines, ink, symbologies), "min_lines must be 0 (off), or " + barcodes_ranges(min_lines, ink, symbologies),
+                    "barcodes are read", [&](Engine& E) {
+                      E.barcodes_min = min_lines;
+                      if (min_lines) { E.barcodes_ink = ink; E.barcodes_sym = symbologies; }
+                    });
 }
 
 int ttr_engine_barcodes(const ttr_engine* e, int* ink, int* symbologies) {
@@ -1980,79 +1940,51 @@ int ttr_result_barcode_count(const ttr_result* r) { return r ? (int)(r->r.barcod
 const int32_t* ttr_result_barcodes(const ttr_result* r) { return r && !r->r.barcodes.empty() ? r->r.barcodes.data() : nullptr; }
 const int32_t* ttr_result_item_barcode(const ttr_result* r) { return r && !r->r.item_barcode.empty() ? r->r.item_barcode.data() : nullptr; }
 
-int ttr_results_gather_barcodes(ttr_result* const* rs, int n, int32_t* item_barcode) {
-  if (!rs || n < 0) return -1;
-  size_t oi = 0, inside = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!rs[i]) continue;
-    const Result& r = rs[i]->r;
-    const size_t cnt = r.text.size();
-    const bool has = cnt > 0 && r.item_barcode.size() == cnt;
-    if (item_barcode) { if (has) std::copy(r.item_barcode.begin(), r.item_barcode.end(), item_barcode + oi); else std::fill(item_barcode + oi, item_barcode + oi + cnt, -1); }
-    if (has) for (int32_t m : r.item_barcode) inside += m >= 0;
-    oi += cnt;
+int ttr_results_gather_barcodes(ttr_result* const* rs, int n, int32_t* item_barcode) { return items_gather(rs, n, {{&Result::item_barcode, item_barcode}}); }
+
+struct BarcodesOut { int32_t *mode, *counts, *barcodes, *item_barcode, *hits, *line_counts; };   // (hits, line_counts: the host form's alone)
+
+static int barcodes_call(const char* what, PageVia via, ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_lines, const InkRule& rule, int symbologies,
+                         const float* quads, int nq, const BarcodesOut& o) {
+  TTR_GUARD_BEGIN
+  if (via == kViaEngine && !e) throw std::runtime_error("null argument");
+  const int ink = layer_ink(via, rule);
+  page_layer_in_ok(what, img, h, w, row_stride, quads, nq, barcodes_args_ok(min_lines, ink, symbologies) ? nullptr : barcodes_ranges(min_lines, ink, symbologies).c_str());
+  if (via == kViaHostLocal) ink_in_ok(what, img, h, w, row_stride, rule.radius, rule.drop, rule.polarity);
+  std::vector<int32_t> side(kBcSideInts), items((size_t)nq);
+  if (via == kViaEngine) {
+    Engine& E = *e->e;
+    EngineScope lk(E);
+    E.refuse_while_streaming(what);
+    E.barcodes_stage(img, h, w, row_stride, 0, 0, min_lines, ink, symbologies, quads, nq, side.data(), items.data(), nullptr, nullptr);
+  } else {
+    barcodes_from_page(img, h, w, row_stride ? row_stride : w * 3, min_lines, rule, symbologies, side.data(), o.hits, o.line_counts);
+    barcodes_items(side.data(), quad_centres(quads, nq).data(), nq, items.data());
   }
-  return (int)inside;
-}
-
-static void barcodes_out(const int32_t* side, const int32_t* items, int nq, int32_t* mode, int32_t* counts, int32_t* barcodes, int32_t* item_barcode) {
-  if (mode) *mode = side[0];
-  if (counts) std::copy(side + 1, side + 7, counts);
-  if (barcodes) std::copy(side + kBcHdr, side + kBcHdr + (size_t)kBcRec * side[1], barcodes);
-  if (item_barcode) std::copy(items, items + nq, item_barcode);
-}
-
-static void barcodes_in_ok(const char* what, const uint8_t* img, int h, int w, int row_stride, int min_lines, int ink, int symbologies, const float* quads, int nq) {
-  if (nq < 0 || (nq > 0 && !quads)) throw std::runtime_error("null argument");
-  page_image_ok(what, img, h, w, row_stride, 32768);
-  if (!barcodes_args_ok(min_lines, ink, symbologies)) throw std::runtime_error(std::string(what) + ": " + barcodes_ranges(min_lines, ink, symbologies));
-  page_quads_ok(what, quads, nq);
-}
-
-static void barcodes_host_items(const int32_t* side, const float* quads, int nq, int32_t* items) {
-  std::vector<int32_t> centres((size_t)nq * 2);
-  for (int i = 0; i < nq; ++i) tables_word_centre(quads + 8 * (size_t)i, &centres[2 * (size_t)i]);
-  barcodes_items(side, centres.data(), nq, items);
+  if (o.mode) *o.mode = side[0];
+  if (o.counts) std::copy(side.begin() + 1, side.begin() + 7, o.counts);
+  if (o.barcodes) std::copy(side.begin() + kBcHdr, side.begin() + kBcHdr + (size_t)kBcRec * side[1], o.barcodes);
+  if (o.item_barcode) std::copy(items.begin(), items.end(), o.item_barcode);
+  return 0;
+  TTR_GUARD_END(-1)
 }
 
 int ttr_barcodes_from_page(const uint8_t* img, int h, int w, int row_stride, int min_lines, int ink, int symbologies, const float* quads, int nq, int32_t* mode,
                            int32_t* counts, int32_t* barcodes, int32_t* item_barcode, int32_t* hits, int32_t* line_counts) {
-  TTR_GUARD_BEGIN
-  barcodes_in_ok("ttr_barcodes_from_page", img, h, w, row_stride, min_lines, ink, symbologies, quads, nq);
-  std::vector<int32_t> side(kBcSideInts), items((size_t)nq);
-  barcodes_from_page(img, h, w, row_stride ? row_stride : w * 3, min_lines, ink, symbologies, side.data(), hits, line_counts);
-  barcodes_host_items(side.data(), quads, nq, items.data());
-  barcodes_out(side.data(), items.data(), nq, mode, counts, barcodes, item_barcode);
-  return 0;
-  TTR_GUARD_END(-1)
+  return barcodes_call("ttr_barcodes_from_page", kViaHost, nullptr, img, h, w, row_stride, min_lines, ink, symbologies, quads, nq,
+                       {mode, counts, barcodes, item_barcode, hits, line_counts});
 }
 
 int ttr_barcodes_from_page_ink(const uint8_t* img, int h, int w, int row_stride, int min_lines, int symbologies, int radius, int drop, int polarity, const float* quads,
                                int nq, int32_t* mode, int32_t* counts, int32_t* barcodes, int32_t* item_barcode) {
-  TTR_GUARD_BEGIN
-  barcodes_in_ok("ttr_barcodes_from_page_ink", img, h, w, row_stride, min_lines, 128, symbologies, quads, nq);
-  ink_in_ok("ttr_barcodes_from_page_ink", img, h, w, row_stride, radius, drop, polarity);
-  std::vector<int32_t> side(kBcSideInts), items((size_t)nq);
-  barcodes_from_page_ink(img, h, w, row_stride ? row_stride : w * 3, min_lines, symbologies, radius, drop, polarity, side.data());
-  barcodes_host_items(side.data(), quads, nq, items.data());
-  barcodes_out(side.data(), items.data(), nq, mode, counts, barcodes, item_barcode);
-  return 0;
-  TTR_GUARD_END(-1)
+  return barcodes_call("ttr_barcodes_from_page_ink", kViaHostLocal, nullptr, img, h, w, row_stride, min_lines, InkRule::local(radius, drop, polarity), symbologies, quads, nq,
+                       {mode, counts, barcodes, item_barcode, nullptr, nullptr});
 }
 
 int ttr_barcodes_page(ttr_engine* e, const uint8_t* img, int h, int w, int row_stride, int min_lines, int ink, int symbologies, const float* quads, int nq, int32_t* mode,
                       int32_t* counts, int32_t* barcodes, int32_t* item_barcode) {
-  TTR_GUARD_BEGIN
-  if (!e) throw std::runtime_error("null argument");
-  barcodes_in_ok("ttr_barcodes_page", img, h, w, row_stride, min_lines, ink, symbologies, quads, nq);
-  Engine& E = *e->e;
-  EngineScope lk(E);
-  E.refuse_while_streaming("ttr_barcodes_page");
-  std::vector<int32_t> side(kBcSideInts), items((size_t)nq);
-  E.barcodes_stage(img, h, w, row_stride, 0, 0, min_lines, ink, symbologies, quads, nq, side.data(), items.data(), nullptr, nullptr);
-  barcodes_out(side.data(), items.data(), nq, mode, counts, barcodes, item_barcode);
-  return 0;
-  TTR_GUARD_END(-1)
+  return barcodes_call("ttr_barcodes_page", kViaEngine, e, img, h, w, row_stride, min_lines, ink, symbologies, quads, nq,
+                       {mode, counts, barcodes, item_barcode, nullptr, nullptr});
 }
 
 int ttr_result_alt_k(const ttr_result* r) { return r ? r->r.alt_k : 0; }

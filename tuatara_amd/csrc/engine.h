@@ -1136,16 +1136,23 @@ struct Engine {
   void plan_wide(PageBatch& B, const float* quads);
   // curved words: one CurveIn per crop of B from quads [N][8] (the quads plan_wide takes) under the engine's `curved`.  Host only; a no-op with curved off.
   void plan_curved(PageBatch& B, const float* quads);
-  // tables: the two kernels of batch B behind its packer (the centres and page offsets travelled with the rectangles' upload); a no-op with tables off
-  void tables_enqueue(const PageBatch& B, int sl);
-  // the ink pass of batch B into tab_bits / tab_bitsT (the fixed rule under `ink`, or the local rule and its records when the batch has a radius): tables_enqueue's
-  // and marks_enqueue's first step, run once per batch
+  // The ink readers of a batch - tables, selection marks, barcodes (DESIGN.md "Adding a page layer").  batch_bits says which rule formed this batch's tab_bits /
+  // tab_bitsT: none yet, the local one, or the fixed one under that threshold (1..255); batch_offsets_up, that a batch without words has its zero offsets on
+  // the device.  recog_enqueue resets both.  page_ink_enqueue is the only place that decides on a pass: it returns when the bitmaps in place are those of the
+  // rule asked for (the local one when the batch has a radius, else the fixed one under `ink`), else enqueues the pass - and with the local rule its records -
+  // and counts it in page_ink_passes
+  static constexpr int kBitsNone = -1, kBitsLocal = 0;
+  int batch_bits = kBitsNone;
+  bool batch_offsets_up = false;
   void page_ink_enqueue(const PageBatch& B, int sl, int ink);
-  // selection marks: the two kernels of batch B behind its packer, or - for a batch without words - on their own; the ink pass first unless tables_enqueue ran it.
-  // A no-op with marks off
+  // what a reader's launches take of the batch: the extent its workspaces are sized by, the first page, the page table (mixed batches, else null), 64 x the
+  // words' centres [N][2] and the pages' offsets [n + 1] behind them (for a batch without words: n + 1 zeros, uploaded by the first reader that asks)
+  struct LayerBatch { int n, N, Hcap, Wcap; const Page& P0; const PageRow* table; const int* centres; const int* first; };
+  LayerBatch layer_batch(const PageBatch& B, int sl);
+  void layer_batch_done(const LayerBatch& L, int sl);   // behind a reader's last kernel: the page table's last reader of this batch so far
+  // each reader's two kernels of batch B behind its packer, or - marks and barcodes, for a batch without words - on their own; a no-op with the layer off
+  void tables_enqueue(const PageBatch& B, int sl);
   void marks_enqueue(const PageBatch& B, int sl);
-  // barcodes: the two kernels of batch B behind its packer, or - for a batch without words - on their own; the ink pass first unless tables_enqueue or
-  // marks_enqueue left this batch's bitmaps under the same rule.  A no-op with barcodes off
   void barcodes_enqueue(const PageBatch& B, int sl);
   // the stage form (ttr_barcodes_page, and the developer hook): through table_ink_kernel, barcode_scan_kernel and barcode_page_kernel -> side [kBcSideInts],
   // item_barcode [nq], hits [(h + w) 2 8][20], cnt [(h + w) 2][4]
@@ -1160,6 +1167,16 @@ struct Engine {
                         const char* bad_args = nullptr, bool check = true);
   void stage_centres(const char* what, const float* quads, int nq);
   const PageRow* staged_page_table(const StagedPage& pg, int h, int w);   // ... and the staged page as the one row of slot 0's page table (the stage calls' use_table)
+  // The ink readers' stage forms open and close alike.  stage_ink_page: stage_page under the 32768 px cap and the layer's refusal, stage_centres, the two
+  // bitmaps under the fixed rule - with `zero`, a workspace of zero_b bytes zeroed ahead of the ink pass, for a hook that returns whole lists.  stage_side_home: the side block [ints] | items [nq][item_ints] and the `extra` arrays whose host pointer is set come home,
+  // one sync; the layer's validator ("the side block holds ..."), the items' range check (noun set: each item is -1 or a record below side[1]); then side_out
+  // gets the counted part - hdr + rec * side[1] ints, the rest zero - and items_out the items
+  StagedPage stage_ink_page(const char* what, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, const char* bad_args, int ink,
+                            const float* quads, int nq, DevBuf* zero = nullptr, size_t zero_b = 0);
+  struct StageSide { const DevBuf* dev; int ints, hdr, rec, item_ints; const char* noun; };
+  struct StageBack { void* host; const DevBuf* dev; size_t bytes; };
+  void stage_side_home(const char* what, const StageSide& s, int nq, std::initializer_list<StageBack> extra, const std::function<bool(const int32_t*, std::string*)>& valid,
+                       int32_t* side_out, int32_t* items_out);
   // the stage form (ttr_marks_page, and the developer hook): as tables_stage, through table_ink_kernel, mark_cand_kernel and mark_page_kernel -> side
   // [kMarkSideInts], item_mark [nq], counts [ceil(h / 32)][2]
   void marks_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_side, int max_side, int fill, int ink, const float* quads,

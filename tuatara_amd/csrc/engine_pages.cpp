@@ -948,7 +948,28 @@ void Engine::curve_crops(const uint8_t* img, int h, int w, int row_stride, const
   if (knots) memcpy(knots, side.data() + curve_side_table_offset(nq), (size_t)nq * 288);
 }
 
+Engine::LayerBatch Engine::layer_batch(const PageBatch& B, int sl) {
+  const auto [Hcap, Wcap] = B.extent();
+  // (detect_enqueue refused a page side of 32768 or more before anything of the batch was enqueued)
+  if (B.N == 0 && !batch_offsets_up) {   // a batch without words has no packer and so no upload: the pages' offsets [n + 1], all 0, go up with the first layer that asks
+    const size_t bytes = ((size_t)B.n + 1) * 4;
+    rects_dev.ensure(bytes); h_rects[sl].ensure(bytes);
+    std::fill(h_rects[sl].as<int32_t>(), h_rects[sl].as<int32_t>() + B.n + 1, 0);
+    TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[sl].p, bytes, hipMemcpyHostToDevice, stream));
+    batch_offsets_up = true;
+  }
+  const int* centres = rects_dev.as<int>() + (B.N ? B.rects.size() : 0);
+  return LayerBatch{B.n, B.N, Hcap, Wcap, B.pages[0], B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr, centres, centres + (size_t)B.N * 2};
+}
+
+void Engine::layer_batch_done(const LayerBatch& L, int sl) {
+  if (L.table) TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the table's last reader of this batch is now the layer's last kernel)
+}
+
 void Engine::page_ink_enqueue(const PageBatch& B, int sl, int ink) {
+  const int want = B.ink_radius ? kBitsLocal : ink;
+  if (batch_bits == want) return;   // the bitmaps in place are this rule's already: whichever layer formed them
+  batch_bits = want;
   const int n = B.n;
   ++page_ink_passes;
   const auto [Hcap, Wcap] = B.extent();
@@ -963,153 +984,111 @@ void Engine::page_ink_enqueue(const PageBatch& B, int sl, int ink) {
   launch_table_ink(P0.data, (size_t)P0.h * P0.w * 3, P0.stride, P0.h, P0.w, table, n, Hcap, Wcap, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
 }
 
+Engine::StagedPage Engine::stage_ink_page(const char* what, const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, const char* bad_args, int ink,
+                                          const float* quads, int nq, DevBuf* zero, size_t zero_b) {
+  // (the image check is stage_page's: both routes here - the ttr_*_page call and the developer hook - have made it under their own names before.  The page's copy
+  // is enqueued before stage_centres looks at the quads; no quad can fail there: the ttr_*_page call has checked them and the hook passes none)
+  const StagedPage pg = stage_page(what, img, h, w, row_stride, dev_offset, dev_stride, 32768, bad_args);
+  stage_centres(what, quads, nq);
+  tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8);
+  if (zero) { zero->ensure(zero_b); TTR_HIP_CHECK(hipMemsetAsync(zero->p, 0, zero_b, stream)); }   // (a hook that returns whole lists)
+  launch_table_ink(pg.data, 0, pg.stride, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  return pg;
+}
+
+void Engine::stage_side_home(const char* what_, const StageSide& s, int nq, std::initializer_list<StageBack> extra, const std::function<bool(const int32_t*, std::string*)>& valid,
+                             int32_t* side_out, int32_t* items_out) {
+  const std::string what(what_);
+  std::vector<int32_t> side((size_t)s.ints + (size_t)nq * s.item_ints);
+  TTR_HIP_CHECK(hipMemcpyAsync(side.data(), s.dev->p, side.size() * 4, hipMemcpyDeviceToHost, stream));
+  for (const StageBack& e : extra)
+    if (e.host) TTR_HIP_CHECK(hipMemcpyAsync(e.host, e.dev->p, e.bytes, hipMemcpyDeviceToHost, stream));
+  TTR_HIP_CHECK(hipStreamSynchronize(stream));
+  std::string why;
+  if (!valid(side.data(), &why)) throw std::runtime_error(what + ": the side block holds " + why);
+  if (s.noun)
+    for (size_t i = s.ints; i < side.size(); ++i)
+      if (side[i] < -1 || side[i] >= side[1]) throw std::runtime_error(what + ": an item names a " + s.noun + " that does not exist");
+  if (side_out) {   // (validated: the counted part is what callers read; the rest is zero as on the host)
+    std::fill(side_out, side_out + s.ints, 0);
+    std::copy(side.begin(), side.begin() + s.hdr + (size_t)s.rec * side[1], side_out);
+  }
+  if (items_out) std::copy(side.begin() + s.ints, side.end(), items_out);
+}
+
 void Engine::tables_enqueue(const PageBatch& B, int sl) {
-  const int n = B.n, N = B.N;
-  const auto [Hcap, Wcap] = B.extent();
-  // (detect_enqueue refused a page side of 32768 or more before anything of the batch was enqueued)
-  tab_runs.ensure((size_t)n * 2 * kTabRunCap * 3 * 4);
-  const size_t side_b = tables_side_bytes(n, N);
+  const LayerBatch L = layer_batch(B, sl);
+  tab_runs.ensure((size_t)L.n * 2 * kTabRunCap * 3 * 4);
+  const size_t side_b = tables_side_bytes(L.n, L.N);
   tab_side.ensure(side_b); h_tab.arm(sl, side_b);
-  const Page& P0 = B.pages[0];
-  const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
-  const int* centres = rects_dev.as<int>() + B.rects.size();
   page_ink_enqueue(B, sl, B.tab_ink);
-  launch_table_grid(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), P0.h, P0.w, table, n, Hcap, Wcap, B.tab_min_len, centres, centres + (size_t)N * 2, tab_runs.as<int>(),
-                    tab_side.as<int>(), tab_side.as<int>() + (size_t)n * kTabSideInts, stream);
-  if (B.mixed) TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the table's last reader of this batch is now this kernel)
+  launch_table_grid(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), L.P0.h, L.P0.w, L.table, L.n, L.Hcap, L.Wcap, B.tab_min_len, L.centres, L.first, tab_runs.as<int>(),
+                    tab_side.as<int>(), tab_side.as<int>() + (size_t)L.n * kTabSideInts, stream);
+  layer_batch_done(L, sl);
 }
 
 void Engine::tables_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_len, int ink, const float* quads, int nq,
                           int32_t* side_out, int32_t* items_out, uint64_t* bits_out, int32_t* runs_out) {
-  // (the image check is stage_page's: both routes here - ttr_tables_page and the developer hook - have made it under their own names before.  The page's copy
-  // is enqueued before stage_centres looks at the quads; no quad can fail there: ttr_tables_page has checked them and the hook passes none - likewise in marks_stage)
-  const StagedPage pg = stage_page("ttr_tables_page", img, h, w, row_stride, dev_offset, dev_stride, 32768, tables_args_ok(min_len, ink) ? nullptr : "min_len must lie in 16..4096 and ink in 1..255");
-  stage_centres("ttr_tables_page", quads, nq);
-  const size_t side_b = tables_side_bytes(1, nq);
-  tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8); tab_runs.ensure((size_t)2 * kTabRunCap * 3 * 4); tab_side.ensure(side_b);
-  TTR_HIP_CHECK(hipMemsetAsync(tab_runs.p, 0, (size_t)2 * kTabRunCap * 3 * 4, stream));   // (the hook returns whole lists)
-  launch_table_ink(pg.data, 0, pg.stride, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  const size_t runs_b = (size_t)2 * kTabRunCap * 3 * 4;
+  stage_ink_page("ttr_tables_page", img, h, w, row_stride, dev_offset, dev_stride, tables_args_ok(min_len, ink) ? nullptr : "min_len must lie in 16..4096 and ink in 1..255", ink,
+                 quads, nq, &tab_runs, runs_b);
+  tab_side.ensure(tables_side_bytes(1, nq));
   launch_table_grid(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), h, w, nullptr, 1, h, w, min_len, rects_dev.as<int>(), rects_dev.as<int>() + (size_t)nq * 2, tab_runs.as<int>(),
                     tab_side.as<int>(), tab_side.as<int>() + kTabSideInts, stream);
-  std::vector<int32_t> side(side_b / 4);
-  TTR_HIP_CHECK(hipMemcpyAsync(side.data(), tab_side.p, side_b, hipMemcpyDeviceToHost, stream));
-  if (bits_out) TTR_HIP_CHECK(hipMemcpyAsync(bits_out, tab_bits.p, tables_bits_slot(h, w) * 8, hipMemcpyDeviceToHost, stream));
-  if (runs_out) TTR_HIP_CHECK(hipMemcpyAsync(runs_out, tab_runs.p, (size_t)2 * kTabRunCap * 3 * 4, hipMemcpyDeviceToHost, stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(stream));
-  std::string why;
-  if (!tables_side_valid(side.data(), &why)) throw std::runtime_error("ttr_tables_page: the side block holds " + why);
-  if (side_out) std::copy(side.begin(), side.begin() + kTabSideInts, side_out);   // (validated: the counted part is what callers read)
-  if (items_out) std::copy(side.begin() + kTabSideInts, side.end(), items_out);
+  // (tables hand out the whole block, not the counted part: hdr = kTabSideInts, no records behind it)
+  stage_side_home("ttr_tables_page", StageSide{&tab_side, kTabSideInts, kTabSideInts, 0, 2, nullptr}, nq, {{bits_out, &tab_bits, tables_bits_slot(h, w) * 8}, {runs_out, &tab_runs, runs_b}},
+                  [&](const int32_t* side, std::string* why) { return tables_side_valid(side, why); }, side_out, items_out);
 }
 
 void Engine::marks_enqueue(const PageBatch& B, int sl) {
-  const int n = B.n, N = B.N;
-  const auto [Hcap, Wcap] = B.extent();
-  // (detect_enqueue refused a page side of 32768 or more before anything of the batch was enqueued)
-  mark_cand.ensure(marks_cand_ints(Hcap, n) * 4); mark_counts.ensure(marks_count_ints(Hcap, n) * 4);
-  const size_t side_b = marks_side_bytes(n, N);
+  const LayerBatch L = layer_batch(B, sl);
+  mark_cand.ensure(marks_cand_ints(L.Hcap, L.n) * 4); mark_counts.ensure(marks_count_ints(L.Hcap, L.n) * 4);
+  const size_t side_b = marks_side_bytes(L.n, L.N);
   mark_side.ensure(side_b); h_mark.arm(sl, side_b);
-  const Page& P0 = B.pages[0];
-  const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
-  const int* centres = rects_dev.as<int>() + B.rects.size();
-  if (N == 0) {   // a batch without words has no packer and so no upload: the pages' offsets [n + 1], all 0, go up here
-    rects_dev.ensure(((size_t)n + 1) * 4); h_rects[sl].ensure(((size_t)n + 1) * 4);
-    std::fill(h_rects[sl].as<int32_t>(), h_rects[sl].as<int32_t>() + n + 1, 0);
-    TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[sl].p, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, stream));
-    centres = rects_dev.as<int>();
-  }
-  // the bitmaps: the tables pass's when it ran in this batch under the same rule (the local one, or the fixed one with the same `ink`), else formed here
-  const bool shared = B.tab_min_len && N > 0 && (B.ink_radius || B.tab_ink == B.mark_ink);
-  if (!shared) page_ink_enqueue(B, sl, B.mark_ink);
-  launch_mark_cand(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), P0.h, P0.w, table, n, Hcap, Wcap, B.mark_min, B.mark_max, B.mark_fill, mark_cand.as<int>(),
+  page_ink_enqueue(B, sl, B.mark_ink);
+  launch_mark_cand(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), L.P0.h, L.P0.w, L.table, L.n, L.Hcap, L.Wcap, B.mark_min, B.mark_max, B.mark_fill, mark_cand.as<int>(),
                    mark_counts.as<int>(), stream);
-  launch_mark_page(mark_cand.as<int>(), mark_counts.as<int>(), n, Hcap, centres, centres + (size_t)N * 2, mark_side.as<int>(), mark_side.as<int>() + (size_t)n * kMarkSideInts, stream);
-  if (B.mixed) TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the table's last reader of this batch is now this kernel)
+  launch_mark_page(mark_cand.as<int>(), mark_counts.as<int>(), L.n, L.Hcap, L.centres, L.first, mark_side.as<int>(), mark_side.as<int>() + (size_t)L.n * kMarkSideInts, stream);
+  layer_batch_done(L, sl);
 }
 
 void Engine::marks_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_side, int max_side, int fill, int ink, const float* quads,
                          int nq, int32_t* side_out, int32_t* item_mark_out, int32_t* counts_out) {
-  const StagedPage pg = stage_page("ttr_marks_page", img, h, w, row_stride, dev_offset, dev_stride, 32768,
-                                   marks_args_ok(min_side, max_side, fill, ink) ? nullptr : "min_side must lie in 8..64, max_side in min_side..128, fill and ink in 1..255");
-  stage_centres("ttr_marks_page", quads, nq);
-  const size_t side_b = marks_side_bytes(1, nq), cnt_b = marks_count_ints(h, 1) * 4;
-  tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8);
-  mark_cand.ensure(marks_cand_ints(h, 1) * 4); mark_counts.ensure(cnt_b); mark_side.ensure(side_b);
-  launch_table_ink(pg.data, 0, pg.stride, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  stage_ink_page("ttr_marks_page", img, h, w, row_stride, dev_offset, dev_stride,
+                 marks_args_ok(min_side, max_side, fill, ink) ? nullptr : "min_side must lie in 8..64, max_side in min_side..128, fill and ink in 1..255", ink, quads, nq);
+  const size_t cnt_b = marks_count_ints(h, 1) * 4;
+  mark_cand.ensure(marks_cand_ints(h, 1) * 4); mark_counts.ensure(cnt_b); mark_side.ensure(marks_side_bytes(1, nq));
   launch_mark_cand(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), h, w, nullptr, 1, h, w, min_side, max_side, fill, mark_cand.as<int>(), mark_counts.as<int>(), stream);
   launch_mark_page(mark_cand.as<int>(), mark_counts.as<int>(), 1, h, rects_dev.as<int>(), rects_dev.as<int>() + (size_t)nq * 2, mark_side.as<int>(),
                    mark_side.as<int>() + kMarkSideInts, stream);
-  std::vector<int32_t> side(side_b / 4);
-  TTR_HIP_CHECK(hipMemcpyAsync(side.data(), mark_side.p, side_b, hipMemcpyDeviceToHost, stream));
-  if (counts_out) TTR_HIP_CHECK(hipMemcpyAsync(counts_out, mark_counts.p, cnt_b, hipMemcpyDeviceToHost, stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(stream));
-  std::string why;
-  if (!marks_side_valid(side.data(), h, w, fill, nq, &why)) throw std::runtime_error("ttr_marks_page: the side block holds " + why);
-  for (int i = 0; i < nq; ++i)
-    if (side[kMarkSideInts + (size_t)i] < -1 || side[kMarkSideInts + (size_t)i] >= side[1]) throw std::runtime_error("ttr_marks_page: an item names a mark that does not exist");
-  if (side_out) {   // (validated: the counted part is what callers read; the rest is zero as on the host)
-    std::fill(side_out, side_out + kMarkSideInts, 0);
-    std::copy(side.begin(), side.begin() + kMarkHdr + (size_t)kMarkRec * side[1], side_out);
-  }
-  if (item_mark_out) std::copy(side.begin() + kMarkSideInts, side.end(), item_mark_out);
+  stage_side_home("ttr_marks_page", StageSide{&mark_side, kMarkSideInts, kMarkHdr, kMarkRec, 1, "mark"}, nq, {{counts_out, &mark_counts, cnt_b}},
+                  [&](const int32_t* side, std::string* why) { return marks_side_valid(side, h, w, fill, nq, why); }, side_out, item_mark_out);
 }
 
 void Engine::barcodes_enqueue(const PageBatch& B, int sl) {
-  const int n = B.n, N = B.N;
-  const auto [Hcap, Wcap] = B.extent();
-  // (detect_enqueue refused a page side of 32768 or more before anything of the batch was enqueued)
-  bc_hits.ensure(barcodes_hit_ints(Hcap, Wcap, n) * 4); bc_cnt.ensure(barcodes_count_ints(Hcap, Wcap, n) * 4);
-  const size_t side_b = barcodes_side_bytes(n, N);
+  const LayerBatch L = layer_batch(B, sl);
+  bc_hits.ensure(barcodes_hit_ints(L.Hcap, L.Wcap, L.n) * 4); bc_cnt.ensure(barcodes_count_ints(L.Hcap, L.Wcap, L.n) * 4);
+  const size_t side_b = barcodes_side_bytes(L.n, L.N);
   bc_side.ensure(side_b); h_barcode.arm(sl, side_b);
-  const Page& P0 = B.pages[0];
-  const PageRow* table = B.mixed ? page_table[sl & 1].as<PageRow>() : nullptr;
-  const int* centres = rects_dev.as<int>() + B.rects.size();
-  if (N == 0) {   // a batch without words has no packer and so no upload: the pages' offsets [n + 1], all 0, go up here unless marks_enqueue sent them
-    if (!B.mark_min) {
-      rects_dev.ensure(((size_t)n + 1) * 4); h_rects[sl].ensure(((size_t)n + 1) * 4);
-      std::fill(h_rects[sl].as<int32_t>(), h_rects[sl].as<int32_t>() + n + 1, 0);
-      TTR_HIP_CHECK(hipMemcpyAsync(rects_dev.p, h_rects[sl].p, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, stream));
-    }
-    centres = rects_dev.as<int>();
-  }
-  // the bitmaps: those the batch's last ink pass left - marks' when it ran, else tables' - when that pass was under the same rule (the local one, or the fixed
-  // one with the same `ink`), else formed here
-  const bool tabs = B.tab_min_len && N > 0;
-  const bool shared = (B.mark_min || tabs) && (B.ink_radius || (B.mark_min ? B.mark_ink : B.tab_ink) == B.bc_ink);
-  if (!shared) page_ink_enqueue(B, sl, B.bc_ink);
-  launch_barcode_scan(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), P0.h, P0.w, table, n, Hcap, Wcap, B.bc_sym, bc_hits.as<int>(), bc_cnt.as<int>(), stream);
-  launch_barcode_page(bc_hits.as<int>(), bc_cnt.as<int>(), P0.h, P0.w, table, n, Hcap, Wcap, B.bc_min, centres, centres + (size_t)N * 2, bc_side.as<int>(),
-                      bc_side.as<int>() + (size_t)n * kBcSideInts, stream);
-  if (B.mixed) TTR_HIP_CHECK(hipEventRecord(table_ev[sl & 1], stream));   // (the table's last reader of this batch is now this kernel)
+  page_ink_enqueue(B, sl, B.bc_ink);
+  launch_barcode_scan(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), L.P0.h, L.P0.w, L.table, L.n, L.Hcap, L.Wcap, B.bc_sym, bc_hits.as<int>(), bc_cnt.as<int>(), stream);
+  launch_barcode_page(bc_hits.as<int>(), bc_cnt.as<int>(), L.P0.h, L.P0.w, L.table, L.n, L.Hcap, L.Wcap, B.bc_min, L.centres, L.first, bc_side.as<int>(),
+                      bc_side.as<int>() + (size_t)L.n * kBcSideInts, stream);
+  layer_batch_done(L, sl);
 }
 
 void Engine::barcodes_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int min_lines, int ink, int symbologies, const float* quads,
                             int nq, int32_t* side_out, int32_t* item_out, int32_t* hits_out, int32_t* cnt_out) {
-  const StagedPage pg = stage_page("ttr_barcodes_page", img, h, w, row_stride, dev_offset, dev_stride, 32768,
-                                   barcodes_args_ok(min_lines, ink, symbologies) ? nullptr : "min_lines must lie in 4..256, ink in 1..255 and symbologies in 1..3");
-  stage_centres("ttr_barcodes_page", quads, nq);
-  const size_t side_b = barcodes_side_bytes(1, nq), hit_b = barcodes_hit_ints(h, w, 1) * 4, cnt_b = barcodes_count_ints(h, w, 1) * 4;
-  tab_bits.ensure(tables_bits_slot(h, w) * 8); tab_bitsT.ensure(tables_bitsT_slot(h, w) * 8);
-  bc_hits.ensure(hit_b); bc_cnt.ensure(cnt_b); bc_side.ensure(side_b);
-  if (hits_out) TTR_HIP_CHECK(hipMemsetAsync(bc_hits.p, 0, hit_b, stream));   // (the hook returns whole slot lists)
-  launch_table_ink(pg.data, 0, pg.stride, h, w, nullptr, 1, h, w, ink, tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), stream);
+  const size_t hit_b = barcodes_hit_ints(h, w, 1) * 4, cnt_b = barcodes_count_ints(h, w, 1) * 4;
+  stage_ink_page("ttr_barcodes_page", img, h, w, row_stride, dev_offset, dev_stride,
+                 barcodes_args_ok(min_lines, ink, symbologies) ? nullptr : "min_lines must lie in 4..256, ink in 1..255 and symbologies in 1..3", ink, quads, nq,
+                 hits_out ? &bc_hits : nullptr, hit_b);
+  bc_hits.ensure(hit_b); bc_cnt.ensure(cnt_b); bc_side.ensure(barcodes_side_bytes(1, nq));
   launch_barcode_scan(tab_bits.as<uint64_t>(), tab_bitsT.as<uint64_t>(), h, w, nullptr, 1, h, w, symbologies, bc_hits.as<int>(), bc_cnt.as<int>(), stream);
   launch_barcode_page(bc_hits.as<int>(), bc_cnt.as<int>(), h, w, nullptr, 1, h, w, min_lines, rects_dev.as<int>(), rects_dev.as<int>() + (size_t)nq * 2, bc_side.as<int>(),
                       bc_side.as<int>() + kBcSideInts, stream);
-  std::vector<int32_t> side(side_b / 4);
-  TTR_HIP_CHECK(hipMemcpyAsync(side.data(), bc_side.p, side_b, hipMemcpyDeviceToHost, stream));
-  if (hits_out) TTR_HIP_CHECK(hipMemcpyAsync(hits_out, bc_hits.p, hit_b, hipMemcpyDeviceToHost, stream));
-  if (cnt_out) TTR_HIP_CHECK(hipMemcpyAsync(cnt_out, bc_cnt.p, cnt_b, hipMemcpyDeviceToHost, stream));
-  TTR_HIP_CHECK(hipStreamSynchronize(stream));
-  std::string why;
-  if (!barcodes_side_valid(side.data(), h, w, min_lines, symbologies, &why)) throw std::runtime_error("ttr_barcodes_page: the side block holds " + why);
-  for (int i = 0; i < nq; ++i)
-    if (side[kBcSideInts + (size_t)i] < -1 || side[kBcSideInts + (size_t)i] >= side[1]) throw std::runtime_error("ttr_barcodes_page: an item names a barcode that does not exist");
-  if (side_out) {   // (validated: the counted part is what callers read; the rest is zero as on the host)
-    std::fill(side_out, side_out + kBcSideInts, 0);
-    std::copy(side.begin(), side.begin() + kBcHdr + (size_t)kBcRec * side[1], side_out);
-  }
-  if (item_out) std::copy(side.begin() + kBcSideInts, side.end(), item_out);
+  stage_side_home("ttr_barcodes_page", StageSide{&bc_side, kBcSideInts, kBcHdr, kBcRec, 1, "barcode"}, nq, {{hits_out, &bc_hits, hit_b}, {cnt_out, &bc_cnt, cnt_b}},
+                  [&](const int32_t* side, std::string* why) { return barcodes_side_valid(side, h, w, min_lines, symbologies, why); }, side_out, item_out);
 }
 
 void Engine::ink_stage(const uint8_t* img, int h, int w, int row_stride, int dev_offset, int dev_stride, int radius, int drop, int polarity, uint64_t* bits_out,
@@ -1132,6 +1111,7 @@ void Engine::ink_stage(const uint8_t* img, int h, int w, int row_stride, int dev
 
 void Engine::recog_enqueue(PageBatch& B) {
   const int N = B.N, sl = B.slot;
+  batch_bits = kBitsNone; batch_offsets_up = false;   // this batch's bitmaps and zero offsets: nothing in place yet (engine.h)
   // the slot's side-block records: disarmed, then armed by each layer that runs for this batch (engine.h: SideCopy)
   for (SideCopy* c : {&h_orient, &h_lines, &h_blocks, &h_chars, &h_alts, &h_lex, &h_pat_logp, &h_wide, &h_curve, &h_tab, &h_tab_ink, &h_mark, &h_barcode}) c->disarm(sl);
   const int line_words = cfg.lines && N > 0 ? stage_batch_lines(B, sl) : 0;   // text lines: the host part, before anything of this batch is enqueued

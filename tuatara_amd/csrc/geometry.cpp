@@ -1273,22 +1273,23 @@ int tables_runs(const uint64_t* bits, int h, int w, int dir, int32_t* runs) {
   return n;
 }
 
-int tables_from_page(const uint8_t* image, int h, int w, int stride, int min_len, int ink, int32_t* side, int32_t* runs_out, uint64_t* bits_out) {
-  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !tables_args_ok(min_len, ink))
-    throw std::runtime_error("tables_from_page: bad argument");
+static bool page_args_ok(const uint8_t* image, int h, int w, int stride, const int32_t* side, const InkRule& rule) {
+  return image && side && h > 0 && w > 0 && h < 32768 && w < 32768 && stride >= 3 * w && (!rule.radius || ink_args_ok(rule.radius, rule.drop, rule.polarity));
+}
+
+void ink_bits(const uint8_t* image, int h, int w, int stride, const InkRule& rule, uint64_t* bits, uint64_t* bitsT) {
+  if (rule.radius) return ink_from_page(image, h, w, stride, rule.radius, rule.drop, rule.polarity, bits, bitsT, nullptr);
+  tables_ink(image, h, w, stride, rule.ink, bits);
+  if (bitsT) marks_transpose(bits, h, w, bitsT);
+}
+
+int tables_from_page(const uint8_t* image, int h, int w, int stride, int min_len, const InkRule& rule, int32_t* side, int32_t* runs_out, uint64_t* bits_out) {
+  if (!page_args_ok(image, h, w, stride, side, rule) || !tables_args_ok(min_len, rule.layer_ink())) throw std::runtime_error("tables_from_page: bad argument");
   std::vector<uint64_t> own_bits;
   uint64_t* bits = bits_out;
   if (!bits) { own_bits.resize(tables_bitmap_words(h, w)); bits = own_bits.data(); }
-  tables_ink(image, h, w, stride, ink, bits);
+  ink_bits(image, h, w, stride, rule, bits, nullptr);
   return tables_from_bits(bits, h, w, min_len, side, runs_out);
-}
-
-int tables_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_len, int radius, int drop, int polarity, int32_t* side) {
-  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !tables_args_ok(min_len, 128) || !ink_args_ok(radius, drop, polarity))
-    throw std::runtime_error("tables_from_page_ink: bad argument");
-  std::vector<uint64_t> bits(tables_bitmap_words(h, w));
-  ink_from_page(image, h, w, stride, radius, drop, polarity, bits.data(), nullptr, nullptr);
-  return tables_from_bits(bits.data(), h, w, min_len, side, nullptr);
 }
 
 // steps 2 - 7 behind a ready bitmap: the one body of the rule, whichever ink rule made the bits
@@ -1457,16 +1458,10 @@ void deskew_resample(const uint8_t* image, int h, int w, int stride, int C, int 
     for (int x = 0; x < w; ++x) dsk_pixel(image, h, w, stride, C, S, x, y, out + (size_t)y * out_stride + 3 * (size_t)x);
 }
 
-void deskew_from_page(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, int ink, uint8_t* out, int out_stride, DeskewRec* rec, uint64_t* scores) {
+void deskew_from_page(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, const InkRule& rule, uint8_t* out, int out_stride, DeskewRec* rec,
+                      uint64_t* scores) {
   std::vector<uint64_t> bits(tables_bitmap_words(h, w));
-  tables_ink(image, h, w, stride, ink, bits.data());
-  deskew_from_bits(bits.data(), image, h, w, stride, max_slope, gain, out, out_stride, rec, scores);
-}
-
-void deskew_from_page_ink(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, int radius, int drop, int polarity, uint8_t* out, int out_stride,
-                          DeskewRec* rec, uint64_t* scores) {
-  std::vector<uint64_t> bits(tables_bitmap_words(h, w));
-  ink_from_page(image, h, w, stride, radius, drop, polarity, bits.data(), nullptr, nullptr);
+  ink_bits(image, h, w, stride, rule, bits.data(), nullptr);
   deskew_from_bits(bits.data(), image, h, w, stride, max_slope, gain, out, out_stride, rec, scores);
 }
 
@@ -1601,21 +1596,11 @@ void marks_items(int32_t* side, const int32_t* centres, int n, int32_t* item_mar
   }
 }
 
-int marks_from_page(const uint8_t* image, int h, int w, int stride, int min_side, int max_side, int fill, int ink, int32_t* side, int32_t* counts) {
-  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !marks_args_ok(min_side, max_side, fill, ink))
-    throw std::runtime_error("marks_from_page: bad argument");
+int marks_from_page(const uint8_t* image, int h, int w, int stride, int min_side, int max_side, int fill, const InkRule& rule, int32_t* side, int32_t* counts) {
+  if (!page_args_ok(image, h, w, stride, side, rule) || !marks_args_ok(min_side, max_side, fill, rule.layer_ink())) throw std::runtime_error("marks_from_page: bad argument");
   std::vector<uint64_t> bits(tables_bitmap_words(h, w)), bitsT(tables_bitmap_words(w, h));
-  tables_ink(image, h, w, stride, ink, bits.data());
-  marks_transpose(bits.data(), h, w, bitsT.data());
+  ink_bits(image, h, w, stride, rule, bits.data(), bitsT.data());
   return marks_from_bits(bits.data(), bitsT.data(), h, w, min_side, max_side, fill, side, counts);
-}
-
-int marks_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_side, int max_side, int fill, int radius, int drop, int polarity, int32_t* side) {
-  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !marks_args_ok(min_side, max_side, fill, 128) || !ink_args_ok(radius, drop, polarity))
-    throw std::runtime_error("marks_from_page_ink: bad argument");
-  std::vector<uint64_t> bits(tables_bitmap_words(h, w)), bitsT(tables_bitmap_words(w, h));
-  ink_from_page(image, h, w, stride, radius, drop, polarity, bits.data(), bitsT.data(), nullptr);
-  return marks_from_bits(bits.data(), bitsT.data(), h, w, min_side, max_side, fill, side, nullptr);
 }
 
 bool marks_side_valid(const int32_t* s, int h, int w, int fill, int items, std::string* why) {
@@ -1702,21 +1687,11 @@ void barcodes_items(const int32_t* side, const int32_t* centres, int n, int32_t*
   for (int i = 0; i < n; ++i) item_barcode[i] = bc_item(side, centres[2 * (size_t)i], centres[2 * (size_t)i + 1]);
 }
 
-int barcodes_from_page(const uint8_t* image, int h, int w, int stride, int min_lines, int ink, int symbologies, int32_t* side, int32_t* hits, int32_t* cnt) {
-  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !barcodes_args_ok(min_lines, ink, symbologies))
-    throw std::runtime_error("barcodes_from_page: bad argument");
+int barcodes_from_page(const uint8_t* image, int h, int w, int stride, int min_lines, const InkRule& rule, int symbologies, int32_t* side, int32_t* hits, int32_t* cnt) {
+  if (!page_args_ok(image, h, w, stride, side, rule) || !barcodes_args_ok(min_lines, rule.layer_ink(), symbologies)) throw std::runtime_error("barcodes_from_page: bad argument");
   std::vector<uint64_t> bits(tables_bitmap_words(h, w)), bitsT(tables_bitmap_words(w, h));
-  tables_ink(image, h, w, stride, ink, bits.data());
-  marks_transpose(bits.data(), h, w, bitsT.data());
+  ink_bits(image, h, w, stride, rule, bits.data(), bitsT.data());
   return barcodes_from_bits(bits.data(), bitsT.data(), h, w, min_lines, symbologies, side, hits, cnt);
-}
-
-int barcodes_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_lines, int symbologies, int radius, int drop, int polarity, int32_t* side) {
-  if (!image || !side || h <= 0 || w <= 0 || h >= 32768 || w >= 32768 || stride < 3 * w || !barcodes_args_ok(min_lines, 128, symbologies) || !ink_args_ok(radius, drop, polarity))
-    throw std::runtime_error("barcodes_from_page_ink: bad argument");
-  std::vector<uint64_t> bits(tables_bitmap_words(h, w)), bitsT(tables_bitmap_words(w, h));
-  ink_from_page(image, h, w, stride, radius, drop, polarity, bits.data(), bitsT.data(), nullptr);
-  return barcodes_from_bits(bits.data(), bitsT.data(), h, w, min_lines, symbologies, side);
 }
 
 bool barcodes_side_valid(const int32_t* s, int h, int w, int min_lines, int symbologies, std::string* why) {

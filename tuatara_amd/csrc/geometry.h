@@ -139,6 +139,18 @@ void curve_outline(const float* quad8, int flag, const int64_t* table, float* ou
 // what decode_pages accepts from the device: flag 0 or 1, half bands in 0..32, and with flag 1 every knot's C -+ H inside the int32 pixel range
 bool curve_word_valid(const CurveWord& w);
 
+// The ink rule as a value: what forms a page's ink bitmaps for tables, deskew, selection marks and barcodes.  radius 0 = the fixed rule (a pixel is ink when it is
+// darker than `ink`, 1..255), else the local rule (DESIGN.md "Local ink") under radius, drop, polarity - `ink` is then not read, and a layer's own range check
+// receives 128 in its place.  The *_from_page functions below refuse a local rule that ink_args_ok refuses
+struct InkRule {
+  int ink = 0, radius = 0, drop = 0, polarity = 0;
+  InkRule(int ink_) : ink(ink_) {}   // the fixed rule: a threshold is a rule, so a caller with an `ink` passes it as it is
+  static InkRule local(int radius, int drop, int polarity) { InkRule r(0); r.radius = radius; r.drop = drop; r.polarity = polarity; return r; }
+  int layer_ink() const { return radius ? 128 : ink; }
+};
+// bits [h][ceil(w / 64)] and - unless null - bitsT [w][ceil(h / 64)] of a page u8 [h][w][3] under `rule` (tables_ink + marks_transpose, or ink_from_page)
+void ink_bits(const uint8_t* image, int h, int w, int stride, const InkRule& rule, uint64_t* bits, uint64_t* bitsT);
+
 // Tables (ttr_engine_set_tables; DESIGN.md "Tables").  Ruling lines are found in the page's own pixels, grouped into tables, each table's grid and merged cells
 // derived, and every word given its cell.  The integer steps live in tables_rule.h, shared with table_ink_kernel and table_grid_kernel (tables.hip); the side
 // block's layout (kTabSideInts int32) is described there.  All of it is integer arithmetic; min_len must lie in 16..4096 and ink in 1..255.
@@ -151,7 +163,7 @@ void tables_ink(const uint8_t* image, int h, int w, int stride, int ink, uint64_
 int tables_runs(const uint64_t* bits, int h, int w, int dir, int32_t* runs);
 // 1 - 7 on one page: side receives the block (kTabSideInts int32), runs (may be null) [2][kTabRunCap][3] the run lists, bits (may be null) the bitmap.  Returns
 // the mode: 1, or -(step) of the cap that overflowed (the block then holds the mode alone).
-int tables_from_page(const uint8_t* image, int h, int w, int stride, int min_len, int ink, int32_t* side, int32_t* runs = nullptr, uint64_t* bits = nullptr);
+int tables_from_page(const uint8_t* image, int h, int w, int stride, int min_len, const InkRule& rule, int32_t* side, int32_t* runs = nullptr, uint64_t* bits = nullptr);
 // 8: {cx, cy} = 64 x the centre of a quad (8 floats): the sums of llrint(16 x) over its corners; then the words' cells, out [n][2] = table, cell (-1, -1 outside)
 void tables_word_centre(const float* quad8, int32_t c[2]);
 void tables_words(const int32_t* side, const int32_t* centres, int n, int32_t* out);
@@ -175,7 +187,8 @@ void deskew_choose(const uint64_t* scores, int max_slope, int gain, int h, int w
 // 5: out u8 [h][w][3] (rows out_stride bytes apart) = the page turned by the slope whose constants are C, S
 void deskew_resample(const uint8_t* image, int h, int w, int stride, int C, int S, uint8_t* out, int out_stride);
 // 1 - 5 on one page; out, rec, scores may be null
-void deskew_from_page(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, int ink, uint8_t* out, int out_stride, DeskewRec* rec, uint64_t* scores);
+void deskew_from_page(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, const InkRule& rule, uint8_t* out, int out_stride, DeskewRec* rec,
+                      uint64_t* scores);
 // what decode_pages accepts from the device; why (may be null) receives the reason
 bool deskew_rec_valid(const DeskewRec& r, int max_slope, int h, int w, const int32_t* cs, std::string* why = nullptr);
 // 6: n points (x, y) of the upright page -> the caller's page, computed in double
@@ -191,10 +204,6 @@ bool ink_rec_valid(const InkRec& r, int radius, int drop, int polarity, int h, i
 // tables_from_page and deskew_from_page behind a ready bitmap (tables_ink's layout): the one body of each rule
 int tables_from_bits(const uint64_t* bits, int h, int w, int min_len, int32_t* side, int32_t* runs = nullptr);
 void deskew_from_bits(const uint64_t* bits, const uint8_t* image, int h, int w, int stride, int max_slope, int gain, uint8_t* out, int out_stride, DeskewRec* rec, uint64_t* scores);
-// ... and under the local rule in the place of `ink`
-int tables_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_len, int radius, int drop, int polarity, int32_t* side);
-void deskew_from_page_ink(const uint8_t* image, int h, int w, int stride, int max_slope, int gain, int radius, int drop, int polarity, uint8_t* out, int out_stride,
-                          DeskewRec* rec, uint64_t* scores);
 
 // Selection marks (ttr_engine_set_marks; DESIGN.md "Selection marks").  Checkboxes are found on the ink bitmap as small square frames, their state read from the
 // ink inside, every item given its mark and every mark its label.  Every step lives in marks_rule.h, shared with mark_cand_kernel and mark_page_kernel
@@ -206,9 +215,8 @@ void marks_transpose(const uint64_t* bits, int h, int w, uint64_t* bitsT);
 int marks_from_bits(const uint64_t* bits, const uint64_t* bitsT, int h, int w, int min_side, int max_side, int fill, int32_t* side, int32_t* counts = nullptr);
 // step 7: item_mark [n] from the centres [n][2] (tables_word_centre), and every mark's label into the block
 void marks_items(int32_t* side, const int32_t* centres, int n, int32_t* item_mark);
-// 1 - 6 on one page under the fixed ink rule, and under the local rule in the place of `ink`
-int marks_from_page(const uint8_t* image, int h, int w, int stride, int min_side, int max_side, int fill, int ink, int32_t* side, int32_t* counts = nullptr);
-int marks_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_side, int max_side, int fill, int radius, int drop, int polarity, int32_t* side);
+// 1 - 6 on one page under either ink rule
+int marks_from_page(const uint8_t* image, int h, int w, int stride, int min_side, int max_side, int fill, const InkRule& rule, int32_t* side, int32_t* counts = nullptr);
 // what decode_pages accepts from the device: a legal mode, a count within the cap, boxes inside the h x w page with x0 <= x1 and y0 <= y1, interiors inside their
 // boxes, inked <= area = the interior's pixel count, state the rule's on inked / area / fill, labels in -1..items - 1, marks in (y, x) order.  why (may be null)
 // receives the reason.
@@ -222,9 +230,9 @@ bool marks_side_valid(const int32_t* side, int h, int w, int fill, int items, st
 int barcodes_from_bits(const uint64_t* bits, const uint64_t* bitsT, int h, int w, int min_lines, int symbologies, int32_t* side, int32_t* hits = nullptr, int32_t* cnt = nullptr);
 // step 9: item_barcode [n] from the centres [n][2] (tables_word_centre)
 void barcodes_items(const int32_t* side, const int32_t* centres, int n, int32_t* item_barcode);
-// 1 - 8 on one page under the fixed ink rule, and under the local rule in the place of `ink`
-int barcodes_from_page(const uint8_t* image, int h, int w, int stride, int min_lines, int ink, int symbologies, int32_t* side, int32_t* hits = nullptr, int32_t* cnt = nullptr);
-int barcodes_from_page_ink(const uint8_t* image, int h, int w, int stride, int min_lines, int symbologies, int radius, int drop, int polarity, int32_t* side);
+// 1 - 8 on one page under either ink rule
+int barcodes_from_page(const uint8_t* image, int h, int w, int stride, int min_lines, const InkRule& rule, int symbologies, int32_t* side, int32_t* hits = nullptr,
+                       int32_t* cnt = nullptr);
 // what decode_pages accepts from the device: a legal mode, a count within the cap, boxes inside the h x w page, (y0, x0, dir) order, symbology 1 or 2 and one
 // that was asked for, dir 0..3, lines >= min_lines, flags within the mask, len <= 48 and zero bytes beyond it, counters that are not negative.  why (may be
 // null) receives the reason.

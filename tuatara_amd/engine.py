@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import collections.abc
 import ctypes as C
+import functools
 import math
 import os
 import sys
@@ -1058,33 +1059,54 @@ def _quad_pairs(q8) -> list:
 TABLES_MIN_LEN, TABLES_INK = 48, 128   # what tables=True means (DESIGN.md "Tables": neither value has been tuned on documents)
 
 
-def _tables_arg(tables):
-    """False / None / 0 -> (0, TABLES_INK); True -> the defaults; (min_len, ink) or a bare min_len otherwise"""
-    if tables is None or tables is False or (isinstance(tables, int) and not isinstance(tables, bool) and tables == 0):
-        return 0, TABLES_INK
-    if tables is True:
-        return TABLES_MIN_LEN, TABLES_INK
-    if isinstance(tables, (tuple, list)) and len(tables) == 2:
-        return int(tables[0]), int(tables[1])
-    if isinstance(tables, int):
-        return int(tables), TABLES_INK
-    raise EngineError("tables must be False, True or (min_len, ink)")
+def _layer_arg(name, value, fields, defaults):
+    """a page layer's setting as its tuple of ints: False / None / 0 -> off (0, then the other defaults); True -> the defaults; a tuple or list of as many values,
+    or a bare first value, otherwise"""
+    if value is None or value is False or (isinstance(value, int) and not isinstance(value, bool) and value == 0):
+        return (0,) + tuple(defaults[1:])
+    if value is True:
+        return tuple(defaults)
+    if isinstance(value, (tuple, list)) and len(value) == len(defaults):
+        return tuple(int(v) for v in value)
+    if isinstance(value, int):
+        return (int(value),) + tuple(defaults[1:])
+    raise EngineError(f"{name} must be False, True or ({fields})")
 
 
-def _tables_call(fn, image, quads, min_len, ink, row_stride=0):
-    """the shared body of tables_from_page and Engine.tables_page: fn(image..., outputs...) -> the dict both return"""
+_tables_arg = functools.partial(_layer_arg, "tables", fields="min_len, ink", defaults=(TABLES_MIN_LEN, TABLES_INK))
+
+
+def _page_image(image, row_stride=0):
+    """the opening of the one-page calls: a host image u8 [H, W, 3] (row_stride: the bytes from row to row of a view into a wider buffer; 0 = packed, copied
+    when it is not) -> the array, H, W and the stride in bytes"""
     image = np.asarray(image, dtype=np.uint8)
     if image.ndim != 3 or image.shape[2] != 3:
         raise RuntimeError("Input array should have 3 dimensions")
     if not row_stride:
         image = np.ascontiguousarray(image)
+    return image, image.shape[0], image.shape[1], int(row_stride) or image.shape[1] * 3
+
+
+def _page_entry(form, layer, head, ink, tail=(), engine=None):
+    """The library call behind a layer's three one-page wrappers, and its parameter tuple: form "from_page" (the host rule; ink = the threshold), "from_page_ink"
+    (the host rule under the local ink rule; ink = local_ink, True or (radius, drop, polarity), which goes behind the layer's other parameters) or "page" (the
+    engine's stage call).  -> fn(image..., params..., outputs...), params"""
+    sym = getattr(engine.lib if engine else load(), f"ttr_{layer}_{form}")
+    params = head + tail + _local_ink_arg(ink) if form == "from_page_ink" else head + (ink,) + tail
+    if engine:
+        return (lambda *a: engine._check(sym(engine.h, *a))), params
+    return (lambda *a: _lib_check(sym(*a))), params
+
+
+def _tables_call(fn, params, image, quads, row_stride=0):
+    """the shared body of tables_from_page and Engine.tables_page: fn(image..., params..., quads, outputs...) -> the dict both return"""
+    image, h, w, stride = _page_image(image, row_stride)
     q = np.zeros((0, 8), np.float32) if quads is None else np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
     nq, m = len(q), max(len(q), 1)
     mode, counts = np.zeros(1, np.int32), np.zeros(6, np.int32)
     rul, tab, lin, cel = np.zeros((512, 6), np.int32), np.zeros((32, 8), np.int32), np.zeros(32 * 130, np.int32), np.zeros((1024, 9), np.int32)
     it, ic = np.full(m, -1, np.int32), np.full(m, -1, np.int32)
-    fn(_u8(image), image.shape[0], image.shape[1], int(row_stride) or image.shape[1] * 3, int(min_len), int(ink), _f(q), nq, _i(mode), _i(counts), _i(rul), _i(tab), _i(lin),
-       _i(cel), _i(it), _i(ic))
+    fn(_u8(image), h, w, stride, *[int(v) for v in params], _f(q), nq, _i(mode), _i(counts), _i(rul), _i(tab), _i(lin), _i(cel), _i(it), _i(ic))
     return {"mode": int(mode[0]), "rulings": rul[:counts[0]].copy(), "tables": tab[:counts[1]].copy(), "lines": lin[:counts[3]].copy(), "cells": cel[:counts[2]].copy(),
             "item_table": it[:nq].copy(), "item_cell": ic[:nq].copy(), "runs": (int(counts[4]), int(counts[5]))}
 
@@ -1093,30 +1115,16 @@ MARKS_MIN_SIDE, MARKS_MAX_SIDE, MARKS_FILL, MARKS_INK = 10, 64, 24, 128   # what
 MARK_FIELDS = ("x0", "y0", "x1", "y1", "ix0", "iy0", "ix1", "iy1", "inked", "area", "state", "label")
 
 
-def _marks_arg(marks):
-    """False / None / 0 -> off; True -> the defaults; (min_side, max_side, fill, ink) or a bare min_side otherwise"""
-    if marks is None or marks is False or (isinstance(marks, int) and not isinstance(marks, bool) and marks == 0):
-        return 0, MARKS_MAX_SIDE, MARKS_FILL, MARKS_INK
-    if marks is True:
-        return MARKS_MIN_SIDE, MARKS_MAX_SIDE, MARKS_FILL, MARKS_INK
-    if isinstance(marks, (tuple, list)) and len(marks) == 4:
-        return tuple(int(v) for v in marks)
-    if isinstance(marks, int):
-        return int(marks), MARKS_MAX_SIDE, MARKS_FILL, MARKS_INK
-    raise EngineError("marks must be False, True or (min_side, max_side, fill, ink)")
+_marks_arg = functools.partial(_layer_arg, "marks", fields="min_side, max_side, fill, ink", defaults=(MARKS_MIN_SIDE, MARKS_MAX_SIDE, MARKS_FILL, MARKS_INK))
 
 
-def _marks_call(fn, image, quads, params, row_stride=0):
+def _marks_call(fn, params, image, quads, row_stride=0):
     """the shared body of marks_from_page and Engine.marks_page: fn(image..., params..., quads, outputs...) -> the dict both return"""
-    image = np.asarray(image, dtype=np.uint8)
-    if image.ndim != 3 or image.shape[2] != 3:
-        raise RuntimeError("Input array should have 3 dimensions")
-    if not row_stride:
-        image = np.ascontiguousarray(image)
+    image, h, w, stride = _page_image(image, row_stride)
     q = np.zeros((0, 8), np.float32) if quads is None else np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
     nq = len(q)
     mode, counts, marks, im = np.zeros(1, np.int32), np.zeros(3, np.int32), np.zeros((512, 12), np.int32), np.full(max(nq, 1), -1, np.int32)
-    fn(_u8(image), image.shape[0], image.shape[1], int(row_stride) or image.shape[1] * 3, *[int(v) for v in params], _f(q), nq, _i(mode), _i(counts), _i(marks), _i(im))
+    fn(_u8(image), h, w, stride, *[int(v) for v in params], _f(q), nq, _i(mode), _i(counts), _i(marks), _i(im))
     return {"mode": int(mode[0]), "marks": marks[:counts[0]].copy(), "item_mark": im[:nq].copy(), "corners": int(counts[1]), "kept": int(counts[2])}
 
 
@@ -1125,22 +1133,13 @@ def marks_from_page(image, quads=None, min_side: int = MARKS_MIN_SIDE, max_side:
     """The selection-marks rule on the host (ttr_marks_from_page, no GPU; DESIGN.md "Selection marks"): a host image u8 [H, W, 3] (row_stride: the bytes from
     row to row of a view into a wider buffer) and quads f32 [nq, 8] -> {"mode" (1, or -6 beyond 512 marks), "marks" i32 [n, 12] (MARK_FIELDS), "item_mark" i32
     [nq], "corners" (examined), "kept" (candidates, beyond 512 on a page of mode -6)}."""
-    lib = load()
-
-    def fn(*a):
-        _lib_check(lib.ttr_marks_from_page(*a))
-    return _marks_call(fn, image, quads, (min_side, max_side, fill, ink), row_stride)
+    return _marks_call(*_page_entry("from_page", "marks", (min_side, max_side, fill), ink), image=image, quads=quads, row_stride=row_stride)
 
 
 def marks_from_page_ink(image, quads=None, min_side: int = MARKS_MIN_SIDE, max_side: int = MARKS_MAX_SIDE, fill: int = MARKS_FILL, local_ink=True,
                         row_stride: int = 0) -> dict:
     """marks_from_page under the local ink rule (ttr_marks_from_page_ink): local_ink = True or (radius, drop, polarity) in the place of ink"""
-    lib = load()
-    r, d, p = _local_ink_arg(local_ink)
-
-    def fn(*a):
-        _lib_check(lib.ttr_marks_from_page_ink(*a))
-    return _marks_call(fn, image, quads, (min_side, max_side, fill, r, d, p), row_stride)
+    return _marks_call(*_page_entry("from_page_ink", "marks", (min_side, max_side, fill), local_ink), image=image, quads=quads, row_stride=row_stride)
 
 
 def mark_dicts(marks, texts=None) -> list:
@@ -1159,32 +1158,17 @@ BARCODE_SYMBOLOGIES = {1: "code128", 2: "code39"}
 BARCODE_DIRECTIONS = ("left-to-right", "top-to-bottom", "right-to-left", "bottom-to-top")
 
 
-def _barcodes_arg(barcodes):
-    """False / None / 0 -> off; True -> the defaults; (min_lines, ink, symbologies) or a bare min_lines otherwise"""
-    if barcodes is None or barcodes is False or (isinstance(barcodes, int) and not isinstance(barcodes, bool) and barcodes == 0):
-        return 0, BARCODES_INK, BARCODES_SYMBOLOGIES
-    if barcodes is True:
-        return BARCODES_MIN_LINES, BARCODES_INK, BARCODES_SYMBOLOGIES
-    if isinstance(barcodes, (tuple, list)) and len(barcodes) == 3:
-        return tuple(int(v) for v in barcodes)
-    if isinstance(barcodes, int):
-        return int(barcodes), BARCODES_INK, BARCODES_SYMBOLOGIES
-    raise EngineError("barcodes must be False, True or (min_lines, ink, symbologies)")
+_barcodes_arg = functools.partial(_layer_arg, "barcodes", fields="min_lines, ink, symbologies", defaults=(BARCODES_MIN_LINES, BARCODES_INK, BARCODES_SYMBOLOGIES))
 
 
-def _barcodes_call(fn, image, quads, params, row_stride=0, raw=False):
+def _barcodes_call(fn, params, image, quads, row_stride=0, raw=False):
     """the shared body of barcodes_from_page and Engine.barcodes_page: fn(image..., params..., quads, outputs...) -> the dict both return"""
-    image = np.asarray(image, dtype=np.uint8)
-    if image.ndim != 3 or image.shape[2] != 3:
-        raise RuntimeError("Input array should have 3 dimensions")
-    if not row_stride:
-        image = np.ascontiguousarray(image)
+    image, h, w, stride = _page_image(image, row_stride)
     q = np.zeros((0, 8), np.float32) if quads is None else np.ascontiguousarray(quads, dtype=np.float32).reshape(-1, 8)
-    nq, lines = len(q), image.shape[0] + image.shape[1]
+    nq, lines = len(q), h + w
     mode, counts, recs, ib = np.zeros(1, np.int32), np.zeros(6, np.int32), np.zeros((64, 24), np.int32), np.full(max(nq, 1), -1, np.int32)
     extra = [np.zeros((lines, 2, 8, 20), np.int32), np.zeros((lines, 2, 4), np.int32)] if raw else []
-    fn(_u8(image), image.shape[0], image.shape[1], int(row_stride) or image.shape[1] * 3, *[int(v) for v in params], _f(q), nq, _i(mode), _i(counts), _i(recs), _i(ib),
-       *[_i(a) for a in extra])
+    fn(_u8(image), h, w, stride, *[int(v) for v in params], _f(q), nq, _i(mode), _i(counts), _i(recs), _i(ib), *[_i(a) for a in extra])
     out = {"mode": int(mode[0]), "records": recs[:counts[0]].copy(), "item_barcode": ib[:nq].copy(), "counts": [int(v) for v in counts]}
     if raw:
         out["hits"], out["line_counts"] = extra
@@ -1198,21 +1182,13 @@ def barcodes_from_page(image, quads=None, min_lines: int = BARCODES_MIN_LINES, i
     a view into a wider buffer) and quads f32 [nq, 8] -> {"mode" (1, or -7 beyond 64 barcodes), "records" i32 [n, 24] (BARCODE_FIELDS, then the text),
     "barcodes" (barcode_dicts), "item_barcode" i32 [nq], "counts" [6] = barcodes, candidates examined, start patterns matched, hits kept, hits dropped, chains
     below min_lines}; raw adds "hits" i32 [H + W, 2, 8, 20] and "line_counts" i32 [H + W, 2, 4], the lines' raw hits."""
-    lib = load()
-
-    def fn(*a):
-        _lib_check(lib.ttr_barcodes_from_page(*a) if raw else lib.ttr_barcodes_from_page(*a, None, None))
-    return _barcodes_call(fn, image, quads, (min_lines, ink, symbologies), row_stride, raw)
+    fn, params = _page_entry("from_page", "barcodes", (min_lines,), ink, (symbologies,))
+    return _barcodes_call(fn if raw else (lambda *a: fn(*a, None, None)), params, image, quads, row_stride, raw)
 
 
 def barcodes_from_page_ink(image, quads=None, min_lines: int = BARCODES_MIN_LINES, symbologies: int = BARCODES_SYMBOLOGIES, local_ink=True, row_stride: int = 0) -> dict:
     """barcodes_from_page under the local ink rule (ttr_barcodes_from_page_ink): local_ink = True or (radius, drop, polarity) in the place of ink"""
-    lib = load()
-    r, d, p = _local_ink_arg(local_ink)
-
-    def fn(*a):
-        _lib_check(lib.ttr_barcodes_from_page_ink(*a))
-    return _barcodes_call(fn, image, quads, (min_lines, symbologies, r, d, p), row_stride)
+    return _barcodes_call(*_page_entry("from_page_ink", "barcodes", (min_lines,), local_ink, (symbologies,)), image=image, quads=quads, row_stride=row_stride)
 
 
 def barcode_dicts(records) -> list:
@@ -1234,17 +1210,7 @@ class Skew(C.Structure):
                 ("reserved", C.c_int32), ("score0", C.c_uint64), ("score_found", C.c_uint64)]
 
 
-def _deskew_arg(deskew):
-    """False / None / 0 -> (0, DESKEW_GAIN, DESKEW_INK); True -> the defaults; (max_slope, gain, ink) or a bare max_slope otherwise"""
-    if deskew is None or deskew is False or (isinstance(deskew, int) and not isinstance(deskew, bool) and deskew == 0):
-        return 0, DESKEW_GAIN, DESKEW_INK
-    if deskew is True:
-        return DESKEW_MAX_SLOPE, DESKEW_GAIN, DESKEW_INK
-    if isinstance(deskew, (tuple, list)) and len(deskew) == 3:
-        return int(deskew[0]), int(deskew[1]), int(deskew[2])
-    if isinstance(deskew, int):
-        return int(deskew), DESKEW_GAIN, DESKEW_INK
-    raise EngineError("deskew must be False, True or (max_slope, gain, ink)")
+_deskew_arg = functools.partial(_layer_arg, "deskew", fields="max_slope, gain, ink", defaults=(DESKEW_MAX_SLOPE, DESKEW_GAIN, DESKEW_INK))
 
 
 def _skew_dict(rec) -> dict:
@@ -1266,27 +1232,18 @@ def skew_to_page(skew: dict, points) -> np.ndarray:
     return out
 
 
-def _deskew_call(fn, image, max_slope, gain, ink, row_stride=0):
-    """the shared body of deskew_from_page and Engine.deskew_page: fn(image..., outputs...) -> the dict both return"""
-    image = np.asarray(image, dtype=np.uint8)
-    if image.ndim != 3 or image.shape[2] != 3:
-        raise RuntimeError("Input array should have 3 dimensions")
-    if not row_stride:
-        image = np.ascontiguousarray(image)
-    h, w = image.shape[:2]
-    out, rec, scores = np.zeros((h, w, 3), np.uint8), Skew(), np.zeros(2 * max(int(max_slope), 0) + 1, np.uint64)
-    fn(_u8(image), h, w, int(row_stride) or w * 3, int(max_slope), int(gain), int(ink), _u8(out), C.addressof(rec), scores.ctypes.data_as(C.POINTER(C.c_uint64)))
+def _deskew_call(fn, params, image, row_stride=0):
+    """the shared body of deskew_from_page and Engine.deskew_page: fn(image..., params..., outputs...) (params: max_slope first) -> the dict both return"""
+    image, h, w, stride = _page_image(image, row_stride)
+    out, rec, scores = np.zeros((h, w, 3), np.uint8), Skew(), np.zeros(2 * max(int(params[0]), 0) + 1, np.uint64)
+    fn(_u8(image), h, w, stride, *[int(v) for v in params], _u8(out), C.addressof(rec), scores.ctypes.data_as(C.POINTER(C.c_uint64)))
     return {"image": out, "skew": _skew_dict(rec), "scores": scores}
 
 
 def deskew_from_page(image, max_slope: int = DESKEW_MAX_SLOPE, gain: int = DESKEW_GAIN, ink: int = DESKEW_INK, row_stride: int = 0) -> dict:
     """The deskew rule on the host (ttr_deskew_from_page, no GPU; DESIGN.md "Deskew"): a host image u8 [H, W, 3] (row_stride: the bytes from row to row of a view
     into a wider buffer) -> {"image" u8 [H, W, 3] the upright page, "skew" the record as PageResult.skew carries it, "scores" u64 [2 max_slope + 1]}."""
-    lib = load()
-
-    def fn(*a):
-        _lib_check(lib.ttr_deskew_from_page(*a))
-    return _deskew_call(fn, image, max_slope, gain, ink, row_stride)
+    return _deskew_call(*_page_entry("from_page", "deskew", (max_slope, gain), ink), image=image, row_stride=row_stride)
 
 
 LOCAL_INK_RADIUS, LOCAL_INK_DROP, LOCAL_INK_POLARITY = 16, 38, 2   # what local_ink=True means (DESIGN.md "Local ink": none of them has been tuned on documents)
@@ -1298,17 +1255,7 @@ class Ink(C.Structure):
     _fields_ = [("radius", C.c_int32), ("drop", C.c_int32), ("polarity", C.c_int32), ("inverted", C.c_int32), ("sum", C.c_uint64), ("w", C.c_int32), ("h", C.c_int32)]
 
 
-def _local_ink_arg(local_ink):
-    """False / None / 0 -> (0, drop, polarity defaults); True -> the defaults; (radius, drop, polarity) or a bare radius otherwise"""
-    if local_ink is None or local_ink is False or (isinstance(local_ink, int) and not isinstance(local_ink, bool) and local_ink == 0):
-        return 0, LOCAL_INK_DROP, LOCAL_INK_POLARITY
-    if local_ink is True:
-        return LOCAL_INK_RADIUS, LOCAL_INK_DROP, LOCAL_INK_POLARITY
-    if isinstance(local_ink, (tuple, list)) and len(local_ink) == 3:
-        return int(local_ink[0]), int(local_ink[1]), int(local_ink[2])
-    if isinstance(local_ink, int):
-        return int(local_ink), LOCAL_INK_DROP, LOCAL_INK_POLARITY
-    raise EngineError("local_ink must be False, True or (radius, drop, polarity)")
+_local_ink_arg = functools.partial(_layer_arg, "local_ink", fields="radius, drop, polarity", defaults=(LOCAL_INK_RADIUS, LOCAL_INK_DROP, LOCAL_INK_POLARITY))
 
 
 def _ink_dict(rec) -> dict:
@@ -1318,15 +1265,10 @@ def _ink_dict(rec) -> dict:
 
 def _ink_call(fn, image, radius, drop, polarity, row_stride=0):
     """the shared body of ink_from_page and Engine.ink_page: fn(image..., outputs...) -> the dict both return"""
-    image = np.asarray(image, dtype=np.uint8)
-    if image.ndim != 3 or image.shape[2] != 3:
-        raise RuntimeError("Input array should have 3 dimensions")
-    if not row_stride:
-        image = np.ascontiguousarray(image)
-    h, w = image.shape[:2]
+    image, h, w, stride = _page_image(image, row_stride)
     bits, bitsT, rec = np.zeros((h, (w + 63) // 64), np.uint64), np.zeros((w, (h + 63) // 64), np.uint64), Ink()
     u64 = C.POINTER(C.c_uint64)
-    fn(_u8(image), h, w, int(row_stride) or w * 3, int(radius), int(drop), int(polarity), bits.ctypes.data_as(u64), bitsT.ctypes.data_as(u64), C.addressof(rec))
+    fn(_u8(image), h, w, stride, int(radius), int(drop), int(polarity), bits.ctypes.data_as(u64), bitsT.ctypes.data_as(u64), C.addressof(rec))
     return {"bits": bits, "bitsT": bitsT, "ink": _ink_dict(rec)}
 
 
@@ -1343,22 +1285,12 @@ def ink_from_page(image, radius: int = LOCAL_INK_RADIUS, drop: int = LOCAL_INK_D
 
 def tables_from_page_ink(image, quads=None, min_len: int = TABLES_MIN_LEN, local_ink=True, row_stride: int = 0) -> dict:
     """tables_from_page under the local ink rule (ttr_tables_from_page_ink): local_ink = True or (radius, drop, polarity) in the place of ink"""
-    lib = load()
-    r, d, p = _local_ink_arg(local_ink)
-
-    def fn(img, h, w, stride, min_len_, _ink, *rest):
-        _lib_check(lib.ttr_tables_from_page_ink(img, h, w, stride, min_len_, r, d, p, *rest))
-    return _tables_call(fn, image, quads, min_len, 0, row_stride)
+    return _tables_call(*_page_entry("from_page_ink", "tables", (min_len,), local_ink), image=image, quads=quads, row_stride=row_stride)
 
 
 def deskew_from_page_ink(image, max_slope: int = DESKEW_MAX_SLOPE, gain: int = DESKEW_GAIN, local_ink=True, row_stride: int = 0) -> dict:
     """deskew_from_page under the local ink rule (ttr_deskew_from_page_ink): local_ink = True or (radius, drop, polarity) in the place of ink"""
-    lib = load()
-    r, d, p = _local_ink_arg(local_ink)
-
-    def fn(img, h, w, stride, max_slope_, gain_, _ink, *rest):
-        _lib_check(lib.ttr_deskew_from_page_ink(img, h, w, stride, max_slope_, gain_, r, d, p, *rest))
-    return _deskew_call(fn, image, max_slope, gain, 0, row_stride)
+    return _deskew_call(*_page_entry("from_page_ink", "deskew", (max_slope, gain), local_ink), image=image, row_stride=row_stride)
 
 
 def table_line_lists(tables, lines) -> list:
@@ -1375,11 +1307,7 @@ def tables_from_page(image, quads=None, min_len: int = TABLES_MIN_LEN, ink: int 
     """The tables rule on the host (ttr_tables_from_page, no GPU; DESIGN.md "Tables"): a host image u8 [H, W, 3] (row_stride: the bytes from row to row of a
     view into a wider buffer) and quads f32 [nq, 8] -> {"mode", "rulings" i32 [nr, 6], "tables" i32 [nt, 8], "lines" i32 (per table its row lines, then its
     column lines, doubled px), "cells" i32 [nc, 9], "item_table" i32 [nq], "item_cell" i32 [nq], "runs": (horizontal, vertical) run counts, 0 for a page beyond a cap}."""
-    lib = load()
-
-    def fn(*a):
-        _lib_check(lib.ttr_tables_from_page(*a))
-    return _tables_call(fn, image, quads, min_len, ink, row_stride)
+    return _tables_call(*_page_entry("from_page", "tables", (min_len,), ink), image=image, quads=quads, row_stride=row_stride)
 
 
 class PageResult(collections.abc.Sequence):
@@ -1711,21 +1639,28 @@ class Engine:
         if local_ink[0]:
             self.set_local_ink(local_ink)
 
+    def _set_layer(self, setter, values):
+        """a page layer's setter with its tuple of ints; the library's refusal (ASCII) as an EngineError"""
+        if setter(self.h, *values) != 0:
+            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+
+    def _get_layer(self, getter, n: int):
+        """a page layer's n values in force - the getter returns the first and writes the others - or None when the layer is off"""
+        rest = [C.c_int() for _ in range(n - 1)]
+        first = int(getter(self.h, *[C.byref(v) for v in rest]))
+        return (first, *[int(v.value) for v in rest]) if first else None
+
     def set_local_ink(self, local_ink=True):
         """Take the ink bitmap of the engine's tables and deskew passes from the adaptive threshold (ttr_engine_set_ink; DESIGN.md "Local ink"): False / 0 = off,
         True = (16, 38, 2), else (radius, drop, polarity) with radius in 1..64 px, drop in 1..255 (1/256ths) and polarity 0 dark / 1 light / 2 auto (none of the
         defaults has been tuned on documents).  With neither tables nor deskew on nothing runs; the stage calls keep the fixed rule.  PageResult.ink carries the
         page's record.  Raises EngineError, and changes nothing, for other values and between a stream_push and its flush."""
-        r, d, p = _local_ink_arg(local_ink)
-        if self.lib.ttr_engine_set_ink(self.h, r, d, p) != 0:
-            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+        self._set_layer(self.lib.ttr_engine_set_ink, _local_ink_arg(local_ink))
 
     @property
     def local_ink(self):
         """(radius, drop, polarity) in force, or None when local ink is off"""
-        d, p = C.c_int(), C.c_int()
-        r = int(self.lib.ttr_engine_ink(self.h, C.byref(d), C.byref(p)))
-        return (r, int(d.value), int(p.value)) if r else None
+        return self._get_layer(self.lib.ttr_engine_ink, 3)
 
     @staticmethod
     def ink_from_page(image, radius: int = LOCAL_INK_RADIUS, drop: int = LOCAL_INK_DROP, polarity: int = LOCAL_INK_POLARITY, row_stride: int = 0) -> dict:
@@ -1747,16 +1682,12 @@ class Engine:
         else (max_slope, gain, ink) with max_slope in 1..128 (px per 512 px; 128 = 14 degrees), gain in 256..65535 (1/256ths) and ink in 1..255 (none of the
         defaults has been tuned on documents).  Results are those of the upright page, in its frame; PageResult.skew / to_page / "quad_page" lead back to the
         caller's.  Raises EngineError, and changes nothing, for other values, between a stream_push and its flush, and with a communicator attached."""
-        m, g, i = _deskew_arg(deskew)
-        if self.lib.ttr_engine_set_deskew(self.h, m, g, i) != 0:
-            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+        self._set_layer(self.lib.ttr_engine_set_deskew, _deskew_arg(deskew))
 
     @property
     def deskew(self):
         """(max_slope, gain, ink) in force, or None when deskew is off"""
-        g, i = C.c_int(), C.c_int()
-        m = int(self.lib.ttr_engine_deskew(self.h, C.byref(g), C.byref(i)))
-        return (m, int(g.value), int(i.value)) if m else None
+        return self._get_layer(self.lib.ttr_engine_deskew, 3)
 
     def deskew_page(self, image, max_slope: int = DESKEW_MAX_SLOPE, gain: int = DESKEW_GAIN, ink: int = DESKEW_INK, dev_offset: int = 0, dev_stride: int = 0) -> dict:
         """ttr_deskew_page: the pixel pass, deskew_score_kernel and deskew_rotate_kernel on a host image u8 [H, W, 3], whatever the engine's setting -> the dict
@@ -1767,45 +1698,35 @@ class Engine:
                 self._check(self.lib.ttr_dbg_deskew_page(self.h, *a[:4], int(dev_offset), int(dev_stride), *a[4:]))
             else:
                 self._check(self.lib.ttr_deskew_page(self.h, *a))
-        return _deskew_call(fn, image, max_slope, gain, ink)
+        return _deskew_call(fn, (max_slope, gain, ink), image)
 
     def set_tables(self, tables=True):
         """Find ruling lines, tables, their grids and merged cells in every page's pixels and give every item its cell (ttr_engine_set_tables; DESIGN.md
         "Tables"): False / 0 = off, True = (48, 128), else (min_len, ink) with min_len in 16..4096 and ink in 1..255 (neither default has been tuned on
         documents).  Items, order, boxes, text, ids and conf keep their bits.  Raises EngineError, and changes nothing, for other values, between a stream_push
         and its flush, and with a communicator attached."""
-        min_len, ink = _tables_arg(tables)
-        if self.lib.ttr_engine_set_tables(self.h, min_len, ink) != 0:
-            raise EngineError(self.lib.ttr_last_error().decode("latin1"))
+        self._set_layer(self.lib.ttr_engine_set_tables, _tables_arg(tables))
 
     @property
     def tables(self):
         """(min_len, ink) in force, or None when tables are off"""
-        ink = C.c_int()
-        m = int(self.lib.ttr_engine_tables(self.h, C.byref(ink)))
-        return (m, int(ink.value)) if m else None
+        return self._get_layer(self.lib.ttr_engine_tables, 2)
 
     def set_marks(self, marks=True):
         """Find every page's checkboxes and their state and give every item its mark (ttr_engine_set_marks; DESIGN.md "Selection marks"): False / 0 = off,
         True = (10, 64, 24, 128), else (min_side 8..64, max_side min_side..128, fill 1..255, ink 1..255) or a bare min_side; none of the defaults has been
         tuned on documents.  Refused while batches stream and with a communicator attached."""
-        a = _marks_arg(marks)
-        if self.lib.ttr_engine_set_marks(self.h, *a) != 0:
-            raise EngineError(self.lib.ttr_last_error().decode())
+        self._set_layer(self.lib.ttr_engine_set_marks, _marks_arg(marks))
 
     @property
     def marks(self):
         """(min_side, max_side, fill, ink) in force, or None when marks are off"""
-        mx, fl, ink = C.c_int(), C.c_int(), C.c_int()
-        m = int(self.lib.ttr_engine_marks(self.h, C.byref(mx), C.byref(fl), C.byref(ink)))
-        return (m, mx.value, fl.value, ink.value) if m else None
+        return self._get_layer(self.lib.ttr_engine_marks, 4)
 
     def marks_page(self, image, quads=None, min_side: int = MARKS_MIN_SIDE, max_side: int = MARKS_MAX_SIDE, fill: int = MARKS_FILL, ink: int = MARKS_INK) -> dict:
         """ttr_marks_page: table_ink_kernel, mark_cand_kernel and mark_page_kernel on a host image u8 [H, W, 3] and host quads f32 [nq, 8], whatever the
         engine's setting -> the dict marks_from_page returns."""
-        def fn(*a):
-            self._check(self.lib.ttr_marks_page(self.h, *a))
-        return _marks_call(fn, image, quads, (min_side, max_side, fill, ink))
+        return _marks_call(*_page_entry("page", "marks", (min_side, max_side, fill), ink, engine=self), image=image, quads=quads)
 
     def marks_debug(self, image, min_side: int = MARKS_MIN_SIDE, max_side: int = MARKS_MAX_SIDE, fill: int = MARKS_FILL, ink: int = MARKS_INK, dev_offset: int = 0,
                     dev_stride: int = 0) -> dict:
@@ -1823,23 +1744,17 @@ class Engine:
         """Read every page's Code 128 and Code 39 barcodes and give every item its barcode (ttr_engine_set_barcodes; DESIGN.md "Barcodes"): False / 0 = off,
         True = (8, 128, 3), else (min_lines 4..256, ink 1..255, symbologies 1..3: bit 0 Code 128, bit 1 Code 39) or a bare min_lines; none of the defaults has
         been tuned on documents.  Refused while batches stream and with a communicator attached."""
-        a = _barcodes_arg(barcodes)
-        if self.lib.ttr_engine_set_barcodes(self.h, *a) != 0:
-            raise EngineError(self.lib.ttr_last_error().decode())
+        self._set_layer(self.lib.ttr_engine_set_barcodes, _barcodes_arg(barcodes))
 
     @property
     def barcodes(self):
         """(min_lines, ink, symbologies) in force, or None when barcodes are off"""
-        ink, sym = C.c_int(), C.c_int()
-        m = int(self.lib.ttr_engine_barcodes(self.h, C.byref(ink), C.byref(sym)))
-        return (m, ink.value, sym.value) if m else None
+        return self._get_layer(self.lib.ttr_engine_barcodes, 3)
 
     def barcodes_page(self, image, quads=None, min_lines: int = BARCODES_MIN_LINES, ink: int = BARCODES_INK, symbologies: int = BARCODES_SYMBOLOGIES) -> dict:
         """ttr_barcodes_page: table_ink_kernel, barcode_scan_kernel and barcode_page_kernel on a host image u8 [H, W, 3] and host quads f32 [nq, 8], whatever
         the engine's setting -> the dict barcodes_from_page returns."""
-        def fn(*a):
-            self._check(self.lib.ttr_barcodes_page(self.h, *a))
-        return _barcodes_call(fn, image, quads, (min_lines, ink, symbologies))
+        return _barcodes_call(*_page_entry("page", "barcodes", (min_lines,), ink, (symbologies,), engine=self), image=image, quads=quads)
 
     def barcodes_debug(self, image, min_lines: int = BARCODES_MIN_LINES, ink: int = BARCODES_INK, symbologies: int = BARCODES_SYMBOLOGIES, dev_offset: int = 0,
                        dev_stride: int = 0) -> dict:
@@ -1859,9 +1774,7 @@ class Engine:
     def tables_page(self, image, quads=None, min_len: int = TABLES_MIN_LEN, ink: int = TABLES_INK) -> dict:
         """ttr_tables_page: table_ink_kernel and table_grid_kernel on a host image u8 [H, W, 3] and host quads f32 [nq, 8], whatever the engine's setting ->
         the dict tables_from_page returns."""
-        def fn(*a):
-            self._check(self.lib.ttr_tables_page(self.h, *a))
-        return _tables_call(fn, image, quads, min_len, ink)
+        return _tables_call(*_page_entry("page", "tables", (min_len,), ink, engine=self), image=image, quads=quads)
 
     def tables_debug(self, image, min_len: int = TABLES_MIN_LEN, ink: int = TABLES_INK, dev_offset: int = 0, dev_stride: int = 0) -> dict:
         """ttr_dbg_tables: the ink bitmap u64 [H, ceil(W / 64)] and the run lists i32 [n, 3] of both directions as the device formed them; the image is placed
@@ -2257,6 +2170,17 @@ class Engine:
     def _quads(self, r, n: int) -> np.ndarray:
         return np.ctypeslib.as_array(self.lib.ttr_result_quads(r), (n, 8)).copy() if n else np.zeros((0, 8), np.float32)
 
+    def _take_records(self, r, c: int, one: str, many: str, width: int, keys) -> dict:
+        """a result's records of one page layer (ttr_result_<one>_mode / _<one>_count / _<many> / _item_<one>) under the keys (mode, records i32 [n, width],
+        items i32 [c], -1 without any); {} for a result the layer did not run for"""
+        mode = int(getattr(self.lib, f"ttr_result_{one}_mode")(r))
+        if not mode:
+            return {}
+        n = int(getattr(self.lib, f"ttr_result_{one}_count")(r))
+        rp, ip = getattr(self.lib, f"ttr_result_{many}")(r), getattr(self.lib, f"ttr_result_item_{one}")(r)
+        return {keys[0]: mode, keys[1]: np.ctypeslib.as_array(rp, (n, width)).copy() if rp and n else np.zeros((0, width), np.int32),
+                keys[2]: np.ctypeslib.as_array(ip, (c,)).copy() if ip and c else np.full(c, -1, np.int32)}
+
     def _take_many(self, arr, n: int, conf: bool = False) -> List[List[dict]]:
         """A batch of ttr_results -> list (per page) of lists of {"text", "bbox", "ids"} (+ "conf", "char_conf" with conf): one gather call
         for the whole batch."""
@@ -2363,18 +2287,9 @@ class Engine:
                            table_rects=view(self.lib.ttr_result_tables(r), (nt_, 8)), table_lines=view(lp, (nl_.value,)),
                            cells=view(self.lib.ttr_result_cells(r), (nc_, 9)), item_table=view(self.lib.ttr_result_item_table(r), (c,)),
                            item_cell=view(self.lib.ttr_result_item_cell(r), (c,)), cell_texts=texts_c)
-            if self.lib.ttr_result_mark_mode(arr[i]):    # selection marks: the page's marks and its items' marks (there for a page without items too)
-                nm_ = int(self.lib.ttr_result_mark_count(arr[i]))
-                mp, ip = self.lib.ttr_result_marks(arr[i]), self.lib.ttr_result_item_mark(arr[i])
-                lex.update(mark_mode=int(self.lib.ttr_result_mark_mode(arr[i])),
-                           mark_recs=np.ctypeslib.as_array(mp, (nm_, 12)).copy() if mp and nm_ else np.zeros((0, 12), np.int32),
-                           item_mark=np.ctypeslib.as_array(ip, (c,)).copy() if ip and c else np.full(c, -1, np.int32))
-            if self.lib.ttr_result_barcode_mode(arr[i]):    # barcodes: the page's barcodes and its items' barcodes (there for a page without items too)
-                nb_ = int(self.lib.ttr_result_barcode_count(arr[i]))
-                bp, ip = self.lib.ttr_result_barcodes(arr[i]), self.lib.ttr_result_item_barcode(arr[i])
-                lex.update(barcode_mode=int(self.lib.ttr_result_barcode_mode(arr[i])),
-                           barcode_recs=np.ctypeslib.as_array(bp, (nb_, 24)).copy() if bp and nb_ else np.zeros((0, 24), np.int32),
-                           item_barcode=np.ctypeslib.as_array(ip, (c,)).copy() if ip and c else np.full(c, -1, np.int32))
+            # selection marks and barcodes: the page's records and its items' (there for a page without items too)
+            lex.update(self._take_records(arr[i], c, "mark", "marks", 12, ("mark_mode", "mark_recs", "item_mark")))
+            lex.update(self._take_records(arr[i], c, "barcode", "barcodes", 24, ("barcode_mode", "barcode_recs", "item_barcode")))
             pl = self.lib.ttr_result_pattern_logp(arr[i])
             if pl:                              # patterns in best mode: the page's log-probabilities
                 lex["pattern_logp"] = np.ctypeslib.as_array(pl, (c,)).copy()
