@@ -80,7 +80,9 @@ int ttr_set_tuning(const char* key, int value);
  * counters, [2] wait for candidates / row extremes, [3] calipers, [4] crop rectangles + PARSeq enqueue, [5] wait for the GPU,
  * [6] event read-back, [7] token decode */
 void ttr_last_host_us(ttr_engine* e, float out[8]);
-/* test hook for the ViT encoder self-attention kernels: qkv f32 [N][128][1152] (rounded to the engine's type) -> out [N][128][384] */
+/* test hook for the ViT encoder self-attention kernels: qkv f32 [N][128][1152] (rounded to the engine's type) -> out [N][128][384].  f16x4 engines run
+ * attn_split.hip the way the encoder does behind a separate qkv GEMM: the fp32 rows become exact triples (split_planes), the kernel reads and writes planes,
+ * and the output triples are joined here.  f32 engines run the fp32 kernel, bf16 engines theirs. */
 int ttr_dbg_attn_enc(ttr_engine* e, const float* qkv, int N, float* out);
 /* test hook for the decoder's cross-attention kernels of the split-operand / fp32 engines (parseq_ops.hip, attn_cross_split.hip; which one runs follows the
  * tuning keys "cross_split", "cross_crop", "cross_rows_hsplit"): q f32 [N * R][384] (R query rows per crop), kvmem f32 [N * 128][768] (K | V of a crop's 128

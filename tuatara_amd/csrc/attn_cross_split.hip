@@ -11,7 +11,9 @@
 //   * K_h and V_h (128 x 32 fp32 each) are read once with 16-byte loads, written to the wave's own LDS as f16 PAIRS (x0 | x1 2^11): K with its rows permuted so
 //     that S^T = K Q^T leaves 8 consecutive keys per lane (the P fragment of O^T = V^T P^T), 16-byte chunks swizzled against the 64-byte row stride;
 //   * Q is the exact triple in registers (a score goes through an exponential), P a pair (p in [0, 1] on 22+ bits is fp32's resolution of it): S^T takes four
-//     MFMAs per product pair, O^T three, 112 MFMAs per head;
+//     MFMAs per product pair, O^T three, 112 MFMAs per head.  Every plane enters its MFMA AS STORED (attn_split.hip): a score is fma(k0 q1s + k0 q2s + k1s q0,
+//     2^-11, k0 q0) from two accumulators, O^T accumulates v0 (2^11 p0) + v0 p1s + v1s p0 with the 2^-11 folded into 1 / sum - no f16 product plane / 2^11, which
+//     is subnormal below 2^-3 (tests/test_gpu_attn_scale.py);
 //   * V^T fragments come by `ds_read_b64_tr_b16` from the row-major V planes; the 26 result rows leave as 8-byte pieces of the three planes.
 // Two waves (two heads) per workgroup, 16 KB of LDS per wave (V takes K's place once S^T is formed; ten waves per CU hide each other's loads): no workgroup
 // barrier anywhere - a wave reads only what it wrote.
@@ -30,9 +32,9 @@ constexpr int XS_KEYS = 128, XS_DH = 32, XS_ROWB = 64;          // bytes per LDS
 constexpr int XS_PLANE = XS_KEYS * XS_ROWB;                       // 8 KiB per plane
 constexpr int XS_WAVE_LDS = 2 * XS_PLANE;                         // x0 | x1 of K, then of V
 
-__device__ __forceinline__ f16x8 xs_scale_down(f16x8 v) {         // v / 2^11 (exact unless subnormal)
-  const f16 s = (f16)(1.f / 2048.f);
-  return v * f16x8{s, s, s, s, s, s, s, s};
+__device__ __forceinline__ f16x8 xs_scale_up(f16x8 p) {           // 2^11 p of a probability plane p <= 1: exact, at most 2048 (subnormal p included)
+  const f16 s = (f16)2048.f;
+  return p * f16x8{s, s, s, s, s, s, s, s};
 }
 }  // namespace
 
@@ -86,14 +88,17 @@ __global__ __launch_bounds__(128) void dec_cross_attn_split_kernel(const float* 
   for (int kt = 0; kt < 8; ++kt) {
     const int off = (kt * 16 + qq) * XS_ROWB + ((g ^ swz) << 4);
     const f16x8 k0 = *reinterpret_cast<const f16x8*>(sK + off), x1 = *reinterpret_cast<const f16x8*>(sK + XS_PLANE + off);
-    const f16x8 k0b = xs_scale_down(k0), k1 = xs_scale_down(x1);
+    // the planes as stored: k0 q0 in one accumulator, the three low-order products (each carrying the 2^11 of its lower plane) in a transient one, joined in fp32
+    // (no f16 product k0 / 2^11: it would be subnormal, an absolute 2^-25, wherever |k| < 2^-3)
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
-      f32x4 a = {0.f, 0.f, 0.f, 0.f};
-      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[0][qt], a, 0, 0, 0);
-      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0b, fq[1][qt], a, 0, 0, 0);
-      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0b, fq[2][qt], a, 0, 0, 0);
-      sacc[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(k1, fq[0][qt], a, 0, 0, 0);
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      const f32x4 hi = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[0][qt], z, 0, 0, 0);
+      f32x4 lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[1][qt], z, 0, 0, 0);
+      lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[2][qt], lo, 0, 0, 0);
+      lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(x1, fq[0][qt], lo, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sacc[qt][kt][r] = fmaf(lo[r], 1.f / 2048.f, hi[r]);
     }
   }
 
@@ -137,12 +142,13 @@ __global__ __launch_bounds__(128) void dec_cross_attn_split_kernel(const float* 
     }
     sum += __shfl_xor(sum, 16);
     sum += __shfl_xor(sum, 32);
-    rinv[qt] = 1.0f / sum;
+    rinv[qt] = (1.f / 2048.f) / sum;                              // (O^T below is accumulated at 2^11 times its value)
   }
 
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // V is in LDS
   __builtin_amdgcn_wave_barrier();
-  // ---- O^T = V^T P^T: A = V^T fragment (16 d x 32 keys) by two transposed reads per plane of the row-major V tile (attn_split.hip, 64-byte rows here)
+  // ---- O^T = V^T P^T: A = V^T fragment (16 d x 32 keys) by two transposed reads per plane of the row-major V tile (attn_split.hip, 64-byte rows here).
+  // 2^11 O^T = v0 (2^11 p0) + v0 p1s + v1s p0 on the planes as stored (p0 <= 1: 2^11 p0 is an exact f16 number); the 2^-11 is in rinv
   f32x4 oacc[2][2];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt)
@@ -159,15 +165,15 @@ __global__ __launch_bounds__(128) void dec_cross_attn_split_kernel(const float* 
     XS_TR(lo[1][1], XS_PLANE + (s) * 2048 + 32); XS_TR(hi[1][1], XS_PLANE + (s) * 2048 + 256 + 32);          \
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo[0][0]), "+v"(lo[0][1]), "+v"(hi[0][0]), "+v"(hi[0][1]),    \
                  "+v"(lo[1][0]), "+v"(lo[1][1]), "+v"(hi[1][0]), "+v"(hi[1][1]));                            \
+    const f16x8 pu[2] = {xs_scale_up(fp[0][0][s]), xs_scale_up(fp[0][1][s])};                                \
     _Pragma("unroll") for (int dt = 0; dt < 2; ++dt) {                                                       \
       const f16x8 v0 = __builtin_shufflevector(lo[0][dt], hi[0][dt], 0, 1, 2, 3, 4, 5, 6, 7);                \
       const f16x8 x1 = __builtin_shufflevector(lo[1][dt], hi[1][dt], 0, 1, 2, 3, 4, 5, 6, 7);                \
-      const f16x8 v0b = xs_scale_down(v0), v1 = xs_scale_down(x1);                                           \
       _Pragma("unroll") for (int qt = 0; qt < 2; ++qt) {                                                     \
         f32x4 a = oacc[qt][dt];                                                                              \
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, fp[0][qt][s], a, 0, 0, 0);                            \
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0b, fp[1][qt][s], a, 0, 0, 0);                           \
-        oacc[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(v1, fp[0][qt][s], a, 0, 0, 0);                 \
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, pu[qt], a, 0, 0, 0);                                  \
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, fp[1][qt][s], a, 0, 0, 0);                            \
+        oacc[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x1, fp[0][qt][s], a, 0, 0, 0);                 \
       }                                                                                                      \
     }                                                                                                        \
   }

@@ -7,13 +7,17 @@
 // qkv arrives as planes [N*128][3][1152] (x0 | x1 | x2 of every value, written by the qkv GEMM's epilogue); the result leaves as
 // planes [N*128][3][384] for the projection GEMM.  Which operand is the exact triple and which the pair (split.h):
 //   * S^T = K Q^T: Q is the triple (q0, q1, q2) - a wave's 32 query rows go global -> registers, they are read once -, K the
-//     pair: its planes x0, x1 come global -> LDS by LDS-DMA and the pair's members k0b = k0 / 2^11 and k1 = x1 / 2^11 are formed from
-//     the fragments by packed f16 multiplies (exact);
-//   * O^T = V^T P^T: P = exp(s - max) is split in registers into (p0, p1, p2) and IS the B fragment (K rows permuted as in
-//     attn_enc2.hip); V is the pair, V^T fragments by `ds_read_b64_tr_b16` from the row-major planes.
-// Four MFMAs per product pair: (w0, x0), (w0b, x1), (w0b, x2), (w1, x0).  Absolute error of a score: <= |q| 64 2^-25 from the
-// pair's subnormal range - below fp32's own rounding of the sum.  64 KB of LDS: two workgroups per CU, one's loads under the
-// other's MFMAs (the kernel is HBM-bound: 7 of the 9 qkv planes = 96 KB per (crop, head)).
+//     pair: its planes k0, k1s = 2^11 k1 come global -> LDS by LDS-DMA and enter the MFMAs AS STORED: k0 q0 goes into one
+//     accumulator, the low-order products k0 q1s + k0 q2s + k1s q0 (each carries the 2^11 of its lower plane) into a transient
+//     one, and the score is fma(lo, 2^-11, hi) in fp32;
+//   * O^T = V^T P^T: P = exp(s - max) is split in registers into (p0, p1s, p2s) and IS the B fragment (K rows permuted as in
+//     attn_enc2.hip); V is the pair, V^T fragments by `ds_read_b64_tr_b16` from the row-major planes.  p0 <= 1, so 2^11 p0 is an
+//     exact f16 number: 2^11 O^T = v0 (2^11 p0) + v0 p1s + v0 p2s + v1s p0 in the one accumulator, the 2^-11 folded into 1 / sum.
+// Four MFMAs per product pair.  No operand is ever scaled DOWN in f16: a plane divided by 2^11 would be subnormal - an absolute
+// 2^-25 instead of 11 bits - wherever |k| or |v| < 2^-3, a score error of |q| 64 2^-25 that is below fp32's own rounding of the
+// sum only for |k| ~ 1 (tests/test_gpu_attn_scale.py: small K under large Q, small V).  What remains is split.h's own: a stored lower
+// plane keeps an absolute 2^-25 below 2^-14, which is 2^-36 in units of the value.  64 KB of LDS: two workgroups
+// per CU, one's loads under the other's MFMAs (the kernel is HBM-bound: 7 of the 9 qkv planes = 96 KB per (crop, head)).
 #include "common.h"
 #include "kernels.h"
 #include "split.h"
@@ -27,9 +31,9 @@ constexpr int S = 128, DH = 64, E3 = 1152, EO = 384;
 constexpr int RS = 3 * E3;           // halves per qkv row (three planes)
 constexpr int TILE = S * DH * 2;     // 16 KiB per tile
 
-__device__ __forceinline__ f16x8 scale_down(f16x8 v) {   // v / 2^11 (exact unless subnormal)
-  const f16 s = (f16)(1.f / 2048.f);
-  return v * f16x8{s, s, s, s, s, s, s, s};
+__device__ __forceinline__ f16x8 scale_up(f16x8 p) {   // 2^11 p of a probability plane p <= 1: exact, at most 2048 (subnormal p included)
+  const f16 s = (f16)2048.f;
+  return p * f16x8{s, s, s, s, s, s, s, s};
 }
 }  // namespace
 
@@ -77,21 +81,23 @@ __global__ __launch_bounds__(256, 2) void attn_enc_split_kernel(const f16* __res
   f32x4 sacc[2][8];
 #pragma unroll
   for (int kt = 0; kt < 8; ++kt) {
-    f32x4 a[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    f32x4 hi[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}}, lo[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       const int off = (kt * 16 + q) * 128 + (((ks * 4 + g) ^ swz) << 4);
       const f16x8 k0 = *reinterpret_cast<const f16x8*>(sK + off), x1 = *reinterpret_cast<const f16x8*>(sK + TILE + off);
-      const f16x8 k0b = scale_down(k0), k1 = scale_down(x1);
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
-        a[qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[0][qt][ks], a[qt], 0, 0, 0);
-        a[qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0b, fq[1][qt][ks], a[qt], 0, 0, 0);
-        a[qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0b, fq[2][qt][ks], a[qt], 0, 0, 0);
-        a[qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(k1, fq[0][qt][ks], a[qt], 0, 0, 0);
+        hi[qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[0][qt][ks], hi[qt], 0, 0, 0);
+        lo[qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[1][qt][ks], lo[qt], 0, 0, 0);
+        lo[qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[2][qt][ks], lo[qt], 0, 0, 0);
+        lo[qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x1, fq[0][qt][ks], lo[qt], 0, 0, 0);
       }
     }
-    sacc[0][kt] = a[0]; sacc[1][kt] = a[1];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sacc[qt][kt][r] = fmaf(lo[qt][r], 1.f / 2048.f, hi[qt][r]);
   }
 
   // ---- softmax over the 128 keys of a query (32 values in this lane, the rest in lanes q + 16 g'); P split into its planes
@@ -119,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void attn_enc_split_kernel(const f16* __res
     }
     sum += __shfl_xor(sum, 16);
     sum += __shfl_xor(sum, 32);
-    rinv[qt] = 1.0f / sum;
+    rinv[qt] = (1.f / 2048.f) / sum;                          // (O^T below is accumulated at 2^11 times its value)
   }
 
   // ---- O^T = V^T P^T: A = V^T fragment (16 d x 32 keys) by two transposed reads per plane of the row-major V tile
@@ -143,16 +149,16 @@ __global__ __launch_bounds__(256, 2) void attn_enc_split_kernel(const f16* __res
     ATS_TR(lo[1][3], TILE + (s) * 4096 + 96); ATS_TR(hi[1][3], TILE + (s) * 4096 + 512 + 96);               \
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo[0][0]), "+v"(lo[0][1]), "+v"(lo[0][2]), "+v"(lo[0][3]), "+v"(hi[0][0]), "+v"(hi[0][1]), "+v"(hi[0][2]), "+v"(hi[0][3]), \
                  "+v"(lo[1][0]), "+v"(lo[1][1]), "+v"(lo[1][2]), "+v"(lo[1][3]), "+v"(hi[1][0]), "+v"(hi[1][1]), "+v"(hi[1][2]), "+v"(hi[1][3])); \
+    const f16x8 pu[2] = {scale_up(fp[0][0][s]), scale_up(fp[0][1][s])};                                     \
     _Pragma("unroll") for (int dt = 0; dt < 4; ++dt) {                                                      \
       const f16x8 v0 = __builtin_shufflevector(lo[0][dt], hi[0][dt], 0, 1, 2, 3, 4, 5, 6, 7);               \
       const f16x8 x1 = __builtin_shufflevector(lo[1][dt], hi[1][dt], 0, 1, 2, 3, 4, 5, 6, 7);               \
-      const f16x8 v0b = scale_down(v0), v1 = scale_down(x1);                                                \
       _Pragma("unroll") for (int qt = 0; qt < 2; ++qt) {                                                    \
         f32x4 a = oacc[qt][dt];                                                                             \
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, fp[0][qt][s], a, 0, 0, 0);                           \
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0b, fp[1][qt][s], a, 0, 0, 0);                          \
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0b, fp[2][qt][s], a, 0, 0, 0);                          \
-        oacc[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(v1, fp[0][qt][s], a, 0, 0, 0);                \
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, pu[qt], a, 0, 0, 0);                                 \
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, fp[1][qt][s], a, 0, 0, 0);                           \
+        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, fp[2][qt][s], a, 0, 0, 0);                           \
+        oacc[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x1, fp[0][qt][s], a, 0, 0, 0);                \
       }                                                                                                     \
     }                                                                                                       \
   }

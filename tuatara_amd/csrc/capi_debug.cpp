@@ -286,6 +286,23 @@ int ttr_dbg_attn_enc(ttr_engine* e, const float* qkv, int N, float* out) {
   EngineScope lk(E);
   const size_t nin = (size_t)N * 128 * 1152, nout = (size_t)N * 128 * 384;
   DevBuf din, dout;
+  if (E.prec == kSplit) {   // attn_split.hip, as the encoder runs it behind a separate qkv GEMM: fp32 qkv -> exact triples -> the kernel -> triples joined here
+    if (N <= 0) throw std::runtime_error("ttr_dbg_attn_enc: N >= 1");
+    DevBuf dpl;
+    din.ensure(nin * 4); dpl.ensure(nin * 6); dout.ensure(nout * 6);
+    TTR_HIP_CHECK(hipMemcpy(din.p, qkv, nin * 4, hipMemcpyHostToDevice));
+    launch_split_planes(din.as<float>(), 1152, dpl.p, (int64_t)N * 128, 1152, 0, E.stream, 3);
+    launch_attn_enc_split(dpl.p, dout.p, N, E.stream);
+    std::vector<_Float16> h(nout * 3);
+    TTR_HIP_CHECK(hipMemcpyAsync(h.data(), dout.p, nout * 6, hipMemcpyDeviceToHost, E.stream));
+    TTR_HIP_CHECK(hipStreamSynchronize(E.stream));
+    for (size_t m = 0; m < (size_t)N * 128; ++m)
+      for (int c = 0; c < 384; ++c) {
+        const _Float16* row = h.data() + m * 1152;
+        out[m * 384 + c] = (float)((double)(float)row[c] + ((double)(float)row[384 + c] + (double)(float)row[768 + c]) / 2048.0);
+      }
+    return 0;
+  }
   din.ensure(nin * E.es); dout.ensure(nout * E.es);
   if (E.prec == kBF16) {
     std::vector<uint16_t> h(nin);

@@ -532,7 +532,8 @@ __global__ __launch_bounds__(WM * WN * 64, MINB) void gemm_sp_kernel(ConvParams 
       //   * K (pair) goes to LDS in attn_split.hip's image (rows permuted so that S^T = K Q^T leaves 8 consecutive keys per lane = the P
       //     fragment of O^T = V^T P^T), V (pair) follows into the same bytes once every wave has its scores, with its d columns permuted so
       //     that O^T's accumulators hold 8 consecutive d per lane (16-byte stores of the output planes);
-      //   * four MFMAs per product as there: (k0, q0) (k0/2^11, q1) (k0/2^11, q2) (k1/2^11, q0).
+      //   * four MFMAs per product as there, on the planes as stored: (k0, q0) into one accumulator, (k0, q1s) (k0, q2s) (k1s, q0) into a transient one, the
+      //     score fma(lo, 2^-11, hi); 2^11 O^T = v0 (2^11 p0) + v0 p1s + v1s p0 with the 2^-11 in rinv.  No plane is scaled down in f16 (subnormal below 2^-3).
       // The rings are not touched: the loader streams run on into the next tile meanwhile.  No wave-dependent control flow.
       typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
       constexpr int KV = 16384;                                   // one plane of K or V: 128 rows x 128 B
@@ -548,10 +549,9 @@ __global__ __launch_bounds__(WM * WN * 64, MINB) void gemm_sp_kernel(ConvParams 
       const float* const bp = p.bias + n0c + wn * 96 + fg * 8;
       f16x8 fq[2][3];                                             // [own d half, other d half][plane]
       f16x8 vp[2][2];                                             // V pairs [plane][i]
-      const f16 dn = (f16)(1.f / 2048.f);
-      const f16x8 dnv = {dn, dn, dn, dn, dn, dn, dn, dn};
-      // (K's and V's second planes go to LDS already scaled by 2^-11 - the factor their MFMA operand carries: one multiply per element where it is written
-      // instead of one per reading wave and product, the same f16 product either way)
+      const f16 up = (f16)2048.f;
+      const f16x8 upv = {up, up, up, up, up, up, up, up};         // 2^11 p0 of a probability plane p0 <= 1: exact
+      // (K's and V's second planes go to LDS as split2_x8 leaves them, at their 2^11 scale)
       auto tile_values = [&](int t, int i, float (&v)[8]) {       // bias + scale of the lane's 8 channels of block t, row half i
         const float4 b0 = *reinterpret_cast<const float4*>(bp + t * 32), b1 = *reinterpret_cast<const float4*>(bp + t * 32 + 4);
         const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
@@ -576,14 +576,13 @@ __global__ __launch_bounds__(WM * WN * 64, MINB) void gemm_sp_kernel(ConvParams 
         f16x8 a, b;
         split2_x8(v, a, b, rw);
         unsigned char* d = sK + (kwr + i * 1024 ^ i * 64);
-        *reinterpret_cast<f16x8*>(d) = a; *reinterpret_cast<f16x8*>(d + KV) = b * dnv;
+        *reinterpret_cast<f16x8*>(d) = a; *reinterpret_cast<f16x8*>(d + KV) = b;
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {   // V: kept until every wave is through with K
         float v[8];
         tile_values(2, i, v);
         split2_x8(v, vp[0][i], vp[1][i], rw);
-        vp[1][i] = vp[1][i] * dnv;
       }
       rw.flush(p.range_flag, p.range_tag);   // (here, not behind the tile: the watch would cost a register across the attention; the output rows are convex combinations of the V rows just watched)
       TTR_SP_STAMP(2);                      // Q / K / V converted, Q and K written
@@ -597,17 +596,17 @@ __global__ __launch_bounds__(WM * WN * 64, MINB) void gemm_sp_kernel(ConvParams 
         const unsigned char* const kb[2] = {sK + krd, sK + (krd ^ 64)};
 #pragma unroll
         for (int kt = 0; kt < 8; ++kt) {
-          f32x4 a = {0.f, 0.f, 0.f, 0.f};
+          f32x4 a = {0.f, 0.f, 0.f, 0.f}, lo = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int hf = 0; hf < 2; ++hf) {
             const f16x8 k0 = *reinterpret_cast<const f16x8*>(kb[hf] + kt * 2048), k1 = *reinterpret_cast<const f16x8*>(kb[hf] + KV + kt * 2048);
-            const f16x8 k0b = k0 * dnv;
             a = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[hf][0], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0b, fq[hf][1], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0b, fq[hf][2], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(k1, fq[hf][0], a, 0, 0, 0);
+            lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[hf][1], lo, 0, 0, 0);
+            lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0, fq[hf][2], lo, 0, 0, 0);
+            lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(k1, fq[hf][0], lo, 0, 0, 0);
           }
-          sacc[kt] = a;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) sacc[kt][r] = fmaf(lo[r], 1.f / 2048.f, a[r]);
         }
       }
       TTR_SP_STAMP(4);                      // S = Q K^T done
@@ -638,9 +637,9 @@ __global__ __launch_bounds__(WM * WN * 64, MINB) void gemm_sp_kernel(ConvParams 
         }
         sum += __shfl_xor(sum, 16);
         sum += __shfl_xor(sum, 32);
-        rinv = 1.0f / sum;
+        rinv = (1.f / 2048.f) / sum;        // (O^T below is accumulated at 2^11 times its value)
       }
-      TTR_SP_STAMP(5);                      // softmax + probability planes done
+      TTR_SP_STAMP(5);                     // softmax + probability planes done
       __syncthreads();                                            // every wave has read K
       TTR_SP_STAMP(6);
       // V: row = key, the 8 values d = 32 wn + 8 g + e go to column positions 32 wn + 4 g + e (e < 4) and 32 wn + 16 + 4 g + e - 4
@@ -675,13 +674,13 @@ __global__ __launch_bounds__(WM * WN * 64, MINB) void gemm_sp_kernel(ConvParams 
           TTR_SPA_TR(lo[1][3], KV + (s) * 4096 + 96); TTR_SPA_TR(hi[1][3], KV + (s) * 4096 + 512 + 96);        \
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo[0][0]), "+v"(lo[0][1]), "+v"(lo[0][2]), "+v"(lo[0][3]), "+v"(hi[0][0]), "+v"(hi[0][1]), "+v"(hi[0][2]), "+v"(hi[0][3]), \
                        "+v"(lo[1][0]), "+v"(lo[1][1]), "+v"(lo[1][2]), "+v"(lo[1][3]), "+v"(hi[1][0]), "+v"(hi[1][1]), "+v"(hi[1][2]), "+v"(hi[1][3])); \
+          const f16x8 pu = fp[0][s] * upv;                                                                     \
           _Pragma("unroll") for (int dt = 0; dt < 4; ++dt) {                                                   \
             const f16x8 v0 = __builtin_shufflevector(lo[0][dt], hi[0][dt], 0, 1, 2, 3, 4, 5, 6, 7);            \
             const f16x8 v1 = __builtin_shufflevector(lo[1][dt], hi[1][dt], 0, 1, 2, 3, 4, 5, 6, 7);            \
-            const f16x8 v0b = v0 * dnv;                                                                        \
             f32x4 a = oacc[dt];                                                                                \
-            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, fp[0][s], a, 0, 0, 0);                              \
-            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0b, fp[1][s], a, 0, 0, 0);                             \
+            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, pu, a, 0, 0, 0);                                    \
+            a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, fp[1][s], a, 0, 0, 0);                              \
             oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(v1, fp[0][s], a, 0, 0, 0);                       \
           }                                                                                                    \
         }

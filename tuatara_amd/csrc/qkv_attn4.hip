@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void qkv_attn4_kernel(ConvParams p) {
       split2_x8(v, a, b, rw);
       const int row = (2 * wm + (i >> 1)) * 32 + (((fr >> 2) & 1) << 4) + ((fr >> 3) << 2) + (fr & 3) + 8 * (i & 1);
       unsigned char* d = sK + row * 128 + (((wn * 4 + fg) ^ ((row >> 1) & 7)) << 4);
-      *reinterpret_cast<f16x8*>(d) = a; *reinterpret_cast<f16x8*>(d + QKV) = b * dnv;
+      *reinterpret_cast<f16x8*>(d) = a; *reinterpret_cast<f16x8*>(d + QKV) = b;   // (the second plane at its 2^11 scale, as split2_x8 leaves it)
     }
     f16x8 vp[2][4];                                     // V pairs [plane][i]: kept until every wave is through with K
 #pragma unroll
@@ -292,7 +292,6 @@ __global__ __launch_bounds__(256, 2) void qkv_attn4_kernel(ConvParams p) {
       float v[8];
       tile_values(2, i, v);
       split2_x8(v, vp[0][i], vp[1][i], rw);
-      vp[1][i] = vp[1][i] * dnv;
     }
     rw.flush(p.range_flag, p.range_tag);
     TTR_Q4_STAMP(3);                                    // Q / K / V converted, Q and K written
@@ -320,22 +319,23 @@ __global__ __launch_bounds__(256, 2) void qkv_attn4_kernel(ConvParams p) {
 #define TTR_Q4_KWAIT(K, r0, r1) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(K[0][0]), "+v"(K[0][1]), "+v"(K[1][0]), "+v"(K[1][1]), "+v"(r0), "+v"(r1));
       auto s_tile = [&](auto first_c, const f16x8 (&K)[2][2], f32x4& a0, f32x4& a1) {   // K[hf][k0 / k1]; F: which of [own, other] is block 0's first half (block 1 takes the other first)
         constexpr int F = decltype(first_c)::value;
-        f16x8 k0b[2];
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) k0b[hf] = K[hf][0] * dnv;
+        // gemm_sp.hip's epilogue: (k0, q0) into the score's accumulator, the three low-order products on the planes as stored into a transient one, joined in fp32
         a0 = f32x4{0.f, 0.f, 0.f, 0.f}; a1 = f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 l0 = {0.f, 0.f, 0.f, 0.f}, l1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int o = 0; o < 2; ++o) {
           const int h0 = o ? 1 - F : F, h1 = 1 - h0;
-          a0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h0][0], fq[0][h0][0], a0, 0, 0, 0);   // (the two blocks' chains alternate: a dependent MFMA is never the next one)
+          a0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h0][0], fq[0][h0][0], a0, 0, 0, 0);   // (the chains alternate: a dependent MFMA is never the next one)
           a1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h1][0], fq[1][h1][0], a1, 0, 0, 0);
-          a0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0b[h0], fq[0][h0][1], a0, 0, 0, 0);
-          a1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0b[h1], fq[1][h1][1], a1, 0, 0, 0);
-          a0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0b[h0], fq[0][h0][2], a0, 0, 0, 0);
-          a1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(k0b[h1], fq[1][h1][2], a1, 0, 0, 0);
-          a0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h0][1], fq[0][h0][0], a0, 0, 0, 0);
-          a1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h1][1], fq[1][h1][0], a1, 0, 0, 0);
+          l0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h0][0], fq[0][h0][1], l0, 0, 0, 0);
+          l1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h1][0], fq[1][h1][1], l1, 0, 0, 0);
+          l0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h0][0], fq[0][h0][2], l0, 0, 0, 0);
+          l1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h1][0], fq[1][h1][2], l1, 0, 0, 0);
+          l0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h0][1], fq[0][h0][0], l0, 0, 0, 0);
+          l1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(K[h1][1], fq[1][h1][0], l1, 0, 0, 0);
         }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { a0[r] = fmaf(l0[r], 1.f / 2048.f, a0[r]); a1[r] = fmaf(l1[r], 1.f / 2048.f, a1[r]); }
       };
       auto s_loop = [&](auto first_c) {
         f16x8 KA[2][2], KB[2][2];
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256, 2) void qkv_attn4_kernel(ConvParams p) {
       }
       sum += __shfl_xor(sum, 16);
       sum += __shfl_xor(sum, 32);
-      rinv[qb] = 1.0f / sum;
+      rinv[qb] = (1.f / 2048.f) / sum;                  // (O^T below is accumulated at 2^11 times its value)
     }
     TTR_Q4_STAMP(6);                                    // softmax + probability planes done
     __syncthreads();                                    // every wave has read K
@@ -426,17 +426,19 @@ __global__ __launch_bounds__(256, 2) void qkv_attn4_kernel(ConvParams p) {
                    "+v"(lo[1][0]), "+v"(lo[1][1]), "+v"(lo[1][2]), "+v"(lo[1][3]), "+v"(hi[1][0]), "+v"(hi[1][1]), "+v"(hi[1][2]), "+v"(hi[1][3]), \
                    "+v"(oacc[0][0]), "+v"(oacc[0][1]), "+v"(oacc[0][2]), "+v"(oacc[0][3]), "+v"(oacc[1][0]), "+v"(oacc[1][1]), "+v"(oacc[1][2]), "+v"(oacc[1][3]));
 #define TTR_Q4_MFMAS(s, lo, hi)                                                                                \
+      const f16x8 pu##s[2] = {fp[0][0][s] * upv, fp[1][0][s] * upv};   /* 2^11 p0: exact (p0 <= 1) */          \
       _Pragma("unroll") for (int dt = 0; dt < 4; ++dt) {                                                       \
         const f16x8 v0 = __builtin_shufflevector(lo[0][dt], hi[0][dt], 0, 1, 2, 3, 4, 5, 6, 7);                \
         const f16x8 v1 = __builtin_shufflevector(lo[1][dt], hi[1][dt], 0, 1, 2, 3, 4, 5, 6, 7);                \
-        const f16x8 v0b = v0 * dnv;                                                                            \
         _Pragma("unroll") for (int qb = 0; qb < 2; ++qb) {                                                     \
           f32x4 a = oacc[qb][dt];                                                                              \
-          a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, fp[qb][0][s], a, 0, 0, 0);                            \
-          a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0b, fp[qb][1][s], a, 0, 0, 0);                           \
+          a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, pu##s[qb], a, 0, 0, 0);                               \
+          a = __builtin_amdgcn_mfma_f32_16x16x32_f16(v0, fp[qb][1][s], a, 0, 0, 0);                            \
           oacc[qb][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(v1, fp[qb][0][s], a, 0, 0, 0);                 \
         }                                                                                                      \
       }
+      const f16 up = (f16)2048.f;
+      const f16x8 upv = {up, up, up, up, up, up, up, up};
       f16x4 loA[2][4], hiA[2][4], loB[2][4], hiB[2][4];
       TTR_Q4_READ(0, loA, hiA, fp[0][0][0])
       TTR_Q4_WAIT(loA, hiA)
